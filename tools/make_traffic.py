@@ -24,7 +24,7 @@ for f in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=T
             # (template instances stay apart: "void pcd::k_ba_points<4, true>" ...)
             agg[name.split("(")[0].replace("void ", "")][r["Counter_Name"]].append(float(r["Counter_Value"]))
 out = {"_source": "tools/prof_bench.sh: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum / --pmc SQ_* "
-                  "passes of `python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras`",
+                  "passes of `python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras`",
        "_correction": "MI355X_MICROARCH.md section HBM: FETCH_SIZE x2 (gfx950 tallies 128-B requests at 64 B), "
                       "WRITE_SIZE exact; both in KiB", "workload": [cloud, queries], "kernels": {}}
 import bench  # noqa: E402  (source_hash only; does not touch the GPU)

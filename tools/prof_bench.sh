@@ -7,7 +7,7 @@ tag=$1
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/profbench_$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-extras"
+ARGS="--steps 10 --warmup 2 --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 $R/bench.py $ARGS > $out/bench_trace.json 2> $out/trace.err || exit 1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 $R/bench.py $ARGS > $out/bench_pmc1.json 2> $out/pmc1.err || exit 1
 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $out/pmc_write -- python3 $R/bench.py $ARGS > $out/bench_pmc2.json 2> $out/pmc2.err || exit 1
