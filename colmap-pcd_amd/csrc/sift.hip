@@ -21,6 +21,7 @@
 // scan), applies acos / max_distance / max_ratio; the cross check and the ordered compaction follow.
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -176,10 +177,69 @@ __device__ __forceinline__ void sift_read_frag(SiftFrag& f, uint32_t a0, uint32_
                : "memory");
 }
 
+// ---- guided matching (feature/sift.cc:1092-1162 MatchGuidedSiftFeaturesCPU): the filter inside the walk ------------
+// Per keypoint and pair one record of kSiftRecComps floats, built by k_sift_guide_prep in tile-major SoA layout
+// (record of row r of a side: rec[(r >> 7) * kSiftRecTile + comp * 128 + (r & 127)]), so a column tile's records are
+// one contiguous kSiftRecTile block that LDS-DMA stages next to the descriptors.
+//   set 1: {a0, a1, a2, a0*a0 + a1*a1, h0/h2, h1/h2}   a_i = (F[i][0] x1 + F[i][1] y1) + F[i][2], h_i likewise with H
+//   set 2: {x2, y2, b0*b0, b1*b1, x2, y2}               b_j = (F[0][j] x2 + F[1][j] y2) + F[2][j]
+// The per-pair remainder, in the order of the reference's float Eigen code (every operation one IEEE float op; the
+// library is built with -ffp-contract=off):
+//   H: d0 = h0/h2 - x2, d1 = h1/h2 - y2, rejected iff d0*d0 + d1*d1 > h_max_residual
+//   F: e = (x2*a0 + y2*a1) + a2, rejected iff (e*e) / (((a0*a0 + a1*a1) + b0*b0) + b1*b1) > f_max_residual
+// A rejected pair's score is 0 (sift.cc:193-196), and a 0 never becomes a best or second best of the strict-> scan:
+// rejecting = leaving the column out of the row's top-2.  The walk folds that into the register test:
+// ballot(score > thr && passes).  (A NaN residual passes, as NaN > t is false in the reference.)
+enum { kSiftGuideH = 1, kSiftGuideF = 2 };
+constexpr int kSiftRecComps = 6;
+constexpr int kSiftRecTile = kSiftRecComps * kSiftTile;   // floats per 128-row tile of records
+
+struct SiftGuidePairDev {
+  const float* loc1;   // [n1][2] locations of set 1 / set 2 (device)
+  const float* loc2;
+  uint32_t n1, n2;
+  uint64_t rec1, rec2; // float offsets of the two sides' records
+  int32_t mode;        // kSiftGuideH | kSiftGuideF (0: no filter)
+  float H[9], F[9];    // row-major
+};
+
+// what a walk needs: its row side's and column side's records (first row of each image), which of them is set 1
+struct SiftGuideWalk {
+  const float* rrec;
+  const float* crec;
+  int mode;
+  bool rows_set1;
+  float th, tf;
+};
+
+// LDS of the guided walk's staged column records (double-buffered, one kSiftRecTile block per tile)
+__device__ __forceinline__ float* sift_guide_lds() {
+  __shared__ __attribute__((aligned(16))) float sG[2][kSiftRecTile];
+  return &sG[0][0];
+}
+
+// comps 0 .. N - 1 (counted from the one at byte offset OFF) of the lane's 4 consecutive columns
+template <int OFF, int N>
+__device__ __forceinline__ void sift_read_rec(float4 (&r)[N], uint32_t a) {
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  v4f t[N];
+#pragma unroll
+  for (int c = 0; c < N; ++c)
+    asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(t[c]) : "v"(a), "n"(OFF + c * kSiftTile * 4) : "memory");
+  // the reads have landed (tied to the registers, as in sift_read_frag)
+  if constexpr (N == 2) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0]), "+v"(t[1]) :: "memory");
+  else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]) :: "memory");
+#pragma unroll
+  for (int c = 0; c < N; ++c) r[c] = make_float4(t[c][0], t[c][1], t[c][2], t[c][3]);
+}
+
 // xr / ccr: the row image in the prepared copy (its first row) and its constants; xc / ccc: the column image
+// GUIDED: the walk of the guided kernels (gw: its records and thresholds); the unguided instantiation ignores gw
+template <bool GUIDED>
 __device__ __forceinline__ void sift_rows(const uint8_t* __restrict__ xr, const int* __restrict__ ccr, int n1,
                                           const uint8_t* __restrict__ xc, const int* __restrict__ ccc, int nbx,
-                                          int4* __restrict__ part, int ct_per_chunk, const int chunk, const int by) {
+                                          int4* __restrict__ part, int ct_per_chunk, const int chunk, const int by,
+                                          const SiftGuideWalk& gw) {
   __shared__ __attribute__((aligned(16))) uint8_t sB[2][kSiftTile * 128];
   __shared__ __attribute__((aligned(16))) int sCc[2][kSiftTile];
   const int row0 = by * kSiftStripe;
@@ -210,6 +270,12 @@ __device__ __forceinline__ void sift_rows(const uint8_t* __restrict__ xr, const 
 #pragma unroll
     for (int j = 0; j < kDma; ++j) sift_dma16<0>(g + goff[j], l + 1024 * j);
     if (wave < 2) sift_dma4(ccc + (size_t)bx * kSiftTile + wave * 64 + lane, &sCc[buf][wave * 64]);
+    if constexpr (GUIDED) {   // the column records: 3 x 1 KB, wavefronts 2 .. 4
+      if (wave >= 2 && wave < 2 + kSiftRecTile * 4 / 1024) {
+        const uint8_t* gr = reinterpret_cast<const uint8_t*>(gw.crec + (size_t)bx * kSiftRecTile) + (wave - 2) * 1024 + lane * 16;
+        sift_dma16<0>(gr, reinterpret_cast<uint8_t*>(sift_guide_lds() + buf * kSiftRecTile) + (wave - 2) * 1024);
+      }
+    }
   };
   issue(bx0, 0);
 
@@ -225,6 +291,17 @@ __device__ __forceinline__ void sift_rows(const uint8_t* __restrict__ xr, const 
       fa[nt][kk] = v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
     }
     rowc[nt] = ccr[r] + kSiftConst;
+  }
+  // guided: the rows' records (rows past n1: zeros; their results are never written)
+  float rrec[2][kSiftRecComps];
+  if constexpr (GUIDED) {
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int r = row0 + wave * kSiftWaveRows + nt * 32 + lr;
+#pragma unroll
+      for (int c = 0; c < kSiftRecComps; ++c)
+        rrec[nt][c] = r < n1 ? gw.rrec[(size_t)(r >> 7) * kSiftRecTile + c * kSiftTile + (r & 127)] : 0.f;
+    }
   }
   // running state per row tile, relative to the row constant: true score 0 = -rowc, code -1 = "no column" (sift.cc:66-68)
   int m1[2], m2[2], arg[2];
@@ -254,9 +331,81 @@ __device__ __forceinline__ void sift_rows(const uint8_t* __restrict__ xr, const 
                  : [v] "v"(v), [code] "s"(code_s)
                  : "vcc");
   };
-  auto scan_block = [&](const v16i (&acc)[2], const int seq) {
+  // guided: per group of 4 registers (4 consecutive columns of the lane half), which lanes' pairs pass the filter
+  const uint32_t sG_base = GUIDED ? sift_lds_addr(sift_guide_lds()) + (uint32_t)lh * 16u : 0u;
+  auto guide_pass = [&](bool (&pass)[2][4], const uint32_t g_a, auto off_tag) {
+    constexpr int OFF = decltype(off_tag)::value;   // byte offset of the group's columns in the records' comp 0
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) pass[j][i] = true;
+    if (gw.mode & kSiftGuideH) {
+      float4 c[2];
+      sift_read_rec<OFF + 4 * kSiftTile * 4, 2>(c, g_a);
+      const float cx[4] = {c[0].x, c[0].y, c[0].z, c[0].w}, cy[4] = {c[1].x, c[1].y, c[1].z, c[1].w};
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float d0 = rrec[j][4] - cx[i], d1 = rrec[j][5] - cy[i];   // (the sign of the difference: squared)
+          pass[j][i] = !(d0 * d0 + d1 * d1 > gw.th);
+        }
+    }
+    if (gw.mode & kSiftGuideF) {
+      float4 c[4];
+      sift_read_rec<OFF, 4>(c, g_a);
+      const float c0[4] = {c[0].x, c[0].y, c[0].z, c[0].w}, c1[4] = {c[1].x, c[1].y, c[1].z, c[1].w};
+      const float c2[4] = {c[2].x, c[2].y, c[2].z, c[2].w}, c3[4] = {c[3].x, c[3].y, c[3].z, c[3].w};
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          // set 1 = {a0, a1, a2, a0^2 + a1^2}, set 2 = {x2, y2, b0^2, b1^2}, whichever of them is the row
+          const float* r = rrec[j];
+          float e, den;
+          if (gw.rows_set1) {
+            e = (c0[i] * r[0] + c1[i] * r[1]) + r[2];
+            den = (r[3] + c2[i]) + c3[i];
+          } else {
+            e = (r[0] * c0[i] + r[1] * c1[i]) + c2[i];
+            den = (c3[i] + r[2]) + r[3];
+          }
+          pass[j][i] = pass[j][i] && !((e * e) / den > gw.tf);
+        }
+    }
+  };
+  auto scan_block = [&](const v16i (&acc)[2], const int seq, auto blk_tag) {
     if (PCD_SIFT_ABLATE & 1) { asm volatile("" ::"v"(acc[0]), "v"(acc[1])); return; }
     const int base = __builtin_amdgcn_readfirstlane(seq * 16);
+    if constexpr (GUIDED) {
+      // register 4 q + i = column 8 q + 4 lh + i of the block: the records of 4 consecutive columns per group, for both
+      // row tiles; every row tile's registers still go in ascending column order
+      constexpr int BLK = decltype(blk_tag)::value;
+      const uint32_t g_a = sG_base + (uint32_t)(seq >> 2 & 1) * (kSiftRecTile * 4);
+      auto group = [&](auto q_tag) {
+        constexpr int Q = decltype(q_tag)::value;
+        bool pass[2][4];
+        guide_pass(pass, g_a, std::integral_constant<int, (BLK * 32 + Q * 8) * 4>{});
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          unsigned long long mk[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) mk[i] = __builtin_amdgcn_ballot_w64(acc[j][4 * Q + i] > thr[j] && pass[j][i]);
+#pragma unroll
+          for (int k = 0; k < 4; k += 2) {
+            if (__builtin_expect((mk[k] | mk[k + 1]) != 0, 0)) {
+              if (mk[k]) slow(pass[j][k] ? acc[j][4 * Q + k] : INT_MIN, j, base + 4 * Q + k);
+              if (mk[k + 1]) slow(pass[j][k + 1] ? acc[j][4 * Q + k + 1] : INT_MIN, j, base + 4 * Q + k + 1);
+            }
+          }
+        }
+      };
+      group(std::integral_constant<int, 0>{});
+      group(std::integral_constant<int, 1>{});
+      group(std::integral_constant<int, 2>{});
+      group(std::integral_constant<int, 3>{});
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -335,16 +484,16 @@ __device__ __forceinline__ void sift_rows(const uint8_t* __restrict__ xr, const 
       const uint32_t cc_a = sCc_base + (uint32_t)buf * (kSiftTile * 4);
       read_frag(f, fb_a, cc_a, std::integral_constant<int, 0>{});
       mfma_block(acc0, f);
-      scan_block(acc0, 4 * t);
+      scan_block(acc0, 4 * t, std::integral_constant<int, 0>{});
       read_frag(f, fb_a, cc_a, std::integral_constant<int, 1>{});
       mfma_block(acc0, f);
-      scan_block(acc0, 4 * t + 1);
+      scan_block(acc0, 4 * t + 1, std::integral_constant<int, 1>{});
       read_frag(f, fb_a, cc_a, std::integral_constant<int, 2>{});
       mfma_block(acc0, f);
-      scan_block(acc0, 4 * t + 2);
+      scan_block(acc0, 4 * t + 2, std::integral_constant<int, 2>{});
       read_frag(f, fb_a, cc_a, std::integral_constant<int, 3>{});
       mfma_block(acc0, f);
-      scan_block(acc0, 4 * t + 3);
+      scan_block(acc0, 4 * t + 3, std::integral_constant<int, 3>{});
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wavefront's part of the next tile has landed
     if (!(PCD_SIFT_ABLATE & 8)) __syncthreads();
@@ -377,8 +526,8 @@ __global__ __launch_bounds__(64 * kSiftWaves, PCD_SIFT_WGS) void k_sift_scores_s
   const uint32_t pr = fwd ? prow1 : prow2, pc = fwd ? prow2 : prow1;
   const int nr = fwd ? n1 : n2, nc = fwd ? n2 : n1;
   if ((int)blockIdx.y * kSiftStripe >= nr) return;
-  sift_rows(xa + (size_t)pr * 128, cc + pr, nr, xa + (size_t)pc * 128, cc + pc, (nc + kSiftTile - 1) / kSiftTile,
-            fwd ? part12 : part21, fwd ? ct12 : ct21, blockIdx.x, blockIdx.y);
+  sift_rows<false>(xa + (size_t)pr * 128, cc + pr, nr, xa + (size_t)pc * 128, cc + pc, (nc + kSiftTile - 1) / kSiftTile,
+                   fwd ? part12 : part21, fwd ? ct12 : ct21, blockIdx.x, blockIdx.y, SiftGuideWalk{});
 }
 
 // ---- many image pairs in one launch set (pcd_sift_match_batch_device) ----------------------------------
@@ -402,8 +551,83 @@ __global__ __launch_bounds__(64 * kSiftWaves, PCD_SIFT_WGS) void k_sift_scores_b
   const int nr = (int)(fwd ? pr.n1 : pr.n2), nc = (int)(fwd ? pr.n2 : pr.n1);
   if ((int)blockIdx.y * kSiftStripe >= nr) return;
   const int nb = (nc + kSiftTile - 1) / kSiftTile;   // chunks past the last column tile leave inside sift_rows
-  sift_rows(xa + (size_t)rr * 128, cc + rr, nr, xa + (size_t)rc * 128, cc + rc, nb,
-            fwd ? part12 + pr.part12 : part21 + pr.part21, (nb + nchunk - 1) / nchunk, blockIdx.x, blockIdx.y);
+  sift_rows<false>(xa + (size_t)rr * 128, cc + rr, nr, xa + (size_t)rc * 128, cc + rc, nb,
+                   fwd ? part12 + pr.part12 : part21 + pr.part21, (nb + nchunk - 1) / nchunk, blockIdx.x, blockIdx.y,
+                   SiftGuideWalk{});
+}
+
+// ---- guided kernels (after the unguided ones: their code and labels stay as they were) ----
+// one workgroup of 128 threads per (128-row tile, side, pair): records of every row of the tile (zeros past n)
+__global__ __launch_bounds__(128) void k_sift_guide_prep(const SiftGuidePairDev* __restrict__ guides,
+                                                         float* __restrict__ rec) {
+  const SiftGuidePairDev& g = guides[blockIdx.z];
+  const bool side2 = blockIdx.y == 1;
+  const uint32_t n = side2 ? g.n2 : g.n1, tile = blockIdx.x, r = tile * kSiftTile + threadIdx.x;
+  if (tile * kSiftTile >= n) return;
+  float v[kSiftRecComps] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (r < n) {
+    const float* loc = side2 ? g.loc2 : g.loc1;
+    const float x = loc[2 * (size_t)r], y = loc[2 * (size_t)r + 1];
+    if (!side2) {
+      if (g.mode & kSiftGuideF) {
+        const float a0 = (g.F[0] * x + g.F[1] * y) + g.F[2];
+        const float a1 = (g.F[3] * x + g.F[4] * y) + g.F[5];
+        const float a2 = (g.F[6] * x + g.F[7] * y) + g.F[8];
+        v[0] = a0; v[1] = a1; v[2] = a2; v[3] = a0 * a0 + a1 * a1;
+      }
+      if (g.mode & kSiftGuideH) {
+        const float h0 = (g.H[0] * x + g.H[1] * y) + g.H[2];
+        const float h1 = (g.H[3] * x + g.H[4] * y) + g.H[5];
+        const float h2 = (g.H[6] * x + g.H[7] * y) + g.H[8];
+        v[4] = h0 / h2; v[5] = h1 / h2;
+      }
+    } else {
+      if (g.mode & kSiftGuideF) {
+        const float b0 = (g.F[0] * x + g.F[3] * y) + g.F[6];
+        const float b1 = (g.F[1] * x + g.F[4] * y) + g.F[7];
+        v[0] = x; v[1] = y; v[2] = b0 * b0; v[3] = b1 * b1;
+      }
+      v[4] = x; v[5] = y;
+    }
+  }
+  float* out = rec + (side2 ? g.rec2 : g.rec1) + (size_t)tile * kSiftRecTile + threadIdx.x;
+#pragma unroll
+  for (int c = 0; c < kSiftRecComps; ++c) out[c * kSiftTile] = v[c];
+}
+
+// guided form of k_sift_scores_stripe: guide = the pair's entry (mode, record offsets), rec = the records
+__global__ __launch_bounds__(64 * kSiftWaves, PCD_SIFT_WGS) void k_sift_guided_stripe(
+    const uint8_t* __restrict__ xa, const int* __restrict__ cc, uint32_t prow1, int n1, uint32_t prow2, int n2,
+    int4* __restrict__ part12, int4* __restrict__ part21, int ct12, int ct21, const SiftGuidePairDev* __restrict__ guide,
+    const float* __restrict__ rec, float th, float tf) {
+  const bool fwd = blockIdx.z == 0;
+  const uint32_t pr = fwd ? prow1 : prow2, pc = fwd ? prow2 : prow1;
+  const int nr = fwd ? n1 : n2, nc = fwd ? n2 : n1;
+  if ((int)blockIdx.y * kSiftStripe >= nr) return;
+  const float* r1 = rec + guide->rec1;
+  const float* r2 = rec + guide->rec2;
+  const SiftGuideWalk gw{fwd ? r1 : r2, fwd ? r2 : r1, guide->mode, fwd, th, tf};
+  sift_rows<true>(xa + (size_t)pr * 128, cc + pr, nr, xa + (size_t)pc * 128, cc + pc, (nc + kSiftTile - 1) / kSiftTile,
+                  fwd ? part12 : part21, fwd ? ct12 : ct21, blockIdx.x, blockIdx.y, gw);
+}
+
+// guided form of k_sift_scores_batch: guides [pair] beside pairs [pair] (mode none: the unguided walk's result)
+__global__ __launch_bounds__(64 * kSiftWaves, PCD_SIFT_WGS) void k_sift_guided_batch(
+    const uint8_t* __restrict__ xa, const int* __restrict__ cc, const SiftPairDev* __restrict__ pairs,
+    int4* __restrict__ part12, int4* __restrict__ part21, int nchunk, const SiftGuidePairDev* __restrict__ guides,
+    const float* __restrict__ rec, float th, float tf) {
+  const SiftPairDev pr = pairs[blockIdx.z >> 1];
+  const bool fwd = (blockIdx.z & 1) == 0;
+  const uint32_t rr = fwd ? pr.prow1 : pr.prow2, rc = fwd ? pr.prow2 : pr.prow1;
+  const int nr = (int)(fwd ? pr.n1 : pr.n2), nc = (int)(fwd ? pr.n2 : pr.n1);
+  if ((int)blockIdx.y * kSiftStripe >= nr) return;
+  const int nb = (nc + kSiftTile - 1) / kSiftTile;
+  const SiftGuidePairDev& g = guides[blockIdx.z >> 1];
+  const float* r1 = rec + g.rec1;
+  const float* r2 = rec + g.rec2;
+  const SiftGuideWalk gw{fwd ? r1 : r2, fwd ? r2 : r1, g.mode, fwd, th, tf};
+  sift_rows<true>(xa + (size_t)rr * 128, cc + rr, nr, xa + (size_t)rc * 128, cc + rc, nb,
+                  fwd ? part12 + pr.part12 : part21 + pr.part21, (nb + nchunk - 1) / nchunk, blockIdx.x, blockIdx.y, gw);
 }
 
 // sift.cc:72-104: merge the per-tile triples in ascending tile order, then the distance / ratio tests.
@@ -581,6 +805,10 @@ struct SiftScratch {
   DevBuf<int> counts;
   DevBuf<uint64_t> dense_off;
   DevBuf<uint32_t> dense;
+  // guided entries: the pair's records, the guide table (uploaded like the pair table, from h_guides), host locations
+  DevBuf<float> grec, loc1, loc2, locs;
+  DevBuf<SiftGuidePairDev> guides;
+  PinnedBuf<SiftGuidePairDev> h_guides;
   // The scratch is per DEVICE and shared by every call on it.  Host side: g_sift_mu (recursive) is held for the whole
   // of a host entry point and while a *_device entry point enqueues.  Device side: calls on different streams are
   // ordered through ev_done (the next call's stream waits for the previous call's last kernel before any of its own
@@ -616,9 +844,29 @@ static pcd_status sift_end_use(SiftScratch& sc, hipStream_t s) {
   return PCD_OK;
 }
 
+// one guided pair's table entry on the device (sc.guides[0]) for sift_device: its records at the start of sc.grec
+static pcd_status sift_upload_guide(SiftScratch& sc, hipStream_t s, const float* d_loc1, int n1, const float* d_loc2,
+                                    int n2, const float* H, const float* F) {
+  SiftGuidePairDev g{};
+  g.loc1 = d_loc1; g.loc2 = d_loc2; g.n1 = (uint32_t)n1; g.n2 = (uint32_t)n2;
+  g.rec1 = 0; g.rec2 = (uint64_t)((n1 + kSiftTile - 1) / kSiftTile) * kSiftRecTile;
+  g.mode = (H ? kSiftGuideH : 0) | (F ? kSiftGuideF : 0);
+  if (H) std::memcpy(g.H, H, sizeof(g.H));
+  if (F) std::memcpy(g.F, F, sizeof(g.F));
+  if (sc.tab_pending) PCD_HIP_TRY(hipEventSynchronize(sc.ev_tab));
+  PCD_TRY(sc.h_guides.reserve(1)); PCD_TRY(sc.guides.reserve(1));
+  sc.h_guides.p[0] = g;
+  PCD_HIP_TRY(hipMemcpyAsync(sc.guides.p, sc.h_guides.p, sizeof(SiftGuidePairDev), hipMemcpyHostToDevice, s));
+  PCD_HIP_TRY(hipEventRecord(sc.ev_tab, s));
+  sc.tab_pending = true;
+  return PCD_OK;
+}
+
+// d_guide (guided entries): the pair's table entry on the device, laid out by sift_upload_guide; th / tf its thresholds
 static pcd_status sift_device(int device, const uint8_t* d_d1, int n1, const uint8_t* d_d2, int n2, float max_ratio,
                               float max_distance, int cross_check, int* d_m12, int* d_m21, uint32_t* d_matches,
-                              int* d_count, SiftScratch& sc, hipStream_t s) {
+                              int* d_count, SiftScratch& sc, hipStream_t s,
+                              const SiftGuidePairDev* d_guide = nullptr, float th = 0.f, float tf = 0.f) {
   const int nb1 = (n1 + kSiftTile - 1) / kSiftTile, nb2 = (n2 + kSiftTile - 1) / kSiftTile;
   // stripe walks in both directions: enough (row tile, chunk) workgroups to fill the chip twice over
   // pcd_sift_set_tuning (tests / fuzzing) can force the number of column chunks, e.g. 1 = every stripe walks all tiles
@@ -642,7 +890,18 @@ static pcd_status sift_device(int device, const uint8_t* d_d1, int n1, const uin
     hipLaunchKernelGGL(k_sift_prep_pair, dim3(std::max(nb1, nb2), 2), dim3(256), 0, s, SiftImageDev{d_d1, (uint32_t)n1, prow1},
                        SiftImageDev{d_d2, (uint32_t)n2, prow2}, sc.xa.p, sc.cc.p);
   }
-  {
+  if (d_guide) {
+    PCD_TRY(sc.grec.reserve((size_t)(nb1 + nb2) * kSiftRecTile));
+    {
+      ScopedKernelTimer t("sift_guide_prep", s);
+      hipLaunchKernelGGL(k_sift_guide_prep, dim3(std::max(nb1, nb2), 2, 1), dim3(kSiftTile), 0, s, d_guide, sc.grec.p);
+    }
+    ScopedKernelTimer t("sift_guided_scores", s);
+    const int ns1 = (n1 + kSiftStripe - 1) / kSiftStripe, ns2 = (n2 + kSiftStripe - 1) / kSiftStripe;
+    hipLaunchKernelGGL(k_sift_guided_stripe, dim3(std::max(used12, used21), std::max(ns1, ns2), 2), dim3(64 * kSiftWaves), 0,
+                       s, sc.xa.p, sc.cc.p, prow1, n1, prow2, n2, sc.part12.p, sc.part21.p, ct12, ct21, d_guide, sc.grec.p,
+                       th, tf);
+  } else {
     ScopedKernelTimer t("sift_scores", s);
     const int ns1 = (n1 + kSiftStripe - 1) / kSiftStripe, ns2 = (n2 + kSiftStripe - 1) / kSiftStripe;
     hipLaunchKernelGGL(k_sift_scores_stripe, dim3(std::max(used12, used21), std::max(ns1, ns2), 2), dim3(64 * kSiftWaves), 0, s, sc.xa.p,
@@ -678,10 +937,12 @@ static pcd_status sift_device(int device, const uint8_t* d_d1, int n1, const uin
 // the arena's row sums one launch in front.  Nothing synchronises with the host.
 constexpr size_t kSiftBatchPartials = (size_t)1 << 27;   // PCD_SIFT_BATCH_PARTIALS overrides it (tests: forces the cuts)
 
+// guided (guides != nullptr): d_locs = [rows][2] locations parallel to the arena, guides[p] pair p's mode and matrices
 static pcd_status sift_batch_device(int device, const uint8_t* d_arena, const uint64_t* first_row, int n_images,
                                     const uint32_t* pair_ids, int n_pairs, float max_ratio, float max_distance,
                                     int cross_check, uint32_t* d_matches, const uint64_t* match_offset, int* d_counts,
-                                    SiftScratch& sc, hipStream_t s) {
+                                    SiftScratch& sc, hipStream_t s, const float* d_locs = nullptr,
+                                    const pcd_sift_guide* guides = nullptr, float th = 0.f, float tf = 0.f) {
   const uint64_t total_rows = first_row[n_images];
   PCD_REQUIRE(total_rows < (1ull << 32), "arena larger than 2^32 descriptors");
   const uint64_t budget_set = g_sift_batch_partials.load(std::memory_order_relaxed);   // pcd_sift_set_tuning
@@ -701,9 +962,14 @@ static pcd_status sift_batch_device(int device, const uint8_t* d_arena, const ui
       const int n1 = (int)(first_row[a + 1] - first_row[a]), n2 = (int)(first_row[b + 1] - first_row[b]);
       if (n1 == 0 || n2 == 0) { PCD_HIP_TRY(hipMemsetAsync(d_counts + p, 0, sizeof(int), s)); continue; }
       PCD_TRY(sc.m12.reserve(n1)); PCD_TRY(sc.m21.reserve(n2));
+      const bool guided = guides && (guides[p].mode & (kSiftGuideH | kSiftGuideF));
+      if (guided)
+        PCD_TRY(sift_upload_guide(sc, s, d_locs + 2 * first_row[a], n1, d_locs + 2 * first_row[b], n2,
+                                  (guides[p].mode & kSiftGuideH) ? guides[p].H : nullptr,
+                                  (guides[p].mode & kSiftGuideF) ? guides[p].F : nullptr));
       PCD_TRY(sift_device(device, d_arena + first_row[a] * 128, n1, d_arena + first_row[b] * 128, n2, max_ratio,
                           max_distance, cross_check, sc.m12.p, sc.m21.p, d_matches + 2 * match_offset[p], d_counts + p,
-                          sc, s));
+                          sc, s, guided ? sc.guides.p : nullptr, th, tf));
     }
     return PCD_OK;
   }
@@ -726,6 +992,8 @@ static pcd_status sift_batch_device(int device, const uint8_t* d_arena, const ui
   std::vector<int> cut_nchunk;
   cut.push_back(0);
   size_t max12 = 0, max21 = 0, maxm12 = 0, maxm21 = 0;
+  std::vector<SiftGuidePairDev> gtab(guides ? (size_t)n_pairs : 0);   // guided: records per sub-batch from 0
+  size_t maxrec = 0;
   {
     int p0 = 0;
     while (p0 < n_pairs) {
@@ -740,7 +1008,7 @@ static pcd_status sift_batch_device(int device, const uint8_t* d_arena, const ui
       const long want = nchunk_env > 0 ? std::min<long>(nchunk_env, std::max(nbx0, nby0))
                                        : std::min<long>(std::max(nbx0, nby0), (512 + stripes0 * left - 1) / (stripes0 * left));
       const int nchunk = (int)std::max<long>(1, want);
-      size_t o12 = 0, o21 = 0, om12 = 0, om21 = 0;
+      size_t o12 = 0, o21 = 0, om12 = 0, om21 = 0, orec = 0;
       int p = p0;
       for (; p < n_pairs; ++p) {
         const uint32_t a = pair_ids[2 * p], b = pair_ids[2 * p + 1];
@@ -751,9 +1019,20 @@ static pcd_status sift_batch_device(int device, const uint8_t* d_arena, const ui
         if (p > p0 && (o12 + need12 + o21 + need21 > budget || p - p0 >= 32767)) break;
         tab[p] = SiftPairDev{imgs[a].prow, (uint32_t)n1, imgs[b].prow, (uint32_t)n2, o12, o21, om12, om21, match_offset[p]};
         o12 += need12; o21 += need21; om12 += n1; om21 += n2;
+        if (guides) {
+          SiftGuidePairDev& g = gtab[p];
+          g = SiftGuidePairDev{};
+          g.loc1 = d_locs + 2 * first_row[a]; g.loc2 = d_locs + 2 * first_row[b];
+          g.n1 = (uint32_t)n1; g.n2 = (uint32_t)n2;
+          g.mode = guides[p].mode & (kSiftGuideH | kSiftGuideF);
+          std::memcpy(g.H, guides[p].H, sizeof(g.H)); std::memcpy(g.F, guides[p].F, sizeof(g.F));
+          g.rec1 = orec; orec += (n1 + kSiftTile - 1) / kSiftTile * kSiftRecTile;
+          g.rec2 = orec; orec += (n2 + kSiftTile - 1) / kSiftTile * kSiftRecTile;
+        }
       }
       max12 = std::max(max12, o12); max21 = std::max(max21, o21);
       maxm12 = std::max(maxm12, om12); maxm21 = std::max(maxm21, om21);
+      maxrec = std::max(maxrec, orec);
       cut.push_back(p);
       cut_nchunk.push_back(nchunk);
       p0 = p;
@@ -770,6 +1049,11 @@ static pcd_status sift_batch_device(int device, const uint8_t* d_arena, const ui
   std::memcpy(sc.h_images.p, imgs.data(), sizeof(SiftImageDev) * (size_t)n_images);
   PCD_HIP_TRY(hipMemcpyAsync(sc.pairs.p, sc.h_pairs.p, sizeof(SiftPairDev) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
   PCD_HIP_TRY(hipMemcpyAsync(sc.images.p, sc.h_images.p, sizeof(SiftImageDev) * (size_t)n_images, hipMemcpyHostToDevice, s));
+  if (guides) {
+    PCD_TRY(sc.h_guides.reserve(n_pairs)); PCD_TRY(sc.guides.reserve(n_pairs)); PCD_TRY(sc.grec.reserve(maxrec));
+    std::memcpy(sc.h_guides.p, gtab.data(), sizeof(SiftGuidePairDev) * (size_t)n_pairs);
+    PCD_HIP_TRY(hipMemcpyAsync(sc.guides.p, sc.h_guides.p, sizeof(SiftGuidePairDev) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+  }
   PCD_HIP_TRY(hipEventRecord(sc.ev_tab, s));
   sc.tab_pending = true;
   if (max_tiles) {
@@ -783,7 +1067,17 @@ static pcd_status sift_batch_device(int device, const uint8_t* d_arena, const ui
       mx1 = std::max(mx1, tab[p].n1); mx2 = std::max(mx2, tab[p].n2); mxsum = std::max(mxsum, tab[p].n1 + tab[p].n2);
     }
     if (mx1 && mx2) {
-      {
+      if (guides) {
+        {
+          ScopedKernelTimer t("sift_guide_prep", s);
+          hipLaunchKernelGGL(k_sift_guide_prep, dim3((std::max(mx1, mx2) + kSiftTile - 1) / kSiftTile, 2, np), dim3(kSiftTile),
+                             0, s, sc.guides.p + p0, sc.grec.p);
+        }
+        ScopedKernelTimer t("sift_guided_scores", s);
+        hipLaunchKernelGGL(k_sift_guided_batch, dim3(nchunk, (std::max(mx1, mx2) + kSiftStripe - 1) / kSiftStripe, 2 * np),
+                           dim3(64 * kSiftWaves), 0, s, sc.xa.p, sc.cc.p, sc.pairs.p + p0, sc.part12.p, sc.part21.p, nchunk,
+                           sc.guides.p + p0, sc.grec.p, th, tf);
+      } else {
         ScopedKernelTimer t("sift_scores", s);
         hipLaunchKernelGGL(k_sift_scores_batch, dim3(nchunk, (std::max(mx1, mx2) + kSiftStripe - 1) / kSiftStripe, 2 * np),
                            dim3(64 * kSiftWaves), 0, s, sc.xa.p, sc.cc.p, sc.pairs.p + p0, sc.part12.p, sc.part21.p, nchunk);
@@ -901,9 +1195,13 @@ pcd_status pcd_sift_match_batch_device(int device, const uint8_t* d_arena, const
   });
 }
 
-pcd_status pcd_sift_match_batch(int device, const uint8_t* arena, const uint64_t* first_row, int n_images,
-                                const uint32_t* pairs, int n_pairs, float max_ratio, float max_distance, int cross_check,
-                                uint32_t* matches, uint64_t matches_capacity, uint64_t* list_offset) {
+}  // extern "C"
+
+// host form of the batch entries (locs / guides: the guided one)
+static pcd_status sift_match_batch_host(int device, const uint8_t* arena, const float* locs, const uint64_t* first_row,
+                                        int n_images, const uint32_t* pairs, int n_pairs, const pcd_sift_guide* guides,
+                                        float th, float tf, float max_ratio, float max_distance, int cross_check,
+                                        uint32_t* matches, uint64_t matches_capacity, uint64_t* list_offset) {
   return pcd::guard([&]() -> pcd_status {
   PCD_REQUIRE(n_images >= 0 && n_pairs >= 0 && first_row && list_offset, "sizes / first_row / list_offset");
   list_offset[0] = 0;
@@ -928,8 +1226,17 @@ pcd_status pcd_sift_match_batch(int device, const uint8_t* arena, const uint64_t
   PCD_TRY(sc->counts.reserve(n_pairs)); PCD_TRY(sc->dense_off.reserve(2 * ((size_t)n_pairs + 1)));
   hipStream_t s = nullptr;
   if (rows) PCD_HIP_TRY(hipMemcpy(sc->arena.p, arena, rows * 128, hipMemcpyHostToDevice));
-  PCD_TRY(pcd_sift_match_batch_device(device, sc->arena.p, first_row, n_images, pairs, n_pairs, max_ratio, max_distance,
-                                      cross_check, sc->matches.p, off.data(), sc->counts.p, s));
+  if (guides) {
+    PCD_REQUIRE(rows == 0 || locs, "null locations");
+    PCD_TRY(sc->locs.reserve(2 * rows));
+    if (rows) PCD_HIP_TRY(hipMemcpy(sc->locs.p, locs, rows * 2 * sizeof(float), hipMemcpyHostToDevice));
+    PCD_TRY(pcd_sift_match_guided_batch_device(device, sc->arena.p, sc->locs.p, first_row, n_images, pairs, n_pairs,
+                                               guides, th, tf, max_ratio, max_distance, cross_check, sc->matches.p,
+                                               off.data(), sc->counts.p, s));
+  } else {
+    PCD_TRY(pcd_sift_match_batch_device(device, sc->arena.p, first_row, n_images, pairs, n_pairs, max_ratio, max_distance,
+                                        cross_check, sc->matches.p, off.data(), sc->counts.p, s));
+  }
   std::vector<int> cnt((size_t)n_pairs);
   PCD_HIP_TRY(hipMemcpy(cnt.data(), sc->counts.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost));
   for (int p = 0; p < n_pairs; ++p) list_offset[p + 1] = list_offset[p] + (uint64_t)cnt[p];
@@ -952,6 +1259,128 @@ pcd_status pcd_sift_match_batch(int device, const uint8_t* arena, const uint64_t
   return PCD_OK;
   });
 }
+
+extern "C" {
+
+pcd_status pcd_sift_match_batch(int device, const uint8_t* arena, const uint64_t* first_row, int n_images,
+                                const uint32_t* pairs, int n_pairs, float max_ratio, float max_distance, int cross_check,
+                                uint32_t* matches, uint64_t matches_capacity, uint64_t* list_offset) {
+  return sift_match_batch_host(device, arena, nullptr, first_row, n_images, pairs, n_pairs, nullptr, 0.f, 0.f, max_ratio,
+                               max_distance, cross_check, matches, matches_capacity, list_offset);
+}
+
+// ---- guided matching (feature/sift.cc:1092-1162, lib/SiftGPU/SiftGPU.h:331-352) ----
+pcd_status pcd_sift_match_guided_device(int device, const uint8_t* d_desc1, const float* d_loc1, int n1,
+                                        const uint8_t* d_desc2, const float* d_loc2, int n2, const float* H,
+                                        const float* F, float h_max_residual, float f_max_residual, float max_ratio,
+                                        float max_distance, int cross_check, int32_t* d_m12, int32_t* d_m21,
+                                        uint32_t* d_matches, int32_t* d_num_matches, void* stream) {
+  if (!H && !F)   // no geometry: the unguided result
+    return pcd_sift_match_device(device, d_desc1, n1, d_desc2, n2, max_ratio, max_distance, cross_check, d_m12, d_m21,
+                                 d_matches, d_num_matches, stream);
+  return pcd::guard([&]() -> pcd_status {
+  PCD_REQUIRE(n1 >= 0 && n2 >= 0 && d_num_matches, "sizes / count pointer");
+  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
+  PCD_TRY(require_device(device));
+  PCD_REFUSE_CAPTURE(stream);
+  hipStream_t s = (hipStream_t)stream;
+  if (n1 == 0 || n2 == 0) {   // sift_test.cc:462-474: an empty set, no matches
+    PCD_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
+    if (n1 && d_m12) PCD_HIP_TRY(hipMemsetAsync(d_m12, 0xFF, sizeof(int32_t) * n1, s));
+    if (n2 && d_m21) PCD_HIP_TRY(hipMemsetAsync(d_m21, 0xFF, sizeof(int32_t) * n2, s));
+    return PCD_OK;
+  }
+  PCD_REQUIRE(d_desc1 && d_desc2 && d_loc1 && d_loc2 && d_m12 && d_m21 && d_matches, "null pointer");
+  SiftLock g(g_sift_mu);
+  PCD_HIP_TRY(hipSetDevice(device));
+  if (!g_sift[device]) g_sift[device] = new SiftScratch();
+  SiftScratch& sc = *g_sift[device];
+  PCD_TRY(sift_begin_use(sc, s));
+  PCD_TRY(sift_upload_guide(sc, s, d_loc1, n1, d_loc2, n2, H, F));
+  const pcd_status st = sift_device(device, d_desc1, n1, d_desc2, n2, max_ratio, max_distance, cross_check, d_m12, d_m21,
+                                    d_matches, d_num_matches, sc, s, sc.guides.p, h_max_residual, f_max_residual);
+  PCD_TRY(sift_end_use(sc, s));
+  return st;
+  });
+}
+
+pcd_status pcd_sift_match_guided(int device, const uint8_t* desc1, const float* loc1, int n1, const uint8_t* desc2,
+                                 const float* loc2, int n2, const float* H, const float* F, float h_max_residual,
+                                 float f_max_residual, float max_ratio, float max_distance, int cross_check,
+                                 uint32_t* matches, int32_t* num_matches) {
+  if (!H && !F)
+    return pcd_sift_match(device, desc1, n1, desc2, n2, max_ratio, max_distance, cross_check, matches, num_matches);
+  return pcd::guard([&]() -> pcd_status {
+  PCD_REQUIRE(num_matches && n1 >= 0 && n2 >= 0, "sizes / count pointer");
+  *num_matches = 0;
+  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
+  PCD_TRY(require_device(device));
+  if (n1 == 0 || n2 == 0) return PCD_OK;
+  PCD_REQUIRE(desc1 && desc2 && loc1 && loc2 && matches, "null pointer");
+  SiftLock g(g_sift_mu);
+  PCD_HIP_TRY(hipSetDevice(device));
+  if (!g_sift[device]) g_sift[device] = new SiftScratch();
+  SiftScratch* sc = g_sift[device];
+  hipStream_t s = nullptr;
+  PCD_TRY(sift_begin_use(*sc, s));
+  PCD_TRY(sc->d1.reserve((size_t)n1 * 128)); PCD_TRY(sc->d2.reserve((size_t)n2 * 128));
+  PCD_TRY(sc->loc1.reserve(2 * (size_t)n1)); PCD_TRY(sc->loc2.reserve(2 * (size_t)n2));
+  PCD_TRY(sc->m12.reserve(n1)); PCD_TRY(sc->m21.reserve(n2)); PCD_TRY(sc->matches.reserve(2 * (size_t)n1));
+  PCD_TRY(sc->count.reserve(1));
+  PCD_HIP_TRY(hipMemcpyAsync(sc->d1.p, desc1, (size_t)n1 * 128, hipMemcpyHostToDevice, s));
+  PCD_HIP_TRY(hipMemcpyAsync(sc->d2.p, desc2, (size_t)n2 * 128, hipMemcpyHostToDevice, s));
+  PCD_HIP_TRY(hipMemcpyAsync(sc->loc1.p, loc1, 2 * sizeof(float) * (size_t)n1, hipMemcpyHostToDevice, s));
+  PCD_HIP_TRY(hipMemcpyAsync(sc->loc2.p, loc2, 2 * sizeof(float) * (size_t)n2, hipMemcpyHostToDevice, s));
+  PCD_TRY(pcd_sift_match_guided_device(device, sc->d1.p, sc->loc1.p, n1, sc->d2.p, sc->loc2.p, n2, H, F, h_max_residual,
+                                       f_max_residual, max_ratio, max_distance, cross_check, sc->m12.p, sc->m21.p,
+                                       sc->matches.p, sc->count.p, s));
+  int cnt = 0;
+  PCD_HIP_TRY(hipMemcpyAsync(&cnt, sc->count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  PCD_HIP_TRY(hipStreamSynchronize(s));
+  if (cnt) PCD_HIP_TRY(hipMemcpy(matches, sc->matches.p, 2 * (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  *num_matches = cnt;
+  return PCD_OK;
+  });
+}
+
+pcd_status pcd_sift_match_guided_batch_device(int device, const uint8_t* d_arena, const float* d_locs,
+                                              const uint64_t* first_row, int n_images, const uint32_t* pairs,
+                                              int n_pairs, const pcd_sift_guide* guides, float h_max_residual,
+                                              float f_max_residual, float max_ratio, float max_distance,
+                                              int cross_check, uint32_t* d_matches, const uint64_t* match_offset,
+                                              int32_t* d_counts, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+  PCD_REQUIRE(n_images >= 0 && n_pairs >= 0 && first_row, "sizes / first_row");
+  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
+  PCD_TRY(require_device(device));
+  PCD_REFUSE_CAPTURE(stream);
+  if (n_pairs == 0) return PCD_OK;
+  PCD_REQUIRE(pairs && match_offset && d_counts && d_matches && guides, "null pointer");
+  PCD_REQUIRE(first_row[n_images] == 0 || (d_arena && d_locs), "null arena / locations");
+  for (int p = 0; p < n_pairs; ++p)
+    PCD_REQUIRE(guides[p].mode >= PCD_SIFT_GUIDE_NONE && guides[p].mode <= PCD_SIFT_GUIDE_HF, "guide mode");
+  SiftLock g(g_sift_mu);
+  PCD_HIP_TRY(hipSetDevice(device));
+  if (!g_sift[device]) g_sift[device] = new SiftScratch();
+  PCD_TRY(sift_begin_use(*g_sift[device], (hipStream_t)stream));
+  const pcd_status st = sift_batch_device(device, d_arena, first_row, n_images, pairs, n_pairs, max_ratio, max_distance,
+                                          cross_check, d_matches, match_offset, d_counts, *g_sift[device],
+                                          (hipStream_t)stream, d_locs, guides, h_max_residual, f_max_residual);
+  PCD_TRY(sift_end_use(*g_sift[device], (hipStream_t)stream));
+  return st;
+  });
+}
+
+pcd_status pcd_sift_match_guided_batch(int device, const uint8_t* arena, const float* locs, const uint64_t* first_row,
+                                       int n_images, const uint32_t* pairs, int n_pairs, const pcd_sift_guide* guides,
+                                       float h_max_residual, float f_max_residual, float max_ratio, float max_distance,
+                                       int cross_check, uint32_t* matches, uint64_t matches_capacity,
+                                       uint64_t* list_offset) {
+  if (n_pairs > 0 && !guides) return (set_error("pcd_sift_match_guided_batch: null guides"), PCD_ERR_INVALID);
+  return sift_match_batch_host(device, arena, locs, first_row, n_images, pairs, n_pairs, guides, h_max_residual,
+                               f_max_residual, max_ratio, max_distance, cross_check, matches, matches_capacity,
+                               list_offset);
+}
 // ---- matcher handle: two descriptor slots resident on the device (SiftMatchGPU's usage pattern) ----
 }  // extern "C"
 
@@ -960,6 +1389,8 @@ struct pcd_sift_matcher {
   int max_sift = 4096;
   int n[2] = {0, 0};
   pcd::DevBuf<uint8_t> d[2];
+  pcd::DevBuf<float> loc[2];
+  bool loc_ok[2] = {false, false};   // the slot's locations belong to its current descriptors
   pcd::DevBuf<int32_t> m12, m21, count;
   pcd::DevBuf<uint32_t> matches;
 };
@@ -998,6 +1429,7 @@ pcd_status pcd_sift_matcher_set_descriptors(pcd_sift_matcher* m, int index, int 
   PCD_HIP_TRY(hipSetDevice(m->device));
   if (num > m->max_sift) num = m->max_sift;
   m->n[index] = num;
+  m->loc_ok[index] = false;
   if (num) {
     PCD_TRY(m->d[index].reserve((size_t)num * 128));
     PCD_HIP_TRY(hipMemcpy(m->d[index].p, desc, (size_t)num * 128, hipMemcpyHostToDevice));
@@ -1019,6 +1451,55 @@ pcd_status pcd_sift_matcher_match(pcd_sift_matcher* m, int max_match, uint32_t* 
   hipStream_t s = nullptr;
   PCD_TRY(pcd_sift_match_device(m->device, m->d[0].p, n1, m->d[1].p, n2, ratiomax, distmax, mutual_best_match,
                                 m->m12.p, m->m21.p, m->matches.p, m->count.p, s));
+  int cnt = 0;
+  PCD_HIP_TRY(hipMemcpyAsync(&cnt, m->count.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  PCD_HIP_TRY(hipStreamSynchronize(s));
+  if (cnt > max_match) cnt = max_match;
+  if (cnt) PCD_HIP_TRY(hipMemcpy(matches, m->matches.p, 2 * (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  *num_matches = cnt;
+  return PCD_OK;
+}
+
+// SiftMatchGPU::SetFeautreLocation(index, locations, gap): n[index] (x, y) pairs at a stride of 2 + gap floats
+pcd_status pcd_sift_matcher_set_locations(pcd_sift_matcher* m, int index, const float* loc, int gap) {
+  PCD_REQUIRE(m && (index == 0 || index == 1) && gap >= 0, "index must be 0 or 1, gap >= 0");
+  const int n = m->n[index];
+  PCD_REQUIRE(n == 0 || loc, "null locations");
+  PCD_HIP_TRY(hipSetDevice(m->device));
+  if (n) {
+    std::vector<float> xy(2 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+      xy[2 * (size_t)i] = loc[(size_t)i * (2 + gap)];
+      xy[2 * (size_t)i + 1] = loc[(size_t)i * (2 + gap) + 1];
+    }
+    PCD_TRY(m->loc[index].reserve(2 * (size_t)n));
+    PCD_HIP_TRY(hipMemcpy(m->loc[index].p, xy.data(), xy.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  m->loc_ok[index] = true;
+  return PCD_OK;
+}
+
+// SiftMatchGPU::GetGuidedSiftMatch (SiftGPU.h:343-352): hdistmax / fdistmax are the squared residual thresholds
+pcd_status pcd_sift_matcher_match_guided(pcd_sift_matcher* m, int max_match, uint32_t* matches, const float* H,
+                                         const float* F, float distmax, float ratiomax, float hdistmax, float fdistmax,
+                                         int mutual_best_match, int32_t* num_matches) {
+  PCD_REQUIRE(m && num_matches && max_match >= 0, "null pointer");
+  *num_matches = 0;
+  if (!H && !F) return pcd_sift_matcher_match(m, max_match, matches, distmax, ratiomax, mutual_best_match, num_matches);
+  const int n1 = m->n[0], n2 = m->n[1];
+  if (n1 == 0 || n2 == 0 || max_match == 0) return PCD_OK;
+  if (!m->loc_ok[0] || !m->loc_ok[1]) {
+    set_error("pcd_sift_matcher_match_guided: a slot's descriptors were set after its locations (or none were set)");
+    return PCD_ERR_INVALID;
+  }
+  PCD_REQUIRE(matches, "null match buffer");
+  PCD_HIP_TRY(hipSetDevice(m->device));
+  PCD_TRY(m->m12.reserve(n1)); PCD_TRY(m->m21.reserve(n2)); PCD_TRY(m->matches.reserve(2 * (size_t)n1));
+  PCD_TRY(m->count.reserve(1));
+  hipStream_t s = nullptr;
+  PCD_TRY(pcd_sift_match_guided_device(m->device, m->d[0].p, m->loc[0].p, n1, m->d[1].p, m->loc[1].p, n2, H, F, hdistmax,
+                                       fdistmax, ratiomax, distmax, mutual_best_match, m->m12.p, m->m21.p, m->matches.p,
+                                       m->count.p, s));
   int cnt = 0;
   PCD_HIP_TRY(hipMemcpyAsync(&cnt, m->count.p, sizeof(int), hipMemcpyDeviceToHost, s));
   PCD_HIP_TRY(hipStreamSynchronize(s));

@@ -110,6 +110,8 @@ ABI_SYMBOLS = [
     "pcd_proj_last_pairs", "pcd_proj_scale_coeffs", "pcd_proj_set_new_images",
     "pcd_sift_matcher_create", "pcd_sift_matcher_destroy", "pcd_sift_matcher_set_max_sift",
     "pcd_sift_matcher_set_descriptors", "pcd_sift_matcher_match",
+    "pcd_sift_match_guided", "pcd_sift_match_guided_device", "pcd_sift_match_guided_batch",
+    "pcd_sift_match_guided_batch_device", "pcd_sift_matcher_set_locations", "pcd_sift_matcher_match_guided",
     "pcd_ba_evaluate_blocks", "pcd_ba_filter_tracks", "pcd_ba_filter_tracks_device",
     "pcd_cloud_create_sharded", "pcd_cloud_shards_destroy", "pcd_cloud_shards_count", "pcd_cloud_shards_size",
     "pcd_cloud_shards_get", "pcd_nn_query_sharded", "pcd_associate_sharded",
@@ -456,6 +458,76 @@ def sift_match_batch(descriptors, pairs, max_ratio=0.8, max_distance=0.7, cross_
     _check(L.pcd_sift_match_batch(device, _vp(arena) if arena.shape[0] else None, _vp(first), len(descriptors),
                                   _vp(pairs) if P else None, P, max_ratio, max_distance, int(cross_check), _vp(m), cap,
                                   _vp(off)))
+    return [m[int(off[p]):int(off[p + 1])].copy() for p in range(P)]
+
+
+SIFT_GUIDE_NONE, SIFT_GUIDE_H, SIFT_GUIDE_F, SIFT_GUIDE_HF = 0, 1, 2, 3
+
+
+class SiftGuide(C.Structure):
+    """pcd_sift_guide: mode (SIFT_GUIDE_*) and the row-major 3x3 H / F of one pair"""
+    _fields_ = [("mode", C.c_int32), ("H", C.c_float * 9), ("F", C.c_float * 9)]
+
+
+def _mat3(m):
+    return None if m is None else np.ascontiguousarray(m, np.float32).reshape(9)
+
+
+def sift_match_guided(d1, loc1, d2, loc2, H=None, F=None, h_max_residual=16.0, f_max_residual=16.0, max_ratio=0.8,
+                      max_distance=0.7, cross_check=True, device=0):
+    """MatchGuidedSiftFeaturesCPU semantics (feature/sift.cc:1092-1162) on the GPU: loc1 / loc2 [n][2] float32, H / F
+    row-major 3x3 or None; returns matches [M][2] uint32 (with neither matrix: exactly sift_match)"""
+    d1 = np.ascontiguousarray(d1, np.uint8).reshape(-1, 128)
+    d2 = np.ascontiguousarray(d2, np.uint8).reshape(-1, 128)
+    n1, n2 = d1.shape[0], d2.shape[0]
+    l1 = np.ascontiguousarray(loc1, np.float32).reshape(n1, 2)
+    l2 = np.ascontiguousarray(loc2, np.float32).reshape(n2, 2)
+    h, f = _mat3(H), _mat3(F)
+    m = np.zeros((max(n1, 1), 2), np.uint32)
+    cnt = C.c_int32(0)
+    L = lib()
+    L.pcd_sift_match_guided.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                        C.c_void_p, C.POINTER(C.c_int32)]
+    _check(L.pcd_sift_match_guided(device, _vp(d1) if n1 else None, _vp(l1) if n1 else None, n1,
+                                   _vp(d2) if n2 else None, _vp(l2) if n2 else None, n2,
+                                   _vp(h) if h is not None else None, _vp(f) if f is not None else None,
+                                   h_max_residual, f_max_residual, max_ratio, max_distance, int(cross_check), _vp(m),
+                                   C.byref(cnt)))
+    return m[:cnt.value].copy()
+
+
+def sift_match_guided_batch(descriptors, locations, pairs, guides, h_max_residual=16.0, f_max_residual=16.0,
+                            max_ratio=0.8, max_distance=0.7, cross_check=True, device=0):
+    """GuidedSiftGPUFeatureMatcher's per-pair loop (feature/matching.cc:523-575) in one call: `locations` = one [n_i][2]
+    float32 array per image, `guides` = one (H or None, F or None) per pair.  Returns a list of P match arrays, each
+    equal to sift_match_guided(...) of that pair."""
+    arena, first = _sift_arena(descriptors)
+    locs = [np.ascontiguousarray(l, np.float32).reshape(-1, 2) for l in locations]
+    assert [l.shape[0] for l in locs] == [int(first[i + 1] - first[i]) for i in range(len(locs))]
+    loc_arena = np.ascontiguousarray(np.concatenate(locs, axis=0) if locs and first[-1] else np.zeros((0, 2), np.float32))
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    P = pairs.shape[0]
+    g = (SiftGuide * max(P, 1))()
+    for p, (H, F) in enumerate(guides):
+        g[p].mode = (SIFT_GUIDE_H if H is not None else 0) | (SIFT_GUIDE_F if F is not None else 0)
+        if H is not None:
+            g[p].H[:] = [float(v) for v in _mat3(H)]
+        if F is not None:
+            g[p].F[:] = [float(v) for v in _mat3(F)]
+    off = np.zeros(P + 1, np.uint64)
+    n1 = (first[1:] - first[:-1])[pairs[:, 0]] if P else np.zeros(0, np.uint64)
+    cap = int(n1.sum())
+    m = np.zeros((max(cap, 1), 2), np.uint32)
+    L = lib()
+    L.pcd_sift_match_guided_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                              C.c_void_p, C.c_uint64, C.c_void_p]
+    _check(L.pcd_sift_match_guided_batch(device, _vp(arena) if arena.shape[0] else None,
+                                         _vp(loc_arena) if loc_arena.shape[0] else None, _vp(first), len(descriptors),
+                                         _vp(pairs) if P else None, P, C.cast(g, C.c_void_p), h_max_residual,
+                                         f_max_residual, max_ratio, max_distance, int(cross_check), _vp(m), cap,
+                                         _vp(off)))
     return [m[int(off[p]):int(off[p + 1])].copy() for p in range(P)]
 
 

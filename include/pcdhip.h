@@ -558,6 +558,67 @@ pcd_status pcd_sift_matcher_set_descriptors(pcd_sift_matcher* m, int index /*0|1
 pcd_status pcd_sift_matcher_match(pcd_sift_matcher* m, int max_match, uint32_t* matches /*[max_match][2]*/,
                                   float distmax, float ratiomax, int mutual_best_match, int32_t* num_matches);
 
+/* Guided matching: replaces feature/sift.cc:1092-1162 MatchGuidedSiftFeaturesCPU (the specification) and
+ * :1274-1365 MatchGuidedSiftFeaturesGPU (lib/SiftGPU/SiftGPU.h:331-352 SetFeautreLocation / GetGuidedSiftMatch),
+ * which feature/matching.cc:459-580 Guided{CPU,GPU}FeatureMatcher run once per verified image pair.
+ * The result is the brute-force match set of sift.cc:55-144 on the distance matrix of sift.cc:171-204 with every
+ * pair the geometric filter rejects scored 0 -- exactly the same as leaving the pair out of both scans.
+ * loc: [n][2] float32 (x, y).  H / F: row-major float 3x3 (colmap passes Eigen::RowMajor .data()) or NULL; the
+ * filter, one IEEE float32 operation at a time in this order (no FMA):
+ *   H: h_i = (H[i][0] x1 + H[i][1] y1) + H[i][2]; r = (h0/h2 - x2)^2 + (h1/h2 - y2)^2; rejected iff r > h_max_residual
+ *   F: a_i = (F[i][0] x1 + F[i][1] y1) + F[i][2]; b_j = (F[0][j] x2 + F[1][j] y2) + F[2][j];
+ *      e = (x2 a0 + y2 a1) + a2; rejected iff (e e) / (((a0 a0 + a1 a1) + b0 b0) + b1 b1) > f_max_residual
+ * (a NaN residual is kept, an infinite one rejected).  With both matrices a pair is rejected if either test rejects
+ * it; with neither the result is exactly pcd_sift_match.  colmap passes max_error^2 for both thresholds
+ * (sift.cc:1346-1353).  The device form follows pcd_sift_match_device (H / F are host pointers, read before the call
+ * returns). */
+pcd_status pcd_sift_match_guided(int device, const uint8_t* desc1, const float* loc1 /*[n1][2]*/, int n1,
+                                 const uint8_t* desc2, const float* loc2 /*[n2][2]*/, int n2,
+                                 const float* H /*row-major 3x3 or NULL*/, const float* F /*row-major 3x3 or NULL*/,
+                                 float h_max_residual, float f_max_residual, float max_ratio, float max_distance,
+                                 int cross_check, uint32_t* matches /*[n1][2]*/, int32_t* num_matches);
+pcd_status pcd_sift_match_guided_device(int device, const uint8_t* d_desc1, const float* d_loc1, int n1,
+                                        const uint8_t* d_desc2, const float* d_loc2, int n2, const float* H,
+                                        const float* F, float h_max_residual, float f_max_residual, float max_ratio,
+                                        float max_distance, int cross_check, int32_t* d_m12, int32_t* d_m21,
+                                        uint32_t* d_matches, int32_t* d_num_matches, void* stream);
+
+/* Guided batch: matching.cc:523-575 GuidedSiftGPUFeatureMatcher's per-pair loop in one launch set.  Arguments as
+ * pcd_sift_match_batch[_device], plus a location arena ([rows][2] float32, indexed by the same first_row) and one
+ * guide per pair; the thresholds are shared.  Per pair the result equals pcd_sift_match_guided with that pair's
+ * matrices; a pair of mode PCD_SIFT_GUIDE_NONE equals pcd_sift_match. */
+typedef enum { PCD_SIFT_GUIDE_NONE = 0, PCD_SIFT_GUIDE_H = 1, PCD_SIFT_GUIDE_F = 2, PCD_SIFT_GUIDE_HF = 3 } pcd_sift_guide_mode;
+typedef struct {
+  int32_t mode;   /* pcd_sift_guide_mode */
+  float H[9];     /* row-major, read iff mode & PCD_SIFT_GUIDE_H */
+  float F[9];     /* row-major, read iff mode & PCD_SIFT_GUIDE_F */
+} pcd_sift_guide;
+pcd_status pcd_sift_match_guided_batch_device(int device, const uint8_t* d_arena, const float* d_locs,
+                                              const uint64_t* first_row /*[n_images+1]*/, int n_images,
+                                              const uint32_t* pairs /*[n_pairs][2]*/, int n_pairs,
+                                              const pcd_sift_guide* guides /*[n_pairs], host*/, float h_max_residual,
+                                              float f_max_residual, float max_ratio, float max_distance,
+                                              int cross_check, uint32_t* d_matches,
+                                              const uint64_t* match_offset /*[n_pairs]*/,
+                                              int32_t* d_counts /*[n_pairs]*/, void* stream);
+pcd_status pcd_sift_match_guided_batch(int device, const uint8_t* arena, const float* locs /*[rows][2]*/,
+                                       const uint64_t* first_row /*[n_images+1]*/, int n_images,
+                                       const uint32_t* pairs /*[n_pairs][2]*/, int n_pairs,
+                                       const pcd_sift_guide* guides /*[n_pairs]*/, float h_max_residual,
+                                       float f_max_residual, float max_ratio, float max_distance, int cross_check,
+                                       uint32_t* matches, uint64_t matches_capacity,
+                                       uint64_t* list_offset /*[n_pairs+1]*/);
+
+/* Matcher slots with locations (SiftMatchGPU::SetFeautreLocation, SiftGPU.h:331-335): reads n locations of slot
+ * `index` (n = the count of its last set_descriptors, clipped to max_sift) at a stride of 2 + gap floats.
+ * match_guided = GetGuidedSiftMatch (SiftGPU.h:343-352); hdistmax / fdistmax are the squared thresholds.  A slot
+ * whose descriptors were set again after its locations makes it return PCD_ERR_INVALID; calling again without new
+ * descriptors or locations reuses the slots (sift_test.cc:715-740). */
+pcd_status pcd_sift_matcher_set_locations(pcd_sift_matcher* m, int index /*0|1*/, const float* loc, int gap);
+pcd_status pcd_sift_matcher_match_guided(pcd_sift_matcher* m, int max_match, uint32_t* matches /*[max_match][2]*/,
+                                         const float* H, const float* F, float distmax, float ratiomax,
+                                         float hdistmax, float fdistmax, int mutual_best_match, int32_t* num_matches);
+
 /* ------------------------------------------------------------------------
  * Profiling hooks used by bench.py (HIP events on the launch stream)
  * --------------------------------------------------------------------- */
