@@ -23,6 +23,8 @@
 // would cost more than the ~300 flops).  MODEL >= 0 compiles one camera model in (all cameras of the
 // problem share it -- the usual case); MODEL = -1 switches per observation.
 #include <algorithm>
+#include <chrono>
+#include <memory>
 #include <numeric>
 
 #include "ba_cam_jac.h"
@@ -813,6 +815,339 @@ __global__ void k_pack_rows(const double* __restrict__ in, const uint32_t* __res
   reinterpret_cast<double2*>(out)[u] = reinterpret_cast<const double2*>(in + (size_t)vobs[r] * N)[k];
 }
 
+// ------------------------------------------------------------- Schur -------
+// Point elimination of the damped normal equations (H + D) delta = -g, unknowns = pose tangents of the variable-pose
+// images ("slots", ascending image index), then the points.  DESIGN 4.3a.  Observation data live in image-major
+// positions e (the layout k_ba_images walks): W and Y = W V^-1 of the observations of an image are contiguous, so the
+// entries of a pair block (a in image i, b in image j) gather from two short ranges.  No atomics anywhere: every sum
+// runs in an order fixed by the structure, so results are bitwise reproducible run to run.
+constexpr double kDiagMin = 1e-6, kDiagMax = 1e32;   // Ceres' LevenbergMarquardtStrategy min/max_diagonal
+
+__device__ __forceinline__ double damp_of(int mode, double mu, double h) {
+  return mode == 0 ? mu * fmin(fmax(h, kDiagMin), kDiagMax) : mu;
+}
+
+// thread = point: V = H_pt + D through a 3x3 Cholesky -> V^-1, V^-1 g, D.  Constant points are not eliminated, points
+// whose damped V is not positive definite are skipped (V^-1 = 0: delta 0, no contribution) and counted.
+__global__ __launch_bounds__(256) void k_schur_points(int P, const double* __restrict__ Hpt, const double* __restrict__ gpt,
+                                                      const uint8_t* __restrict__ point_const, double mu, int mode,
+                                                      double* __restrict__ Vinv, double* __restrict__ Vg,
+                                                      double* __restrict__ Dpt, uint32_t* __restrict__ skip_partial) {
+  __shared__ uint32_t s_n[4];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  uint32_t skipped = 0;
+  if (p < P) {
+    double vi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, d[3] = {0, 0, 0};
+    if (!(point_const && point_const[p])) {
+      const double* h = Hpt + 9 * (size_t)p;
+      d[0] = damp_of(mode, mu, h[0]); d[1] = damp_of(mode, mu, h[4]); d[2] = damp_of(mode, mu, h[8]);
+      const double a00 = h[0] + d[0], a01 = h[1], a02 = h[2], a11 = h[4] + d[1], a12 = h[5], a22 = h[8] + d[2];
+      bool ok = a00 > 0.0;   // false for NaN too
+      double l00 = 0, l10 = 0, l20 = 0, l11 = 0, l21 = 0, l22 = 0;
+      if (ok) { l00 = sqrt(a00); l10 = a01 / l00; l20 = a02 / l00; const double t = a11 - l10 * l10; ok = t > 0.0; l11 = ok ? sqrt(t) : 0.0; }
+      if (ok) { l21 = (a12 - l20 * l10) / l11; const double t = a22 - l20 * l20 - l21 * l21; ok = t > 0.0; l22 = ok ? sqrt(t) : 0.0; }
+      if (ok) {
+        // M = L^-1 (lower), V^-1 = M^T M
+        const double m00 = 1.0 / l00, m11 = 1.0 / l11, m22 = 1.0 / l22;
+        const double m10 = -(l10 * m00) * m11, m21 = -(l21 * m11) * m22, m20 = -(l20 * m00 + l21 * m10) * m22;
+        vi[0] = m00 * m00 + m10 * m10 + m20 * m20; vi[1] = m10 * m11 + m20 * m21; vi[2] = m20 * m22;
+        vi[4] = m11 * m11 + m21 * m21; vi[5] = m21 * m22; vi[8] = m22 * m22;
+        vi[3] = vi[1]; vi[6] = vi[2]; vi[7] = vi[5];
+      } else {
+        skipped = 1;
+      }
+    }
+    const double* g = gpt + 3 * (size_t)p;
+    double* o = Vinv + 9 * (size_t)p;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[k] = vi[k];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      Vg[3 * (size_t)p + r] = vi[3 * r] * g[0] + vi[3 * r + 1] * g[1] + vi[3 * r + 2] * g[2];
+      Dpt[3 * (size_t)p + r] = d[r];
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) skipped += __shfl_xor(skipped, off);
+  if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = skipped;
+  __syncthreads();
+  if (threadIdx.x == 0) skip_partial[blockIdx.x] = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+}
+
+// thread = image-major observation e: Y_e = W_e V_p^-1 (6x3)
+__global__ __launch_bounds__(256) void k_schur_obs(uint64_t O, const int* __restrict__ img_pt, const double* __restrict__ Wim,
+                                                   const double* __restrict__ Vinv, double* __restrict__ Y) {
+  const uint64_t e = blockIdx.x * (uint64_t)256 + threadIdx.x;
+  if (e >= O) return;
+  const double* v = Vinv + 9 * (size_t)img_pt[e];
+  const double* w = Wim + 18 * e;
+  double vi[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) vi[k] = v[k];
+  double* y = Y + 18 * e;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const double w0 = w[3 * r], w1 = w[3 * r + 1], w2 = w[3 * r + 2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) y[3 * r + c] = w0 * vi[c] + w1 * vi[3 + c] + w2 * vi[6 + c];
+  }
+}
+
+// Inputs of the block kernel (one struct keeps the launch readable)
+struct SchurBlocks {
+  int ns; uint32_t nblk;
+  const uint32_t* blk_start;   // [nblk+1] entries of each block: the ns diagonal blocks, then the pair blocks
+  const uint32_t* ent_a; const uint32_t* ent_b;   // image-major positions (a in image i, b in image j)
+  const uint32_t* pair_ij;     // [npairs][2] slots i < j
+  const int* slot_img;         // [ns]
+  const uint32_t* img_obs_start; const int* img_pt;
+  const double* Y; const double* Wim; const double* Vg;
+  const double* Himg; const double* gimg;
+  const uint8_t* image_const_tvec;
+  double mu; int mode;
+  double* Sdiag; double* Soff; double* rhs; double* Dimg;
+};
+
+// one wavefront per block: lane-strided entries, 36 accumulators, xor butterfly (every lane ends with the same
+// bitwise value, the order of the adds depends on the entry count only).  Diagonal blocks add U_i + D_i and the
+// right-hand side.  Constant-tvec coordinates become identity rows / columns with a zero right-hand side.
+__global__ __launch_bounds__(256) void k_schur_blocks(SchurBlocks sb) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t blk = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (blk >= sb.nblk) return;
+  double acc[36];
+#pragma unroll
+  for (int k = 0; k < 36; ++k) acc[k] = 0.0;
+  for (uint32_t t = sb.blk_start[blk] + lane; t < sb.blk_start[blk + 1]; t += 64) {
+    const double* y = sb.Y + 18 * (size_t)sb.ent_a[t];
+    const double* w = sb.Wim + 18 * (size_t)sb.ent_b[t];
+    double yv[18], wv[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) { yv[k] = y[k]; wv[k] = w[k]; }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int s = 0; s < 6; ++s)
+        acc[6 * r + s] += yv[3 * r] * wv[3 * s] + yv[3 * r + 1] * wv[3 * s + 1] + yv[3 * r + 2] * wv[3 * s + 2];
+  }
+  double mine = 0.0;   // lane k < 36 keeps entry k (selects, no dynamic register indexing)
+#pragma unroll
+  for (int k = 0; k < 36; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    mine = lane == k ? v : mine;
+  }
+  const int r = lane / 6, s = lane - 6 * (lane / 6);
+  if (blk < (uint32_t)sb.ns) {
+    const int i = (int)blk, im = sb.slot_img[i];
+    const unsigned tm = sb.image_const_tvec ? sb.image_const_tvec[im] : 0u;
+    // rhs_i = -g_i + sum_{a in i} W_a V^-1 g_p(a), observations of the image in image-major order
+    double q[6] = {0, 0, 0, 0, 0, 0};
+    for (uint32_t e = sb.img_obs_start[im] + lane; e < sb.img_obs_start[im + 1]; e += 64) {
+      const double* w = sb.Wim + 18 * (size_t)e;
+      const double* vg = sb.Vg + 3 * (size_t)sb.img_pt[e];
+      const double v0 = vg[0], v1 = vg[1], v2 = vg[2];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) q[k] += w[3 * k] * v0 + w[3 * k + 1] * v1 + w[3 * k + 2] * v2;
+    }
+    double qm = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      double v = q[k];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+      qm = lane == k ? v : qm;
+    }
+    const double* H = sb.Himg + 36 * (size_t)im;
+    if (lane < 36) {
+      const bool ir = r >= 3 && ((tm >> (r - 3)) & 1u), is = s >= 3 && ((tm >> (s - 3)) & 1u);
+      double v = H[6 * r + s] - mine;
+      if (r == s) v += damp_of(sb.mode, sb.mu, H[7 * r]);
+      if (ir || is) v = r == s ? 1.0 : 0.0;
+      sb.Sdiag[36 * (size_t)i + lane] = v;
+    }
+    if (lane < 6) {
+      const bool in = lane >= 3 && ((tm >> (lane - 3)) & 1u);
+      sb.rhs[6 * (size_t)i + lane] = in ? 0.0 : qm - sb.gimg[6 * (size_t)im + lane];
+      sb.Dimg[6 * (size_t)i + lane] = in ? 0.0 : damp_of(sb.mode, sb.mu, H[7 * lane]);
+    }
+  } else if (lane < 36) {
+    const uint32_t pq = blk - (uint32_t)sb.ns;
+    const int si = (int)sb.pair_ij[2 * (size_t)pq], sj = (int)sb.pair_ij[2 * (size_t)pq + 1];
+    const unsigned ti = sb.image_const_tvec ? sb.image_const_tvec[sb.slot_img[si]] : 0u;
+    const unsigned tj = sb.image_const_tvec ? sb.image_const_tvec[sb.slot_img[sj]] : 0u;
+    const bool ir = r >= 3 && ((ti >> (r - 3)) & 1u), is = s >= 3 && ((tj >> (s - 3)) & 1u);
+    sb.Soff[36 * (size_t)pq + lane] = (ir || is) ? 0.0 : 0.0 - mine;
+  }
+}
+
+// dense S [n][n] (n = 6 ns, both triangles) from the blocks; the caller zeroed it.  thread = (block, entry)
+__global__ __launch_bounds__(256) void k_schur_dense(int ns, uint32_t nblk, const uint32_t* __restrict__ pair_ij,
+                                                     const double* __restrict__ Sdiag, const double* __restrict__ Soff,
+                                                     double* __restrict__ S) {
+  const uint64_t t = blockIdx.x * (uint64_t)256 + threadIdx.x;
+  if (t >= (uint64_t)nblk * 36) return;
+  const uint32_t blk = (uint32_t)(t / 36);
+  const int k = (int)(t - 36 * (uint64_t)blk), r = k / 6, s = k - 6 * (k / 6);
+  const size_t n = 6 * (size_t)ns;
+  if (blk < (uint32_t)ns) {
+    S[(6 * (size_t)blk + r) * n + 6 * (size_t)blk + s] = Sdiag[36 * (size_t)blk + k];
+  } else {
+    const uint32_t pq = blk - (uint32_t)ns;
+    const size_t i = pair_ij[2 * (size_t)pq], j = pair_ij[2 * (size_t)pq + 1];
+    const double v = Soff[36 * (size_t)pq + k];
+    S[(6 * i + r) * n + 6 * j + s] = v;
+    S[(6 * j + s) * n + 6 * i + r] = v;
+  }
+}
+
+// thread = point: delta X_p = -V^-1 (g_p + sum_{a in p} W_a^T delta c_img(a)), its observations in ascending caller
+// order; partial of the model decrease -delta^T g + delta^T D delta over the points (fixed-order block sum)
+__global__ __launch_bounds__(256) void k_schur_back(int P, const uint32_t* __restrict__ pt_start,
+                                                    const uint32_t* __restrict__ pt_list, const int* __restrict__ obs_image,
+                                                    const uint32_t* __restrict__ obs_pos, const int* __restrict__ img_slot,
+                                                    const double* __restrict__ Wim, const double* __restrict__ Vinv,
+                                                    const double* __restrict__ gpt, const double* __restrict__ Dpt,
+                                                    const double* __restrict__ dpose, double* __restrict__ dpoint,
+                                                    double* __restrict__ md_partial) {
+  __shared__ double s_m[4];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  double md = 0.0;
+  if (p < P) {
+    const double* g = gpt + 3 * (size_t)p;
+    double r0 = g[0], r1 = g[1], r2 = g[2];
+    for (uint32_t k = pt_start[p]; k < pt_start[p + 1]; ++k) {
+      const uint32_t o = pt_list[k];
+      const int s = img_slot[obs_image[o]];
+      if (s < 0) continue;
+      const double* w = Wim + 18 * (size_t)obs_pos[o];
+      const double* dc = dpose + 6 * (size_t)s;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const double c = dc[a];
+        r0 += w[3 * a] * c; r1 += w[3 * a + 1] * c; r2 += w[3 * a + 2] * c;
+      }
+    }
+    const double* v = Vinv + 9 * (size_t)p;
+    const double dx0 = -(v[0] * r0 + v[1] * r1 + v[2] * r2);
+    const double dx1 = -(v[3] * r0 + v[4] * r1 + v[5] * r2);
+    const double dx2 = -(v[6] * r0 + v[7] * r1 + v[8] * r2);
+    dpoint[3 * (size_t)p] = dx0; dpoint[3 * (size_t)p + 1] = dx1; dpoint[3 * (size_t)p + 2] = dx2;
+    const double* d = Dpt + 3 * (size_t)p;
+    md = -(dx0 * g[0] + dx1 * g[1] + dx2 * g[2]) + (d[0] * dx0 * dx0 + d[1] * dx1 * dx1 + d[2] * dx2 * dx2);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) md += __shfl_xor(md, off);
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = md;
+  __syncthreads();
+  if (threadIdx.x == 0) md_partial[blockIdx.x] = (s_m[0] + s_m[1]) + (s_m[2] + s_m[3]);
+}
+
+// one workgroup: 1/2 (slot terms + point partials), strided per thread then a fixed tree
+__global__ __launch_bounds__(256) void k_schur_model_decrease(int ns, const int* __restrict__ slot_img,
+                                                              const uint8_t* __restrict__ image_const_tvec,
+                                                              const double* __restrict__ gimg, const double* __restrict__ Dimg,
+                                                              const double* __restrict__ dpose,
+                                                              const double* __restrict__ md_partial, int nbp,
+                                                              double* __restrict__ out) {
+  __shared__ double s_c[256];
+  double a = 0.0, b = 0.0;
+  for (int i = threadIdx.x; i < ns; i += 256) {
+    const int im = slot_img[i];
+    const unsigned tm = image_const_tvec ? image_const_tvec[im] : 0u;
+    const double* g = gimg + 6 * (size_t)im;
+    const double* d = Dimg + 6 * (size_t)i;
+    const double* x = dpose + 6 * (size_t)i;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const bool inactive = k >= 3 && ((tm >> (k - 3)) & 1u);   // delta 0 there, whatever the caller passed
+      a += inactive ? 0.0 : -x[k] * g[k] + d[k] * x[k] * x[k];
+    }
+  }
+  for (int i = threadIdx.x; i < nbp; i += 256) b += md_partial[i];
+  s_c[threadIdx.x] = a + b;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) s_c[threadIdx.x] += s_c[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = 0.5 * s_c[0];
+}
+
+__global__ __launch_bounds__(256) void k_sum_u32(const uint32_t* __restrict__ partial, int n, unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long s_c[256];
+  unsigned long long a = 0;
+  for (int i = threadIdx.x; i < n; i += 256) a += partial[i];
+  s_c[threadIdx.x] = a;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) s_c[threadIdx.x] += s_c[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = s_c[0];
+}
+
+// Ceres' QuaternionManifold::Plus (q <- [cos|d|, sin|d|/|d| d] * q) and t += dt on the variable coordinates;
+// constant poses / tvec components / points are copied.  thread = image (t < I) or point.  In-place safe.
+__global__ __launch_bounds__(256) void k_ba_plus(int I, int P, const int* __restrict__ img_slot,
+                                                 const uint8_t* __restrict__ image_const_tvec,
+                                                 const uint8_t* __restrict__ point_const, const double* poses,
+                                                 const double* points, const double* __restrict__ dpose,
+                                                 const double* __restrict__ dpoint, double* poses_out, double* points_out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < I) {
+    const double* x = poses + 7 * (size_t)t;
+    double y[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) y[k] = x[k];
+    const int s = img_slot[t];
+    if (s >= 0) {
+      const double* d = dpose + 6 * (size_t)s;
+      const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+      if (nd != 0.0) {
+        const double sd = sin(nd) / nd;
+        const double a0 = cos(nd), a1 = sd * d[0], a2 = sd * d[1], a3 = sd * d[2];
+        y[0] = a0 * x[0] - a1 * x[1] - a2 * x[2] - a3 * x[3];
+        y[1] = a0 * x[1] + a1 * x[0] + a2 * x[3] - a3 * x[2];
+        y[2] = a0 * x[2] - a1 * x[3] + a2 * x[0] + a3 * x[1];
+        y[3] = a0 * x[3] + a1 * x[2] - a2 * x[1] + a3 * x[0];
+      }
+      const unsigned tm = image_const_tvec ? image_const_tvec[t] : 0u;
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (!((tm >> k) & 1u)) y[4 + k] = x[4 + k] + d[3 + k];
+    }
+    double* o = poses_out + 7 * (size_t)t;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) o[k] = y[k];
+  } else if (t < I + P) {
+    const int p = t - I;
+    const double* x = points + 3 * (size_t)p;
+    const double* d = dpoint + 3 * (size_t)p;
+    const bool c = point_const && point_const[p];
+    double* o = points_out + 3 * (size_t)p;
+    const double y0 = c ? x[0] : x[0] + d[0], y1 = c ? x[1] : x[1] + d[1], y2 = c ? x[2] : x[2] + d[2];
+    o[0] = y0; o[1] = y1; o[2] = y2;
+  }
+}
+
+// Host-built structure (first Schur call) and the numeric state of the last Schur call
+struct BaSchur {
+  bool built = false;
+  int ns = 0;
+  uint64_t npairs = 0, nent = 0;
+  double build_ms = 0.0;
+  std::vector<int32_t> h_slot, h_pair_i, h_pair_j;
+  DevBuf<int> img_slot, slot_img;
+  DevBuf<uint32_t> blk_start, ent_a, ent_b, pair_ij, iota, obs_pos;
+  bool valid = false;   // a Schur call has filled the state below
+  DevBuf<double> Himg, gimg, Hpt, gpt, Wim, Y, Vinv, Vg, Dpt, Dimg, Sdiag, Soff, rhs, md_partial, md;
+  DevBuf<uint32_t> skip_partial;
+  DevBuf<unsigned long long> skip_cnt;
+  DevBuf<double> cost, dense;   // dense: staging of the host form's S
+};
+
 }  // namespace pcd
 
 using namespace pcd;
@@ -848,6 +1183,9 @@ struct pcd_ba {
   DevBuf<uint32_t> pt_obs_start, pt_obs_list;
   DevBuf<double> f_sq, f_depth, f_part, f_summary;
   DevBuf<uint8_t> f_u8;
+  // point elimination (pcd_ba_schur*): built on the first call, so pcd_ba_create costs existing users nothing
+  bool refines_intrinsics = false;   // some camera_refine byte is set: the reduced system would need camera rows
+  std::unique_ptr<BaSchur> schur;
   BaDev dev() const {
     BaDev d;
     d.cam_model = cam_model.p; d.cam_off = cam_off.p; d.cam_params = cam_params.p;
@@ -944,6 +1282,131 @@ static unsigned cost_blocks(const pcd_ba* b, bool want_blocks) {
                      : std::max(1u, std::min(kCostBlocks, div_up(b->O + b->L, 256)));
 }
 
+// ---- point elimination: guards and the co-visibility structure ----------------------------------------------
+// Every Schur entry point: no gfx950 device -> NO_DEVICE, no handle -> INVALID, refined intrinsics -> UNSUPPORTED
+// (the reduced system would need the camera rows), all before anything is allocated or launched.
+static pcd_status schur_guard(pcd_ba* b) {
+  PCD_TRY(require_device(b ? b->device : 0));
+  PCD_REQUIRE(b, "null handle");
+  if (b->refines_intrinsics) {
+    set_error("point elimination with refined intrinsics (camera_refine) is not supported");
+    return PCD_ERR_UNSUPPORTED;
+  }
+  return PCD_OK;
+}
+
+// Slots, the per-block entry lists and the inverse image-major permutation, by host counting sorts over index arrays
+// read back once.  Blocks: the ns diagonal blocks, then the pair blocks in ascending (i, j).  Entries (a, b) of a block:
+// a ascending (image-major position in image i), then b ascending (image j).  A diagonal block holds (a, a) and the
+// pairs of a point observed more than once in the image.  Only variable-pose observations of non-constant points
+// take part.
+static pcd_status schur_build(pcd_ba* b) {
+  if (!b->schur) b->schur.reset(new BaSchur());
+  BaSchur& S = *b->schur;
+  if (S.built) return PCD_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t O = b->O;
+  const int I = b->I, P = b->P;
+  std::vector<int32_t> oimg(O), opt(O);
+  std::vector<uint32_t> ist((size_t)I + 1), iobs(O);
+  std::vector<uint8_t> cpose(I, 0), cpt(P, 0);
+  if (O) {
+    PCD_HIP_TRY(hipMemcpy(oimg.data(), b->obs_image.p, O * sizeof(int32_t), hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipMemcpy(opt.data(), b->obs_point.p, O * sizeof(int32_t), hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipMemcpy(iobs.data(), b->img_obs.p, O * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  PCD_HIP_TRY(hipMemcpy(ist.data(), b->img_obs_start.p, ist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (b->has_cpose) PCD_HIP_TRY(hipMemcpy(cpose.data(), b->image_const_pose.p, I, hipMemcpyDeviceToHost));
+  if (b->has_cpt) PCD_HIP_TRY(hipMemcpy(cpt.data(), b->point_const.p, P, hipMemcpyDeviceToHost));
+  S.h_slot.assign(I, -1);
+  std::vector<int32_t> slot_img;
+  for (int i = 0; i < I; ++i)
+    if (!cpose[i]) { S.h_slot[i] = (int32_t)slot_img.size(); slot_img.push_back(i); }
+  const int ns = (int)slot_img.size();
+  S.ns = ns;
+  std::vector<uint32_t> obs_pos(O), iota(O);
+  std::vector<int32_t> eslot(O), ept(O);
+  for (int i = 0; i < I; ++i)
+    for (uint32_t e = ist[i]; e < ist[i + 1]; ++e) {
+      const uint32_t o = iobs[e];
+      obs_pos[o] = e; iota[e] = e; ept[e] = opt[o];
+      eslot[e] = cpt[opt[o]] ? -1 : S.h_slot[i];   // -1: takes no part in the elimination
+    }
+  // eliminated observations of every point, ascending image-major position
+  std::vector<uint32_t> pst((size_t)P + 1, 0), pli;
+  for (uint64_t e = 0; e < O; ++e) if (eslot[e] >= 0) pst[(size_t)ept[e] + 1]++;
+  for (int p = 0; p < P; ++p) pst[p + 1] += pst[p];
+  pli.resize(pst[P]);
+  {
+    std::vector<uint32_t> cur(pst.begin(), pst.end() - 1);
+    for (uint64_t e = 0; e < O; ++e) if (eslot[e] >= 0) pli[cur[ept[e]]++] = (uint32_t)e;
+  }
+  std::vector<uint64_t> blk(1, 0);
+  std::vector<uint32_t> ea, eb;
+  for (int s = 0; s < ns; ++s) {   // diagonal blocks
+    const int im = slot_img[s];
+    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
+      if (eslot[e] < 0) continue;
+      const int p = ept[e];
+      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k)
+        if (eslot[pli[k]] == s) { ea.push_back(e); eb.push_back(pli[k]); }
+    }
+    blk.push_back(ea.size());
+  }
+  S.h_pair_i.clear(); S.h_pair_j.clear();
+  std::vector<uint32_t> cnt(ns, 0);
+  std::vector<uint64_t> cur(ns, 0);
+  std::vector<int> touched;
+  for (int s = 0; s < ns; ++s) {   // pair blocks of row s: a per-row counting sort over the partner slot
+    const int im = slot_img[s];
+    touched.clear();
+    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
+      if (eslot[e] < 0) continue;
+      const int p = ept[e];
+      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k) {
+        const int j = eslot[pli[k]];
+        if (j > s && cnt[j]++ == 0) touched.push_back(j);
+      }
+    }
+    std::sort(touched.begin(), touched.end());
+    uint64_t off = ea.size();
+    for (int j : touched) {
+      cur[j] = off; off += cnt[j];
+      S.h_pair_i.push_back(s); S.h_pair_j.push_back(j);
+      blk.push_back(off);
+    }
+    ea.resize(off); eb.resize(off);
+    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
+      if (eslot[e] < 0) continue;
+      const int p = ept[e];
+      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k) {
+        const int j = eslot[pli[k]];
+        if (j > s) { ea[cur[j]] = e; eb[cur[j]++] = pli[k]; }
+      }
+    }
+    for (int j : touched) cnt[j] = 0;
+  }
+  if (ea.size() >= 0xFFFFFFF0ull || blk.size() >= 0xFFFFFFF0ull) {
+    set_error("point elimination: %zu block entries exceed the 32-bit layout", ea.size());
+    return PCD_ERR_UNSUPPORTED;
+  }
+  S.npairs = S.h_pair_i.size();
+  S.nent = ea.size();
+  std::vector<uint32_t> blk32(blk.begin(), blk.end()), pij(2 * S.npairs);
+  for (uint64_t q = 0; q < S.npairs; ++q) { pij[2 * q] = (uint32_t)S.h_pair_i[q]; pij[2 * q + 1] = (uint32_t)S.h_pair_j[q]; }
+  PCD_TRY(upload(S.img_slot, S.h_slot.data(), (size_t)I));
+  PCD_TRY(upload(S.slot_img, slot_img.data(), slot_img.size()));
+  PCD_TRY(upload(S.blk_start, blk32.data(), blk32.size()));
+  PCD_TRY(upload(S.ent_a, ea.data(), ea.size()));
+  PCD_TRY(upload(S.ent_b, eb.data(), eb.size()));
+  PCD_TRY(upload(S.pair_ij, pij.data(), pij.size()));
+  PCD_TRY(upload(S.iota, iota.data(), iota.size()));
+  PCD_TRY(upload(S.obs_pos, obs_pos.data(), obs_pos.size()));
+  S.built = true;
+  S.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PCD_OK;
+}
+
 extern "C" {
 
 pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
@@ -993,6 +1456,7 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
   if (d->image_const_tvec) { b->has_ctvec = true; UP(image_const_tvec, d->image_const_tvec, b->I); }
   if (d->point_const) { b->has_cpt = true; UP(point_const, d->point_const, b->P); }
   if (d->camera_refine) { b->has_refine = true; UP(cam_refine, d->camera_refine, d->cam_params_len); }
+  for (uint64_t k = 0; d->camera_refine && k < d->cam_params_len; ++k) b->refines_intrinsics |= d->camera_refine[k] != 0;
 
   std::vector<uint32_t> st, li;
   // ---- per-track sliced ELL in order of track length ----
@@ -1340,6 +1804,192 @@ pcd_status pcd_ba_evaluate(pcd_ba* b, const pcd_ba_out* o) {
   for (auto& it : items)
     if (it.host && it.n) PCD_HIP_TRY(hipMemcpy(it.host, it.buf->p, it.n * sizeof(double), hipMemcpyDeviceToHost));
   PCD_HIP_TRY(hipDeviceSynchronize());
+  return PCD_OK;
+}
+
+// ---- point elimination ------------------------------------------------------------------------------
+pcd_status pcd_ba_schur_structure(pcd_ba* b, int32_t* image_slot, int32_t* num_slots, uint64_t* num_pairs,
+                                  int32_t* pair_i, int32_t* pair_j) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_TRY(schur_build(b));
+    const BaSchur& S = *b->schur;
+    if (image_slot) std::memcpy(image_slot, S.h_slot.data(), (size_t)b->I * sizeof(int32_t));
+    if (num_slots) *num_slots = S.ns;
+    if (num_pairs) *num_pairs = S.npairs;
+    if (pair_i && S.npairs) std::memcpy(pair_i, S.h_pair_i.data(), S.npairs * sizeof(int32_t));
+    if (pair_j && S.npairs) std::memcpy(pair_j, S.h_pair_j.data(), S.npairs * sizeof(int32_t));
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_stats(pcd_ba* b, pcd_ba_schur_info* info) {
+  PCD_TRY(schur_guard(b));
+  PCD_REQUIRE(info, "null pointer");
+  std::memset(info, 0, sizeof *info);
+  if (!b->schur || !b->schur->built) return PCD_OK;
+  const BaSchur& S = *b->schur;
+  info->build_ms = S.build_ms;
+  info->num_entries = S.nent;
+  uint64_t bytes = 0;
+  bytes += (S.img_slot.n + S.slot_img.n) * sizeof(int);
+  bytes += (S.blk_start.n + S.ent_a.n + S.ent_b.n + S.pair_ij.n + S.iota.n + S.obs_pos.n + S.skip_partial.n) * sizeof(uint32_t);
+  for (const DevBuf<double>* d : {&S.Himg, &S.gimg, &S.Hpt, &S.gpt, &S.Wim, &S.Y, &S.Vinv, &S.Vg, &S.Dpt, &S.Dimg,
+                                  &S.Sdiag, &S.Soff, &S.rhs, &S.md_partial, &S.md, &S.cost, &S.dense})
+    bytes += d->n * sizeof(double);
+  info->scratch_bytes = bytes;
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(opt && o, "null pointer");
+    PCD_REQUIRE(opt->damping == PCD_DAMP_MARQUARDT || opt->damping == PCD_DAMP_LEVENBERG, "damping");
+    PCD_REQUIRE(opt->mu >= 0.0, "mu must be >= 0");
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(schur_build(b));
+    BaSchur& S = *b->schur;
+    hipStream_t s = (hipStream_t)stream;
+    const int I = b->I, P = b->P, ns = S.ns;
+    const uint64_t O = b->O;
+    const uint32_t nblk = (uint32_t)(ns + S.npairs);
+    const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
+    S.valid = false;
+    PCD_TRY(S.Himg.reserve(36 * (size_t)I)); PCD_TRY(S.gimg.reserve(6 * (size_t)I));
+    PCD_TRY(S.Hpt.reserve(9 * (size_t)P)); PCD_TRY(S.gpt.reserve(3 * (size_t)P));
+    PCD_TRY(S.Wim.reserve(std::max<size_t>(18 * O, 1))); PCD_TRY(S.Y.reserve(std::max<size_t>(18 * O, 1)));
+    PCD_TRY(S.Vinv.reserve(9 * (size_t)P)); PCD_TRY(S.Vg.reserve(3 * (size_t)P)); PCD_TRY(S.Dpt.reserve(3 * (size_t)P));
+    PCD_TRY(S.Dimg.reserve(std::max<size_t>(6 * (size_t)ns, 1)));
+    PCD_TRY(S.Sdiag.reserve(std::max<size_t>(36 * (size_t)ns, 1)));
+    PCD_TRY(S.Soff.reserve(std::max<size_t>(36 * S.npairs, 1)));
+    PCD_TRY(S.rhs.reserve(std::max<size_t>(6 * (size_t)ns, 1)));
+    PCD_TRY(S.skip_partial.reserve(nbp)); PCD_TRY(S.skip_cnt.reserve(1));
+    PCD_TRY(S.md_partial.reserve(nbp)); PCD_TRY(S.md.reserve(1)); PCD_TRY(S.cost.reserve(1));
+    PCD_TRY(b->img_partial.reserve(27 * (size_t)std::max(b->nseg, 1u)));
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    const BaDev d = b->dev();
+    BaDev dim = d;
+    dim.img_obs = S.iota.p;   // W lands in image-major order (k_ba_images' contiguous store path)
+    const int model = b->uniform_model;
+    double* Sdiag = o->S_diag ? o->S_diag : S.Sdiag.p;
+    double* Soff = o->S_off ? o->S_off : S.Soff.p;
+    double* rhs = o->rhs ? o->rhs : S.rhs.p;
+    {
+      ScopedKernelTimer t("ba_schur_normal", s);
+      const unsigned blocks = cost_blocks(b, true);
+      PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_points<M, true>), dim3(blocks), dim3(256), 0, s, d, S.Hpt.p,
+                                                 S.gpt.p, b->cost_partial.p));
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, b->cost_partial.p, (int)blocks,
+                         o->cost ? o->cost : S.cost.p);
+      if (b->nseg)
+        PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_images<M, true>), dim3(b->nseg), dim3(256), 0, s, dim,
+                                                   b->img_partial.p, S.Wim.p));
+      hipLaunchKernelGGL(k_ba_images_reduce, dim3(div_up(I, 2)), dim3(64), 0, s, d, b->img_partial.p, S.Himg.p, S.gimg.p);
+    }
+    {
+      ScopedKernelTimer t("ba_schur_eliminate", s);
+      hipLaunchKernelGGL(k_schur_points, dim3(nbp), dim3(256), 0, s, P, S.Hpt.p, S.gpt.p, d.point_const, opt->mu,
+                         opt->damping, S.Vinv.p, S.Vg.p, S.Dpt.p, S.skip_partial.p);
+      hipLaunchKernelGGL(k_sum_u32, dim3(1), dim3(256), 0, s, S.skip_partial.p, (int)nbp,
+                         o->num_skipped ? reinterpret_cast<unsigned long long*>(o->num_skipped) : S.skip_cnt.p);
+      if (O) hipLaunchKernelGGL(k_schur_obs, dim3(div_up(O, 256)), dim3(256), 0, s, O, b->img_pt.p, S.Wim.p, S.Vinv.p, S.Y.p);
+      SchurBlocks sb;
+      sb.ns = ns; sb.nblk = nblk; sb.blk_start = S.blk_start.p; sb.ent_a = S.ent_a.p; sb.ent_b = S.ent_b.p;
+      sb.pair_ij = S.pair_ij.p; sb.slot_img = S.slot_img.p; sb.img_obs_start = b->img_obs_start.p; sb.img_pt = b->img_pt.p;
+      sb.Y = S.Y.p; sb.Wim = S.Wim.p; sb.Vg = S.Vg.p; sb.Himg = S.Himg.p; sb.gimg = S.gimg.p;
+      sb.image_const_tvec = d.image_const_tvec; sb.mu = opt->mu; sb.mode = opt->damping;
+      sb.Sdiag = Sdiag; sb.Soff = Soff; sb.rhs = rhs; sb.Dimg = S.Dimg.p;
+      if (nblk) hipLaunchKernelGGL(k_schur_blocks, dim3(div_up(nblk, 4)), dim3(256), 0, s, sb);
+    }
+    if (o->S && ns) {
+      ScopedKernelTimer t("ba_schur_dense", s);
+      const size_t n = 6 * (size_t)ns;
+      PCD_HIP_TRY(hipMemsetAsync(o->S, 0, n * n * sizeof(double), s));
+      hipLaunchKernelGGL(k_schur_dense, dim3(div_up((uint64_t)nblk * 36, 256)), dim3(256), 0, s, ns, nblk, S.pair_ij.p,
+                         Sdiag, Soff, o->S);
+    }
+    PCD_HIP_TRY(hipGetLastError());
+    S.valid = true;
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(opt && o, "null pointer");
+    PCD_TRY(schur_build(b));
+    BaSchur& S = *b->schur;
+    const size_t n = 6 * (size_t)S.ns;
+    pcd_ba_schur_out d{};
+    if (o->S) { PCD_TRY(S.dense.reserve(std::max<size_t>(n * n, 1))); d.S = S.dense.p; }
+    PCD_TRY(pcd_ba_schur_device(b, opt, &d, nullptr));
+    if (o->cost) PCD_HIP_TRY(hipMemcpy(o->cost, S.cost.p, sizeof(double), hipMemcpyDeviceToHost));
+    if (o->num_skipped) PCD_HIP_TRY(hipMemcpy(o->num_skipped, S.skip_cnt.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (o->S_diag && S.ns) PCD_HIP_TRY(hipMemcpy(o->S_diag, S.Sdiag.p, 36 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
+    if (o->S_off && S.npairs) PCD_HIP_TRY(hipMemcpy(o->S_off, S.Soff.p, 36 * S.npairs * sizeof(double), hipMemcpyDeviceToHost));
+    if (o->rhs && S.ns) PCD_HIP_TRY(hipMemcpy(o->rhs, S.rhs.p, 6 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
+    if (o->S && n) PCD_HIP_TRY(hipMemcpy(o->S, S.dense.p, n * n * sizeof(double), hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipDeviceSynchronize());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_back_substitute_device(pcd_ba* b, const double* d_dpose, double* d_dpoint,
+                                               double* d_model_decrease, void* stream) {
+  PCD_TRY(schur_guard(b));
+  PCD_REQUIRE(d_dpose && d_dpoint, "null pointer");
+  PCD_REFUSE_CAPTURE(stream);
+  if (!b->schur || !b->schur->valid) {
+    set_error("pcd_ba_schur_back_substitute_device: no Schur state (call pcd_ba_schur[_device] first)");
+    return PCD_ERR_INVALID;
+  }
+  BaSchur& S = *b->schur;
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int P = b->P;
+  const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
+  ScopedKernelTimer t("ba_schur_back", s);
+  hipLaunchKernelGGL(k_schur_back, dim3(nbp), dim3(256), 0, s, P, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p,
+                     S.obs_pos.p, S.img_slot.p, S.Wim.p, S.Vinv.p, S.gpt.p, S.Dpt.p, d_dpose, d_dpoint, S.md_partial.p);
+  if (d_model_decrease)
+    hipLaunchKernelGGL(k_schur_model_decrease, dim3(1), dim3(256), 0, s, S.ns, S.slot_img.p,
+                       b->has_ctvec ? b->image_const_tvec.p : (const uint8_t*)nullptr, S.gimg.p, S.Dimg.p, d_dpose,
+                       S.md_partial.p, (int)nbp, d_model_decrease);
+  PCD_HIP_TRY(hipGetLastError());
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_plus_device(pcd_ba* b, const double* d_dpose, const double* d_dpoint, double* d_poses_out,
+                              double* d_points_out, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(d_dpose && d_dpoint && d_poses_out && d_points_out, "null pointer");
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(schur_build(b));
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    ScopedKernelTimer t("ba_plus", s);
+    hipLaunchKernelGGL(k_ba_plus, dim3(div_up((uint64_t)b->I + b->P, 256)), dim3(256), 0, s, b->I, b->P,
+                       b->schur->img_slot.p, b->has_ctvec ? b->image_const_tvec.p : (const uint8_t*)nullptr,
+                       b->has_cpt ? b->point_const.p : (const uint8_t*)nullptr, b->poses.p, b->points.p, d_dpose,
+                       d_dpoint, d_poses_out, d_points_out);
+    PCD_HIP_TRY(hipGetLastError());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_set_parameters_device(pcd_ba* b, const double* d_poses, const double* d_points, void* stream) {
+  PCD_TRY(require_device(b ? b->device : 0));
+  PCD_REQUIRE(b, "null handle");
+  PCD_REFUSE_CAPTURE(stream);
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (d_poses && d_poses != b->poses.p)
+    PCD_HIP_TRY(hipMemcpyAsync(b->poses.p, d_poses, 7 * (size_t)b->I * sizeof(double), hipMemcpyDeviceToDevice, s));
+  if (d_points && d_points != b->points.p)
+    PCD_HIP_TRY(hipMemcpyAsync(b->points.p, d_points, 3 * (size_t)b->P * sizeof(double), hipMemcpyDeviceToDevice, s));
   return PCD_OK;
 }
 

@@ -84,6 +84,22 @@ class BAOut(C.Structure):
                                            "H_cam", "g_cam", "E_cam", "W_cam")]
 
 
+DAMP_MARQUARDT, DAMP_LEVENBERG = 0, 1
+_DAMPING = {"marquardt": DAMP_MARQUARDT, "levenberg": DAMP_LEVENBERG}
+
+
+class BASchurOpts(C.Structure):
+    _fields_ = [("mu", C.c_double), ("damping", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class BASchurOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "S_diag", "S_off", "rhs", "S", "num_skipped")]
+
+
+class BASchurInfo(C.Structure):
+    _fields_ = [("build_ms", C.c_double), ("num_entries", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -115,6 +131,8 @@ ABI_SYMBOLS = [
     "pcd_ba_evaluate_blocks", "pcd_ba_filter_tracks", "pcd_ba_filter_tracks_device",
     "pcd_cloud_create_sharded", "pcd_cloud_shards_destroy", "pcd_cloud_shards_count", "pcd_cloud_shards_size",
     "pcd_cloud_shards_get", "pcd_nn_query_sharded", "pcd_associate_sharded",
+    "pcd_ba_set_parameters_device", "pcd_ba_schur_structure", "pcd_ba_schur_device", "pcd_ba_schur",
+    "pcd_ba_schur_back_substitute_device", "pcd_ba_plus_device", "pcd_ba_schur_stats",
 ]
 
 
@@ -183,6 +201,15 @@ def lib():
         L.pcd_ba_evaluate.argtypes = [C.c_void_p, C.POINTER(BAOut)]
         L.pcd_ba_evaluate_device.argtypes = [C.c_void_p, C.POINTER(BAOut), C.c_void_p]
         L.pcd_ba_device_parameters.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    if hasattr(L, "pcd_ba_schur_device"):
+        L.pcd_ba_set_parameters_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pcd_ba_schur_structure.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+                                             C.c_void_p, C.c_void_p]
+        L.pcd_ba_schur_device.argtypes = [C.c_void_p, C.POINTER(BASchurOpts), C.POINTER(BASchurOut), C.c_void_p]
+        L.pcd_ba_schur.argtypes = [C.c_void_p, C.POINTER(BASchurOpts), C.POINTER(BASchurOut)]
+        L.pcd_ba_schur_back_substitute_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pcd_ba_plus_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+        L.pcd_ba_schur_stats.argtypes = [C.c_void_p, C.POINTER(BASchurInfo)]
     _LIB = L
     return L
 
@@ -757,6 +784,7 @@ class BA:
             assert self.camera_refine.shape[0] == len(self.cam_params)
             d.camera_refine = _vp(self.camera_refine)
         self.C = len(self.cam_model)
+        self.device = device
         h = C.c_void_p()
         self._h = None
         _check(lib().pcd_ba_create(C.byref(d), C.byref(h)))
@@ -824,3 +852,137 @@ class BA:
         a, b = C.c_void_p(), C.c_void_p()
         _check(lib().pcd_ba_device_parameters(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    # ---- point elimination on the device (pcd_ba_schur*) ----
+    def _torch(self):
+        import torch
+        dev = torch.device("cuda", self.device)
+        return torch, dev, torch.cuda.current_stream(dev).cuda_stream
+
+    def schur_structure(self):
+        """co-visibility structure: dict(image_slot [I] int32 (-1 = constant pose), num_slots, pairs [num_pairs][2]
+        int32 slot pairs i < j sharing an eliminated point, ascending)"""
+        L = lib()
+        ns, npair = C.c_int32(0), C.c_uint64(0)
+        _check(L.pcd_ba_schur_structure(self._h, None, C.byref(ns), C.byref(npair), None, None))
+        slot = np.zeros(self.I, np.int32)
+        pi = np.zeros(max(npair.value, 1), np.int32)
+        pj = np.zeros(max(npair.value, 1), np.int32)
+        _check(L.pcd_ba_schur_structure(self._h, _vp(slot), C.byref(ns), C.byref(npair), _vp(pi), _vp(pj)))
+        n = npair.value
+        return dict(image_slot=slot, num_slots=ns.value, pairs=np.stack([pi[:n], pj[:n]], axis=1))
+
+    def schur_stats(self):
+        i = BASchurInfo()
+        _check(lib().pcd_ba_schur_stats(self._h, C.byref(i)))
+        return dict(build_ms=i.build_ms, num_entries=int(i.num_entries), scratch_bytes=int(i.scratch_bytes))
+
+    def schur(self, mu, damping="marquardt", dense=False, want=("cost", "S_diag", "S_off", "rhs", "num_skipped")):
+        """normal equations at the current parameters, points eliminated on the device: dict of torch device
+        tensors cost [1], S_diag [ns][6][6], S_off [num_pairs][6][6], rhs [ns][6], num_skipped [1] (int64) and, with
+        dense=True, S [6 ns][6 ns]"""
+        torch, dev, stream = self._torch()
+        if not hasattr(self, "_schur_dims"):
+            st = self.schur_structure()
+            self._schur_dims = (st["num_slots"], st["pairs"].shape[0])
+        ns, npair = self._schur_dims
+        f64 = dict(dtype=torch.float64, device=dev)
+        shapes = dict(cost=(1,), S_diag=(ns, 6, 6), S_off=(npair, 6, 6), rhs=(ns, 6), S=(6 * ns, 6 * ns))
+        out = {k: torch.empty(shapes[k], **f64) for k in want if k in shapes}
+        if "num_skipped" in want:
+            out["num_skipped"] = torch.zeros(1, dtype=torch.int64, device=dev)
+        if dense:
+            out["S"] = torch.empty(shapes["S"], **f64)
+        o = BASchurOut(*[_ptr(out.get(n)) for n, _ in BASchurOut._fields_])
+        opts = BASchurOpts(float(mu), _DAMPING[damping])
+        _check(lib().pcd_ba_schur_device(self._h, C.byref(opts), C.byref(o), C.c_void_p(stream)))
+        return out
+
+    def back_substitute(self, dpose, dpoint=None, model_decrease=True):
+        """point steps of the last schur() call for the pose step dpose [ns][6] (torch, device): returns
+        (dpoint [P][3], model decrease [1] or None)"""
+        torch, dev, stream = self._torch()
+        dpose = dpose.to(device=dev, dtype=torch.float64).contiguous()
+        if dpoint is None:
+            dpoint = torch.empty((self.P, 3), dtype=torch.float64, device=dev)
+        md = torch.empty(1, dtype=torch.float64, device=dev) if model_decrease else None
+        _check(lib().pcd_ba_schur_back_substitute_device(self._h, _ptr(dpose), _ptr(dpoint), _ptr(md), C.c_void_p(stream)))
+        return dpoint, md
+
+    def plus(self, dpose, dpoint, poses_out=None, points_out=None):
+        """candidate parameters (quaternion manifold Plus, t + dt, X + dX; constants copied) from the handle's current
+        ones: returns (poses [I][7], points [P][3]) torch device tensors"""
+        torch, dev, stream = self._torch()
+        dpose = dpose.to(device=dev, dtype=torch.float64).contiguous()
+        dpoint = dpoint.to(device=dev, dtype=torch.float64).contiguous()
+        if poses_out is None:
+            poses_out = torch.empty((self.I, 7), dtype=torch.float64, device=dev)
+        if points_out is None:
+            points_out = torch.empty((self.P, 3), dtype=torch.float64, device=dev)
+        _check(lib().pcd_ba_plus_device(self._h, _ptr(dpose), _ptr(dpoint), _ptr(poses_out), _ptr(points_out),
+                                        C.c_void_p(stream)))
+        return poses_out, points_out
+
+    def set_parameters_device(self, poses=None, points=None):
+        """device -> device parameter update from torch tensors (None keeps the old values)"""
+        _, _, stream = self._torch()
+        _check(lib().pcd_ba_set_parameters_device(self._h, _ptr(poses), _ptr(points), C.c_void_p(stream)))
+
+    def cost_device(self, out=None):
+        """cost at the current parameters (the residual-only pass) into a torch device tensor [1]"""
+        torch, dev, stream = self._torch()
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device=dev)
+        self.evaluate_device({"cost": out}, stream=stream)
+        return out
+
+
+def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", min_relative_decrease=1e-3,
+                max_radius=1e16):
+    """Device-resident Levenberg-Marquardt on a BA handle.  Each iteration: ba.schur (points eliminated on the
+    device), torch.linalg.cholesky of the dense reduced camera system (a failed factorisation counts as a rejected
+    step), back-substitution and plus into candidate buffers, the cost pass at the candidate, then Ceres' trust-region
+    rule: accept if rho = (cost - candidate cost) / model decrease > min_relative_decrease; on success
+    radius /= max(1/3, 1 - (2 rho - 1)^3) and the decrease factor resets to 2, on failure radius /= decrease factor
+    and the factor doubles.  mu = 1 / radius.
+
+    There is no Jacobi scaling of the columns (Ceres scales them by default), so the iterates are not Ceres' own
+    iterate for iterate; the step, model and radius rules are.  On return the handle holds the accepted parameters.
+    Returns a list with one dict per iteration: cost (before the step), candidate_cost, rho, accepted, radius (after
+    the update), num_skipped."""
+    import torch
+    dev = torch.device("cuda", ba.device)
+    zero_pose = torch.zeros((max(ba.schur_structure()["num_slots"], 1), 6), dtype=torch.float64, device=dev)
+    zero_pt = torch.zeros((ba.P, 3), dtype=torch.float64, device=dev)
+    acc_poses, acc_points = ba.plus(zero_pose, zero_pt)   # copy of the current parameters
+    cand_poses, cand_points = torch.empty_like(acc_poses), torch.empty_like(acc_points)
+    radius, decrease_factor = float(initial_radius), 2.0
+    history = []
+    for _ in range(int(max_iterations)):
+        out = ba.schur(1.0 / radius, damping=damping, dense=True, want=("cost", "rhs", "num_skipped"))
+        cost = float(out["cost"].item())
+        Lc, info = torch.linalg.cholesky_ex(out["S"])
+        rec = dict(cost=cost, candidate_cost=float("nan"), rho=float("nan"), accepted=False,
+                   num_skipped=int(out["num_skipped"].item()))
+        if int(info.item()) == 0:
+            dpose = torch.cholesky_solve(out["rhs"].reshape(-1, 1), Lc).reshape(-1, 6)
+            dpoint, md = ba.back_substitute(dpose)
+            ba.plus(dpose, dpoint, cand_poses, cand_points)
+            ba.set_parameters_device(cand_poses, cand_points)
+            new_cost = float(ba.cost_device().item())
+            model = float(md.item())
+            rho = (cost - new_cost) / model if model > 0 else float("-inf")
+            rec.update(candidate_cost=new_cost, rho=rho, accepted=bool(rho > min_relative_decrease))
+        if rec["accepted"]:
+            radius = min(max_radius, radius / max(1.0 / 3.0, 1.0 - (2.0 * rec["rho"] - 1.0) ** 3))
+            decrease_factor = 2.0
+            acc_poses, cand_poses = cand_poses, acc_poses
+            acc_points, cand_points = cand_points, acc_points
+        else:
+            ba.set_parameters_device(acc_poses, acc_points)
+            radius /= decrease_factor
+            decrease_factor *= 2.0
+        rec["radius"] = radius
+        history.append(rec)
+    torch.cuda.synchronize(dev)
+    return history

@@ -504,6 +504,63 @@ pcd_status pcd_ba_observation_errors(pcd_ba* ba, double* sq_err /*[O]*/, double*
 pcd_status pcd_ba_observation_errors_device(pcd_ba* ba, double* d_sq_err, double* d_depth, void* stream);
 /* device-side parameter pointers for zero-copy updates: [I][7] and [P][3] doubles */
 pcd_status pcd_ba_device_parameters(pcd_ba* ba, double** d_poses, double** d_points);
+/* device -> device parameter update on `stream` (NULL keeps the old values) */
+pcd_status pcd_ba_set_parameters_device(pcd_ba* ba, const double* d_poses, const double* d_points, void* stream);
+
+/* Point elimination on the device: one Levenberg-Marquardt step of the normal equations without the
+ * per-observation blocks leaving HBM.  Unknowns: the 6-dim pose tangents (3 quaternion-tangent + 3 tvec, the manifold
+ * of H_img) of the variable-pose images -- "slots", numbered in ascending image index -- then the 3-dim points.  The
+ * step solves (H + D) delta = -g with D on the pose and point diagonals:
+ *   PCD_DAMP_MARQUARDT  D_kk = mu * clamp(H_kk, 1e-6, 1e32)   (Ceres' LM form, mu = 1 / radius)
+ *   PCD_DAMP_LEVENBERG  D_kk = mu
+ * Every non-constant point is eliminated: V_p = H_pt[p] + D_p through a 3x3 Cholesky; a point whose V_p is not
+ * positive definite (possible with mu = 0) is skipped -- delta 0, no contribution -- and counted.  Reduced system:
+ *   S_ij  = delta_ij (U_i + D_i) - sum_p sum_{a in p,i; b in p,j} W_a V_p^-1 W_b^T
+ *   rhs_i = -g_i + sum_{a in i} W_a V_p(a)^-1 g_p(a)
+ * Constant-pose images have no slot; constant-tvec components are inactive (identity rows / columns of S, rhs 0,
+ * delta 0); constant points get delta 0.  No atomics, fixed-order sums: bitwise reproducible run to run.
+ * Guards of every entry point below, before anything is allocated or launched: no gfx950 device -> NO_DEVICE; a
+ * capturing stream -> UNSUPPORTED (as every _device call); a handle with some camera_refine byte set -> UNSUPPORTED
+ * (the camera rows are not part of the reduced system).  All scratch is owned by the handle (freed by
+ * pcd_ba_destroy); the co-visibility structure is built on the first call (host counting sorts, build_ms). */
+typedef enum { PCD_DAMP_MARQUARDT = 0, PCD_DAMP_LEVENBERG = 1 } pcd_ba_damping;
+typedef struct {
+  double mu;          /* >= 0 */
+  int32_t damping;    /* pcd_ba_damping */
+  int32_t reserved[7];
+} pcd_ba_schur_opts;
+/* every pointer may be NULL (not written); ns = num_slots, n = 6 ns */
+typedef struct {
+  double* cost;            /* [1] cost at the current parameters (per-track sum, as pcd_ba_evaluate with H_pt) */
+  double* S_diag;          /* [ns][6][6]                                                                       */
+  double* S_off;           /* [num_pairs][6][6] block (pair_i[q], pair_j[q]), pair_i < pair_j                   */
+  double* rhs;             /* [ns][6]                                                                          */
+  double* S;               /* [n][n] dense, row-major, both triangles (for a direct Cholesky)                 */
+  uint64_t* num_skipped;   /* [1] eliminated points whose damped V was not positive definite                  */
+} pcd_ba_schur_out;
+/* Co-visibility structure (host query): image_slot [I] (-1 = constant pose), the number of slots, and the slot pairs
+ * i < j that share an eliminated point, ascending (i, j).  Every output may be NULL (size the buffers first). */
+pcd_status pcd_ba_schur_structure(pcd_ba* ba, int32_t* image_slot, int32_t* num_slots, uint64_t* num_pairs,
+                                  int32_t* pair_i, int32_t* pair_j);
+/* Normal-equation pass at the current parameters into handle scratch, then the elimination. */
+pcd_status pcd_ba_schur_device(pcd_ba* ba, const pcd_ba_schur_opts* opts, const pcd_ba_schur_out* d_out, void* stream);
+pcd_status pcd_ba_schur(pcd_ba* ba, const pcd_ba_schur_opts* opts, const pcd_ba_schur_out* out);   /* host outputs */
+/* delta X_p = -V_p^-1 (g_p + sum_{a in p} W_a^T dpose[slot(a)]) from the state of the last Schur call (INVALID
+ * without one); d_dpoint [P][3] (0 for constant / skipped points).  d_model_decrease (may be NULL): [1]
+ * 1/2 (-delta^T g + delta^T D delta), the decrease of the LM model, summed in a fixed order. */
+pcd_status pcd_ba_schur_back_substitute_device(pcd_ba* ba, const double* d_dpose /*[ns][6]*/, double* d_dpoint,
+                                               double* d_model_decrease, void* stream);
+/* Candidate parameters: Ceres' QuaternionManifold::Plus on the quaternion, t + dt on the variable tvec components,
+ * X + dX on the non-constant points, copies of everything constant.  Reads the handle's current parameters; the
+ * outputs may be the handle's own buffers (pcd_ba_device_parameters). */
+pcd_status pcd_ba_plus_device(pcd_ba* ba, const double* d_dpose /*[ns][6]*/, const double* d_dpoint /*[P][3]*/,
+                              double* d_poses_out /*[I][7]*/, double* d_points_out /*[P][3]*/, void* stream);
+typedef struct {
+  double build_ms;          /* host time of the structure build (0: not built yet) */
+  uint64_t num_entries;     /* (a, b) observation pairs of all blocks              */
+  uint64_t scratch_bytes;   /* device memory the elimination holds in the handle   */
+} pcd_ba_schur_info;
+pcd_status pcd_ba_schur_stats(pcd_ba* ba, pcd_ba_schur_info* info);
 
 /* ------------------------------------------------------------------------
  * Exact SIFT descriptor matching (stretch row a19)

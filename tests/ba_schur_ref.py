@@ -1,0 +1,289 @@
+"""numpy reference of the device point elimination (pcd_ba_schur*), built from the oracle's block-form
+normal equations (oracle.BA(...).normal_equations(want_w=True)).
+
+Two independent routes to the LM step of (H + D) delta = -g:
+  dense_solve     the full damped system (pose tangents of the variable images, then the points) by numpy.linalg.solve;
+  schur_blocks    S / rhs formed block by block from the same blocks (per point and image: Z_pi = sum of W_a), then
+                  back_substitute for the points.
+plus implements Ceres' QuaternionManifold::Plus; lm runs the trust-region loop of pcdhip.ba_solve_lm on the oracle.
+Test infrastructure: small scenes only (dense matrices, Python loops over pairs)."""
+import numpy as np
+
+DIAG_MIN, DIAG_MAX = 1e-6, 1e32
+
+
+def damping(h_diag, mu, mode):
+    """mode 'marquardt': mu * clamp(H_kk, 1e-6, 1e32); 'levenberg': mu"""
+    if mode == "marquardt":
+        return mu * np.clip(h_diag, DIAG_MIN, DIAG_MAX)
+    return np.full_like(h_diag, mu)
+
+
+def problem(scene):
+    """constness of the scene dict (pcdhip.BA / oracle.BA keyword arguments) with the defaults filled in"""
+    I, P = np.asarray(scene["poses"]).reshape(-1, 7).shape[0], np.asarray(scene["points"]).reshape(-1, 3).shape[0]
+    cpose = np.zeros(I, np.uint8) if scene.get("image_const_pose") is None else np.asarray(scene["image_const_pose"], np.uint8)
+    ctvec = np.zeros(I, np.uint8) if scene.get("image_const_tvec") is None else np.asarray(scene["image_const_tvec"], np.uint8)
+    cpt = np.zeros(P, np.uint8) if scene.get("point_const") is None else np.asarray(scene["point_const"], np.uint8)
+    slot = np.full(I, -1, np.int64)
+    var = np.flatnonzero(cpose == 0)
+    slot[var] = np.arange(var.size)
+    active = np.ones((var.size, 6), bool)          # constant-tvec components are inactive coordinates
+    for k in range(3):
+        active[:, 3 + k] = ((ctvec[var] >> k) & 1) == 0
+    return dict(I=I, P=P, slot=slot, slot_img=var, active=active, point_const=cpt,
+                obs_image=np.asarray(scene["obs_image"], np.int64), obs_point=np.asarray(scene["obs_point"], np.int64))
+
+
+def point_inverse(Hpt, Dpt, point_const):
+    """V_p^-1 through the same 3x3 Cholesky as the device (a pivot <= 0 -> skipped, V^-1 = 0); constant points: 0"""
+    A = Hpt + Dpt[:, :, None] * np.eye(3)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ok = A[:, 0, 0] > 0
+        l00 = np.sqrt(np.where(ok, A[:, 0, 0], 1.0))
+        l10, l20 = A[:, 0, 1] / l00, A[:, 0, 2] / l00
+        t1 = A[:, 1, 1] - l10 * l10
+        ok &= t1 > 0
+        l11 = np.sqrt(np.where(ok, t1, 1.0))
+        l21 = (A[:, 1, 2] - l20 * l10) / l11
+        t2 = A[:, 2, 2] - l20 * l20 - l21 * l21
+        ok &= t2 > 0
+        l22 = np.sqrt(np.where(ok, t2, 1.0))
+    L = np.zeros_like(A)
+    L[:, 0, 0], L[:, 1, 0], L[:, 2, 0], L[:, 1, 1], L[:, 2, 1], L[:, 2, 2] = l00, l10, l20, l11, l21, l22
+    elim = point_const == 0
+    good = ok & elim
+    Vinv = np.zeros_like(A)
+    if good.any():
+        M = np.linalg.inv(L[good])
+        Vinv[good] = np.einsum("pki,pkj->pij", M, M)
+    return Vinv, elim & ~ok
+
+
+class NormalEquations:
+    """the oracle's blocks of one scene at its parameters, with the damping of (mu, mode) applied"""
+
+    def __init__(self, oracle, scene, mu, mode="marquardt"):
+        self.pr = problem(scene)
+        ob = oracle.BA(**scene)
+        self.cost, self.Himg, self.gimg, self.Hpt, self.gpt, self.W = ob.normal_equations(want_w=True)
+        pr = self.pr
+        self.Dimg = damping(np.diagonal(self.Himg, axis1=1, axis2=2)[pr["slot_img"]], mu, mode) * pr["active"]
+        self.Dpt = damping(np.diagonal(self.Hpt, axis1=1, axis2=2), mu, mode)
+        self.Vinv, self.skipped = point_inverse(self.Hpt, self.Dpt, pr["point_const"])
+        s = pr["slot"][pr["obs_image"]]
+        # observations that take part: variable pose, eliminated (non-constant, non-skipped) point
+        self.elig = (s >= 0) & (pr["point_const"][pr["obs_point"]] == 0) & ~self.skipped[pr["obs_point"]]
+        self.obs_slot = s
+        # the co-visibility structure does not depend on the numbers: skipped points still define pairs (zero blocks)
+        self.struct_elig = (s >= 0) & (pr["point_const"][pr["obs_point"]] == 0)
+
+    # ---- route 1: the whole damped system ----
+    def dense_solve(self):
+        A, b, ns, pts = self.dense_system()
+        x = np.linalg.solve(A, b)
+        dpoint = np.zeros((self.pr["P"], 3))
+        dpoint[pts] = x[6 * ns:].reshape(-1, 3)
+        return x[:6 * ns].reshape(ns, 6), dpoint
+
+    def dense_vector(self, dpose, dpoint):
+        """(dpose, dpoint) in the unknown order of dense_system"""
+        _, _, ns, pts = self._layout()
+        return np.concatenate([np.asarray(dpose).reshape(-1), np.asarray(dpoint)[pts].reshape(-1)])
+
+    def _layout(self):
+        pr = self.pr
+        pts = np.flatnonzero((pr["point_const"] == 0) & ~self.skipped)
+        return None, None, pr["slot_img"].size, pts
+
+    def dense_system(self):
+        """(A, b, ns, eliminated points): (H + D) over the pose tangents of the variable images, then the points"""
+        pr = self.pr
+        ns, P = pr["slot_img"].size, pr["P"]
+        pts = np.flatnonzero((pr["point_const"] == 0) & ~self.skipped)
+        col = np.full(P, -1, np.int64)
+        col[pts] = 6 * ns + 3 * np.arange(pts.size)
+        n = 6 * ns + 3 * pts.size
+        A = np.zeros((n, n))
+        b = np.zeros(n)
+        for i, im in enumerate(pr["slot_img"]):
+            A[6 * i:6 * i + 6, 6 * i:6 * i + 6] = self.Himg[im] + np.diag(self.Dimg[i])
+            b[6 * i:6 * i + 6] = -self.gimg[im]
+        for p in pts:
+            c = col[p]
+            A[c:c + 3, c:c + 3] = self.Hpt[p] + np.diag(self.Dpt[p])
+            b[c:c + 3] = -self.gpt[p]
+        for a in np.flatnonzero(self.elig):
+            i, c = 6 * self.obs_slot[a], col[pr["obs_point"][a]]
+            A[i:i + 6, c:c + 3] += self.W[a]
+            A[c:c + 3, i:i + 6] += self.W[a].T
+        for i in range(ns):                          # inactive coordinates: identity rows / columns, rhs 0
+            for k in np.flatnonzero(~pr["active"][i]):
+                r = 6 * i + k
+                A[r, :] = 0.0; A[:, r] = 0.0; A[r, r] = 1.0; b[r] = 0.0
+        return A, b, ns, pts
+
+    # ---- route 2: block by block ----
+    def _z(self, pts=None):
+        """Z[(p, slot)] = sum of W_a over the eliminated observations of point p in that slot's image"""
+        pr = self.pr
+        Z = {}
+        for a in np.flatnonzero(self.elig):
+            p = int(pr["obs_point"][a])
+            if pts is not None and p not in pts:
+                continue
+            key = (p, int(self.obs_slot[a]))
+            Z[key] = Z.get(key, 0.0) + self.W[a]
+        return Z
+
+    def schur_blocks(self):
+        """dict(S_diag [ns][6][6], S_off {(i, j): 6x6} for i < j, pairs (ascending), rhs [ns][6], S dense)"""
+        pr = self.pr
+        ns = pr["slot_img"].size
+        Z = self._z()
+        by_point = {}
+        for (p, i), z in Z.items():
+            by_point.setdefault(p, []).append((i, z))
+        Sd = np.stack([self.Himg[im] + np.diag(self.Dimg[i]) for i, im in enumerate(pr["slot_img"])]) if ns else \
+            np.zeros((0, 6, 6))
+        rhs = -self.gimg[pr["slot_img"]].copy()
+        off = {}
+        for p, lst in by_point.items():
+            Vi, vg = self.Vinv[p], self.Vinv[p] @ self.gpt[p]
+            for i, zi in lst:
+                rhs[i] += zi @ vg
+                for j, zj in lst:
+                    blk = zi @ Vi @ zj.T
+                    if i == j:
+                        Sd[i] -= blk
+                    elif i < j:
+                        off[(i, j)] = off.get((i, j), 0.0) - blk
+        st = {}
+        for a in np.flatnonzero(self.struct_elig):
+            st.setdefault(int(pr["obs_point"][a]), set()).add(int(self.obs_slot[a]))
+        for sl in st.values():
+            sl = sorted(sl)
+            for k, i in enumerate(sl):
+                for j in sl[k + 1:]:
+                    off.setdefault((i, j), np.zeros((6, 6)))
+        self._mask(Sd, off, rhs)
+        pairs = sorted(off)
+        S = np.zeros((6 * ns, 6 * ns))
+        for i in range(ns):
+            S[6 * i:6 * i + 6, 6 * i:6 * i + 6] = Sd[i]
+        for (i, j) in pairs:
+            S[6 * i:6 * i + 6, 6 * j:6 * j + 6] = off[(i, j)]
+            S[6 * j:6 * j + 6, 6 * i:6 * i + 6] = off[(i, j)].T
+        return dict(S_diag=Sd, S_off=off, pairs=np.array(pairs, np.int64).reshape(-1, 2), rhs=rhs, S=S)
+
+    def _mask(self, Sd, off, rhs):
+        act = self.pr["active"]
+        for i in range(Sd.shape[0]):
+            for k in np.flatnonzero(~act[i]):
+                Sd[i][k, :] = 0.0; Sd[i][:, k] = 0.0; Sd[i][k, k] = 1.0; rhs[i][k] = 0.0
+        for (i, j), blk in off.items():
+            blk[~act[i], :] = 0.0
+            blk[:, ~act[j]] = 0.0
+
+    def pair_block(self, i, j):
+        """one block of S (i <= j) without forming the others: the config-B-sized check"""
+        pr = self.pr
+        ims = pr["slot_img"]
+        ob_i = np.flatnonzero(self.elig & (pr["obs_image"] == ims[i]))
+        ob_j = np.flatnonzero(self.elig & (pr["obs_image"] == ims[j]))
+        common = set(pr["obs_point"][ob_i].tolist()) & set(pr["obs_point"][ob_j].tolist())
+        acc = np.zeros((6, 6))
+        for p in common:
+            zi = self.W[ob_i[pr["obs_point"][ob_i] == p]].sum(0)
+            zj = self.W[ob_j[pr["obs_point"][ob_j] == p]].sum(0)
+            acc += zi @ self.Vinv[p] @ zj.T
+        act = pr["active"]
+        if i == j:
+            blk = self.Himg[ims[i]] + np.diag(self.Dimg[i]) - acc
+            for k in np.flatnonzero(~act[i]):
+                blk[k, :] = 0.0; blk[:, k] = 0.0; blk[k, k] = 1.0
+            return blk
+        blk = -acc
+        blk[~act[i], :] = 0.0
+        blk[:, ~act[j]] = 0.0
+        return blk
+
+    def back_substitute(self, dpose):
+        pr = self.pr
+        r = self.gpt.copy()
+        for a in np.flatnonzero(self.elig):
+            r[pr["obs_point"][a]] += self.W[a].T @ dpose[self.obs_slot[a]]
+        return -np.einsum("pij,pj->pi", self.Vinv, r)
+
+    def model_decrease(self, dpose, dpoint):
+        """1/2 (-delta^T g + delta^T D delta) over the active pose coordinates and the points"""
+        pr = self.pr
+        dp = np.where(pr["active"], dpose, 0.0)
+        g = self.gimg[pr["slot_img"]]
+        t = np.sum(-dp * g + self.Dimg * dp * dp) + np.sum(-dpoint * self.gpt + self.Dpt * dpoint * dpoint)
+        return 0.5 * t
+
+
+def quat_plus(q, d):
+    """Ceres QuaternionManifold::Plus: [cos|d|, sin|d|/|d| d] * q (q = w x y z)"""
+    nd = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    if nd == 0.0:
+        return np.array(q, np.float64)
+    s = np.sin(nd) / nd
+    a = np.array([np.cos(nd), s * d[0], s * d[1], s * d[2]])
+    return np.array([a[0] * q[0] - a[1] * q[1] - a[2] * q[2] - a[3] * q[3],
+                     a[0] * q[1] + a[1] * q[0] + a[2] * q[3] - a[3] * q[2],
+                     a[0] * q[2] - a[1] * q[3] + a[2] * q[0] + a[3] * q[1],
+                     a[0] * q[3] + a[1] * q[2] - a[2] * q[1] + a[3] * q[0]])
+
+
+def plus(scene, dpose, dpoint):
+    """candidate (poses [I][7], points [P][3]): constant poses, tvec components and points are copied"""
+    pr = problem(scene)
+    poses = np.array(scene["poses"], np.float64).reshape(-1, 7).copy()
+    points = np.array(scene["points"], np.float64).reshape(-1, 3).copy()
+    for i, im in enumerate(pr["slot_img"]):
+        poses[im, :4] = quat_plus(poses[im, :4], dpose[i, :3])
+        for k in range(3):
+            if pr["active"][i, 3 + k]:
+                poses[im, 4 + k] += dpose[i, 3 + k]
+    var = pr["point_const"] == 0
+    points[var] += dpoint[var]
+    return poses, points
+
+
+def lm(oracle, scene, max_iterations, initial_radius=1e4, mode="marquardt", min_relative_decrease=1e-3,
+       max_radius=1e16):
+    """pcdhip.ba_solve_lm's loop on the oracle (Cholesky of the block-wise S).  Returns (history, final scene)."""
+    scene = dict(scene)
+    radius, factor = float(initial_radius), 2.0
+    hist = []
+    for _ in range(max_iterations):
+        ne = NormalEquations(oracle, scene, 1.0 / radius, mode)
+        sb = ne.schur_blocks()
+        rec = dict(cost=ne.cost, candidate_cost=np.nan, rho=np.nan, accepted=False)
+        try:
+            Lc = np.linalg.cholesky(sb["S"])
+        except np.linalg.LinAlgError:
+            Lc = None
+        cand = None
+        if Lc is not None:
+            y = np.linalg.solve(Lc, sb["rhs"].reshape(-1))
+            dpose = np.linalg.solve(Lc.T, y).reshape(-1, 6)
+            dpoint = ne.back_substitute(dpose)
+            model = ne.model_decrease(dpose, dpoint)
+            poses, points = plus(scene, dpose, dpoint)
+            cand = dict(scene, poses=poses, points=points)
+            new_cost = oracle.BA(**cand).normal_equations()[0]
+            rho = (ne.cost - new_cost) / model if model > 0 else -np.inf
+            rec.update(candidate_cost=new_cost, rho=rho, accepted=bool(rho > min_relative_decrease))
+        if rec["accepted"]:
+            radius = min(max_radius, radius / max(1.0 / 3.0, 1.0 - (2.0 * rec["rho"] - 1.0) ** 3))
+            factor = 2.0
+            scene = cand
+        else:
+            radius /= factor
+            factor *= 2.0
+        rec["radius"] = radius
+        hist.append(rec)
+    return hist, scene

@@ -1,0 +1,139 @@
+"""Timing of the device point elimination (pcd_ba_schur*) part by part, at workload M (bench.py's BA scene,
+1000 images / 1 M points / 4.72 M observations) and at config B's size (450 images / 400 k points / 1.87 M observations).
+
+  python tools/ba_schur_probe.py [--out profiles/ba_schur_probe.txt] [--reps 15] [--only M|B]
+
+Parts: structure build (host counting sorts, once per handle), normal-equation pass, elimination, dense fill,
+torch.linalg.cholesky + solve, back-substitution + plus, cost pass, a whole LM iteration of pcdhip.ba_solve_lm.
+Device parts are timed with the library's per-scope hipEvents (pcdhip.profile_*), host-driven parts with
+torch.cuda.Event pairs; warm-up first, then the median (and min / max) of --reps runs."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "colmap-pcd_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import pcdhip  # noqa: E402
+from pcdhip import synth  # noqa: E402
+
+SCENES = {"M": (1000, 1_000_000), "B": (450, 400_000)}
+
+
+def stats(v):
+    v = np.asarray(v)
+    return "median %8.3f ms   min %8.3f   max %8.3f   (n=%d)" % (np.median(v), v.min(), v.max(), v.size)
+
+
+def scoped(ba, fn, scope, reps):
+    """library scope timings (hipEvents around the scope's launches) of `reps` calls of fn after one warm-up"""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        pcdhip.profile_reset()
+        pcdhip.profile_enable(True)
+        fn()
+        torch.cuda.synchronize()
+        t = pcdhip.profile_get()
+        pcdhip.profile_enable(False)
+        out.append(sum(ms for name, (_, ms) in t.items() if name == scope))
+    return out
+
+
+def evented(fn, reps, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return out
+
+
+def probe(tag, reps, log):
+    cams, pts = SCENES[tag]
+    scene = synth.ba_scene(cams, pts, seed=11, order="image")
+    ba = pcdhip.BA(**scene)
+    log("== %s: %d images, %d points, %d observations, %d LiDAR terms" % (tag, ba.I, ba.P, ba.O, ba.L))
+    t0 = time.perf_counter()
+    st = ba.schur_structure()
+    wall = (time.perf_counter() - t0) * 1e3
+    info = ba.schur_stats()
+    ns, npair = st["num_slots"], len(st["pairs"])
+    log("structure build (host, once per handle): %.1f ms (library) / %.1f ms (call); %d slots, %d pairs, %d entries"
+        % (info["build_ms"], wall, ns, npair, info["num_entries"]))
+    mu = 1e-4
+    ba.schur(mu, dense=True)     # allocates the scratch
+    torch.cuda.synchronize()
+    log("device memory held by the elimination: %.1f MB (dense S %.1f MB, caller-owned)"
+        % (ba.schur_stats()["scratch_bytes"] / 1e6, 36.0 * ns * ns * 8 / 1e6))
+    r = {}
+    r["normal-equation pass"] = scoped(ba, lambda: ba.schur(mu), "ba_schur_normal", reps)
+    r["elimination"] = scoped(ba, lambda: ba.schur(mu), "ba_schur_eliminate", reps)
+    r["dense fill"] = scoped(ba, lambda: ba.schur(mu, dense=True), "ba_schur_dense", reps)
+    out = ba.schur(mu, dense=True)
+    S, rhs = out["S"], out["rhs"].reshape(-1, 1)
+
+    def chol():
+        L, info_ = torch.linalg.cholesky_ex(S)
+        return torch.cholesky_solve(rhs, L)
+    r["cholesky + solve (torch)"] = evented(chol, reps)
+    dpose = chol().reshape(-1, 6)
+    dpoint = torch.empty((ba.P, 3), dtype=torch.float64, device="cuda")
+    md = torch.empty(1, dtype=torch.float64, device="cuda")
+    cp = torch.empty((ba.I, 7), dtype=torch.float64, device="cuda")
+    cx = torch.empty((ba.P, 3), dtype=torch.float64, device="cuda")
+
+    def back_plus():
+        ba.back_substitute(dpose, dpoint)
+        ba.plus(dpose, dpoint, cp, cx)
+    r["back-substitution + plus"] = evented(back_plus, reps)
+    cost = torch.empty(1, dtype=torch.float64, device="cuda")
+    r["cost pass"] = evented(lambda: ba.cost_device(cost), reps)
+    keep = scene["poses"].copy(), scene["points"].copy()
+
+    def lm_iter():
+        ba.set_parameters(*keep)          # every run starts from the same parameters (a host upload, not timed below)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        pcdhip.ba_solve_lm(ba, max_iterations=1)
+        return (time.perf_counter() - t) * 1e3
+    lm_iter()
+    r["whole LM iteration (wall, incl. host syncs)"] = [lm_iter() for _ in range(reps)]
+    for k, v in r.items():
+        log("  %-44s %s" % (k, stats(v)))
+    ba.close()
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--only", choices=sorted(SCENES), default=None)
+    a = ap.parse_args()
+    lines = []
+
+    def log(s):
+        print(s, flush=True)
+        lines.append(s)
+    log("# tools/ba_schur_probe.py on %s, torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    for tag in ([a.only] if a.only else ["M", "B"]):
+        probe(tag, a.reps, log)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

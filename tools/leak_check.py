@@ -29,6 +29,9 @@ for r in range(rounds):
     pj = pcdhip.Projector(c); pj.set_new_images(imgs, feat); pj.close()
     c.close()
     ba = pcdhip.BA(**scene); ba.evaluate(("cost", "H_img", "g_img", "H_pt", "g_pt", "W")); ba.evaluate(("residuals", "jac_q")); ba.close()
+    ba = pcdhip.BA(**scene); so = ba.schur(1e-3, dense=True)      # point elimination: structure + scratch per handle
+    dp = torch.linalg.solve(so["S"], so["rhs"].reshape(-1)).reshape(-1, 6)
+    ba.back_substitute(dp); del so, dp; ba.close()
     pcdhip.sift_match(d1, d1[::-1].copy()); pcdhip.sift_match_batch([d1, d1[:300]], [(0, 1), (1, 0)])
     u = used()
     if r == 2:
