@@ -39,6 +39,7 @@ struct PyramidParams {
   int nlev;                       // >= 2
   int dims[kMaxPyrLevels][3];
   uint32_t off[kMaxPyrLevels];    // node offset of each level
+  int seed_dims[3];               // lattice of the fallback's seed table: 8x8x8-cell cubes (nn.hip fb_seed_table)
 };
 
 struct QueryScratch;  // nn.hip

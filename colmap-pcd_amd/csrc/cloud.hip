@@ -355,6 +355,7 @@ static pcd_status build_grid(pcd_cloud* c, float user_h, hipStream_t s) {
     set_error("grid too large for %d pyramid levels", kMaxPyrLevels);
     return PCD_ERR_UNSUPPORTED;
   }
+  for (int d = 0; d < 3; ++d) py.seed_dims[d] = (g.dims[d] + 7) / 8;   // (cell >> 3 for every cell of the grid)
   py.dims[py.nlev][0] = py.dims[py.nlev][1] = py.dims[py.nlev][2] = 1;   // the virtual top
   py.off[py.nlev] = (uint32_t)total_nodes;
   py.nlev++;

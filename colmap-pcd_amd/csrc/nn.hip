@@ -24,7 +24,9 @@
 //                    (level 0 = leaves of 2x2x2 cells, one contiguous point range each;
 //                    a virtual top over the first level with <= 64 nodes), the 64
 //                    children of a node one per lane, pruned with the exact float
-//                    lower bound.  Exact for any query position, also outside the grid.
+//                    lower bound.  Exact for any query position, also outside the grid.  The walk starts
+//                    from min(incoming key, key of the query's SEED): the exact nearest cloud point of the centre
+//                    of the query's 8x8x8-cell cube (a table built once per cloud, fb_seed_table).
 // Query bookkeeping in front of k_nn_brick: a two-level counting sort on the brick id
 // (k_bk_slots, k_bk_scatter, k_bk_count, k_bk_emit) that yields the brick-sorted query
 // records and the work items; queries with no cloud point in their brick's halo go
@@ -42,6 +44,12 @@
 //     (grid.slack = 9.6e-7 * max(extent, |coord|) >= 4 roundings of 2^-24),
 //     and its float distance is >= true^2 * (1 - 2.4e-7).  A result is final
 //     iff best < (margin - slack)^2 * (1 - 1e-6), margin > slack.
+//   * seed: the seed is a point of this cloud and its key is computed with the walk's own arithmetic
+//     (l2_simple3 on the float query, make_key with the point's global index), so min(best, seed key) is the key
+//     of a real candidate -- exactly what a leaf scan that met the point would have left.  The walk's pruning only
+//     ever compares bounds with the current best, whatever produced it, so no bound argument is needed: the result
+//     is the minimum over the cloud as before.  Ties: a point at the seed's distance with a lower index lies in a
+//     block with lb <= best, which is not skipped.
 #include <cstring>  // rocprim's texture_cache_iterator.hpp needs memset declared first
 
 #include <rocprim/rocprim.hpp>
@@ -720,6 +728,7 @@ template <int FUSED>
 __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams py, const float4* __restrict__ sorted,
                                                       const uint32_t* __restrict__ cell_start,
                                                       const float* __restrict__ aabb,
+                                                      const float4* __restrict__ seeds,
                                                       const float4* __restrict__ qf4,
                                                       const uint32_t* __restrict__ list,  // NULL: queries 0..count-1
                                                       const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
@@ -763,6 +772,18 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
       best = FUSED == 2 ? bounded_init_key(fu.max_range ? fu.max_range[fu.mr_count == 1 ? 0 : qi] : fu.fixed_range,
                                              fu.q[3 * (size_t)qi], fu.q[3 * (size_t)qi + 1], fu.q[3 * (size_t)qi + 2])
                           : kKeyInit;
+    }
+    {
+      // seed bound (fb_seed_table): the point of the query's 8x8x8-cell cube -- of the nearest cube for a query
+      // outside the grid -- as a candidate before the walk.  Far outliers no longer start from kKeyInit, and the first
+      // leaves the walk meets are pruned against a distance near the true one (tools/fb_walk_sim.py).  The load
+      // does not depend on the first expansion's and goes out beside it.
+      const int sx = cell_coord(qx, g.origin[0], g.inv_h, g.dims[0]) >> 3;
+      const int sy = cell_coord(qy, g.origin[1], g.inv_h, g.dims[1]) >> 3;
+      const int sz = cell_coord(qz, g.origin[2], g.inv_h, g.dims[2]) >> 3;
+      const float4 sp = seeds[((size_t)sz * py.seed_dims[1] + sy) * py.seed_dims[0] + sx];
+      const uint64_t sk = make_key(l2_simple3(qx, qy, qz, sp.x, sp.y, sp.z), __float_as_uint(sp.w));
+      best = sk < best ? sk : best;
     }
     // The state of the level being iterated lives in REGISTERS (the children's bounds one per lane, the mask of the
     // children still to visit in an SGPR pair, the node in SGPRs); the LDS arrays are a stack touched only when the walk
@@ -956,6 +977,56 @@ static pcd_status brick_slots(pcd_cloud* c, QueryScratch* sc, const BrickParams&
   return PCD_OK;
 }
 
+// Seed table of k_nn_fallback (per cloud, built once, on first use like the slot table): for every cube of 8x8x8 cells
+// (py.seed_dims; = the level-1 nodes of the pyramid) the record {x, y, z, bits(global index)} of the exact nearest cloud
+// point to the cube's centre, found by the library's own exact search (k_nn_fallback over the centres, every seed still
+// the sentinel {+inf, +inf, +inf, 0}: its key (inf, 0) is above kKeyInit and changes no minimum).  74 k cubes for
+// workload M's grid: a fallback batch of far queries, about a millisecond.
+__global__ void k_seed_init(GridParams g, int sdx, int sdy, int sdz, float4* __restrict__ seeds, float4* __restrict__ qf4,
+                            uint64_t* __restrict__ keys) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= (uint64_t)sdx * sdy * sdz) return;
+  const int x = (int)(i % sdx), y = (int)((i / sdx) % sdy), z = (int)(i / ((uint64_t)sdx * sdy));
+  seeds[i] = make_float4(INFINITY, INFINITY, INFINITY, 0.f);
+  // the centre of the cube's part inside the grid (any position would do: the seed only has to be a real point)
+  const float cx = 0.5f * (float)(8 * x + min(8 * x + 8, g.dims[0])), cy = 0.5f * (float)(8 * y + min(8 * y + 8, g.dims[1])),
+              cz = 0.5f * (float)(8 * z + min(8 * z + 8, g.dims[2]));
+  qf4[i] = make_float4(g.origin[0] + cx * g.h, g.origin[1] + cy * g.h, g.origin[2] + cz * g.h, 1.f);
+  keys[i] = kKeyInit;
+}
+__global__ void k_seed_gather(const uint64_t* __restrict__ keys, uint64_t n, ShardIndex si, const float4* __restrict__ pts4,
+                              float4* __restrict__ seeds) {
+  const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t k = keys[i];
+  const uint64_t row = k == PCD_KEY_NONE ? ~0ull : shard_local_row(si, (uint32_t)k);
+  if (row == ~0ull) return;   // nothing found (distances beyond FLT_MAX): the sentinel stays
+  const float4 p = pts4[row];
+  seeds[i] = make_float4(p.x, p.y, p.z, __uint_as_float((uint32_t)k));
+}
+static pcd_status fb_seed_table(pcd_cloud* c, QueryScratch* sc, hipStream_t s) {
+  if (sc->fb_seed_ok) return PCD_OK;
+  const PyramidParams& py = c->pyr;
+  const uint64_t n = (uint64_t)py.seed_dims[0] * py.seed_dims[1] * py.seed_dims[2];
+  DevBuf<float4> qf4;
+  DevBuf<uint64_t> keys;
+  DevBuf<float4>& seeds = sc->fb_seed;
+  PCD_TRY(seeds.reserve(n));
+  PCD_TRY(qf4.reserve(n));
+  PCD_TRY(keys.reserve(n));
+  hipLaunchKernelGGL(k_seed_init, dim3(div_up(n, 256)), dim3(256), 0, s, c->grid, py.seed_dims[0], py.seed_dims[1],
+                     py.seed_dims[2], seeds.p, qf4.p, keys.p);
+  hipLaunchKernelGGL(k_nn_fallback<0>, dim3((unsigned)std::min<uint64_t>(div_up(n, 4), g_fb_max_blocks)), dim3(256), 0, s,
+                     c->grid, py, c->sorted.p, c->cell_start.p, c->blk_aabb.p, (const float4*)seeds.p, qf4.p,
+                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)n, keys.p, (NnCounters*)nullptr, 0,
+                     FbFused{nullptr, nullptr, 0, 0.0});
+  hipLaunchKernelGGL(k_seed_gather, dim3(div_up(n, 256)), dim3(256), 0, s, keys.p, n, c->shard_index(), c->pts4.p, seeds.p);
+  PCD_HIP_TRY(hipGetLastError());
+  PCD_HIP_TRY(hipStreamSynchronize(s));   // one-off per cloud; qf4 / keys go out of scope
+  sc->fb_seed_ok = true;
+  return PCD_OK;
+}
+
 template <int G>
 static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t* d_keys, hipStream_t s, bool refine) {
   const GridParams& g = c->grid;
@@ -1047,7 +1118,7 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
                        &sc->counters.p->fb_count, sc->fb_dense.p, &sc->counters.p->pad[0]);
     const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(Q, 4), g_fb_max_blocks);
     hipLaunchKernelGGL(k_nn_fallback<0>, dim3(blocks), dim3(256), 0, s, g, c->pyr, c->sorted.p, c->cell_start.p,
-                       c->blk_aabb.p, sc->qf4.p, sc->fb_dense.p, &sc->counters.p->pad[0], 0u, d_keys,
+                       c->blk_aabb.p, sc->fb_seed.p, sc->qf4.p, sc->fb_dense.p, &sc->counters.p->pad[0], 0u, d_keys,
                        sc->counters.p, collect_stats, FbFused{nullptr, nullptr, 0, 0.0});
   }
   return PCD_OK;
@@ -1070,6 +1141,7 @@ static pcd_status nn_device(pcd_cloud* c, const double* d_q, uint64_t Q, int alg
   // finalised keys, so the per-call latency is one kernel instead of prepare + memset + search + finalize.
   const bool one_launch = c->m > 0 && !refine &&
                           (algo == PCD_NN_FALLBACK_ONLY || (algo == PCD_NN_AUTO && Q <= kSmallBatch));
+  if (c->m > 0 && algo != PCD_NN_BRUTEFORCE) PCD_TRY(fb_seed_table(c, sc, s));
   if (one_launch) {
     PCD_TRY(sc->counters.reserve(1));
     if (collect_stats) PCD_HIP_TRY(hipMemsetAsync(sc->counters.p, 0, sizeof(NnCounters), s));
@@ -1078,11 +1150,11 @@ static pcd_status nn_device(pcd_cloud* c, const double* d_q, uint64_t Q, int alg
     const FbFused fu{d_q, bound ? bound->d_max_range : nullptr, bound ? bound->count : 0, bound ? bound->fixed : 0.0};
     if (bound)
       hipLaunchKernelGGL(k_nn_fallback<2>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
-                         c->blk_aabb.p, (const float4*)nullptr, (const uint32_t*)nullptr,
+                         c->blk_aabb.p, sc->fb_seed.p, (const float4*)nullptr, (const uint32_t*)nullptr,
                          (const uint32_t*)nullptr, (uint32_t)Q, d_keys, sc->counters.p, collect_stats, fu);
     else
       hipLaunchKernelGGL(k_nn_fallback<1>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
-                         c->blk_aabb.p, (const float4*)nullptr, (const uint32_t*)nullptr,
+                         c->blk_aabb.p, sc->fb_seed.p, (const float4*)nullptr, (const uint32_t*)nullptr,
                          (const uint32_t*)nullptr, (uint32_t)Q, d_keys, sc->counters.p, collect_stats, fu);
     PCD_HIP_TRY(hipGetLastError());
     return PCD_OK;
@@ -1117,7 +1189,7 @@ static pcd_status nn_device(pcd_cloud* c, const double* d_q, uint64_t Q, int alg
       ScopedKernelTimer t("nn_fallback", s);
       const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(Q, 4), g_fb_max_blocks);
       hipLaunchKernelGGL(k_nn_fallback<0>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
-                         c->blk_aabb.p, sc->qf4.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)Q,
+                         c->blk_aabb.p, sc->fb_seed.p, sc->qf4.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)Q,
                          d_keys, sc->counters.p, collect_stats, FbFused{nullptr, nullptr, 0, 0.0});
     } else if (algo == PCD_NN_AUTO || algo == PCD_NN_GRID) {
       PCD_TRY(run_grid<8>(c, sc, Q, d_keys, s, refine || bound != nullptr));   // incoming keys matter: carry them

@@ -28,6 +28,8 @@ struct QueryScratch {
   DevBuf<uint64_t> ksorted;    // their incoming keys, same order
   DevBuf<uint4> items;         // {first query, brick x, brick y, brick z | count << 28}
   DevBuf<uint32_t> fb_list, fb_dense;   // fallback list as the brick kernel fills it (chunked) / squeezed
+  DevBuf<float4> fb_seed;      // k_nn_fallback's seed table, built on first use (nn.hip fb_seed_table)
+  bool fb_seed_ok = false;
   DevBuf<NnCounters> counters;
   DevBuf<char> tmp;
   DevBuf<double> d_q;          // staging of host queries
