@@ -828,7 +828,14 @@ __device__ __forceinline__ double damp_of(int mode, double mu, double h) {
 }
 
 // thread = point: V = H_pt + D through a 3x3 Cholesky -> V^-1, V^-1 g, D.  Constant points are not eliminated, points
-// whose damped V is not positive definite are skipped (V^-1 = 0: delta 0, no contribution) and counted.
+// whose damped V is not numerically positive definite are skipped (V^-1 = 0: delta 0, no contribution) and counted.
+// The pivot rule is scale-invariant: pivot k must exceed kPivotTol * V_kk, which is the k-th pivot of the Jacobi-scaled
+// V (unit diagonal) exceeding kPivotTol.  A sign test would decide rank-deficient V (a point with one observation and
+// no LiDAR term, or only LiDAR terms, at mu = 0) by the rounding error of the accumulation of H_pt; that error is a
+// few ulp of V_kk, far below the threshold, while a 1e-4 Marquardt damping puts the scaled pivots of such points near
+// 1e-4, far above it.
+// tests/ba_schur_ref.point_inverse applies the same rule in the same operation order.
+constexpr double kPivotTol = 1e-10;
 __global__ __launch_bounds__(256) void k_schur_points(int P, const double* __restrict__ Hpt, const double* __restrict__ gpt,
                                                       const uint8_t* __restrict__ point_const, double mu, int mode,
                                                       double* __restrict__ Vinv, double* __restrict__ Vg,
@@ -837,15 +844,17 @@ __global__ __launch_bounds__(256) void k_schur_points(int P, const double* __res
   const int p = blockIdx.x * 256 + threadIdx.x;
   uint32_t skipped = 0;
   if (p < P) {
-    double vi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, d[3] = {0, 0, 0};
+    double vi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, d[3];
+    double* dp = Dpt + 3 * (size_t)p;
     if (!(point_const && point_const[p])) {
       const double* h = Hpt + 9 * (size_t)p;
       d[0] = damp_of(mode, mu, h[0]); d[1] = damp_of(mode, mu, h[4]); d[2] = damp_of(mode, mu, h[8]);
+      dp[0] = d[0]; dp[1] = d[1]; dp[2] = d[2];   // stored now: d is not live across the factorisation
       const double a00 = h[0] + d[0], a01 = h[1], a02 = h[2], a11 = h[4] + d[1], a12 = h[5], a22 = h[8] + d[2];
-      bool ok = a00 > 0.0;   // false for NaN too
+      bool ok = a00 > 0.0;   // false for NaN too; t <= V_kk, so a negative V_kk fails t > kPivotTol * V_kk as well
       double l00 = 0, l10 = 0, l20 = 0, l11 = 0, l21 = 0, l22 = 0;
-      if (ok) { l00 = sqrt(a00); l10 = a01 / l00; l20 = a02 / l00; const double t = a11 - l10 * l10; ok = t > 0.0; l11 = ok ? sqrt(t) : 0.0; }
-      if (ok) { l21 = (a12 - l20 * l10) / l11; const double t = a22 - l20 * l20 - l21 * l21; ok = t > 0.0; l22 = ok ? sqrt(t) : 0.0; }
+      if (ok) { l00 = sqrt(a00); l10 = a01 / l00; l20 = a02 / l00; const double t = a11 - l10 * l10; ok = t > kPivotTol * a11; l11 = ok ? sqrt(t) : 0.0; }
+      if (ok) { l21 = (a12 - l20 * l10) / l11; const double t = a22 - l20 * l20 - l21 * l21; ok = t > kPivotTol * a22; l22 = ok ? sqrt(t) : 0.0; }
       if (ok) {
         // M = L^-1 (lower), V^-1 = M^T M
         const double m00 = 1.0 / l00, m11 = 1.0 / l11, m22 = 1.0 / l22;
@@ -856,16 +865,15 @@ __global__ __launch_bounds__(256) void k_schur_points(int P, const double* __res
       } else {
         skipped = 1;
       }
+    } else {
+      dp[0] = 0.0; dp[1] = 0.0; dp[2] = 0.0;
     }
     const double* g = gpt + 3 * (size_t)p;
     double* o = Vinv + 9 * (size_t)p;
 #pragma unroll
     for (int k = 0; k < 9; ++k) o[k] = vi[k];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      Vg[3 * (size_t)p + r] = vi[3 * r] * g[0] + vi[3 * r + 1] * g[1] + vi[3 * r + 2] * g[2];
-      Dpt[3 * (size_t)p + r] = d[r];
-    }
+    for (int r = 0; r < 3; ++r) Vg[3 * (size_t)p + r] = vi[3 * r] * g[0] + vi[3 * r + 1] * g[1] + vi[3 * r + 2] * g[2];
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) skipped += __shfl_xor(skipped, off);
@@ -1939,13 +1947,14 @@ pcd_status pcd_ba_schur(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_sc
 pcd_status pcd_ba_schur_back_substitute_device(pcd_ba* b, const double* d_dpose, double* d_dpoint,
                                                double* d_model_decrease, void* stream) {
   PCD_TRY(schur_guard(b));
-  PCD_REQUIRE(d_dpose && d_dpoint, "null pointer");
   PCD_REFUSE_CAPTURE(stream);
   if (!b->schur || !b->schur->valid) {
     set_error("pcd_ba_schur_back_substitute_device: no Schur state (call pcd_ba_schur[_device] first)");
     return PCD_ERR_INVALID;
   }
   BaSchur& S = *b->schur;
+  // a zero-length array may be NULL (an empty torch tensor has data_ptr() 0): ns = 0 when every pose is constant
+  PCD_REQUIRE((d_dpose || S.ns == 0) && (d_dpoint || b->P == 0), "null pointer");
   PCD_HIP_TRY(hipSetDevice(b->device));
   hipStream_t s = (hipStream_t)stream;
   const int P = b->P;
@@ -1965,9 +1974,11 @@ pcd_status pcd_ba_plus_device(pcd_ba* b, const double* d_dpose, const double* d_
                               double* d_points_out, void* stream) {
   return pcd::guard([&]() -> pcd_status {
     PCD_TRY(schur_guard(b));
-    PCD_REQUIRE(d_dpose && d_dpoint && d_poses_out && d_points_out, "null pointer");
     PCD_REFUSE_CAPTURE(stream);
     PCD_TRY(schur_build(b));
+    // zero-length arrays may be NULL (ns = 0 when every pose is constant)
+    PCD_REQUIRE((d_dpose || b->schur->ns == 0) && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) &&
+                (d_points_out || b->P == 0), "null pointer");
     PCD_HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream;
     ScopedKernelTimer t("ba_plus", s);

@@ -952,7 +952,8 @@ def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", 
     the update), num_skipped."""
     import torch
     dev = torch.device("cuda", ba.device)
-    zero_pose = torch.zeros((max(ba.schur_structure()["num_slots"], 1), 6), dtype=torch.float64, device=dev)
+    ns = ba.schur_structure()["num_slots"]
+    zero_pose = torch.zeros((ns, 6), dtype=torch.float64, device=dev)
     zero_pt = torch.zeros((ba.P, 3), dtype=torch.float64, device=dev)
     acc_poses, acc_points = ba.plus(zero_pose, zero_pt)   # copy of the current parameters
     cand_poses, cand_points = torch.empty_like(acc_poses), torch.empty_like(acc_points)
@@ -961,11 +962,14 @@ def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", 
     for _ in range(int(max_iterations)):
         out = ba.schur(1.0 / radius, damping=damping, dense=True, want=("cost", "rhs", "num_skipped"))
         cost = float(out["cost"].item())
-        Lc, info = torch.linalg.cholesky_ex(out["S"])
         rec = dict(cost=cost, candidate_cost=float("nan"), rho=float("nan"), accepted=False,
                    num_skipped=int(out["num_skipped"].item()))
-        if int(info.item()) == 0:
-            dpose = torch.cholesky_solve(out["rhs"].reshape(-1, 1), Lc).reshape(-1, 6)
+        factored = True
+        if ns:
+            Lc, info = torch.linalg.cholesky_ex(out["S"])
+            factored = int(info.item()) == 0
+        if factored:   # ns = 0 (every pose constant): no reduced system, only the points move
+            dpose = torch.cholesky_solve(out["rhs"].reshape(-1, 1), Lc).reshape(-1, 6) if ns else zero_pose
             dpoint, md = ba.back_substitute(dpose)
             ba.plus(dpose, dpoint, cand_poses, cand_points)
             ba.set_parameters_device(cand_poses, cand_points)

@@ -514,7 +514,10 @@ pcd_status pcd_ba_set_parameters_device(pcd_ba* ba, const double* d_poses, const
  *   PCD_DAMP_MARQUARDT  D_kk = mu * clamp(H_kk, 1e-6, 1e32)   (Ceres' LM form, mu = 1 / radius)
  *   PCD_DAMP_LEVENBERG  D_kk = mu
  * Every non-constant point is eliminated: V_p = H_pt[p] + D_p through a 3x3 Cholesky; a point whose V_p is not
- * positive definite (possible with mu = 0) is skipped -- delta 0, no contribution -- and counted.  Reduced system:
+ * numerically positive definite is skipped -- delta 0, no contribution -- and counted.  The test is scale-invariant:
+ * V_00 > 0 and Cholesky pivot k > 1e-10 V_kk (the pivots of the unit-diagonal, Jacobi-scaled V exceed 1e-10), so a
+ * rank-deficient V_p (one observation and no LiDAR term, or LiDAR terms only, at mu = 0 or a tiny mu) is skipped
+ * whatever the rounding of H_pt.  Reduced system:
  *   S_ij  = delta_ij (U_i + D_i) - sum_p sum_{a in p,i; b in p,j} W_a V_p^-1 W_b^T
  *   rhs_i = -g_i + sum_{a in i} W_a V_p(a)^-1 g_p(a)
  * Constant-pose images have no slot; constant-tvec components are inactive (identity rows / columns of S, rhs 0,
@@ -536,7 +539,7 @@ typedef struct {
   double* S_off;           /* [num_pairs][6][6] block (pair_i[q], pair_j[q]), pair_i < pair_j                   */
   double* rhs;             /* [ns][6]                                                                          */
   double* S;               /* [n][n] dense, row-major, both triangles (for a direct Cholesky)                 */
-  uint64_t* num_skipped;   /* [1] eliminated points whose damped V was not positive definite                  */
+  uint64_t* num_skipped;   /* [1] eliminated points skipped by the pivot test above (V_p numerically singular) */
 } pcd_ba_schur_out;
 /* Co-visibility structure (host query): image_slot [I] (-1 = constant pose), the number of slots, and the slot pairs
  * i < j that share an eliminated point, ascending (i, j).  Every output may be NULL (size the buffers first). */
@@ -547,12 +550,13 @@ pcd_status pcd_ba_schur_device(pcd_ba* ba, const pcd_ba_schur_opts* opts, const 
 pcd_status pcd_ba_schur(pcd_ba* ba, const pcd_ba_schur_opts* opts, const pcd_ba_schur_out* out);   /* host outputs */
 /* delta X_p = -V_p^-1 (g_p + sum_{a in p} W_a^T dpose[slot(a)]) from the state of the last Schur call (INVALID
  * without one); d_dpoint [P][3] (0 for constant / skipped points).  d_model_decrease (may be NULL): [1]
- * 1/2 (-delta^T g + delta^T D delta), the decrease of the LM model, summed in a fixed order. */
+ * 1/2 (-delta^T g + delta^T D delta), the decrease of the LM model, summed in a fixed order.  d_dpose may be NULL
+ * when ns = 0 (every pose constant). */
 pcd_status pcd_ba_schur_back_substitute_device(pcd_ba* ba, const double* d_dpose /*[ns][6]*/, double* d_dpoint,
                                                double* d_model_decrease, void* stream);
 /* Candidate parameters: Ceres' QuaternionManifold::Plus on the quaternion, t + dt on the variable tvec components,
  * X + dX on the non-constant points, copies of everything constant.  Reads the handle's current parameters; the
- * outputs may be the handle's own buffers (pcd_ba_device_parameters). */
+ * outputs may be the handle's own buffers (pcd_ba_device_parameters).  d_dpose may be NULL when ns = 0. */
 pcd_status pcd_ba_plus_device(pcd_ba* ba, const double* d_dpose /*[ns][6]*/, const double* d_dpoint /*[P][3]*/,
                               double* d_poses_out /*[I][7]*/, double* d_points_out /*[P][3]*/, void* stream);
 typedef struct {

@@ -10,6 +10,7 @@ Test infrastructure: small scenes only (dense matrices, Python loops over pairs)
 import numpy as np
 
 DIAG_MIN, DIAG_MAX = 1e-6, 1e32
+PIVOT_TOL = 1e-10          # k_schur_points' kPivotTol: pivot k must exceed PIVOT_TOL * V_kk
 
 
 def damping(h_diag, mu, mode):
@@ -36,18 +37,20 @@ def problem(scene):
 
 
 def point_inverse(Hpt, Dpt, point_const):
-    """V_p^-1 through the same 3x3 Cholesky as the device (a pivot <= 0 -> skipped, V^-1 = 0); constant points: 0"""
+    """V_p^-1 through the same 3x3 Cholesky as the device, with its scale-invariant pivot rule in the same operation
+    order: V_00 <= 0 or pivot k <= PIVOT_TOL * V_kk (pivot of the Jacobi-scaled V <= PIVOT_TOL) -> skipped, V^-1 = 0;
+    constant points: 0"""
     A = Hpt + Dpt[:, :, None] * np.eye(3)
     with np.errstate(invalid="ignore", divide="ignore"):
         ok = A[:, 0, 0] > 0
         l00 = np.sqrt(np.where(ok, A[:, 0, 0], 1.0))
         l10, l20 = A[:, 0, 1] / l00, A[:, 0, 2] / l00
         t1 = A[:, 1, 1] - l10 * l10
-        ok &= t1 > 0
+        ok &= t1 > PIVOT_TOL * A[:, 1, 1]
         l11 = np.sqrt(np.where(ok, t1, 1.0))
         l21 = (A[:, 1, 2] - l20 * l10) / l11
         t2 = A[:, 2, 2] - l20 * l20 - l21 * l21
-        ok &= t2 > 0
+        ok &= t2 > PIVOT_TOL * A[:, 2, 2]
         l22 = np.sqrt(np.where(ok, t2, 1.0))
     L = np.zeros_like(A)
     L[:, 0, 0], L[:, 1, 0], L[:, 2, 0], L[:, 1, 1], L[:, 2, 1], L[:, 2, 2] = l00, l10, l20, l11, l21, l22
@@ -287,3 +290,84 @@ def lm(oracle, scene, max_iterations, initial_radius=1e4, mode="marquardt", min_
         rec["radius"] = radius
         hist.append(rec)
     return hist, scene
+
+
+# ---- scenes shared by the CPU and GPU tests ----
+def camera_params(model, focal_scale=1.0):
+    """parameters of camera `model` around synth.OPENCV_PARAMS' focal length and principal point, small distortion"""
+    from pcdhip import synth
+    fx, fy, cx, cy = synth.OPENCV_PARAMS[:4]
+    nf = 1 if model in (0, 2, 3, 8, 9) else 2          # focal lengths: f, or fx fy
+    extra = {0: [], 1: [], 2: [-0.03], 3: [-0.03, 0.005], 4: [-0.05, 0.01, 1e-4, 1e-4], 5: [0.02, -0.01, 0.003, -0.001],
+             6: [-0.05, 0.01, 1e-4, 1e-4, 0.002, 0.01, -0.005, 0.001], 7: [0.4], 8: [0.02], 9: [0.02, -0.004],
+             10: [0.02, -0.01, 1e-4, -1e-4, 0.003, -0.001, 2e-4, -1e-4]}[model]
+    return np.array([fx * focal_scale, fy * focal_scale * 1.01][:nf] + [cx, cy] + extra, np.float64)
+
+
+def reproject(oracle, scene, rng, noise=1.0):
+    """observations = projection of each observed point through its image's camera (oracle) + U(-noise, noise) px"""
+    models = np.asarray(scene["cam_model"])
+    poses, X = np.asarray(scene["poses"]), np.asarray(scene["points"])
+    xy = np.empty((len(scene["obs_image"]), 2))
+    for o, (i, p) in enumerate(zip(scene["obs_image"], scene["obs_point"])):
+        c = int(scene["image_camera"][i])
+        xy[o] = oracle.reproj_residual(int(models[c]), poses[i, :4], poses[i, 4:], X[p], scene["cam_params_list"][c],
+                                       np.zeros(2))
+    scene["obs_xy"] = xy + rng.uniform(-noise, noise, xy.shape)
+    assert np.isfinite(scene["obs_xy"]).all()
+    return scene
+
+
+def camera_scene(oracle, models, seed, I=6, P=150, lidar_frac=1.0):
+    """synth.ba_scene with cameras of the given models (one camera per entry, parameters differing), image i on camera
+    i % len(models), observations re-projected through those cameras; image 0 constant, some constant tvec components
+    and constant points"""
+    from pcdhip import synth
+    s = synth.ba_scene(I, P, seed=seed, const_pose_frac=0.3, lidar_frac=lidar_frac)
+    nc = len(models)
+    s["cam_model"] = np.array(models, np.int32)
+    s["cam_params_list"] = [camera_params(m, 1.0 + 1e-3 * k) for k, m in enumerate(models)]
+    s["image_camera"] = (np.arange(I) % nc).astype(np.int32)
+    rng = np.random.default_rng(seed)
+    s["image_const_pose"][0] = 1
+    s["image_const_tvec"] = (rng.integers(1, 8, I) * (rng.random(I) < 0.4)).astype(np.uint8)
+    s["point_const"] = (rng.random(P) < 0.1).astype(np.uint8)
+    return reproject(oracle, s, rng)
+
+
+def degenerate_scene(oracle, seed, n_single=8, n_lidar=6):
+    """a well-conditioned base scene (every point has a LiDAR term) plus points whose H_pt is rank-deficient:
+    n_single points with one observation near the centre of a variable image at 8-15 m depth and no LiDAR term (rank 2),
+    n_lidar points with only a LiDAR term of a generic normal and 3 with axis-aligned normals (rank 1).
+    Returns (scene, indices of the rank-deficient points)."""
+    from pcdhip import synth
+    s = synth.ba_scene(6, 150, seed=seed, const_pose_frac=0.3, lidar_frac=1.0)
+    rng = np.random.default_rng(seed)
+    s["image_const_pose"][0] = 1
+    P0 = s["points"].shape[0]
+    var = np.flatnonzero(s["image_const_pose"] == 0)
+    pts, oi, op, lp, ab, lw = [], [], [], [], [], []
+    for k in range(n_single):
+        i = int(var[k % var.size])
+        q, t = s["poses"][i, :4], s["poses"][i, 4:]
+        pc = np.array([rng.uniform(-0.05, 0.05), rng.uniform(-0.05, 0.05), 1.0]) * rng.uniform(8, 15)
+        pts.append(synth._quat_rotate(q * np.array([1, -1, -1, -1]), pc - t))
+        oi.append(i); op.append(P0 + k)
+    normals = [n / np.linalg.norm(n) for n in rng.normal(size=(n_lidar, 3))] + list(np.eye(3))
+    for k, n in enumerate(normals):
+        X = s["points"][rng.integers(P0)] + rng.normal(0, 0.5, 3)
+        pts.append(X)
+        lp.append(P0 + n_single + k)
+        ab.append(np.r_[n, -n @ (X + rng.normal(0, 0.05, 3))])
+        lw.append(100.0)
+    s["points"] = np.concatenate([s["points"], pts])
+    xy_new = np.array([oracle.reproj_residual(4, s["poses"][i, :4], s["poses"][i, 4:], s["points"][p],
+                                              synth.OPENCV_PARAMS, np.zeros(2)) for i, p in zip(oi, op)])
+    s["obs_image"] = np.concatenate([s["obs_image"], oi]).astype(np.int32)
+    s["obs_point"] = np.concatenate([s["obs_point"], op]).astype(np.int32)
+    s["obs_xy"] = np.concatenate([s["obs_xy"], xy_new + rng.uniform(-1, 1, xy_new.shape)])
+    s["lidar_point"] = np.concatenate([s["lidar_point"], lp]).astype(np.int32)
+    s["lidar_abcd"] = np.concatenate([s["lidar_abcd"], ab])
+    s["lidar_weight"] = np.concatenate([s["lidar_weight"], lw])
+    s["point_const"] = np.zeros(s["points"].shape[0], np.uint8)
+    return s, np.arange(P0, s["points"].shape[0])

@@ -155,3 +155,57 @@ def test_no_device_refusal(pcdhip):
     with pytest.raises(pcdhip.PcdError) as e:
         pcdhip.BA(**synth.ba_scene(3, 10, seed=1))
     assert e.value.status == pcdhip.PCD_ERR_NO_DEVICE
+
+
+@pytest.mark.parametrize("seed", [50, 51, 52])
+def test_pivot_rule_is_stable_under_rounding(oracle, seed):
+    """the skip decision of point_inverse (the rule of k_schur_points) does not depend on the last bits of H_pt: the
+    device sums H_pt in another order than the oracle, so the two agree only to a few ulp.  Rank-deficient points of
+    ref.degenerate_scene (one observation without a LiDAR term, only a LiDAR term) are skipped at mu = 0 and kept at a
+    1e-4 Marquardt damping, and no decision flips under a symmetric relative perturbation of 4e-16 N(0, 1); full-rank
+    points (two or more observations, or one observation plus a LiDAR term) are never skipped."""
+    s, deg = ref.degenerate_scene(oracle, seed)
+    ne0 = ref.NormalEquations(oracle, s, 0.0)
+    P = s["points"].shape[0]
+    nobs = np.bincount(s["obs_point"], minlength=P)
+    nlid = np.bincount(s["lidar_point"], minlength=P)
+    assert (nobs[deg[:8]] == 1).all() and (nlid[deg[:8]] == 0).all()
+    assert (nobs[deg[8:]] == 0).all() and (nlid[deg[8:]] == 1).all()
+    full = np.flatnonzero((nobs >= 2) | ((nobs == 1) & (nlid >= 1)))
+    assert full.size > 100 and not np.isin(full, deg).any()
+    rng = np.random.default_rng(seed)
+    H = ne0.Hpt
+    pc = np.zeros(P, np.uint8)
+    for mu in (0.0, 1e-16, 1e-4):
+        D = ref.damping(np.diagonal(H, axis1=1, axis2=2), mu, "marquardt")
+        _, skip = ref.point_inverse(H, D, pc)
+        if mu == 0.0:
+            assert np.array_equal(np.flatnonzero(skip), deg)
+        elif mu == 1e-16:   # axis-aligned LiDAR-only points: exactly diagonal V, kept (pivots = diagonal)
+            assert np.array_equal(np.flatnonzero(skip), deg[:-3])
+        else:
+            assert not skip.any()
+        for _ in range(200):
+            E = rng.normal(size=H.shape)
+            E = 0.5 * (E + E.transpose(0, 2, 1))
+            Hp = H * (1.0 + 4e-16 * E)
+            Dp = ref.damping(np.diagonal(Hp, axis1=1, axis2=2), mu, "marquardt")
+            _, sp = ref.point_inverse(Hp, Dp, pc)
+            assert np.array_equal(sp, skip), (mu, np.flatnonzero(sp != skip))
+        assert not skip[full].any()
+
+
+def test_pivot_rule_is_scale_invariant():
+    """scaling a point's coordinates (V -> S V S, S diagonal) does not change the decision"""
+    rng = np.random.default_rng(3)
+    J = rng.normal(size=(500, 2, 3))
+    H = np.einsum("pki,pkj->pij", J, J)                       # rank 2
+    Hf = H + np.einsum("pi,pj->pij", *(2 * [rng.normal(size=(500, 3))]))   # + a rank-1 term: full rank
+    pc = np.zeros(500, np.uint8)
+    for scale in (1e-6, 1.0, 1e8):
+        Sc = np.diag([scale, 1.0, 1.0 / scale])
+        for A, want in ((H, True), (Hf, False)):
+            As = Sc @ A @ Sc
+            for mu, w in ((0.0, want), (1e-4, False)):
+                _, skip = ref.point_inverse(As, ref.damping(np.diagonal(As, axis1=1, axis2=2), mu, "marquardt"), pc)
+                assert (skip == w).all(), (scale, mu, want, int(skip.sum()))
