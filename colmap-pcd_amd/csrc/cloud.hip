@@ -131,8 +131,7 @@ __global__ void k_gather_sorted(const float4* __restrict__ pts4, const uint32_t*
   uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i >= m + kSortedSpare) return;
   // rows m .. m+15 repeat the last record: the brick kernel reads ranges in groups of 4 records and may run up to
-  // 3 records past the end of the last range (brick_kernel.h), the stencil kernel in steps of 16 records
-  // (stencil_kernel.h); a repeated real point cannot change a minimum
+  // 3 records past the end of the last range (brick_kernel.h); a repeated real point cannot change a minimum
   uint32_t src = order[i < m ? i : m - 1];
   float4 p = pts4[src];
   p.w = __uint_as_float(row_index ? row_index[src] : index_base + src * index_stride);

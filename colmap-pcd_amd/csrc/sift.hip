@@ -11,14 +11,15 @@
 // so the bytes are re-centred to int8 (a ^ 0x80) and fed to v_mfma_i32_32x32x32_i8 (K = 32 per
 // instruction, int32 accumulate: exact), the row-sum correction is added in the epilogue.
 //
-// Default scores kernel: sift_stripe (k_sift_scores_stripe / k_sift_scores_batch, below): a persistent row-stripe walk
-// that multiplies every tile ONCE -- the column-direction top-2 is register-local in the MFMA result layout, the
-// row-direction top-2 is a running per-lane state over the whole walk that is merged across lanes once at the end.
-// (Rounds 1-2 multiplied every tile twice, A.B^T and B.A^T, so that both scans were register-local.)
-// Per chunk / 64-row group and direction one (best, second, argbest) triple per descriptor goes to a partial buffer
-// (column direction: 8 bytes, the two packed scan values as they are; k_sift_finalize decodes them);
-// k_sift_finalize merges the partials in ascending order (ties -> first index, as the reference's ascending strict->
-// scan), applies acos / max_distance / max_ratio; the cross check and the ordered compaction follow.
+// Scores kernels (k_sift_scores_stripe / k_sift_scores_batch, guided: k_sift_guided_stripe / k_sift_guided_batch, all
+// around sift_rows below): a persistent row-stripe walk of ONE direction -- lane = row of the row set, so a row's running
+// (best, second, argbest) is three registers that live for the whole walk.  The other direction (best row per column)
+// is the same walk with the two sets exchanged: every tile is multiplied twice, nothing else is done twice.
+// Per column chunk and row one int4 {best, second, arg, 0} with true scores goes to a partial buffer (part12 / part21);
+// k_sift_finalize merges the chunks' partials in ascending order (ties -> first index, as the reference's ascending
+// strict-> scan), applies acos / max_distance / max_ratio; the cross check and the ordered compaction follow.
+// Guided matching (H / F filter): per keypoint and pair one record of six floats (k_sift_guide_prep); the walk stages the
+// column records beside the descriptors and leaves a rejected pair out of the row's top-2.
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -35,8 +36,8 @@ namespace pcd {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-// test / fuzzing knobs (pcd_sift_set_tuning; 0 = the library's choice): column chunks per stripe walk, bytes of partial
-// results per sub-batch.  Atomics read once per call: no environment lookups on the call path.
+// test / fuzzing knobs (pcd_sift_set_tuning; 0 = the library's choice): column chunks per stripe walk, partial results
+// per sub-batch in int4 elements (16-byte units).  Atomics read once per call: no environment lookups on the call path.
 static std::atomic<int> g_sift_nchunk{0};
 static std::atomic<uint64_t> g_sift_batch_partials{0};
 
@@ -556,7 +557,7 @@ __global__ __launch_bounds__(64 * kSiftWaves, PCD_SIFT_WGS) void k_sift_scores_b
                    SiftGuideWalk{});
 }
 
-// ---- guided kernels (after the unguided ones: their code and labels stay as they were) ----
+// ---- guided kernels ----
 // one workgroup of 128 threads per (128-row tile, side, pair): records of every row of the tile (zeros past n)
 __global__ __launch_bounds__(128) void k_sift_guide_prep(const SiftGuidePairDev* __restrict__ guides,
                                                          float* __restrict__ rec) {
@@ -826,86 +827,107 @@ struct SiftScratch {
 };
 static SiftScratch* g_sift[64] = {nullptr};
 static std::recursive_mutex g_sift_mu;
-typedef std::lock_guard<std::recursive_mutex> SiftLock;
 
-// bracket of every use of the shared scratch on stream s (g_sift_mu held)
-static pcd_status sift_begin_use(SiftScratch& sc, hipStream_t s) {
+// THE use of a device's shared scratch: body(scratch) enqueues on stream s with g_sift_mu held, behind the previous
+// use's ev_done if that was on another stream.  ev_done is recorded on every way out of body -- an error return or an
+// exception included, as body may have enqueued work that touches the scratch before it failed.  Uses nest (a host
+// entry holds the scratch around the device entry it calls); device < 64 is the caller's check.
+template <typename Body>
+static pcd_status sift_use_scratch(int device, hipStream_t s, Body&& body) {
+  std::lock_guard<std::recursive_mutex> g(g_sift_mu);
+  PCD_HIP_TRY(hipSetDevice(device));
+  if (!g_sift[device]) g_sift[device] = new SiftScratch();
+  SiftScratch& sc = *g_sift[device];
   if (!sc.ev_done) {
     PCD_HIP_TRY(hipEventCreateWithFlags(&sc.ev_done, hipEventDisableTiming));
     PCD_HIP_TRY(hipEventCreateWithFlags(&sc.ev_tab, hipEventDisableTiming));
   }
   if (sc.used && sc.last_stream != s) PCD_HIP_TRY(hipStreamWaitEvent(s, sc.ev_done, 0));
-  return PCD_OK;
-}
-static pcd_status sift_end_use(SiftScratch& sc, hipStream_t s) {
+  const pcd_status st = pcd::guard([&]() -> pcd_status { return body(sc); });
   PCD_HIP_TRY(hipEventRecord(sc.ev_done, s));
   sc.last_stream = s;
   sc.used = true;
-  return PCD_OK;
+  return st;
 }
 
-// one guided pair's table entry on the device (sc.guides[0]) for sift_device: its records at the start of sc.grec
-static pcd_status sift_upload_guide(SiftScratch& sc, hipStream_t s, const float* d_loc1, int n1, const float* d_loc2,
-                                    int n2, const float* H, const float* F) {
-  SiftGuidePairDev g{};
-  g.loc1 = d_loc1; g.loc2 = d_loc2; g.n1 = (uint32_t)n1; g.n2 = (uint32_t)n2;
-  g.rec1 = 0; g.rec2 = (uint64_t)((n1 + kSiftTile - 1) / kSiftTile) * kSiftRecTile;
-  g.mode = (H ? kSiftGuideH : 0) | (F ? kSiftGuideF : 0);
-  if (H) std::memcpy(g.H, H, sizeof(g.H));
-  if (F) std::memcpy(g.F, F, sizeof(g.F));
+// the pinned staging of the pair / image / guide tables is free again (the previous upload has left it)
+static pcd_status sift_tables_free(SiftScratch& sc) {
   if (sc.tab_pending) PCD_HIP_TRY(hipEventSynchronize(sc.ev_tab));
-  PCD_TRY(sc.h_guides.reserve(1)); PCD_TRY(sc.guides.reserve(1));
-  sc.h_guides.p[0] = g;
-  PCD_HIP_TRY(hipMemcpyAsync(sc.guides.p, sc.h_guides.p, sizeof(SiftGuidePairDev), hipMemcpyHostToDevice, s));
+  return PCD_OK;
+}
+static pcd_status sift_tables_sent(SiftScratch& sc, hipStream_t s) {
   PCD_HIP_TRY(hipEventRecord(sc.ev_tab, s));
   sc.tab_pending = true;
   return PCD_OK;
 }
 
-// d_guide (guided entries): the pair's table entry on the device, laid out by sift_upload_guide; th / tf its thresholds
-static pcd_status sift_device(int device, const uint8_t* d_d1, int n1, const uint8_t* d_d2, int n2, float max_ratio,
+static inline uint64_t sift_tiles(uint64_t n) { return (n + kSiftTile - 1) / kSiftTile; }
+
+// one pair's guide table entry: its records start at float offset rec1 of the record buffer, side 2 behind side 1
+// (H / F are read iff the mode names them)
+static SiftGuidePairDev sift_guide_entry(const float* d_loc1, uint64_t n1, const float* d_loc2, uint64_t n2,
+                                         uint64_t rec1, int mode, const float* H, const float* F) {
+  SiftGuidePairDev g{};
+  g.loc1 = d_loc1; g.loc2 = d_loc2; g.n1 = (uint32_t)n1; g.n2 = (uint32_t)n2;
+  g.rec1 = rec1; g.rec2 = rec1 + sift_tiles(n1) * kSiftRecTile;
+  g.mode = mode & (kSiftGuideH | kSiftGuideF);
+  if (g.mode & kSiftGuideH) std::memcpy(g.H, H, sizeof(g.H));
+  if (g.mode & kSiftGuideF) std::memcpy(g.F, F, sizeof(g.F));
+  return g;
+}
+
+// one guided pair's table entry on the device (sc.guides[0]) for sift_device: its records at the start of sc.grec
+static pcd_status sift_upload_guide(SiftScratch& sc, hipStream_t s, const float* d_loc1, int n1, const float* d_loc2,
+                                    int n2, int mode, const float* H, const float* F) {
+  PCD_TRY(sift_tables_free(sc));
+  PCD_TRY(sc.h_guides.reserve(1)); PCD_TRY(sc.guides.reserve(1));
+  sc.h_guides.p[0] = sift_guide_entry(d_loc1, n1, d_loc2, n2, 0, mode, H, F);
+  PCD_HIP_TRY(hipMemcpyAsync(sc.guides.p, sc.h_guides.p, sizeof(SiftGuidePairDev), hipMemcpyHostToDevice, s));
+  return sift_tables_sent(sc, s);
+}
+
+// One pair, both sets non-empty, on the device.  d_guide (guided): the pair's table entry on the device, laid out by
+// sift_upload_guide; th / tf its thresholds.
+static pcd_status sift_device(const uint8_t* d_d1, int n1, const uint8_t* d_d2, int n2, float max_ratio,
                               float max_distance, int cross_check, int* d_m12, int* d_m21, uint32_t* d_matches,
-                              int* d_count, SiftScratch& sc, hipStream_t s,
-                              const SiftGuidePairDev* d_guide = nullptr, float th = 0.f, float tf = 0.f) {
-  const int nb1 = (n1 + kSiftTile - 1) / kSiftTile, nb2 = (n2 + kSiftTile - 1) / kSiftTile;
-  // stripe walks in both directions: enough (row tile, chunk) workgroups to fill the chip twice over
+                              int* d_count, SiftScratch& sc, hipStream_t s, const SiftGuidePairDev* d_guide, float th,
+                              float tf) {
+  const int nb1 = (int)sift_tiles(n1), nb2 = (int)sift_tiles(n2);
+  const int ns1 = (n1 + kSiftStripe - 1) / kSiftStripe, ns2 = (n2 + kSiftStripe - 1) / kSiftStripe;
+  // stripe walks in both directions: enough (row stripe, chunk) workgroups to fill the chip twice over
   // pcd_sift_set_tuning (tests / fuzzing) can force the number of column chunks, e.g. 1 = every stripe walks all tiles
   const int nchunk_set = g_sift_nchunk.load(std::memory_order_relaxed);
-  auto chunks = [&](int nrow_tiles, int ncol_tiles) {
-    const int stripes = (n1 + kSiftStripe - 1) / kSiftStripe + (n2 + kSiftStripe - 1) / kSiftStripe;
-    const int want = nchunk_set > 0 ? std::min(nchunk_set, ncol_tiles) : std::min(ncol_tiles, (512 + stripes - 1) / stripes);
-    (void)nrow_tiles;
-    return std::max(1, want);
+  auto chunks = [&](int ncol_tiles) {
+    const int want = nchunk_set > 0 ? nchunk_set : (512 + ns1 + ns2 - 1) / (ns1 + ns2);
+    return std::max(1, std::min(want, ncol_tiles));
   };
-  const int nchunk12 = chunks(nb1, nb2), nchunk21 = chunks(nb2, nb1);
+  const int nchunk12 = chunks(nb2), nchunk21 = chunks(nb1);
   const int ct12 = (nb2 + nchunk12 - 1) / nchunk12, ct21 = (nb1 + nchunk21 - 1) / nchunk21;
   const int used12 = sift_chunks_used(nb2, nchunk12), used21 = sift_chunks_used(nb1, nchunk21);
+  const dim3 grid(std::max(used12, used21), std::max(ns1, ns2), 2), block(64 * kSiftWaves);
   const uint32_t prow1 = 0, prow2 = (uint32_t)nb1 * kSiftTile;
   const size_t prows = (size_t)(nb1 + nb2) * kSiftTile + kSiftStripe;   // a stripe's row fragments are read unconditionally
   PCD_TRY(sc.xa.reserve(prows * 128)); PCD_TRY(sc.cc.reserve(prows));
   PCD_TRY(sc.part12.reserve((size_t)n1 * used12)); PCD_TRY(sc.part21.reserve((size_t)n2 * used21));
   PCD_TRY(sc.keep.reserve(n1)); PCD_TRY(sc.pos.reserve(n1));
+  if (d_guide) PCD_TRY(sc.grec.reserve((size_t)(nb1 + nb2) * kSiftRecTile));
   {
     ScopedKernelTimer t("sift_prep", s);
     hipLaunchKernelGGL(k_sift_prep_pair, dim3(std::max(nb1, nb2), 2), dim3(256), 0, s, SiftImageDev{d_d1, (uint32_t)n1, prow1},
                        SiftImageDev{d_d2, (uint32_t)n2, prow2}, sc.xa.p, sc.cc.p);
   }
   if (d_guide) {
-    PCD_TRY(sc.grec.reserve((size_t)(nb1 + nb2) * kSiftRecTile));
-    {
-      ScopedKernelTimer t("sift_guide_prep", s);
-      hipLaunchKernelGGL(k_sift_guide_prep, dim3(std::max(nb1, nb2), 2, 1), dim3(kSiftTile), 0, s, d_guide, sc.grec.p);
-    }
-    ScopedKernelTimer t("sift_guided_scores", s);
-    const int ns1 = (n1 + kSiftStripe - 1) / kSiftStripe, ns2 = (n2 + kSiftStripe - 1) / kSiftStripe;
-    hipLaunchKernelGGL(k_sift_guided_stripe, dim3(std::max(used12, used21), std::max(ns1, ns2), 2), dim3(64 * kSiftWaves), 0,
-                       s, sc.xa.p, sc.cc.p, prow1, n1, prow2, n2, sc.part12.p, sc.part21.p, ct12, ct21, d_guide, sc.grec.p,
-                       th, tf);
-  } else {
-    ScopedKernelTimer t("sift_scores", s);
-    const int ns1 = (n1 + kSiftStripe - 1) / kSiftStripe, ns2 = (n2 + kSiftStripe - 1) / kSiftStripe;
-    hipLaunchKernelGGL(k_sift_scores_stripe, dim3(std::max(used12, used21), std::max(ns1, ns2), 2), dim3(64 * kSiftWaves), 0, s, sc.xa.p,
-                       sc.cc.p, prow1, n1, prow2, n2, sc.part12.p, sc.part21.p, ct12, ct21);
+    ScopedKernelTimer t("sift_guide_prep", s);
+    hipLaunchKernelGGL(k_sift_guide_prep, dim3(std::max(nb1, nb2), 2, 1), dim3(kSiftTile), 0, s, d_guide, sc.grec.p);
+  }
+  {
+    ScopedKernelTimer t(d_guide ? "sift_guided_scores" : "sift_scores", s);
+    if (d_guide)
+      hipLaunchKernelGGL(k_sift_guided_stripe, grid, block, 0, s, sc.xa.p, sc.cc.p, prow1, n1, prow2, n2, sc.part12.p,
+                         sc.part21.p, ct12, ct21, d_guide, sc.grec.p, th, tf);
+    else
+      hipLaunchKernelGGL(k_sift_scores_stripe, grid, block, 0, s, sc.xa.p, sc.cc.p, prow1, n1, prow2, n2, sc.part12.p,
+                         sc.part21.p, ct12, ct21);
   }
   {
     ScopedKernelTimer t("sift_finalize", s);
@@ -931,171 +953,391 @@ static pcd_status sift_device(int device, const uint8_t* d_d1, int n1, const uin
   return PCD_OK;
 }
 
+// ---- many pairs over one descriptor arena ---------------------------------------------------------------------------
+// Sub-batches are cut so that the partial results of a sub-batch stay under kSiftBatchPartials int4 (2 GiB); each
+// sub-batch is three launches (scores, finalize, cross check + compaction; guided: the records' launch in front), the
+// arena's preparation one launch in front of all.  Nothing synchronises with the host.
+constexpr size_t kSiftBatchPartials = (size_t)1 << 27;   // pcd_sift_set_tuning overrides it (tests: forces the cuts)
 
-// Many pairs over one descriptor arena.  Sub-batches are cut so that the partial results of a sub-batch stay under
-// kSiftBatchPartials int4 (2 GiB); each sub-batch is three launches (scores, finalize, cross check + compaction),
-// the arena's row sums one launch in front.  Nothing synchronises with the host.
-constexpr size_t kSiftBatchPartials = (size_t)1 << 27;   // PCD_SIFT_BATCH_PARTIALS overrides it (tests: forces the cuts)
+// what a batch call is given (guides == nullptr: unguided; d_locs = [rows][2] locations parallel to the arena)
+struct SiftBatchArgs {
+  const uint8_t* d_arena;
+  const float* d_locs;
+  const uint64_t* first_row;
+  int n_images;
+  const uint32_t* pair_ids;
+  int n_pairs;
+  const pcd_sift_guide* guides;
+  float th, tf, max_ratio, max_distance;
+  int cross_check;
+  uint32_t* d_matches;
+  const uint64_t* match_offset;
+  int* d_counts;
+  uint64_t rows(uint32_t image) const { return first_row[image + 1] - first_row[image]; }
+};
 
-// guided (guides != nullptr): d_locs = [rows][2] locations parallel to the arena, guides[p] pair p's mode and matrices
-static pcd_status sift_batch_device(int device, const uint8_t* d_arena, const uint64_t* first_row, int n_images,
-                                    const uint32_t* pair_ids, int n_pairs, float max_ratio, float max_distance,
-                                    int cross_check, uint32_t* d_matches, const uint64_t* match_offset, int* d_counts,
-                                    SiftScratch& sc, hipStream_t s, const float* d_locs = nullptr,
-                                    const pcd_sift_guide* guides = nullptr, float th = 0.f, float tf = 0.f) {
-  const uint64_t total_rows = first_row[n_images];
-  PCD_REQUIRE(total_rows < (1ull << 32), "arena larger than 2^32 descriptors");
-  const uint64_t budget_set = g_sift_batch_partials.load(std::memory_order_relaxed);   // pcd_sift_set_tuning
-  const size_t budget = budget_set ? (size_t)budget_set : kSiftBatchPartials;
-  for (int i = 0; i < n_images; ++i) PCD_REQUIRE(first_row[i] <= first_row[i + 1], "first_row must ascend");
-  bool wide = false;   // a set too long for the one-workgroup compaction: those batches run pair by pair
-  for (int p = 0; p < n_pairs; ++p) {
-    PCD_REQUIRE(pair_ids[2 * p] < (uint32_t)n_images && pair_ids[2 * p + 1] < (uint32_t)n_images, "pair names an image outside the arena");
-    const uint64_t n1 = first_row[pair_ids[2 * p] + 1] - first_row[pair_ids[2 * p]];
-    const uint64_t n2 = first_row[pair_ids[2 * p + 1] + 1] - first_row[pair_ids[2 * p + 1]];
-    PCD_REQUIRE(n1 < (1u << 30) && n2 < (1u << 30), "image too large");
-    wide = wide || n1 > (uint64_t)1024 * kCompactPer;
+// the pair list is consistent with the arena; *wide: some first set is too long for the one-workgroup compaction
+static pcd_status sift_batch_validate(const SiftBatchArgs& a, bool* wide) {
+  PCD_REQUIRE(a.first_row[a.n_images] < (1ull << 32), "arena larger than 2^32 descriptors");
+  for (int i = 0; i < a.n_images; ++i) PCD_REQUIRE(a.first_row[i] <= a.first_row[i + 1], "first_row must ascend");
+  *wide = false;
+  for (int p = 0; p < a.n_pairs; ++p) {
+    const uint32_t i1 = a.pair_ids[2 * p], i2 = a.pair_ids[2 * p + 1];
+    PCD_REQUIRE(i1 < (uint32_t)a.n_images && i2 < (uint32_t)a.n_images, "pair names an image outside the arena");
+    PCD_REQUIRE(a.rows(i1) < (1u << 30) && a.rows(i2) < (1u << 30), "image too large");
+    *wide = *wide || a.rows(i1) > (uint64_t)1024 * kCompactPer;
   }
-  if (wide) {
-    for (int p = 0; p < n_pairs; ++p) {
-      const uint32_t a = pair_ids[2 * p], b = pair_ids[2 * p + 1];
-      const int n1 = (int)(first_row[a + 1] - first_row[a]), n2 = (int)(first_row[b + 1] - first_row[b]);
-      if (n1 == 0 || n2 == 0) { PCD_HIP_TRY(hipMemsetAsync(d_counts + p, 0, sizeof(int), s)); continue; }
-      PCD_TRY(sc.m12.reserve(n1)); PCD_TRY(sc.m21.reserve(n2));
-      const bool guided = guides && (guides[p].mode & (kSiftGuideH | kSiftGuideF));
-      if (guided)
-        PCD_TRY(sift_upload_guide(sc, s, d_locs + 2 * first_row[a], n1, d_locs + 2 * first_row[b], n2,
-                                  (guides[p].mode & kSiftGuideH) ? guides[p].H : nullptr,
-                                  (guides[p].mode & kSiftGuideF) ? guides[p].F : nullptr));
-      PCD_TRY(sift_device(device, d_arena + first_row[a] * 128, n1, d_arena + first_row[b] * 128, n2, max_ratio,
-                          max_distance, cross_check, sc.m12.p, sc.m21.p, d_matches + 2 * match_offset[p], d_counts + p,
-                          sc, s, guided ? sc.guides.p : nullptr, th, tf));
-    }
-    return PCD_OK;
+  return PCD_OK;
+}
+
+// batches with a wide set run pair by pair through sift_device (the three-kernel compaction)
+static pcd_status sift_batch_pairwise(const SiftBatchArgs& a, SiftScratch& sc, hipStream_t s) {
+  for (int p = 0; p < a.n_pairs; ++p) {
+    const uint32_t i1 = a.pair_ids[2 * p], i2 = a.pair_ids[2 * p + 1];
+    const int n1 = (int)a.rows(i1), n2 = (int)a.rows(i2);
+    if (n1 == 0 || n2 == 0) { PCD_HIP_TRY(hipMemsetAsync(a.d_counts + p, 0, sizeof(int), s)); continue; }
+    PCD_TRY(sc.m12.reserve(n1)); PCD_TRY(sc.m21.reserve(n2));
+    const bool guided = a.guides && (a.guides[p].mode & (kSiftGuideH | kSiftGuideF));
+    if (guided)
+      PCD_TRY(sift_upload_guide(sc, s, a.d_locs + 2 * a.first_row[i1], n1, a.d_locs + 2 * a.first_row[i2], n2,
+                                a.guides[p].mode, a.guides[p].H, a.guides[p].F));
+    PCD_TRY(sift_device(a.d_arena + a.first_row[i1] * 128, n1, a.d_arena + a.first_row[i2] * 128, n2, a.max_ratio,
+                        a.max_distance, a.cross_check, sc.m12.p, sc.m21.p, a.d_matches + 2 * a.match_offset[p],
+                        a.d_counts + p, sc, s, guided ? sc.guides.p : nullptr, a.th, a.tf));
   }
-  // the prepared copy: every image padded to a multiple of 128 rows
-  std::vector<SiftImageDev> imgs((size_t)n_images);
-  uint64_t prows = 0;
-  uint32_t max_tiles = 0;
-  for (int i = 0; i < n_images; ++i) {
-    const uint64_t n = first_row[i + 1] - first_row[i];
-    imgs[i] = SiftImageDev{d_arena + first_row[i] * 128, (uint32_t)n, (uint32_t)prows};
-    const uint64_t tiles = (n + kSiftTile - 1) / kSiftTile;
-    max_tiles = std::max<uint32_t>(max_tiles, (uint32_t)tiles);
-    prows += tiles * kSiftTile;
+  return PCD_OK;
+}
+
+// the prepared copy: every image padded to a multiple of 128 rows, one behind the other
+struct SiftBatchLayout {
+  std::vector<SiftImageDev> images;
+  uint64_t prows = 0;       // rows of the copy
+  uint32_t max_tiles = 0;   // of the largest image
+};
+static SiftBatchLayout sift_batch_layout(const SiftBatchArgs& a) {
+  SiftBatchLayout l;
+  l.images.resize((size_t)a.n_images);
+  for (int i = 0; i < a.n_images; ++i) {
+    const uint64_t n = a.rows(i);
+    l.images[i] = SiftImageDev{a.d_arena + a.first_row[i] * 128, (uint32_t)n, (uint32_t)l.prows};
+    l.max_tiles = std::max<uint32_t>(l.max_tiles, (uint32_t)sift_tiles(n));
+    l.prows += sift_tiles(n) * kSiftTile;
   }
-  PCD_REQUIRE(prows + kSiftStripe < (1ull << 32), "arena larger than 2^32 descriptors");
-  PCD_TRY(sc.xa.reserve((prows + kSiftStripe) * 128)); PCD_TRY(sc.cc.reserve(prows + kSiftStripe));
-  // pair table for the whole call (uploaded once; sub-batches index into it)
-  std::vector<SiftPairDev> tab((size_t)n_pairs);
-  std::vector<int> cut;   // sub-batch boundaries
-  std::vector<int> cut_nchunk;
-  cut.push_back(0);
-  size_t max12 = 0, max21 = 0, maxm12 = 0, maxm21 = 0;
-  std::vector<SiftGuidePairDev> gtab(guides ? (size_t)n_pairs : 0);   // guided: records per sub-batch from 0
-  size_t maxrec = 0;
-  {
-    int p0 = 0;
-    while (p0 < n_pairs) {
-      // how many column chunks per row stripe: enough workgroups to fill the chip twice when the batch is small
-      // (decided on the first pair's size and the pairs left; any value gives the same results)
-      const uint32_t a0 = pair_ids[2 * p0], b0 = pair_ids[2 * p0 + 1];
-      const int nby0 = std::max<int>(1, (int)((first_row[a0 + 1] - first_row[a0] + kSiftTile - 1) / kSiftTile));
-      const int nbx0 = std::max<int>(1, (int)((first_row[b0 + 1] - first_row[b0] + kSiftTile - 1) / kSiftTile));
-      const long stripes0 = (nby0 * kSiftTile + kSiftStripe - 1) / kSiftStripe + (nbx0 * kSiftTile + kSiftStripe - 1) / kSiftStripe;   // stripes of both directions
-      const long left = n_pairs - p0;
-      const int nchunk_env = g_sift_nchunk.load(std::memory_order_relaxed);
-      const long want = nchunk_env > 0 ? std::min<long>(nchunk_env, std::max(nbx0, nby0))
-                                       : std::min<long>(std::max(nbx0, nby0), (512 + stripes0 * left - 1) / (stripes0 * left));
-      const int nchunk = (int)std::max<long>(1, want);
-      size_t o12 = 0, o21 = 0, om12 = 0, om21 = 0, orec = 0;
-      int p = p0;
-      for (; p < n_pairs; ++p) {
-        const uint32_t a = pair_ids[2 * p], b = pair_ids[2 * p + 1];
-        uint64_t n1 = first_row[a + 1] - first_row[a], n2 = first_row[b + 1] - first_row[b];
-        if (n1 == 0 || n2 == 0) n1 = n2 = 0;   // an empty image: no matches (sift_test.cc:311-318); every kernel skips the pair
-        const size_t need12 = (size_t)nchunk * n1, need21 = (size_t)nchunk * n2;
-        // (the budget counts 16-byte units: both partial arrays are int4; 2 z-slices per pair in the scores launch)
-        if (p > p0 && (o12 + need12 + o21 + need21 > budget || p - p0 >= 32767)) break;
-        tab[p] = SiftPairDev{imgs[a].prow, (uint32_t)n1, imgs[b].prow, (uint32_t)n2, o12, o21, om12, om21, match_offset[p]};
-        o12 += need12; o21 += need21; om12 += n1; om21 += n2;
-        if (guides) {
-          SiftGuidePairDev& g = gtab[p];
-          g = SiftGuidePairDev{};
-          g.loc1 = d_locs + 2 * first_row[a]; g.loc2 = d_locs + 2 * first_row[b];
-          g.n1 = (uint32_t)n1; g.n2 = (uint32_t)n2;
-          g.mode = guides[p].mode & (kSiftGuideH | kSiftGuideF);
-          std::memcpy(g.H, guides[p].H, sizeof(g.H)); std::memcpy(g.F, guides[p].F, sizeof(g.F));
-          g.rec1 = orec; orec += (n1 + kSiftTile - 1) / kSiftTile * kSiftRecTile;
-          g.rec2 = orec; orec += (n2 + kSiftTile - 1) / kSiftTile * kSiftRecTile;
-        }
+  return l;
+}
+
+// the sub-batches of a call: pairs [cut[k], cut[k + 1]) run in one launch set with nchunk[k] column chunks per walk
+struct SiftBatchPlan {
+  std::vector<SiftPairDev> pairs;         // for the whole call (uploaded once; sub-batches index into it)
+  std::vector<SiftGuidePairDev> guides;   // guided: beside pairs; partials, best matches and records of a sub-batch from 0
+  std::vector<int> cut, nchunk;
+  size_t max12 = 0, max21 = 0, maxm12 = 0, maxm21 = 0, maxrec = 0;   // the largest sub-batch's scratch, in elements
+};
+// Pure host arithmetic (device pointers are only offset).  nchunk_set / budget: pcd_sift_set_tuning's values or the
+// defaults; the budget counts 16-byte units: both partial arrays are int4.
+static SiftBatchPlan sift_batch_plan(const SiftBatchArgs& a, const std::vector<SiftImageDev>& images, int nchunk_set,
+                                     size_t budget) {
+  SiftBatchPlan pl;
+  pl.pairs.resize((size_t)a.n_pairs);
+  pl.guides.resize(a.guides ? (size_t)a.n_pairs : 0);
+  pl.cut.push_back(0);
+  for (int p0 = 0; p0 < a.n_pairs;) {
+    // how many column chunks per row stripe: enough workgroups to fill the chip twice when the batch is small
+    // (decided on the first pair's size and the pairs left; any value gives the same results)
+    const int nby0 = std::max<int>(1, (int)sift_tiles(a.rows(a.pair_ids[2 * p0])));
+    const int nbx0 = std::max<int>(1, (int)sift_tiles(a.rows(a.pair_ids[2 * p0 + 1])));
+    const long stripes0 = (nby0 * kSiftTile + kSiftStripe - 1) / kSiftStripe + (nbx0 * kSiftTile + kSiftStripe - 1) / kSiftStripe;   // stripes of both directions
+    const long left = a.n_pairs - p0;
+    const long want = nchunk_set > 0 ? nchunk_set : (512 + stripes0 * left - 1) / (stripes0 * left);
+    const int nchunk = (int)std::max<long>(1, std::min<long>(want, std::max(nbx0, nby0)));
+    size_t o12 = 0, o21 = 0, om12 = 0, om21 = 0, orec = 0;
+    int p = p0;
+    for (; p < a.n_pairs; ++p) {
+      const uint32_t i1 = a.pair_ids[2 * p], i2 = a.pair_ids[2 * p + 1];
+      uint64_t n1 = a.rows(i1), n2 = a.rows(i2);
+      if (n1 == 0 || n2 == 0) n1 = n2 = 0;   // an empty image: no matches (sift_test.cc:311-318); every kernel skips the pair
+      const size_t need12 = (size_t)nchunk * n1, need21 = (size_t)nchunk * n2;
+      // (2 z-slices per pair in the scores launch: at most 32767 pairs)
+      if (p > p0 && (o12 + need12 + o21 + need21 > budget || p - p0 >= 32767)) break;
+      pl.pairs[p] = SiftPairDev{images[i1].prow, (uint32_t)n1, images[i2].prow, (uint32_t)n2, o12, o21, om12, om21, a.match_offset[p]};
+      o12 += need12; o21 += need21; om12 += n1; om21 += n2;
+      if (a.guides) {
+        pl.guides[p] = sift_guide_entry(a.d_locs + 2 * a.first_row[i1], n1, a.d_locs + 2 * a.first_row[i2], n2, orec,
+                                        a.guides[p].mode, a.guides[p].H, a.guides[p].F);
+        orec = pl.guides[p].rec2 + sift_tiles(n2) * kSiftRecTile;
       }
-      max12 = std::max(max12, o12); max21 = std::max(max21, o21);
-      maxm12 = std::max(maxm12, om12); maxm21 = std::max(maxm21, om21);
-      maxrec = std::max(maxrec, orec);
-      cut.push_back(p);
-      cut_nchunk.push_back(nchunk);
-      p0 = p;
     }
+    pl.max12 = std::max(pl.max12, o12); pl.max21 = std::max(pl.max21, o21);
+    pl.maxm12 = std::max(pl.maxm12, om12); pl.maxm21 = std::max(pl.maxm21, om21);
+    pl.maxrec = std::max(pl.maxrec, orec);
+    pl.cut.push_back(p);
+    pl.nchunk.push_back(nchunk);
+    p0 = p;
   }
-  PCD_TRY(sc.pairs.reserve(n_pairs));
-  PCD_TRY(sc.part12.reserve(max12)); PCD_TRY(sc.part21.reserve(max21));
-  PCD_TRY(sc.m12.reserve(maxm12)); PCD_TRY(sc.m21.reserve(maxm21));
-  // the table goes up ON THE CALLER'S STREAM (a null-stream copy is not ordered against a non-blocking stream: a second
-  // call could overwrite sc.pairs under the first call's kernels); pinned staging, guarded by ev_tab
-  if (sc.tab_pending) PCD_HIP_TRY(hipEventSynchronize(sc.ev_tab));
-  PCD_TRY(sc.h_pairs.reserve(n_pairs)); PCD_TRY(sc.h_images.reserve(n_images)); PCD_TRY(sc.images.reserve(n_images));
-  std::memcpy(sc.h_pairs.p, tab.data(), sizeof(SiftPairDev) * (size_t)n_pairs);
-  std::memcpy(sc.h_images.p, imgs.data(), sizeof(SiftImageDev) * (size_t)n_images);
-  PCD_HIP_TRY(hipMemcpyAsync(sc.pairs.p, sc.h_pairs.p, sizeof(SiftPairDev) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-  PCD_HIP_TRY(hipMemcpyAsync(sc.images.p, sc.h_images.p, sizeof(SiftImageDev) * (size_t)n_images, hipMemcpyHostToDevice, s));
-  if (guides) {
-    PCD_TRY(sc.h_guides.reserve(n_pairs)); PCD_TRY(sc.guides.reserve(n_pairs)); PCD_TRY(sc.grec.reserve(maxrec));
-    std::memcpy(sc.h_guides.p, gtab.data(), sizeof(SiftGuidePairDev) * (size_t)n_pairs);
-    PCD_HIP_TRY(hipMemcpyAsync(sc.guides.p, sc.h_guides.p, sizeof(SiftGuidePairDev) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+  return pl;
+}
+
+// The tables go up ON THE CALLER'S STREAM (a null-stream copy is not ordered against a non-blocking stream: a second
+// call could overwrite sc.pairs under the first call's kernels); pinned staging, guarded by ev_tab.
+template <typename T>
+static pcd_status sift_upload_table(DevBuf<T>& dev, PinnedBuf<T>& pinned, const std::vector<T>& tab, hipStream_t s) {
+  PCD_TRY(pinned.reserve(tab.size())); PCD_TRY(dev.reserve(tab.size()));
+  std::memcpy(pinned.p, tab.data(), sizeof(T) * tab.size());
+  PCD_HIP_TRY(hipMemcpyAsync(dev.p, pinned.p, sizeof(T) * tab.size(), hipMemcpyHostToDevice, s));
+  return PCD_OK;
+}
+static pcd_status sift_batch_upload(SiftScratch& sc, hipStream_t s, const SiftBatchLayout& l, const SiftBatchPlan& pl) {
+  PCD_TRY(sift_tables_free(sc));
+  PCD_TRY(sift_upload_table(sc.pairs, sc.h_pairs, pl.pairs, s));
+  PCD_TRY(sift_upload_table(sc.images, sc.h_images, l.images, s));
+  if (!pl.guides.empty()) PCD_TRY(sift_upload_table(sc.guides, sc.h_guides, pl.guides, s));
+  return sift_tables_sent(sc, s);
+}
+
+// sub-batch k of the plan: (records,) scores, finalize, cross check + compaction
+static void sift_batch_launch(const SiftBatchArgs& a, const SiftBatchPlan& pl, size_t k, SiftScratch& sc, hipStream_t s) {
+  const int p0 = pl.cut[k], np = pl.cut[k + 1] - pl.cut[k], nchunk = pl.nchunk[k];
+  uint32_t mx1 = 0, mx2 = 0, mxsum = 0;
+  for (int p = p0; p < p0 + np; ++p) {
+    const SiftPairDev& pr = pl.pairs[p];
+    mx1 = std::max(mx1, pr.n1); mx2 = std::max(mx2, pr.n2); mxsum = std::max(mxsum, pr.n1 + pr.n2);
   }
-  PCD_HIP_TRY(hipEventRecord(sc.ev_tab, s));
-  sc.tab_pending = true;
-  if (max_tiles) {
-    ScopedKernelTimer t("sift_prep", s);
-    hipLaunchKernelGGL(k_sift_prep_images, dim3(max_tiles, n_images), dim3(256), 0, s, sc.images.p, sc.xa.p, sc.cc.p);
-  }
-  for (size_t k = 0; k + 1 < cut.size(); ++k) {
-    const int p0 = cut[k], np = cut[k + 1] - cut[k], nchunk = cut_nchunk[k];
-    uint32_t mx1 = 0, mx2 = 0, mxsum = 0;
-    for (int p = p0; p < p0 + np; ++p) {
-      mx1 = std::max(mx1, tab[p].n1); mx2 = std::max(mx2, tab[p].n2); mxsum = std::max(mxsum, tab[p].n1 + tab[p].n2);
-    }
-    if (mx1 && mx2) {
-      if (guides) {
-        {
-          ScopedKernelTimer t("sift_guide_prep", s);
-          hipLaunchKernelGGL(k_sift_guide_prep, dim3((std::max(mx1, mx2) + kSiftTile - 1) / kSiftTile, 2, np), dim3(kSiftTile),
-                             0, s, sc.guides.p + p0, sc.grec.p);
-        }
-        ScopedKernelTimer t("sift_guided_scores", s);
-        hipLaunchKernelGGL(k_sift_guided_batch, dim3(nchunk, (std::max(mx1, mx2) + kSiftStripe - 1) / kSiftStripe, 2 * np),
-                           dim3(64 * kSiftWaves), 0, s, sc.xa.p, sc.cc.p, sc.pairs.p + p0, sc.part12.p, sc.part21.p, nchunk,
-                           sc.guides.p + p0, sc.grec.p, th, tf);
-      } else {
-        ScopedKernelTimer t("sift_scores", s);
-        hipLaunchKernelGGL(k_sift_scores_batch, dim3(nchunk, (std::max(mx1, mx2) + kSiftStripe - 1) / kSiftStripe, 2 * np),
-                           dim3(64 * kSiftWaves), 0, s, sc.xa.p, sc.cc.p, sc.pairs.p + p0, sc.part12.p, sc.part21.p, nchunk);
-      }
-      {
-        ScopedKernelTimer t("sift_finalize", s);
-        hipLaunchKernelGGL(k_sift_finalize_batch, dim3(div_up((uint64_t)mxsum * 16, 256), 1, np), dim3(256), 0, s,
-                           sc.pairs.p + p0, sc.part12.p, sc.part21.p, nchunk, max_ratio, max_distance, sc.m12.p, sc.m21.p);
-      }
+  if (mx1 && mx2) {
+    const uint32_t mx = std::max(mx1, mx2);
+    const dim3 grid(nchunk, (mx + kSiftStripe - 1) / kSiftStripe, 2 * np), block(64 * kSiftWaves);
+    if (a.guides) {
+      ScopedKernelTimer t("sift_guide_prep", s);
+      hipLaunchKernelGGL(k_sift_guide_prep, dim3((unsigned)sift_tiles(mx), 2, np), dim3(kSiftTile), 0, s, sc.guides.p + p0,
+                         sc.grec.p);
     }
     {
-      ScopedKernelTimer t("sift_compact", s);
-      hipLaunchKernelGGL(k_sift_keep_compact_batch, dim3(np), dim3(1024), 0, s, sc.pairs.p + p0, sc.m12.p, sc.m21.p,
-                         cross_check, d_matches, d_counts + p0);
+      ScopedKernelTimer t(a.guides ? "sift_guided_scores" : "sift_scores", s);
+      if (a.guides)
+        hipLaunchKernelGGL(k_sift_guided_batch, grid, block, 0, s, sc.xa.p, sc.cc.p, sc.pairs.p + p0, sc.part12.p,
+                           sc.part21.p, nchunk, sc.guides.p + p0, sc.grec.p, a.th, a.tf);
+      else
+        hipLaunchKernelGGL(k_sift_scores_batch, grid, block, 0, s, sc.xa.p, sc.cc.p, sc.pairs.p + p0, sc.part12.p,
+                           sc.part21.p, nchunk);
     }
+    ScopedKernelTimer t("sift_finalize", s);
+    hipLaunchKernelGGL(k_sift_finalize_batch, dim3(div_up((uint64_t)mxsum * 16, 256), 1, np), dim3(256), 0, s,
+                       sc.pairs.p + p0, sc.part12.p, sc.part21.p, nchunk, a.max_ratio, a.max_distance, sc.m12.p, sc.m21.p);
   }
+  ScopedKernelTimer t("sift_compact", s);
+  hipLaunchKernelGGL(k_sift_keep_compact_batch, dim3(np), dim3(1024), 0, s, sc.pairs.p + p0, sc.m12.p, sc.m21.p,
+                     a.cross_check, a.d_matches, a.d_counts + p0);
+}
+
+static pcd_status sift_batch_device(const SiftBatchArgs& a, SiftScratch& sc, hipStream_t s) {
+  bool wide = false;
+  PCD_TRY(sift_batch_validate(a, &wide));
+  if (wide) return sift_batch_pairwise(a, sc, s);
+  const SiftBatchLayout l = sift_batch_layout(a);
+  PCD_REQUIRE(l.prows + kSiftStripe < (1ull << 32), "arena larger than 2^32 descriptors");
+  const uint64_t budget_set = g_sift_batch_partials.load(std::memory_order_relaxed);
+  const SiftBatchPlan pl = sift_batch_plan(a, l.images, g_sift_nchunk.load(std::memory_order_relaxed),
+                                           budget_set ? (size_t)budget_set : kSiftBatchPartials);
+  // (+ one stripe: a stripe's row fragments are read unconditionally)
+  PCD_TRY(sc.xa.reserve((l.prows + kSiftStripe) * 128)); PCD_TRY(sc.cc.reserve(l.prows + kSiftStripe));
+  PCD_TRY(sc.part12.reserve(pl.max12)); PCD_TRY(sc.part21.reserve(pl.max21));
+  PCD_TRY(sc.m12.reserve(pl.maxm12)); PCD_TRY(sc.m21.reserve(pl.maxm21));
+  if (a.guides) PCD_TRY(sc.grec.reserve(pl.maxrec));
+  PCD_TRY(sift_batch_upload(sc, s, l, pl));
+  if (l.max_tiles) {
+    ScopedKernelTimer t("sift_prep", s);
+    hipLaunchKernelGGL(k_sift_prep_images, dim3(l.max_tiles, a.n_images), dim3(256), 0, s, sc.images.p, sc.xa.p, sc.cc.p);
+  }
+  for (size_t k = 0; k + 1 < pl.cut.size(); ++k) sift_batch_launch(a, pl, k, sc, s);
   PCD_HIP_TRY(hipGetLastError());
   return PCD_OK;
+}
+
+// ---- the entry points' bodies: one per family, the guided and the unguided exported function call the same one -----
+// Argument checks in one order everywhere: sizes and the pointers every call needs, the device ordinal (before
+// g_sift[device] is indexed), require_device, no capturing stream, the empty input's early return, then the pointers a
+// non-empty input needs.
+
+// pair on the device; guided iff H || F (then d_loc1 / d_loc2 are needed), otherwise the unguided result
+static pcd_status sift_match_device(int device, const uint8_t* d_desc1, const float* d_loc1, int n1,
+                                    const uint8_t* d_desc2, const float* d_loc2, int n2, const float* H, const float* F,
+                                    float th, float tf, float max_ratio, float max_distance, int cross_check,
+                                    int32_t* d_m12, int32_t* d_m21, uint32_t* d_matches, int32_t* d_num_matches,
+                                    hipStream_t s) {
+  return pcd::guard([&]() -> pcd_status {
+  PCD_REQUIRE(n1 >= 0 && n2 >= 0 && d_num_matches, "sizes / count pointer");
+  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
+  PCD_TRY(require_device(device));
+  PCD_REFUSE_CAPTURE(s);
+  if (n1 == 0 || n2 == 0) {   // MatchSiftFeaturesCPU with an empty set: no matches (sift_test.cc:311-318, :462-474)
+    PCD_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
+    if (n1 && d_m12) PCD_HIP_TRY(hipMemsetAsync(d_m12, 0xFF, sizeof(int32_t) * n1, s));
+    if (n2 && d_m21) PCD_HIP_TRY(hipMemsetAsync(d_m21, 0xFF, sizeof(int32_t) * n2, s));
+    return PCD_OK;
+  }
+  const int mode = (H ? kSiftGuideH : 0) | (F ? kSiftGuideF : 0);
+  PCD_REQUIRE(d_desc1 && d_desc2 && d_m12 && d_m21 && d_matches && (!mode || (d_loc1 && d_loc2)), "null pointer");
+  return sift_use_scratch(device, s, [&](SiftScratch& sc) -> pcd_status {
+    if (mode) PCD_TRY(sift_upload_guide(sc, s, d_loc1, n1, d_loc2, n2, mode, H, F));
+    return sift_device(d_desc1, n1, d_desc2, n2, max_ratio, max_distance, cross_check, d_m12, d_m21, d_matches,
+                       d_num_matches, sc, s, mode ? sc.guides.p : nullptr, th, tf);
+  });
+  });
+}
+
+// the end of a host pair call: the count comes down, is clipped to the caller's capacity, that many matches follow
+static pcd_status sift_download_matches(const int32_t* d_count, const uint32_t* d_matches, int capacity, hipStream_t s,
+                                        uint32_t* matches, int32_t* num_matches) {
+  int cnt = 0;
+  PCD_HIP_TRY(hipMemcpyAsync(&cnt, d_count, sizeof(int), hipMemcpyDeviceToHost, s));
+  PCD_HIP_TRY(hipStreamSynchronize(s));
+  cnt = std::min(cnt, capacity);
+  if (cnt) PCD_HIP_TRY(hipMemcpy(matches, d_matches, 2 * (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  *num_matches = cnt;
+  return PCD_OK;
+}
+
+// pair from host memory (`matches` holds n1 entries)
+static pcd_status sift_match_host(int device, const uint8_t* desc1, const float* loc1, int n1, const uint8_t* desc2,
+                                  const float* loc2, int n2, const float* H, const float* F, float th, float tf,
+                                  float max_ratio, float max_distance, int cross_check, uint32_t* matches,
+                                  int32_t* num_matches) {
+  return pcd::guard([&]() -> pcd_status {
+  PCD_REQUIRE(num_matches && n1 >= 0 && n2 >= 0, "sizes / count pointer");
+  *num_matches = 0;
+  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
+  PCD_TRY(require_device(device));
+  if (n1 == 0 || n2 == 0) return PCD_OK;
+  const bool guided = H || F;
+  PCD_REQUIRE(desc1 && desc2 && matches && (!guided || (loc1 && loc2)), "null pointer");
+  hipStream_t s = nullptr;
+  // the whole host call: it owns the scratch's d1 / d2 / m12 / matches until it has synchronised
+  return sift_use_scratch(device, s, [&](SiftScratch& sc) -> pcd_status {
+    PCD_TRY(sc.d1.reserve((size_t)n1 * 128)); PCD_TRY(sc.d2.reserve((size_t)n2 * 128));
+    PCD_TRY(sc.m12.reserve(n1)); PCD_TRY(sc.m21.reserve(n2)); PCD_TRY(sc.matches.reserve(2 * (size_t)n1));
+    PCD_TRY(sc.count.reserve(1));
+    PCD_HIP_TRY(hipMemcpyAsync(sc.d1.p, desc1, (size_t)n1 * 128, hipMemcpyHostToDevice, s));
+    PCD_HIP_TRY(hipMemcpyAsync(sc.d2.p, desc2, (size_t)n2 * 128, hipMemcpyHostToDevice, s));
+    if (guided) {
+      PCD_TRY(sc.loc1.reserve(2 * (size_t)n1)); PCD_TRY(sc.loc2.reserve(2 * (size_t)n2));
+      PCD_HIP_TRY(hipMemcpyAsync(sc.loc1.p, loc1, 2 * sizeof(float) * (size_t)n1, hipMemcpyHostToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(sc.loc2.p, loc2, 2 * sizeof(float) * (size_t)n2, hipMemcpyHostToDevice, s));
+    }
+    PCD_TRY(sift_match_device(device, sc.d1.p, sc.loc1.p, n1, sc.d2.p, sc.loc2.p, n2, H, F, th, tf, max_ratio,
+                              max_distance, cross_check, sc.m12.p, sc.m21.p, sc.matches.p, sc.count.p, s));
+    return sift_download_matches(sc.count.p, sc.matches.p, n1, s, matches, num_matches);
+  });
+  });
+}
+
+// batch on the device (guided: `guides` is needed, and d_locs beside a non-empty arena)
+static pcd_status sift_match_batch_device(int device, bool guided, const SiftBatchArgs& a, hipStream_t s) {
+  return pcd::guard([&]() -> pcd_status {
+  PCD_REQUIRE(a.n_images >= 0 && a.n_pairs >= 0 && a.first_row, "sizes / first_row");
+  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
+  PCD_TRY(require_device(device));
+  PCD_REFUSE_CAPTURE(s);
+  if (a.n_pairs == 0) return PCD_OK;
+  PCD_REQUIRE(a.pair_ids && a.match_offset && a.d_counts && a.d_matches && (!guided || a.guides), "null pointer");
+  PCD_REQUIRE(a.first_row[a.n_images] == 0 || (a.d_arena && (!guided || a.d_locs)), "null arena / locations");
+  for (int p = 0; guided && p < a.n_pairs; ++p)
+    PCD_REQUIRE(a.guides[p].mode >= PCD_SIFT_GUIDE_NONE && a.guides[p].mode <= PCD_SIFT_GUIDE_HF, "guide mode");
+  return sift_use_scratch(device, s, [&](SiftScratch& sc) { return sift_batch_device(a, sc, s); });
+  });
+}
+
+// batch from host memory (locs / guides: the guided one)
+static pcd_status sift_match_batch_host(int device, const uint8_t* arena, const float* locs, const uint64_t* first_row,
+                                        int n_images, const uint32_t* pairs, int n_pairs, const pcd_sift_guide* guides,
+                                        float th, float tf, float max_ratio, float max_distance, int cross_check,
+                                        uint32_t* matches, uint64_t matches_capacity, uint64_t* list_offset) {
+  return pcd::guard([&]() -> pcd_status {
+  PCD_REQUIRE(n_images >= 0 && n_pairs >= 0 && first_row && list_offset, "sizes / first_row / list_offset");
+  list_offset[0] = 0;
+  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
+  PCD_TRY(require_device(device));
+  if (n_pairs == 0) return PCD_OK;
+  PCD_REQUIRE(pairs, "null pair list");
+  const uint64_t rows = first_row[n_images];
+  PCD_REQUIRE(rows == 0 || (arena && (!guides || locs)), "null arena / locations");
+  // the whole host call: arena / matches / counts / dense are the device's shared scratch
+  return sift_use_scratch(device, nullptr, [&](SiftScratch& sc) -> pcd_status {
+    hipStream_t s = nullptr;
+    // worst-case list of pair p: one match per descriptor of its first image
+    std::vector<uint64_t> off((size_t)n_pairs + 1, 0);
+    for (int p = 0; p < n_pairs; ++p) {
+      PCD_REQUIRE(pairs[2 * p] < (uint32_t)n_images && pairs[2 * p + 1] < (uint32_t)n_images, "pair names an image outside the arena");
+      off[p + 1] = off[p] + (first_row[pairs[2 * p] + 1] - first_row[pairs[2 * p]]);
+    }
+    PCD_TRY(sc.arena.reserve(rows * 128)); PCD_TRY(sc.matches.reserve(2 * off[n_pairs] + 2));
+    PCD_TRY(sc.counts.reserve(n_pairs)); PCD_TRY(sc.dense_off.reserve(2 * ((size_t)n_pairs + 1)));
+    if (rows) PCD_HIP_TRY(hipMemcpy(sc.arena.p, arena, rows * 128, hipMemcpyHostToDevice));
+    if (guides) {
+      PCD_TRY(sc.locs.reserve(2 * rows));
+      if (rows) PCD_HIP_TRY(hipMemcpy(sc.locs.p, locs, rows * 2 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    PCD_TRY(sift_match_batch_device(device, guides != nullptr,
+                                    SiftBatchArgs{sc.arena.p, sc.locs.p, first_row, n_images, pairs, n_pairs, guides, th, tf,
+                                                  max_ratio, max_distance, cross_check, sc.matches.p, off.data(),
+                                                  sc.counts.p},
+                                    s));
+    std::vector<int> cnt((size_t)n_pairs);
+    PCD_HIP_TRY(hipMemcpy(cnt.data(), sc.counts.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    for (int p = 0; p < n_pairs; ++p) list_offset[p + 1] = list_offset[p] + (uint64_t)cnt[p];
+    const uint64_t total = list_offset[n_pairs];
+    if (total > matches_capacity) {
+      set_error("pcd_sift_match_batch: %llu matches, capacity %llu", (unsigned long long)total, (unsigned long long)matches_capacity);
+      return PCD_ERR_INVALID;
+    }
+    if (total == 0) return PCD_OK;
+    PCD_REQUIRE(matches, "null match buffer");
+    // pack the lists back to back on the device: one download of exactly the matches
+    PCD_TRY(sc.dense.reserve(2 * total));
+    const size_t np1 = (size_t)n_pairs + 1;
+    PCD_HIP_TRY(hipMemcpy(sc.dense_off.p, list_offset, sizeof(uint64_t) * np1, hipMemcpyHostToDevice));
+    PCD_HIP_TRY(hipMemcpy(sc.dense_off.p + np1, off.data(), sizeof(uint64_t) * np1, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_sift_pack_lists, dim3(n_pairs), dim3(256), 0, s, sc.dense_off.p + np1, sc.counts.p,
+                       sc.dense_off.p, sc.matches.p, sc.dense.p);
+    PCD_HIP_TRY(hipGetLastError());
+    PCD_HIP_TRY(hipMemcpy(matches, sc.dense.p, 2 * total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return PCD_OK;
+  });
+  });
+}
+}  // namespace pcd
+
+// ---- matcher handle: two descriptor slots resident on the device (SiftMatchGPU's usage pattern) ----
+struct pcd_sift_matcher {
+  int device = 0;
+  int max_sift = 4096;
+  int n[2] = {0, 0};
+  pcd::DevBuf<uint8_t> d[2];
+  pcd::DevBuf<float> loc[2];
+  bool loc_ok[2] = {false, false};   // the slot's locations belong to its current descriptors
+  pcd::DevBuf<int32_t> m12, m21, count;
+  pcd::DevBuf<uint32_t> matches;
+};
+
+namespace pcd {
+// GetSiftMatch / GetGuidedSiftMatch (guided iff H || F): at most max_match matches, in ascending index of set 0
+static pcd_status sift_matcher_match(pcd_sift_matcher* m, int max_match, uint32_t* matches, const float* H,
+                                     const float* F, float distmax, float ratiomax, float hdistmax, float fdistmax,
+                                     int mutual_best_match, int32_t* num_matches) {
+  PCD_REQUIRE(m && num_matches && max_match >= 0, "null pointer");
+  *num_matches = 0;
+  const int n1 = m->n[0], n2 = m->n[1];
+  if (n1 == 0 || n2 == 0 || max_match == 0) return PCD_OK;
+  if ((H || F) && (!m->loc_ok[0] || !m->loc_ok[1])) {
+    set_error("pcd_sift_matcher_match_guided: a slot's descriptors were set after its locations (or none were set)");
+    return PCD_ERR_INVALID;
+  }
+  PCD_REQUIRE(matches, "null match buffer");
+  PCD_HIP_TRY(hipSetDevice(m->device));
+  PCD_TRY(m->m12.reserve(n1)); PCD_TRY(m->m21.reserve(n2)); PCD_TRY(m->matches.reserve(2 * (size_t)n1));
+  PCD_TRY(m->count.reserve(1));
+  hipStream_t s = nullptr;
+  PCD_TRY(sift_match_device(m->device, m->d[0].p, m->loc[0].p, n1, m->d[1].p, m->loc[1].p, n2, H, F, hdistmax, fdistmax,
+                            ratiomax, distmax, mutual_best_match, m->m12.p, m->m21.p, m->matches.p, m->count.p, s));
+  return sift_download_matches(m->count.p, m->matches.p, max_match, s, matches, num_matches);
 }
 }  // namespace pcd
 
@@ -1104,163 +1346,37 @@ using namespace pcd;
 extern "C" {
 
 /* tuning hook (tests, fuzzing; not part of the stable ABI): force the number of column chunks of a stripe walk and the
- * bytes of partial results per sub-batch of pcd_sift_match_batch; 0 = the library's choice */
-pcd_status pcd_sift_set_tuning(int nchunk, uint64_t batch_partials_bytes) {
+ * partial results per sub-batch of pcd_sift_match_batch, counted in int4 elements (16-byte units); 0 = the library's
+ * choice */
+pcd_status pcd_sift_set_tuning(int nchunk, uint64_t batch_partials_int4) {
   PCD_REQUIRE(nchunk >= 0, "nchunk");
   g_sift_nchunk.store(nchunk, std::memory_order_relaxed);
-  g_sift_batch_partials.store(batch_partials_bytes, std::memory_order_relaxed);
+  g_sift_batch_partials.store(batch_partials_int4, std::memory_order_relaxed);
   return PCD_OK;
 }
 
 pcd_status pcd_sift_match_device(int device, const uint8_t* d_desc1, int n1, const uint8_t* d_desc2, int n2,
                                  float max_ratio, float max_distance, int cross_check, int32_t* d_m12,
                                  int32_t* d_m21, uint32_t* d_matches, int32_t* d_num_matches, void* stream) {
-  return pcd::guard([&]() -> pcd_status {
-  PCD_REQUIRE(n1 >= 0 && n2 >= 0 && d_num_matches, "sizes / count pointer");
-  PCD_REFUSE_CAPTURE(stream);
-  PCD_TRY(require_device(device));
-  hipStream_t s = (hipStream_t)stream;
-  if (n1 == 0 || n2 == 0) {   // MatchSiftFeaturesCPU with an empty set: no matches (sift_test.cc:311-318)
-    PCD_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
-    if (n1 && d_m12) PCD_HIP_TRY(hipMemsetAsync(d_m12, 0xFF, sizeof(int32_t) * n1, s));
-    if (n2 && d_m21) PCD_HIP_TRY(hipMemsetAsync(d_m21, 0xFF, sizeof(int32_t) * n2, s));
-    return PCD_OK;
-  }
-  PCD_REQUIRE(d_desc1 && d_desc2 && d_m12 && d_m21 && d_matches, "null pointer");
-  PCD_REQUIRE(device < 64, "device ordinal");
-  SiftLock g(g_sift_mu);
-  PCD_HIP_TRY(hipSetDevice(device));
-  if (!g_sift[device]) g_sift[device] = new SiftScratch();
-  PCD_TRY(sift_begin_use(*g_sift[device], s));
-  const pcd_status st = sift_device(device, d_desc1, n1, d_desc2, n2, max_ratio, max_distance, cross_check, d_m12, d_m21,
-                                    d_matches, d_num_matches, *g_sift[device], s);
-  PCD_TRY(sift_end_use(*g_sift[device], s));
-  return st;
-  });
+  return sift_match_device(device, d_desc1, nullptr, n1, d_desc2, nullptr, n2, nullptr, nullptr, 0.f, 0.f, max_ratio,
+                           max_distance, cross_check, d_m12, d_m21, d_matches, d_num_matches, (hipStream_t)stream);
 }
 
 pcd_status pcd_sift_match(int device, const uint8_t* desc1, int n1, const uint8_t* desc2, int n2, float max_ratio,
                           float max_distance, int cross_check, uint32_t* matches, int32_t* num_matches) {
-  return pcd::guard([&]() -> pcd_status {
-  PCD_REQUIRE(num_matches && n1 >= 0 && n2 >= 0, "sizes / count pointer");
-  *num_matches = 0;
-  if (n1 == 0 || n2 == 0) return PCD_OK;
-  PCD_REQUIRE(desc1 && desc2 && matches, "null pointer");
-  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
-  PCD_TRY(require_device(device));
-  SiftLock g(g_sift_mu);   // the whole host call: it owns the scratch's d1 / d2 / m12 / matches until it has synchronised
-  PCD_HIP_TRY(hipSetDevice(device));
-  if (!g_sift[device]) g_sift[device] = new SiftScratch();
-  SiftScratch* sc = g_sift[device];
-  hipStream_t s = nullptr;
-  PCD_TRY(sift_begin_use(*sc, s));   // an earlier *_device call on another stream may still be reading the scratch
-  PCD_TRY(sc->d1.reserve((size_t)n1 * 128)); PCD_TRY(sc->d2.reserve((size_t)n2 * 128));
-  PCD_TRY(sc->m12.reserve(n1)); PCD_TRY(sc->m21.reserve(n2)); PCD_TRY(sc->matches.reserve(2 * (size_t)n1));
-  PCD_TRY(sc->count.reserve(1));
-  PCD_HIP_TRY(hipMemcpyAsync(sc->d1.p, desc1, (size_t)n1 * 128, hipMemcpyHostToDevice, s));
-  PCD_HIP_TRY(hipMemcpyAsync(sc->d2.p, desc2, (size_t)n2 * 128, hipMemcpyHostToDevice, s));
-  PCD_TRY(pcd_sift_match_device(device, sc->d1.p, n1, sc->d2.p, n2, max_ratio, max_distance, cross_check, sc->m12.p,
-                                sc->m21.p, sc->matches.p, sc->count.p, s));
-  int cnt = 0;
-  PCD_HIP_TRY(hipMemcpyAsync(&cnt, sc->count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  PCD_HIP_TRY(hipStreamSynchronize(s));
-  if (cnt) PCD_HIP_TRY(hipMemcpy(matches, sc->matches.p, 2 * (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  *num_matches = cnt;
-  return PCD_OK;
-  });
+  return sift_match_host(device, desc1, nullptr, n1, desc2, nullptr, n2, nullptr, nullptr, 0.f, 0.f, max_ratio,
+                         max_distance, cross_check, matches, num_matches);
 }
-
 
 pcd_status pcd_sift_match_batch_device(int device, const uint8_t* d_arena, const uint64_t* first_row, int n_images,
                                        const uint32_t* pairs, int n_pairs, float max_ratio, float max_distance,
                                        int cross_check, uint32_t* d_matches, const uint64_t* match_offset,
                                        int32_t* d_counts, void* stream) {
-  return pcd::guard([&]() -> pcd_status {
-  PCD_REQUIRE(n_images >= 0 && n_pairs >= 0 && first_row, "sizes / first_row");
-  PCD_REFUSE_CAPTURE(stream);
-  if (n_pairs == 0) return PCD_OK;
-  PCD_REQUIRE(pairs && match_offset && d_counts && d_matches, "null pointer");
-  PCD_REQUIRE(first_row[n_images] == 0 || d_arena, "null arena");
-  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
-  PCD_TRY(require_device(device));
-  SiftLock g(g_sift_mu);
-  PCD_HIP_TRY(hipSetDevice(device));
-  if (!g_sift[device]) g_sift[device] = new SiftScratch();
-  PCD_TRY(sift_begin_use(*g_sift[device], (hipStream_t)stream));
-  const pcd_status st = sift_batch_device(device, d_arena, first_row, n_images, pairs, n_pairs, max_ratio, max_distance,
-                                          cross_check, d_matches, match_offset, d_counts, *g_sift[device],
-                                          (hipStream_t)stream);
-  PCD_TRY(sift_end_use(*g_sift[device], (hipStream_t)stream));
-  return st;
-  });
+  return sift_match_batch_device(device, false,
+                                 SiftBatchArgs{d_arena, nullptr, first_row, n_images, pairs, n_pairs, nullptr, 0.f, 0.f,
+                                               max_ratio, max_distance, cross_check, d_matches, match_offset, d_counts},
+                                 (hipStream_t)stream);
 }
-
-}  // extern "C"
-
-// host form of the batch entries (locs / guides: the guided one)
-static pcd_status sift_match_batch_host(int device, const uint8_t* arena, const float* locs, const uint64_t* first_row,
-                                        int n_images, const uint32_t* pairs, int n_pairs, const pcd_sift_guide* guides,
-                                        float th, float tf, float max_ratio, float max_distance, int cross_check,
-                                        uint32_t* matches, uint64_t matches_capacity, uint64_t* list_offset) {
-  return pcd::guard([&]() -> pcd_status {
-  PCD_REQUIRE(n_images >= 0 && n_pairs >= 0 && first_row && list_offset, "sizes / first_row / list_offset");
-  list_offset[0] = 0;
-  if (n_pairs == 0) return PCD_OK;
-  PCD_REQUIRE(pairs, "null pair list");
-  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
-  PCD_TRY(require_device(device));
-  const uint64_t rows = first_row[n_images];
-  PCD_REQUIRE(rows == 0 || arena, "null arena");
-  SiftLock g(g_sift_mu);   // the whole host call: arena / matches / counts / dense are the device's shared scratch
-  PCD_HIP_TRY(hipSetDevice(device));
-  if (!g_sift[device]) g_sift[device] = new SiftScratch();
-  SiftScratch* sc = g_sift[device];
-  PCD_TRY(sift_begin_use(*sc, nullptr));
-  // worst-case list of pair p: one match per descriptor of its first image
-  std::vector<uint64_t> off((size_t)n_pairs + 1, 0);
-  for (int p = 0; p < n_pairs; ++p) {
-    PCD_REQUIRE(pairs[2 * p] < (uint32_t)n_images && pairs[2 * p + 1] < (uint32_t)n_images, "pair names an image outside the arena");
-    off[p + 1] = off[p] + (first_row[pairs[2 * p] + 1] - first_row[pairs[2 * p]]);
-  }
-  PCD_TRY(sc->arena.reserve(rows * 128)); PCD_TRY(sc->matches.reserve(2 * off[n_pairs] + 2));
-  PCD_TRY(sc->counts.reserve(n_pairs)); PCD_TRY(sc->dense_off.reserve(2 * ((size_t)n_pairs + 1)));
-  hipStream_t s = nullptr;
-  if (rows) PCD_HIP_TRY(hipMemcpy(sc->arena.p, arena, rows * 128, hipMemcpyHostToDevice));
-  if (guides) {
-    PCD_REQUIRE(rows == 0 || locs, "null locations");
-    PCD_TRY(sc->locs.reserve(2 * rows));
-    if (rows) PCD_HIP_TRY(hipMemcpy(sc->locs.p, locs, rows * 2 * sizeof(float), hipMemcpyHostToDevice));
-    PCD_TRY(pcd_sift_match_guided_batch_device(device, sc->arena.p, sc->locs.p, first_row, n_images, pairs, n_pairs,
-                                               guides, th, tf, max_ratio, max_distance, cross_check, sc->matches.p,
-                                               off.data(), sc->counts.p, s));
-  } else {
-    PCD_TRY(pcd_sift_match_batch_device(device, sc->arena.p, first_row, n_images, pairs, n_pairs, max_ratio, max_distance,
-                                        cross_check, sc->matches.p, off.data(), sc->counts.p, s));
-  }
-  std::vector<int> cnt((size_t)n_pairs);
-  PCD_HIP_TRY(hipMemcpy(cnt.data(), sc->counts.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost));
-  for (int p = 0; p < n_pairs; ++p) list_offset[p + 1] = list_offset[p] + (uint64_t)cnt[p];
-  const uint64_t total = list_offset[n_pairs];
-  if (total > matches_capacity) {
-    set_error("pcd_sift_match_batch: %llu matches, capacity %llu", (unsigned long long)total, (unsigned long long)matches_capacity);
-    return PCD_ERR_INVALID;
-  }
-  if (total == 0) return PCD_OK;
-  PCD_REQUIRE(matches, "null match buffer");
-  // pack the lists back to back on the device: one download of exactly the matches
-  PCD_TRY(sc->dense.reserve(2 * total));
-  const size_t np1 = (size_t)n_pairs + 1;
-  PCD_HIP_TRY(hipMemcpy(sc->dense_off.p, list_offset, sizeof(uint64_t) * np1, hipMemcpyHostToDevice));
-  PCD_HIP_TRY(hipMemcpy(sc->dense_off.p + np1, off.data(), sizeof(uint64_t) * np1, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_sift_pack_lists, dim3(n_pairs), dim3(256), 0, s, sc->dense_off.p + np1, sc->counts.p,
-                     sc->dense_off.p, sc->matches.p, sc->dense.p);
-  PCD_HIP_TRY(hipGetLastError());
-  PCD_HIP_TRY(hipMemcpy(matches, sc->dense.p, 2 * total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return PCD_OK;
-  });
-}
-
-extern "C" {
 
 pcd_status pcd_sift_match_batch(int device, const uint8_t* arena, const uint64_t* first_row, int n_images,
                                 const uint32_t* pairs, int n_pairs, float max_ratio, float max_distance, int cross_check,
@@ -1269,78 +1385,23 @@ pcd_status pcd_sift_match_batch(int device, const uint8_t* arena, const uint64_t
                                max_distance, cross_check, matches, matches_capacity, list_offset);
 }
 
-// ---- guided matching (feature/sift.cc:1092-1162, lib/SiftGPU/SiftGPU.h:331-352) ----
+// ---- guided matching (feature/sift.cc:1092-1162, lib/SiftGPU/SiftGPU.h:331-352); neither matrix: the unguided result
 pcd_status pcd_sift_match_guided_device(int device, const uint8_t* d_desc1, const float* d_loc1, int n1,
                                         const uint8_t* d_desc2, const float* d_loc2, int n2, const float* H,
                                         const float* F, float h_max_residual, float f_max_residual, float max_ratio,
                                         float max_distance, int cross_check, int32_t* d_m12, int32_t* d_m21,
                                         uint32_t* d_matches, int32_t* d_num_matches, void* stream) {
-  if (!H && !F)   // no geometry: the unguided result
-    return pcd_sift_match_device(device, d_desc1, n1, d_desc2, n2, max_ratio, max_distance, cross_check, d_m12, d_m21,
-                                 d_matches, d_num_matches, stream);
-  return pcd::guard([&]() -> pcd_status {
-  PCD_REQUIRE(n1 >= 0 && n2 >= 0 && d_num_matches, "sizes / count pointer");
-  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
-  PCD_TRY(require_device(device));
-  PCD_REFUSE_CAPTURE(stream);
-  hipStream_t s = (hipStream_t)stream;
-  if (n1 == 0 || n2 == 0) {   // sift_test.cc:462-474: an empty set, no matches
-    PCD_HIP_TRY(hipMemsetAsync(d_num_matches, 0, sizeof(int32_t), s));
-    if (n1 && d_m12) PCD_HIP_TRY(hipMemsetAsync(d_m12, 0xFF, sizeof(int32_t) * n1, s));
-    if (n2 && d_m21) PCD_HIP_TRY(hipMemsetAsync(d_m21, 0xFF, sizeof(int32_t) * n2, s));
-    return PCD_OK;
-  }
-  PCD_REQUIRE(d_desc1 && d_desc2 && d_loc1 && d_loc2 && d_m12 && d_m21 && d_matches, "null pointer");
-  SiftLock g(g_sift_mu);
-  PCD_HIP_TRY(hipSetDevice(device));
-  if (!g_sift[device]) g_sift[device] = new SiftScratch();
-  SiftScratch& sc = *g_sift[device];
-  PCD_TRY(sift_begin_use(sc, s));
-  PCD_TRY(sift_upload_guide(sc, s, d_loc1, n1, d_loc2, n2, H, F));
-  const pcd_status st = sift_device(device, d_desc1, n1, d_desc2, n2, max_ratio, max_distance, cross_check, d_m12, d_m21,
-                                    d_matches, d_num_matches, sc, s, sc.guides.p, h_max_residual, f_max_residual);
-  PCD_TRY(sift_end_use(sc, s));
-  return st;
-  });
+  return sift_match_device(device, d_desc1, d_loc1, n1, d_desc2, d_loc2, n2, H, F, h_max_residual, f_max_residual,
+                           max_ratio, max_distance, cross_check, d_m12, d_m21, d_matches, d_num_matches,
+                           (hipStream_t)stream);
 }
 
 pcd_status pcd_sift_match_guided(int device, const uint8_t* desc1, const float* loc1, int n1, const uint8_t* desc2,
                                  const float* loc2, int n2, const float* H, const float* F, float h_max_residual,
                                  float f_max_residual, float max_ratio, float max_distance, int cross_check,
                                  uint32_t* matches, int32_t* num_matches) {
-  if (!H && !F)
-    return pcd_sift_match(device, desc1, n1, desc2, n2, max_ratio, max_distance, cross_check, matches, num_matches);
-  return pcd::guard([&]() -> pcd_status {
-  PCD_REQUIRE(num_matches && n1 >= 0 && n2 >= 0, "sizes / count pointer");
-  *num_matches = 0;
-  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
-  PCD_TRY(require_device(device));
-  if (n1 == 0 || n2 == 0) return PCD_OK;
-  PCD_REQUIRE(desc1 && desc2 && loc1 && loc2 && matches, "null pointer");
-  SiftLock g(g_sift_mu);
-  PCD_HIP_TRY(hipSetDevice(device));
-  if (!g_sift[device]) g_sift[device] = new SiftScratch();
-  SiftScratch* sc = g_sift[device];
-  hipStream_t s = nullptr;
-  PCD_TRY(sift_begin_use(*sc, s));
-  PCD_TRY(sc->d1.reserve((size_t)n1 * 128)); PCD_TRY(sc->d2.reserve((size_t)n2 * 128));
-  PCD_TRY(sc->loc1.reserve(2 * (size_t)n1)); PCD_TRY(sc->loc2.reserve(2 * (size_t)n2));
-  PCD_TRY(sc->m12.reserve(n1)); PCD_TRY(sc->m21.reserve(n2)); PCD_TRY(sc->matches.reserve(2 * (size_t)n1));
-  PCD_TRY(sc->count.reserve(1));
-  PCD_HIP_TRY(hipMemcpyAsync(sc->d1.p, desc1, (size_t)n1 * 128, hipMemcpyHostToDevice, s));
-  PCD_HIP_TRY(hipMemcpyAsync(sc->d2.p, desc2, (size_t)n2 * 128, hipMemcpyHostToDevice, s));
-  PCD_HIP_TRY(hipMemcpyAsync(sc->loc1.p, loc1, 2 * sizeof(float) * (size_t)n1, hipMemcpyHostToDevice, s));
-  PCD_HIP_TRY(hipMemcpyAsync(sc->loc2.p, loc2, 2 * sizeof(float) * (size_t)n2, hipMemcpyHostToDevice, s));
-  PCD_TRY(pcd_sift_match_guided_device(device, sc->d1.p, sc->loc1.p, n1, sc->d2.p, sc->loc2.p, n2, H, F, h_max_residual,
-                                       f_max_residual, max_ratio, max_distance, cross_check, sc->m12.p, sc->m21.p,
-                                       sc->matches.p, sc->count.p, s));
-  int cnt = 0;
-  PCD_HIP_TRY(hipMemcpyAsync(&cnt, sc->count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  PCD_HIP_TRY(hipStreamSynchronize(s));
-  if (cnt) PCD_HIP_TRY(hipMemcpy(matches, sc->matches.p, 2 * (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  *num_matches = cnt;
-  return PCD_OK;
-  });
+  return sift_match_host(device, desc1, loc1, n1, desc2, loc2, n2, H, F, h_max_residual, f_max_residual, max_ratio,
+                         max_distance, cross_check, matches, num_matches);
 }
 
 pcd_status pcd_sift_match_guided_batch_device(int device, const uint8_t* d_arena, const float* d_locs,
@@ -1349,26 +1410,11 @@ pcd_status pcd_sift_match_guided_batch_device(int device, const uint8_t* d_arena
                                               float f_max_residual, float max_ratio, float max_distance,
                                               int cross_check, uint32_t* d_matches, const uint64_t* match_offset,
                                               int32_t* d_counts, void* stream) {
-  return pcd::guard([&]() -> pcd_status {
-  PCD_REQUIRE(n_images >= 0 && n_pairs >= 0 && first_row, "sizes / first_row");
-  PCD_REQUIRE(device >= 0 && device < 64, "device ordinal");
-  PCD_TRY(require_device(device));
-  PCD_REFUSE_CAPTURE(stream);
-  if (n_pairs == 0) return PCD_OK;
-  PCD_REQUIRE(pairs && match_offset && d_counts && d_matches && guides, "null pointer");
-  PCD_REQUIRE(first_row[n_images] == 0 || (d_arena && d_locs), "null arena / locations");
-  for (int p = 0; p < n_pairs; ++p)
-    PCD_REQUIRE(guides[p].mode >= PCD_SIFT_GUIDE_NONE && guides[p].mode <= PCD_SIFT_GUIDE_HF, "guide mode");
-  SiftLock g(g_sift_mu);
-  PCD_HIP_TRY(hipSetDevice(device));
-  if (!g_sift[device]) g_sift[device] = new SiftScratch();
-  PCD_TRY(sift_begin_use(*g_sift[device], (hipStream_t)stream));
-  const pcd_status st = sift_batch_device(device, d_arena, first_row, n_images, pairs, n_pairs, max_ratio, max_distance,
-                                          cross_check, d_matches, match_offset, d_counts, *g_sift[device],
-                                          (hipStream_t)stream, d_locs, guides, h_max_residual, f_max_residual);
-  PCD_TRY(sift_end_use(*g_sift[device], (hipStream_t)stream));
-  return st;
-  });
+  return sift_match_batch_device(device, true,
+                                 SiftBatchArgs{d_arena, d_locs, first_row, n_images, pairs, n_pairs, guides,
+                                               h_max_residual, f_max_residual, max_ratio, max_distance, cross_check,
+                                               d_matches, match_offset, d_counts},
+                                 (hipStream_t)stream);
 }
 
 pcd_status pcd_sift_match_guided_batch(int device, const uint8_t* arena, const float* locs, const uint64_t* first_row,
@@ -1381,21 +1427,6 @@ pcd_status pcd_sift_match_guided_batch(int device, const uint8_t* arena, const f
                                f_max_residual, max_ratio, max_distance, cross_check, matches, matches_capacity,
                                list_offset);
 }
-// ---- matcher handle: two descriptor slots resident on the device (SiftMatchGPU's usage pattern) ----
-}  // extern "C"
-
-struct pcd_sift_matcher {
-  int device = 0;
-  int max_sift = 4096;
-  int n[2] = {0, 0};
-  pcd::DevBuf<uint8_t> d[2];
-  pcd::DevBuf<float> loc[2];
-  bool loc_ok[2] = {false, false};   // the slot's locations belong to its current descriptors
-  pcd::DevBuf<int32_t> m12, m21, count;
-  pcd::DevBuf<uint32_t> matches;
-};
-
-extern "C" {
 
 pcd_status pcd_sift_matcher_create(int device, int max_sift, pcd_sift_matcher** out) {
   return pcd::guard([&]() -> pcd_status {
@@ -1437,29 +1468,6 @@ pcd_status pcd_sift_matcher_set_descriptors(pcd_sift_matcher* m, int index, int 
   return PCD_OK;
 }
 
-// SiftMatchGPU::GetSiftMatch: number of matches written (at most max_match, in ascending index of set 0)
-pcd_status pcd_sift_matcher_match(pcd_sift_matcher* m, int max_match, uint32_t* matches, float distmax, float ratiomax,
-                                  int mutual_best_match, int32_t* num_matches) {
-  PCD_REQUIRE(m && num_matches && max_match >= 0, "null pointer");
-  *num_matches = 0;
-  const int n1 = m->n[0], n2 = m->n[1];
-  if (n1 == 0 || n2 == 0 || max_match == 0) return PCD_OK;
-  PCD_REQUIRE(matches, "null match buffer");
-  PCD_HIP_TRY(hipSetDevice(m->device));
-  PCD_TRY(m->m12.reserve(n1)); PCD_TRY(m->m21.reserve(n2)); PCD_TRY(m->matches.reserve(2 * (size_t)n1));
-  PCD_TRY(m->count.reserve(1));
-  hipStream_t s = nullptr;
-  PCD_TRY(pcd_sift_match_device(m->device, m->d[0].p, n1, m->d[1].p, n2, ratiomax, distmax, mutual_best_match,
-                                m->m12.p, m->m21.p, m->matches.p, m->count.p, s));
-  int cnt = 0;
-  PCD_HIP_TRY(hipMemcpyAsync(&cnt, m->count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  PCD_HIP_TRY(hipStreamSynchronize(s));
-  if (cnt > max_match) cnt = max_match;
-  if (cnt) PCD_HIP_TRY(hipMemcpy(matches, m->matches.p, 2 * (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  *num_matches = cnt;
-  return PCD_OK;
-}
-
 // SiftMatchGPU::SetFeautreLocation(index, locations, gap): n[index] (x, y) pairs at a stride of 2 + gap floats
 pcd_status pcd_sift_matcher_set_locations(pcd_sift_matcher* m, int index, const float* loc, int gap) {
   PCD_REQUIRE(m && (index == 0 || index == 1) && gap >= 0, "index must be 0 or 1, gap >= 0");
@@ -1479,34 +1487,19 @@ pcd_status pcd_sift_matcher_set_locations(pcd_sift_matcher* m, int index, const 
   return PCD_OK;
 }
 
+// SiftMatchGPU::GetSiftMatch: number of matches written (at most max_match, in ascending index of set 0)
+pcd_status pcd_sift_matcher_match(pcd_sift_matcher* m, int max_match, uint32_t* matches, float distmax, float ratiomax,
+                                  int mutual_best_match, int32_t* num_matches) {
+  return sift_matcher_match(m, max_match, matches, nullptr, nullptr, distmax, ratiomax, 0.f, 0.f, mutual_best_match,
+                            num_matches);
+}
+
 // SiftMatchGPU::GetGuidedSiftMatch (SiftGPU.h:343-352): hdistmax / fdistmax are the squared residual thresholds
 pcd_status pcd_sift_matcher_match_guided(pcd_sift_matcher* m, int max_match, uint32_t* matches, const float* H,
                                          const float* F, float distmax, float ratiomax, float hdistmax, float fdistmax,
                                          int mutual_best_match, int32_t* num_matches) {
-  PCD_REQUIRE(m && num_matches && max_match >= 0, "null pointer");
-  *num_matches = 0;
-  if (!H && !F) return pcd_sift_matcher_match(m, max_match, matches, distmax, ratiomax, mutual_best_match, num_matches);
-  const int n1 = m->n[0], n2 = m->n[1];
-  if (n1 == 0 || n2 == 0 || max_match == 0) return PCD_OK;
-  if (!m->loc_ok[0] || !m->loc_ok[1]) {
-    set_error("pcd_sift_matcher_match_guided: a slot's descriptors were set after its locations (or none were set)");
-    return PCD_ERR_INVALID;
-  }
-  PCD_REQUIRE(matches, "null match buffer");
-  PCD_HIP_TRY(hipSetDevice(m->device));
-  PCD_TRY(m->m12.reserve(n1)); PCD_TRY(m->m21.reserve(n2)); PCD_TRY(m->matches.reserve(2 * (size_t)n1));
-  PCD_TRY(m->count.reserve(1));
-  hipStream_t s = nullptr;
-  PCD_TRY(pcd_sift_match_guided_device(m->device, m->d[0].p, m->loc[0].p, n1, m->d[1].p, m->loc[1].p, n2, H, F, hdistmax,
-                                       fdistmax, ratiomax, distmax, mutual_best_match, m->m12.p, m->m21.p, m->matches.p,
-                                       m->count.p, s));
-  int cnt = 0;
-  PCD_HIP_TRY(hipMemcpyAsync(&cnt, m->count.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  PCD_HIP_TRY(hipStreamSynchronize(s));
-  if (cnt > max_match) cnt = max_match;
-  if (cnt) PCD_HIP_TRY(hipMemcpy(matches, m->matches.p, 2 * (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  *num_matches = cnt;
-  return PCD_OK;
+  return sift_matcher_match(m, max_match, matches, H, F, distmax, ratiomax, hdistmax, fdistmax, mutual_best_match,
+                            num_matches);
 }
 
 }  // extern "C"

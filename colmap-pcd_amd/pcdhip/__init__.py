@@ -435,19 +435,29 @@ class ShardedCloud:
         return out
 
 
-def sift_match(d1, d2, max_ratio=0.8, max_distance=0.7, cross_check=True, device=0):
-    """MatchSiftFeaturesCPUBruteForce semantics on the GPU: returns matches [M][2] uint32"""
+def _sift_pair(d1, d2, max_ratio, max_distance, cross_check, device, guide=None):
+    """pcd_sift_match, or with guide = (loc1, loc2, H, F, h_max_residual, f_max_residual) pcd_sift_match_guided"""
     d1 = np.ascontiguousarray(d1, np.uint8).reshape(-1, 128)
     d2 = np.ascontiguousarray(d2, np.uint8).reshape(-1, 128)
     n1, n2 = d1.shape[0], d2.shape[0]
     m = np.zeros((max(n1, 1), 2), np.uint32)
     cnt = C.c_int32(0)
-    L = lib()
-    L.pcd_sift_match.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int,
-                                 C.c_void_p, C.POINTER(C.c_int32)]
-    _check(L.pcd_sift_match(device, _vp(d1) if n1 else None, n1, _vp(d2) if n2 else None, n2, max_ratio,
-                            max_distance, int(cross_check), _vp(m), C.byref(cnt)))
+    vp = lambda a: _vp(a) if a is not None and a.shape[0] else None
+    tail = (C.c_float(max_ratio), C.c_float(max_distance), int(cross_check), _vp(m), C.byref(cnt))
+    if guide is None:
+        _check(lib().pcd_sift_match(device, vp(d1), n1, vp(d2), n2, *tail))
+    else:
+        loc1, loc2, H, F, th, tf = guide
+        l1 = np.ascontiguousarray(loc1, np.float32).reshape(n1, 2)
+        l2 = np.ascontiguousarray(loc2, np.float32).reshape(n2, 2)
+        _check(lib().pcd_sift_match_guided(device, vp(d1), vp(l1), n1, vp(d2), vp(l2), n2, vp(_mat3(H)), vp(_mat3(F)),
+                                           C.c_float(th), C.c_float(tf), *tail))
     return m[:cnt.value].copy()
+
+
+def sift_match(d1, d2, max_ratio=0.8, max_distance=0.7, cross_check=True, device=0):
+    """MatchSiftFeaturesCPUBruteForce semantics on the GPU: returns matches [M][2] uint32"""
+    return _sift_pair(d1, d2, max_ratio, max_distance, cross_check, device)
 
 
 def sift_match_device(d_d1, n1, d_d2, n2, d_m12, d_m21, d_matches, d_count, max_ratio=0.8, max_distance=0.7,
@@ -457,35 +467,6 @@ def sift_match_device(d_d1, n1, d_d2, n2, d_m12, d_m21, d_matches, d_count, max_
                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _check(L.pcd_sift_match_device(device, _ptr(d_d1), n1, _ptr(d_d2), n2, max_ratio, max_distance, int(cross_check),
                                    _ptr(d_m12), _ptr(d_m21), _ptr(d_matches), _ptr(d_count), C.c_void_p(stream)))
-
-
-def _sift_arena(descriptors):
-    """list of [n_i][128] uint8 arrays -> (arena [sum n_i][128], first_row [len + 1] uint64)"""
-    ds = [np.ascontiguousarray(d, np.uint8).reshape(-1, 128) for d in descriptors]
-    first = np.zeros(len(ds) + 1, np.uint64)
-    first[1:] = np.cumsum([d.shape[0] for d in ds])
-    arena = np.concatenate(ds, axis=0) if ds and first[-1] else np.zeros((0, 128), np.uint8)
-    return np.ascontiguousarray(arena), first
-
-
-def sift_match_batch(descriptors, pairs, max_ratio=0.8, max_distance=0.7, cross_check=True, device=0):
-    """SiftFeatureMatcher::Match(image_pairs) (feature/matching.cc:798): `descriptors` = one [n_i][128] uint8 array
-    per image, `pairs` = [P][2] image indices.  Returns a list of P match arrays [M_p][2] uint32, each equal to
-    sift_match(descriptors[a], descriptors[b])."""
-    arena, first = _sift_arena(descriptors)
-    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
-    P = pairs.shape[0]
-    off = np.zeros(P + 1, np.uint64)
-    n1 = (first[1:] - first[:-1])[pairs[:, 0]] if P else np.zeros(0, np.uint64)
-    cap = int(n1.sum())
-    m = np.zeros((max(cap, 1), 2), np.uint32)
-    L = lib()
-    L.pcd_sift_match_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float,
-                                       C.c_float, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
-    _check(L.pcd_sift_match_batch(device, _vp(arena) if arena.shape[0] else None, _vp(first), len(descriptors),
-                                  _vp(pairs) if P else None, P, max_ratio, max_distance, int(cross_check), _vp(m), cap,
-                                  _vp(off)))
-    return [m[int(off[p]):int(off[p + 1])].copy() for p in range(P)]
 
 
 SIFT_GUIDE_NONE, SIFT_GUIDE_H, SIFT_GUIDE_F, SIFT_GUIDE_HF = 0, 1, 2, 3
@@ -500,28 +481,61 @@ def _mat3(m):
     return None if m is None else np.ascontiguousarray(m, np.float32).reshape(9)
 
 
+def _sift_arena(arrays, dtype=np.uint8, width=128):
+    """list of [n_i][width] arrays -> (arena [sum n_i][width], first_row [len + 1] uint64)"""
+    ds = [np.ascontiguousarray(d, dtype).reshape(-1, width) for d in arrays]
+    first = np.zeros(len(ds) + 1, np.uint64)
+    first[1:] = np.cumsum([d.shape[0] for d in ds])
+    arena = np.concatenate(ds, axis=0) if ds and first[-1] else np.zeros((0, width), dtype)
+    return np.ascontiguousarray(arena), first
+
+
+def _sift_batch(descriptors, pairs, max_ratio, max_distance, cross_check, device, guide=None):
+    """pcd_sift_match_batch, or with guide = (locations, guides, h_max_residual, f_max_residual)
+    pcd_sift_match_guided_batch"""
+    arena, first = _sift_arena(descriptors)
+    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+    P = pairs.shape[0]
+    off = np.zeros(P + 1, np.uint64)
+    n1 = (first[1:] - first[:-1])[pairs[:, 0]] if P else np.zeros(0, np.uint64)
+    cap = int(n1.sum())   # worst case: one match per descriptor of every pair's first image
+    m = np.zeros((max(cap, 1), 2), np.uint32)
+    vp = lambda a: _vp(a) if a.shape[0] else None
+    head = (device, vp(arena))
+    mid = (_vp(first), len(descriptors), vp(pairs), P)
+    tail = (C.c_float(max_ratio), C.c_float(max_distance), int(cross_check), _vp(m), C.c_uint64(cap),
+            _vp(off))
+    if guide is None:
+        _check(lib().pcd_sift_match_batch(*head, *mid, *tail))
+    else:
+        locations, guides, th, tf = guide
+        loc_arena, lfirst = _sift_arena(locations, np.float32, 2)
+        assert np.array_equal(lfirst, first)
+        g = (SiftGuide * max(P, 1))()
+        for p, (H, F) in enumerate(guides):
+            g[p].mode = (SIFT_GUIDE_H if H is not None else 0) | (SIFT_GUIDE_F if F is not None else 0)
+            if H is not None:
+                g[p].H[:] = [float(v) for v in _mat3(H)]
+            if F is not None:
+                g[p].F[:] = [float(v) for v in _mat3(F)]
+        _check(lib().pcd_sift_match_guided_batch(*head, vp(loc_arena), *mid, C.cast(g, C.c_void_p), C.c_float(th),
+                                                 C.c_float(tf), *tail))
+    return [m[int(off[p]):int(off[p + 1])].copy() for p in range(P)]
+
+
+def sift_match_batch(descriptors, pairs, max_ratio=0.8, max_distance=0.7, cross_check=True, device=0):
+    """SiftFeatureMatcher::Match(image_pairs) (feature/matching.cc:798): `descriptors` = one [n_i][128] uint8 array
+    per image, `pairs` = [P][2] image indices.  Returns a list of P match arrays [M_p][2] uint32, each equal to
+    sift_match(descriptors[a], descriptors[b])."""
+    return _sift_batch(descriptors, pairs, max_ratio, max_distance, cross_check, device)
+
+
 def sift_match_guided(d1, loc1, d2, loc2, H=None, F=None, h_max_residual=16.0, f_max_residual=16.0, max_ratio=0.8,
                       max_distance=0.7, cross_check=True, device=0):
     """MatchGuidedSiftFeaturesCPU semantics (feature/sift.cc:1092-1162) on the GPU: loc1 / loc2 [n][2] float32, H / F
     row-major 3x3 or None; returns matches [M][2] uint32 (with neither matrix: exactly sift_match)"""
-    d1 = np.ascontiguousarray(d1, np.uint8).reshape(-1, 128)
-    d2 = np.ascontiguousarray(d2, np.uint8).reshape(-1, 128)
-    n1, n2 = d1.shape[0], d2.shape[0]
-    l1 = np.ascontiguousarray(loc1, np.float32).reshape(n1, 2)
-    l2 = np.ascontiguousarray(loc2, np.float32).reshape(n2, 2)
-    h, f = _mat3(H), _mat3(F)
-    m = np.zeros((max(n1, 1), 2), np.uint32)
-    cnt = C.c_int32(0)
-    L = lib()
-    L.pcd_sift_match_guided.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                        C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
-                                        C.c_void_p, C.POINTER(C.c_int32)]
-    _check(L.pcd_sift_match_guided(device, _vp(d1) if n1 else None, _vp(l1) if n1 else None, n1,
-                                   _vp(d2) if n2 else None, _vp(l2) if n2 else None, n2,
-                                   _vp(h) if h is not None else None, _vp(f) if f is not None else None,
-                                   h_max_residual, f_max_residual, max_ratio, max_distance, int(cross_check), _vp(m),
-                                   C.byref(cnt)))
-    return m[:cnt.value].copy()
+    return _sift_pair(d1, d2, max_ratio, max_distance, cross_check, device,
+                      (loc1, loc2, H, F, h_max_residual, f_max_residual))
 
 
 def sift_match_guided_batch(descriptors, locations, pairs, guides, h_max_residual=16.0, f_max_residual=16.0,
@@ -529,33 +543,8 @@ def sift_match_guided_batch(descriptors, locations, pairs, guides, h_max_residua
     """GuidedSiftGPUFeatureMatcher's per-pair loop (feature/matching.cc:523-575) in one call: `locations` = one [n_i][2]
     float32 array per image, `guides` = one (H or None, F or None) per pair.  Returns a list of P match arrays, each
     equal to sift_match_guided(...) of that pair."""
-    arena, first = _sift_arena(descriptors)
-    locs = [np.ascontiguousarray(l, np.float32).reshape(-1, 2) for l in locations]
-    assert [l.shape[0] for l in locs] == [int(first[i + 1] - first[i]) for i in range(len(locs))]
-    loc_arena = np.ascontiguousarray(np.concatenate(locs, axis=0) if locs and first[-1] else np.zeros((0, 2), np.float32))
-    pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
-    P = pairs.shape[0]
-    g = (SiftGuide * max(P, 1))()
-    for p, (H, F) in enumerate(guides):
-        g[p].mode = (SIFT_GUIDE_H if H is not None else 0) | (SIFT_GUIDE_F if F is not None else 0)
-        if H is not None:
-            g[p].H[:] = [float(v) for v in _mat3(H)]
-        if F is not None:
-            g[p].F[:] = [float(v) for v in _mat3(F)]
-    off = np.zeros(P + 1, np.uint64)
-    n1 = (first[1:] - first[:-1])[pairs[:, 0]] if P else np.zeros(0, np.uint64)
-    cap = int(n1.sum())
-    m = np.zeros((max(cap, 1), 2), np.uint32)
-    L = lib()
-    L.pcd_sift_match_guided_batch.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                              C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
-                                              C.c_void_p, C.c_uint64, C.c_void_p]
-    _check(L.pcd_sift_match_guided_batch(device, _vp(arena) if arena.shape[0] else None,
-                                         _vp(loc_arena) if loc_arena.shape[0] else None, _vp(first), len(descriptors),
-                                         _vp(pairs) if P else None, P, C.cast(g, C.c_void_p), h_max_residual,
-                                         f_max_residual, max_ratio, max_distance, int(cross_check), _vp(m), cap,
-                                         _vp(off)))
-    return [m[int(off[p]):int(off[p + 1])].copy() for p in range(P)]
+    return _sift_batch(descriptors, pairs, max_ratio, max_distance, cross_check, device,
+                       (locations, guides, h_max_residual, f_max_residual))
 
 
 def exhaustive_blocks(n_images, block_size=50):
@@ -706,7 +695,8 @@ def set_nn_search(kernel=0):
 
 
 def set_sift_tuning(nchunk=0, batch_partials=0):
-    """tests / fuzzing: column chunks per stripe walk and bytes of partial results per sub-batch (0 = library's choice)"""
+    """tests / fuzzing: column chunks per stripe walk and partial results per sub-batch, counted in int4 elements
+    (16-byte units); 0 = the library's choice"""
     L = lib()
     L.pcd_sift_set_tuning.argtypes = [C.c_int, C.c_uint64]
     _check(L.pcd_sift_set_tuning(int(nchunk), int(batch_partials)))

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture
 def sift_tuning(gpu):
-    """pcd_sift_set_tuning for one test (chunks per stripe walk, bytes of partials per sub-batch), reset afterwards"""
+    """pcd_sift_set_tuning for one test (chunks per stripe walk, partials per sub-batch in 16-byte units), reset afterwards"""
     def set_(nchunk=0, batch_partials=0):
         gpu.set_sift_tuning(nchunk, batch_partials)
     yield set_
