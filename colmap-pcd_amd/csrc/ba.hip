@@ -24,6 +24,8 @@
 // problem share it -- the usual case); MODEL = -1 switches per observation.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <limits>
 #include <memory>
 #include <numeric>
 
@@ -1140,6 +1142,346 @@ __global__ __launch_bounds__(256) void k_ba_plus(int I, int P, const int* __rest
   }
 }
 
+// ---- block-sparse preconditioned CG on the reduced camera system (pcd_ba_schur_solve_pcg*) -----------
+// S x = rhs from the handle's own blocks.  An iteration is three plain launches (product, vector update, scalars);
+// scalars, the iteration count and the done flag live in PcgState on the device and every kernel of an iteration
+// returns at once when done is set, so the host enqueues a batch of iterations between two looks at the flag.
+// p and x are double-buffered (iteration it reads buffer it & 1 and writes the other): the product forms the new
+// direction of a partner slot on the fly from z and the old p instead of waiting for a fourth launch, and a breakdown
+// leaves the last finite x untouched.  All sums run in an order fixed by the structure.
+struct PcgState {
+  double rho, alpha, beta, pw, q, rn2, bnorm, xr;
+  int k, done, term, xsel;
+  unsigned fallbacks; int pad;
+};
+struct PcgRule { int max_iterations, min_iterations; double q_tolerance, r_tolerance; };
+
+// sum over the workgroup (256 threads), every thread gets the result; fixed order: wavefront butterfly, then the 4 waves
+__device__ __forceinline__ double block_sum256(double v, double* lds4) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();   // lds4 may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+// strided sum of partial[i * stride] (i < n) over one workgroup
+__device__ __forceinline__ double block_sum_strided(const double* __restrict__ partial, int n, int stride, double* lds4) {
+  double a = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) a += partial[(size_t)i * stride];
+  return block_sum256(a, lds4);
+}
+
+// thread = slot: M_i^-1 (SCHUR_JACOBI: inverse of the 6x6 diagonal block through its Cholesky factor, identity when a
+// pivot is not positive and finite -- counted; IDENTITY: I), x = 0, r = rhs, z = M^-1 r, both direction buffers 0;
+// partials [nb][4] of r.z, rhs.rhs and the fallback count.  An identity row / column of the block (constant tvec
+// coordinate) gives an identity row / column of the factor and of the inverse, exactly.
+__global__ __launch_bounds__(256) void k_pcg_init(int ns, int precond, const double* __restrict__ Sdiag,
+                                                  const double* __restrict__ rhs, double* __restrict__ Minv,
+                                                  double* __restrict__ x0, double* __restrict__ r, double* __restrict__ z,
+                                                  double* __restrict__ p0, double* __restrict__ p1,
+                                                  double* __restrict__ partial) {
+  __shared__ double s_l[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double rz = 0.0, bb = 0.0, fb = 0.0;
+  if (i < ns) {
+    double mi[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) mi[k] = (k % 7 == 0) ? 1.0 : 0.0;
+    if (precond != 0) {
+      const double* A = Sdiag + 36 * (size_t)i;
+      double L[36];
+#pragma unroll
+      for (int k = 0; k < 36; ++k) L[k] = 0.0;
+      bool ok = true;
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        double d = A[7 * j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[6 * j + k] * L[6 * j + k];
+        ok = ok && d > 0.0 && d <= 1.7976931348623157e308;
+        const double ljj = ok ? sqrt(d) : 1.0;
+        L[7 * j] = ljj;
+#pragma unroll
+        for (int a = j + 1; a < 6; ++a) {
+          double s = A[6 * a + j];
+#pragma unroll
+          for (int k = 0; k < j; ++k) s -= L[6 * a + k] * L[6 * j + k];
+          L[6 * a + j] = s / ljj;
+        }
+      }
+      if (ok) {
+        double M[36];   // L^-1, lower
+#pragma unroll
+        for (int k = 0; k < 36; ++k) M[k] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          M[7 * j] = 1.0 / L[7 * j];
+#pragma unroll
+          for (int a = j + 1; a < 6; ++a) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = j; k < a; ++k) s += L[6 * a + k] * M[6 * k + j];
+            M[6 * a + j] = -s / L[7 * a];
+          }
+        }
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+          for (int c = 0; c <= a; ++c) {
+            double s = 0.0;   // (M^T M)_ac, k from a (>= c) upwards
+#pragma unroll
+            for (int k = a; k < 6; ++k) s += M[6 * k + a] * M[6 * k + c];
+            mi[6 * a + c] = s; mi[6 * c + a] = s;
+          }
+      } else {
+        fb = 1.0;
+      }
+    }
+    double* mo = Minv + 36 * (size_t)i;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) mo[k] = mi[k];
+    double b[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] = rhs[6 * (size_t)i + k];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s += mi[6 * a + c] * b[c];
+      const size_t o = 6 * (size_t)i + a;
+      z[o] = s; r[o] = b[a]; x0[o] = 0.0; p0[o] = 0.0; p1[o] = 0.0;
+      rz += b[a] * s; bb += b[a] * b[a];
+    }
+  }
+  rz = block_sum256(rz, s_l); bb = block_sum256(bb, s_l); fb = block_sum256(fb, s_l);
+  if (threadIdx.x == 0) {
+    double* o = partial + 4 * (size_t)blockIdx.x;
+    o[0] = rz; o[1] = bb; o[2] = fb; o[3] = 0.0;
+  }
+}
+
+// one workgroup: the scalars of iteration 0.  ||rhs|| = 0 -> ZERO_RHS, max_iterations <= 0 -> MAX_ITERATIONS, x = 0
+__global__ __launch_bounds__(256) void k_pcg_begin(int nb, const double* __restrict__ partial, PcgRule rule,
+                                                   PcgState* __restrict__ st) {
+  __shared__ double s_l[4];
+  const double rz = block_sum_strided(partial, nb, 4, s_l);
+  const double bb = block_sum_strided(partial + 1, nb, 4, s_l);
+  const double fb = block_sum_strided(partial + 2, nb, 4, s_l);
+  if (threadIdx.x != 0) return;
+  PcgState s;
+  s.rho = rz; s.alpha = 0.0; s.beta = 0.0; s.pw = 0.0; s.q = 0.0; s.rn2 = bb; s.bnorm = sqrt(bb); s.xr = 0.0;
+  s.k = 0; s.done = 0; s.term = PCD_PCG_MAX_ITERATIONS; s.xsel = 0; s.fallbacks = (unsigned)fb; s.pad = 0;
+  if (!(bb > 0.0)) {   // zero (or not a number: nothing to iterate on)
+    s.done = 1; s.term = bb == 0.0 ? PCD_PCG_ZERO_RHS : PCD_PCG_BREAKDOWN;
+  } else if (!(rz > 0.0) || !(rz <= 1.7976931348623157e308)) {
+    s.done = 1; s.term = PCD_PCG_BREAKDOWN;
+  } else if (rule.max_iterations <= 0) {
+    s.done = 1;
+  }
+  *st = s;
+}
+
+// one wavefront per slot row: w_i = sum over the row list (ascending partner slot; block, transposed flag) of
+// B p_j with p_j = z_j + beta p_old_j, lane-strided blocks, six accumulators, xor butterfly.  Lane 0 stores the row's
+// new direction, w_i and p_i . w_i.
+__global__ __launch_bounds__(256) void k_pcg_spmv(int ns, const PcgState* __restrict__ st,
+                                                  const uint32_t* __restrict__ row_start, const uint32_t* __restrict__ row_blk,
+                                                  const uint32_t* __restrict__ row_col, const double* __restrict__ Sdiag,
+                                                  const double* __restrict__ Soff, const double* __restrict__ z,
+                                                  const double* __restrict__ p_old, double* __restrict__ p_new,
+                                                  double* __restrict__ w, double* __restrict__ pw_partial) {
+  if (st->done) return;
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (i >= ns) return;
+  const double beta = st->beta;
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  for (uint32_t t = row_start[i] + lane; t < row_start[i + 1]; t += 64) {
+    const uint32_t blk = row_blk[t], cj = row_col[t];
+    const bool tr = cj & 1u;
+    const size_t j = cj >> 1;
+    const double* B = blk < (uint32_t)ns ? Sdiag + 36 * (size_t)blk : Soff + 36 * (size_t)(blk - (uint32_t)ns);
+    double bv[36], pj[6];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) bv[k] = B[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pj[k] = z[6 * j + k] + beta * p_old[6 * j + k];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s += (tr ? bv[6 * c + a] : bv[6 * a + c]) * pj[c];
+      acc[a] += s;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[a] += __shfl_xor(acc[a], off);
+  if (lane == 0) {
+    double pw = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const size_t o = 6 * (size_t)i + k;
+      const double pk = z[o] + beta * p_old[o];
+      p_new[o] = pk; w[o] = acc[k];
+      pw += pk * acc[k];
+    }
+    pw_partial[i] = pw;
+  }
+}
+
+// thread = slot: alpha = rho / p.w (every workgroup sums the ns row partials in the same order), then
+// x_new = x_old + alpha p, r -= alpha w, z = M^-1 r and the partials [nb][4] of r.z, r.r, x.(rhs + r), x.r.
+// p.w <= 0 or a non-finite alpha: nothing is updated (k_pcg_step ends the solve with BREAKDOWN).
+__global__ __launch_bounds__(256) void k_pcg_update(int ns, PcgState* __restrict__ st, const double* __restrict__ pw_partial,
+                                                    const double* __restrict__ Minv, const double* __restrict__ rhs,
+                                                    const double* __restrict__ p, const double* __restrict__ w,
+                                                    const double* __restrict__ x_old, double* __restrict__ x_new,
+                                                    double* __restrict__ r, double* __restrict__ z,
+                                                    double* __restrict__ partial) {
+  __shared__ double s_l[4];
+  if (st->done) return;
+  const double pw = block_sum_strided(pw_partial, ns, 1, s_l);
+  const double alpha = st->rho / pw;
+  const bool good = pw > 0.0 && alpha <= 1.7976931348623157e308 && alpha >= -1.7976931348623157e308;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { st->pw = pw; st->alpha = alpha; }
+  if (!good) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double rz = 0.0, rr = 0.0, xbr = 0.0, xr = 0.0;
+  if (i < ns) {
+    double rv[6], xv[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const size_t o = 6 * (size_t)i + k;
+      xv[k] = x_old[o] + alpha * p[o];
+      rv[k] = r[o] - alpha * w[o];
+      x_new[o] = xv[k]; r[o] = rv[k];
+    }
+    const double* mi = Minv + 36 * (size_t)i;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s += mi[6 * a + c] * rv[c];
+      z[6 * (size_t)i + a] = s;
+      rz += rv[a] * s; rr += rv[a] * rv[a];
+      xbr += xv[a] * (rhs[6 * (size_t)i + a] + rv[a]); xr += xv[a] * rv[a];
+    }
+  }
+  rz = block_sum256(rz, s_l); rr = block_sum256(rr, s_l); xbr = block_sum256(xbr, s_l); xr = block_sum256(xr, s_l);
+  if (threadIdx.x == 0) {
+    double* o = partial + 4 * (size_t)blockIdx.x;
+    o[0] = rz; o[1] = rr; o[2] = xbr; o[3] = xr;
+  }
+}
+
+// one workgroup: sums of the partials, Q_k = -1/2 x.(rhs + r), the stopping rule (Q, then r, then the iteration
+// limit), beta and the counter.  `it` is the iteration's index (the buffer that holds its x is (it + 1) & 1).
+__global__ __launch_bounds__(256) void k_pcg_step(int nb, int it, const double* __restrict__ partial, PcgRule rule,
+                                                  PcgState* __restrict__ st) {
+  __shared__ double s_l[4];
+  if (st->done) return;
+  const double pw = st->pw, alpha = st->alpha;
+  if (!(pw > 0.0 && alpha <= 1.7976931348623157e308 && alpha >= -1.7976931348623157e308)) {
+    if (threadIdx.x == 0) { st->done = 1; st->term = PCD_PCG_BREAKDOWN; }
+    return;
+  }
+  const double rz = block_sum_strided(partial, nb, 4, s_l);
+  const double rr = block_sum_strided(partial + 1, nb, 4, s_l);
+  const double xbr = block_sum_strided(partial + 2, nb, 4, s_l);
+  const double xr = block_sum_strided(partial + 3, nb, 4, s_l);
+  if (threadIdx.x != 0) return;
+  const double q = -0.5 * xbr;
+  const double lim = 1.7976931348623157e308;
+  if (!(rz >= 0.0 && rz <= lim && rr <= lim && q >= -lim && q <= lim)) {   // the x of this iteration is not used
+    st->done = 1; st->term = PCD_PCG_BREAKDOWN;
+    return;
+  }
+  const int k = st->k + 1;
+  const double zeta = (double)k * (q - st->q) / q;
+  int done = 0, term = PCD_PCG_MAX_ITERATIONS;
+  if (k >= rule.min_iterations && rule.q_tolerance >= 0.0 && zeta < rule.q_tolerance) { done = 1; term = PCD_PCG_Q_TOLERANCE; }
+  else if (k >= rule.min_iterations && rule.r_tolerance >= 0.0 && sqrt(rr) <= rule.r_tolerance * st->bnorm) { done = 1; term = PCD_PCG_R_TOLERANCE; }
+  else if (k >= rule.max_iterations) { done = 1; }
+  st->beta = rz / st->rho; st->rho = rz; st->q = q; st->rn2 = rr; st->xr = xr;
+  st->k = k; st->xsel = (it + 1) & 1; st->term = term; st->done = done;
+}
+
+// the selected x into the caller's dpose, the record into info (termination -1: still running)
+__global__ __launch_bounds__(256) void k_pcg_finish(int ns, const PcgState* __restrict__ st, const double* __restrict__ x0,
+                                                    const double* __restrict__ x1, double* __restrict__ dpose,
+                                                    pcd_ba_pcg_info* __restrict__ info) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (dpose && t < 6 * ns) dpose[t] = (st->xsel ? x1 : x0)[t];
+  if (t == 0 && info) {
+    pcd_ba_pcg_info o;
+    o.iterations = st->k; o.termination = st->done ? st->term : -1; o.precond_fallbacks = st->fallbacks;
+    o.rhs_norm = st->bnorm; o.residual_norm = sqrt(st->rn2); o.q = st->q; o.step_dot_residual = st->xr;
+    *info = o;
+  }
+}
+
+// max |g| over the active pose coordinates of the slots and the non-constant points: partial max per workgroup
+// (a maximum does not depend on the order), grid-stride
+__global__ __launch_bounds__(256) void k_ba_grad_max(int ns, const int* __restrict__ slot_img,
+                                                     const uint8_t* __restrict__ image_const_tvec,
+                                                     const double* __restrict__ gimg, int P,
+                                                     const uint8_t* __restrict__ point_const,
+                                                     const double* __restrict__ gpt, double* __restrict__ partial) {
+  __shared__ double s_m[4];
+  double m = 0.0;
+  const int n = ns + P;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) {
+    if (t < ns) {
+      const int im = slot_img[t];
+      const unsigned tm = image_const_tvec ? image_const_tvec[im] : 0u;
+      const double* g = gimg + 6 * (size_t)im;
+#pragma unroll
+      for (int k = 0; k < 6; ++k)
+        if (!(k >= 3 && ((tm >> (k - 3)) & 1u))) m = fmax(m, fabs(g[k]));
+    } else {
+      const int p = t - ns;
+      if (!(point_const && point_const[p])) {
+        const double* g = gpt + 3 * (size_t)p;
+        m = fmax(m, fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2]))));
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
+}
+
+// what the LM loop of pcd_ba_solve reads per iteration, in one device-to-host copy
+struct LmRecord {
+  double cost, candidate_cost, model_decrease, gradient_max;
+  unsigned long long num_skipped;
+  pcd_ba_pcg_info pcg;
+};
+__global__ __launch_bounds__(256) void k_ba_lm_record(const double* __restrict__ cost, const double* __restrict__ cand,
+                                                      const double* __restrict__ md, const double* __restrict__ gpart,
+                                                      int ngp, const unsigned long long* __restrict__ skipped,
+                                                      const pcd_ba_pcg_info* __restrict__ info, LmRecord* __restrict__ out) {
+  __shared__ double s_m[4];
+  double m = 0.0;
+  for (int i = threadIdx.x; i < ngp; i += 256) m = fmax(m, gpart[i]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    LmRecord r;
+    r.cost = cost[0]; r.candidate_cost = cand[0]; r.model_decrease = md[0];
+    r.gradient_max = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
+    r.num_skipped = skipped[0]; r.pcg = *info;
+    *out = r;
+  }
+}
+
 // Host-built structure (first Schur call) and the numeric state of the last Schur call
 struct BaSchur {
   bool built = false;
@@ -1154,6 +1496,18 @@ struct BaSchur {
   DevBuf<uint32_t> skip_partial;
   DevBuf<unsigned long long> skip_cnt;
   DevBuf<double> cost, dense;   // dense: staging of the host form's S
+  // rows of S for the product y = S x (built with the structure): row i = its blocks in ascending partner slot
+  DevBuf<uint32_t> row_start, row_blk, row_col;   // [ns+1]; block (< ns: diagonal, else ns + pair); partner << 1 | transposed
+  bool own_diag = false, own_off = false, own_rhs = false;   // the last Schur call left S_diag / S_off / rhs in the handle
+  // PCG state (pcd_ba_schur_solve_pcg*) and the LM loop's buffers (pcd_ba_solve)
+  DevBuf<double> Minv, cg_x0, cg_x1, cg_r, cg_z, cg_p0, cg_p1, cg_w, cg_pw, cg_partial, cg_out;
+  DevBuf<PcgState> cg_state;
+  DevBuf<pcd_ba_pcg_info> cg_info;
+  PinnedBuf<int> cg_flag;
+  int cg_it = 0;   // iterations enqueued in the running solve (buffer parity)
+  DevBuf<double> lm_dpose, lm_dpoint, lm_poses, lm_points, lm_cand_cost, lm_gpart;
+  DevBuf<LmRecord> lm_rec;
+  PinnedBuf<LmRecord> lm_host;
 };
 
 }  // namespace pcd
@@ -1410,6 +1764,25 @@ static pcd_status schur_build(pcd_ba* b) {
   PCD_TRY(upload(S.pair_ij, pij.data(), pij.size()));
   PCD_TRY(upload(S.iota, iota.data(), iota.size()));
   PCD_TRY(upload(S.obs_pos, obs_pos.data(), obs_pos.size()));
+  {   // row lists of the product: transposes of the (k, s) blocks (k ascending), the diagonal, the (s, j) blocks
+    std::vector<uint32_t> rst((size_t)ns + 1, 0);
+    for (int s = 0; s < ns; ++s) rst[(size_t)s + 1] = 1;
+    for (uint64_t q = 0; q < S.npairs; ++q) { rst[(size_t)S.h_pair_i[q] + 1]++; rst[(size_t)S.h_pair_j[q] + 1]++; }
+    for (int s = 0; s < ns; ++s) rst[(size_t)s + 1] += rst[s];
+    std::vector<uint32_t> rblk(rst[ns]), rcol(rst[ns]), pos(rst.begin(), rst.end() - 1);
+    for (uint64_t q = 0; q < S.npairs; ++q) {
+      const uint32_t t = pos[S.h_pair_j[q]]++;
+      rblk[t] = (uint32_t)(ns + q); rcol[t] = ((uint32_t)S.h_pair_i[q] << 1) | 1u;
+    }
+    for (int s = 0; s < ns; ++s) { const uint32_t t = pos[s]++; rblk[t] = (uint32_t)s; rcol[t] = (uint32_t)s << 1; }
+    for (uint64_t q = 0; q < S.npairs; ++q) {
+      const uint32_t t = pos[S.h_pair_i[q]]++;
+      rblk[t] = (uint32_t)(ns + q); rcol[t] = (uint32_t)S.h_pair_j[q] << 1;
+    }
+    PCD_TRY(upload(S.row_start, rst.data(), rst.size()));
+    PCD_TRY(upload(S.row_blk, rblk.data(), rblk.size()));
+    PCD_TRY(upload(S.row_col, rcol.data(), rcol.size()));
+  }
   S.built = true;
   S.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return PCD_OK;
@@ -1841,10 +2214,15 @@ pcd_status pcd_ba_schur_stats(pcd_ba* b, pcd_ba_schur_info* info) {
   info->num_entries = S.nent;
   uint64_t bytes = 0;
   bytes += (S.img_slot.n + S.slot_img.n) * sizeof(int);
-  bytes += (S.blk_start.n + S.ent_a.n + S.ent_b.n + S.pair_ij.n + S.iota.n + S.obs_pos.n + S.skip_partial.n) * sizeof(uint32_t);
+  bytes += (S.blk_start.n + S.ent_a.n + S.ent_b.n + S.pair_ij.n + S.iota.n + S.obs_pos.n + S.skip_partial.n +
+            S.row_start.n + S.row_blk.n + S.row_col.n) * sizeof(uint32_t);
   for (const DevBuf<double>* d : {&S.Himg, &S.gimg, &S.Hpt, &S.gpt, &S.Wim, &S.Y, &S.Vinv, &S.Vg, &S.Dpt, &S.Dimg,
-                                  &S.Sdiag, &S.Soff, &S.rhs, &S.md_partial, &S.md, &S.cost, &S.dense})
+                                  &S.Sdiag, &S.Soff, &S.rhs, &S.md_partial, &S.md, &S.cost, &S.dense,
+                                  &S.Minv, &S.cg_x0, &S.cg_x1, &S.cg_r, &S.cg_z, &S.cg_p0, &S.cg_p1, &S.cg_w, &S.cg_pw,
+                                  &S.cg_partial, &S.cg_out, &S.lm_dpose, &S.lm_dpoint, &S.lm_poses, &S.lm_points,
+                                  &S.lm_cand_cost, &S.lm_gpart})
     bytes += d->n * sizeof(double);
+  bytes += S.cg_state.n * sizeof(PcgState) + S.cg_info.n * sizeof(pcd_ba_pcg_info) + S.lm_rec.n * sizeof(LmRecord);
   info->scratch_bytes = bytes;
   return PCD_OK;
 }
@@ -1919,6 +2297,7 @@ pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pc
     }
     PCD_HIP_TRY(hipGetLastError());
     S.valid = true;
+    S.own_diag = !o->S_diag; S.own_off = !o->S_off; S.own_rhs = !o->rhs;
     return PCD_OK;
   });
 }
@@ -2002,6 +2381,281 @@ pcd_status pcd_ba_set_parameters_device(pcd_ba* b, const double* d_poses, const 
   if (d_points && d_points != b->points.p)
     PCD_HIP_TRY(hipMemcpyAsync(b->points.p, d_points, 3 * (size_t)b->P * sizeof(double), hipMemcpyDeviceToDevice, s));
   return PCD_OK;
+}
+
+}  // extern "C"
+
+// ---- reduced solve: PCG and the LM loop -------------------------------------------------------------
+// Iterations are enqueued in batches; between two batches the host reads the done flag (one 4-byte copy and a stream
+// synchronisation).  8 covers the inexact steps of the LM loop (2-5 iterations at the defaults) in one batch at the
+// price of a few returned-at-once launches; a tight solve grows the batch to 32.
+static constexpr int kPcgFirstBatch = 8, kPcgMaxBatch = 32;
+
+static pcd_status pcg_check_opts(const pcd_ba_pcg_opts* o) {
+  PCD_REQUIRE(o, "null pointer");
+  PCD_REQUIRE(o->preconditioner == PCD_PRECOND_IDENTITY || o->preconditioner == PCD_PRECOND_SCHUR_JACOBI, "preconditioner");
+  PCD_REQUIRE(o->max_iterations >= 0 && o->min_iterations >= 0, "iteration limits must be >= 0");
+  PCD_REQUIRE(o->q_tolerance == o->q_tolerance && o->r_tolerance == o->r_tolerance, "tolerance is not a number");
+  return PCD_OK;
+}
+
+static pcd_status pcg_state_guard(pcd_ba* b, const char* fn) {
+  if (!b->schur || !b->schur->valid) {
+    set_error("%s: no Schur state (call pcd_ba_schur[_device] first)", fn);
+    return PCD_ERR_INVALID;
+  }
+  const BaSchur& S = *b->schur;
+  if (!S.own_diag || !S.own_off || !S.own_rhs) {
+    set_error("%s: the last Schur call sent %s%s%s to caller memory; the solver reads the handle's own copy "
+              "(leave those outputs NULL)", fn, S.own_diag ? "" : "S_diag ", S.own_off ? "" : "S_off ",
+              S.own_rhs ? "" : "rhs ");
+    return PCD_ERR_INVALID;
+  }
+  return PCD_OK;
+}
+
+static PcgRule pcg_rule(const pcd_ba_pcg_opts* o) {
+  PcgRule r;
+  r.max_iterations = o->max_iterations; r.min_iterations = o->min_iterations;
+  r.q_tolerance = o->q_tolerance; r.r_tolerance = o->r_tolerance;
+  return r;
+}
+
+// preconditioner, x = 0, r = rhs, the scalars of iteration 0
+static pcd_status pcg_begin(pcd_ba* b, const pcd_ba_pcg_opts* o, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  const int ns = S.ns;
+  const size_t n6 = std::max<size_t>(6 * (size_t)ns, 1);
+  const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256));
+  PCD_TRY(S.Minv.reserve(std::max<size_t>(36 * (size_t)ns, 1)));
+  for (DevBuf<double>* d : {&S.cg_x0, &S.cg_x1, &S.cg_r, &S.cg_z, &S.cg_p0, &S.cg_p1, &S.cg_w}) PCD_TRY(d->reserve(n6));
+  PCD_TRY(S.cg_pw.reserve(std::max<size_t>(ns, 1))); PCD_TRY(S.cg_partial.reserve(4 * (size_t)nb));
+  PCD_TRY(S.cg_state.reserve(1)); PCD_TRY(S.cg_info.reserve(1)); PCD_TRY(S.cg_flag.reserve(4));
+  S.cg_it = 0;
+  hipLaunchKernelGGL(k_pcg_init, dim3(nb), dim3(256), 0, s, ns, o->preconditioner, S.Sdiag.p, S.rhs.p, S.Minv.p,
+                     S.cg_x0.p, S.cg_r.p, S.cg_z.p, S.cg_p0.p, S.cg_p1.p, S.cg_partial.p);
+  hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(256), 0, s, (int)nb, S.cg_partial.p, pcg_rule(o), S.cg_state.p);
+  return PCD_OK;
+}
+
+// `count` more iterations (three launches each; all of them return at once when the solve has ended)
+static void pcg_enqueue(pcd_ba* b, const pcd_ba_pcg_opts* o, int count, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  const int ns = S.ns;
+  if (!ns) return;
+  const unsigned nb = div_up((uint64_t)ns, 256);
+  const PcgRule rule = pcg_rule(o);
+  for (int c = 0; c < count; ++c, ++S.cg_it) {
+    const int it = S.cg_it;
+    double* p_old = (it & 1) ? S.cg_p1.p : S.cg_p0.p; double* p_new = (it & 1) ? S.cg_p0.p : S.cg_p1.p;
+    double* x_old = (it & 1) ? S.cg_x1.p : S.cg_x0.p; double* x_new = (it & 1) ? S.cg_x0.p : S.cg_x1.p;
+    hipLaunchKernelGGL(k_pcg_spmv, dim3(div_up((uint64_t)ns, 4)), dim3(256), 0, s, ns, S.cg_state.p, S.row_start.p,
+                       S.row_blk.p, S.row_col.p, S.Sdiag.p, S.Soff.p, S.cg_z.p, p_old, p_new, S.cg_w.p, S.cg_pw.p);
+    hipLaunchKernelGGL(k_pcg_update, dim3(nb), dim3(256), 0, s, ns, S.cg_state.p, S.cg_pw.p, S.Minv.p, S.rhs.p, p_new,
+                       S.cg_w.p, x_old, x_new, S.cg_r.p, S.cg_z.p, S.cg_partial.p);
+    hipLaunchKernelGGL(k_pcg_step, dim3(1), dim3(256), 0, s, (int)nb, it, S.cg_partial.p, rule, S.cg_state.p);
+  }
+}
+
+static void pcg_finish(pcd_ba* b, double* d_dpose, pcd_ba_pcg_info* d_info, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  hipLaunchKernelGGL(k_pcg_finish, dim3(std::max(1u, div_up(6 * (uint64_t)S.ns, 256))), dim3(256), 0, s, S.ns,
+                     S.cg_state.p, S.cg_x0.p, S.cg_x1.p, d_dpose, d_info);
+}
+
+// batches until the device says done; `enqueued` iterations are already in the stream.  One flag copy per batch.
+static pcd_status pcg_run(pcd_ba* b, const pcd_ba_pcg_opts* o, int enqueued, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  int batch = kPcgFirstBatch;
+  if (!enqueued) { pcg_enqueue(b, o, std::min(batch, o->max_iterations), s); enqueued = std::min(batch, o->max_iterations); }
+  for (;;) {
+    PCD_HIP_TRY(hipMemcpyAsync(S.cg_flag.p, &S.cg_state.p->done, sizeof(int), hipMemcpyDeviceToHost, s));
+    PCD_HIP_TRY(hipStreamSynchronize(s));
+    if (S.cg_flag.p[0] || !S.ns || enqueued >= o->max_iterations) return PCD_OK;
+    batch = std::min(2 * batch, kPcgMaxBatch);
+    const int n = std::min(batch, o->max_iterations - enqueued);
+    pcg_enqueue(b, o, n, s);
+    enqueued += n;
+  }
+}
+
+extern "C" {
+
+void pcd_ba_pcg_opts_default(pcd_ba_pcg_opts* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->max_iterations = 100; o->min_iterations = 0; o->preconditioner = PCD_PRECOND_SCHUR_JACOBI;
+  o->q_tolerance = 0.1; o->r_tolerance = -1.0;
+}
+
+pcd_status pcd_ba_schur_solve_pcg_device(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* d_dpose,
+                                         pcd_ba_pcg_info* d_info, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_TRY(pcg_check_opts(opts));
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_pcg_device"));
+    PCD_REQUIRE(d_dpose || b->schur->ns == 0, "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    ScopedKernelTimer t("ba_schur_pcg", s);
+    PCD_TRY(pcg_begin(b, opts, s));
+    PCD_TRY(pcg_run(b, opts, 0, s));
+    pcg_finish(b, d_dpose, d_info, s);
+    PCD_HIP_TRY(hipGetLastError());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_solve_pcg(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* dpose, pcd_ba_pcg_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_TRY(pcg_check_opts(opts));
+    PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_pcg"));
+    BaSchur& S = *b->schur;
+    PCD_REQUIRE(dpose || S.ns == 0, "null pointer");
+    PCD_TRY(S.cg_out.reserve(std::max<size_t>(6 * (size_t)S.ns, 1))); PCD_TRY(S.cg_info.reserve(1));
+    PCD_TRY(pcd_ba_schur_solve_pcg_device(b, opts, S.cg_out.p, S.cg_info.p, nullptr));
+    if (S.ns) PCD_HIP_TRY(hipMemcpy(dpose, S.cg_out.p, 6 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) PCD_HIP_TRY(hipMemcpy(info, S.cg_info.p, sizeof *info, hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipDeviceSynchronize());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_get_parameters(pcd_ba* b, double* poses, double* points) {
+  PCD_TRY(require_device(b ? b->device : 0));
+  PCD_REQUIRE(b, "null handle");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  if (poses) PCD_HIP_TRY(hipMemcpy(poses, b->poses.p, 7 * (size_t)b->I * sizeof(double), hipMemcpyDeviceToHost));
+  if (points) PCD_HIP_TRY(hipMemcpy(points, b->points.p, 3 * (size_t)b->P * sizeof(double), hipMemcpyDeviceToHost));
+  return PCD_OK;
+}
+
+void pcd_ba_solve_opts_default(pcd_ba_solve_opts* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->max_num_iterations = 10; o->damping = PCD_DAMP_MARQUARDT;
+  o->initial_radius = 1e4; o->max_radius = 1e16; o->min_radius = 1e-32; o->min_relative_decrease = 1e-3;
+  o->function_tolerance = 0.0; o->gradient_tolerance = 0.0;
+  pcd_ba_pcg_opts_default(&o->linear);
+}
+
+pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_summary* summary,
+                        pcd_ba_solve_iteration* iterations) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(opts, "null pointer");
+    PCD_TRY(pcg_check_opts(&opts->linear));
+    PCD_REQUIRE(opts->damping == PCD_DAMP_MARQUARDT || opts->damping == PCD_DAMP_LEVENBERG, "damping");
+    PCD_REQUIRE(opts->max_num_iterations >= 0, "max_num_iterations must be >= 0");
+    PCD_REQUIRE(opts->initial_radius > 0.0 && opts->max_radius > 0.0, "radius must be > 0");
+    hipStream_t s = nullptr;
+    PCD_REFUSE_CAPTURE(s);
+    PCD_TRY(schur_build(b));
+    BaSchur& S = *b->schur;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int I = b->I, P = b->P, ns = S.ns;
+    const size_t nposes = 7 * (size_t)I, npoints = 3 * (size_t)P;
+    PCD_TRY(S.lm_dpose.reserve(std::max<size_t>(6 * (size_t)ns, 1))); PCD_TRY(S.lm_dpoint.reserve(npoints));
+    PCD_TRY(S.lm_poses.reserve(nposes)); PCD_TRY(S.lm_points.reserve(npoints));
+    PCD_TRY(S.lm_cand_cost.reserve(1)); PCD_TRY(S.lm_rec.reserve(1)); PCD_TRY(S.lm_host.reserve(1));
+    const unsigned ngp = std::max(1u, std::min(1024u, div_up((uint64_t)ns + P, 256)));
+    PCD_TRY(S.lm_gpart.reserve(ngp));
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    PCD_HIP_TRY(hipEventCreate(&ev0));
+    if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); set_error("hipEventCreate failed"); return PCD_ERR_HIP; }
+    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{ev0, ev1};
+    // the accepted parameters: a rejected step copies them back into the handle
+    PCD_HIP_TRY(hipMemcpyAsync(S.lm_poses.p, b->poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
+    PCD_HIP_TRY(hipMemcpyAsync(S.lm_points.p, b->points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
+    pcd_ba_solve_summary sm{};
+    sm.termination = PCD_SOLVE_MAX_ITERATIONS;
+    double radius = opts->initial_radius, factor = 2.0, linear_ms = 0.0;
+    const pcd_ba_pcg_opts* lo = &opts->linear;
+    const uint8_t* ctvec = b->has_ctvec ? b->image_const_tvec.p : nullptr;
+    const uint8_t* cpt = b->has_cpt ? b->point_const.p : nullptr;
+    pcd_ba_out co{};
+    co.cost = S.lm_cand_cost.p;
+    for (int it = 0; it < opts->max_num_iterations; ++it) {
+      if (radius < opts->min_radius) { sm.termination = PCD_SOLVE_MIN_RADIUS; break; }
+      pcd_ba_schur_opts so{};
+      so.mu = 1.0 / radius; so.damping = opts->damping;
+      pcd_ba_schur_out none{};
+      PCD_TRY(pcd_ba_schur_device(b, &so, &none, s));
+      hipLaunchKernelGGL(k_ba_grad_max, dim3(ngp), dim3(256), 0, s, ns, S.slot_img.p, ctvec, S.gimg.p, P, cpt, S.gpt.p,
+                         S.lm_gpart.p);
+      PCD_HIP_TRY(hipEventRecord(ev0, s));
+      PCD_TRY(pcg_begin(b, lo, s));
+      int enq = std::min(kPcgFirstBatch, lo->max_iterations);
+      pcg_enqueue(b, lo, enq, s);
+      PCD_HIP_TRY(hipEventRecord(ev1, s));
+      // the tail is enqueued behind the first batch without looking at the flag: at the defaults the PCG has ended
+      // by then and the iteration costs one copy; otherwise the batches go on and the tail runs once more
+      const LmRecord* rec = S.lm_host.p;
+      for (;;) {
+        pcg_finish(b, S.lm_dpose.p, S.cg_info.p, s);
+        PCD_TRY(pcd_ba_schur_back_substitute_device(b, S.lm_dpose.p, S.lm_dpoint.p, S.md.p, s));
+        PCD_TRY(pcd_ba_plus_device(b, S.lm_dpose.p, S.lm_dpoint.p, b->poses.p, b->points.p, s));
+        PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
+        hipLaunchKernelGGL(k_ba_lm_record, dim3(1), dim3(256), 0, s, S.cost.p, S.lm_cand_cost.p, S.md.p, S.lm_gpart.p,
+                           (int)ngp, S.skip_cnt.p, S.cg_info.p, S.lm_rec.p);
+        PCD_HIP_TRY(hipMemcpyAsync(S.lm_host.p, S.lm_rec.p, sizeof(LmRecord), hipMemcpyDeviceToHost, s));
+        PCD_HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) linear_ms += ms;
+        if (rec->pcg.termination >= 0 || enq >= lo->max_iterations) break;
+        // the step just tried came from an unfinished solve: back to the accepted parameters, finish the solve
+        PCD_HIP_TRY(hipMemcpyAsync(b->poses.p, S.lm_poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipMemcpyAsync(b->points.p, S.lm_points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipEventRecord(ev0, s));
+        PCD_TRY(pcg_run(b, lo, enq, s));
+        enq = lo->max_iterations;
+        PCD_HIP_TRY(hipEventRecord(ev1, s));
+      }
+      PCD_HIP_TRY(hipGetLastError());
+      if (it == 0) sm.initial_cost = sm.final_cost = rec->cost;
+      const bool restore_only = opts->gradient_tolerance > 0.0 && rec->gradient_max <= opts->gradient_tolerance;
+      pcd_ba_solve_iteration r{};
+      r.cost = rec->cost; r.candidate_cost = rec->candidate_cost; r.model_decrease = rec->model_decrease;
+      r.gradient_max_norm = rec->gradient_max; r.num_skipped = rec->num_skipped;
+      r.linear_iterations = rec->pcg.iterations; r.linear_termination = rec->pcg.termination;
+      const bool solved = rec->pcg.termination != PCD_PCG_BREAKDOWN;
+      const double rho = (solved && r.model_decrease > 0.0) ? (r.cost - r.candidate_cost) / r.model_decrease
+                                                            : -std::numeric_limits<double>::infinity();
+      r.relative_decrease = rho;
+      r.accepted = !restore_only && rho > opts->min_relative_decrease;
+      if (r.accepted) {
+        radius = std::min(opts->max_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3.0)));
+        factor = 2.0;
+        PCD_HIP_TRY(hipMemcpyAsync(S.lm_poses.p, b->poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipMemcpyAsync(S.lm_points.p, b->points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
+      } else {
+        PCD_HIP_TRY(hipMemcpyAsync(b->poses.p, S.lm_poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipMemcpyAsync(b->points.p, S.lm_points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
+      }
+      if (restore_only) { sm.termination = PCD_SOLVE_GRADIENT_TOLERANCE; break; }
+      if (!r.accepted) { radius /= factor; factor *= 2.0; }
+      r.radius = radius;
+      if (iterations) iterations[it] = r;
+      sm.num_iterations = it + 1;
+      if (r.accepted) {
+        sm.num_accepted++;
+        sm.final_cost = r.candidate_cost;
+        if (opts->function_tolerance > 0.0 && std::fabs(r.cost - r.candidate_cost) <= opts->function_tolerance * r.cost) {
+          sm.termination = PCD_SOLVE_FUNCTION_TOLERANCE;
+          break;
+        }
+      }
+    }
+    PCD_HIP_TRY(hipStreamSynchronize(s));
+    S.valid = false;   // the Schur state belongs to parameters the loop has moved on from
+    sm.linear_solver_ms = linear_ms;
+    sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (summary) *summary = sm;
+    return PCD_OK;
+  });
 }
 
 }  // extern "C"

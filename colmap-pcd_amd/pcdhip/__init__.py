@@ -100,6 +100,49 @@ class BASchurInfo(C.Structure):
     _fields_ = [("build_ms", C.c_double), ("num_entries", C.c_uint64), ("scratch_bytes", C.c_uint64)]
 
 
+PRECOND_IDENTITY, PRECOND_SCHUR_JACOBI = 0, 1
+_PRECOND = {"identity": PRECOND_IDENTITY, "schur_jacobi": PRECOND_SCHUR_JACOBI}
+PCG_MAX_ITERATIONS, PCG_Q_TOLERANCE, PCG_R_TOLERANCE, PCG_BREAKDOWN, PCG_ZERO_RHS = range(5)
+SOLVE_MAX_ITERATIONS, SOLVE_FUNCTION_TOLERANCE, SOLVE_GRADIENT_TOLERANCE, SOLVE_MIN_RADIUS = range(4)
+
+
+class BAPcgOpts(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("min_iterations", C.c_int32), ("preconditioner", C.c_int32),
+                ("q_tolerance", C.c_double), ("r_tolerance", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class BAPcgInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("termination", C.c_int32), ("precond_fallbacks", C.c_uint32),
+                ("rhs_norm", C.c_double), ("residual_norm", C.c_double), ("q", C.c_double),
+                ("step_dot_residual", C.c_double)]
+
+
+PCG_INFO_DTYPE = np.dtype([("iterations", np.int32), ("termination", np.int32), ("precond_fallbacks", np.uint32),
+                           ("pad", np.uint32), ("rhs_norm", np.float64), ("residual_norm", np.float64),
+                           ("q", np.float64), ("step_dot_residual", np.float64)])
+assert PCG_INFO_DTYPE.itemsize == C.sizeof(BAPcgInfo) == 48
+
+
+class BASolveOpts(C.Structure):
+    _fields_ = [("max_num_iterations", C.c_int32), ("damping", C.c_int32), ("initial_radius", C.c_double),
+                ("max_radius", C.c_double), ("min_radius", C.c_double), ("min_relative_decrease", C.c_double),
+                ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double), ("linear", BAPcgOpts),
+                ("reserved", C.c_int32 * 8)]
+
+
+class BASolveIteration(C.Structure):
+    _fields_ = [("cost", C.c_double), ("candidate_cost", C.c_double), ("model_decrease", C.c_double),
+                ("relative_decrease", C.c_double), ("radius", C.c_double), ("gradient_max_norm", C.c_double),
+                ("accepted", C.c_int32), ("linear_iterations", C.c_int32), ("linear_termination", C.c_int32),
+                ("num_skipped", C.c_uint64)]
+
+
+class BASolveSummary(C.Structure):
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("num_iterations", C.c_int32),
+                ("num_accepted", C.c_int32), ("termination", C.c_int32), ("total_ms", C.c_double),
+                ("linear_solver_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -133,6 +176,8 @@ ABI_SYMBOLS = [
     "pcd_cloud_shards_get", "pcd_nn_query_sharded", "pcd_associate_sharded",
     "pcd_ba_set_parameters_device", "pcd_ba_schur_structure", "pcd_ba_schur_device", "pcd_ba_schur",
     "pcd_ba_schur_back_substitute_device", "pcd_ba_plus_device", "pcd_ba_schur_stats",
+    "pcd_ba_pcg_opts_default", "pcd_ba_schur_solve_pcg_device", "pcd_ba_schur_solve_pcg", "pcd_ba_get_parameters",
+    "pcd_ba_solve_opts_default", "pcd_ba_solve",
 ]
 
 
@@ -210,6 +255,15 @@ def lib():
         L.pcd_ba_schur_back_substitute_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pcd_ba_plus_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5
         L.pcd_ba_schur_stats.argtypes = [C.c_void_p, C.POINTER(BASchurInfo)]
+    if hasattr(L, "pcd_ba_solve"):
+        L.pcd_ba_pcg_opts_default.argtypes = [C.POINTER(BAPcgOpts)]
+        L.pcd_ba_pcg_opts_default.restype = None
+        L.pcd_ba_schur_solve_pcg_device.argtypes = [C.c_void_p, C.POINTER(BAPcgOpts), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pcd_ba_schur_solve_pcg.argtypes = [C.c_void_p, C.POINTER(BAPcgOpts), C.c_void_p, C.POINTER(BAPcgInfo)]
+        L.pcd_ba_get_parameters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pcd_ba_solve_opts_default.argtypes = [C.POINTER(BASolveOpts)]
+        L.pcd_ba_solve_opts_default.restype = None
+        L.pcd_ba_solve.argtypes = [C.c_void_p, C.POINTER(BASolveOpts), C.POINTER(BASolveSummary), C.c_void_p]
     _LIB = L
     return L
 
@@ -913,6 +967,39 @@ class BA:
                                         C.c_void_p(stream)))
         return poses_out, points_out
 
+    def schur_solve_pcg(self, dpose=None, **opts):
+        """block-sparse PCG on the reduced system of the last schur() call (whose S_diag / S_off / rhs must have stayed
+        in the handle: want without them).  opts: pcg_opts() arguments.  Returns (dpose [ns][6] torch device tensor,
+        info dict: iterations, termination, precond_fallbacks, rhs_norm, residual_norm, q, step_dot_residual)"""
+        torch, dev, stream = self._torch()
+        if not hasattr(self, "_schur_dims"):
+            st = self.schur_structure()
+            self._schur_dims = (st["num_slots"], st["pairs"].shape[0])
+        ns = self._schur_dims[0]
+        if dpose is None:
+            dpose = torch.empty((ns, 6), dtype=torch.float64, device=dev)
+        d_info = torch.zeros(C.sizeof(BAPcgInfo), dtype=torch.uint8, device=dev)
+        o = pcg_opts(**opts)
+        _check(lib().pcd_ba_schur_solve_pcg_device(self._h, C.byref(o), _ptr(dpose), _ptr(d_info), C.c_void_p(stream)))
+        i = d_info.cpu().numpy().view(PCG_INFO_DTYPE)[0]
+        return dpose, {k: (float(i[k]) if PCG_INFO_DTYPE[k] == np.float64 else int(i[k]))
+                       for k in PCG_INFO_DTYPE.names if k != "pad"}
+
+    def schur_solve_pcg_host(self, **opts):
+        """pcd_ba_schur_solve_pcg: the same solve with host outputs (numpy dpose [ns][6], info dict)"""
+        ns = self.schur_structure()["num_slots"]
+        dpose = np.zeros((ns, 6))
+        info = BAPcgInfo()
+        o = pcg_opts(**opts)
+        _check(lib().pcd_ba_schur_solve_pcg(self._h, C.byref(o), _vp(dpose), C.byref(info)))
+        return dpose, _pcg_info(info)
+
+    def get_parameters(self):
+        """the handle's current parameters, device -> host: (poses [I][7], points [P][3]) numpy"""
+        poses, points = np.empty((self.I, 7)), np.empty((self.P, 3))
+        _check(lib().pcd_ba_get_parameters(self._h, _vp(poses), _vp(points)))
+        return poses, points
+
     def set_parameters_device(self, poses=None, points=None):
         """device -> device parameter update from torch tensors (None keeps the old values)"""
         _, _, stream = self._torch()
@@ -927,8 +1014,63 @@ class BA:
         return out
 
 
+def pcg_opts(max_iterations=None, min_iterations=None, preconditioner=None, q_tolerance=None, r_tolerance=None):
+    """pcd_ba_pcg_opts at the library's defaults (100, 0, schur_jacobi, 0.1, -1) with the given fields replaced"""
+    o = BAPcgOpts()
+    lib().pcd_ba_pcg_opts_default(C.byref(o))
+    if max_iterations is not None:
+        o.max_iterations = int(max_iterations)
+    if min_iterations is not None:
+        o.min_iterations = int(min_iterations)
+    if preconditioner is not None:
+        o.preconditioner = _PRECOND[preconditioner] if isinstance(preconditioner, str) else int(preconditioner)
+    if q_tolerance is not None:
+        o.q_tolerance = float(q_tolerance)
+    if r_tolerance is not None:
+        o.r_tolerance = float(r_tolerance)
+    return o
+
+
+def _pcg_info(i):
+    return dict(iterations=int(i.iterations), termination=int(i.termination),
+                precond_fallbacks=int(i.precond_fallbacks), rhs_norm=float(i.rhs_norm),
+                residual_norm=float(i.residual_norm), q=float(i.q), step_dot_residual=float(i.step_dot_residual))
+
+
+def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max_radius=None, min_radius=None,
+             min_relative_decrease=None, function_tolerance=None, gradient_tolerance=None, linear=None):
+    """pcd_ba_solve: the LM loop in the library (Schur, PCG, back-substitution, cost pass; no torch).  Options left
+    None keep pcd_ba_solve_opts_default; linear is a dict of pcg_opts() arguments.  Returns (summary dict, list of one
+    dict per iteration); the handle holds the accepted parameters (BA.get_parameters())."""
+    L = lib()
+    o = BASolveOpts()
+    L.pcd_ba_solve_opts_default(C.byref(o))
+    if max_num_iterations is not None:
+        o.max_num_iterations = int(max_num_iterations)
+    if damping is not None:
+        o.damping = _DAMPING[damping]
+    for name, v in (("initial_radius", initial_radius), ("max_radius", max_radius), ("min_radius", min_radius),
+                    ("min_relative_decrease", min_relative_decrease), ("function_tolerance", function_tolerance),
+                    ("gradient_tolerance", gradient_tolerance)):
+        if v is not None:
+            setattr(o, name, float(v))
+    if linear is not None:
+        o.linear = linear if isinstance(linear, BAPcgOpts) else pcg_opts(**linear)
+    its = (BASolveIteration * max(o.max_num_iterations, 1))()
+    sm = BASolveSummary()
+    _check(L.pcd_ba_solve(ba._h, C.byref(o), C.byref(sm), C.cast(its, C.c_void_p)))
+    summary = {n: getattr(sm, n) for n, _ in BASolveSummary._fields_}
+    hist = []
+    for k in range(sm.num_iterations):
+        r = {n: getattr(its[k], n) for n, _ in BASolveIteration._fields_}
+        r["accepted"] = bool(r["accepted"])
+        r["rho"] = r["relative_decrease"]
+        hist.append(r)
+    return summary, hist
+
+
 def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", min_relative_decrease=1e-3,
-                max_radius=1e16):
+                max_radius=1e16, linear_solver="cholesky", pcg=None):
     """Device-resident Levenberg-Marquardt on a BA handle.  Each iteration: ba.schur (points eliminated on the
     device), torch.linalg.cholesky of the dense reduced camera system (a failed factorisation counts as a rejected
     step), back-substitution and plus into candidate buffers, the cost pass at the candidate, then Ceres' trust-region
@@ -939,8 +1081,15 @@ def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", 
     There is no Jacobi scaling of the columns (Ceres scales them by default), so the iterates are not Ceres' own
     iterate for iterate; the step, model and radius rules are.  On return the handle holds the accepted parameters.
     Returns a list with one dict per iteration: cost (before the step), candidate_cost, rho, accepted, radius (after
-    the update), num_skipped."""
+    the update), num_skipped.
+
+    linear_solver="pcg" replaces the dense factorisation with BA.schur_solve_pcg on the block-sparse system (the dense
+    S is not asked for); pcg is a dict of pcg_opts() arguments.  A BREAKDOWN counts as a rejected step.  Each record
+    then also has linear_iterations and linear_termination."""
     import torch
+    if linear_solver not in ("cholesky", "pcg"):
+        raise ValueError(f"linear_solver {linear_solver!r}: 'cholesky' or 'pcg'")
+    use_pcg = linear_solver == "pcg"
     dev = torch.device("cuda", ba.device)
     ns = ba.schur_structure()["num_slots"]
     zero_pose = torch.zeros((ns, 6), dtype=torch.float64, device=dev)
@@ -950,16 +1099,26 @@ def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", 
     radius, decrease_factor = float(initial_radius), 2.0
     history = []
     for _ in range(int(max_iterations)):
-        out = ba.schur(1.0 / radius, damping=damping, dense=True, want=("cost", "rhs", "num_skipped"))
+        if use_pcg:
+            out = ba.schur(1.0 / radius, damping=damping, want=("cost", "num_skipped"))
+        else:
+            out = ba.schur(1.0 / radius, damping=damping, dense=True, want=("cost", "rhs", "num_skipped"))
         cost = float(out["cost"].item())
         rec = dict(cost=cost, candidate_cost=float("nan"), rho=float("nan"), accepted=False,
                    num_skipped=int(out["num_skipped"].item()))
         factored = True
-        if ns:
+        if use_pcg:
+            dpose_pcg, info = ba.schur_solve_pcg(**(pcg or {}))
+            rec.update(linear_iterations=info["iterations"], linear_termination=info["termination"])
+            factored = info["termination"] != PCG_BREAKDOWN
+        elif ns:
             Lc, info = torch.linalg.cholesky_ex(out["S"])
             factored = int(info.item()) == 0
         if factored:   # ns = 0 (every pose constant): no reduced system, only the points move
-            dpose = torch.cholesky_solve(out["rhs"].reshape(-1, 1), Lc).reshape(-1, 6) if ns else zero_pose
+            if use_pcg:
+                dpose = dpose_pcg
+            else:
+                dpose = torch.cholesky_solve(out["rhs"].reshape(-1, 1), Lc).reshape(-1, 6) if ns else zero_pose
             dpoint, md = ba.back_substitute(dpose)
             ba.plus(dpose, dpoint, cand_poses, cand_points)
             ba.set_parameters_device(cand_poses, cand_points)

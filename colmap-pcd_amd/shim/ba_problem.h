@@ -74,6 +74,11 @@ struct BundleAdjustmentOptions {  // optim/bundle_adjustment.h:52-91 (this fork'
   double loss_function_scale = 1.0;
   bool refine_focal_length = false, refine_principal_point = false, refine_extra_params = false;
   bool refine_extrinsics = true;
+  // ceres::Solver::Options members BundleAdjusterHip::Solve reads (optim/bundle_adjustment.h:96-103)
+  int max_num_iterations = 100;
+  int max_linear_solver_iterations = 200;
+  double function_tolerance = 0.0;
+  double gradient_tolerance = 0.0;
 };
 
 class BundleAdjustmentConfig {  // optim/bundle_adjustment.h:118-200, .cc:76-233
@@ -198,6 +203,40 @@ class BundleAdjusterHip {
     return pcd_ba_create(&d, &ba_) == PCD_OK;
   }
   pcd_ba* handle() const { return ba_; }
+
+  // ---- solve (HIP): the device route end to end, after SetUp() ---------------------------------
+  // Create, pcd_ba_solve (LM with the block-sparse PCG on the reduced camera system), then the accepted poses and
+  // points go back into the Reconstruction through image_ids_ / point_ids_; constant poses and points are not
+  // written at all.  false when there are no residuals (as the reference, :489-491), when intrinsics are refined
+  // (the device route does not carry camera rows: the caller stays on the Ceres route) or when a call fails
+  // (pcd_last_error()).
+  bool Solve(Reconstruction* rec, int device = 0) {
+    summary_ = pcd_ba_solve_summary{};
+    if (NumResiduals() == 0) return false;
+    for (uint8_t v : cam_refine_)
+      if (v) return false;
+    if (!Create(device)) return false;
+    pcd_ba_solve_opts o;
+    pcd_ba_solve_opts_default(&o);
+    o.max_num_iterations = options_.max_num_iterations;
+    o.function_tolerance = options_.function_tolerance;
+    o.gradient_tolerance = options_.gradient_tolerance;
+    o.linear.max_iterations = options_.max_linear_solver_iterations;
+    if (pcd_ba_solve(ba_, &o, &summary_, nullptr) != PCD_OK) return false;
+    if (pcd_ba_get_parameters(ba_, poses_.data(), points_.data()) != PCD_OK) return false;
+    for (size_t i = 0; i < image_ids_.size(); ++i) {
+      if (image_const_pose_[i]) continue;
+      Image& im = rec->images.at(image_ids_[i]);
+      std::copy(poses_.begin() + 7 * i, poses_.begin() + 7 * i + 4, im.qvec);
+      std::copy(poses_.begin() + 7 * i + 4, poses_.begin() + 7 * i + 7, im.tvec);
+    }
+    for (size_t p = 0; p < point_ids_.size(); ++p) {
+      if (point_const_[p]) continue;
+      std::copy(points_.begin() + 3 * p, points_.begin() + 3 * p + 3, rec->points3D.at(point_ids_[p]).xyz);
+    }
+    return true;
+  }
+  const pcd_ba_solve_summary& Summary() const { return summary_; }
 
   // flat arrays (also what a solver scatters back into the Reconstruction)
   std::vector<int32_t> cam_model_, cam_off_, image_cam_, obs_image_, obs_point_, lidar_point_;
@@ -347,6 +386,7 @@ class BundleAdjusterHip {
   const BundleAdjustmentOptions options_;
   BundleAdjustmentConfig config_;
   pcd_ba* ba_ = nullptr;
+  pcd_ba_solve_summary summary_{};
   std::unordered_map<camera_t, int> cam_index_;
   std::unordered_map<image_t, int> image_index_;
   std::unordered_map<point3D_t, int> point_index_;

@@ -566,6 +566,86 @@ typedef struct {
 } pcd_ba_schur_info;
 pcd_status pcd_ba_schur_stats(pcd_ba* ba, pcd_ba_schur_info* info);
 
+/* Reduced camera system on the device: block-sparse preconditioned conjugate gradients on S dpose = rhs of the LAST
+ * Schur call on the handle, read from the handle's own S_diag / S_off / rhs (INVALID, with a message that says which,
+ * when there is no Schur state or when that call sent one of the three to caller memory).  fp64, no atomics,
+ * fixed-order sums: bitwise reproducible.  From x_0 = 0 (no warm start: r_k stays orthogonal to x_k, so the model
+ * decrease of pcd_ba_schur_back_substitute_device holds for an inexact step), iteration k = 1, 2, ...:
+ *   z = M^-1 r; rho = r.z; p = z + (rho / rho_old) p; w = S p; alpha = rho / (p.w); x += alpha p; r -= alpha w
+ * then, with Q_k = -1/2 x.(rhs + r) (= 1/2 x^T S x - x^T rhs):
+ *   1. zeta = k (Q_k - Q_{k-1}) / Q_k;  k >= min_iterations and zeta < q_tolerance          -> PCD_PCG_Q_TOLERANCE
+ *   2. k >= min_iterations and ||r|| <= r_tolerance ||rhs||                                   -> PCD_PCG_R_TOLERANCE
+ *   3. k = max_iterations                                                                     -> PCD_PCG_MAX_ITERATIONS
+ * A negative tolerance switches its test off.  ||rhs|| = 0 (and ns = 0): x = 0, PCD_PCG_ZERO_RHS, 0 iterations.
+ * p.w <= 0 or a non-finite scalar: PCD_PCG_BREAKDOWN, x is the last finite iterate.
+ * Preconditioner: SCHUR_JACOBI = the inverse of every 6x6 diagonal block of S through its Cholesky factor (a block with
+ * a non-positive pivot falls back to the identity and is counted; constant-tvec coordinates stay identity), or IDENTITY.
+ * Guards as for the other pcd_ba_schur* calls.  The host looks at the device's done flag once per batch of
+ * iterations (8, 16, then 32 at a time); nothing else is synchronised. */
+typedef enum { PCD_PRECOND_IDENTITY = 0, PCD_PRECOND_SCHUR_JACOBI = 1 } pcd_ba_preconditioner;
+typedef enum { PCD_PCG_MAX_ITERATIONS = 0, PCD_PCG_Q_TOLERANCE = 1, PCD_PCG_R_TOLERANCE = 2,
+               PCD_PCG_BREAKDOWN = 3, PCD_PCG_ZERO_RHS = 4 } pcd_ba_pcg_termination;
+typedef struct {
+  int32_t max_iterations, min_iterations;
+  int32_t preconditioner;           /* pcd_ba_preconditioner */
+  double q_tolerance, r_tolerance;
+  int32_t reserved[8];
+} pcd_ba_pcg_opts;
+typedef struct {
+  int32_t iterations, termination;  /* pcd_ba_pcg_termination */
+  uint32_t precond_fallbacks;       /* slots whose diagonal block failed its Cholesky */
+  double rhs_norm, residual_norm;   /* ||rhs||, ||r|| of the recurrence */
+  double q;                         /* Q of the last iteration */
+  double step_dot_residual;         /* x.r, 0 up to rounding (diagnostic) */
+} pcd_ba_pcg_info;
+void pcd_ba_pcg_opts_default(pcd_ba_pcg_opts* opts);   /* 100, 0, SCHUR_JACOBI, 0.1, -1 */
+pcd_status pcd_ba_schur_solve_pcg_device(pcd_ba* ba, const pcd_ba_pcg_opts* opts, double* d_dpose /*[ns][6]*/,
+                                         pcd_ba_pcg_info* d_info /*device, may be NULL*/, void* stream);
+pcd_status pcd_ba_schur_solve_pcg(pcd_ba* ba, const pcd_ba_pcg_opts* opts, double* dpose /*[ns][6] host*/,
+                                  pcd_ba_pcg_info* info /*host, may be NULL*/);
+/* current parameters, device -> host (either pointer may be NULL) */
+pcd_status pcd_ba_get_parameters(pcd_ba* ba, double* poses /*[I][7]*/, double* points /*[P][3]*/);
+
+/* Levenberg-Marquardt in the library.  Each iteration: pcd_ba_schur_device at mu = 1 / radius, the PCG above
+ * (BREAKDOWN counts as a rejected step), back-substitution, Plus into the handle's parameters (the accepted ones are
+ * kept in handle scratch), the cost pass at the candidate, then Ceres' trust-region rule: accept if
+ * rho = (cost - candidate_cost) / model_decrease > min_relative_decrease; on success
+ * radius = min(max_radius, radius / max(1/3, 1 - (2 rho - 1)^3)) and the decrease factor resets to 2, on failure
+ * radius /= factor and the factor doubles.  No Jacobi scaling of the columns.  It stops at max_num_iterations
+ * (PCD_SOLVE_MAX_ITERATIONS), when |cost - candidate_cost| <= function_tolerance cost after an accepted step, when
+ * the gradient max-norm at the current parameters is <= gradient_tolerance (tested before the step is tried), or when
+ * radius < min_radius.  The gradient test is the plain max-norm of g over the active pose coordinates and the
+ * non-constant points, NOT Ceres' manifold-projected ||Plus(x, -g) - x||.  A tolerance of 0 switches its test off.
+ * One small device-to-host copy per iteration carries the costs, the model decrease, the PCG record and the gradient
+ * norm (one more per extra batch when the PCG runs past its first 8 iterations).  On return the handle holds the
+ * accepted parameters. */
+typedef enum { PCD_SOLVE_MAX_ITERATIONS = 0, PCD_SOLVE_FUNCTION_TOLERANCE = 1, PCD_SOLVE_GRADIENT_TOLERANCE = 2,
+               PCD_SOLVE_MIN_RADIUS = 3 } pcd_ba_solve_termination;
+typedef struct {
+  int32_t max_num_iterations;
+  int32_t damping;                  /* pcd_ba_damping */
+  double initial_radius, max_radius, min_radius, min_relative_decrease, function_tolerance, gradient_tolerance;
+  pcd_ba_pcg_opts linear;
+  int32_t reserved[8];
+} pcd_ba_solve_opts;
+typedef struct {
+  double cost, candidate_cost, model_decrease, relative_decrease;
+  double radius;                    /* after the update */
+  double gradient_max_norm;         /* at the parameters the iteration started from */
+  int32_t accepted, linear_iterations, linear_termination;
+  uint64_t num_skipped;
+} pcd_ba_solve_iteration;
+typedef struct {
+  double initial_cost, final_cost;
+  int32_t num_iterations, num_accepted;
+  int32_t termination;              /* pcd_ba_solve_termination */
+  double total_ms, linear_solver_ms;
+} pcd_ba_solve_summary;
+/* 10, MARQUARDT, 1e4, 1e16, 1e-32, 1e-3, 0, 0, linear = pcd_ba_pcg_opts_default */
+void pcd_ba_solve_opts_default(pcd_ba_solve_opts* opts);
+pcd_status pcd_ba_solve(pcd_ba* ba, const pcd_ba_solve_opts* opts, pcd_ba_solve_summary* summary,
+                        pcd_ba_solve_iteration* iterations /*[max_num_iterations] or NULL*/);
+
 /* ------------------------------------------------------------------------
  * Exact SIFT descriptor matching (stretch row a19)
  *   replaces feature/sift.cc:1041-1054 MatchSiftFeaturesCPUBruteForce =

@@ -1,10 +1,12 @@
 """Timing of the device point elimination (pcd_ba_schur*) part by part, at workload M (bench.py's BA scene,
 1000 images / 1 M points / 4.72 M observations) and at config B's size (450 images / 400 k points / 1.87 M observations).
 
-  python tools/ba_schur_probe.py [--out profiles/ba_schur_probe.txt] [--reps 15] [--only M|B]
+  python tools/ba_schur_probe.py [--out profiles/ba_solve_probe.txt] [--reps 15] [--only M|B]
 
 Parts: structure build (host counting sorts, once per handle), normal-equation pass, elimination, dense fill,
-torch.linalg.cholesky + solve, back-substitution + plus, cost pass, a whole LM iteration of pcdhip.ba_solve_lm.
+torch.linalg.cholesky + solve, back-substitution + plus, cost pass, a whole LM iteration of pcdhip.ba_solve_lm; then
+the block-sparse PCG beside the Cholesky (at the defaults and to r_tolerance 1e-10, each call with its one read of the
+record), the time per CG iteration, and a whole LM iteration through pcd_ba_solve.
 Device parts are timed with the library's per-scope hipEvents (pcdhip.profile_*), host-driven parts with
 torch.cuda.Event pairs; warm-up first, then the median (and min / max) of --reps runs."""
 import argparse
@@ -109,8 +111,41 @@ def probe(tag, reps, log):
         return (time.perf_counter() - t) * 1e3
     lm_iter()
     r["whole LM iteration (wall, incl. host syncs)"] = [lm_iter() for _ in range(reps)]
+    # the reduced solve on the block-sparse system, same S (mu 1e-4, blocks left in the handle)
+    ba.set_parameters(*keep)
+    ba.schur(mu, want=("cost", "num_skipped"))
+    xbuf = torch.empty((ns, 6), dtype=torch.float64, device="cuda")
+    its = {}
+
+    def pcg_default():
+        its["default"] = ba.schur_solve_pcg(dpose=xbuf)[1]
+
+    def pcg_tight():
+        its["tight"] = ba.schur_solve_pcg(dpose=xbuf, r_tolerance=1e-10, q_tolerance=-1.0, max_iterations=2000)[1]
+    r["PCG at the defaults"] = evented(pcg_default, reps)
+    r["PCG to r_tolerance 1e-10"] = evented(pcg_tight, reps)
+
+    def solve_iter():
+        ba.set_parameters(*keep)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        pcdhip.ba_solve(ba, max_num_iterations=1)
+        return (time.perf_counter() - t) * 1e3
+    solve_iter()
+    r["whole LM iteration, pcd_ba_solve (wall)"] = [solve_iter() for _ in range(reps)]
     for k, v in r.items():
         log("  %-44s %s" % (k, stats(v)))
+    nd, nt = its["default"]["iterations"], its["tight"]["iterations"]
+    td, tt = np.median(r["PCG at the defaults"]), np.median(r["PCG to r_tolerance 1e-10"])
+    log("  PCG iterations: %d at the defaults (relative residual %.3f), %d to 1e-10; %.1f us per CG iteration "
+        "((tight - default) / (iterations apart)), %.1f us with the set-up shared out (tight / iterations); "
+        "three launch boundaries are ~5 us"
+        % (nd, its["default"]["residual_norm"] / its["default"]["rhs_norm"], nt,
+           1e3 * (tt - td) / max(nt - nd, 1), 1e3 * tt / max(nt, 1)))
+    lo, hi = np.min(r["whole LM iteration (wall, incl. host syncs)"]), np.max(r["whole LM iteration (wall, incl. host syncs)"])
+    log("  whole LM iteration: dense Cholesky route %.3f ms (spread %.3f), pcd_ba_solve %.3f ms"
+        % (np.median(r["whole LM iteration (wall, incl. host syncs)"]), hi - lo,
+           np.median(r["whole LM iteration, pcd_ba_solve (wall)"])))
     ba.close()
     return r
 
