@@ -84,6 +84,12 @@ class BAOut(C.Structure):
                                            "H_cam", "g_cam", "E_cam", "W_cam")]
 
 
+class BABlocks(C.Structure):
+    """pcd_ba_blocks: pointers into the handle's pinned buffers"""
+    _fields_ = [(n, C.c_void_p) for n in ("residuals", "jac_q", "jac_t", "jac_X", "jac_lidar", "jac_cam", "pose_row")] + \
+               [("num_pose_rows", C.c_uint64), ("bytes_d2h", C.c_uint64)]
+
+
 DAMP_MARQUARDT, DAMP_LEVENBERG = 0, 1
 _DAMPING = {"marquardt": DAMP_MARQUARDT, "levenberg": DAMP_LEVENBERG}
 
@@ -246,6 +252,8 @@ def lib():
         L.pcd_ba_evaluate.argtypes = [C.c_void_p, C.POINTER(BAOut)]
         L.pcd_ba_evaluate_device.argtypes = [C.c_void_p, C.POINTER(BAOut), C.c_void_p]
         L.pcd_ba_device_parameters.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        L.pcd_ba_set_camera_parameters.argtypes = [C.c_void_p, C.c_void_p]
+        L.pcd_ba_evaluate_blocks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(BABlocks)]
     if hasattr(L, "pcd_ba_schur_device"):
         L.pcd_ba_set_parameters_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pcd_ba_schur_structure.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
@@ -849,6 +857,46 @@ class BA:
         p = None if poses is None else np.ascontiguousarray(poses, np.float64)
         x = None if points is None else np.ascontiguousarray(points, np.float64)
         _check(lib().pcd_ba_set_parameters(self._h, _vp(p), _vp(x)))
+
+    def set_camera_parameters(self, cam_params):
+        """refined intrinsics between iterations: a list of per-camera vectors (as cam_params_list) or the packed
+        array, same layout as at creation"""
+        flat = np.asarray(cam_params, np.float64) if np.ndim(cam_params[0]) == 0 else np.concatenate(
+            [np.asarray(c, np.float64) for c in cam_params])
+        flat = np.ascontiguousarray(flat, np.float64)
+        assert flat.shape == self.cam_params.shape
+        _check(lib().pcd_ba_set_camera_parameters(self._h, _vp(flat)))
+        self.cam_params = flat
+
+    def evaluate_blocks(self, want_jacobians=True, want_jac_cam=False):
+        """the Ceres route (pcd_ba_evaluate_blocks): raw blocks of every residual block through the handle's pinned
+        buffers, copied out before returning.  jac_q / jac_t hold one row per variable-pose observation, pose_row [O]
+        uint32 is observation o's row (0xFFFFFFFF: constant pose).  Arrays that were not asked for are None (the C
+        pointer is NULL); an array that was asked for and has no rows is empty."""
+        bl = BABlocks()
+        _check(lib().pcd_ba_evaluate_blocks(self._h, int(bool(want_jacobians)), int(bool(want_jac_cam)), C.byref(bl)))
+        V = int(bl.num_pose_rows)
+
+        def take(name, shape, wanted, dtype=np.float64):
+            ptr = getattr(bl, name)
+            n = int(np.prod(shape))
+            if not wanted:
+                if ptr:
+                    raise PcdError(PCD_ERR_INVALID, f"pcd_ba_evaluate_blocks: {name} not requested but not NULL")
+                return None
+            if n == 0:
+                return np.zeros(shape, dtype)
+            if not ptr:
+                raise PcdError(PCD_ERR_INVALID, f"pcd_ba_evaluate_blocks: {name} is NULL")
+            return np.frombuffer((C.c_char * (n * np.dtype(dtype).itemsize)).from_address(ptr), dtype).reshape(shape).copy()
+        wj = bool(want_jacobians)
+        out = dict(residuals=take("residuals", (2 * self.O + self.L,), True),
+                   jac_q=take("jac_q", (V, 2, 4), wj), jac_t=take("jac_t", (V, 2, 3), wj),
+                   jac_X=take("jac_X", (self.O, 2, 3), wj), jac_lidar=take("jac_lidar", (self.L, 3), wj),
+                   jac_cam=take("jac_cam", (self.O, 2, CAM_JAC_STRIDE), wj and bool(want_jac_cam)),
+                   pose_row=take("pose_row", (self.O,), True, np.uint32),
+                   num_pose_rows=V, bytes_d2h=int(bl.bytes_d2h))
+        return out
 
     def evaluate(self, want=("cost", "residuals", "jac_q", "jac_t", "jac_X", "jac_lidar", "H_img", "g_img", "H_pt",
                              "g_pt")):
