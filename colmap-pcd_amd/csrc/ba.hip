@@ -14,9 +14,10 @@
 //                iterations and every load instruction reads 64 consecutive records.  Accumulates the
 //                point's 3x3 block, gradient and the cost.  No atomics: point blocks are complete inside
 //                one thread, the cost goes through a fixed-order two-stage sum.
-//   k_ba_images  workgroup = image; its observations are stored image-major (contiguous), strided over
-//                256 lanes; each lane recomputes the 2x6 pose-tangent Jacobian and accumulates 21 + 6
-//                unique entries; fixed-order block reduction -> deterministic 6x6 block + gradient.
+//   k_ba_images  workgroup = segment of an image; its observations are stored image-major (contiguous), strided
+//                over 256 lanes; each lane recomputes the 2x6 pose-tangent Jacobian, the 21 + 6 unique entries of
+//                [J | r]^T [J | r] are summed on the fp64 matrix pipe; fixed-order reduction -> deterministic 6x6
+//                block + gradient.
 //   k_ba_raw     thread = observation / LiDAR term: the raw ambient blocks exactly as
 //                CostFunction::Evaluate returns them (for the Ceres EvaluationCallback adapter).
 // Jacobians are recomputed in each kernel instead of being staged through HBM (160 B/obs of traffic
@@ -277,27 +278,58 @@ __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__
 // `partial` and k_ba_images_reduce adds the segments of an image in ascending order: still no atomics, still
 // bitwise reproducible.
 constexpr uint32_t kImgSeg = 1024;
+// The 27 sums of a segment are the upper triangle and the last column of A^T A, A = [J | r]: 7 columns and two rows
+// per observation, a small-N GEMM.  They are summed on the fp64 matrix pipe (v_mfma_f64_16x16x4_f64) instead of in
+// 27 per-lane fp64 accumulators: a wavefront's sums live in one 4-double accumulator (8 VGPRs instead of 54, held
+// across the whole Jacobian evaluation before), the 54 VALU FMAs per observation and the 27 x 6-step shuffle butterfly
+// at the end of the segment go away, and the matrix pipe (otherwise idle here) runs beside the other wavefronts' VALU.
+//
+// Per iteration a wavefront has 128 rows (lane l: rows 2l and 2l+1) of 7 values.  They are staged COLUMN-major in the
+// wavefront's LDS scratch -- column c, rows 2l..2l+1 as one 16-B write at c * kRowColStride + 16 l, so a write
+// instruction covers 1 KiB of consecutive addresses -- and read back as MFMA operands.  The 16x16x4 instruction has
+// room for two independent 7-column products: with the SAME register as both operands, lane l holding
+// data[row(k = l >> 4, h = (l >> 3) & 1)][col = l & 7], the result is D[i][j] = sum_k op[k][i] op[k][j], whose
+// top-left 8x8 block is the product over the rows with h = 0 and whose bottom-right 8x8 block is the product over the
+// rows with h = 1 (the off-diagonal blocks mix the two and are not read).  So one step takes 8 rows and an
+// iteration 16 steps; row of (step s, k, h) = 8 s + 2 k + h, which with the 1056-B column stride
+// puts the 32 addresses of each half-wavefront read on 32 different bank pairs.  Column 7 is never staged: its lanes
+// re-read column 0 and feed row/column 7 of D, which nobody reads.
+// C/D map of the f64 instruction: register g of lane l is D[(l >> 4) + 4 g][l & 15].
+constexpr int kRowColStride = 132;   // doubles between two staged columns: 128 rows + 32 B (bank spread, keeps 16-B alignment)
+static_assert(7 * kRowColStride <= 64 * 18, "the staged rows share the W transpose scratch");
+typedef double mfma_f64x4 __attribute__((ext_vector_type(4)));
+
+// Launch bound: the OPENCV instantiation with W (the one that was measured) fits 4 wavefronts per SIMD (<= 128 VGPRs)
+// without scratch and is faster there; every other instantiation is left to the register allocator.
 template <int MODEL, bool WANT_W>
-__global__ __launch_bounds__(256) void k_ba_images(BaDev d, double* __restrict__ partial, double* __restrict__ W_o) {
-  __shared__ __attribute__((aligned(16))) double s_w[WANT_W ? 4 : 1][WANT_W ? 64 * 18 : 2];
+__global__ __launch_bounds__(256, (MODEL == 4 && WANT_W) ? 4 : 1) void k_ba_images(BaDev d, double* __restrict__ partial,
+                                                                       double* __restrict__ W_o) {
+  __shared__ __attribute__((aligned(16))) double s_w[4][64 * 18];   // per wavefront: staged rows, then the W transpose
+  __shared__ double s_a[4][2][27];
   const int im = (int)d.seg_img[blockIdx.x];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // uniform for the compiler
   const bool cpose = d.image_const_pose && d.image_const_pose[im];
-  double acc[27];
-#pragma unroll
-  for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+  mfma_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
   const unsigned tmask = d.image_const_tvec ? d.image_const_tvec[im] : 0u;
   const uint32_t e_beg = d.seg_begin[blockIdx.x];
   const uint32_t e_end = min(d.seg_begin[blockIdx.x + 1], d.img_obs_start[im + 1]);   // segments never span images
+  // operand address of this lane: column l & 7 (7 -> 0), row 2 k + h of the step's 8
+  const int op_k = lane >> 4, op_c = (lane & 7) == 7 ? 0 : (lane & 7);
+  const double* op_src = s_w[wave] + op_c * kRowColStride + 2 * op_k + ((lane >> 3) & 1);
   if (!cpose || WANT_W) {
-    // every lane runs every iteration (the W store below is a whole-wavefront operation)
+    // every lane runs every iteration (the row staging and the W store below are whole-wavefront operations)
     for (uint32_t e0 = e_beg; e0 < e_end; e0 += 256) {
       const uint32_t e = e0 + threadIdx.x;
       const bool active = e < e_end;
+      // observations left for this wavefront (uniform): 0 for the wavefronts past the end in the last iteration
+      const int cnt = (int)min(64u, e_end > e0 + wave * 64u ? e_end - (e0 + wave * 64u) : 0u);
       double w[18];
 #pragma unroll
       for (int k = 0; k < 18; ++k) w[k] = 0.0;   // constant pose / constant point: the coupling is zero
+      double J[12], r0 = 0.0, r1 = 0.0;          // 2 x 6 and the residual; zero rows for inactive lanes
+#pragma unroll
+      for (int k = 0; k < 12; ++k) J[k] = 0.0;
       if (active && !cpose) {
         const int pt = d.img_pt[e];
         const double X[3] = {d.points[3 * (size_t)pt], d.points[3 * (size_t)pt + 1], d.points[3 * (size_t)pt + 2]};
@@ -310,7 +342,6 @@ __global__ __launch_bounds__(256) void k_ba_images(BaDev d, double* __restrict__
         double Jq[8], Jt[6], JX[6], Jqt[6];
         reproj_jacobians(b, Jq, Jt, JX);
         quat_tangent(q, Jq, Jqt);
-        double J[12];  // 2 x 6
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -318,14 +349,8 @@ __global__ __launch_bounds__(256) void k_ba_images(BaDev d, double* __restrict__
             J[6 * r + k] = sr * Jqt[3 * r + k];
             J[6 * r + 3 + k] = ((tmask >> k) & 1u) ? 0.0 : sr * Jt[3 * r + k];
           }
-        const double r0 = sr * b.r[0], r1 = sr * b.r[1];
-        int idx = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-          for (int c = a; c < 6; ++c) acc[idx++] += J[a] * J[c] + J[6 + a] * J[6 + c];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * r0 + J[6 + a] * r1;
+        r0 = sr * b.r[0];
+        r1 = sr * b.r[1];
         if (WANT_W && !(d.point_const && d.point_const[pt])) {
 #pragma unroll
           for (int a = 0; a < 6; ++a)
@@ -333,11 +358,27 @@ __global__ __launch_bounds__(256) void k_ba_images(BaDev d, double* __restrict__
             for (int c = 0; c < 3; ++c) w[3 * a + c] = J[a] * (sr * JX[c]) + J[6 + a] * (sr * JX[3 + c]);
         }
       }
+      if (!cpose && cnt > 0) {   // uniform; a constant pose keeps its sums at exactly zero, an idle wavefront adds nothing
+        double2* row_dst = reinterpret_cast<double2*>(s_w[wave]) + lane;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) row_dst[c * (kRowColStride / 2)] = make_double2(J[c], J[6 + c]);
+        row_dst[6 * (kRowColStride / 2)] = make_double2(r0, r1);
+        // one wavefront: LDS operations complete in order; the fences keep the compiler from moving the reads up
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+          const double a = op_src[8 * s];
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, acc, 0, 0, 0);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();   // the scratch may be rewritten after this
+      }
       if (WANT_W) {
         // rows of this wavefront: observation indices in the caller's order
         const uint32_t o = active ? d.img_obs[e] : 0u;
         const uint32_t o_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)o);
-        const int cnt = (int)min(64u, e_end > e0 + wave * 64u ? e_end - (e0 + wave * 64u) : 0u);
         const bool contiguous = __all(!active || o == o_first + (uint32_t)lane);
         if (contiguous) {
           wave_store_rows<18>(W_o, o_first, cnt, w, s_w[wave]);
@@ -349,19 +390,24 @@ __global__ __launch_bounds__(256) void k_ba_images(BaDev d, double* __restrict__
       }
     }
   }
-  // fixed-order reduction: wave butterfly, then the 4 waves through LDS
-  __shared__ double s_a[4][27];
+  // the wavefront's two 7x7 products -> LDS in the packing of `partial` (upper triangle by rows, then the gradient):
+  // lane (g = l >> 4, h, c) holds rows a = g and a = 4 + g of product h, column c
+  {
+    const int g = lane >> 4, h = (lane >> 3) & 1, c = lane & 7;
 #pragma unroll
-  for (int k = 0; k < 27; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if (lane == 0) s_a[wave][k] = v;
+    for (int hi = 0; hi < 2; ++hi) {
+      const int a = g + 4 * hi;
+      const double v = h ? acc[2 + hi] : acc[hi];
+      if (a < 6 && c >= a && c < 7) s_a[wave][h][c == 6 ? 21 + a : a * 6 - a * (a - 1) / 2 + (c - a)] = v;
+    }
   }
   __syncthreads();
-  if (threadIdx.x < 27)
-    partial[27 * (size_t)blockIdx.x + threadIdx.x] =
-        (s_a[0][threadIdx.x] + s_a[1][threadIdx.x]) + (s_a[2][threadIdx.x] + s_a[3][threadIdx.x]);
+  // fixed order: the two products of a wavefront, then the wavefronts as (0 + 1) + (2 + 3)
+  if (threadIdx.x < 27) {
+    const int k = threadIdx.x;
+    partial[27 * (size_t)blockIdx.x + k] = ((s_a[0][0][k] + s_a[0][1][k]) + (s_a[1][0][k] + s_a[1][1][k])) +
+                                           ((s_a[2][0][k] + s_a[2][1][k]) + (s_a[3][0][k] + s_a[3][1][k]));
+  }
 }
 
 // segments of an image added in ascending order -> 6x6 block (symmetric) + gradient
