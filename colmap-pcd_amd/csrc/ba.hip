@@ -730,6 +730,48 @@ __global__ __launch_bounds__(256) void k_ba_cam_jac(BaDev d, double* __restrict_
   for (int k = 0; k < 2 * PCD_CAM_JAC_STRIDE; ++k) out[k] = J[k];
 }
 
+// Compact Ceres route (pcd_ba_evaluate_blocks_compact): one record {r0, r1, M row-major 2x3} per observation, M = dr/dP.
+// Every Jacobian block of the observation is M times a factor of the evaluation point alone (jac_t = M, jac_X = M D(q),
+// jac_q = M dPdq(q, X)), which the host rebuilds (shim/ceres_compact.h): 64 B cross PCIe instead of 176 B.  r and M are
+// the values eval_block gives k_ba_raw, bit for bit; D and dPdq are never read here, so the compiler drops them
+// (tests/test_ceres_compact_isa.py holds the register count against k_ba_raw's).  A constant-pose observation keeps
+// its true M: its jac_X needs it.
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_ba_raw_compact(BaDev d, double* __restrict__ rec_o) {
+  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 8];
+  const int wave = threadIdx.x >> 6;
+  const uint64_t o = blockIdx.x * (uint64_t)256 + threadIdx.x;
+  const uint64_t o_wave = blockIdx.x * (uint64_t)256 + wave * 64;
+  if (o_wave >= d.O) return;   // whole wavefront past the end
+  const int cnt = (int)min((uint64_t)64, d.O - o_wave);
+  double rec[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) rec[k] = 0.0;
+  if (o < d.O) {
+    const int im = d.obs_image[o], pt = d.obs_point[o];
+    const double X[3] = {d.points[3 * (size_t)pt], d.points[3 * (size_t)pt + 1], d.points[3 * (size_t)pt + 2]};
+    ReprojBlock b;
+    double q[4];
+    eval_block<MODEL>(d, im, X, d.obs_xy[2 * o], d.obs_xy[2 * o + 1], b, q);
+    rec[0] = b.r[0]; rec[1] = b.r[1];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rec[2 + k] = b.M[k];
+  }
+  wave_store_rows<8>(rec_o, o_wave, cnt, rec, s_rows[wave]);   // 4 KiB of consecutive addresses per wavefront
+}
+
+// Camera blocks for the compact route: [O][2][PCD_CAM_JAC_STRIDE] -> [O][2][cs], cs = the widest camera of the handle
+// (columns >= K of a narrower camera are the zeros k_ba_cam_jac wrote).  thread = output double: consecutive lanes
+// write consecutive addresses and read runs of cs doubles.
+__global__ __launch_bounds__(256) void k_ba_pack_cam_jac(const double* __restrict__ in, uint64_t nrows, int cs,
+                                                         double* __restrict__ out) {
+  const uint64_t u = blockIdx.x * (uint64_t)256 + threadIdx.x;
+  if (u >= nrows * (uint64_t)cs) return;
+  const uint64_t r = u / (uint64_t)cs;
+  const int k = (int)(u - r * (uint64_t)cs);
+  out[u] = in[r * PCD_CAM_JAC_STRIDE + k];
+}
+
 // Inputs of the post-BA filters, per observation:
 //   sq_err = CalculateSquaredReprojectionError (base/projection.cc:104-117; quaternion normalised first as
 //            base/pose.cc QuaternionRotatePoint does; DBL_MAX when the point is not in front of the camera)
@@ -1587,6 +1629,9 @@ struct pcd_ba {
   DevBuf<uint32_t> vobs;                 // [n_pose_rows] observation of every packed row
   DevBuf<double> p_jq, p_jt;             // packed pose Jacobians (only when some pose is constant)
   PinnedBuf<double> h_blocks;            // residuals | jac_q | jac_t | jac_X | jac_lidar | jac_cam
+  // pcd_ba_evaluate_blocks_compact: records and packed camera blocks (h_blocks is shared with the full route)
+  int cam_stride = 0;                    // largest pcd_camera_num_params over the cameras
+  DevBuf<double> o_rec, p_jc;
   // pcd_ba_filter_tracks: the track CSR (point -> its observations, ascending), scratch
   DevBuf<uint32_t> pt_obs_start, pt_obs_list;
   DevBuf<double> f_sq, f_depth, f_part, f_summary;
@@ -1869,6 +1914,7 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
   b->C = d->num_cameras; b->I = d->num_images; b->P = d->num_points; b->O = d->num_obs; b->L = d->num_lidar;
   b->loss_type = d->loss_type; b->loss_scale = d->loss_scale;
   b->cam_params_len = d->cam_params_len;
+  for (int c = 0; c < d->num_cameras; ++c) b->cam_stride = std::max(b->cam_stride, cam_num_params(d->cam_model[c]));
   b->uniform_model = d->cam_model[0];
   for (int c = 1; c < d->num_cameras; ++c)
     if (d->cam_model[c] != b->uniform_model) b->uniform_model = -1;
@@ -2196,6 +2242,63 @@ pcd_status pcd_ba_evaluate_blocks(pcd_ba* b, int want_jacobians, int want_jac_ca
   PCD_HIP_TRY(hipStreamSynchronize(s));
   out->pose_row = b->h_pose_row.data();
   out->num_pose_rows = V;
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_evaluate_blocks_compact(pcd_ba* b, int want_jacobians, int want_jac_cam, pcd_ba_blocks_compact* out) {
+  PCD_TRY(require_device(b ? b->device : 0));
+  PCD_REQUIRE(b && out, "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  std::memset(out, 0, sizeof *out);
+  const uint64_t O = b->O, L = b->L;
+  const int cs = b->cam_stride;
+  out->cam_stride = cs;
+  const size_t n_res = want_jacobians ? 0 : 2 * O, n_rec = want_jacobians ? 8 * O : 0, n_jl = want_jacobians ? 3 * L : 0,
+               n_jc = (want_jacobians && want_jac_cam) ? 2 * (size_t)cs * O : 0;
+  PCD_TRY(b->h_blocks.reserve(n_res + n_rec + L + n_jl + n_jc + 2));
+  PCD_TRY(b->o_res.reserve(std::max<size_t>(2 * O + L, 1)));   // the LiDAR residuals sit behind the 2 O reprojection slots
+  hipStream_t s = nullptr;
+  if (want_jacobians) {
+    PCD_TRY(b->o_rec.reserve(std::max<size_t>(n_rec, 1))); PCD_TRY(b->o_jl.reserve(std::max<size_t>(n_jl, 1)));
+    const BaDev d = b->dev();
+    if (O) {
+      ScopedKernelTimer t("ba_raw_compact", s);
+      PCD_BA_DISPATCH(b->uniform_model, hipLaunchKernelGGL((k_ba_raw_compact<M>), dim3(div_up(O, 256)), dim3(256), 0, s,
+                                                           d, b->o_rec.p));
+    }
+    if (L) {
+      ScopedKernelTimer t("ba_lidar_raw", s);
+      hipLaunchKernelGGL(k_ba_lidar_raw, dim3(div_up(L, 256)), dim3(256), 0, s, d, b->o_res.p, b->o_jl.p);
+    }
+    PCD_HIP_TRY(hipGetLastError());
+    if (n_jc) {
+      PCD_TRY(b->o_jc.reserve(2 * (size_t)PCD_CAM_JAC_STRIDE * O)); PCD_TRY(b->p_jc.reserve(n_jc));
+      pcd_ba_out dc{};
+      dc.jac_cam = b->o_jc.p;
+      PCD_TRY(pcd_ba_evaluate_device(b, &dc, s));   // k_ba_cam_jac alone
+      ScopedKernelTimer t("ba_pack_cam_jac", s);
+      hipLaunchKernelGGL(k_ba_pack_cam_jac, dim3(div_up(n_jc, 256)), dim3(256), 0, s, b->o_jc.p, 2 * O, cs, b->p_jc.p);
+      PCD_HIP_TRY(hipGetLastError());
+    }
+  } else {   // a trial step: the residual rows of k_ba_raw and k_ba_lidar_raw, nothing else
+    pcd_ba_out dr{};
+    dr.residuals = b->o_res.p;
+    PCD_TRY(pcd_ba_evaluate_device(b, &dr, s));
+  }
+  double* h = b->h_blocks.p;
+  auto down = [&](const double*& slot, const double* src, size_t n) -> hipError_t {
+    slot = n ? h : nullptr;
+    const hipError_t e = n ? hipMemcpyAsync(h, src, n * sizeof(double), hipMemcpyDeviceToHost, s) : hipSuccess;
+    h += n;
+    out->bytes_d2h += n * sizeof(double);
+    return e;
+  };
+  PCD_HIP_TRY(down(out->residuals, b->o_res.p, n_res));
+  PCD_HIP_TRY(down(out->records, b->o_rec.p, n_rec));
+  PCD_HIP_TRY(down(out->lidar_residuals, b->o_res.p + 2 * O, L));
+  PCD_HIP_TRY(down(out->jac_lidar, b->o_jl.p, n_jl));
+  PCD_HIP_TRY(down(out->jac_cam, b->p_jc.p, n_jc));
+  PCD_HIP_TRY(hipStreamSynchronize(s));
   return PCD_OK;
 }
 

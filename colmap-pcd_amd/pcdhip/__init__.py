@@ -90,6 +90,12 @@ class BABlocks(C.Structure):
                [("num_pose_rows", C.c_uint64), ("bytes_d2h", C.c_uint64)]
 
 
+class BABlocksCompact(C.Structure):
+    """pcd_ba_blocks_compact: pointers into the handle's pinned buffers"""
+    _fields_ = [(n, C.c_void_p) for n in ("residuals", "records", "lidar_residuals", "jac_lidar", "jac_cam")] + \
+               [("cam_stride", C.c_int32), ("bytes_d2h", C.c_uint64)]
+
+
 DAMP_MARQUARDT, DAMP_LEVENBERG = 0, 1
 _DAMPING = {"marquardt": DAMP_MARQUARDT, "levenberg": DAMP_LEVENBERG}
 
@@ -177,7 +183,7 @@ ABI_SYMBOLS = [
     "pcd_sift_matcher_set_descriptors", "pcd_sift_matcher_match",
     "pcd_sift_match_guided", "pcd_sift_match_guided_device", "pcd_sift_match_guided_batch",
     "pcd_sift_match_guided_batch_device", "pcd_sift_matcher_set_locations", "pcd_sift_matcher_match_guided",
-    "pcd_ba_evaluate_blocks", "pcd_ba_filter_tracks", "pcd_ba_filter_tracks_device",
+    "pcd_ba_evaluate_blocks", "pcd_ba_evaluate_blocks_compact", "pcd_ba_filter_tracks", "pcd_ba_filter_tracks_device",
     "pcd_cloud_create_sharded", "pcd_cloud_shards_destroy", "pcd_cloud_shards_count", "pcd_cloud_shards_size",
     "pcd_cloud_shards_get", "pcd_nn_query_sharded", "pcd_associate_sharded",
     "pcd_ba_set_parameters_device", "pcd_ba_schur_structure", "pcd_ba_schur_device", "pcd_ba_schur",
@@ -254,6 +260,7 @@ def lib():
         L.pcd_ba_device_parameters.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.pcd_ba_set_camera_parameters.argtypes = [C.c_void_p, C.c_void_p]
         L.pcd_ba_evaluate_blocks.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(BABlocks)]
+        L.pcd_ba_evaluate_blocks_compact.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(BABlocksCompact)]
     if hasattr(L, "pcd_ba_schur_device"):
         L.pcd_ba_set_parameters_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pcd_ba_schur_structure.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
@@ -897,6 +904,36 @@ class BA:
                    pose_row=take("pose_row", (self.O,), True, np.uint32),
                    num_pose_rows=V, bytes_d2h=int(bl.bytes_d2h))
         return out
+
+    def evaluate_blocks_compact(self, want_jacobians=True, want_jac_cam=False):
+        """the compact Ceres route (pcd_ba_evaluate_blocks_compact), copied out before returning: with Jacobians
+        records [O][8] = {r0, r1, M row-major 2x3} (M = dr/dP: jac_t = M, jac_X = M D(q), jac_q = M dPdq(q, X); not zero
+        for constant-pose observations), lidar_residuals [L], jac_lidar [L][3], jac_cam [O][2][cam_stride]; without them
+        residuals [2 O] and lidar_residuals.  Arrays that were not asked for are None (the C pointer is NULL); an array
+        that was asked for and has no rows is empty."""
+        bl = BABlocksCompact()
+        _check(lib().pcd_ba_evaluate_blocks_compact(self._h, int(bool(want_jacobians)), int(bool(want_jac_cam)),
+                                                    C.byref(bl)))
+        cs = int(bl.cam_stride)
+
+        def take(name, shape, wanted):
+            ptr = getattr(bl, name)
+            n = int(np.prod(shape))
+            if not wanted:
+                if ptr:
+                    raise PcdError(PCD_ERR_INVALID, f"pcd_ba_evaluate_blocks_compact: {name} not requested but not NULL")
+                return None
+            if n == 0:
+                return np.zeros(shape)
+            if not ptr:
+                raise PcdError(PCD_ERR_INVALID, f"pcd_ba_evaluate_blocks_compact: {name} is NULL")
+            return np.frombuffer((C.c_char * (n * 8)).from_address(ptr), np.float64).reshape(shape).copy()
+        wj = bool(want_jacobians)
+        return dict(residuals=take("residuals", (2 * self.O,), not wj), records=take("records", (self.O, 8), wj),
+                    lidar_residuals=take("lidar_residuals", (self.L,), True),
+                    jac_lidar=take("jac_lidar", (self.L, 3), wj),
+                    jac_cam=take("jac_cam", (self.O, 2, cs), wj and bool(want_jac_cam)),
+                    cam_stride=cs, bytes_d2h=int(bl.bytes_d2h))
 
     def evaluate(self, want=("cost", "residuals", "jac_q", "jac_t", "jac_X", "jac_lidar", "H_img", "g_img", "H_pt",
                              "g_pt")):

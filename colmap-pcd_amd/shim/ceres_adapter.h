@@ -20,6 +20,10 @@
 // Reconstruction, updated in place) holding the evaluation point; Evaluate may then run concurrently from Ceres'
 // threads -- it only reads the result buffers.  jacobians == NULL and jacobians[i] == NULL (constant block) are
 // honoured as Ceres requires.  COLMAP_PCD_HIP=0 (HipBackendEnabled) keeps the reference's own autodiff blocks.
+//
+// Compact mode (SetCompact(true) or COLMAP_PCD_HIP_COMPACT=1, off by default): PrepareForEvaluation calls
+// pcd_ba_evaluate_blocks_compact, 64 B per reprojection block over PCIe instead of 176 B, and Evaluate rebuilds
+// jac_q / jac_t / jac_X from the record and the evaluation point Ceres passes in `parameters` (ceres_compact.h).
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +38,7 @@
 #endif
 
 #include "ba_problem.h"
+#include "ceres_compact.h"
 
 namespace colmap_hip {
 
@@ -58,10 +63,22 @@ struct ShimParameterSource {
   double* Params(camera_t id) const { return rec->cameras.at(id).params.data(); }
 };
 
+// COLMAP_PCD_HIP_COMPACT=1 asks for the compact route; read once per callback object (construction / Finalize), never
+// on the evaluation path
+inline bool HipCompactRequested() {
+  const char* e = std::getenv("COLMAP_PCD_HIP_COMPACT");
+  return e && e[0] == '1' && e[1] == '\0';
+}
+
 struct HipBlockBuffers {   // results of the last PrepareForEvaluation, read by every block: views of the pinned host
   pcd_ba_blocks b{};       // buffers the pcd_ba handle owns (pcd_ba_evaluate_blocks)
   bool have_jacobians = false;
   size_t num_obs = 0;      // reprojection blocks of the problem: the lidar residuals follow their 2 * num_obs entries
+  // compact mode: `c` is filled instead of `b` (pcd_ba_evaluate_blocks_compact)
+  bool compact = false;
+  pcd_ba_blocks_compact c{};
+  const double* poses = nullptr;        // [I][7] the gathered evaluation point: the pose of a constant-pose block
+  const int32_t* obs_image = nullptr;   // [O]
 };
 
 // one reprojection residual block (variable or constant pose), optim/bundle_adjustment.cc:858-893, :967-983
@@ -74,7 +91,8 @@ class HipReprojectionBlock : public ceres::CostFunction {
     mutable_parameter_block_sizes()->push_back(3);
     mutable_parameter_block_sizes()->push_back(K_);
   }
-  bool Evaluate(double const* const*, double* residuals, double** jacobians) const override {
+  bool Evaluate(double const* const* parameters, double* residuals, double** jacobians) const override {
+    if (buf_->compact) return EvaluateCompact(parameters, residuals, jacobians);
     const pcd_ba_blocks& r = buf_->b;
     residuals[0] = r.residuals[2 * o_];
     residuals[1] = r.residuals[2 * o_ + 1];
@@ -99,6 +117,37 @@ class HipReprojectionBlock : public ceres::CostFunction {
   }
 
  private:
+  // parameters: (qvec, tvec, xyz, camera) of a variable-pose block, (xyz, camera) of a constant-pose one
+  bool EvaluateCompact(double const* const* parameters, double* residuals, double** jacobians) const {
+    const pcd_ba_blocks_compact& c = buf_->c;
+    if (!c.records) {                            // the last PrepareForEvaluation was a residual-only pass
+      residuals[0] = c.residuals[2 * o_];
+      residuals[1] = c.residuals[2 * o_ + 1];
+      return jacobians == nullptr;
+    }
+    const double* rec = c.records + 8 * o_;
+    residuals[0] = rec[0];
+    residuals[1] = rec[1];
+    if (!jacobians) return true;
+    if (!buf_->have_jacobians) return false;
+    int b = 0;
+    if (!cpose_) {
+      ExpandReprojectionBlock(parameters[0], parameters[2], rec, jacobians[0], jacobians[1], jacobians[2]);
+      b = 3;
+    } else {
+      if (jacobians[0])
+        ExpandReprojectionBlock(buf_->poses + 7 * (size_t)buf_->obs_image[o_], parameters[0], rec, nullptr, nullptr,
+                                jacobians[0]);
+      b = 1;
+    }
+    if (jacobians[b]) {
+      if (!c.jac_cam) return false;
+      for (int k = 0; k < 2; ++k)   // device rows have cam_stride columns, Ceres wants 2 x K row-major
+        std::memcpy(jacobians[b] + k * K_, c.jac_cam + (2 * o_ + k) * (size_t)c.cam_stride, K_ * sizeof(double));
+    }
+    return true;
+  }
+
   const HipBlockBuffers* buf_;
   size_t o_;
   bool cpose_;
@@ -113,10 +162,10 @@ class HipLidarBlock : public ceres::CostFunction {
     mutable_parameter_block_sizes()->push_back(3);
   }
   bool Evaluate(double const* const*, double* residuals, double** jacobians) const override {
-    residuals[0] = buf_->b.residuals[2 * buf_->num_obs + l_];
+    residuals[0] = buf_->compact ? buf_->c.lidar_residuals[l_] : buf_->b.residuals[2 * buf_->num_obs + l_];
     if (jacobians && jacobians[0]) {
       if (!buf_->have_jacobians) return false;
-      std::memcpy(jacobians[0], buf_->b.jac_lidar + 3 * l_, 3 * sizeof(double));
+      std::memcpy(jacobians[0], (buf_->compact ? buf_->c.jac_lidar : buf_->b.jac_lidar) + 3 * l_, 3 * sizeof(double));
     }
     return true;
   }
@@ -133,7 +182,11 @@ class HipEvaluation : public ceres::EvaluationCallback {
   HipEvaluation(BundleAdjusterHip* ba, const Source& src) : ba_(ba), src_(src) {
     for (uint8_t v : ba_->cam_refine_) cameras_variable_ |= v != 0;
     buf_.num_obs = ba_->obs_image_.size();
+    buf_.compact = HipCompactRequested();
   }
+  // before the first PrepareForEvaluation (the views of the other mode are dropped)
+  void SetCompact(bool on) { buf_.compact = on; buf_.b = pcd_ba_blocks{}; buf_.c = pcd_ba_blocks_compact{}; buf_.have_jacobians = false; }
+  bool compact() const { return buf_.compact; }
 
   void PrepareForEvaluation(bool evaluate_jacobians, bool new_evaluation_point) override {
     ok_ = true;
@@ -155,8 +208,15 @@ class HipEvaluation : public ceres::EvaluationCallback {
     }
     // ONE batch for every residual block; results in pinned memory of the handle (constant cameras: Ceres passes
     // NULL for the camera block, so its Jacobian is not even computed)
-    ok_ &= pcd_ba_evaluate_blocks(ba_->handle(), evaluate_jacobians ? 1 : 0, cameras_variable_ ? 1 : 0, &buf_.b) == PCD_OK;
-    bytes_d2h_ += buf_.b.bytes_d2h;
+    if (buf_.compact) {
+      buf_.poses = ba_->poses_.data();
+      buf_.obs_image = ba_->obs_image_.data();
+      ok_ &= pcd_ba_evaluate_blocks_compact(ba_->handle(), evaluate_jacobians ? 1 : 0, cameras_variable_ ? 1 : 0, &buf_.c) == PCD_OK;
+      bytes_d2h_ += buf_.c.bytes_d2h;
+    } else {
+      ok_ &= pcd_ba_evaluate_blocks(ba_->handle(), evaluate_jacobians ? 1 : 0, cameras_variable_ ? 1 : 0, &buf_.b) == PCD_OK;
+      bytes_d2h_ += buf_.b.bytes_d2h;
+    }
     buf_.have_jacobians = evaluate_jacobians && ok_;
     ++num_evaluations_;
   }
@@ -227,6 +287,9 @@ class HipBlockRecorder : public ceres::EvaluationCallback {
     return new HipLidarBlock(&buf_, lidar_point_.size() - 1);
   }
   size_t NumResiduals() const { return 2 * obs_image_.size() + lidar_point_.size(); }
+  // before Finalize; without it Finalize takes the mode from COLMAP_PCD_HIP_COMPACT
+  void SetCompact(bool on) { compact_ = on ? 1 : 0; }
+  bool compact() const { return buf_.compact; }
 
   // cameras_variable: some camera parameter block is optimised (ParameterizeCameras, :1047-1100): its Jacobians are
   // computed and copied only then.  Returns false when there is nothing to evaluate or the device refuses.
@@ -234,6 +297,7 @@ class HipBlockRecorder : public ceres::EvaluationCallback {
     if (NumResiduals() == 0) return false;
     cameras_variable_ = cameras_variable;
     buf_.num_obs = obs_image_.size();
+    buf_.compact = compact_ < 0 ? HipCompactRequested() : compact_ == 1;
     poses_.resize(7 * qvec_ptr_.size());
     points_.resize(3 * xyz_ptr_.size());
     cam_params_.resize(cam_len_);
@@ -265,13 +329,20 @@ class HipBlockRecorder : public ceres::EvaluationCallback {
       ok_ &= pcd_ba_set_parameters(ba_, poses_.data(), points_.data()) == PCD_OK;
       if (cameras_variable_) ok_ &= pcd_ba_set_camera_parameters(ba_, cam_params_.data()) == PCD_OK;
     }
-    ok_ &= pcd_ba_evaluate_blocks(ba_, evaluate_jacobians ? 1 : 0, cameras_variable_ ? 1 : 0, &buf_.b) == PCD_OK;
+    if (buf_.compact) {
+      buf_.poses = poses_.data();
+      buf_.obs_image = obs_image_.data();
+      ok_ &= pcd_ba_evaluate_blocks_compact(ba_, evaluate_jacobians ? 1 : 0, cameras_variable_ ? 1 : 0, &buf_.c) == PCD_OK;
+    } else {
+      ok_ &= pcd_ba_evaluate_blocks(ba_, evaluate_jacobians ? 1 : 0, cameras_variable_ ? 1 : 0, &buf_.b) == PCD_OK;
+    }
     buf_.have_jacobians = evaluate_jacobians && ok_;
     ++num_evaluations_;
   }
   bool ok() const { return ok_; }
   size_t num_evaluations() const { return num_evaluations_; }
   pcd_ba* handle() const { return ba_; }
+  const HipBlockBuffers& buffers() const { return buf_; }
 
  private:
   static int Index(std::unordered_map<const double*, int>* index, double* ptr, std::vector<double*>* ptrs) {
@@ -302,6 +373,7 @@ class HipBlockRecorder : public ceres::EvaluationCallback {
   HipBlockBuffers buf_;
   pcd_ba* ba_ = nullptr;
   bool cameras_variable_ = false, ok_ = true;
+  int compact_ = -1;   // -1: not set, Finalize asks the environment
 };
 
 }  // namespace colmap_hip

@@ -6,7 +6,10 @@
 //   optim/bundle_adjustment.cc:537 -> Ceres -> the blocks added at :858-893, :967-983, :1031-1037), single-threaded and
 //   on all host threads.
 // Next to it: the raw pinned device->host rate for the same number of bytes (the PCIe ceiling of this route).
-// Prints one JSON object.  Usage: ceres_route_bench <images> <points> [const_pose_fraction] [threads]
+// Prints one JSON object.  Usage: ceres_route_bench <images> <points> [const_pose_fraction] [threads] [compact]
+// compact = 1: the compact route (pcd_ba_evaluate_blocks_compact, 64 B per reprojection block; every Evaluate rebuilds
+// its Jacobian blocks from the record and the parameters, which the sweep then passes as Ceres would); the object gains
+// the keys "compact" and "bytes_per_observation_compact".  compact = 0 (default): the output is unchanged.
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
@@ -45,6 +48,7 @@ int main(int argc, char** argv) {
   const double cfrac = argc > 3 ? std::atof(argv[3]) : 0.0;
   const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
   const unsigned T = argc > 4 ? (unsigned)std::atoi(argv[4]) : std::min(hw, 16u);
+  const bool compact = argc > 5 && std::atoi(argv[5]) == 1;
   if (pcd_device_count() < 1) { std::printf("{\"error\": \"no gfx950 device\"}\n"); return 1; }
 
   // ---- synthetic scene (shape of SURVEY 8d: cameras along x looking down +z, OPENCV intrinsics, tracks of mean
@@ -107,6 +111,7 @@ int main(int argc, char** argv) {
   std::vector<double> s_poses = ba.poses_, s_points = ba.points_, s_cams = ba.cam_params_;
   FlatSource src{s_poses.data(), s_points.data(), s_cams.data()};
   HipEvaluation<FlatSource> cb(&ba, src);
+  cb.SetCompact(compact);
   std::vector<std::unique_ptr<ceres::CostFunction>> blocks;
   blocks.reserve(O + L);
   for (size_t o = 0; o < O; ++o) blocks.emplace_back(cb.ReprojectionBlock(o));
@@ -121,6 +126,7 @@ int main(int argc, char** argv) {
         // per-thread destination (Ceres copies each block into its own Jacobian storage)
         double r[2], jq[8], jt[6], jx[6];
         double* jp[4];
+        const double* pp[4] = {nullptr, nullptr, nullptr, nullptr};   // compact: (qvec, tvec, xyz, camera) as Ceres passes them
         double acc = 0;
         const size_t n = blocks.size(), b0 = n * t / threads, b1 = n * (t + 1) / threads;
         for (size_t b = b0; b < b1; ++b) {
@@ -128,7 +134,13 @@ int main(int argc, char** argv) {
           if (sz.size() == 4) { jp[0] = jq; jp[1] = jt; jp[2] = jx; jp[3] = nullptr; }        // q, t, X, camera (constant)
           else if (sz.size() == 2) { jp[0] = jx; jp[1] = nullptr; }                           // X, camera
           else { jp[0] = jx; }                                                                 // lidar: X
-          blocks[b]->Evaluate(nullptr, r, with_jac ? jp : nullptr);
+          if (compact && b < O) {
+            const int im = ba.obs_image_[b];
+            const double* X = src.XYZ((point3D_t)ba.obs_point_[b]);
+            if (sz.size() == 4) { pp[0] = src.Qvec(im); pp[1] = src.Tvec(im); pp[2] = X; pp[3] = src.cams; }
+            else { pp[0] = X; pp[1] = src.cams; }
+          }
+          blocks[b]->Evaluate(compact ? pp : nullptr, r, with_jac ? jp : nullptr);
           acc += r[0] + (with_jac ? jx[0] : 0.0);
         }
         sums[t] = acc;
@@ -169,6 +181,8 @@ int main(int argc, char** argv) {
     if (d) (void)hipFree(d);
     if (h) (void)hipHostFree(h);
   }
+  uint64_t pose_rows = cb.buffers().b.num_pose_rows;   // the compact route does not pack rows: count them here
+  if (compact) { pose_rows = 0; for (size_t o = 0; o < O; ++o) pose_rows += !ba.image_const_pose_[ba.obs_image_[o]]; }
   const uint64_t h2d = (ba.poses_.size() + ba.points_.size()) * sizeof(double);
   std::printf("{\"images\": %d, \"points\": %d, \"observations\": %zu, \"lidar_terms\": %zu, \"const_pose_fraction\": %.2f, "
               "\"pose_rows\": %llu, \"create_ms\": %.2f, "
@@ -176,10 +190,12 @@ int main(int argc, char** argv) {
               "\"d2h_GBps_in_prepare\": %.1f, \"pinned_d2h_same_bytes_ms\": %.3f, \"pinned_d2h_GBps\": %.1f, "
               "\"prepare_over_pcie_ceiling\": %.2f, "
               "\"block_sweep_jacobians_ms_1_thread\": %.2f, \"block_sweep_jacobians_ms\": %.2f, \"block_sweep_residuals_ms\": %.2f, "
-              "\"threads\": %u, \"ceres_route_e2e_ms\": %.2f, \"ceres_route_residual_pass_ms\": %.2f, \"checksum\": %.6g}\n",
-              I, P, O, L, cfrac, (unsigned long long)cb.buffers().b.num_pose_rows, create_ms, prep_j, prep_r,
+              "\"threads\": %u, \"ceres_route_e2e_ms\": %.2f, \"ceres_route_residual_pass_ms\": %.2f, \"checksum\": %.6g",
+              I, P, O, L, cfrac, (unsigned long long)pose_rows, create_ms, prep_j, prep_r,
               (unsigned long long)bytes_j, (unsigned long long)h2d, bytes_j / prep_j * 1e-6, pcie_ms,
               pcie_ms > 0 ? bytes_j / pcie_ms * 1e-6 : 0.0, pcie_ms > 0 ? prep_j / pcie_ms : 0.0, sw1, swT, swr, T,
               prep_j + swT, prep_r + swr, chk);
+  if (compact) std::printf(", \"compact\": 1, \"bytes_per_observation_compact\": %.1f", O ? (double)(bytes_j - 32 * L) / (double)O : 0.0);
+  std::printf("}\n");
   return 0;
 }

@@ -493,6 +493,32 @@ typedef struct {
   uint64_t bytes_d2h;        /* bytes that crossed PCIe device -> host in this call             */
 } pcd_ba_blocks;
 pcd_status pcd_ba_evaluate_blocks(pcd_ba* ba, int want_jacobians, int want_jac_cam, pcd_ba_blocks* out);
+/* The same route at 64 B instead of 176 B per reprojection block over PCIe.  With want_jacobians the reprojection
+ * blocks arrive as one record of 8 doubles per observation, in the caller's observation order:
+ *   records[o] = {r0, r1, M00, M01, M02, M10, M11, M12},   M = d r / d P (2x3 row-major), P = R(q) X + t.
+ * Every Jacobian block is M times a factor of the evaluation point alone, which the caller already holds:
+ *   jac_t = M     jac_X = M * D(q)     jac_q = M * dPdq(q, X)
+ * with D = dP/dX (3x3) and dPdq = dP/dq (3x4) of Ceres' UnitQuaternionRotatePoint polynomial, q taken as it is (not
+ * normalised).  shim/ceres_compact.h rebuilds the three blocks in the operation order of the device code, so they are
+ * the rows pcd_ba_evaluate_blocks returns.  M of a CONSTANT-POSE block is not zero: the block has no pose Jacobians,
+ * but its jac_X is M * D(q of the constant pose).  There is no pose_row: records are not packed.
+ * jac_cam rows have cam_stride columns, cam_stride = the largest pcd_camera_num_params over the handle's cameras;
+ * columns >= K of a narrower camera are zero.  Otherwise the contract of pcd_ba_evaluate_blocks: one device pass, one
+ * asynchronous copy per array into the handle's pinned buffer (shared with pcd_ba_evaluate_blocks), one stream
+ * synchronisation; pointers valid until the next pcd_ba_evaluate_blocks* / pcd_ba_destroy on the handle;
+ * PCD_ERR_NO_DEVICE without a gfx950.  bytes_d2h = 8 (2 O + L) without Jacobians, else
+ * 8 (8 O + 4 L) + (want_jac_cam ? 16 cam_stride O : 0). */
+typedef struct {
+  const double* residuals;        /* [2*O]  only when want_jacobians == 0, else NULL            */
+  const double* records;          /* [O][8] {r0,r1,M row-major 2x3}, only when want_jacobians   */
+  const double* lidar_residuals;  /* [L]                                                        */
+  const double* jac_lidar;        /* [L][3] or NULL                                             */
+  const double* jac_cam;          /* [O][2][cam_stride] or NULL                                 */
+  int32_t cam_stride;
+  uint64_t bytes_d2h;
+} pcd_ba_blocks_compact;
+pcd_status pcd_ba_evaluate_blocks_compact(pcd_ba* ba, int want_jacobians, int want_jac_cam,
+                                          pcd_ba_blocks_compact* out);
 pcd_status pcd_ba_evaluate_device(pcd_ba* ba, const pcd_ba_out* d_out, void* stream);  /* device outputs */
 /* Inputs of the post-BA filters, per observation (either pointer may be NULL):
  *   sq_err[o] = CalculateSquaredReprojectionError (base/projection.cc:104-117), DBL_MAX when the point is not
