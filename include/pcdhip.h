@@ -306,7 +306,9 @@ void pcd_proj_default_options(pcd_proj_options* o);
 pcd_status pcd_proj_create(pcd_cloud* cloud, const pcd_proj_options* options, pcd_proj** out);
 void pcd_proj_destroy(pcd_proj* p);
 uint64_t pcd_proj_num_submaps(const pcd_proj* p);
-uint64_t pcd_proj_last_pairs(const pcd_proj* p);   /* (image, submap) pairs the last call projected */
+/* (image, submap) pairs the last call projected, summed over its chunks.  A chunk in which no image has a feature
+ * is not culled at all (nobody would read the result) and adds 0, so a featureless batch reports 0. */
+uint64_t pcd_proj_last_pairs(const pcd_proj* p);
 /* The splat half-width beyond min_proj_dist is a_x*depth+b_x (and y): four function-local `static`s in the
  * reference (.cc:391-397), initialised from the FIRST camera the process projects with and never again.
  * Here they latch per projector on the first image of the first call; set=1 overrides them (coeffs4 = a_x, b_x,

@@ -114,6 +114,17 @@ static void distort_opencv(const double* prm, double u, double v, double* ou, do
   *ov = dv * fy + cy;
 }
 
+/* pcd_projection.cc:35-36, 67-68: uv = (xy * scale).cast<int>(), then the bounds check.  The cast of a double
+ * outside int's range (or NaN) is undefined in the reference; the documented choice here, as for non-finite cloud
+ * rows, is that such a feature is not a feature pixel. */
+static int feature_pixel(const double* xy, double scale, int img_w, int img_h, int* u, int* v) {
+  const double fu = xy[0] * scale, fv = xy[1] * scale;
+  if (!(fabs(fu) < 2e9) || !(fabs(fv) < 2e9)) return 0;
+  *u = (int)fu;
+  *v = (int)fv;
+  return *u >= 0 && *u < img_w && *v >= 0 && *v < img_h;
+}
+
 /* The four function-local statics of pcd_projection.cc:391-397, as computed on
  * the first camera the process sees (b_y really does use the unscaled
  * min_proj_scale). */
@@ -172,8 +183,8 @@ int64_t oracle_proj_images(const float* xyz, uint64_t n, const proj_options* o, 
     memset(zidx, 0xFF, npx * sizeof(uint32_t));
     for (uint64_t f = 0; f < nf; ++f) {
       const double* xy = &feat_xy[2 * (im->feat_begin + f)];
-      const int u = (int)(xy[0] * scale), v = (int)(xy[1] * scale);
-      if (u < 0 || u >= img_w || v < 0 || v >= img_h) continue;
+      int u, v;
+      if (!feature_pixel(xy, scale, img_w, img_h, &u, &v)) continue;
       is_feat[(size_t)v * img_w + u] = 1;
     }
 
@@ -260,8 +271,8 @@ int64_t oracle_proj_images(const float* xyz, uint64_t n, const proj_options* o, 
     for (uint64_t f = 0; f < nf; ++f) {
       const uint64_t g = im->feat_begin + f;
       const double* xy = &feat_xy[2 * g];
-      const int u = (int)(xy[0] * scale), v = (int)(xy[1] * scale);
-      if (u < 0 || u >= img_w || v < 0 || v >= img_h) continue;
+      int u, v;
+      if (!feature_pixel(xy, scale, img_w, img_h, &u, &v)) continue;
       const size_t px = (size_t)v * img_w + u;
       if (zidx[px] != 0xFFFFFFFFu) { found[g] = 1; index[g] = zidx[px]; dist_out[g] = zdist[px]; }
     }

@@ -478,8 +478,10 @@ class ProjImage(C.Structure):
 
 
 def proj_options(depth_image_scale=0.2, max_proj_scale=10, min_proj_scale=2, min_proj_dist=2.0, submap=1.0,
-                 choose_meter=40.0, min_lidar_proj_dist=0.5):
-    return ProjOptions(depth_image_scale, max_proj_scale, min_proj_scale, min_proj_dist, submap, submap, submap,
+                 choose_meter=40.0, min_lidar_proj_dist=0.5, submap_length=None, submap_width=None, submap_height=None):
+    """submap_length / width / height (x / z / y, pcd_projection.h:71-78) default to `submap`."""
+    length, width, height = [submap if v is None else v for v in (submap_length, submap_width, submap_height)]
+    return ProjOptions(depth_image_scale, max_proj_scale, min_proj_scale, min_proj_dist, length, width, height,
                        choose_meter, min_lidar_proj_dist)
 
 

@@ -1,6 +1,8 @@
 """(test infrastructure, run by hand; not collected by pytest)  Randomised parity sweep of the depth-projection association
 (lidar/pcd_projection.cc) against the oracle: python tests/fuzz_proj.py [seconds] [seed].  Random clouds, image counts,
-feature counts, image sizes, OPENCV parameters, scale / splat / submap options."""
+feature counts (up to 300 000 for a single image: the grid-stride step of the feature kernels), image sizes, OPENCV
+parameters, scale / splat options (max_proj_scale up to 40: splats three and four bitmap words wide) and an
+independent submap size per axis."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "colmap-pcd_amd")); sys.path.insert(0, ROOT)
@@ -22,10 +24,13 @@ while time.time() < t_end:
     prm = [f, f * rng.uniform(0.97, 1.03), w / 2 + rng.normal(0, 20), h / 2 + rng.normal(0, 20),
            rng.normal(0, 0.05), rng.normal(0, 0.02), rng.normal(0, 3e-4), rng.normal(0, 3e-4)]
     ni, nf = int(rng.choice([1, 3, 9])), int(rng.choice([1, 200, 3000]))
+    if ni == 1 and rng.random() < 0.25:
+        nf = int(rng.integers(3001, 300_001))
     images, feat = synth.proj_scene(ni, nf, seed=int(rng.integers(1 << 30)), width=w, height=h, params=prm)
-    okw = dict(depth_image_scale=float(rng.choice([0.1, 0.2, 0.25, 0.5])), max_proj_scale=int(rng.choice([3, 6, 10])),
-               min_proj_scale=int(rng.choice([1, 2])), min_proj_dist=float(rng.choice([1.0, 3.0, 8.0])),
-               submap=float(rng.choice([1.0, 2.0, 5.0])), choose_meter=float(rng.choice([10.0, 25.0, 60.0])),
+    okw = dict(depth_image_scale=float(rng.choice([0.1, 0.2, 0.25, 0.5])), max_proj_scale=int(rng.choice([0, 3, 10, 40])),
+               min_proj_scale=int(rng.choice([0, 1, 2])), min_proj_dist=float(rng.choice([1.0, 3.0, 8.0])),
+               submap_length=float(rng.choice([0.7, 1.0, 2.0, 5.0])), submap_width=float(rng.choice([0.7, 1.0, 2.0, 5.0])),
+               submap_height=float(rng.choice([0.7, 1.0, 2.0, 5.0])), choose_meter=float(rng.choice([10.0, 25.0, 60.0])),
                min_lidar_proj_dist=float(rng.choice([0.0, 0.5, 2.0])))
     oo = oracle.proj_options(**okw)
     coeffs = oracle.proj_scale_coeffs(oo, images[0]["params"][0], images[0]["params"][1])
