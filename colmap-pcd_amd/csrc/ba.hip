@@ -64,8 +64,58 @@ struct BaDev {
   const double* img_xy;           // [O][2]
   int I, P, nslices; uint64_t O, L;
   int loss_type; double loss_scale;
+  int shared_cam;                 // >= 0: every image maps to this camera (one physical camera, the usual dataset); -1: per image
 };
 
+// The camera of an evaluation: model id and parameters.
+// SHARED: the handle has one camera for every image (BaDev::shared_cam >= 0).  The camera index is then a kernel
+// argument: cam_off, cam_model and the parameters are read ONCE per thread, when the object is made at the top of the
+// kernel, through wave-uniform addresses (scalar loads) -- not per observation through the three-deep per-lane gather
+// chain image -> camera -> offset -> parameters behind the load of `im`.  The parameters are still read from cam_params
+// at every launch (pcd_ba_set_camera_parameters and the device LM update them in place), and the arithmetic is the same
+// expressions on the same values: the results are bit-identical to the per-image path.
+template <int MODEL, bool SHARED>
+struct BaCam {
+  static constexpr int K = cam_num_params(MODEL >= 0 ? MODEL : 0);
+  int model = MODEL;
+  const double* p = nullptr;
+  double v[K];   // SHARED with a compiled-in model: the parameters themselves
+  __device__ __forceinline__ void resolve(const BaDev& d, int cm) {
+    if (MODEL < 0) model = d.cam_model[cm];
+    p = d.cam_params + d.cam_off[cm];
+  }
+  __device__ __forceinline__ explicit BaCam(const BaDev& d) {
+    if (!SHARED) return;
+    resolve(d, d.shared_cam);
+    if (MODEL >= 0) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) v[k] = p[k];   // uniform: held in SGPRs (copied to VGPRs they measured slower)
+    }
+  }
+  // what reproj_eval / world_to_image_d2 read the parameters from
+  __device__ __forceinline__ const double* params() const { return (SHARED && MODEL >= 0) ? v : p; }
+  // per-image path: the camera of image im
+  __device__ __forceinline__ void of_image(const BaDev& d, int im) {
+    if (!SHARED) resolve(d, d.image_cam[im]);
+  }
+};
+
+__device__ __forceinline__ void load_pose(const BaDev& d, int im, double pose[7]) {
+#pragma unroll
+  for (int k = 0; k < 7; ++k) pose[k] = d.poses[7 * (size_t)im + k];
+}
+// pose = the 7 doubles of the image, cam = its camera
+template <int MODEL, bool SHARED>
+__device__ __forceinline__ void eval_block_at(const BaCam<MODEL, SHARED>& cam, const double pose[7], const double X[3],
+                                              double ox, double oy, ReprojBlock& b, double q[4]) {
+  double t[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = pose[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) t[k] = pose[4 + k];
+  reproj_eval(cam.model, cam.params(), q, t, X, ox, oy, b);
+}
+// the per-image path in one call (the image and camera passes, whose image is workgroup-uniform anyway)
 template <int MODEL>
 __device__ __forceinline__ void eval_block(const BaDev& d, int im, const double X[3], double ox, double oy,
                                            ReprojBlock& b, double q[4]) {
@@ -78,6 +128,13 @@ __device__ __forceinline__ void eval_block(const BaDev& d, int im, const double 
   const int cm = d.image_cam[im];
   const int model = MODEL >= 0 ? MODEL : d.cam_model[cm];
   reproj_eval(model, d.cam_params + d.cam_off[cm], q, t, X, ox, oy, b);
+}
+// a double every lane of the wavefront holds the same value of, as the compiler sees it
+__device__ __forceinline__ double wave_uniform(double v) {
+  const long long u = __double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)u >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
 // Coalesced store of one row of N doubles per lane, rows of consecutive lanes adjacent in memory
@@ -114,7 +171,7 @@ __device__ __forceinline__ void wave_store_rows(double* __restrict__ out, uint64
 // the wavefronts in flight took it from 0.18 to ~0.1 ms on the bench scene.  The halves live in different wavefronts
 // of the workgroup (threads 0-63 / 64-127 = halves 0 / 1 of slice 2b, 128-255 of slice 2b + 1); half 1 hands its sums
 // over through LDS and half 0 adds them in a fixed order and also takes the track's LiDAR terms.
-template <int MODEL, bool BLOCKS>
+template <int MODEL, bool BLOCKS, bool SHARED>
 __global__ __launch_bounds__(256) void k_ba_points(BaDev d, double* __restrict__ Hpt, double* __restrict__ gpt,
                                                    double* __restrict__ cost_partial) {
   __shared__ double s_half[2][64][9];
@@ -126,6 +183,7 @@ __global__ __launch_bounds__(256) void k_ba_points(BaDev d, double* __restrict__
   int p = -1;
   bool cpt = true;
   double X[3] = {0, 0, 0};
+  BaCam<MODEL, SHARED> cam(d);
   if (slice < d.nslices) {
     p = d.pt_order[t];
     const uint32_t s0 = d.slice_start[slice], s1 = d.slice_start[slice + 1];
@@ -137,8 +195,10 @@ __global__ __launch_bounds__(256) void k_ba_points(BaDev d, double* __restrict__
       const int im = d.sell_img[s];
       if (im < 0) continue;  // padding of a shorter track
       ReprojBlock b;
-      double q[4];
-      eval_block<MODEL>(d, im, X, d.sell_xy[2 * (size_t)s], d.sell_xy[2 * (size_t)s + 1], b, q);
+      double q[4], pose[7];
+      cam.of_image(d, im);
+      load_pose(d, im, pose);
+      eval_block_at(cam, pose, X, d.sell_xy[2 * (size_t)s], d.sell_xy[2 * (size_t)s + 1], b, q);
       double rho0, rho1;
       loss_eval(d.loss_type, d.loss_scale, b.r[0] * b.r[0] + b.r[1] * b.r[1], rho0, rho1);
       cost += 0.5 * rho0;
@@ -213,19 +273,33 @@ __global__ __launch_bounds__(256) void k_ba_points(BaDev d, double* __restrict__
 // observations and LiDAR terms in their given order, one thread each -- 5.9 M independent threads instead of
 // 1 M tracks with serial inner loops.  Same fixed-order two-stage sum (bitwise reproducible run to run; the
 // summation order, hence the last bits, differ from the cost the Jacobian pass reports).
-template <int MODEL>
+template <int MODEL, bool SHARED>
 __global__ __launch_bounds__(256) void k_ba_cost(BaDev d, double* __restrict__ cost_partial) {
   // one residual block per thread (a fixed grid of 2048 workgroups looping over them measured 0.109 ms against
   // 0.096 ms: fewer wavefronts in flight for a latency-bound gather); the loop form is kept for grids that are
   // capped.  The assignment of blocks to threads and the order of the sums depend on the problem size only.
   double cost = 0.0;
+  BaCam<MODEL, SHARED> cam(d);
   for (uint64_t i = blockIdx.x * (uint64_t)256 + threadIdx.x; i < d.O + d.L; i += (uint64_t)gridDim.x * 256) {
     if (i < d.O) {
       const int im = d.obs_image[i], pt = d.obs_point[i];
       const double X[3] = {d.points[3 * (size_t)pt], d.points[3 * (size_t)pt + 1], d.points[3 * (size_t)pt + 2]};
       ReprojBlock b;
       double q[4];
-      eval_block<MODEL>(d, im, X, d.obs_xy[2 * i], d.obs_xy[2 * i + 1], b, q);
+      // In AddImageToProblem order an image owns thousands of consecutive observations, so nearly every wavefront sees
+      // one image: its pose is then read once through a wave-uniform address (scalar loads) instead of four per-lane
+      // gathers.  Same values into the same arithmetic.  wave_uniform keeps the two branches from being merged back into
+      // one per-lane gather on a selected index.
+      double pose[7];
+      const int im0 = __builtin_amdgcn_readfirstlane(im);
+      if (__all(im == im0)) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) pose[k] = wave_uniform(d.poses[7 * (size_t)im0 + k]);
+      } else {
+        load_pose(d, im, pose);
+      }
+      cam.of_image(d, im);
+      eval_block_at(cam, pose, X, d.obs_xy[2 * i], d.obs_xy[2 * i + 1], b, q);
       double rho0, rho1;
       loss_eval(d.loss_type, d.loss_scale, b.r[0] * b.r[0] + b.r[1] * b.r[1], rho0, rho1);
       cost += 0.5 * rho0;
@@ -252,15 +326,25 @@ __global__ __launch_bounds__(256) void k_ba_cost(BaDev d, double* __restrict__ c
 }
 constexpr unsigned kCostBlocks = 1u << 20;   // cap of the cost pass's grid (256 M residual blocks in one sweep)
 
-__global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__ partial, int n, double* __restrict__ out) {
-  __shared__ double s_c[256];
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;   // four loads in flight per thread; the order is fixed
+// One workgroup, bound by the latency of its loads: 1024 threads with eight independent accumulators each keep 8192
+// loads in flight per sweep (the cost pass of the bench scene leaves ~23 k partials: three sweeps instead of 23 with 256
+// threads x 4).  Which partial goes to which accumulator and the order of every addition depend on n only: the sum is
+// bitwise reproducible run to run.
+constexpr int kSumThreads = 1024;
+__global__ __launch_bounds__(kSumThreads) void k_sum_partials(const double* __restrict__ partial, int n,
+                                                              double* __restrict__ out) {
+  constexpr int T = kSumThreads;
+  __shared__ double s_c[T];
+  double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   int i = threadIdx.x;
-  for (; i + 768 < n; i += 1024) { a0 += partial[i]; a1 += partial[i + 256]; a2 += partial[i + 512]; a3 += partial[i + 768]; }
-  for (; i < n; i += 256) a0 += partial[i];
-  s_c[threadIdx.x] = (a0 + a1) + (a2 + a3);
+  for (; i + 7 * T < n; i += 8 * T) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] += partial[i + j * T];
+  }
+  for (; i < n; i += T) a[0] += partial[i];
+  s_c[threadIdx.x] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
   __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
+  for (int off = T / 2; off > 0; off >>= 1) {
     if ((int)threadIdx.x < off) s_c[threadIdx.x] += s_c[threadIdx.x + off];
     __syncthreads();
   }
@@ -638,13 +722,14 @@ __global__ __launch_bounds__(256) void k_ba_cam_w(BaDev d, double* __restrict__ 
 }
 
 // ---------------------------------------------------------------- raw ------
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_ba_raw(BaDev d, double* __restrict__ residuals, double* __restrict__ Jq_o,
-                                                double* __restrict__ Jt_o, double* __restrict__ JX_o,
-                                                double* __restrict__ W_o) {
+// k_ba_raw / k_ba_raw_compact / k_ba_obs_errors come as pairs: the kernel of the generic path keeps its name and
+// signature, its _sc twin is the same body with eval_block's SHARED flag (own register allocation, no branch inside).
+template <int MODEL, bool SHARED>
+__device__ __forceinline__ void ba_raw_body(const BaDev& d, double* __restrict__ residuals, double* __restrict__ Jq_o,
+                                            double* __restrict__ Jt_o, double* __restrict__ JX_o,
+                                            double* __restrict__ W_o, double (*s_rows)[64 * 18]) {
   // thread = observation in the caller's order: the blocks of a wavefront are adjacent in every output array,
   // so each array is written through wave_store_rows (coalesced 16-B stores)
-  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 18];
   const int wave = threadIdx.x >> 6;
   const uint64_t o = blockIdx.x * (uint64_t)256 + threadIdx.x;
   const uint64_t o_wave = blockIdx.x * (uint64_t)256 + wave * 64;
@@ -663,7 +748,11 @@ __global__ __launch_bounds__(256) void k_ba_raw(BaDev d, double* __restrict__ re
     const double X[3] = {d.points[3 * (size_t)pt], d.points[3 * (size_t)pt + 1], d.points[3 * (size_t)pt + 2]};
     ReprojBlock b;
     double q[4];
-    eval_block<MODEL>(d, im, X, d.obs_xy[2 * o], d.obs_xy[2 * o + 1], b, q);
+    double pose[7];
+    BaCam<MODEL, SHARED> cam(d);
+    cam.of_image(d, im);
+    load_pose(d, im, pose);
+    eval_block_at(cam, pose, X, d.obs_xy[2 * o], d.obs_xy[2 * o + 1], b, q);
     reproj_jacobians(b, Jq, Jt, JX);
     const bool cpose = d.image_const_pose && d.image_const_pose[im];
     res[0] = b.r[0]; res[1] = b.r[1];
@@ -701,6 +790,20 @@ __global__ __launch_bounds__(256) void k_ba_raw(BaDev d, double* __restrict__ re
   if (JX_o) wave_store_rows<6>(JX_o, o_wave, cnt, JX, s_rows[wave]);
   if (W_o) wave_store_rows<18>(W_o, o_wave, cnt, Wb, s_rows[wave]);
 }
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_ba_raw(BaDev d, double* __restrict__ residuals, double* __restrict__ Jq_o,
+                                                double* __restrict__ Jt_o, double* __restrict__ JX_o,
+                                                double* __restrict__ W_o) {
+  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 18];
+  ba_raw_body<MODEL, false>(d, residuals, Jq_o, Jt_o, JX_o, W_o, s_rows);
+}
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_ba_raw_sc(BaDev d, double* __restrict__ residuals, double* __restrict__ Jq_o,
+                                                   double* __restrict__ Jt_o, double* __restrict__ JX_o,
+                                                   double* __restrict__ W_o) {
+  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 18];
+  ba_raw_body<MODEL, true>(d, residuals, Jq_o, Jt_o, JX_o, W_o, s_rows);
+}
 
 // Camera-parameter block of every reprojection residual (2 x K, row stride PCD_CAM_JAC_STRIDE).
 template <int MODEL>
@@ -736,9 +839,8 @@ __global__ __launch_bounds__(256) void k_ba_cam_jac(BaDev d, double* __restrict_
 // the values eval_block gives k_ba_raw, bit for bit; D and dPdq are never read here, so the compiler drops them
 // (tests/test_ceres_compact_isa.py holds the register count against k_ba_raw's).  A constant-pose observation keeps
 // its true M: its jac_X needs it.
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_ba_raw_compact(BaDev d, double* __restrict__ rec_o) {
-  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 8];
+template <int MODEL, bool SHARED>
+__device__ __forceinline__ void ba_raw_compact_body(const BaDev& d, double* __restrict__ rec_o, double (*s_rows)[64 * 8]) {
   const int wave = threadIdx.x >> 6;
   const uint64_t o = blockIdx.x * (uint64_t)256 + threadIdx.x;
   const uint64_t o_wave = blockIdx.x * (uint64_t)256 + wave * 64;
@@ -752,12 +854,26 @@ __global__ __launch_bounds__(256) void k_ba_raw_compact(BaDev d, double* __restr
     const double X[3] = {d.points[3 * (size_t)pt], d.points[3 * (size_t)pt + 1], d.points[3 * (size_t)pt + 2]};
     ReprojBlock b;
     double q[4];
-    eval_block<MODEL>(d, im, X, d.obs_xy[2 * o], d.obs_xy[2 * o + 1], b, q);
+    double pose[7];
+    BaCam<MODEL, SHARED> cam(d);
+    cam.of_image(d, im);
+    load_pose(d, im, pose);
+    eval_block_at(cam, pose, X, d.obs_xy[2 * o], d.obs_xy[2 * o + 1], b, q);
     rec[0] = b.r[0]; rec[1] = b.r[1];
 #pragma unroll
     for (int k = 0; k < 6; ++k) rec[2 + k] = b.M[k];
   }
   wave_store_rows<8>(rec_o, o_wave, cnt, rec, s_rows[wave]);   // 4 KiB of consecutive addresses per wavefront
+}
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_ba_raw_compact(BaDev d, double* __restrict__ rec_o) {
+  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 8];
+  ba_raw_compact_body<MODEL, false>(d, rec_o, s_rows);
+}
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_ba_raw_compact_sc(BaDev d, double* __restrict__ rec_o) {
+  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 8];
+  ba_raw_compact_body<MODEL, true>(d, rec_o, s_rows);
 }
 
 // Camera blocks for the compact route: [O][2][PCD_CAM_JAC_STRIDE] -> [O][2][cs], cs = the widest camera of the handle
@@ -776,8 +892,8 @@ __global__ __launch_bounds__(256) void k_ba_pack_cam_jac(const double* __restric
 //   sq_err = CalculateSquaredReprojectionError (base/projection.cc:104-117; quaternion normalised first as
 //            base/pose.cc QuaternionRotatePoint does; DBL_MAX when the point is not in front of the camera)
 //   depth  = P.z (FilterObservationsWithNegativeDepth, base/reconstruction.cc:837-855, tests it against eps)
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_ba_obs_errors(BaDev d, double* __restrict__ sq_err, double* __restrict__ depth) {
+template <int MODEL, bool SHARED>
+__device__ __forceinline__ void ba_obs_errors_body(const BaDev& d, double* __restrict__ sq_err, double* __restrict__ depth) {
   const uint64_t o = blockIdx.x * (uint64_t)256 + threadIdx.x;
   if (o >= d.O) return;
   const int im = d.obs_image[o], pt = d.obs_point[o];
@@ -795,12 +911,20 @@ __global__ __launch_bounds__(256) void k_ba_obs_errors(BaDev d, double* __restri
   if (depth) depth[o] = Pz;
   if (!sq_err) return;
   if (Pz < 2.220446049250313e-16) { sq_err[o] = 1.7976931348623157e308; return; }
-  const int cm = d.image_cam[im];
-  const int model = MODEL >= 0 ? MODEL : d.cam_model[cm];
+  BaCam<MODEL, SHARED> cam(d);
+  cam.of_image(d, im);
   D2 x, y;
-  world_to_image_d2(model, d.cam_params + d.cam_off[cm], Px / Pz, Py / Pz, x, y);
+  world_to_image_d2(cam.model, cam.params(), Px / Pz, Py / Pz, x, y);
   const double dx = x.a - d.obs_xy[2 * o], dy = y.a - d.obs_xy[2 * o + 1];
   sq_err[o] = dx * dx + dy * dy;
+}
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_ba_obs_errors(BaDev d, double* __restrict__ sq_err, double* __restrict__ depth) {
+  ba_obs_errors_body<MODEL, false>(d, sq_err, depth);
+}
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_ba_obs_errors_sc(BaDev d, double* __restrict__ sq_err, double* __restrict__ depth) {
+  ba_obs_errors_body<MODEL, true>(d, sq_err, depth);
 }
 
 __global__ __launch_bounds__(256) void k_ba_lidar_raw(BaDev d, double* __restrict__ residuals, double* __restrict__ JL) {
@@ -1609,6 +1733,7 @@ struct pcd_ba {
   int loss_type = 0;
   double loss_scale = 1.0;
   int uniform_model = -1;  // >= 0: every camera has this model
+  int shared_cam = -1;     // >= 0: every image maps to this camera (BaDev::shared_cam)
   DevBuf<int> cam_model, cam_off, image_cam, obs_image, obs_point, lidar_point, pt_order, sell_img, img_pt;
   DevBuf<double> cam_params, poses, points, obs_xy, lidar_abcd, lidar_w, sell_xy, img_xy;
   DevBuf<uint8_t> image_const_pose, image_const_tvec, point_const;
@@ -1653,7 +1778,7 @@ struct pcd_ba {
     d.img_obs_start = img_obs_start.p; d.img_pt = img_pt.p; d.img_xy = img_xy.p; d.img_obs = img_obs.p;
     d.seg_img = seg_img.p; d.seg_begin = seg_begin.p; d.img_seg_start = img_seg_start.p;
     d.cam_refine = has_refine ? cam_refine.p : nullptr; d.cam_img_start = cam_img_start.p; d.cam_img_list = cam_img_list.p;
-    d.C = C; d.cam_k = (uniform_model >= 0 && uniform_model <= 4) ? cam_num_params(uniform_model) : PCD_CAM_JAC_STRIDE;
+    d.C = C; d.shared_cam = shared_cam; d.cam_k = (uniform_model >= 0 && uniform_model <= 4) ? cam_num_params(uniform_model) : PCD_CAM_JAC_STRIDE;
     d.I = I; d.P = P; d.nslices = nslices; d.O = O; d.L = L; d.loss_type = loss_type; d.loss_scale = loss_scale;
     return d;
   }
@@ -1726,6 +1851,11 @@ static void build_csr(const int32_t* key, uint64_t n, int nkeys, std::vector<uin
     case 4: { constexpr int M = 4; __VA_ARGS__; } break;          \
     default: { constexpr int M = -1; __VA_ARGS__; } break;        \
   }
+
+// the same with the shared-camera flag of the handle as a second template argument SH
+#define PCD_BA_DISPATCH_CAM(MODELVAR, SHAREDVAR, ...)                                  \
+  if (SHAREDVAR) { constexpr bool SH = true; PCD_BA_DISPATCH(MODELVAR, __VA_ARGS__) }  \
+  else { constexpr bool SH = false; PCD_BA_DISPATCH(MODELVAR, __VA_ARGS__) }
 
 // Grid of the kernel that writes cost_partial[blockIdx.x]: k_ba_points takes two 64-track slices per workgroup,
 // k_ba_cost sweeps the residual blocks with a capped grid.  pcd_ba_create sizes cost_partial from the SAME function
@@ -1918,6 +2048,9 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
   b->uniform_model = d->cam_model[0];
   for (int c = 1; c < d->num_cameras; ++c)
     if (d->cam_model[c] != b->uniform_model) b->uniform_model = -1;
+  b->shared_cam = d->image_camera[0];
+  for (int i = 1; i < d->num_images; ++i)
+    if (d->image_camera[i] != b->shared_cam) b->shared_cam = -1;
   auto fail = [&](pcd_status st) { pcd_ba_destroy(b); return st; };
 #define UP(buf, src, n) do { pcd_status _st = upload(b->buf, src, (size_t)(n)); if (_st != PCD_OK) return fail(_st); } while (0)
   UP(cam_model, d->cam_model, b->C); UP(cam_off, d->cam_param_offset, b->C); UP(cam_params, d->cam_params, d->cam_params_len);
@@ -2076,13 +2209,15 @@ pcd_status pcd_ba_evaluate_device(pcd_ba* b, const pcd_ba_out* o, void* stream) 
     {
       ScopedKernelTimer t(want_blocks ? "ba_points" : "ba_points_cost", s);
       if (want_blocks) {
-        PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_points<M, true>), dim3(blocks), dim3(256), 0, s, d, o->H_pt,
-                                                   o->g_pt, b->cost_partial.p));
+        PCD_BA_DISPATCH_CAM(model, d.shared_cam >= 0,
+                            hipLaunchKernelGGL((k_ba_points<M, true, SH>), dim3(blocks), dim3(256), 0, s, d, o->H_pt, o->g_pt,
+                                               b->cost_partial.p));
       } else {
-        PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_cost<M>), dim3(blocks), dim3(256), 0, s, d, b->cost_partial.p));
+        PCD_BA_DISPATCH_CAM(model, d.shared_cam >= 0,
+                            hipLaunchKernelGGL((k_ba_cost<M, SH>), dim3(blocks), dim3(256), 0, s, d, b->cost_partial.p));
       }
     }
-    if (o->cost) hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, b->cost_partial.p, (int)blocks, o->cost);
+    if (o->cost) hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(kSumThreads), 0, s, b->cost_partial.p, (int)blocks, o->cost);
   }
   // W rides on the image pass when that runs anyway (normal-equation mode); otherwise the raw kernel fills it
   const bool w_fused = o->W && (o->H_img || o->g_img) && b->O;
@@ -2103,8 +2238,13 @@ pcd_status pcd_ba_evaluate_device(pcd_ba* b, const pcd_ba_out* o, void* stream) 
   double* const W_raw = w_fused ? nullptr : o->W;
   if ((o->residuals || o->jac_q || o->jac_t || o->jac_X || W_raw) && b->O) {
     ScopedKernelTimer t("ba_raw", s);
-    PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_raw<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, o->residuals,
-                                               o->jac_q, o->jac_t, o->jac_X, W_raw));
+    if (d.shared_cam >= 0) {
+      PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_raw_sc<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, o->residuals,
+                                                 o->jac_q, o->jac_t, o->jac_X, W_raw));
+    } else {
+      PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_raw<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, o->residuals,
+                                                 o->jac_q, o->jac_t, o->jac_X, W_raw));
+    }
   }
   if (o->jac_cam && b->O) {
     ScopedKernelTimer t("ba_cam_jac", s);
@@ -2138,8 +2278,13 @@ pcd_status pcd_ba_observation_errors_device(pcd_ba* b, double* d_sq_err, double*
   const BaDev d = b->dev();
   const int model = b->uniform_model;
   ScopedKernelTimer t("ba_obs_errors", s);
-  PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_obs_errors<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, d_sq_err,
-                                            d_depth));
+  if (d.shared_cam >= 0) {
+    PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_obs_errors_sc<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, d_sq_err,
+                                              d_depth));
+  } else {
+    PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_obs_errors<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, d_sq_err,
+                                              d_depth));
+  }
   PCD_HIP_TRY(hipGetLastError());
   return PCD_OK;
 }
@@ -2263,8 +2408,13 @@ pcd_status pcd_ba_evaluate_blocks_compact(pcd_ba* b, int want_jacobians, int wan
     const BaDev d = b->dev();
     if (O) {
       ScopedKernelTimer t("ba_raw_compact", s);
-      PCD_BA_DISPATCH(b->uniform_model, hipLaunchKernelGGL((k_ba_raw_compact<M>), dim3(div_up(O, 256)), dim3(256), 0, s,
-                                                           d, b->o_rec.p));
+      if (d.shared_cam >= 0) {
+        PCD_BA_DISPATCH(b->uniform_model, hipLaunchKernelGGL((k_ba_raw_compact_sc<M>), dim3(div_up(O, 256)), dim3(256), 0,
+                                                             s, d, b->o_rec.p));
+      } else {
+        PCD_BA_DISPATCH(b->uniform_model, hipLaunchKernelGGL((k_ba_raw_compact<M>), dim3(div_up(O, 256)), dim3(256), 0, s,
+                                                             d, b->o_rec.p));
+      }
     }
     if (L) {
       ScopedKernelTimer t("ba_lidar_raw", s);
@@ -2413,9 +2563,10 @@ pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pc
     {
       ScopedKernelTimer t("ba_schur_normal", s);
       const unsigned blocks = cost_blocks(b, true);
-      PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_points<M, true>), dim3(blocks), dim3(256), 0, s, d, S.Hpt.p,
-                                                 S.gpt.p, b->cost_partial.p));
-      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, b->cost_partial.p, (int)blocks,
+      PCD_BA_DISPATCH_CAM(model, d.shared_cam >= 0,
+                          hipLaunchKernelGGL((k_ba_points<M, true, SH>), dim3(blocks), dim3(256), 0, s, d, S.Hpt.p, S.gpt.p,
+                                             b->cost_partial.p));
+      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(kSumThreads), 0, s, b->cost_partial.p, (int)blocks,
                          o->cost ? o->cost : S.cost.p);
       if (b->nseg)
         PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_images<M, true>), dim3(b->nseg), dim3(256), 0, s, dim,
