@@ -59,6 +59,14 @@ struct QueryScratch {
   }
   DevBuf<pcd_assoc_hit> d_hits;
   DevBuf<uint32_t> hit_pos, hit_count;
+  // normal estimation (normals.hip): 64-query passes per leaf and their exclusive scan, the (leaf, pass) work items,
+  // the per-block partial sums followed by their totals, and the staging of the host API's outputs
+  DevBuf<uint32_t> nr_pass, nr_off;
+  DevBuf<uint2> nr_items;
+  DevBuf<unsigned long long> nr_part;
+  DevBuf<char> nr_tmp;
+  DevBuf<uint32_t> nr_count;
+  DevBuf<double> nr_curv;
 };
 
 inline QueryScratch* scratch_of(pcd_cloud* c) {

@@ -21,6 +21,7 @@ GATE_BOUNDED_SEARCH = 0x100   # OR-ed into a gate mode: search bounded by the ga
 LIDAR_NONE, LIDAR_ICP, LIDAR_ICP_GROUND = 0, 1, 2
 LOSS_TRIVIAL, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2
 LAYOUT_XYZ_NRM, LAYOUT_AOS32 = 0, 1
+NORMALS_ORIENT_NONE, NORMALS_ORIENT_VIEWPOINT = 0, 1
 KEY_NONE = 0x7FFFFFFFFFFFFFFF
 
 CAMERA_MODELS = ["SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL", "OPENCV", "OPENCV_FISHEYE",
@@ -159,6 +160,18 @@ class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
 
+class NormalsOptions(C.Structure):
+    """pcd_normals_options (pcdhip.h)."""
+    _fields_ = [("radius", C.c_float), ("min_neighbors", C.c_int32), ("orient", C.c_int32),
+                ("viewpoint", C.c_float * 3), ("only_missing", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+class NormalsInfo(C.Structure):
+    _fields_ = [("num_estimated", C.c_uint64), ("num_too_few", C.c_uint64), ("num_degenerate", C.c_uint64),
+                ("num_kept", C.c_uint64), ("pair_tests", C.c_uint64), ("max_neighbors", C.c_uint32),
+                ("mean_neighbors", C.c_double), ("ms", C.c_double)]
+
+
 class NNStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("queries", "brick_groups", "staged_points", "fallback_queries",
                                            "fallback_points", "pair_evals")]
@@ -190,6 +203,7 @@ ABI_SYMBOLS = [
     "pcd_ba_schur_back_substitute_device", "pcd_ba_plus_device", "pcd_ba_schur_stats",
     "pcd_ba_pcg_opts_default", "pcd_ba_schur_solve_pcg_device", "pcd_ba_schur_solve_pcg", "pcd_ba_get_parameters",
     "pcd_ba_solve_opts_default", "pcd_ba_solve",
+    "pcd_normals_options_default", "pcd_cloud_estimate_normals_device", "pcd_cloud_estimate_normals",
 ]
 
 
@@ -250,6 +264,12 @@ def lib():
     L.pcd_search_range_schedule.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p]
     L.pcd_profile_get.argtypes = [C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]
     L.pcd_nn_last_stats.argtypes = [C.c_void_p, C.POINTER(NNStats)]
+    L.pcd_normals_options_default.argtypes = [C.POINTER(NormalsOptions)]
+    L.pcd_normals_options_default.restype = None
+    L.pcd_cloud_estimate_normals_device.argtypes = [C.c_void_p, C.POINTER(NormalsOptions), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]
+    L.pcd_cloud_estimate_normals.argtypes = [C.c_void_p, C.POINTER(NormalsOptions), C.c_void_p, C.c_void_p,
+                                             C.POINTER(NormalsInfo)]
     if hasattr(L, "pcd_ba_create"):
         L.pcd_ba_create.argtypes = [C.POINTER(BADesc), C.POINTER(C.c_void_p)]
         L.pcd_ba_destroy.argtypes = [C.c_void_p]
@@ -307,6 +327,16 @@ def _ptr(x):
     return C.c_void_p(x.data_ptr())
 
 
+def normals_options(radius=0.15, min_neighbors=3, orient=None, viewpoint=(0, 0, 0), only_missing=False):
+    o = NormalsOptions()
+    lib().pcd_normals_options_default(C.byref(o))
+    o.radius, o.min_neighbors, o.only_missing = radius, min_neighbors, int(bool(only_missing))
+    if orient is not None:
+        o.orient = orient
+    o.viewpoint[:] = [float(v) for v in viewpoint]
+    return o
+
+
 class Cloud:
     """Device-resident LiDAR cloud index (reference: lidar::PointCloudProcess + lidar::Kdtree)."""
 
@@ -359,6 +389,25 @@ class Cloud:
         nrm = np.empty((n, 3), np.float32)
         _check(lib().pcd_cloud_download(self._h, _vp(xyz), _vp(nrm)))
         return xyz, nrm
+
+    def estimate_normals(self, radius=0.15, min_neighbors=3, orient=NORMALS_ORIENT_VIEWPOINT, viewpoint=(0, 0, 0),
+                         only_missing=False):
+        """Radius-PCA normals for every row, stored in the handle (pcd_cloud_estimate_normals): returns the
+        neighbour count (uint32) and curvature (float64) per row and the info counters as a dict."""
+        n = len(self)
+        count = np.empty(n, np.uint32)
+        curv = np.empty(n, np.float64)
+        info = NormalsInfo()
+        o = normals_options(radius, min_neighbors, orient, viewpoint, only_missing)
+        _check(lib().pcd_cloud_estimate_normals(self._h, C.byref(o), _vp(count), _vp(curv), C.byref(info)))
+        return {"count": count, "curvature": curv, "info": {k: getattr(info, k) for k, _ in NormalsInfo._fields_}}
+
+    def estimate_normals_device(self, d_count=None, d_curvature=None, radius=0.15, min_neighbors=3,
+                                orient=NORMALS_ORIENT_VIEWPOINT, viewpoint=(0, 0, 0), only_missing=False, stream=0):
+        """the same with device outputs (torch tensors or raw pointers; either may be None), asynchronous on `stream`"""
+        o = normals_options(radius, min_neighbors, orient, viewpoint, only_missing)
+        _check(lib().pcd_cloud_estimate_normals_device(self._h, C.byref(o), _ptr(d_count), _ptr(d_curvature),
+                                                       C.c_void_p(stream)))
 
     def nn(self, q, algo=NN_AUTO):
         """Kdtree::GetClosestPoint for a batch: returns (idx uint32, sqdist float32, found uint8)."""

@@ -13,6 +13,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -67,9 +68,23 @@ class PointCloudProcess {
   // read (the reference prints and returns false; callers only print, sfm/incremental_mapper.cc:201-205).
   bool Initialize() {
     std::vector<float> xyz, nrm;
-    if (!ReadPlyXYZNormal(path_, &xyz, &nrm)) return false;
-    return InitializeFromRawCloud(xyz.data(), nrm.data(), xyz.size() / 3);
+    bool has_normals = false;
+    if (!ReadPlyXYZNormal(path_, &xyz, &nrm, &has_normals)) return false;
+    return InitializeFromRawCloud(xyz.data(), nrm.data(), xyz.size() / 3, false, has_normals);
   }
+
+  // Normals on the device instead of the manual's CloudCompare step (README.md "Preparing point cloud", "calculate
+  // normals using radius at 10-20cm"): radius PCA over the cloud index (pcd_cloud_estimate_normals), oriented towards
+  // the sensor origin.  Off (the default): the cloud keeps the normals it came with, as the reference does -- a PLY
+  // without normal properties then associates nothing (lidar/ply.cc:101).  WhenMissing: estimate when the file (or the
+  // caller of InitializeFromRawCloud) has no normals.  Always: replace them.  Call before Initialize.
+  enum class NormalEstimation { Off, WhenMissing, Always };
+  void SetNormalEstimation(float radius, int min_neighbors, NormalEstimation mode) {
+    nrm_radius_ = radius;
+    nrm_min_neighbors_ = min_neighbors;
+    nrm_mode_ = mode;
+  }
+  const pcd_normals_info& normals_info() const { return nrm_info_; }   // of the last estimation (zeros: none ran)
   // lidar/ply.cc:9-31 with its own signature: also creates pcd_proj_ and builds its submaps (ply.cc:10, 27)
   bool Initialize(const PcdProjectionOptions& pp_options) {
     if (!Initialize()) return false;
@@ -84,7 +99,9 @@ class PointCloudProcess {
   // lidar/ply.cc:9-31 after pcl::io::loadPLYFile: rows as stored in the PLY (LiDAR frame, lidarpt::Point
   // AoS 32 B or two arrays).  Applies the axis swap + NaN filter of ply.cc:33-57 and builds the index.
   // Returns false on failure like the reference (the caller only prints).
-  bool InitializeFromRawCloud(const float* xyz, const float* nrm, uint64_t n, bool aos32 = false) {
+  // has_normals = false: the rows carry no normals (all 0), which SetNormalEstimation's WhenMissing mode acts on.
+  bool InitializeFromRawCloud(const float* xyz, const float* nrm, uint64_t n, bool aos32 = false,
+                              bool has_normals = true) {
     pcd_cloud_options o;
     pcd_cloud_options_default(&o);
     o.device = device_;
@@ -94,7 +111,24 @@ class PointCloudProcess {
     pcd_cloud_destroy(cloud_);
     cloud_ = nullptr;
     host_nrm_.clear();   // cached normals belong to the old cloud
-    return pcd_cloud_create(xyz, nrm, n, &o, &cloud_) == PCD_OK;
+    nrm_info_ = pcd_normals_info{};
+    if (pcd_cloud_create(xyz, nrm, n, &o, &cloud_) != PCD_OK) return false;
+    if (nrm_mode_ == NormalEstimation::Always || (nrm_mode_ == NormalEstimation::WhenMissing && !has_normals)) {
+      pcd_normals_options no;
+      pcd_normals_options_default(&no);
+      no.radius = nrm_radius_;
+      no.min_neighbors = nrm_min_neighbors_;
+      if (pcd_cloud_estimate_normals(cloud_, &no, nullptr, nullptr, &nrm_info_) != PCD_OK) {
+        std::fprintf(stderr, "normal estimation failed: %s\n", pcd_last_error());
+        return false;
+      }
+      std::fprintf(stderr, "estimated normals at radius %g: %llu rows, %llu with too few neighbours, %llu degenerate, "
+                   "mean %.1f / max %u neighbours, %.2f ms\n", (double)nrm_radius_,
+                   (unsigned long long)nrm_info_.num_estimated, (unsigned long long)nrm_info_.num_too_few,
+                   (unsigned long long)nrm_info_.num_degenerate, nrm_info_.mean_neighbors, nrm_info_.max_neighbors,
+                   nrm_info_.ms);
+    }
+    return true;
   }
 
   // lidar/ply.h:31, ply.cc:90-107 -- unchanged signature; one query per call (correct, launch-bound)
@@ -142,6 +176,10 @@ class PointCloudProcess {
   int device_;
   pcd_cloud* cloud_ = nullptr;
   std::vector<float> host_nrm_;
+  float nrm_radius_ = 0.15f;
+  int nrm_min_neighbors_ = 3;
+  NormalEstimation nrm_mode_ = NormalEstimation::Off;
+  pcd_normals_info nrm_info_{};
 };
 
 }  // namespace lidar

@@ -5,8 +5,8 @@
 // else in the file is ignored.  This reader restates that contract without PCL: `ascii 1.0` and
 // `binary_little_endian 1.0`, the vertex element with scalar properties of any PLY type (converted to
 // float), normals named normal_x/normal_y/normal_z or nx/ny/nz, missing normals left at 0 (such points
-// are later rejected by lidar/ply.cc:101, ||n|| < 1e-6).  Elements after `vertex` (faces ...) are not
-// read; list properties inside the vertex element are not supported (returns false, like a failed load).
+// are later rejected by lidar/ply.cc:101, ||n|| < 1e-6, unless the caller has them estimated: see has_normals).
+// Elements after `vertex` (faces ...) are not read; list properties inside the vertex element are not supported (returns false, like a failed load).
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -19,7 +19,11 @@
 
 namespace colmap_hip {
 
-inline bool ReadPlyXYZNormal(const std::string& path, std::vector<float>* xyz, std::vector<float>* nrm) {
+// has_normals (may be NULL): whether the vertex element declares all three normal properties -- a file without them
+// loads with normals 0, and PointCloudProcess::SetNormalEstimation (lidar_hip.h) can have them estimated on the device
+inline bool ReadPlyXYZNormal(const std::string& path, std::vector<float>* xyz, std::vector<float>* nrm,
+                             bool* has_normals) {
+  if (has_normals) *has_normals = false;
   FILE* f = std::fopen(path.c_str(), "rb");
   if (!f) return false;
   struct Prop { std::string type, name; };
@@ -80,6 +84,7 @@ inline bool ReadPlyXYZNormal(const std::string& path, std::vector<float>* xyz, s
     else if (n == "normal_z" || n == "nz") slot[5] = (int)i;
   }
   if (slot[0] < 0 || slot[1] < 0 || slot[2] < 0) { std::fclose(f); return false; }
+  if (has_normals) *has_normals = slot[3] >= 0 && slot[4] >= 0 && slot[5] >= 0;
   // a corrupt header must not drive the allocation: the vertex data cannot be larger than what is left of the
   // file (binary: stride bytes per vertex; ascii: at least "0 " per property)
   {
@@ -136,6 +141,10 @@ inline bool ReadPlyXYZNormal(const std::string& path, std::vector<float>* xyz, s
   }
   std::fclose(f);
   return ok;
+}
+
+inline bool ReadPlyXYZNormal(const std::string& path, std::vector<float>* xyz, std::vector<float>* nrm) {
+  return ReadPlyXYZNormal(path, xyz, nrm, nullptr);
 }
 
 }  // namespace colmap_hip

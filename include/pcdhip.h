@@ -125,6 +125,56 @@ uint64_t pcd_cloud_shards_size(const pcd_cloud_shards* s);          /* rows kept
 pcd_cloud* pcd_cloud_shards_get(pcd_cloud_shards* s, int shard);    /* borrowed: shard `shard` as a pcd_cloud      */
 
 /* ------------------------------------------------------------------------
+ * Normal estimation (radius PCA)      replaces the preparation step of the reference's manual
+ *   (README.md "Preparing point cloud": CloudCompare, "calculate normals using radius at 10-20cm");
+ *   a cloud whose normals are 0 associates nothing (lidar/ply.cc:101 drops ||n|| < 1e-6).
+ * Index space: the handle's post-filter rows.  For every finite row i, with r2 = radius*radius in float:
+ *   neighbours  N_i = { finite rows j : ((dx*dx) + dy*dy) + dz*dz <= r2 }, d = p_i - p_j evaluated in float with
+ *               separate multiply / add (the arithmetic of the search); i itself and duplicates count, a point at
+ *               distance exactly r is inside; count[i] = |N_i| = k;
+ *   moments     the float differences widened to double: m = (1/k) sum d, C = (1/k) sum d d^T - m m^T in fp64, every
+ *               row's sum in an order fixed by the cloud layout (no atomics: a repeated call is bitwise identical);
+ *   normal      unit eigenvector of the smallest eigenvalue of C (cyclic Jacobi in fp64), eigenvalues l0 <= l1 <= l2;
+ *               curvature[i] = l0 / (l0 + l1 + l2)  (PCL's surface variation);
+ *   no normal   (normal 0 0 0, curvature 0): k < max(min_neighbors, 3) [num_too_few]; l2 == 0 or l1 <= 1e-10 * l2,
+ *               i.e. coincident or collinear neighbours [num_degenerate]; rows with an Inf coordinate (count 0);
+ *   sign        PCD_NORMALS_ORIENT_VIEWPOINT: n . (viewpoint - p_i) >= 0, in double; viewpoint is given in the handle's
+ *               frame, (0,0,0) = the sensor after the raw_lidar_frame swap.  PCD_NORMALS_ORIENT_NONE, or a dot product
+ *               of exactly 0: the component of largest magnitude is positive (ties: lowest axis).  Nothing downstream
+ *               depends on the sign (lidar/lidar_point.cc:21-37 takes abs, base/cost_functions.h:226-229 squares);
+ *   store       the double vector rounded to float replaces the row's normal in the handle: every later search,
+ *               association, projection read-out and pcd_cloud_download sees it.  only_missing != 0: rows whose
+ *               stored normal has ||n|| >= 1e-6 keep it [num_kept]; their count and curvature are still reported.
+ * Limits: radius <= 8 * cell_size of the handle (PCD_ERR_INVALID otherwise: create the handle with a larger
+ * cell_size); ONE handle holding the whole cloud -- a shard of pcd_cloud_create_sharded or a handle with
+ * index_stride != 1 / index_base != 0 is refused with PCD_ERR_UNSUPPORTED, its neighbourhoods cross handle borders:
+ * estimate on one handle, download, then shard.  An empty cloud returns PCD_OK with zero counts.
+ * --------------------------------------------------------------------- */
+typedef enum { PCD_NORMALS_ORIENT_NONE = 0, PCD_NORMALS_ORIENT_VIEWPOINT = 1 } pcd_normals_orient;
+typedef struct {
+  float radius;            /* metres, finite and > 0                                        */
+  int32_t min_neighbors;   /* >= 0; fewer than max(min_neighbors, 3) neighbours: no normal  */
+  int32_t orient;          /* pcd_normals_orient                                            */
+  float viewpoint[3];
+  int32_t only_missing;
+  int32_t reserved[8];
+} pcd_normals_options;
+typedef struct {
+  uint64_t num_estimated, num_too_few, num_degenerate, num_kept;   /* finite rows: the four add up to num_indexed */
+  uint64_t pair_tests;       /* distance tests made (candidates staged x queries)            */
+  uint32_t max_neighbors;
+  double mean_neighbors;     /* over the finite rows                                         */
+  double ms;                 /* device time of the pass                                      */
+} pcd_normals_info;
+void pcd_normals_options_default(pcd_normals_options* o);   /* 0.15, 3, VIEWPOINT, {0,0,0}, 0 */
+/* d_count [size] / d_curvature [size]: device outputs, either may be NULL */
+pcd_status pcd_cloud_estimate_normals_device(pcd_cloud* c, const pcd_normals_options* opts /*NULL = defaults*/,
+                                             uint32_t* d_count, double* d_curvature, void* stream);
+/* host outputs; count, curvature and info may be NULL */
+pcd_status pcd_cloud_estimate_normals(pcd_cloud* c, const pcd_normals_options* opts, uint32_t* count,
+                                      double* curvature, pcd_normals_info* info);
+
+/* ------------------------------------------------------------------------
  * Nearest neighbour                          replaces lidar/kdtree.cc:10-21
  *   Kdtree::GetClosestPoint  (k = 1 pcl::KdTreeFLANN::nearestKSearch,
  *   FLANN L2_Simple<float> on x,y,z; exact)
