@@ -496,16 +496,32 @@ class ShardReduce(C.Structure):
     _fields_ = [("min_u64", MINFN), ("sum_i32", SUMFN), ("user", C.c_void_p)]
 
 
+class _BorrowedCloud(Cloud):
+    """a Cloud over a handle somebody else owns: close() forgets the handle instead of destroying it"""
+
+    def __init__(self, handle, owner):
+        self._h = C.c_void_p(handle)
+        self._owner = owner          # keeps the owner alive
+        self.device = 0
+
+    def close(self):
+        self._h = None
+
+
 class ShardedCloud:
     """One cloud over several devices of this process (pcd_cloud_create_sharded): what a multi-GPU C++ host builds in
     LoadPointcloud.  devices may repeat (tests put every shard on device 0)."""
 
-    def __init__(self, xyz, nrm, devices, raw_lidar_frame=True, cell_size=0.0):
+    def __init__(self, xyz, nrm, devices, raw_lidar_frame=True, cell_size=0.0, layout=LAYOUT_XYZ_NRM):
         L = lib()
         xyz = np.ascontiguousarray(xyz, np.float32)
-        nrm = np.ascontiguousarray(nrm, np.float32)
+        if layout == LAYOUT_AOS32:
+            xyz, nrm = xyz.reshape(-1, 8), None        # one array of 8-float rows, nrm ignored
+        else:
+            nrm = np.ascontiguousarray(nrm, np.float32)
         o = CloudOptions()
         L.pcd_cloud_options_default(C.byref(o))
+        o.layout = layout
         o.raw_lidar_frame = int(raw_lidar_frame)
         o.cell_size = cell_size
         dv = (C.c_int * len(devices))(*devices)
@@ -515,13 +531,28 @@ class ShardedCloud:
         L.pcd_cloud_shards_destroy.restype = None
         L.pcd_cloud_shards_size.argtypes = [C.c_void_p]
         L.pcd_cloud_shards_size.restype = C.c_uint64
+        L.pcd_cloud_shards_count.argtypes = [C.c_void_p]
+        L.pcd_cloud_shards_get.argtypes = [C.c_void_p, C.c_int]
+        L.pcd_cloud_shards_get.restype = C.c_void_p
         self._h = C.c_void_p()
         n = xyz.shape[0]
-        _check(L.pcd_cloud_create_sharded(_vp(xyz) if n else None, _vp(nrm) if n else None, n, C.byref(o), dv, len(devices),
-                                          C.byref(self._h)))
+        _check(L.pcd_cloud_create_sharded(_vp(xyz) if n else None, _vp(nrm) if n and nrm is not None else None, n,
+                                          C.byref(o), dv, len(devices), C.byref(self._h)))
 
     def __len__(self):
         return int(lib().pcd_cloud_shards_size(self._h))
+
+    def count(self):
+        """number of shards (pcd_cloud_shards_count)"""
+        return int(lib().pcd_cloud_shards_count(self._h))
+
+    def shard(self, i):
+        """shard i as a Cloud (pcd_cloud_shards_get).  Borrowed: it answers with the ORIGINAL row indices of the whole
+        cloud, lives as long as this object and is not destroyed by its own close()."""
+        h = lib().pcd_cloud_shards_get(self._h, int(i))
+        if not h:
+            raise IndexError(f"shard {i} of {self.count()}")
+        return _BorrowedCloud(h, self)
 
     def close(self):
         if self._h:
