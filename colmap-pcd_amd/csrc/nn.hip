@@ -28,8 +28,9 @@
 //                    from min(incoming key, key of the query's SEED): the exact nearest cloud point of the centre
 //                    of the query's 8x8x8-cell cube (a table built once per cloud, fb_seed_table).
 // Query bookkeeping in front of k_nn_brick: a two-level counting sort on the brick id
-// (k_bk_slots, k_bk_scatter, k_bk_count, k_bk_emit) that yields the brick-sorted query
-// records and the work items; queries with no cloud point in their brick's halo go
+// (k_bk_slots, k_bk_colscan, k_bk_scatter, k_bk_count, k_bk_emit) that starts from the
+// caller's double queries and yields the float records, the initial keys, the brick-sorted
+// query records and the work items; queries with no cloud point in their brick's halo go
 // straight to the fallback list.
 //
 // Exactness of the pruning (float distances, not real ones):
@@ -102,35 +103,50 @@ __device__ __forceinline__ uint64_t finalized_key(uint64_t k) {
 
 // ------------------------------------------------------- query preparation --
 // ply.cc:92: feature_point.getVector3fMap() = point_3d.cast<float>()
+// One __device__ function per prepare flavour: the record qf4[i] is returned, the query's initial key goes to *key.
+// Shared by the stand-alone k_prepare_* kernels and by k_bk_slots, which does the preparation itself on the
+// counting-sort path: the arithmetic lives here only.
+__device__ __forceinline__ float4 prepare_plain(const double* __restrict__ q, uint64_t i, uint64_t* key) {
+  float x = (float)q[3 * i], y = (float)q[3 * i + 1], z = (float)q[3 * i + 2];
+  bool ok = isfinite(x) && isfinite(y) && isfinite(z);
+  *key = ok ? kKeyInit : PCD_KEY_NONE;   // a query no search kernel touches leaves with its final key
+  return make_float4(x, y, z, ok ? 1.f : 0.f);
+}
 __global__ void k_prepare_queries(const double* __restrict__ q, uint64_t Q, float4* __restrict__ qf4,
                                   uint64_t* __restrict__ keys) {
   uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i >= Q) return;
-  float x = (float)q[3 * i], y = (float)q[3 * i + 1], z = (float)q[3 * i + 2];
-  bool ok = isfinite(x) && isfinite(y) && isfinite(z);
-  qf4[i] = make_float4(x, y, z, ok ? 1.f : 0.f);
-  keys[i] = ok ? kKeyInit : PCD_KEY_NONE;   // a query no search kernel touches leaves with its final key
+  uint64_t k;
+  qf4[i] = prepare_plain(q, i, &k);
+  keys[i] = k;
 }
 
 // pcd_nn_refine_device: the keys come in with another shard's results.  A query stays active only if this shard
 // can still improve it: lower bound of the float distance to the shard's tight bounding box <= incoming distance
 // (monotone rounding: fl_dist(q, p) >= fl_dist(q, clamp(q, lo, hi)) for every p in the box; equality is kept --
 // a lower index at the same distance may live here).  Inactive queries get w = 0 and no kernel touches their key.
-__global__ void k_prepare_refine(const double* __restrict__ q, uint64_t Q, const uint8_t* __restrict__ skip,
-                                 float lox, float loy, float loz, float hix, float hiy, float hiz,
+struct BoxF { float lox, loy, loz, hix, hiy, hiz; };
+// *key: in = the incoming key, out = the key the search starts from (inactive: the incoming key in its final form)
+__device__ __forceinline__ float4 prepare_refine(const double* __restrict__ q, uint64_t i, const uint8_t* __restrict__ skip,
+                                                 const BoxF& bx, uint64_t* key) {
+  float x = (float)q[3 * i], y = (float)q[3 * i + 1], z = (float)q[3 * i + 2];
+  bool ok = isfinite(x) && isfinite(y) && isfinite(z) && !(skip && skip[i]);
+  uint64_t k = *key;
+  if (k == PCD_KEY_NONE) k = kKeyInit;
+  if (ok) {
+    const float px = fminf(fmaxf(x, bx.lox), bx.hix), py = fminf(fmaxf(y, bx.loy), bx.hiy), pz = fminf(fmaxf(z, bx.loz), bx.hiz);
+    ok = l2_simple3(x, y, z, px, py, pz) <= __uint_as_float((uint32_t)(k >> 32));
+  }
+  *key = ok ? k : finalized_key(k);   // inactive: the key it came with, in its final form
+  return make_float4(x, y, z, ok ? 1.f : 0.f);
+}
+__global__ void k_prepare_refine(const double* __restrict__ q, uint64_t Q, const uint8_t* __restrict__ skip, BoxF bx,
                                  float4* __restrict__ qf4, uint64_t* __restrict__ keys) {
   uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i >= Q) return;
-  float x = (float)q[3 * i], y = (float)q[3 * i + 1], z = (float)q[3 * i + 2];
-  bool ok = isfinite(x) && isfinite(y) && isfinite(z) && !(skip && skip[i]);
   uint64_t k = keys[i];
-  if (k == PCD_KEY_NONE) k = kKeyInit;
-  if (ok) {
-    const float px = fminf(fmaxf(x, lox), hix), py = fminf(fmaxf(y, loy), hiy), pz = fminf(fmaxf(z, loz), hiz);
-    ok = l2_simple3(x, y, z, px, py, pz) <= __uint_as_float((uint32_t)(k >> 32));
-  }
-  qf4[i] = make_float4(x, y, z, ok ? 1.f : 0.f);
-  keys[i] = ok ? k : finalized_key(k);   // inactive: the key it came with, in its final form
+  qf4[i] = prepare_refine(q, i, skip, bx, &k);
+  keys[i] = k;
 }
 
 // Gate-bounded search (the association entry points): the three call sites reject an association whose point-to-point
@@ -158,16 +174,40 @@ __device__ __forceinline__ uint64_t bounded_init_key(double R, double x, double 
   }
   return k;
 }
+__device__ __forceinline__ float4 prepare_bounded(const double* __restrict__ q, uint64_t i,
+                                                  const double* __restrict__ max_range, uint64_t mr_count,
+                                                  double fixed_range, uint64_t* key) {
+  float x = (float)q[3 * i], y = (float)q[3 * i + 1], z = (float)q[3 * i + 2];
+  bool ok = isfinite(x) && isfinite(y) && isfinite(z);
+  *key = ok ? bounded_init_key(max_range ? max_range[mr_count == 1 ? 0 : i] : fixed_range, q[3 * i], q[3 * i + 1], q[3 * i + 2])
+            : PCD_KEY_NONE;
+  return make_float4(x, y, z, ok ? 1.f : 0.f);
+}
 __global__ void k_prepare_bounded(const double* __restrict__ q, uint64_t Q, const double* __restrict__ max_range,
                                   uint64_t mr_count, double fixed_range, float4* __restrict__ qf4,
                                   uint64_t* __restrict__ keys) {
   uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i >= Q) return;
-  float x = (float)q[3 * i], y = (float)q[3 * i + 1], z = (float)q[3 * i + 2];
-  bool ok = isfinite(x) && isfinite(y) && isfinite(z);
-  qf4[i] = make_float4(x, y, z, ok ? 1.f : 0.f);
-  keys[i] = ok ? bounded_init_key(max_range ? max_range[mr_count == 1 ? 0 : i] : fixed_range, q[3 * i], q[3 * i + 1], q[3 * i + 2])
-               : PCD_KEY_NONE;
+  uint64_t k;
+  qf4[i] = prepare_bounded(q, i, max_range, mr_count, fixed_range, &k);
+  keys[i] = k;
+}
+
+// which prepare flavour a call uses, and its inputs (host and device)
+enum { kPrepPlain = 0, kPrepRefine = 1, kPrepBounded = 2 };
+struct PrepArgs {
+  const double* q;             // the caller's queries, 3 doubles each
+  const uint8_t* skip;         // refine: queries to leave alone (may be null)
+  BoxF box;                    // refine: the shard's tight bounding box
+  const double* max_range;     // gate-bounded: 1 or Q ranges, or null: fixed_range
+  uint64_t mr_count;
+  double fixed_range;
+};
+template <int MODE>
+__device__ __forceinline__ float4 prepare_query(const PrepArgs& a, uint64_t i, uint64_t* key) {
+  if (MODE == kPrepRefine) return prepare_refine(a.q, i, a.skip, a.box, key);
+  if (MODE == kPrepBounded) return prepare_bounded(a.q, i, a.max_range, a.mr_count, a.fixed_range, key);
+  return prepare_plain(a.q, i, key);
 }
 
 __global__ void k_finalize_keys(uint64_t* __restrict__ keys, uint64_t Q) {
@@ -387,29 +427,42 @@ __global__ __launch_bounds__(256) void k_brick_emit(const uint32_t* __restrict__
 }
 
 // ------------------------------------------- brick bookkeeping, counting sort ---
-// Four launches instead of the radix sort's seven (round 2: 0.17 ms at Q = 1 M, three Onesweep digit passes at ~29 us
-// each whatever the size).  Per cloud and brick geometry, once: a SLOT for every brick whose halo region holds at
-// least one cloud point (k_brick_occupied + an exclusive scan; slots ascend with the brick id); a query in a brick
-// without a slot has nothing within the halo and goes straight to the exact fallback -- which is where the brick
-// kernel would have sent it after walking an empty region.  Per batch a two-level counting sort on the slot:
-//   k_bk_slots    query -> sort key (brick id) or "fallback" (outside the grid / brick with an empty halo region: those
-//                 are appended to the chunked fallback list here); histogram of the COARSE keys (id >> shift, at most
-//                 4096 buckets): LDS histogram per workgroup, merged with global atomics.
-//   k_bk_scatter  every workgroup scans the histogram into bucket starts itself; tiles of 4096 queries: rank inside the
-//                 tile by LDS atomics, one global atomic per (tile, bucket) for the tile's place in the bucket,
-//                 (key, query) pairs written bucket by bucket.
+// Five short launches instead of the radix sort's seven (round 2: 0.17 ms at Q = 1 M, three Onesweep digit passes at
+// ~29 us each whatever the size), and nothing in front of them: the first one reads the caller's double queries itself
+// (no stand-alone prepare pass) and the counters clean themselves (no memset, see counters_ready).  Per cloud and brick
+// geometry, once: one bit for every brick whose halo region holds at least one cloud point (k_brick_occupied +
+// k_brick_bitmap); a query in a brick without the bit has nothing within the halo and goes straight to the exact
+// fallback -- which is where the brick kernel would have sent it after walking an empty region.  Per batch a two-level
+// counting sort on the brick id:
+//   k_bk_slots<MODE>  at most 256 workgroups, each with a contiguous RANGE of rounds x 4096 queries.  Per query: the
+//                 prepare flavour MODE (prepare_query: float record qf4[i] and initial key keys[i], as the k_prepare_*
+//                 kernels write them on the other paths), then the sort key (brick id) or "fallback" (outside the grid /
+//                 brick with an empty halo region: those are appended to the chunked fallback list here).  The LDS
+//                 histogram of the COARSE keys (id >> shift, at most 4096 buckets) is left as one row of a
+//                 [ranges][buckets] matrix -- no global atomics.  One thread clears the counters of the NEXT call.
+//   k_bk_colscan  the matrix column by column, in place: queries of the bucket in the ranges before this one; the
+//                 bucket totals.
+//   k_bk_scatter  the same ranges: every workgroup scans the (at most 4096) bucket totals into bucket starts itself,
+//                 adds its row of the matrix and has its private cursor per bucket in LDS; every query takes its place
+//                 with one returning LDS atomic and is written as ONE 8-byte {fine key, query id} pair.
 //   k_bk_count    one workgroup per coarse bucket: queries per FINE key (low bits) in LDS -> the bucket's item count.
 //   k_bk_emit     one workgroup per coarse bucket: the same counting sort again, now with the item base known (sum
 //                 of the item counts to the left: items stay in brick order, which the XCD-aware walk of k_nn_brick
 //                 is worth 0.04 ms for), then the brick-sorted query records, their incoming keys and the work
-//                 items (G queries of one brick each).
-// (No workgroup waits for another one: a look-back over per-bucket descriptors needs agent-scope release / acquire to
-//  cross the XCDs' L2s -- with relaxed polling the descriptors never arrived -- and at that price was slower than this
-//  fourth launch.)
-// Queries of one brick arrive in any order (LDS / global atomics): WHICH queries share a work item varies from run to
-// run, every query's result does not.
+//                 items (G queries of one brick each).  LDS sized by the call's fine keys (dynamic), a thread's first
+//                 two pairs kept in registers between the two passes.
+// (No workgroup waits for another one: every hand-over is a kernel boundary.  A look-back over per-bucket descriptors
+//  needs agent-scope release / acquire to cross the XCDs' L2s -- with relaxed polling the descriptors never arrived --
+//  and at that price was slower than one more launch.)
+// Measured at Q = 1 M on the 10 M-point cloud (profiles/bk_fused_bench_lines.txt; scope nn_brick_bookkeeping, which now
+// holds the preparation too): 0.0925 ms, against 0.0953 + 0.0175 (nn_prepare) + the 64-byte memset's launch before.
+// By item: fused prepare + no memset 0.1049; + histogram matrix, LDS cursors and 8-byte pairs 0.0945; + dynamic LDS and
+// held pairs in k_bk_emit 0.0925.  Step 1.349 -> 1.330 ms.
+// Queries of one brick arrive in any order (LDS atomics): WHICH queries share a work item varies from run to run, every
+// query's result does not.
 constexpr uint32_t kSlotFallback = 0xFFFFFFFEu;   // query: finite, but outside the grid or in a brick without a slot
 constexpr uint32_t kSlotSkip = 0xFFFFFFFFu;       // query: not finite
+constexpr uint32_t kBkMaxRanges = 256;   // workgroups of k_bk_slots / k_bk_scatter: rows of the histogram matrix
 constexpr uint32_t kBkMaxCoarse = 4096, kBkMaxFine = 4096, kBkTileQ = 4096;   // 2^24 bricks: every grid of the 2^26-cell budget
 
 // one thread per brick: does the halo region (whole quad rows, as brick_load_meta walks them) hold any point?
@@ -458,26 +511,37 @@ __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* s_
   return block_excl_scan<4>(v, s_w, total);
 }
 
-__global__ __launch_bounds__(1024) void k_bk_slots(const float4* __restrict__ qf4, uint32_t Q, GridParams g, BrickParams b,
+template <int MODE>   // the call's prepare flavour, a template parameter for the reason given at k_nn_fallback<FUSED>
+__global__ __launch_bounds__(1024) void k_bk_slots(PrepArgs pa, uint32_t Q, uint32_t rounds, GridParams g, BrickParams b,
                                                    const uint32_t* __restrict__ brick_slot, uint32_t shift, uint32_t ncoarse,
-                                                   uint32_t* __restrict__ qslot, uint32_t* __restrict__ chist,
-                                                   uint32_t* __restrict__ fb_list, NnCounters* __restrict__ ctr) {
-  // few, large workgroups: every workgroup merges its whole LDS histogram into the global one with atomics
-  // (1024 workgroups x 2048 buckets = 2 M global atomics made this kernel 145 us)
+                                                   float4* __restrict__ qf4, uint64_t* __restrict__ keys,
+                                                   uint32_t* __restrict__ qslot, uint32_t* __restrict__ hmat,
+                                                   uint32_t* __restrict__ fb_list, NnCounters* __restrict__ ctr,
+                                                   NnCounters* __restrict__ ctr_next) {
+  // few, large workgroups (at most kBkMaxRanges): each owns a contiguous RANGE of `rounds` x 4096 queries and leaves its
+  // LDS histogram as one row of the [ranges][ncoarse] matrix
   __shared__ uint32_t s_h[kBkMaxCoarse], s_w[16], s_base;
+  // the counters of the NEXT grid-path call: every user of that block (the call before this one) has finished
+  if (blockIdx.x == 0 && threadIdx.x < sizeof(NnCounters) / 4) reinterpret_cast<uint32_t*>(ctr_next)[threadIdx.x] = 0;
   for (uint32_t c = threadIdx.x; c < ncoarse; c += 1024) s_h[c] = 0;
   __syncthreads();
   // rounds of 4 queries per thread: the fallback queries of a round are counted over the WORKGROUP and placed with one
   // global atomic (a chunk per wavefront, as the brick kernel does it, was one same-address returning atomic per
   // wavefront of this short kernel: 4096 of them, ~40 of its 54 us)
-  for (uint32_t r0 = blockIdx.x * 4096u; r0 < Q; r0 += gridDim.x * 4096u) {
+  for (uint32_t rr = 0; rr < rounds; ++rr) {
+    const uint64_t r0 = ((uint64_t)blockIdx.x * rounds + rr) * kBkTileQ;   // (64 bits: Q may be close to 2^32)
+    if (r0 >= Q) break;
     uint32_t sv[4], nfb = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const uint32_t i = r0 + k * 1024u + threadIdx.x;
+      const uint64_t i = r0 + k * 1024u + threadIdx.x;
       uint32_t s = kSlotSkip;
       if (i < Q) {
-        const float4 q = qf4[i];
+        // the caller's double query -> float record and initial key (what the k_prepare_* kernels do elsewhere)
+        uint64_t key = MODE == kPrepRefine ? keys[i] : 0;
+        const float4 q = prepare_query<MODE>(pa, i, &key);
+        qf4[i] = q;
+        keys[i] = key;
         if (q.w != 0.f) {
           const int cx = cell_coord_raw(q.x, g.origin[0], g.inv_h, g.dims[0]);
           const int cy = cell_coord_raw(q.y, g.origin[1], g.inv_h, g.dims[1]);
@@ -502,71 +566,91 @@ __global__ __launch_bounds__(1024) void k_bk_slots(const float4* __restrict__ qf
       pos += s_base;
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if (sv[k] == kSlotFallback) fb_list[pos++] = r0 + k * 1024u + threadIdx.x;
+        if (sv[k] == kSlotFallback) fb_list[pos++] = (uint32_t)r0 + k * 1024u + threadIdx.x;
       __syncthreads();   // s_base is rewritten in the next round
     }
   }
   __syncthreads();
-  for (uint32_t c = threadIdx.x; c < ncoarse; c += 1024)
-    if (s_h[c]) atomicAdd(&chist[c], s_h[c]);
+  for (uint32_t c = threadIdx.x; c < ncoarse; c += 1024) hmat[(size_t)blockIdx.x * ncoarse + c] = s_h[c];   // zeros too
 }
 
-__global__ __launch_bounds__(1024) void k_bk_scatter(const uint32_t* __restrict__ qslot, uint32_t Q, uint32_t shift,
-                                                     uint32_t ncoarse, const uint32_t* __restrict__ chist,
-                                                     uint32_t* __restrict__ cstart, uint32_t* __restrict__ ccur,
-                                                     uint32_t* __restrict__ pslot, uint32_t* __restrict__ pqid,
-                                                     NnCounters* __restrict__ ctr) {
-  __shared__ uint32_t s_h[kBkMaxCoarse], s_start[kBkMaxCoarse], s_w[16];
-  // bucket starts: every workgroup scans the (at most 4096-entry) histogram itself; workgroup 0 keeps the result
+// Column scan of the histogram matrix, in place: hmat[r][c] becomes the number of bucket c's queries in the ranges
+// before r, ctot[c] the bucket's total.  One workgroup per 64 buckets (a lane each), its 16 wavefronts share the ranges:
+// partial sums, their scan through LDS, then the prefixes.
+__global__ __launch_bounds__(1024) void k_bk_colscan(uint32_t* __restrict__ hmat, uint32_t nranges, uint32_t ncoarse,
+                                                     uint32_t* __restrict__ ctot) {
+  __shared__ uint32_t s_p[16][64];
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, c = blockIdx.x * 64u + lane;
+  const uint32_t per = (nranges + 15u) / 16u, ra = min(w * per, nranges), rb = min(ra + per, nranges);
+  uint32_t sum = 0;
+  if (c < ncoarse)
+    for (uint32_t r = ra; r < rb; ++r) sum += hmat[(size_t)r * ncoarse + c];
+  s_p[w][lane] = sum;
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 16; ++k) { const uint32_t v = s_p[k][lane]; base += k < w ? v : 0u; tot += v; }
+  if (c >= ncoarse) return;
+  if (w == 0) ctot[c] = tot;
+  for (uint32_t r = ra; r < rb; ++r) {
+    const uint32_t v = hmat[(size_t)r * ncoarse + c];
+    hmat[(size_t)r * ncoarse + c] = base;
+    base += v;
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_bk_scatter(const uint32_t* __restrict__ qslot, uint32_t Q, uint32_t rounds,
+                                                     uint32_t shift, uint32_t ncoarse, const uint32_t* __restrict__ ctot,
+                                                     const uint32_t* __restrict__ hmat, uint32_t* __restrict__ cstart,
+                                                     uint2* __restrict__ ppair, NnCounters* __restrict__ ctr) {
+  __shared__ uint32_t s_cur[kBkMaxCoarse], s_w[16];
+  // cursors of this range: bucket start (every workgroup scans the at most 4096 bucket totals itself; workgroup 0
+  // keeps the result) + the bucket's queries in the ranges before this one (k_bk_colscan)
   {
     const uint32_t per = (ncoarse + 1023u) / 1024u, c0 = threadIdx.x * per;   // per <= 4
     uint32_t h[4] = {0, 0, 0, 0}, sum = 0;
-    for (uint32_t k = 0; k < per && c0 + k < ncoarse; ++k) { h[k] = chist[c0 + k]; sum += h[k]; }
+    for (uint32_t k = 0; k < per && c0 + k < ncoarse; ++k) { h[k] = ctot[c0 + k]; sum += h[k]; }
     uint32_t total;
     uint32_t base = block_excl_scan<16>(sum, s_w, &total);
     for (uint32_t k = 0; k < per && c0 + k < ncoarse; ++k) {
-      s_start[c0 + k] = base;
+      s_cur[c0 + k] = base + hmat[(size_t)blockIdx.x * ncoarse + c0 + k];
       if (blockIdx.x == 0) cstart[c0 + k] = base;
       base += h[k];
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) { cstart[ncoarse] = total; ctr->n_in_grid = total; }
   }
-  for (uint32_t c = threadIdx.x; c < ncoarse; c += 1024) s_h[c] = 0;
   __syncthreads();
-  const uint32_t i0 = blockIdx.x * kBkTileQ + threadIdx.x;
-  uint32_t sl[4], lr[4];
+  // every query of the range: one returning LDS atomic on its bucket's cursor, one 8-byte store {fine key, query id}
+  const uint32_t mask = (1u << shift) - 1u;
+  for (uint32_t rr = 0; rr < rounds; ++rr) {
+    const uint64_t r0 = ((uint64_t)blockIdx.x * rounds + rr) * kBkTileQ;
+    if (r0 >= Q) break;
+    uint32_t sl[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint32_t i = i0 + k * 1024u;
-    sl[k] = i < Q ? qslot[i] : kSlotSkip;
-    lr[k] = sl[k] < kSlotFallback ? atomicAdd(&s_h[sl[k] >> shift], 1u) : 0u;   // rank inside the tile
-  }
-  __syncthreads();
-  for (uint32_t c = threadIdx.x; c < ncoarse; c += 1024) {
-    const uint32_t n = s_h[c];
-    s_h[c] = s_start[c] + (n ? atomicAdd(&ccur[c], n) : 0u);     // the tile's place in the bucket (cursors start at 0)
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (sl[k] < kSlotFallback) {
-      const uint32_t p = s_h[sl[k] >> shift] + lr[k];
-      pslot[p] = sl[k];
-      pqid[p] = i0 + k * 1024u;
+    for (int k = 0; k < 4; ++k) {
+      const uint64_t i = r0 + k * 1024u + threadIdx.x;
+      sl[k] = i < Q ? qslot[i] : kSlotSkip;
     }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (sl[k] < kSlotFallback) {
+        const uint32_t p = atomicAdd(&s_cur[sl[k] >> shift], 1u);
+        ppair[p] = make_uint2(sl[k] & mask, (uint32_t)r0 + k * 1024u + threadIdx.x);
+      }
+  }
 }
 
 // work items of every coarse bucket: one workgroup per bucket counts the bucket's queries per fine key in LDS
 template <int G>
 __global__ __launch_bounds__(256) void k_bk_count(uint32_t shift, const uint32_t* __restrict__ cstart,
-                                                  const uint32_t* __restrict__ pslot, uint32_t* __restrict__ bitems) {
+                                                  const uint2* __restrict__ ppair, uint32_t* __restrict__ bitems) {
   __shared__ uint32_t s_cnt[kBkMaxFine], s_w[4];
   const uint32_t nfine = 1u << shift, mask = nfine - 1u;
   const uint32_t beg = cstart[blockIdx.x], end = cstart[blockIdx.x + 1];
   if (beg == end) { if (threadIdx.x == 0) bitems[blockIdx.x] = 0; return; }
   for (uint32_t f = threadIdx.x; f < nfine; f += 256) s_cnt[f] = 0;
   __syncthreads();
-  for (uint32_t p = beg + threadIdx.x; p < end; p += 256) atomicAdd(&s_cnt[pslot[p] & mask], 1u);
+  for (uint32_t p = beg + threadIdx.x; p < end; p += 256) atomicAdd(&s_cnt[ppair[p].x & mask], 1u);
   __syncthreads();
   uint32_t ai = 0;
   for (uint32_t f = threadIdx.x; f < nfine; f += 256) ai += (s_cnt[f] + G - 1) / G;
@@ -578,15 +662,16 @@ __global__ __launch_bounds__(256) void k_bk_count(uint32_t shift, const uint32_t
 template <int G>
 __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4, const uint64_t* __restrict__ keys_in,
                                                  GridParams g, BrickParams b, uint32_t shift,
-                                                 const uint32_t* __restrict__ cstart, const uint32_t* __restrict__ pslot,
-                                                 const uint32_t* __restrict__ pqid, const uint32_t* __restrict__ bitems,
-                                                 uint32_t* __restrict__ chist, uint32_t* __restrict__ ccur,
-                                                 uint4* __restrict__ items, float4* __restrict__ qsorted,
+                                                 const uint32_t* __restrict__ cstart, const uint2* __restrict__ ppair,
+                                                 const uint32_t* __restrict__ bitems, uint4* __restrict__ items, float4* __restrict__ qsorted,
                                                  uint64_t* __restrict__ ksorted, NnCounters* __restrict__ ctr) {
-  // per fine key: start of its queries / items inside the bucket (kBkMaxFine + 1 entries: the count of key f is
-  // s_off[f + 1] - s_off[f]) and the running rank; 48 KB at 4096 fine keys
-  __shared__ uint32_t s_off[kBkMaxFine + 1], s_ioff[kBkMaxFine + 1], s_cur[kBkMaxFine], s_w[4];
+  // per fine key: start of its queries / items inside the bucket (nfine + 1 entries: the count of key f is
+  // s_off[f + 1] - s_off[f]) and the running rank.  Dynamic LDS, 12 B per fine key of THIS call: 24 KB at the 2048 fine
+  // keys of a 4.65 M-brick grid (six workgroups per CU), 48 KB at the maximum of 4096
+  extern __shared__ uint32_t s_dyn[];
+  __shared__ uint32_t s_w[4];
   const uint32_t nfine = 1u << shift, mask = nfine - 1u;
+  uint32_t *s_off = s_dyn, *s_ioff = s_off + nfine + 1, *s_cur = s_ioff + nfine + 1;
   const uint32_t beg = cstart[blockIdx.x], end = cstart[blockIdx.x + 1];
   // item base = items of all buckets to the left, in bucket order = brick order (the XCD-aware walk of k_nn_brick
   // depends on it): summed from k_bk_count's per-bucket totals -- no atomics, no waiting on other workgroups
@@ -595,11 +680,22 @@ __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4,
   uint32_t ibase;
   (void)block_excl_scan_256(acc, s_w, &ibase);
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) ctr->nitems = ibase + bitems[blockIdx.x];
-  if (threadIdx.x == 0) { chist[blockIdx.x] = 0; ccur[blockIdx.x] = 0; }   // clean for the next batch
   if (beg == end) return;
   for (uint32_t f = threadIdx.x; f < nfine; f += 256) s_cur[f] = 0;
   __syncthreads();
-  for (uint32_t p = beg + threadIdx.x; p < end; p += 256) atomicAdd(&s_cur[pslot[p] & mask], 1u);   // counts
+  // a thread's first kBkHeld entries stay in registers from the counting pass to the placement pass (a bucket of the
+  // 1 M-query workload holds ~440 entries: all of them); larger buckets read the rest twice
+  constexpr uint32_t kBkHeld = 2;
+  uint2 held[kBkHeld];
+#pragma unroll
+  for (uint32_t k = 0; k < kBkHeld; ++k) {
+    const uint32_t p = beg + threadIdx.x + k * 256u;
+    held[k] = p < end ? ppair[p] : make_uint2(0u, 0u);
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < kBkHeld; ++k)
+    if (beg + threadIdx.x + k * 256u < end) atomicAdd(&s_cur[held[k].x & mask], 1u);   // counts
+  for (uint32_t p = beg + threadIdx.x + kBkHeld * 256u; p < end; p += 256) atomicAdd(&s_cur[ppair[p].x & mask], 1u);
   __syncthreads();
   // exclusive prefixes of the query counts and of the item counts over the bucket's fine keys
   const uint32_t per = (nfine + 255u) / 256u, f0 = threadIdx.x * per;
@@ -617,8 +713,8 @@ __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4,
     if (threadIdx.x == 255) { s_off[nfine] = tq; s_ioff[nfine] = ti; }
     __syncthreads();
   }
-  for (uint32_t p = beg + threadIdx.x; p < end; p += 256) {
-    const uint32_t f = pslot[p] & mask, i = pqid[p];
+  auto place = [&](const uint2 e) {
+    const uint32_t f = e.x & mask, i = e.y;
     const uint32_t r = atomicAdd(&s_cur[f], 1u);
     float4 q = qf4[i];
     const uint32_t pos = beg + s_off[f] + r;
@@ -634,7 +730,11 @@ __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4,
     q.w = __uint_as_float(i);
     qsorted[pos] = q;
     ksorted[pos] = keys_in ? keys_in[i] : kKeyInit;
-  }
+  };
+#pragma unroll
+  for (uint32_t k = 0; k < kBkHeld; ++k)
+    if (beg + threadIdx.x + k * 256u < end) place(held[k]);
+  for (uint32_t p = beg + threadIdx.x + kBkHeld * 256u; p < end; p += 256) place(ppair[p]);
 }
 
 // ------------------------------------------------------------ brick kernel ---
@@ -1027,8 +1127,38 @@ static pcd_status fb_seed_table(pcd_cloud* c, QueryScratch* sc, hipStream_t s) {
   return PCD_OK;
 }
 
+// The counters: two blocks, zeroed once when they are allocated.  Grid-path calls with the counting-sort bookkeeping
+// use them alternately and need no memset of their own: k_bk_slots of call n clears the block call n + 1 will use (its
+// last users, the kernels of call n - 1, finished before call n started on the stream).  sc->ctr_cur is the block of
+// the last call (pcd_nn_last_stats reads it); every other path clears and uses that block with its own memset.
+// sc->ctr_next_clean is false from the start of a counting-sort call until all of its launches went through: a call
+// that failed part-way makes the next one fall back to the memset.
+static pcd_status counters_ready(QueryScratch* sc, hipStream_t s) {
+  if (sc->counters.p) return PCD_OK;
+  PCD_TRY(sc->counters.reserve(2));
+  PCD_HIP_TRY(hipMemsetAsync(sc->counters.p, 0, 2 * sizeof(NnCounters), s));
+  sc->ctr_cur = 0;
+  sc->ctr_next_clean = true;
+  return PCD_OK;
+}
+
+static void launch_prepare(int mode, const PrepArgs& pa, uint64_t Q, float4* qf4, uint64_t* d_keys, hipStream_t s) {
+  ScopedKernelTimer t("nn_prepare", s);
+  if (mode == kPrepBounded)
+    hipLaunchKernelGGL(k_prepare_bounded, dim3(div_up(Q, 256)), dim3(256), 0, s, pa.q, Q, pa.max_range, pa.mr_count,
+                       pa.fixed_range, qf4, d_keys);
+  else if (mode == kPrepRefine)
+    hipLaunchKernelGGL(k_prepare_refine, dim3(div_up(Q, 256)), dim3(256), 0, s, pa.q, Q, pa.skip, pa.box, qf4, d_keys);
+  else
+    hipLaunchKernelGGL(k_prepare_queries, dim3(div_up(Q, 256)), dim3(256), 0, s, pa.q, Q, qf4, d_keys);
+}
+
+// prep / pa: the call's prepare flavour.  The counting-sort bookkeeping does the preparation in its first kernel; the
+// radix-sort bookkeeping runs the stand-alone prepare kernel first.
 template <int G>
-static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t* d_keys, hipStream_t s, bool refine) {
+static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t* d_keys, hipStream_t s, int prep,
+                           const PrepArgs& pa) {
+  const bool refine = prep != kPrepPlain;   // incoming keys matter: carry them
   const GridParams& g = c->grid;
   // one snapshot of the tuning state for the whole call
   const int nn_kernel = g_nn_kernel.load(), bk_sort = g_bk_sort.load(), collect_stats = g_collect_stats.load();
@@ -1051,31 +1181,49 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
   PCD_TRY(sc->bk_vals.reserve(2 * Q));
   PCD_TRY(sc->bk_item.reserve(div_up(Q, kBkTile) + 1));
   PCD_TRY(sc->items.reserve(Q + 1));
-  PCD_TRY(sc->counters.reserve(1));
-  PCD_HIP_TRY(hipMemsetAsync(sc->counters.p, 0, sizeof(NnCounters), s));
+  PCD_TRY(counters_ready(sc, s));
   PCD_TRY(brick_slots(c, sc, b, s));
   // sort key = brick id: coarse key = id >> shift (at most 4096 buckets), fine key = the low bits (at most 4096)
   uint32_t shift = 8;
   while ((((uint64_t)b.nbricks + (1u << shift) - 1) >> shift) > 2304 && shift < 16) ++shift;
   const uint32_t ncoarse = std::max<uint32_t>(1u, (uint32_t)(((uint64_t)b.nbricks + (1u << shift) - 1) >> shift));
-  if ((1u << shift) <= kBkMaxFine && ncoarse <= kBkMaxCoarse && bk_sort == 0) {
+  const bool counting = (1u << shift) <= kBkMaxFine && ncoarse <= kBkMaxCoarse && bk_sort == 0;
+  NnCounters* ctr;
+  if (counting) {
+    const int use = 1 - sc->ctr_cur;
+    ctr = sc->counters.p + use;
+    if (!sc->ctr_next_clean) PCD_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(NnCounters), s));   // after a failed call
+    sc->ctr_next_clean = false;
+    sc->ctr_cur = use;
+  } else {
+    ctr = sc->counters.p + sc->ctr_cur;
+    PCD_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(NnCounters), s));
+    launch_prepare(prep, pa, Q, sc->qf4.p, d_keys, s);
+  }
+  if (counting) {
     ScopedKernelTimer t("nn_brick_bookkeeping", s);
-    if (!sc->bk_chist.p) {                 // histogram + cursors: zero once, k_bk_emit leaves them zero
-      PCD_TRY(sc->bk_chist.reserve(4 * (size_t)kBkMaxCoarse + 4));
-      PCD_HIP_TRY(hipMemsetAsync(sc->bk_chist.p, 0, (4 * (size_t)kBkMaxCoarse + 4) * sizeof(uint32_t), s));
-    }
-    uint32_t *chist = sc->bk_chist.p, *cstart = chist + kBkMaxCoarse + 1, *ccur = cstart + kBkMaxCoarse + 1,
-             *bitems = ccur + kBkMaxCoarse + 1;
-    uint32_t *qslot = sc->bk_keys.p, *pslot = sc->bk_keys.p + Q, *pqid = sc->bk_vals.p;
-    const unsigned sblocks = (unsigned)std::min<uint64_t>(div_up(Q, 4096), 256);
-    hipLaunchKernelGGL(k_bk_slots, dim3(sblocks), dim3(1024), 0, s, sc->qf4.p, (uint32_t)Q, g, b, sc->bk_slot.p, shift,
-                       ncoarse, qslot, chist, sc->fb_list.p, sc->counters.p);
-    hipLaunchKernelGGL(k_bk_scatter, dim3(div_up(Q, kBkTileQ)), dim3(1024), 0, s, qslot, (uint32_t)Q, shift, ncoarse, chist,
-                       cstart, ccur, pslot, pqid, sc->counters.p);
-    hipLaunchKernelGGL(k_bk_count<G>, dim3(ncoarse), dim3(256), 0, s, shift, cstart, pslot, bitems);
-    hipLaunchKernelGGL(k_bk_emit<G>, dim3(ncoarse), dim3(256), 0, s, sc->qf4.p, refine ? d_keys : (const uint64_t*)nullptr,
-                       g, b, shift, cstart, pslot, pqid, bitems, chist, ccur, sc->items.p, sc->qsorted.p, sc->ksorted.p,
-                       sc->counters.p);
+    // bucket totals | bucket starts | items per bucket; the histogram matrix [ranges][ncoarse] (<= 256 x 4096 entries);
+    // every entry that is read is written by the call itself: nothing to zero
+    const uint32_t nrounds = div_up(Q, kBkTileQ), rounds = div_up(nrounds, kBkMaxRanges), nranges = div_up(nrounds, rounds);
+    PCD_TRY(sc->bk_chist.reserve(3 * (size_t)kBkMaxCoarse + 3));
+    PCD_TRY(sc->bk_hmat.reserve((size_t)nranges * ncoarse));
+    uint32_t *ctot = sc->bk_chist.p, *cstart = ctot + kBkMaxCoarse + 1, *bitems = cstart + kBkMaxCoarse + 1;
+    uint32_t* qslot = sc->bk_keys.p;
+    uint2* ppair = reinterpret_cast<uint2*>(sc->bk_vals.p);   // 2 Q words: Q {fine key, query id} pairs
+    NnCounters* ctr_next = sc->counters.p + (1 - sc->ctr_cur);
+#define PCD_BK_SLOTS(MODE)                                                                                            \
+    hipLaunchKernelGGL(k_bk_slots<MODE>, dim3(nranges), dim3(1024), 0, s, pa, (uint32_t)Q, rounds, g, b, sc->bk_slot.p, \
+                       shift, ncoarse, sc->qf4.p, d_keys, qslot, sc->bk_hmat.p, sc->fb_list.p, ctr, ctr_next)
+    if (prep == kPrepBounded) PCD_BK_SLOTS(kPrepBounded);
+    else if (prep == kPrepRefine) PCD_BK_SLOTS(kPrepRefine);
+    else PCD_BK_SLOTS(kPrepPlain);
+#undef PCD_BK_SLOTS
+    hipLaunchKernelGGL(k_bk_colscan, dim3(div_up(ncoarse, 64)), dim3(1024), 0, s, sc->bk_hmat.p, nranges, ncoarse, ctot);
+    hipLaunchKernelGGL(k_bk_scatter, dim3(nranges), dim3(1024), 0, s, qslot, (uint32_t)Q, rounds, shift, ncoarse, ctot,
+                       sc->bk_hmat.p, cstart, ppair, ctr);
+    hipLaunchKernelGGL(k_bk_count<G>, dim3(ncoarse), dim3(256), 0, s, shift, cstart, ppair, bitems);
+    hipLaunchKernelGGL(k_bk_emit<G>, dim3(ncoarse), dim3(256), (3u * (1u << shift) + 2u) * sizeof(uint32_t), s, sc->qf4.p, refine ? d_keys : (const uint64_t*)nullptr,
+                       g, b, shift, cstart, ppair, bitems, sc->items.p, sc->qsorted.p, sc->ksorted.p, ctr);
   } else {
     // (grids with more than 8 M occupied bricks: the radix-sort bookkeeping of round 2)
     ScopedKernelTimer t("nn_brick_bookkeeping", s);
@@ -1097,7 +1245,7 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
     hipLaunchKernelGGL(k_brick_tile_count<G>, dim3(ntiles), dim3(256), 0, s, k1, (uint32_t)Q, b.nbricks, sc->bk_item.p);
     hipLaunchKernelGGL(k_brick_emit<G>, dim3(ntiles), dim3(256), 0, s, k1, v1, sc->bk_item.p, sc->qf4.p,
                        refine ? d_keys : (const uint64_t*)nullptr, (uint32_t)Q, b.nbricks, (uint32_t)b.nb[0],
-                       (uint32_t)b.nb[1], sc->items.p, sc->qsorted.p, sc->ksorted.p, sc->fb_list.p, sc->counters.p);
+                       (uint32_t)b.nb[1], sc->items.p, sc->qsorted.p, sc->ksorted.p, sc->fb_list.p, ctr);
   }
   {
     ScopedKernelTimer t("nn_brick", s);
@@ -1105,22 +1253,24 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
     if (clip) {
       const int fl = (collect_stats & ~2) | (nn_kernel == 1 ? 2 : 0);
       hipLaunchKernelGGL(k_nn_brick_clip, dim3(blocks), dim3(256), 0, s, g, c->sorted.p, c->cell_start.p, sc->qsorted.p,
-                         sc->ksorted.p, sc->items.p, sc->counters.p, d_keys, sc->fb_list.p, &sc->counters.p->fb_count, fl);
+                         sc->ksorted.p, sc->items.p, ctr, d_keys, sc->fb_list.p, &ctr->fb_count, fl);
     } else
       hipLaunchKernelGGL(k_nn_brick<G>, dim3(blocks), dim3(256), 0, s, g, b, c->sorted.p, c->cell_start.p,
-                         sc->qsorted.p, sc->ksorted.p, sc->items.p, sc->counters.p, d_keys, sc->fb_list.p,
-                         &sc->counters.p->fb_count, collect_stats);
+                         sc->qsorted.p, sc->ksorted.p, sc->items.p, ctr, d_keys, sc->fb_list.p,
+                         &ctr->fb_count, collect_stats);
   }
   {
     ScopedKernelTimer t("nn_fallback", s);
     PCD_TRY(sc->fb_dense.reserve(Q));
     hipLaunchKernelGGL(k_fb_compact, dim3(div_up(fb_cap, kFbcThreads * kFbcPer)), dim3(kFbcThreads), 0, s, sc->fb_list.p,
-                       &sc->counters.p->fb_count, sc->fb_dense.p, &sc->counters.p->pad[0]);
+                       &ctr->fb_count, sc->fb_dense.p, &ctr->pad[0]);
     const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(Q, 4), g_fb_max_blocks);
     hipLaunchKernelGGL(k_nn_fallback<0>, dim3(blocks), dim3(256), 0, s, g, c->pyr, c->sorted.p, c->cell_start.p,
-                       c->blk_aabb.p, sc->fb_seed.p, sc->qf4.p, sc->fb_dense.p, &sc->counters.p->pad[0], 0u, d_keys,
-                       sc->counters.p, collect_stats, FbFused{nullptr, nullptr, 0, 0.0});
+                       c->blk_aabb.p, sc->fb_seed.p, sc->qf4.p, sc->fb_dense.p, &ctr->pad[0], 0u, d_keys,
+                       ctr, collect_stats, FbFused{nullptr, nullptr, 0, 0.0});
   }
+  PCD_HIP_TRY(hipGetLastError());
+  if (counting) sc->ctr_next_clean = true;   // every launch went through: k_bk_slots has left the other block clean
   return PCD_OK;
 }
 
@@ -1143,34 +1293,31 @@ static pcd_status nn_device(pcd_cloud* c, const double* d_q, uint64_t Q, int alg
                           (algo == PCD_NN_FALLBACK_ONLY || (algo == PCD_NN_AUTO && Q <= kSmallBatch));
   if (c->m > 0 && algo != PCD_NN_BRUTEFORCE) PCD_TRY(fb_seed_table(c, sc, s));
   if (one_launch) {
-    PCD_TRY(sc->counters.reserve(1));
-    if (collect_stats) PCD_HIP_TRY(hipMemsetAsync(sc->counters.p, 0, sizeof(NnCounters), s));
+    PCD_TRY(counters_ready(sc, s));
+    NnCounters* ctr = sc->counters.p + sc->ctr_cur;
+    if (collect_stats) PCD_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(NnCounters), s));
     ScopedKernelTimer t("nn_fallback", s);
     const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(Q, 4), g_fb_max_blocks);
     const FbFused fu{d_q, bound ? bound->d_max_range : nullptr, bound ? bound->count : 0, bound ? bound->fixed : 0.0};
     if (bound)
       hipLaunchKernelGGL(k_nn_fallback<2>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
                          c->blk_aabb.p, sc->fb_seed.p, (const float4*)nullptr, (const uint32_t*)nullptr,
-                         (const uint32_t*)nullptr, (uint32_t)Q, d_keys, sc->counters.p, collect_stats, fu);
+                         (const uint32_t*)nullptr, (uint32_t)Q, d_keys, ctr, collect_stats, fu);
     else
       hipLaunchKernelGGL(k_nn_fallback<1>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
                          c->blk_aabb.p, sc->fb_seed.p, (const float4*)nullptr, (const uint32_t*)nullptr,
-                         (const uint32_t*)nullptr, (uint32_t)Q, d_keys, sc->counters.p, collect_stats, fu);
+                         (const uint32_t*)nullptr, (uint32_t)Q, d_keys, ctr, collect_stats, fu);
     PCD_HIP_TRY(hipGetLastError());
     return PCD_OK;
   }
   PCD_TRY(sc->qf4.reserve(Q));
-  {
-    ScopedKernelTimer t("nn_prepare", s);
-    if (bound)
-      hipLaunchKernelGGL(k_prepare_bounded, dim3(div_up(Q, 256)), dim3(256), 0, s, d_q, Q, bound->d_max_range,
-                         bound->count, bound->fixed, sc->qf4.p, d_keys);
-    else if (refine)
-      hipLaunchKernelGGL(k_prepare_refine, dim3(div_up(Q, 256)), dim3(256), 0, s, d_q, Q, d_skip, c->bb_lo[0],
-                         c->bb_lo[1], c->bb_lo[2], c->bb_hi[0], c->bb_hi[1], c->bb_hi[2], sc->qf4.p, d_keys);
-    else
-      hipLaunchKernelGGL(k_prepare_queries, dim3(div_up(Q, 256)), dim3(256), 0, s, d_q, Q, sc->qf4.p, d_keys);
-  }
+  const int prep = bound ? kPrepBounded : refine ? kPrepRefine : kPrepPlain;
+  const PrepArgs pa{d_q, d_skip, BoxF{c->bb_lo[0], c->bb_lo[1], c->bb_lo[2], c->bb_hi[0], c->bb_hi[1], c->bb_hi[2]},
+                    bound ? bound->d_max_range : nullptr, bound ? bound->count : 0, bound ? bound->fixed : 0.0};
+  const bool small = algo == PCD_NN_FALLBACK_ONLY || (algo == PCD_NN_AUTO && Q <= kSmallBatch);
+  // the grid path prepares the queries itself (run_grid); every other path starts with the stand-alone kernel
+  const bool grid = c->m > 0 && algo != PCD_NN_BRUTEFORCE && !small && (algo == PCD_NN_AUTO || algo == PCD_NN_GRID);
+  if (!grid) launch_prepare(prep, pa, Q, sc->qf4.p, d_keys, s);
   if (c->m > 0) {
     if (algo == PCD_NN_BRUTEFORCE) {
       ScopedKernelTimer t("nn_bruteforce", s);
@@ -1182,17 +1329,18 @@ static pcd_status nn_device(pcd_cloud* c, const double* d_q, uint64_t Q, int alg
       chunks = div_up(c->n, chunk);
       hipLaunchKernelGGL(k_nn_bruteforce, dim3(qblocks, chunks), dim3(256), 0, s, c->pts4.p, c->n, c->index_base,
                          c->index_stride, c->row_index.p, sc->qf4.p, Q, chunk, d_keys);
-    } else if (algo == PCD_NN_FALLBACK_ONLY || (algo == PCD_NN_AUTO && Q <= kSmallBatch)) {
+    } else if (small) {
       // (refining another shard's keys: the keys come in, so the prepare / finalize kernels stay)
-      PCD_TRY(sc->counters.reserve(1));
-      PCD_HIP_TRY(hipMemsetAsync(sc->counters.p, 0, sizeof(NnCounters), s));
+      PCD_TRY(counters_ready(sc, s));
+      NnCounters* ctr = sc->counters.p + sc->ctr_cur;
+      PCD_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(NnCounters), s));
       ScopedKernelTimer t("nn_fallback", s);
       const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(Q, 4), g_fb_max_blocks);
       hipLaunchKernelGGL(k_nn_fallback<0>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
                          c->blk_aabb.p, sc->fb_seed.p, sc->qf4.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)Q,
-                         d_keys, sc->counters.p, collect_stats, FbFused{nullptr, nullptr, 0, 0.0});
-    } else if (algo == PCD_NN_AUTO || algo == PCD_NN_GRID) {
-      PCD_TRY(run_grid<8>(c, sc, Q, d_keys, s, refine || bound != nullptr));   // incoming keys matter: carry them
+                         d_keys, ctr, collect_stats, FbFused{nullptr, nullptr, 0, 0.0});
+    } else if (grid) {
+      PCD_TRY(run_grid<8>(c, sc, Q, d_keys, s, prep, pa));
     } else {
       set_error("unknown nn algo %d", algo);
       return PCD_ERR_INVALID;
@@ -1277,7 +1425,7 @@ pcd_status pcd_nn_last_stats(pcd_cloud* c, pcd_nn_stats* st) {
   PCD_HIP_TRY(hipSetDevice(c->device));
   PCD_HIP_TRY(hipDeviceSynchronize());
   NnCounters h;
-  PCD_HIP_TRY(hipMemcpy(&h, c->scratch->counters.p, sizeof h, hipMemcpyDeviceToHost));
+  PCD_HIP_TRY(hipMemcpy(&h, c->scratch->counters.p + c->scratch->ctr_cur, sizeof h, hipMemcpyDeviceToHost));
   st->brick_groups = h.brick_groups;
   st->staged_points = h.staged_points;
   st->fallback_queries = h.fallback_queries;

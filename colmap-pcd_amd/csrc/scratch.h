@@ -21,7 +21,8 @@ struct QueryScratch {
   DevBuf<uint32_t> bk_item;            // work items per tile of 1024 sorted positions
   // counting-sort bookkeeping (nn.hip): slot of every brick with a non-empty halo region (kSlotNone otherwise), valid
   // for the brick geometry in bk_slot_key; per batch the slots' query counters, in-tile prefixes and tile totals
-  DevBuf<uint32_t> bk_slot, bk_chist;   // bk_chist: coarse histogram | bucket starts | bucket cursors
+  DevBuf<uint32_t> bk_slot, bk_chist;   // bk_chist: coarse bucket totals | bucket starts | items per bucket
+  DevBuf<uint32_t> bk_hmat;             // coarse histogram per range of queries: [ranges <= 256][buckets <= 4096], <= 4 MB
   int bk_slot_key[5] = {0, 0, 0, 0, 0};
   uint32_t bk_nslots = 0;
   DevBuf<float4> qsorted;      // brick-sorted query records {x,y,z,bits(query id)}
@@ -30,7 +31,9 @@ struct QueryScratch {
   DevBuf<uint32_t> fb_list, fb_dense;   // fallback list as the brick kernel fills it (chunked) / squeezed
   DevBuf<float4> fb_seed;      // k_nn_fallback's seed table, built on first use (nn.hip fb_seed_table)
   bool fb_seed_ok = false;
-  DevBuf<NnCounters> counters;
+  DevBuf<NnCounters> counters;   // two blocks, used alternately by the grid-path calls (nn.hip counters_ready)
+  int ctr_cur = 0;               // the block of the last call
+  bool ctr_next_clean = false;   // the other block is zero (or will be when the stream gets there)
   DevBuf<char> tmp;
   DevBuf<double> d_q;          // staging of host queries
   DevBuf<uint32_t> d_idx; DevBuf<float> d_sq; DevBuf<uint8_t> d_found;
