@@ -1,11 +1,11 @@
-// brick_clip_kernel.h -- the default first stage of the NN grid path (included by nn.hip behind brick_kernel.h).
+// brick_clip_kernel.h -- the first stage of the NN grid path (included by nn.hip behind brick_kernel.h).
 //
-// k_nn_brick (brick_kernel.h) compares every query of a brick with every point of the brick's 6x6x6-cell region:
-// 1 293 point-query pairs per query on workload M, 278 M staged points for a 10 M-point cloud.  Most of them cannot
-// matter: a query that sits on a sampled surface has its neighbour a few centimetres away, the region reaches 0.49 m.
-// This kernel keeps the brick kernel's machinery (one wavefront per work item of <= 8 queries of one brick, wave-uniform
-// queries, LDS-DMA tiles, FLANN's float arithmetic + v_min_f64 on the packed key, one transposed reduction per item)
-// and clips the region INSIDE the item, wave-uniformly:
+// Comparing every query of a brick with every point of the brick's 6x6x6-cell region (what this kernel does with the
+// clip switched off, pcd_nn_set_search(1)) costs 1 293 point-query pairs per query on workload M, 278 M staged points
+// for a 10 M-point cloud.  Most of them cannot matter: a query that sits on a sampled surface has its neighbour a few
+// centimetres away, the region reaches 0.49 m.  This kernel uses the machinery of brick_kernel.h (one wavefront per work
+// item of <= 8 queries of one brick, wave-uniform queries, LDS-DMA tiles, FLANN's float arithmetic + v_min_f64 on the
+// packed key, one transposed reduction per item) and clips the region INSIDE the item, wave-uniformly:
 //
 //   stage A   the brick's own 2x2x2 cells (one contiguous range of the centre quad row) are staged and compared,
 //             64 points per step; one reduction gives every query its tentative distance d_k (or the bound it came
@@ -18,8 +18,12 @@
 //             7 row + k holds cell_start at x boundary k of quad row `row` (63 loads in one instruction, prefetched
 //             an item ahead) -- so clipping costs no dependent memory access: v_readlane with a scalar lane index.
 //
+// A query is final when best < (distance to the region's boundary)^2 (proven_bound_f below, nn.hip header); the others
+// go to the exact fallback with their tentative key as starting bound.  Work items are software-pipelined: the item
+// record of item k+2 and the query / boundary-table loads of item k+1 are issued before item k is processed.
+//
 // Exactness.  Every point that is not compared lies (a) outside the region -- the region bound of nn.hip's header
-// decides as before whether the query is final -- or (b) inside the region but outside the box of every query's ball:
+// decides whether the query is final -- or (b) inside the region but outside the box of every query's ball:
 // then its float distance to query k exceeds d_k >= the final distance (strictly; an equal distance lies inside the
 // closed ball).  For (b): FLANN's sum is monotone in every term, so fl_dist(q, p) <= d implies fl((qx - px)^2) <= d,
 // i.e. |qx - px| <= sqrt(d) (1 + 2^-23); the radius is widened by 1e-5 relative, the box by 2e-7 relative outwards, and
@@ -69,10 +73,15 @@ __device__ __forceinline__ void compare_step(const f32x4 (&p)[2], const float (&
   }
 }
 
-// nn.hip proven_bound in float, rounded to the safe side: squared safe radius around q inside the cells [c0, c1); < 0:
-// nothing is proven.  The face positions and the differences carry at most 2 ulp of max(|face|, |q|) = 2.4e-7 max |coord|
-// of rounding, which a second grid.slack (9.6e-7 max(extent, |coord|)) covers; the square is shrunk by 1e-5 instead of
-// 1e-6.  The bound never exceeds the double one, so a query it proves is proven there as well.
+// The region bound of nn.hip's header: squared safe radius around q inside the cells [c0, c1), in float and rounded to
+// the safe side; faces on the grid boundary do not bound anything (no points beyond them).  < 0: nothing is proven.
+// Exactness.  Let m be the real distance from q to the nearest bounding face.  A point binned outside the range can lie
+// at most grid.slack inside it because of float rounding in the binning (grid.slack = 9.6e-7 max(extent, |coord|) >= 4
+// roundings of 2^-24), so its real distance to q is >= m - slack and its float distance >= (m - slack)^2 (1 - 2.4e-7).
+// The face positions and the differences computed here carry at most 2 ulp of max(|face|, |q|) = 2.4e-7 max |coord| of
+// rounding, which a second grid.slack covers: margin - 2 slack <= m - slack.  The square is shrunk by 1e-5: the 2.4e-7
+// above and the roundings of the two multiplications stay far below it.  So best < bound implies that no point outside
+// the range is as near as best.
 __device__ __forceinline__ float proven_bound_f(const GridParams& g, float qx, float qy, float qz, const int c0[3],
                                                 const int c1[3]) {
   const float q[3] = {qx, qy, qz};
@@ -101,7 +110,9 @@ __device__ __forceinline__ ClipMeta clip_load_meta(const GridParams& g, const ui
   const int lane = threadIdx.x & 63;
   const int lk = (int)(lpos & 0xFFu), lry = (int)((lpos >> 8) & 0xFFu), lrz = (int)(lpos >> 16);
   ClipMeta m;
-  // every lane issues every load (clamped indices, results masked afterwards): brick_kernel.h brick_load_meta
+  // Every lane issues every load (indices clamped, results masked afterwards): a load under a
+  // divergent `if` may be branched around, and then hipcc can no longer count the loads in flight and
+  // falls back to s_waitcnt vmcnt(0) at the first use -- which would serialise the prefetch.
   const int cnt = item_count(it);   // >= 1
   m.q = qsorted[it.x + (lane < cnt ? lane : cnt - 1)];
   m.prior = ksorted[it.x + (lane < cnt ? lane : cnt - 1)];
@@ -128,7 +139,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
   __shared__ __attribute__((aligned(16))) float4 s_tile[4][2][kTile];
   __shared__ __attribute__((aligned(16))) float4 s_a[4][kATile];
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform for the compiler too: LDS tile addresses and M0 values stay in SGPRs
   const uint32_t nitems = ctr->nitems;
   const uint32_t nwaves = gridDim.x * 4;
   unsigned long long st_staged = 0, st_pairs = 0, st_groups = 0;
@@ -144,7 +155,10 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
   // entry e of the table of item metadata m (e wave-uniform)
 #define PCD_BND(m, e) PCD_RL((m).bnd, (e))
 
-  // XCD-aware work split (brick_kernel.h): blocks b, b+8, ... walk their own contiguous eighth of the item list
+  // XCD-aware work split: blocks b, b+8, b+16, ... share an XCD (and its 4 MiB L2), so each of the 8
+  // block classes walks its own contiguous eighth of the item list (items are in brick order, x fastest):
+  // bricks that are neighbours in space -- and share most of their staged rows -- meet in one L2.
+  // (speed only: any mapping gives the same results.)
   uint32_t item, item_end, stride;
   if ((gridDim.x & 7u) == 0) {
     const uint32_t cls = blockIdx.x & 7u, per = (nitems + 7u) / 8u;
@@ -172,7 +186,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
     lds_dma16(reinterpret_cast<const float4*>(src_bytes + ((uint64_t)i1 << 4)), bufA + 64);
   };
 
-  uint4 it0 = items[PCD_UNI(item)];
+  uint4 it0 = items[PCD_UNI(item)];   // through uniform (scalar) indices: brick_kernel.h PCD_UNI
   ClipMeta m0 = clip_load_meta(g, it0, qsorted, ksorted, cell_start, lpos);
   uint4 it1 = items[PCD_UNI(min(item + stride, item_end - 1))];
   issue_a(m0);
@@ -186,7 +200,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
     const uint4 it2 = items[PCD_UNI(min(item + 2 * stride, item_end - 1))];
 
     const uint32_t cnt = (uint32_t)item_count(it0);
-    // The item's queries as wave-uniform values in VGPRs (an SGPR operand halves the VALU rate: brick_kernel.h).  Through
+    // The item's queries as wave-uniform values in VGPRs (an SGPR operand halves the VALU rate: brick_kernel.h PCD_CMP_PAIR).  Through
     // LDS: every lane writes its record (lanes >= cnt hold a copy of the last query) into the first tile buffer -- free
     // between two items' tiles -- and all lanes read the first 8 records back, 12 bytes each, same address for the whole
     // wavefront (a broadcast).  One ds_write_b128 + 8 ds_read_b96 on the LDS port instead of 24 v_readlane + 24 v_mov
@@ -287,6 +301,17 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
 #undef PCD_OR_SHR
     const uint32_t M[3] = {PCD_RL(w0, 7), PCD_RL(w1, 7), PCD_RL(w2, 7)};
     // ---- stage B ranges (all wave-uniform scalars): start and length of the 10 ranges -------------------------
+    // The concatenation of the ranges is addressed in GROUPS of 4 consecutive slots: every range is
+    // padded to a multiple of 4 slots (the <= 3 padding slots read the records that follow the range in memory:
+    // real cloud points of the neighbouring cells, harmless extra candidates; the `sorted` buffer ends with 4
+    // spare records), so the 4 slots of a group are 4 consecutive records.  Lane l of tile t takes group
+    // t * 64 + l: ONE source address per lane per tile, and the tile's 4 DMA instructions are that address +
+    // 0 / 16 / 32 / 48 bytes (instruction k fills LDS slot k * 64 + l -- a permutation of the tile, and the
+    // compare does not care about the order).  The range of a group is found with one compare + select per
+    // range start (the starts are wave-uniform): no per-window tables, no v_readlane inside the tile loop,
+    // any number of range starts inside a tile.  Round 1-2a computed an address per 64-slot DMA window (three
+    // v_readlane + ~10 VALU each, plus a generic path for windows with two starts); timing-only ablations put
+    // that address generation at 0.34 ms of the kernel's 0.84.
     uint32_t rs[kClipRanges], rl[kClipRanges];
 #pragma unroll
     for (int r = 0; r < kClipRows; ++r) {
@@ -313,6 +338,8 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
       uint32_t dv[kClipRanges];   // source - start deltas in VGPRs (v_cndmask cannot read an SGPR next to VCC)
 #pragma unroll
       for (int i = 0; i < kClipRanges; ++i) asm volatile("v_mov_b32 %0, %1" : "=v"(dv[i]) : "s"(rs[i] - ro[i]));
+      // issue the 4 DMAs of tile t (always exactly 4 instructions: groups past T re-read the last group, which
+      // cannot change a minimum -- the compare needs no tail mask)
       auto issue_tile = [&](int t) {
         float4* buf = s_tile[wave][t & 1];
         const uint32_t s4 = min((uint32_t)t * kTile + 4u * (uint32_t)lane, T - 4u);
@@ -323,9 +350,11 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
         PCD_SEL(ro[6], dv[6]); PCD_SEL(ro[7], dv[7]); PCD_SEL(ro[8], dv[8]); PCD_SEL(ro[9], dv[9]);
 #undef PCD_SEL
         }
+        // uniform base + byte offset (64-bit: a cloud may exceed 2^28 points = 4 GiB of records)
         const float4* gp = reinterpret_cast<const float4*>(src_bytes + ((uint64_t)(s4 + dl) << 4));
-        // (the instruction offset is added to the LDS address as well as to the source address: brick_kernel.h)
         if (flags & kAblateNoDma) { asm volatile("" ::"v"(gp)); return; }
+        // the instruction offset is added to the LDS address as well as to the source address
+        // (LDS address = M0 base + instruction offset + lane * 16): take it off the base again
         lds_dma16_off<0>(gp, buf);
         lds_dma16_off<16>(gp, buf + 64 - 1);
         lds_dma16_off<32>(gp, buf + 128 - 2);
@@ -349,6 +378,8 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           }
           __builtin_amdgcn_wave_barrier();
+          // The tile is read with inline-asm ds_read_b128: for an ordinary LDS load hipcc would insert
+          // s_waitcnt vmcnt(0) (it cannot tell the two buffers apart) and drain tile t+1's DMAs.
           f32x4 p[4];
           const uint32_t rd = lds_addr(s_tile[wave][t & 1]) + lane * 16;
           if (flags & kAblateNoLdsRead) {
@@ -396,7 +427,11 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
       keys[my_qi] = unproven ? mine : finalized_key(mine);   // final, or the starting bound of the exact fallback
     }
     const unsigned long long um = __ballot(unproven);
-    if (um) {   // chunked fallback list: brick_kernel.h
+    if (um) {
+      // the wavefront appends to the fallback list inside chunks of kFbChunk slots it reserves with ONE returning
+      // atomic each (an atomic per item exposed its latency on every fourth item); the slots of a chunk it does not
+      // use get 0xFFFFFFFF when the chunk is left (here and at the end of the kernel): the list needs no memset;
+      // k_fb_compact squeezes the sentinels out
       const uint32_t k = (uint32_t)__popcll(um);
       if (k > fb_left) {
         if (lane < (int)fb_left) fb_list[fb_base + lane] = 0xFFFFFFFFu;
@@ -416,7 +451,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
     it0 = it1; it1 = it2; m0 = m1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last (redundant) stage-A prefetch must not outlive the wavefront's LDS
-  if (lane < (int)fb_left) fb_list[fb_base + lane] = 0xFFFFFFFFu;
+  if (lane < (int)fb_left) fb_list[fb_base + lane] = 0xFFFFFFFFu;   // rest of the last chunk
   if (collect_stats && lane == 0) {
     atomicAdd(&ctr->staged_points, st_staged);
     atomicAdd(&ctr->pair_evals, st_pairs);

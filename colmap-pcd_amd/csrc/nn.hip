@@ -12,13 +12,15 @@
 // Three kernels, all with lanes = cloud points and wave-uniform queries, each
 // finishing with a per-wavefront min-reduction of packed keys:
 //   k_nn_bruteforce  all pairs; LDS-tiled; reference for the other two.
-//   k_nn_brick       one wavefront per group of <= G queries that fall into
-//                    the same brick of B^3 grid cells: the cell rows of the
-//                    brick grown by R cells are streamed through an LDS tile
+//   k_nn_brick_clip  one wavefront per group of <= G queries that fall into
+//                    the same brick of 2^3 grid cells: the brick's own cells, then
+//                    the parts of the cell rows of the brick grown by 2 cells that
+//                    the queries' balls touch are streamed through LDS tiles
 //                    (16-B records, coalesced row ranges) and every query of
 //                    the group is compared with every staged point.  A query
 //                    is final when its best distance is provably smaller than
-//                    its distance to the boundary of the staged region.
+//                    its distance to the boundary of the region
+//                    (brick_clip_kernel.h; the shared machinery: brick_kernel.h).
 //   k_nn_fallback    one wavefront per remaining query: depth-first, nearest-first
 //                    descent of the 64-ary pyramid of tight AABBs over the grid
 //                    (level 0 = leaves of 2x2x2 cells, one contiguous point range each;
@@ -27,11 +29,12 @@
 //                    lower bound.  Exact for any query position, also outside the grid.  The walk starts
 //                    from min(incoming key, key of the query's SEED): the exact nearest cloud point of the centre
 //                    of the query's 8x8x8-cell cube (a table built once per cloud, fb_seed_table).
-// Query bookkeeping in front of k_nn_brick: a two-level counting sort on the brick id
+// Query bookkeeping in front of k_nn_brick_clip: a two-level counting sort on the brick id
 // (k_bk_slots, k_bk_colscan, k_bk_scatter, k_bk_count, k_bk_emit) that starts from the
 // caller's double queries and yields the float records, the initial keys, the brick-sorted
 // query records and the work items; queries with no cloud point in their brick's halo go
-// straight to the fallback list.
+// straight to the fallback list.  Grids beyond the counting sort's limits take a radix sort
+// on the brick id instead (k_brick_keys, rocPRIM, k_brick_tile_count, k_brick_emit).
 //
 // Exactness of the pruning (float distances, not real ones):
 //   * AABB bound: lb = l2_simple3(q, clamp(q, lo, hi)) with lo/hi the actual
@@ -40,11 +43,13 @@
 //     lb > best (strictly: an equal-distance point with a lower index may hide
 //     in it).
 //   * region bound: margin = min distance from q to the faces of the
-//     staged cell range (double).  A point binned outside the range can lie at
+//     brick's cell range (float).  A point binned outside the range can lie at
 //     most `slack` inside it because of float rounding in the binning
 //     (grid.slack = 9.6e-7 * max(extent, |coord|) >= 4 roundings of 2^-24),
-//     and its float distance is >= true^2 * (1 - 2.4e-7).  A result is final
-//     iff best < (margin - slack)^2 * (1 - 1e-6), margin > slack.
+//     and its float distance is >= true^2 * (1 - 2.4e-7); a second slack covers
+//     the rounding of the margin itself.  A result is final
+//     iff best < (margin - 2 slack)^2 * (1 - 1e-5), margin > 2 slack
+//     (brick_clip_kernel.h proven_bound_f).
 //   * seed: the seed is a point of this cloud and its key is computed with the walk's own arithmetic
 //     (l2_simple3 on the float query, make_key with the point's global index), so min(best, seed key) is the key
 //     of a real candidate -- exactly what a leaf scan that met the point would have left.  The walk's pruning only
@@ -67,7 +72,6 @@ namespace pcd {
 void free_query_scratch(QueryScratch* s) { delete s; }
 
 constexpr uint64_t kKeyInit = (uint64_t)0x7F7FFFFFu << 32;  // (FLT_MAX, idx 0): nothing with d >= FLT_MAX beats it
-constexpr int kMaxRows = 64;                                // rows of a brick region (one per lane)
 // Batches up to this size skip the grid path (query sort + brick kernel + fallback = 13 launches) and go
 // straight to the per-wavefront hierarchical search, one launch: measured on a 2 M-point cloud
 // (tools/nn_latency.py), 20 k queries take 99 us that way against 190 us, 100 k queries 290 against 329.
@@ -81,12 +85,18 @@ struct BrickParams {
   uint32_t nbricks;
 };
 
-static BrickParams make_bricks(const GridParams& g, int B, int Bx, int R) {
+// The geometry k_nn_brick_clip is written for.  Others were measured and not adopted: x-long bricks (Bx = 2B, 3B, 4B:
+// fewer, fuller groups but a longer region per query) on workload M 0.638 / 0.698 / 0.768 ms against 0.633 ms for
+// cubes (profiles/r02_nn_config_sweeps.txt); x-long bricks of 3 and 4 cells with the in-kernel clip 0.529 / 0.551 ms
+// against 0.509 (profiles/r04_nn_experiments.txt).
+constexpr int kBrickCells = 2, kBrickCellsX = 2, kBrickHalo = 2;
+
+static BrickParams make_bricks(const GridParams& g) {
   BrickParams b;
-  b.B = B; b.R = R; b.Bx = Bx;
+  b.B = kBrickCells; b.R = kBrickHalo; b.Bx = kBrickCellsX;
   uint64_t n = 1;
   for (int d = 0; d < 3; ++d) {
-    const int e = d == 0 ? Bx : B;
+    const int e = d == 0 ? b.Bx : b.B;
     b.nb[d] = (g.dims[d] + e - 1) / e;
     n *= (uint64_t)b.nb[d];
   }
@@ -447,7 +457,7 @@ __global__ __launch_bounds__(256) void k_brick_emit(const uint32_t* __restrict__
 //                 with one returning LDS atomic and is written as ONE 8-byte {fine key, query id} pair.
 //   k_bk_count    one workgroup per coarse bucket: queries per FINE key (low bits) in LDS -> the bucket's item count.
 //   k_bk_emit     one workgroup per coarse bucket: the same counting sort again, now with the item base known (sum
-//                 of the item counts to the left: items stay in brick order, which the XCD-aware walk of k_nn_brick
+//                 of the item counts to the left: items stay in brick order, which the XCD-aware walk of k_nn_brick_clip
 //                 is worth 0.04 ms for), then the brick-sorted query records, their incoming keys and the work
 //                 items (G queries of one brick each).  LDS sized by the call's fine keys (dynamic), a thread's first
 //                 two pairs kept in registers between the two passes.
@@ -465,7 +475,7 @@ constexpr uint32_t kSlotSkip = 0xFFFFFFFFu;       // query: not finite
 constexpr uint32_t kBkMaxRanges = 256;   // workgroups of k_bk_slots / k_bk_scatter: rows of the histogram matrix
 constexpr uint32_t kBkMaxCoarse = 4096, kBkMaxFine = 4096, kBkTileQ = 4096;   // 2^24 bricks: every grid of the 2^26-cell budget
 
-// one thread per brick: does the halo region (whole quad rows, as brick_load_meta walks them) hold any point?
+// one thread per brick: does the halo region (whole quad rows, as the brick kernel's boundary table has them) hold any point?
 __global__ void k_brick_occupied(GridParams g, BrickParams b, const uint32_t* __restrict__ cell_start,
                                  uint32_t* __restrict__ flag) {
   const uint32_t bid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -673,7 +683,7 @@ __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4,
   const uint32_t nfine = 1u << shift, mask = nfine - 1u;
   uint32_t *s_off = s_dyn, *s_ioff = s_off + nfine + 1, *s_cur = s_ioff + nfine + 1;
   const uint32_t beg = cstart[blockIdx.x], end = cstart[blockIdx.x + 1];
-  // item base = items of all buckets to the left, in bucket order = brick order (the XCD-aware walk of k_nn_brick
+  // item base = items of all buckets to the left, in bucket order = brick order (the XCD-aware walk of k_nn_brick_clip
   // depends on it): summed from k_bk_count's per-bucket totals -- no atomics, no waiting on other workgroups
   uint32_t acc = 0;
   for (uint32_t c = threadIdx.x; c < blockIdx.x; c += 256) acc += bitems[c];
@@ -738,33 +748,6 @@ __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4,
 }
 
 // ------------------------------------------------------------ brick kernel ---
-// wave-uniform copy of lane l's value (lands in an SGPR)
-__device__ __forceinline__ float readlane_f(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ uint32_t wave_excl_scan_u32(uint32_t v, uint32_t& total) {
-  const uint32_t inc = wave_scan_add_u32(v);
-  total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-  return inc - v;
-}
-
-// squared safe radius (double) around q inside the cell range [c0,c1) per axis; faces on the
-// grid boundary do not bound anything (no points beyond them). Returns < 0 when nothing is proven.
-__device__ __forceinline__ double proven_bound(const GridParams& g, float qx, float qy, float qz, const int c0[3],
-                                               const int c1[3]) {
-  const double q[3] = {(double)qx, (double)qy, (double)qz};
-  double margin = 1e300;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    if (c0[d] > 0) margin = fmin(margin, q[d] - ((double)g.origin[d] + (double)c0[d] * (double)g.h));
-    if (c1[d] < g.dims[d]) margin = fmin(margin, ((double)g.origin[d] + (double)c1[d] * (double)g.h) - q[d]);
-  }
-  if (margin >= 1e300) return 1e300;  // the range covers the whole grid
-  margin -= (double)g.slack;
-  if (!(margin > 0.0)) return -1.0;
-  return margin * margin * (1.0 - 1e-6);
-}
-
 }  // namespace pcd
 #include "brick_kernel.h"
 #include "brick_clip_kernel.h"
@@ -1046,34 +1029,30 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
 // the hardware's workgroup dispatch as the load balancer (query costs spread 1:4).  2048 / 4096 / 16384 / 65536
 // workgroups: 0.384 / 0.387 / 0.368 / 0.369 ms at workload M, 0.136 / 0.125 / 0.126 / 0.125 ms on an eighth of it.
 constexpr unsigned g_fb_max_blocks = 16384;
-// process-global tuning state (pcd_nn_set_*: experiments and tests, not part of the stable ABI): atomics, and every call
-// works on ONE snapshot taken at its top, so a setter racing a search on another thread cannot pair the slot bitmap of
-// one brick geometry with the kernel of another
-static std::atomic<int> g_brick_B{2}, g_brick_R{2}, g_collect_stats{0};
+// process-global tuning state (pcd_nn_set_*: experiments and tests, not part of the stable ABI): independent atomic
+// switches, each read once at the top of a call
+static std::atomic<int> g_collect_stats{0};
 #ifdef PCD_ABLATE   // occupancy experiments (tools/nn_ablate.py): workgroups of the brick kernels per CU
 static const int g_brick_blocks_per_cu = std::getenv("PCD_BRICK_BLOCKS") ? std::atoi(std::getenv("PCD_BRICK_BLOCKS")) : PCD_BRICK_MINWAVES;
 #else
 constexpr int g_brick_blocks_per_cu = PCD_BRICK_MINWAVES;
 #endif
-// first stage of the grid path: 0 = the clipped brick kernel (brick_clip_kernel.h; needs the default brick geometry
-// B = R = 2), 1 = the same kernel with the clip switched off (A/B timing: it then stages the whole region like
-// round 3's kernel), 2 = round 3's brick kernel (brick_kernel.h; also what other brick geometries run on).
+// first stage of the grid path: 0 = the clipped brick kernel (brick_clip_kernel.h), 1 = the same kernel with the clip
+// switched off (A/B timing and tests: it then stages the whole region; results identical)
 static std::atomic<int> g_nn_kernel{0};
 
 static std::atomic<int> g_bk_sort{0};   // 1: force the radix-sort bookkeeping (A/B timing, tests)
 
-// slot table of the cloud for this brick geometry (built on first use, rebuilt when the geometry changes)
+// slot table of the cloud (built on first use)
 static pcd_status brick_slots(pcd_cloud* c, QueryScratch* sc, const BrickParams& b, hipStream_t s) {
-  const int key[5] = {b.B, b.R, 0, b.Bx, (int)b.nbricks};
-  if (sc->bk_slot.p && std::memcmp(key, sc->bk_slot_key, sizeof key) == 0) return PCD_OK;
+  if (sc->bk_slot.p && sc->bk_nslots == b.nbricks) return PCD_OK;
   PCD_TRY(sc->bk_slot.reserve((size_t)b.nbricks / 32 + 1));
   DevBuf<uint32_t> flag;
   PCD_TRY(flag.reserve((size_t)b.nbricks + 1));
   hipLaunchKernelGGL(k_brick_occupied, dim3(div_up(b.nbricks, 256)), dim3(256), 0, s, c->grid, b, c->cell_start.p, flag.p);
   hipLaunchKernelGGL(k_brick_bitmap, dim3(div_up(div_up(b.nbricks, 32), 256)), dim3(256), 0, s, flag.p, b.nbricks, sc->bk_slot.p);
-  PCD_HIP_TRY(hipStreamSynchronize(s));   // one-off per cloud and geometry; `flag` goes out of scope
+  PCD_HIP_TRY(hipStreamSynchronize(s));   // one-off per cloud; `flag` goes out of scope
   sc->bk_nslots = b.nbricks;
-  std::memcpy(sc->bk_slot_key, key, sizeof key);
   return PCD_OK;
 }
 
@@ -1160,15 +1139,8 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
                            const PrepArgs& pa) {
   const bool refine = prep != kPrepPlain;   // incoming keys matter: carry them
   const GridParams& g = c->grid;
-  // one snapshot of the tuning state for the whole call
   const int nn_kernel = g_nn_kernel.load(), bk_sort = g_bk_sort.load(), collect_stats = g_collect_stats.load();
-  int B = g_brick_B.load(), R = g_brick_R.load();
-  if ((B + 2 * R) * (B + 2 * R) > kMaxRows) { B = 2; R = 2; }
-  // x-long bricks (Bx = 2B, 3B, 4B: fewer, fuller groups but a longer region per query) were measured on workload M:
-  // 0.638 / 0.698 / 0.768 ms against 0.633 ms for cubes (profiles/r02_nn_config_sweeps.txt)
-  // x-long bricks (3, 4 cells): with the in-kernel clip 0.529 / 0.551 ms against 0.509 (profiles/r04_nn_experiments.txt)
-  const bool clip = nn_kernel != 2 && B == 2 && R == 2;   // other geometries run on round 3's kernel
-  const BrickParams b = make_bricks(g, B, B, R);
+  const BrickParams b = make_bricks(g);
   PCD_TRY(sc->qsorted.reserve(Q));
   PCD_TRY(sc->ksorted.reserve(Q));
   // fallback list: one slot per query + the chunk slack of every wavefront of the brick kernel (brick_kernel.h)
@@ -1250,14 +1222,9 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
   {
     ScopedKernelTimer t("nn_brick", s);
     const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(div_up(Q, G), 4) + 1, 256 * (uint64_t)g_brick_blocks_per_cu);
-    if (clip) {
-      const int fl = (collect_stats & ~2) | (nn_kernel == 1 ? 2 : 0);
-      hipLaunchKernelGGL(k_nn_brick_clip, dim3(blocks), dim3(256), 0, s, g, c->sorted.p, c->cell_start.p, sc->qsorted.p,
-                         sc->ksorted.p, sc->items.p, ctr, d_keys, sc->fb_list.p, &ctr->fb_count, fl);
-    } else
-      hipLaunchKernelGGL(k_nn_brick<G>, dim3(blocks), dim3(256), 0, s, g, b, c->sorted.p, c->cell_start.p,
-                         sc->qsorted.p, sc->ksorted.p, sc->items.p, ctr, d_keys, sc->fb_list.p,
-                         &ctr->fb_count, collect_stats);
+    const int fl = (collect_stats & ~2) | (nn_kernel == 1 ? 2 : 0);
+    hipLaunchKernelGGL(k_nn_brick_clip, dim3(blocks), dim3(256), 0, s, g, c->sorted.p, c->cell_start.p, sc->qsorted.p,
+                       sc->ksorted.p, sc->items.p, ctr, d_keys, sc->fb_list.p, &ctr->fb_count, fl);
   }
   {
     ScopedKernelTimer t("nn_fallback", s);
@@ -1442,7 +1409,8 @@ pcd_status pcd_nn_last_stats(pcd_cloud* c, pcd_nn_stats* st) {
 /* tuning hook: which kernel serves the grid path's first stage (g_nn_kernel above).  Negative: leave it as it is. */
 pcd_status pcd_nn_set_search(int kernel) {
   if (kernel < 0) return PCD_OK;
-  PCD_REQUIRE(kernel <= 2, "kernel must be 0 (clipped brick kernel), 1 (the same, clip off) or 2 (round 3's brick kernel)");
+  PCD_REQUIRE(kernel <= 1, "kernel must be 0 (clipped brick kernel) or 1 (the same with the clip off); there is no separate "
+                           "whole-region kernel: the clip-off switch, pcd_nn_set_search(1), is the A/B reference");
   g_nn_kernel = kernel;
   return PCD_OK;
 }
@@ -1452,10 +1420,14 @@ pcd_status pcd_nn_set_bookkeeping(int radix_sort) {
   return PCD_OK;
 }
 
-/* tuning hooks (not part of the stable ABI; used by bench.py and tests) */
+/* tuning hook (not part of the stable ABI; used by bench.py and tests): the statistics switch.  The brick geometry is
+   fixed (kBrickCells / kBrickHalo); brick_cells = 0 and halo_cells < 0 mean "as it is".  A refused call changes nothing. */
 pcd_status pcd_nn_set_tuning(int brick_cells, int halo_cells, int collect_stats) {
-  if (brick_cells > 0) g_brick_B = brick_cells;
-  if (halo_cells >= 0) g_brick_R = halo_cells;
+  if ((brick_cells != 0 && brick_cells != kBrickCells) || (halo_cells >= 0 && halo_cells != kBrickHalo)) {
+    set_error("pcd_nn_set_tuning: the brick geometry is fixed at %d cells with a halo of %d (asked for %d / %d)",
+              kBrickCells, kBrickHalo, brick_cells, halo_cells);
+    return PCD_ERR_UNSUPPORTED;
+  }
 #ifdef PCD_ABLATE
   g_collect_stats = collect_stats;
 #else

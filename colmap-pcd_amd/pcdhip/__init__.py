@@ -835,11 +835,13 @@ def search_range_schedule(opt_num, kd_max=1.5, kd_min=0.2, drop=0.1):
 
 
 def set_nn_tuning(brick_cells=0, halo_cells=-1, collect_stats=0):
-    lib().pcd_nn_set_tuning(int(brick_cells), int(halo_cells), int(collect_stats))
+    """statistics switch of the grid path; the brick geometry is fixed at 2 / 2 (0 / -1 = leave it), others are refused"""
+    _check(lib().pcd_nn_set_tuning(int(brick_cells), int(halo_cells), int(collect_stats)))
 
 
 def set_nn_search(kernel=0):
-    """first stage of the grid path: 0 = clipped brick kernel (default), 1 = the same with the clip off, 2 = round 3's kernel"""
+    """first stage of the grid path: 0 = clipped brick kernel (default), 1 = the same with the clip off (stages the whole
+    region: the A/B reference)"""
     _check(lib().pcd_nn_set_search(int(kernel)))
 
 

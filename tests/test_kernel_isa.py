@@ -54,40 +54,37 @@ def test_no_fused_multiply_add_in_the_distance_kernels(nn_isa):
 
 def test_brick_kernels_resources(nn_isa):
     meta, body = _kernels(nn_isa)
-    clip = _find(meta, "k_nn_brick_clip")[0]
-    old = _find(meta, "k_nn_brickILi8")[0]
-    for k, lds in ((clip, 4 * 2 * 256 * 16 + 4 * 128 * 16), (old, 4 * 2 * 256 * 16)):   # tiles (+ the stage-A buffer)
-        m = meta[k]
-        assert m["vgpr"] <= 128, (k, m)              # 4 wavefronts per SIMD
-        assert m["scratch"] == 0, (k, m)             # no spills: the tile loops count their VMEM operations by hand
-        assert m["lds"] == lds, (k, m)               # 4 workgroups per CU
-        assert "scratch_" not in body[k], k
+    k = _find(meta, "k_nn_brick_clip")[0]
+    m = meta[k]
+    assert m["vgpr"] <= 128, (k, m)                  # 4 wavefronts per SIMD
+    assert m["scratch"] == 0, (k, m)                 # no spills: the tile loops count their VMEM operations by hand
+    assert m["lds"] == 4 * 2 * 256 * 16 + 4 * 128 * 16, (k, m)   # tiles + the stage-A buffer: 4 workgroups per CU
+    assert "scratch_" not in body[k], k
     # the fallback walk keeps 8 wavefronts per SIMD
     for k in _find(meta, "k_nn_fallback"):
         assert meta[k]["vgpr"] <= 64 and meta[k]["scratch"] == 0, (k, meta[k])
 
 
 def test_tile_loop_has_only_its_own_vmem_operations(nn_isa):
-    """between a tile's LDS-DMA instructions and the counted wait that covers them the kernels may issue no other
+    """between a tile's LDS-DMA instructions and the counted wait that covers them the kernel may issue no other
     vector-memory instruction than LDS-DMA: `s_waitcnt vmcnt(4)` means "all but the 4 DMAs of the next tile" """
     meta, body = _kernels(nn_isa)
-    for part in ("k_nn_brick_clip", "k_nn_brickILi8"):
-        k = _find(body, part)[0]
-        lines = body[k].split("\n")
-        waits = [i for i, ln in enumerate(lines) if "s_waitcnt vmcnt(4)" in ln]
-        assert waits, k
-        for w in waits:
-            # walk back over the 4 DMA instructions of the tile in flight; everything between them and the wait
-            seen, j = 0, w - 1
-            while j >= 0 and seen < 4:
-                ln = lines[j].strip()
-                if ln.startswith("global_load_lds_dwordx4"):
-                    seen += 1
-                elif re.match(r"(global|buffer|flat|scratch)_(load|store|atomic)", ln):
-                    raise AssertionError(f"{k}: `{ln}` between a tile's DMAs and its counted wait (line {j})")
-                elif re.match(r"\.LBB|s_cbranch|s_branch", ln):
-                    break      # left the basic block: the tile was issued in the predecessor
-                j -= 1
+    k = _find(body, "k_nn_brick_clip")[0]
+    lines = body[k].split("\n")
+    waits = [i for i, ln in enumerate(lines) if "s_waitcnt vmcnt(4)" in ln]
+    assert waits, k
+    for w in waits:
+        # walk back over the 4 DMA instructions of the tile in flight; everything between them and the wait
+        seen, j = 0, w - 1
+        while j >= 0 and seen < 4:
+            ln = lines[j].strip()
+            if ln.startswith("global_load_lds_dwordx4"):
+                seen += 1
+            elif re.match(r"(global|buffer|flat|scratch)_(load|store|atomic)", ln):
+                raise AssertionError(f"{k}: `{ln}` between a tile's DMAs and its counted wait (line {j})")
+            elif re.match(r"\.LBB|s_cbranch|s_branch", ln):
+                break      # left the basic block: the tile was issued in the predecessor
+            j -= 1
 
 
 @pytest.fixture(scope="module")

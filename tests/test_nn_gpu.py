@@ -342,11 +342,11 @@ def _hard_cases():
     return cases
 
 
-@pytest.mark.parametrize("kernel", [0, 1, 2])
+@pytest.mark.parametrize("kernel", [0, 1])
 def test_brick_kernel_variants(gpu, oracle, kernel):
     """First stage of the grid path: 0 = the clipped brick kernel (csrc/brick_clip_kernel.h: the brick's own cells first,
-    then only the quad-row parts the queries' balls touch), 1 = the same kernel with the clip switched off, 2 = round
-    3's whole-region kernel.  All three must give the oracle's keys bit for bit -- on a surface cloud, on exact ties
+    then only the quad-row parts the queries' balls touch), 1 = the same kernel with the clip switched off (it stages
+    the whole region).  Both must give the oracle's keys bit for bit -- on a surface cloud, on exact ties
     (duplicates, lattice midpoints), on a cell far denser than stage A's 128 points, on a thin sheet, with near and far
     queries, on several cell sizes (regions that leave the grid on every side)."""
     rng = np.random.default_rng(32)
@@ -365,18 +365,27 @@ def test_brick_kernel_variants(gpu, oracle, kernel):
         gpu.set_nn_search(0)
 
 
-@pytest.mark.parametrize("br", [(2, 1), (4, 1), (3, 2)])
-def test_other_brick_geometries(gpu, oracle, br):
-    """brick edges / halos other than the default 2 / 2 run on round 3's kernel (pcd_nn_set_tuning): still exact"""
+def test_brick_geometry_is_fixed(gpu, oracle):
+    """bricks are 2 cells wide with a halo of 2: pcd_nn_set_tuning refuses every other geometry and pcd_nn_set_search the
+    retired whole-region kernel, and a refused call changes nothing -- the search afterwards is still exact"""
     xyz, nrm = _clouds()["planes"]
     q = synth.queries(xyz, 6000, seed=9, sigma=0.3)
     try:
-        gpu.set_nn_tuning(br[0], br[1], 0)
+        for br in ((2, 1), (4, 1), (3, 2)):
+            with pytest.raises(gpu.PcdError) as e:
+                gpu.set_nn_tuning(br[0], br[1], 1)
+            assert e.value.status == gpu.PCD_ERR_UNSUPPORTED, br
+        with pytest.raises(gpu.PcdError) as e:
+            gpu.set_nn_search(2)
+        assert e.value.status == gpu.PCD_ERR_INVALID
+        gpu.set_nn_tuning(2, 2, 0)
+        gpu.set_nn_tuning(0, -1, 0)
         c = gpu.Cloud(xyz, nrm, raw_lidar_frame=False)
-        _check_exact(c.nn(q, gpu.NN_GRID), oracle.nn_bruteforce(xyz, q), f"brick{br}")
+        _check_exact(c.nn(q, gpu.NN_GRID), oracle.nn_bruteforce(xyz, q), "after the refused calls")
         c.close()
     finally:
         gpu.set_nn_tuning(2, 2, 0)
+        gpu.set_nn_search(0)
 
 
 def test_clip_with_incoming_bounds(gpu, oracle):

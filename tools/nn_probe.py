@@ -13,7 +13,9 @@ B = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 R = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 cell = float(sys.argv[5]) if len(sys.argv) > 5 else 0.0
 outl = float(sys.argv[6]) if len(sys.argv) > 6 else 0.05
-kern = int(os.environ.get("PCD_PROBE_KERNEL", "0"))   # pcd_nn_set_search: 0 clipped brick kernel, 1 clip off, 2 round 3's kernel
+kern = int(os.environ.get("PCD_PROBE_KERNEL", "0"))   # pcd_nn_set_search: 0 clipped brick kernel, 1 clip off
+if kern not in (0, 1): sys.exit("PCD_PROBE_KERNEL must be 0 or 1")
+if (B, R) != (2, 2): sys.exit("the brick geometry is fixed: B R must be 2 2")
 pcdhip.set_nn_search(kern)
 print("first-stage kernel", kern, flush=True)
 t = time.time(); xyz, nrm = synth.cloud_planes(N); q = synth.queries(xyz, Q, outlier_frac=outl, sigma=float(os.environ.get("PCD_PROBE_SIGMA", "0.25"))); print("gen %.1fs" % (time.time() - t), flush=True)
