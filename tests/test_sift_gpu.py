@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import sift_edge_ref as er
 from tests.test_sift_cpu import sift_reference_cases
+from tests.test_sift_edge_gpu import _device as device_match
 
 pytestmark = pytest.mark.gpu
 
@@ -75,6 +77,21 @@ def test_long_walks_with_ties(gpu, oracle, nchunk, sift_tuning):
     res = gpu.sift_match_batch([d1, d2], pairs, max_ratio=1.0, max_distance=3.2, cross_check=True)
     assert np.array_equal(res[0], oracle.sift_match(d1, d2, max_ratio=1.0, max_distance=3.2, cross_check=True)[0])
     assert np.array_equal(res[1], oracle.sift_match(d2, d1, max_ratio=1.0, max_distance=3.2, cross_check=True)[0])
+    # The inputs above cannot show a tie: at max_ratio <= 1 a tied row is rejected whichever column won, and nearly all
+    # of their scores clamp (every expected list is empty).  Beside them: tied sets below the clamp under a ratio above
+    # 1, where a tied row passes and reports WHICH of the equal columns the merges kept; one-way results compared too.
+    t1, t2 = er.tied_sets(n1, n2)
+    for a, b in ((t1, t2), (t2, t1)):
+        for cross in (True, False):
+            exp = oracle.sift_match(a, b, cross_check=cross, **er.RATIO_PROBE)
+            assert len(exp[0]) == (6 if cross else (exp[1] != -1).sum()) and (exp[1] != -1).sum() >= 600
+            assert (exp[2] != -1).sum() >= 600
+            got = device_match(gpu, a, b, cross_check=cross, **er.RATIO_PROBE)
+            for g, e in zip(got, exp):
+                assert np.array_equal(g, e), (nchunk, cross, len(a))
+    res = gpu.sift_match_batch([t1, t2], pairs, cross_check=False, **er.RATIO_PROBE)
+    assert len(res[0]) == n1 - 1 and np.array_equal(res[0], oracle.sift_match(t1, t2, cross_check=False, **er.RATIO_PROBE)[0])
+    assert len(res[1]) == n2 and np.array_equal(res[1], oracle.sift_match(t2, t1, cross_check=False, **er.RATIO_PROBE)[0])
 
 
 def test_one_way_results_and_asymmetric_layout_check(gpu, oracle):

@@ -6,7 +6,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import sift_edge_ref as er
 from tests import sift_guided_ref as ref
+from tests.test_sift_edge_gpu import _device as device_match
 from tests.test_sift_guided_cpu import I3, kat_case
 
 pytestmark = pytest.mark.gpu
@@ -114,6 +116,24 @@ def test_forced_chunks_with_ties(gpu, oracle, nchunk, sift_tuning):
             got = gpu.sift_match_guided(d1, l1, d2, l2, H=H, F=Fm, h_max_residual=400.0, f_max_residual=50.0,
                                         max_ratio=ratio, max_distance=dist, cross_check=cross)
             assert np.array_equal(got, exp), (nchunk, H is not None, Fm is not None, cross, len(got), len(exp))
+    # The sets above hold so many equal rows that 12 of these 18 expectations are empty and the rest hold at most 20
+    # matches; at max_ratio 1 a tie is rejected whichever column won.  Beside them: tied sets below the clamp under a
+    # ratio above 1, where the guided walk's choice among equal columns that PASS the filter shows in m12 / m21.
+    t1, t2 = er.tied_sets(n1, n2)
+    S = er.scores(t1, t2)
+    for H, Fm in ((I3, None), (None, F), (I3, F)):
+        Sg = S.copy()
+        Sg[ref.guided_reject(l1, l2, H, Fm, 400.0, 50.0)] = 0
+        first = er.match(S, cross_check=False, **er.RATIO_PROBE)
+        for cross in (True, False):
+            exp = er.match(Sg, cross_check=cross, **er.RATIO_PROBE)
+            assert exp[3] >= er.MARGIN and len(exp[0]) > 10 and (exp[1] != -1).sum() > 50 and (exp[2] != -1).sum() > 100
+            got = device_match(gpu, t1, t2, cross_check=cross, guide=(l1, l2, H, Fm, 400.0, 50.0), **er.RATIO_PROBE)
+            for g, e in zip(got, exp[:3]):
+                assert np.array_equal(g, e), (nchunk, H is not None, Fm is not None, cross)
+            assert np.array_equal(gpu.sift_match_guided(t1, l1, t2, l2, H=H, F=Fm, h_max_residual=400.0, f_max_residual=50.0,
+                                                        cross_check=cross, **er.RATIO_PROBE), exp[0])
+        assert (exp[1] != first[1]).sum() > 50          # the filter moves the winner to a later equal column
 
 
 @pytest.mark.parametrize("budget", [0, 3000])
