@@ -1,0 +1,119 @@
+// ba_handle.h -- the part of the bundle-adjustment handle that both BA units see: ba.hip (evaluation) and
+// ba_solve.hip (point elimination, PCG, LM loop).  Internal; no kernels here.
+#pragma once
+#include <memory>
+
+#include "ba_cam_jac.h"
+#include "common.h"
+
+namespace pcd {
+
+struct BaDev {
+  // problem (device)
+  const int* cam_model; const int* cam_off; const double* cam_params;
+  const double* poses; const int* image_cam; const uint8_t* image_const_pose; const uint8_t* image_const_tvec;
+  const double* points; const uint8_t* point_const;
+  const int* obs_image; const int* obs_point; const double* obs_xy;
+  const int* lidar_point; const double* lidar_abcd; const double* lidar_w;
+  // per-track (sliced ELL, length-sorted) and per-image (contiguous) copies of the observations
+  const int* pt_order;            // [nslices*64]  thread -> point id (-1 = padding)
+  const uint32_t* slice_start;    // [nslices+1]   first slot of each 64-track slice
+  const int* sell_img;            // [nslots]      image of the observation, -1 = padding
+  const double* sell_xy;          // [nslots][2]
+  const uint32_t* pt_lidar_start; const uint32_t* pt_lidar_list;
+  const uint32_t* img_obs_start;  // [I+1]
+  const int* img_pt;              // [O] point of the e-th observation of the image-major order
+  const uint32_t* img_obs;        // [O] its index in the caller's observation order (W is written there)
+  const uint32_t* seg_img;        // [nseg] image of each segment of <= kImgSeg observations (image-major order)
+  const uint32_t* seg_begin;      // [nseg+1] first observation (image-major position) of each segment
+  const uint32_t* img_seg_start;  // [I+1] segments of each image
+  const uint8_t* cam_refine;      // [cam_params_len] 1 = parameter optimised (nullptr: all constant)
+  const uint32_t* cam_img_start;  // [C+1] images of each camera (CSR, ascending image index)
+  const uint32_t* cam_img_list;
+  int C;
+  int cam_k;                      // K of the camera accumulation: the model's when one of the compiled-in models is
+                                  // used by every camera, PCD_CAM_JAC_STRIDE for the generic (per-observation switch) path
+  const double* img_xy;           // [O][2]
+  int I, P, nslices; uint64_t O, L;
+  int loss_type; double loss_scale;
+  int shared_cam;                 // >= 0: every image maps to this camera (one physical camera, the usual dataset); -1: per image
+};
+
+// The point-elimination state is complete in ba_solve.hip only.  The deleter is defined there, so a pcd_ba can be
+// made and destroyed where BaSchur is an incomplete type (the default deleter would need the complete one).
+struct BaSchur;
+struct BaSchurDelete { void operator()(BaSchur* s) const; };
+
+template <typename T>
+static pcd_status upload(DevBuf<T>& b, const T* src, size_t n) {
+  PCD_TRY(b.reserve(std::max<size_t>(n, 1)));
+  if (n) PCD_HIP_TRY(hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return PCD_OK;
+}
+
+// The normal equations at the handle's parameters (ba.hip): point blocks and the cost (k_ba_points, k_sum_partials),
+// then image blocks with W riding on the image pass (k_ba_images, k_ba_images_reduce), on stream s.  w_order[e] is
+// the row of W that image-major observation e writes; nullptr = the caller's observation order (BaDev::img_obs).
+// Every output is device memory and required.  Opens no profiling scope, sets no device.
+pcd_status ba_normal_equations(pcd_ba* b, const uint32_t* w_order, double* Hpt, double* gpt, double* cost, double* Himg,
+                               double* gimg, double* W, hipStream_t s);
+
+}  // namespace pcd
+
+struct pcd_ba {
+  int device = 0;
+  int C = 0, I = 0, P = 0, nslices = 0;
+  uint64_t O = 0, L = 0, cam_params_len = 0;
+  int loss_type = 0;
+  double loss_scale = 1.0;
+  int uniform_model = -1;  // >= 0: every camera has this model
+  int shared_cam = -1;     // >= 0: every image maps to this camera (BaDev::shared_cam)
+  pcd::DevBuf<int> cam_model, cam_off, image_cam, obs_image, obs_point, lidar_point, pt_order, sell_img, img_pt;
+  pcd::DevBuf<double> cam_params, poses, points, obs_xy, lidar_abcd, lidar_w, sell_xy, img_xy;
+  pcd::DevBuf<uint8_t> image_const_pose, image_const_tvec, point_const;
+  bool has_cpose = false, has_ctvec = false, has_cpt = false;
+  pcd::DevBuf<uint32_t> slice_start, pt_lidar_start, pt_lidar_list, img_obs_start, img_obs, cam_img_start, cam_img_list;
+  pcd::DevBuf<uint32_t> seg_img, seg_begin, img_seg_start;
+  uint32_t nseg = 0;
+  pcd::DevBuf<double> img_partial;
+  pcd::DevBuf<uint8_t> cam_refine;
+  bool has_refine = false;
+  pcd::DevBuf<double> cam_partial;
+  pcd::DevBuf<double> cost_partial, cost;
+  // host-API staging
+  pcd::DevBuf<double> o_res, o_jq, o_jt, o_jx, o_jl, o_himg, o_gimg, o_hpt, o_gpt, o_w, o_jc, o_hcam, o_gcam, o_ecam, o_wcam;
+  // pcd_ba_evaluate_blocks: rows of the variable-pose observations, packed pose Jacobians, pinned results
+  std::vector<uint32_t> h_pose_row;      // [O] row of observation o in the packed jac_q / jac_t (0xFFFFFFFF: constant pose)
+  uint64_t n_pose_rows = 0;
+  pcd::DevBuf<uint32_t> vobs;            // [n_pose_rows] observation of every packed row
+  pcd::DevBuf<double> p_jq, p_jt;        // packed pose Jacobians (only when some pose is constant)
+  pcd::PinnedBuf<double> h_blocks;       // residuals | jac_q | jac_t | jac_X | jac_lidar | jac_cam
+  // pcd_ba_evaluate_blocks_compact: records and packed camera blocks (h_blocks is shared with the full route)
+  int cam_stride = 0;                    // largest pcd_camera_num_params over the cameras
+  pcd::DevBuf<double> o_rec, p_jc;
+  // pcd_ba_filter_tracks: the track CSR (point -> its observations, ascending), scratch
+  pcd::DevBuf<uint32_t> pt_obs_start, pt_obs_list;
+  pcd::DevBuf<double> f_sq, f_depth, f_part, f_summary;
+  pcd::DevBuf<uint8_t> f_u8;
+  // point elimination (pcd_ba_schur*): built on the first call, so pcd_ba_create costs existing users nothing
+  bool refines_intrinsics = false;   // some camera_refine byte is set: the reduced system would need camera rows
+  std::unique_ptr<pcd::BaSchur, pcd::BaSchurDelete> schur;
+  pcd::BaDev dev() const {
+    pcd::BaDev d;
+    d.cam_model = cam_model.p; d.cam_off = cam_off.p; d.cam_params = cam_params.p;
+    d.poses = poses.p; d.image_cam = image_cam.p;
+    d.image_const_pose = has_cpose ? image_const_pose.p : nullptr;
+    d.image_const_tvec = has_ctvec ? image_const_tvec.p : nullptr;
+    d.points = points.p; d.point_const = has_cpt ? point_const.p : nullptr;
+    d.obs_image = obs_image.p; d.obs_point = obs_point.p; d.obs_xy = obs_xy.p;
+    d.lidar_point = lidar_point.p; d.lidar_abcd = lidar_abcd.p; d.lidar_w = lidar_w.p;
+    d.pt_order = pt_order.p; d.slice_start = slice_start.p; d.sell_img = sell_img.p; d.sell_xy = sell_xy.p;
+    d.pt_lidar_start = pt_lidar_start.p; d.pt_lidar_list = pt_lidar_list.p;
+    d.img_obs_start = img_obs_start.p; d.img_pt = img_pt.p; d.img_xy = img_xy.p; d.img_obs = img_obs.p;
+    d.seg_img = seg_img.p; d.seg_begin = seg_begin.p; d.img_seg_start = img_seg_start.p;
+    d.cam_refine = has_refine ? cam_refine.p : nullptr; d.cam_img_start = cam_img_start.p; d.cam_img_list = cam_img_list.p;
+    d.C = C; d.shared_cam = shared_cam; d.cam_k = (uniform_model >= 0 && uniform_model <= 4) ? pcd::cam_num_params(uniform_model) : PCD_CAM_JAC_STRIDE;
+    d.I = I; d.P = P; d.nslices = nslices; d.O = O; d.L = L; d.loss_type = loss_type; d.loss_scale = loss_scale;
+    return d;
+  }
+};

@@ -1,0 +1,1295 @@
+// ba_solve.hip -- the device solver of bundle adjustment: point elimination of the damped normal
+// equations into the reduced camera system (k_schur_*), the manifold update (k_ba_plus), the block-sparse
+// preconditioned CG on that system (k_pcg_*) and the Levenberg-Marquardt loop around them (pcd_ba_solve).
+//
+// The blocks it eliminates come from ba.hip, which this unit reaches through two calls only: ba_normal_equations
+// (ba_handle.h) for H, g, W and the cost, and pcd_ba_evaluate_device for the cost of a trial step.  No evaluation
+// kernel is compiled here.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <limits>
+
+#include "ba_handle.h"
+#include "common.h"
+
+namespace pcd {
+
+// ------------------------------------------------------------- Schur -------
+// Point elimination of the damped normal equations (H + D) delta = -g, unknowns = pose tangents of the variable-pose
+// images ("slots", ascending image index), then the points.  DESIGN 4.3a.  Observation data live in image-major
+// positions e (the layout k_ba_images walks): W and Y = W V^-1 of the observations of an image are contiguous, so the
+// entries of a pair block (a in image i, b in image j) gather from two short ranges.  No atomics anywhere: every sum
+// runs in an order fixed by the structure, so results are bitwise reproducible run to run.
+constexpr double kDiagMin = 1e-6, kDiagMax = 1e32;   // Ceres' LevenbergMarquardtStrategy min/max_diagonal
+
+__device__ __forceinline__ double damp_of(int mode, double mu, double h) {
+  return mode == 0 ? mu * fmin(fmax(h, kDiagMin), kDiagMax) : mu;
+}
+
+// thread = point: V = H_pt + D through a 3x3 Cholesky -> V^-1, V^-1 g, D.  Constant points are not eliminated, points
+// whose damped V is not numerically positive definite are skipped (V^-1 = 0: delta 0, no contribution) and counted.
+// The pivot rule is scale-invariant: pivot k must exceed kPivotTol * V_kk, which is the k-th pivot of the Jacobi-scaled
+// V (unit diagonal) exceeding kPivotTol.  A sign test would decide rank-deficient V (a point with one observation and
+// no LiDAR term, or only LiDAR terms, at mu = 0) by the rounding error of the accumulation of H_pt; that error is a
+// few ulp of V_kk, far below the threshold, while a 1e-4 Marquardt damping puts the scaled pivots of such points near
+// 1e-4, far above it.
+// tests/ba_schur_ref.point_inverse applies the same rule in the same operation order.
+constexpr double kPivotTol = 1e-10;
+__global__ __launch_bounds__(256) void k_schur_points(int P, const double* __restrict__ Hpt, const double* __restrict__ gpt,
+                                                      const uint8_t* __restrict__ point_const, double mu, int mode,
+                                                      double* __restrict__ Vinv, double* __restrict__ Vg,
+                                                      double* __restrict__ Dpt, uint32_t* __restrict__ skip_partial) {
+  __shared__ uint32_t s_n[4];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  uint32_t skipped = 0;
+  if (p < P) {
+    double vi[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, d[3];
+    double* dp = Dpt + 3 * (size_t)p;
+    if (!(point_const && point_const[p])) {
+      const double* h = Hpt + 9 * (size_t)p;
+      d[0] = damp_of(mode, mu, h[0]); d[1] = damp_of(mode, mu, h[4]); d[2] = damp_of(mode, mu, h[8]);
+      dp[0] = d[0]; dp[1] = d[1]; dp[2] = d[2];   // stored now: d is not live across the factorisation
+      const double a00 = h[0] + d[0], a01 = h[1], a02 = h[2], a11 = h[4] + d[1], a12 = h[5], a22 = h[8] + d[2];
+      bool ok = a00 > 0.0;   // false for NaN too; t <= V_kk, so a negative V_kk fails t > kPivotTol * V_kk as well
+      double l00 = 0, l10 = 0, l20 = 0, l11 = 0, l21 = 0, l22 = 0;
+      if (ok) { l00 = sqrt(a00); l10 = a01 / l00; l20 = a02 / l00; const double t = a11 - l10 * l10; ok = t > kPivotTol * a11; l11 = ok ? sqrt(t) : 0.0; }
+      if (ok) { l21 = (a12 - l20 * l10) / l11; const double t = a22 - l20 * l20 - l21 * l21; ok = t > kPivotTol * a22; l22 = ok ? sqrt(t) : 0.0; }
+      if (ok) {
+        // M = L^-1 (lower), V^-1 = M^T M
+        const double m00 = 1.0 / l00, m11 = 1.0 / l11, m22 = 1.0 / l22;
+        const double m10 = -(l10 * m00) * m11, m21 = -(l21 * m11) * m22, m20 = -(l20 * m00 + l21 * m10) * m22;
+        vi[0] = m00 * m00 + m10 * m10 + m20 * m20; vi[1] = m10 * m11 + m20 * m21; vi[2] = m20 * m22;
+        vi[4] = m11 * m11 + m21 * m21; vi[5] = m21 * m22; vi[8] = m22 * m22;
+        vi[3] = vi[1]; vi[6] = vi[2]; vi[7] = vi[5];
+      } else {
+        skipped = 1;
+      }
+    } else {
+      dp[0] = 0.0; dp[1] = 0.0; dp[2] = 0.0;
+    }
+    const double* g = gpt + 3 * (size_t)p;
+    double* o = Vinv + 9 * (size_t)p;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[k] = vi[k];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) Vg[3 * (size_t)p + r] = vi[3 * r] * g[0] + vi[3 * r + 1] * g[1] + vi[3 * r + 2] * g[2];
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) skipped += __shfl_xor(skipped, off);
+  if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = skipped;
+  __syncthreads();
+  if (threadIdx.x == 0) skip_partial[blockIdx.x] = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+}
+
+// thread = image-major observation e: Y_e = W_e V_p^-1 (6x3)
+__global__ __launch_bounds__(256) void k_schur_obs(uint64_t O, const int* __restrict__ img_pt, const double* __restrict__ Wim,
+                                                   const double* __restrict__ Vinv, double* __restrict__ Y) {
+  const uint64_t e = blockIdx.x * (uint64_t)256 + threadIdx.x;
+  if (e >= O) return;
+  const double* v = Vinv + 9 * (size_t)img_pt[e];
+  const double* w = Wim + 18 * e;
+  double vi[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) vi[k] = v[k];
+  double* y = Y + 18 * e;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const double w0 = w[3 * r], w1 = w[3 * r + 1], w2 = w[3 * r + 2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) y[3 * r + c] = w0 * vi[c] + w1 * vi[3 + c] + w2 * vi[6 + c];
+  }
+}
+
+// Inputs of the block kernel (one struct keeps the launch readable)
+struct SchurBlocks {
+  int ns; uint32_t nblk;
+  const uint32_t* blk_start;   // [nblk+1] entries of each block: the ns diagonal blocks, then the pair blocks
+  const uint32_t* ent_a; const uint32_t* ent_b;   // image-major positions (a in image i, b in image j)
+  const uint32_t* pair_ij;     // [npairs][2] slots i < j
+  const int* slot_img;         // [ns]
+  const uint32_t* img_obs_start; const int* img_pt;
+  const double* Y; const double* Wim; const double* Vg;
+  const double* Himg; const double* gimg;
+  const uint8_t* image_const_tvec;
+  double mu; int mode;
+  double* Sdiag; double* Soff; double* rhs; double* Dimg;
+};
+
+// one wavefront per block: lane-strided entries, 36 accumulators, xor butterfly (every lane ends with the same
+// bitwise value, the order of the adds depends on the entry count only).  Diagonal blocks add U_i + D_i and the
+// right-hand side.  Constant-tvec coordinates become identity rows / columns with a zero right-hand side.
+__global__ __launch_bounds__(256) void k_schur_blocks(SchurBlocks sb) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t blk = blockIdx.x * 4u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (blk >= sb.nblk) return;
+  double acc[36];
+#pragma unroll
+  for (int k = 0; k < 36; ++k) acc[k] = 0.0;
+  for (uint32_t t = sb.blk_start[blk] + lane; t < sb.blk_start[blk + 1]; t += 64) {
+    const double* y = sb.Y + 18 * (size_t)sb.ent_a[t];
+    const double* w = sb.Wim + 18 * (size_t)sb.ent_b[t];
+    double yv[18], wv[18];
+#pragma unroll
+    for (int k = 0; k < 18; ++k) { yv[k] = y[k]; wv[k] = w[k]; }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int s = 0; s < 6; ++s)
+        acc[6 * r + s] += yv[3 * r] * wv[3 * s] + yv[3 * r + 1] * wv[3 * s + 1] + yv[3 * r + 2] * wv[3 * s + 2];
+  }
+  double mine = 0.0;   // lane k < 36 keeps entry k (selects, no dynamic register indexing)
+#pragma unroll
+  for (int k = 0; k < 36; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    mine = lane == k ? v : mine;
+  }
+  const int r = lane / 6, s = lane - 6 * (lane / 6);
+  if (blk < (uint32_t)sb.ns) {
+    const int i = (int)blk, im = sb.slot_img[i];
+    const unsigned tm = sb.image_const_tvec ? sb.image_const_tvec[im] : 0u;
+    // rhs_i = -g_i + sum_{a in i} W_a V^-1 g_p(a), observations of the image in image-major order
+    double q[6] = {0, 0, 0, 0, 0, 0};
+    for (uint32_t e = sb.img_obs_start[im] + lane; e < sb.img_obs_start[im + 1]; e += 64) {
+      const double* w = sb.Wim + 18 * (size_t)e;
+      const double* vg = sb.Vg + 3 * (size_t)sb.img_pt[e];
+      const double v0 = vg[0], v1 = vg[1], v2 = vg[2];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) q[k] += w[3 * k] * v0 + w[3 * k + 1] * v1 + w[3 * k + 2] * v2;
+    }
+    double qm = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      double v = q[k];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+      qm = lane == k ? v : qm;
+    }
+    const double* H = sb.Himg + 36 * (size_t)im;
+    if (lane < 36) {
+      const bool ir = r >= 3 && ((tm >> (r - 3)) & 1u), is = s >= 3 && ((tm >> (s - 3)) & 1u);
+      double v = H[6 * r + s] - mine;
+      if (r == s) v += damp_of(sb.mode, sb.mu, H[7 * r]);
+      if (ir || is) v = r == s ? 1.0 : 0.0;
+      sb.Sdiag[36 * (size_t)i + lane] = v;
+    }
+    if (lane < 6) {
+      const bool in = lane >= 3 && ((tm >> (lane - 3)) & 1u);
+      sb.rhs[6 * (size_t)i + lane] = in ? 0.0 : qm - sb.gimg[6 * (size_t)im + lane];
+      sb.Dimg[6 * (size_t)i + lane] = in ? 0.0 : damp_of(sb.mode, sb.mu, H[7 * lane]);
+    }
+  } else if (lane < 36) {
+    const uint32_t pq = blk - (uint32_t)sb.ns;
+    const int si = (int)sb.pair_ij[2 * (size_t)pq], sj = (int)sb.pair_ij[2 * (size_t)pq + 1];
+    const unsigned ti = sb.image_const_tvec ? sb.image_const_tvec[sb.slot_img[si]] : 0u;
+    const unsigned tj = sb.image_const_tvec ? sb.image_const_tvec[sb.slot_img[sj]] : 0u;
+    const bool ir = r >= 3 && ((ti >> (r - 3)) & 1u), is = s >= 3 && ((tj >> (s - 3)) & 1u);
+    sb.Soff[36 * (size_t)pq + lane] = (ir || is) ? 0.0 : 0.0 - mine;
+  }
+}
+
+// dense S [n][n] (n = 6 ns, both triangles) from the blocks; the caller zeroed it.  thread = (block, entry)
+__global__ __launch_bounds__(256) void k_schur_dense(int ns, uint32_t nblk, const uint32_t* __restrict__ pair_ij,
+                                                     const double* __restrict__ Sdiag, const double* __restrict__ Soff,
+                                                     double* __restrict__ S) {
+  const uint64_t t = blockIdx.x * (uint64_t)256 + threadIdx.x;
+  if (t >= (uint64_t)nblk * 36) return;
+  const uint32_t blk = (uint32_t)(t / 36);
+  const int k = (int)(t - 36 * (uint64_t)blk), r = k / 6, s = k - 6 * (k / 6);
+  const size_t n = 6 * (size_t)ns;
+  if (blk < (uint32_t)ns) {
+    S[(6 * (size_t)blk + r) * n + 6 * (size_t)blk + s] = Sdiag[36 * (size_t)blk + k];
+  } else {
+    const uint32_t pq = blk - (uint32_t)ns;
+    const size_t i = pair_ij[2 * (size_t)pq], j = pair_ij[2 * (size_t)pq + 1];
+    const double v = Soff[36 * (size_t)pq + k];
+    S[(6 * i + r) * n + 6 * j + s] = v;
+    S[(6 * j + s) * n + 6 * i + r] = v;
+  }
+}
+
+// thread = point: delta X_p = -V^-1 (g_p + sum_{a in p} W_a^T delta c_img(a)), its observations in ascending caller
+// order; partial of the model decrease -delta^T g + delta^T D delta over the points (fixed-order block sum)
+__global__ __launch_bounds__(256) void k_schur_back(int P, const uint32_t* __restrict__ pt_start,
+                                                    const uint32_t* __restrict__ pt_list, const int* __restrict__ obs_image,
+                                                    const uint32_t* __restrict__ obs_pos, const int* __restrict__ img_slot,
+                                                    const double* __restrict__ Wim, const double* __restrict__ Vinv,
+                                                    const double* __restrict__ gpt, const double* __restrict__ Dpt,
+                                                    const double* __restrict__ dpose, double* __restrict__ dpoint,
+                                                    double* __restrict__ md_partial) {
+  __shared__ double s_m[4];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  double md = 0.0;
+  if (p < P) {
+    const double* g = gpt + 3 * (size_t)p;
+    double r0 = g[0], r1 = g[1], r2 = g[2];
+    for (uint32_t k = pt_start[p]; k < pt_start[p + 1]; ++k) {
+      const uint32_t o = pt_list[k];
+      const int s = img_slot[obs_image[o]];
+      if (s < 0) continue;
+      const double* w = Wim + 18 * (size_t)obs_pos[o];
+      const double* dc = dpose + 6 * (size_t)s;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const double c = dc[a];
+        r0 += w[3 * a] * c; r1 += w[3 * a + 1] * c; r2 += w[3 * a + 2] * c;
+      }
+    }
+    const double* v = Vinv + 9 * (size_t)p;
+    const double dx0 = -(v[0] * r0 + v[1] * r1 + v[2] * r2);
+    const double dx1 = -(v[3] * r0 + v[4] * r1 + v[5] * r2);
+    const double dx2 = -(v[6] * r0 + v[7] * r1 + v[8] * r2);
+    dpoint[3 * (size_t)p] = dx0; dpoint[3 * (size_t)p + 1] = dx1; dpoint[3 * (size_t)p + 2] = dx2;
+    const double* d = Dpt + 3 * (size_t)p;
+    md = -(dx0 * g[0] + dx1 * g[1] + dx2 * g[2]) + (d[0] * dx0 * dx0 + d[1] * dx1 * dx1 + d[2] * dx2 * dx2);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) md += __shfl_xor(md, off);
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = md;
+  __syncthreads();
+  if (threadIdx.x == 0) md_partial[blockIdx.x] = (s_m[0] + s_m[1]) + (s_m[2] + s_m[3]);
+}
+
+// one workgroup: 1/2 (slot terms + point partials), strided per thread then a fixed tree
+__global__ __launch_bounds__(256) void k_schur_model_decrease(int ns, const int* __restrict__ slot_img,
+                                                              const uint8_t* __restrict__ image_const_tvec,
+                                                              const double* __restrict__ gimg, const double* __restrict__ Dimg,
+                                                              const double* __restrict__ dpose,
+                                                              const double* __restrict__ md_partial, int nbp,
+                                                              double* __restrict__ out) {
+  __shared__ double s_c[256];
+  double a = 0.0, b = 0.0;
+  for (int i = threadIdx.x; i < ns; i += 256) {
+    const int im = slot_img[i];
+    const unsigned tm = image_const_tvec ? image_const_tvec[im] : 0u;
+    const double* g = gimg + 6 * (size_t)im;
+    const double* d = Dimg + 6 * (size_t)i;
+    const double* x = dpose + 6 * (size_t)i;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const bool inactive = k >= 3 && ((tm >> (k - 3)) & 1u);   // delta 0 there, whatever the caller passed
+      a += inactive ? 0.0 : -x[k] * g[k] + d[k] * x[k] * x[k];
+    }
+  }
+  for (int i = threadIdx.x; i < nbp; i += 256) b += md_partial[i];
+  s_c[threadIdx.x] = a + b;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) s_c[threadIdx.x] += s_c[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = 0.5 * s_c[0];
+}
+
+__global__ __launch_bounds__(256) void k_sum_u32(const uint32_t* __restrict__ partial, int n, unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long s_c[256];
+  unsigned long long a = 0;
+  for (int i = threadIdx.x; i < n; i += 256) a += partial[i];
+  s_c[threadIdx.x] = a;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) s_c[threadIdx.x] += s_c[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = s_c[0];
+}
+
+// Ceres' QuaternionManifold::Plus (q <- [cos|d|, sin|d|/|d| d] * q) and t += dt on the variable coordinates;
+// constant poses / tvec components / points are copied.  thread = image (t < I) or point.  In-place safe.
+__global__ __launch_bounds__(256) void k_ba_plus(int I, int P, const int* __restrict__ img_slot,
+                                                 const uint8_t* __restrict__ image_const_tvec,
+                                                 const uint8_t* __restrict__ point_const, const double* poses,
+                                                 const double* points, const double* __restrict__ dpose,
+                                                 const double* __restrict__ dpoint, double* poses_out, double* points_out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < I) {
+    const double* x = poses + 7 * (size_t)t;
+    double y[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) y[k] = x[k];
+    const int s = img_slot[t];
+    if (s >= 0) {
+      const double* d = dpose + 6 * (size_t)s;
+      const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+      if (nd != 0.0) {
+        const double sd = sin(nd) / nd;
+        const double a0 = cos(nd), a1 = sd * d[0], a2 = sd * d[1], a3 = sd * d[2];
+        y[0] = a0 * x[0] - a1 * x[1] - a2 * x[2] - a3 * x[3];
+        y[1] = a0 * x[1] + a1 * x[0] + a2 * x[3] - a3 * x[2];
+        y[2] = a0 * x[2] - a1 * x[3] + a2 * x[0] + a3 * x[1];
+        y[3] = a0 * x[3] + a1 * x[2] - a2 * x[1] + a3 * x[0];
+      }
+      const unsigned tm = image_const_tvec ? image_const_tvec[t] : 0u;
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (!((tm >> k) & 1u)) y[4 + k] = x[4 + k] + d[3 + k];
+    }
+    double* o = poses_out + 7 * (size_t)t;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) o[k] = y[k];
+  } else if (t < I + P) {
+    const int p = t - I;
+    const double* x = points + 3 * (size_t)p;
+    const double* d = dpoint + 3 * (size_t)p;
+    const bool c = point_const && point_const[p];
+    double* o = points_out + 3 * (size_t)p;
+    const double y0 = c ? x[0] : x[0] + d[0], y1 = c ? x[1] : x[1] + d[1], y2 = c ? x[2] : x[2] + d[2];
+    o[0] = y0; o[1] = y1; o[2] = y2;
+  }
+}
+
+// ---- block-sparse preconditioned CG on the reduced camera system (pcd_ba_schur_solve_pcg*) -----------
+// S x = rhs from the handle's own blocks.  An iteration is three plain launches (product, vector update, scalars);
+// scalars, the iteration count and the done flag live in PcgState on the device and every kernel of an iteration
+// returns at once when done is set, so the host enqueues a batch of iterations between two looks at the flag.
+// p and x are double-buffered (iteration it reads buffer it & 1 and writes the other): the product forms the new
+// direction of a partner slot on the fly from z and the old p instead of waiting for a fourth launch, and a breakdown
+// leaves the last finite x untouched.  All sums run in an order fixed by the structure.
+struct PcgState {
+  double rho, alpha, beta, pw, q, rn2, bnorm, xr;
+  int k, done, term, xsel;
+  unsigned fallbacks; int pad;
+};
+struct PcgRule { int max_iterations, min_iterations; double q_tolerance, r_tolerance; };
+
+// sum over the workgroup (256 threads), every thread gets the result; fixed order: wavefront butterfly, then the 4 waves
+__device__ __forceinline__ double block_sum256(double v, double* lds4) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();   // lds4 may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+// strided sum of partial[i * stride] (i < n) over one workgroup
+__device__ __forceinline__ double block_sum_strided(const double* __restrict__ partial, int n, int stride, double* lds4) {
+  double a = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) a += partial[(size_t)i * stride];
+  return block_sum256(a, lds4);
+}
+
+// thread = slot: M_i^-1 (SCHUR_JACOBI: inverse of the 6x6 diagonal block through its Cholesky factor, identity when a
+// pivot is not positive and finite -- counted; IDENTITY: I), x = 0, r = rhs, z = M^-1 r, both direction buffers 0;
+// partials [nb][4] of r.z, rhs.rhs and the fallback count.  An identity row / column of the block (constant tvec
+// coordinate) gives an identity row / column of the factor and of the inverse, exactly.
+__global__ __launch_bounds__(256) void k_pcg_init(int ns, int precond, const double* __restrict__ Sdiag,
+                                                  const double* __restrict__ rhs, double* __restrict__ Minv,
+                                                  double* __restrict__ x0, double* __restrict__ r, double* __restrict__ z,
+                                                  double* __restrict__ p0, double* __restrict__ p1,
+                                                  double* __restrict__ partial) {
+  __shared__ double s_l[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double rz = 0.0, bb = 0.0, fb = 0.0;
+  if (i < ns) {
+    double mi[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) mi[k] = (k % 7 == 0) ? 1.0 : 0.0;
+    if (precond != 0) {
+      const double* A = Sdiag + 36 * (size_t)i;
+      double L[36];
+#pragma unroll
+      for (int k = 0; k < 36; ++k) L[k] = 0.0;
+      bool ok = true;
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        double d = A[7 * j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= L[6 * j + k] * L[6 * j + k];
+        ok = ok && d > 0.0 && d <= 1.7976931348623157e308;
+        const double ljj = ok ? sqrt(d) : 1.0;
+        L[7 * j] = ljj;
+#pragma unroll
+        for (int a = j + 1; a < 6; ++a) {
+          double s = A[6 * a + j];
+#pragma unroll
+          for (int k = 0; k < j; ++k) s -= L[6 * a + k] * L[6 * j + k];
+          L[6 * a + j] = s / ljj;
+        }
+      }
+      if (ok) {
+        double M[36];   // L^-1, lower
+#pragma unroll
+        for (int k = 0; k < 36; ++k) M[k] = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+          M[7 * j] = 1.0 / L[7 * j];
+#pragma unroll
+          for (int a = j + 1; a < 6; ++a) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = j; k < a; ++k) s += L[6 * a + k] * M[6 * k + j];
+            M[6 * a + j] = -s / L[7 * a];
+          }
+        }
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+          for (int c = 0; c <= a; ++c) {
+            double s = 0.0;   // (M^T M)_ac, k from a (>= c) upwards
+#pragma unroll
+            for (int k = a; k < 6; ++k) s += M[6 * k + a] * M[6 * k + c];
+            mi[6 * a + c] = s; mi[6 * c + a] = s;
+          }
+      } else {
+        fb = 1.0;
+      }
+    }
+    double* mo = Minv + 36 * (size_t)i;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) mo[k] = mi[k];
+    double b[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] = rhs[6 * (size_t)i + k];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s += mi[6 * a + c] * b[c];
+      const size_t o = 6 * (size_t)i + a;
+      z[o] = s; r[o] = b[a]; x0[o] = 0.0; p0[o] = 0.0; p1[o] = 0.0;
+      rz += b[a] * s; bb += b[a] * b[a];
+    }
+  }
+  rz = block_sum256(rz, s_l); bb = block_sum256(bb, s_l); fb = block_sum256(fb, s_l);
+  if (threadIdx.x == 0) {
+    double* o = partial + 4 * (size_t)blockIdx.x;
+    o[0] = rz; o[1] = bb; o[2] = fb; o[3] = 0.0;
+  }
+}
+
+// one workgroup: the scalars of iteration 0.  ||rhs|| = 0 -> ZERO_RHS, max_iterations <= 0 -> MAX_ITERATIONS, x = 0
+__global__ __launch_bounds__(256) void k_pcg_begin(int nb, const double* __restrict__ partial, PcgRule rule,
+                                                   PcgState* __restrict__ st) {
+  __shared__ double s_l[4];
+  const double rz = block_sum_strided(partial, nb, 4, s_l);
+  const double bb = block_sum_strided(partial + 1, nb, 4, s_l);
+  const double fb = block_sum_strided(partial + 2, nb, 4, s_l);
+  if (threadIdx.x != 0) return;
+  PcgState s;
+  s.rho = rz; s.alpha = 0.0; s.beta = 0.0; s.pw = 0.0; s.q = 0.0; s.rn2 = bb; s.bnorm = sqrt(bb); s.xr = 0.0;
+  s.k = 0; s.done = 0; s.term = PCD_PCG_MAX_ITERATIONS; s.xsel = 0; s.fallbacks = (unsigned)fb; s.pad = 0;
+  if (!(bb > 0.0)) {   // zero (or not a number: nothing to iterate on)
+    s.done = 1; s.term = bb == 0.0 ? PCD_PCG_ZERO_RHS : PCD_PCG_BREAKDOWN;
+  } else if (!(rz > 0.0) || !(rz <= 1.7976931348623157e308)) {
+    s.done = 1; s.term = PCD_PCG_BREAKDOWN;
+  } else if (rule.max_iterations <= 0) {
+    s.done = 1;
+  }
+  *st = s;
+}
+
+// one wavefront per slot row: w_i = sum over the row list (ascending partner slot; block, transposed flag) of
+// B p_j with p_j = z_j + beta p_old_j, lane-strided blocks, six accumulators, xor butterfly.  Lane 0 stores the row's
+// new direction, w_i and p_i . w_i.
+__global__ __launch_bounds__(256) void k_pcg_spmv(int ns, const PcgState* __restrict__ st,
+                                                  const uint32_t* __restrict__ row_start, const uint32_t* __restrict__ row_blk,
+                                                  const uint32_t* __restrict__ row_col, const double* __restrict__ Sdiag,
+                                                  const double* __restrict__ Soff, const double* __restrict__ z,
+                                                  const double* __restrict__ p_old, double* __restrict__ p_new,
+                                                  double* __restrict__ w, double* __restrict__ pw_partial) {
+  if (st->done) return;
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (i >= ns) return;
+  const double beta = st->beta;
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  for (uint32_t t = row_start[i] + lane; t < row_start[i + 1]; t += 64) {
+    const uint32_t blk = row_blk[t], cj = row_col[t];
+    const bool tr = cj & 1u;
+    const size_t j = cj >> 1;
+    const double* B = blk < (uint32_t)ns ? Sdiag + 36 * (size_t)blk : Soff + 36 * (size_t)(blk - (uint32_t)ns);
+    double bv[36], pj[6];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) bv[k] = B[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pj[k] = z[6 * j + k] + beta * p_old[6 * j + k];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s += (tr ? bv[6 * c + a] : bv[6 * a + c]) * pj[c];
+      acc[a] += s;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc[a] += __shfl_xor(acc[a], off);
+  if (lane == 0) {
+    double pw = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const size_t o = 6 * (size_t)i + k;
+      const double pk = z[o] + beta * p_old[o];
+      p_new[o] = pk; w[o] = acc[k];
+      pw += pk * acc[k];
+    }
+    pw_partial[i] = pw;
+  }
+}
+
+// thread = slot: alpha = rho / p.w (every workgroup sums the ns row partials in the same order), then
+// x_new = x_old + alpha p, r -= alpha w, z = M^-1 r and the partials [nb][4] of r.z, r.r, x.(rhs + r), x.r.
+// p.w <= 0 or a non-finite alpha: nothing is updated (k_pcg_step ends the solve with BREAKDOWN).
+__global__ __launch_bounds__(256) void k_pcg_update(int ns, PcgState* __restrict__ st, const double* __restrict__ pw_partial,
+                                                    const double* __restrict__ Minv, const double* __restrict__ rhs,
+                                                    const double* __restrict__ p, const double* __restrict__ w,
+                                                    const double* __restrict__ x_old, double* __restrict__ x_new,
+                                                    double* __restrict__ r, double* __restrict__ z,
+                                                    double* __restrict__ partial) {
+  __shared__ double s_l[4];
+  if (st->done) return;
+  const double pw = block_sum_strided(pw_partial, ns, 1, s_l);
+  const double alpha = st->rho / pw;
+  const bool good = pw > 0.0 && alpha <= 1.7976931348623157e308 && alpha >= -1.7976931348623157e308;
+  if (blockIdx.x == 0 && threadIdx.x == 0) { st->pw = pw; st->alpha = alpha; }
+  if (!good) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double rz = 0.0, rr = 0.0, xbr = 0.0, xr = 0.0;
+  if (i < ns) {
+    double rv[6], xv[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const size_t o = 6 * (size_t)i + k;
+      xv[k] = x_old[o] + alpha * p[o];
+      rv[k] = r[o] - alpha * w[o];
+      x_new[o] = xv[k]; r[o] = rv[k];
+    }
+    const double* mi = Minv + 36 * (size_t)i;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s += mi[6 * a + c] * rv[c];
+      z[6 * (size_t)i + a] = s;
+      rz += rv[a] * s; rr += rv[a] * rv[a];
+      xbr += xv[a] * (rhs[6 * (size_t)i + a] + rv[a]); xr += xv[a] * rv[a];
+    }
+  }
+  rz = block_sum256(rz, s_l); rr = block_sum256(rr, s_l); xbr = block_sum256(xbr, s_l); xr = block_sum256(xr, s_l);
+  if (threadIdx.x == 0) {
+    double* o = partial + 4 * (size_t)blockIdx.x;
+    o[0] = rz; o[1] = rr; o[2] = xbr; o[3] = xr;
+  }
+}
+
+// one workgroup: sums of the partials, Q_k = -1/2 x.(rhs + r), the stopping rule (Q, then r, then the iteration
+// limit), beta and the counter.  `it` is the iteration's index (the buffer that holds its x is (it + 1) & 1).
+__global__ __launch_bounds__(256) void k_pcg_step(int nb, int it, const double* __restrict__ partial, PcgRule rule,
+                                                  PcgState* __restrict__ st) {
+  __shared__ double s_l[4];
+  if (st->done) return;
+  const double pw = st->pw, alpha = st->alpha;
+  if (!(pw > 0.0 && alpha <= 1.7976931348623157e308 && alpha >= -1.7976931348623157e308)) {
+    if (threadIdx.x == 0) { st->done = 1; st->term = PCD_PCG_BREAKDOWN; }
+    return;
+  }
+  const double rz = block_sum_strided(partial, nb, 4, s_l);
+  const double rr = block_sum_strided(partial + 1, nb, 4, s_l);
+  const double xbr = block_sum_strided(partial + 2, nb, 4, s_l);
+  const double xr = block_sum_strided(partial + 3, nb, 4, s_l);
+  if (threadIdx.x != 0) return;
+  const double q = -0.5 * xbr;
+  const double lim = 1.7976931348623157e308;
+  if (!(rz >= 0.0 && rz <= lim && rr <= lim && q >= -lim && q <= lim)) {   // the x of this iteration is not used
+    st->done = 1; st->term = PCD_PCG_BREAKDOWN;
+    return;
+  }
+  const int k = st->k + 1;
+  const double zeta = (double)k * (q - st->q) / q;
+  int done = 0, term = PCD_PCG_MAX_ITERATIONS;
+  if (k >= rule.min_iterations && rule.q_tolerance >= 0.0 && zeta < rule.q_tolerance) { done = 1; term = PCD_PCG_Q_TOLERANCE; }
+  else if (k >= rule.min_iterations && rule.r_tolerance >= 0.0 && sqrt(rr) <= rule.r_tolerance * st->bnorm) { done = 1; term = PCD_PCG_R_TOLERANCE; }
+  else if (k >= rule.max_iterations) { done = 1; }
+  st->beta = rz / st->rho; st->rho = rz; st->q = q; st->rn2 = rr; st->xr = xr;
+  st->k = k; st->xsel = (it + 1) & 1; st->term = term; st->done = done;
+}
+
+// the selected x into the caller's dpose, the record into info (termination -1: still running)
+__global__ __launch_bounds__(256) void k_pcg_finish(int ns, const PcgState* __restrict__ st, const double* __restrict__ x0,
+                                                    const double* __restrict__ x1, double* __restrict__ dpose,
+                                                    pcd_ba_pcg_info* __restrict__ info) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (dpose && t < 6 * ns) dpose[t] = (st->xsel ? x1 : x0)[t];
+  if (t == 0 && info) {
+    pcd_ba_pcg_info o;
+    o.iterations = st->k; o.termination = st->done ? st->term : -1; o.precond_fallbacks = st->fallbacks;
+    o.rhs_norm = st->bnorm; o.residual_norm = sqrt(st->rn2); o.q = st->q; o.step_dot_residual = st->xr;
+    *info = o;
+  }
+}
+
+// max |g| over the active pose coordinates of the slots and the non-constant points: partial max per workgroup
+// (a maximum does not depend on the order), grid-stride
+__global__ __launch_bounds__(256) void k_ba_grad_max(int ns, const int* __restrict__ slot_img,
+                                                     const uint8_t* __restrict__ image_const_tvec,
+                                                     const double* __restrict__ gimg, int P,
+                                                     const uint8_t* __restrict__ point_const,
+                                                     const double* __restrict__ gpt, double* __restrict__ partial) {
+  __shared__ double s_m[4];
+  double m = 0.0;
+  const int n = ns + P;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) {
+    if (t < ns) {
+      const int im = slot_img[t];
+      const unsigned tm = image_const_tvec ? image_const_tvec[im] : 0u;
+      const double* g = gimg + 6 * (size_t)im;
+#pragma unroll
+      for (int k = 0; k < 6; ++k)
+        if (!(k >= 3 && ((tm >> (k - 3)) & 1u))) m = fmax(m, fabs(g[k]));
+    } else {
+      const int p = t - ns;
+      if (!(point_const && point_const[p])) {
+        const double* g = gpt + 3 * (size_t)p;
+        m = fmax(m, fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2]))));
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
+}
+
+// what the LM loop of pcd_ba_solve reads per iteration, in one device-to-host copy
+struct LmRecord {
+  double cost, candidate_cost, model_decrease, gradient_max;
+  unsigned long long num_skipped;
+  pcd_ba_pcg_info pcg;
+};
+__global__ __launch_bounds__(256) void k_ba_lm_record(const double* __restrict__ cost, const double* __restrict__ cand,
+                                                      const double* __restrict__ md, const double* __restrict__ gpart,
+                                                      int ngp, const unsigned long long* __restrict__ skipped,
+                                                      const pcd_ba_pcg_info* __restrict__ info, LmRecord* __restrict__ out) {
+  __shared__ double s_m[4];
+  double m = 0.0;
+  for (int i = threadIdx.x; i < ngp; i += 256) m = fmax(m, gpart[i]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    LmRecord r;
+    r.cost = cost[0]; r.candidate_cost = cand[0]; r.model_decrease = md[0];
+    r.gradient_max = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
+    r.num_skipped = skipped[0]; r.pcg = *info;
+    *out = r;
+  }
+}
+
+// Host-built structure (first Schur call) and the numeric state of the last Schur call
+struct BaSchur {
+  bool built = false;
+  int ns = 0;
+  uint64_t npairs = 0, nent = 0;
+  double build_ms = 0.0;
+  std::vector<int32_t> h_slot, h_pair_i, h_pair_j;
+  DevBuf<int> img_slot, slot_img;
+  DevBuf<uint32_t> blk_start, ent_a, ent_b, pair_ij, iota, obs_pos;
+  bool valid = false;   // a Schur call has filled the state below
+  DevBuf<double> Himg, gimg, Hpt, gpt, Wim, Y, Vinv, Vg, Dpt, Dimg, Sdiag, Soff, rhs, md_partial, md;
+  DevBuf<uint32_t> skip_partial;
+  DevBuf<unsigned long long> skip_cnt;
+  DevBuf<double> cost, dense;   // dense: staging of the host form's S
+  // rows of S for the product y = S x (built with the structure): row i = its blocks in ascending partner slot
+  DevBuf<uint32_t> row_start, row_blk, row_col;   // [ns+1]; block (< ns: diagonal, else ns + pair); partner << 1 | transposed
+  bool own_diag = false, own_off = false, own_rhs = false;   // the last Schur call left S_diag / S_off / rhs in the handle
+  // PCG state (pcd_ba_schur_solve_pcg*) and the LM loop's buffers (pcd_ba_solve)
+  DevBuf<double> Minv, cg_x0, cg_x1, cg_r, cg_z, cg_p0, cg_p1, cg_w, cg_pw, cg_partial, cg_out;
+  DevBuf<PcgState> cg_state;
+  DevBuf<pcd_ba_pcg_info> cg_info;
+  PinnedBuf<int> cg_flag;
+  int cg_it = 0;   // iterations enqueued in the running solve (buffer parity)
+  DevBuf<double> lm_dpose, lm_dpoint, lm_poses, lm_points, lm_cand_cost, lm_gpart;
+  DevBuf<LmRecord> lm_rec;
+  PinnedBuf<LmRecord> lm_host;
+  // device memory held (pcd_ba_schur_stats): every DevBuf above but the 8 bytes of skip_cnt
+  uint64_t device_bytes() const {
+    auto sum = [](const auto&... b) { return (uint64_t(0) + ... + (b.n * sizeof(*b.p))); };
+    return sum(img_slot, slot_img, blk_start, ent_a, ent_b, pair_ij, iota, obs_pos, Himg, gimg, Hpt, gpt, Wim, Y, Vinv,
+               Vg, Dpt, Dimg, Sdiag, Soff, rhs, md_partial, md, skip_partial, cost, dense, row_start, row_blk, row_col,
+               Minv, cg_x0, cg_x1, cg_r, cg_z, cg_p0, cg_p1, cg_w, cg_pw, cg_partial, cg_out, cg_state, cg_info,
+               lm_dpose, lm_dpoint, lm_poses, lm_points, lm_cand_cost, lm_gpart, lm_rec);
+  }
+};
+
+void BaSchurDelete::operator()(BaSchur* s) const { delete s; }
+
+}  // namespace pcd
+
+using namespace pcd;
+
+// ---- point elimination: guards and the co-visibility structure ----------------------------------------------
+// Every Schur entry point: no gfx950 device -> NO_DEVICE, no handle -> INVALID, refined intrinsics -> UNSUPPORTED
+// (the reduced system would need the camera rows), all before anything is allocated or launched.
+static pcd_status schur_guard(pcd_ba* b) {
+  PCD_TRY(require_device(b ? b->device : 0));
+  PCD_REQUIRE(b, "null handle");
+  if (b->refines_intrinsics) {
+    set_error("point elimination with refined intrinsics (camera_refine) is not supported");
+    return PCD_ERR_UNSUPPORTED;
+  }
+  return PCD_OK;
+}
+
+// Slots, the per-block entry lists and the inverse image-major permutation, by host counting sorts over index arrays
+// read back once.  Blocks: the ns diagonal blocks, then the pair blocks in ascending (i, j).  Entries (a, b) of a block:
+// a ascending (image-major position in image i), then b ascending (image j).  A diagonal block holds (a, a) and the
+// pairs of a point observed more than once in the image.  Only variable-pose observations of non-constant points
+// take part.
+static pcd_status schur_build(pcd_ba* b) {
+  if (!b->schur) b->schur.reset(new BaSchur());
+  BaSchur& S = *b->schur;
+  if (S.built) return PCD_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t O = b->O;
+  const int I = b->I, P = b->P;
+  std::vector<int32_t> oimg(O), opt(O);
+  std::vector<uint32_t> ist((size_t)I + 1), iobs(O);
+  std::vector<uint8_t> cpose(I, 0), cpt(P, 0);
+  if (O) {
+    PCD_HIP_TRY(hipMemcpy(oimg.data(), b->obs_image.p, O * sizeof(int32_t), hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipMemcpy(opt.data(), b->obs_point.p, O * sizeof(int32_t), hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipMemcpy(iobs.data(), b->img_obs.p, O * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  PCD_HIP_TRY(hipMemcpy(ist.data(), b->img_obs_start.p, ist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (b->has_cpose) PCD_HIP_TRY(hipMemcpy(cpose.data(), b->image_const_pose.p, I, hipMemcpyDeviceToHost));
+  if (b->has_cpt) PCD_HIP_TRY(hipMemcpy(cpt.data(), b->point_const.p, P, hipMemcpyDeviceToHost));
+  S.h_slot.assign(I, -1);
+  std::vector<int32_t> slot_img;
+  for (int i = 0; i < I; ++i)
+    if (!cpose[i]) { S.h_slot[i] = (int32_t)slot_img.size(); slot_img.push_back(i); }
+  const int ns = (int)slot_img.size();
+  S.ns = ns;
+  std::vector<uint32_t> obs_pos(O), iota(O);
+  std::vector<int32_t> eslot(O), ept(O);
+  for (int i = 0; i < I; ++i)
+    for (uint32_t e = ist[i]; e < ist[i + 1]; ++e) {
+      const uint32_t o = iobs[e];
+      obs_pos[o] = e; iota[e] = e; ept[e] = opt[o];
+      eslot[e] = cpt[opt[o]] ? -1 : S.h_slot[i];   // -1: takes no part in the elimination
+    }
+  // eliminated observations of every point, ascending image-major position
+  std::vector<uint32_t> pst((size_t)P + 1, 0), pli;
+  for (uint64_t e = 0; e < O; ++e) if (eslot[e] >= 0) pst[(size_t)ept[e] + 1]++;
+  for (int p = 0; p < P; ++p) pst[p + 1] += pst[p];
+  pli.resize(pst[P]);
+  {
+    std::vector<uint32_t> cur(pst.begin(), pst.end() - 1);
+    for (uint64_t e = 0; e < O; ++e) if (eslot[e] >= 0) pli[cur[ept[e]]++] = (uint32_t)e;
+  }
+  std::vector<uint64_t> blk(1, 0);
+  std::vector<uint32_t> ea, eb;
+  for (int s = 0; s < ns; ++s) {   // diagonal blocks
+    const int im = slot_img[s];
+    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
+      if (eslot[e] < 0) continue;
+      const int p = ept[e];
+      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k)
+        if (eslot[pli[k]] == s) { ea.push_back(e); eb.push_back(pli[k]); }
+    }
+    blk.push_back(ea.size());
+  }
+  S.h_pair_i.clear(); S.h_pair_j.clear();
+  std::vector<uint32_t> cnt(ns, 0);
+  std::vector<uint64_t> cur(ns, 0);
+  std::vector<int> touched;
+  for (int s = 0; s < ns; ++s) {   // pair blocks of row s: a per-row counting sort over the partner slot
+    const int im = slot_img[s];
+    touched.clear();
+    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
+      if (eslot[e] < 0) continue;
+      const int p = ept[e];
+      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k) {
+        const int j = eslot[pli[k]];
+        if (j > s && cnt[j]++ == 0) touched.push_back(j);
+      }
+    }
+    std::sort(touched.begin(), touched.end());
+    uint64_t off = ea.size();
+    for (int j : touched) {
+      cur[j] = off; off += cnt[j];
+      S.h_pair_i.push_back(s); S.h_pair_j.push_back(j);
+      blk.push_back(off);
+    }
+    ea.resize(off); eb.resize(off);
+    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
+      if (eslot[e] < 0) continue;
+      const int p = ept[e];
+      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k) {
+        const int j = eslot[pli[k]];
+        if (j > s) { ea[cur[j]] = e; eb[cur[j]++] = pli[k]; }
+      }
+    }
+    for (int j : touched) cnt[j] = 0;
+  }
+  if (ea.size() >= 0xFFFFFFF0ull || blk.size() >= 0xFFFFFFF0ull) {
+    set_error("point elimination: %zu block entries exceed the 32-bit layout", ea.size());
+    return PCD_ERR_UNSUPPORTED;
+  }
+  S.npairs = S.h_pair_i.size();
+  S.nent = ea.size();
+  std::vector<uint32_t> blk32(blk.begin(), blk.end()), pij(2 * S.npairs);
+  for (uint64_t q = 0; q < S.npairs; ++q) { pij[2 * q] = (uint32_t)S.h_pair_i[q]; pij[2 * q + 1] = (uint32_t)S.h_pair_j[q]; }
+  PCD_TRY(upload(S.img_slot, S.h_slot.data(), (size_t)I));
+  PCD_TRY(upload(S.slot_img, slot_img.data(), slot_img.size()));
+  PCD_TRY(upload(S.blk_start, blk32.data(), blk32.size()));
+  PCD_TRY(upload(S.ent_a, ea.data(), ea.size()));
+  PCD_TRY(upload(S.ent_b, eb.data(), eb.size()));
+  PCD_TRY(upload(S.pair_ij, pij.data(), pij.size()));
+  PCD_TRY(upload(S.iota, iota.data(), iota.size()));
+  PCD_TRY(upload(S.obs_pos, obs_pos.data(), obs_pos.size()));
+  {   // row lists of the product: transposes of the (k, s) blocks (k ascending), the diagonal, the (s, j) blocks
+    std::vector<uint32_t> rst((size_t)ns + 1, 0);
+    for (int s = 0; s < ns; ++s) rst[(size_t)s + 1] = 1;
+    for (uint64_t q = 0; q < S.npairs; ++q) { rst[(size_t)S.h_pair_i[q] + 1]++; rst[(size_t)S.h_pair_j[q] + 1]++; }
+    for (int s = 0; s < ns; ++s) rst[(size_t)s + 1] += rst[s];
+    std::vector<uint32_t> rblk(rst[ns]), rcol(rst[ns]), pos(rst.begin(), rst.end() - 1);
+    for (uint64_t q = 0; q < S.npairs; ++q) {
+      const uint32_t t = pos[S.h_pair_j[q]]++;
+      rblk[t] = (uint32_t)(ns + q); rcol[t] = ((uint32_t)S.h_pair_i[q] << 1) | 1u;
+    }
+    for (int s = 0; s < ns; ++s) { const uint32_t t = pos[s]++; rblk[t] = (uint32_t)s; rcol[t] = (uint32_t)s << 1; }
+    for (uint64_t q = 0; q < S.npairs; ++q) {
+      const uint32_t t = pos[S.h_pair_i[q]]++;
+      rblk[t] = (uint32_t)(ns + q); rcol[t] = (uint32_t)S.h_pair_j[q] << 1;
+    }
+    PCD_TRY(upload(S.row_start, rst.data(), rst.size()));
+    PCD_TRY(upload(S.row_blk, rblk.data(), rblk.size()));
+    PCD_TRY(upload(S.row_col, rcol.data(), rcol.size()));
+  }
+  S.built = true;
+  S.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PCD_OK;
+}
+
+// ---- reduced solve: PCG and the LM loop -------------------------------------------------------------
+// Iterations are enqueued in batches; between two batches the host reads the done flag (one 4-byte copy and a stream
+// synchronisation).  8 covers the inexact steps of the LM loop (2-5 iterations at the defaults) in one batch at the
+// price of a few returned-at-once launches; a tight solve grows the batch to 32.
+static constexpr int kPcgFirstBatch = 8, kPcgMaxBatch = 32;
+
+static pcd_status pcg_check_opts(const pcd_ba_pcg_opts* o) {
+  PCD_REQUIRE(o, "null pointer");
+  PCD_REQUIRE(o->preconditioner == PCD_PRECOND_IDENTITY || o->preconditioner == PCD_PRECOND_SCHUR_JACOBI, "preconditioner");
+  PCD_REQUIRE(o->max_iterations >= 0 && o->min_iterations >= 0, "iteration limits must be >= 0");
+  PCD_REQUIRE(o->q_tolerance == o->q_tolerance && o->r_tolerance == o->r_tolerance, "tolerance is not a number");
+  return PCD_OK;
+}
+
+static pcd_status pcg_state_guard(pcd_ba* b, const char* fn) {
+  if (!b->schur || !b->schur->valid) {
+    set_error("%s: no Schur state (call pcd_ba_schur[_device] first)", fn);
+    return PCD_ERR_INVALID;
+  }
+  const BaSchur& S = *b->schur;
+  if (!S.own_diag || !S.own_off || !S.own_rhs) {
+    set_error("%s: the last Schur call sent %s%s%s to caller memory; the solver reads the handle's own copy "
+              "(leave those outputs NULL)", fn, S.own_diag ? "" : "S_diag ", S.own_off ? "" : "S_off ",
+              S.own_rhs ? "" : "rhs ");
+    return PCD_ERR_INVALID;
+  }
+  return PCD_OK;
+}
+
+static PcgRule pcg_rule(const pcd_ba_pcg_opts* o) {
+  PcgRule r;
+  r.max_iterations = o->max_iterations; r.min_iterations = o->min_iterations;
+  r.q_tolerance = o->q_tolerance; r.r_tolerance = o->r_tolerance;
+  return r;
+}
+
+// preconditioner, x = 0, r = rhs, the scalars of iteration 0
+static pcd_status pcg_begin(pcd_ba* b, const pcd_ba_pcg_opts* o, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  const int ns = S.ns;
+  const size_t n6 = std::max<size_t>(6 * (size_t)ns, 1);
+  const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256));
+  PCD_TRY(S.Minv.reserve(std::max<size_t>(36 * (size_t)ns, 1)));
+  for (DevBuf<double>* d : {&S.cg_x0, &S.cg_x1, &S.cg_r, &S.cg_z, &S.cg_p0, &S.cg_p1, &S.cg_w}) PCD_TRY(d->reserve(n6));
+  PCD_TRY(S.cg_pw.reserve(std::max<size_t>(ns, 1))); PCD_TRY(S.cg_partial.reserve(4 * (size_t)nb));
+  PCD_TRY(S.cg_state.reserve(1)); PCD_TRY(S.cg_info.reserve(1)); PCD_TRY(S.cg_flag.reserve(4));
+  S.cg_it = 0;
+  hipLaunchKernelGGL(k_pcg_init, dim3(nb), dim3(256), 0, s, ns, o->preconditioner, S.Sdiag.p, S.rhs.p, S.Minv.p,
+                     S.cg_x0.p, S.cg_r.p, S.cg_z.p, S.cg_p0.p, S.cg_p1.p, S.cg_partial.p);
+  hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(256), 0, s, (int)nb, S.cg_partial.p, pcg_rule(o), S.cg_state.p);
+  return PCD_OK;
+}
+
+// `count` more iterations (three launches each; all of them return at once when the solve has ended)
+static void pcg_enqueue(pcd_ba* b, const pcd_ba_pcg_opts* o, int count, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  const int ns = S.ns;
+  if (!ns) return;
+  const unsigned nb = div_up((uint64_t)ns, 256);
+  const PcgRule rule = pcg_rule(o);
+  for (int c = 0; c < count; ++c, ++S.cg_it) {
+    const int it = S.cg_it;
+    double* p_old = (it & 1) ? S.cg_p1.p : S.cg_p0.p; double* p_new = (it & 1) ? S.cg_p0.p : S.cg_p1.p;
+    double* x_old = (it & 1) ? S.cg_x1.p : S.cg_x0.p; double* x_new = (it & 1) ? S.cg_x0.p : S.cg_x1.p;
+    hipLaunchKernelGGL(k_pcg_spmv, dim3(div_up((uint64_t)ns, 4)), dim3(256), 0, s, ns, S.cg_state.p, S.row_start.p,
+                       S.row_blk.p, S.row_col.p, S.Sdiag.p, S.Soff.p, S.cg_z.p, p_old, p_new, S.cg_w.p, S.cg_pw.p);
+    hipLaunchKernelGGL(k_pcg_update, dim3(nb), dim3(256), 0, s, ns, S.cg_state.p, S.cg_pw.p, S.Minv.p, S.rhs.p, p_new,
+                       S.cg_w.p, x_old, x_new, S.cg_r.p, S.cg_z.p, S.cg_partial.p);
+    hipLaunchKernelGGL(k_pcg_step, dim3(1), dim3(256), 0, s, (int)nb, it, S.cg_partial.p, rule, S.cg_state.p);
+  }
+}
+
+static void pcg_finish(pcd_ba* b, double* d_dpose, pcd_ba_pcg_info* d_info, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  hipLaunchKernelGGL(k_pcg_finish, dim3(std::max(1u, div_up(6 * (uint64_t)S.ns, 256))), dim3(256), 0, s, S.ns,
+                     S.cg_state.p, S.cg_x0.p, S.cg_x1.p, d_dpose, d_info);
+}
+
+// batches until the device says done; `enqueued` iterations are already in the stream.  One flag copy per batch.
+static pcd_status pcg_run(pcd_ba* b, const pcd_ba_pcg_opts* o, int enqueued, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  int batch = kPcgFirstBatch;
+  if (!enqueued) { pcg_enqueue(b, o, std::min(batch, o->max_iterations), s); enqueued = std::min(batch, o->max_iterations); }
+  for (;;) {
+    PCD_HIP_TRY(hipMemcpyAsync(S.cg_flag.p, &S.cg_state.p->done, sizeof(int), hipMemcpyDeviceToHost, s));
+    PCD_HIP_TRY(hipStreamSynchronize(s));
+    if (S.cg_flag.p[0] || !S.ns || enqueued >= o->max_iterations) return PCD_OK;
+    batch = std::min(2 * batch, kPcgMaxBatch);
+    const int n = std::min(batch, o->max_iterations - enqueued);
+    pcg_enqueue(b, o, n, s);
+    enqueued += n;
+  }
+}
+
+extern "C" {
+
+// ---- point elimination ------------------------------------------------------------------------------
+pcd_status pcd_ba_schur_structure(pcd_ba* b, int32_t* image_slot, int32_t* num_slots, uint64_t* num_pairs,
+                                  int32_t* pair_i, int32_t* pair_j) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_TRY(schur_build(b));
+    const BaSchur& S = *b->schur;
+    if (image_slot) std::memcpy(image_slot, S.h_slot.data(), (size_t)b->I * sizeof(int32_t));
+    if (num_slots) *num_slots = S.ns;
+    if (num_pairs) *num_pairs = S.npairs;
+    if (pair_i && S.npairs) std::memcpy(pair_i, S.h_pair_i.data(), S.npairs * sizeof(int32_t));
+    if (pair_j && S.npairs) std::memcpy(pair_j, S.h_pair_j.data(), S.npairs * sizeof(int32_t));
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_stats(pcd_ba* b, pcd_ba_schur_info* info) {
+  PCD_TRY(schur_guard(b));
+  PCD_REQUIRE(info, "null pointer");
+  std::memset(info, 0, sizeof *info);
+  if (!b->schur || !b->schur->built) return PCD_OK;
+  const BaSchur& S = *b->schur;
+  info->build_ms = S.build_ms;
+  info->num_entries = S.nent;
+  info->scratch_bytes = S.device_bytes();
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(opt && o, "null pointer");
+    PCD_REQUIRE(opt->damping == PCD_DAMP_MARQUARDT || opt->damping == PCD_DAMP_LEVENBERG, "damping");
+    PCD_REQUIRE(opt->mu >= 0.0, "mu must be >= 0");
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(schur_build(b));
+    BaSchur& S = *b->schur;
+    hipStream_t s = (hipStream_t)stream;
+    const int I = b->I, P = b->P, ns = S.ns;
+    const uint64_t O = b->O;
+    const uint32_t nblk = (uint32_t)(ns + S.npairs);
+    const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
+    S.valid = false;
+    PCD_TRY(S.Himg.reserve(36 * (size_t)I)); PCD_TRY(S.gimg.reserve(6 * (size_t)I));
+    PCD_TRY(S.Hpt.reserve(9 * (size_t)P)); PCD_TRY(S.gpt.reserve(3 * (size_t)P));
+    PCD_TRY(S.Wim.reserve(std::max<size_t>(18 * O, 1))); PCD_TRY(S.Y.reserve(std::max<size_t>(18 * O, 1)));
+    PCD_TRY(S.Vinv.reserve(9 * (size_t)P)); PCD_TRY(S.Vg.reserve(3 * (size_t)P)); PCD_TRY(S.Dpt.reserve(3 * (size_t)P));
+    PCD_TRY(S.Dimg.reserve(std::max<size_t>(6 * (size_t)ns, 1)));
+    PCD_TRY(S.Sdiag.reserve(std::max<size_t>(36 * (size_t)ns, 1)));
+    PCD_TRY(S.Soff.reserve(std::max<size_t>(36 * S.npairs, 1)));
+    PCD_TRY(S.rhs.reserve(std::max<size_t>(6 * (size_t)ns, 1)));
+    PCD_TRY(S.skip_partial.reserve(nbp)); PCD_TRY(S.skip_cnt.reserve(1));
+    PCD_TRY(S.md_partial.reserve(nbp)); PCD_TRY(S.md.reserve(1)); PCD_TRY(S.cost.reserve(1));
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    const uint8_t* ctvec = b->has_ctvec ? b->image_const_tvec.p : nullptr;
+    const uint8_t* cpt = b->has_cpt ? b->point_const.p : nullptr;
+    double* Sdiag = o->S_diag ? o->S_diag : S.Sdiag.p;
+    double* Soff = o->S_off ? o->S_off : S.Soff.p;
+    double* rhs = o->rhs ? o->rhs : S.rhs.p;
+    {
+      ScopedKernelTimer t("ba_schur_normal", s);
+      // iota as the W order: W lands in image-major order (k_ba_images' contiguous store path)
+      PCD_TRY(ba_normal_equations(b, S.iota.p, S.Hpt.p, S.gpt.p, o->cost ? o->cost : S.cost.p, S.Himg.p, S.gimg.p,
+                                  S.Wim.p, s));
+    }
+    {
+      ScopedKernelTimer t("ba_schur_eliminate", s);
+      hipLaunchKernelGGL(k_schur_points, dim3(nbp), dim3(256), 0, s, P, S.Hpt.p, S.gpt.p, cpt, opt->mu,
+                         opt->damping, S.Vinv.p, S.Vg.p, S.Dpt.p, S.skip_partial.p);
+      hipLaunchKernelGGL(k_sum_u32, dim3(1), dim3(256), 0, s, S.skip_partial.p, (int)nbp,
+                         o->num_skipped ? reinterpret_cast<unsigned long long*>(o->num_skipped) : S.skip_cnt.p);
+      if (O) hipLaunchKernelGGL(k_schur_obs, dim3(div_up(O, 256)), dim3(256), 0, s, O, b->img_pt.p, S.Wim.p, S.Vinv.p, S.Y.p);
+      SchurBlocks sb;
+      sb.ns = ns; sb.nblk = nblk; sb.blk_start = S.blk_start.p; sb.ent_a = S.ent_a.p; sb.ent_b = S.ent_b.p;
+      sb.pair_ij = S.pair_ij.p; sb.slot_img = S.slot_img.p; sb.img_obs_start = b->img_obs_start.p; sb.img_pt = b->img_pt.p;
+      sb.Y = S.Y.p; sb.Wim = S.Wim.p; sb.Vg = S.Vg.p; sb.Himg = S.Himg.p; sb.gimg = S.gimg.p;
+      sb.image_const_tvec = ctvec; sb.mu = opt->mu; sb.mode = opt->damping;
+      sb.Sdiag = Sdiag; sb.Soff = Soff; sb.rhs = rhs; sb.Dimg = S.Dimg.p;
+      if (nblk) hipLaunchKernelGGL(k_schur_blocks, dim3(div_up(nblk, 4)), dim3(256), 0, s, sb);
+    }
+    if (o->S && ns) {
+      ScopedKernelTimer t("ba_schur_dense", s);
+      const size_t n = 6 * (size_t)ns;
+      PCD_HIP_TRY(hipMemsetAsync(o->S, 0, n * n * sizeof(double), s));
+      hipLaunchKernelGGL(k_schur_dense, dim3(div_up((uint64_t)nblk * 36, 256)), dim3(256), 0, s, ns, nblk, S.pair_ij.p,
+                         Sdiag, Soff, o->S);
+    }
+    PCD_HIP_TRY(hipGetLastError());
+    S.valid = true;
+    S.own_diag = !o->S_diag; S.own_off = !o->S_off; S.own_rhs = !o->rhs;
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(opt && o, "null pointer");
+    PCD_TRY(schur_build(b));
+    BaSchur& S = *b->schur;
+    const size_t n = 6 * (size_t)S.ns;
+    pcd_ba_schur_out d{};
+    if (o->S) { PCD_TRY(S.dense.reserve(std::max<size_t>(n * n, 1))); d.S = S.dense.p; }
+    PCD_TRY(pcd_ba_schur_device(b, opt, &d, nullptr));
+    if (o->cost) PCD_HIP_TRY(hipMemcpy(o->cost, S.cost.p, sizeof(double), hipMemcpyDeviceToHost));
+    if (o->num_skipped) PCD_HIP_TRY(hipMemcpy(o->num_skipped, S.skip_cnt.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (o->S_diag && S.ns) PCD_HIP_TRY(hipMemcpy(o->S_diag, S.Sdiag.p, 36 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
+    if (o->S_off && S.npairs) PCD_HIP_TRY(hipMemcpy(o->S_off, S.Soff.p, 36 * S.npairs * sizeof(double), hipMemcpyDeviceToHost));
+    if (o->rhs && S.ns) PCD_HIP_TRY(hipMemcpy(o->rhs, S.rhs.p, 6 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
+    if (o->S && n) PCD_HIP_TRY(hipMemcpy(o->S, S.dense.p, n * n * sizeof(double), hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipDeviceSynchronize());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_back_substitute_device(pcd_ba* b, const double* d_dpose, double* d_dpoint,
+                                               double* d_model_decrease, void* stream) {
+  PCD_TRY(schur_guard(b));
+  PCD_REFUSE_CAPTURE(stream);
+  if (!b->schur || !b->schur->valid) {
+    set_error("pcd_ba_schur_back_substitute_device: no Schur state (call pcd_ba_schur[_device] first)");
+    return PCD_ERR_INVALID;
+  }
+  BaSchur& S = *b->schur;
+  // a zero-length array may be NULL (an empty torch tensor has data_ptr() 0): ns = 0 when every pose is constant
+  PCD_REQUIRE((d_dpose || S.ns == 0) && (d_dpoint || b->P == 0), "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int P = b->P;
+  const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
+  ScopedKernelTimer t("ba_schur_back", s);
+  hipLaunchKernelGGL(k_schur_back, dim3(nbp), dim3(256), 0, s, P, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p,
+                     S.obs_pos.p, S.img_slot.p, S.Wim.p, S.Vinv.p, S.gpt.p, S.Dpt.p, d_dpose, d_dpoint, S.md_partial.p);
+  if (d_model_decrease)
+    hipLaunchKernelGGL(k_schur_model_decrease, dim3(1), dim3(256), 0, s, S.ns, S.slot_img.p,
+                       b->has_ctvec ? b->image_const_tvec.p : (const uint8_t*)nullptr, S.gimg.p, S.Dimg.p, d_dpose,
+                       S.md_partial.p, (int)nbp, d_model_decrease);
+  PCD_HIP_TRY(hipGetLastError());
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_plus_device(pcd_ba* b, const double* d_dpose, const double* d_dpoint, double* d_poses_out,
+                              double* d_points_out, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(schur_build(b));
+    // zero-length arrays may be NULL (ns = 0 when every pose is constant)
+    PCD_REQUIRE((d_dpose || b->schur->ns == 0) && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) &&
+                (d_points_out || b->P == 0), "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    ScopedKernelTimer t("ba_plus", s);
+    hipLaunchKernelGGL(k_ba_plus, dim3(div_up((uint64_t)b->I + b->P, 256)), dim3(256), 0, s, b->I, b->P,
+                       b->schur->img_slot.p, b->has_ctvec ? b->image_const_tvec.p : (const uint8_t*)nullptr,
+                       b->has_cpt ? b->point_const.p : (const uint8_t*)nullptr, b->poses.p, b->points.p, d_dpose,
+                       d_dpoint, d_poses_out, d_points_out);
+    PCD_HIP_TRY(hipGetLastError());
+    return PCD_OK;
+  });
+}
+
+void pcd_ba_pcg_opts_default(pcd_ba_pcg_opts* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->max_iterations = 100; o->min_iterations = 0; o->preconditioner = PCD_PRECOND_SCHUR_JACOBI;
+  o->q_tolerance = 0.1; o->r_tolerance = -1.0;
+}
+
+pcd_status pcd_ba_schur_solve_pcg_device(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* d_dpose,
+                                         pcd_ba_pcg_info* d_info, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_TRY(pcg_check_opts(opts));
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_pcg_device"));
+    PCD_REQUIRE(d_dpose || b->schur->ns == 0, "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    ScopedKernelTimer t("ba_schur_pcg", s);
+    PCD_TRY(pcg_begin(b, opts, s));
+    PCD_TRY(pcg_run(b, opts, 0, s));
+    pcg_finish(b, d_dpose, d_info, s);
+    PCD_HIP_TRY(hipGetLastError());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_solve_pcg(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* dpose, pcd_ba_pcg_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_TRY(pcg_check_opts(opts));
+    PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_pcg"));
+    BaSchur& S = *b->schur;
+    PCD_REQUIRE(dpose || S.ns == 0, "null pointer");
+    PCD_TRY(S.cg_out.reserve(std::max<size_t>(6 * (size_t)S.ns, 1))); PCD_TRY(S.cg_info.reserve(1));
+    PCD_TRY(pcd_ba_schur_solve_pcg_device(b, opts, S.cg_out.p, S.cg_info.p, nullptr));
+    if (S.ns) PCD_HIP_TRY(hipMemcpy(dpose, S.cg_out.p, 6 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) PCD_HIP_TRY(hipMemcpy(info, S.cg_info.p, sizeof *info, hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipDeviceSynchronize());
+    return PCD_OK;
+  });
+}
+
+void pcd_ba_solve_opts_default(pcd_ba_solve_opts* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->max_num_iterations = 10; o->damping = PCD_DAMP_MARQUARDT;
+  o->initial_radius = 1e4; o->max_radius = 1e16; o->min_radius = 1e-32; o->min_relative_decrease = 1e-3;
+  o->function_tolerance = 0.0; o->gradient_tolerance = 0.0;
+  pcd_ba_pcg_opts_default(&o->linear);
+}
+
+pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_summary* summary,
+                        pcd_ba_solve_iteration* iterations) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(opts, "null pointer");
+    PCD_TRY(pcg_check_opts(&opts->linear));
+    PCD_REQUIRE(opts->damping == PCD_DAMP_MARQUARDT || opts->damping == PCD_DAMP_LEVENBERG, "damping");
+    PCD_REQUIRE(opts->max_num_iterations >= 0, "max_num_iterations must be >= 0");
+    PCD_REQUIRE(opts->initial_radius > 0.0 && opts->max_radius > 0.0, "radius must be > 0");
+    hipStream_t s = nullptr;
+    PCD_REFUSE_CAPTURE(s);
+    PCD_TRY(schur_build(b));
+    BaSchur& S = *b->schur;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int I = b->I, P = b->P, ns = S.ns;
+    const size_t nposes = 7 * (size_t)I, npoints = 3 * (size_t)P;
+    PCD_TRY(S.lm_dpose.reserve(std::max<size_t>(6 * (size_t)ns, 1))); PCD_TRY(S.lm_dpoint.reserve(npoints));
+    PCD_TRY(S.lm_poses.reserve(nposes)); PCD_TRY(S.lm_points.reserve(npoints));
+    PCD_TRY(S.lm_cand_cost.reserve(1)); PCD_TRY(S.lm_rec.reserve(1)); PCD_TRY(S.lm_host.reserve(1));
+    const unsigned ngp = std::max(1u, std::min(1024u, div_up((uint64_t)ns + P, 256)));
+    PCD_TRY(S.lm_gpart.reserve(ngp));
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    PCD_HIP_TRY(hipEventCreate(&ev0));
+    if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); set_error("hipEventCreate failed"); return PCD_ERR_HIP; }
+    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{ev0, ev1};
+    // the accepted parameters: a rejected step copies them back into the handle
+    PCD_HIP_TRY(hipMemcpyAsync(S.lm_poses.p, b->poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
+    PCD_HIP_TRY(hipMemcpyAsync(S.lm_points.p, b->points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
+    pcd_ba_solve_summary sm{};
+    sm.termination = PCD_SOLVE_MAX_ITERATIONS;
+    double radius = opts->initial_radius, factor = 2.0, linear_ms = 0.0;
+    const pcd_ba_pcg_opts* lo = &opts->linear;
+    const uint8_t* ctvec = b->has_ctvec ? b->image_const_tvec.p : nullptr;
+    const uint8_t* cpt = b->has_cpt ? b->point_const.p : nullptr;
+    pcd_ba_out co{};
+    co.cost = S.lm_cand_cost.p;
+    for (int it = 0; it < opts->max_num_iterations; ++it) {
+      if (radius < opts->min_radius) { sm.termination = PCD_SOLVE_MIN_RADIUS; break; }
+      pcd_ba_schur_opts so{};
+      so.mu = 1.0 / radius; so.damping = opts->damping;
+      pcd_ba_schur_out none{};
+      PCD_TRY(pcd_ba_schur_device(b, &so, &none, s));
+      hipLaunchKernelGGL(k_ba_grad_max, dim3(ngp), dim3(256), 0, s, ns, S.slot_img.p, ctvec, S.gimg.p, P, cpt, S.gpt.p,
+                         S.lm_gpart.p);
+      PCD_HIP_TRY(hipEventRecord(ev0, s));
+      PCD_TRY(pcg_begin(b, lo, s));
+      int enq = std::min(kPcgFirstBatch, lo->max_iterations);
+      pcg_enqueue(b, lo, enq, s);
+      PCD_HIP_TRY(hipEventRecord(ev1, s));
+      // the tail is enqueued behind the first batch without looking at the flag: at the defaults the PCG has ended
+      // by then and the iteration costs one copy; otherwise the batches go on and the tail runs once more
+      const LmRecord* rec = S.lm_host.p;
+      for (;;) {
+        pcg_finish(b, S.lm_dpose.p, S.cg_info.p, s);
+        PCD_TRY(pcd_ba_schur_back_substitute_device(b, S.lm_dpose.p, S.lm_dpoint.p, S.md.p, s));
+        PCD_TRY(pcd_ba_plus_device(b, S.lm_dpose.p, S.lm_dpoint.p, b->poses.p, b->points.p, s));
+        PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
+        hipLaunchKernelGGL(k_ba_lm_record, dim3(1), dim3(256), 0, s, S.cost.p, S.lm_cand_cost.p, S.md.p, S.lm_gpart.p,
+                           (int)ngp, S.skip_cnt.p, S.cg_info.p, S.lm_rec.p);
+        PCD_HIP_TRY(hipMemcpyAsync(S.lm_host.p, S.lm_rec.p, sizeof(LmRecord), hipMemcpyDeviceToHost, s));
+        PCD_HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) linear_ms += ms;
+        if (rec->pcg.termination >= 0 || enq >= lo->max_iterations) break;
+        // the step just tried came from an unfinished solve: back to the accepted parameters, finish the solve
+        PCD_HIP_TRY(hipMemcpyAsync(b->poses.p, S.lm_poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipMemcpyAsync(b->points.p, S.lm_points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipEventRecord(ev0, s));
+        PCD_TRY(pcg_run(b, lo, enq, s));
+        enq = lo->max_iterations;
+        PCD_HIP_TRY(hipEventRecord(ev1, s));
+      }
+      PCD_HIP_TRY(hipGetLastError());
+      if (it == 0) sm.initial_cost = sm.final_cost = rec->cost;
+      const bool restore_only = opts->gradient_tolerance > 0.0 && rec->gradient_max <= opts->gradient_tolerance;
+      pcd_ba_solve_iteration r{};
+      r.cost = rec->cost; r.candidate_cost = rec->candidate_cost; r.model_decrease = rec->model_decrease;
+      r.gradient_max_norm = rec->gradient_max; r.num_skipped = rec->num_skipped;
+      r.linear_iterations = rec->pcg.iterations; r.linear_termination = rec->pcg.termination;
+      const bool solved = rec->pcg.termination != PCD_PCG_BREAKDOWN;
+      const double rho = (solved && r.model_decrease > 0.0) ? (r.cost - r.candidate_cost) / r.model_decrease
+                                                            : -std::numeric_limits<double>::infinity();
+      r.relative_decrease = rho;
+      r.accepted = !restore_only && rho > opts->min_relative_decrease;
+      if (r.accepted) {
+        radius = std::min(opts->max_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3.0)));
+        factor = 2.0;
+        PCD_HIP_TRY(hipMemcpyAsync(S.lm_poses.p, b->poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipMemcpyAsync(S.lm_points.p, b->points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
+      } else {
+        PCD_HIP_TRY(hipMemcpyAsync(b->poses.p, S.lm_poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipMemcpyAsync(b->points.p, S.lm_points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
+      }
+      if (restore_only) { sm.termination = PCD_SOLVE_GRADIENT_TOLERANCE; break; }
+      if (!r.accepted) { radius /= factor; factor *= 2.0; }
+      r.radius = radius;
+      if (iterations) iterations[it] = r;
+      sm.num_iterations = it + 1;
+      if (r.accepted) {
+        sm.num_accepted++;
+        sm.final_cost = r.candidate_cost;
+        if (opts->function_tolerance > 0.0 && std::fabs(r.cost - r.candidate_cost) <= opts->function_tolerance * r.cost) {
+          sm.termination = PCD_SOLVE_FUNCTION_TOLERANCE;
+          break;
+        }
+      }
+    }
+    PCD_HIP_TRY(hipStreamSynchronize(s));
+    S.valid = false;   // the Schur state belongs to parameters the loop has moved on from
+    sm.linear_solver_ms = linear_ms;
+    sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (summary) *summary = sm;
+    return PCD_OK;
+  });
+}
+
+}  // extern "C"

@@ -64,12 +64,13 @@ def point_inverse(Hpt, Dpt, point_const):
 
 
 class NormalEquations:
-    """the oracle's blocks of one scene at its parameters, with the damping of (mu, mode) applied"""
+    """the oracle's blocks of one scene at its parameters, with the damping of (mu, mode) applied; `blocks` =
+    (cost, H_img, g_img, H_pt, g_pt, W) puts blocks from elsewhere (the device's evaluation) in their place"""
 
-    def __init__(self, oracle, scene, mu, mode="marquardt"):
+    def __init__(self, oracle, scene, mu, mode="marquardt", blocks=None):
         self.pr = problem(scene)
-        ob = oracle.BA(**scene)
-        self.cost, self.Himg, self.gimg, self.Hpt, self.gpt, self.W = ob.normal_equations(want_w=True)
+        self.cost, self.Himg, self.gimg, self.Hpt, self.gpt, self.W = \
+            blocks if blocks is not None else oracle.BA(**scene).normal_equations(want_w=True)
         pr = self.pr
         self.Dimg = damping(np.diagonal(self.Himg, axis1=1, axis2=2)[pr["slot_img"]], mu, mode) * pr["active"]
         self.Dpt = damping(np.diagonal(self.Hpt, axis1=1, axis2=2), mu, mode)
@@ -333,6 +334,41 @@ def camera_scene(oracle, models, seed, I=6, P=150, lidar_frac=1.0):
     s["image_const_tvec"] = (rng.integers(1, 8, I) * (rng.random(I) < 0.4)).astype(np.uint8)
     s["point_const"] = (rng.random(P) < 0.1).astype(np.uint8)
     return reproject(oracle, s, rng)
+
+
+def shared_launch_scene(seed=461):
+    """the smallest scene that reaches all four launches of the normal equations (point pass, cost sum, image pass,
+    image reduction) with every branch of their grids: 3 images one metre apart looking along +z, image 0 with a constant
+    pose; 70 points in front of all three (two 64-track slices, the second partial), point 5 constant, LiDAR terms on 6
+    points; every point is observed once in images 0 and 1 and 15 times in image 2, which so holds 1050 observations:
+    two image segments of at most 1024.  Observations are grouped by track, so the caller's order is not image-major.
+    Three views of every point: no point is rank-deficient at mu = 0."""
+    from pcdhip import synth
+    rng = np.random.default_rng(seed)
+    I, P, rep = 3, 70, 15
+    poses = np.zeros((I, 7))
+    poses[:, 0] = 1.0
+    poses[:, 4] = -np.arange(I)                                   # t = -R C, camera centres (i, 0, 0)
+    points = np.stack([rng.uniform(-3, 5, P), rng.uniform(-2, 2, P), rng.uniform(6, 20, P)], axis=1)
+    obs_image = np.tile(np.r_[0, 1, np.full(rep, 2)], P).astype(np.int32)
+    obs_point = np.repeat(np.arange(P), 2 + rep).astype(np.int32)
+    Pc = points[obs_point] + poses[obs_image, 4:]
+    x, y = synth._opencv_project(synth.OPENCV_PARAMS, Pc[:, 0] / Pc[:, 2], Pc[:, 1] / Pc[:, 2])
+    obs_xy = np.stack([x, y], axis=1) + rng.uniform(-2, 2, (obs_image.size, 2))
+    poses[:, 1:4] = rng.normal(0, 0.004, (I, 3))                  # what BA starts from: ~0.5 degrees, 5 cm off
+    poses[:, :4] /= np.linalg.norm(poses[:, :4], axis=1, keepdims=True)
+    poses[:, 4:] += rng.normal(0, 0.05, (I, 3))
+    lidar_point = np.array([0, 5, 17, 63, 64, 69], np.int32)
+    nrm = rng.normal(size=(lidar_point.size, 3))
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    lp = points[lidar_point] + rng.normal(0, 0.05, (lidar_point.size, 3))
+    point_const = np.zeros(P, np.uint8)
+    point_const[5] = 1
+    return dict(cam_model=np.array([4], np.int32), cam_params_list=[synth.OPENCV_PARAMS], poses=poses,
+                image_camera=np.zeros(I, np.int32), points=points, obs_image=obs_image, obs_point=obs_point, obs_xy=obs_xy,
+                lidar_point=lidar_point, lidar_abcd=np.concatenate([nrm, -np.sum(nrm * lp, 1, keepdims=True)], axis=1),
+                lidar_weight=np.full(lidar_point.size, 100.0), image_const_pose=np.array([1, 0, 0], np.uint8),
+                point_const=point_const)
 
 
 def degenerate_scene(oracle, seed, n_single=8, n_lidar=6):

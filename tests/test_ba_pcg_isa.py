@@ -1,4 +1,4 @@
-"""ISA of the reduced-solve kernels (csrc/ba.hip: the block-sparse PCG, the gradient max-norm and the LM record,
+"""ISA of the reduced-solve kernels (csrc/ba_solve.hip: the block-sparse PCG, the gradient max-norm and the LM record,
 DESIGN 4.3a), checked without a GPU: they compile for gfx950 with no scratch, and their VGPR counts are pinned from
 above at what the build gives.  k_pcg_spmv holds one 6x6 block (36 fp64) per lane plus the partner's direction and six
 accumulators: 120 VGPRs, 4 wavefronts per SIMD; k_pcg_init keeps the block's factor and its inverse in registers."""
@@ -25,8 +25,8 @@ VGPRS = {                     # counts of the gfx950 build (hipcc -O3)
 
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "ba.s"
-    subprocess.check_call([HIPCC] + FLAGS + [os.path.join(ROOT, "colmap-pcd_amd", "csrc", "ba.hip"), "-o", str(out)])
+    out = tmp_path_factory.mktemp("isa") / "ba_solve.s"
+    subprocess.check_call([HIPCC] + FLAGS + [os.path.join(ROOT, "colmap-pcd_amd", "csrc", "ba_solve.hip"), "-o", str(out)])
     return _kernels(out.read_text())
 
 

@@ -195,6 +195,21 @@ def test_pivot_rule_is_stable_under_rounding(oracle, seed):
         assert not skip[full].any()
 
 
+def test_shared_launch_scene_skips_no_point(oracle):
+    """ref.shared_launch_scene is what its docstring says, and the reference elimination skips none of its points at
+    mu = 0: the GPU comparison on it (test_ba_schur_gpu.py) covers all 70"""
+    s = ref.shared_launch_scene()
+    assert s["poses"].shape == (3, 7) and s["points"].shape == (70, 3)
+    assert s["image_const_pose"].tolist() == [1, 0, 0] and np.flatnonzero(s["point_const"]).tolist() == [5]
+    per_image = np.bincount(s["obs_image"], minlength=3)
+    assert per_image.tolist() == [70, 70, 1050] and 1024 < per_image[2] <= 2 * 1024
+    assert 0 < s["lidar_point"].size < 10
+    assert not np.array_equal(np.argsort(s["obs_image"], kind="stable"), np.arange(s["obs_image"].size))
+    ne = ref.NormalEquations(oracle, s, 0.0)
+    assert not ne.skipped.any()
+    assert ne.elig.sum() == 69 * 16 and np.isfinite(ne.schur_blocks()["S"]).all()
+
+
 def test_pivot_rule_is_scale_invariant():
     """scaling a point's coordinates (V -> S V S, S diagonal) does not change the decision"""
     rng = np.random.default_rng(3)

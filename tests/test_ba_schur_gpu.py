@@ -5,6 +5,8 @@ Bounds: S_diag, S_off, rhs and the dense S within 1e-9 relative (scale-aware flo
 (GPU Schur -> numpy solve -> GPU back-substitution) within 1e-8 of the dense solve of the whole damped system where that
 system is well conditioned, and within 1e-8 of the reference back-substitution of the same pose step everywhere;
 plus within 1e-14."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -103,6 +105,30 @@ def test_schur_parity(gpu, oracle, case):
     _close(points.cpu().numpy(), rx, 1e-14, "plus (points)")
     cpose = np.flatnonzero(s["image_const_pose"]) if s.get("image_const_pose") is not None else []
     assert np.array_equal(poses.cpu().numpy()[cpose], np.asarray(s["poses"])[cpose])
+    ba.close()
+
+
+def test_schur_and_evaluate_share_the_normal_equations(gpu):
+    """pcd_ba_evaluate and pcd_ba_schur reach the point and image passes through the same launches: on one handle the
+    Schur call's cost is the evaluated cost bit for bit, and its S and rhs at mu = 0 are what the reference builds from
+    the evaluated blocks -- W in the caller's order there, image-major inside the Schur call.  The scene
+    (ref.shared_launch_scene) takes every launch: two point slices, two segments in one image, a constant pose, a
+    constant point, LiDAR terms; test_ba_schur_cpu.py checks that the reference skips none of its 70 points."""
+    s = ref.shared_launch_scene()
+    ba = gpu.BA(**s)
+    ev = ba.evaluate(("cost", "H_img", "g_img", "H_pt", "g_pt", "W"))
+    ns = 2
+    out = dict(cost=np.full(1, np.nan), rhs=np.full((ns, 6), np.nan), S=np.full((6 * ns, 6 * ns), np.nan),
+               num_skipped=np.full(1, 2 ** 63, np.uint64))
+    o = gpu.BASchurOut(*[gpu._ptr(out.get(n)) for n, _ in gpu.BASchurOut._fields_])
+    gpu._check(gpu.lib().pcd_ba_schur(ba._h, C.byref(gpu.BASchurOpts(0.0, gpu.DAMP_MARQUARDT)), C.byref(o)))
+    assert ba.schur_structure()["num_slots"] == ns
+    assert out["cost"].view(np.uint64)[0] == ev["cost"].view(np.uint64)[0]
+    ne = ref.NormalEquations(None, s, 0.0, blocks=[ev[k] for k in ("cost", "H_img", "g_img", "H_pt", "g_pt", "W")])
+    assert not ne.skipped.any() and int(out["num_skipped"][0]) == 0
+    sb = ne.schur_blocks()
+    _close(out["S"], sb["S"], 1e-9, "dense S from the evaluated blocks")
+    _close(out["rhs"], sb["rhs"], 1e-9, "rhs from the evaluated blocks")
     ba.close()
 
 

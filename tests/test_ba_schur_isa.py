@@ -1,4 +1,4 @@
-"""ISA of the point-elimination kernels (csrc/ba.hip), checked without a GPU: no scratch (a spill would
+"""ISA of the point-elimination kernels (csrc/ba_solve.hip), checked without a GPU: no scratch (a spill would
 put per-lane fp64 traffic on the memory path these kernels are bound by) and the VGPR counts stated below, pinned from
 above so that growth shows up here rather than as a loss of wavefronts in flight.  k_schur_blocks holds 36 fp64
 accumulators plus the 2 x 18 doubles of an entry: 156 VGPRs, 3 wavefronts per SIMD."""
@@ -25,8 +25,8 @@ VGPRS = {                     # counts of the gfx950 build (hipcc -O3), DESIGN 4
 
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "ba.s"
-    subprocess.check_call([HIPCC] + FLAGS + [os.path.join(ROOT, "colmap-pcd_amd", "csrc", "ba.hip"), "-o", str(out)])
+    out = tmp_path_factory.mktemp("isa") / "ba_solve.s"
+    subprocess.check_call([HIPCC] + FLAGS + [os.path.join(ROOT, "colmap-pcd_amd", "csrc", "ba_solve.hip"), "-o", str(out)])
     return _kernels(out.read_text())
 
 

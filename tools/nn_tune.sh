@@ -15,7 +15,7 @@ if [ "$mode" = build ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -I$R/include \
       -DPCD_KTILE=$t -DPCD_BRICK_MINWAVES=$w -c $P/csrc/nn.hip -o $P/variants/nn_${t}_${w}.o
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $P/variants/libpcdhip_${t}_${w}.so \
-      $P/csrc/common.o $P/csrc/cloud.o $P/variants/nn_${t}_${w}.o $P/csrc/assoc.o $P/csrc/ba.o
+      $P/csrc/common.o $P/csrc/cloud.o $P/variants/nn_${t}_${w}.o $P/csrc/assoc.o $P/csrc/ba.o $P/csrc/ba_solve.o
     echo "built $v"
   done
 else

@@ -10,7 +10,7 @@ if [ "$1" = build ]; then
   mkdir -p variants
   for k in $VARIANTS; do
     /opt/rocm/bin/hipcc $FLAGS -DPCD_SIFT_ABLATE=$k ${SIFT_EXTRA} -c csrc/sift.hip -o variants/sift_$k.o
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o variants/libpcdhip_sift$k.so csrc/common.o csrc/cloud.o csrc/nn.o csrc/assoc.o csrc/ba.o variants/sift_$k.o csrc/proj.o csrc/shards.o
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o variants/libpcdhip_sift$k.so csrc/common.o csrc/cloud.o csrc/nn.o csrc/assoc.o csrc/ba.o csrc/ba_solve.o variants/sift_$k.o csrc/proj.o csrc/shards.o
   done
 else
   for k in $VARIANTS; do
