@@ -105,15 +105,29 @@ __device__ __forceinline__ double wave_uniform(double v) {
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
+// The same value, in its SGPR pair and opaque to the optimiser from here on: inside a loop it keeps arithmetic on
+// wave-uniform doubles (VALU-only, so its results would sit in VGPRs) from being hoisted out and held across the loop.
+__device__ __forceinline__ double sgpr_pin(double v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
+// A copy of a per-lane value made at this point of the program (not where the register allocator would put it)
+template <typename T>
+__device__ __forceinline__ T vgpr_pin(T v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 // Coalesced store of one row of N doubles per lane, rows of consecutive lanes adjacent in memory
 // (out[(row0 + lane) * N + k] = v[k] for lane < cnt): the rows are transposed through a per-wavefront LDS
 // scratch of 64 * N doubles and leave as 16-B-per-lane stores of consecutive addresses (1 KiB per instruction)
 // instead of N stores that each touch 64 different cache lines.  Every lane of the wavefront must call it.
+// (lane = threadIdx.x & 63, handed in by a caller that wants the addresses derived from its own copy of it)
 template <int N>
 __device__ __forceinline__ void wave_store_rows(double* __restrict__ out, uint64_t row0, int cnt, const double (&v)[N],
-                                                double* __restrict__ lds) {
+                                                double* __restrict__ lds, int lane) {
   static_assert(N % 2 == 0, "rows are moved in 16-byte units");
-  const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int k = 0; k < N; ++k) lds[lane * N + k] = v[k];
   // one wavefront: LDS operations complete in order; the fences keep the compiler from moving the reads up
@@ -131,59 +145,127 @@ __device__ __forceinline__ void wave_store_rows(double* __restrict__ out, uint64
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();   // the scratch may be rewritten after this
 }
+template <int N>
+__device__ __forceinline__ void wave_store_rows(double* __restrict__ out, uint64_t row0, int cnt, const double (&v)[N],
+                                                double* __restrict__ lds) {
+  wave_store_rows<N>(out, row0, cnt, v, lds, (int)(threadIdx.x & 63));
+}
 
 // ------------------------------------------------------------- points ------
+// One LiDAR term of a track into its sums (the cost, and with BLOCKS the 3x3 block and the gradient)
+template <bool BLOCKS>
+__device__ __forceinline__ void points_add_lidar(const BaDev& d, const double X[3], const double abcd[4], double w, bool cpt,
+                                                 double& cost, double H[6], double g[3]) {
+  double r, J[3];
+  lidar_eval(X, abcd, w, 0, r, J);
+  double rho0, rho1;
+  loss_eval(d.loss_type, d.loss_scale, r * r, rho0, rho1);
+  cost += 0.5 * rho0;
+  if (BLOCKS && !cpt) {
+    const double sr = sqrt(rho1);
+    const double rc = sr * r;
+    J[0] *= sr; J[1] *= sr; J[2] *= sr;
+    H[0] += J[0] * J[0]; H[1] += J[0] * J[1]; H[2] += J[0] * J[2];
+    H[3] += J[1] * J[1]; H[4] += J[1] * J[2]; H[5] += J[2] * J[2];
+    g[0] += J[0] * rc; g[1] += J[1] * rc; g[2] += J[2] * rc;
+  }
+}
+
+// number of LiDAR terms of track t, plane and weight of the first (half 0 takes the LiDAR terms; wave-uniform branch)
+__device__ __forceinline__ void load_lidar_first(const BaDev& d, int half, int t, uint32_t& ln, double lf[5]) {
+  if (half != 0 || !d.L) return;   // a handle without LiDAR terms has no such arrays
+  const size_t ntr = 64 * (size_t)d.nslices;
+  ln = d.pt_lidar_cnt[t];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) lf[k] = d.pt_lidar_first[k * ntr + t];
+}
+
 // BLOCKS = false: residual-only pass (cost), what Ceres asks for when it evaluates a trial step
 // Two threads per track (the even and the odd observations of its sliced-ELL column): the kernel is bound by the
 // latency of each track's serial chain of observations, not by arithmetic or bytes, so halving the chain and doubling
 // the wavefronts in flight took it from 0.18 to ~0.1 ms on the bench scene.  The halves live in different wavefronts
 // of the workgroup (threads 0-63 / 64-127 = halves 0 / 1 of slice 2b, 128-255 of slice 2b + 1); half 1 hands its sums
 // over through LDS and half 0 adds them in a fixed order and also takes the track's LiDAR terms.
+//
+// Load order.  The kernel is bound by the round trips a wavefront waits for one after the other, so every load is
+// issued as soon as its address is known, next to the others of the same round trip:
+//   trip 1   pt_order[t], the first row's sell_img and sell_xy, the number of LiDAR terms of the track and the first
+//            of them (half 0; BaDev::pt_lidar_cnt / pt_lidar_first are stored in track order: the address needs only t)
+//   trip 2   points[p], point_const[p], the first row's pose, the second row's sell_img
+//   trip k   the pose and sell_xy of row k - 1, the sell_img of row k: the image of every row is read one row ahead
+// (before: index, wait, pose, wait for every row, and three more dependent trips for the LiDAR term after the barrier).
+// Indices past the end of the slice are replaced by slot 0, so no branch stands around the loads; what they return is
+// not used.  Same values into the same arithmetic in the same order: the results are bit-identical.
 template <int MODEL, bool BLOCKS, bool SHARED>
 __global__ __launch_bounds__(256) void k_ba_points(BaDev d, double* __restrict__ Hpt, double* __restrict__ gpt,
                                                    double* __restrict__ cost_partial) {
   __shared__ double s_half[2][64][9];
-  const int sl = threadIdx.x >> 7, half = (threadIdx.x >> 6) & 1, lane = threadIdx.x & 63;
+  // slice and half are those of the wavefront: uniform for the compiler too (scalar loads of the slice bounds, scalar branches)
+  const int sl = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7));
+  const int half = __builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 6) & 1));
+  const int lane = threadIdx.x & 63;
   const int slice = blockIdx.x * 2 + sl;
   const int t = slice * 64 + lane;
   double cost = 0.0;
   double H[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
   int p = -1;
-  bool cpt = true;
+  unsigned cpt_b = 1;                       // point_const[p] as loaded (converted where it is used: no wait behind the load)
   double X[3] = {0, 0, 0};
+  uint32_t ln = 0;                          // LiDAR terms of the track (half 0)
+  double lf[5] = {0, 0, 0, 0, 0};           // the first of them: plane and weight
+  // Per-image cameras keep up to twelve more VGPRs per lane in the loop (OPENCV: 138 with the term held across it), so
+  // there the term is read behind the loop instead: still one coalesced trip, in flight across the barrier.
+  constexpr bool kLidarEarly = SHARED;
   BaCam<MODEL, SHARED> cam(d);
   if (slice < d.nslices) {
-    p = d.pt_order[t];
     const uint32_t s0 = d.slice_start[slice], s1 = d.slice_start[slice + 1];
+    uint32_t sb = s0 + 64u * half;          // this wavefront's part of the row: lane l has slot sb + l; a slice holds whole rows
+    // (the row goes out ahead of pt_order[t]: the wait for p then covers im on every path, LiDAR terms or none, and the
+    // first row's pose loads stand behind no other wait)
+    const uint32_t sc = sb < s1 ? sb + lane : 0u;
+    int im = d.sell_img[sc];
+    double ox = d.sell_xy[2 * (size_t)sc], oy = d.sell_xy[2 * (size_t)sc + 1];
+    p = d.pt_order[t];
+    if (kLidarEarly) load_lidar_first(d, half, t, ln, lf);
     if (p >= 0) {
       X[0] = d.points[3 * (size_t)p]; X[1] = d.points[3 * (size_t)p + 1]; X[2] = d.points[3 * (size_t)p + 2];
-      cpt = d.point_const && d.point_const[p];
+      cpt_b = d.point_const ? d.point_const[p] : 0u;
     }
-    for (uint32_t s = s0 + lane + 64u * half; s < s1; s += 128) {
-      const int im = d.sell_img[s];
-      if (im < 0) continue;  // padding of a shorter track
-      ReprojBlock b;
-      double q[4], pose[7];
-      cam.of_image(d, im);
-      load_pose(d, im, pose);
-      eval_block_at(cam, pose, X, d.sell_xy[2 * (size_t)s], d.sell_xy[2 * (size_t)s + 1], b, q);
-      double rho0, rho1;
-      loss_eval(d.loss_type, d.loss_scale, b.r[0] * b.r[0] + b.r[1] * b.r[1], rho0, rho1);
-      cost += 0.5 * rho0;
-      if (BLOCKS && !cpt) {
-        const double sr = sqrt(rho1);
-        double J[6];
+    while (sb < s1) {
+      const uint32_t sn = sb + 128;
+      const int im_next = d.sell_img[sn < s1 ? sn + lane : 0u];
+      if (im >= 0) {   // not the padding of a shorter track
+        ReprojBlock b;
+        double q[4], pose[7];
+        cam.of_image(d, im);
+        load_pose(d, im, pose);
+        eval_block_at(cam, pose, X, ox, oy, b, q);
+        double rho0, rho1;
+        loss_eval(d.loss_type, d.loss_scale, b.r[0] * b.r[0] + b.r[1] * b.r[1], rho0, rho1);
+        cost += 0.5 * rho0;
+        cpt_b = vgpr_pin(cpt_b);   // tested here, in every row: ahead of the loop the test would wait for the byte
+        if (BLOCKS && cpt_b == 0) {
+          const double sr = sqrt(rho1);
+          double J[6];
 #pragma unroll
-        for (int r = 0; r < 2; ++r)
+          for (int r = 0; r < 2; ++r)
 #pragma unroll
-          for (int k = 0; k < 3; ++k)
-            J[3 * r + k] = sr * (b.M[3 * r] * b.D[k] + b.M[3 * r + 1] * b.D[3 + k] + b.M[3 * r + 2] * b.D[6 + k]);
-        const double r0 = sr * b.r[0], r1 = sr * b.r[1];
-        H[0] += J[0] * J[0] + J[3] * J[3]; H[1] += J[0] * J[1] + J[3] * J[4]; H[2] += J[0] * J[2] + J[3] * J[5];
-        H[3] += J[1] * J[1] + J[4] * J[4]; H[4] += J[1] * J[2] + J[4] * J[5]; H[5] += J[2] * J[2] + J[5] * J[5];
-        g[0] += J[0] * r0 + J[3] * r1; g[1] += J[1] * r0 + J[4] * r1; g[2] += J[2] * r0 + J[5] * r1;
+            for (int k = 0; k < 3; ++k)
+              J[3 * r + k] = sr * (b.M[3 * r] * b.D[k] + b.M[3 * r + 1] * b.D[3 + k] + b.M[3 * r + 2] * b.D[6 + k]);
+          const double r0 = sr * b.r[0], r1 = sr * b.r[1];
+          H[0] += J[0] * J[0] + J[3] * J[3]; H[1] += J[0] * J[1] + J[3] * J[4]; H[2] += J[0] * J[2] + J[3] * J[5];
+          H[3] += J[1] * J[1] + J[4] * J[4]; H[4] += J[1] * J[2] + J[4] * J[5]; H[5] += J[2] * J[2] + J[5] * J[5];
+          g[0] += J[0] * r0 + J[3] * r1; g[1] += J[1] * r0 + J[4] * r1; g[2] += J[2] * r0 + J[5] * r1;
+        }
+      }
+      sb = sn;
+      im = vgpr_pin(im_next);   // the copy is made here, not behind the load below
+      if (sb < s1) {            // goes out with the row's pose loads
+        ox = d.sell_xy[2 * ((size_t)sb + lane)];
+        oy = d.sell_xy[2 * ((size_t)sb + lane) + 1];
       }
     }
+    if (!kLidarEarly) load_lidar_first(d, half, t, ln, lf);
   }
   if (BLOCKS && half == 1) {
 #pragma unroll
@@ -200,22 +282,15 @@ __global__ __launch_bounds__(256) void k_ba_points(BaDev d, double* __restrict__
       for (int k = 0; k < 3; ++k) g[k] += s_half[sl][lane][6 + k];
     }
     if (p >= 0) {
-      for (uint32_t e = d.pt_lidar_start[p]; e < d.pt_lidar_start[p + 1]; ++e) {
-        const uint32_t l = d.pt_lidar_list[e];
-        const double abcd[4] = {d.lidar_abcd[4 * (size_t)l], d.lidar_abcd[4 * (size_t)l + 1],
-                                d.lidar_abcd[4 * (size_t)l + 2], d.lidar_abcd[4 * (size_t)l + 3]};
-        double r, J[3];
-        lidar_eval(X, abcd, d.lidar_w[l], 0, r, J);
-        double rho0, rho1;
-        loss_eval(d.loss_type, d.loss_scale, r * r, rho0, rho1);
-        cost += 0.5 * rho0;
-        if (BLOCKS && !cpt) {
-          const double sr = sqrt(rho1);
-          const double rc = sr * r;
-          J[0] *= sr; J[1] *= sr; J[2] *= sr;
-          H[0] += J[0] * J[0]; H[1] += J[0] * J[1]; H[2] += J[0] * J[2];
-          H[3] += J[1] * J[1]; H[4] += J[1] * J[2]; H[5] += J[2] * J[2];
-          g[0] += J[0] * rc; g[1] += J[1] * rc; g[2] += J[2] * rc;
+      if (ln) {
+        // colmap-pcd adds one plane per point: that one is in registers; any further term takes the list
+        points_add_lidar<BLOCKS>(d, X, lf, lf[4], cpt_b != 0, cost, H, g);
+        const uint32_t le = ln > 1 ? d.pt_lidar_start[p] : 0u;
+        for (uint32_t e = le + 1; e < le + ln; ++e) {
+          const uint32_t l = d.pt_lidar_list[e];
+          const double abcd[4] = {d.lidar_abcd[4 * (size_t)l], d.lidar_abcd[4 * (size_t)l + 1],
+                                  d.lidar_abcd[4 * (size_t)l + 2], d.lidar_abcd[4 * (size_t)l + 3]};
+          points_add_lidar<BLOCKS>(d, X, abcd, d.lidar_w[l], cpt_b != 0, cost, H, g);
         }
       }
       if (BLOCKS && Hpt) {
@@ -351,8 +426,43 @@ constexpr int kRowColStride = 132;   // doubles between two staged columns: 128 
 static_assert(7 * kRowColStride <= 64 * 18, "the staged rows share the W transpose scratch");
 typedef double mfma_f64x4 __attribute__((ext_vector_type(4)));
 
+// The camera of a workgroup-uniform image: model id and parameters, read once through wave-uniform addresses at the
+// top of the kernel and held in SGPRs.  MODEL = -1 reads the slots its model does not have from slot 0 (never used).
+template <int MODEL>
+struct BaImageCam {
+  static constexpr int K = MODEL >= 0 ? cam_num_params(MODEL >= 0 ? MODEL : 0) : PCD_CAM_JAC_STRIDE;
+  int model = MODEL;
+  double v[K];
+  __device__ __forceinline__ BaImageCam(const BaDev& d, int im) {
+    const int cm = d.image_cam[im];
+    if (MODEL < 0) model = d.cam_model[cm];
+    const double* p = d.cam_params + d.cam_off[cm];
+    const int kn = MODEL >= 0 ? K : cam_num_params(model);
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_uniform(p[k < kn ? k : 0]);
+  }
+};
+
+// Where the constant-point flag of point pt is read from.  A handle without constant points (has_pc false, uniform)
+// reads a byte of the point itself instead -- its line is being fetched anyway -- and ignores it: the load stands in
+// the instruction stream unconditionally, and a branch around it would make every wait behind it a wait for all.
+__device__ __forceinline__ const uint8_t* const_byte(const BaDev& d, bool has_pc, uint32_t pt) {
+  return has_pc ? d.point_const + pt : reinterpret_cast<const uint8_t*>(d.points + 3 * (size_t)pt);
+}
+
 // Launch bound: the OPENCV instantiation with W (the one that was measured) fits 4 wavefronts per SIMD (<= 128 VGPRs)
-// without scratch and is faster there; every other instantiation is left to the register allocator.
+// without scratch and is faster there; every other instantiation is left to the register allocator (with the pose and
+// the camera in SGPRs the other compiled-in models with W come to 116-120 VGPRs on their own).
+//
+// Load order.  The image is fixed for the workgroup, so its pose and camera are read ONCE, ahead of the loop (scalar
+// loads, SGPRs; inside the loop they would have to be vector loads of uniform addresses behind the W stores, a
+// three-deep chain image -> camera -> offset -> parameters per iteration).  They are still read at every launch:
+// pcd_ba_set_* and the device LM update them in place.  The observation indices of every iteration are known up front
+// (e0 + threadIdx.x), so img_pt / img_xy / img_obs of iteration i + 1 are issued before the Jacobian arithmetic of
+// iteration i, and the points[pt] / point_const[pt] gather of i + 1 before the row staging, the MFMA block and the W
+// store of i.  Indices past the end of the segment are clamped to its last observation: no branch around the loads
+// (a constant-pose image that only writes its zero W rows loads as well), and what the surplus lanes and the surplus
+// last prefetch return is not used.  Same values into the same arithmetic.
 template <int MODEL, bool WANT_W>
 __global__ __launch_bounds__(256, (MODEL == 4 && WANT_W) ? 4 : 1) void k_ba_images(BaDev d, double* __restrict__ partial,
                                                                        double* __restrict__ W_o) {
@@ -361,21 +471,61 @@ __global__ __launch_bounds__(256, (MODEL == 4 && WANT_W) ? 4 : 1) void k_ba_imag
   const int im = (int)d.seg_img[blockIdx.x];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // uniform for the compiler
-  const bool cpose = d.image_const_pose && d.image_const_pose[im];
+  // the two flag bytes of the image: read unconditionally (from the segment table when the handle has no such array,
+  // and then ignored), so that they travel with the loads below instead of each behind a branch and a wait of its own
+  const uint8_t* any_byte = reinterpret_cast<const uint8_t*>(d.seg_img + blockIdx.x);
+  const unsigned cpose_b = *(d.image_const_pose ? d.image_const_pose + im : any_byte);
+  const unsigned tmask_b = *(d.image_const_tvec ? d.image_const_tvec + im : any_byte);
   mfma_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-  const unsigned tmask = d.image_const_tvec ? d.image_const_tvec[im] : 0u;
   const uint32_t e_beg = d.seg_begin[blockIdx.x];
   const uint32_t e_end = min(d.seg_begin[blockIdx.x + 1], d.img_obs_start[im + 1]);   // segments never span images
+  BaImageCam<MODEL> cam(d, im);
+  double q[4], tv[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = wave_uniform(d.poses[7 * (size_t)im + k]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) tv[k] = wave_uniform(d.poses[7 * (size_t)im + 4 + k]);
   // operand address of this lane: column l & 7 (7 -> 0), row 2 k + h of the step's 8
   const int op_k = lane >> 4, op_c = (lane & 7) == 7 ? 0 : (lane & 7);
   const double* op_src = s_w[wave] + op_c * kRowColStride + 2 * op_k + ((lane >> 3) & 1);
+  const bool cpose = d.image_const_pose && cpose_b;
+  const unsigned tmask = d.image_const_tvec ? tmask_b : 0u;
   if (!cpose || WANT_W) {
+    const uint32_t e_last = e_end - 1;   // a segment holds at least one observation
+    const bool has_pc = WANT_W && d.point_const;
+    // the first iteration's loads
+    // (indices and the point_const byte stay as loaded until their first use: converting them where they are loaded
+    // would put a wait right behind the load)
+    uint32_t pt = 0, o = 0, pc = 0;
+    double ox = 0.0, oy = 0.0, X[3] = {0.0, 0.0, 0.0};
+    {
+      const uint32_t ec = min(e_beg + threadIdx.x, e_last);
+      pt = (uint32_t)d.img_pt[ec]; ox = d.img_xy[2 * (size_t)ec]; oy = d.img_xy[2 * (size_t)ec + 1];
+      if (WANT_W) o = d.img_obs[ec];
+      X[0] = d.points[3 * (size_t)pt]; X[1] = d.points[3 * (size_t)pt + 1]; X[2] = d.points[3 * (size_t)pt + 2];
+      if (WANT_W) pc = *const_byte(d, has_pc, pt);
+    }
     // every lane runs every iteration (the row staging and the W store below are whole-wavefront operations)
     for (uint32_t e0 = e_beg; e0 < e_end; e0 += 256) {
       const uint32_t e = e0 + threadIdx.x;
       const bool active = e < e_end;
       // observations left for this wavefront (uniform): 0 for the wavefronts past the end in the last iteration
       const int cnt = (int)min(64u, e_end > e0 + wave * 64u ? e_end - (e0 + wave * 64u) : 0u);
+      // Pose and parameters pass through sgpr_pin once per iteration: the uniform factors of the Jacobians (rotation
+      // polynomial, doubled coefficients) are then recomputed per iteration, as before.  Hoisted out of the loop they
+      // cost ~45 VGPRs and the fourth wavefront per SIMD.
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q[k] = sgpr_pin(q[k]);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) tv[k] = sgpr_pin(tv[k]);
+#pragma unroll
+      for (int k = 0; k < BaImageCam<MODEL>::K; ++k) cam.v[k] = sgpr_pin(cam.v[k]);
+      // the next iteration's indices
+      const uint32_t en = (e_last >= 256u && e <= e_last - 256u) ? e + 256u : e_last;
+      uint32_t pt_n = 0, o_n = 0;
+      double ox_n = 0.0, oy_n = 0.0;
+      pt_n = (uint32_t)d.img_pt[en]; ox_n = d.img_xy[2 * (size_t)en]; oy_n = d.img_xy[2 * (size_t)en + 1];
+      if (WANT_W) o_n = d.img_obs[en];
       double w[18];
 #pragma unroll
       for (int k = 0; k < 18; ++k) w[k] = 0.0;   // constant pose / constant point: the coupling is zero
@@ -383,11 +533,8 @@ __global__ __launch_bounds__(256, (MODEL == 4 && WANT_W) ? 4 : 1) void k_ba_imag
 #pragma unroll
       for (int k = 0; k < 12; ++k) J[k] = 0.0;
       if (active && !cpose) {
-        const int pt = d.img_pt[e];
-        const double X[3] = {d.points[3 * (size_t)pt], d.points[3 * (size_t)pt + 1], d.points[3 * (size_t)pt + 2]};
         ReprojBlock b;
-        double q[4];
-        eval_block<MODEL>(d, im, X, d.img_xy[2 * (size_t)e], d.img_xy[2 * (size_t)e + 1], b, q);
+        reproj_eval(cam.model, cam.v, q, tv, X, ox, oy, b);
         double rho0, rho1;
         loss_eval(d.loss_type, d.loss_scale, b.r[0] * b.r[0] + b.r[1] * b.r[1], rho0, rho1);
         const double sr = sqrt(rho1);
@@ -403,15 +550,27 @@ __global__ __launch_bounds__(256, (MODEL == 4 && WANT_W) ? 4 : 1) void k_ba_imag
           }
         r0 = sr * b.r[0];
         r1 = sr * b.r[1];
-        if (WANT_W && !(d.point_const && d.point_const[pt])) {
+        if (WANT_W && !(has_pc && pc != 0)) {
 #pragma unroll
           for (int a = 0; a < 6; ++a)
 #pragma unroll
             for (int c = 0; c < 3; ++c) w[3 * a + c] = J[a] * (sr * JX[c]) + J[6 + a] * (sr * JX[3 + c]);
         }
       }
+      // the next iteration's point: in flight under the staging, the MFMA block and the W store
+      {
+        X[0] = d.points[3 * (size_t)pt_n]; X[1] = d.points[3 * (size_t)pt_n + 1]; X[2] = d.points[3 * (size_t)pt_n + 2];
+        if (WANT_W) pc = *const_byte(d, has_pc, pt_n);
+        // the prefetched values move into the loop's registers HERE (vgpr_pin): left to the end of the iteration the
+        // copies stand behind a wait for everything in flight, the W stores included
+        ox = vgpr_pin(ox_n);
+        oy = vgpr_pin(oy_n);
+      }
+      // the LDS addresses of the staging and of the W transpose are formed from this copy of the lane in every iteration
+      // (held across the loop they are a dozen VGPRs)
+      const int lane_i = vgpr_pin(lane);
       if (!cpose && cnt > 0) {   // uniform; a constant pose keeps its sums at exactly zero, an idle wavefront adds nothing
-        double2* row_dst = reinterpret_cast<double2*>(s_w[wave]) + lane;
+        double2* row_dst = reinterpret_cast<double2*>(s_w[wave]) + lane_i;
 #pragma unroll
         for (int c = 0; c < 6; ++c) row_dst[c * (kRowColStride / 2)] = make_double2(J[c], J[6 + c]);
         row_dst[6 * (kRowColStride / 2)] = make_double2(r0, r1);
@@ -429,13 +588,14 @@ __global__ __launch_bounds__(256, (MODEL == 4 && WANT_W) ? 4 : 1) void k_ba_imag
       }
       if (WANT_W) {
         // rows of this wavefront: observation indices in the caller's order
-        const uint32_t o = active ? d.img_obs[e] : 0u;
-        const uint32_t o_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)o);
-        const bool contiguous = __all(!active || o == o_first + (uint32_t)lane);
+        const uint32_t oa = active ? o : 0u;
+        o = vgpr_pin(o_n);
+        const uint32_t o_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)oa);
+        const bool contiguous = __all(!active || oa == o_first + (uint32_t)lane_i);
         if (contiguous) {
-          wave_store_rows<18>(W_o, o_first, cnt, w, s_w[wave]);
+          wave_store_rows<18>(W_o, o_first, cnt, w, s_w[wave], lane_i);
         } else if (active) {
-          double* dst = W_o + 18 * (size_t)o;
+          double* dst = W_o + 18 * (size_t)oa;
 #pragma unroll
           for (int k = 0; k < 18; ++k) dst[k] = w[k];
         }
@@ -1168,6 +1328,7 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
   for (uint64_t k = 0; d->camera_refine && k < d->cam_params_len; ++k) b->refines_intrinsics |= d->camera_refine[k] != 0;
 
   std::vector<uint32_t> st, li;
+  std::vector<int> order;   // thread of k_ba_points -> point
   // ---- per-track sliced ELL in order of track length ----
   build_csr(d->obs_point, b->O, b->P, st, li);
   {
@@ -1179,7 +1340,7 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
     for (size_t k = 1; k < bucket.size(); ++k) bucket[k] += bucket[k - 1];
     const int nslices = (b->P + 63) / 64;
     b->nslices = nslices;
-    std::vector<int> order((size_t)nslices * 64, -1);
+    order.assign((size_t)nslices * 64, -1);
     for (int p = 0; p < b->P; ++p) order[bucket[st[p + 1] - st[p]]++] = p;
     std::vector<uint32_t> slice_start(nslices + 1, 0);
     for (int s = 0; s < nslices; ++s) {
@@ -1211,6 +1372,21 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
   }
   build_csr(d->lidar_point, b->L, b->P, st, li);
   UP(pt_lidar_start, st.data(), st.size()); UP(pt_lidar_list, li.data(), li.size());
+  if (b->L) {   // the terms of every track in thread order: how many, and the first (BaDev::pt_lidar_cnt, pt_lidar_first)
+    const size_t ntr = order.size();
+    std::vector<double> first(5 * ntr, 0.0);
+    std::vector<uint32_t> cnt(ntr, 0);
+    for (size_t t = 0; t < ntr; ++t) {
+      const int p = order[t];
+      if (p < 0 || st[p] == st[p + 1]) continue;
+      cnt[t] = st[p + 1] - st[p];
+      const uint32_t l = li[st[p]];
+      for (int k = 0; k < 4; ++k) first[k * ntr + t] = d->lidar_abcd[4 * (size_t)l + k];
+      first[4 * ntr + t] = d->lidar_weight[l];
+    }
+    UP(pt_lidar_first, first.data(), first.size());
+    UP(pt_lidar_cnt, cnt.data(), cnt.size());
+  }
   // ---- per-image contiguous copies ----
   build_csr(d->obs_image, b->O, b->I, st, li);
   {

@@ -21,6 +21,11 @@ struct BaDev {
   const int* sell_img;            // [nslots]      image of the observation, -1 = padding
   const double* sell_xy;          // [nslots][2]
   const uint32_t* pt_lidar_start; const uint32_t* pt_lidar_list;
+  // The LiDAR terms in the order of k_ba_points' threads (both nullptr when L == 0).  The terms are constants of the
+  // handle (set in pcd_ba_create only), so the kernel reads its one plane per point coalesced and ahead of everything
+  // else, not through point -> list -> term; only a second or third term of a point goes through the lists.
+  const uint32_t* pt_lidar_cnt;   // [nslices*64] number of LiDAR terms of the track of thread t
+  const double* pt_lidar_first;   // [5][nslices*64] plane (a, b, c, d) and weight of the first of them, component-major
   const uint32_t* img_obs_start;  // [I+1]
   const int* img_pt;              // [O] point of the e-th observation of the image-major order
   const uint32_t* img_obs;        // [O] its index in the caller's observation order (W is written there)
@@ -69,11 +74,11 @@ struct pcd_ba {
   int uniform_model = -1;  // >= 0: every camera has this model
   int shared_cam = -1;     // >= 0: every image maps to this camera (BaDev::shared_cam)
   pcd::DevBuf<int> cam_model, cam_off, image_cam, obs_image, obs_point, lidar_point, pt_order, sell_img, img_pt;
-  pcd::DevBuf<double> cam_params, poses, points, obs_xy, lidar_abcd, lidar_w, sell_xy, img_xy;
+  pcd::DevBuf<double> cam_params, poses, points, obs_xy, lidar_abcd, lidar_w, sell_xy, img_xy, pt_lidar_first;
   pcd::DevBuf<uint8_t> image_const_pose, image_const_tvec, point_const;
   bool has_cpose = false, has_ctvec = false, has_cpt = false;
   pcd::DevBuf<uint32_t> slice_start, pt_lidar_start, pt_lidar_list, img_obs_start, img_obs, cam_img_start, cam_img_list;
-  pcd::DevBuf<uint32_t> seg_img, seg_begin, img_seg_start;
+  pcd::DevBuf<uint32_t> seg_img, seg_begin, img_seg_start, pt_lidar_cnt;
   uint32_t nseg = 0;
   pcd::DevBuf<double> img_partial;
   pcd::DevBuf<uint8_t> cam_refine;
@@ -109,6 +114,7 @@ struct pcd_ba {
     d.lidar_point = lidar_point.p; d.lidar_abcd = lidar_abcd.p; d.lidar_w = lidar_w.p;
     d.pt_order = pt_order.p; d.slice_start = slice_start.p; d.sell_img = sell_img.p; d.sell_xy = sell_xy.p;
     d.pt_lidar_start = pt_lidar_start.p; d.pt_lidar_list = pt_lidar_list.p;
+    d.pt_lidar_first = L ? pt_lidar_first.p : nullptr; d.pt_lidar_cnt = L ? pt_lidar_cnt.p : nullptr;
     d.img_obs_start = img_obs_start.p; d.img_pt = img_pt.p; d.img_xy = img_xy.p; d.img_obs = img_obs.p;
     d.seg_img = seg_img.p; d.seg_begin = seg_begin.p; d.img_seg_start = img_seg_start.p;
     d.cam_refine = has_refine ? cam_refine.p : nullptr; d.cam_img_start = cam_img_start.p; d.cam_img_list = cam_img_list.p;
