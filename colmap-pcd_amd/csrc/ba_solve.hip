@@ -1,6 +1,7 @@
 // ba_solve.hip -- the device solver of bundle adjustment: point elimination of the damped normal
 // equations into the reduced camera system (k_schur_*), the manifold update (k_ba_plus), the block-sparse
-// preconditioned CG on that system (k_pcg_*) and the Levenberg-Marquardt loop around them (pcd_ba_solve).
+// preconditioned CG on that system (k_pcg_*), the direct solve of it (the handle's blocks or the caller's dense S into
+// the scratch of ba_chol.hip, which factors and solves) and the Levenberg-Marquardt loop around them (pcd_ba_solve).
 //
 // The blocks it eliminates come from ba.hip, which this unit reaches through two calls only: ba_normal_equations
 // (ba_handle.h) for H, g, W and the cost, and pcd_ba_evaluate_device for the cost of a trial step.  No evaluation
@@ -10,6 +11,7 @@
 #include <cmath>
 #include <limits>
 
+#include "ba_chol.h"
 #include "ba_handle.h"
 #include "common.h"
 
@@ -207,6 +209,27 @@ __global__ __launch_bounds__(256) void k_schur_dense(int ns, uint32_t nblk, cons
     const double v = Soff[36 * (size_t)pq + k];
     S[(6 * i + r) * n + 6 * j + s] = v;
     S[(6 * j + s) * n + 6 * i + r] = v;
+  }
+}
+
+// The handle's blocks into the padded scratch of the direct solve (ba_chol.h; the caller zeroed it): lower triangle
+// only -- a diagonal block's entries r >= s, a pair block (i < j) transposed into rows of j -- and the right-hand side
+// row.  thread = (block, entry); the first 6 ns threads also carry the right-hand side.
+__global__ __launch_bounds__(256) void k_chol_fill_blocks(int ns, uint32_t nblk, const uint32_t* __restrict__ pair_ij,
+                                                          const double* __restrict__ Sdiag, const double* __restrict__ Soff,
+                                                          const double* __restrict__ rhs, int np, double* __restrict__ A) {
+  const uint64_t t = blockIdx.x * (uint64_t)256 + threadIdx.x;
+  if (t >= (uint64_t)nblk * 36) return;
+  const size_t ld = (size_t)np;
+  if (t < 6 * (uint64_t)ns) A[ld * ld + t] = rhs[t];
+  const uint32_t blk = (uint32_t)(t / 36);
+  const int k = (int)(t - 36 * (uint64_t)blk), r = k / 6, s = k - 6 * (k / 6);
+  if (blk < (uint32_t)ns) {
+    if (r >= s) A[(6 * (size_t)blk + r) * ld + 6 * (size_t)blk + s] = Sdiag[36 * (size_t)blk + k];
+  } else {
+    const uint32_t pq = blk - (uint32_t)ns;
+    const size_t i = pair_ij[2 * (size_t)pq], j = pair_ij[2 * (size_t)pq + 1];
+    A[(6 * j + s) * ld + 6 * i + r] = Soff[36 * (size_t)pq + k];
   }
 }
 
@@ -680,6 +703,14 @@ __global__ __launch_bounds__(256) void k_ba_lm_record(const double* __restrict__
   }
 }
 
+// the record of a direct solve in the form k_ba_lm_record reads: 0 iterations, termination = pcd_ba_chol_status
+__global__ void k_chol_lm_info(const pcd_ba_chol_info* __restrict__ c, pcd_ba_pcg_info* __restrict__ out) {
+  pcd_ba_pcg_info o;
+  o.iterations = 0; o.termination = c->status; o.precond_fallbacks = 0;
+  o.rhs_norm = 0.0; o.residual_norm = 0.0; o.q = 0.0; o.step_dot_residual = 0.0;
+  *out = o;
+}
+
 // Host-built structure (first Schur call) and the numeric state of the last Schur call
 struct BaSchur {
   bool built = false;
@@ -706,13 +737,17 @@ struct BaSchur {
   DevBuf<double> lm_dpose, lm_dpoint, lm_poses, lm_points, lm_cand_cost, lm_gpart;
   DevBuf<LmRecord> lm_rec;
   PinnedBuf<LmRecord> lm_host;
+  // direct solve (pcd_ba_schur_solve_cholesky*): the padded dense scratch of ba_chol.h, allocated on first use
+  DevBuf<double> chol_A, chol_S, chol_rhs, chol_out;   // chol_S / chol_rhs (freed after each call) / chol_out: staging of the host form
+  DevBuf<pcd_ba_chol_info> chol_info, chol_info_out;
   // device memory held (pcd_ba_schur_stats): every DevBuf above but the 8 bytes of skip_cnt
   uint64_t device_bytes() const {
     auto sum = [](const auto&... b) { return (uint64_t(0) + ... + (b.n * sizeof(*b.p))); };
     return sum(img_slot, slot_img, blk_start, ent_a, ent_b, pair_ij, iota, obs_pos, Himg, gimg, Hpt, gpt, Wim, Y, Vinv,
                Vg, Dpt, Dimg, Sdiag, Soff, rhs, md_partial, md, skip_partial, cost, dense, row_start, row_blk, row_col,
                Minv, cg_x0, cg_x1, cg_r, cg_z, cg_p0, cg_p1, cg_w, cg_pw, cg_partial, cg_out, cg_state, cg_info,
-               lm_dpose, lm_dpoint, lm_poses, lm_points, lm_cand_cost, lm_gpart, lm_rec);
+               lm_dpose, lm_dpoint, lm_poses, lm_points, lm_cand_cost, lm_gpart, lm_rec, chol_A, chol_S, chol_rhs,
+               chol_out, chol_info, chol_info_out);
   }
 };
 
@@ -960,6 +995,26 @@ static pcd_status pcg_run(pcd_ba* b, const pcd_ba_pcg_opts* o, int enqueued, hip
   }
 }
 
+// Direct solve: scratch on first use, fill (the handle's blocks when d_S is null, else the caller's dense S), factor and
+// solve.  No synchronisation; the status record stays in S.chol_info.
+static pcd_status chol_solve(pcd_ba* b, const double* d_S, const double* d_rhs, double* d_dpose,
+                             pcd_ba_chol_info* d_info, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  const int ns = S.ns, n = 6 * ns;
+  PCD_TRY(S.chol_A.reserve(chol_scratch_doubles(n)));
+  PCD_TRY(S.chol_info.reserve(1));
+  chol_begin(S.chol_A.p, n, S.chol_info.p, s);
+  if (d_S) {
+    chol_fill_dense(S.chol_A.p, n, d_S, d_rhs, s);
+  } else {
+    const uint32_t nblk = (uint32_t)(ns + S.npairs);
+    hipLaunchKernelGGL(k_chol_fill_blocks, dim3(div_up((uint64_t)nblk * 36, 256)), dim3(256), 0, s, ns, nblk,
+                       S.pair_ij.p, S.Sdiag.p, S.Soff.p, S.rhs.p, chol_padded(n), S.chol_A.p);
+  }
+  chol_factor_solve(S.chol_A.p, n, S.chol_info.p, d_dpose, d_info, s);
+  return PCD_OK;
+}
+
 extern "C" {
 
 // ---- point elimination ------------------------------------------------------------------------------
@@ -1166,6 +1221,63 @@ pcd_status pcd_ba_schur_solve_pcg(pcd_ba* b, const pcd_ba_pcg_opts* opts, double
   });
 }
 
+pcd_status pcd_ba_schur_solve_cholesky_device(pcd_ba* b, const double* d_S, const double* d_rhs, double* d_dpose,
+                                              pcd_ba_chol_info* d_info, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(!d_S == !d_rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
+    PCD_REFUSE_CAPTURE(stream);
+    if (d_S) PCD_TRY(schur_build(b));
+    else PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_cholesky_device"));
+    BaSchur& S = *b->schur;
+    PCD_REQUIRE(d_dpose || S.ns == 0, "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (S.ns == 0) {   // nothing to solve, nothing launched
+      if (d_info) {
+        pcd_ba_chol_info o{};
+        o.status = PCD_CHOL_OK; o.failed_column = -1;
+        PCD_HIP_TRY(hipMemcpyAsync(d_info, &o, sizeof o, hipMemcpyHostToDevice, s));
+        PCD_HIP_TRY(hipStreamSynchronize(s));   // o leaves scope
+      }
+      return PCD_OK;
+    }
+    ScopedKernelTimer t("ba_schur_cholesky", s);
+    PCD_TRY(chol_solve(b, d_S, d_rhs, d_dpose, d_info, s));
+    PCD_HIP_TRY(hipGetLastError());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_solve_cholesky(pcd_ba* b, const double* Sh, const double* rhs, double* dpose,
+                                       pcd_ba_chol_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b));
+    PCD_REQUIRE(!Sh == !rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
+    if (Sh) PCD_TRY(schur_build(b));
+    else PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_cholesky"));
+    BaSchur& S = *b->schur;
+    const size_t n = 6 * (size_t)S.ns;
+    PCD_REQUIRE(dpose || n == 0, "null pointer");
+    PCD_TRY(S.chol_out.reserve(std::max<size_t>(n, 1))); PCD_TRY(S.chol_info_out.reserve(1));
+    const double* d_S = nullptr; const double* d_rhs = nullptr;
+    if (Sh && n) {
+      PCD_TRY(S.chol_S.reserve(n * n)); PCD_TRY(S.chol_rhs.reserve(n));
+      PCD_HIP_TRY(hipMemcpy(S.chol_S.p, Sh, n * n * sizeof(double), hipMemcpyHostToDevice));
+      PCD_HIP_TRY(hipMemcpy(S.chol_rhs.p, rhs, n * sizeof(double), hipMemcpyHostToDevice));
+      d_S = S.chol_S.p; d_rhs = S.chol_rhs.p;
+    } else if (Sh) {   // an empty system given in caller memory: the device form only looks at the pointers
+      d_S = S.chol_out.p; d_rhs = S.chol_out.p;
+    }
+    PCD_TRY(pcd_ba_schur_solve_cholesky_device(b, d_S, d_rhs, S.chol_out.p, S.chol_info_out.p, nullptr));
+    if (n) PCD_HIP_TRY(hipMemcpy(dpose, S.chol_out.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (info) PCD_HIP_TRY(hipMemcpy(info, S.chol_info_out.p, sizeof *info, hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipDeviceSynchronize());
+    S.chol_S.release(); S.chol_rhs.release();   // n^2 of staging: not kept beside the padded scratch
+    return PCD_OK;
+  });
+}
+
 void pcd_ba_solve_opts_default(pcd_ba_solve_opts* o) {
   if (!o) return;
   std::memset(o, 0, sizeof *o);
@@ -1184,6 +1296,8 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
     PCD_REQUIRE(opts->damping == PCD_DAMP_MARQUARDT || opts->damping == PCD_DAMP_LEVENBERG, "damping");
     PCD_REQUIRE(opts->max_num_iterations >= 0, "max_num_iterations must be >= 0");
     PCD_REQUIRE(opts->initial_radius > 0.0 && opts->max_radius > 0.0, "radius must be > 0");
+    PCD_REQUIRE(opts->linear_solver == PCD_LINEAR_PCG || opts->linear_solver == PCD_LINEAR_CHOLESKY, "linear_solver");
+    const bool direct = opts->linear_solver == PCD_LINEAR_CHOLESKY;
     hipStream_t s = nullptr;
     PCD_REFUSE_CAPTURE(s);
     PCD_TRY(schur_build(b));
@@ -1221,15 +1335,27 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
       hipLaunchKernelGGL(k_ba_grad_max, dim3(ngp), dim3(256), 0, s, ns, S.slot_img.p, ctvec, S.gimg.p, P, cpt, S.gpt.p,
                          S.lm_gpart.p);
       PCD_HIP_TRY(hipEventRecord(ev0, s));
-      PCD_TRY(pcg_begin(b, lo, s));
-      int enq = std::min(kPcgFirstBatch, lo->max_iterations);
-      pcg_enqueue(b, lo, enq, s);
+      int enq = lo->max_iterations;
+      if (direct) {   // fill + factor + solve: an exact step, so there is no second batch below
+        PCD_TRY(S.cg_info.reserve(1));
+        if (ns) {
+          ScopedKernelTimer t("ba_schur_cholesky", s);
+          PCD_TRY(chol_solve(b, nullptr, nullptr, S.lm_dpose.p, nullptr, s));
+          hipLaunchKernelGGL(k_chol_lm_info, dim3(1), dim3(1), 0, s, S.chol_info.p, S.cg_info.p);
+        } else {
+          PCD_HIP_TRY(hipMemsetAsync(S.cg_info.p, 0, sizeof(pcd_ba_pcg_info), s));   // 0 iterations, PCD_CHOL_OK
+        }
+      } else {
+        PCD_TRY(pcg_begin(b, lo, s));
+        enq = std::min(kPcgFirstBatch, lo->max_iterations);
+        pcg_enqueue(b, lo, enq, s);
+      }
       PCD_HIP_TRY(hipEventRecord(ev1, s));
       // the tail is enqueued behind the first batch without looking at the flag: at the defaults the PCG has ended
       // by then and the iteration costs one copy; otherwise the batches go on and the tail runs once more
       const LmRecord* rec = S.lm_host.p;
       for (;;) {
-        pcg_finish(b, S.lm_dpose.p, S.cg_info.p, s);
+        if (!direct) pcg_finish(b, S.lm_dpose.p, S.cg_info.p, s);
         PCD_TRY(pcd_ba_schur_back_substitute_device(b, S.lm_dpose.p, S.lm_dpoint.p, S.md.p, s));
         PCD_TRY(pcd_ba_plus_device(b, S.lm_dpose.p, S.lm_dpoint.p, b->poses.p, b->points.p, s));
         PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
@@ -1255,7 +1381,7 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
       r.cost = rec->cost; r.candidate_cost = rec->candidate_cost; r.model_decrease = rec->model_decrease;
       r.gradient_max_norm = rec->gradient_max; r.num_skipped = rec->num_skipped;
       r.linear_iterations = rec->pcg.iterations; r.linear_termination = rec->pcg.termination;
-      const bool solved = rec->pcg.termination != PCD_PCG_BREAKDOWN;
+      const bool solved = direct ? rec->pcg.termination == PCD_CHOL_OK : rec->pcg.termination != PCD_PCG_BREAKDOWN;
       const double rho = (solved && r.model_decrease > 0.0) ? (r.cost - r.candidate_cost) / r.model_decrease
                                                             : -std::numeric_limits<double>::infinity();
       r.relative_decrease = rho;

@@ -136,11 +136,30 @@ PCG_INFO_DTYPE = np.dtype([("iterations", np.int32), ("termination", np.int32), 
 assert PCG_INFO_DTYPE.itemsize == C.sizeof(BAPcgInfo) == 48
 
 
+LINEAR_PCG, LINEAR_CHOLESKY = 0, 1
+_LINEAR = {"pcg": LINEAR_PCG, "cholesky": LINEAR_CHOLESKY}
+CHOL_OK, CHOL_NOT_POSITIVE_DEFINITE = 0, 1
+
+
+class BACholInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("failed_column", C.c_int32), ("n", C.c_int32), ("n_padded", C.c_int32),
+                ("panels", C.c_int32), ("min_pivot", C.c_double), ("max_pivot", C.c_double)]
+
+
+CHOL_INFO_DTYPE = np.dtype([("status", np.int32), ("failed_column", np.int32), ("n", np.int32), ("n_padded", np.int32),
+                            ("panels", np.int32), ("pad", np.int32), ("min_pivot", np.float64),
+                            ("max_pivot", np.float64)])
+assert CHOL_INFO_DTYPE.itemsize == C.sizeof(BACholInfo) == 40
+
+
 class BASolveOpts(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int32), ("damping", C.c_int32), ("initial_radius", C.c_double),
                 ("max_radius", C.c_double), ("min_radius", C.c_double), ("min_relative_decrease", C.c_double),
                 ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double), ("linear", BAPcgOpts),
-                ("reserved", C.c_int32 * 8)]
+                ("linear_solver", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+assert C.sizeof(BASolveOpts) == 152   # linear_solver took the first word of reserved: the size did not change
 
 
 class BASolveIteration(C.Structure):
@@ -203,6 +222,7 @@ ABI_SYMBOLS = [
     "pcd_ba_schur_back_substitute_device", "pcd_ba_plus_device", "pcd_ba_schur_stats",
     "pcd_ba_pcg_opts_default", "pcd_ba_schur_solve_pcg_device", "pcd_ba_schur_solve_pcg", "pcd_ba_get_parameters",
     "pcd_ba_solve_opts_default", "pcd_ba_solve",
+    "pcd_ba_schur_solve_cholesky_device", "pcd_ba_schur_solve_cholesky",
     "pcd_normals_options_default", "pcd_cloud_estimate_normals_device", "pcd_cloud_estimate_normals",
 ]
 
@@ -299,6 +319,10 @@ def lib():
         L.pcd_ba_solve_opts_default.argtypes = [C.POINTER(BASolveOpts)]
         L.pcd_ba_solve_opts_default.restype = None
         L.pcd_ba_solve.argtypes = [C.c_void_p, C.POINTER(BASolveOpts), C.POINTER(BASolveSummary), C.c_void_p]
+    if hasattr(L, "pcd_ba_schur_solve_cholesky_device"):
+        L.pcd_ba_schur_solve_cholesky_device.argtypes = [C.c_void_p] * 6
+        L.pcd_ba_schur_solve_cholesky.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(BACholInfo)]
     _LIB = L
     return L
 
@@ -1161,6 +1185,50 @@ class BA:
         _check(lib().pcd_ba_schur_solve_pcg(self._h, C.byref(o), _vp(dpose), C.byref(info)))
         return dpose, _pcg_info(info)
 
+    def schur_solve_cholesky(self, S=None, rhs=None, dpose=None):
+        """direct solve of the reduced system (blocked fp64 Cholesky on the device).  Without arguments: the handle's own
+        blocks of the last schur() call (whose S_diag / S_off / rhs must have stayed in the handle).  With S [6 ns][6 ns]
+        and rhs (torch device tensors, fp64): that system; only the lower triangle of S is read and S is not modified.
+        Returns (dpose [ns][6] torch device tensor -- zeros when the factorisation failed --, info dict: status,
+        failed_column, n, n_padded, panels, min_pivot, max_pivot)"""
+        torch, dev, stream = self._torch()
+        if not hasattr(self, "_schur_dims"):
+            st = self.schur_structure()
+            self._schur_dims = (st["num_slots"], st["pairs"].shape[0])
+        ns = self._schur_dims[0]
+        if S is not None:
+            S = S.to(device=dev, dtype=torch.float64).contiguous()
+            if tuple(S.shape) != (6 * ns, 6 * ns):
+                raise ValueError(f"S must be [{6 * ns}][{6 * ns}], got {tuple(S.shape)}")
+        if rhs is not None:
+            rhs = rhs.to(device=dev, dtype=torch.float64).contiguous()
+            if rhs.numel() != 6 * ns:
+                raise ValueError(f"rhs must have {6 * ns} entries, got {rhs.numel()}")
+        if dpose is None:
+            dpose = torch.empty((ns, 6), dtype=torch.float64, device=dev)
+        d_info = torch.zeros(C.sizeof(BACholInfo), dtype=torch.uint8, device=dev)
+        # an empty tensor (ns = 0) has a null data pointer, which would read as "not given": lend it one element
+        one = torch.zeros(1, dtype=torch.float64, device=dev)
+        ps = None if S is None else _ptr(S if S.numel() else one)
+        pr = None if rhs is None else _ptr(rhs if rhs.numel() else one)
+        _check(lib().pcd_ba_schur_solve_cholesky_device(self._h, ps, pr, _ptr(dpose), _ptr(d_info), C.c_void_p(stream)))
+        i = d_info.cpu().numpy().view(CHOL_INFO_DTYPE)[0]
+        return dpose, {k: (float(i[k]) if CHOL_INFO_DTYPE[k] == np.float64 else int(i[k]))
+                       for k in CHOL_INFO_DTYPE.names if k != "pad"}
+
+    def schur_solve_cholesky_host(self, S=None, rhs=None):
+        """pcd_ba_schur_solve_cholesky, the host form of the C ABI that C and C++ callers use: the same solve with host
+        arrays (numpy S, rhs or neither; numpy dpose, info dict).  Here for the tests of that entry point; Python
+        callers want schur_solve_cholesky, which keeps everything on the device."""
+        ns = self.schur_structure()["num_slots"]
+        dpose = np.zeros((ns, 6))
+        info = BACholInfo()
+        S = None if S is None else np.ascontiguousarray(S, np.float64)
+        rhs = None if rhs is None else np.ascontiguousarray(rhs, np.float64)
+        _check(lib().pcd_ba_schur_solve_cholesky(self._h, None if S is None else _vp(S), None if rhs is None else _vp(rhs),
+                                                 _vp(dpose), C.byref(info)))
+        return dpose, {n: getattr(info, n) for n, _ in BACholInfo._fields_}
+
     def get_parameters(self):
         """the handle's current parameters, device -> host: (poses [I][7], points [P][3]) numpy"""
         poses, points = np.empty((self.I, 7)), np.empty((self.P, 3))
@@ -1205,10 +1273,13 @@ def _pcg_info(i):
 
 
 def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max_radius=None, min_radius=None,
-             min_relative_decrease=None, function_tolerance=None, gradient_tolerance=None, linear=None):
+             min_relative_decrease=None, function_tolerance=None, gradient_tolerance=None, linear=None,
+             linear_solver="pcg"):
     """pcd_ba_solve: the LM loop in the library (Schur, PCG, back-substitution, cost pass; no torch).  Options left
-    None keep pcd_ba_solve_opts_default; linear is a dict of pcg_opts() arguments.  Returns (summary dict, list of one
-    dict per iteration); the handle holds the accepted parameters (BA.get_parameters())."""
+    None keep pcd_ba_solve_opts_default; linear is a dict of pcg_opts() arguments.  linear_solver="cholesky" takes the
+    exact step of the library's blocked Cholesky instead of the PCG's inexact one (linear_iterations is then 0 and
+    linear_termination a CHOL_* status).  Returns (summary dict, list of one dict per iteration); the handle holds
+    the accepted parameters (BA.get_parameters())."""
     L = lib()
     o = BASolveOpts()
     L.pcd_ba_solve_opts_default(C.byref(o))
@@ -1221,6 +1292,7 @@ def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max
                     ("gradient_tolerance", gradient_tolerance)):
         if v is not None:
             setattr(o, name, float(v))
+    o.linear_solver = _LINEAR[linear_solver] if isinstance(linear_solver, str) else int(linear_solver)
     if linear is not None:
         o.linear = linear if isinstance(linear, BAPcgOpts) else pcg_opts(**linear)
     its = (BASolveIteration * max(o.max_num_iterations, 1))()
@@ -1252,11 +1324,15 @@ def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", 
 
     linear_solver="pcg" replaces the dense factorisation with BA.schur_solve_pcg on the block-sparse system (the dense
     S is not asked for); pcg is a dict of pcg_opts() arguments.  A BREAKDOWN counts as a rejected step.  Each record
-    then also has linear_iterations and linear_termination."""
+    then also has linear_iterations and linear_termination.
+
+    linear_solver="cholesky_hip" keeps the dense route and hands S and rhs to BA.schur_solve_cholesky (the library's
+    blocked Cholesky) in place of torch's factorisation; linear_termination is then a CHOL_* status."""
     import torch
-    if linear_solver not in ("cholesky", "pcg"):
-        raise ValueError(f"linear_solver {linear_solver!r}: 'cholesky' or 'pcg'")
+    if linear_solver not in ("cholesky", "pcg", "cholesky_hip"):
+        raise ValueError(f"linear_solver {linear_solver!r}: 'cholesky', 'cholesky_hip' or 'pcg'")
     use_pcg = linear_solver == "pcg"
+    use_hip = linear_solver == "cholesky_hip"
     dev = torch.device("cuda", ba.device)
     ns = ba.schur_structure()["num_slots"]
     zero_pose = torch.zeros((ns, 6), dtype=torch.float64, device=dev)
@@ -1278,11 +1354,15 @@ def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", 
             dpose_pcg, info = ba.schur_solve_pcg(**(pcg or {}))
             rec.update(linear_iterations=info["iterations"], linear_termination=info["termination"])
             factored = info["termination"] != PCG_BREAKDOWN
+        elif use_hip:
+            dpose_pcg, info = ba.schur_solve_cholesky(out["S"], out["rhs"])
+            rec.update(linear_iterations=0, linear_termination=info["status"])
+            factored = info["status"] == CHOL_OK
         elif ns:
             Lc, info = torch.linalg.cholesky_ex(out["S"])
             factored = int(info.item()) == 0
         if factored:   # ns = 0 (every pose constant): no reduced system, only the points move
-            if use_pcg:
+            if use_pcg or use_hip:
                 dpose = dpose_pcg
             else:
                 dpose = torch.cholesky_solve(out["rhs"].reshape(-1, 1), Lc).reshape(-1, 6) if ns else zero_pose

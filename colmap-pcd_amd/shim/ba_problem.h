@@ -79,6 +79,13 @@ struct BundleAdjustmentOptions {  // optim/bundle_adjustment.h:52-91 (this fork'
   int max_linear_solver_iterations = 200;
   double function_tolerance = 0.0;
   double gradient_tolerance = 0.0;
+  // Linear solver of BundleAdjusterHip::Solve.  ITERATIVE: the block-sparse PCG (inexact steps).  DIRECT: the blocked
+  // Cholesky of the dense reduced camera system (exact steps).  AUTO: the reference's switch (optim/
+  // bundle_adjustment.cc:500-512: DENSE_SCHUR up to 50 images, SPARSE_SCHUR up to 1000, ITERATIVE_SCHUR above) collapsed
+  // onto the two solvers there are here: DIRECT up to kMaxNumImagesDirectSolver images in the config, ITERATIVE above.
+  enum class LinearSolverType { ITERATIVE, DIRECT, AUTO };
+  LinearSolverType linear_solver_type = LinearSolverType::ITERATIVE;
+  static constexpr size_t kMaxNumImagesDirectSolver = 1000;
 };
 
 class BundleAdjustmentConfig {  // optim/bundle_adjustment.h:118-200, .cc:76-233
@@ -205,7 +212,8 @@ class BundleAdjusterHip {
   pcd_ba* handle() const { return ba_; }
 
   // ---- solve (HIP): the device route end to end, after SetUp() ---------------------------------
-  // Create, pcd_ba_solve (LM with the block-sparse PCG on the reduced camera system), then the accepted poses and
+  // Create, pcd_ba_solve (LM with the linear solver options_.linear_solver_type selects, the block-sparse PCG on the
+  // reduced camera system unless told otherwise), then the accepted poses and
   // points go back into the Reconstruction through image_ids_ / point_ids_; constant poses and points are not
   // written at all.  false when there are no residuals (as the reference, :489-491), when intrinsics are refined
   // (the device route does not carry camera rows: the caller stays on the Ceres route) or when a call fails
@@ -222,6 +230,7 @@ class BundleAdjusterHip {
     o.function_tolerance = options_.function_tolerance;
     o.gradient_tolerance = options_.gradient_tolerance;
     o.linear.max_iterations = options_.max_linear_solver_iterations;
+    o.linear_solver = UsesDirectSolver() ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG;
     if (pcd_ba_solve(ba_, &o, &summary_, nullptr) != PCD_OK) return false;
     if (pcd_ba_get_parameters(ba_, poses_.data(), points_.data()) != PCD_OK) return false;
     for (size_t i = 0; i < image_ids_.size(); ++i) {
@@ -237,6 +246,13 @@ class BundleAdjusterHip {
     return true;
   }
   const pcd_ba_solve_summary& Summary() const { return summary_; }
+  // what Solve hands to pcd_ba_solve: AUTO goes by the number of images in the config, as the reference does
+  bool UsesDirectSolver() const {
+    using T = BundleAdjustmentOptions::LinearSolverType;
+    return options_.linear_solver_type == T::DIRECT ||
+           (options_.linear_solver_type == T::AUTO &&
+            config_.NumImages() <= BundleAdjustmentOptions::kMaxNumImagesDirectSolver);
+  }
 
   // flat arrays (also what a solver scatters back into the Reconstruction)
   std::vector<int32_t> cam_model_, cam_off_, image_cam_, obs_image_, obs_point_, lidar_point_;

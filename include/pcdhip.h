@@ -616,7 +616,8 @@ typedef struct {
   double* S_diag;          /* [ns][6][6]                                                                       */
   double* S_off;           /* [num_pairs][6][6] block (pair_i[q], pair_j[q]), pair_i < pair_j                   */
   double* rhs;             /* [ns][6]                                                                          */
-  double* S;               /* [n][n] dense, row-major, both triangles (for a direct Cholesky)                 */
+  double* S;               /* [n][n] dense, row-major, both triangles (for a direct Cholesky:                 */
+                           /* pcd_ba_schur_solve_cholesky* below reads its lower triangle)                     */
   uint64_t* num_skipped;   /* [1] eliminated points skipped by the pivot test above (V_p numerically singular) */
 } pcd_ba_schur_out;
 /* Co-visibility structure (host query): image_slot [I] (-1 = constant pose), the number of slots, and the slot pairs
@@ -681,6 +682,39 @@ pcd_status pcd_ba_schur_solve_pcg_device(pcd_ba* ba, const pcd_ba_pcg_opts* opts
                                          pcd_ba_pcg_info* d_info /*device, may be NULL*/, void* stream);
 pcd_status pcd_ba_schur_solve_pcg(pcd_ba* ba, const pcd_ba_pcg_opts* opts, double* dpose /*[ns][6] host*/,
                                   pcd_ba_pcg_info* info /*host, may be NULL*/);
+/* Direct solve of the reduced camera system on the device: blocked right-looking fp64 Cholesky S = L L^T, then the two
+ * triangular solves.  n = 6 ns is padded to n_padded, a multiple of the panel width 96 (16 pose slots), with identity
+ * rows / columns and rhs 0, so no kernel has a ragged edge.  Per panel: one launch factors the 96 x 96 diagonal block
+ * and solves the rows below against it (every workgroup re-derives the same diagonal factor in the same operation
+ * order, so they agree bit for bit; the launch never writes the block it reads: the factor of a diagonal block goes
+ * to rows of its own behind the matrix), one launch updates the lower-triangle tiles behind it on the fp64 matrix pipe
+ * (v_mfma_f64_16x16x4_f64).  The right-hand side rides along as one more row of the matrix, which makes the panel
+ * solve deliver y = L^-1 rhs; L^T x = y then runs panel by panel from the last.  Plain launches only, no atomics, every
+ * sum in an order fixed by n: bitwise reproducible.  The host does not synchronise inside the solve.
+ *   d_S == NULL && d_rhs == NULL: reads the handle's own S_diag / S_off / rhs of the LAST Schur call (same state guard
+ *     and message as the PCG);
+ *   both given: d_S [n][n] row-major as pcd_ba_schur_out.S delivers it, of which only the lower triangle is read and
+ *     nothing is modified, d_rhs [n];  exactly one of the two: PCD_ERR_INVALID.
+ * A pivot that is <= 0 or not finite ends the factorisation at that column: PCD_CHOL_NOT_POSITIVE_DEFINITE,
+ * failed_column, and dpose = 0 exactly (the call itself still returns PCD_OK).  The dense scratch
+ * ((n_padded + 192) n_padded doubles) belongs to the handle, is allocated on first use (PCD_ERR_OOM when that fails) and
+ * counted in pcd_ba_schur_stats.  ns = 0: PCD_OK, status OK, nothing launched.  Guards as for the other pcd_ba_schur*
+ * calls; d_dpose may be NULL only when ns = 0.  The host form with S given stages the n^2 doubles of S on the device for
+ * the call and frees them again (a hipMalloc / hipFree pair per call, 288 MB at n = 6000): a caller in a loop wants the
+ * _device form, or the handle's own blocks, which need no staging. */
+typedef enum { PCD_LINEAR_PCG = 0, PCD_LINEAR_CHOLESKY = 1 } pcd_ba_linear_solver;
+typedef enum { PCD_CHOL_OK = 0, PCD_CHOL_NOT_POSITIVE_DEFINITE = 1 } pcd_ba_chol_status;
+typedef struct {
+  int32_t status;          /* pcd_ba_chol_status */
+  int32_t failed_column;   /* first column whose pivot was <= 0 or not finite; -1 when OK */
+  int32_t n, n_padded, panels;
+  double min_pivot, max_pivot;   /* of L's diagonal, as stored, over the unpadded columns factored so far */
+} pcd_ba_chol_info;
+pcd_status pcd_ba_schur_solve_cholesky_device(pcd_ba* ba, const double* d_S, const double* d_rhs,
+                                              double* d_dpose /*[ns][6]*/,
+                                              pcd_ba_chol_info* d_info /*device, may be NULL*/, void* stream);
+pcd_status pcd_ba_schur_solve_cholesky(pcd_ba* ba, const double* S, const double* rhs, double* dpose,
+                                       pcd_ba_chol_info* info /*may be NULL*/);   /* host pointers */
 /* current parameters, device -> host (either pointer may be NULL) */
 pcd_status pcd_ba_get_parameters(pcd_ba* ba, double* poses /*[I][7]*/, double* points /*[P][3]*/);
 
@@ -696,7 +730,12 @@ pcd_status pcd_ba_get_parameters(pcd_ba* ba, double* poses /*[I][7]*/, double* p
  * non-constant points, NOT Ceres' manifold-projected ||Plus(x, -g) - x||.  A tolerance of 0 switches its test off.
  * One small device-to-host copy per iteration carries the costs, the model decrease, the PCG record and the gradient
  * norm (one more per extra batch when the PCG runs past its first 8 iterations).  On return the handle holds the
- * accepted parameters. */
+ * accepted parameters.
+ * linear_solver = PCD_LINEAR_CHOLESKY replaces the PCG by pcd_ba_schur_solve_cholesky_device on the handle's own
+ * blocks (an exact step; `linear` is then checked but not used).  There is no second batch: exactly one copy per
+ * iteration.  PCD_CHOL_NOT_POSITIVE_DEFINITE counts as a rejected step, as BREAKDOWN does.  In pcd_ba_solve_iteration
+ * linear_iterations is then 0 and linear_termination holds the pcd_ba_chol_status; linear_solver_ms covers fill,
+ * factorisation and the triangular solves.  Any other value of linear_solver: PCD_ERR_INVALID. */
 typedef enum { PCD_SOLVE_MAX_ITERATIONS = 0, PCD_SOLVE_FUNCTION_TOLERANCE = 1, PCD_SOLVE_GRADIENT_TOLERANCE = 2,
                PCD_SOLVE_MIN_RADIUS = 3 } pcd_ba_solve_termination;
 typedef struct {
@@ -704,7 +743,8 @@ typedef struct {
   int32_t damping;                  /* pcd_ba_damping */
   double initial_radius, max_radius, min_radius, min_relative_decrease, function_tolerance, gradient_tolerance;
   pcd_ba_pcg_opts linear;
-  int32_t reserved[8];
+  int32_t linear_solver;            /* pcd_ba_linear_solver; 0 (a zero-filled struct, the defaults) = PCG */
+  int32_t reserved[7];
 } pcd_ba_solve_opts;
 typedef struct {
   double cost, candidate_cost, model_decrease, relative_decrease;

@@ -6,7 +6,9 @@
 Parts: structure build (host counting sorts, once per handle), normal-equation pass, elimination, dense fill,
 torch.linalg.cholesky + solve, back-substitution + plus, cost pass, a whole LM iteration of pcdhip.ba_solve_lm; then
 the block-sparse PCG beside the Cholesky (at the defaults and to r_tolerance 1e-10, each call with its one read of the
-record), the time per CG iteration, and a whole LM iteration through pcd_ba_solve.
+record), the time per CG iteration, and a whole LM iteration through pcd_ba_solve; then the library's own blocked
+Cholesky (fill + factor + solve, from the handle's blocks and from the same dense S torch factors) beside torch's in
+the same run, and a whole LM iteration through pcd_ba_solve with that solver.
 Device parts are timed with the library's per-scope hipEvents (pcdhip.profile_*), host-driven parts with
 torch.cuda.Event pairs; warm-up first, then the median (and min / max) of --reps runs."""
 import argparse
@@ -85,8 +87,11 @@ def probe(tag, reps, log):
     out = ba.schur(mu, dense=True)
     S, rhs = out["S"], out["rhs"].reshape(-1, 1)
 
+    torch_info = {}
+
     def chol():
         L, info_ = torch.linalg.cholesky_ex(S)
+        torch_info["S"] = info_          # read after the timing: 0 = factored, k > 0 = the leading minor k is not PD
         return torch.cholesky_solve(rhs, L)
     r["cholesky + solve (torch)"] = evented(chol, reps)
     dpose = chol().reshape(-1, 6)
@@ -133,6 +138,32 @@ def probe(tag, reps, log):
         return (time.perf_counter() - t) * 1e3
     solve_iter()
     r["whole LM iteration, pcd_ba_solve (wall)"] = [solve_iter() for _ in range(reps)]
+    # the library's direct solve: the same S as torch's leg above, then the handle's own blocks
+    ba.set_parameters(*keep)
+    ba.schur(mu, want=("cost", "num_skipped"))
+    chol_info = {}
+
+    def chol_hip_dense():
+        chol_info["dense"] = ba.schur_solve_cholesky(S, rhs, dpose=xbuf)[1]
+
+    def chol_hip_blocks():
+        chol_info["blocks"] = ba.schur_solve_cholesky(dpose=xbuf)[1]
+    r["cholesky + solve (library, caller's dense S)"] = evented(chol_hip_dense, reps)
+    r["cholesky + solve (library, handle's blocks)"] = evented(chol_hip_blocks, reps)
+    r["  of which on the device (scope)"] = scoped(ba, chol_hip_blocks, "ba_schur_cholesky", reps)
+    r["cholesky + solve (torch), again"] = evented(chol, reps)
+    x_hip = xbuf.reshape(-1, 1).clone()
+    res = lambda x: float((S @ x - rhs).abs().max() / (S.abs().sum(1).max() * x.abs().max() + rhs.abs().max()))
+    eta_hip, eta_torch = res(x_hip), res(chol())
+
+    def solve_iter_chol():
+        ba.set_parameters(*keep)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        pcdhip.ba_solve(ba, max_num_iterations=1, linear_solver="cholesky")
+        return (time.perf_counter() - t) * 1e3
+    solve_iter_chol()
+    r["whole LM iteration, pcd_ba_solve cholesky"] = [solve_iter_chol() for _ in range(reps)]
     for k, v in r.items():
         log("  %-44s %s" % (k, stats(v)))
     nd, nt = its["default"]["iterations"], its["tight"]["iterations"]
@@ -146,6 +177,74 @@ def probe(tag, reps, log):
     log("  whole LM iteration: dense Cholesky route %.3f ms (spread %.3f), pcd_ba_solve %.3f ms"
         % (np.median(r["whole LM iteration (wall, incl. host syncs)"]), hi - lo,
            np.median(r["whole LM iteration, pcd_ba_solve (wall)"])))
+    tl, tb = np.median(r["cholesky + solve (library, caller's dense S)"]), np.median(r["cholesky + solve (library, handle's blocks)"])
+    tt2 = min(np.median(r["cholesky + solve (torch)"]), np.median(r["cholesky + solve (torch), again"]))
+    ci = chol_info["dense"]
+    t_info = int(torch_info["S"].item())
+    both_ok = ci["status"] == pcdhip.CHOL_OK and chol_info["blocks"]["status"] == pcdhip.CHOL_OK and t_info == 0
+    log("  direct solve of the scene's S at mu %g, n = %d (%d panels of 96): library status %d failed_column %d pivots "
+        "%.6g .. %.6g; torch cholesky_ex info %d" % (mu, ci["n"], ci["panels"], ci["status"], ci["failed_column"],
+                                                    ci["min_pivot"], ci["max_pivot"], t_info))
+    if both_ok:
+        log("  library %.3f ms from the dense S, %.3f ms from the blocks; torch %.3f ms (the faster of its two legs): "
+            "library / torch = %.2f (%s); backward error eta library %.2e, torch %.2e"
+            % (tl, tb, tt2, tl / tt2, "the library wins" if tl < tt2 else "the library LOSES", eta_hip, eta_torch))
+    else:
+        log("  NO VERDICT on this system: a factorisation failed (S is not numerically positive definite for it), so the "
+            "times above are times to the failure (library) or of a factor that was not completed (torch), not of a solve")
+    lc = np.median(r["whole LM iteration, pcd_ba_solve cholesky"])
+    ld = np.median(r["whole LM iteration (wall, incl. host syncs)"])
+    _, it_hip = pcdhip.ba_solve(ba, max_num_iterations=1, linear_solver="cholesky")
+    ba.set_parameters(*keep)
+    it_lm = pcdhip.ba_solve_lm(ba, max_iterations=1)
+    ba.set_parameters(*keep)
+    step_ok = it_hip[0]["linear_termination"] == pcdhip.CHOL_OK and np.isfinite(it_lm[0]["candidate_cost"])
+    log("  whole LM iteration: pcd_ba_solve cholesky %.3f ms (linear_termination %d), ba_solve_lm (torch) %.3f ms "
+        "(step %s); pcd_ba_solve PCG %.3f ms"
+        % (lc, it_hip[0]["linear_termination"], ld, "taken" if np.isfinite(it_lm[0]["candidate_cost"]) else
+           "not taken: its factorisation failed", np.median(r["whole LM iteration, pcd_ba_solve (wall)"])))
+    if step_ok:
+        log("  ratio %.2f (%s)" % (lc / ld, "under ba_solve_lm" if lc < ld else "NOT under ba_solve_lm"))
+    else:
+        log("  NO VERDICT on the LM iteration: a factorisation failed, the iterations timed are rejected steps")
+    # a system of the same size that both solvers factor: G G^T + n I from a seeded G (what tests/test_ba_chol_gpu.py
+    # solves at n = 2700), the caller's-dense-S form
+    n = 6 * ns
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(7000 + ns)
+    G = torch.randn((n, n), dtype=torch.float64, device="cuda", generator=gen)
+    Sp = G @ G.T + n * torch.eye(n, dtype=torch.float64, device="cuda")
+    Sp = 0.5 * (Sp + Sp.T)
+    bp = Sp @ torch.randn((n, 1), dtype=torch.float64, device="cuda", generator=gen)
+    del G
+    spd = {}
+
+    def chol_spd_torch():
+        L, info_ = torch.linalg.cholesky_ex(Sp)
+        spd["torch"] = info_
+        return torch.cholesky_solve(bp, L)
+
+    def chol_spd_hip():
+        spd["hip"] = ba.schur_solve_cholesky(Sp, bp, dpose=xbuf)[1]
+    ts = evented(chol_spd_torch, reps)
+    th = evented(chol_spd_hip, reps)
+    ts2 = evented(chol_spd_torch, reps)
+    resp = lambda x: float((Sp @ x - bp).abs().max() / (Sp.abs().sum(1).max() * x.abs().max() + bp.abs().max()))
+    e_h, e_t = resp(xbuf.reshape(-1, 1)), resp(chol_spd_torch())
+    log("  SPD system G G^T + n I, n = %d:" % n)
+    log("  %-44s %s" % ("cholesky + solve (torch)", stats(ts)))
+    log("  %-44s %s" % ("cholesky + solve (library, caller's dense S)", stats(th)))
+    log("  %-44s %s" % ("cholesky + solve (torch), again", stats(ts2)))
+    hi_ = spd["hip"]
+    log("  library status %d failed_column %d pivots %.6g .. %.6g; torch cholesky_ex info %d"
+        % (hi_["status"], hi_["failed_column"], hi_["min_pivot"], hi_["max_pivot"], int(spd["torch"].item())))
+    if hi_["status"] == pcdhip.CHOL_OK and int(spd["torch"].item()) == 0:
+        tt3 = min(np.median(ts), np.median(ts2))
+        log("  library %.3f ms, torch %.3f ms (the faster of its two legs): library / torch = %.2f (%s); backward error "
+            "eta library %.2e, torch %.2e" % (np.median(th), tt3, np.median(th) / tt3,
+                                              "the library wins" if np.median(th) < tt3 else "the library LOSES", e_h, e_t))
+    else:
+        log("  NO VERDICT: a factorisation failed")
     ba.close()
     return r
 
