@@ -8,12 +8,21 @@
 //   sorted [m] float4 {x,y,z,bits(global_idx)}  finite rows in cell-sorted order (x fastest):
 //              one 16-B record per lane per load; a row of cells along x is one contiguous range
 //   cell_start [ncells+1] uint32    exclusive prefix of per-cell counts
-//   blk_aabb [nodes][8] float       the AABB pyramid of the exact fallback.  Level 0 = LEAVES: every sub-block of
-//                                   2x2x2 cells -- an x-range of 2 cells of ONE quad row, i.e. one contiguous point
-//                                   range -- as {lo.xyz, hi.x | hi.y, hi.z, bits(first point), bits(count)}; level
-//                                   k+1 = 4x4x4 nodes of level k as {lo.xyz, hi.xyz, 0, 0}, up to the first level with <= 64 nodes
-//                                   (the walk starts at a virtual top over all of them, PyramidParams below).
-//                                   An expansion tests 64 children with the exact float bound; a leaf is scanned.
+//   blk_aabb [records][8] float     the AABB tree of the exact fallback: a 64-ary tree over the OCCUPIED nodes of the
+//                                   4x4x4 pyramid over the grid, 32 B per record, {lo.xyz, hi.x | hi.y, hi.z, bits(first),
+//                                   bits(count)}.  A LEAF is a sub-block of 2x2x2 cells -- an x-range of 2 cells of ONE
+//                                   quad row, i.e. one contiguous point range -- and first / count are that range in
+//                                   `sorted`; an INNER node's first / count are the range of its children's records in
+//                                   this array.  Only nodes that hold a point have a record; the children of a node are
+//                                   contiguous, in ascending order of their position ci + 4 cj + 16 ck inside the node's
+//                                   4x4x4 lattice (the walk breaks ties towards the lowest lane: the order is part of
+//                                   the result's definition).  Levels are stored top down, each level's nodes in the
+//                                   order of their parents, so the upper levels of the whole cloud are a few hundred KB
+//                                   at the front of the array (workload M: 99 k records, 3 MB; the dense lattice the
+//                                   records are compacted from is 4.7 M nodes, 151 MB, and lives only during the build).
+//                                   The walk starts at a virtual top whose children are the records of the first level
+//                                   with <= 64 lattice nodes (PyramidParams below).
+//                                   An expansion tests up to 64 children with the exact float bound; a leaf is scanned.
 #pragma once
 #include "common.h"
 
@@ -31,16 +40,18 @@ struct GridParams {
   float slack;    // metres: bound on binning rounding, see nn.hip
 };
 
-// 64-ary AABB pyramid: level 0 = leaves (2x2x2-cell sub-blocks), level k+1 = 4x4x4 nodes of level k, up to the first
-// level with at most 64 nodes (level nlev-2); level nlev-1 is a VIRTUAL top whose children are all nodes of level
-// nlev-2, one per lane.  The real levels live in blk_aabb (8 floats per node) at off[level].
+// 64-ary AABB tree over the occupied nodes of the pyramid: level 0 = leaves (2x2x2-cell sub-blocks), level k+1 = 4x4x4
+// nodes of level k, up to the first level with at most 64 lattice nodes (level nlev-2); level nlev-1 is a VIRTUAL top
+// whose children are the occupied nodes of level nlev-2 in the order of their flat lattice index: the records
+// root_first .. root_first + root_count - 1 of blk_aabb (root_count = 0: a cloud without a finite point).
 constexpr int kMaxPyrLevels = 10;
 struct PyramidParams {
   int nlev;                       // >= 2
-  int dims[kMaxPyrLevels][3];
-  uint32_t off[kMaxPyrLevels];    // node offset of each level
+  uint32_t root_first, root_count;
   int seed_dims[3];               // lattice of the fallback's seed table: 8x8x8-cell cubes (nn.hip fb_seed_table)
 };
+// an inner node's child range travels through the walk's stack as first | (count - 1) << 26
+constexpr uint32_t kMaxPyrRecords = 1u << 26;
 
 struct QueryScratch;  // nn.hip
 

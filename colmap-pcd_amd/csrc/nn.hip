@@ -799,10 +799,12 @@ struct FbFused {   // inputs of k_nn_fallback<1 / 2> (the kernel as the only lau
   double fixed_range;
 };
 
-// One wavefront per query walks the 64-ary AABB pyramid over the grid (level 0 = 2x2x2-cell leaves carrying their
-// point range, level k+1 = 4x4x4 nodes of level k, cloud.h): the 64 children of the current node sit one per lane, each
-// lane computes the exact float lower bound of its child, and the wave descends into the nearest
-// child whose bound does not exceed the best distance so far (depth first, nearest first).
+// One wavefront per query walks the 64-ary AABB tree over the occupied nodes of the grid's pyramid (level 0 = 2x2x2-cell
+// leaves carrying their point range, level k+1 = 4x4x4 nodes of level k carrying the range of their children's records,
+// cloud.h): the up to 64 children of the current node sit one per lane in the order of their records (= of their
+// position in the node's 4x4x4 lattice), each lane computes the exact float lower bound of its child, and the wave
+// descends into the nearest child whose bound does not exceed the best distance so far (depth first, nearest first,
+// ties to the lowest lane).
 // Every skipped subtree has bound > best, so the result is the exact minimum of the packed keys.
 // FUSED: 0 = queries from qf4, keys in and out raw (the grid path's second stage; refining), 1 / 2 = the kernel is the
 // only launch of the call (plain / gate-bounded).  A template parameter, not a run-time mode: with the mode tested at
@@ -817,22 +819,17 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
                                                       const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
                                                       uint64_t* __restrict__ keys, NnCounters* __restrict__ ctr,
                                                       int collect_stats, FbFused fu) {
-  __shared__ float s_lb[4][kMaxPyrLevels][64];
-  __shared__ unsigned long long s_mask[4][kMaxPyrLevels];
-  __shared__ int s_node[4][kMaxPyrLevels][3];
-  __shared__ int4 s_pyr[kMaxPyrLevels];   // per level {dims x, y, z, node offset}
-  if (threadIdx.x < (unsigned)kMaxPyrLevels)
-    s_pyr[threadIdx.x] = make_int4(py.dims[threadIdx.x][0], py.dims[threadIdx.x][1], py.dims[threadIdx.x][2], (int)py.off[threadIdx.x]);
-  __syncthreads();
+  // the stack: levels 2 .. nlev - 1 push (a level-1 node's children are leaves).  Per lane the child's bound and its
+  // own child range as first | (count - 1) << 26 (cloud.h kMaxPyrRecords): 16 KB, 8 workgroups per CU
+  constexpr int kStack = kMaxPyrLevels - 2;
+  __shared__ float s_lb[4][kStack][64];
+  __shared__ uint32_t s_rng[4][kStack][64];
+  __shared__ unsigned long long s_mask[4][kStack];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // uniform for the compiler: LDS addresses on the scalar unit
   const uint32_t count = count_ptr ? *count_ptr : count_imm;
   const uint32_t nwaves = gridDim.x * 4;
   const int top = py.nlev - 1;  // >= 1
-  const int ci = lane & 3, cj = (lane >> 2) & 3, ck = lane >> 4;
-  // the lane's child of the virtual top: flat index over the dimensions of level top - 1 (at most 64 nodes)
-  const int tdx = py.dims[top - 1][0], tdy = py.dims[top - 1][1];
-  const int tcx = lane % tdx, tcy = (lane / tdx) % tdy, tcz = lane / (tdx * tdy);   // tcz >= dims z: no such node
   unsigned long long st_pts = 0, st_q = 0, st_steps = 0, st_leaves = 0;
   uint32_t st_max_steps = 0, st_max_leaves = 0;
   for (uint32_t e = blockIdx.x * 4 + wave; e < count; e += nwaves) {
@@ -869,56 +866,51 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
       best = sk < best ? sk : best;
     }
     // The state of the level being iterated lives in REGISTERS (the children's bounds one per lane, the mask of the
-    // children still to visit in an SGPR pair, the node in SGPRs); the LDS arrays are a stack touched only when the walk
-    // descends (push) or comes back (pop).  Before, every iteration went through LDS for the mask and the node -- a
+    // children still to visit in an SGPR pair, the children's ranges one per lane); the LDS arrays are a stack touched
+    // only when the walk descends (push) or comes back (pop).  Before, every iteration went through LDS for the mask and the node -- a
     // write -> read round trip in the walk's dependent chain, and most iterations are leaves of ONE level-1 node.
     // The keys are compared as doubles (brick_kernel.h: one v_min_f64 instead of a 64-bit compare + two selects).
     double lane_best = __builtin_bit_cast(double, best);
     float best_d = __uint_as_float((uint32_t)(best >> 32));
-    int lev = top;                 // the children of node (nx, ny, nz) of level `lev` are being iterated
-    int nx = 0, ny = 0, nz = 0;
+    int lev = top;                 // the children of a node of level `lev` are being iterated
     float cur_lb;
     unsigned long long cur_m;
-    uint32_t rs = 0, rn = 0;       // lev == 1: the lane's leaf's point range
+    uint32_t rs = 0, rn = 0;       // the lane's child's range: points of `sorted` (lev == 1) or records of its children
     uint32_t q_steps = 0, q_leaves = 0;
-    // children of node (nx,ny,nz) of level `lev` live on level lev-1.  ONE memory round trip per expansion: the level's
-    // dimensions and offset come from LDS (as kernel arguments indexed by `lev` they were four dependent scalar loads),
-    // the child's two 16-byte loads are unconditional on a clamped index and the bound is selected afterwards (under
-    // `if (non-empty)` the compiler split them into a first pair of dwords, the test, and a second, dependent pair of
-    // loads): the walk is a chain of such steps and its latency is the kernel's time.
-#define PCD_FB_EXPAND()                                                                                               \
+    // the children of the node are the records cf .. cf + cn - 1 (uniform: the virtual top's from the kernel arguments,
+    // a child's from the lane that holds it).  ONE memory round trip per expansion: the child's two 16-byte loads are
+    // unconditional on a clamped index -- the lanes past the last child re-read its record, a line a live lane fetches
+    // anyway -- and the bound is selected afterwards (under `if (live)` the compiler split them into a first pair of
+    // dwords, the test, and a second, dependent pair of loads): the walk is a chain of such steps.
+#define PCD_FB_EXPAND(cf, cn)                                                                                         \
     {                                                                                                                 \
-      const int4 dm = s_pyr[lev - 1]; /* {dims x, y, z, node offset} */                                               \
-      /* (the virtual top's children are ALL nodes of the level below, lane = flat node index) */                     \
-      const int cx = lev == top ? tcx : 4 * nx + ci, cy = lev == top ? tcy : 4 * ny + cj,                             \
-                cz = lev == top ? tcz : 4 * nz + ck;                                                                  \
-      const bool in = cx < dm.x && cy < dm.y && cz < dm.z;                                                            \
-      const uint32_t id = (uint32_t)dm.w + (in ? (uint32_t)((cz * dm.y + cy) * dm.x + cx) : 0u); /* < 2^32 nodes */   \
+      const uint32_t cn_ = (cn);                                                                                      \
+      const uint32_t last = cn_ ? cn_ - 1u : 0u; /* (no children: a cloud without a finite point) */                  \
+      const uint32_t id = (cf) + ((uint32_t)lane < last ? (uint32_t)lane : last);                                     \
       const float4 lo = *reinterpret_cast<const float4*>(aabb + 8 * (size_t)id);     /* lo.x lo.y lo.z hi.x */        \
-      const float4 hi = *reinterpret_cast<const float4*>(aabb + 8 * (size_t)id + 4); /* hi.y hi.z start count */      \
+      const float4 hi = *reinterpret_cast<const float4*>(aabb + 8 * (size_t)id + 4); /* hi.y hi.z first count */      \
       /* clamp(q, lo, hi) = the median of the three for lo <= hi: ONE v_med3_f32 (fminf(fmaxf()) costs two ops + */     \
-      /* three canonicalising v_max x, x, x); an empty node's inverted box is masked below */                         \
+      /* three canonicalising v_max x, x, x); every record holds a point, so its box is not inverted */                \
       const float px = __builtin_amdgcn_fmed3f(qx, lo.x, lo.w), pyc = __builtin_amdgcn_fmed3f(qy, lo.y, hi.x),        \
                   pz = __builtin_amdgcn_fmed3f(qz, lo.z, hi.y);                                                       \
       const float lbv = l2_simple3(qx, qy, qz, px, pyc, pz);                                                          \
-      cur_lb = (in && lo.x <= lo.w) ? lbv : INFINITY; /* empty nodes have an inverted box */                          \
-      rs = __float_as_uint(hi.z); rn = __float_as_uint(hi.w); /* leaves carry their range */                          \
+      cur_lb = (uint32_t)lane < cn_ ? lbv : INFINITY;                                                                 \
+      rs = __float_as_uint(hi.z); rn = __float_as_uint(hi.w);                                                         \
       cur_m = __ballot(cur_lb <= best_d);                                                                             \
     }
-    PCD_FB_EXPAND();
+    PCD_FB_EXPAND(py.root_first, py.root_count);
     while (true) {
       ++q_steps;
       unsigned long long m = cur_m & __ballot(cur_lb <= best_d);
       if (m == 0) {
         if (lev == top) break;
         ++lev;   // pop
-        cur_lb = s_lb[wave][lev][lane];
-        const unsigned long long pm = s_mask[wave][lev];
+        cur_lb = s_lb[wave][lev - 2][lane];
+        const uint32_t pr = s_rng[wave][lev - 2][lane];
+        rs = pr & (kMaxPyrRecords - 1u); rn = (pr >> 26) + 1u;
+        const unsigned long long pm = s_mask[wave][lev - 2];
         cur_m = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(pm >> 32)) << 32) |
                 (uint32_t)__builtin_amdgcn_readfirstlane((int)pm);
-        nx = __builtin_amdgcn_readfirstlane(s_node[wave][lev][0]);
-        ny = __builtin_amdgcn_readfirstlane(s_node[wave][lev][1]);
-        nz = __builtin_amdgcn_readfirstlane(s_node[wave][lev][2]);
         continue;
       }
       const int sl = wave_argmin_u32(__float_as_uint(cur_lb), m);  // nearest remaining child (lb >= 0: bit order)
@@ -984,16 +976,13 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
           best_d = __uint_as_float((uint32_t)(best >> 32));
         }
       } else {
-        // push the level, descend into child `sl`
-        s_lb[wave][lev][lane] = cur_lb;
-        if (lane == 0) { s_mask[wave][lev] = cur_m; s_node[wave][lev][0] = nx; s_node[wave][lev][1] = ny; s_node[wave][lev][2] = nz; }
-        if (lev == top) {
-          nx = __builtin_amdgcn_readlane(tcx, sl); ny = __builtin_amdgcn_readlane(tcy, sl); nz = __builtin_amdgcn_readlane(tcz, sl);
-        } else {
-          nx = 4 * nx + (sl & 3); ny = 4 * ny + ((sl >> 2) & 3); nz = 4 * nz + (sl >> 4);
-        }
+        // push the level, descend into child `sl`: its children's records are named by its own
+        s_lb[wave][lev - 2][lane] = cur_lb;
+        s_rng[wave][lev - 2][lane] = rs | ((rn - 1u) << 26);   // (lanes past the last child hold its copy: rn >= 1)
+        if (lane == 0) s_mask[wave][lev - 2] = cur_m;
+        const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)rs, sl), cn = (uint32_t)__builtin_amdgcn_readlane((int)rn, sl);
         --lev;
-        PCD_FB_EXPAND();
+        PCD_FB_EXPAND(cf, cn);
       }
     }
 #undef PCD_FB_EXPAND

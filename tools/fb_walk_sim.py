@@ -13,6 +13,13 @@ PCD_FB_STATS counts).  Classes:
 Cases: (a) today; (b) a seed bound: best starts at min(best, key of the seed point of the query's seed cell); (c) slab
 bounds on the leaves, lb = max(AABB bound, plane-slab bound); (d) both.  Bounds are evaluated in double here (the
 model prices walk lengths; exactness is the kernel's and the tests' business).
+
+Bytes: the walk also counts what it requests from memory (Index.tr, printed per class for case "b seed 8", the kernel
+as built): per expansion of a level-k node the child records of the DENSE lattice (64 records of 32 B = 16 lines of
+128 B, whatever they hold), how many of them are occupied, how many 4-child rows (one line each) hold an occupied child,
+and the lines a COMPACT child list needs (occupied records, contiguous: ceil(32 * n / 128), + 1 at worst when the list
+does not start on a line); per leaf scan the 128-B lines its 16-B point records span.  That is the pricing of the
+compact pyramid (cloud.h: records of the occupied nodes only).
 """
 import os
 import sys
@@ -100,6 +107,7 @@ class Index:
             self.dims.append(pd)
         self.top = len(self.dims)   # virtual top level
         self.slab = self._slabs()
+        self.reset_traffic()
         print("index: h %.4f dims %s leaves %d (%d occupied) levels %s  %.1fs" % (
             g["h"], dims.tolist(), nl, len(occ), [d.tolist() for d in self.dims], time.time() - t), flush=True)
 
@@ -123,6 +131,29 @@ class Index:
         T1 = np.zeros(nl)
         N[occ], T0[occ], T1[occ] = n, t0, t1
         return N, T0, T1
+
+    def reset_traffic(self):
+        """per level of the expanded node: expansions, occupied children, occupied 4-child rows, compact lines; leaf lines"""
+        self.tr = dict(exp=np.zeros(12, np.int64), occ=np.zeros(12, np.int64), rows=np.zeros(12, np.int64),
+                       clines=np.zeros(12, np.int64), dlines=np.zeros(12, np.int64), leaf_lines=0, queries=0)
+
+    def traffic_report(self, name):
+        t = self.tr
+        nq = max(t["queries"], 1)
+        print("%s: requested per query (n %d)" % (name, t["queries"]))
+        dense = compact = 0.0
+        for lev in range(1, self.top + 1):
+            if not t["exp"][lev]:
+                continue
+            e = t["exp"][lev]
+            print("  level-%d expansions %.2f  occupied children %.1f of 64  occupied rows %.1f  lines dense %.1f / compact %.1f"
+                  % (lev, e / nq, t["occ"][lev] / e, t["rows"][lev] / e, t["dlines"][lev] / e, t["clines"][lev] / e))
+            dense += 128.0 * t["dlines"][lev] / nq
+            compact += 128.0 * t["clines"][lev] / nq
+        leaf = 128.0 * t["leaf_lines"] / nq
+        print("  leaf scans %.1f lines = %.1f KB; child records dense %.1f KB, compact %.1f KB; total %.1f -> %.1f KB (%.0f %% less)"
+              % (t["leaf_lines"] / nq, leaf / 1e3, dense / 1e3, compact / 1e3, (leaf + dense) / 1e3, (leaf + compact) / 1e3,
+                 100.0 * (dense - compact) / (leaf + dense)), flush=True)
 
     def region_min(self, qf, cell):
         """the brick kernel's region-restricted minimum: leaves within one leaf of the query's leaf."""
@@ -164,6 +195,12 @@ class Index:
             lb = l2(qf, pc)
             ok = inn & (lo[:, 0] <= hi[:, 0])
             lb = np.where(ok, lb, np.inf)
+            tr = self.tr
+            tr["exp"][lev] += 1
+            tr["occ"][lev] += int(ok.sum())
+            tr["rows"][lev] += int(ok.sum()) if lev == self.top else int(ok.reshape(16, 4).any(1).sum())
+            tr["dlines"][lev] += -(-int(np.prod(d)) // 4) if lev == self.top else 16
+            tr["clines"][lev] += -(-int(ok.sum()) // 4)
             if slab and lev == 1:
                 t = N[ids] @ q64
                 g = np.maximum(np.maximum(T0[ids] - t, t - T1[ids]), 0.0)
@@ -171,6 +208,7 @@ class Index:
             return lb, ok, (cx, cy, cz), ids
 
         steps = leaves = pts = 0
+        self.tr["queries"] += 1
         lev, node = self.top, (0, 0, 0)
         lb, mask, cc, ids = expand(lev, node)
         stack = {}
@@ -208,6 +246,7 @@ class Index:
         s, e = self.start[li], self.start[li + 1]
         if s == e:
             return best
+        self.tr["leaf_lines"] += int((16 * e - 1) // 128 - (16 * s) // 128 + 1)
         dd = l2(qf, self.sp[s:e])
         k = np.lexsort((self.sidx[s:e], dd))[0]
         return min(best, (dd[k], self.sidx[s + k]))
@@ -290,6 +329,7 @@ def main():
                 [("b seed %d" % s, s, False) for s in seed_cells] + [("c slab", None, True)] + \
                 [("d seed %d + slab" % s, s, True) for s in seed_cells]:
             t = time.time()
+            ix.reset_traffic()
             st = np.zeros((len(ids), 3), np.int64)
             for r, i in enumerate(ids):
                 if name == "empty":
@@ -310,6 +350,8 @@ def main():
                          st[:, 2].mean(), st[:, 2].max()))
             print("%-6s %-18s n %5d  steps %5.2f (max %3d)  leaves %5.2f (max %3d)  leaf points %6.1f (max %5d)  %.0fs"
                   % (rows[-1] + (time.time() - t,)), flush=True)
+            if case == "b seed 8":
+                ix.traffic_report(name)
     # the fallback as a whole: the classes weighted by their share
     w = {"empty": empty.sum(), "open": open_.sum()}
     print("\nweighted over the fallback list (%d empty-halo / outside + %d open):" % (w["empty"], w["open"]))
