@@ -9,12 +9,13 @@
 //
 //   stage A   the brick's own 2x2x2 cells (one contiguous range of the centre quad row) are staged and compared,
 //             64 points per step; one reduction gives every query its tentative distance d_k (or the bound it came
-//             with: gate-bounded search, refining another shard's result);
+//             with: gate-bounded search, refining another shard's result).  A brick without a point of its own
+//             takes the first <= 128 records of a neighbouring brick's span of the region instead (issue_a);
 //   clip      a point that can still beat query k lies in the ball of radius sqrt(d_k) around it.  Lane k turns its
 //             ball's bounding box into a mask of (quad row, x cell) pairs of the region -- 9 rows x 6 cells = 54 bits;
 //             the masks of the item's queries are OR-ed (three DPP steps) and become wave-uniform scalars;
-//   stage B   of every quad row only the hull of its masked x cells is staged (the centre row without the cells of
-//             stage A); rows the balls do not touch are dropped.  The ranges come from ONE table per item -- lane
+//   stage B   of every quad row only the hull of its masked x cells is staged (the row of stage A without the records
+//             stage A compared); rows the balls do not touch are dropped.  The ranges come from ONE table per item -- lane
 //             7 row + k holds cell_start at x boundary k of quad row `row` (63 loads in one instruction, prefetched
 //             an item ahead) -- so clipping costs no dependent memory access: v_readlane with a scalar lane index.
 //
@@ -29,14 +30,18 @@
 // i.e. |qx - px| <= sqrt(d) (1 + 2^-23); the radius is widened by 1e-5 relative, the box by 2e-7 relative outwards, and
 // cells are compared through the very expression the build bins points with (grid.h cell_coord: monotone in the
 // coordinate), so a point's cell lies between the cells of the box's corners.
+// The argument asks of d_k only that it is an upper bound of query k's final distance.  The records stage A compares
+// for an empty brick are real cloud points of the region like the brick's own, their keys enter the minimum in the
+// same arithmetic, so d_k is such a bound whichever span they come from; stage B still covers every record of the
+// masked hulls that stage A did not compare (the split of stage A's row below).
 #pragma once
 
 namespace pcd {
 
 constexpr int kClipNk = 7;      // x boundaries of a region row: cells 2 bx - 2 .. 2 bx + 4
 constexpr int kClipRows = 9;    // quad rows of the region: (by - 1 .. by + 1) x (bz - 1 .. bz + 1)
-constexpr int kATile = 128;     // points stage A stages at most (2 DMA instructions); the rest of the brick's range joins stage B
-constexpr int kClipRanges = 10; // 8 halo rows + the centre row's left and right parts
+constexpr int kATile = 128;     // points stage A stages at most (2 DMA instructions); the rest of its range joins stage B
+constexpr int kClipRanges = 10; // 8 rows + the left and right parts of the row stage A took its records from
 #ifdef PCD_ABLATE   // timing-only ablations (tools/nn_ablate.py; results are wrong): brick_kernel.h
 constexpr int kAblateClipMath = 0x10000, kAblateBound = 0x20000, kAblateStageA = 0x40000, kAblateSelect = 0x80000;
 #else
@@ -95,6 +100,16 @@ __device__ __forceinline__ float proven_bound_f(const GridParams& g, float qx, f
   margin -= 2.0f * g.slack;
   if (!(margin > 0.0f)) return -1.0f;
   return margin * margin * (1.0f - 1e-5f);
+}
+
+// lanes 7 r + 2 j of the boundary table whose two-cell span (row r, x cells 2 j, 2 j + 1) is a neighbouring brick of
+// class cls: 1 shares a face with the item's brick, 2 an edge, 3 a corner
+constexpr uint64_t span_lanes(int cls) {
+  uint64_t m = 0;
+  for (int r = 0; r < kClipRows; ++r)
+    for (int j = 0; j < 3; ++j)
+      if ((j != 1) + (r % 3 != 1) + (r / 3 != 1) == cls) m |= 1ull << (kClipNk * r + 2 * j);
+  return m;
 }
 
 struct ClipMeta {    // per-item loads issued one item ahead
@@ -176,20 +191,48 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
 #define PCD_RL(v, r) ((uint32_t)__builtin_amdgcn_readlane((int)(v), (int)(r)))
   // stage A of an item: the brick's own cells = x boundaries 2 .. 4 of the centre row (row 4); always exactly two
   // DMA instructions (lanes past the range re-read its last record; an empty range reads the record at its start,
-  // which exists -- `sorted` ends with spare records -- and is not compared)
-  auto issue_a = [&](const ClipMeta& m) {
-    const uint32_t sA = PCD_BND(m, 4 * NK + 2), eA = PCD_BND(m, 4 * NK + 4);
+  // which exists -- `sorted` ends with spare records -- and is not compared).
+  // An EMPTY brick (48 % of workload M's items: the queries sit off the surfaces, only the halo is occupied) would
+  // leave every d_k at its incoming value and stage the whole region.  It takes a substitute range from the boundary
+  // table alone: the 26 other two-cell spans (row r, x boundaries 2 j .. 2 j + 2) are the neighbouring bricks; lane
+  // 7 r + 2 j forms its span's size from the table entry two lanes up (two wave shifts), one ballot gives the spans
+  // that hold a point, constant lane masks sort them into face, edge and corner neighbours, and the lowest class
+  // with a point is searched for its fullest span with one minimum over the lanes, ties to the lowest table entry
+  // (tools/brick_clip_sim.py prices the rules).  The range is wave-uniform -- its first record, and its length and
+  // first table entry in one word -- and is carried to the item's own iteration: the stage-B split follows it.
+  struct ARange { uint32_t s, ne; };   // first record; records staged (<= kATile) | first table entry (7 row + k) << 8
+  auto issue_a = [&](const ClipMeta& m) -> ARange {
+    uint32_t sA = PCD_BND(m, 4 * NK + 2), eA = PCD_BND(m, 4 * NK + 4);
+    uint32_t e = 4 * NK + 2;
+    if (sA == eA) {   // wave-uniform
+      // wave_shl:1 twice: lane l reads lane l + 2 (lanes 62 / 63 keep their own value: not a span's first lane)
+      uint32_t up = (uint32_t)__builtin_amdgcn_update_dpp((int)m.bnd, (int)m.bnd, 0x130, 0xf, 0xf, false);
+      up = (uint32_t)__builtin_amdgcn_update_dpp((int)up, (int)up, 0x130, 0xf, 0xf, false);
+      const uint32_t size = up - m.bnd;
+      const uint64_t occ = __builtin_amdgcn_ballot_w64(size != 0u);   // (the own span is empty; other lanes are masked away)
+      const uint64_t fc = occ & span_lanes(1), ed = occ & span_lanes(2), co = occ & span_lanes(3);
+      const uint64_t pick = fc ? fc : ed ? ed : co;
+      if (pick & (pick - 1)) {   // several spans of the class: the fullest
+        uint32_t key = ((0xFFFFFFu - min(size, 0xFFFFFFu)) << 6) | (uint32_t)lane;
+        asm("v_cndmask_b32_e64 %0, -1, %1, %2" : "=v"(key) : "v"(key), "s"(pick));
+        e = wave_min_u32(key) & 63u;
+      } else if (pick) {   // (a brick with an empty halo never becomes an item; a table of zeros would keep the own span)
+        e = (uint32_t)__builtin_ctzll(pick);
+      }
+      sA = PCD_RL(m.bnd, e); eA = PCD_RL(m.bnd, e + 2u);   // e = 7 row + 2 j: both entries lie in the row
+    }
     const uint32_t nA = min(eA - sA, (uint32_t)kATile);
     const uint32_t last = nA ? nA - 1u : 0u;
     const uint32_t i0 = sA + min((uint32_t)lane, last), i1 = sA + min((uint32_t)lane + 64u, last);
     lds_dma16(reinterpret_cast<const float4*>(src_bytes + ((uint64_t)i0 << 4)), bufA);
     lds_dma16(reinterpret_cast<const float4*>(src_bytes + ((uint64_t)i1 << 4)), bufA + 64);
+    return ARange{sA, nA | (e << 8)};
   };
 
   uint4 it0 = items[PCD_UNI(item)];   // through uniform (scalar) indices: brick_kernel.h PCD_UNI
   ClipMeta m0 = clip_load_meta(g, it0, qsorted, ksorted, cell_start, lpos);
   uint4 it1 = items[PCD_UNI(min(item + stride, item_end - 1))];
-  issue_a(m0);
+  ARange a0 = issue_a(m0);
 
   for (; item < item_end; item += stride) {
     // stage A of this item (issued while the previous item was compared) has landed; nothing else is in flight
@@ -226,9 +269,8 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
 #pragma unroll
     for (int k = 0; k < G; ++k) best[k] = __builtin_bit_cast(double, kKeyInit);
 
-    // ---- stage A: the brick's own cells ----------------------------------------------------------------------
-    const uint32_t sA = PCD_BND(m0, 4 * NK + 2), eA = PCD_BND(m0, 4 * NK + 4);
-    const uint32_t nA = min(eA - sA, (uint32_t)kATile);
+    // ---- stage A: the brick's own cells, or the neighbouring span issue_a chose for an empty brick ---------------
+    const uint32_t sA = a0.s, nA = a0.ne & 0xFFu;
     if (nA > 0 && !(flags & kAblateStageA)) {
       f32x4 pa[2];
       const uint32_t rd = lds_addr(bufA) + lane * 16;
@@ -312,20 +354,27 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
     // any number of range starts inside a tile.  Round 1-2a computed an address per 64-slot DMA window (three
     // v_readlane + ~10 VALU each, plus a generic path for windows with two starts); timing-only ablations put
     // that address generation at 0.34 ms of the kernel's 0.84.
+    // The row stage A took its records from (row 4, or the substitute's) goes without them: [s, min(e, sA)) stays the
+    // row's range -- the lanes of that row clamp their table entries to sA, so the row is read like every other --
+    // and [max(s, sA + nA), e) is range 9 (the hull need not contain a substitute's span; it does contain the
+    // brick's own cells, the queries lie in them).
+    const uint32_t rowA = ((a0.ne >> 8) * 9363u) >> 16;   // table entry / 7
+    const uint32_t bndL = (uint32_t)lane - 7u * rowA < 7u ? min(m0.bnd, sA) : m0.bnd;
     uint32_t rs[kClipRanges], rl[kClipRanges];
 #pragma unroll
     for (int r = 0; r < kClipRows; ++r) {
       const uint32_t xm = (M[r / 3] >> (6 * (r % 3))) & 63u;
       const int k0 = xm ? __builtin_ctz(xm) : 0, k1 = xm ? 32 - __builtin_clz(xm) : 0;   // cells k0 .. k1 - 1
-      const uint32_t s = PCD_BND(m0, r * NK + k0), e = PCD_BND(m0, r * NK + k1);
-      if (r == 4) {
-        // the centre row without what stage A staged: [s, sA) and [sA + nA, e)
-        const uint32_t rgt = sA + nA;
-        rs[4] = s; rl[4] = (xm && sA > s) ? sA - s : 0u;
-        rs[9] = rgt; rl[9] = (xm && e > rgt) ? e - rgt : 0u;
-      } else {
-        rs[r] = s; rl[r] = e - s;
-      }
+      const uint32_t s = PCD_RL(bndL, r * NK + k0), e = PCD_RL(bndL, r * NK + k1);   // (no masked cell: s == e)
+      rs[r] = s; rl[r] = e - s;
+    }
+    {
+      const uint64_t m54 = (uint64_t)M[0] | ((uint64_t)M[1] << 18) | ((uint64_t)M[2] << 36);
+      const uint32_t xm = (uint32_t)(m54 >> (6u * rowA)) & 63u;
+      const uint32_t k0 = xm ? (uint32_t)__builtin_ctz(xm) : 0u, k1 = xm ? 32u - (uint32_t)__builtin_clz(xm) : 0u;
+      const uint32_t e = PCD_BND(m0, rowA * NK + k1);
+      rs[9] = max(PCD_BND(m0, rowA * NK + k0), sA + nA);
+      rl[9] = e > rs[9] ? e - rs[9] : 0u;
     }
     uint32_t ro[kClipRanges + 1];   // start of range i in the concatenation padded to groups of 4 slots
     ro[0] = 0;
@@ -334,6 +383,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
     const uint32_t T = (flags & kAblateTiles) ? 0u : ro[kClipRanges];
     const int ntiles = (int)((T + kTile - 1) / kTile);
 
+    ARange a1;   // the next item's stage-A range: chosen once, where its DMAs are issued
     if (T > 0) {
       uint32_t dv[kClipRanges];   // source - start deltas in VGPRs (v_cndmask cannot read an SGPR next to VCC)
 #pragma unroll
@@ -361,7 +411,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
         lds_dma16_off<48>(gp, buf + 192 - 3);
       };
       issue_tile(0);
-      issue_a(m1);   // stage A of the NEXT item: lands under this item's tiles
+      a1 = issue_a(m1);   // stage A of the NEXT item: lands under this item's tiles
       // One tile loop per group size (cnt is wave-uniform): the dispatch on the number of queries happens once per item,
       // not once per tile -- the compare-and-branch chain in front of every tile's compare block was 7 % of the kernel
       // (0.488 -> 0.453 ms), more than any memory instruction of the loop.
@@ -414,7 +464,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
       const uint64_t red = __builtin_bit_cast(uint64_t, (flags & kAblateReduce) ? best[0] : wave_min8_key(best));
       mine = min_u64(mine, ((uint64_t)__shfl((uint32_t)(red >> 32), holder) << 32) | __shfl((uint32_t)red, holder));
     } else {
-      issue_a(m1);
+      a1 = issue_a(m1);
     }
     // ---- epilogue: final, or on to the exact fallback with the tentative key as starting bound ----------------
     bool unproven = false;
@@ -448,7 +498,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
       const uint32_t slots = (nA > 64 ? 128u : nA ? 64u : 0u) + (uint32_t)ntiles * kTile;
       st_staged += nA + T; st_pairs += (unsigned long long)slots * cnt; st_groups += 1;
     }
-    it0 = it1; it1 = it2; m0 = m1;
+    it0 = it1; it1 = it2; m0 = m1; a0 = a1;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last (redundant) stage-A prefetch must not outlive the wavefront's LDS
   if (lane < (int)fb_left) fb_list[fb_base + lane] = 0xFFFFFFFFu;   // rest of the last chunk
