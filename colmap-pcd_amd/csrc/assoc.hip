@@ -173,11 +173,6 @@ __global__ void k_pack_hits(const uint8_t* __restrict__ type, const uint32_t* __
   if (i == Q - 1) *count = pos[i] + (t != PCD_LIDAR_NONE ? 1u : 0u);
 }
 
-pcd_status nn_query_device_internal(pcd_cloud* c, const double* d_q, uint64_t Q, int algo, uint64_t* d_keys,
-                                    hipStream_t s);
-pcd_status nn_query_bounded_internal(pcd_cloud* c, const double* d_q, uint64_t Q, const double* d_max_range,
-                                     uint64_t mr_count, double fixed_range, uint64_t* d_keys, hipStream_t s);
-
 static AssocOut to_dev(const pcd_assoc_out* o) {
   AssocOut a{o->lidar_xyz, o->abcd, o->type, o->dist, o->angle, o->dist2plane, o->nn_idx, o->nn_sqdist};
   return a;

@@ -53,7 +53,8 @@ struct PyramidParams {
 // an inner node's child range travels through the walk's stack as first | (count - 1) << 26
 constexpr uint32_t kMaxPyrRecords = 1u << 26;
 
-struct QueryScratch;  // nn.hip
+struct QueryScratch;                          // scratch.h
+void free_query_scratch(QueryScratch* s);     // nn.hip
 
 // ownership of a global index by a shard: local row or 0xFFFFFFFFFFFFFFFF
 struct ShardIndex {

@@ -508,8 +508,6 @@ static pcd_status build_grid(pcd_cloud* c, float user_h, hipStream_t s) {
   return PCD_OK;
 }
 
-void free_query_scratch(QueryScratch* s);  // nn.hip
-
 }  // namespace pcd
 
 using namespace pcd;

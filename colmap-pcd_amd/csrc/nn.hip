@@ -9,8 +9,9 @@
 // the float distance go to the lowest index; a point only counts if
 // d < FLT_MAX (FLANN's initial worst distance).
 //
-// Three kernels, all with lanes = cloud points and wave-uniform queries, each
-// finishing with a per-wavefront min-reduction of packed keys:
+// Three search kernels, all with lanes = cloud points and wave-uniform queries, each
+// finishing with a per-wavefront min-reduction of packed keys (around them k_prepare<MODE>, k_finalize_keys and the
+// bookkeeping kernels described below; the host driver at the end strings them together, one path per call: choose_path):
 //   k_nn_bruteforce  all pairs; LDS-tiled; reference for the other two.
 //   k_nn_brick_clip  one wavefront per group of <= G queries that fall into
 //                    the same brick of 2^3 grid cells: the brick's own cells, then
@@ -72,9 +73,10 @@ namespace pcd {
 void free_query_scratch(QueryScratch* s) { delete s; }
 
 constexpr uint64_t kKeyInit = (uint64_t)0x7F7FFFFFu << 32;  // (FLT_MAX, idx 0): nothing with d >= FLT_MAX beats it
-// Batches up to this size skip the grid path (query sort + brick kernel + fallback = 13 launches) and go
-// straight to the per-wavefront hierarchical search, one launch: measured on a 2 M-point cloud
-// (tools/nn_latency.py), 20 k queries take 99 us that way against 190 us, 100 k queries 290 against 329.
+// Batches up to this size skip the grid path (query sort + brick kernel + list squeeze + fallback = 8 launches with the
+// counting-sort bookkeeping; 13 with the radix sort at the time of the measurement) and go straight to the
+// per-wavefront hierarchical search, one launch: measured on a 2 M-point cloud (tools/nn_latency.py), 20 k queries take
+// 99 us that way against 190 us, 100 k queries 290 against 329.
 constexpr uint64_t kSmallBatch = 65536;
 
 // ------------------------------------------------------------ brick math ---
@@ -114,21 +116,13 @@ __device__ __forceinline__ uint64_t finalized_key(uint64_t k) {
 // ------------------------------------------------------- query preparation --
 // ply.cc:92: feature_point.getVector3fMap() = point_3d.cast<float>()
 // One __device__ function per prepare flavour: the record qf4[i] is returned, the query's initial key goes to *key.
-// Shared by the stand-alone k_prepare_* kernels and by k_bk_slots, which does the preparation itself on the
-// counting-sort path: the arithmetic lives here only.
+// Shared by the stand-alone k_prepare<MODE> and by k_bk_slots, which does the preparation itself on the counting-sort
+// path: the arithmetic lives here only.
 __device__ __forceinline__ float4 prepare_plain(const double* __restrict__ q, uint64_t i, uint64_t* key) {
   float x = (float)q[3 * i], y = (float)q[3 * i + 1], z = (float)q[3 * i + 2];
   bool ok = isfinite(x) && isfinite(y) && isfinite(z);
   *key = ok ? kKeyInit : PCD_KEY_NONE;   // a query no search kernel touches leaves with its final key
   return make_float4(x, y, z, ok ? 1.f : 0.f);
-}
-__global__ void k_prepare_queries(const double* __restrict__ q, uint64_t Q, float4* __restrict__ qf4,
-                                  uint64_t* __restrict__ keys) {
-  uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (i >= Q) return;
-  uint64_t k;
-  qf4[i] = prepare_plain(q, i, &k);
-  keys[i] = k;
 }
 
 // pcd_nn_refine_device: the keys come in with another shard's results.  A query stays active only if this shard
@@ -149,14 +143,6 @@ __device__ __forceinline__ float4 prepare_refine(const double* __restrict__ q, u
   }
   *key = ok ? k : finalized_key(k);   // inactive: the key it came with, in its final form
   return make_float4(x, y, z, ok ? 1.f : 0.f);
-}
-__global__ void k_prepare_refine(const double* __restrict__ q, uint64_t Q, const uint8_t* __restrict__ skip, BoxF bx,
-                                 float4* __restrict__ qf4, uint64_t* __restrict__ keys) {
-  uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (i >= Q) return;
-  uint64_t k = keys[i];
-  qf4[i] = prepare_refine(q, i, skip, bx, &k);
-  keys[i] = k;
 }
 
 // Gate-bounded search (the association entry points): the three call sites reject an association whose point-to-point
@@ -193,17 +179,9 @@ __device__ __forceinline__ float4 prepare_bounded(const double* __restrict__ q, 
             : PCD_KEY_NONE;
   return make_float4(x, y, z, ok ? 1.f : 0.f);
 }
-__global__ void k_prepare_bounded(const double* __restrict__ q, uint64_t Q, const double* __restrict__ max_range,
-                                  uint64_t mr_count, double fixed_range, float4* __restrict__ qf4,
-                                  uint64_t* __restrict__ keys) {
-  uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (i >= Q) return;
-  uint64_t k;
-  qf4[i] = prepare_bounded(q, i, max_range, mr_count, fixed_range, &k);
-  keys[i] = k;
-}
 
-// which prepare flavour a call uses, and its inputs (host and device)
+// which prepare flavour a call uses, and its inputs (host and device; NnCall: the two together, as the entry points
+// hand them to the driver)
 enum { kPrepPlain = 0, kPrepRefine = 1, kPrepBounded = 2 };
 struct PrepArgs {
   const double* q;             // the caller's queries, 3 doubles each
@@ -213,11 +191,28 @@ struct PrepArgs {
   uint64_t mr_count;
   double fixed_range;
 };
+struct NnCall { int prep; PrepArgs pa; };
 template <int MODE>
 __device__ __forceinline__ float4 prepare_query(const PrepArgs& a, uint64_t i, uint64_t* key) {
   if (MODE == kPrepRefine) return prepare_refine(a.q, i, a.skip, a.box, key);
   if (MODE == kPrepBounded) return prepare_bounded(a.q, i, a.max_range, a.mr_count, a.fixed_range, key);
   return prepare_plain(a.q, i, key);
+}
+// the stand-alone prepare pass of every path whose first search kernel does not prepare the queries itself
+template <int MODE>
+__global__ void k_prepare(PrepArgs pa, uint64_t Q, float4* __restrict__ qf4, uint64_t* __restrict__ keys) {
+  uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+  if (i >= Q) return;
+  uint64_t k = MODE == kPrepRefine ? keys[i] : 0;   // refine: the key the query comes with
+  qf4[i] = prepare_query<MODE>(pa, i, &k);
+  keys[i] = k;
+}
+// the prepare flavour of a call as a template argument: f(std::integral_constant<int, MODE>)
+template <class F>
+static void with_prep_mode(int mode, F&& f) {
+  if (mode == kPrepBounded) f(std::integral_constant<int, kPrepBounded>{});
+  else if (mode == kPrepRefine) f(std::integral_constant<int, kPrepRefine>{});
+  else f(std::integral_constant<int, kPrepPlain>{});
 }
 
 __global__ void k_finalize_keys(uint64_t* __restrict__ keys, uint64_t Q) {
@@ -338,12 +333,9 @@ __device__ __forceinline__ void brick_tile(const uint32_t* __restrict__ keys, ui
     s_left[0] = left;
   }
   __syncthreads();
-  uint32_t carry = (uint32_t)__builtin_amdgcn_readlane((int)inc, 0);   // placeholder, replaced below
-  {
-    uint32_t up = __shfl_up(inc, 1);
-    carry = lane == 0 ? 0u : up;            // exclusive within the wave
-    for (uint32_t w = 0; w < wave; ++w) carry = max(carry, s_wave[w]);
-  }
+  const uint32_t up = __shfl_up(inc, 1);
+  uint32_t carry = lane == 0 ? 0u : up;     // exclusive within the wave
+  for (uint32_t w = 0; w < wave; ++w) carry = max(carry, s_wave[w]);
   const uint32_t left = s_left[0];
   uint32_t cnt = 0;
 #pragma unroll
@@ -439,14 +431,14 @@ __global__ __launch_bounds__(256) void k_brick_emit(const uint32_t* __restrict__
 // ------------------------------------------- brick bookkeeping, counting sort ---
 // Five short launches instead of the radix sort's seven (round 2: 0.17 ms at Q = 1 M, three Onesweep digit passes at
 // ~29 us each whatever the size), and nothing in front of them: the first one reads the caller's double queries itself
-// (no stand-alone prepare pass) and the counters clean themselves (no memset, see counters_ready).  Per cloud and brick
+// (no stand-alone prepare pass) and the counters clean themselves (no memset, see take_counters).  Per cloud and brick
 // geometry, once: one bit for every brick whose halo region holds at least one cloud point (k_brick_occupied +
 // k_brick_bitmap); a query in a brick without the bit has nothing within the halo and goes straight to the exact
 // fallback -- which is where the brick kernel would have sent it after walking an empty region.  Per batch a two-level
 // counting sort on the brick id:
 //   k_bk_slots<MODE>  at most 256 workgroups, each with a contiguous RANGE of rounds x 4096 queries.  Per query: the
-//                 prepare flavour MODE (prepare_query: float record qf4[i] and initial key keys[i], as the k_prepare_*
-//                 kernels write them on the other paths), then the sort key (brick id) or "fallback" (outside the grid /
+//                 prepare flavour MODE (prepare_query: float record qf4[i] and initial key keys[i], as k_prepare<MODE>
+//                 writes them on the other paths), then the sort key (brick id) or "fallback" (outside the grid /
 //                 brick with an empty halo region: those are appended to the chunked fallback list here).  The LDS
 //                 histogram of the COARSE keys (id >> shift, at most 4096 buckets) is left as one row of a
 //                 [ranges][buckets] matrix -- no global atomics.  One thread clears the counters of the NEXT call.
@@ -517,9 +509,6 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_w /*
   *total = tot;
   return base + inc - v;
 }
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t* s_w, uint32_t* total) {
-  return block_excl_scan<4>(v, s_w, total);
-}
 
 template <int MODE>   // the call's prepare flavour, a template parameter for the reason given at k_nn_fallback<FUSED>
 __global__ __launch_bounds__(1024) void k_bk_slots(PrepArgs pa, uint32_t Q, uint32_t rounds, GridParams g, BrickParams b,
@@ -547,7 +536,7 @@ __global__ __launch_bounds__(1024) void k_bk_slots(PrepArgs pa, uint32_t Q, uint
       const uint64_t i = r0 + k * 1024u + threadIdx.x;
       uint32_t s = kSlotSkip;
       if (i < Q) {
-        // the caller's double query -> float record and initial key (what the k_prepare_* kernels do elsewhere)
+        // the caller's double query -> float record and initial key (what k_prepare<MODE> does elsewhere)
         uint64_t key = MODE == kPrepRefine ? keys[i] : 0;
         const float4 q = prepare_query<MODE>(pa, i, &key);
         qf4[i] = q;
@@ -665,7 +654,7 @@ __global__ __launch_bounds__(256) void k_bk_count(uint32_t shift, const uint32_t
   uint32_t ai = 0;
   for (uint32_t f = threadIdx.x; f < nfine; f += 256) ai += (s_cnt[f] + G - 1) / G;
   uint32_t ti;
-  (void)block_excl_scan_256(ai, s_w, &ti);
+  (void)block_excl_scan<4>(ai, s_w, &ti);
   if (threadIdx.x == 0) bitems[blockIdx.x] = ti;
 }
 
@@ -688,7 +677,7 @@ __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4,
   uint32_t acc = 0;
   for (uint32_t c = threadIdx.x; c < blockIdx.x; c += 256) acc += bitems[c];
   uint32_t ibase;
-  (void)block_excl_scan_256(acc, s_w, &ibase);
+  (void)block_excl_scan<4>(acc, s_w, &ibase);
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) ctr->nitems = ibase + bitems[blockIdx.x];
   if (beg == end) return;
   for (uint32_t f = threadIdx.x; f < nfine; f += 256) s_cur[f] = 0;
@@ -713,8 +702,8 @@ __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4,
     uint32_t aq = 0, ai = 0;
     for (uint32_t f = f0; f < min(f0 + per, nfine); ++f) { aq += s_cur[f]; ai += (s_cur[f] + G - 1) / G; }
     uint32_t tq, ti;
-    uint32_t bq = block_excl_scan_256(aq, s_w, &tq);
-    uint32_t bi = block_excl_scan_256(ai, s_w, &ti);
+    uint32_t bq = block_excl_scan<4>(aq, s_w, &tq);
+    uint32_t bi = block_excl_scan<4>(ai, s_w, &ti);
     for (uint32_t f = f0; f < min(f0 + per, nfine); ++f) {
       const uint32_t c = s_cur[f];
       s_off[f] = bq; s_ioff[f] = bi; bq += c; bi += (c + G - 1) / G;
@@ -752,7 +741,6 @@ __global__ __launch_bounds__(256) void k_bk_emit(const float4* __restrict__ qf4,
 #include "brick_kernel.h"
 #include "brick_clip_kernel.h"
 namespace pcd {
-
 
 // The brick kernel fills the fallback list in per-wavefront chunks (brick_kernel.h kFbChunk); the unused slots of
 // the chunks keep 0xFFFFFFFF.  One pass squeezes them out (wave-aggregated atomics: the order of the dense list is
@@ -1018,6 +1006,20 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
 // the hardware's workgroup dispatch as the load balancer (query costs spread 1:4).  2048 / 4096 / 16384 / 65536
 // workgroups: 0.384 / 0.387 / 0.368 / 0.369 ms at workload M, 0.136 / 0.125 / 0.126 / 0.125 ms on an eighth of it.
 constexpr unsigned g_fb_max_blocks = 16384;
+// where k_nn_fallback finds its queries: prepared records (FUSED == 0) or the caller's doubles (FUSED != 0); the
+// queries list[0 .. *list_count), or without a list 0 .. n - 1 (n: an upper bound when the list's length is on the device)
+struct FbQueries {
+  const float4* qf4;
+  FbFused fused;
+  const uint32_t *list, *list_count;
+};
+template <int FUSED>
+static void launch_fallback(const pcd_cloud* c, const float4* seeds, const FbQueries& src, uint64_t n, uint64_t* keys,
+                            NnCounters* ctr, int collect_stats, hipStream_t s) {
+  hipLaunchKernelGGL(k_nn_fallback<FUSED>, dim3((unsigned)std::min<uint64_t>(div_up(n, 4), g_fb_max_blocks)), dim3(256), 0,
+                     s, c->grid, c->pyr, c->sorted.p, c->cell_start.p, c->blk_aabb.p, seeds, src.qf4, src.list,
+                     src.list_count, src.list_count ? 0u : (uint32_t)n, keys, ctr, collect_stats, src.fused);
+}
 // process-global tuning state (pcd_nn_set_*: experiments and tests, not part of the stable ABI): independent atomic
 // switches, each read once at the top of a call
 static std::atomic<int> g_collect_stats{0};
@@ -1029,7 +1031,6 @@ constexpr int g_brick_blocks_per_cu = PCD_BRICK_MINWAVES;
 // first stage of the grid path: 0 = the clipped brick kernel (brick_clip_kernel.h), 1 = the same kernel with the clip
 // switched off (A/B timing and tests: it then stages the whole region; results identical)
 static std::atomic<int> g_nn_kernel{0};
-
 static std::atomic<int> g_bk_sort{0};   // 1: force the radix-sort bookkeeping (A/B timing, tests)
 
 // slot table of the cloud (built on first use)
@@ -1084,10 +1085,7 @@ static pcd_status fb_seed_table(pcd_cloud* c, QueryScratch* sc, hipStream_t s) {
   PCD_TRY(keys.reserve(n));
   hipLaunchKernelGGL(k_seed_init, dim3(div_up(n, 256)), dim3(256), 0, s, c->grid, py.seed_dims[0], py.seed_dims[1],
                      py.seed_dims[2], seeds.p, qf4.p, keys.p);
-  hipLaunchKernelGGL(k_nn_fallback<0>, dim3((unsigned)std::min<uint64_t>(div_up(n, 4), g_fb_max_blocks)), dim3(256), 0, s,
-                     c->grid, py, c->sorted.p, c->cell_start.p, c->blk_aabb.p, (const float4*)seeds.p, qf4.p,
-                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)n, keys.p, (NnCounters*)nullptr, 0,
-                     FbFused{nullptr, nullptr, 0, 0.0});
+  launch_fallback<0>(c, seeds.p, {qf4.p}, n, keys.p, nullptr, 0, s);
   hipLaunchKernelGGL(k_seed_gather, dim3(div_up(n, 256)), dim3(256), 0, s, keys.p, n, c->shard_index(), c->pts4.p, seeds.p);
   PCD_HIP_TRY(hipGetLastError());
   PCD_HIP_TRY(hipStreamSynchronize(s));   // one-off per cloud; qf4 / keys go out of scope
@@ -1098,9 +1096,10 @@ static pcd_status fb_seed_table(pcd_cloud* c, QueryScratch* sc, hipStream_t s) {
 // The counters: two blocks, zeroed once when they are allocated.  Grid-path calls with the counting-sort bookkeeping
 // use them alternately and need no memset of their own: k_bk_slots of call n clears the block call n + 1 will use (its
 // last users, the kernels of call n - 1, finished before call n started on the stream).  sc->ctr_cur is the block of
-// the last call (pcd_nn_last_stats reads it); every other path clears and uses that block with its own memset.
-// sc->ctr_next_clean is false from the start of a counting-sort call until all of its launches went through: a call
-// that failed part-way makes the next one fall back to the memset.
+// the last call (pcd_nn_last_stats reads it); every other path clears and uses that block with its own memset (the
+// one-launch walk only when it collects statistics: nothing else reads its counters).
+// sc->ctr_next_clean is false from the start of a counting-sort call until all of its launches went through
+// (counters_left_clean): a call that failed part-way makes the next one fall back to the memset.
 static pcd_status counters_ready(QueryScratch* sc, hipStream_t s) {
   if (sc->counters.p) return PCD_OK;
   PCD_TRY(sc->counters.reserve(2));
@@ -1109,24 +1108,50 @@ static pcd_status counters_ready(QueryScratch* sc, hipStream_t s) {
   sc->ctr_next_clean = true;
   return PCD_OK;
 }
+// hands a path its block (*ctr; *ctr_next: the block of the next alternating call), cleared where the path needs it
+enum class CtrUse { kAlternate, kClear, kClearForStats };
+static pcd_status take_counters(QueryScratch* sc, CtrUse use, int collect_stats, hipStream_t s, NnCounters** ctr,
+                                NnCounters** ctr_next = nullptr) {
+  PCD_TRY(counters_ready(sc, s));
+  const bool clean = use == CtrUse::kAlternate ? sc->ctr_next_clean : use == CtrUse::kClearForStats && !collect_stats;
+  if (use == CtrUse::kAlternate) {
+    sc->ctr_cur = 1 - sc->ctr_cur;
+    sc->ctr_next_clean = false;
+  }
+  *ctr = sc->counters.p + sc->ctr_cur;
+  if (ctr_next) *ctr_next = sc->counters.p + (1 - sc->ctr_cur);
+  if (!clean) PCD_HIP_TRY(hipMemsetAsync(*ctr, 0, sizeof(NnCounters), s));
+  return PCD_OK;
+}
+static void counters_left_clean(QueryScratch* sc) { sc->ctr_next_clean = true; }
 
-static void launch_prepare(int mode, const PrepArgs& pa, uint64_t Q, float4* qf4, uint64_t* d_keys, hipStream_t s) {
+static void launch_prepare(const NnCall& call, uint64_t Q, float4* qf4, uint64_t* d_keys, hipStream_t s) {
   ScopedKernelTimer t("nn_prepare", s);
-  if (mode == kPrepBounded)
-    hipLaunchKernelGGL(k_prepare_bounded, dim3(div_up(Q, 256)), dim3(256), 0, s, pa.q, Q, pa.max_range, pa.mr_count,
-                       pa.fixed_range, qf4, d_keys);
-  else if (mode == kPrepRefine)
-    hipLaunchKernelGGL(k_prepare_refine, dim3(div_up(Q, 256)), dim3(256), 0, s, pa.q, Q, pa.skip, pa.box, qf4, d_keys);
-  else
-    hipLaunchKernelGGL(k_prepare_queries, dim3(div_up(Q, 256)), dim3(256), 0, s, pa.q, Q, qf4, d_keys);
+  with_prep_mode(call.prep, [&](auto mode) {
+    hipLaunchKernelGGL(k_prepare<decltype(mode)::value>, dim3(div_up(Q, 256)), dim3(256), 0, s, call.pa, Q, qf4, d_keys);
+  });
+}
+static void launch_finalize(uint64_t Q, uint64_t* d_keys, hipStream_t s) {
+  ScopedKernelTimer t("nn_finalize", s);
+  hipLaunchKernelGGL(k_finalize_keys, dim3(div_up(Q, 256)), dim3(256), 0, s, d_keys, Q);
+}
+static void launch_bruteforce(const pcd_cloud* c, const float4* qf4, uint64_t Q, uint64_t* d_keys, hipStream_t s) {
+  ScopedKernelTimer t("nn_bruteforce", s);
+  // enough chunks to fill the chip even for few queries
+  const unsigned qblocks = div_up(Q, 256);
+  unsigned chunks = std::max(1u, std::min<unsigned>(div_up(c->n, 4096), 2048u / std::max(1u, qblocks)));
+  chunks = std::min(chunks, 65535u);
+  const uint64_t chunk = ((c->n + chunks - 1) / chunks + 1023) / 1024 * 1024;
+  chunks = div_up(c->n, chunk);
+  hipLaunchKernelGGL(k_nn_bruteforce, dim3(qblocks, chunks), dim3(256), 0, s, c->pts4.p, c->n, c->index_base,
+                     c->index_stride, c->row_index.p, qf4, Q, chunk, d_keys);
 }
 
-// prep / pa: the call's prepare flavour.  The counting-sort bookkeeping does the preparation in its first kernel; the
-// radix-sort bookkeeping runs the stand-alone prepare kernel first.
-template <int G>
-static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t* d_keys, hipStream_t s, int prep,
-                           const PrepArgs& pa) {
-  const bool refine = prep != kPrepPlain;   // incoming keys matter: carry them
+// The grid path: query bookkeeping, brick kernel, exact fallback for what is left.  The counting-sort bookkeeping does
+// the preparation in its first kernel; the radix-sort bookkeeping runs the stand-alone prepare kernel first.
+constexpr int kGroup = 8;   // queries per work item of the brick kernel (brick_clip_kernel.h is written for 8)
+static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t* d_keys, hipStream_t s, const NnCall& call) {
+  const uint64_t* carried_keys = call.prep != kPrepPlain ? d_keys : nullptr;   // refine, gate-bounded: the keys the queries come with matter
   const GridParams& g = c->grid;
   const int nn_kernel = g_nn_kernel.load(), bk_sort = g_bk_sort.load(), collect_stats = g_collect_stats.load();
   const BrickParams b = make_bricks(g);
@@ -1142,25 +1167,15 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
   PCD_TRY(sc->bk_vals.reserve(2 * Q));
   PCD_TRY(sc->bk_item.reserve(div_up(Q, kBkTile) + 1));
   PCD_TRY(sc->items.reserve(Q + 1));
-  PCD_TRY(counters_ready(sc, s));
+  PCD_TRY(counters_ready(sc, s));   // (the one-off work of a cloud's first call, in this order)
   PCD_TRY(brick_slots(c, sc, b, s));
   // sort key = brick id: coarse key = id >> shift (at most 4096 buckets), fine key = the low bits (at most 4096)
   uint32_t shift = 8;
   while ((((uint64_t)b.nbricks + (1u << shift) - 1) >> shift) > 2304 && shift < 16) ++shift;
   const uint32_t ncoarse = std::max<uint32_t>(1u, (uint32_t)(((uint64_t)b.nbricks + (1u << shift) - 1) >> shift));
   const bool counting = (1u << shift) <= kBkMaxFine && ncoarse <= kBkMaxCoarse && bk_sort == 0;
-  NnCounters* ctr;
-  if (counting) {
-    const int use = 1 - sc->ctr_cur;
-    ctr = sc->counters.p + use;
-    if (!sc->ctr_next_clean) PCD_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(NnCounters), s));   // after a failed call
-    sc->ctr_next_clean = false;
-    sc->ctr_cur = use;
-  } else {
-    ctr = sc->counters.p + sc->ctr_cur;
-    PCD_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(NnCounters), s));
-    launch_prepare(prep, pa, Q, sc->qf4.p, d_keys, s);
-  }
+  NnCounters *ctr, *ctr_next;
+  PCD_TRY(take_counters(sc, counting ? CtrUse::kAlternate : CtrUse::kClear, collect_stats, s, &ctr, &ctr_next));
   if (counting) {
     ScopedKernelTimer t("nn_brick_bookkeeping", s);
     // bucket totals | bucket starts | items per bucket; the histogram matrix [ranges][ncoarse] (<= 256 x 4096 entries);
@@ -1171,22 +1186,20 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
     uint32_t *ctot = sc->bk_chist.p, *cstart = ctot + kBkMaxCoarse + 1, *bitems = cstart + kBkMaxCoarse + 1;
     uint32_t* qslot = sc->bk_keys.p;
     uint2* ppair = reinterpret_cast<uint2*>(sc->bk_vals.p);   // 2 Q words: Q {fine key, query id} pairs
-    NnCounters* ctr_next = sc->counters.p + (1 - sc->ctr_cur);
-#define PCD_BK_SLOTS(MODE)                                                                                            \
-    hipLaunchKernelGGL(k_bk_slots<MODE>, dim3(nranges), dim3(1024), 0, s, pa, (uint32_t)Q, rounds, g, b, sc->bk_slot.p, \
-                       shift, ncoarse, sc->qf4.p, d_keys, qslot, sc->bk_hmat.p, sc->fb_list.p, ctr, ctr_next)
-    if (prep == kPrepBounded) PCD_BK_SLOTS(kPrepBounded);
-    else if (prep == kPrepRefine) PCD_BK_SLOTS(kPrepRefine);
-    else PCD_BK_SLOTS(kPrepPlain);
-#undef PCD_BK_SLOTS
+    with_prep_mode(call.prep, [&](auto mode) {
+      hipLaunchKernelGGL(k_bk_slots<decltype(mode)::value>, dim3(nranges), dim3(1024), 0, s, call.pa, (uint32_t)Q, rounds,
+                         g, b, sc->bk_slot.p, shift, ncoarse, sc->qf4.p, d_keys, qslot, sc->bk_hmat.p, sc->fb_list.p, ctr,
+                         ctr_next);
+    });
     hipLaunchKernelGGL(k_bk_colscan, dim3(div_up(ncoarse, 64)), dim3(1024), 0, s, sc->bk_hmat.p, nranges, ncoarse, ctot);
     hipLaunchKernelGGL(k_bk_scatter, dim3(nranges), dim3(1024), 0, s, qslot, (uint32_t)Q, rounds, shift, ncoarse, ctot,
                        sc->bk_hmat.p, cstart, ppair, ctr);
-    hipLaunchKernelGGL(k_bk_count<G>, dim3(ncoarse), dim3(256), 0, s, shift, cstart, ppair, bitems);
-    hipLaunchKernelGGL(k_bk_emit<G>, dim3(ncoarse), dim3(256), (3u * (1u << shift) + 2u) * sizeof(uint32_t), s, sc->qf4.p, refine ? d_keys : (const uint64_t*)nullptr,
-                       g, b, shift, cstart, ppair, bitems, sc->items.p, sc->qsorted.p, sc->ksorted.p, ctr);
+    hipLaunchKernelGGL(k_bk_count<kGroup>, dim3(ncoarse), dim3(256), 0, s, shift, cstart, ppair, bitems);
+    hipLaunchKernelGGL(k_bk_emit<kGroup>, dim3(ncoarse), dim3(256), (3u * (1u << shift) + 2u) * sizeof(uint32_t), s,
+                       sc->qf4.p, carried_keys, g, b, shift, cstart, ppair, bitems, sc->items.p, sc->qsorted.p, sc->ksorted.p, ctr);
   } else {
     // (grids with more than 8 M occupied bricks: the radix-sort bookkeeping of round 2)
+    launch_prepare(call, Q, sc->qf4.p, d_keys, s);
     ScopedKernelTimer t("nn_brick_bookkeeping", s);
     uint32_t *k0 = sc->bk_keys.p, *k1 = sc->bk_keys.p + Q, *v0 = sc->bk_vals.p, *v1 = sc->bk_vals.p + Q;
     hipLaunchKernelGGL(k_brick_keys, dim3(div_up(Q, 256)), dim3(256), 0, s, sc->qf4.p, Q, g, b, k0, v0);
@@ -1203,14 +1216,14 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
     PCD_TRY(sc->tmp.reserve(tb));
     PCD_HIP_TRY(rocprim::radix_sort_pairs<SortCfg>(sc->tmp.p, tb, k0, k1, v0, v1, (unsigned)Q, 0u, end_bit, s));
     const unsigned ntiles = div_up(Q, kBkTile);
-    hipLaunchKernelGGL(k_brick_tile_count<G>, dim3(ntiles), dim3(256), 0, s, k1, (uint32_t)Q, b.nbricks, sc->bk_item.p);
-    hipLaunchKernelGGL(k_brick_emit<G>, dim3(ntiles), dim3(256), 0, s, k1, v1, sc->bk_item.p, sc->qf4.p,
-                       refine ? d_keys : (const uint64_t*)nullptr, (uint32_t)Q, b.nbricks, (uint32_t)b.nb[0],
-                       (uint32_t)b.nb[1], sc->items.p, sc->qsorted.p, sc->ksorted.p, sc->fb_list.p, ctr);
+    hipLaunchKernelGGL(k_brick_tile_count<kGroup>, dim3(ntiles), dim3(256), 0, s, k1, (uint32_t)Q, b.nbricks, sc->bk_item.p);
+    hipLaunchKernelGGL(k_brick_emit<kGroup>, dim3(ntiles), dim3(256), 0, s, k1, v1, sc->bk_item.p, sc->qf4.p, carried_keys,
+                       (uint32_t)Q, b.nbricks, (uint32_t)b.nb[0], (uint32_t)b.nb[1], sc->items.p, sc->qsorted.p,
+                       sc->ksorted.p, sc->fb_list.p, ctr);
   }
   {
     ScopedKernelTimer t("nn_brick", s);
-    const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(div_up(Q, G), 4) + 1, 256 * (uint64_t)g_brick_blocks_per_cu);
+    const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(div_up(Q, kGroup), 4) + 1, 256 * (uint64_t)g_brick_blocks_per_cu);
     const int fl = (collect_stats & ~2) | (nn_kernel == 1 ? 2 : 0);
     hipLaunchKernelGGL(k_nn_brick_clip, dim3(blocks), dim3(256), 0, s, g, c->sorted.p, c->cell_start.p, sc->qsorted.p,
                        sc->ksorted.p, sc->items.p, ctr, d_keys, sc->fb_list.p, &ctr->fb_count, fl);
@@ -1220,106 +1233,90 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
     PCD_TRY(sc->fb_dense.reserve(Q));
     hipLaunchKernelGGL(k_fb_compact, dim3(div_up(fb_cap, kFbcThreads * kFbcPer)), dim3(kFbcThreads), 0, s, sc->fb_list.p,
                        &ctr->fb_count, sc->fb_dense.p, &ctr->pad[0]);
-    const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(Q, 4), g_fb_max_blocks);
-    hipLaunchKernelGGL(k_nn_fallback<0>, dim3(blocks), dim3(256), 0, s, g, c->pyr, c->sorted.p, c->cell_start.p,
-                       c->blk_aabb.p, sc->fb_seed.p, sc->qf4.p, sc->fb_dense.p, &ctr->pad[0], 0u, d_keys,
-                       ctr, collect_stats, FbFused{nullptr, nullptr, 0, 0.0});
+    launch_fallback<0>(c, sc->fb_seed.p, {sc->qf4.p, {}, sc->fb_dense.p, &ctr->pad[0]}, Q, d_keys, ctr, collect_stats, s);
   }
   PCD_HIP_TRY(hipGetLastError());
-  if (counting) sc->ctr_next_clean = true;   // every launch went through: k_bk_slots has left the other block clean
+  if (counting) counters_left_clean(sc);   // every launch went through: k_bk_slots has left the other block clean
   return PCD_OK;
 }
 
-struct NnBound {        // gate-bounded search: per-query / scalar ranges, or one fixed range; count == 0: unbounded
-  const double* d_max_range = nullptr;
-  uint64_t count = 0;
-  double fixed = 0.0;
-};
+// The one place that decides which way a call goes.  kOneLaunch: k_nn_fallback converts the queries itself and writes
+// finalised keys, so the per-call latency of a small batch (and of PCD_NN_FALLBACK_ONLY) is one kernel instead of
+// prepare + memset + search; refining another shard's keys, the keys come in, so the prepare kernel stays (kPrepareWalk).
+enum class NnPath { kEmptyCloud, kBruteForce, kOneLaunch, kPrepareWalk, kGrid };
+static pcd_status choose_path(bool empty_cloud, int algo, uint64_t Q, int prep, NnPath* path) {
+  const NnPath walk = prep == kPrepRefine ? NnPath::kPrepareWalk : NnPath::kOneLaunch;
+  if (empty_cloud) *path = NnPath::kEmptyCloud;   // whatever the algo
+  else if (algo == PCD_NN_BRUTEFORCE) *path = NnPath::kBruteForce;
+  else if (algo == PCD_NN_FALLBACK_ONLY) *path = walk;
+  else if (algo == PCD_NN_AUTO) *path = Q <= kSmallBatch ? walk : NnPath::kGrid;
+  else if (algo == PCD_NN_GRID) *path = NnPath::kGrid;
+  else {
+    set_error("unknown nn algo %d", algo);
+    return PCD_ERR_INVALID;
+  }
+  return PCD_OK;
+}
 
-static pcd_status nn_device(pcd_cloud* c, const double* d_q, uint64_t Q, int algo, uint64_t* d_keys,
-                            hipStream_t s, bool refine = false, const uint8_t* d_skip = nullptr,
-                            const NnBound* bound = nullptr) {
+static pcd_status nn_device(pcd_cloud* c, const NnCall& call, uint64_t Q, int algo, uint64_t* d_keys, hipStream_t s) {
   QueryScratch* sc = scratch_of(c);
   if (Q == 0) return PCD_OK;
   PCD_REQUIRE(Q < 0xFFFFFFF0ull, "more than 2^32 queries in one call");
+  NnPath path;
+  PCD_TRY(choose_path(c->m == 0, algo, Q, call.prep, &path));
   const int collect_stats = g_collect_stats.load();
-  // Small batches (and PCD_NN_FALLBACK_ONLY): ONE launch -- k_nn_fallback converts the queries itself and writes
-  // finalised keys, so the per-call latency is one kernel instead of prepare + memset + search + finalize.
-  const bool one_launch = c->m > 0 && !refine &&
-                          (algo == PCD_NN_FALLBACK_ONLY || (algo == PCD_NN_AUTO && Q <= kSmallBatch));
-  if (c->m > 0 && algo != PCD_NN_BRUTEFORCE) PCD_TRY(fb_seed_table(c, sc, s));
-  if (one_launch) {
-    PCD_TRY(counters_ready(sc, s));
-    NnCounters* ctr = sc->counters.p + sc->ctr_cur;
-    if (collect_stats) PCD_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(NnCounters), s));
-    ScopedKernelTimer t("nn_fallback", s);
-    const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(Q, 4), g_fb_max_blocks);
-    const FbFused fu{d_q, bound ? bound->d_max_range : nullptr, bound ? bound->count : 0, bound ? bound->fixed : 0.0};
-    if (bound)
-      hipLaunchKernelGGL(k_nn_fallback<2>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
-                         c->blk_aabb.p, sc->fb_seed.p, (const float4*)nullptr, (const uint32_t*)nullptr,
-                         (const uint32_t*)nullptr, (uint32_t)Q, d_keys, ctr, collect_stats, fu);
-    else
-      hipLaunchKernelGGL(k_nn_fallback<1>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
-                         c->blk_aabb.p, sc->fb_seed.p, (const float4*)nullptr, (const uint32_t*)nullptr,
-                         (const uint32_t*)nullptr, (uint32_t)Q, d_keys, ctr, collect_stats, fu);
-    PCD_HIP_TRY(hipGetLastError());
-    return PCD_OK;
-  }
-  PCD_TRY(sc->qf4.reserve(Q));
-  const int prep = bound ? kPrepBounded : refine ? kPrepRefine : kPrepPlain;
-  const PrepArgs pa{d_q, d_skip, BoxF{c->bb_lo[0], c->bb_lo[1], c->bb_lo[2], c->bb_hi[0], c->bb_hi[1], c->bb_hi[2]},
-                    bound ? bound->d_max_range : nullptr, bound ? bound->count : 0, bound ? bound->fixed : 0.0};
-  const bool small = algo == PCD_NN_FALLBACK_ONLY || (algo == PCD_NN_AUTO && Q <= kSmallBatch);
-  // the grid path prepares the queries itself (run_grid); every other path starts with the stand-alone kernel
-  const bool grid = c->m > 0 && algo != PCD_NN_BRUTEFORCE && !small && (algo == PCD_NN_AUTO || algo == PCD_NN_GRID);
-  if (!grid) launch_prepare(prep, pa, Q, sc->qf4.p, d_keys, s);
-  if (c->m > 0) {
-    if (algo == PCD_NN_BRUTEFORCE) {
-      ScopedKernelTimer t("nn_bruteforce", s);
-      // enough chunks to fill the chip even for few queries
-      const unsigned qblocks = div_up(Q, 256);
-      unsigned chunks = std::max(1u, std::min<unsigned>(div_up(c->n, 4096), 2048u / std::max(1u, qblocks)));
-      chunks = std::min(chunks, 65535u);
-      const uint64_t chunk = ((c->n + chunks - 1) / chunks + 1023) / 1024 * 1024;
-      chunks = div_up(c->n, chunk);
-      hipLaunchKernelGGL(k_nn_bruteforce, dim3(qblocks, chunks), dim3(256), 0, s, c->pts4.p, c->n, c->index_base,
-                         c->index_stride, c->row_index.p, sc->qf4.p, Q, chunk, d_keys);
-    } else if (small) {
-      // (refining another shard's keys: the keys come in, so the prepare / finalize kernels stay)
-      PCD_TRY(counters_ready(sc, s));
-      NnCounters* ctr = sc->counters.p + sc->ctr_cur;
-      PCD_HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(NnCounters), s));
+  NnCounters* ctr;
+  switch (path) {
+    case NnPath::kEmptyCloud:   // nothing to search: the prepare kernel's keys are all there is
+    case NnPath::kBruteForce:
+      PCD_TRY(sc->qf4.reserve(Q));
+      launch_prepare(call, Q, sc->qf4.p, d_keys, s);
+      if (path == NnPath::kBruteForce) launch_bruteforce(c, sc->qf4.p, Q, d_keys, s);
+      launch_finalize(Q, d_keys, s);   // raw keys left behind: the brute-force kernel's atomicMin, an empty cloud
+      break;
+    case NnPath::kOneLaunch: {
+      PCD_TRY(fb_seed_table(c, sc, s));
+      PCD_TRY(take_counters(sc, CtrUse::kClearForStats, collect_stats, s, &ctr));
       ScopedKernelTimer t("nn_fallback", s);
-      const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(Q, 4), g_fb_max_blocks);
-      hipLaunchKernelGGL(k_nn_fallback<0>, dim3(blocks), dim3(256), 0, s, c->grid, c->pyr, c->sorted.p, c->cell_start.p,
-                         c->blk_aabb.p, sc->fb_seed.p, sc->qf4.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)Q,
-                         d_keys, ctr, collect_stats, FbFused{nullptr, nullptr, 0, 0.0});
-    } else if (grid) {
-      PCD_TRY(run_grid<8>(c, sc, Q, d_keys, s, prep, pa));
-    } else {
-      set_error("unknown nn algo %d", algo);
-      return PCD_ERR_INVALID;
+      const FbQueries src{nullptr, FbFused{call.pa.q, call.pa.max_range, call.pa.mr_count, call.pa.fixed_range}};
+      if (call.prep == kPrepBounded) launch_fallback<2>(c, sc->fb_seed.p, src, Q, d_keys, ctr, collect_stats, s);
+      else launch_fallback<1>(c, sc->fb_seed.p, src, Q, d_keys, ctr, collect_stats, s);
+      break;
     }
-  }
-  if (c->m == 0 || algo == PCD_NN_BRUTEFORCE) {   // raw keys left behind: the brute-force kernel's atomicMin, an empty cloud
-    ScopedKernelTimer t("nn_finalize", s);
-    hipLaunchKernelGGL(k_finalize_keys, dim3(div_up(Q, 256)), dim3(256), 0, s, d_keys, Q);
+    case NnPath::kPrepareWalk: {
+      PCD_TRY(fb_seed_table(c, sc, s));
+      PCD_TRY(sc->qf4.reserve(Q));
+      launch_prepare(call, Q, sc->qf4.p, d_keys, s);
+      PCD_TRY(take_counters(sc, CtrUse::kClear, collect_stats, s, &ctr));
+      ScopedKernelTimer t("nn_fallback", s);
+      launch_fallback<0>(c, sc->fb_seed.p, {sc->qf4.p}, Q, d_keys, ctr, collect_stats, s);
+      break;
+    }
+    case NnPath::kGrid:
+      PCD_TRY(fb_seed_table(c, sc, s));
+      PCD_TRY(sc->qf4.reserve(Q));
+      PCD_TRY(run_grid(c, sc, Q, d_keys, s, call));
+      break;
   }
   PCD_HIP_TRY(hipGetLastError());
   return PCD_OK;
+}
+
+// the entry points' description of a call: the flavour and what it reads
+static NnCall make_call(int prep, const pcd_cloud* c, const double* d_q, const uint8_t* d_skip = nullptr,
+                        const double* d_max_range = nullptr, uint64_t mr_count = 0, double fixed_range = 0.0) {
+  const BoxF box{c->bb_lo[0], c->bb_lo[1], c->bb_lo[2], c->bb_hi[0], c->bb_hi[1], c->bb_hi[2]};
+  return {prep, {d_q, d_skip, box, d_max_range, mr_count, fixed_range}};
 }
 
 pcd_status nn_query_device_internal(pcd_cloud* c, const double* d_q, uint64_t Q, int algo, uint64_t* d_keys,
                                     hipStream_t s) {
-  return nn_device(c, d_q, Q, algo, d_keys, s);
+  return nn_device(c, make_call(kPrepPlain, c, d_q), Q, algo, d_keys, s);
 }
 // bounded by the association gate: d_max_range (1 or Q entries) or, when NULL, fixed_range
 pcd_status nn_query_bounded_internal(pcd_cloud* c, const double* d_q, uint64_t Q, const double* d_max_range,
                                      uint64_t mr_count, double fixed_range, uint64_t* d_keys, hipStream_t s) {
-  NnBound b;
-  b.d_max_range = d_max_range; b.count = mr_count; b.fixed = fixed_range;
-  return nn_device(c, d_q, Q, PCD_NN_AUTO, d_keys, s, false, nullptr, &b);
+  return nn_device(c, make_call(kPrepBounded, c, d_q, nullptr, d_max_range, mr_count, fixed_range), Q, PCD_NN_AUTO, d_keys, s);
 }
 
 }  // namespace pcd
@@ -1334,7 +1331,7 @@ pcd_status pcd_nn_query_device(pcd_cloud* c, const double* d_q_xyz, uint64_t Q, 
   PCD_REQUIRE(Q == 0 || (d_q_xyz && d_keys), "null pointer");
   PCD_REFUSE_CAPTURE(stream);
   PCD_HIP_TRY(hipSetDevice(c->device));
-  return nn_device(c, d_q_xyz, Q, algo, d_keys, (hipStream_t)stream);
+  return nn_device(c, make_call(kPrepPlain, c, d_q_xyz), Q, algo, d_keys, (hipStream_t)stream);
 }
 
 pcd_status pcd_nn_refine_device(pcd_cloud* c, const double* d_q_xyz, uint64_t Q, const uint8_t* d_skip,
@@ -1343,7 +1340,7 @@ pcd_status pcd_nn_refine_device(pcd_cloud* c, const double* d_q_xyz, uint64_t Q,
   PCD_REQUIRE(Q == 0 || (d_q_xyz && d_keys), "null pointer");
   PCD_REFUSE_CAPTURE(stream);
   PCD_HIP_TRY(hipSetDevice(c->device));
-  return nn_device(c, d_q_xyz, Q, PCD_NN_AUTO, d_keys, (hipStream_t)stream, /*refine=*/true, d_skip);
+  return nn_device(c, make_call(kPrepRefine, c, d_q_xyz, d_skip), Q, PCD_NN_AUTO, d_keys, (hipStream_t)stream);
 }
 
 pcd_status pcd_nn_query_algo(pcd_cloud* c, const double* q_xyz, uint64_t Q, int algo, uint32_t* idx, float* sqdist,
@@ -1360,7 +1357,7 @@ pcd_status pcd_nn_query_algo(pcd_cloud* c, const double* q_xyz, uint64_t Q, int 
   PCD_TRY(sc->d_sq.reserve(Q));
   PCD_TRY(sc->d_found.reserve(Q));
   PCD_HIP_TRY(hipMemcpyAsync(sc->d_q.p, q_xyz, 3 * Q * sizeof(double), hipMemcpyHostToDevice, s));
-  PCD_TRY(nn_device(c, sc->d_q.p, Q, algo, sc->keys.p, s));
+  PCD_TRY(nn_device(c, make_call(kPrepPlain, c, sc->d_q.p), Q, algo, sc->keys.p, s));
   hipLaunchKernelGGL(k_unpack_keys, dim3(div_up(Q, 256)), dim3(256), 0, s, sc->keys.p, Q, sc->d_idx.p, sc->d_sq.p,
                      sc->d_found.p);
   PCD_HIP_TRY(hipMemcpyAsync(idx, sc->d_idx.p, Q * sizeof(uint32_t), hipMemcpyDeviceToHost, s));

@@ -17,10 +17,11 @@ struct NnCounters {
 struct QueryScratch {
   DevBuf<float4> qf4;          // (float)query, w = 1 valid / 0 not finite
   DevBuf<uint64_t> keys;       // host-API result keys
-  DevBuf<uint32_t> bk_keys, bk_vals;   // (brick id, query id) pairs, unsorted | sorted halves
-  DevBuf<uint32_t> bk_item;            // work items per tile of 1024 sorted positions
-  // counting-sort bookkeeping (nn.hip): slot of every brick with a non-empty halo region (kSlotNone otherwise), built
-  // once bk_nslots is the cloud's number of bricks; per batch the slots' query counters, in-tile prefixes and tile totals
+  DevBuf<uint32_t> bk_keys, bk_vals;   // radix-sort bookkeeping: (brick id, query id) pairs, unsorted | sorted halves
+  DevBuf<uint32_t> bk_item;            // radix-sort bookkeeping: work items per tile of 1024 sorted positions
+  // counting-sort bookkeeping (nn.hip): bk_slot = one bit per brick whose halo region holds a cloud point, built once
+  // (valid while bk_nslots is the cloud's number of bricks); per batch bk_keys = every query's sort key (brick id, or
+  // fallback / skip), bk_vals = the Q {fine key, query id} pairs of the scatter
   DevBuf<uint32_t> bk_slot, bk_chist;   // bk_chist: coarse bucket totals | bucket starts | items per bucket
   DevBuf<uint32_t> bk_hmat;             // coarse histogram per range of queries: [ranges <= 256][buckets <= 4096], <= 4 MB
   uint32_t bk_nslots = 0;
@@ -30,7 +31,7 @@ struct QueryScratch {
   DevBuf<uint32_t> fb_list, fb_dense;   // fallback list as the brick kernel fills it (chunked) / squeezed
   DevBuf<float4> fb_seed;      // k_nn_fallback's seed table, built on first use (nn.hip fb_seed_table)
   bool fb_seed_ok = false;
-  DevBuf<NnCounters> counters;   // two blocks, used alternately by the grid-path calls (nn.hip counters_ready)
+  DevBuf<NnCounters> counters;   // two blocks, used alternately by the grid-path calls (nn.hip counters_for)
   int ctr_cur = 0;               // the block of the last call
   bool ctr_next_clean = false;   // the other block is zero (or will be when the stream gets there)
   DevBuf<char> tmp;
@@ -75,5 +76,11 @@ inline QueryScratch* scratch_of(pcd_cloud* c) {
   if (!c->scratch) c->scratch = new QueryScratch();
   return c->scratch;
 }
+
+// nn.hip: the search of pcd_nn_query_device; the same bounded by the gate (d_max_range: 1 or Q entries, NULL: fixed_range)
+pcd_status nn_query_device_internal(pcd_cloud* c, const double* d_q, uint64_t Q, int algo, uint64_t* d_keys,
+                                    hipStream_t s);
+pcd_status nn_query_bounded_internal(pcd_cloud* c, const double* d_q, uint64_t Q, const double* d_max_range,
+                                     uint64_t mr_count, double fixed_range, uint64_t* d_keys, hipStream_t s);
 
 }  // namespace pcd

@@ -1,5 +1,5 @@
 """Plain numpy restatement of the cloud build (csrc/cloud.hip, csrc/grid.h) and of the shard split and refine
-predicate (csrc/shards.hip, k_prepare_refine in csrc/nn.hip).  No device code: tests/test_cloud_ref_cpu.py pins these
+predicate (csrc/shards.hip, k_prepare<kPrepRefine> in csrc/nn.hip).  No device code: tests/test_cloud_ref_cpu.py pins these
 functions on hand-computed cases, the GPU tests compare the library with them bit for bit.
 
 Every function takes the cloud in the HANDLE's frame: rows already transformed and NaN-filtered, float32."""
@@ -150,7 +150,7 @@ def point_distance(q, p):
 
 
 def refine_active(q, box_lo, box_hi, incoming_sqdist_bits):
-    """k_prepare_refine: a finite query stays active in a shard iff the float distance to the shard's box does not
+    """k_prepare<kPrepRefine>: a finite query stays active in a shard iff the float distance to the shard's box does not
     exceed the distance it comes in with (equality kept: a lower index at the same distance may live there)"""
     qf = _qf(q)
     inc = np.ascontiguousarray(incoming_sqdist_bits, np.uint32).view(np.float32)
