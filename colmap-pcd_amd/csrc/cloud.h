@@ -101,4 +101,10 @@ namespace pcd {
 // a cloud of global_n rows in total
 pcd_status cloud_create_indexed(const float* xyz, const float* nrm, uint64_t n, const pcd_cloud_options* opts,
                                 const uint32_t* row_index, uint64_t global_n, pcd_cloud** out);
+// A handle whose rows are produced on the device (voxel.hip): cloud_alloc_rows gives a handle on `device` with pts4 /
+// pn8 allocated for n rows (index_base 0, stride 1) and no index; the caller writes every row of both arrays on stream
+// s, then cloud_build_index builds the grid, the sorted records and the pyramid exactly as pcd_cloud_create does after
+// its row transform (it synchronises s).  On failure the caller destroys the handle.
+pcd_status cloud_alloc_rows(int device, uint64_t n, pcd_cloud** out);
+pcd_status cloud_build_index(pcd_cloud* c, float cell_size, hipStream_t s);
 }

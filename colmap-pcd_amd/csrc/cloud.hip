@@ -508,6 +508,29 @@ static pcd_status build_grid(pcd_cloud* c, float user_h, hipStream_t s) {
   return PCD_OK;
 }
 
+pcd_status cloud_alloc_rows(int device, uint64_t n, pcd_cloud** out) {
+  *out = nullptr;
+  PCD_REQUIRE(n < 0xFFFFFFF0ull, "more than 2^32 rows");
+  pcd_cloud* c = new pcd_cloud();
+  c->device = device;
+  c->n = n;
+  pcd_status st = c->pts4.reserve(std::max<uint64_t>(n, 1));
+  if (st == PCD_OK) st = c->pn8.reserve(2 * std::max<uint64_t>(n, 1));
+  if (st != PCD_OK) {
+    pcd_cloud_destroy(c);
+    return st;
+  }
+  *out = c;
+  return PCD_OK;
+}
+
+pcd_status cloud_build_index(pcd_cloud* c, float cell_size, hipStream_t s) {
+  auto t0 = std::chrono::steady_clock::now();
+  PCD_TRY(build_grid(c, cell_size, s));
+  c->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return PCD_OK;
+}
+
 }  // namespace pcd
 
 using namespace pcd;

@@ -191,6 +191,18 @@ class NormalsInfo(C.Structure):
                 ("mean_neighbors", C.c_double), ("ms", C.c_double)]
 
 
+class VoxelOptions(C.Structure):
+    """pcd_voxel_options (pcdhip.h)."""
+    _fields_ = [("leaf", C.c_float * 3), ("min_points", C.c_int32), ("cell_size", C.c_float),
+                ("reserved", C.c_int32 * 8)]
+
+
+class VoxelInfo(C.Structure):
+    _fields_ = [("num_input", C.c_uint64), ("num_voxels", C.c_uint64), ("num_output", C.c_uint64),
+                ("num_dropped_rows", C.c_uint64), ("min_b", C.c_int32 * 3), ("dims", C.c_int32 * 3),
+                ("max_points_per_voxel", C.c_uint32), ("ms", C.c_double), ("build_ms", C.c_double)]
+
+
 class NNStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("queries", "brick_groups", "staged_points", "fallback_queries",
                                            "fallback_points", "pair_evals")]
@@ -224,6 +236,7 @@ ABI_SYMBOLS = [
     "pcd_ba_solve_opts_default", "pcd_ba_solve",
     "pcd_ba_schur_solve_cholesky_device", "pcd_ba_schur_solve_cholesky",
     "pcd_normals_options_default", "pcd_cloud_estimate_normals_device", "pcd_cloud_estimate_normals",
+    "pcd_voxel_options_default", "pcd_cloud_voxel_downsample", "pcd_cloud_voxel_downsample_device",
 ]
 
 
@@ -290,6 +303,12 @@ def lib():
                                                     C.c_void_p]
     L.pcd_cloud_estimate_normals.argtypes = [C.c_void_p, C.POINTER(NormalsOptions), C.c_void_p, C.c_void_p,
                                              C.POINTER(NormalsInfo)]
+    L.pcd_voxel_options_default.argtypes = [C.POINTER(VoxelOptions)]
+    L.pcd_voxel_options_default.restype = None
+    L.pcd_cloud_voxel_downsample.argtypes = [C.c_void_p, C.POINTER(VoxelOptions), C.c_void_p, C.POINTER(C.c_void_p),
+                                             C.POINTER(VoxelInfo)]
+    L.pcd_cloud_voxel_downsample_device.argtypes = [C.c_void_p, C.POINTER(VoxelOptions), C.c_void_p, C.c_void_p,
+                                                    C.POINTER(C.c_void_p), C.POINTER(VoxelInfo)]
     if hasattr(L, "pcd_ba_create"):
         L.pcd_ba_create.argtypes = [C.POINTER(BADesc), C.POINTER(C.c_void_p)]
         L.pcd_ba_destroy.argtypes = [C.c_void_p]
@@ -361,6 +380,22 @@ def normals_options(radius=0.15, min_neighbors=3, orient=None, viewpoint=(0, 0, 
     return o
 
 
+def voxel_options(leaf=0.05, min_points=0, cell_size=0.0):
+    """pcd_voxel_options; leaf: one edge for all three axes, or three"""
+    o = VoxelOptions()
+    lib().pcd_voxel_options_default(C.byref(o))
+    l3 = np.broadcast_to(np.asarray(leaf, np.float32), (3,))
+    o.leaf[:] = [float(v) for v in l3]
+    o.min_points, o.cell_size = int(min_points), float(cell_size)
+    return o
+
+
+def _voxel_info(i):
+    d = {k: getattr(i, k) for k, _ in VoxelInfo._fields_}
+    d["min_b"], d["dims"] = list(i.min_b), list(i.dims)
+    return d
+
+
 class Cloud:
     """Device-resident LiDAR cloud index (reference: lidar::PointCloudProcess + lidar::Kdtree)."""
 
@@ -385,6 +420,14 @@ class Cloud:
         _check(lib().pcd_cloud_create(_vp(xyz), _vp(nrm), n, C.byref(o), C.byref(h)))
         self._h = h
         self.device = device
+
+    @classmethod
+    def _from_handle(cls, handle, device=0):
+        """a Cloud that OWNS an existing pcd_cloud* (what pcd_cloud_voxel_downsample returns)"""
+        c = cls.__new__(cls)
+        c._h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        c.device = device
+        return c
 
     def close(self):
         if self._h:
@@ -432,6 +475,26 @@ class Cloud:
         o = normals_options(radius, min_neighbors, orient, viewpoint, only_missing)
         _check(lib().pcd_cloud_estimate_normals_device(self._h, C.byref(o), _ptr(d_count), _ptr(d_curvature),
                                                        C.c_void_p(stream)))
+
+    def voxel_downsample(self, leaf, min_points=0, cell_size=0.0, want_map=False):
+        """Voxel-grid downsampling into a NEW handle (pcd_cloud_voxel_downsample): returns (Cloud, info dict), with
+        want_map also row_voxel (uint32 per row of this cloud: its output row, 0xFFFFFFFF for none).  leaf: one edge or
+        three; cell_size is the new handle's.  This cloud is not modified."""
+        o = voxel_options(leaf, min_points, cell_size)
+        row_voxel = np.empty(len(self), np.uint32) if want_map else None
+        h, info = C.c_void_p(), VoxelInfo()
+        _check(lib().pcd_cloud_voxel_downsample(self._h, C.byref(o), _vp(row_voxel), C.byref(h), C.byref(info)))
+        out = Cloud._from_handle(h, self.device)
+        return (out, _voxel_info(info), row_voxel) if want_map else (out, _voxel_info(info))
+
+    def voxel_downsample_device(self, d_row_voxel, leaf, min_points=0, cell_size=0.0, stream=0):
+        """the same with the map written to device memory (a torch int32 tensor of len(self) or a raw pointer; may be
+        None), on `stream` -- which is synchronised: the row count sizes the new handle.  Returns (Cloud, info)."""
+        o = voxel_options(leaf, min_points, cell_size)
+        h, info = C.c_void_p(), VoxelInfo()
+        _check(lib().pcd_cloud_voxel_downsample_device(self._h, C.byref(o), _ptr(d_row_voxel), C.c_void_p(stream),
+                                                       C.byref(h), C.byref(info)))
+        return Cloud._from_handle(h, self.device), _voxel_info(info)
 
     def nn(self, q, algo=NN_AUTO):
         """Kdtree::GetClosestPoint for a batch: returns (idx uint32, sqdist float32, found uint8)."""

@@ -85,6 +85,48 @@ class PointCloudProcess {
     nrm_mode_ = mode;
   }
   const pcd_normals_info& normals_info() const { return nrm_info_; }   // of the last estimation (zeros: none ran)
+
+  // Downsampling on the device instead of the manual's other CloudCompare step (README.md "Preparing point cloud",
+  // "Downsample the point cloud to 3-5cm resolution"): a voxel grid of edge `leaf` over the loaded cloud
+  // (pcd_cloud_voxel_downsample; voxels with fewer than min_points rows are dropped).  Off (leaf <= 0, the default): the
+  // cloud is indexed as it was read, as the reference does.  InitializeFromRawCloud applies it after the axis swap and
+  // BEFORE the normal estimation, the manual's order.  Call before Initialize.
+  void SetDownsample(float leaf, int min_points) {
+    ds_leaf_ = leaf;
+    ds_min_points_ = min_points;
+  }
+  const pcd_voxel_info& downsample_info() const { return ds_info_; }   // of the last downsampling (zeros: none ran)
+
+  // lidar/ply.cc:59-84 / ply.h:28-29, the viewer's display cloud (ui/model_viewer_widget.cc:774-791): a voxel grid of
+  // edge filter_size over the cloud.  The reference reads the PLY again and transforms it; this downsamples the handle
+  // Initialize built (cloud_, already in the visual frame -- with SetDownsample in force, the downsampled one), so
+  // it needs Initialize first and returns false without it.  GetDownsizedMap: the rows as lidarpt::Point (AoS 32 B:
+  // x y z pad nx ny nz pad) on the host, in ascending voxel key as pcl::VoxelGrid emits them.
+  bool LoadDownsizedMap(double filter_size = 1.0) {
+    downsized_map_.clear();
+    if (!cloud_) return false;
+    pcd_voxel_options vo;
+    pcd_voxel_options_default(&vo);
+    vo.leaf[0] = vo.leaf[1] = vo.leaf[2] = (float)filter_size;
+    pcd_cloud* small = nullptr;
+    if (pcd_cloud_voxel_downsample(cloud_, &vo, nullptr, &small, nullptr) != PCD_OK) {
+      std::fprintf(stderr, "downsized map failed: %s\n", pcd_last_error());
+      return false;
+    }
+    const uint64_t n = pcd_cloud_size(small);
+    std::vector<float> xyz(3 * n), nrm(3 * n);
+    const bool ok = pcd_cloud_download(small, xyz.data(), nrm.data()) == PCD_OK;
+    pcd_cloud_destroy(small);
+    if (!ok) return false;
+    downsized_map_.assign(8 * n, 0.f);
+    for (uint64_t i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) {
+        downsized_map_[8 * i + k] = xyz[3 * i + k];
+        downsized_map_[8 * i + 4 + k] = nrm[3 * i + k];
+      }
+    return true;
+  }
+  const std::vector<float>& GetDownsizedMap() const { return downsized_map_; }
   // lidar/ply.cc:9-31 with its own signature: also creates pcd_proj_ and builds its submaps (ply.cc:10, 27)
   bool Initialize(const PcdProjectionOptions& pp_options) {
     if (!Initialize()) return false;
@@ -112,7 +154,26 @@ class PointCloudProcess {
     cloud_ = nullptr;
     host_nrm_.clear();   // cached normals belong to the old cloud
     nrm_info_ = pcd_normals_info{};
+    ds_info_ = pcd_voxel_info{};
     if (pcd_cloud_create(xyz, nrm, n, &o, &cloud_) != PCD_OK) return false;
+    if (ds_leaf_ > 0.f) {
+      pcd_voxel_options vo;
+      pcd_voxel_options_default(&vo);
+      vo.leaf[0] = vo.leaf[1] = vo.leaf[2] = ds_leaf_;
+      vo.min_points = ds_min_points_;
+      pcd_cloud* small = nullptr;
+      if (pcd_cloud_voxel_downsample(cloud_, &vo, nullptr, &small, &ds_info_) != PCD_OK) {
+        std::fprintf(stderr, "downsampling failed: %s\n", pcd_last_error());
+        return false;
+      }
+      pcd_cloud_destroy(cloud_);   // the raw cloud: every later stage works on the downsampled handle
+      cloud_ = small;
+      std::fprintf(stderr, "downsampled at leaf %g: %llu rows in %llu voxels -> %llu rows (%llu rows in voxels below %d "
+                   "dropped), at most %u rows per voxel, %.2f ms + %.2f ms index build\n", (double)ds_leaf_,
+                   (unsigned long long)ds_info_.num_input, (unsigned long long)ds_info_.num_voxels,
+                   (unsigned long long)ds_info_.num_output, (unsigned long long)ds_info_.num_dropped_rows,
+                   ds_min_points_, ds_info_.max_points_per_voxel, ds_info_.ms, ds_info_.build_ms);
+    }
     if (nrm_mode_ == NormalEstimation::Always || (nrm_mode_ == NormalEstimation::WhenMissing && !has_normals)) {
       pcd_normals_options no;
       pcd_normals_options_default(&no);
@@ -180,6 +241,10 @@ class PointCloudProcess {
   int nrm_min_neighbors_ = 3;
   NormalEstimation nrm_mode_ = NormalEstimation::Off;
   pcd_normals_info nrm_info_{};
+  float ds_leaf_ = 0.f;   // <= 0: no downsampling
+  int ds_min_points_ = 0;
+  pcd_voxel_info ds_info_{};
+  std::vector<float> downsized_map_;
 };
 
 }  // namespace lidar

@@ -175,6 +175,73 @@ pcd_status pcd_cloud_estimate_normals(pcd_cloud* c, const pcd_normals_options* o
                                       double* curvature, pcd_normals_info* info);
 
 /* ------------------------------------------------------------------------
+ * Voxel-grid downsampling      replaces the other half of the manual's preparation step (README.md "Preparing point
+ *   cloud": "Downsample the point cloud to 3-5cm resolution") and PointCloudProcess::LoadDownsizedMap
+ *   (lidar/ply.cc:59-84, pcl::VoxelGrid at a 1 m leaf for the viewer, ui/model_viewer_widget.cc:774-791).
+ * The model is pcl::VoxelGrid with downsample_all_data = true.  PCL sums in float in the order of an unstable
+ * std::sort, so bit parity with it does not exist; the contract is this definition.
+ * Source: ONE handle holding the whole cloud -- a shard of pcd_cloud_create_sharded or a handle with
+ * index_stride != 1 / index_base != 0 is refused with PCD_ERR_UNSUPPORTED, its voxels cross handle borders.  The source
+ * handle is not modified.  For every finite row p and leaf l[3] (floats, finite, > 0):
+ *   inv_a       1.0f / l_a, in float;
+ *   voxel       v_a = (int32) floorf(p_a * inv_a): ONE float multiply, not fused, then floor -- a point at -0.01 with
+ *               leaf 0.05 lies in voxel -1;
+ *   bounds      min_b_a = floorf(bbox_lo_a * inv_a), max_b_a = floorf(bbox_hi_a * inv_a) from the handle's tight bounds
+ *               (multiply and floor are monotone: these are the extreme v_a); d_a = max_b_a - min_b_a + 1;
+ *   key         (v_0 - min_b_0) + d_0 ((v_1 - min_b_1) + d_1 (v_2 - min_b_2)) as uint64.  Keys above 2^32 are ordinary
+ *               (100 m at a 1 cm leaf is 10^12 voxels; PCL gives up at 2^31);
+ *   refused     with PCD_ERR_INVALID and no handle created: |bbox * inv| >= 2^31 on any axis; d_0 d_1 d_2 >= 2^63;
+ *   Inf rows    (a non-finite coordinate) belong to no voxel.
+ * Output rows are the occupied voxels in ascending key (PCL's output order, x fastest).  For voxel V with rows R(V) in
+ * ascending source row, k = |R(V)|:
+ *   position    float((sum double(p_j)) / k);
+ *   normal      s = sum double(n_j); |s| (fp64 norm) not finite or < 1e-12: (0,0,0); else float(s / |s|)  (PCL's
+ *               normal accumulator: sum, then normalise).  Rows with a zero normal add nothing; a cloud without normals
+ *               stays without them;
+ *   sums        fp64, no atomics, in an order that is a function of k and of the rows' order alone -- never of the launch
+ *               geometry or of timing; a repeated call is bitwise identical.  The order: the segment is cut into pieces
+ *               of 512 rows from its start; in a piece, lane L of 64 adds rows L, L + 64, ... in sequence; the 64 lane
+ *               sums (absent rows are +0.0) are added by a butterfly over the lane offsets 8, 16, 32, 1, 2, 4; the pieces
+ *               are added in sequence; +0.0 is added to the total (a sum of zeros is +0.0);
+ *   min_points  (>= 0) a voxel with k < min_points is dropped [num_dropped_rows counts its rows]; the survivors keep
+ *               their key order.
+ * row_voxel[i]: the output row of source row i, 0xFFFFFFFF for Inf rows and for rows of dropped voxels -- the map a
+ * caller needs to carry colour or intensity along.
+ * *out: an ordinary handle on the source's device (index_base 0, stride 1), rows written device to device, index built
+ * as pcd_cloud_create builds it; destroy it with pcd_cloud_destroy.  On any failure *out is NULL.
+ * BOTH forms synchronise (the _device form synchronises `stream`): the row count sizes the new handle.  The guards
+ * of every _device call apply (a capturing stream: PCD_ERR_UNSUPPORTED before anything is allocated).  An empty source,
+ * or one with only Inf rows, returns PCD_OK with an empty handle and zero counts.
+ * --------------------------------------------------------------------- */
+typedef struct {
+  float leaf[3];        /* metres, finite and > 0                                          */
+  int32_t min_points;   /* >= 0                                                            */
+  float cell_size;      /* of the NEW handle, 0 = auto                                     */
+  int32_t reserved[8];
+} pcd_voxel_options;
+
+typedef struct {
+  uint64_t num_input;        /* finite rows                                                */
+  uint64_t num_voxels;       /* occupied, before min_points                                */
+  uint64_t num_output;
+  uint64_t num_dropped_rows;
+  int32_t min_b[3], dims[3]; /* dims saturates at INT32_MAX (d_a can reach 2^32)           */
+  uint32_t max_points_per_voxel;
+  double ms;                 /* device time without the new handle's index build          */
+  double build_ms;
+} pcd_voxel_info;
+
+void pcd_voxel_options_default(pcd_voxel_options* o);   /* 0.05 x3, 0, 0 */
+
+pcd_status pcd_cloud_voxel_downsample(pcd_cloud* src, const pcd_voxel_options* opts /*NULL = defaults*/,
+                                      uint32_t* row_voxel /*[size(src)] host, may be NULL*/,
+                                      pcd_cloud** out, pcd_voxel_info* info /*may be NULL*/);
+
+pcd_status pcd_cloud_voxel_downsample_device(pcd_cloud* src, const pcd_voxel_options* opts,
+                                             uint32_t* d_row_voxel /*device, may be NULL*/,
+                                             void* stream, pcd_cloud** out, pcd_voxel_info* info);
+
+/* ------------------------------------------------------------------------
  * Nearest neighbour                          replaces lidar/kdtree.cc:10-21
  *   Kdtree::GetClosestPoint  (k = 1 pcl::KdTreeFLANN::nearestKSearch,
  *   FLANN L2_Simple<float> on x,y,z; exact)
