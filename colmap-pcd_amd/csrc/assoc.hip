@@ -9,11 +9,8 @@
 //   sfm/incremental_mapper.cc:1444-1463  same gate, dist/angle not stored by the reference      (mode 1)
 //   controllers/bundle_adjustment.cc:156-176 gate dist2plane > 1 || dist2point > 2              (mode 2)
 // Compiled with -ffp-contract=off so the operation order below is what runs.
-#include <cstring>  // rocprim's texture_cache_iterator.hpp needs memset declared first
-
-#include <rocprim/rocprim.hpp>
-
 #include "cloud.h"
+#include "prim.h"
 #include "scratch.h"
 
 namespace pcd {
@@ -349,10 +346,7 @@ pcd_status pcd_associate_staged(pcd_cloud* c, uint64_t Q, uint64_t max_range_cou
       ScopedKernelTimer t("associate_compact", s);
       const auto flags = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u),
                                                           HitFlag{a.a_type.p + q0});
-      size_t tb = 0;
-      PCD_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, flags, a.hit_pos.p + q0, 0u, (size_t)qn, rocprim::plus<uint32_t>(), s));
-      PCD_TRY(a.tmp.reserve(tb));
-      PCD_HIP_TRY(rocprim::exclusive_scan(a.tmp.p, tb, flags, a.hit_pos.p + q0, 0u, (size_t)qn, rocprim::plus<uint32_t>(), s));
+      PCD_TRY(exclusive_sum(a.tmp, flags, a.hit_pos.p + q0, 0u, (size_t)qn, s));
       // chunk k's records are packed at the start of its own region of d_hits (first record = slot q0)
       hipLaunchKernelGGL(k_pack_hits, dim3(div_up(qn, 256)), dim3(256), 0, s, a.a_type.p + q0, a.hit_pos.p + q0, (uint32_t)qn,
                          a.a_xyz.p + 3 * q0, a.a_abcd.p + 4 * q0, a.a_dist.p + q0, a.a_angle.p + q0, a.d_hits.p + q0,

@@ -27,6 +27,7 @@
 // MODEL = -1 switches per observation.
 #include <algorithm>
 #include <cmath>
+#include <memory>
 
 #include "ba_cam_jac.h"
 #include "ba_handle.h"
@@ -1314,8 +1315,9 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
   b->shared_cam = d->image_camera[0];
   for (int i = 1; i < d->num_images; ++i)
     if (d->image_camera[i] != b->shared_cam) b->shared_cam = -1;
-  auto fail = [&](pcd_status st) { pcd_ba_destroy(b); return st; };
-#define UP(buf, src, n) do { pcd_status _st = upload(b->buf, src, (size_t)(n)); if (_st != PCD_OK) return fail(_st); } while (0)
+  struct Destroy { void operator()(pcd_ba* p) const { pcd_ba_destroy(p); } };
+  std::unique_ptr<pcd_ba, Destroy> owner(b);   // destroys the handle on every failing return below
+#define UP(buf, src, n) PCD_TRY(upload(b->buf, src, (size_t)(n)))
   UP(cam_model, d->cam_model, b->C); UP(cam_off, d->cam_param_offset, b->C); UP(cam_params, d->cam_params, d->cam_params_len);
   UP(poses, d->poses, 7 * (size_t)b->I); UP(image_cam, d->image_camera, b->I);
   UP(points, d->points, 3 * (size_t)b->P);
@@ -1358,16 +1360,15 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
     UP(pt_obs_start, st.data(), st.size()); UP(pt_obs_list, li.data(), li.size());   // kept: pcd_ba_filter_tracks
     // the ELL fill borrows the buffers of the lidar CSR uploaded right after
     UP(pt_lidar_start, st.data(), st.size()); UP(pt_lidar_list, li.data(), li.size());
-    pcd_status sa = b->sell_img.reserve(std::max<size_t>(nslots, 1));
-    if (sa == PCD_OK) sa = b->sell_xy.reserve(std::max<size_t>(2 * nslots, 2));
-    if (sa != PCD_OK) return fail(sa);
+    PCD_TRY(b->sell_img.reserve(std::max<size_t>(nslots, 1)));
+    PCD_TRY(b->sell_xy.reserve(std::max<size_t>(2 * nslots, 2)));
     if (nslots)
       hipLaunchKernelGGL(k_ba_fill_sell, dim3(div_up((size_t)nslices * 64, 256)), dim3(256), 0, nullptr, b->pt_order.p,
                          b->slice_start.p, b->pt_lidar_start.p, b->pt_lidar_list.p, b->obs_image.p, b->obs_xy.p, nslices,
                          b->sell_img.p, b->sell_xy.p);
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
       set_error("pcd_ba_create: filling the per-track layout failed");
-      return fail(PCD_ERR_HIP);
+      return PCD_ERR_HIP;
     }
   }
   build_csr(d->lidar_point, b->L, b->P, st, li);
@@ -1411,15 +1412,14 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
       UP(cam_img_list, cli.data(), cli.size());
     }
     UP(img_obs, li.data(), li.size());
-    pcd_status sa = b->img_pt.reserve(std::max<size_t>(b->O, 1));
-    if (sa == PCD_OK) sa = b->img_xy.reserve(std::max<size_t>(2 * b->O, 2));
-    if (sa != PCD_OK) return fail(sa);
+    PCD_TRY(b->img_pt.reserve(std::max<size_t>(b->O, 1)));
+    PCD_TRY(b->img_xy.reserve(std::max<size_t>(2 * b->O, 2)));
     if (b->O)
       hipLaunchKernelGGL(k_ba_fill_image_major, dim3(div_up(b->O, 256)), dim3(256), 0, nullptr, b->img_obs.p,
                          b->obs_point.p, b->obs_xy.p, b->O, b->img_pt.p, b->img_xy.p);
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
       set_error("pcd_ba_create: filling the image-major layout failed");
-      return fail(PCD_ERR_HIP);
+      return PCD_ERR_HIP;
     }
   }
 #undef UP
@@ -1433,16 +1433,12 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
         vobs.push_back((uint32_t)o);
       }
     b->n_pose_rows = vobs.size();
-    if (b->n_pose_rows != b->O) {
-      pcd_status sv = upload(b->vobs, vobs.data(), vobs.size());
-      if (sv != PCD_OK) return fail(sv);
-    }
+    if (b->n_pose_rows != b->O) PCD_TRY(upload(b->vobs, vobs.data(), vobs.size()));
   }
   // one partial per workgroup of whichever of the two cost-producing kernels has the larger grid (cost_blocks)
-  pcd_status s1 = b->cost_partial.reserve((size_t)std::max(cost_blocks(b, true), cost_blocks(b, false)) + 1);
-  if (s1 != PCD_OK) return fail(s1);
-  if ((s1 = b->cost.reserve(1)) != PCD_OK) return fail(s1);
-  *out = b;
+  PCD_TRY(b->cost_partial.reserve((size_t)std::max(cost_blocks(b, true), cost_blocks(b, false)) + 1));
+  PCD_TRY(b->cost.reserve(1));
+  *out = owner.release();
   return PCD_OK;
   });
 }

@@ -1311,10 +1311,8 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
     const unsigned ngp = std::max(1u, std::min(1024u, div_up((uint64_t)ns + P, 256)));
     PCD_TRY(S.lm_gpart.reserve(ngp));
     PCD_HIP_TRY(hipSetDevice(b->device));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    PCD_HIP_TRY(hipEventCreate(&ev0));
-    if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); set_error("hipEventCreate failed"); return PCD_ERR_HIP; }
-    struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{ev0, ev1};
+    EventPair ev;   // around the linear solve of an iteration
+    PCD_TRY(ev.create());
     // the accepted parameters: a rejected step copies them back into the handle
     PCD_HIP_TRY(hipMemcpyAsync(S.lm_poses.p, b->poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
     PCD_HIP_TRY(hipMemcpyAsync(S.lm_points.p, b->points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -1334,7 +1332,7 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
       PCD_TRY(pcd_ba_schur_device(b, &so, &none, s));
       hipLaunchKernelGGL(k_ba_grad_max, dim3(ngp), dim3(256), 0, s, ns, S.slot_img.p, ctvec, S.gimg.p, P, cpt, S.gpt.p,
                          S.lm_gpart.p);
-      PCD_HIP_TRY(hipEventRecord(ev0, s));
+      PCD_HIP_TRY(ev.start(s));
       int enq = lo->max_iterations;
       if (direct) {   // fill + factor + solve: an exact step, so there is no second batch below
         PCD_TRY(S.cg_info.reserve(1));
@@ -1350,7 +1348,7 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
         enq = std::min(kPcgFirstBatch, lo->max_iterations);
         pcg_enqueue(b, lo, enq, s);
       }
-      PCD_HIP_TRY(hipEventRecord(ev1, s));
+      PCD_HIP_TRY(ev.stop(s));
       // the tail is enqueued behind the first batch without looking at the flag: at the defaults the PCG has ended
       // by then and the iteration costs one copy; otherwise the batches go on and the tail runs once more
       const LmRecord* rec = S.lm_host.p;
@@ -1364,15 +1362,15 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
         PCD_HIP_TRY(hipMemcpyAsync(S.lm_host.p, S.lm_rec.p, sizeof(LmRecord), hipMemcpyDeviceToHost, s));
         PCD_HIP_TRY(hipStreamSynchronize(s));
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) linear_ms += ms;
+        if (ev.elapsed(&ms) == hipSuccess) linear_ms += ms;
         if (rec->pcg.termination >= 0 || enq >= lo->max_iterations) break;
         // the step just tried came from an unfinished solve: back to the accepted parameters, finish the solve
         PCD_HIP_TRY(hipMemcpyAsync(b->poses.p, S.lm_poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
         PCD_HIP_TRY(hipMemcpyAsync(b->points.p, S.lm_points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
-        PCD_HIP_TRY(hipEventRecord(ev0, s));
+        PCD_HIP_TRY(ev.start(s));
         PCD_TRY(pcg_run(b, lo, enq, s));
         enq = lo->max_iterations;
-        PCD_HIP_TRY(hipEventRecord(ev1, s));
+        PCD_HIP_TRY(ev.stop(s));
       }
       PCD_HIP_TRY(hipGetLastError());
       if (it == 0) sm.initial_cost = sm.final_cost = rec->cost;

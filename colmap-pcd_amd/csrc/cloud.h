@@ -24,6 +24,8 @@
 //                                   with <= 64 lattice nodes (PyramidParams below).
 //                                   An expansion tests up to 64 children with the exact float bound; a leaf is scanned.
 #pragma once
+#include <memory>
+
 #include "common.h"
 
 namespace pcd {
@@ -97,14 +99,32 @@ struct pcd_cloud {
 };
 
 namespace pcd {
+// owner of a handle under construction: a failure path destroys it by returning; success hands it out with release()
+struct CloudDeleter {
+  void operator()(pcd_cloud* c) const { pcd_cloud_destroy(c); }
+};
+using CloudPtr = std::unique_ptr<pcd_cloud, CloudDeleter>;
+
 // pcd_cloud_create with an explicit global index per row (row_index[n], host; NULL = index_base / index_stride) over
 // a cloud of global_n rows in total
 pcd_status cloud_create_indexed(const float* xyz, const float* nrm, uint64_t n, const pcd_cloud_options* opts,
                                 const uint32_t* row_index, uint64_t global_n, pcd_cloud** out);
 // A handle whose rows are produced on the device (voxel.hip): cloud_alloc_rows gives a handle on `device` with pts4 /
 // pn8 allocated for n rows (index_base 0, stride 1) and no index; the caller writes every row of both arrays on stream
-// s, then cloud_build_index builds the grid, the sorted records and the pyramid exactly as pcd_cloud_create does after
-// its row transform (it synchronises s).  On failure the caller destroys the handle.
-pcd_status cloud_alloc_rows(int device, uint64_t n, pcd_cloud** out);
+// s, then cloud_build_index builds the index.
+pcd_status cloud_alloc_rows(int device, uint64_t n, CloudPtr& out);
+// The index of a handle whose pts4 holds its n rows: bounds, cell size, cell table, sorted records, pyramid records
+// (the stages are in cloud.hip).  pcd_cloud_create runs it after its row transform.  It synchronises s, and build_ms
+// is its wall time.
 pcd_status cloud_build_index(pcd_cloud* c, float cell_size, hipStream_t s);
+// Refusal (PCD_ERR_UNSUPPORTED) of a shard or a strided handle by a pass over the neighbourhood of every row: `what`
+// names the pass, `parts` what would cross handle borders, `verb` what to do on one handle instead.
+inline pcd_status require_whole_cloud(const pcd_cloud* c, const char* what, const char* parts, const char* verb) {
+  if (c->row_index.p || c->g2l.p || c->index_stride != 1 || c->index_base != 0) {
+    set_error("%s needs ONE handle holding the whole cloud: %s of a shard (pcd_cloud_create_sharded, index_stride / "
+              "index_base) cross handle borders; %s on one handle, download, then shard", what, parts, verb);
+    return PCD_ERR_UNSUPPORTED;
+  }
+  return PCD_OK;
+}
 }

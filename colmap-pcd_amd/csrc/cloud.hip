@@ -1,15 +1,13 @@
 // cloud.hip -- build of the device-resident cloud index.
 // Reference behaviour restated: lidar/ply.cc:33-57 (axis swap, NaN-row filter,
 // order preserved); lidar/kdtree.cc:5-8 (index over x,y,z of every kept row).
-#include <cstring>  // rocprim's texture_cache_iterator.hpp needs memset declared first
-
-#include <rocprim/rocprim.hpp>
-
+// Host side: cloud_create_indexed (upload, row transform) and cloud_build_index, the driver of the build's six stages.
 #include <chrono>
 #include <cmath>
 
 #include "cloud.h"
 #include "grid.h"
+#include "prim.h"
 
 namespace pcd {
 
@@ -299,44 +297,64 @@ static uint64_t num_cells(const GridParams& g) { return (uint64_t)g.dims[0] * g.
 constexpr uint64_t kMaxCells = 1ull << 26;
 constexpr double kTargetOcc = 24.0;  // mean points per occupied cell
 
-static pcd_status build_grid(pcd_cloud* c, float user_h, hipStream_t s) {
+// ---- the index build, stage by stage (cloud_build_index is the driver).  The stages allocate and free their scratch in
+// a fixed order: what hipMalloc hands out next, to the handle's arrays and the query scratch too, depends on it ----
+// the dense levels of the pyramid: a scaffold of one build (151 MB for workload M, 98 % of it empty nodes)
+struct Lattice {
+  int nreal = 1;                  // real levels (level 0 = leaves)
+  int dims[kMaxPyrLevels][3];
+  uint32_t off[kMaxPyrLevels] = {};   // node offset of each level in `nodes`
+  DevBuf<float> nodes;            // 8 floats per node, the record layout of blk_aabb
+  uint64_t count(int l) const { return (uint64_t)dims[l][0] * dims[l][1] * dims[l][2]; }
+};
+
+// bounds (k_bbox): reads pts4; writes c->m, bb_lo, bb_hi (zeros without a finite row)
+static pcd_status index_bounds(pcd_cloud* c, DevBuf<int>& bb, DevBuf<unsigned long long>& cnt, hipStream_t s) {
   const uint64_t n = c->n;
-  GridParams& g = c->grid;
-  DevBuf<int> bb;
-  DevBuf<unsigned long long> cnt;
   PCD_TRY(bb.reserve(6));
   PCD_TRY(cnt.reserve(2));
   int init[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
   PCD_HIP_TRY(hipMemcpyAsync(bb.p, init, sizeof init, hipMemcpyHostToDevice, s));
   PCD_HIP_TRY(hipMemsetAsync(cnt.p, 0, 2 * sizeof(unsigned long long), s));
-  if (n) {
-    unsigned blocks = std::min<unsigned>(div_up(n, 256), 2048);
-    hipLaunchKernelGGL(k_bbox, dim3(blocks), dim3(256), 0, s, c->pts4.p, n, bb.p, cnt.p);
-  }
+  if (n)
+    hipLaunchKernelGGL(k_bbox, dim3(std::min<unsigned>(div_up(n, 256), 2048)), dim3(256), 0, s, c->pts4.p, n, bb.p, cnt.p);
   int hb[6];
   unsigned long long hc[2];
   PCD_HIP_TRY(hipMemcpyAsync(hb, bb.p, sizeof hb, hipMemcpyDeviceToHost, s));
   PCD_HIP_TRY(hipMemcpyAsync(hc, cnt.p, sizeof hc, hipMemcpyDeviceToHost, s));
   PCD_HIP_TRY(hipStreamSynchronize(s));
   c->m = hc[0];
-  float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  if (c->m) for (int d = 0; d < 3; ++d) { lo[d] = ord2f(hb[d]); hi[d] = ord2f(hb[3 + d]); }
-  for (int d = 0; d < 3; ++d) { c->bb_lo[d] = lo[d]; c->bb_hi[d] = hi[d]; }
+  for (int d = 0; d < 3; ++d) { c->bb_lo[d] = c->m ? ord2f(hb[d]) : 0.f; c->bb_hi[d] = c->m ? ord2f(hb[3 + d]) : 0.f; }
+  return PCD_OK;
+}
 
-  // --- cell size: user value, or iterate towards kTargetOcc points per occupied cell ---
-  double ext[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
-  double maxext = std::fmax(ext[0], std::fmax(ext[1], ext[2]));
-  auto min_h_for_budget = [&]() {
-    double h = std::cbrt((ext[0] + 1e-3) * (ext[1] + 1e-3) * (ext[2] + 1e-3) / (double)kMaxCells);
-    for (int it = 0; it < 64; ++it) {
-      double cells = (std::floor(ext[0] / h) + 1) * (std::floor(ext[1] / h) + 1) * (std::floor(ext[2] / h) + 1);
-      if (cells <= (double)kMaxCells) break;
-      h *= 1.05;
-    }
-    return h;
-  };
-  float h;
-  const double hmin = std::fmax(min_h_for_budget(), 1e-6 * std::fmax(maxext, 1e-3));
+// histogram of the finite rows over the cells of c->grid into count[0 .. cells], the number of occupied cells into
+// *occupied (host): enqueued on s, so *occupied is valid after the caller's next synchronisation
+static pcd_status cell_histogram(const pcd_cloud* c, uint32_t* count, unsigned long long* d_cnt,
+                                 unsigned long long* occupied, hipStream_t s) {
+  const uint64_t n = c->n, nc = num_cells(c->grid);
+  PCD_HIP_TRY(hipMemsetAsync(count, 0, (nc + 1) * sizeof(uint32_t), s));
+  PCD_HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), s));
+  if (n) hipLaunchKernelGGL(k_cell_hist, dim3(div_up(n, 256)), dim3(256), 0, s, c->pts4.p, n, c->grid, count);
+  hipLaunchKernelGGL(k_count_nonzero, dim3(std::min<unsigned>(div_up(nc, 256), 4096)), dim3(256), 0, s, count, nc, d_cnt);
+  PCD_HIP_TRY(hipMemcpyAsync(occupied, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  return PCD_OK;
+}
+
+// cell size: the user's value (raised to the cell budget), or up to six rounds towards kTargetOcc points per occupied
+// cell.  Reads m and the bounds; sets h.  The rounds use c->grid and c->cell_start as their scratch.
+static pcd_status choose_cell_size(pcd_cloud* c, float user_h, DevBuf<unsigned long long>& cnt, hipStream_t s, float& h) {
+  const float *lo = c->bb_lo, *hi = c->bb_hi;
+  const double ext[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
+  const double maxext = std::fmax(ext[0], std::fmax(ext[1], ext[2]));
+  // the smallest cell whose grid over the bounds stays within kMaxCells
+  double hb = std::cbrt((ext[0] + 1e-3) * (ext[1] + 1e-3) * (ext[2] + 1e-3) / (double)kMaxCells);
+  for (int it = 0; it < 64; ++it) {
+    double cells = (std::floor(ext[0] / hb) + 1) * (std::floor(ext[1] / hb) + 1) * (std::floor(ext[2] / hb) + 1);
+    if (cells <= (double)kMaxCells) break;
+    hb *= 1.05;
+  }
+  const double hmin = std::fmax(hb, 1e-6 * std::fmax(maxext, 1e-3));
   if (c->m == 0 || maxext <= 0) {
     h = user_h > 0 ? user_h : 1.0f;
   } else if (user_h > 0) {
@@ -346,17 +364,12 @@ static pcd_status build_grid(pcd_cloud* c, float user_h, hipStream_t s) {
     double hguess = std::sqrt(kTargetOcc * (ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2] + 1e-6) / (double)c->m);
     h = (float)std::fmin(std::fmax(hguess, hmin), std::fmax(maxext, hmin));
     for (int it = 0; it < 6; ++it) {
-      set_dims(g, lo, hi, h);
-      uint64_t nc = num_cells(g);
-      PCD_TRY(c->cell_start.reserve(nc + 1));
-      PCD_HIP_TRY(hipMemsetAsync(c->cell_start.p, 0, (nc + 1) * sizeof(uint32_t), s));
-      PCD_HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), s));
-      hipLaunchKernelGGL(k_cell_hist, dim3(div_up(n, 256)), dim3(256), 0, s, c->pts4.p, n, g, c->cell_start.p);
-      hipLaunchKernelGGL(k_count_nonzero, dim3(std::min<unsigned>(div_up(nc, 256), 4096)), dim3(256), 0, s,
-                         c->cell_start.p, nc, cnt.p);
-      PCD_HIP_TRY(hipMemcpyAsync(hc, cnt.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+      set_dims(c->grid, lo, hi, h);
+      PCD_TRY(c->cell_start.reserve(num_cells(c->grid) + 1));
+      unsigned long long occupied = 0;
+      PCD_TRY(cell_histogram(c, c->cell_start.p, cnt.p, &occupied, s));
       PCD_HIP_TRY(hipStreamSynchronize(s));
-      double occ = (double)c->m / (double)std::max<unsigned long long>(hc[0], 1);
+      double occ = (double)c->m / (double)std::max<unsigned long long>(occupied, 1);
       if (occ > 0.75 * kTargetOcc && occ < 1.5 * kTargetOcc) break;
       // occupancy ~ h^2 on surfaces, h^3 in volumes: use exponent 2.5
       double hn = h * std::pow(kTargetOcc / occ, 1.0 / 2.5);
@@ -365,98 +378,95 @@ static pcd_status build_grid(pcd_cloud* c, float user_h, hipStream_t s) {
       h = (float)hn;
     }
   }
-  set_dims(g, lo, hi, h);
-  c->ncells = num_cells(g);
-  c->nblocks = (uint64_t)g.bdims[0] * g.bdims[1] * g.bdims[2];
+  return PCD_OK;
+}
+
+// cell table: the grid at cell size h, the budget check, the final histogram and its exclusive scan.  Writes c->grid,
+// ncells, nblocks, cell_start, occupied.
+static pcd_status build_cell_table(pcd_cloud* c, float h, DevBuf<unsigned long long>& cnt, hipStream_t s) {
+  set_dims(c->grid, c->bb_lo, c->bb_hi, h);
+  c->ncells = num_cells(c->grid);
+  c->nblocks = (uint64_t)c->grid.bdims[0] * c->grid.bdims[1] * c->grid.bdims[2];
   if (c->ncells > kMaxCells * 2) {
     set_error("grid of %llu cells exceeds the budget", (unsigned long long)c->ncells);
     return PCD_ERR_UNSUPPORTED;
   }
-
-  // --- final histogram -> cell_start (exclusive scan) ---
   PCD_TRY(c->cell_start.reserve(c->ncells + 1));
-  {
-    DevBuf<uint32_t> counts;
-    PCD_TRY(counts.reserve(c->ncells + 1));
-    PCD_HIP_TRY(hipMemsetAsync(counts.p, 0, (c->ncells + 1) * sizeof(uint32_t), s));
-    PCD_HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), s));
-    if (n) hipLaunchKernelGGL(k_cell_hist, dim3(div_up(n, 256)), dim3(256), 0, s, c->pts4.p, n, g, counts.p);
-    hipLaunchKernelGGL(k_count_nonzero, dim3(std::min<unsigned>(div_up(c->ncells, 256), 4096)), dim3(256), 0, s,
-                       counts.p, c->ncells, cnt.p);
-    PCD_HIP_TRY(hipMemcpyAsync(hc, cnt.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    size_t tb = 0;
-    PCD_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, counts.p, c->cell_start.p, 0u, c->ncells + 1,
-                                        rocprim::plus<uint32_t>(), s));
-    DevBuf<char> tmp;
-    PCD_TRY(tmp.reserve(tb));
-    PCD_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, counts.p, c->cell_start.p, 0u, c->ncells + 1,
-                                        rocprim::plus<uint32_t>(), s));
-    PCD_HIP_TRY(hipStreamSynchronize(s));
-  }
-  c->occupied = hc[0];
+  DevBuf<uint32_t> counts;
+  PCD_TRY(counts.reserve(c->ncells + 1));
+  unsigned long long occupied = 0;
+  PCD_TRY(cell_histogram(c, counts.p, cnt.p, &occupied, s));
+  DevBuf<char> tmp;
+  PCD_TRY(exclusive_sum(tmp, counts.p, c->cell_start.p, 0u, c->ncells + 1, s));
+  PCD_HIP_TRY(hipStreamSynchronize(s));
+  c->occupied = occupied;
+  return PCD_OK;
+}
 
-  // --- sort rows by cell (stable radix sort keeps original order inside a cell) ---
+// sorted records: rows by cell (the stable radix sort keeps the original order inside a cell), gathered with their
+// global index.  Reads pts4, grid, m; writes c->sorted.
+static pcd_status sort_rows(pcd_cloud* c, hipStream_t s) {
+  const uint64_t n = c->n;
   PCD_TRY(c->sorted.reserve(c->m + kSortedSpare));   // spare records, see k_gather_sorted
-  if (n) {
-    DevBuf<uint32_t> k0, k1, v0, v1;
-    PCD_TRY(k0.reserve(n)); PCD_TRY(k1.reserve(n)); PCD_TRY(v0.reserve(n)); PCD_TRY(v1.reserve(n));
-    hipLaunchKernelGGL(k_cell_keys, dim3(div_up(n, 256)), dim3(256), 0, s, c->pts4.p, n, g, k0.p, v0.p);
-    size_t tb = 0;
-    PCD_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, k0.p, k1.p, v0.p, v1.p, n, 0, 32, s));
-    DevBuf<char> tmp;
-    PCD_TRY(tmp.reserve(tb));
-    PCD_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, k0.p, k1.p, v0.p, v1.p, n, 0, 32, s));
-    if (c->m)
-      hipLaunchKernelGGL(k_gather_sorted, dim3(div_up(c->m + kSortedSpare, 256)), dim3(256), 0, s, c->pts4.p, v1.p, c->m,
-                         c->index_base, c->index_stride, c->row_index.p, c->sorted.p);
-    PCD_HIP_TRY(hipStreamSynchronize(s));
-  }
+  if (n == 0) return PCD_OK;
+  DevBuf<uint32_t> k0, k1, v0, v1;
+  PCD_TRY(k0.reserve(n)); PCD_TRY(k1.reserve(n)); PCD_TRY(v0.reserve(n)); PCD_TRY(v1.reserve(n));
+  hipLaunchKernelGGL(k_cell_keys, dim3(div_up(n, 256)), dim3(256), 0, s, c->pts4.p, n, c->grid, k0.p, v0.p);
+  DevBuf<char> tmp;
+  PCD_TRY(sort_pairs(tmp, k0.p, k1.p, v0.p, v1.p, n, 0, 32, s));
+  if (c->m)
+    hipLaunchKernelGGL(k_gather_sorted, dim3(div_up(c->m + kSortedSpare, 256)), dim3(256), 0, s, c->pts4.p, v1.p, c->m,
+                       c->index_base, c->index_stride, c->row_index.p, c->sorted.p);
+  PCD_HIP_TRY(hipStreamSynchronize(s));   // the keys go out of scope
+  return PCD_OK;
+}
 
-  // --- leaves (2x2x2-cell sub-blocks: tight box + point range) + coarser pyramid levels, on the dense lattice ---
-  PyramidParams& py = c->pyr;
-  int dims[kMaxPyrLevels][3];
-  uint32_t off[kMaxPyrLevels];   // node offset of each level in `dense`
-  int nreal = 1;                 // real levels
-  dims[0][0] = (g.dims[0] + 1) / 2; dims[0][1] = g.qdims[0]; dims[0][2] = g.qdims[1];
-  off[0] = 0;
-  const uint64_t nleaves = (uint64_t)dims[0][0] * dims[0][1] * dims[0][2];
+// lattice: leaves (2x2x2-cell sub-blocks: tight box + point range) and the coarser levels, dense.  Reads sorted,
+// cell_start, grid; writes L, c->pyr.nlev and c->pyr.seed_dims.  Enqueues only.
+static pcd_status build_lattice(pcd_cloud* c, Lattice& L, hipStream_t s) {
+  const GridParams& g = c->grid;
+  L.dims[0][0] = (g.dims[0] + 1) / 2; L.dims[0][1] = g.qdims[0]; L.dims[0][2] = g.qdims[1];
+  const uint64_t nleaves = L.count(0);
   uint64_t total_nodes = nleaves;
-  auto level_nodes = [&](int l) { return (uint64_t)dims[l][0] * dims[l][1] * dims[l][2]; };
   // real levels until one has at most 64 nodes; above it sits a VIRTUAL top whose children are ALL nodes of that level,
   // one per lane (k_nn_fallback): for workload M's grid that is 5 x 2 x 5 = 50 nodes -- the walk starts there instead of
   // expanding a root of 1 and a level of 4 nodes first (two expansions and two pops less per query)
-  while (nreal < kMaxPyrLevels - 1) {
-    if (level_nodes(nreal - 1) <= 64) break;
-    for (int d = 0; d < 3; ++d) dims[nreal][d] = (dims[nreal - 1][d] + 3) / 4;
-    off[nreal] = (uint32_t)total_nodes;
-    total_nodes += level_nodes(nreal);
-    nreal++;
+  while (L.nreal < kMaxPyrLevels - 1) {
+    if (L.count(L.nreal - 1) <= 64) break;
+    for (int d = 0; d < 3; ++d) L.dims[L.nreal][d] = (L.dims[L.nreal - 1][d] + 3) / 4;
+    L.off[L.nreal] = (uint32_t)total_nodes;
+    total_nodes += L.count(L.nreal);
+    L.nreal++;
   }
-  if (level_nodes(nreal - 1) > 64) {
+  if (L.count(L.nreal - 1) > 64) {
     set_error("grid too large for %d pyramid levels", kMaxPyrLevels);
     return PCD_ERR_UNSUPPORTED;
   }
-  for (int d = 0; d < 3; ++d) py.seed_dims[d] = (g.dims[d] + 7) / 8;   // (cell >> 3 for every cell of the grid)
-  py.nlev = nreal + 1;   // + the virtual top
-  DevBuf<float> dense;   // the lattice levels: a scaffold of this build (151 MB for workload M, 98 % of it empty nodes)
-  PCD_TRY(dense.reserve(8 * total_nodes));
+  for (int d = 0; d < 3; ++d) c->pyr.seed_dims[d] = (g.dims[d] + 7) / 8;   // (cell >> 3 for every cell of the grid)
+  c->pyr.nlev = L.nreal + 1;   // + the virtual top
+  PCD_TRY(L.nodes.reserve(8 * total_nodes));
   hipLaunchKernelGGL(k_leaf_aabb, dim3(div_up(nleaves * 64, 256)), dim3(256), 0, s, c->sorted.p, c->cell_start.p, g,
-                     dims[0][0], dims[0][1], dims[0][2], dense.p);
-  for (int l = 1; l < nreal; ++l) {
-    const int* cd = dims[l - 1];
-    const int* pd = dims[l];
-    hipLaunchKernelGGL(k_pyramid_level, dim3(div_up(level_nodes(l), 256)), dim3(256), 0, s, dense.p, off[l - 1], cd[0],
-                       cd[1], cd[2], off[l], pd[0], pd[1], pd[2]);
+                     L.dims[0][0], L.dims[0][1], L.dims[0][2], L.nodes.p);
+  for (int l = 1; l < L.nreal; ++l) {
+    const int *cd = L.dims[l - 1], *pd = L.dims[l];
+    hipLaunchKernelGGL(k_pyramid_level, dim3(div_up(L.count(l), 256)), dim3(256), 0, s, L.nodes.p, L.off[l - 1], cd[0],
+                       cd[1], cd[2], L.off[l], pd[0], pd[1], pd[2]);
   }
+  return PCD_OK;
+}
 
-  // --- the tree over the occupied nodes (cloud.h): records top down, children contiguous and in lane order ---
+// tree: the records of the occupied nodes (cloud.h), top down, children contiguous and in lane order.  Reads L; writes
+// c->blk_aabb, c->pyr.root_first and root_count.
+static pcd_status compact_tree(pcd_cloud* c, const Lattice& L, hipStream_t s) {
+  const int nreal = L.nreal;
+  const float* dense = L.nodes.p;
   DevBuf<unsigned long long> occ;
   unsigned long long hocc[kMaxPyrLevels] = {};
   PCD_TRY(occ.reserve(kMaxPyrLevels));
   PCD_HIP_TRY(hipMemsetAsync(occ.p, 0, kMaxPyrLevels * sizeof(unsigned long long), s));
   for (int l = 0; l < nreal; ++l)
-    hipLaunchKernelGGL(k_count_occupied, dim3(std::min<unsigned>(div_up(level_nodes(l), 256), 4096)), dim3(256), 0, s,
-                       dense.p, (uint64_t)off[l], level_nodes(l), occ.p + l);
+    hipLaunchKernelGGL(k_count_occupied, dim3(std::min<unsigned>(div_up(L.count(l), 256), 4096)), dim3(256), 0, s,
+                       dense, (uint64_t)L.off[l], L.count(l), occ.p + l);
   PCD_HIP_TRY(hipMemcpyAsync(hocc, occ.p, nreal * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
   PCD_HIP_TRY(hipStreamSynchronize(s));
   uint64_t base[kMaxPyrLevels], total_rec = 0, max_level = 1;
@@ -469,64 +479,65 @@ static pcd_status build_grid(pcd_cloud* c, float user_h, hipStream_t s) {
     set_error("%llu pyramid records exceed the walk's range encoding", (unsigned long long)total_rec);
     return PCD_ERR_UNSUPPORTED;
   }
-  py.root_first = (uint32_t)base[nreal - 1];
-  py.root_count = (uint32_t)hocc[nreal - 1];
+  c->pyr.root_first = (uint32_t)base[nreal - 1];
+  c->pyr.root_count = (uint32_t)hocc[nreal - 1];
   PCD_TRY(c->blk_aabb.reserve(8 * std::max<uint64_t>(total_rec, 1)));
   if (total_rec == 0) {   // one record that is never a child: defined bytes for the walk's clamped load
     PCD_HIP_TRY(hipMemsetAsync(c->blk_aabb.p, 0, 8 * sizeof(float), s));
+    return PCD_OK;
   }
-  if (total_rec) {
-    DevBuf<uint32_t> list_a, list_b, cnt, first;
-    DevBuf<char> tmp;
-    PCD_TRY(list_a.reserve(max_level)); PCD_TRY(list_b.reserve(max_level));
-    PCD_TRY(cnt.reserve(max_level)); PCD_TRY(first.reserve(max_level));
-    uint32_t* cur = list_a.p;
-    uint32_t* nxt = list_b.p;
-    hipLaunchKernelGGL(k_top_list, dim3(1), dim3(64), 0, s, dense.p, off[nreal - 1], (uint32_t)level_nodes(nreal - 1), cur);
-    for (int l = nreal - 1; l >= 1; --l) {
-      const uint32_t np = (uint32_t)hocc[l];
-      const int* cd = dims[l - 1];
-      const int* pd = dims[l];
-      hipLaunchKernelGGL(k_child_count, dim3(div_up((uint64_t)np * 64, 256)), dim3(256), 0, s, dense.p, cur, np, pd[0], pd[1],
-                         off[l - 1], cd[0], cd[1], cd[2], cnt.p);
-      size_t tb = 0;
-      PCD_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, cnt.p, first.p, 0u, np, rocprim::plus<uint32_t>(), s));
-      PCD_TRY(tmp.reserve(tb));
-      PCD_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, cnt.p, first.p, 0u, np, rocprim::plus<uint32_t>(), s));
-      hipLaunchKernelGGL(k_emit_children, dim3(div_up((uint64_t)np * 64, 256)), dim3(256), 0, s, dense.p, cur, np, off[l],
-                         pd[0], pd[1], off[l - 1], cd[0], cd[1], cd[2], first.p, (uint32_t)base[l], (uint32_t)base[l - 1],
-                         nxt, c->blk_aabb.p);
-      std::swap(cur, nxt);
-    }
-    hipLaunchKernelGGL(k_emit_leaves, dim3(div_up(hocc[0], 256)), dim3(256), 0, s,
-                       reinterpret_cast<const float4*>(dense.p), cur, (uint32_t)hocc[0],
-                       reinterpret_cast<float4*>(c->blk_aabb.p + 8 * base[0]));
-    PCD_HIP_TRY(hipStreamSynchronize(s));   // the lists go out of scope
+  DevBuf<uint32_t> list_a, list_b, nchild, first;
+  DevBuf<char> tmp;
+  PCD_TRY(list_a.reserve(max_level)); PCD_TRY(list_b.reserve(max_level));
+  PCD_TRY(nchild.reserve(max_level)); PCD_TRY(first.reserve(max_level));
+  uint32_t *cur = list_a.p, *nxt = list_b.p;
+  hipLaunchKernelGGL(k_top_list, dim3(1), dim3(64), 0, s, dense, L.off[nreal - 1], (uint32_t)L.count(nreal - 1), cur);
+  for (int l = nreal - 1; l >= 1; --l) {
+    const uint32_t np = (uint32_t)hocc[l];
+    const int *cd = L.dims[l - 1], *pd = L.dims[l];
+    hipLaunchKernelGGL(k_child_count, dim3(div_up((uint64_t)np * 64, 256)), dim3(256), 0, s, dense, cur, np, pd[0], pd[1],
+                       L.off[l - 1], cd[0], cd[1], cd[2], nchild.p);
+    PCD_TRY(exclusive_sum(tmp, nchild.p, first.p, 0u, np, s));
+    hipLaunchKernelGGL(k_emit_children, dim3(div_up((uint64_t)np * 64, 256)), dim3(256), 0, s, dense, cur, np, L.off[l],
+                       pd[0], pd[1], L.off[l - 1], cd[0], cd[1], cd[2], first.p, (uint32_t)base[l], (uint32_t)base[l - 1],
+                       nxt, c->blk_aabb.p);
+    std::swap(cur, nxt);
   }
-  PCD_HIP_TRY(hipStreamSynchronize(s));     // ... and the scaffold
-  PCD_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_emit_leaves, dim3(div_up(hocc[0], 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(dense),
+                     cur, (uint32_t)hocc[0], reinterpret_cast<float4*>(c->blk_aabb.p + 8 * base[0]));
+  PCD_HIP_TRY(hipStreamSynchronize(s));   // the lists go out of scope
   return PCD_OK;
 }
 
-pcd_status cloud_alloc_rows(int device, uint64_t n, pcd_cloud** out) {
-  *out = nullptr;
+// the rows of a handle: n, pts4 and pn8 (never empty allocations: kernels and the walk may form their addresses)
+static pcd_status reserve_rows(pcd_cloud* c, uint64_t n) {
   PCD_REQUIRE(n < 0xFFFFFFF0ull, "more than 2^32 rows");
-  pcd_cloud* c = new pcd_cloud();
-  c->device = device;
   c->n = n;
-  pcd_status st = c->pts4.reserve(std::max<uint64_t>(n, 1));
-  if (st == PCD_OK) st = c->pn8.reserve(2 * std::max<uint64_t>(n, 1));
-  if (st != PCD_OK) {
-    pcd_cloud_destroy(c);
-    return st;
-  }
-  *out = c;
+  PCD_TRY(c->pts4.reserve(std::max<uint64_t>(n, 1)));
+  PCD_TRY(c->pn8.reserve(2 * std::max<uint64_t>(n, 1)));
   return PCD_OK;
+}
+
+pcd_status cloud_alloc_rows(int device, uint64_t n, CloudPtr& out) {
+  out.reset(new pcd_cloud());
+  out->device = device;
+  return reserve_rows(out.get(), n);
 }
 
 pcd_status cloud_build_index(pcd_cloud* c, float cell_size, hipStream_t s) {
-  auto t0 = std::chrono::steady_clock::now();
-  PCD_TRY(build_grid(c, cell_size, s));
+  const auto t0 = std::chrono::steady_clock::now();
+  DevBuf<int> bb;                   // device results of the bounds pass ...
+  DevBuf<unsigned long long> cnt;   // ... and of the histograms: freed last
+  Lattice L;                        // lives to the end of the build and no longer
+  float h = 0.f;
+  PCD_TRY(index_bounds(c, bb, cnt, s));
+  PCD_TRY(choose_cell_size(c, cell_size, cnt, s, h));
+  PCD_TRY(build_cell_table(c, h, cnt, s));
+  PCD_TRY(sort_rows(c, s));
+  PCD_TRY(build_lattice(c, L, s));
+  PCD_TRY(compact_tree(c, L, s));
+  PCD_HIP_TRY(hipStreamSynchronize(s));   // the scaffold and the scratch go out of scope
+  PCD_HIP_TRY(hipGetLastError());
   c->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return PCD_OK;
 }
@@ -575,62 +586,50 @@ pcd_status pcd::cloud_create_indexed(const float* xyz, const float* nrm, uint64_
   PCD_REQUIRE(o.cell_size >= 0 && std::isfinite(o.cell_size), "cell_size");
   PCD_TRY(require_device(o.device));
 
-  auto t0 = std::chrono::steady_clock::now();
-  pcd_cloud* c = new pcd_cloud();
+  const auto t0 = std::chrono::steady_clock::now();
+  CloudPtr c(new pcd_cloud());   // destroyed by every failing return below
   c->device = o.device;
   c->index_base = o.index_base;
   c->index_stride = o.index_stride;
   hipStream_t s = nullptr;
-  auto fail = [&](pcd_status st) { pcd_cloud_destroy(c); return st; };
   if (row_index) {
-    if (o.raw_lidar_frame) { set_error("indexed shards need raw_lidar_frame = 0"); return fail(PCD_ERR_INVALID); }
-    pcd_status sr;
-    if ((sr = c->row_index.reserve(std::max<uint64_t>(n, 1))) != PCD_OK) return fail(sr);
-    if ((sr = c->g2l.reserve(std::max<uint64_t>(global_n, 1))) != PCD_OK) return fail(sr);
+    PCD_REQUIRE(!o.raw_lidar_frame, "indexed shards need raw_lidar_frame = 0");
+    PCD_TRY(c->row_index.reserve(std::max<uint64_t>(n, 1)));
+    PCD_TRY(c->g2l.reserve(std::max<uint64_t>(global_n, 1)));
     c->g2l_n = global_n;
-    if (n && hipMemcpy(c->row_index.p, row_index, n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return fail(PCD_ERR_HIP);
-    if (hipMemset(c->g2l.p, 0xFF, std::max<uint64_t>(global_n, 1) * sizeof(uint32_t)) != hipSuccess) return fail(PCD_ERR_HIP);
+    if (n) PCD_HIP_TRY(hipMemcpy(c->row_index.p, row_index, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    PCD_HIP_TRY(hipMemset(c->g2l.p, 0xFF, std::max<uint64_t>(global_n, 1) * sizeof(uint32_t)));
     if (n) hipLaunchKernelGGL(k_fill_g2l, dim3(div_up(n, 256)), dim3(256), 0, s, c->row_index.p, n, c->g2l.p);
   }
 
   const size_t row = o.layout == PCD_LAYOUT_AOS32 ? 8 : 3;
   DevBuf<float> d_xyz, d_nrm;
   DevBuf<uint32_t> keep, pos;
-  pcd_status st;
-  if ((st = d_xyz.reserve(std::max<size_t>(n * row, 1))) != PCD_OK) return fail(st);
-  if ((st = d_nrm.reserve(std::max<size_t>(n * 3, 1))) != PCD_OK) return fail(st);
+  PCD_TRY(d_xyz.reserve(std::max<size_t>(n * row, 1)));
+  PCD_TRY(d_nrm.reserve(std::max<size_t>(n * 3, 1)));
   if (n) {
-    if (hipMemcpy(d_xyz.p, xyz, n * row * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(PCD_ERR_HIP);
-    if (o.layout == PCD_LAYOUT_XYZ_NRM &&
-        hipMemcpy(d_nrm.p, nrm, n * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(PCD_ERR_HIP);
+    PCD_HIP_TRY(hipMemcpy(d_xyz.p, xyz, n * row * sizeof(float), hipMemcpyHostToDevice));
+    if (o.layout == PCD_LAYOUT_XYZ_NRM) PCD_HIP_TRY(hipMemcpy(d_nrm.p, nrm, n * 3 * sizeof(float), hipMemcpyHostToDevice));
   }
   uint64_t kept = n;
   if (o.raw_lidar_frame && n) {
-    if ((st = keep.reserve(n)) != PCD_OK) return fail(st);
-    if ((st = pos.reserve(n)) != PCD_OK) return fail(st);
+    PCD_TRY(keep.reserve(n)); PCD_TRY(pos.reserve(n));
     hipLaunchKernelGGL(k_flag_rows, dim3(div_up(n, 256)), dim3(256), 0, s, d_xyz.p, d_nrm.p, n, o.layout, keep.p);
-    size_t tb = 0;
-    if (rocprim::exclusive_scan(nullptr, tb, keep.p, pos.p, 0u, n, rocprim::plus<uint32_t>(), s) != hipSuccess)
-      return fail(PCD_ERR_HIP);
     DevBuf<char> tmp;
-    if ((st = tmp.reserve(tb)) != PCD_OK) return fail(st);
-    if (rocprim::exclusive_scan(tmp.p, tb, keep.p, pos.p, 0u, n, rocprim::plus<uint32_t>(), s) != hipSuccess)
-      return fail(PCD_ERR_HIP);
+    PCD_TRY(exclusive_sum(tmp, keep.p, pos.p, 0u, n, s));
     uint32_t lastp = 0, lastk = 0;
-    if (hipMemcpy(&lastp, pos.p + (n - 1), 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(PCD_ERR_HIP);
-    if (hipMemcpy(&lastk, keep.p + (n - 1), 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(PCD_ERR_HIP);
+    PCD_HIP_TRY(hipMemcpy(&lastp, pos.p + (n - 1), 4, hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipMemcpy(&lastk, keep.p + (n - 1), 4, hipMemcpyDeviceToHost));
     kept = (uint64_t)lastp + lastk;
   }
-  c->n = kept;
-  if ((st = c->pts4.reserve(std::max<uint64_t>(kept, 1))) != PCD_OK) return fail(st);
-  if ((st = c->pn8.reserve(2 * std::max<uint64_t>(kept, 1))) != PCD_OK) return fail(st);
+  PCD_TRY(reserve_rows(c.get(), kept));
   if (n)
     hipLaunchKernelGGL(k_compact_rows, dim3(div_up(n, 256)), dim3(256), 0, s, d_xyz.p, d_nrm.p, n, o.layout,
                        o.raw_lidar_frame, keep.p, pos.p, c->pts4.p, c->pn8.p);
-  if (hipStreamSynchronize(s) != hipSuccess) { set_error("row transform failed"); return fail(PCD_ERR_HIP); }
-  if ((st = build_grid(c, o.cell_size, s)) != PCD_OK) return fail(st);
+  if (hipStreamSynchronize(s) != hipSuccess) { set_error("row transform failed"); return PCD_ERR_HIP; }
+  PCD_TRY(cloud_build_index(c.get(), o.cell_size, s));
   c->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = c;
+  *out = c.release();
   return PCD_OK;
 }
 

@@ -65,6 +65,9 @@ const char* get_error();
 
 // Checks that `device` exists and is a gfx950 part.  No CPU fallback exists.
 pcd_status require_device(int device);
+// Its head alone: PCD_ERR_NO_DEVICE unless the process sees a HIP device (*count, if given, is their number).  For
+// entry points that document this guard ahead of their argument checks.
+pcd_status require_any_device(int* count = nullptr);
 
 // The *_device entry points are written for EAGER launches on the caller's stream: they grow per-handle scratch
 // (hipFree + hipMalloc), build per-cloud tables behind a hipStreamSynchronize on first use and time scopes with
@@ -142,6 +145,34 @@ struct PinnedBuf {
     }
     n = count;
     return PCD_OK;
+  }
+};
+
+// ----------------------------------------------------------- event pair ----
+// Two timing events around a span of one stream's work, destroyed with the object.
+struct EventPair {
+  hipEvent_t a = nullptr, b = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  pcd_status create() {
+    PCD_HIP_TRY(hipEventCreate(&a));
+    PCD_HIP_TRY(hipEventCreate(&b));
+    return PCD_OK;
+  }
+  hipError_t start(hipStream_t s) { return hipEventRecord(a, s); }
+  hipError_t stop(hipStream_t s) { return hipEventRecord(b, s); }
+  hipError_t elapsed(float* ms) const { return hipEventElapsedTime(ms, a, b); }   // after both events have completed
+  // records the stop event, waits for it and reads the span; the result is the wait's
+  hipError_t stop_and_wait(hipStream_t s, float* ms) {
+    (void)stop(s);
+    const hipError_t e = hipEventSynchronize(b);
+    if (e == hipSuccess) (void)elapsed(ms);
+    return e;
   }
 };
 

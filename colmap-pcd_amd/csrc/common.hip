@@ -19,7 +19,7 @@ static bool is_gfx950(int device) {
   return std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
 }
 
-pcd_status require_device(int device) {
+pcd_status require_any_device(int* count) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || n <= 0) {
@@ -28,6 +28,13 @@ pcd_status require_device(int device) {
               e == hipSuccess ? "device count 0" : hipGetErrorString(e));
     return PCD_ERR_NO_DEVICE;
   }
+  if (count) *count = n;
+  return PCD_OK;
+}
+
+pcd_status require_device(int device) {
+  int n = 0;
+  PCD_TRY(require_any_device(&n));
   if (device < 0 || device >= n) {
     set_error("device %d out of range (0..%d)", device, n - 1);
     return PCD_ERR_INVALID;

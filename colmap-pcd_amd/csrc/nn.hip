@@ -57,15 +57,12 @@
 //     ever compares bounds with the current best, whatever produced it, so no bound argument is needed: the result
 //     is the minimum over the cloud as before.  Ties: a point at the seed's distance with a lower index lies in a
 //     block with lb <= best, which is not skipped.
-#include <cstring>  // rocprim's texture_cache_iterator.hpp needs memset declared first
-
-#include <rocprim/rocprim.hpp>
-
 #include <atomic>
 #include <cfloat>
 
 #include "cloud.h"
 #include "grid.h"
+#include "prim.h"
 #include "scratch.h"
 
 namespace pcd {
@@ -1205,16 +1202,13 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
     hipLaunchKernelGGL(k_brick_keys, dim3(div_up(Q, 256)), dim3(256), 0, s, sc->qf4.p, Q, g, b, k0, v0);
     unsigned end_bit = 1;
     while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)b.nbricks + 1) ++end_bit;
-    size_t tb = 0;
 #ifndef PCD_SORT_MERGE_LIMIT
 #define PCD_SORT_MERGE_LIMIT 262144
 #endif
     // rocPRIM's default takes its merge sort up to 2^20 items: Onesweep above 256 k
     using SortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
                                                rocprim::default_config, PCD_SORT_MERGE_LIMIT>;
-    PCD_HIP_TRY(rocprim::radix_sort_pairs<SortCfg>(nullptr, tb, k0, k1, v0, v1, (unsigned)Q, 0u, end_bit, s));
-    PCD_TRY(sc->tmp.reserve(tb));
-    PCD_HIP_TRY(rocprim::radix_sort_pairs<SortCfg>(sc->tmp.p, tb, k0, k1, v0, v1, (unsigned)Q, 0u, end_bit, s));
+    PCD_TRY(sort_pairs<SortCfg>(sc->tmp, k0, k1, v0, v1, (unsigned)Q, 0u, end_bit, s));
     const unsigned ntiles = div_up(Q, kBkTile);
     hipLaunchKernelGGL(k_brick_tile_count<kGroup>, dim3(ntiles), dim3(256), 0, s, k1, (uint32_t)Q, b.nbricks, sc->bk_item.p);
     hipLaunchKernelGGL(k_brick_emit<kGroup>, dim3(ntiles), dim3(256), 0, s, k1, v1, sc->bk_item.p, sc->qf4.p, carried_keys,

@@ -24,14 +24,11 @@
 //   * epilogue per lane: covariance, cyclic Jacobi in fp64, the degenerate rules, orientation, stores through the
 //     global row in sorted[].w; the info counters are block sums written per block and added up by one more launch
 //     (integers: any order gives the same totals).
-#include <cstring>  // rocprim's texture_cache_iterator.hpp needs memset declared first
-
-#include <rocprim/rocprim.hpp>
-
 #include <cmath>
 
 #include "cloud.h"
 #include "grid.h"
+#include "prim.h"
 #include "scratch.h"
 
 namespace pcd {
@@ -395,12 +392,7 @@ __global__ __launch_bounds__(256) void k_normals_totals(const unsigned long long
 // ------------------------------------------------------------ host side ----
 // Guards of both entry points, in the order pcdhip.h lists them; fills `o` with the options in force.
 static pcd_status normals_guards(const pcd_cloud* c, const pcd_normals_options* opts, pcd_normals_options& o) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    set_error("no HIP device available; libpcdhip has no CPU fallback");
-    return PCD_ERR_NO_DEVICE;
-  }
+  PCD_TRY(require_any_device());
   PCD_REQUIRE(c, "null cloud");
   if (opts) o = *opts; else pcd_normals_options_default(&o);
   PCD_REQUIRE(std::isfinite(o.radius) && o.radius > 0.f, "radius must be finite and positive");
@@ -413,16 +405,6 @@ static pcd_status normals_guards(const pcd_cloud* c, const pcd_normals_options* 
     set_error("radius %g is %.3g cells of the handle's grid (cell_size %g); at most 8: create the handle with a "
               "larger cell_size", (double)o.radius, (double)o.radius / (double)c->grid.h, (double)c->grid.h);
     return PCD_ERR_INVALID;
-  }
-  return PCD_OK;
-}
-
-static pcd_status normals_refuse_shards(const pcd_cloud* c) {
-  if (c->row_index.p || c->g2l.p || c->index_stride != 1 || c->index_base != 0) {
-    set_error("normal estimation needs ONE handle holding the whole cloud: the neighbourhoods of a shard "
-              "(pcd_cloud_create_sharded, index_stride / index_base) cross handle borders; estimate on one handle, "
-              "download, then shard");
-    return PCD_ERR_UNSUPPORTED;
   }
   return PCD_OK;
 }
@@ -463,12 +445,7 @@ static pcd_status normals_device(pcd_cloud* c, const pcd_normals_options& o, uin
     PCD_TRY(sc->nr_off.reserve(nleaves + 1));
     hipLaunchKernelGGL(k_normals_passes, dim3(div_up(nleaves + 1, 256)), dim3(256), 0, s, g, c->cell_start.p, P.sdx,
                        P.sdy, P.sdz, sc->nr_pass.p);
-    size_t tb = 0;
-    PCD_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, sc->nr_pass.p, sc->nr_off.p, 0u, nleaves + 1,
-                                        rocprim::plus<uint32_t>(), s));
-    PCD_TRY(sc->nr_tmp.reserve(tb));
-    PCD_HIP_TRY(rocprim::exclusive_scan(sc->nr_tmp.p, tb, sc->nr_pass.p, sc->nr_off.p, 0u, nleaves + 1,
-                                        rocprim::plus<uint32_t>(), s));
+    PCD_TRY(exclusive_sum(sc->nr_tmp, sc->nr_pass.p, sc->nr_off.p, 0u, nleaves + 1, s));
     PCD_HIP_TRY(hipMemcpyAsync(&nitems, sc->nr_off.p + nleaves, sizeof nitems, hipMemcpyDeviceToHost, s));
     PCD_HIP_TRY(hipStreamSynchronize(s));
     PCD_TRY(sc->nr_items.reserve(nitems));
@@ -508,7 +485,7 @@ pcd_status pcd_cloud_estimate_normals_device(pcd_cloud* c, const pcd_normals_opt
     pcd_normals_options o;
     PCD_TRY(normals_guards(c, opts, o));
     PCD_TRY(refuse_capture((hipStream_t)stream, "pcd_cloud_estimate_normals_device"));
-    PCD_TRY(normals_refuse_shards(c));
+    PCD_TRY(require_whole_cloud(c, "normal estimation", "the neighbourhoods", "estimate"));
     int have = 0;
     return normals_device(c, o, d_count, d_curvature, (hipStream_t)stream, &have);
   });
@@ -519,25 +496,20 @@ pcd_status pcd_cloud_estimate_normals(pcd_cloud* c, const pcd_normals_options* o
   return pcd::guard([&]() -> pcd_status {
     pcd_normals_options o;
     PCD_TRY(normals_guards(c, opts, o));
-    PCD_TRY(normals_refuse_shards(c));
+    PCD_TRY(require_whole_cloud(c, "normal estimation", "the neighbourhoods", "estimate"));
     if (info) std::memset(info, 0, sizeof *info);
     if (c->n == 0) return PCD_OK;
     QueryScratch* sc = scratch_of(c);
     hipStream_t s = nullptr;
     PCD_TRY(sc->nr_count.reserve(c->n));
     PCD_TRY(sc->nr_curv.reserve(c->n));
-    hipEvent_t ea = nullptr, eb = nullptr;
-    PCD_HIP_TRY(hipEventCreate(&ea));
-    if (hipEventCreate(&eb) != hipSuccess) { (void)hipEventDestroy(ea); set_error("hipEventCreate failed"); return PCD_ERR_HIP; }
-    (void)hipEventRecord(ea, s);
+    EventPair ev;
+    PCD_TRY(ev.create());
+    (void)ev.start(s);
     int have = 0;
     const pcd_status st = normals_device(c, o, sc->nr_count.p, sc->nr_curv.p, s, &have);
-    (void)hipEventRecord(eb, s);
-    const hipError_t es = hipEventSynchronize(eb);
     float ms = 0.f;
-    if (es == hipSuccess) (void)hipEventElapsedTime(&ms, ea, eb);
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
+    const hipError_t es = ev.stop_and_wait(s, &ms);
     PCD_TRY(st);
     PCD_HIP_TRY(es);
     if (count) PCD_HIP_TRY(hipMemcpy(count, sc->nr_count.p, c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));

@@ -21,11 +21,10 @@
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "common.h"
 #include "cloud.h"
 #include "grid.h"
+#include "prim.h"
 
 namespace pcd {
 
@@ -477,21 +476,15 @@ pcd_status build_submaps(pcd_proj* p) {
   hipLaunchKernelGGL(k_proj_keys, dim3(div_up(n, 256)), dim3(256), 0, s, c->pts4.p, n, o.submap_length,
                      o.submap_height, o.submap_width, r.lo[0], r.lo[1], r.lo[2], bx, by, bz, k0.p, v0.p);
   {
-    size_t tb = 0;
-    PCD_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, k0.p, k1.p, v0.p, v1.p, n, 0, bx + by + bz + 1, s));
     DevBuf<char> tmp;
-    PCD_TRY(tmp.reserve(tb));
-    PCD_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, k0.p, k1.p, v0.p, v1.p, n, 0, bx + by + bz + 1, s));
+    PCD_TRY(sort_pairs(tmp, k0.p, k1.p, v0.p, v1.p, n, 0, bx + by + bz + 1, s));
   }
   const uint64_t m = p->m;
   PCD_TRY(head.reserve(m)); PCD_TRY(sub_of.reserve(m));
   hipLaunchKernelGGL(k_proj_heads, dim3(div_up(m, 256)), dim3(256), 0, s, k1.p, m, head.p);
   {
-    size_t tb = 0;
-    PCD_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, head.p, sub_of.p, 0u, m, rocprim::plus<uint32_t>(), s));
     DevBuf<char> tmp;
-    PCD_TRY(tmp.reserve(tb));
-    PCD_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, head.p, sub_of.p, 0u, m, rocprim::plus<uint32_t>(), s));
+    PCD_TRY(exclusive_sum(tmp, head.p, sub_of.p, 0u, m, s));
   }
   uint32_t last_sub = 0, last_head = 0;
   PCD_HIP_TRY(hipMemcpy(&last_sub, sub_of.p + (m - 1), 4, hipMemcpyDeviceToHost));

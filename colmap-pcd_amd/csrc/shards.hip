@@ -213,9 +213,9 @@ pcd_status pcd_cloud_create_sharded(const float* xyz, const float* nrm, uint64_t
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
   key.clear(); key.shrink_to_fit();
 
-  pcd_cloud_shards* sh = new pcd_cloud_shards();
+  struct Destroy { void operator()(pcd_cloud_shards* p) const { pcd_cloud_shards_destroy(p); } };
+  std::unique_ptr<pcd_cloud_shards, Destroy> sh(new pcd_cloud_shards());   // destroyed by every failing return below
   sh->n_total = m;
-  auto fail = [&](pcd_status st) { pcd_cloud_shards_destroy(sh); return st; };
   std::vector<float> sx, sn;
   for (int s = 0; s < ndev; ++s) {
     const uint64_t r0 = m * (uint64_t)s / ndev, r1 = m * (uint64_t)(s + 1) / ndev, cnt = r1 - r0;
@@ -225,8 +225,7 @@ pcd_status pcd_cloud_create_sharded(const float* xyz, const float* nrm, uint64_t
     pcd_cloud_options so = o;
     so.layout = PCD_LAYOUT_XYZ_NRM; so.raw_lidar_frame = 0; so.device = devices[s]; so.index_base = 0; so.index_stride = 1;
     pcd_cloud* c = nullptr;
-    const pcd_status st = cloud_create_indexed(sx.data(), sn.data(), cnt, &so, order.data() + r0, m, &c);
-    if (st != PCD_OK) return fail(st);
+    PCD_TRY(cloud_create_indexed(sx.data(), sn.data(), cnt, &so, order.data() + r0, m, &c));
     sh->devices.push_back(devices[s]);
     sh->shard.push_back(c);
     sh->dev.push_back(new pcd_cloud_shards::Dev());
@@ -238,13 +237,11 @@ pcd_status pcd_cloud_create_sharded(const float* xyz, const float* nrm, uint64_t
     for (int k = 0; k < 3; ++k) sh->boxes.push_back(has ? info.bbox_hi[k] : -INFINITY);
   }
   for (int s = 0; s < ndev; ++s) {
-    if (hipSetDevice(devices[s]) != hipSuccess) return fail(PCD_ERR_HIP);
-    const pcd_status st = sh->dev[s]->boxes.reserve(sh->boxes.size());
-    if (st != PCD_OK) return fail(st);
-    if (hipMemcpy(sh->dev[s]->boxes.p, sh->boxes.data(), sh->boxes.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-      return fail(PCD_ERR_HIP);
+    PCD_HIP_TRY(hipSetDevice(devices[s]));
+    PCD_TRY(sh->dev[s]->boxes.reserve(sh->boxes.size()));
+    PCD_HIP_TRY(hipMemcpy(sh->dev[s]->boxes.p, sh->boxes.data(), sh->boxes.size() * sizeof(float), hipMemcpyHostToDevice));
   }
-  *out = sh;
+  *out = sh.release();
   return PCD_OK;
   });
 }

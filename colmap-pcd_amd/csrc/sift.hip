@@ -27,9 +27,8 @@
 #include <cstring>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "common.h"
+#include "prim.h"
 
 namespace pcd {
 
@@ -941,10 +940,7 @@ static pcd_status sift_device(const uint8_t* d_d1, int n1, const uint8_t* d_d2, 
                          d_count);
     } else {
       hipLaunchKernelGGL(k_sift_keep, dim3(div_up(n1, 256)), dim3(256), 0, s, d_m12, d_m21, n1, cross_check, sc.keep.p);
-      size_t tb = 0;
-      PCD_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, sc.keep.p, sc.pos.p, 0u, (size_t)n1, rocprim::plus<uint32_t>(), s));
-      PCD_TRY(sc.tmp.reserve(tb));
-      PCD_HIP_TRY(rocprim::exclusive_scan(sc.tmp.p, tb, sc.keep.p, sc.pos.p, 0u, (size_t)n1, rocprim::plus<uint32_t>(), s));
+      PCD_TRY(exclusive_sum(sc.tmp, sc.keep.p, sc.pos.p, 0u, (size_t)n1, s));
       hipLaunchKernelGGL(k_sift_compact, dim3(div_up(n1, 256)), dim3(256), 0, s, d_m12, sc.keep.p, sc.pos.p, n1,
                          d_matches, d_count);
     }

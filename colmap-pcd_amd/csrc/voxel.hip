@@ -18,13 +18,10 @@
 //                     group -- at a 3-5 cm leaf most voxels hold a handful of rows and a wavefront serves 8 of them.
 // Absent rows are +0.0, which changes no sum but the sign of a zero one; the epilogue adds +0.0 to every total so both
 // kernels give the same bits for the same rows.
-#include <cstring>  // rocprim's texture_cache_iterator.hpp needs memset declared first
-
-#include <rocprim/rocprim.hpp>
-
 #include <cmath>
 
 #include "cloud.h"
+#include "prim.h"
 
 namespace pcd {
 
@@ -277,12 +274,7 @@ __global__ void k_voxel_map(const uint32_t* __restrict__ vals, const uint32_t* _
 static pcd_status voxel_guards(const pcd_cloud* src, const pcd_voxel_options* opts, pcd_cloud** out,
                                pcd_voxel_options& o) {
   if (out) *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    (void)hipGetLastError();
-    set_error("no HIP device available; libpcdhip has no CPU fallback");
-    return PCD_ERR_NO_DEVICE;
-  }
+  PCD_TRY(require_any_device());
   PCD_REQUIRE(src, "null cloud");
   PCD_REQUIRE(out, "out is null");
   if (opts) o = *opts; else pcd_voxel_options_default(&o);
@@ -290,16 +282,6 @@ static pcd_status voxel_guards(const pcd_cloud* src, const pcd_voxel_options* op
   PCD_REQUIRE(o.min_points >= 0, "min_points < 0");
   PCD_REQUIRE(o.cell_size >= 0 && std::isfinite(o.cell_size), "cell_size");
   PCD_TRY(require_device(src->device));
-  return PCD_OK;
-}
-
-static pcd_status voxel_refuse_shards(const pcd_cloud* c) {
-  if (c->row_index.p || c->g2l.p || c->index_stride != 1 || c->index_base != 0) {
-    set_error("voxel downsampling needs ONE handle holding the whole cloud: the voxels of a shard "
-              "(pcd_cloud_create_sharded, index_stride / index_base) cross handle borders; downsample on one handle, "
-              "download, then shard");
-    return PCD_ERR_UNSUPPORTED;
-  }
   return PCD_OK;
 }
 
@@ -338,9 +320,9 @@ static pcd_status voxel_params(const pcd_cloud* src, const pcd_voxel_options& o,
   return PCD_OK;
 }
 
-// The device passes on stream s.  d_row_voxel may be NULL.  *out is created here and destroyed on failure.
+// The device passes on stream s.  d_row_voxel may be NULL.  c receives the new handle; it is complete only on PCD_OK.
 static pcd_status voxel_device(pcd_cloud* src, const pcd_voxel_options& o, uint32_t* d_row_voxel, hipStream_t s,
-                               pcd_cloud** out, pcd_voxel_info* info) {
+                               CloudPtr& c, pcd_voxel_info* info) {
   pcd_voxel_info vi;
   std::memset(&vi, 0, sizeof vi);
   PCD_HIP_TRY(hipSetDevice(src->device));
@@ -349,28 +331,27 @@ static pcd_status voxel_device(pcd_cloud* src, const pcd_voxel_options& o, uint3
   int key_bits = 1;
   if (m) PCD_TRY(voxel_params(src, o, P, vi, &key_bits));
 
-  pcd_cloud* c = nullptr;
-  auto fail = [&](pcd_status st) { pcd_cloud_destroy(c); return st; };
-  hipEvent_t ea = nullptr, eb = nullptr;
-  PCD_HIP_TRY(hipEventCreate(&ea));
-  if (hipEventCreate(&eb) != hipSuccess) { (void)hipEventDestroy(ea); set_error("hipEventCreate failed"); return PCD_ERR_HIP; }
-  (void)hipEventRecord(ea, s);
+  EventPair ev;
+  PCD_TRY(ev.create());
+  (void)ev.start(s);
 
   // everything between the two events; returns with c allocated and its rows written (asynchronously)
   auto passes = [&]() -> pcd_status {
     if (m == 0) {
       if (d_row_voxel && n) PCD_HIP_TRY(hipMemsetAsync(d_row_voxel, 0xFF, n * sizeof(uint32_t), s));   // no row has a voxel
-      return cloud_alloc_rows(src->device, 0, &c);
+      return cloud_alloc_rows(src->device, 0, c);
     }
-    // one allocation for the scratch of the call (a dozen hipMalloc / hipFree pairs cost more than the passes):
-    // sizes first -- rocprim's temporary storage is the largest of the sort's and the two scans'
-    size_t tb = 0, tb1 = 0, tb2 = 0;
-    PCD_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                          (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, key_bits, s));
-    PCD_HIP_TRY(rocprim::inclusive_scan(nullptr, tb1, (uint32_t*)nullptr, (uint32_t*)nullptr, m,
-                                        rocprim::plus<uint32_t>(), s));
-    PCD_HIP_TRY(rocprim::exclusive_scan(nullptr, tb2, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull,
-                                        m + 1, rocprim::plus<unsigned long long>(), s));
+    // One allocation for the scratch of the call (a dozen hipMalloc / hipFree pairs cost more than the passes), so the
+    // rocPRIM operations are bound here, before their arrays exist: a size query (storage == nullptr) reads no pointer
+    unsigned long long *k0 = nullptr, *k1 = nullptr, *kl = nullptr, *pos = nullptr, *cnt = nullptr;
+    uint32_t *v0 = nullptr, *v1 = nullptr, *flag = nullptr, *vid1 = nullptr, *seg = nullptr, *long_list = nullptr;
+    auto sort = [&](void* t, size_t& b) { return sort_pairs_at(t, b, k0, k1, v0, v1, n, 0, key_bits, s); };
+    auto scan_heads = [&](void* t, size_t& b) { return inclusive_sum_at(t, b, flag, vid1, m, s); };
+    auto scan_keep = [&](void* t, size_t& b) { return exclusive_sum_at(t, b, kl, pos, 0ull, m + 1, s); };
+    size_t tb = 0, tb1 = 0, tb2 = 0;   // temporary storage: the largest of the three
+    PCD_HIP_TRY(sort(nullptr, tb));
+    PCD_HIP_TRY(scan_heads(nullptr, tb1));
+    PCD_HIP_TRY(scan_keep(nullptr, tb2));
     tb = std::max(tb, std::max(tb1, tb2));
     size_t bytes = 0;
     auto carve = [&](size_t count, size_t elem) { const size_t at = bytes; bytes += (count * elem + 255) & ~(size_t)255; return at; };
@@ -381,10 +362,8 @@ static pcd_status voxel_device(pcd_cloud* src, const pcd_voxel_options& o, uint3
     PCD_TRY(arena.reserve(bytes));
     auto u64 = [&](size_t at) { return reinterpret_cast<unsigned long long*>(arena.p + at); };
     auto u32 = [&](size_t at) { return reinterpret_cast<uint32_t*>(arena.p + at); };
-    unsigned long long *const k0 = u64(o_k0), *const k1 = u64(o_k1), *const kl = u64(o_kl), *const pos = u64(o_pos),
-                       *const cnt = u64(o_cnt);
-    uint32_t *const v0 = u32(o_v0), *const v1 = u32(o_v1), *const flag = u32(o_flag), *const vid1 = u32(o_vid1),
-             *const seg = u32(o_seg), *const long_list = u32(o_long);
+    k0 = u64(o_k0); k1 = u64(o_k1); kl = u64(o_kl); pos = u64(o_pos); cnt = u64(o_cnt);
+    v0 = u32(o_v0); v1 = u32(o_v1); flag = u32(o_flag); vid1 = u32(o_vid1); seg = u32(o_seg); long_list = u32(o_long);
     char* const tmp = arena.p + o_tmp;
     PCD_HIP_TRY(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), s));
     {
@@ -393,17 +372,17 @@ static pcd_status voxel_device(pcd_cloud* src, const pcd_voxel_options& o, uint3
     }
     {
       ScopedKernelTimer tm("voxel_sort", s);
-      PCD_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, k0, k1, v0, v1, n, 0, key_bits, s));
+      PCD_HIP_TRY(sort(tmp, tb));
     }
     unsigned long long hc[4] = {0, 0, 0, 0}, hpos = 0;
     {
       ScopedKernelTimer tm("voxel_heads", s);
       hipLaunchKernelGGL(k_voxel_heads, dim3(div_up(m, 256)), dim3(256), 0, s, k1, m, flag);
-      PCD_HIP_TRY(rocprim::inclusive_scan(tmp, tb, flag, vid1, m, rocprim::plus<uint32_t>(), s));
+      PCD_HIP_TRY(scan_heads(tmp, tb));
       hipLaunchKernelGGL(k_voxel_segments, dim3(div_up(m, 256)), dim3(256), 0, s, flag, vid1, m, seg, cnt);
       hipLaunchKernelGGL(k_voxel_keep, dim3(div_up(m + 1, 256)), dim3(256), 0, s, seg, m, (uint32_t)o.min_points,
                          kl, cnt);
-      PCD_HIP_TRY(rocprim::exclusive_scan(tmp, tb, kl, pos, 0ull, m + 1, rocprim::plus<unsigned long long>(), s));
+      PCD_HIP_TRY(scan_keep(tmp, tb));
       PCD_HIP_TRY(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, s));
       PCD_HIP_TRY(hipMemcpyAsync(&hpos, pos + m, sizeof hpos, hipMemcpyDeviceToHost, s));
     }
@@ -413,7 +392,7 @@ static pcd_status voxel_device(pcd_cloud* src, const pcd_voxel_options& o, uint3
     vi.num_output = nout;
     vi.num_dropped_rows = hc[1];
     vi.max_points_per_voxel = (uint32_t)hc[2];
-    PCD_TRY(cloud_alloc_rows(src->device, nout, &c));
+    PCD_TRY(cloud_alloc_rows(src->device, nout, c));
     {
       ScopedKernelTimer tm("k_voxel_reduce", s);
       if (nlong) {
@@ -434,25 +413,18 @@ static pcd_status voxel_device(pcd_cloud* src, const pcd_voxel_options& o, uint3
     return PCD_OK;
   };
   const pcd_status st = passes();
-  (void)hipEventRecord(eb, s);
-  const hipError_t es = hipEventSynchronize(eb);
   float ms = 0.f;
-  if (es == hipSuccess) (void)hipEventElapsedTime(&ms, ea, eb);
-  (void)hipEventDestroy(ea);
-  (void)hipEventDestroy(eb);
-  if (st != PCD_OK) return fail(st);
-  if (es != hipSuccess) { set_error("voxel passes failed: %s", hipGetErrorString(es)); return fail(PCD_ERR_HIP); }
-  pcd_status sb;
+  const hipError_t es = ev.stop_and_wait(s, &ms);
+  PCD_TRY(st);
+  if (es != hipSuccess) { set_error("voxel passes failed: %s", hipGetErrorString(es)); return PCD_ERR_HIP; }
   {
     ScopedKernelTimer tm("voxel_build", s);
-    sb = cloud_build_index(c, o.cell_size, s);
+    PCD_TRY(cloud_build_index(c.get(), o.cell_size, s));
   }
-  if (sb != PCD_OK) return fail(sb);
   vi.num_input = m;
   vi.ms = (double)ms;
   vi.build_ms = c->build_ms;
   if (info) *info = vi;
-  *out = c;
   return PCD_OK;
 }
 
@@ -474,8 +446,11 @@ pcd_status pcd_cloud_voxel_downsample_device(pcd_cloud* src, const pcd_voxel_opt
     pcd_voxel_options o;
     PCD_TRY(voxel_guards(src, opts, out, o));
     PCD_TRY(refuse_capture((hipStream_t)stream, "pcd_cloud_voxel_downsample_device"));
-    PCD_TRY(voxel_refuse_shards(src));
-    return voxel_device(src, o, d_row_voxel, (hipStream_t)stream, out, info);
+    PCD_TRY(require_whole_cloud(src, "voxel downsampling", "the voxels", "downsample"));
+    CloudPtr c;
+    PCD_TRY(voxel_device(src, o, d_row_voxel, (hipStream_t)stream, c, info));
+    *out = c.release();
+    return PCD_OK;
   });
 }
 
@@ -484,18 +459,18 @@ pcd_status pcd_cloud_voxel_downsample(pcd_cloud* src, const pcd_voxel_options* o
   return pcd::guard([&]() -> pcd_status {
     pcd_voxel_options o;
     PCD_TRY(voxel_guards(src, opts, out, o));
-    PCD_TRY(voxel_refuse_shards(src));
+    PCD_TRY(require_whole_cloud(src, "voxel downsampling", "the voxels", "downsample"));
     PCD_HIP_TRY(hipSetDevice(src->device));
     DevBuf<uint32_t> d_map;
     const bool want = row_voxel && src->n;
     if (want) PCD_TRY(d_map.reserve(src->n));
-    PCD_TRY(voxel_device(src, o, want ? d_map.p : nullptr, nullptr, out, info));
+    CloudPtr c;
+    PCD_TRY(voxel_device(src, o, want ? d_map.p : nullptr, nullptr, c, info));
     if (want && hipMemcpy(row_voxel, d_map.p, src->n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
       set_error("copy of row_voxel failed");
-      pcd_cloud_destroy(*out);
-      *out = nullptr;
       return PCD_ERR_HIP;
     }
+    *out = c.release();
     return PCD_OK;
   });
 }

@@ -90,7 +90,7 @@ def budget_min_cell(ext):
 
 
 def effective_cell_size(lo, hi, m, user_h):
-    """the cell size build_grid settles on for a user value > 0, as float32"""
+    """the cell size choose_cell_size (cloud.hip) settles on for a user value > 0, as float32"""
     assert user_h > 0
     user_h = np.float32(user_h)
     ext = [float(np.float64(np.float32(hi[d])) - np.float64(np.float32(lo[d]))) for d in range(3)]

@@ -33,7 +33,7 @@ def _cells_cloud(cells, h, seed, per=3):
 
 
 def _child_counts(xyz, h):
-    """numpy restatement of the lattice (cloud.hip build_grid with a user cell size): per real level above the
+    """numpy restatement of the lattice (cloud.hip build_lattice with a user cell size): per real level above the
     leaves the sorted list of the number of occupied children of every occupied node, top level last; and the number
     of occupied nodes of the top real level (= the children of the virtual top)"""
     lo = xyz.min(0)

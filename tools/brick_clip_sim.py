@@ -44,7 +44,7 @@ RULES = ("noclip", "own", "class", "first", "fullest", "near", "floor")
 
 
 def grid_params(p, cell_size=0.0):
-    """cloud.hip build_grid / set_dims: cell size (given, or the iteration towards 24 points per occupied cell)"""
+    """cloud.hip choose_cell_size / set_dims: cell size (given, or the iteration towards 24 points per occupied cell)"""
     lo, hi = p.min(0), p.max(0)
     m = len(p)
     ext = hi.astype(np.float64) - lo.astype(np.float64)

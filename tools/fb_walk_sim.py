@@ -36,7 +36,7 @@ F = np.float32
 
 
 def build_grid(p):
-    """cloud.hip build_grid: cell size iteration and set_dims, float32 binning."""
+    """cloud.hip choose_cell_size: cell size iteration and set_dims, float32 binning."""
     lo, hi = p.min(0), p.max(0)
     m = len(p)
     ext = hi.astype(np.float64) - lo.astype(np.float64)
