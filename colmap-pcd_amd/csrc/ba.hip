@@ -4,8 +4,10 @@
 // (AddImageToProblem, AddImageInSphereToProblem, AddPointToProblem, AddLidarToProblem, ParameterizeCameras/Points):
 // every residual block's CostFunction::Evaluate (base/cost_functions.h:49-141, :150-241, :256-370), the loss correction
 // (optim/bundle_adjustment.cc:53-68) and the manifold projection (base/cost_functions.h:610-627), then J^T J / J^T r
-// block accumulation.  The device solver on these blocks (point elimination, PCG, LM loop) is ba_solve.hip; it reaches
-// this unit through pcd_ba_evaluate_device and ba_normal_equations (ba_handle.h) only.
+// block accumulation.  This unit holds the evaluation kernels and the entry points that launch them (parameter access,
+// pcd_ba_evaluate*, observation errors, track filters); the handle and the layouts they read are made in ba_build.hip
+// (pcd_ba_create), sized from ba_handle.h.  The device solver on these blocks (point elimination, PCG, LM loop) is
+// ba_solve.hip; it reaches this unit through pcd_ba_evaluate_device and ba_normal_equations (ba_handle.h) only.
 //
 // Kernels (all fp64, memory/latency-bound: ~300 flop per ~60-200 B per observation):
 //   k_ba_points  thread = 3D point (track).  Tracks are processed in order of track length and their observations are
@@ -27,7 +29,6 @@
 // MODEL = -1 switches per observation.
 #include <algorithm>
 #include <cmath>
-#include <memory>
 
 #include "ba_cam_jac.h"
 #include "ba_handle.h"
@@ -368,7 +369,6 @@ __global__ __launch_bounds__(256) void k_ba_cost(BaDev d, double* __restrict__ c
   }
   if (threadIdx.x == 0) cost_partial[blockIdx.x] = s_c[0];
 }
-constexpr unsigned kCostBlocks = 1u << 20;   // cap of the cost pass's grid (256 M residual blocks in one sweep)
 
 // One workgroup, bound by the latency of its loads: 1024 threads with eight independent accumulators each keep 8192
 // loads in flight per sweep (the cost pass of the bench scene leaves ~23 k partials: three sweeps instead of 23 with 256
@@ -401,11 +401,10 @@ __global__ __launch_bounds__(kSumThreads) void k_sum_partials(const double* __re
 // in registers anyway (no second sweep).  When the caller's observations are image-major (the order
 // AddImageToProblem creates them in, optim/bundle_adjustment.cc:814-919) the 144-B blocks of consecutive
 // lanes are adjacent in memory.
-// Work item = one SEGMENT of <= kImgSeg observations of an image (an image per workgroup left a quarter of the chip
-// idle on a 1000-image scene and nearly all of it on a 25-image one); the 27 partial sums of a segment go to
-// `partial` and k_ba_images_reduce adds the segments of an image in ascending order: still no atomics, still
+// Work item = one SEGMENT of <= kImgSeg (ba_handle.h) observations of an image (an image per workgroup left a quarter
+// of the chip idle on a 1000-image scene and nearly all of it on a 25-image one); the 27 partial sums of a segment go
+// to `partial` and k_ba_images_reduce adds the segments of an image in ascending order: still no atomics, still
 // bitwise reproducible.
-constexpr uint32_t kImgSeg = 1024;
 // The 27 sums of a segment are the upper triangle and the last column of A^T A, A = [J | r]: 7 columns and two rows
 // per observation, a small-N GEMM.  They are summed on the fp64 matrix pipe (v_mfma_f64_16x16x4_f64) instead of in
 // 27 per-lane fp64 accumulators: a wavefront's sums live in one 4-double accumulator (8 VGPRs instead of 54, held
@@ -692,19 +691,15 @@ __device__ __forceinline__ void cam_accumulate(const BaDev& d, int im, double* _
     const double sr = sqrt(rho1);
     double A[2][NA];
     {  // camera columns: same normalised coordinates as reproj_eval
-      const double* pose = d.poses + 7 * (size_t)im;
-      const double w = pose[0], a = pose[1], bq = pose[2], c = pose[3];
-      const double cx = bq * X[2] - c * X[1], cy = c * X[0] - a * X[2], cz = a * X[1] - bq * X[0];
-      const double ux = 2.0 * cx, uy = 2.0 * cy, uz = 2.0 * cz;
-      const double Px = X[0] + w * ux + (bq * uz - c * uy) + pose[4];
-      const double Py = X[1] + w * uy + (c * ux - a * uz) + pose[5];
-      const double Pz = X[2] + w * uz + (a * uy - bq * ux) + pose[6];
-      const double iz = 1.0 / Pz;
+      double pose[7], P[3];
+      load_pose(d, im, pose);
+      pose_transform(pose, pose + 4, X, P);
+      const double iz = 1.0 / P[2];
       double Jc[2 * K];
 #pragma unroll
       for (int k = 0; k < 2 * K; ++k) Jc[k] = 0.0;
-      if (MODEL >= 0) cam_param_jacobian<(MODEL >= 0 ? MODEL : 0)>(cam, Px * iz, Py * iz, Jc, K);
-      else cam_param_jacobian_any(model, cam, Px * iz, Py * iz, Jc, K);
+      if (MODEL >= 0) cam_param_jacobian<(MODEL >= 0 ? MODEL : 0)>(cam, P[0] * iz, P[1] * iz, Jc, K);
+      else cam_param_jacobian_any(model, cam, P[0] * iz, P[1] * iz, Jc, K);
       const int kn = MODEL >= 0 ? K : cam_num_params(model);
 #pragma unroll
       for (int k = 0; k < K; ++k) {
@@ -823,20 +818,16 @@ __global__ __launch_bounds__(256) void k_ba_cam_w(BaDev d, double* __restrict__ 
       loss_eval(d.loss_type, d.loss_scale, b.r[0] * b.r[0] + b.r[1] * b.r[1], rho0, rho1);
       double Jq[8], Jt[6], JX[6];
       reproj_jacobians(b, Jq, Jt, JX);
-      const double* pose = d.poses + 7 * (size_t)im;
-      const double w = pose[0], a = pose[1], bq = pose[2], c = pose[3];
-      const double cx = bq * X[2] - c * X[1], cy = c * X[0] - a * X[2], cz = a * X[1] - bq * X[0];
-      const double ux = 2.0 * cx, uy = 2.0 * cy, uz = 2.0 * cz;
-      const double Px = X[0] + w * ux + (bq * uz - c * uy) + pose[4];
-      const double Py = X[1] + w * uy + (c * ux - a * uz) + pose[5];
-      const double Pz = X[2] + w * uz + (a * uy - bq * ux) + pose[6];
-      const double iz = 1.0 / Pz;
+      double pose[7], P[3];
+      load_pose(d, im, pose);
+      pose_transform(pose, pose + 4, X, P);
+      const double iz = 1.0 / P[2];
       const int model = MODEL >= 0 ? MODEL : d.cam_model[cm];
       double Jc[2 * S];
 #pragma unroll
       for (int k = 0; k < 2 * S; ++k) Jc[k] = 0.0;
-      if (MODEL >= 0) cam_param_jacobian<(MODEL >= 0 ? MODEL : 0)>(d.cam_params + d.cam_off[cm], Px * iz, Py * iz, Jc, S);
-      else cam_param_jacobian_any(model, d.cam_params + d.cam_off[cm], Px * iz, Py * iz, Jc, S);
+      if (MODEL >= 0) cam_param_jacobian<(MODEL >= 0 ? MODEL : 0)>(d.cam_params + d.cam_off[cm], P[0] * iz, P[1] * iz, Jc, S);
+      else cam_param_jacobian_any(model, d.cam_params + d.cam_off[cm], P[0] * iz, P[1] * iz, Jc, S);
       const int kn = cam_num_params(model);
 #pragma unroll
       for (int k = 0; k < S; ++k) {
@@ -851,8 +842,9 @@ __global__ __launch_bounds__(256) void k_ba_cam_w(BaDev d, double* __restrict__ 
 }
 
 // ---------------------------------------------------------------- raw ------
-// k_ba_raw / k_ba_raw_compact / k_ba_obs_errors come as pairs: the kernel of the generic path keeps its name and
-// signature, its _sc twin is the same body with eval_block's SHARED flag (own register allocation, no branch inside).
+// k_ba_raw / k_ba_raw_compact / k_ba_obs_errors take BaCam's SHARED flag as a template argument, like k_ba_points and
+// k_ba_cost (own register allocation per instantiation, no branch inside).  k_ba_raw alone keeps its body in a device
+// function: written into the kernel, the same statements compile to 116-142 VGPRs instead of 96-100 (compiled-in models).
 template <int MODEL, bool SHARED>
 __device__ __forceinline__ void ba_raw_body(const BaDev& d, double* __restrict__ residuals, double* __restrict__ Jq_o,
                                             double* __restrict__ Jt_o, double* __restrict__ JX_o,
@@ -919,19 +911,12 @@ __device__ __forceinline__ void ba_raw_body(const BaDev& d, double* __restrict__
   if (JX_o) wave_store_rows<6>(JX_o, o_wave, cnt, JX, s_rows[wave]);
   if (W_o) wave_store_rows<18>(W_o, o_wave, cnt, Wb, s_rows[wave]);
 }
-template <int MODEL>
+template <int MODEL, bool SHARED>
 __global__ __launch_bounds__(256) void k_ba_raw(BaDev d, double* __restrict__ residuals, double* __restrict__ Jq_o,
                                                 double* __restrict__ Jt_o, double* __restrict__ JX_o,
                                                 double* __restrict__ W_o) {
   __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 18];
-  ba_raw_body<MODEL, false>(d, residuals, Jq_o, Jt_o, JX_o, W_o, s_rows);
-}
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_ba_raw_sc(BaDev d, double* __restrict__ residuals, double* __restrict__ Jq_o,
-                                                   double* __restrict__ Jt_o, double* __restrict__ JX_o,
-                                                   double* __restrict__ W_o) {
-  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 18];
-  ba_raw_body<MODEL, true>(d, residuals, Jq_o, Jt_o, JX_o, W_o, s_rows);
+  ba_raw_body<MODEL, SHARED>(d, residuals, Jq_o, Jt_o, JX_o, W_o, s_rows);
 }
 
 // Camera-parameter block of every reprojection residual (2 x K, row stride PCD_CAM_JAC_STRIDE).
@@ -943,20 +928,15 @@ __global__ __launch_bounds__(256) void k_ba_cam_jac(BaDev d, double* __restrict_
   const double* pose = d.poses + 7 * (size_t)im;
   const double* Xp = d.points + 3 * (size_t)pt;
   const double X[3] = {Xp[0], Xp[1], Xp[2]};
-  const double w = pose[0], a = pose[1], bq = pose[2], c = pose[3];
-  // same rotation polynomial as reproj_eval
-  const double cx = bq * X[2] - c * X[1], cy = c * X[0] - a * X[2], cz = a * X[1] - bq * X[0];
-  const double ux = 2.0 * cx, uy = 2.0 * cy, uz = 2.0 * cz;
-  const double Px = X[0] + w * ux + (bq * uz - c * uy) + pose[4];
-  const double Py = X[1] + w * uy + (c * ux - a * uz) + pose[5];
-  const double Pz = X[2] + w * uz + (a * uy - bq * ux) + pose[6];
-  const double iz = 1.0 / Pz;
+  double P[3];
+  pose_transform(pose, pose + 4, X, P);
+  const double iz = 1.0 / P[2];
   const int cm = d.image_cam[im];
   double J[2 * PCD_CAM_JAC_STRIDE];
 #pragma unroll
   for (int k = 0; k < 2 * PCD_CAM_JAC_STRIDE; ++k) J[k] = 0.0;
-  if (MODEL >= 0) cam_param_jacobian<(MODEL >= 0 ? MODEL : 0)>(d.cam_params + d.cam_off[cm], Px * iz, Py * iz, J, PCD_CAM_JAC_STRIDE);
-  else cam_param_jacobian_any(d.cam_model[cm], d.cam_params + d.cam_off[cm], Px * iz, Py * iz, J, PCD_CAM_JAC_STRIDE);
+  if (MODEL >= 0) cam_param_jacobian<(MODEL >= 0 ? MODEL : 0)>(d.cam_params + d.cam_off[cm], P[0] * iz, P[1] * iz, J, PCD_CAM_JAC_STRIDE);
+  else cam_param_jacobian_any(d.cam_model[cm], d.cam_params + d.cam_off[cm], P[0] * iz, P[1] * iz, J, PCD_CAM_JAC_STRIDE);
   double* out = Jc_o + 2 * PCD_CAM_JAC_STRIDE * o;
 #pragma unroll
   for (int k = 0; k < 2 * PCD_CAM_JAC_STRIDE; ++k) out[k] = J[k];
@@ -969,7 +949,8 @@ __global__ __launch_bounds__(256) void k_ba_cam_jac(BaDev d, double* __restrict_
 // (tests/test_ceres_compact_isa.py holds the register count against k_ba_raw's).  A constant-pose observation keeps
 // its true M: its jac_X needs it.
 template <int MODEL, bool SHARED>
-__device__ __forceinline__ void ba_raw_compact_body(const BaDev& d, double* __restrict__ rec_o, double (*s_rows)[64 * 8]) {
+__global__ __launch_bounds__(256) void k_ba_raw_compact(BaDev d, double* __restrict__ rec_o) {
+  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 8];
   const int wave = threadIdx.x >> 6;
   const uint64_t o = blockIdx.x * (uint64_t)256 + threadIdx.x;
   const uint64_t o_wave = blockIdx.x * (uint64_t)256 + wave * 64;
@@ -994,16 +975,6 @@ __device__ __forceinline__ void ba_raw_compact_body(const BaDev& d, double* __re
   }
   wave_store_rows<8>(rec_o, o_wave, cnt, rec, s_rows[wave]);   // 4 KiB of consecutive addresses per wavefront
 }
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_ba_raw_compact(BaDev d, double* __restrict__ rec_o) {
-  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 8];
-  ba_raw_compact_body<MODEL, false>(d, rec_o, s_rows);
-}
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_ba_raw_compact_sc(BaDev d, double* __restrict__ rec_o) {
-  __shared__ __attribute__((aligned(16))) double s_rows[4][64 * 8];
-  ba_raw_compact_body<MODEL, true>(d, rec_o, s_rows);
-}
 
 // Camera blocks for the compact route: [O][2][PCD_CAM_JAC_STRIDE] -> [O][2][cs], cs = the widest camera of the handle
 // (columns >= K of a narrower camera are the zeros k_ba_cam_jac wrote).  thread = output double: consecutive lanes
@@ -1022,7 +993,7 @@ __global__ __launch_bounds__(256) void k_ba_pack_cam_jac(const double* __restric
 //            base/pose.cc QuaternionRotatePoint does; DBL_MAX when the point is not in front of the camera)
 //   depth  = P.z (FilterObservationsWithNegativeDepth, base/reconstruction.cc:837-855, tests it against eps)
 template <int MODEL, bool SHARED>
-__device__ __forceinline__ void ba_obs_errors_body(const BaDev& d, double* __restrict__ sq_err, double* __restrict__ depth) {
+__global__ __launch_bounds__(256) void k_ba_obs_errors(BaDev d, double* __restrict__ sq_err, double* __restrict__ depth) {
   const uint64_t o = blockIdx.x * (uint64_t)256 + threadIdx.x;
   if (o >= d.O) return;
   const int im = d.obs_image[o], pt = d.obs_point[o];
@@ -1032,28 +1003,17 @@ __device__ __forceinline__ void ba_obs_errors_body(const BaDev& d, double* __res
   if (n == 0.0) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; }
   else { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; }
   const double X[3] = {d.points[3 * (size_t)pt], d.points[3 * (size_t)pt + 1], d.points[3 * (size_t)pt + 2]};
-  const double cx = q[2] * X[2] - q[3] * X[1], cy = q[3] * X[0] - q[1] * X[2], cz = q[1] * X[1] - q[2] * X[0];
-  const double ux = 2.0 * cx, uy = 2.0 * cy, uz = 2.0 * cz;
-  const double Px = X[0] + q[0] * ux + (q[2] * uz - q[3] * uy) + pose[4];
-  const double Py = X[1] + q[0] * uy + (q[3] * ux - q[1] * uz) + pose[5];
-  const double Pz = X[2] + q[0] * uz + (q[1] * uy - q[2] * ux) + pose[6];
-  if (depth) depth[o] = Pz;
+  double P[3];
+  pose_transform(q, pose + 4, X, P);
+  if (depth) depth[o] = P[2];
   if (!sq_err) return;
-  if (Pz < 2.220446049250313e-16) { sq_err[o] = 1.7976931348623157e308; return; }
+  if (P[2] < 2.220446049250313e-16) { sq_err[o] = 1.7976931348623157e308; return; }
   BaCam<MODEL, SHARED> cam(d);
   cam.of_image(d, im);
   D2 x, y;
-  world_to_image_d2(cam.model, cam.params(), Px / Pz, Py / Pz, x, y);
+  world_to_image_d2(cam.model, cam.params(), P[0] / P[2], P[1] / P[2], x, y);
   const double dx = x.a - d.obs_xy[2 * o], dy = y.a - d.obs_xy[2 * o + 1];
   sq_err[o] = dx * dx + dy * dy;
-}
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_ba_obs_errors(BaDev d, double* __restrict__ sq_err, double* __restrict__ depth) {
-  ba_obs_errors_body<MODEL, false>(d, sq_err, depth);
-}
-template <int MODEL>
-__global__ __launch_bounds__(256) void k_ba_obs_errors_sc(BaDev d, double* __restrict__ sq_err, double* __restrict__ depth) {
-  ba_obs_errors_body<MODEL, true>(d, sq_err, depth);
 }
 
 __global__ __launch_bounds__(256) void k_ba_lidar_raw(BaDev d, double* __restrict__ residuals, double* __restrict__ JL) {
@@ -1162,56 +1122,6 @@ __global__ void k_pack_rows(const double* __restrict__ in, const uint32_t* __res
 
 using namespace pcd;
 
-// ---- derived layouts, filled on the device from the uploaded observation arrays -----------------------------
-// The host only sorts indices (counting sorts); the 16-byte observation payloads never make a second trip over PCIe
-// and are never gathered by a host loop (pcd_ba_create: 220 -> see DESIGN 4.3 for the bench scene).
-// sliced ELL: thread = (slice, lane): track p = order[slice*64 + lane], its j-th observation goes to slot
-// slice_start[slice] + 64 j + lane
-__global__ void k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __restrict__ slice_start,
-                               const uint32_t* __restrict__ pt_start, const uint32_t* __restrict__ pt_list,
-                               const int* __restrict__ obs_image, const double* __restrict__ obs_xy, int nslices,
-                               int* __restrict__ sell_img, double* __restrict__ sell_xy) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int slice = t >> 6, lane = t & 63;
-  if (slice >= nslices) return;
-  const uint32_t s0 = slice_start[slice], width = (slice_start[slice + 1] - s0) >> 6;
-  const int p = order[t];
-  const uint32_t b = p >= 0 ? pt_start[p] : 0u, len = p >= 0 ? pt_start[p + 1] - b : 0u;
-  for (uint32_t j = 0; j < width; ++j) {
-    const size_t slot = (size_t)s0 + 64 * (size_t)j + lane;
-    if (j < len) {
-      const uint32_t o = pt_list[b + j];
-      sell_img[slot] = obs_image[o];
-      const double2 xy = *reinterpret_cast<const double2*>(obs_xy + 2 * (size_t)o);
-      *reinterpret_cast<double2*>(sell_xy + 2 * slot) = xy;
-    } else {
-      sell_img[slot] = -1;   // padding of a shorter track
-      *reinterpret_cast<double2*>(sell_xy + 2 * slot) = make_double2(0.0, 0.0);
-    }
-  }
-}
-// image-major copies: e-th observation of the image-major order = observation img_obs[e] of the caller's order
-__global__ void k_ba_fill_image_major(const uint32_t* __restrict__ img_obs, const int* __restrict__ obs_point,
-                                      const double* __restrict__ obs_xy, uint64_t O, int* __restrict__ img_pt,
-                                      double* __restrict__ img_xy) {
-  const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-  if (e >= O) return;
-  const uint32_t o = img_obs[e];
-  img_pt[e] = obs_point[o];
-  *reinterpret_cast<double2*>(img_xy + 2 * e) = *reinterpret_cast<const double2*>(obs_xy + 2 * (size_t)o);
-}
-
-// stable counting sort of element ids by key -> CSR (start[nkeys+1], list[n])
-static void build_csr(const int32_t* key, uint64_t n, int nkeys, std::vector<uint32_t>& start,
-                      std::vector<uint32_t>& list) {
-  start.assign((size_t)nkeys + 1, 0);
-  for (uint64_t i = 0; i < n; ++i) start[(size_t)key[i] + 1]++;
-  for (int k = 0; k < nkeys; ++k) start[k + 1] += start[k];
-  list.resize(n);
-  std::vector<uint32_t> cur(start.begin(), start.end() - 1);
-  for (uint64_t i = 0; i < n; ++i) list[cur[key[i]]++] = (uint32_t)i;
-}
-
 // kernel dispatch on the (uniform) camera model; the five common models are compiled in
 #define PCD_BA_DISPATCH(MODELVAR, ...)                            \
   switch (MODELVAR) {                                             \
@@ -1227,14 +1137,6 @@ static void build_csr(const int32_t* key, uint64_t n, int nkeys, std::vector<uin
 #define PCD_BA_DISPATCH_CAM(MODELVAR, SHAREDVAR, ...)                                  \
   if (SHAREDVAR) { constexpr bool SH = true; PCD_BA_DISPATCH(MODELVAR, __VA_ARGS__) }  \
   else { constexpr bool SH = false; PCD_BA_DISPATCH(MODELVAR, __VA_ARGS__) }
-
-// Grid of the kernel that writes cost_partial[blockIdx.x]: k_ba_points takes two 64-track slices per workgroup,
-// k_ba_cost sweeps the residual blocks with a capped grid.  pcd_ba_create sizes cost_partial from the SAME function
-// (round 2 sized it for an older k_ba_points grid: scenes with O + L < ~2 P wrote past the end).
-static unsigned cost_blocks(const pcd_ba* b, bool want_blocks) {
-  return want_blocks ? std::max(1u, div_up((size_t)b->nslices, 2))
-                     : std::max(1u, std::min(kCostBlocks, div_up(b->O + b->L, 256)));
-}
 
 // One block of a blocks route's pinned result: n doubles from src to the cursor h, which moves past them; slot points
 // at the copy (nullptr when the block is empty)
@@ -1274,180 +1176,6 @@ pcd_status pcd::ba_normal_equations(pcd_ba* b, const uint32_t* w_order, double* 
 }
 
 extern "C" {
-
-pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
-  return pcd::guard([&]() -> pcd_status {
-  PCD_REQUIRE(d && out, "null pointer");
-  *out = nullptr;
-  PCD_REQUIRE(d->num_cameras > 0 && d->cam_model && d->cam_param_offset && d->cam_params, "cameras");
-  PCD_REQUIRE(d->num_images > 0 && d->poses && d->image_camera, "images");
-  PCD_REQUIRE(d->num_points > 0 && d->points, "points");
-  PCD_REQUIRE(d->num_obs == 0 || (d->obs_image && d->obs_point && d->obs_xy), "observations");
-  PCD_REQUIRE(d->num_lidar == 0 || (d->lidar_point && d->lidar_abcd && d->lidar_weight), "lidar terms");
-  PCD_REQUIRE(d->loss_type >= 0 && d->loss_type <= 2, "loss_type");
-  PCD_REQUIRE(d->loss_type == PCD_LOSS_TRIVIAL || d->loss_scale > 0, "loss_scale");
-  PCD_REQUIRE(d->num_obs < 0xFFFFFFF0ull && d->num_lidar < 0xFFFFFFF0ull, "too many residual blocks");
-  for (int c = 0; c < d->num_cameras; ++c) {
-    const int k = pcd_camera_num_params(d->cam_model[c]);
-    PCD_REQUIRE(k > 0, "unknown camera model id");  // reference: std::domain_error, camera_models.h:140
-    PCD_REQUIRE(d->cam_param_offset[c] >= 0 && (uint64_t)d->cam_param_offset[c] + k <= d->cam_params_len,
-                "camera parameter offsets");
-  }
-  for (int i = 0; i < d->num_images; ++i)
-    PCD_REQUIRE(d->image_camera[i] >= 0 && d->image_camera[i] < d->num_cameras, "image_camera out of range");
-  for (uint64_t o = 0; o < d->num_obs; ++o) {
-    PCD_REQUIRE(d->obs_image[o] >= 0 && d->obs_image[o] < d->num_images, "obs_image out of range");
-    PCD_REQUIRE(d->obs_point[o] >= 0 && d->obs_point[o] < d->num_points, "obs_point out of range");
-  }
-  for (uint64_t l = 0; l < d->num_lidar; ++l)
-    PCD_REQUIRE(d->lidar_point[l] >= 0 && d->lidar_point[l] < d->num_points, "lidar_point out of range");
-  PCD_TRY(require_device(d->device));
-
-  pcd_ba* b = new pcd_ba();
-  b->device = d->device;
-  b->C = d->num_cameras; b->I = d->num_images; b->P = d->num_points; b->O = d->num_obs; b->L = d->num_lidar;
-  b->loss_type = d->loss_type; b->loss_scale = d->loss_scale;
-  b->cam_params_len = d->cam_params_len;
-  for (int c = 0; c < d->num_cameras; ++c) b->cam_stride = std::max(b->cam_stride, cam_num_params(d->cam_model[c]));
-  b->uniform_model = d->cam_model[0];
-  for (int c = 1; c < d->num_cameras; ++c)
-    if (d->cam_model[c] != b->uniform_model) b->uniform_model = -1;
-  b->shared_cam = d->image_camera[0];
-  for (int i = 1; i < d->num_images; ++i)
-    if (d->image_camera[i] != b->shared_cam) b->shared_cam = -1;
-  struct Destroy { void operator()(pcd_ba* p) const { pcd_ba_destroy(p); } };
-  std::unique_ptr<pcd_ba, Destroy> owner(b);   // destroys the handle on every failing return below
-#define UP(buf, src, n) PCD_TRY(upload(b->buf, src, (size_t)(n)))
-  UP(cam_model, d->cam_model, b->C); UP(cam_off, d->cam_param_offset, b->C); UP(cam_params, d->cam_params, d->cam_params_len);
-  UP(poses, d->poses, 7 * (size_t)b->I); UP(image_cam, d->image_camera, b->I);
-  UP(points, d->points, 3 * (size_t)b->P);
-  UP(obs_image, d->obs_image, b->O); UP(obs_point, d->obs_point, b->O); UP(obs_xy, d->obs_xy, 2 * b->O);
-  UP(lidar_point, d->lidar_point, b->L); UP(lidar_abcd, d->lidar_abcd, 4 * b->L); UP(lidar_w, d->lidar_weight, b->L);
-  if (d->image_const_pose) { b->has_cpose = true; UP(image_const_pose, d->image_const_pose, b->I); }
-  if (d->image_const_tvec) { b->has_ctvec = true; UP(image_const_tvec, d->image_const_tvec, b->I); }
-  if (d->point_const) { b->has_cpt = true; UP(point_const, d->point_const, b->P); }
-  if (d->camera_refine) { b->has_refine = true; UP(cam_refine, d->camera_refine, d->cam_params_len); }
-  for (uint64_t k = 0; d->camera_refine && k < d->cam_params_len; ++k) b->refines_intrinsics |= d->camera_refine[k] != 0;
-
-  std::vector<uint32_t> st, li;
-  std::vector<int> order;   // thread of k_ba_points -> point
-  // ---- per-track sliced ELL in order of track length ----
-  build_csr(d->obs_point, b->O, b->P, st, li);
-  {
-    // tracks in ascending order of length, ties in ascending point id: a counting sort (lengths are small numbers)
-    uint32_t maxlen = 0;
-    for (int p = 0; p < b->P; ++p) maxlen = std::max(maxlen, st[p + 1] - st[p]);
-    std::vector<uint32_t> bucket((size_t)maxlen + 2, 0);
-    for (int p = 0; p < b->P; ++p) bucket[(size_t)(st[p + 1] - st[p]) + 1]++;
-    for (size_t k = 1; k < bucket.size(); ++k) bucket[k] += bucket[k - 1];
-    const int nslices = (b->P + 63) / 64;
-    b->nslices = nslices;
-    order.assign((size_t)nslices * 64, -1);
-    for (int p = 0; p < b->P; ++p) order[bucket[st[p + 1] - st[p]]++] = p;
-    std::vector<uint32_t> slice_start(nslices + 1, 0);
-    for (int s = 0; s < nslices; ++s) {
-      // ascending lengths: the longest track of a slice is its last real one
-      uint32_t mx = 0;
-      for (int l = 63; l >= 0; --l) {
-        const int p = order[(size_t)s * 64 + l];
-        if (p >= 0) { mx = st[p + 1] - st[p]; break; }
-      }
-      slice_start[s + 1] = slice_start[s] + mx * 64;
-    }
-    const size_t nslots = slice_start[nslices];
-    UP(pt_order, order.data(), order.size());
-    UP(slice_start, slice_start.data(), slice_start.size());
-    UP(pt_obs_start, st.data(), st.size()); UP(pt_obs_list, li.data(), li.size());   // kept: pcd_ba_filter_tracks
-    // the ELL fill borrows the buffers of the lidar CSR uploaded right after
-    UP(pt_lidar_start, st.data(), st.size()); UP(pt_lidar_list, li.data(), li.size());
-    PCD_TRY(b->sell_img.reserve(std::max<size_t>(nslots, 1)));
-    PCD_TRY(b->sell_xy.reserve(std::max<size_t>(2 * nslots, 2)));
-    if (nslots)
-      hipLaunchKernelGGL(k_ba_fill_sell, dim3(div_up((size_t)nslices * 64, 256)), dim3(256), 0, nullptr, b->pt_order.p,
-                         b->slice_start.p, b->pt_lidar_start.p, b->pt_lidar_list.p, b->obs_image.p, b->obs_xy.p, nslices,
-                         b->sell_img.p, b->sell_xy.p);
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
-      set_error("pcd_ba_create: filling the per-track layout failed");
-      return PCD_ERR_HIP;
-    }
-  }
-  build_csr(d->lidar_point, b->L, b->P, st, li);
-  UP(pt_lidar_start, st.data(), st.size()); UP(pt_lidar_list, li.data(), li.size());
-  if (b->L) {   // the terms of every track in thread order: how many, and the first (BaDev::pt_lidar_cnt, pt_lidar_first)
-    const size_t ntr = order.size();
-    std::vector<double> first(5 * ntr, 0.0);
-    std::vector<uint32_t> cnt(ntr, 0);
-    for (size_t t = 0; t < ntr; ++t) {
-      const int p = order[t];
-      if (p < 0 || st[p] == st[p + 1]) continue;
-      cnt[t] = st[p + 1] - st[p];
-      const uint32_t l = li[st[p]];
-      for (int k = 0; k < 4; ++k) first[k * ntr + t] = d->lidar_abcd[4 * (size_t)l + k];
-      first[4 * ntr + t] = d->lidar_weight[l];
-    }
-    UP(pt_lidar_first, first.data(), first.size());
-    UP(pt_lidar_cnt, cnt.data(), cnt.size());
-  }
-  // ---- per-image contiguous copies ----
-  build_csr(d->obs_image, b->O, b->I, st, li);
-  {
-    UP(img_obs_start, st.data(), st.size());
-    {  // segments of <= kImgSeg observations, never spanning two images (an image without observations has none)
-      std::vector<uint32_t> seg_img, seg_begin, img_seg_start(b->I + 1, 0);
-      for (int i = 0; i < b->I; ++i) {
-        img_seg_start[i] = (uint32_t)seg_img.size();
-        for (uint32_t e = st[i]; e < st[i + 1]; e += kImgSeg) { seg_img.push_back((uint32_t)i); seg_begin.push_back(e); }
-      }
-      img_seg_start[b->I] = (uint32_t)seg_img.size();
-      b->nseg = (uint32_t)seg_img.size();
-      seg_begin.push_back((uint32_t)b->O);
-      UP(seg_img, seg_img.data(), seg_img.size());
-      UP(seg_begin, seg_begin.data(), seg_begin.size());
-      UP(img_seg_start, img_seg_start.data(), img_seg_start.size());
-    }
-    {  // images of each camera, ascending
-      std::vector<uint32_t> cst, cli;
-      build_csr(d->image_camera, (uint64_t)b->I, b->C, cst, cli);
-      UP(cam_img_start, cst.data(), cst.size());
-      UP(cam_img_list, cli.data(), cli.size());
-    }
-    UP(img_obs, li.data(), li.size());
-    PCD_TRY(b->img_pt.reserve(std::max<size_t>(b->O, 1)));
-    PCD_TRY(b->img_xy.reserve(std::max<size_t>(2 * b->O, 2)));
-    if (b->O)
-      hipLaunchKernelGGL(k_ba_fill_image_major, dim3(div_up(b->O, 256)), dim3(256), 0, nullptr, b->img_obs.p,
-                         b->obs_point.p, b->obs_xy.p, b->O, b->img_pt.p, b->img_xy.p);
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
-      set_error("pcd_ba_create: filling the image-major layout failed");
-      return PCD_ERR_HIP;
-    }
-  }
-#undef UP
-  {  // rows of the packed pose Jacobians (pcd_ba_evaluate_blocks)
-    b->h_pose_row.assign(b->O, 0xFFFFFFFFu);
-    std::vector<uint32_t> vobs;
-    vobs.reserve(b->O);
-    for (uint64_t o = 0; o < b->O; ++o)
-      if (!(d->image_const_pose && d->image_const_pose[d->obs_image[o]])) {
-        b->h_pose_row[o] = (uint32_t)vobs.size();
-        vobs.push_back((uint32_t)o);
-      }
-    b->n_pose_rows = vobs.size();
-    if (b->n_pose_rows != b->O) PCD_TRY(upload(b->vobs, vobs.data(), vobs.size()));
-  }
-  // one partial per workgroup of whichever of the two cost-producing kernels has the larger grid (cost_blocks)
-  PCD_TRY(b->cost_partial.reserve((size_t)std::max(cost_blocks(b, true), cost_blocks(b, false)) + 1));
-  PCD_TRY(b->cost.reserve(1));
-  *out = owner.release();
-  return PCD_OK;
-  });
-}
-
-void pcd_ba_destroy(pcd_ba* b) {
-  if (!b) return;
-  (void)hipSetDevice(b->device);
-  delete b;
-}
 
 pcd_status pcd_ba_set_parameters(pcd_ba* b, const double* poses, const double* points) {
   PCD_REQUIRE(b, "null handle");
@@ -1524,13 +1252,9 @@ pcd_status pcd_ba_evaluate_device(pcd_ba* b, const pcd_ba_out* o, void* stream) 
   double* const W_raw = w_fused ? nullptr : o->W;
   if ((o->residuals || o->jac_q || o->jac_t || o->jac_X || W_raw) && b->O) {
     ScopedKernelTimer t("ba_raw", s);
-    if (d.shared_cam >= 0) {
-      PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_raw_sc<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, o->residuals,
-                                                 o->jac_q, o->jac_t, o->jac_X, W_raw));
-    } else {
-      PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_raw<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, o->residuals,
-                                                 o->jac_q, o->jac_t, o->jac_X, W_raw));
-    }
+    PCD_BA_DISPATCH_CAM(model, d.shared_cam >= 0,
+                        hipLaunchKernelGGL((k_ba_raw<M, SH>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, o->residuals,
+                                           o->jac_q, o->jac_t, o->jac_X, W_raw));
   }
   if (o->jac_cam && b->O) {
     ScopedKernelTimer t("ba_cam_jac", s);
@@ -1562,15 +1286,10 @@ pcd_status pcd_ba_observation_errors_device(pcd_ba* b, double* d_sq_err, double*
   PCD_HIP_TRY(hipSetDevice(b->device));
   hipStream_t s = (hipStream_t)stream;
   const BaDev d = b->dev();
-  const int model = b->uniform_model;
   ScopedKernelTimer t("ba_obs_errors", s);
-  if (d.shared_cam >= 0) {
-    PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_obs_errors_sc<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, d_sq_err,
-                                              d_depth));
-  } else {
-    PCD_BA_DISPATCH(model, hipLaunchKernelGGL((k_ba_obs_errors<M>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, d_sq_err,
-                                              d_depth));
-  }
+  PCD_BA_DISPATCH_CAM(b->uniform_model, d.shared_cam >= 0,
+                      hipLaunchKernelGGL((k_ba_obs_errors<M, SH>), dim3(div_up(b->O, 256)), dim3(256), 0, s, d, d_sq_err,
+                                         d_depth));
   PCD_HIP_TRY(hipGetLastError());
   return PCD_OK;
 }
@@ -1579,11 +1298,10 @@ pcd_status pcd_ba_observation_errors(pcd_ba* b, double* sq_err, double* depth) {
   PCD_REQUIRE(b, "null handle");
   if (!b->O) return PCD_OK;
   PCD_HIP_TRY(hipSetDevice(b->device));
-  PCD_TRY(b->o_jq.reserve(b->O));
-  PCD_TRY(b->o_jt.reserve(b->O));
-  PCD_TRY(pcd_ba_observation_errors_device(b, sq_err ? b->o_jq.p : nullptr, depth ? b->o_jt.p : nullptr, nullptr));
-  if (sq_err) PCD_HIP_TRY(hipMemcpy(sq_err, b->o_jq.p, b->O * sizeof(double), hipMemcpyDeviceToHost));
-  if (depth) PCD_HIP_TRY(hipMemcpy(depth, b->o_jt.p, b->O * sizeof(double), hipMemcpyDeviceToHost));
+  PCD_TRY(b->f_sq.reserve(b->O)); PCD_TRY(b->f_depth.reserve(b->O));
+  PCD_TRY(pcd_ba_observation_errors_device(b, sq_err ? b->f_sq.p : nullptr, depth ? b->f_depth.p : nullptr, nullptr));
+  if (sq_err) PCD_HIP_TRY(hipMemcpy(sq_err, b->f_sq.p, b->O * sizeof(double), hipMemcpyDeviceToHost));
+  if (depth) PCD_HIP_TRY(hipMemcpy(depth, b->f_depth.p, b->O * sizeof(double), hipMemcpyDeviceToHost));
   return PCD_OK;
 }
 
@@ -1687,13 +1405,8 @@ pcd_status pcd_ba_evaluate_blocks_compact(pcd_ba* b, int want_jacobians, int wan
     const BaDev d = b->dev();
     if (O) {
       ScopedKernelTimer t("ba_raw_compact", s);
-      if (d.shared_cam >= 0) {
-        PCD_BA_DISPATCH(b->uniform_model, hipLaunchKernelGGL((k_ba_raw_compact_sc<M>), dim3(div_up(O, 256)), dim3(256), 0,
-                                                             s, d, b->o_rec.p));
-      } else {
-        PCD_BA_DISPATCH(b->uniform_model, hipLaunchKernelGGL((k_ba_raw_compact<M>), dim3(div_up(O, 256)), dim3(256), 0, s,
-                                                             d, b->o_rec.p));
-      }
+      PCD_BA_DISPATCH_CAM(b->uniform_model, d.shared_cam >= 0,
+                          hipLaunchKernelGGL((k_ba_raw_compact<M, SH>), dim3(div_up(O, 256)), dim3(256), 0, s, d, b->o_rec.p));
     }
     if (L) {
       ScopedKernelTimer t("ba_lidar_raw", s);

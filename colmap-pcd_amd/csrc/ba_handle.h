@@ -1,5 +1,8 @@
-// ba_handle.h -- the part of the bundle-adjustment handle that both BA units see: ba.hip (evaluation) and
-// ba_solve.hip (point elimination, PCG, LM loop).  Internal; no kernels here.
+// ba_handle.h -- the bundle-adjustment handle as every BA unit sees it, and the sizes builder and launchers must agree
+// on (kImgSeg, kCostBlocks, cost_blocks).  Internal; no kernels here.
+//   ba_build.hip  makes and destroys it: pcd_ba_create uploads the problem and builds the derived layouts below
+//   ba.hip        evaluates on it: the kernels that read BaDev, and every pcd_ba_evaluate* / filter entry point
+//   ba_solve.hip  point elimination, PCG, LM loop (its own state hangs off pcd_ba::schur)
 #pragma once
 #include <memory>
 
@@ -7,6 +10,9 @@
 #include "common.h"
 
 namespace pcd {
+
+constexpr uint32_t kImgSeg = 1024;           // observations per segment of an image: the work item of k_ba_images
+constexpr unsigned kCostBlocks = 1u << 20;   // cap of the cost pass's grid (256 M residual blocks in one sweep)
 
 struct BaDev {
   // problem (device)
@@ -96,8 +102,9 @@ struct pcd_ba {
   // pcd_ba_evaluate_blocks_compact: records and packed camera blocks (h_blocks is shared with the full route)
   int cam_stride = 0;                    // largest pcd_camera_num_params over the cameras
   pcd::DevBuf<double> o_rec, p_jc;
-  // pcd_ba_filter_tracks: the track CSR (point -> its observations, ascending), scratch
+  // the track CSR (point -> its observations, ascending): the sliced-ELL fill and pcd_ba_filter_tracks read it
   pcd::DevBuf<uint32_t> pt_obs_start, pt_obs_list;
+  // filter scratch; f_sq / f_depth also stage pcd_ba_observation_errors
   pcd::DevBuf<double> f_sq, f_depth, f_part, f_summary;
   pcd::DevBuf<uint8_t> f_u8;
   // point elimination (pcd_ba_schur*): built on the first call, so pcd_ba_create costs existing users nothing
@@ -123,3 +130,14 @@ struct pcd_ba {
     return d;
   }
 };
+
+namespace pcd {
+
+// Grid of the kernel that writes cost_partial[blockIdx.x]: k_ba_points takes two 64-track slices per workgroup,
+// k_ba_cost sweeps the residual blocks with a capped grid.  pcd_ba_create sizes cost_partial from the SAME function.
+inline unsigned cost_blocks(const pcd_ba* b, bool want_blocks) {
+  return want_blocks ? std::max(1u, div_up((size_t)b->nslices, 2))
+                     : std::max(1u, std::min(kCostBlocks, div_up(b->O + b->L, 256)));
+}
+
+}  // namespace pcd

@@ -118,6 +118,17 @@ __device__ __forceinline__ void world_to_image_d2(int model, const double* __res
   }
 }
 
+// P = R(q) X + t with q = (w,x,y,z) as given (not normalised):  uv = 2 v x X ; P = X + w uv + v x uv + t, the
+// polynomial of Ceres' UnitQuaternionRotatePoint.  Every kernel that needs P outside reproj_eval calls this.
+__device__ __forceinline__ void pose_transform(const double q[4], const double t[3], const double X[3], double P[3]) {
+  const double w = q[0], a = q[1], bq = q[2], c = q[3];
+  const double cx = bq * X[2] - c * X[1], cy = c * X[0] - a * X[2], cz = a * X[1] - bq * X[0];
+  const double ux = 2.0 * cx, uy = 2.0 * cy, uz = 2.0 * cz;
+  P[0] = X[0] + w * ux + (bq * uz - c * uy) + t[0];
+  P[1] = X[1] + w * uy + (c * ux - a * uz) + t[1];
+  P[2] = X[2] + w * uz + (a * uy - bq * ux) + t[2];
+}
+
 struct ReprojBlock {
   double r[2];
   double M[6];   // d r / d P  (2x3) = A * d(u,v)/dP ;  J_t = M
@@ -130,7 +141,7 @@ __device__ __forceinline__ void reproj_eval(int model, const double* __restrict_
                                             const double t[3], const double X[3], double ox, double oy,
                                             ReprojBlock& b) {
   const double w = q[0], a = q[1], bq = q[2], c = q[3];
-  // uv = 2 v x X ; P = X + w uv + v x uv + t      (same polynomial as Ceres' UnitQuaternionRotatePoint)
+  // pose_transform written out (ux, uy, uz are also dP/dw; through the helper the cost and image passes compile differently)
   const double cx = bq * X[2] - c * X[1], cy = c * X[0] - a * X[2], cz = a * X[1] - bq * X[0];
   const double ux = 2.0 * cx, uy = 2.0 * cy, uz = 2.0 * cz;
   const double Px = X[0] + w * ux + (bq * uz - c * uy) + t[0];

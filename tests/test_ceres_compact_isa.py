@@ -10,6 +10,7 @@ from tests.test_kernel_isa import FLAGS, HIPCC, ROOT, _kernels
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 MODELS = ("ILi0E", "ILi1E", "ILi2E", "ILi3E", "ILi4E", "ILin1E")      # the dispatched instantiations, -1 = per observation
+SHARED = ("Lb0EE", "Lb1EE")                                           # second template argument: per-image / shared camera
 
 
 @pytest.fixture(scope="module")
@@ -28,11 +29,12 @@ def _one(meta, part):
 @pytest.mark.parametrize("model", MODELS)
 def test_compact_kernel_is_leaner_than_the_full_one(isa, model):
     meta, body = isa
-    full = _one(meta, "8k_ba_raw" + model)
-    k = _one(meta, "16k_ba_raw_compact" + model)
-    m = meta[k]
-    assert m["scratch"] == 0 and "scratch_" not in body[k], (k, m)
-    assert m["vgpr"] <= meta[full]["vgpr"], (k, m, meta[full])
+    for shared in SHARED:
+        full = _one(meta, "8k_ba_raw" + model + shared)
+        k = _one(meta, "16k_ba_raw_compact" + model + shared)
+        m = meta[k]
+        assert m["scratch"] == 0 and "scratch_" not in body[k], (k, m)
+        assert m["vgpr"] <= meta[full]["vgpr"], (k, m, meta[full])
 
 
 def test_packed_camera_kernel(isa):
@@ -41,4 +43,5 @@ def test_packed_camera_kernel(isa):
     m = meta[k]
     assert m["scratch"] == 0 and "scratch_" not in body[k], (k, m)
     for model in MODELS:
-        assert m["vgpr"] <= meta[_one(meta, "8k_ba_raw" + model)]["vgpr"], (k, m)
+        for shared in SHARED:
+            assert m["vgpr"] <= meta[_one(meta, "8k_ba_raw" + model + shared)]["vgpr"], (k, m)
