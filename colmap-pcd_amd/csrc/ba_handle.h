@@ -3,6 +3,7 @@
 //   ba_build.hip  makes and destroys it: pcd_ba_create uploads the problem and builds the derived layouts below
 //   ba.hip        evaluates on it: the kernels that read BaDev, and every pcd_ba_evaluate* / filter entry point
 //   ba_solve.hip  point elimination, PCG, LM loop (its own state hangs off pcd_ba::schur)
+//   ba_lidar.hip  replaces the LiDAR terms of a live handle: pcd_ba_set_lidar_device / pcd_ba_associate_lidar_device
 #pragma once
 #include <memory>
 
@@ -27,9 +28,11 @@ struct BaDev {
   const int* sell_img;            // [nslots]      image of the observation, -1 = padding
   const double* sell_xy;          // [nslots][2]
   const uint32_t* pt_lidar_start; const uint32_t* pt_lidar_list;
-  // The LiDAR terms in the order of k_ba_points' threads (both nullptr when L == 0).  The terms are constants of the
-  // handle (set in pcd_ba_create only), so the kernel reads its one plane per point coalesced and ahead of everything
-  // else, not through point -> list -> term; only a second or third term of a point goes through the lists.
+  // The LiDAR terms in the order of k_ba_points' threads (both nullptr when L == 0).  The terms change only as a whole
+  // (pcd_ba_create, or pcd_ba_set_lidar_device / pcd_ba_associate_lidar_device, which rebuild these two arrays with the
+  // CSR above and swap all of them in together: ba_lidar.hip), never between the launches of one evaluation, so the
+  // kernel reads its one plane per point coalesced and ahead of everything else, not through point -> list -> term;
+  // only a second or third term of a point goes through the lists.
   const uint32_t* pt_lidar_cnt;   // [nslices*64] number of LiDAR terms of the track of thread t
   const double* pt_lidar_first;   // [5][nslices*64] plane (a, b, c, d) and weight of the first of them, component-major
   const uint32_t* img_obs_start;  // [I+1]
@@ -50,6 +53,16 @@ struct BaDev {
   int shared_cam;                 // >= 0: every image maps to this camera (one physical camera, the usual dataset); -1: per image
 };
 
+// Scratch of the device rebuild of the LiDAR terms (ba_lidar.hip).  The first group is the layout under construction:
+// on success it is swapped with the live arrays of pcd_ba, so the buffers a call retires are the next call's.
+struct BaLidarScratch {
+  DevBuf<int> point; DevBuf<double> abcd, w, xyz, first; DevBuf<uint8_t> type; DevBuf<uint32_t> start, list, cnt;
+  DevBuf<uint32_t> flag, pos, part, status, keys, iota;   // per row: kept / position; per workgroup and total: the record
+  DevBuf<char> prim;                                      // rocPRIM temporary storage (scan, sort)
+  PinnedBuf<uint32_t> h_status;
+  DevBuf<double> a_xyz, a_abcd; DevBuf<uint8_t> a_type;   // association rows of pcd_ba_associate_lidar_device, [P]
+};
+
 // The point-elimination state is complete in ba_solve.hip only.  The deleter is defined there, so a pcd_ba can be
 // made and destroyed where BaSchur is an incomplete type (the default deleter would need the complete one).
 struct BaSchur;
@@ -68,6 +81,9 @@ static pcd_status upload(DevBuf<T>& b, const T* src, size_t n) {
 // Every output is device memory and required.  Opens no profiling scope, sets no device.
 pcd_status ba_normal_equations(pcd_ba* b, const uint32_t* w_order, double* Hpt, double* gpt, double* cost, double* Himg,
                                double* gimg, double* W, hipStream_t s);
+// Drops the numeric state of the last Schur call (ba_solve.hip): pcd_ba_schur_solve_* and the back-substitution report
+// "no Schur state" until the next one.  The co-visibility structure and every scratch buffer stay.
+void ba_schur_invalidate(pcd_ba* b);
 
 }  // namespace pcd
 
@@ -83,6 +99,12 @@ struct pcd_ba {
   pcd::DevBuf<double> cam_params, poses, points, obs_xy, lidar_abcd, lidar_w, sell_xy, img_xy, pt_lidar_first;
   pcd::DevBuf<uint8_t> image_const_pose, image_const_tvec, point_const;
   bool has_cpose = false, has_ctvec = false, has_cpt = false;
+  // per term, beside lidar_point / lidar_abcd / lidar_w: its pcd_lidar_type and LiDAR point, for the outlier filter.
+  // pcd_ba_create knows neither: the buffers then do not exist until pcd_ba_lidar_device asks for them (zeros).
+  pcd::DevBuf<uint8_t> lidar_type;
+  pcd::DevBuf<double> lidar_xyz;
+  bool has_lidar_meta = false;
+  pcd::BaLidarScratch lidar_next;
   pcd::DevBuf<uint32_t> slice_start, pt_lidar_start, pt_lidar_list, img_obs_start, img_obs, cam_img_start, cam_img_list;
   pcd::DevBuf<uint32_t> seg_img, seg_begin, img_seg_start, pt_lidar_cnt;
   uint32_t nseg = 0;
@@ -135,9 +157,10 @@ namespace pcd {
 
 // Grid of the kernel that writes cost_partial[blockIdx.x]: k_ba_points takes two 64-track slices per workgroup,
 // k_ba_cost sweeps the residual blocks with a capped grid.  pcd_ba_create sizes cost_partial from the SAME function.
+// The sweep's grid alone, for a term count the handle does not have yet (ba_lidar.hip sizes cost_partial before the swap).
+inline unsigned cost_sweep_blocks(uint64_t O, uint64_t L) { return std::max(1u, std::min(kCostBlocks, div_up(O + L, 256))); }
 inline unsigned cost_blocks(const pcd_ba* b, bool want_blocks) {
-  return want_blocks ? std::max(1u, div_up((size_t)b->nslices, 2))
-                     : std::max(1u, std::min(kCostBlocks, div_up(b->O + b->L, 256)));
+  return want_blocks ? std::max(1u, div_up((size_t)b->nslices, 2)) : cost_sweep_blocks(b->O, b->L);
 }
 
 }  // namespace pcd

@@ -1,0 +1,399 @@
+// ba_lidar.hip -- the LiDAR terms of a BA handle rebuilt on the device: pcd_ba_set_lidar_device,
+// pcd_ba_get_lidar / pcd_ba_lidar_device, pcd_ba_associate_lidar_device.
+// What build_lidar_layout (ba_build.hip) makes on the host from the caller's term list is made here from Q device rows,
+// byte for byte: the terms (rows that pass the type / NaN rule, in ascending row order), the CSR point -> terms
+// (ascending term number) and the first term of every track in the thread order of k_ba_points.  The passes:
+//   k_lidar_flag     row -> kept?, and one record per workgroup: invalid rows, selected rows, terms of each type, and
+//                    the first / last point and the order of the workgroup's kept rows
+//   exclusive_sum    kept -> term number
+//   k_lidar_status   the workgroup records merged in workgroup order -> one record; read back with the term count (the
+//                    ONE synchronisation: the count sizes the buffers and grids below)
+//   k_lidar_compact  kept rows -> terms
+//   sort_pairs       (point, term), stable, only when the terms' points are not already non-decreasing
+//   k_lidar_bounds   CSR bounds of every point by bisection of the sorted points
+//   k_lidar_tracks   thread of k_ba_points -> number of terms and the first of them, component-major
+// No atomics; every order is that of the rows: nothing depends on the launch geometry.  The new layout is built in
+// pcd_ba::lidar_next and swapped in at the end; a refusal returns before the swap.
+#include <cmath>
+
+#include "ba_handle.h"
+#include "cloud.h"
+#include "prim.h"
+
+namespace pcd {
+
+constexpr uint32_t kNoPoint = 0xFFFFFFFFu;
+// per workgroup of k_lidar_flag, and their merge in row order
+struct LidarPart {
+  uint32_t bad, selected, ntype[3];   // invalid rows; selected rows; kept rows of type 1, 2, 3
+  uint32_t first_pt, last_pt;         // point of the first / last kept row, kNoPoint: none
+  uint32_t unsorted;                  // some kept row's point is below that of the kept row before it
+};
+constexpr int kPartWords = sizeof(LidarPart) / sizeof(uint32_t);
+// the record the host reads: the merged LidarPart, then the number of terms
+constexpr int kStatusWords = kPartWords + 1;
+
+__device__ __forceinline__ LidarPart part_empty() {
+  LidarPart p;
+  p.bad = p.selected = p.ntype[0] = p.ntype[1] = p.ntype[2] = 0;
+  p.first_pt = p.last_pt = kNoPoint;
+  p.unsorted = 0;
+  return p;
+}
+// a: rows before those of b
+__device__ __forceinline__ LidarPart part_merge(const LidarPart& a, const LidarPart& b) {
+  LidarPart p;
+  p.bad = a.bad + b.bad;
+  p.selected = a.selected + b.selected;
+  for (int k = 0; k < 3; ++k) p.ntype[k] = a.ntype[k] + b.ntype[k];
+  p.first_pt = a.first_pt != kNoPoint ? a.first_pt : b.first_pt;
+  p.last_pt = b.last_pt != kNoPoint ? b.last_pt : a.last_pt;
+  p.unsorted = a.unsorted | b.unsorted | ((a.last_pt != kNoPoint && b.first_pt != kNoPoint && a.last_pt > b.first_pt) ? 1u : 0u);
+  return p;
+}
+
+// One row: its record as a LidarPart of one row, and whether it is kept.  A point outside [0, P) or a type above 3 is
+// invalid in any row; an unselected row counts as type 0 behind that test.
+__global__ __launch_bounds__(256) void k_lidar_flag(uint32_t Q, int P, const int32_t* __restrict__ point,
+                                                    const uint8_t* __restrict__ type, const double* __restrict__ abcd,
+                                                    const uint8_t* __restrict__ select, uint32_t* __restrict__ flag,
+                                                    LidarPart* __restrict__ part) {
+  __shared__ LidarPart s_row[256];
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  LidarPart r = part_empty();
+  if (q < Q) {
+    const int p = point ? point[q] : (int)q;
+    uint32_t t = type[q];
+    r.bad = (p < 0 || p >= P || t > 3u) ? 1u : 0u;
+    const bool sel = !select || select[q] != 0;
+    r.selected = sel ? 1u : 0u;
+    if (!sel) t = 0;
+    bool keep = t != 0 && !r.bad;
+    if (keep) {
+      const double* v = abcd + 4 * (size_t)q;   // the caller's rows: no alignment beyond a double's is assumed
+      keep = !(isnan(v[0]) || isnan(v[1]) || isnan(v[2]) || isnan(v[3]));   // optim/bundle_adjustment.cc:1005-1009
+    }
+    if (keep) {
+      r.ntype[t - 1] = 1;
+      r.first_pt = r.last_pt = (uint32_t)p;
+    }
+    flag[q] = keep ? 1u : 0u;
+  }
+  s_row[threadIdx.x] = r;
+  __syncthreads();
+  // merge in row order: a tree over adjacent ranges keeps the order (part_merge is associative)
+  for (int w = 1; w < 256; w <<= 1) {
+    LidarPart m = r;
+    const bool on = (threadIdx.x & (2 * w - 1)) == 0;
+    if (on) m = part_merge(s_row[threadIdx.x], s_row[threadIdx.x + w]);
+    __syncthreads();
+    if (on) s_row[threadIdx.x] = m;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = s_row[0];
+}
+
+// the nb workgroup records -> status[0 .. kPartWords), and the term count behind them.  One workgroup: thread t merges a
+// contiguous run of records in order, then the 256 runs are merged in order.
+__global__ __launch_bounds__(256) void k_lidar_status(uint32_t nb, const LidarPart* __restrict__ part, uint32_t Q,
+                                                      const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
+                                                      uint32_t* __restrict__ status) {
+  __shared__ LidarPart s_run[256];
+  const uint32_t per = (nb + 255u) / 256u;
+  LidarPart r = part_empty();
+  for (uint32_t k = 0; k < per; ++k) {
+    const uint32_t i = threadIdx.x * per + k;
+    if (i < nb) r = part_merge(r, part[i]);
+  }
+  s_run[threadIdx.x] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    LidarPart m = s_run[0];
+    for (int t = 1; t < 256; ++t) m = part_merge(m, s_run[t]);
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(&m);
+    for (int k = 0; k < kPartWords; ++k) status[k] = w[k];
+    status[kPartWords] = Q ? pos[Q - 1] + flag[Q - 1] : 0u;
+  }
+}
+
+struct LidarWeights { double w[4]; };
+
+// kept row q -> term pos[q].  ident[t] = t, the value array of the sort or, when the points are
+// already in order, the term list itself.
+__global__ __launch_bounds__(256) void k_lidar_compact(uint32_t Q, const uint32_t* __restrict__ flag,
+                                                       const uint32_t* __restrict__ pos, const int32_t* __restrict__ point,
+                                                       const uint8_t* __restrict__ type, const double* __restrict__ abcd,
+                                                       const double* __restrict__ xyz, LidarWeights wt,
+                                                       int* __restrict__ o_point, double* __restrict__ o_abcd,
+                                                       double* __restrict__ o_w, uint8_t* __restrict__ o_type,
+                                                       double* __restrict__ o_xyz, uint32_t* __restrict__ ident) {
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= Q || !flag[q]) return;
+  const uint32_t t = pos[q];
+  const uint8_t ty = type[q];
+  o_point[t] = point ? point[q] : (int)q;
+  for (int k = 0; k < 4; ++k) o_abcd[4 * (size_t)t + k] = abcd[4 * (size_t)q + k];
+  o_w[t] = wt.w[ty & 3];
+  o_type[t] = ty;
+  for (int k = 0; k < 3; ++k) o_xyz[3 * (size_t)t + k] = xyz ? xyz[3 * (size_t)q + k] : 0.0;
+  ident[t] = t;
+}
+
+// start[p] = number of terms whose point is below p, p = 0 .. P: bisection of the L sorted points
+__global__ __launch_bounds__(256) void k_lidar_bounds(int P, uint32_t L, const uint32_t* __restrict__ sorted_pt,
+                                                      uint32_t* __restrict__ start) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p > (uint32_t)P) return;
+  uint32_t lo = 0, hi = L;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (sorted_pt[mid] < p) lo = mid + 1; else hi = mid;
+  }
+  start[p] = lo;
+}
+
+// thread t of k_ba_points (track order[t], -1: padding): how many terms its track has, and the first of them
+__global__ __launch_bounds__(256) void k_lidar_tracks(uint32_t ntr, const int* __restrict__ order,
+                                                      const uint32_t* __restrict__ start, const uint32_t* __restrict__ list,
+                                                      const double* __restrict__ abcd, const double* __restrict__ w,
+                                                      uint32_t* __restrict__ cnt, double* __restrict__ first) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= ntr) return;
+  const int p = order[t];
+  uint32_t n = 0;
+  double f[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if (p >= 0) {
+    const uint32_t b = start[p];
+    n = start[p + 1] - b;
+    if (n) {
+      const uint32_t l = list[b];
+      const double4 v = *reinterpret_cast<const double4*>(abcd + 4 * (size_t)l);
+      f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; f[4] = w[l];
+    }
+  }
+  cnt[t] = n;
+  for (int k = 0; k < 5; ++k) first[(size_t)k * ntr + t] = f[k];
+}
+
+// what the host reads back
+struct LidarStatus {
+  LidarPart part;
+  uint32_t L;
+};
+static_assert(sizeof(LidarStatus) == kStatusWords * sizeof(uint32_t), "status record");
+
+// Argument checks shared by the entry points, in the documented order: arguments (INVALID), device (NO_DEVICE), capture
+// (UNSUPPORTED) -- nothing allocated before them
+static pcd_status lidar_guards(pcd_ba* b, void* stream, const char* fn) {
+  PCD_REQUIRE(b, "null handle");
+  PCD_TRY(require_device(b->device));
+  PCD_TRY(refuse_capture((hipStream_t)stream, fn));
+  return PCD_OK;
+}
+
+// The rebuild.  Rows as documented for pcd_ba_set_lidar_device, plus d_select (unselected rows count as type 0).
+// Synchronises s once.  st (may be null) receives the record.
+static pcd_status lidar_rebuild(pcd_ba* b, uint64_t Q, const int32_t* d_point, const uint8_t* d_type, const double* d_abcd,
+                                const double* d_xyz, const uint8_t* d_select, const double weight[4], hipStream_t s,
+                                LidarStatus* st) {
+  BaLidarScratch& N = b->lidar_next;
+  const int P = b->P;
+  const uint32_t q32 = (uint32_t)Q;
+  const uint32_t nb = div_up(Q, 256);
+  LidarStatus hs{};
+  if (Q) {
+    PCD_TRY(N.flag.reserve(Q)); PCD_TRY(N.pos.reserve(Q));
+    PCD_TRY(N.part.reserve((size_t)nb * kPartWords)); PCD_TRY(N.status.reserve(kStatusWords));
+    PCD_TRY(N.h_status.reserve(kStatusWords));
+    LidarPart* part = reinterpret_cast<LidarPart*>(N.part.p);
+    {
+      ScopedKernelTimer t("ba_lidar_flag", s);
+      hipLaunchKernelGGL(k_lidar_flag, dim3(nb), dim3(256), 0, s, q32, P, d_point, d_type, d_abcd, d_select, N.flag.p, part);
+      PCD_TRY(exclusive_sum(N.prim, N.flag.p, N.pos.p, 0u, (size_t)Q, s));
+      hipLaunchKernelGGL(k_lidar_status, dim3(1), dim3(256), 0, s, nb, part, q32, N.flag.p, N.pos.p, N.status.p);
+    }
+    PCD_HIP_TRY(hipMemcpyAsync(N.h_status.p, N.status.p, sizeof(LidarStatus), hipMemcpyDeviceToHost, s));
+    PCD_HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(&hs, N.h_status.p, sizeof hs);
+  }
+  if (hs.part.bad) {
+    set_error("pcd_ba_set_lidar_device: %u row(s) with a point outside [0, %d) or a type above 3; the handle is unchanged",
+              hs.part.bad, P);
+    return PCD_ERR_INVALID;
+  }
+  for (int k = 0; k < 3; ++k)
+    if (hs.part.ntype[k] && !std::isfinite(weight[k + 1])) {
+      set_error("pcd_ba_set_lidar_device: the weight of type %d, which %u term(s) have, is not finite; the handle is unchanged",
+                k + 1, hs.part.ntype[k]);
+      return PCD_ERR_INVALID;
+    }
+  const uint32_t L = hs.L;
+  const size_t ntr = (size_t)b->nslices * 64;
+  // the layout under construction, sized as pcd_ba_create sizes the live one
+  PCD_TRY(N.point.reserve(std::max<size_t>(L, 1))); PCD_TRY(N.abcd.reserve(std::max<size_t>(4 * (size_t)L, 1)));
+  PCD_TRY(N.w.reserve(std::max<size_t>(L, 1))); PCD_TRY(N.type.reserve(std::max<size_t>(L, 1)));
+  PCD_TRY(N.xyz.reserve(std::max<size_t>(3 * (size_t)L, 1)));
+  PCD_TRY(N.start.reserve((size_t)P + 1)); PCD_TRY(N.list.reserve(std::max<size_t>(L, 1)));
+  if (L) { PCD_TRY(N.cnt.reserve(std::max<size_t>(ntr, 1))); PCD_TRY(N.first.reserve(std::max<size_t>(5 * ntr, 1))); }
+  const bool sorted = !hs.part.unsorted;
+  if (L && !sorted) { PCD_TRY(N.keys.reserve(L)); PCD_TRY(N.iota.reserve(L)); }
+  // one cost partial per workgroup of the larger of the two cost-producing grids: the sweep's follows O + L
+  PCD_TRY(b->cost_partial.reserve((size_t)std::max(cost_blocks(b, true), cost_sweep_blocks(b->O, L)) + 1));
+  {
+    ScopedKernelTimer t("ba_lidar_rebuild", s);
+    LidarWeights wt;
+    for (int k = 0; k < 4; ++k) wt.w[k] = weight[k];
+    if (L)
+      hipLaunchKernelGGL(k_lidar_compact, dim3(nb), dim3(256), 0, s, q32, N.flag.p, N.pos.p, d_point, d_type, d_abcd, d_xyz,
+                         wt, N.point.p, N.abcd.p, N.w.p, N.type.p, N.xyz.p, sorted ? N.list.p : N.iota.p);
+    const uint32_t* sorted_pt = reinterpret_cast<const uint32_t*>(N.point.p);
+    if (L && !sorted) {
+      unsigned bits = 1;
+      while (bits < 32 && (1ull << bits) < (uint64_t)P) ++bits;   // points are < P: ceil(log2 P) key bits
+      PCD_TRY(sort_pairs(N.prim, reinterpret_cast<uint32_t*>(N.point.p), N.keys.p, N.iota.p, N.list.p, (size_t)L, 0u, bits, s));
+      sorted_pt = N.keys.p;
+    }
+    hipLaunchKernelGGL(k_lidar_bounds, dim3(div_up((uint64_t)P + 1, 256)), dim3(256), 0, s, P, L, sorted_pt, N.start.p);
+    if (L && ntr)
+      hipLaunchKernelGGL(k_lidar_tracks, dim3(div_up(ntr, 256)), dim3(256), 0, s, (uint32_t)ntr, b->pt_order.p, N.start.p,
+                         N.list.p, N.abcd.p, N.w.p, N.cnt.p, N.first.p);
+    PCD_HIP_TRY(hipGetLastError());
+  }
+  // success: the new layout becomes the handle's; the retired buffers are the next call's
+  b->lidar_point.swap(N.point); b->lidar_abcd.swap(N.abcd); b->lidar_w.swap(N.w);
+  b->lidar_type.swap(N.type); b->lidar_xyz.swap(N.xyz);
+  b->pt_lidar_start.swap(N.start); b->pt_lidar_list.swap(N.list);
+  if (L) { b->pt_lidar_cnt.swap(N.cnt); b->pt_lidar_first.swap(N.first); }
+  b->L = L;
+  b->has_lidar_meta = true;
+  ba_schur_invalidate(b);
+  if (st) *st = hs;
+  return PCD_OK;
+}
+
+// type / lidar_xyz of terms that came from pcd_ba_create: zeros, made when first asked for
+static pcd_status lidar_meta(pcd_ba* b) {
+  if (b->has_lidar_meta) return PCD_OK;
+  const size_t L = b->L;
+  PCD_TRY(b->lidar_type.reserve(std::max<size_t>(L, 1))); PCD_TRY(b->lidar_xyz.reserve(std::max<size_t>(3 * L, 1)));
+  PCD_HIP_TRY(hipMemset(b->lidar_type.p, 0, std::max<size_t>(L, 1)));
+  PCD_HIP_TRY(hipMemset(b->lidar_xyz.p, 0, std::max<size_t>(3 * L, 1) * sizeof(double)));
+  b->has_lidar_meta = true;
+  return PCD_OK;
+}
+
+}  // namespace pcd
+
+using namespace pcd;
+
+extern "C" {
+
+pcd_status pcd_ba_set_lidar_device(pcd_ba* b, uint64_t Q, const int32_t* d_point, const uint8_t* d_type,
+                                   const double* d_abcd, const double* d_lidar_xyz, const double weight[4], void* stream,
+                                   uint64_t* num_terms) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_REQUIRE(b, "null handle");
+    PCD_REQUIRE(weight, "null weight");
+    PCD_REQUIRE(Q == 0 || (d_type && d_abcd), "null rows");
+    PCD_REQUIRE(Q < 0xFFFFFFF0ull, "too many rows");
+    PCD_REQUIRE(d_point || Q == (uint64_t)b->P, "without d_point row q is point q: Q must equal the number of points");
+    PCD_TRY(lidar_guards(b, stream, "pcd_ba_set_lidar_device"));
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    LidarStatus st{};
+    PCD_TRY(lidar_rebuild(b, Q, d_point, d_type, d_abcd, d_lidar_xyz, nullptr, weight, (hipStream_t)stream, &st));
+    if (num_terms) *num_terms = st.L;
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_get_lidar(pcd_ba* b, uint64_t* num_terms, int32_t* point, double* abcd, double* weight, uint8_t* type,
+                            double* lidar_xyz) {
+  PCD_REQUIRE(b, "null handle");
+  PCD_TRY(require_device(b->device));
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  const size_t L = b->L;
+  if (num_terms) *num_terms = L;
+  if (!L) return PCD_OK;
+  if (type || lidar_xyz) PCD_TRY(lidar_meta(b));
+  if (point) PCD_HIP_TRY(hipMemcpy(point, b->lidar_point.p, L * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (abcd) PCD_HIP_TRY(hipMemcpy(abcd, b->lidar_abcd.p, 4 * L * sizeof(double), hipMemcpyDeviceToHost));
+  if (weight) PCD_HIP_TRY(hipMemcpy(weight, b->lidar_w.p, L * sizeof(double), hipMemcpyDeviceToHost));
+  if (type) PCD_HIP_TRY(hipMemcpy(type, b->lidar_type.p, L, hipMemcpyDeviceToHost));
+  if (lidar_xyz) PCD_HIP_TRY(hipMemcpy(lidar_xyz, b->lidar_xyz.p, 3 * L * sizeof(double), hipMemcpyDeviceToHost));
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_lidar_device(pcd_ba* b, uint64_t* num_terms, const int32_t** d_point, const double** d_abcd,
+                               const double** d_weight, const uint8_t** d_type, const double** d_lidar_xyz) {
+  PCD_REQUIRE(b, "null handle");
+  PCD_TRY(require_device(b->device));
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  if (d_type || d_lidar_xyz) PCD_TRY(lidar_meta(b));
+  if (num_terms) *num_terms = b->L;
+  if (d_point) *d_point = b->lidar_point.p;
+  if (d_abcd) *d_abcd = b->lidar_abcd.p;
+  if (d_weight) *d_weight = b->lidar_w.p;
+  if (d_type) *d_type = b->lidar_type.p;
+  if (d_lidar_xyz) *d_lidar_xyz = b->lidar_xyz.p;
+  return PCD_OK;
+}
+
+void pcd_ba_assoc_opts_default(pcd_ba_assoc_opts* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->gate_mode = PCD_GATE_MAPPER_GLOBAL;
+  o->icp_weight = 100.0;
+  o->icp_ground_weight = 1000.0;
+}
+
+pcd_status pcd_ba_associate_lidar_device(pcd_ba* b, pcd_cloud* c, const pcd_ba_assoc_opts* opts, void* stream,
+                                         pcd_ba_assoc_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    if (info) std::memset(info, 0, sizeof *info);
+    PCD_REQUIRE(opts, "null options");
+    const int mode = opts->gate_mode & ~PCD_GATE_BOUNDED_SEARCH;
+    PCD_REQUIRE(mode >= 0 && mode <= 2, "gate_mode");
+    PCD_REQUIRE(b, "null handle");
+    PCD_REQUIRE(c, "null cloud");
+    const uint64_t P = (uint64_t)b->P;
+    PCD_REQUIRE(mode == PCD_GATE_CONTROLLER ||
+                (opts->d_max_range && (opts->max_range_count == 1 || opts->max_range_count == P)),
+                "max_range must have 1 or num_points entries");
+    PCD_REQUIRE(b->device == c->device, "the BA handle and the cloud live on different devices");
+    PCD_TRY(lidar_guards(b, stream, "pcd_ba_associate_lidar_device"));
+    if (c->row_index.p || c->g2l.p || c->index_stride != 1 || c->index_base != 0) {
+      set_error("pcd_ba_associate_lidar_device needs ONE handle holding the whole cloud, not a shard or a strided handle "
+                "(pcd_cloud_create_sharded, index_stride / index_base)");
+      return PCD_ERR_UNSUPPORTED;
+    }
+    if (P == 0) return PCD_OK;
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    BaLidarScratch& N = b->lidar_next;
+    PCD_TRY(N.a_xyz.reserve(3 * P)); PCD_TRY(N.a_abcd.reserve(4 * P)); PCD_TRY(N.a_type.reserve(P));
+    EventPair ea, er;
+    if (info) { PCD_TRY(ea.create()); PCD_TRY(er.create()); (void)ea.start(s); }
+    pcd_assoc_out ao{};
+    ao.lidar_xyz = N.a_xyz.p; ao.abcd = N.a_abcd.p; ao.type = N.a_type.p;
+    PCD_TRY(pcd_associate_device(c, b->points.p, P, opts->d_max_range, opts->max_range_count, opts->gate_mode, nullptr,
+                                 &ao, stream));
+    if (info) { (void)ea.stop(s); (void)er.start(s); }
+    const double weight[4] = {0.0, opts->icp_weight, opts->icp_ground_weight, 0.0};
+    LidarStatus st{};
+    PCD_TRY(lidar_rebuild(b, P, nullptr, N.a_type.p, N.a_abcd.p, N.a_xyz.p, opts->d_select, weight, s, &st));
+    if (info) {
+      float ms = 0.f;
+      PCD_HIP_TRY(er.stop_and_wait(s, &ms));
+      info->rebuild_ms = ms;
+      PCD_HIP_TRY(ea.elapsed(&ms));
+      info->assoc_ms = ms;
+      info->num_queries = st.part.selected;
+      info->num_terms = st.L;
+      info->num_icp = st.part.ntype[0];
+      info->num_icp_ground = st.part.ntype[1];
+    }
+    return PCD_OK;
+  });
+}
+
+}  // extern "C"

@@ -752,6 +752,9 @@ struct BaSchur {
 };
 
 void BaSchurDelete::operator()(BaSchur* s) const { delete s; }
+void ba_schur_invalidate(pcd_ba* b) {
+  if (b->schur) b->schur->valid = false;
+}
 
 }  // namespace pcd
 

@@ -102,6 +102,10 @@ struct DevBuf {
     p = nullptr;
     n = 0;
   }
+  void swap(DevBuf& o) {
+    std::swap(p, o.p);
+    std::swap(n, o.n);
+  }
   // grow-only (keeps contents undefined)
   pcd_status reserve(size_t count) {
     if (count <= n) return PCD_OK;

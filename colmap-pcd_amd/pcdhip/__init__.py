@@ -19,6 +19,7 @@ NN_AUTO, NN_BRUTEFORCE, NN_FALLBACK_ONLY, NN_GRID = 0, 1, 2, 3
 GATE_MAPPER_LOCAL, GATE_MAPPER_GLOBAL, GATE_CONTROLLER = 0, 1, 2
 GATE_BOUNDED_SEARCH = 0x100   # OR-ed into a gate mode: search bounded by the gate (pcdhip.h)
 LIDAR_NONE, LIDAR_ICP, LIDAR_ICP_GROUND = 0, 1, 2
+LIDAR_PROJ = 3
 LOSS_TRIVIAL, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2
 LAYOUT_XYZ_NRM, LAYOUT_AOS32 = 0, 1
 NORMALS_ORIENT_NONE, NORMALS_ORIENT_VIEWPOINT = 0, 1
@@ -175,6 +176,18 @@ class BASolveSummary(C.Structure):
                 ("linear_solver_ms", C.c_double)]
 
 
+class BAAssocOpts(C.Structure):
+    """pcd_ba_assoc_opts (pcdhip.h)."""
+    _fields_ = [("gate_mode", C.c_int32), ("d_max_range", C.c_void_p), ("max_range_count", C.c_uint64),
+                ("d_select", C.c_void_p), ("icp_weight", C.c_double), ("icp_ground_weight", C.c_double),
+                ("reserved", C.c_int32 * 8)]
+
+
+class BAAssocInfo(C.Structure):
+    _fields_ = [("num_queries", C.c_uint64), ("num_terms", C.c_uint64), ("num_icp", C.c_uint64),
+                ("num_icp_ground", C.c_uint64), ("assoc_ms", C.c_double), ("rebuild_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -237,6 +250,8 @@ ABI_SYMBOLS = [
     "pcd_ba_schur_solve_cholesky_device", "pcd_ba_schur_solve_cholesky",
     "pcd_normals_options_default", "pcd_cloud_estimate_normals_device", "pcd_cloud_estimate_normals",
     "pcd_voxel_options_default", "pcd_cloud_voxel_downsample", "pcd_cloud_voxel_downsample_device",
+    "pcd_ba_set_lidar_device", "pcd_ba_get_lidar", "pcd_ba_lidar_device", "pcd_ba_assoc_opts_default",
+    "pcd_ba_associate_lidar_device",
 ]
 
 
@@ -342,6 +357,15 @@ def lib():
         L.pcd_ba_schur_solve_cholesky_device.argtypes = [C.c_void_p] * 6
         L.pcd_ba_schur_solve_cholesky.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(BACholInfo)]
+    if hasattr(L, "pcd_ba_set_lidar_device"):
+        L.pcd_ba_set_lidar_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.pcd_ba_get_lidar.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)] + [C.c_void_p] * 5
+        L.pcd_ba_lidar_device.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_void_p)] * 5
+        L.pcd_ba_assoc_opts_default.argtypes = [C.POINTER(BAAssocOpts)]
+        L.pcd_ba_assoc_opts_default.restype = None
+        L.pcd_ba_associate_lidar_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BAAssocOpts), C.c_void_p,
+                                                    C.POINTER(BAAssocInfo)]
     _LIB = L
     return L
 
@@ -1311,6 +1335,92 @@ class BA:
         self.evaluate_device({"cost": out}, stream=stream)
         return out
 
+    # ---- LiDAR terms rebuilt on the device (pcd_ba_set_lidar_device / pcd_ba_associate_lidar_device) ----
+    def _stage(self, x, dtype):
+        """numpy (or anything array-like) -> contiguous torch device tensor on the handle's device; torch tensors are
+        converted in place of a copy when they already fit; None stays None"""
+        if x is None:
+            return None
+        torch, dev, _ = self._torch()
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype))
+        return x.to(device=dev, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+
+    def _terms_changed(self, n):
+        self.L = int(n)
+        self.lidar_point = self.lidar_abcd = self.lidar_weight = None   # stale: BA.get_lidar() has the current terms
+
+    def set_lidar_device(self, type, abcd, weight, point=None, lidar_xyz=None):
+        """pcd_ba_set_lidar_device: replace ALL LiDAR terms by those of the rows (type [Q] uint8, abcd [Q][4], point [Q]
+        int32 or None: row q is point q, lidar_xyz [Q][3] or None; numpy or torch).  A row becomes a term iff its type is
+        not 0 and its abcd holds no NaN; its weight is weight[type] (a sequence of 4: -, Icp, IcpGround, Proj).  Host
+        arrays are staged to the device through torch.  Synchronises the current stream once.  Returns the number of
+        terms; afterwards the handle equals one created with that term list."""
+        _, _, stream = self._torch()
+        t, a = self._stage(type, np.uint8), self._stage(abcd, np.float64)
+        p, x = self._stage(point, np.int32), self._stage(lidar_xyz, np.float64)
+        Q = int(t.numel())
+        if int(a.numel()) != 4 * Q or (p is not None and int(p.numel()) != Q) or (x is not None and int(x.numel()) != 3 * Q):
+            raise ValueError("set_lidar_device: type [Q], abcd [Q][4], point [Q], lidar_xyz [Q][3] disagree on Q")
+        w = np.ascontiguousarray(weight, np.float64)
+        if w.shape != (4,):
+            raise ValueError("set_lidar_device: weight must have 4 entries (by type: -, Icp, IcpGround, Proj)")
+        n = C.c_uint64(0)
+        if p is not None and Q == 0:
+            # an empty tensor has a null data pointer, which would read as "no point array": lend it one element
+            p = self._stage(np.zeros(1, np.int32), np.int32)
+        _check(lib().pcd_ba_set_lidar_device(self._h, Q, _ptr(p), _ptr(t), _ptr(a), _ptr(x), _vp(w), C.c_void_p(stream),
+                                             C.byref(n)))
+        self._terms_changed(n.value)
+        return int(n.value)
+
+    def get_lidar(self):
+        """pcd_ba_get_lidar: host copies of the current terms, dict of point [L] int32, abcd [L][4], weight [L], type [L]
+        uint8, lidar_xyz [L][3] (type and lidar_xyz are zero for terms that came from the constructor)"""
+        n = C.c_uint64(0)
+        _check(lib().pcd_ba_get_lidar(self._h, C.byref(n), None, None, None, None, None))
+        L = int(n.value)
+        out = dict(point=np.zeros(L, np.int32), abcd=np.zeros((L, 4)), weight=np.zeros(L), type=np.zeros(L, np.uint8),
+                   lidar_xyz=np.zeros((L, 3)))
+        _check(lib().pcd_ba_get_lidar(self._h, C.byref(n), _vp(out["point"]), _vp(out["abcd"]), _vp(out["weight"]),
+                                      _vp(out["type"]), _vp(out["lidar_xyz"])))
+        return out
+
+    def lidar_device(self):
+        """pcd_ba_lidar_device: (L, dict of raw device pointers point / abcd / weight / type / lidar_xyz), valid until the
+        terms change"""
+        n = C.c_uint64(0)
+        ptrs = [C.c_void_p() for _ in range(5)]
+        _check(lib().pcd_ba_lidar_device(self._h, C.byref(n), *[C.byref(p) for p in ptrs]))
+        return int(n.value), dict(zip(("point", "abcd", "weight", "type", "lidar_xyz"), [p.value for p in ptrs]))
+
+    def associate_lidar(self, cloud, max_range=None, gate_mode=GATE_MAPPER_GLOBAL, select=None, icp_weight=100.0,
+                        icp_ground_weight=1000.0):
+        """pcd_ba_associate_lidar_device: associate the handle's CURRENT points against `cloud` and install the accepted
+        associations as the handle's LiDAR terms (one per point at most, ascending point).  max_range: one value or one
+        per point (ignored for GATE_CONTROLLER); select: [P] mask of the points that are queries (None: all), applied
+        after a full association.  Returns the info dict (num_queries, num_terms, num_icp, num_icp_ground, assoc_ms,
+        rebuild_ms)."""
+        _, _, stream = self._torch()
+        o = BAAssocOpts()
+        lib().pcd_ba_assoc_opts_default(C.byref(o))
+        o.gate_mode = int(gate_mode)
+        mr = None
+        if (int(gate_mode) & 0xFF) != GATE_CONTROLLER:
+            mr = self._stage(np.atleast_1d(np.asarray(max_range, np.float64)) if not hasattr(max_range, "data_ptr")
+                             else max_range, np.float64)
+            o.d_max_range, o.max_range_count = mr.data_ptr(), int(mr.numel())
+        sel = self._stage(select, np.uint8)
+        if sel is not None:
+            if int(sel.numel()) != self.P:
+                raise ValueError("associate_lidar: select must have one entry per point")
+            o.d_select = sel.data_ptr()
+        o.icp_weight, o.icp_ground_weight = float(icp_weight), float(icp_ground_weight)
+        info = BAAssocInfo()
+        _check(lib().pcd_ba_associate_lidar_device(self._h, cloud._h, C.byref(o), C.c_void_p(stream), C.byref(info)))
+        self._terms_changed(info.num_terms)
+        return {k: getattr(info, k) for k, _ in BAAssocInfo._fields_}
+
 
 def pcg_opts(max_iterations=None, min_iterations=None, preconditioner=None, q_tolerance=None, r_tolerance=None):
     """pcd_ba_pcg_opts at the library's defaults (100, 0, schur_jacobi, 0.1, -1) with the given fields replaced"""
@@ -1369,6 +1479,23 @@ def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max
         r["rho"] = r["relative_decrease"]
         hist.append(r)
     return summary, hist
+
+
+def register_refine(ba, cloud, rounds, kd_max=1.5, kd_min=0.2, drop=0.1, gate_mode=GATE_MAPPER_GLOBAL, select=None,
+                    **solve_opts):
+    """The loop of IncrementalMapper::AdjustGlobalBundleByLidar (sfm/incremental_mapper.cc:1413-1478) on one handle,
+    GlobalOptNum advancing once per round: in round r every selected point searches within search_range_schedule(r)
+    (kd_max, kd_min, drop), BA.associate_lidar installs the accepted associations, ba_solve(**solve_opts) refines.
+    Nothing goes through the host and nothing that depends on the observations alone is rebuilt; no device work of its
+    own.  Returns one (association info, solve summary, iterations) per round."""
+    out = []
+    for r in range(int(rounds)):
+        rng = float(search_range_schedule(np.array([r], np.int32), kd_max, kd_min, drop)[0])
+        info = ba.associate_lidar(cloud, max_range=rng, gate_mode=gate_mode, select=select)
+        info["max_range"] = rng
+        summary, its = ba_solve(ba, **solve_opts)
+        out.append((info, summary, its))
+    return out
 
 
 def ba_solve_lm(ba, max_iterations=10, initial_radius=1e4, damping="marquardt", min_relative_decrease=1e-3,

@@ -20,6 +20,8 @@
 #include <unordered_set>
 #include <vector>
 
+#include <hip/hip_runtime_api.h>   // ReassociateLidar stages its range schedule and selection on the device
+
 #include "../../include/pcdhip.h"
 #include "lidar_hip.h"
 
@@ -223,7 +225,9 @@ class BundleAdjusterHip {
     if (NumResiduals() == 0) return false;
     for (uint8_t v : cam_refine_)
       if (v) return false;
-    if (!Create(device)) return false;
+    // after ReassociateLidar the live handle IS the problem (its parameters and terms are the flat arrays'): keep it
+    if (!(reassociated_ && ba_) && !Create(device)) return false;
+    reassociated_ = false;
     pcd_ba_solve_opts o;
     pcd_ba_solve_opts_default(&o);
     o.max_num_iterations = options_.max_num_iterations;
@@ -246,6 +250,74 @@ class BundleAdjusterHip {
     return true;
   }
   const pcd_ba_solve_summary& Summary() const { return summary_; }
+
+  // ---- re-association (HIP): the loop of IncrementalMapper::AdjustGlobalBundleByLidar (sfm/incremental_mapper.cc:
+  // 1413-1478) and of BundleAdjustmentController::Run (controllers/bundle_adjustment.cc:130-201) on the LIVE handle ----
+  // After Create() or Solve(): the handle's current points are associated against `cloud` (anything with handle()
+  // returning its pcd_cloud*, lidar::PointCloudProcess for one) and the accepted associations replace the handle's LiDAR
+  // terms (pcd_ba_associate_lidar_device): nothing is uploaded again, nothing that depends on the observations is
+  // rebuilt.  gate_mode: pcd_gate_mode, PCD_GATE_BOUNDED_SEARCH may be OR-ed in.  max_search_range: the schedule, one
+  // entry or one per point in the order of point_ids_ (sfm/incremental_mapper.cc:1423-1427; ignored for
+  // PCD_GATE_CONTROLLER).  select: the ids that are queries (the mapper's variable_point3D_ids; NULL: every point of
+  // the problem, the controller's loop).  Weights: the options' icp / icp_ground weights; a Proj term does not survive
+  // a re-association, so proj_lidar_constraint_weight has nothing left to weigh.
+  // Then config_.lidar_maps_ and the flat term arrays are refreshed from pcd_ba_get_lidar, so NumResiduals() and a
+  // later Solve -- which keeps this handle instead of creating a new one -- agree with the handle.
+  // false without a live handle, or when a call fails (pcd_last_error()); the problem is then as it was.
+  template <typename Cloud>
+  bool ReassociateLidar(Cloud& cloud, int gate_mode, const std::vector<double>& max_search_range,
+                        const std::unordered_set<point3D_t>* select = nullptr, pcd_ba_assoc_info* info = nullptr) {
+    if (!ba_ || !cloud.handle()) return false;
+    const size_t P = point_ids_.size();
+    struct DevMem {   // freed on every return
+      void* p = nullptr;
+      ~DevMem() { if (p) (void)hipFree(p); }
+      bool put(const void* src, size_t bytes) {
+        return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess &&
+               (bytes == 0 || hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess);
+      }
+    } d_range, d_select;
+    pcd_ba_assoc_opts o;
+    pcd_ba_assoc_opts_default(&o);
+    o.gate_mode = gate_mode;
+    o.icp_weight = options_.icp_lidar_constraint_weight;
+    o.icp_ground_weight = options_.icp_ground_lidar_constraint_weight;
+    if ((gate_mode & 0xFF) != PCD_GATE_CONTROLLER) {
+      if (max_search_range.size() != 1 && max_search_range.size() != P) return false;
+      if (!d_range.put(max_search_range.data(), max_search_range.size() * sizeof(double))) return false;
+      o.d_max_range = static_cast<const double*>(d_range.p);
+      o.max_range_count = max_search_range.size();
+    }
+    if (select) {
+      std::vector<uint8_t> mask(P, 0);
+      for (size_t p = 0; p < P; ++p) mask[p] = select->count(point_ids_[p]) ? 1 : 0;
+      if (!d_select.put(mask.data(), P)) return false;
+      o.d_select = static_cast<const uint8_t*>(d_select.p);
+    }
+    pcd_ba_assoc_info local{};
+    if (pcd_ba_associate_lidar_device(ba_, cloud.handle(), &o, nullptr, &local) != PCD_OK) return false;
+    if (info) *info = local;
+    uint64_t L = 0;
+    if (pcd_ba_get_lidar(ba_, &L, nullptr, nullptr, nullptr, nullptr, nullptr) != PCD_OK) return false;
+    std::vector<int32_t> point(L);
+    std::vector<double> abcd(4 * L), w(L), xyz(3 * L);
+    std::vector<uint8_t> type(L);
+    if (pcd_ba_get_lidar(ba_, &L, point.data(), abcd.data(), w.data(), type.data(), xyz.data()) != PCD_OK) return false;
+    lidar_point_ = point; lidar_abcd_ = abcd; lidar_w_ = w;
+    config_.lidar_maps_.clear();
+    for (uint64_t l = 0; l < L; ++l) {
+      LidarPoint lp;
+      lp.type = type[l] == PCD_LIDAR_ICP_GROUND ? LidarPointType::IcpGround : LidarPointType::Icp;
+      for (int k = 0; k < 3; ++k) lp.xyz[k] = xyz[3 * l + k];
+      for (int k = 0; k < 4; ++k) lp.abcd[k] = abcd[4 * l + k];
+      if (lp.type == LidarPointType::IcpGround) lp.color = {255, 255, 0};
+      else lp.color = {0, 0, 255};
+      config_.lidar_maps_[point_ids_[point[l]]] = lp;
+    }
+    reassociated_ = true;
+    return true;
+  }
+  const BundleAdjustmentConfig& config() const { return config_; }
   // what Solve hands to pcd_ba_solve: AUTO goes by the number of images in the config, as the reference does
   bool UsesDirectSolver() const {
     using T = BundleAdjustmentOptions::LinearSolverType;
@@ -281,6 +353,7 @@ class BundleAdjusterHip {
     point_const_.clear(); image_used_.clear(); image_ids_.clear(); point_ids_.clear();
     cam_refine_.clear(); camera_ids_.clear();
     cam_index_.clear(); image_index_.clear(); point_index_.clear(); point3D_num_observations_.clear();
+    reassociated_ = false;
   }
   int CameraIndex(camera_t id, const Reconstruction* rec) {
     auto it = cam_index_.find(id);
@@ -403,6 +476,7 @@ class BundleAdjusterHip {
   BundleAdjustmentConfig config_;
   pcd_ba* ba_ = nullptr;
   pcd_ba_solve_summary summary_{};
+  bool reassociated_ = false;   // ReassociateLidar ran on ba_ since the last Create: Solve keeps the handle
   std::unordered_map<camera_t, int> cam_index_;
   std::unordered_map<image_t, int> image_index_;
   std::unordered_map<point3D_t, int> point_index_;

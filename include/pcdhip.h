@@ -832,6 +832,81 @@ pcd_status pcd_ba_solve(pcd_ba* ba, const pcd_ba_solve_opts* opts, pcd_ba_solve_
                         pcd_ba_solve_iteration* iterations /*[max_num_iterations] or NULL*/);
 
 /* ------------------------------------------------------------------------
+ * Re-association of a handle's LiDAR terms on the device        
+ *   the loop of sfm/incremental_mapper.cc:1413-1478 IncrementalMapper::AdjustGlobalBundleByLidar and of
+ *   controllers/bundle_adjustment.cc:130-201 BundleAdjustmentController::Run: associate, solve, associate again
+ *   with a tighter radius, solve again -- without a host round trip and without rebuilding anything that depends
+ *   on the observations alone.
+ * pcd_ba_set_lidar_device replaces ALL LiDAR terms of the handle by those of Q device rows:
+ *   row q becomes a term iff type[q] != 0 and none of its four abcd values is NaN (the guard of
+ *   optim/bundle_adjustment.cc:1005-1009; an Inf passes, as there); its point is d_point[q] (d_point == NULL: q, and
+ *   Q must equal num_points), its weight is weight[type[q]] (:1013-1028); terms are numbered in ascending row order.
+ *   A point may receive several terms, rows may come in any point order, and the number of terms may grow, shrink,
+ *   become 0, or become non-zero on a handle created without terms.
+ * Contract: afterwards the handle is indistinguishable from one that pcd_ba_create built from the same description
+ *   with lidar_point / lidar_abcd / lidar_weight set to this term list -- every derived array is the one
+ *   pcd_ba_create would upload, byte for byte, so every later result on the handle (evaluate, blocks, Schur, solve,
+ *   filters) is bit-identical to the fresh handle's.
+ * Refused with PCD_ERR_INVALID, the handle left exactly as it was: a d_point entry outside [0, num_points) or a
+ *   type above 3 in ANY row (rows of type 0 included), a weight that is not finite for a type some term has,
+ *   Q >= 0xFFFFFFF0, d_point == NULL with Q != num_points.  The new layout is built in buffers of its own and
+ *   swapped in only on success.
+ * Guards: a NULL handle or argument -> INVALID; no gfx950 -> NO_DEVICE; a capturing stream -> UNSUPPORTED before
+ *   anything is allocated (as every _device call).
+ * The call synchronises `stream` ONCE: the number of terms (read back together with the validation record) sizes
+ *   buffers and launch grids, as the row count does in pcd_cloud_voxel_downsample_device.  The rest is enqueued on
+ *   `stream`; later work on the handle must be ordered behind it (the same stream, or the legacy stream).
+ * What the call invalidates: pointers handed out by an earlier pcd_ba_evaluate_blocks* (the pinned buffer follows the
+ *   number of terms) and by pcd_ba_lidar_device; the Schur state of the last call (pcd_ba_schur_solve_* and the
+ *   back-substitution return their "no Schur state" PCD_ERR_INVALID until the next Schur call).  The co-visibility
+ *   structure and the elimination scratch are kept: they depend on the observations alone.
+ * No atomics; no order depends on launch geometry: a repeated call is bitwise identical.
+ * --------------------------------------------------------------------- */
+pcd_status pcd_ba_set_lidar_device(pcd_ba* ba, uint64_t Q,
+    const int32_t* d_point   /* [Q] point of row q; NULL: row q is point q (then Q must equal P) */,
+    const uint8_t* d_type    /* [Q] pcd_lidar_type or PCD_LIDAR_PROJ; 0 = no term */,
+    const double*  d_abcd    /* [Q][4] */,
+    const double*  d_lidar_xyz /* [Q][3] or NULL: kept per term for the outlier filter */,
+    const double   weight[4] /* host; by type: [1] Icp, [2] IcpGround, [3] Proj; [0] unused */,
+    void* stream, uint64_t* num_terms /* host, may be NULL */);
+/* Host copies of the current terms: point [L], abcd [L][4], weight [L], type [L], lidar_xyz [L][3]; every pointer may
+ * be NULL (size the arrays with num_terms first).  type and lidar_xyz are zero for terms that came from pcd_ba_create,
+ * which knows neither. */
+pcd_status pcd_ba_get_lidar(pcd_ba* ba, uint64_t* num_terms, int32_t* point, double* abcd, double* weight,
+                            uint8_t* type, double* lidar_xyz);
+/* The same arrays as device pointers (every output may be NULL), e.g. for pcd_filter_lidar_outlier_device on the
+ * terms (gather the points by d_point first).  Valid until the next pcd_ba_set_lidar_device /
+ * pcd_ba_associate_lidar_device / pcd_ba_destroy on the handle. */
+pcd_status pcd_ba_lidar_device(pcd_ba* ba, uint64_t* num_terms, const int32_t** d_point, const double** d_abcd,
+                               const double** d_weight, const uint8_t** d_type, const double** d_lidar_xyz);
+
+/* One call for "associate this handle's CURRENT points against this cloud and install the terms":
+ * pcd_associate_device with the handle's device points [P][3] as the queries, the rows written to scratch owned by the
+ * BA handle, then the machinery of pcd_ba_set_lidar_device with row = point and weight = {-, icp_weight,
+ * icp_ground_weight, -}.  d_select is applied AFTER a full-P association: the association rows are exactly those of
+ * pcd_associate_device on all points, and an unselected row then counts as type 0.  One term per point at most, in
+ * ascending point order: what the reference's loops (point-id order, a map keyed by point) produce.
+ * Refusals: handle and cloud on different devices -> INVALID; a cloud that is a shard or strided (index_stride != 1 or
+ * index_base != 0) -> UNSUPPORTED; otherwise those of pcd_associate_device and pcd_ba_set_lidar_device.  P == 0:
+ * PCD_OK with zero counts.  With info the call also waits for its last kernel, to report rebuild_ms. */
+typedef struct {
+  int32_t gate_mode;            /* pcd_gate_mode, PCD_GATE_BOUNDED_SEARCH may be OR-ed in */
+  const double* d_max_range;    /* device, [P] or [1]; ignored for PCD_GATE_CONTROLLER */
+  uint64_t max_range_count;
+  const uint8_t* d_select;      /* device [P] or NULL: which points are queries (the mapper's variable points; the controller: all) */
+  double icp_weight, icp_ground_weight;
+  int32_t reserved[8];
+} pcd_ba_assoc_opts;
+typedef struct {
+  uint64_t num_queries;         /* selected points (P without d_select) */
+  uint64_t num_terms, num_icp, num_icp_ground;
+  double assoc_ms, rebuild_ms;  /* device time of the association and of the rebuild (its one synchronisation included) */
+} pcd_ba_assoc_info;
+void pcd_ba_assoc_opts_default(pcd_ba_assoc_opts* opts);   /* MAPPER_GLOBAL, NULL, 0, NULL, 100, 1000 (shim/ba_problem.h:71-72) */
+pcd_status pcd_ba_associate_lidar_device(pcd_ba* ba, pcd_cloud* cloud, const pcd_ba_assoc_opts* opts,
+                                         void* stream, pcd_ba_assoc_info* info /* host, may be NULL */);
+
+/* ------------------------------------------------------------------------
  * Exact SIFT descriptor matching (stretch row a19)
  *   replaces feature/sift.cc:1041-1054 MatchSiftFeaturesCPUBruteForce =
  *     feature/sift.cc:171-204 ComputeSiftDistanceMatrix (int32 dot of uint8 x 128) +
