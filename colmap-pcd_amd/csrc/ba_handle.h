@@ -1,5 +1,5 @@
 // ba_handle.h -- the bundle-adjustment handle as every BA unit sees it, and the sizes builder and launchers must agree
-// on (kImgSeg, kCostBlocks, cost_blocks).  Internal; no kernels here.
+// on (kImgSeg, kCostBlocks, cost_blocks, the element counts of the block form).  Internal; no kernels here.
 //   ba_build.hip  makes and destroys it: pcd_ba_create uploads the problem and builds the derived layouts below
 //   ba.hip        evaluates on it: the kernels that read BaDev, and every pcd_ba_evaluate* / filter entry point
 //   ba_solve.hip  point elimination, PCG, LM loop (its own state hangs off pcd_ba::schur)
@@ -68,12 +68,30 @@ struct BaLidarScratch {
 struct BaSchur;
 struct BaSchurDelete { void operator()(BaSchur* s) const; };
 
+// Element counts of the block form, each written once: a vector over n images or slots, n 6x6 blocks (per image; the
+// reduced system's diagonal or pair blocks), the 6x3 blocks W / Y of O observations, the 3x3 blocks of P points and a
+// vector over them.  at_least_1: for a buffer a kernel is handed even when its count is 0.
+inline size_t at_least_1(size_t n) { return std::max<size_t>(n, 1); }
+inline size_t slot_vec(uint64_t n) { return 6 * (size_t)n; }
+inline size_t blocks_6x6(uint64_t n) { return 36 * (size_t)n; }
+inline size_t obs_blocks(uint64_t O) { return 18 * (size_t)O; }
+inline size_t point_blocks(uint64_t P) { return 9 * (size_t)P; }
+inline size_t point_vec(uint64_t P) { return 3 * (size_t)P; }
+
 template <typename T>
 static pcd_status upload(DevBuf<T>& b, const T* src, size_t n) {
-  PCD_TRY(b.reserve(std::max<size_t>(n, 1)));
+  PCD_TRY(b.reserve(at_least_1(n)));
   if (n) PCD_HIP_TRY(hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice));
   return PCD_OK;
 }
+// its counterpart for a host form's copy-backs: n elements of a buffer, if the caller wants them and there are any
+template <typename T>
+static pcd_status copy_back(void* dst, const DevBuf<T>& src, size_t n) {
+  if (dst && n) PCD_HIP_TRY(hipMemcpy(dst, src.p, n * sizeof(T), hipMemcpyDeviceToHost));
+  return PCD_OK;
+}
+template <typename... B>
+static uint64_t dev_bytes(const B&... b) { return (uint64_t(0) + ... + (b.n * sizeof(*b.p))); }   // capacity held
 
 // The normal equations at the handle's parameters (ba.hip): point blocks and the cost (k_ba_points, k_sum_partials),
 // then image blocks with W riding on the image pass (k_ba_images, k_ba_images_reduce), on stream s.  w_order[e] is
@@ -132,13 +150,16 @@ struct pcd_ba {
   // point elimination (pcd_ba_schur*): built on the first call, so pcd_ba_create costs existing users nothing
   bool refines_intrinsics = false;   // some camera_refine byte is set: the reduced system would need camera rows
   std::unique_ptr<pcd::BaSchur, pcd::BaSchurDelete> schur;
+  // the optional constant masks as the kernels take them: nullptr when the problem gave none
+  const uint8_t* const_poses() const { return has_cpose ? image_const_pose.p : nullptr; }
+  const uint8_t* const_tvec() const { return has_ctvec ? image_const_tvec.p : nullptr; }
+  const uint8_t* const_points() const { return has_cpt ? point_const.p : nullptr; }
   pcd::BaDev dev() const {
     pcd::BaDev d;
     d.cam_model = cam_model.p; d.cam_off = cam_off.p; d.cam_params = cam_params.p;
     d.poses = poses.p; d.image_cam = image_cam.p;
-    d.image_const_pose = has_cpose ? image_const_pose.p : nullptr;
-    d.image_const_tvec = has_ctvec ? image_const_tvec.p : nullptr;
-    d.points = points.p; d.point_const = has_cpt ? point_const.p : nullptr;
+    d.image_const_pose = const_poses(); d.image_const_tvec = const_tvec();
+    d.points = points.p; d.point_const = const_points();
     d.obs_image = obs_image.p; d.obs_point = obs_point.p; d.obs_xy = obs_xy.p;
     d.lidar_point = lidar_point.p; d.lidar_abcd = lidar_abcd.p; d.lidar_w = lidar_w.p;
     d.pt_order = pt_order.p; d.slice_start = slice_start.p; d.sell_img = sell_img.p; d.sell_xy = sell_xy.p;

@@ -6,6 +6,10 @@
 // The blocks it eliminates come from ba.hip, which this unit reaches through two calls only: ba_normal_equations
 // (ba_handle.h) for H, g, W and the cost, and pcd_ba_evaluate_device for the cost of a trial step.  No evaluation
 // kernel is compiled here.
+//
+// Host side, behind the kernels: BaSchur, the solver state grouped by owner; schur_build over schur_read_back,
+// schur_assign_slots, schur_point_lists, schur_diag_blocks, schur_pair_blocks (both on schur_walk_row), schur_row_lists
+// and schur_upload; the PCG batches; pcd_ba_solve over lm_check_opts, lm_reserve, lm_enqueue_linear, lm_try_step, lm_decide.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -711,50 +715,53 @@ __global__ void k_chol_lm_info(const pcd_ba_chol_info* __restrict__ c, pcd_ba_pc
   *out = o;
 }
 
-// Host-built structure (first Schur call) and the numeric state of the last Schur call
+// The solver state of a handle, one group per owner; the element counts are ba_handle.h's.  device_bytes()
+// (pcd_ba_schur_stats) is the sum of the groups' bytes(): every DevBuf but the 8 bytes of num.skip_cnt.
 struct BaSchur {
-  bool built = false;
-  int ns = 0;
-  uint64_t npairs = 0, nent = 0;
-  double build_ms = 0.0;
-  std::vector<int32_t> h_slot, h_pair_i, h_pair_j;
-  DevBuf<int> img_slot, slot_img;
-  DevBuf<uint32_t> blk_start, ent_a, ent_b, pair_ij, iota, obs_pos;
-  bool valid = false;   // a Schur call has filled the state below
-  DevBuf<double> Himg, gimg, Hpt, gpt, Wim, Y, Vinv, Vg, Dpt, Dimg, Sdiag, Soff, rhs, md_partial, md;
-  DevBuf<uint32_t> skip_partial;
-  DevBuf<unsigned long long> skip_cnt;
-  DevBuf<double> cost, dense;   // dense: staging of the host form's S
-  // rows of S for the product y = S x (built with the structure): row i = its blocks in ascending partner slot
-  DevBuf<uint32_t> row_start, row_blk, row_col;   // [ns+1]; block (< ns: diagonal, else ns + pair); partner << 1 | transposed
-  bool own_diag = false, own_off = false, own_rhs = false;   // the last Schur call left S_diag / S_off / rhs in the handle
-  // PCG state (pcd_ba_schur_solve_pcg*) and the LM loop's buffers (pcd_ba_solve)
-  DevBuf<double> Minv, cg_x0, cg_x1, cg_r, cg_z, cg_p0, cg_p1, cg_w, cg_pw, cg_partial, cg_out;
-  DevBuf<PcgState> cg_state;
-  DevBuf<pcd_ba_pcg_info> cg_info;
-  PinnedBuf<int> cg_flag;
-  int cg_it = 0;   // iterations enqueued in the running solve (buffer parity)
-  DevBuf<double> lm_dpose, lm_dpoint, lm_poses, lm_points, lm_cand_cost, lm_gpart;
-  DevBuf<LmRecord> lm_rec;
-  PinnedBuf<LmRecord> lm_host;
-  // direct solve (pcd_ba_schur_solve_cholesky*): the padded dense scratch of ba_chol.h, allocated on first use
-  DevBuf<double> chol_A, chol_S, chol_rhs, chol_out;   // chol_S / chol_rhs (freed after each call) / chol_out: staging of the host form
-  DevBuf<pcd_ba_chol_info> chol_info, chol_info_out;
-  // device memory held (pcd_ba_schur_stats): every DevBuf above but the 8 bytes of skip_cnt
-  uint64_t device_bytes() const {
-    auto sum = [](const auto&... b) { return (uint64_t(0) + ... + (b.n * sizeof(*b.p))); };
-    return sum(img_slot, slot_img, blk_start, ent_a, ent_b, pair_ij, iota, obs_pos, Himg, gimg, Hpt, gpt, Wim, Y, Vinv,
-               Vg, Dpt, Dimg, Sdiag, Soff, rhs, md_partial, md, skip_partial, cost, dense, row_start, row_blk, row_col,
-               Minv, cg_x0, cg_x1, cg_r, cg_z, cg_p0, cg_p1, cg_w, cg_pw, cg_partial, cg_out, cg_state, cg_info,
-               lm_dpose, lm_dpoint, lm_poses, lm_points, lm_cand_cost, lm_gpart, lm_rec, chol_A, chol_S, chol_rhs,
-               chol_out, chol_info, chol_info_out);
-  }
+  struct Structure {   // built on the host by the first Schur call (schur_build), then read only
+    bool built = false; int ns = 0; uint64_t npairs = 0, nent = 0; double build_ms = 0.0;
+    uint32_t nblk() const { return (uint32_t)(ns + npairs); }   // the ns diagonal blocks, then the pair blocks
+    std::vector<int32_t> h_slot, h_pair_i, h_pair_j;
+    DevBuf<int> img_slot, slot_img;
+    DevBuf<uint32_t> blk_start, ent_a, ent_b, pair_ij, iota, obs_pos;
+    // rows of S for y = S x, ascending partner slot: [ns+1]; block (< ns: diagonal, else ns + pair); partner << 1 | transposed
+    DevBuf<uint32_t> row_start, row_blk, row_col;
+    uint64_t bytes() const {
+      return dev_bytes(img_slot, slot_img, blk_start, ent_a, ent_b, pair_ij, iota, obs_pos, row_start, row_blk, row_col);
+    }
+  } st;
+  struct Numeric {   // the last Schur call (pcd_ba_schur_device)
+    bool valid = false;   // it has filled the buffers below ...
+    bool own_diag = false, own_off = false, own_rhs = false;   // ... and left S_diag / S_off / rhs in the handle
+    DevBuf<double> Himg, gimg, Hpt, gpt, Wim, Y, Vinv, Vg, Dpt, Dimg, Sdiag, Soff, rhs, md_partial, md;
+    DevBuf<uint32_t> skip_partial; DevBuf<unsigned long long> skip_cnt;
+    DevBuf<double> cost, dense;   // dense: staging of the host form's S
+    uint64_t bytes() const {
+      return dev_bytes(Himg, gimg, Hpt, gpt, Wim, Y, Vinv, Vg, Dpt, Dimg, Sdiag, Soff, rhs, md_partial, md, skip_partial,
+                       cost, dense);
+    }
+  } num;
+  struct Pcg {   // pcd_ba_schur_solve_pcg*
+    DevBuf<double> Minv, x0, x1, r, z, p0, p1, w, pw, partial, out;   // out: staging of the host form
+    DevBuf<PcgState> state; DevBuf<pcd_ba_pcg_info> info; PinnedBuf<int> flag;
+    int it = 0;   // iterations enqueued in the running solve (buffer parity)
+    uint64_t bytes() const { return dev_bytes(Minv, x0, x1, r, z, p0, p1, w, pw, partial, out, state, info); }
+  } cg;
+  struct Lm {   // pcd_ba_solve: the step, the accepted parameters, the record of an iteration
+    DevBuf<double> dpose, dpoint, poses, points, cand_cost, gpart;
+    DevBuf<LmRecord> rec; PinnedBuf<LmRecord> host;
+    uint64_t bytes() const { return dev_bytes(dpose, dpoint, poses, points, cand_cost, gpart, rec); }
+  } lm;
+  struct Chol {   // pcd_ba_schur_solve_cholesky*: the padded dense scratch of ba_chol.h, allocated on first use
+    DevBuf<double> A, S, rhs, out;   // S / rhs (freed after each call) / out: staging of the host form
+    DevBuf<pcd_ba_chol_info> info, info_out;
+    uint64_t bytes() const { return dev_bytes(A, S, rhs, out, info, info_out); }
+  } chol;
+  uint64_t device_bytes() const { return st.bytes() + num.bytes() + cg.bytes() + lm.bytes() + chol.bytes(); }
 };
 
 void BaSchurDelete::operator()(BaSchur* s) const { delete s; }
-void ba_schur_invalidate(pcd_ba* b) {
-  if (b->schur) b->schur->valid = false;
-}
+void ba_schur_invalidate(pcd_ba* b) { if (b->schur) b->schur->num.valid = false; }
 
 }  // namespace pcd
 
@@ -777,130 +784,139 @@ static pcd_status schur_guard(pcd_ba* b) {
 // read back once.  Blocks: the ns diagonal blocks, then the pair blocks in ascending (i, j).  Entries (a, b) of a block:
 // a ascending (image-major position in image i), then b ascending (image j).  A diagonal block holds (a, a) and the
 // pairs of a point observed more than once in the image.  Only variable-pose observations of non-constant points
-// take part.
-static pcd_status schur_build(pcd_ba* b) {
-  if (!b->schur) b->schur.reset(new BaSchur());
-  BaSchur& S = *b->schur;
-  if (S.built) return PCD_OK;
-  const auto t0 = std::chrono::steady_clock::now();
+// take part.  Every sum downstream runs in the order of these lists, so the stages below keep it to the entry.
+struct SchurIndex {   // what travels between the stages; e = image-major position, o = observation in the caller's order
+  std::vector<int32_t> opt; std::vector<uint32_t> iobs;   // read back: [O] point of o; o at e
+  std::vector<uint32_t> ist; std::vector<uint8_t> cpose, cpt;   // [I+1] first e of an image; [I], [P] the masks (0: none given)
+  std::vector<int32_t> slot_img, eslot, ept;   // [ns] image of a slot; [O] slot of e (-1: not eliminated) and its point
+  std::vector<uint32_t> pst, pli;              // [P+1] -> a point's eliminated observations, ascending e
+};
+struct SchurLists {   // what schur_upload sends: [O] e of observation o, the identity; entries; row lists; [nblk+1]
+  std::vector<uint32_t> obs_pos, iota, ea, eb, rst, rblk, rcol; std::vector<uint64_t> blk;
+};
+
+static pcd_status schur_read_back(const pcd_ba* b, SchurIndex& x) {
   const uint64_t O = b->O;
-  const int I = b->I, P = b->P;
-  std::vector<int32_t> oimg(O), opt(O);
-  std::vector<uint32_t> ist((size_t)I + 1), iobs(O);
-  std::vector<uint8_t> cpose(I, 0), cpt(P, 0);
+  x.opt.resize(O); x.iobs.resize(O); x.ist.resize((size_t)b->I + 1); x.cpose.assign(b->I, 0); x.cpt.assign(b->P, 0);
   if (O) {
-    PCD_HIP_TRY(hipMemcpy(oimg.data(), b->obs_image.p, O * sizeof(int32_t), hipMemcpyDeviceToHost));
-    PCD_HIP_TRY(hipMemcpy(opt.data(), b->obs_point.p, O * sizeof(int32_t), hipMemcpyDeviceToHost));
-    PCD_HIP_TRY(hipMemcpy(iobs.data(), b->img_obs.p, O * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipMemcpy(x.opt.data(), b->obs_point.p, O * sizeof(int32_t), hipMemcpyDeviceToHost));
+    PCD_HIP_TRY(hipMemcpy(x.iobs.data(), b->img_obs.p, O * sizeof(uint32_t), hipMemcpyDeviceToHost));
   }
-  PCD_HIP_TRY(hipMemcpy(ist.data(), b->img_obs_start.p, ist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (b->has_cpose) PCD_HIP_TRY(hipMemcpy(cpose.data(), b->image_const_pose.p, I, hipMemcpyDeviceToHost));
-  if (b->has_cpt) PCD_HIP_TRY(hipMemcpy(cpt.data(), b->point_const.p, P, hipMemcpyDeviceToHost));
-  S.h_slot.assign(I, -1);
-  std::vector<int32_t> slot_img;
+  PCD_HIP_TRY(hipMemcpy(x.ist.data(), b->img_obs_start.p, x.ist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (b->const_poses()) PCD_HIP_TRY(hipMemcpy(x.cpose.data(), b->const_poses(), b->I, hipMemcpyDeviceToHost));
+  if (b->const_points()) PCD_HIP_TRY(hipMemcpy(x.cpt.data(), b->const_points(), b->P, hipMemcpyDeviceToHost));
+  return PCD_OK;
+}
+
+static void schur_assign_slots(SchurIndex& x, std::vector<int32_t>& h_slot, SchurLists& l) {
+  const int I = (int)x.cpose.size(); const size_t O = x.opt.size();
+  h_slot.assign(I, -1);
   for (int i = 0; i < I; ++i)
-    if (!cpose[i]) { S.h_slot[i] = (int32_t)slot_img.size(); slot_img.push_back(i); }
-  const int ns = (int)slot_img.size();
-  S.ns = ns;
-  std::vector<uint32_t> obs_pos(O), iota(O);
-  std::vector<int32_t> eslot(O), ept(O);
+    if (!x.cpose[i]) { h_slot[i] = (int32_t)x.slot_img.size(); x.slot_img.push_back(i); }
+  x.eslot.resize(O); x.ept.resize(O); l.obs_pos.resize(O); l.iota.resize(O);
   for (int i = 0; i < I; ++i)
-    for (uint32_t e = ist[i]; e < ist[i + 1]; ++e) {
-      const uint32_t o = iobs[e];
-      obs_pos[o] = e; iota[e] = e; ept[e] = opt[o];
-      eslot[e] = cpt[opt[o]] ? -1 : S.h_slot[i];   // -1: takes no part in the elimination
+    for (uint32_t e = x.ist[i]; e < x.ist[i + 1]; ++e) {
+      const uint32_t o = x.iobs[e];
+      l.obs_pos[o] = e; l.iota[e] = e; x.ept[e] = x.opt[o];
+      x.eslot[e] = x.cpt[x.opt[o]] ? -1 : h_slot[i];   // -1: takes no part in the elimination
     }
-  // eliminated observations of every point, ascending image-major position
-  std::vector<uint32_t> pst((size_t)P + 1, 0), pli;
-  for (uint64_t e = 0; e < O; ++e) if (eslot[e] >= 0) pst[(size_t)ept[e] + 1]++;
-  for (int p = 0; p < P; ++p) pst[p + 1] += pst[p];
-  pli.resize(pst[P]);
-  {
-    std::vector<uint32_t> cur(pst.begin(), pst.end() - 1);
-    for (uint64_t e = 0; e < O; ++e) if (eslot[e] >= 0) pli[cur[ept[e]]++] = (uint32_t)e;
+}
+
+static void schur_point_lists(int P, SchurIndex& x) {
+  const size_t O = x.eslot.size();
+  x.pst.assign((size_t)P + 1, 0);
+  for (size_t e = 0; e < O; ++e) if (x.eslot[e] >= 0) x.pst[(size_t)x.ept[e] + 1]++;
+  for (int p = 0; p < P; ++p) x.pst[p + 1] += x.pst[p];
+  x.pli.resize(x.pst[P]);
+  std::vector<uint32_t> cur(x.pst.begin(), x.pst.end() - 1);
+  for (size_t e = 0; e < O; ++e) if (x.eslot[e] >= 0) x.pli[cur[x.ept[e]]++] = (uint32_t)e;
+}
+
+// The walk all three block passes make: every eliminated observation e of slot s (ascending) against every entry of its
+// point's list (ascending) -> f(e, the partner's position, the partner's slot)
+template <typename F>
+static inline void schur_walk_row(const SchurIndex& x, int s, F&& f) {
+  const int32_t* eslot = x.eslot.data(); const int32_t* ept = x.ept.data();
+  const uint32_t* pst = x.pst.data(); const uint32_t* pli = x.pli.data();
+  const int im = x.slot_img[s];
+  for (uint32_t e = x.ist[im], end = x.ist[im + 1]; e < end; ++e) {
+    if (eslot[e] < 0) continue;
+    for (uint32_t k = pst[ept[e]], kend = pst[ept[e] + 1]; k < kend; ++k) f(e, pli[k], (int)eslot[pli[k]]);
   }
-  std::vector<uint64_t> blk(1, 0);
-  std::vector<uint32_t> ea, eb;
-  for (int s = 0; s < ns; ++s) {   // diagonal blocks
-    const int im = slot_img[s];
-    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
-      if (eslot[e] < 0) continue;
-      const int p = ept[e];
-      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k)
-        if (eslot[pli[k]] == s) { ea.push_back(e); eb.push_back(pli[k]); }
-    }
-    blk.push_back(ea.size());
+}
+
+static void schur_diag_blocks(const SchurIndex& x, SchurLists& l) {
+  l.blk.assign(1, 0);
+  for (int s = 0; s < (int)x.slot_img.size(); ++s) {
+    schur_walk_row(x, s, [&](uint32_t e, uint32_t f, int j) { if (j == s) { l.ea.push_back(e); l.eb.push_back(f); } });
+    l.blk.push_back(l.ea.size());
   }
-  S.h_pair_i.clear(); S.h_pair_j.clear();
-  std::vector<uint32_t> cnt(ns, 0);
-  std::vector<uint64_t> cur(ns, 0);
-  std::vector<int> touched;
-  for (int s = 0; s < ns; ++s) {   // pair blocks of row s: a per-row counting sort over the partner slot
-    const int im = slot_img[s];
+}
+
+// pair blocks of row s behind the diagonal blocks: a per-row counting sort over the partner slot j > s
+static void schur_pair_blocks(const SchurIndex& x, std::vector<int32_t>& pair_i, std::vector<int32_t>& pair_j, SchurLists& l) {
+  const int ns = (int)x.slot_img.size();
+  pair_i.clear(); pair_j.clear();
+  std::vector<uint32_t> cnt(ns, 0); std::vector<uint64_t> cur(ns, 0); std::vector<int> touched;
+  for (int s = 0; s < ns; ++s) {
     touched.clear();
-    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
-      if (eslot[e] < 0) continue;
-      const int p = ept[e];
-      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k) {
-        const int j = eslot[pli[k]];
-        if (j > s && cnt[j]++ == 0) touched.push_back(j);
-      }
-    }
+    schur_walk_row(x, s, [&](uint32_t, uint32_t, int j) { if (j > s && cnt[j]++ == 0) touched.push_back(j); });
     std::sort(touched.begin(), touched.end());
-    uint64_t off = ea.size();
-    for (int j : touched) {
-      cur[j] = off; off += cnt[j];
-      S.h_pair_i.push_back(s); S.h_pair_j.push_back(j);
-      blk.push_back(off);
-    }
-    ea.resize(off); eb.resize(off);
-    for (uint32_t e = ist[im]; e < ist[im + 1]; ++e) {
-      if (eslot[e] < 0) continue;
-      const int p = ept[e];
-      for (uint32_t k = pst[p]; k < pst[p + 1]; ++k) {
-        const int j = eslot[pli[k]];
-        if (j > s) { ea[cur[j]] = e; eb[cur[j]++] = pli[k]; }
-      }
-    }
+    uint64_t off = l.ea.size();
+    for (int j : touched) { cur[j] = off; off += cnt[j]; pair_i.push_back(s); pair_j.push_back(j); l.blk.push_back(off); }
+    l.ea.resize(off); l.eb.resize(off);
+    schur_walk_row(x, s, [&](uint32_t e, uint32_t f, int j) { if (j > s) { l.ea[cur[j]] = e; l.eb[cur[j]++] = f; } });
     for (int j : touched) cnt[j] = 0;
   }
-  if (ea.size() >= 0xFFFFFFF0ull || blk.size() >= 0xFFFFFFF0ull) {
-    set_error("point elimination: %zu block entries exceed the 32-bit layout", ea.size());
+}
+
+// row lists of the product: transposes of the (k, s) blocks (k ascending), the diagonal, the (s, j) blocks
+static void schur_row_lists(int ns, const std::vector<int32_t>& pair_i, const std::vector<int32_t>& pair_j, SchurLists& l) {
+  const size_t npairs = pair_i.size();
+  l.rst.assign((size_t)ns + 1, 0);
+  for (int s = 0; s < ns; ++s) l.rst[(size_t)s + 1] = 1;
+  for (size_t q = 0; q < npairs; ++q) { l.rst[(size_t)pair_i[q] + 1]++; l.rst[(size_t)pair_j[q] + 1]++; }
+  for (int s = 0; s < ns; ++s) l.rst[(size_t)s + 1] += l.rst[s];
+  l.rblk.resize(l.rst[ns]); l.rcol.resize(l.rst[ns]);
+  std::vector<uint32_t> pos(l.rst.begin(), l.rst.end() - 1);
+  auto put = [&](int row, size_t blk, uint32_t col) { const uint32_t t = pos[row]++; l.rblk[t] = (uint32_t)blk; l.rcol[t] = col; };
+  for (size_t q = 0; q < npairs; ++q) put(pair_j[q], ns + q, ((uint32_t)pair_i[q] << 1) | 1u);
+  for (int s = 0; s < ns; ++s) put(s, s, (uint32_t)s << 1);
+  for (size_t q = 0; q < npairs; ++q) put(pair_i[q], ns + q, (uint32_t)pair_j[q] << 1);
+}
+
+static pcd_status schur_upload(BaSchur::Structure& T, const SchurIndex& x, const SchurLists& l) {
+  const std::vector<uint32_t> blk32(l.blk.begin(), l.blk.end()); std::vector<uint32_t> pij(2 * T.npairs);
+  for (uint64_t q = 0; q < T.npairs; ++q) { pij[2 * q] = (uint32_t)T.h_pair_i[q]; pij[2 * q + 1] = (uint32_t)T.h_pair_j[q]; }
+  auto up = [](auto& buf, const auto& v) { return upload(buf, v.data(), v.size()); };
+  PCD_TRY(up(T.img_slot, T.h_slot)); PCD_TRY(up(T.slot_img, x.slot_img)); PCD_TRY(up(T.blk_start, blk32));
+  PCD_TRY(up(T.ent_a, l.ea)); PCD_TRY(up(T.ent_b, l.eb)); PCD_TRY(up(T.pair_ij, pij));
+  PCD_TRY(up(T.iota, l.iota)); PCD_TRY(up(T.obs_pos, l.obs_pos));
+  PCD_TRY(up(T.row_start, l.rst)); PCD_TRY(up(T.row_blk, l.rblk)); PCD_TRY(up(T.row_col, l.rcol));
+  return PCD_OK;
+}
+
+static pcd_status schur_build(pcd_ba* b) {
+  if (!b->schur) b->schur.reset(new BaSchur());
+  BaSchur::Structure& T = b->schur->st;
+  if (T.built) return PCD_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  SchurIndex x; SchurLists l;
+  PCD_TRY(schur_read_back(b, x));
+  schur_assign_slots(x, T.h_slot, l);
+  T.ns = (int)x.slot_img.size();
+  schur_point_lists(b->P, x);
+  schur_diag_blocks(x, l);
+  schur_pair_blocks(x, T.h_pair_i, T.h_pair_j, l);
+  if (l.ea.size() >= 0xFFFFFFF0ull || l.blk.size() >= 0xFFFFFFF0ull) {
+    set_error("point elimination: %zu block entries exceed the 32-bit layout", l.ea.size());
     return PCD_ERR_UNSUPPORTED;
   }
-  S.npairs = S.h_pair_i.size();
-  S.nent = ea.size();
-  std::vector<uint32_t> blk32(blk.begin(), blk.end()), pij(2 * S.npairs);
-  for (uint64_t q = 0; q < S.npairs; ++q) { pij[2 * q] = (uint32_t)S.h_pair_i[q]; pij[2 * q + 1] = (uint32_t)S.h_pair_j[q]; }
-  PCD_TRY(upload(S.img_slot, S.h_slot.data(), (size_t)I));
-  PCD_TRY(upload(S.slot_img, slot_img.data(), slot_img.size()));
-  PCD_TRY(upload(S.blk_start, blk32.data(), blk32.size()));
-  PCD_TRY(upload(S.ent_a, ea.data(), ea.size()));
-  PCD_TRY(upload(S.ent_b, eb.data(), eb.size()));
-  PCD_TRY(upload(S.pair_ij, pij.data(), pij.size()));
-  PCD_TRY(upload(S.iota, iota.data(), iota.size()));
-  PCD_TRY(upload(S.obs_pos, obs_pos.data(), obs_pos.size()));
-  {   // row lists of the product: transposes of the (k, s) blocks (k ascending), the diagonal, the (s, j) blocks
-    std::vector<uint32_t> rst((size_t)ns + 1, 0);
-    for (int s = 0; s < ns; ++s) rst[(size_t)s + 1] = 1;
-    for (uint64_t q = 0; q < S.npairs; ++q) { rst[(size_t)S.h_pair_i[q] + 1]++; rst[(size_t)S.h_pair_j[q] + 1]++; }
-    for (int s = 0; s < ns; ++s) rst[(size_t)s + 1] += rst[s];
-    std::vector<uint32_t> rblk(rst[ns]), rcol(rst[ns]), pos(rst.begin(), rst.end() - 1);
-    for (uint64_t q = 0; q < S.npairs; ++q) {
-      const uint32_t t = pos[S.h_pair_j[q]]++;
-      rblk[t] = (uint32_t)(ns + q); rcol[t] = ((uint32_t)S.h_pair_i[q] << 1) | 1u;
-    }
-    for (int s = 0; s < ns; ++s) { const uint32_t t = pos[s]++; rblk[t] = (uint32_t)s; rcol[t] = (uint32_t)s << 1; }
-    for (uint64_t q = 0; q < S.npairs; ++q) {
-      const uint32_t t = pos[S.h_pair_i[q]]++;
-      rblk[t] = (uint32_t)(ns + q); rcol[t] = (uint32_t)S.h_pair_j[q] << 1;
-    }
-    PCD_TRY(upload(S.row_start, rst.data(), rst.size()));
-    PCD_TRY(upload(S.row_blk, rblk.data(), rblk.size()));
-    PCD_TRY(upload(S.row_col, rcol.data(), rcol.size()));
-  }
-  S.built = true;
-  S.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  T.npairs = T.h_pair_i.size(); T.nent = l.ea.size();
+  schur_row_lists(T.ns, T.h_pair_i, T.h_pair_j, l);
+  PCD_TRY(schur_upload(T, x, l));
+  T.built = true;
+  T.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return PCD_OK;
 }
 
@@ -918,104 +934,210 @@ static pcd_status pcg_check_opts(const pcd_ba_pcg_opts* o) {
   return PCD_OK;
 }
 
-static pcd_status pcg_state_guard(pcd_ba* b, const char* fn) {
-  if (!b->schur || !b->schur->valid) {
+// Can a solver read the handle's own system?  The state of a Schur call (what the back-substitution reads), and with
+// `blocks` its S_diag / S_off / rhs in the handle's buffers (what the PCG and the direct solve read).
+static pcd_status schur_state_guard(const pcd_ba* b, const char* fn, bool blocks) {
+  if (!b->schur || !b->schur->num.valid) {
     set_error("%s: no Schur state (call pcd_ba_schur[_device] first)", fn);
     return PCD_ERR_INVALID;
   }
-  const BaSchur& S = *b->schur;
-  if (!S.own_diag || !S.own_off || !S.own_rhs) {
+  const BaSchur::Numeric& N = b->schur->num;
+  if (blocks && !(N.own_diag && N.own_off && N.own_rhs)) {
     set_error("%s: the last Schur call sent %s%s%s to caller memory; the solver reads the handle's own copy "
-              "(leave those outputs NULL)", fn, S.own_diag ? "" : "S_diag ", S.own_off ? "" : "S_off ",
-              S.own_rhs ? "" : "rhs ");
+              "(leave those outputs NULL)", fn, N.own_diag ? "" : "S_diag ", N.own_off ? "" : "S_off ",
+              N.own_rhs ? "" : "rhs ");
     return PCD_ERR_INVALID;
   }
   return PCD_OK;
 }
 
 static PcgRule pcg_rule(const pcd_ba_pcg_opts* o) {
-  PcgRule r;
-  r.max_iterations = o->max_iterations; r.min_iterations = o->min_iterations;
-  r.q_tolerance = o->q_tolerance; r.r_tolerance = o->r_tolerance;
-  return r;
+  return PcgRule{o->max_iterations, o->min_iterations, o->q_tolerance, o->r_tolerance};
 }
 
 // preconditioner, x = 0, r = rhs, the scalars of iteration 0
 static pcd_status pcg_begin(pcd_ba* b, const pcd_ba_pcg_opts* o, hipStream_t s) {
-  BaSchur& S = *b->schur;
-  const int ns = S.ns;
-  const size_t n6 = std::max<size_t>(6 * (size_t)ns, 1);
-  const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256));
-  PCD_TRY(S.Minv.reserve(std::max<size_t>(36 * (size_t)ns, 1)));
-  for (DevBuf<double>* d : {&S.cg_x0, &S.cg_x1, &S.cg_r, &S.cg_z, &S.cg_p0, &S.cg_p1, &S.cg_w}) PCD_TRY(d->reserve(n6));
-  PCD_TRY(S.cg_pw.reserve(std::max<size_t>(ns, 1))); PCD_TRY(S.cg_partial.reserve(4 * (size_t)nb));
-  PCD_TRY(S.cg_state.reserve(1)); PCD_TRY(S.cg_info.reserve(1)); PCD_TRY(S.cg_flag.reserve(4));
-  S.cg_it = 0;
-  hipLaunchKernelGGL(k_pcg_init, dim3(nb), dim3(256), 0, s, ns, o->preconditioner, S.Sdiag.p, S.rhs.p, S.Minv.p,
-                     S.cg_x0.p, S.cg_r.p, S.cg_z.p, S.cg_p0.p, S.cg_p1.p, S.cg_partial.p);
-  hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(256), 0, s, (int)nb, S.cg_partial.p, pcg_rule(o), S.cg_state.p);
+  BaSchur& S = *b->schur; BaSchur::Pcg& C = S.cg;
+  const int ns = S.st.ns; const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256));
+  PCD_TRY(C.Minv.reserve(at_least_1(blocks_6x6(ns))));
+  for (DevBuf<double>* d : {&C.x0, &C.x1, &C.r, &C.z, &C.p0, &C.p1, &C.w}) PCD_TRY(d->reserve(at_least_1(slot_vec(ns))));
+  PCD_TRY(C.pw.reserve(at_least_1(ns))); PCD_TRY(C.partial.reserve(4 * (size_t)nb));
+  PCD_TRY(C.state.reserve(1)); PCD_TRY(C.info.reserve(1)); PCD_TRY(C.flag.reserve(4));
+  C.it = 0;
+  hipLaunchKernelGGL(k_pcg_init, dim3(nb), dim3(256), 0, s, ns, o->preconditioner, S.num.Sdiag.p, S.num.rhs.p, C.Minv.p,
+                     C.x0.p, C.r.p, C.z.p, C.p0.p, C.p1.p, C.partial.p);
+  hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(256), 0, s, (int)nb, C.partial.p, pcg_rule(o), C.state.p);
   return PCD_OK;
 }
 
 // `count` more iterations (three launches each; all of them return at once when the solve has ended)
 static void pcg_enqueue(pcd_ba* b, const pcd_ba_pcg_opts* o, int count, hipStream_t s) {
-  BaSchur& S = *b->schur;
-  const int ns = S.ns;
+  const BaSchur::Structure& T = b->schur->st; const BaSchur::Numeric& N = b->schur->num; BaSchur::Pcg& C = b->schur->cg;
+  const int ns = T.ns;
   if (!ns) return;
-  const unsigned nb = div_up((uint64_t)ns, 256);
-  const PcgRule rule = pcg_rule(o);
-  for (int c = 0; c < count; ++c, ++S.cg_it) {
-    const int it = S.cg_it;
-    double* p_old = (it & 1) ? S.cg_p1.p : S.cg_p0.p; double* p_new = (it & 1) ? S.cg_p0.p : S.cg_p1.p;
-    double* x_old = (it & 1) ? S.cg_x1.p : S.cg_x0.p; double* x_new = (it & 1) ? S.cg_x0.p : S.cg_x1.p;
-    hipLaunchKernelGGL(k_pcg_spmv, dim3(div_up((uint64_t)ns, 4)), dim3(256), 0, s, ns, S.cg_state.p, S.row_start.p,
-                       S.row_blk.p, S.row_col.p, S.Sdiag.p, S.Soff.p, S.cg_z.p, p_old, p_new, S.cg_w.p, S.cg_pw.p);
-    hipLaunchKernelGGL(k_pcg_update, dim3(nb), dim3(256), 0, s, ns, S.cg_state.p, S.cg_pw.p, S.Minv.p, S.rhs.p, p_new,
-                       S.cg_w.p, x_old, x_new, S.cg_r.p, S.cg_z.p, S.cg_partial.p);
-    hipLaunchKernelGGL(k_pcg_step, dim3(1), dim3(256), 0, s, (int)nb, it, S.cg_partial.p, rule, S.cg_state.p);
+  const unsigned nb = div_up((uint64_t)ns, 256); const PcgRule rule = pcg_rule(o);
+  for (int c = 0; c < count; ++c, ++C.it) {
+    const int it = C.it;
+    double* p_old = (it & 1) ? C.p1.p : C.p0.p; double* p_new = (it & 1) ? C.p0.p : C.p1.p;
+    double* x_old = (it & 1) ? C.x1.p : C.x0.p; double* x_new = (it & 1) ? C.x0.p : C.x1.p;
+    hipLaunchKernelGGL(k_pcg_spmv, dim3(div_up((uint64_t)ns, 4)), dim3(256), 0, s, ns, C.state.p, T.row_start.p,
+                       T.row_blk.p, T.row_col.p, N.Sdiag.p, N.Soff.p, C.z.p, p_old, p_new, C.w.p, C.pw.p);
+    hipLaunchKernelGGL(k_pcg_update, dim3(nb), dim3(256), 0, s, ns, C.state.p, C.pw.p, C.Minv.p, N.rhs.p, p_new, C.w.p,
+                       x_old, x_new, C.r.p, C.z.p, C.partial.p);
+    hipLaunchKernelGGL(k_pcg_step, dim3(1), dim3(256), 0, s, (int)nb, it, C.partial.p, rule, C.state.p);
   }
 }
 
 static void pcg_finish(pcd_ba* b, double* d_dpose, pcd_ba_pcg_info* d_info, hipStream_t s) {
-  BaSchur& S = *b->schur;
-  hipLaunchKernelGGL(k_pcg_finish, dim3(std::max(1u, div_up(6 * (uint64_t)S.ns, 256))), dim3(256), 0, s, S.ns,
-                     S.cg_state.p, S.cg_x0.p, S.cg_x1.p, d_dpose, d_info);
+  const int ns = b->schur->st.ns; BaSchur::Pcg& C = b->schur->cg;
+  hipLaunchKernelGGL(k_pcg_finish, dim3(std::max(1u, div_up(slot_vec(ns), 256))), dim3(256), 0, s, ns, C.state.p, C.x0.p,
+                     C.x1.p, d_dpose, d_info);
 }
 
 // batches until the device says done; `enqueued` iterations are already in the stream.  One flag copy per batch.
 static pcd_status pcg_run(pcd_ba* b, const pcd_ba_pcg_opts* o, int enqueued, hipStream_t s) {
-  BaSchur& S = *b->schur;
+  BaSchur::Pcg& C = b->schur->cg;
   int batch = kPcgFirstBatch;
   if (!enqueued) { pcg_enqueue(b, o, std::min(batch, o->max_iterations), s); enqueued = std::min(batch, o->max_iterations); }
   for (;;) {
-    PCD_HIP_TRY(hipMemcpyAsync(S.cg_flag.p, &S.cg_state.p->done, sizeof(int), hipMemcpyDeviceToHost, s));
+    PCD_HIP_TRY(hipMemcpyAsync(C.flag.p, &C.state.p->done, sizeof(int), hipMemcpyDeviceToHost, s));
     PCD_HIP_TRY(hipStreamSynchronize(s));
-    if (S.cg_flag.p[0] || !S.ns || enqueued >= o->max_iterations) return PCD_OK;
+    if (C.flag.p[0] || !b->schur->st.ns || enqueued >= o->max_iterations) return PCD_OK;
     batch = std::min(2 * batch, kPcgMaxBatch);
     const int n = std::min(batch, o->max_iterations - enqueued);
-    pcg_enqueue(b, o, n, s);
-    enqueued += n;
+    pcg_enqueue(b, o, n, s); enqueued += n;
   }
 }
 
 // Direct solve: scratch on first use, fill (the handle's blocks when d_S is null, else the caller's dense S), factor and
-// solve.  No synchronisation; the status record stays in S.chol_info.
+// solve.  No synchronisation; the status record stays in chol.info.
 static pcd_status chol_solve(pcd_ba* b, const double* d_S, const double* d_rhs, double* d_dpose,
                              pcd_ba_chol_info* d_info, hipStream_t s) {
-  BaSchur& S = *b->schur;
-  const int ns = S.ns, n = 6 * ns;
-  PCD_TRY(S.chol_A.reserve(chol_scratch_doubles(n)));
-  PCD_TRY(S.chol_info.reserve(1));
-  chol_begin(S.chol_A.p, n, S.chol_info.p, s);
-  if (d_S) {
-    chol_fill_dense(S.chol_A.p, n, d_S, d_rhs, s);
-  } else {
-    const uint32_t nblk = (uint32_t)(ns + S.npairs);
-    hipLaunchKernelGGL(k_chol_fill_blocks, dim3(div_up((uint64_t)nblk * 36, 256)), dim3(256), 0, s, ns, nblk,
-                       S.pair_ij.p, S.Sdiag.p, S.Soff.p, S.rhs.p, chol_padded(n), S.chol_A.p);
-  }
-  chol_factor_solve(S.chol_A.p, n, S.chol_info.p, d_dpose, d_info, s);
+  const BaSchur::Structure& T = b->schur->st; const BaSchur::Numeric& N = b->schur->num; BaSchur::Chol& K = b->schur->chol;
+  const int ns = T.ns, n = (int)slot_vec(ns);
+  PCD_TRY(K.A.reserve(chol_scratch_doubles(n))); PCD_TRY(K.info.reserve(1));
+  chol_begin(K.A.p, n, K.info.p, s);
+  if (d_S) chol_fill_dense(K.A.p, n, d_S, d_rhs, s);
+  else hipLaunchKernelGGL(k_chol_fill_blocks, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, ns, T.nblk(),
+                          T.pair_ij.p, N.Sdiag.p, N.Soff.p, N.rhs.p, chol_padded(n), K.A.p);
+  chol_factor_solve(K.A.p, n, K.info.p, d_dpose, d_info, s);
   return PCD_OK;
+}
+
+// the elimination proper: V^-1 per point and the skip count, Y per observation, the blocks of S and rhs
+static void schur_eliminate(pcd_ba* b, const pcd_ba_schur_opts* opt, unsigned nbp, double* Sdiag, double* Soff,
+                            double* rhs, unsigned long long* skipped, hipStream_t s) {
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
+  const int P = b->P; const uint64_t O = b->O;
+  hipLaunchKernelGGL(k_schur_points, dim3(nbp), dim3(256), 0, s, P, N.Hpt.p, N.gpt.p, b->const_points(), opt->mu,
+                     opt->damping, N.Vinv.p, N.Vg.p, N.Dpt.p, N.skip_partial.p);
+  hipLaunchKernelGGL(k_sum_u32, dim3(1), dim3(256), 0, s, N.skip_partial.p, (int)nbp, skipped);
+  if (O) hipLaunchKernelGGL(k_schur_obs, dim3(div_up(O, 256)), dim3(256), 0, s, O, b->img_pt.p, N.Wim.p, N.Vinv.p, N.Y.p);
+  SchurBlocks sb;
+  sb.ns = T.ns; sb.nblk = T.nblk(); sb.blk_start = T.blk_start.p; sb.ent_a = T.ent_a.p; sb.ent_b = T.ent_b.p;
+  sb.pair_ij = T.pair_ij.p; sb.slot_img = T.slot_img.p; sb.img_obs_start = b->img_obs_start.p; sb.img_pt = b->img_pt.p;
+  sb.Y = N.Y.p; sb.Wim = N.Wim.p; sb.Vg = N.Vg.p; sb.Himg = N.Himg.p; sb.gimg = N.gimg.p;
+  sb.image_const_tvec = b->const_tvec(); sb.mu = opt->mu; sb.mode = opt->damping;
+  sb.Sdiag = Sdiag; sb.Soff = Soff; sb.rhs = rhs; sb.Dimg = N.Dimg.p;
+  if (sb.nblk) hipLaunchKernelGGL(k_schur_blocks, dim3(div_up(sb.nblk, 4)), dim3(256), 0, s, sb);
+}
+
+static pcd_status lm_check_opts(const pcd_ba_solve_opts* o) {
+  PCD_REQUIRE(o, "null pointer"); PCD_TRY(pcg_check_opts(&o->linear));
+  PCD_REQUIRE(o->damping == PCD_DAMP_MARQUARDT || o->damping == PCD_DAMP_LEVENBERG, "damping");
+  PCD_REQUIRE(o->max_num_iterations >= 0, "max_num_iterations must be >= 0");
+  PCD_REQUIRE(o->initial_radius > 0.0 && o->max_radius > 0.0, "radius must be > 0");
+  PCD_REQUIRE(o->linear_solver == PCD_LINEAR_PCG || o->linear_solver == PCD_LINEAR_CHOLESKY, "linear_solver");
+  return PCD_OK;
+}
+
+static pcd_status lm_reserve(pcd_ba* b, unsigned ngp) {
+  BaSchur::Lm& M = b->schur->lm;
+  PCD_TRY(M.dpose.reserve(at_least_1(slot_vec(b->schur->st.ns)))); PCD_TRY(M.poses.reserve(7 * (size_t)b->I));
+  PCD_TRY(M.dpoint.reserve(point_vec(b->P))); PCD_TRY(M.points.reserve(point_vec(b->P)));
+  PCD_TRY(M.cand_cost.reserve(1)); PCD_TRY(M.rec.reserve(1)); PCD_TRY(M.host.reserve(1));
+  return M.gpart.reserve(ngp);
+}
+
+// poses and points of the handle's size from src to dst, on the device: the handle's own and lm.poses / lm.points
+static pcd_status copy_parameters(const pcd_ba* b, double* dst_poses, double* dst_points, const double* src_poses,
+                                  const double* src_points, hipStream_t s) {
+  PCD_HIP_TRY(hipMemcpyAsync(dst_poses, src_poses, 7 * (size_t)b->I * sizeof(double), hipMemcpyDeviceToDevice, s));
+  PCD_HIP_TRY(hipMemcpyAsync(dst_points, src_points, point_vec(b->P) * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return PCD_OK;
+}
+
+// The linear solve of an iteration into lm.dpose / cg.info: the direct solve (an exact step: nothing left to run, *enq =
+// max_iterations), or pcg_begin and the first batch (*enq = its iterations)
+static pcd_status lm_enqueue_linear(pcd_ba* b, const pcd_ba_solve_opts* o, int* enq, hipStream_t s) {
+  BaSchur& S = *b->schur;
+  *enq = o->linear.max_iterations;
+  if (o->linear_solver == PCD_LINEAR_CHOLESKY) {
+    PCD_TRY(S.cg.info.reserve(1));
+    if (S.st.ns) {
+      ScopedKernelTimer t("ba_schur_cholesky", s);
+      PCD_TRY(chol_solve(b, nullptr, nullptr, S.lm.dpose.p, nullptr, s));
+      hipLaunchKernelGGL(k_chol_lm_info, dim3(1), dim3(1), 0, s, S.chol.info.p, S.cg.info.p);
+    } else {
+      PCD_HIP_TRY(hipMemsetAsync(S.cg.info.p, 0, sizeof(pcd_ba_pcg_info), s));   // 0 iterations, PCD_CHOL_OK
+    }
+  } else {
+    PCD_TRY(pcg_begin(b, &o->linear, s));
+    *enq = std::min(kPcgFirstBatch, o->linear.max_iterations);
+    pcg_enqueue(b, &o->linear, *enq, s);
+  }
+  return PCD_OK;
+}
+
+// Tail of an iteration up to the synchronised read-back of its record into lm.host.  It is enqueued behind the first
+// batch without looking at the flag: at the defaults the PCG has ended by then and the iteration costs one copy.  If the
+// step came from an unfinished solve, the accepted parameters go back, the batches go on and the tail runs once more.
+static pcd_status lm_try_step(pcd_ba* b, const pcd_ba_solve_opts* o, int enq, unsigned ngp, EventPair& ev,
+                              double* linear_ms, hipStream_t s) {
+  BaSchur& S = *b->schur; BaSchur::Lm& M = S.lm;
+  pcd_ba_out co{}; co.cost = M.cand_cost.p;
+  for (;;) {
+    if (o->linear_solver == PCD_LINEAR_PCG) pcg_finish(b, M.dpose.p, S.cg.info.p, s);
+    PCD_TRY(pcd_ba_schur_back_substitute_device(b, M.dpose.p, M.dpoint.p, S.num.md.p, s));
+    PCD_TRY(pcd_ba_plus_device(b, M.dpose.p, M.dpoint.p, b->poses.p, b->points.p, s));
+    PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
+    hipLaunchKernelGGL(k_ba_lm_record, dim3(1), dim3(256), 0, s, S.num.cost.p, M.cand_cost.p, S.num.md.p, M.gpart.p,
+                       (int)ngp, S.num.skip_cnt.p, S.cg.info.p, M.rec.p);
+    PCD_HIP_TRY(hipMemcpyAsync(M.host.p, M.rec.p, sizeof(LmRecord), hipMemcpyDeviceToHost, s));
+    PCD_HIP_TRY(hipStreamSynchronize(s));
+    if (float ms = 0.f; ev.elapsed(&ms) == hipSuccess) *linear_ms += ms;
+    if (M.host.p->pcg.termination >= 0 || enq >= o->linear.max_iterations) break;
+    PCD_TRY(copy_parameters(b, b->poses.p, b->points.p, M.poses.p, M.points.p, s));
+    PCD_HIP_TRY(ev.start(s));
+    PCD_TRY(pcg_run(b, &o->linear, enq, s)); enq = o->linear.max_iterations;
+    PCD_HIP_TRY(ev.stop(s));
+  }
+  PCD_HIP_TRY(hipGetLastError());
+  return PCD_OK;
+}
+
+// What a record means for the loop, host arithmetic only: the iteration as reported (radius: the new one), radius and
+// shrink factor of the next, the termination that ends the loop or -1 (gradient tolerance: nothing is recorded).
+struct LmDecision { pcd_ba_solve_iteration it; double radius, factor; int termination; };
+static LmDecision lm_decide(const LmRecord& rec, const pcd_ba_solve_opts& o, double radius, double factor, bool direct) {
+  LmDecision d{}; pcd_ba_solve_iteration& r = d.it;
+  const bool restore_only = o.gradient_tolerance > 0.0 && rec.gradient_max <= o.gradient_tolerance;
+  r.cost = rec.cost; r.candidate_cost = rec.candidate_cost; r.model_decrease = rec.model_decrease;
+  r.gradient_max_norm = rec.gradient_max; r.num_skipped = rec.num_skipped;
+  r.linear_iterations = rec.pcg.iterations; r.linear_termination = rec.pcg.termination;
+  const bool solved = direct ? rec.pcg.termination == PCD_CHOL_OK : rec.pcg.termination != PCD_PCG_BREAKDOWN;
+  const double rho = (solved && r.model_decrease > 0.0) ? (r.cost - r.candidate_cost) / r.model_decrease
+                                                        : -std::numeric_limits<double>::infinity();
+  r.relative_decrease = rho; r.accepted = !restore_only && rho > o.min_relative_decrease;
+  d.termination = restore_only ? (int)PCD_SOLVE_GRADIENT_TOLERANCE : -1;
+  if (r.accepted) {
+    radius = std::min(o.max_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3.0)));
+    factor = 2.0;
+    if (o.function_tolerance > 0.0 && std::fabs(r.cost - r.candidate_cost) <= o.function_tolerance * r.cost)
+      d.termination = PCD_SOLVE_FUNCTION_TOLERANCE;
+  } else if (!restore_only) { radius /= factor; factor *= 2.0; }
+  r.radius = d.radius = radius; d.factor = factor;
+  return d;
 }
 
 extern "C" {
@@ -1024,27 +1146,22 @@ extern "C" {
 pcd_status pcd_ba_schur_structure(pcd_ba* b, int32_t* image_slot, int32_t* num_slots, uint64_t* num_pairs,
                                   int32_t* pair_i, int32_t* pair_j) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b));
-    PCD_TRY(schur_build(b));
-    const BaSchur& S = *b->schur;
-    if (image_slot) std::memcpy(image_slot, S.h_slot.data(), (size_t)b->I * sizeof(int32_t));
-    if (num_slots) *num_slots = S.ns;
-    if (num_pairs) *num_pairs = S.npairs;
-    if (pair_i && S.npairs) std::memcpy(pair_i, S.h_pair_i.data(), S.npairs * sizeof(int32_t));
-    if (pair_j && S.npairs) std::memcpy(pair_j, S.h_pair_j.data(), S.npairs * sizeof(int32_t));
+    PCD_TRY(schur_guard(b)); PCD_TRY(schur_build(b));
+    const BaSchur::Structure& T = b->schur->st;
+    if (image_slot) std::memcpy(image_slot, T.h_slot.data(), (size_t)b->I * sizeof(int32_t));
+    if (num_slots) *num_slots = T.ns; if (num_pairs) *num_pairs = T.npairs;
+    if (pair_i && T.npairs) std::memcpy(pair_i, T.h_pair_i.data(), T.npairs * sizeof(int32_t));
+    if (pair_j && T.npairs) std::memcpy(pair_j, T.h_pair_j.data(), T.npairs * sizeof(int32_t));
     return PCD_OK;
   });
 }
 
 pcd_status pcd_ba_schur_stats(pcd_ba* b, pcd_ba_schur_info* info) {
-  PCD_TRY(schur_guard(b));
-  PCD_REQUIRE(info, "null pointer");
+  PCD_TRY(schur_guard(b)); PCD_REQUIRE(info, "null pointer");
   std::memset(info, 0, sizeof *info);
-  if (!b->schur || !b->schur->built) return PCD_OK;
-  const BaSchur& S = *b->schur;
-  info->build_ms = S.build_ms;
-  info->num_entries = S.nent;
-  info->scratch_bytes = S.device_bytes();
+  if (!b->schur || !b->schur->st.built) return PCD_OK;
+  info->build_ms = b->schur->st.build_ms; info->num_entries = b->schur->st.nent;
+  info->scratch_bytes = b->schur->device_bytes();
   return PCD_OK;
 }
 
@@ -1056,80 +1173,57 @@ pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pc
     PCD_REQUIRE(opt->mu >= 0.0, "mu must be >= 0");
     PCD_REFUSE_CAPTURE(stream);
     PCD_TRY(schur_build(b));
-    BaSchur& S = *b->schur;
+    const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
     hipStream_t s = (hipStream_t)stream;
-    const int I = b->I, P = b->P, ns = S.ns;
-    const uint64_t O = b->O;
-    const uint32_t nblk = (uint32_t)(ns + S.npairs);
-    const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
-    S.valid = false;
-    PCD_TRY(S.Himg.reserve(36 * (size_t)I)); PCD_TRY(S.gimg.reserve(6 * (size_t)I));
-    PCD_TRY(S.Hpt.reserve(9 * (size_t)P)); PCD_TRY(S.gpt.reserve(3 * (size_t)P));
-    PCD_TRY(S.Wim.reserve(std::max<size_t>(18 * O, 1))); PCD_TRY(S.Y.reserve(std::max<size_t>(18 * O, 1)));
-    PCD_TRY(S.Vinv.reserve(9 * (size_t)P)); PCD_TRY(S.Vg.reserve(3 * (size_t)P)); PCD_TRY(S.Dpt.reserve(3 * (size_t)P));
-    PCD_TRY(S.Dimg.reserve(std::max<size_t>(6 * (size_t)ns, 1)));
-    PCD_TRY(S.Sdiag.reserve(std::max<size_t>(36 * (size_t)ns, 1)));
-    PCD_TRY(S.Soff.reserve(std::max<size_t>(36 * S.npairs, 1)));
-    PCD_TRY(S.rhs.reserve(std::max<size_t>(6 * (size_t)ns, 1)));
-    PCD_TRY(S.skip_partial.reserve(nbp)); PCD_TRY(S.skip_cnt.reserve(1));
-    PCD_TRY(S.md_partial.reserve(nbp)); PCD_TRY(S.md.reserve(1)); PCD_TRY(S.cost.reserve(1));
+    const int I = b->I, P = b->P, ns = T.ns;
+    const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));   // grid of k_schur_points = length of its partials
+    N.valid = false;
+    PCD_TRY(N.Himg.reserve(blocks_6x6(I))); PCD_TRY(N.gimg.reserve(slot_vec(I)));
+    PCD_TRY(N.Hpt.reserve(point_blocks(P))); PCD_TRY(N.gpt.reserve(point_vec(P)));
+    PCD_TRY(N.Wim.reserve(at_least_1(obs_blocks(b->O)))); PCD_TRY(N.Y.reserve(at_least_1(obs_blocks(b->O))));
+    PCD_TRY(N.Vinv.reserve(point_blocks(P))); PCD_TRY(N.Vg.reserve(point_vec(P))); PCD_TRY(N.Dpt.reserve(point_vec(P)));
+    PCD_TRY(N.Dimg.reserve(at_least_1(slot_vec(ns)))); PCD_TRY(N.Sdiag.reserve(at_least_1(blocks_6x6(ns))));
+    PCD_TRY(N.Soff.reserve(at_least_1(blocks_6x6(T.npairs)))); PCD_TRY(N.rhs.reserve(at_least_1(slot_vec(ns))));
+    PCD_TRY(N.skip_partial.reserve(nbp)); PCD_TRY(N.skip_cnt.reserve(1));
+    PCD_TRY(N.md_partial.reserve(nbp)); PCD_TRY(N.md.reserve(1)); PCD_TRY(N.cost.reserve(1));
     PCD_HIP_TRY(hipSetDevice(b->device));
-    const uint8_t* ctvec = b->has_ctvec ? b->image_const_tvec.p : nullptr;
-    const uint8_t* cpt = b->has_cpt ? b->point_const.p : nullptr;
-    double* Sdiag = o->S_diag ? o->S_diag : S.Sdiag.p;
-    double* Soff = o->S_off ? o->S_off : S.Soff.p;
-    double* rhs = o->rhs ? o->rhs : S.rhs.p;
+    double* Sdiag = o->S_diag ? o->S_diag : N.Sdiag.p; double* Soff = o->S_off ? o->S_off : N.Soff.p;
     {
       ScopedKernelTimer t("ba_schur_normal", s);
       // iota as the W order: W lands in image-major order (k_ba_images' contiguous store path)
-      PCD_TRY(ba_normal_equations(b, S.iota.p, S.Hpt.p, S.gpt.p, o->cost ? o->cost : S.cost.p, S.Himg.p, S.gimg.p,
-                                  S.Wim.p, s));
+      PCD_TRY(ba_normal_equations(b, T.iota.p, N.Hpt.p, N.gpt.p, o->cost ? o->cost : N.cost.p, N.Himg.p, N.gimg.p,
+                                  N.Wim.p, s));
     }
     {
       ScopedKernelTimer t("ba_schur_eliminate", s);
-      hipLaunchKernelGGL(k_schur_points, dim3(nbp), dim3(256), 0, s, P, S.Hpt.p, S.gpt.p, cpt, opt->mu,
-                         opt->damping, S.Vinv.p, S.Vg.p, S.Dpt.p, S.skip_partial.p);
-      hipLaunchKernelGGL(k_sum_u32, dim3(1), dim3(256), 0, s, S.skip_partial.p, (int)nbp,
-                         o->num_skipped ? reinterpret_cast<unsigned long long*>(o->num_skipped) : S.skip_cnt.p);
-      if (O) hipLaunchKernelGGL(k_schur_obs, dim3(div_up(O, 256)), dim3(256), 0, s, O, b->img_pt.p, S.Wim.p, S.Vinv.p, S.Y.p);
-      SchurBlocks sb;
-      sb.ns = ns; sb.nblk = nblk; sb.blk_start = S.blk_start.p; sb.ent_a = S.ent_a.p; sb.ent_b = S.ent_b.p;
-      sb.pair_ij = S.pair_ij.p; sb.slot_img = S.slot_img.p; sb.img_obs_start = b->img_obs_start.p; sb.img_pt = b->img_pt.p;
-      sb.Y = S.Y.p; sb.Wim = S.Wim.p; sb.Vg = S.Vg.p; sb.Himg = S.Himg.p; sb.gimg = S.gimg.p;
-      sb.image_const_tvec = ctvec; sb.mu = opt->mu; sb.mode = opt->damping;
-      sb.Sdiag = Sdiag; sb.Soff = Soff; sb.rhs = rhs; sb.Dimg = S.Dimg.p;
-      if (nblk) hipLaunchKernelGGL(k_schur_blocks, dim3(div_up(nblk, 4)), dim3(256), 0, s, sb);
+      schur_eliminate(b, opt, nbp, Sdiag, Soff, o->rhs ? o->rhs : N.rhs.p,
+                      o->num_skipped ? reinterpret_cast<unsigned long long*>(o->num_skipped) : N.skip_cnt.p, s);
     }
-    if (o->S && ns) {
+    if (o->S && T.ns) {
       ScopedKernelTimer t("ba_schur_dense", s);
-      const size_t n = 6 * (size_t)ns;
+      const size_t n = slot_vec(T.ns);
       PCD_HIP_TRY(hipMemsetAsync(o->S, 0, n * n * sizeof(double), s));
-      hipLaunchKernelGGL(k_schur_dense, dim3(div_up((uint64_t)nblk * 36, 256)), dim3(256), 0, s, ns, nblk, S.pair_ij.p,
-                         Sdiag, Soff, o->S);
+      hipLaunchKernelGGL(k_schur_dense, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, T.ns, T.nblk(),
+                         T.pair_ij.p, Sdiag, Soff, o->S);
     }
     PCD_HIP_TRY(hipGetLastError());
-    S.valid = true;
-    S.own_diag = !o->S_diag; S.own_off = !o->S_off; S.own_rhs = !o->rhs;
+    N.valid = true; N.own_diag = !o->S_diag; N.own_off = !o->S_off; N.own_rhs = !o->rhs;
     return PCD_OK;
   });
 }
 
 pcd_status pcd_ba_schur(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b));
-    PCD_REQUIRE(opt && o, "null pointer");
+    PCD_TRY(schur_guard(b)); PCD_REQUIRE(opt && o, "null pointer");
     PCD_TRY(schur_build(b));
-    BaSchur& S = *b->schur;
-    const size_t n = 6 * (size_t)S.ns;
+    const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
+    const size_t n = slot_vec(T.ns);
     pcd_ba_schur_out d{};
-    if (o->S) { PCD_TRY(S.dense.reserve(std::max<size_t>(n * n, 1))); d.S = S.dense.p; }
+    if (o->S) { PCD_TRY(N.dense.reserve(at_least_1(n * n))); d.S = N.dense.p; }
     PCD_TRY(pcd_ba_schur_device(b, opt, &d, nullptr));
-    if (o->cost) PCD_HIP_TRY(hipMemcpy(o->cost, S.cost.p, sizeof(double), hipMemcpyDeviceToHost));
-    if (o->num_skipped) PCD_HIP_TRY(hipMemcpy(o->num_skipped, S.skip_cnt.p, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (o->S_diag && S.ns) PCD_HIP_TRY(hipMemcpy(o->S_diag, S.Sdiag.p, 36 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
-    if (o->S_off && S.npairs) PCD_HIP_TRY(hipMemcpy(o->S_off, S.Soff.p, 36 * S.npairs * sizeof(double), hipMemcpyDeviceToHost));
-    if (o->rhs && S.ns) PCD_HIP_TRY(hipMemcpy(o->rhs, S.rhs.p, 6 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
-    if (o->S && n) PCD_HIP_TRY(hipMemcpy(o->S, S.dense.p, n * n * sizeof(double), hipMemcpyDeviceToHost));
+    PCD_TRY(copy_back(o->cost, N.cost, 1)); PCD_TRY(copy_back(o->num_skipped, N.skip_cnt, 1));
+    PCD_TRY(copy_back(o->S_diag, N.Sdiag, blocks_6x6(T.ns))); PCD_TRY(copy_back(o->S_off, N.Soff, blocks_6x6(T.npairs)));
+    PCD_TRY(copy_back(o->rhs, N.rhs, n)); PCD_TRY(copy_back(o->S, N.dense, n * n));
     PCD_HIP_TRY(hipDeviceSynchronize());
     return PCD_OK;
   });
@@ -1139,24 +1233,18 @@ pcd_status pcd_ba_schur_back_substitute_device(pcd_ba* b, const double* d_dpose,
                                                double* d_model_decrease, void* stream) {
   PCD_TRY(schur_guard(b));
   PCD_REFUSE_CAPTURE(stream);
-  if (!b->schur || !b->schur->valid) {
-    set_error("pcd_ba_schur_back_substitute_device: no Schur state (call pcd_ba_schur[_device] first)");
-    return PCD_ERR_INVALID;
-  }
-  BaSchur& S = *b->schur;
+  PCD_TRY(schur_state_guard(b, "pcd_ba_schur_back_substitute_device", false));
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
   // a zero-length array may be NULL (an empty torch tensor has data_ptr() 0): ns = 0 when every pose is constant
-  PCD_REQUIRE((d_dpose || S.ns == 0) && (d_dpoint || b->P == 0), "null pointer");
-  PCD_HIP_TRY(hipSetDevice(b->device));
-  hipStream_t s = (hipStream_t)stream;
-  const int P = b->P;
-  const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
+  PCD_REQUIRE((d_dpose || T.ns == 0) && (d_dpoint || b->P == 0), "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
+  const int P = b->P; const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
   ScopedKernelTimer t("ba_schur_back", s);
   hipLaunchKernelGGL(k_schur_back, dim3(nbp), dim3(256), 0, s, P, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p,
-                     S.obs_pos.p, S.img_slot.p, S.Wim.p, S.Vinv.p, S.gpt.p, S.Dpt.p, d_dpose, d_dpoint, S.md_partial.p);
+                     T.obs_pos.p, T.img_slot.p, N.Wim.p, N.Vinv.p, N.gpt.p, N.Dpt.p, d_dpose, d_dpoint, N.md_partial.p);
   if (d_model_decrease)
-    hipLaunchKernelGGL(k_schur_model_decrease, dim3(1), dim3(256), 0, s, S.ns, S.slot_img.p,
-                       b->has_ctvec ? b->image_const_tvec.p : (const uint8_t*)nullptr, S.gimg.p, S.Dimg.p, d_dpose,
-                       S.md_partial.p, (int)nbp, d_model_decrease);
+    hipLaunchKernelGGL(k_schur_model_decrease, dim3(1), dim3(256), 0, s, T.ns, T.slot_img.p, b->const_tvec(), N.gimg.p,
+                       N.Dimg.p, d_dpose, N.md_partial.p, (int)nbp, d_model_decrease);
   PCD_HIP_TRY(hipGetLastError());
   return PCD_OK;
 }
@@ -1168,14 +1256,12 @@ pcd_status pcd_ba_plus_device(pcd_ba* b, const double* d_dpose, const double* d_
     PCD_REFUSE_CAPTURE(stream);
     PCD_TRY(schur_build(b));
     // zero-length arrays may be NULL (ns = 0 when every pose is constant)
-    PCD_REQUIRE((d_dpose || b->schur->ns == 0) && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) &&
+    PCD_REQUIRE((d_dpose || b->schur->st.ns == 0) && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) &&
                 (d_points_out || b->P == 0), "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
+    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
     ScopedKernelTimer t("ba_plus", s);
     hipLaunchKernelGGL(k_ba_plus, dim3(div_up((uint64_t)b->I + b->P, 256)), dim3(256), 0, s, b->I, b->P,
-                       b->schur->img_slot.p, b->has_ctvec ? b->image_const_tvec.p : (const uint8_t*)nullptr,
-                       b->has_cpt ? b->point_const.p : (const uint8_t*)nullptr, b->poses.p, b->points.p, d_dpose,
+                       b->schur->st.img_slot.p, b->const_tvec(), b->const_points(), b->poses.p, b->points.p, d_dpose,
                        d_dpoint, d_poses_out, d_points_out);
     PCD_HIP_TRY(hipGetLastError());
     return PCD_OK;
@@ -1192,13 +1278,11 @@ void pcd_ba_pcg_opts_default(pcd_ba_pcg_opts* o) {
 pcd_status pcd_ba_schur_solve_pcg_device(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* d_dpose,
                                          pcd_ba_pcg_info* d_info, void* stream) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b));
-    PCD_TRY(pcg_check_opts(opts));
+    PCD_TRY(schur_guard(b)); PCD_TRY(pcg_check_opts(opts));
     PCD_REFUSE_CAPTURE(stream);
-    PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_pcg_device"));
-    PCD_REQUIRE(d_dpose || b->schur->ns == 0, "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
+    PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_pcg_device", true));
+    PCD_REQUIRE(d_dpose || b->schur->st.ns == 0, "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
     ScopedKernelTimer t("ba_schur_pcg", s);
     PCD_TRY(pcg_begin(b, opts, s));
     PCD_TRY(pcg_run(b, opts, 0, s));
@@ -1210,15 +1294,14 @@ pcd_status pcd_ba_schur_solve_pcg_device(pcd_ba* b, const pcd_ba_pcg_opts* opts,
 
 pcd_status pcd_ba_schur_solve_pcg(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* dpose, pcd_ba_pcg_info* info) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b));
-    PCD_TRY(pcg_check_opts(opts));
-    PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_pcg"));
-    BaSchur& S = *b->schur;
-    PCD_REQUIRE(dpose || S.ns == 0, "null pointer");
-    PCD_TRY(S.cg_out.reserve(std::max<size_t>(6 * (size_t)S.ns, 1))); PCD_TRY(S.cg_info.reserve(1));
-    PCD_TRY(pcd_ba_schur_solve_pcg_device(b, opts, S.cg_out.p, S.cg_info.p, nullptr));
-    if (S.ns) PCD_HIP_TRY(hipMemcpy(dpose, S.cg_out.p, 6 * (size_t)S.ns * sizeof(double), hipMemcpyDeviceToHost));
-    if (info) PCD_HIP_TRY(hipMemcpy(info, S.cg_info.p, sizeof *info, hipMemcpyDeviceToHost));
+    PCD_TRY(schur_guard(b)); PCD_TRY(pcg_check_opts(opts));
+    PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_pcg", true));
+    BaSchur::Pcg& C = b->schur->cg;
+    const size_t n = slot_vec(b->schur->st.ns);
+    PCD_REQUIRE(dpose || n == 0, "null pointer");
+    PCD_TRY(C.out.reserve(at_least_1(n))); PCD_TRY(C.info.reserve(1));
+    PCD_TRY(pcd_ba_schur_solve_pcg_device(b, opts, C.out.p, C.info.p, nullptr));
+    PCD_TRY(copy_back(dpose, C.out, n)); PCD_TRY(copy_back(info, C.info, 1));
     PCD_HIP_TRY(hipDeviceSynchronize());
     return PCD_OK;
   });
@@ -1231,15 +1314,13 @@ pcd_status pcd_ba_schur_solve_cholesky_device(pcd_ba* b, const double* d_S, cons
     PCD_REQUIRE(!d_S == !d_rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
     PCD_REFUSE_CAPTURE(stream);
     if (d_S) PCD_TRY(schur_build(b));
-    else PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_cholesky_device"));
-    BaSchur& S = *b->schur;
-    PCD_REQUIRE(d_dpose || S.ns == 0, "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (S.ns == 0) {   // nothing to solve, nothing launched
+    else PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_cholesky_device", true));
+    const int ns = b->schur->st.ns;
+    PCD_REQUIRE(d_dpose || ns == 0, "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
+    if (ns == 0) {   // nothing to solve, nothing launched
       if (d_info) {
-        pcd_ba_chol_info o{};
-        o.status = PCD_CHOL_OK; o.failed_column = -1;
+        pcd_ba_chol_info o{}; o.status = PCD_CHOL_OK; o.failed_column = -1;
         PCD_HIP_TRY(hipMemcpyAsync(d_info, &o, sizeof o, hipMemcpyHostToDevice, s));
         PCD_HIP_TRY(hipStreamSynchronize(s));   // o leaves scope
       }
@@ -1258,25 +1339,24 @@ pcd_status pcd_ba_schur_solve_cholesky(pcd_ba* b, const double* Sh, const double
     PCD_TRY(schur_guard(b));
     PCD_REQUIRE(!Sh == !rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
     if (Sh) PCD_TRY(schur_build(b));
-    else PCD_TRY(pcg_state_guard(b, "pcd_ba_schur_solve_cholesky"));
-    BaSchur& S = *b->schur;
-    const size_t n = 6 * (size_t)S.ns;
+    else PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_cholesky", true));
+    BaSchur::Chol& K = b->schur->chol;
+    const size_t n = slot_vec(b->schur->st.ns);
     PCD_REQUIRE(dpose || n == 0, "null pointer");
-    PCD_TRY(S.chol_out.reserve(std::max<size_t>(n, 1))); PCD_TRY(S.chol_info_out.reserve(1));
+    PCD_TRY(K.out.reserve(at_least_1(n))); PCD_TRY(K.info_out.reserve(1));
     const double* d_S = nullptr; const double* d_rhs = nullptr;
     if (Sh && n) {
-      PCD_TRY(S.chol_S.reserve(n * n)); PCD_TRY(S.chol_rhs.reserve(n));
-      PCD_HIP_TRY(hipMemcpy(S.chol_S.p, Sh, n * n * sizeof(double), hipMemcpyHostToDevice));
-      PCD_HIP_TRY(hipMemcpy(S.chol_rhs.p, rhs, n * sizeof(double), hipMemcpyHostToDevice));
-      d_S = S.chol_S.p; d_rhs = S.chol_rhs.p;
+      PCD_TRY(K.S.reserve(n * n)); PCD_TRY(K.rhs.reserve(n));
+      PCD_HIP_TRY(hipMemcpy(K.S.p, Sh, n * n * sizeof(double), hipMemcpyHostToDevice));
+      PCD_HIP_TRY(hipMemcpy(K.rhs.p, rhs, n * sizeof(double), hipMemcpyHostToDevice));
+      d_S = K.S.p; d_rhs = K.rhs.p;
     } else if (Sh) {   // an empty system given in caller memory: the device form only looks at the pointers
-      d_S = S.chol_out.p; d_rhs = S.chol_out.p;
+      d_S = K.out.p; d_rhs = K.out.p;
     }
-    PCD_TRY(pcd_ba_schur_solve_cholesky_device(b, d_S, d_rhs, S.chol_out.p, S.chol_info_out.p, nullptr));
-    if (n) PCD_HIP_TRY(hipMemcpy(dpose, S.chol_out.p, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (info) PCD_HIP_TRY(hipMemcpy(info, S.chol_info_out.p, sizeof *info, hipMemcpyDeviceToHost));
+    PCD_TRY(pcd_ba_schur_solve_cholesky_device(b, d_S, d_rhs, K.out.p, K.info_out.p, nullptr));
+    PCD_TRY(copy_back(dpose, K.out, n)); PCD_TRY(copy_back(info, K.info_out, 1));
     PCD_HIP_TRY(hipDeviceSynchronize());
-    S.chol_S.release(); S.chol_rhs.release();   // n^2 of staging: not kept beside the padded scratch
+    K.S.release(); K.rhs.release();   // n^2 of staging: not kept beside the padded scratch
     return PCD_OK;
   });
 }
@@ -1293,126 +1373,46 @@ void pcd_ba_solve_opts_default(pcd_ba_solve_opts* o) {
 pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_summary* summary,
                         pcd_ba_solve_iteration* iterations) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b));
-    PCD_REQUIRE(opts, "null pointer");
-    PCD_TRY(pcg_check_opts(&opts->linear));
-    PCD_REQUIRE(opts->damping == PCD_DAMP_MARQUARDT || opts->damping == PCD_DAMP_LEVENBERG, "damping");
-    PCD_REQUIRE(opts->max_num_iterations >= 0, "max_num_iterations must be >= 0");
-    PCD_REQUIRE(opts->initial_radius > 0.0 && opts->max_radius > 0.0, "radius must be > 0");
-    PCD_REQUIRE(opts->linear_solver == PCD_LINEAR_PCG || opts->linear_solver == PCD_LINEAR_CHOLESKY, "linear_solver");
-    const bool direct = opts->linear_solver == PCD_LINEAR_CHOLESKY;
+    PCD_TRY(schur_guard(b)); PCD_TRY(lm_check_opts(opts));
     hipStream_t s = nullptr;
     PCD_REFUSE_CAPTURE(s);
     PCD_TRY(schur_build(b));
-    BaSchur& S = *b->schur;
+    BaSchur& S = *b->schur; BaSchur::Lm& M = S.lm;
     const auto t0 = std::chrono::steady_clock::now();
-    const int I = b->I, P = b->P, ns = S.ns;
-    const size_t nposes = 7 * (size_t)I, npoints = 3 * (size_t)P;
-    PCD_TRY(S.lm_dpose.reserve(std::max<size_t>(6 * (size_t)ns, 1))); PCD_TRY(S.lm_dpoint.reserve(npoints));
-    PCD_TRY(S.lm_poses.reserve(nposes)); PCD_TRY(S.lm_points.reserve(npoints));
-    PCD_TRY(S.lm_cand_cost.reserve(1)); PCD_TRY(S.lm_rec.reserve(1)); PCD_TRY(S.lm_host.reserve(1));
-    const unsigned ngp = std::max(1u, std::min(1024u, div_up((uint64_t)ns + P, 256)));
-    PCD_TRY(S.lm_gpart.reserve(ngp));
+    const unsigned ngp = std::max(1u, std::min(1024u, div_up((uint64_t)S.st.ns + b->P, 256)));
+    PCD_TRY(lm_reserve(b, ngp));
     PCD_HIP_TRY(hipSetDevice(b->device));
-    EventPair ev;   // around the linear solve of an iteration
-    PCD_TRY(ev.create());
+    EventPair ev; PCD_TRY(ev.create());   // around the linear solve of an iteration
     // the accepted parameters: a rejected step copies them back into the handle
-    PCD_HIP_TRY(hipMemcpyAsync(S.lm_poses.p, b->poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
-    PCD_HIP_TRY(hipMemcpyAsync(S.lm_points.p, b->points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
-    pcd_ba_solve_summary sm{};
-    sm.termination = PCD_SOLVE_MAX_ITERATIONS;
-    double radius = opts->initial_radius, factor = 2.0, linear_ms = 0.0;
-    const pcd_ba_pcg_opts* lo = &opts->linear;
-    const uint8_t* ctvec = b->has_ctvec ? b->image_const_tvec.p : nullptr;
-    const uint8_t* cpt = b->has_cpt ? b->point_const.p : nullptr;
-    pcd_ba_out co{};
-    co.cost = S.lm_cand_cost.p;
+    PCD_TRY(copy_parameters(b, M.poses.p, M.points.p, b->poses.p, b->points.p, s));
+    pcd_ba_solve_summary sm{}; sm.termination = PCD_SOLVE_MAX_ITERATIONS;
+    double radius = opts->initial_radius, factor = 2.0;
     for (int it = 0; it < opts->max_num_iterations; ++it) {
       if (radius < opts->min_radius) { sm.termination = PCD_SOLVE_MIN_RADIUS; break; }
-      pcd_ba_schur_opts so{};
-      so.mu = 1.0 / radius; so.damping = opts->damping;
+      pcd_ba_schur_opts so{}; so.mu = 1.0 / radius; so.damping = opts->damping;
       pcd_ba_schur_out none{};
       PCD_TRY(pcd_ba_schur_device(b, &so, &none, s));
-      hipLaunchKernelGGL(k_ba_grad_max, dim3(ngp), dim3(256), 0, s, ns, S.slot_img.p, ctvec, S.gimg.p, P, cpt, S.gpt.p,
-                         S.lm_gpart.p);
+      hipLaunchKernelGGL(k_ba_grad_max, dim3(ngp), dim3(256), 0, s, S.st.ns, S.st.slot_img.p, b->const_tvec(), S.num.gimg.p,
+                         b->P, b->const_points(), S.num.gpt.p, M.gpart.p);
+      int enq = 0;
       PCD_HIP_TRY(ev.start(s));
-      int enq = lo->max_iterations;
-      if (direct) {   // fill + factor + solve: an exact step, so there is no second batch below
-        PCD_TRY(S.cg_info.reserve(1));
-        if (ns) {
-          ScopedKernelTimer t("ba_schur_cholesky", s);
-          PCD_TRY(chol_solve(b, nullptr, nullptr, S.lm_dpose.p, nullptr, s));
-          hipLaunchKernelGGL(k_chol_lm_info, dim3(1), dim3(1), 0, s, S.chol_info.p, S.cg_info.p);
-        } else {
-          PCD_HIP_TRY(hipMemsetAsync(S.cg_info.p, 0, sizeof(pcd_ba_pcg_info), s));   // 0 iterations, PCD_CHOL_OK
-        }
-      } else {
-        PCD_TRY(pcg_begin(b, lo, s));
-        enq = std::min(kPcgFirstBatch, lo->max_iterations);
-        pcg_enqueue(b, lo, enq, s);
-      }
+      PCD_TRY(lm_enqueue_linear(b, opts, &enq, s));
       PCD_HIP_TRY(ev.stop(s));
-      // the tail is enqueued behind the first batch without looking at the flag: at the defaults the PCG has ended
-      // by then and the iteration costs one copy; otherwise the batches go on and the tail runs once more
-      const LmRecord* rec = S.lm_host.p;
-      for (;;) {
-        if (!direct) pcg_finish(b, S.lm_dpose.p, S.cg_info.p, s);
-        PCD_TRY(pcd_ba_schur_back_substitute_device(b, S.lm_dpose.p, S.lm_dpoint.p, S.md.p, s));
-        PCD_TRY(pcd_ba_plus_device(b, S.lm_dpose.p, S.lm_dpoint.p, b->poses.p, b->points.p, s));
-        PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
-        hipLaunchKernelGGL(k_ba_lm_record, dim3(1), dim3(256), 0, s, S.cost.p, S.lm_cand_cost.p, S.md.p, S.lm_gpart.p,
-                           (int)ngp, S.skip_cnt.p, S.cg_info.p, S.lm_rec.p);
-        PCD_HIP_TRY(hipMemcpyAsync(S.lm_host.p, S.lm_rec.p, sizeof(LmRecord), hipMemcpyDeviceToHost, s));
-        PCD_HIP_TRY(hipStreamSynchronize(s));
-        float ms = 0.f;
-        if (ev.elapsed(&ms) == hipSuccess) linear_ms += ms;
-        if (rec->pcg.termination >= 0 || enq >= lo->max_iterations) break;
-        // the step just tried came from an unfinished solve: back to the accepted parameters, finish the solve
-        PCD_HIP_TRY(hipMemcpyAsync(b->poses.p, S.lm_poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
-        PCD_HIP_TRY(hipMemcpyAsync(b->points.p, S.lm_points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
-        PCD_HIP_TRY(ev.start(s));
-        PCD_TRY(pcg_run(b, lo, enq, s));
-        enq = lo->max_iterations;
-        PCD_HIP_TRY(ev.stop(s));
-      }
-      PCD_HIP_TRY(hipGetLastError());
-      if (it == 0) sm.initial_cost = sm.final_cost = rec->cost;
-      const bool restore_only = opts->gradient_tolerance > 0.0 && rec->gradient_max <= opts->gradient_tolerance;
-      pcd_ba_solve_iteration r{};
-      r.cost = rec->cost; r.candidate_cost = rec->candidate_cost; r.model_decrease = rec->model_decrease;
-      r.gradient_max_norm = rec->gradient_max; r.num_skipped = rec->num_skipped;
-      r.linear_iterations = rec->pcg.iterations; r.linear_termination = rec->pcg.termination;
-      const bool solved = direct ? rec->pcg.termination == PCD_CHOL_OK : rec->pcg.termination != PCD_PCG_BREAKDOWN;
-      const double rho = (solved && r.model_decrease > 0.0) ? (r.cost - r.candidate_cost) / r.model_decrease
-                                                            : -std::numeric_limits<double>::infinity();
-      r.relative_decrease = rho;
-      r.accepted = !restore_only && rho > opts->min_relative_decrease;
-      if (r.accepted) {
-        radius = std::min(opts->max_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3.0)));
-        factor = 2.0;
-        PCD_HIP_TRY(hipMemcpyAsync(S.lm_poses.p, b->poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
-        PCD_HIP_TRY(hipMemcpyAsync(S.lm_points.p, b->points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
-      } else {
-        PCD_HIP_TRY(hipMemcpyAsync(b->poses.p, S.lm_poses.p, nposes * sizeof(double), hipMemcpyDeviceToDevice, s));
-        PCD_HIP_TRY(hipMemcpyAsync(b->points.p, S.lm_points.p, npoints * sizeof(double), hipMemcpyDeviceToDevice, s));
-      }
-      if (restore_only) { sm.termination = PCD_SOLVE_GRADIENT_TOLERANCE; break; }
-      if (!r.accepted) { radius /= factor; factor *= 2.0; }
-      r.radius = radius;
-      if (iterations) iterations[it] = r;
+      PCD_TRY(lm_try_step(b, opts, enq, ngp, ev, &sm.linear_solver_ms, s));
+      const LmRecord& rec = *M.host.p;
+      if (it == 0) sm.initial_cost = sm.final_cost = rec.cost;
+      const LmDecision d = lm_decide(rec, *opts, radius, factor, opts->linear_solver == PCD_LINEAR_CHOLESKY);
+      if (d.it.accepted) PCD_TRY(copy_parameters(b, M.poses.p, M.points.p, b->poses.p, b->points.p, s));
+      else PCD_TRY(copy_parameters(b, b->poses.p, b->points.p, M.poses.p, M.points.p, s));
+      if (d.termination == PCD_SOLVE_GRADIENT_TOLERANCE) { sm.termination = d.termination; break; }   // no iteration recorded
+      radius = d.radius; factor = d.factor;
+      if (iterations) iterations[it] = d.it;
       sm.num_iterations = it + 1;
-      if (r.accepted) {
-        sm.num_accepted++;
-        sm.final_cost = r.candidate_cost;
-        if (opts->function_tolerance > 0.0 && std::fabs(r.cost - r.candidate_cost) <= opts->function_tolerance * r.cost) {
-          sm.termination = PCD_SOLVE_FUNCTION_TOLERANCE;
-          break;
-        }
-      }
+      if (d.it.accepted) { sm.num_accepted++; sm.final_cost = d.it.candidate_cost; }
+      if (d.termination >= 0) { sm.termination = d.termination; break; }
     }
     PCD_HIP_TRY(hipStreamSynchronize(s));
-    S.valid = false;   // the Schur state belongs to parameters the loop has moved on from
-    sm.linear_solver_ms = linear_ms;
+    S.num.valid = false;   // the Schur state belongs to parameters the loop has moved on from
     sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (summary) *summary = sm;
     return PCD_OK;
