@@ -1211,6 +1211,7 @@ pcd_status pcd_ba_set_camera_parameters(pcd_ba* b, const double* cam_params) {
   PCD_REQUIRE(b && cam_params, "null pointer");
   PCD_HIP_TRY(hipSetDevice(b->device));
   PCD_HIP_TRY(hipMemcpy(b->cam_params.p, cam_params, b->cam_params_len * sizeof(double), hipMemcpyHostToDevice));
+  b->h_cam_params.assign(cam_params, cam_params + b->cam_params_len);   // pcd_ba_project_lidar_device reads the mirror
   return PCD_OK;
 }
 

@@ -99,6 +99,9 @@ static pcd_status upload_problem(const pcd_ba_desc* d, pcd_ba* b) {
   for (int i = 1; i < d->num_images; ++i)
     if (d->image_camera[i] != b->shared_cam) b->shared_cam = -1;
   UP(cam_model, d->cam_model, b->C); UP(cam_off, d->cam_param_offset, b->C); UP(cam_params, d->cam_params, d->cam_params_len);
+  b->h_cam_model.assign(d->cam_model, d->cam_model + b->C); b->h_cam_off.assign(d->cam_param_offset, d->cam_param_offset + b->C);
+  b->h_cam_params.assign(d->cam_params, d->cam_params + d->cam_params_len);
+  b->h_image_cam.assign(d->image_camera, d->image_camera + b->I);
   UP(poses, d->poses, 7 * (size_t)b->I); UP(image_cam, d->image_camera, b->I);
   UP(points, d->points, 3 * (size_t)b->P);
   UP(obs_image, d->obs_image, b->O); UP(obs_point, d->obs_point, b->O); UP(obs_xy, d->obs_xy, 2 * b->O);
@@ -178,6 +181,7 @@ static pcd_status build_image_layout(const pcd_ba_desc* d, pcd_ba* b) {
   std::vector<uint32_t> st, li;
   build_csr(d->obs_image, b->O, b->I, st, li);
   UP(img_obs_start, st.data(), st.size());
+  b->h_img_obs_start = st;
   // segments of <= kImgSeg observations, never spanning two images (an image without observations has none)
   std::vector<uint32_t> seg_img, seg_begin, img_seg_start(b->I + 1, 0);
   for (int i = 0; i < b->I; ++i) {

@@ -61,6 +61,11 @@ struct BaLidarScratch {
   DevBuf<char> prim;                                      // rocPRIM temporary storage (scan, sort)
   PinnedBuf<uint32_t> h_status;
   DevBuf<double> a_xyz, a_abcd; DevBuf<uint8_t> a_type;   // association rows of pcd_ba_associate_lidar_device, [P]
+  // pcd_ba_project_lidar_device: per observation (the caller's order) whether its feature found a winner and the winner's
+  // x y z nx ny nz; the Proj rows [P] when they are merged with association rows; the counts of the info record
+  DevBuf<uint8_t> p_found, p_type; DevBuf<double> p_l6, p_xyz, p_abcd;
+  DevBuf<uint64_t> p_count_part, p_count;
+  PinnedBuf<uint64_t> h_count;
 };
 
 // The point-elimination state is complete in ba_solve.hip only.  The deleter is defined there, so a pcd_ba can be
@@ -117,6 +122,11 @@ struct pcd_ba {
   pcd::DevBuf<double> cam_params, poses, points, obs_xy, lidar_abcd, lidar_w, sell_xy, img_xy, pt_lidar_first;
   pcd::DevBuf<uint8_t> image_const_pose, image_const_tvec, point_const;
   bool has_cpose = false, has_ctvec = false, has_cpt = false;
+  // host mirrors of what pcd_ba_project_lidar_device decides on the host (focal lengths, the coefficient latch, the
+  // sizes of the depth images, the feature ranges): cam_params follows pcd_ba_set_camera_parameters, the rest is fixed
+  std::vector<double> h_cam_params;
+  std::vector<int> h_cam_model, h_cam_off, h_image_cam;
+  std::vector<uint32_t> h_img_obs_start;
   // per term, beside lidar_point / lidar_abcd / lidar_w: its pcd_lidar_type and LiDAR point, for the outlier filter.
   // pcd_ba_create knows neither: the buffers then do not exist until pcd_ba_lidar_device asks for them (zeros).
   pcd::DevBuf<uint8_t> lidar_type;

@@ -1,5 +1,5 @@
-// ba_lidar.hip -- the LiDAR terms of a BA handle rebuilt on the device (DESIGN 4.3b): pcd_ba_set_lidar_device,
-// pcd_ba_get_lidar / pcd_ba_lidar_device, pcd_ba_associate_lidar_device.
+// ba_lidar.hip -- the LiDAR terms of a BA handle rebuilt on the device (DESIGN 4.3b, 4.3c): pcd_ba_set_lidar_device,
+// pcd_ba_get_lidar / pcd_ba_lidar_device, pcd_ba_associate_lidar_device, pcd_ba_project_lidar_device.
 // What build_lidar_layout (ba_build.hip) makes on the host from the caller's term list is made here from Q device rows,
 // byte for byte: the terms (rows that pass the type / NaN rule, in ascending row order), the CSR point -> terms
 // (ascending term number) and the first term of every track in the thread order of k_ba_points.  The passes:
@@ -14,11 +14,15 @@
 //   k_lidar_tracks   thread of k_ba_points -> number of terms and the first of them, component-major
 // No atomics; every order is that of the rows: nothing depends on the launch geometry.  The new layout is built in
 // pcd_ba::lidar_next and swapped in at the end; a refusal returns before the swap.
+// pcd_ba_project_lidar_device makes its rows here too, in front of the same rebuild: the projector (proj.h)
+// writes found / lidar6 per observation, k_lidar_proj_pick picks per track, k_lidar_proj_merge folds the Proj rows into the
+// association's, k_lidar_proj_count* sum the counts of the info record.
 #include <cmath>
 
 #include "ba_handle.h"
 #include "cloud.h"
 #include "prim.h"
+#include "proj.h"
 
 namespace pcd {
 
@@ -175,6 +179,126 @@ __global__ __launch_bounds__(256) void k_lidar_tracks(uint32_t ntr, const int* _
   for (int k = 0; k < 5; ++k) first[(size_t)k * ntr + t] = f[k];
 }
 
+// ---- pcd_ba_project_lidar_device ------------------------------------------------------------------------
+// BundleAdjustmentConfig::MatchVariablePoint2LidarPoint (optim/bundle_adjustment.cc:288-350) for every track at once: one
+// thread per point walks its observations in ascending observation index (the track CSR).  The projector wrote found /
+// l6 in the CALLER's observation order (its read-out scatters through img_obs), so the walk reads the 48-byte candidate
+// of observation o at l6 + 6 o: one hop from pt_obs_list, not o -> image-major position -> row.  An observation of an
+// image that was not projected has found = 0.  Of several found observations of the point in ONE image only the first
+// counts (std::map::insert, pcd_projection.cc:79): a candidate is skipped when an earlier found observation of the track
+// has its image.  Double arithmetic in the order of shim/lidar_hip.h:326-346, no FMA (the unit is built without
+// contraction); strict < from 360, so ties stay with the lowest observation and a NaN never wins.  No atomics.
+__global__ __launch_bounds__(64) void k_lidar_proj_pick(int P, const uint32_t* __restrict__ pt_obs_start,
+                                                        const uint32_t* __restrict__ pt_obs_list,
+                                                        const int* __restrict__ obs_image, const uint8_t* __restrict__ found,
+                                                        const double* __restrict__ l6, const double* __restrict__ points,
+                                                        const uint8_t* __restrict__ mode, uint8_t* __restrict__ o_type,
+                                                        double* __restrict__ o_abcd, double* __restrict__ o_xyz) {
+  const uint32_t p = blockIdx.x * 64u + threadIdx.x;
+  if (p >= (uint32_t)P) return;
+  uint8_t ty = 0;
+  double abcd[4] = {0.0, 0.0, 0.0, 0.0}, xyz[3] = {0.0, 0.0, 0.0};
+  if (!mode || mode[p] == 1) {
+    const double X[3] = {points[3 * (size_t)p], points[3 * (size_t)p + 1], points[3 * (size_t)p + 2]};
+    const uint32_t kb = pt_obs_start[p], ke = pt_obs_start[p + 1];
+    double angle = 360;
+    double best[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t k = kb; k < ke; ++k) {
+      const uint32_t o = pt_obs_list[k];
+      if (!found[o]) continue;
+      const int img = obs_image[o];
+      bool dup = false;
+      for (uint32_t k2 = kb; k2 < k && !dup; ++k2) {
+        const uint32_t o2 = pt_obs_list[k2];
+        dup = found[o2] && obs_image[o2] == img;
+      }
+      if (dup) continue;
+      // the handle's own scratch: a 48-byte row is 16-byte aligned, three 16-byte loads
+      const double2* row = reinterpret_cast<const double2*>(l6 + 6 * (size_t)o);
+      const double2 r0 = row[0], r1 = row[1], r2 = row[2];
+      const double c[6] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y};
+      const double v[3] = {X[0] - c[0], X[1] - c[1], X[2] - c[2]};
+      const double dot = v[0] * c[3] + v[1] * c[4] + v[2] * c[5];
+      const double nn = sqrt(c[3] * c[3] + c[4] * c[4] + c[5] * c[5]);
+      const double vn = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+      const double a = fabs(dot / (nn * vn));
+      if (a < angle) {
+        angle = a;
+        for (int j = 0; j < 6; ++j) best[j] = c[j];
+      }
+    }
+    if (angle != 360) {   // lidar_point.cc:39-50: the plane normalised, d from the LiDAR point
+      ty = PCD_LIDAR_PROJ;
+      for (int j = 0; j < 3; ++j) xyz[j] = best[j];
+      const double norm = sqrt(best[3] * best[3] + best[4] * best[4] + best[5] * best[5]);
+      abcd[0] = best[3] / norm; abcd[1] = best[4] / norm; abcd[2] = best[5] / norm;
+      abcd[3] = 0 - abcd[0] * xyz[0] - abcd[1] * xyz[1] - abcd[2] * xyz[2];
+    }
+  }
+  o_type[p] = ty;
+  for (int j = 0; j < 4; ++j) o_abcd[4 * (size_t)p + j] = abcd[j];
+  for (int j = 0; j < 3; ++j) o_xyz[3 * (size_t)p + j] = xyz[j];
+}
+
+// The rows of the two routes into one: a_* hold the association of ALL points; a point of mode 1 takes its Proj row, a
+// point of mode 0 gets no term, a point of mode 2 keeps its association.  A mode above 2 becomes a type above 3, which
+// the rebuild's validation record counts: the refusal needs no read-back of its own.
+__global__ __launch_bounds__(256) void k_lidar_proj_merge(int P, const uint8_t* __restrict__ mode,
+                                                          const uint8_t* __restrict__ p_type, const double* __restrict__ p_abcd,
+                                                          const double* __restrict__ p_xyz, uint8_t* __restrict__ a_type,
+                                                          double* __restrict__ a_abcd, double* __restrict__ a_xyz) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= (uint32_t)P) return;
+  const uint8_t m = mode[p];
+  if (m == 2) return;
+  if (m == 1) {
+    a_type[p] = p_type[p];
+    for (int j = 0; j < 4; ++j) a_abcd[4 * (size_t)p + j] = p_abcd[4 * (size_t)p + j];
+    for (int j = 0; j < 3; ++j) a_xyz[3 * (size_t)p + j] = p_xyz[3 * (size_t)p + j];
+  } else {
+    a_type[p] = m == 0 ? 0 : 0xFF;
+  }
+}
+
+// The counts of pcd_ba_proj_info, without atomics: found observations per workgroup (kCountPer each), then one workgroup
+// sums those and, over the images, the selected ones and their observations -> count[0..3) = images, features, found
+constexpr uint32_t kCountPer = 4096;
+__device__ __forceinline__ uint64_t block_sum_256(uint64_t v, uint64_t* s_v) {
+  s_v[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) s_v[threadIdx.x] += s_v[threadIdx.x + w];
+    __syncthreads();
+  }
+  const uint64_t r = s_v[0];
+  __syncthreads();
+  return r;
+}
+__global__ __launch_bounds__(256) void k_lidar_proj_count_found(uint64_t O, const uint8_t* __restrict__ found,
+                                                                uint64_t* __restrict__ part) {
+  __shared__ uint64_t s_v[256];
+  const uint64_t base = (uint64_t)blockIdx.x * kCountPer;
+  uint64_t n = 0;
+  for (uint32_t k = threadIdx.x; k < kCountPer; k += 256)
+    if (base + k < O) n += found[base + k] ? 1u : 0u;
+  n = block_sum_256(n, s_v);
+  if (threadIdx.x == 0) part[blockIdx.x] = n;
+}
+__global__ __launch_bounds__(256) void k_lidar_proj_count(uint32_t nb, const uint64_t* __restrict__ part, int I,
+                                                          const uint8_t* __restrict__ select,
+                                                          const uint32_t* __restrict__ img_obs_start,
+                                                          uint64_t* __restrict__ count) {
+  __shared__ uint64_t s_v[256];
+  uint64_t f = 0, ni = 0, nf = 0;
+  for (uint32_t k = threadIdx.x; k < nb; k += 256) f += part[k];
+  for (int i = threadIdx.x; i < I; i += 256)
+    if (!select || select[i]) { ni += 1; nf += img_obs_start[i + 1] - img_obs_start[i]; }
+  f = block_sum_256(f, s_v);
+  ni = block_sum_256(ni, s_v);
+  nf = block_sum_256(nf, s_v);
+  if (threadIdx.x == 0) { count[0] = ni; count[1] = nf; count[2] = f; }
+}
+
 // what the host reads back
 struct LidarStatus {
   LidarPart part;
@@ -216,6 +340,7 @@ static pcd_status lidar_rebuild(pcd_ba* b, uint64_t Q, const int32_t* d_point, c
     PCD_HIP_TRY(hipStreamSynchronize(s));
     std::memcpy(&hs, N.h_status.p, sizeof hs);
   }
+  if (st) *st = hs;   // a caller that is refused below can still say what was wrong with ITS rows
   if (hs.part.bad) {
     set_error("pcd_ba_set_lidar_device: %u row(s) with a point outside [0, %d) or a type above 3; the handle is unchanged",
               hs.part.bad, P);
@@ -267,7 +392,6 @@ static pcd_status lidar_rebuild(pcd_ba* b, uint64_t Q, const int32_t* d_point, c
   b->L = L;
   b->has_lidar_meta = true;
   ba_schur_invalidate(b);
-  if (st) *st = hs;
   return PCD_OK;
 }
 
@@ -391,6 +515,132 @@ pcd_status pcd_ba_associate_lidar_device(pcd_ba* b, pcd_cloud* c, const pcd_ba_a
       info->num_terms = st.L;
       info->num_icp = st.part.ntype[0];
       info->num_icp_ground = st.part.ntype[1];
+    }
+    return PCD_OK;
+  });
+}
+
+void pcd_ba_proj_opts_default(pcd_ba_proj_opts* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->gate_mode = PCD_GATE_MAPPER_LOCAL;
+  o->proj_weight = 1.0;
+  o->icp_weight = 100.0;
+  o->icp_ground_weight = 1000.0;
+}
+
+pcd_status pcd_ba_project_lidar_device(pcd_ba* b, pcd_proj* proj, const pcd_ba_proj_opts* opts, void* stream,
+                                       pcd_ba_proj_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    if (info) std::memset(info, 0, sizeof *info);
+    PCD_REQUIRE(opts, "null options");
+    PCD_REQUIRE(opts->cam_width && opts->cam_height, "null cam_width / cam_height");
+    PCD_REQUIRE(b, "null handle");
+    PCD_REQUIRE(proj, "null projector");
+    const bool mixed = opts->d_point_mode != nullptr;   // some point may take the nearest-neighbour route
+    const uint64_t P = (uint64_t)b->P;
+    const int mode = opts->gate_mode & ~PCD_GATE_BOUNDED_SEARCH;
+    if (mixed) {
+      PCD_REQUIRE(mode >= 0 && mode <= 2, "gate_mode");
+      PCD_REQUIRE(mode == PCD_GATE_CONTROLLER ||
+                  (opts->d_max_range && (opts->max_range_count == 1 || opts->max_range_count == P)),
+                  "max_range must have 1 or num_points entries");
+    }
+    pcd_cloud* c = proj_cloud(proj);
+    PCD_REQUIRE(b->device == c->device, "the BA handle and the projector live on different devices");
+    if (mixed && (c->row_index.p || c->g2l.p || c->index_stride != 1 || c->index_base != 0)) {
+      set_error("pcd_ba_project_lidar_device needs ONE handle holding the whole cloud, not a shard or a strided handle");
+      return PCD_ERR_UNSUPPORTED;
+    }
+    for (int k = 0; k < b->C; ++k) {   // pcd_proj_set_new_images' check, on the host mirror: params[0], params[1] of an OPENCV camera
+      const double* cp = b->h_cam_params.data() + b->h_cam_off[k];
+      const int K = cam_num_params(b->h_cam_model[k]);
+      PCD_REQUIRE(cp[0] != 0 && (K > 1 ? cp[1] : 0.0) != 0, "focal length");
+    }
+    PCD_TRY(lidar_guards(b, stream, "pcd_ba_project_lidar_device"));
+    if (P == 0) return PCD_OK;
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream;
+    BaLidarScratch& N = b->lidar_next;
+    const uint64_t O = b->O;
+    const int I = b->I;
+    PCD_TRY(N.a_xyz.reserve(3 * P)); PCD_TRY(N.a_abcd.reserve(4 * P)); PCD_TRY(N.a_type.reserve(P));
+    PCD_TRY(N.p_found.reserve(at_least_1(O))); PCD_TRY(N.p_l6.reserve(at_least_1(6 * O)));
+    if (mixed) { PCD_TRY(N.p_xyz.reserve(3 * P)); PCD_TRY(N.p_abcd.reserve(4 * P)); PCD_TRY(N.p_type.reserve(P)); }
+    const uint32_t nbf = div_up(O, kCountPer);
+    if (info) {
+      PCD_TRY(N.p_count_part.reserve(at_least_1(nbf))); PCD_TRY(N.p_count.reserve(3)); PCD_TRY(N.h_count.reserve(3));
+    }
+    EventPair ep, ea, er;
+    if (info) { PCD_TRY(ep.create()); PCD_TRY(ea.create()); PCD_TRY(er.create()); (void)ep.start(s); }
+    // the images: sizes and parameter counts by camera, from the mirrors; poses and parameters stay where they are
+    std::vector<uint64_t> width((size_t)I), height((size_t)I);
+    std::vector<int> nprm((size_t)I);
+    for (int i = 0; i < I; ++i) {
+      const int cam = b->h_image_cam[i];
+      width[i] = opts->cam_width[cam];
+      height[i] = opts->cam_height[cam];
+      nprm[i] = cam_num_params(b->h_cam_model[cam]);
+    }
+    ProjDeviceImages im;
+    im.n = (uint64_t)I;
+    im.width = width.data(); im.height = height.data(); im.num_params = nprm.data();
+    im.feat_start = b->h_img_obs_start.data();
+    {
+      const int cam0 = b->h_image_cam[0];
+      const double* cp = b->h_cam_params.data() + b->h_cam_off[cam0];
+      im.latch_fx = cp[0];
+      im.latch_fy = cam_num_params(b->h_cam_model[cam0]) > 1 ? cp[1] : 0.0;
+    }
+    im.d_poses = b->poses.p; im.d_image_cam = b->image_cam.p; im.d_cam_off = b->cam_off.p;
+    im.d_cam_params = b->cam_params.p; im.d_select = opts->d_image_select;
+    // from here to the rebuild's synchronisation the projector's pinned scratch is in flight: a refusal waits for s
+    auto fail = [&](pcd_status st) { (void)hipStreamSynchronize(s); return st; };
+    pcd_status st = proj_project_device_images(proj, im, O, b->img_xy.p, b->img_obs.p, N.p_found.p, N.p_l6.p, s);
+    if (st != PCD_OK) return fail(st);
+    {
+      ScopedKernelTimer t("ba_lidar_proj_pick", s);
+      hipLaunchKernelGGL(k_lidar_proj_pick, dim3(div_up(P, 64)), dim3(64), 0, s, b->P, b->pt_obs_start.p, b->pt_obs_list.p,
+                         b->obs_image.p, N.p_found.p, N.p_l6.p, b->points.p, opts->d_point_mode,
+                         mixed ? N.p_type.p : N.a_type.p, mixed ? N.p_abcd.p : N.a_abcd.p, mixed ? N.p_xyz.p : N.a_xyz.p);
+    }
+    if (info) {
+      hipLaunchKernelGGL(k_lidar_proj_count_found, dim3(std::max(nbf, 1u)), dim3(256), 0, s, O, N.p_found.p, N.p_count_part.p);
+      hipLaunchKernelGGL(k_lidar_proj_count, dim3(1), dim3(256), 0, s, O ? nbf : 0u, N.p_count_part.p, I, opts->d_image_select,
+                         b->img_obs_start.p, N.p_count.p);
+      PCD_HIP_TRY(hipMemcpyAsync(N.h_count.p, N.p_count.p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+      (void)ep.stop(s); (void)ea.start(s);
+    }
+    if (mixed) {
+      pcd_assoc_out ao{};
+      ao.lidar_xyz = N.a_xyz.p; ao.abcd = N.a_abcd.p; ao.type = N.a_type.p;
+      st = pcd_associate_device(c, b->points.p, P, opts->d_max_range, opts->max_range_count, opts->gate_mode, nullptr, &ao,
+                                stream);
+      if (st != PCD_OK) return fail(st);
+      hipLaunchKernelGGL(k_lidar_proj_merge, dim3(div_up(P, 256)), dim3(256), 0, s, b->P, opts->d_point_mode, N.p_type.p,
+                         N.p_abcd.p, N.p_xyz.p, N.a_type.p, N.a_abcd.p, N.a_xyz.p);
+    }
+    if (info) { (void)ea.stop(s); (void)er.start(s); }
+    const double weight[4] = {0.0, opts->icp_weight, opts->icp_ground_weight, opts->proj_weight};
+    LidarStatus ls{};
+    st = lidar_rebuild(b, P, nullptr, N.a_type.p, N.a_abcd.p, N.a_xyz.p, nullptr, weight, s, &ls);   // synchronises s
+    if (st != PCD_OK) (void)hipStreamSynchronize(s);   // a rebuild that failed ahead of its synchronisation
+    const uint64_t pairs = proj_collect_pairs(proj);
+    if (st == PCD_ERR_INVALID && ls.part.bad)
+      set_error("pcd_ba_project_lidar_device: %u point_mode value(s) above 2; the handle is unchanged", ls.part.bad);
+    PCD_TRY(st);
+    if (info) {
+      float ms = 0.f;
+      PCD_HIP_TRY(er.stop_and_wait(s, &ms));
+      info->rebuild_ms = ms;
+      PCD_HIP_TRY(ea.elapsed(&ms));
+      info->assoc_ms = ms;
+      PCD_HIP_TRY(ep.elapsed(&ms));
+      info->proj_ms = ms;
+      info->num_images = N.h_count.p[0]; info->num_features = N.h_count.p[1]; info->num_found = N.h_count.p[2];
+      info->num_terms = ls.L;
+      info->num_icp = ls.part.ntype[0]; info->num_icp_ground = ls.part.ntype[1]; info->num_proj = ls.part.ntype[2];
+      info->pairs = pairs;
     }
     return PCD_OK;
   });

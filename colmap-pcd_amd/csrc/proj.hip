@@ -25,6 +25,7 @@
 #include "cloud.h"
 #include "grid.h"
 #include "prim.h"
+#include "proj.h"
 
 namespace pcd {
 
@@ -53,6 +54,102 @@ __device__ __host__ __forceinline__ float dot3_e(float a0, float b0, float a1, f
   const float p0 = a0 * b0, p1 = a1 * b1, p2 = a2 * b2;
   const float s = p1 + p2;
   return p0 + s;
+}
+
+// Eigen::Quaterniond(w,x,y,z).toRotationMatrix(): no normalisation
+__host__ __device__ inline void quat_to_rot(const double* q, double* R) {
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w;
+  const double txx = tx * x, txy = ty * x, txz = tz * x;
+  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
+  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+}
+
+// pcd_projection.h:139-146
+__host__ __device__ inline void get_plane(const float* a, const float* b, const float* c, float* pl) {
+  const float ab[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
+  const float ac[3] = {a[0] - c[0], a[1] - c[1], a[2] - c[2]};
+  const float n0 = ab[1] * ac[2] - ab[2] * ac[1];
+  const float n1 = ab[2] * ac[0] - ab[0] * ac[2];
+  const float n2 = ab[0] * ac[1] - ab[1] * ac[0];
+  float d = n0 * a[0] + n1 * a[1];
+  d = d + n2 * a[2];
+  pl[0] = n0; pl[1] = n1; pl[2] = n2; pl[3] = -d;
+}
+
+// SetNewImage head + SearchSubMap, all in the reference's float/double mix, in two halves.  Host and device run the
+// SAME statements (the unit is compiled without FMA contraction on both sides), so a record made by k_proj_prepare
+// from a pose that is on the device has the bits of one the host makes from a copy of that pose.
+//   image_dims   what the sizes alone decide: the scaled image, which the host needs to lay the winner buffers out
+//   image_pose   the rest, from the pose and the OPENCV parameters; reads d->w / d->h
+__host__ __device__ inline void image_dims(double scale, uint64_t width, uint64_t height, ProjImageDev* d) {
+  d->h = (int)((double)height * scale);
+  d->w = (int)((double)width * scale);
+  d->row_words = d->w > 0 ? (d->w + 31) / 32 : 0;
+  d->pad = 0;
+}
+__host__ __device__ inline void image_pose(const pcd_proj_options& o, const double* qvec, const double* tvec,
+                                           const double* params, ProjImageDev* d) {
+  const double scale = o.depth_image_scale;
+  double Rd[9];
+  quat_to_rot(qvec, Rd);
+  for (int k = 0; k < 9; ++k) d->R[k] = (float)Rd[k];
+  for (int k = 0; k < 3; ++k) d->t[k] = (float)tvec[k];
+  for (int k = 0; k < 8; ++k) d->prm[k] = params[k];
+  const double ifx = params[0] * scale, ify = params[1] * scale;
+  const double icx = params[2] * scale, icy = params[3] * scale;
+  float Rt[9];
+  for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Rt[3 * r + c] = d->R[3 * c + r];
+  float twc[3];
+  for (int r = 0; r < 3; ++r) twc[r] = dot3_e(-Rt[3 * r], d->t[0], -Rt[3 * r + 1], d->t[1], -Rt[3 * r + 2], d->t[2]);
+  const float xb_min = (float)(-icx / ifx), xb_max = (float)(((double)d->w - icx) / ifx);
+  const float yb_min = (float)(-icy / ify), yb_max = (float)(((double)d->h - icy) / ify);
+  const float dir[4][2] = {{xb_max, yb_max}, {xb_max, yb_min}, {xb_min, yb_min}, {xb_min, yb_max}};
+  float corner[4][3];
+  for (int c = 0; c < 4; ++c)
+    for (int r = 0; r < 3; ++r) {
+      float v = dot3_e(Rt[3 * r], dir[c][0], Rt[3 * r + 1], dir[c][1], Rt[3 * r + 2], 1.0f);
+      v = v * o.choose_meter;
+      corner[c][r] = twc[r] + v;
+    }
+  get_plane(corner[0], corner[3], corner[2], d->pl[0]);
+  get_plane(twc, corner[0], corner[1], d->pl[1]);
+  get_plane(twc, corner[1], corner[2], d->pl[2]);
+  get_plane(twc, corner[2], corner[3], d->pl[3]);
+  get_plane(twc, corner[3], corner[0], d->pl[4]);
+  d->sx_near = (int)((double)o.max_proj_scale * (params[0] / 3039.0) * (scale / 0.2));
+  d->sy_near = (int)((double)o.max_proj_scale * (params[1] / 3039.0) * (scale / 0.2));
+}
+__host__ __device__ inline void prepare_image(const pcd_proj_options& o, const pcd_proj_image& in, ProjImageDev* d) {
+  image_dims(o.depth_image_scale, in.width, in.height, d);
+  image_pose(o, in.qvec, in.tvec, in.params, d);
+  d->feat_begin = in.feat_begin;
+  d->feat_end = in.feat_end;
+}
+
+// The records of images whose pose and camera are on the device (pcd_ba_project_lidar_device).  The host uploaded the
+// skeleton of every record: image_dims, the feature range, the buffer offsets, and in `pad` the camera's parameter
+// count K.  One thread per image completes it: prm[k] = k < K ? cam_params[off + k] : 0, image_pose at poses[i].  An
+// image that is not selected gets an empty scaled image: nothing is culled, splatted or found for it.
+__global__ __launch_bounds__(64) void k_proj_prepare(uint32_t n_img, pcd_proj_options o, const double* __restrict__ poses,
+                                                     const int* __restrict__ image_cam, const int* __restrict__ cam_off,
+                                                     const double* __restrict__ cam_params,
+                                                     const uint8_t* __restrict__ select, ProjImageDev* __restrict__ imgs) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n_img) return;
+  ProjImageDev d = imgs[i];
+  const int K = d.pad;
+  d.pad = 0;
+  const double* cp = cam_params + cam_off[image_cam[i]];
+  double prm[8], pose[7];
+  for (int k = 0; k < 8; ++k) prm[k] = k < K ? cp[k] : 0.0;
+  for (int k = 0; k < 7; ++k) pose[k] = poses[7 * (size_t)i + k];
+  image_pose(o, pose, pose + 4, prm, &d);
+  if (select && !select[i]) d.w = d.h = d.row_words = 0;
+  imgs[i] = d;
 }
 
 __device__ __forceinline__ bool finite3(float4 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
@@ -295,7 +392,7 @@ __global__ __launch_bounds__(256) void k_proj_splat(const ProjImageDev* __restri
 
 __global__ void k_proj_readout(const ProjImageDev* __restrict__ imgs, const double* __restrict__ feat_xy,
                                double scale, const uint64_t* __restrict__ zbuf, const float4* __restrict__ sorted,
-                               const float4* __restrict__ pn8,
+                               const float4* __restrict__ pn8, const uint32_t* __restrict__ out_row,
                                uint8_t* __restrict__ found, uint32_t* __restrict__ index, float* __restrict__ dist,
                                double* __restrict__ l6, double* __restrict__ cam_xyz) {
   const uint32_t ii = blockIdx.y;
@@ -326,11 +423,12 @@ __global__ void k_proj_readout(const ProjImageDev* __restrict__ imgs, const doub
       cxyz[1] = z * (vv - cy) / fy;
       cxyz[2] = z;
     }
-    if (found) found[g] = ok ? 1 : 0;
-    if (index) index[g] = idx;
-    if (dist) dist[g] = d;
-    if (l6) for (int k = 0; k < 6; ++k) l6[6 * g + k] = o[k];
-    if (cam_xyz) for (int k = 0; k < 3; ++k) cam_xyz[3 * g + k] = cxyz[k];
+    const uint64_t r = out_row ? out_row[g] : g;   // the row the caller wants feature g in (nullptr: its own)
+    if (found) found[r] = ok ? 1 : 0;
+    if (index) index[r] = idx;
+    if (dist) dist[r] = d;
+    if (l6) for (int k = 0; k < 6; ++k) l6[6 * r + k] = o[k];
+    if (cam_xyz) for (int k = 0; k < 3; ++k) cam_xyz[3 * r + k] = cxyz[k];
   }
 }
 
@@ -360,6 +458,11 @@ struct pcd_proj {
   DevBuf<float> o_dist;
   DevBuf<double> o_l6, o_cam;
   uint64_t last_items = 0;
+  // one call's records as they are uploaded, and its chunks' pair counts as they come back: both pinned, so that
+  // neither copy makes the launcher wait
+  PinnedBuf<ProjImageDev> h_imgs;
+  PinnedBuf<unsigned> h_cnt;
+  uint32_t n_chunks = 0;
 };
 
 namespace {
@@ -368,30 +471,6 @@ int bits_for(int64_t range) {
   int b = 1;
   while ((1ll << b) <= range) ++b;
   return b;
-}
-
-// Eigen::Quaterniond(w,x,y,z).toRotationMatrix(): no normalisation
-void quat_to_rot(const double* q, double* R) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-
-// pcd_projection.h:139-146
-void get_plane(const float* a, const float* b, const float* c, float* pl) {
-  const float ab[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
-  const float ac[3] = {a[0] - c[0], a[1] - c[1], a[2] - c[2]};
-  const float n0 = ab[1] * ac[2] - ab[2] * ac[1];
-  const float n1 = ab[2] * ac[0] - ab[0] * ac[2];
-  const float n2 = ab[0] * ac[1] - ab[1] * ac[0];
-  float d = n0 * a[0] + n1 * a[1];
-  d = d + n2 * a[2];
-  pl[0] = n0; pl[1] = n1; pl[2] = n2; pl[3] = -d;
 }
 
 void scale_coeffs(const pcd_proj_options& o, double fx, double fy, double* c4) {
@@ -404,45 +483,6 @@ void scale_coeffs(const pcd_proj_options& o, double fx, double fy, double* c4) {
   c4[1] = min_x - c4[0] * (double)o.choose_meter;
   c4[2] = (max_y - min_y) / (o.min_proj_dist - (double)o.choose_meter);
   c4[3] = (double)o.min_proj_scale - c4[2] * (double)o.choose_meter;   // sic: pcd_projection.cc:397
-}
-
-// SetNewImage head + SearchSubMap, all in the reference's float/double mix
-void prepare_image(const pcd_proj_options& o, const pcd_proj_image& in, ProjImageDev* d) {
-  const double scale = o.depth_image_scale;
-  d->h = (int)((double)in.height * scale);
-  d->w = (int)((double)in.width * scale);
-  d->row_words = d->w > 0 ? (d->w + 31) / 32 : 0;
-  d->pad = 0;
-  double Rd[9];
-  quat_to_rot(in.qvec, Rd);
-  for (int k = 0; k < 9; ++k) d->R[k] = (float)Rd[k];
-  for (int k = 0; k < 3; ++k) d->t[k] = (float)in.tvec[k];
-  for (int k = 0; k < 8; ++k) d->prm[k] = in.params[k];
-  const double ifx = in.params[0] * scale, ify = in.params[1] * scale;
-  const double icx = in.params[2] * scale, icy = in.params[3] * scale;
-  float Rt[9];
-  for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Rt[3 * r + c] = d->R[3 * c + r];
-  float twc[3];
-  for (int r = 0; r < 3; ++r) twc[r] = dot3_e(-Rt[3 * r], d->t[0], -Rt[3 * r + 1], d->t[1], -Rt[3 * r + 2], d->t[2]);
-  const float xb_min = (float)(-icx / ifx), xb_max = (float)(((double)d->w - icx) / ifx);
-  const float yb_min = (float)(-icy / ify), yb_max = (float)(((double)d->h - icy) / ify);
-  const float dir[4][2] = {{xb_max, yb_max}, {xb_max, yb_min}, {xb_min, yb_min}, {xb_min, yb_max}};
-  float corner[4][3];
-  for (int c = 0; c < 4; ++c)
-    for (int r = 0; r < 3; ++r) {
-      float v = dot3_e(Rt[3 * r], dir[c][0], Rt[3 * r + 1], dir[c][1], Rt[3 * r + 2], 1.0f);
-      v = v * o.choose_meter;
-      corner[c][r] = twc[r] + v;
-    }
-  get_plane(corner[0], corner[3], corner[2], d->pl[0]);
-  get_plane(twc, corner[0], corner[1], d->pl[1]);
-  get_plane(twc, corner[1], corner[2], d->pl[2]);
-  get_plane(twc, corner[2], corner[3], d->pl[3]);
-  get_plane(twc, corner[3], corner[0], d->pl[4]);
-  d->sx_near = (int)((double)o.max_proj_scale * (in.params[0] / 3039.0) * (scale / 0.2));
-  d->sy_near = (int)((double)o.max_proj_scale * (in.params[1] / 3039.0) * (scale / 0.2));
-  d->feat_begin = in.feat_begin;
-  d->feat_end = in.feat_end;
 }
 
 pcd_status build_submaps(pcd_proj* p) {
@@ -560,10 +600,124 @@ pcd_status pcd_proj_scale_coeffs(pcd_proj* p, int set, double* coeffs4, int* lat
   return PCD_OK;
 }
 
-pcd_status pcd_proj_set_new_images(pcd_proj* p, uint64_t n_images, const pcd_proj_image* images, uint64_t n_feat,
-                                   const double* feat_xy, uint8_t* found, uint32_t* lidar_index, float* dist,
-                                   double* lidar6, double* cam_xyz) {
-  return pcd::guard([&]() -> pcd_status {
+
+}  // extern "C"
+
+namespace {
+
+struct ProjOutputs {   // device, each may be nullptr
+  uint8_t* found; uint32_t* index; float* dist; double* l6; double* cam;
+};
+
+// The one launcher behind pcd_proj_set_new_images, its _device form and pcd_ba_project_lidar_device.  recs: one record
+// per image, complete (prepare_image on the host) or, with `fill`, the skeleton k_proj_prepare completes on the device.
+// The batch is cut into chunks so that the (image, submap) pair list and the winner buffers stay bounded; the cut
+// depends on the image sizes alone.  Everything is enqueued on s and nothing waits: the records go up from pinned
+// memory and every chunk's pair count comes back into pinned memory (proj_collect_pairs, once s has been synchronised).
+pcd_status proj_launch(pcd_proj* p, const std::vector<ProjImageDev>& recs, const ProjDeviceImages* fill, uint64_t n_feat,
+                       const double* d_feat, const uint32_t* d_out_row, const ProjOutputs& out, hipStream_t s) {
+  const uint64_t n_images = recs.size();
+  const ProjConst pc{p->opt.depth_image_scale, p->opt.min_lidar_proj_dist, p->opt.min_proj_dist,
+                     p->coeffs[0], p->coeffs[1], p->coeffs[2], p->coeffs[3]};
+  p->n_chunks = 0;
+  p->last_items = 0;
+  // features outside every image range keep found = 0
+  if (n_feat) {
+    if (out.found) PCD_HIP_TRY(hipMemsetAsync(out.found, 0, n_feat, s));
+    if (out.index) PCD_HIP_TRY(hipMemsetAsync(out.index, 0xFF, n_feat * 4, s));
+    if (out.dist) PCD_HIP_TRY(hipMemsetAsync(out.dist, 0, n_feat * 4, s));
+    if (out.l6) PCD_HIP_TRY(hipMemsetAsync(out.l6, 0, 6 * n_feat * 8, s));
+    if (out.cam) PCD_HIP_TRY(hipMemsetAsync(out.cam, 0, 3 * n_feat * 8, s));
+  }
+  if (n_images == 0) return PCD_OK;
+  const uint64_t kMaxItems = 32ull << 20, kMaxZ = 1ull << 30;   // 256 MB of pairs, 8 GB of winner slots
+  const uint64_t per_chunk = std::max<uint64_t>(1, kMaxItems / std::max<uint32_t>(p->n_sub, 1));
+  struct Chunk { uint64_t i0, i1, zsize, bsize, maxf; };
+  std::vector<Chunk> chunks;
+  PCD_TRY(p->h_imgs.reserve(n_images));
+  uint64_t max_z = 1, max_b = 1, max_ni = 1;
+  for (uint64_t i0 = 0; i0 < n_images;) {
+    uint64_t zoff = 0, boff = 0, maxf = 0;
+    uint64_t i1 = i0;
+    while (i1 < n_images && (i1 - i0) < per_chunk) {
+      ProjImageDev d = recs[i1];
+      const uint64_t px = d.w > 0 && d.h > 0 ? (uint64_t)d.w * d.h : 0;
+      if (i1 > i0 && zoff + px > kMaxZ) break;
+      d.zoff = zoff;
+      d.boff = boff;
+      zoff += px;
+      boff += d.h > 0 ? (uint64_t)d.row_words * d.h : 0;
+      maxf = std::max(maxf, d.feat_end - d.feat_begin);
+      p->h_imgs.p[i1] = d;
+      ++i1;
+    }
+    chunks.push_back({i0, i1, zoff, boff, maxf});
+    max_z = std::max(max_z, zoff);
+    max_b = std::max(max_b, boff);
+    max_ni = std::max(max_ni, i1 - i0);
+    i0 = i1;
+  }
+  PCD_TRY(p->d_imgs.reserve(n_images));
+  PCD_TRY(p->zbuf.reserve(max_z));
+  PCD_TRY(p->bitmap.reserve(max_b));
+  PCD_TRY(p->items.reserve(std::max<uint64_t>(max_ni * p->n_sub, 1)));
+  PCD_TRY(p->n_items.reserve(1));
+  PCD_TRY(p->h_cnt.reserve(chunks.size()));
+  PCD_HIP_TRY(hipMemcpyAsync(p->d_imgs.p, p->h_imgs.p, n_images * sizeof(ProjImageDev), hipMemcpyHostToDevice, s));
+  if (fill) {
+    ScopedKernelTimer t("proj_prepare", s);
+    hipLaunchKernelGGL(k_proj_prepare, dim3(div_up(n_images, 64)), dim3(64), 0, s, (uint32_t)n_images, p->opt, fill->d_poses,
+                       fill->d_image_cam, fill->d_cam_off, fill->d_cam_params, fill->d_select, p->d_imgs.p);
+  }
+  for (size_t c = 0; c < chunks.size(); ++c) {
+    const Chunk& ch = chunks[c];
+    const uint32_t ni = (uint32_t)(ch.i1 - ch.i0);
+    const uint64_t maxf = ch.maxf;
+    const ProjImageDev* imgs = p->d_imgs.p + ch.i0;
+    PCD_HIP_TRY(hipMemsetAsync(p->bitmap.p, 0, std::max<uint64_t>(ch.bsize, 1) * 4, s));
+    PCD_HIP_TRY(hipMemsetAsync(p->n_items.p, 0, sizeof(unsigned), s));
+    const unsigned fblocks = std::max(1u, std::min(div_up(maxf, 256), 1024u));
+    if (maxf) {
+      ScopedKernelTimer t("proj_feat_init", s);
+      hipLaunchKernelGGL(k_proj_feat_init, dim3(fblocks, ni), dim3(256), 0, s, imgs, ni, d_feat, pc.scale, p->bitmap.p,
+                         p->zbuf.p);
+    }
+    if (maxf && p->n_sub) {
+      {
+        ScopedKernelTimer t("proj_cull", s);
+        hipLaunchKernelGGL(k_proj_cull, dim3(div_up(p->n_sub, 256), ni), dim3(256), 0, s, imgs, p->sub_key.p,
+                           p->n_sub, p->opt.submap_length, p->opt.submap_height, p->opt.submap_width, p->items.p,
+                           p->n_items.p);
+      }
+      {
+        ScopedKernelTimer t("proj_splat", s);
+        hipLaunchKernelGGL(k_proj_splat, dim3(256 * 8), dim3(256), 0, s, imgs, p->items.p, p->n_items.p,
+                           p->sub_start.p, p->sorted.p, pc, p->bitmap.p, p->zbuf.p);
+      }
+    }
+    if (maxf) {
+      ScopedKernelTimer t("proj_readout", s);
+      hipLaunchKernelGGL(k_proj_readout, dim3(fblocks, ni), dim3(256), 0, s, imgs, d_feat, pc.scale, p->zbuf.p,
+                         p->sorted.p, p->cloud->pn8.p, d_out_row, out.found, out.index, out.dist, out.l6, out.cam);
+    }
+    PCD_HIP_TRY(hipGetLastError());
+    // the next chunk reuses the pair list and the winner buffers: the stream orders it behind this copy
+    PCD_HIP_TRY(hipMemcpyAsync(p->h_cnt.p + c, p->n_items.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  }
+  p->n_chunks = (uint32_t)chunks.size();
+  return PCD_OK;
+}
+
+// the reference's function-local statics latch on the first camera it projects with
+void latch_coeffs(pcd_proj* p, double fx, double fy) {
+  if (p->latched) return;
+  scale_coeffs(p->opt, fx, fy, p->coeffs);
+  p->latched = true;
+}
+
+// the checks the two public forms share
+pcd_status check_images(const pcd_proj* p, uint64_t n_images, const pcd_proj_image* images, uint64_t n_feat,
+                        const double* feat_xy) {
   PCD_REQUIRE(p, "null pointer");
   if (n_images == 0) return PCD_OK;
   PCD_REQUIRE(images, "null images");
@@ -572,90 +726,66 @@ pcd_status pcd_proj_set_new_images(pcd_proj* p, uint64_t n_images, const pcd_pro
     PCD_REQUIRE(images[i].feat_begin <= images[i].feat_end && images[i].feat_end <= n_feat, "feature range");
     PCD_REQUIRE(images[i].params[0] != 0 && images[i].params[1] != 0, "focal length");
   }
+  return PCD_OK;
+}
+
+pcd_status host_records(pcd_proj* p, uint64_t n_images, const pcd_proj_image* images, std::vector<ProjImageDev>& recs) {
+  latch_coeffs(p, images[0].params[0], images[0].params[1]);
+  recs.resize(n_images);
+  for (uint64_t i = 0; i < n_images; ++i) prepare_image(p->opt, images[i], &recs[i]);
+  return PCD_OK;
+}
+
+}  // namespace
+
+namespace pcd {
+
+uint64_t proj_collect_pairs(pcd_proj* p) {
+  uint64_t sum = 0;
+  for (uint32_t c = 0; c < p->n_chunks; ++c) sum += p->h_cnt.p[c];
+  p->last_items = sum;
+  return sum;
+}
+
+pcd_cloud* proj_cloud(pcd_proj* p) { return p->cloud; }
+
+pcd_status proj_project_device_images(pcd_proj* p, const ProjDeviceImages& in, uint64_t n_feat, const double* d_feat_xy,
+                                      const uint32_t* d_out_row, uint8_t* d_found, double* d_l6, hipStream_t s) {
+  if (in.n) latch_coeffs(p, in.latch_fx, in.latch_fy);
+  std::vector<ProjImageDev> recs(in.n);
+  for (uint64_t i = 0; i < in.n; ++i) {
+    ProjImageDev& d = recs[i];
+    std::memset(&d, 0, sizeof d);
+    image_dims(p->opt.depth_image_scale, in.width[i], in.height[i], &d);
+    d.pad = in.num_params[i];
+    d.feat_begin = in.feat_start[i];
+    d.feat_end = in.feat_start[i + 1];
+  }
+  const ProjOutputs out{d_found, nullptr, nullptr, d_l6, nullptr};
+  return proj_launch(p, recs, &in, n_feat, d_feat_xy, d_out_row, out, s);
+}
+
+}  // namespace pcd
+
+extern "C" {
+
+pcd_status pcd_proj_set_new_images(pcd_proj* p, uint64_t n_images, const pcd_proj_image* images, uint64_t n_feat,
+                                   const double* feat_xy, uint8_t* found, uint32_t* lidar_index, float* dist,
+                                   double* lidar6, double* cam_xyz) {
+  return pcd::guard([&]() -> pcd_status {
+  PCD_TRY(check_images(p, n_images, images, n_feat, feat_xy));
+  if (n_images == 0) return PCD_OK;
   PCD_HIP_TRY(hipSetDevice(p->cloud->device));
   hipStream_t s = nullptr;
-  if (!p->latched) {   // the reference's function-local statics latch on the first camera it projects with
-    scale_coeffs(p->opt, images[0].params[0], images[0].params[1], p->coeffs);
-    p->latched = true;
-  }
-  const ProjConst pc{p->opt.depth_image_scale, p->opt.min_lidar_proj_dist, p->opt.min_proj_dist,
-                     p->coeffs[0], p->coeffs[1], p->coeffs[2], p->coeffs[3]};
+  std::vector<ProjImageDev> recs;
+  PCD_TRY(host_records(p, n_images, images, recs));
   const uint64_t nfa = std::max<uint64_t>(n_feat, 1);
   PCD_TRY(p->d_feat.reserve(2 * nfa));
   PCD_TRY(p->o_found.reserve(nfa)); PCD_TRY(p->o_index.reserve(nfa)); PCD_TRY(p->o_dist.reserve(nfa));
   PCD_TRY(p->o_l6.reserve(6 * nfa)); PCD_TRY(p->o_cam.reserve(3 * nfa));
-  PCD_TRY(p->n_items.reserve(1));
   if (n_feat) PCD_HIP_TRY(hipMemcpyAsync(p->d_feat.p, feat_xy, 2 * n_feat * sizeof(double), hipMemcpyHostToDevice, s));
-  // features outside every image range keep found = 0
-  PCD_HIP_TRY(hipMemsetAsync(p->o_found.p, 0, nfa, s));
-  PCD_HIP_TRY(hipMemsetAsync(p->o_index.p, 0xFF, nfa * 4, s));
-  PCD_HIP_TRY(hipMemsetAsync(p->o_dist.p, 0, nfa * 4, s));
-  PCD_HIP_TRY(hipMemsetAsync(p->o_l6.p, 0, 6 * nfa * 8, s));
-  PCD_HIP_TRY(hipMemsetAsync(p->o_cam.p, 0, 3 * nfa * 8, s));
-
-  // chunk the batch so that the (image, submap) pair list and the winner buffers stay bounded
-  const uint64_t kMaxItems = 32ull << 20, kMaxZ = 1ull << 30;   // 256 MB of pairs, 8 GB of winner slots
-  const uint64_t per_chunk = std::max<uint64_t>(1, kMaxItems / std::max<uint32_t>(p->n_sub, 1));
-  std::vector<ProjImageDev> h;
-  p->last_items = 0;
-  uint64_t i0 = 0;
-  while (i0 < n_images) {
-    h.clear();
-    uint64_t zoff = 0, boff = 0, maxf = 0;
-    uint64_t i1 = i0;
-    while (i1 < n_images && (i1 - i0) < per_chunk) {
-      ProjImageDev d;
-      prepare_image(p->opt, images[i1], &d);
-      const uint64_t px = d.w > 0 && d.h > 0 ? (uint64_t)d.w * d.h : 0;
-      if (i1 > i0 && zoff + px > kMaxZ) break;
-      d.zoff = zoff;
-      d.boff = boff;
-      zoff += px;
-      boff += d.h > 0 ? (uint64_t)d.row_words * d.h : 0;
-      maxf = std::max(maxf, d.feat_end - d.feat_begin);
-      h.push_back(d);
-      ++i1;
-    }
-    const uint32_t ni = (uint32_t)h.size();
-    PCD_TRY(p->d_imgs.reserve(ni));
-    PCD_TRY(p->zbuf.reserve(std::max<uint64_t>(zoff, 1)));
-    PCD_TRY(p->bitmap.reserve(std::max<uint64_t>(boff, 1)));
-    PCD_TRY(p->items.reserve(std::max<uint64_t>((uint64_t)ni * p->n_sub, 1)));
-    PCD_HIP_TRY(hipMemcpyAsync(p->d_imgs.p, h.data(), ni * sizeof(ProjImageDev), hipMemcpyHostToDevice, s));
-    PCD_HIP_TRY(hipMemsetAsync(p->bitmap.p, 0, std::max<uint64_t>(boff, 1) * 4, s));
-    PCD_HIP_TRY(hipMemsetAsync(p->n_items.p, 0, sizeof(unsigned), s));
-    const unsigned fblocks = std::max(1u, std::min(div_up(maxf, 256), 1024u));
-    if (maxf) {
-      ScopedKernelTimer t("proj_feat_init", s);
-      hipLaunchKernelGGL(k_proj_feat_init, dim3(fblocks, ni), dim3(256), 0, s, p->d_imgs.p, ni, p->d_feat.p,
-                         pc.scale, p->bitmap.p, p->zbuf.p);
-    }
-    if (maxf && p->n_sub) {
-      {
-        ScopedKernelTimer t("proj_cull", s);
-        hipLaunchKernelGGL(k_proj_cull, dim3(div_up(p->n_sub, 256), ni), dim3(256), 0, s, p->d_imgs.p, p->sub_key.p,
-                           p->n_sub, p->opt.submap_length, p->opt.submap_height, p->opt.submap_width, p->items.p,
-                           p->n_items.p);
-      }
-      {
-        ScopedKernelTimer t("proj_splat", s);
-        hipLaunchKernelGGL(k_proj_splat, dim3(256 * 8), dim3(256), 0, s, p->d_imgs.p, p->items.p, p->n_items.p,
-                           p->sub_start.p, p->sorted.p, pc, p->bitmap.p, p->zbuf.p);
-      }
-    }
-    if (maxf) {
-      ScopedKernelTimer t("proj_readout", s);
-      hipLaunchKernelGGL(k_proj_readout, dim3(fblocks, ni), dim3(256), 0, s, p->d_imgs.p, p->d_feat.p, pc.scale,
-                         p->zbuf.p, p->sorted.p, p->cloud->pn8.p, p->o_found.p, p->o_index.p,
-                         p->o_dist.p, p->o_l6.p, p->o_cam.p);
-    }
-    PCD_HIP_TRY(hipGetLastError());
-    unsigned cnt = 0;
-    PCD_HIP_TRY(hipMemcpyAsync(&cnt, p->n_items.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    PCD_HIP_TRY(hipStreamSynchronize(s));   // h (pinned by the async upload) is reused by the next chunk
-    p->last_items += cnt;
-    i0 = i1;
-  }
+  const ProjOutputs out{p->o_found.p, p->o_index.p, p->o_dist.p, p->o_l6.p, p->o_cam.p};
+  PCD_TRY(proj_launch(p, recs, nullptr, n_feat, p->d_feat.p, nullptr, out, s));
   auto back = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
     return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
   };
@@ -665,6 +795,28 @@ pcd_status pcd_proj_set_new_images(pcd_proj* p, uint64_t n_images, const pcd_pro
   PCD_HIP_TRY(back(lidar6, p->o_l6.p, 6 * n_feat * 8));
   PCD_HIP_TRY(back(cam_xyz, p->o_cam.p, 3 * n_feat * 8));
   PCD_HIP_TRY(hipStreamSynchronize(s));
+  (void)proj_collect_pairs(p);
+  return PCD_OK;
+  });
+}
+
+pcd_status pcd_proj_set_new_images_device(pcd_proj* p, uint64_t n_images, const pcd_proj_image* images, uint64_t n_feat,
+                                          const double* d_feat_xy, uint8_t* d_found, uint32_t* d_lidar_index,
+                                          float* d_dist, double* d_lidar6, double* d_cam_xyz, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+  PCD_TRY(check_images(p, n_images, images, n_feat, d_feat_xy));
+  PCD_TRY(require_device(p->cloud->device));
+  PCD_TRY(refuse_capture((hipStream_t)stream, "pcd_proj_set_new_images_device"));
+  if (n_images == 0) return PCD_OK;
+  PCD_HIP_TRY(hipSetDevice(p->cloud->device));
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<ProjImageDev> recs;
+  PCD_TRY(host_records(p, n_images, images, recs));
+  const ProjOutputs out{d_found, d_lidar_index, d_dist, d_lidar6, d_cam_xyz};
+  const pcd_status st = proj_launch(p, recs, nullptr, n_feat, d_feat_xy, nullptr, out, s);
+  PCD_HIP_TRY(hipStreamSynchronize(s));   // the pair counts of pcd_proj_last_pairs; the pinned records are free again
+  PCD_TRY(st);
+  (void)proj_collect_pairs(p);
   return PCD_OK;
   });
 }

@@ -188,6 +188,20 @@ class BAAssocInfo(C.Structure):
                 ("num_icp_ground", C.c_uint64), ("assoc_ms", C.c_double), ("rebuild_ms", C.c_double)]
 
 
+class BAProjOpts(C.Structure):
+    """pcd_ba_proj_opts (pcdhip.h)."""
+    _fields_ = [("cam_width", C.c_void_p), ("cam_height", C.c_void_p), ("d_image_select", C.c_void_p),
+                ("d_point_mode", C.c_void_p), ("gate_mode", C.c_int32), ("d_max_range", C.c_void_p),
+                ("max_range_count", C.c_uint64), ("proj_weight", C.c_double), ("icp_weight", C.c_double),
+                ("icp_ground_weight", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class BAProjInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("num_images", "num_features", "num_found", "num_terms", "num_proj", "num_icp",
+                                           "num_icp_ground", "pairs")] + \
+               [(n, C.c_double) for n in ("proj_ms", "assoc_ms", "rebuild_ms")]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -252,6 +266,7 @@ ABI_SYMBOLS = [
     "pcd_voxel_options_default", "pcd_cloud_voxel_downsample", "pcd_cloud_voxel_downsample_device",
     "pcd_ba_set_lidar_device", "pcd_ba_get_lidar", "pcd_ba_lidar_device", "pcd_ba_assoc_opts_default",
     "pcd_ba_associate_lidar_device",
+    "pcd_proj_set_new_images_device", "pcd_ba_proj_opts_default", "pcd_ba_project_lidar_device",
 ]
 
 
@@ -364,6 +379,10 @@ def lib():
         L.pcd_ba_lidar_device.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)] + [C.POINTER(C.c_void_p)] * 5
         L.pcd_ba_assoc_opts_default.argtypes = [C.POINTER(BAAssocOpts)]
         L.pcd_ba_assoc_opts_default.restype = None
+        L.pcd_ba_proj_opts_default.argtypes = [C.POINTER(BAProjOpts)]
+        L.pcd_ba_proj_opts_default.restype = None
+        L.pcd_ba_project_lidar_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BAProjOpts), C.c_void_p,
+                                                  C.POINTER(BAProjInfo)]
         L.pcd_ba_associate_lidar_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BAAssocOpts), C.c_void_p,
                                                     C.POINTER(BAAssocInfo)]
     _LIB = L
@@ -860,6 +879,8 @@ class Projector:
         L.pcd_proj_scale_coeffs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.pcd_proj_set_new_images.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ProjImage), C.c_uint64] + \
             [C.c_void_p] * 6
+        L.pcd_proj_set_new_images_device.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(ProjImage), C.c_uint64] + \
+            [C.c_void_p] * 7
         if options is None:
             options = ProjOptions()
             L.pcd_proj_default_options(C.byref(options))
@@ -897,16 +918,40 @@ class Projector:
         _check(lib().pcd_proj_scale_coeffs(self._h, 0 if set_to is None else 1, _vp(c4), C.byref(latched)))
         return c4, bool(latched.value)
 
-    def set_new_images(self, images, feat_xy):
-        """images: list of dict(qvec, tvec, params[8], width, height, feat_begin, feat_end).
-        Returns found, lidar_index, dist, lidar6, cam_xyz."""
-        feat_xy = np.ascontiguousarray(feat_xy, np.float64).reshape(-1, 2)
-        nf = feat_xy.shape[0]
+    @staticmethod
+    def _images(images):
         arr = (ProjImage * max(len(images), 1))()
         for k, im in enumerate(images):
             arr[k] = ProjImage((C.c_double * 4)(*im["qvec"]), (C.c_double * 3)(*im["tvec"]),
                                (C.c_double * 8)(*im["params"]), im["width"], im["height"], im["feat_begin"],
                                im["feat_end"])
+        return arr
+
+    def set_new_images_device(self, images, d_feat_xy, want=("found", "lidar_index", "dist", "lidar6", "cam_xyz"),
+                              stream=None):
+        """pcd_proj_set_new_images_device: d_feat_xy is a torch device tensor [n_feat][2] float64 on the cloud's device;
+        the outputs named in `want` are allocated there and returned as a dict of torch tensors (the others are not
+        computed).  All work is on `stream` (a raw handle; None: torch's current stream), which is synchronised once."""
+        import torch
+        d_feat_xy = d_feat_xy.contiguous()
+        assert d_feat_xy.dtype == torch.float64 and d_feat_xy.is_cuda
+        nf = int(d_feat_xy.numel()) // 2
+        if stream is None:
+            stream = torch.cuda.current_stream(d_feat_xy.device).cuda_stream
+        shapes = dict(found=((nf,), torch.uint8), lidar_index=((nf,), torch.int32), dist=((nf,), torch.float32),
+                      lidar6=((nf, 6), torch.float64), cam_xyz=((nf, 3), torch.float64))
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=d_feat_xy.device) for k in want}
+        ptr = [_ptr(out.get(k)) for k in ("found", "lidar_index", "dist", "lidar6", "cam_xyz")]
+        _check(lib().pcd_proj_set_new_images_device(self._h, len(images), self._images(images), nf, _ptr(d_feat_xy), *ptr,
+                                                    C.c_void_p(stream)))
+        return out
+
+    def set_new_images(self, images, feat_xy):
+        """images: list of dict(qvec, tvec, params[8], width, height, feat_begin, feat_end).
+        Returns found, lidar_index, dist, lidar6, cam_xyz."""
+        feat_xy = np.ascontiguousarray(feat_xy, np.float64).reshape(-1, 2)
+        nf = feat_xy.shape[0]
+        arr = self._images(images)
         found = np.zeros(nf, np.uint8)
         index = np.zeros(nf, np.uint32)
         dist = np.zeros(nf, np.float32)
@@ -1421,6 +1466,49 @@ class BA:
         self._terms_changed(info.num_terms)
         return {k: getattr(info, k) for k, _ in BAAssocInfo._fields_}
 
+    def project_lidar(self, projector, cam_size, image_select=None, point_mode=None, max_range=None,
+                      gate_mode=GATE_MAPPER_LOCAL, proj_weight=1.0, icp_weight=100.0, icp_ground_weight=1000.0):
+        """pcd_ba_project_lidar_device: project the handle's images at their CURRENT poses with `projector`, pick per
+        point among the candidates of its track (MatchVariablePoint2LidarPoint), associate the points of mode 2 against
+        the projector's cloud, and install the terms (one per point at most, ascending point).  cam_size: one
+        (width, height) or one per camera; image_select: [I] mask (None: all); point_mode: [P] of 0 no term / 1 Proj / 2
+        nearest neighbour (None: every point Proj, no association); max_range / gate_mode: for mode-2 points, as
+        associate_lidar.  Returns the info dict (num_images, num_features, num_found, num_terms, num_proj, num_icp,
+        num_icp_ground, pairs, proj_ms, assoc_ms, rebuild_ms)."""
+        _, _, stream = self._torch()
+        o = BAProjOpts()
+        lib().pcd_ba_proj_opts_default(C.byref(o))
+        wh = None
+        if cam_size is not None:
+            wh = np.ascontiguousarray(cam_size, np.uint64).reshape(-1, 2)
+            if wh.shape[0] == 1 and self.C > 1:
+                wh = np.repeat(wh, self.C, axis=0)
+            if wh.shape[0] != self.C:
+                raise ValueError("project_lidar: cam_size must be one (width, height) or one per camera")
+            w, h = np.ascontiguousarray(wh[:, 0]), np.ascontiguousarray(wh[:, 1])
+            o.cam_width, o.cam_height = w.ctypes.data, h.ctypes.data
+        o.gate_mode = int(gate_mode)
+        sel = self._stage(image_select, np.uint8)
+        if sel is not None:
+            if int(sel.numel()) != self.I:
+                raise ValueError("project_lidar: image_select must have one entry per image")
+            o.d_image_select = sel.data_ptr()
+        pm = self._stage(point_mode, np.uint8)
+        mr = None
+        if pm is not None:
+            if int(pm.numel()) != self.P:
+                raise ValueError("project_lidar: point_mode must have one entry per point")
+            o.d_point_mode = pm.data_ptr()
+            if (int(gate_mode) & 0xFF) != GATE_CONTROLLER and max_range is not None:
+                mr = self._stage(np.atleast_1d(np.asarray(max_range, np.float64)) if not hasattr(max_range, "data_ptr")
+                                 else max_range, np.float64)
+                o.d_max_range, o.max_range_count = mr.data_ptr(), int(mr.numel())
+        o.proj_weight, o.icp_weight, o.icp_ground_weight = float(proj_weight), float(icp_weight), float(icp_ground_weight)
+        info = BAProjInfo()
+        _check(lib().pcd_ba_project_lidar_device(self._h, projector._h, C.byref(o), C.c_void_p(stream), C.byref(info)))
+        self._terms_changed(info.num_terms)
+        return {k: getattr(info, k) for k, _ in BAProjInfo._fields_}
+
 
 def pcg_opts(max_iterations=None, min_iterations=None, preconditioner=None, q_tolerance=None, r_tolerance=None):
     """pcd_ba_pcg_opts at the library's defaults (100, 0, schur_jacobi, 0.1, -1) with the given fields replaced"""
@@ -1482,16 +1570,24 @@ def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max
 
 
 def register_refine(ba, cloud, rounds, kd_max=1.5, kd_min=0.2, drop=0.1, gate_mode=GATE_MAPPER_GLOBAL, select=None,
-                    **solve_opts):
+                    projector=None, cam_size=None, point_mode=None, image_select=None, proj_weight=1.0, **solve_opts):
     """The loop of IncrementalMapper::AdjustGlobalBundleByLidar (sfm/incremental_mapper.cc:1413-1478) on one handle,
     GlobalOptNum advancing once per round: in round r every selected point searches within search_range_schedule(r)
     (kd_max, kd_min, drop), BA.associate_lidar installs the accepted associations, ba_solve(**solve_opts) refines.
     Nothing goes through the host and nothing that depends on the observations alone is rebuilt; no device work of its
-    own.  Returns one (association info, solve summary, iterations) per round."""
+    own.  Returns one (association info, solve summary, iterations) per round.
+    With a `projector` (over `cloud`; cam_size as BA.project_lidar) a round is the mapper's LOCAL one: "project +
+    associate + solve" through BA.project_lidar -- the points of point_mode 1 take a depth-projection term from the images
+    of image_select, those of mode 2 the nearest-neighbour association within the round's range (point_mode None: every
+    point Proj); `select` is not used then (mode 0 is "not a query")."""
     out = []
     for r in range(int(rounds)):
         rng = float(search_range_schedule(np.array([r], np.int32), kd_max, kd_min, drop)[0])
-        info = ba.associate_lidar(cloud, max_range=rng, gate_mode=gate_mode, select=select)
+        if projector is not None:
+            info = ba.project_lidar(projector, cam_size, image_select=image_select, point_mode=point_mode, max_range=rng,
+                                    gate_mode=gate_mode, proj_weight=proj_weight)
+        else:
+            info = ba.associate_lidar(cloud, max_range=rng, gate_mode=gate_mode, select=select)
         info["max_range"] = rng
         summary, its = ba_solve(ba, **solve_opts)
         out.append((info, summary, its))

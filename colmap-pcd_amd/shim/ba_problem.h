@@ -259,8 +259,9 @@ class BundleAdjusterHip {
   // rebuilt.  gate_mode: pcd_gate_mode, PCD_GATE_BOUNDED_SEARCH may be OR-ed in.  max_search_range: the schedule, one
   // entry or one per point in the order of point_ids_ (sfm/incremental_mapper.cc:1423-1427; ignored for
   // PCD_GATE_CONTROLLER).  select: the ids that are queries (the mapper's variable_point3D_ids; NULL: every point of
-  // the problem, the controller's loop).  Weights: the options' icp / icp_ground weights; a Proj term does not survive
-  // a re-association, so proj_lidar_constraint_weight has nothing left to weigh.
+  // the problem, the controller's loop).  Weights: the options' icp / icp_ground weights.  This call installs
+  // nearest-neighbour terms only: Proj terms the problem had are replaced with the rest.  ProjectLidar (below) is the
+  // call that produces Proj terms on the live handle, weighted by proj_lidar_constraint_weight.
   // Then config_.lidar_maps_ and the flat term arrays are refreshed from pcd_ba_get_lidar, so NumResiduals() and a
   // later Solve -- which keeps this handle instead of creating a new one -- agree with the handle.
   // false without a live handle, or when a call fails (pcd_last_error()); the problem is then as it was.
@@ -317,6 +318,90 @@ class BundleAdjusterHip {
     reassociated_ = true;
     return true;
   }
+  // ---- the LOCAL round (HIP): sfm/incremental_mapper.cc:1109-1165 on the live handle ----------------------------------
+  // Short tracks take the depth-projection route (Project2Image -> PcdProj::SetNewImage on searched_image_ids, then
+  // BundleAdjustmentConfig::MatchVariablePoint2LidarPoint), long tracks MatchClosestLidarPoint; both feed one term list.
+  // proj: anything with handle() returning its pcd_proj* (lidar::PcdProj), built over the cloud the nearest-neighbour
+  // points are associated against.  searched_image_ids: the images that are projected (lidar_searched_image_ids_; ids
+  // outside the problem are ignored).  proj_point_ids / nn_point_ids: the points of either route; a point in neither
+  // gets no term, a point in both takes the projection route.  max_search_range: one entry or one per point in the
+  // order of point_ids_, for the nn points (PCD_GATE_MAPPER_LOCAL); may be empty when nn_point_ids is.
+  // Everything runs in pcd_ba_project_lidar_device at the handle's CURRENT poses and points.  Then config_.lidar_maps_
+  // and the flat term arrays are refreshed from pcd_ba_get_lidar as ReassociateLidar does; Proj terms get type Proj, the
+  // colour red, and dist / angle recomputed from pcd_ba_get_parameters by lidar_hip.h's formulas.
+  // false without a live handle or projector, or when a call fails (pcd_last_error()); the problem is then as it was.
+  template <typename Projector>
+  bool ProjectLidar(Projector& proj, const std::unordered_set<image_t>& searched_image_ids,
+                    const std::unordered_set<point3D_t>& proj_point_ids, const std::unordered_set<point3D_t>& nn_point_ids,
+                    const std::vector<double>& max_search_range, pcd_ba_proj_info* info = nullptr) {
+    if (!ba_ || !proj.handle()) return false;
+    const size_t P = point_ids_.size(), I = image_ids_.size();
+    struct DevMem {   // freed on every return
+      void* p = nullptr;
+      ~DevMem() { if (p) (void)hipFree(p); }
+      bool put(const void* src, size_t bytes) {
+        return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess &&
+               (bytes == 0 || hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) == hipSuccess);
+      }
+    } d_range, d_images, d_mode;
+    pcd_ba_proj_opts o;
+    pcd_ba_proj_opts_default(&o);
+    o.cam_width = cam_width_.data();
+    o.cam_height = cam_height_.data();
+    o.gate_mode = PCD_GATE_MAPPER_LOCAL;
+    o.proj_weight = options_.proj_lidar_constraint_weight;
+    o.icp_weight = options_.icp_lidar_constraint_weight;
+    o.icp_ground_weight = options_.icp_ground_lidar_constraint_weight;
+    std::vector<uint8_t> images(I, 0), mode(P, PCD_BA_POINT_NONE);
+    for (size_t i = 0; i < I; ++i) images[i] = searched_image_ids.count(image_ids_[i]) ? 1 : 0;
+    if (!d_images.put(images.data(), I)) return false;
+    o.d_image_select = static_cast<const uint8_t*>(d_images.p);
+    for (size_t p = 0; p < P; ++p)
+      mode[p] = proj_point_ids.count(point_ids_[p]) ? PCD_BA_POINT_PROJ : nn_point_ids.count(point_ids_[p]) ? PCD_BA_POINT_NN
+                                                                                                           : PCD_BA_POINT_NONE;
+    if (!d_mode.put(mode.data(), P)) return false;
+    o.d_point_mode = static_cast<const uint8_t*>(d_mode.p);
+    std::vector<double> range = max_search_range;
+    if (range.empty() && nn_point_ids.empty()) range.push_back(0.0);   // nobody reads it: no point has mode 2
+    if (range.size() != 1 && range.size() != P) return false;
+    if (!d_range.put(range.data(), range.size() * sizeof(double))) return false;
+    o.d_max_range = static_cast<const double*>(d_range.p);
+    o.max_range_count = range.size();
+    pcd_ba_proj_info local{};
+    if (pcd_ba_project_lidar_device(ba_, proj.handle(), &o, nullptr, &local) != PCD_OK) return false;
+    if (info) *info = local;
+    uint64_t L = 0;
+    if (pcd_ba_get_lidar(ba_, &L, nullptr, nullptr, nullptr, nullptr, nullptr) != PCD_OK) return false;
+    std::vector<int32_t> point(L);
+    std::vector<double> abcd(4 * L), w(L), xyz(3 * L), X(3 * P);
+    std::vector<uint8_t> type(L);
+    if (pcd_ba_get_lidar(ba_, &L, point.data(), abcd.data(), w.data(), type.data(), xyz.data()) != PCD_OK) return false;
+    if (pcd_ba_get_parameters(ba_, nullptr, X.data()) != PCD_OK) return false;
+    lidar_point_ = point; lidar_abcd_ = abcd; lidar_w_ = w;
+    config_.lidar_maps_.clear();
+    for (uint64_t l = 0; l < L; ++l) {
+      LidarPoint lp;
+      lp.type = type[l] == PCD_LIDAR_PROJ ? LidarPointType::Proj
+                : type[l] == PCD_LIDAR_ICP_GROUND ? LidarPointType::IcpGround : LidarPointType::Icp;
+      for (int k = 0; k < 3; ++k) lp.xyz[k] = xyz[3 * l + k];
+      for (int k = 0; k < 4; ++k) lp.abcd[k] = abcd[4 * l + k];
+      if (lp.type == LidarPointType::Proj) {   // lidar_hip.h MatchVariablePoint2LidarPoint: point-to-plane, |cos|, red
+        const double* x = &X[3 * (size_t)point[l]];
+        const double a = lp.abcd[0], b = lp.abcd[1], c = lp.abcd[2], d = lp.abcd[3];
+        lp.dist = std::fabs((x[0] * a + x[1] * b + x[2] * c) + d);
+        const double v[3] = {x[0] - lp.xyz[0], x[1] - lp.xyz[1], x[2] - lp.xyz[2]};
+        lp.angle = std::fabs((a * v[0] + b * v[1] + c * v[2]) / std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+        lp.color = {255, 0, 0};
+      } else if (lp.type == LidarPointType::IcpGround) {
+        lp.color = {255, 255, 0};
+      } else {
+        lp.color = {0, 255, 0};   // the colour of the local call site (ToLidarPoint, PCD_GATE_MAPPER_LOCAL)
+      }
+      config_.lidar_maps_[point_ids_[point[l]]] = lp;
+    }
+    reassociated_ = true;
+    return true;
+  }
   const BundleAdjustmentConfig& config() const { return config_; }
   // what Solve hands to pcd_ba_solve: AUTO goes by the number of images in the config, as the reference does
   bool UsesDirectSolver() const {
@@ -332,6 +417,7 @@ class BundleAdjusterHip {
   std::vector<uint8_t> image_const_pose_, image_const_tvec_, point_const_, image_used_;
   std::vector<uint8_t> cam_refine_;      // per entry of cam_params_: 1 = optimised (pcd_ba_desc.camera_refine)
   std::vector<camera_t> camera_ids_;     // flat index -> id
+  std::vector<uint64_t> cam_width_, cam_height_;   // Camera::Width / Height by flat index (ProjectLidar)
   std::vector<image_t> image_ids_;       // flat index -> id
   std::vector<point3D_t> point_ids_;
 
@@ -351,7 +437,7 @@ class BundleAdjusterHip {
     lidar_point_.clear(); cam_params_.clear(); poses_.clear(); points_.clear(); obs_xy_.clear();
     lidar_abcd_.clear(); lidar_w_.clear(); image_const_pose_.clear(); image_const_tvec_.clear();
     point_const_.clear(); image_used_.clear(); image_ids_.clear(); point_ids_.clear();
-    cam_refine_.clear(); camera_ids_.clear();
+    cam_refine_.clear(); camera_ids_.clear(); cam_width_.clear(); cam_height_.clear();
     cam_index_.clear(); image_index_.clear(); point_index_.clear(); point3D_num_observations_.clear();
     reassociated_ = false;
   }
@@ -362,6 +448,7 @@ class BundleAdjusterHip {
     const int idx = (int)cam_model_.size();
     cam_index_[id] = idx;
     camera_ids_.push_back(id);
+    cam_width_.push_back(c.width); cam_height_.push_back(c.height);
     cam_model_.push_back(c.model_id);
     cam_off_.push_back((int32_t)cam_params_.size());
     cam_params_.insert(cam_params_.end(), c.params.begin(), c.params.end());

@@ -440,6 +440,16 @@ pcd_status pcd_proj_scale_coeffs(pcd_proj* p, int set, double* coeffs4, int* lat
 pcd_status pcd_proj_set_new_images(pcd_proj* p, uint64_t n_images, const pcd_proj_image* images, uint64_t n_feat,
                                    const double* feat_xy, uint8_t* found, uint32_t* lidar_index, float* dist,
                                    double* lidar6, double* cam_xyz);
+/* The same call with the features and every output in device memory (each output may be NULL) and all work on
+ * `stream`: the same winner rule, coefficient latch, chunking and pcd_proj_last_pairs.  `images` stays a host array
+ * (the poses size nothing, but the image sizes lay the buffers out).  Guards as every _device call: NULL / a bad
+ * feature range / a zero focal length -> INVALID; no gfx950 -> NO_DEVICE; a capturing stream -> UNSUPPORTED before
+ * anything is allocated.  Synchronises `stream` once, at the end (the pair counts of pcd_proj_last_pairs).  The host
+ * form is a wrapper over the same launcher. */
+pcd_status pcd_proj_set_new_images_device(pcd_proj* p, uint64_t n_images, const pcd_proj_image* images /*host*/,
+                                          uint64_t n_feat, const double* d_feat_xy, uint8_t* d_found,
+                                          uint32_t* d_lidar_index, float* d_dist, double* d_lidar6, double* d_cam_xyz,
+                                          void* stream);
 
 /* search-radius schedule, sfm/incremental_mapper.cc:1159-1163, 1423-1427 */
 pcd_status pcd_search_range_schedule(const int32_t* global_opt_num, uint64_t n, double kd_max,
@@ -905,6 +915,66 @@ typedef struct {
 void pcd_ba_assoc_opts_default(pcd_ba_assoc_opts* opts);   /* MAPPER_GLOBAL, NULL, 0, NULL, 100, 1000 (shim/ba_problem.h:71-72) */
 pcd_status pcd_ba_associate_lidar_device(pcd_ba* ba, pcd_cloud* cloud, const pcd_ba_assoc_opts* opts,
                                          void* stream, pcd_ba_assoc_info* info /* host, may be NULL */);
+
+/* ------------------------------------------------------------------------
+ * Depth-projection (Proj) terms installed on a live handle        
+ *   the short-track route of the local bundle adjustment, sfm/incremental_mapper.cc:1109-1165: Project2Image
+ *   (PcdProj::SetNewImage on the images of the track), then optim/bundle_adjustment.cc:288-350
+ *   BundleAdjustmentConfig::MatchVariablePoint2LidarPoint; long tracks take MatchClosestLidarPoint, and both feed one
+ *   term list.  One call: project the handle's images at their CURRENT poses, pick per track, associate the
+ *   nearest-neighbour points, install.
+ * Images.  Image i is projected iff d_image_select is NULL or d_image_select[i] != 0.  Its pose is the handle's current
+ *   poses[i], read on the device.  Its parameters are prm[k] = k < K ? cam_params[off + k] : 0 for k < 8 (K the
+ *   parameter count of its camera's model): the reference reads an OPENCV camera unconditionally.  Width and height are
+ *   cam_width / cam_height of its camera.  Its features are its observations in ascending observation index.  The
+ *   focal-length check of pcd_proj_set_new_images (params[0] != 0 && params[1] != 0) runs over all cameras of the handle,
+ *   on a host mirror of the camera parameters that pcd_ba_create and pcd_ba_set_camera_parameters keep.  A projector
+ *   that has not latched its splat coefficients yet latches on the camera of image 0.
+ * Candidates of a point of mode PCD_BA_POINT_PROJ: its observations in ascending observation index; an observation is
+ *   a candidate when its image is selected and its feature found a winner; of several such observations of the point
+ *   in one image only the one with the lowest index counts (std::map::insert, pcd_projection.cc:79).
+ * Pick.  With X the point and c = (x y z nx ny nz) the candidate's winner, in double, left to right, without FMA:
+ *   v = X - c.xyz; dot = v0 nx + v1 ny + v2 nz; nn = sqrt(nx nx + ny ny + nz nz); vn = sqrt(v0 v0 + v1 v1 + v2 v2);
+ *   the candidate with the smallest fabs(dot / (nn * vn)) wins; the comparison is strict < starting from 360, so ties go
+ *   to the lowest observation index and a NaN (zero normal, X on the LiDAR point) never wins.
+ * Row of the point: with a winner, type PCD_LIDAR_PROJ, lidar_xyz = c.xyz, abcd = (n / sqrt(nx nx + ny ny + nz nz),
+ *   0 - a x - b y - c z) (lidar_point.cc:39-50); without one, type 0.  A NaN in abcd drops the row by the rule of
+ *   pcd_ba_set_lidar_device.
+ * Points of mode PCD_BA_POINT_NN: their row is exactly that of pcd_associate_device on ALL the handle's points against
+ *   the projector's cloud (a full-P association, then masked, as pcd_ba_associate_lidar_device defines it), with
+ *   gate_mode / d_max_range.  The association does not run at all when d_point_mode is NULL.  Mode 0: no term.
+ * Install: the machinery of pcd_ba_set_lidar_device with row = point and weight = {-, icp_weight, icp_ground_weight,
+ *   proj_weight}: at most one term per point, in ascending point order; afterwards the handle is bit-identical to one
+ *   pcd_ba_create built with this term list.  The same invalidations and the same single synchronisation of `stream`
+ *   (with info the call also waits for its last kernel).  A repeated call is bitwise identical.
+ * Refused with the handle exactly as it was: NULL opts / cam_width / cam_height / handle / projector, a mode above 2 in
+ *   any row, a zero focal length, handle and projector on different devices -> INVALID; a capturing stream ->
+ *   UNSUPPORTED before anything is allocated; otherwise the refusals of pcd_associate_device (when d_point_mode is
+ *   given) and pcd_ba_set_lidar_device.  num_points == 0: PCD_OK with zero counts; no observations: zero terms.
+ * Scratch belongs to the handle and the projector and only grows.
+ * --------------------------------------------------------------------- */
+#define PCD_BA_POINT_NONE 0
+#define PCD_BA_POINT_PROJ 1
+#define PCD_BA_POINT_NN   2
+typedef struct {
+  const uint64_t* cam_width;        /* host [num_cameras]  Camera::Width()  -- the handle does not know image sizes */
+  const uint64_t* cam_height;       /* host [num_cameras] */
+  const uint8_t* d_image_select;    /* device [I] or NULL (all): the images that are projected
+                                       (lidar_searched_image_ids_; Project2Image's pair-count test stays with the caller) */
+  const uint8_t* d_point_mode;      /* device [P] or NULL (= every point PROJ): 0 no term, 1 PCD_BA_POINT_PROJ, 2 PCD_BA_POINT_NN */
+  int32_t gate_mode;                /* for mode-2 points, as pcd_ba_assoc_opts */
+  const double* d_max_range; uint64_t max_range_count;
+  double proj_weight, icp_weight, icp_ground_weight;   /* defaults 1, 100, 1000 */
+  int32_t reserved[8];
+} pcd_ba_proj_opts;
+typedef struct {
+  uint64_t num_images, num_features, num_found;     /* selected images, their observations, those with a winner */
+  uint64_t num_terms, num_proj, num_icp, num_icp_ground, pairs;   /* pairs: pcd_proj_last_pairs of this call */
+  double proj_ms, assoc_ms, rebuild_ms;
+} pcd_ba_proj_info;
+void pcd_ba_proj_opts_default(pcd_ba_proj_opts* opts);   /* NULLs, MAPPER_LOCAL, 1, 100, 1000 */
+pcd_status pcd_ba_project_lidar_device(pcd_ba* ba, pcd_proj* proj, const pcd_ba_proj_opts* opts, void* stream,
+                                       pcd_ba_proj_info* info /* host, may be NULL */);
 
 /* ------------------------------------------------------------------------
  * Exact SIFT descriptor matching (stretch row a19)
