@@ -24,6 +24,7 @@
 //   k_ba_raw*, k_ba_cam_jac, k_ba_lidar_raw  thread = observation / LiDAR term: the raw ambient blocks exactly as
 //                CostFunction::Evaluate returns them, whole or as 64-byte records (the Ceres EvaluationCallback adapter).
 //   k_ba_obs_errors, k_ba_filter_tracks, k_ba_negative_depth  the post-BA filters.
+//   k_ba_proj_centers, k_ba_filter_tri_angle  the triangulation-angle filter on what k_ba_filter_tracks left.
 // Jacobians are recomputed in each kernel instead of being staged through HBM (160 B/obs of traffic would cost more than
 // the ~300 flops).  MODEL >= 0 compiles one camera model in (all cameras of the problem share it -- the usual case);
 // MODEL = -1 switches per observation.
@@ -1106,6 +1107,109 @@ __global__ __launch_bounds__(256) void k_ba_filter_summary(const double* __restr
   }
 }
 
+// ---- the triangulation-angle filter (base/reconstruction.cc:1600-1660), stage 2 of pcd_ba_filter_points --------
+// thread = image: ProjectionCenterFromPose (base/pose.cc:164-171), the normalised quaternion conjugated and applied to
+// -tvec; a zero quaternion counts as the identity, as in k_ba_obs_errors
+__global__ __launch_bounds__(256) void k_ba_proj_centers(int I, const double* __restrict__ poses,
+                                                         double* __restrict__ centers) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= I) return;
+  const double* pose = poses + 7 * (size_t)i;
+  double q[4] = {pose[0], pose[1], pose[2], pose[3]};
+  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  if (n == 0.0) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; }
+  else { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; }
+  const double qc[4] = {q[0], -q[1], -q[2], -q[3]};
+  const double mt[3] = {-pose[4], -pose[5], -pose[6]}, zero[3] = {0.0, 0.0, 0.0};
+  double c[3];
+  pose_transform(qc, zero, mt, c);
+  centers[3 * (size_t)i] = c[0]; centers[3 * (size_t)i + 1] = c[1]; centers[3 * (size_t)i + 2] = c[2];
+}
+
+// CalculateTriangulationAngle (base/triangulation.cc:122-145): a NaN (the acos argument outside [-1, 1] by rounding)
+// passes through fabs and the min (std::min(a, b) = b < a ? b : a) and then fails every >=
+__device__ __forceinline__ double tri_angle(const double c1[3], const double c2[3], const double X[3]) {
+  const double b0 = c1[0] - c2[0], b1 = c1[1] - c2[1], b2 = c1[2] - c2[2];
+  const double r0 = X[0] - c1[0], r1 = X[1] - c1[1], r2 = X[2] - c1[2];
+  const double s0 = X[0] - c2[0], s1 = X[1] - c2[1], s2 = X[2] - c2[2];
+  const double base2 = b0 * b0 + b1 * b1 + b2 * b2;
+  const double ray1 = r0 * r0 + r1 * r1 + r2 * r2, ray2 = s0 * s0 + s1 * s1 + s2 * s2;
+  const double den = 2.0 * sqrt(ray1 * ray2);
+  if (den == 0.0) return 0.0;
+  const double angle = fabs(acos((ray1 + ray2 - base2) / den));
+  const double other = 3.14159265358979323846 - angle;
+  return other < angle ? other : angle;
+}
+
+// thread = point, on what stage 1 (k_ba_filter_tracks) left in obs_erase / point_delete / point_error, all three
+// required here.  A point stage 1 kept is kept as soon as one pair (i1, i2 < i1) of its SURVIVING elements, in ascending
+// observation index, reaches min_angle; the centre of element i1 is loaded once, those of i2 come from the [I][3] table
+// (24 KB at 1000 images: cache hits).  A point that no pair keeps is deleted: point_delete = 1, every obs_erase = 1,
+// point_error = -1.  The three summary partials of the workgroup are written anew from the final state (elements stage 1
+// filtered, plus ONE per point deleted here; the error of every point still alive), by k_ba_filter_tracks' fixed-order
+// reduction, so k_ba_filter_summary serves both filters.
+// Cost of the pair loop: quadratic in the survivors, but only for a point that ends deleted -- a kept point leaves at its
+// first sufficient pair, for a triangulated point usually the first.  The longest track of workload M has 30 elements:
+// 435 pairs of ~60 fp64 operations, one sqrt, one division and one acos, ~0.2 M cycles (~0.1 ms) for the one thread if
+// every pair fails; its wavefront's other lanes have left by then.  Such a point needs 30 cameras within 1.5 degrees of
+// each other as seen from it; the kernel has no wavefront-per-track path for it.  Measured at workload M with the stage
+// on all 979 k tracks, 36 k of them deleted after all their pairs: 0.18 ms for the stage (profiles/ba_filter_probe.txt).
+__global__ __launch_bounds__(256) void k_ba_filter_tri_angle(int P, const uint32_t* __restrict__ pt_start,
+                                                             const uint32_t* __restrict__ pt_list,
+                                                             const int* __restrict__ obs_image,
+                                                             const double* __restrict__ centers,
+                                                             const double* __restrict__ points, double min_angle,
+                                                             uint8_t* __restrict__ obs_erase, uint8_t* __restrict__ point_delete,
+                                                             double* __restrict__ point_error, double* __restrict__ partial) {
+  __shared__ double s_f[4], s_e[4], s_n[4];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  double filtered = 0.0, esum = 0.0, valid = 0.0;
+  if (p < P) {
+    const uint32_t b = pt_start[p], len = pt_start[p + 1] - b;
+    if (point_delete[p]) {
+      filtered = (double)len;
+    } else {
+      const double X[3] = {points[3 * (size_t)p], points[3 * (size_t)p + 1], points[3 * (size_t)p + 2]};
+      uint32_t ndel = 0;
+      bool keep = false;
+      for (uint32_t j1 = 0; j1 < len; ++j1) {
+        const uint32_t o1 = pt_list[b + j1];
+        if (obs_erase[o1]) { ++ndel; continue; }
+        if (keep) continue;   // only the count of stage 1's erasures is still wanted
+        const double* cp1 = centers + 3 * (size_t)obs_image[o1];
+        const double c1[3] = {cp1[0], cp1[1], cp1[2]};
+        for (uint32_t j2 = 0; j2 < j1 && !keep; ++j2) {
+          const uint32_t o2 = pt_list[b + j2];
+          if (obs_erase[o2]) continue;
+          const double* cp2 = centers + 3 * (size_t)obs_image[o2];
+          const double c2[3] = {cp2[0], cp2[1], cp2[2]};
+          keep = tri_angle(c1, c2, X) >= min_angle;
+        }
+      }
+      if (keep) {
+        filtered = (double)ndel; esum = point_error[p]; valid = 1.0;
+      } else {
+        filtered = (double)ndel + 1.0;   // the reference counts points here, not elements
+        point_delete[p] = 1;
+        point_error[p] = -1.0;
+        for (uint32_t j = 0; j < len; ++j) obs_erase[pt_list[b + j]] = 1;
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    filtered += __shfl_xor(filtered, off); esum += __shfl_xor(esum, off); valid += __shfl_xor(valid, off);
+  }
+  if (lane == 0) { s_f[wave] = filtered; s_e[wave] = esum; s_n[wave] = valid; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[3 * (size_t)blockIdx.x] = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
+    partial[3 * (size_t)blockIdx.x + 1] = (s_e[0] + s_e[1]) + (s_e[2] + s_e[3]);
+    partial[3 * (size_t)blockIdx.x + 2] = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+  }
+}
+
 // rows of the variable-pose observations, packed: thread = 16-byte unit of an output row
 template <int N>   // doubles per row
 __global__ void k_pack_rows(const double* __restrict__ in, const uint32_t* __restrict__ vobs, uint64_t nrows,
@@ -1347,10 +1451,88 @@ pcd_status pcd_ba_filter_tracks(pcd_ba* b, double max_reproj_error, const pcd_ba
   return PCD_OK;
 }
 
+void pcd_ba_filter_opts_default(pcd_ba_filter_opts* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->max_reproj_error = 8.0;
+  o->min_tri_angle_deg = 1.5;
+}
+
+pcd_status pcd_ba_filter_points_device(pcd_ba* b, const pcd_ba_filter_opts* opts, const pcd_ba_filter_out* o, void* stream) {
+  PCD_REQUIRE(b && opts && o, "null pointer");
+  PCD_REFUSE_CAPTURE(stream);
+  if (!(opts->min_tri_angle_deg > 0.0)) return pcd_ba_filter_tracks_device(b, opts->max_reproj_error, o, stream);
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t O = b->O, P = (size_t)b->P;
+  // stage 2 reads and rewrites all three per-track outputs of stage 1: those the caller left NULL go to scratch
+  pcd_ba_filter_out d = *o;
+  d.summary = nullptr;
+  if (!d.obs_erase || !d.point_delete) {
+    PCD_TRY(b->f_tri_u8.reserve(O + P + 1));
+    if (!d.obs_erase) d.obs_erase = b->f_tri_u8.p;
+    if (!d.point_delete) d.point_delete = b->f_tri_u8.p + O;
+  }
+  if (!d.point_error) { PCD_TRY(b->f_tri_err.reserve(at_least_1(P))); d.point_error = b->f_tri_err.p; }
+  PCD_TRY(b->f_centers.reserve(3 * at_least_1((size_t)b->I)));
+  PCD_TRY(pcd_ba_filter_tracks_device(b, opts->max_reproj_error, &d, stream));
+  ScopedKernelTimer t("ba_filter_tri_angle", s);
+  const int nbp = (int)div_up((uint64_t)b->P, 256), nbo = (int)div_up(std::max<uint64_t>(O, 1), 256);
+  double* part3 = b->f_part.p, *part1 = b->f_part.p + 3 * (size_t)nbp;   // as stage 1 laid them out
+  const double min_angle = opts->min_tri_angle_deg * 0.0174532925199432954743716805978692718781530857086181640625;   // DegToRad
+  hipLaunchKernelGGL(k_ba_proj_centers, dim3(div_up((uint64_t)b->I, 256)), dim3(256), 0, s, b->I, b->poses.p, b->f_centers.p);
+  hipLaunchKernelGGL(k_ba_filter_tri_angle, dim3(nbp), dim3(256), 0, s, b->P, b->pt_obs_start.p, b->pt_obs_list.p,
+                     b->obs_image.p, b->f_centers.p, b->points.p, min_angle, d.obs_erase, d.point_delete, d.point_error, part3);
+  if (o->summary) hipLaunchKernelGGL(k_ba_filter_summary, dim3(1), dim3(256), 0, s, part3, nbp, part1, nbo, o->summary);
+  PCD_HIP_TRY(hipGetLastError());
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_filter_points(pcd_ba* b, const pcd_ba_filter_opts* opts, const pcd_ba_filter_out* o) {
+  PCD_REQUIRE(b && opts && o, "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  const size_t O = b->O, P = (size_t)b->P;
+  PCD_TRY(b->f_u8.reserve(2 * O + P + 1)); PCD_TRY(b->f_summary.reserve(P + 4));
+  pcd_ba_filter_out d{};
+  d.obs_erase = o->obs_erase ? b->f_u8.p : nullptr;
+  d.obs_negative_depth = o->obs_negative_depth ? b->f_u8.p + O : nullptr;
+  d.point_delete = o->point_delete ? b->f_u8.p + 2 * O : nullptr;
+  d.point_error = o->point_error ? b->f_summary.p + 4 : nullptr;
+  d.summary = o->summary ? b->f_summary.p : nullptr;
+  PCD_TRY(pcd_ba_filter_points_device(b, opts, &d, nullptr));
+  if (o->obs_erase && O) PCD_HIP_TRY(hipMemcpy(o->obs_erase, d.obs_erase, O, hipMemcpyDeviceToHost));
+  if (o->obs_negative_depth && O) PCD_HIP_TRY(hipMemcpy(o->obs_negative_depth, d.obs_negative_depth, O, hipMemcpyDeviceToHost));
+  if (o->point_delete) PCD_HIP_TRY(hipMemcpy(o->point_delete, d.point_delete, P, hipMemcpyDeviceToHost));
+  if (o->point_error) PCD_HIP_TRY(hipMemcpy(o->point_error, d.point_error, P * sizeof(double), hipMemcpyDeviceToHost));
+  if (o->summary) PCD_HIP_TRY(hipMemcpy(o->summary, d.summary, 4 * sizeof(double), hipMemcpyDeviceToHost));
+  PCD_HIP_TRY(hipDeviceSynchronize());
+  return PCD_OK;
+}
+
+// h_pose_row after pcd_ba_remove_observations_device: the walk of build_pose_rows (ba_build.hip) over the device's
+// obs_image, read back once.  The blocking copy below is on the null stream while the removal wrote obs_image on the
+// caller's: it reads finished data only because the removal synchronises that stream (after k_edit_compact_obs) before
+// it returns.  A removal without that synchronisation would have to order this copy behind its stream.
+static pcd_status ba_refresh_pose_rows(pcd_ba* b) {
+  if (!b->pose_row_stale) return PCD_OK;
+  const size_t O = b->O;
+  std::vector<int> img(O);
+  std::vector<uint8_t> cpose((size_t)b->I, 0);
+  if (O) PCD_HIP_TRY(hipMemcpy(img.data(), b->obs_image.p, O * sizeof(int), hipMemcpyDeviceToHost));
+  if (b->has_cpose) PCD_HIP_TRY(hipMemcpy(cpose.data(), b->image_const_pose.p, (size_t)b->I, hipMemcpyDeviceToHost));
+  b->h_pose_row.assign(O, 0xFFFFFFFFu);
+  uint32_t row = 0;
+  for (size_t o = 0; o < O; ++o)
+    if (!cpose[img[o]]) b->h_pose_row[o] = row++;
+  b->pose_row_stale = false;
+  return PCD_OK;
+}
+
 pcd_status pcd_ba_evaluate_blocks(pcd_ba* b, int want_jacobians, int want_jac_cam, pcd_ba_blocks* out) {
   PCD_REQUIRE(b && out, "null pointer");
   PCD_HIP_TRY(hipSetDevice(b->device));
   std::memset(out, 0, sizeof *out);
+  PCD_TRY(ba_refresh_pose_rows(b));
   const uint64_t O = b->O, L = b->L, V = b->n_pose_rows;
   const bool packed = V != O;
   const size_t n_res = 2 * O + L, n_jq = want_jacobians ? 8 * V : 0, n_jt = want_jacobians ? 6 * V : 0,

@@ -9,7 +9,7 @@ using namespace pcd;
 
 // sliced ELL: thread = (slice, lane): track p = order[slice*64 + lane], its j-th observation goes to slot
 // slice_start[slice] + 64 j + lane
-__global__ void k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __restrict__ slice_start,
+__global__ void pcd::k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __restrict__ slice_start,
                                const uint32_t* __restrict__ pt_start, const uint32_t* __restrict__ pt_list,
                                const int* __restrict__ obs_image, const double* __restrict__ obs_xy, int nslices,
                                int* __restrict__ sell_img, double* __restrict__ sell_xy) {
@@ -33,7 +33,7 @@ __global__ void k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __
   }
 }
 // image-major copies: e-th observation of the image-major order = observation img_obs[e] of the caller's order
-__global__ void k_ba_fill_image_major(const uint32_t* __restrict__ img_obs, const int* __restrict__ obs_point,
+__global__ void pcd::k_ba_fill_image_major(const uint32_t* __restrict__ img_obs, const int* __restrict__ obs_point,
                                       const double* __restrict__ obs_xy, uint64_t O, int* __restrict__ img_pt,
                                       double* __restrict__ img_xy) {
   const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;

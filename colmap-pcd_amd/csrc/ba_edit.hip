@@ -1,0 +1,360 @@
+// ba_edit.hip -- observations and points dropped from a live BA handle on the device:
+// pcd_ba_remove_observations_device.  What pcd_ba_create (ba_build.hip) derives on the host from the caller's
+// observation and term lists is derived here from the handle's own device arrays and two flag arrays, byte for byte.
+// Dropping rows keeps the order of the rest, so every list of the old handle, read through one scan of its keep flags,
+// is the list of the new one; only the order of the tracks by length is sorted anew.  The passes, all on `stream`:
+//   k_edit_obs_flag / k_edit_term_flag   row -> kept?  (n + 1 flags, the last 0: the scan's last value is the count)
+//   k_edit_list_flag                     the same flags in the order of a CSR's list (track, image, point -> terms)
+//   k_edit_vobs_flag                     kept and of a variable pose (only with constant poses)
+//   exclusive_sum                        flags -> new index; one per order
+//   k_edit_compact_obs / _terms / _list  kept rows and list entries to their new places, renumbered; obs_map
+//   k_edit_starts                        new CSR bounds: the scan value at the old bound
+//   k_edit_lengths, sort_pairs           track lengths; point ids stably by length = pcd_ba_create's counting sort
+//   k_edit_slice_width, exclusive_sum    64 x the longest track of every slice -> slice_start
+//   k_edit_seg_count, exclusive_sum, k_edit_segs   segments of <= kImgSeg observations per image
+//   k_ba_fill_sell, k_ba_fill_image_major, k_lidar_tracks   the fills pcd_ba_create and ba_lidar.hip use
+//   k_edit_record                        the counts the host reads (the ONE synchronisation), with img_obs_start
+// No atomics; nothing depends on the launch geometry.  The new layout is built in pcd_ba::edit_next, every buffer of it
+// reserved before the first launch, and swapped in at the end.
+#include "ba_handle.h"
+#include "prim.h"
+
+namespace pcd {
+
+constexpr uint32_t kDropped = 0xFFFFFFFFu;
+enum { kRecObs = 0, kRecTerms, kRecSegs, kRecPoseRows, kRecEmptied, kRecWords };
+
+// flag[o] = 1: observation o stays.  Thread O writes the closing 0.
+__global__ __launch_bounds__(256) void k_edit_obs_flag(uint32_t O, const uint8_t* __restrict__ erase,
+                                                       const uint8_t* __restrict__ pdel, const int* __restrict__ obs_point,
+                                                       uint32_t* __restrict__ flag) {
+  const uint32_t o = blockIdx.x * 256u + threadIdx.x;
+  if (o > O) return;
+  flag[o] = (o < O && !(erase && erase[o]) && !(pdel && pdel[obs_point[o]])) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_edit_term_flag(uint32_t L, const uint8_t* __restrict__ pdel,
+                                                        const int* __restrict__ lidar_point, uint32_t* __restrict__ flag) {
+  const uint32_t l = blockIdx.x * 256u + threadIdx.x;
+  if (l > L) return;
+  flag[l] = (l < L && !(pdel && pdel[lidar_point[l]])) ? 1u : 0u;
+}
+// out[k] = flag[list[k]], out[n] = 0
+__global__ __launch_bounds__(256) void k_edit_list_flag(uint32_t n, const uint32_t* __restrict__ list,
+                                                        const uint32_t* __restrict__ flag, uint32_t* __restrict__ out) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k > n) return;
+  out[k] = k < n ? flag[list[k]] : 0u;
+}
+__global__ __launch_bounds__(256) void k_edit_vobs_flag(uint32_t O, const uint32_t* __restrict__ flag,
+                                                        const int* __restrict__ obs_image, const uint8_t* __restrict__ cpose,
+                                                        uint32_t* __restrict__ out) {
+  const uint32_t o = blockIdx.x * 256u + threadIdx.x;
+  if (o > O) return;
+  out[o] = (o < O && flag[o] && !cpose[obs_image[o]]) ? 1u : 0u;
+}
+
+// kept observation o -> row pos[o]; obs_map (may be null) for every old observation; the packed pose rows (v_flag null:
+// no constant pose, no vobs)
+__global__ __launch_bounds__(256) void k_edit_compact_obs(uint32_t O, const uint32_t* __restrict__ flag,
+                                                          const uint32_t* __restrict__ pos, const int* __restrict__ obs_image,
+                                                          const int* __restrict__ obs_point, const double* __restrict__ obs_xy,
+                                                          const uint32_t* __restrict__ v_flag, const uint32_t* __restrict__ v_pos,
+                                                          int* __restrict__ n_image, int* __restrict__ n_point,
+                                                          double* __restrict__ n_xy, uint32_t* __restrict__ vobs,
+                                                          uint32_t* __restrict__ obs_map) {
+  const uint32_t o = blockIdx.x * 256u + threadIdx.x;
+  if (o >= O) return;
+  const bool keep = flag[o] != 0;
+  const uint32_t t = pos[o];
+  if (obs_map) obs_map[o] = keep ? t : kDropped;
+  if (!keep) return;
+  n_image[t] = obs_image[o];
+  n_point[t] = obs_point[o];
+  *reinterpret_cast<double2*>(n_xy + 2 * (size_t)t) = *reinterpret_cast<const double2*>(obs_xy + 2 * (size_t)o);
+  if (v_flag && v_flag[o]) vobs[v_pos[o]] = t;
+}
+// type / xyz (the meta of pcd_ba_set_lidar_device) only when the handle has them
+__global__ __launch_bounds__(256) void k_edit_compact_terms(uint32_t L, const uint32_t* __restrict__ flag,
+                                                            const uint32_t* __restrict__ pos, const int* __restrict__ point,
+                                                            const double* __restrict__ abcd, const double* __restrict__ w,
+                                                            const uint8_t* __restrict__ type, const double* __restrict__ xyz,
+                                                            int* __restrict__ n_point, double* __restrict__ n_abcd,
+                                                            double* __restrict__ n_w, uint8_t* __restrict__ n_type,
+                                                            double* __restrict__ n_xyz) {
+  const uint32_t l = blockIdx.x * 256u + threadIdx.x;
+  if (l >= L || !flag[l]) return;
+  const uint32_t t = pos[l];
+  n_point[t] = point[l];
+  for (int k = 0; k < 4; ++k) n_abcd[4 * (size_t)t + k] = abcd[4 * (size_t)l + k];
+  n_w[t] = w[l];
+  if (type) {
+    n_type[t] = type[l];
+    for (int k = 0; k < 3; ++k) n_xyz[3 * (size_t)t + k] = xyz[3 * (size_t)l + k];
+  }
+}
+// kept entry k of a CSR's list -> entry l_pos[k], holding the new index of its row
+__global__ __launch_bounds__(256) void k_edit_compact_list(uint32_t n, const uint32_t* __restrict__ list,
+                                                           const uint32_t* __restrict__ l_flag, const uint32_t* __restrict__ l_pos,
+                                                           const uint32_t* __restrict__ pos, uint32_t* __restrict__ out) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n || !l_flag[k]) return;
+  out[l_pos[k]] = pos[list[k]];
+}
+// start[key] for key = 0 .. nkeys: the kept entries in front of the old bound (l_pos has the list's n + 1 scan values)
+__global__ __launch_bounds__(256) void k_edit_starts(uint32_t nkeys, const uint32_t* __restrict__ old_start,
+                                                     const uint32_t* __restrict__ l_pos, uint32_t* __restrict__ start) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k > nkeys) return;
+  start[k] = l_pos[old_start[k]];
+}
+__global__ __launch_bounds__(256) void k_edit_lengths(uint32_t P, const uint32_t* __restrict__ start,
+                                                      uint32_t* __restrict__ len, uint32_t* __restrict__ iota) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= P) return;
+  len[p] = start[p + 1] - start[p];
+  iota[p] = p;
+}
+// threads behind the P tracks are padding (-1); width[s] = 64 x the length of the last real track of slice s (ascending
+// lengths: its longest), width[nslices] = 0 closes the scan
+__global__ __launch_bounds__(256) void k_edit_slice_width(uint32_t P, uint32_t nslices, const uint32_t* __restrict__ len_sorted,
+                                                          int* __restrict__ order, uint32_t* __restrict__ width) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= P && t < nslices * 64u) order[t] = -1;
+  if (t > nslices) return;
+  uint32_t w = 0;
+  if (t < nslices) {
+    const uint32_t last = min(t * 64u + 63u, P - 1u);
+    w = len_sorted[last] * 64u;
+  }
+  width[t] = w;
+}
+__global__ __launch_bounds__(256) void k_edit_seg_count(uint32_t I, const uint32_t* __restrict__ img_start,
+                                                        uint32_t* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i > I) return;
+  cnt[i] = i < I ? (img_start[i + 1] - img_start[i] + kImgSeg - 1u) / kImgSeg : 0u;
+}
+// thread = image: its segments; thread I closes seg_begin with the number of observations
+__global__ __launch_bounds__(256) void k_edit_segs(uint32_t I, const uint32_t* __restrict__ img_start,
+                                                   const uint32_t* __restrict__ img_seg_start, uint32_t* __restrict__ seg_img,
+                                                   uint32_t* __restrict__ seg_begin) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i > I) return;
+  if (i == I) { seg_begin[img_seg_start[I]] = img_start[I]; return; }
+  uint32_t j = img_seg_start[i];
+  for (uint32_t e = img_start[i]; e < img_start[i + 1]; e += kImgSeg, ++j) { seg_img[j] = i; seg_begin[j] = e; }
+}
+// one workgroup: the counts; emptied = points that had observations and have none now (an integer sum: any order)
+__global__ __launch_bounds__(256) void k_edit_record(uint32_t O, uint32_t L, uint32_t I, uint32_t P,
+                                                     const uint32_t* __restrict__ pos, const uint32_t* __restrict__ l_pos,
+                                                     const uint32_t* __restrict__ img_seg_start, const uint32_t* __restrict__ v_pos,
+                                                     const uint32_t* __restrict__ old_start, const uint32_t* __restrict__ start,
+                                                     uint32_t* __restrict__ rec) {
+  __shared__ uint32_t s_n[256];
+  uint32_t n = 0;
+  for (uint32_t p = threadIdx.x; p < P; p += 256)
+    n += (old_start[p + 1] != old_start[p] && start[p + 1] == start[p]) ? 1u : 0u;
+  s_n[threadIdx.x] = n;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) s_n[threadIdx.x] += s_n[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    rec[kRecObs] = pos[O];
+    rec[kRecTerms] = l_pos ? l_pos[L] : 0u;
+    rec[kRecSegs] = img_seg_start[I];
+    rec[kRecPoseRows] = v_pos ? v_pos[O] : pos[O];
+    rec[kRecEmptied] = s_n[0];
+  }
+}
+
+// key bits of the sort by track length: a length is at most O
+static unsigned length_bits(uint64_t O) {
+  unsigned bits = 1;
+  while (bits < 32 && (1ull << bits) <= O) ++bits;
+  return bits;
+}
+
+static pcd_status scan_flags(BaEditScratch& N, const uint32_t* flag, uint32_t* pos, size_t n, hipStream_t s) {
+  return exclusive_sum(N.prim, flag, pos, 0u, n, s);
+}
+
+// Every buffer the rebuild writes, at the sizes of the handle as it is: nothing grows when rows are dropped, so nothing
+// is allocated after the first launch
+static pcd_status edit_reserve(pcd_ba* b) {
+  BaEditScratch& N = b->edit_next;
+  const size_t O = b->O, L = b->L, P = (size_t)b->P, I = (size_t)b->I, ntr = (size_t)b->nslices * 64;
+  PCD_TRY(N.obs_image.reserve(at_least_1(O))); PCD_TRY(N.obs_point.reserve(at_least_1(O)));
+  PCD_TRY(N.obs_xy.reserve(at_least_1(2 * O)));
+  PCD_TRY(N.pt_obs_start.reserve(P + 1)); PCD_TRY(N.pt_obs_list.reserve(at_least_1(O)));
+  PCD_TRY(N.pt_order.reserve(at_least_1(ntr))); PCD_TRY(N.slice_start.reserve((size_t)b->nslices + 1));
+  PCD_TRY(N.sell_img.reserve(b->sell_img.n)); PCD_TRY(N.sell_xy.reserve(b->sell_xy.n));   // slices only get narrower
+  PCD_TRY(N.img_obs_start.reserve(I + 1)); PCD_TRY(N.img_obs.reserve(at_least_1(O)));
+  PCD_TRY(N.img_pt.reserve(at_least_1(O))); PCD_TRY(N.img_xy.reserve(std::max<size_t>(2 * O, 2)));
+  PCD_TRY(N.seg_img.reserve(at_least_1(b->nseg))); PCD_TRY(N.seg_begin.reserve((size_t)b->nseg + 1));
+  PCD_TRY(N.img_seg_start.reserve(I + 1));
+  if (b->has_cpose) { PCD_TRY(N.vobs.reserve(at_least_1(O))); PCD_TRY(N.v_flag.reserve(O + 1)); PCD_TRY(N.v_pos.reserve(O + 1)); }
+  PCD_TRY(N.flag.reserve(O + 1)); PCD_TRY(N.pos.reserve(O + 1));
+  PCD_TRY(N.t_flag.reserve(O + 1)); PCD_TRY(N.t_pos.reserve(O + 1));
+  PCD_TRY(N.i_flag.reserve(O + 1)); PCD_TRY(N.i_pos.reserve(O + 1));
+  PCD_TRY(N.len.reserve(P)); PCD_TRY(N.len_sorted.reserve(P)); PCD_TRY(N.iota.reserve(P));
+  PCD_TRY(N.width.reserve((size_t)b->nslices + 1)); PCD_TRY(N.seg_cnt.reserve(I + 1));
+  PCD_TRY(N.record.reserve(kRecWords)); PCD_TRY(N.h_record.reserve(kRecWords + I + 1));
+  if (L) {
+    PCD_TRY(N.l_point.reserve(L)); PCD_TRY(N.l_abcd.reserve(4 * L)); PCD_TRY(N.l_w.reserve(L));
+    if (b->has_lidar_meta) { PCD_TRY(N.l_type.reserve(L)); PCD_TRY(N.l_xyz.reserve(3 * L)); }
+    PCD_TRY(N.l_start.reserve(P + 1)); PCD_TRY(N.l_list.reserve(L));
+    PCD_TRY(N.l_cnt.reserve(at_least_1(ntr))); PCD_TRY(N.l_first.reserve(at_least_1(5 * ntr)));
+    PCD_TRY(N.lf.reserve(L + 1)); PCD_TRY(N.lp.reserve(L + 1)); PCD_TRY(N.lt_flag.reserve(L + 1)); PCD_TRY(N.lt_pos.reserve(L + 1));
+  }
+  // rocPRIM's storage: the largest need over every scan size the rebuild uses (no monotonicity in n is assumed) and the
+  // sort as the rebuild calls it, so that no call below has to grow the buffer
+  size_t need = 0;
+  for (size_t n : {O + 1, L + 1, (size_t)b->nslices + 1, I + 1}) {
+    size_t bytes = 0;
+    PCD_HIP_TRY(exclusive_sum_at(nullptr, bytes, N.flag.p, N.pos.p, 0u, n, nullptr));
+    need = std::max(need, bytes);
+  }
+  size_t bytes = 0;
+  PCD_HIP_TRY(sort_pairs_at(nullptr, bytes, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(N.pt_order.p), P, 0u,
+                            length_bits(O), nullptr));
+  PCD_TRY(N.prim.reserve(std::max(need, bytes)));
+  return PCD_OK;
+}
+
+static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t* d_pdel, uint32_t* d_map, hipStream_t s,
+                               pcd_ba_remove_info* info) {
+  BaEditScratch& N = b->edit_next;
+  const uint32_t O = (uint32_t)b->O, L = (uint32_t)b->L, P = (uint32_t)b->P, I = (uint32_t)b->I;
+  const uint32_t nslices = (uint32_t)b->nslices, ntr = nslices * 64u;
+  PCD_TRY(edit_reserve(b));
+  EventPair ev;
+  if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
+  auto grid = [](uint64_t n) { return dim3(div_up(n, 256)); };
+  const bool vrows = b->has_cpose;
+  {
+    ScopedKernelTimer t("ba_edit_scan", s);
+    hipLaunchKernelGGL(k_edit_obs_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, d_erase, d_pdel, b->obs_point.p, N.flag.p);
+    PCD_TRY(scan_flags(N, N.flag.p, N.pos.p, (size_t)O + 1, s));
+    hipLaunchKernelGGL(k_edit_list_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, b->pt_obs_list.p, N.flag.p, N.t_flag.p);
+    PCD_TRY(scan_flags(N, N.t_flag.p, N.t_pos.p, (size_t)O + 1, s));
+    hipLaunchKernelGGL(k_edit_list_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, b->img_obs.p, N.flag.p, N.i_flag.p);
+    PCD_TRY(scan_flags(N, N.i_flag.p, N.i_pos.p, (size_t)O + 1, s));
+    if (vrows) {
+      hipLaunchKernelGGL(k_edit_vobs_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, N.flag.p, b->obs_image.p,
+                         b->image_const_pose.p, N.v_flag.p);
+      PCD_TRY(scan_flags(N, N.v_flag.p, N.v_pos.p, (size_t)O + 1, s));
+    }
+    if (L) {
+      hipLaunchKernelGGL(k_edit_term_flag, grid((uint64_t)L + 1), dim3(256), 0, s, L, d_pdel, b->lidar_point.p, N.lf.p);
+      PCD_TRY(scan_flags(N, N.lf.p, N.lp.p, (size_t)L + 1, s));
+      hipLaunchKernelGGL(k_edit_list_flag, grid((uint64_t)L + 1), dim3(256), 0, s, L, b->pt_lidar_list.p, N.lf.p, N.lt_flag.p);
+      PCD_TRY(scan_flags(N, N.lt_flag.p, N.lt_pos.p, (size_t)L + 1, s));
+    }
+  }
+  {
+    ScopedKernelTimer t("ba_edit_rebuild", s);
+    // the observations, the track CSR and the image CSR
+    if (O) {
+      hipLaunchKernelGGL(k_edit_compact_obs, grid(O), dim3(256), 0, s, O, N.flag.p, N.pos.p, b->obs_image.p, b->obs_point.p,
+                         b->obs_xy.p, vrows ? N.v_flag.p : nullptr, N.v_pos.p, N.obs_image.p, N.obs_point.p, N.obs_xy.p,
+                         N.vobs.p, d_map);
+      hipLaunchKernelGGL(k_edit_compact_list, grid(O), dim3(256), 0, s, O, b->pt_obs_list.p, N.t_flag.p, N.t_pos.p, N.pos.p,
+                         N.pt_obs_list.p);
+      hipLaunchKernelGGL(k_edit_compact_list, grid(O), dim3(256), 0, s, O, b->img_obs.p, N.i_flag.p, N.i_pos.p, N.pos.p,
+                         N.img_obs.p);
+    }
+    hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)P + 1), dim3(256), 0, s, P, b->pt_obs_start.p, N.t_pos.p, N.pt_obs_start.p);
+    hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)I + 1), dim3(256), 0, s, I, b->img_obs_start.p, N.i_pos.p, N.img_obs_start.p);
+    // tracks in ascending order of length, ties in ascending point id; a length is below 2^length_bits(O)
+    hipLaunchKernelGGL(k_edit_lengths, grid(P), dim3(256), 0, s, P, N.pt_obs_start.p, N.len.p, N.iota.p);
+    PCD_TRY(sort_pairs(N.prim, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(N.pt_order.p), (size_t)P, 0u,
+                       length_bits(O), s));
+    hipLaunchKernelGGL(k_edit_slice_width, grid(std::max<uint64_t>(ntr, (uint64_t)nslices + 1)), dim3(256), 0, s, P, nslices,
+                       N.len_sorted.p, N.pt_order.p, N.width.p);
+    PCD_TRY(scan_flags(N, N.width.p, N.slice_start.p, (size_t)nslices + 1, s));
+    hipLaunchKernelGGL(k_ba_fill_sell, grid(ntr), dim3(256), 0, s, N.pt_order.p, N.slice_start.p, N.pt_obs_start.p,
+                       N.pt_obs_list.p, N.obs_image.p, N.obs_xy.p, (int)nslices, N.sell_img.p, N.sell_xy.p);
+    // segments of the images
+    hipLaunchKernelGGL(k_edit_seg_count, grid((uint64_t)I + 1), dim3(256), 0, s, I, N.img_obs_start.p, N.seg_cnt.p);
+    PCD_TRY(scan_flags(N, N.seg_cnt.p, N.img_seg_start.p, (size_t)I + 1, s));
+    hipLaunchKernelGGL(k_edit_segs, grid((uint64_t)I + 1), dim3(256), 0, s, I, N.img_obs_start.p, N.img_seg_start.p,
+                       N.seg_img.p, N.seg_begin.p);
+    // the terms, their CSR, and those of every track in the new thread order
+    if (L) {
+      const bool meta = b->has_lidar_meta;
+      hipLaunchKernelGGL(k_edit_compact_terms, grid(L), dim3(256), 0, s, L, N.lf.p, N.lp.p, b->lidar_point.p, b->lidar_abcd.p,
+                         b->lidar_w.p, meta ? b->lidar_type.p : nullptr, meta ? b->lidar_xyz.p : nullptr, N.l_point.p,
+                         N.l_abcd.p, N.l_w.p, N.l_type.p, N.l_xyz.p);
+      hipLaunchKernelGGL(k_edit_compact_list, grid(L), dim3(256), 0, s, L, b->pt_lidar_list.p, N.lt_flag.p, N.lt_pos.p, N.lp.p,
+                         N.l_list.p);
+      hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)P + 1), dim3(256), 0, s, P, b->pt_lidar_start.p, N.lt_pos.p, N.l_start.p);
+      hipLaunchKernelGGL(k_lidar_tracks, grid(ntr), dim3(256), 0, s, ntr, N.pt_order.p, N.l_start.p, N.l_list.p, N.l_abcd.p,
+                         N.l_w.p, N.l_cnt.p, N.l_first.p);
+    }
+    hipLaunchKernelGGL(k_edit_record, dim3(1), dim3(256), 0, s, O, L, I, P, N.pos.p, L ? N.lp.p : nullptr, N.img_seg_start.p,
+                       vrows ? N.v_pos.p : nullptr, b->pt_obs_start.p, N.pt_obs_start.p, N.record.p);
+    PCD_HIP_TRY(hipGetLastError());
+  }
+  // the one synchronisation: the counts and the image bounds (O(I) bytes)
+  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p, N.record.p, kRecWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p + kRecWords, N.img_obs_start.p, ((size_t)I + 1) * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, s));
+  if (info) (void)ev.stop(s);   // rebuild_ms ends here: the wait below completes the event, no second one is needed
+  PCD_HIP_TRY(hipStreamSynchronize(s));
+  const uint32_t* rec = N.h_record.p;
+  const uint32_t nO = rec[kRecObs], nL = rec[kRecTerms];
+  if (nO)
+    hipLaunchKernelGGL(k_ba_fill_image_major, grid(nO), dim3(256), 0, s, N.img_obs.p, N.obs_point.p, N.obs_xy.p, (uint64_t)nO,
+                       N.img_pt.p, N.img_xy.p);
+  PCD_HIP_TRY(hipGetLastError());
+  // success: the new layout becomes the handle's; the retired buffers are the next call's
+  b->obs_image.swap(N.obs_image); b->obs_point.swap(N.obs_point); b->obs_xy.swap(N.obs_xy);
+  b->pt_obs_start.swap(N.pt_obs_start); b->pt_obs_list.swap(N.pt_obs_list);
+  b->pt_order.swap(N.pt_order); b->slice_start.swap(N.slice_start); b->sell_img.swap(N.sell_img); b->sell_xy.swap(N.sell_xy);
+  b->img_obs_start.swap(N.img_obs_start); b->img_obs.swap(N.img_obs); b->img_pt.swap(N.img_pt); b->img_xy.swap(N.img_xy);
+  b->seg_img.swap(N.seg_img); b->seg_begin.swap(N.seg_begin); b->img_seg_start.swap(N.img_seg_start);
+  if (vrows) b->vobs.swap(N.vobs);
+  if (L) {
+    b->lidar_point.swap(N.l_point); b->lidar_abcd.swap(N.l_abcd); b->lidar_w.swap(N.l_w);
+    if (b->has_lidar_meta) { b->lidar_type.swap(N.l_type); b->lidar_xyz.swap(N.l_xyz); }
+    b->pt_lidar_start.swap(N.l_start); b->pt_lidar_list.swap(N.l_list);
+    b->pt_lidar_cnt.swap(N.l_cnt); b->pt_lidar_first.swap(N.l_first);
+  }
+  if (info) {
+    info->num_obs = nO; info->num_obs_removed = O - nO;
+    info->num_lidar = nL; info->num_lidar_removed = L - nL;
+    info->num_points_emptied = rec[kRecEmptied];
+  }
+  b->O = nO; b->L = nL;
+  b->nseg = rec[kRecSegs];
+  b->n_pose_rows = rec[kRecPoseRows];
+  b->h_img_obs_start.assign(rec + kRecWords, rec + kRecWords + I + 1);
+  b->pose_row_stale = true;
+  ba_schur_drop_structure(b);
+  if (info) {
+    float ms = 0.f;
+    PCD_HIP_TRY(ev.elapsed(&ms));
+    info->rebuild_ms = ms;
+  }
+  return PCD_OK;
+}
+
+}  // namespace pcd
+
+using namespace pcd;
+
+extern "C" pcd_status pcd_ba_remove_observations_device(pcd_ba* b, const uint8_t* d_obs_erase, const uint8_t* d_point_delete,
+                                                        uint32_t* d_obs_map, void* stream, pcd_ba_remove_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    if (info) std::memset(info, 0, sizeof *info);
+    PCD_REQUIRE(b, "null handle");
+    PCD_TRY(require_device(b->device));
+    PCD_TRY(refuse_capture((hipStream_t)stream, "pcd_ba_remove_observations_device"));
+    if (info) { info->num_obs = b->O; info->num_lidar = b->L; }
+    if (!d_obs_erase && !d_point_delete) return PCD_OK;   // nothing flagged: nothing changes, nothing is invalidated
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    return edit_rebuild(b, d_obs_erase, d_point_delete, d_obs_map, (hipStream_t)stream, info);
+  });
+}

@@ -1,9 +1,11 @@
 // ba_handle.h -- the bundle-adjustment handle as every BA unit sees it, and the sizes builder and launchers must agree
-// on (kImgSeg, kCostBlocks, cost_blocks, the element counts of the block form).  Internal; no kernels here.
+// on (kImgSeg, kCostBlocks, cost_blocks, the element counts of the block form).  Internal; no kernel is defined here
+// (three that several units launch are declared).
 //   ba_build.hip  makes and destroys it: pcd_ba_create uploads the problem and builds the derived layouts below
 //   ba.hip        evaluates on it: the kernels that read BaDev, and every pcd_ba_evaluate* / filter entry point
 //   ba_solve.hip  point elimination, PCG, LM loop (its own state hangs off pcd_ba::schur)
 //   ba_lidar.hip  replaces the LiDAR terms of a live handle: pcd_ba_set_lidar_device / pcd_ba_associate_lidar_device
+//   ba_edit.hip   drops observations and points from a live handle: pcd_ba_remove_observations_device
 #pragma once
 #include <memory>
 
@@ -68,6 +70,21 @@ struct BaLidarScratch {
   PinnedBuf<uint64_t> h_count;
 };
 
+// Scratch of pcd_ba_remove_observations_device (ba_edit.hip).  The first two groups are the layouts under construction:
+// on success they are swapped with the live arrays of pcd_ba, so the buffers a call retires are the next call's.
+struct BaEditScratch {
+  DevBuf<int> obs_image, obs_point, pt_order, sell_img, img_pt;
+  DevBuf<double> obs_xy, sell_xy, img_xy;
+  DevBuf<uint32_t> pt_obs_start, pt_obs_list, slice_start, img_obs_start, img_obs, seg_img, seg_begin, img_seg_start, vobs;
+  DevBuf<int> l_point; DevBuf<double> l_abcd, l_w, l_xyz, l_first; DevBuf<uint8_t> l_type; DevBuf<uint32_t> l_start, l_list, l_cnt;
+  // keep flags and their scans (n + 1 entries each: the last scan value is the count): observations in the caller's order,
+  // through the track lists, through the image lists, the variable-pose ones; terms in term order, through the point lists
+  DevBuf<uint32_t> flag, pos, t_flag, t_pos, i_flag, i_pos, v_flag, v_pos, lf, lp, lt_flag, lt_pos;
+  DevBuf<uint32_t> len, len_sorted, iota, width, seg_cnt, record;
+  DevBuf<char> prim;                                      // rocPRIM temporary storage (scan, sort)
+  PinnedBuf<uint32_t> h_record;                           // the counts, then img_obs_start [I+1]
+};
+
 // The point-elimination state is complete in ba_solve.hip only.  The deleter is defined there, so a pcd_ba can be
 // made and destroyed where BaSchur is an incomplete type (the default deleter would need the complete one).
 struct BaSchur;
@@ -107,6 +124,24 @@ pcd_status ba_normal_equations(pcd_ba* b, const uint32_t* w_order, double* Hpt, 
 // Drops the numeric state of the last Schur call (ba_solve.hip): pcd_ba_schur_solve_* and the back-substitution report
 // "no Schur state" until the next one.  The co-visibility structure and every scratch buffer stay.
 void ba_schur_invalidate(pcd_ba* b);
+// The same, and the co-visibility structure with it: the next Schur call builds it as the first call on a fresh handle
+// does (ba_edit.hip, when the observations change).  Scratch buffers stay.
+void ba_schur_drop_structure(pcd_ba* b);
+
+// Kernels one unit defines and another launches too (the handle's derived layouts are made in three places: on creation,
+// when the terms change, when observations are dropped).  ba_build.hip: the sliced-ELL fill and the image-major copies;
+// ba_lidar.hip: the terms of every track in the thread order of k_ba_points.
+__global__ void k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __restrict__ slice_start,
+                               const uint32_t* __restrict__ pt_start, const uint32_t* __restrict__ pt_list,
+                               const int* __restrict__ obs_image, const double* __restrict__ obs_xy, int nslices,
+                               int* __restrict__ sell_img, double* __restrict__ sell_xy);
+__global__ void k_ba_fill_image_major(const uint32_t* __restrict__ img_obs, const int* __restrict__ obs_point,
+                                      const double* __restrict__ obs_xy, uint64_t O, int* __restrict__ img_pt,
+                                      double* __restrict__ img_xy);
+__global__ __launch_bounds__(256) void k_lidar_tracks(uint32_t ntr, const int* __restrict__ order,
+                                                      const uint32_t* __restrict__ start, const uint32_t* __restrict__ list,
+                                                      const double* __restrict__ abcd, const double* __restrict__ w,
+                                                      uint32_t* __restrict__ cnt, double* __restrict__ first);
 
 }  // namespace pcd
 
@@ -133,6 +168,7 @@ struct pcd_ba {
   pcd::DevBuf<double> lidar_xyz;
   bool has_lidar_meta = false;
   pcd::BaLidarScratch lidar_next;
+  pcd::BaEditScratch edit_next;
   pcd::DevBuf<uint32_t> slice_start, pt_lidar_start, pt_lidar_list, img_obs_start, img_obs, cam_img_start, cam_img_list;
   pcd::DevBuf<uint32_t> seg_img, seg_begin, img_seg_start, pt_lidar_cnt;
   uint32_t nseg = 0;
@@ -144,7 +180,11 @@ struct pcd_ba {
   // host-API staging
   pcd::DevBuf<double> o_res, o_jq, o_jt, o_jx, o_jl, o_himg, o_gimg, o_hpt, o_gpt, o_w, o_jc, o_hcam, o_gcam, o_ecam, o_wcam;
   // pcd_ba_evaluate_blocks: rows of the variable-pose observations, packed pose Jacobians, pinned results
-  std::vector<uint32_t> h_pose_row;      // [O] row of observation o in the packed jac_q / jac_t (0xFFFFFFFF: constant pose)
+  // [O] row of observation o in the packed jac_q / jac_t (0xFFFFFFFF: constant pose).  O(O) on the host and read only by
+  // pcd_ba_evaluate_blocks: pcd_ba_remove_observations_device marks it stale instead of rebuilding it, and the first
+  // pcd_ba_evaluate_blocks afterwards refreshes it from the device's obs_image (ba_refresh_pose_rows, ba.hip)
+  std::vector<uint32_t> h_pose_row;
+  bool pose_row_stale = false;
   uint64_t n_pose_rows = 0;
   pcd::DevBuf<uint32_t> vobs;            // [n_pose_rows] observation of every packed row
   pcd::DevBuf<double> p_jq, p_jt;        // packed pose Jacobians (only when some pose is constant)
@@ -157,6 +197,9 @@ struct pcd_ba {
   // filter scratch; f_sq / f_depth also stage pcd_ba_observation_errors
   pcd::DevBuf<double> f_sq, f_depth, f_part, f_summary;
   pcd::DevBuf<uint8_t> f_u8;
+  // pcd_ba_filter_points_device: projection centres [I][3]; the stage-1 outputs the caller did not ask for
+  pcd::DevBuf<double> f_centers, f_tri_err;
+  pcd::DevBuf<uint8_t> f_tri_u8;
   // point elimination (pcd_ba_schur*): built on the first call, so pcd_ba_create costs existing users nothing
   bool refines_intrinsics = false;   // some camera_refine byte is set: the reduced system would need camera rows
   std::unique_ptr<pcd::BaSchur, pcd::BaSchurDelete> schur;

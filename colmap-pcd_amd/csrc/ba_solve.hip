@@ -762,6 +762,11 @@ struct BaSchur {
 
 void BaSchurDelete::operator()(BaSchur* s) const { delete s; }
 void ba_schur_invalidate(pcd_ba* b) { if (b->schur) b->schur->num.valid = false; }
+void ba_schur_drop_structure(pcd_ba* b) {
+  if (!b->schur) return;
+  b->schur->num.valid = false;
+  b->schur->st.built = false;   // schur_build assigns every member of the structure anew
+}
 
 }  // namespace pcd
 

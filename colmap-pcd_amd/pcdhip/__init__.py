@@ -202,6 +202,21 @@ class BAProjInfo(C.Structure):
                [(n, C.c_double) for n in ("proj_ms", "assoc_ms", "rebuild_ms")]
 
 
+class BAFilterOpts(C.Structure):
+    """pcd_ba_filter_opts (pcdhip.h)."""
+    _fields_ = [("max_reproj_error", C.c_double), ("min_tri_angle_deg", C.c_double), ("reserved", C.c_int32 * 8)]
+
+
+class BAFilterOut(C.Structure):
+    """pcd_ba_filter_out (pcdhip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("obs_erase", "obs_negative_depth", "point_delete", "point_error", "summary")]
+
+
+class BARemoveInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("num_obs", "num_obs_removed", "num_lidar", "num_lidar_removed",
+                                           "num_points_emptied")] + [("rebuild_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -267,6 +282,8 @@ ABI_SYMBOLS = [
     "pcd_ba_set_lidar_device", "pcd_ba_get_lidar", "pcd_ba_lidar_device", "pcd_ba_assoc_opts_default",
     "pcd_ba_associate_lidar_device",
     "pcd_proj_set_new_images_device", "pcd_ba_proj_opts_default", "pcd_ba_project_lidar_device",
+    "pcd_ba_filter_opts_default", "pcd_ba_filter_points_device", "pcd_ba_filter_points",
+    "pcd_ba_remove_observations_device",
 ]
 
 
@@ -385,6 +402,13 @@ def lib():
                                                   C.POINTER(BAProjInfo)]
         L.pcd_ba_associate_lidar_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BAAssocOpts), C.c_void_p,
                                                     C.POINTER(BAAssocInfo)]
+    if hasattr(L, "pcd_ba_remove_observations_device"):
+        L.pcd_ba_filter_opts_default.argtypes = [C.POINTER(BAFilterOpts)]
+        L.pcd_ba_filter_opts_default.restype = None
+        L.pcd_ba_filter_points.argtypes = [C.c_void_p, C.POINTER(BAFilterOpts), C.POINTER(BAFilterOut)]
+        L.pcd_ba_filter_points_device.argtypes = [C.c_void_p, C.POINTER(BAFilterOpts), C.POINTER(BAFilterOut), C.c_void_p]
+        L.pcd_ba_remove_observations_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.POINTER(BARemoveInfo)]
     _LIB = L
     return L
 
@@ -1215,6 +1239,75 @@ class BA:
                    num_negative_depth=int(sm[3]))
         return out
 
+    @staticmethod
+    def _filter_opts(max_reproj_error, min_tri_angle):
+        o = BAFilterOpts()
+        lib().pcd_ba_filter_opts_default(C.byref(o))
+        o.max_reproj_error, o.min_tri_angle_deg = float(max_reproj_error), float(min_tri_angle)
+        return o
+
+    def filter_points(self, max_reproj_error=8.0, min_tri_angle=1.5):
+        """Reconstruction::FilterPoints3D on the device (pcd_ba_filter_points): filter_tracks, then the
+        triangulation-angle filter (degrees; <= 0: the first filter alone) on what it left.  The same dict as
+        filter_tracks; num_filtered counts elements for the first filter and one per point for the second."""
+        out = dict(obs_erase=np.zeros(self.O, np.uint8), obs_negative_depth=np.zeros(self.O, np.uint8),
+                   point_delete=np.zeros(self.P, np.uint8), point_error=np.zeros(self.P), summary=np.zeros(4))
+        fo = BAFilterOut(*[_vp(out[k]) for k, _ in BAFilterOut._fields_])
+        o = self._filter_opts(max_reproj_error, min_tri_angle)
+        _check(lib().pcd_ba_filter_points(self._h, C.byref(o), C.byref(fo)))
+        sm = out.pop("summary")
+        out.update(num_filtered=int(sm[0]), mean_reproj_error=float(sm[1]), num_points_with_error=int(sm[2]),
+                   num_negative_depth=int(sm[3]))
+        return out
+
+    def filter_points_device(self, max_reproj_error=8.0, min_tri_angle=1.5, out=None):
+        """pcd_ba_filter_points_device on the current torch stream: dict of torch device tensors obs_erase [O] uint8,
+        obs_negative_depth [O] uint8, point_delete [P] uint8, point_error [P], summary [4] float64 (made here, or the
+        tensors of `out` reused; a key of `out` set to None is not computed).  Nothing is synchronised."""
+        torch, dev, stream = self._torch()
+        if out is None:
+            out = dict(obs_erase=torch.empty(self.O, dtype=torch.uint8, device=dev),
+                       obs_negative_depth=torch.empty(self.O, dtype=torch.uint8, device=dev),
+                       point_delete=torch.empty(self.P, dtype=torch.uint8, device=dev),
+                       point_error=torch.empty(self.P, dtype=torch.float64, device=dev),
+                       summary=torch.empty(4, dtype=torch.float64, device=dev))
+        fo = BAFilterOut(*[_ptr(out.get(k)) for k, _ in BAFilterOut._fields_])
+        o = self._filter_opts(max_reproj_error, min_tri_angle)
+        _check(lib().pcd_ba_filter_points_device(self._h, C.byref(o), C.byref(fo), C.c_void_p(stream)))
+        return out
+
+    def remove_observations(self, obs_erase=None, point_delete=None, want_map=False):
+        """pcd_ba_remove_observations_device: drop the observations with obs_erase != 0 and, for every point with
+        point_delete != 0, all its observations and LiDAR terms ([O] / [P] uint8, torch device tensors or numpy; None:
+        none).  Afterwards the handle equals one created from the compacted arrays; point ids stay, a deleted point's
+        coordinates are meaningless.  Synchronises the current stream once.  Returns the info dict (num_obs,
+        num_obs_removed, num_lidar, num_lidar_removed, num_points_emptied, rebuild_ms), with want_map also "obs_map": an
+        [O before] int32 device tensor, the new index of every old observation, -1 for a dropped one (the C ABI's
+        0xFFFFFFFF)."""
+        torch, dev, stream = self._torch()
+        e, p = self._stage(obs_erase, np.uint8), self._stage(point_delete, np.uint8)
+        if e is not None and int(e.numel()) != self.O:
+            raise ValueError("remove_observations: obs_erase must have one entry per observation")
+        if p is not None and int(p.numel()) != self.P:
+            raise ValueError("remove_observations: point_delete must have one entry per point")
+        if e is not None and self.O == 0:
+            e = None    # an empty tensor has a null data pointer anyway: no observation to erase
+        m = None
+        if want_map:
+            m = torch.arange(self.O, dtype=torch.int32, device=dev)   # the identity: what a call without flags leaves
+        info = BARemoveInfo()
+        _check(lib().pcd_ba_remove_observations_device(self._h, _ptr(e), _ptr(p), _ptr(m), C.c_void_p(stream),
+                                                       C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in BARemoveInfo._fields_}
+        if e is not None or p is not None:
+            self.O, self.L = int(info.num_obs), int(info.num_lidar)
+            self.obs_image = self.obs_point = self.obs_xy = None      # stale: the handle has the current rows
+            self.lidar_point = self.lidar_abcd = self.lidar_weight = None
+            self.__dict__.pop("_schur_dims", None)                    # the co-visibility structure is built anew
+        if want_map:
+            out["obs_map"] = m
+        return out
+
     def device_parameters(self):
         a, b = C.c_void_p(), C.c_void_p()
         _check(lib().pcd_ba_device_parameters(self._h, C.byref(a), C.byref(b)))
@@ -1591,6 +1684,31 @@ def register_refine(ba, cloud, rounds, kd_max=1.5, kd_min=0.2, drop=0.1, gate_mo
         info["max_range"] = rng
         summary, its = ba_solve(ba, **solve_opts)
         out.append((info, summary, its))
+    return out
+
+
+def refine_filter(ba, max_refinements=5, max_change=0.0005, max_reproj_error=8.0, min_tri_angle=1.5, **solve_opts):
+    """The loop of IncrementalMapperController's IterativeGlobalRefinement (controllers/incremental_mapper.cc:150-199) on
+    one handle: ba_solve(**solve_opts), BA.filter_points_device, BA.remove_observations with the filter's flags, until a
+    round changes less than max_change of the observations it started with (changed = num_filtered / observations before
+    the round's removal; a handle without observations counts as unchanged) or max_refinements rounds have run.  No
+    observation payload crosses PCIe; per round the host reads the filter's 4-double summary and the removal's counts.
+    CompleteAndMergeTracks and retriangulation add observations: they are the host's business and are left out, so
+    `changed` counts the filtered observations alone.  Returns one (solve summary, filter summary, remove info) per
+    round; the filter summary is a dict of num_filtered, mean_reproj_error, num_points_with_error, num_negative_depth,
+    changed."""
+    out = []
+    for _ in range(int(max_refinements)):
+        num_obs = ba.O
+        summary, _its = ba_solve(ba, **solve_opts)
+        f = ba.filter_points_device(max_reproj_error, min_tri_angle)
+        info = ba.remove_observations(f["obs_erase"], f["point_delete"])
+        sm = f["summary"].cpu().numpy()
+        changed = float(sm[0]) / num_obs if num_obs else 0.0
+        out.append((summary, dict(num_filtered=int(sm[0]), mean_reproj_error=float(sm[1]),
+                                  num_points_with_error=int(sm[2]), num_negative_depth=int(sm[3]), changed=changed), info))
+        if changed < max_change:
+            break
     return out
 
 

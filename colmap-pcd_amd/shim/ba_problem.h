@@ -243,9 +243,16 @@ class BundleAdjusterHip {
       std::copy(poses_.begin() + 7 * i, poses_.begin() + 7 * i + 4, im.qvec);
       std::copy(poses_.begin() + 7 * i + 4, poses_.begin() + 7 * i + 7, im.tvec);
     }
+    // A point without a residual block (one FilterPoints deleted: it stays in point_ids_) has meaningless coordinates and,
+    // once the caller has run DeletePoint3D on the ids FilterPoints reported, no entry in the Reconstruction: not written
+    std::vector<uint8_t> has_block(point_ids_.size(), 0);
+    for (int p : obs_point_) has_block[p] = 1;
+    for (int p : lidar_point_) has_block[p] = 1;
     for (size_t p = 0; p < point_ids_.size(); ++p) {
-      if (point_const_[p]) continue;
-      std::copy(points_.begin() + 3 * p, points_.begin() + 3 * p + 3, rec->points3D.at(point_ids_[p]).xyz);
+      if (point_const_[p] || !has_block[p]) continue;
+      auto it = rec->points3D.find(point_ids_[p]);
+      if (it == rec->points3D.end()) continue;
+      std::copy(points_.begin() + 3 * p, points_.begin() + 3 * p + 3, it->second.xyz);
     }
     return true;
   }
@@ -402,6 +409,76 @@ class BundleAdjusterHip {
     reassociated_ = true;
     return true;
   }
+  // ---- the post-BA filter (HIP): IncrementalMapper::FilterPoints / Reconstruction::FilterPoints3D (base/reconstruction.cc:
+  // 760-769) on the LIVE handle, at its current parameters (after Create() or Solve()) ------------------------------------
+  // pcd_ba_filter_points_device over every point of the problem.  erased (may be NULL) receives the (image_id,
+  // point2D_idx) of every observation the filter erases on a point it keeps, for the caller's DeleteObservation; deleted
+  // (may be NULL) the ids of the points it deletes, for DeletePoint3D, which removes their remaining observations itself
+  // (a point that has no observation in the problem, such as one an earlier call deleted, is not reported again).
+  // With `apply` the flags are applied on the device (pcd_ba_remove_observations_device: nothing is uploaded, no second
+  // Create) and the flat arrays -- obs_image_ / obs_point_ / obs_xy_ / obs_point2D_ and the term vectors, with
+  // config_.lidar_maps_ -- are compacted by the same rule, so NumResiduals(), a later Create() and a later Solve (which
+  // keeps this handle) agree with the handle.  A deleted point stays in point_ids_ without a residual block.
+  // Returns the reference's num_filtered (elements for the reprojection filter, one per point for the angle filter);
+  // *ok (may be NULL) is false without a live handle or when a call fails (pcd_last_error()): the problem is then as it was.
+  size_t FilterPoints(double max_reproj_error, double min_tri_angle, bool apply,
+                      std::vector<std::pair<image_t, point2D_t>>* erased = nullptr, std::vector<point3D_t>* deleted = nullptr,
+                      bool* ok = nullptr) {
+    if (ok) *ok = false;
+    if (erased) erased->clear();
+    if (deleted) deleted->clear();
+    if (!ba_) return 0;
+    const size_t O = obs_image_.size(), P = point_ids_.size();
+    struct DevMem {   // freed on every return
+      void* p = nullptr;
+      ~DevMem() { if (p) (void)hipFree(p); }
+    } d_flags, d_summary;
+    if (hipMalloc(&d_flags.p, O + P + 1) != hipSuccess || hipMalloc(&d_summary.p, 4 * sizeof(double)) != hipSuccess) return 0;
+    pcd_ba_filter_opts fo;
+    pcd_ba_filter_opts_default(&fo);
+    fo.max_reproj_error = max_reproj_error;
+    fo.min_tri_angle_deg = min_tri_angle;
+    pcd_ba_filter_out out{};
+    out.obs_erase = static_cast<uint8_t*>(d_flags.p);
+    out.point_delete = static_cast<uint8_t*>(d_flags.p) + O;
+    out.summary = static_cast<double*>(d_summary.p);
+    if (pcd_ba_filter_points_device(ba_, &fo, &out, nullptr) != PCD_OK) return 0;
+    std::vector<uint8_t> flags(O + P + 1);
+    double summary[4] = {0, 0, 0, 0};
+    if (hipMemcpy(flags.data(), d_flags.p, O + P, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(summary, d_summary.p, sizeof summary, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    const uint8_t* erase = flags.data(), *pdel = flags.data() + O;
+    if (apply && pcd_ba_remove_observations_device(ba_, out.obs_erase, out.point_delete, nullptr, nullptr, nullptr) != PCD_OK)
+      return 0;
+    for (size_t o = 0; o < O; ++o)
+      if (erased && erase[o] && !pdel[obs_point_[o]]) erased->emplace_back(image_ids_[obs_image_[o]], obs_point2D_[o]);
+    // a point without observations in the problem (one an earlier call emptied) is no news to the caller
+    std::vector<uint32_t> track_len(P, 0);
+    for (size_t o = 0; o < O; ++o) track_len[obs_point_[o]]++;
+    for (size_t p = 0; p < P; ++p)
+      if (deleted && pdel[p] && track_len[p]) deleted->push_back(point_ids_[p]);
+    if (apply) {
+      size_t n = 0;
+      for (size_t o = 0; o < O; ++o) {
+        if (erase[o] || pdel[obs_point_[o]]) continue;
+        obs_image_[n] = obs_image_[o]; obs_point_[n] = obs_point_[o]; obs_point2D_[n] = obs_point2D_[o];
+        obs_xy_[2 * n] = obs_xy_[2 * o]; obs_xy_[2 * n + 1] = obs_xy_[2 * o + 1];
+        ++n;
+      }
+      obs_image_.resize(n); obs_point_.resize(n); obs_point2D_.resize(n); obs_xy_.resize(2 * n);
+      size_t m = 0;
+      for (size_t l = 0; l < lidar_point_.size(); ++l) {
+        if (pdel[lidar_point_[l]]) { config_.lidar_maps_.erase(point_ids_[lidar_point_[l]]); continue; }
+        lidar_point_[m] = lidar_point_[l]; lidar_w_[m] = lidar_w_[l];
+        for (int k = 0; k < 4; ++k) lidar_abcd_[4 * m + k] = lidar_abcd_[4 * l + k];
+        ++m;
+      }
+      lidar_point_.resize(m); lidar_w_.resize(m); lidar_abcd_.resize(4 * m);
+      reassociated_ = true;   // the live handle is the problem: Solve keeps it
+    }
+    if (ok) *ok = true;
+    return (size_t)summary[0];
+  }
   const BundleAdjustmentConfig& config() const { return config_; }
   // what Solve hands to pcd_ba_solve: AUTO goes by the number of images in the config, as the reference does
   bool UsesDirectSolver() const {
@@ -420,6 +497,7 @@ class BundleAdjusterHip {
   std::vector<uint64_t> cam_width_, cam_height_;   // Camera::Width / Height by flat index (ProjectLidar)
   std::vector<image_t> image_ids_;       // flat index -> id
   std::vector<point3D_t> point_ids_;
+  std::vector<point2D_t> obs_point2D_;   // per observation: its index among the image's points2D (FilterPoints hands it back)
 
  private:
   template <typename S>
@@ -439,6 +517,7 @@ class BundleAdjusterHip {
     point_const_.clear(); image_used_.clear(); image_ids_.clear(); point_ids_.clear();
     cam_refine_.clear(); camera_ids_.clear(); cam_width_.clear(); cam_height_.clear();
     cam_index_.clear(); image_index_.clear(); point_index_.clear(); point3D_num_observations_.clear();
+    obs_point2D_.clear();
     reassociated_ = false;
   }
   int CameraIndex(camera_t id, const Reconstruction* rec) {
@@ -484,7 +563,8 @@ class BundleAdjusterHip {
     point_const_.push_back(0);
     return idx;
   }
-  void AddObservation(int image_idx, int point_idx, const double xy[2]) {
+  void AddObservation(int image_idx, int point_idx, point2D_t point2D_idx, const double xy[2]) {
+    obs_point2D_.push_back(point2D_idx);
     obs_image_.push_back(image_idx);
     obs_point_.push_back(point_idx);
     obs_xy_.push_back(xy[0]);
@@ -497,11 +577,12 @@ class BundleAdjusterHip {
     image.NormalizeQvec();                                                                     // :823
     const bool constant_pose = !options_.refine_extrinsics || config_.HasConstantPose(image_id);  // :831
     const int ii = ImageIndex(image_id, rec, constant_pose);
-    for (const Point2D& p2 : image.points2D) {
+    for (size_t k = 0; k < image.points2D.size(); ++k) {
+      const Point2D& p2 = image.points2D[k];
       if (!p2.HasPoint3D()) continue;
       if (in_sphere_only && !rec->points3D.at(p2.point3D_id).if_in_sphere) continue;
       point3D_num_observations_[p2.point3D_id] += 1;
-      AddObservation(ii, PointIndex(p2.point3D_id, rec), p2.xy);
+      AddObservation(ii, PointIndex(p2.point3D_id, rec), (point2D_t)k, p2.xy);
     }
   }
   // :927-985: observations of the point from images outside the config -> constant-pose blocks
@@ -514,7 +595,7 @@ class BundleAdjusterHip {
       Image& image = rec->images.at(te.image_id);
       if (cam_index_.count(image.camera_id) == 0) config_.SetConstantCamera(image.camera_id);   // :951-954
       const int ii = ImageIndex(te.image_id, rec, /*const_pose_block=*/true);
-      AddObservation(ii, PointIndex(pid, rec), image.points2D.at(te.point2D_idx).xy);
+      AddObservation(ii, PointIndex(pid, rec), te.point2D_idx, image.points2D.at(te.point2D_idx).xy);
     }
   }
   // :993-1040

@@ -603,6 +603,32 @@ typedef struct {
 pcd_status pcd_ba_filter_tracks_device(pcd_ba* ba, double max_reproj_error, const pcd_ba_filter_out* d_out, void* stream);
 pcd_status pcd_ba_filter_tracks(pcd_ba* ba, double max_reproj_error, const pcd_ba_filter_out* out);   /* host outputs */
 
+/* Reconstruction::FilterPoints3D (base/reconstruction.cc:760-769) on the device: the filter above, then
+ * FilterPoints3DWithSmallTriangulationAngle (:1600-1660) on what it left.
+ *   Stage 1 is pcd_ba_filter_tracks_device with max_reproj_error: every output has its bits.
+ *   Stage 2 runs for every point stage 1 did not delete, on its surviving elements (obs_erase == 0) in ascending
+ *   observation index, pairs (i1, i2 < i1) in the reference's loop order.  The projection centre of an image is
+ *   ProjectionCenterFromPose (base/pose.cc:164-171) of the handle's CURRENT pose: the normalised quaternion, conjugated,
+ *   applied to -tvec (a zero quaternion counts as the identity, as in pcd_ba_observation_errors).  The angle is
+ *   CalculateTriangulationAngle (base/triangulation.cc:122-145): squared norms, denominator == 0 gives 0, acos, abs,
+ *   min(angle, pi - angle).  The point is kept as soon as one pair reaches DegToRad(min_tri_angle_deg); a NaN angle (the
+ *   acos argument outside [-1, 1] by rounding) keeps nothing.
+ *   A point stage 2 does not keep is deleted: point_delete = 1, obs_erase = 1 for all its observations, point_error =
+ *   -1; summary[0] grows by 1 PER SUCH POINT (the reference counts points here, elements in stage 1), summary[1..2]
+ *   lose the point's error, summary[3] is unchanged.  The summary is a fixed-order reduction: a repeated call is
+ *   bitwise identical.
+ * min_tri_angle_deg <= 0 (or NaN): stage 1 alone.  Every output pointer may be NULL.
+ * There is no point-subset argument (FilterPoints3D takes an id set): the call filters every point; a caller who wants
+ * a subset masks obs_erase / point_delete before applying them (pcd_ba_remove_observations_device). */
+typedef struct {
+  double max_reproj_error;     /* as pcd_ba_filter_tracks */
+  double min_tri_angle_deg;    /* degrees, converted as DegToRad does; <= 0 keeps every point the first filter kept */
+  int32_t reserved[8];
+} pcd_ba_filter_opts;
+void pcd_ba_filter_opts_default(pcd_ba_filter_opts* opts);   /* 8.0, 1.5: sfm/incremental_mapper.h:131,135 */
+pcd_status pcd_ba_filter_points_device(pcd_ba* ba, const pcd_ba_filter_opts* opts, const pcd_ba_filter_out* d_out, void* stream);
+pcd_status pcd_ba_filter_points(pcd_ba* ba, const pcd_ba_filter_opts* opts, const pcd_ba_filter_out* out);   /* host outputs */
+
 /* The Ceres route (optim/bundle_adjustment.cc:858-893, :967-983, :1031-1037: every residual block's Evaluate copies
  * its rows): the raw blocks of ALL residual blocks land in PINNED host buffers owned by the handle -- one device pass,
  * then one asynchronous copy per array at the pinned PCIe rate instead of pcd_ba_evaluate's synchronous copies into
@@ -975,6 +1001,47 @@ typedef struct {
 void pcd_ba_proj_opts_default(pcd_ba_proj_opts* opts);   /* NULLs, MAPPER_LOCAL, 1, 100, 1000 */
 pcd_status pcd_ba_project_lidar_device(pcd_ba* ba, pcd_proj* proj, const pcd_ba_proj_opts* opts, void* stream,
                                        pcd_ba_proj_info* info /* host, may be NULL */);
+
+/* ------------------------------------------------------------------------
+ * Observations and points dropped from a live handle on the device        
+ *   the "adjust, filter, adjust" of controllers/incremental_mapper.cc:150-199 IterativeGlobalRefinement and of the
+ *   local round, sfm/incremental_mapper.cc:1190-1211: the flags of pcd_ba_filter_points_device (or any others) applied
+ *   to the handle without a host round trip and without a second pcd_ba_create.
+ * Observation o is kept iff !d_obs_erase[o] && !d_point_delete[obs_point[o]]; LiDAR term l is kept iff
+ *   !d_point_delete[lidar_point[l]].  Any non-zero byte counts as 1.  Kept rows keep their relative order.  P, I, C, the
+ *   parameters currently on the device, the constness masks, the refine mask and the loss are unchanged.  A deleted
+ *   point stays as a row without a residual block, so point ids remain stable for the caller; nothing constrains its
+ *   coordinates any more: they are meaningless from then on (a solve leaves them where they are).
+ * Contract (that of pcd_ba_set_lidar_device): afterwards the handle is indistinguishable from one pcd_ba_create built
+ *   from the same description with obs_* and lidar_* compacted this way -- every derived array is the one pcd_ba_create
+ *   would upload, byte for byte, so every later result on the handle (evaluate, both block routes, the filters, the
+ *   Schur structure and blocks, both solves, associate_lidar / project_lidar, get_lidar with its type / lidar_xyz meta)
+ *   is bit-identical to the fresh handle's.
+ * d_obs_map, if given, receives the new index of every old observation, 0xFFFFFFFF for a dropped one.
+ * Both flag pointers NULL is a valid call that changes nothing and invalidates nothing (d_obs_map is not written).
+ * Guards, the handle exactly as it was: a NULL handle -> INVALID; no gfx950 -> NO_DEVICE; a capturing stream ->
+ *   UNSUPPORTED before anything is allocated.  The flags cannot be invalid; a failed allocation is the only other
+ *   failure, and every buffer is reserved before the first kernel; the new layout is built in buffers of its own and
+ *   swapped in at the end.
+ * The call synchronises `stream` ONCE, to read O(I) bytes: the counts and the image bounds.  The rest is enqueued on
+ *   `stream`; later work on the handle must be ordered behind it.  info does not add a wait: rebuild_ms is the device
+ *   time up to that synchronisation (every pass but the image-major fill, which is enqueued behind it).
+ * What the call invalidates: pointers handed out by an earlier pcd_ba_evaluate_blocks* and pcd_ba_lidar_device; the
+ *   Schur state of the last call AND the co-visibility structure, which depends on the observations: the next Schur
+ *   call builds it as on a fresh handle.  Scratch only shrinks and is kept.
+ * No atomics; no order depends on launch geometry: a repeated call is bitwise identical.
+ * --------------------------------------------------------------------- */
+typedef struct {
+  uint64_t num_obs, num_obs_removed;      /* after / removed */
+  uint64_t num_lidar, num_lidar_removed;
+  uint64_t num_points_emptied;            /* points that had observations before and have none now */
+  double rebuild_ms;                      /* device time up to the call's one synchronisation */
+} pcd_ba_remove_info;
+pcd_status pcd_ba_remove_observations_device(pcd_ba* ba,
+    const uint8_t* d_obs_erase     /* [O] != 0: drop; NULL: none */,
+    const uint8_t* d_point_delete  /* [P] != 0: drop all observations AND all LiDAR terms of the point; NULL: none */,
+    uint32_t* d_obs_map            /* [O before] or NULL: new index of every old observation, 0xFFFFFFFF = dropped */,
+    void* stream, pcd_ba_remove_info* info /* host, may be NULL */);
 
 /* ------------------------------------------------------------------------
  * Exact SIFT descriptor matching (stretch row a19)
