@@ -4,6 +4,7 @@
 //   ba_build.hip  makes and destroys it: pcd_ba_create uploads the problem and builds the derived layouts below
 //   ba.hip        evaluates on it: the kernels that read BaDev, and every pcd_ba_evaluate* / filter entry point
 //   ba_solve.hip  point elimination, PCG, LM loop (its own state hangs off pcd_ba::schur)
+//   ba_schur_structure.hip  the co-visibility structure of the elimination, built on the device (ba_schur_structure.h)
 //   ba_lidar.hip  replaces the LiDAR terms of a live handle: pcd_ba_set_lidar_device / pcd_ba_associate_lidar_device
 //   ba_edit.hip   drops observations and points from a live handle: pcd_ba_remove_observations_device
 #pragma once

@@ -7,9 +7,9 @@
 // (ba_handle.h) for H, g, W and the cost, and pcd_ba_evaluate_device for the cost of a trial step.  No evaluation
 // kernel is compiled here.
 //
-// Host side, behind the kernels: BaSchur, the solver state grouped by owner; schur_build over schur_read_back,
-// schur_assign_slots, schur_point_lists, schur_diag_blocks, schur_pair_blocks (both on schur_walk_row), schur_row_lists
-// and schur_upload; the PCG batches; pcd_ba_solve over lm_check_opts, lm_reserve, lm_enqueue_linear, lm_try_step, lm_decide.
+// Host side, behind the kernels: BaSchur, the solver state grouped by owner; schur_build, which has the co-visibility
+// structure built on the device (ba_schur_structure.hip) on the stream of the call that needs it; the PCG batches;
+// pcd_ba_solve over lm_check_opts, lm_reserve, lm_enqueue_linear, lm_try_step, lm_decide.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -17,6 +17,7 @@
 
 #include "ba_chol.h"
 #include "ba_handle.h"
+#include "ba_schur_structure.h"
 #include "common.h"
 
 namespace pcd {
@@ -718,18 +719,8 @@ __global__ void k_chol_lm_info(const pcd_ba_chol_info* __restrict__ c, pcd_ba_pc
 // The solver state of a handle, one group per owner; the element counts are ba_handle.h's.  device_bytes()
 // (pcd_ba_schur_stats) is the sum of the groups' bytes(): every DevBuf but the 8 bytes of num.skip_cnt.
 struct BaSchur {
-  struct Structure {   // built on the host by the first Schur call (schur_build), then read only
-    bool built = false; int ns = 0; uint64_t npairs = 0, nent = 0; double build_ms = 0.0;
-    uint32_t nblk() const { return (uint32_t)(ns + npairs); }   // the ns diagonal blocks, then the pair blocks
-    std::vector<int32_t> h_slot, h_pair_i, h_pair_j;
-    DevBuf<int> img_slot, slot_img;
-    DevBuf<uint32_t> blk_start, ent_a, ent_b, pair_ij, iota, obs_pos;
-    // rows of S for y = S x, ascending partner slot: [ns+1]; block (< ns: diagonal, else ns + pair); partner << 1 | transposed
-    DevBuf<uint32_t> row_start, row_blk, row_col;
-    uint64_t bytes() const {
-      return dev_bytes(img_slot, slot_img, blk_start, ent_a, ent_b, pair_ij, iota, obs_pos, row_start, row_blk, row_col);
-    }
-  } st;
+  using Structure = SchurStructure;   // ba_schur_structure.h: built on the device by the first Schur call, then read only
+  Structure st;
   struct Numeric {   // the last Schur call (pcd_ba_schur_device)
     bool valid = false;   // it has filled the buffers below ...
     bool own_diag = false, own_off = false, own_rhs = false;   // ... and left S_diag / S_off / rhs in the handle
@@ -765,7 +756,7 @@ void ba_schur_invalidate(pcd_ba* b) { if (b->schur) b->schur->num.valid = false;
 void ba_schur_drop_structure(pcd_ba* b) {
   if (!b->schur) return;
   b->schur->num.valid = false;
-  b->schur->st.built = false;   // schur_build assigns every member of the structure anew
+  b->schur->st.built = false;   // the build assigns every member of the structure anew
 }
 
 }  // namespace pcd
@@ -785,143 +776,20 @@ static pcd_status schur_guard(pcd_ba* b) {
   return PCD_OK;
 }
 
-// Slots, the per-block entry lists and the inverse image-major permutation, by host counting sorts over index arrays
-// read back once.  Blocks: the ns diagonal blocks, then the pair blocks in ascending (i, j).  Entries (a, b) of a block:
-// a ascending (image-major position in image i), then b ascending (image j).  A diagonal block holds (a, a) and the
-// pairs of a point observed more than once in the image.  Only variable-pose observations of non-constant points
-// take part.  Every sum downstream runs in the order of these lists, so the stages below keep it to the entry.
-struct SchurIndex {   // what travels between the stages; e = image-major position, o = observation in the caller's order
-  std::vector<int32_t> opt; std::vector<uint32_t> iobs;   // read back: [O] point of o; o at e
-  std::vector<uint32_t> ist; std::vector<uint8_t> cpose, cpt;   // [I+1] first e of an image; [I], [P] the masks (0: none given)
-  std::vector<int32_t> slot_img, eslot, ept;   // [ns] image of a slot; [O] slot of e (-1: not eliminated) and its point
-  std::vector<uint32_t> pst, pli;              // [P+1] -> a point's eliminated observations, ascending e
-};
-struct SchurLists {   // what schur_upload sends: [O] e of observation o, the identity; entries; row lists; [nblk+1]
-  std::vector<uint32_t> obs_pos, iota, ea, eb, rst, rblk, rcol; std::vector<uint64_t> blk;
-};
-
-static pcd_status schur_read_back(const pcd_ba* b, SchurIndex& x) {
-  const uint64_t O = b->O;
-  x.opt.resize(O); x.iobs.resize(O); x.ist.resize((size_t)b->I + 1); x.cpose.assign(b->I, 0); x.cpt.assign(b->P, 0);
-  if (O) {
-    PCD_HIP_TRY(hipMemcpy(x.opt.data(), b->obs_point.p, O * sizeof(int32_t), hipMemcpyDeviceToHost));
-    PCD_HIP_TRY(hipMemcpy(x.iobs.data(), b->img_obs.p, O * sizeof(uint32_t), hipMemcpyDeviceToHost));
+// The co-visibility structure, if the handle has none (after pcd_ba_create, or after an edit dropped it): built on the
+// device, on the stream of the call that needs it (ba_schur_structure.hip).  A capturing stream is refused before
+// anything is allocated.  info (may be null): what the build did; build_ms 0 when there was nothing to build.
+static pcd_status schur_build(pcd_ba* b, hipStream_t s, pcd_ba_schur_build_info* info = nullptr) {
+  if (!b->schur || !b->schur->st.built) {
+    PCD_TRY(refuse_capture(s, "pcd_ba_schur* (structure build)"));
+    if (!b->schur) b->schur.reset(new BaSchur());
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    int syncs = 0;
+    PCD_TRY(schur_structure_build(b, b->schur->st, s, &syncs));
+    if (info) { info->build_ms = b->schur->st.build_ms; info->num_syncs = syncs; }
   }
-  PCD_HIP_TRY(hipMemcpy(x.ist.data(), b->img_obs_start.p, x.ist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  if (b->const_poses()) PCD_HIP_TRY(hipMemcpy(x.cpose.data(), b->const_poses(), b->I, hipMemcpyDeviceToHost));
-  if (b->const_points()) PCD_HIP_TRY(hipMemcpy(x.cpt.data(), b->const_points(), b->P, hipMemcpyDeviceToHost));
-  return PCD_OK;
-}
-
-static void schur_assign_slots(SchurIndex& x, std::vector<int32_t>& h_slot, SchurLists& l) {
-  const int I = (int)x.cpose.size(); const size_t O = x.opt.size();
-  h_slot.assign(I, -1);
-  for (int i = 0; i < I; ++i)
-    if (!x.cpose[i]) { h_slot[i] = (int32_t)x.slot_img.size(); x.slot_img.push_back(i); }
-  x.eslot.resize(O); x.ept.resize(O); l.obs_pos.resize(O); l.iota.resize(O);
-  for (int i = 0; i < I; ++i)
-    for (uint32_t e = x.ist[i]; e < x.ist[i + 1]; ++e) {
-      const uint32_t o = x.iobs[e];
-      l.obs_pos[o] = e; l.iota[e] = e; x.ept[e] = x.opt[o];
-      x.eslot[e] = x.cpt[x.opt[o]] ? -1 : h_slot[i];   // -1: takes no part in the elimination
-    }
-}
-
-static void schur_point_lists(int P, SchurIndex& x) {
-  const size_t O = x.eslot.size();
-  x.pst.assign((size_t)P + 1, 0);
-  for (size_t e = 0; e < O; ++e) if (x.eslot[e] >= 0) x.pst[(size_t)x.ept[e] + 1]++;
-  for (int p = 0; p < P; ++p) x.pst[p + 1] += x.pst[p];
-  x.pli.resize(x.pst[P]);
-  std::vector<uint32_t> cur(x.pst.begin(), x.pst.end() - 1);
-  for (size_t e = 0; e < O; ++e) if (x.eslot[e] >= 0) x.pli[cur[x.ept[e]]++] = (uint32_t)e;
-}
-
-// The walk all three block passes make: every eliminated observation e of slot s (ascending) against every entry of its
-// point's list (ascending) -> f(e, the partner's position, the partner's slot)
-template <typename F>
-static inline void schur_walk_row(const SchurIndex& x, int s, F&& f) {
-  const int32_t* eslot = x.eslot.data(); const int32_t* ept = x.ept.data();
-  const uint32_t* pst = x.pst.data(); const uint32_t* pli = x.pli.data();
-  const int im = x.slot_img[s];
-  for (uint32_t e = x.ist[im], end = x.ist[im + 1]; e < end; ++e) {
-    if (eslot[e] < 0) continue;
-    for (uint32_t k = pst[ept[e]], kend = pst[ept[e] + 1]; k < kend; ++k) f(e, pli[k], (int)eslot[pli[k]]);
-  }
-}
-
-static void schur_diag_blocks(const SchurIndex& x, SchurLists& l) {
-  l.blk.assign(1, 0);
-  for (int s = 0; s < (int)x.slot_img.size(); ++s) {
-    schur_walk_row(x, s, [&](uint32_t e, uint32_t f, int j) { if (j == s) { l.ea.push_back(e); l.eb.push_back(f); } });
-    l.blk.push_back(l.ea.size());
-  }
-}
-
-// pair blocks of row s behind the diagonal blocks: a per-row counting sort over the partner slot j > s
-static void schur_pair_blocks(const SchurIndex& x, std::vector<int32_t>& pair_i, std::vector<int32_t>& pair_j, SchurLists& l) {
-  const int ns = (int)x.slot_img.size();
-  pair_i.clear(); pair_j.clear();
-  std::vector<uint32_t> cnt(ns, 0); std::vector<uint64_t> cur(ns, 0); std::vector<int> touched;
-  for (int s = 0; s < ns; ++s) {
-    touched.clear();
-    schur_walk_row(x, s, [&](uint32_t, uint32_t, int j) { if (j > s && cnt[j]++ == 0) touched.push_back(j); });
-    std::sort(touched.begin(), touched.end());
-    uint64_t off = l.ea.size();
-    for (int j : touched) { cur[j] = off; off += cnt[j]; pair_i.push_back(s); pair_j.push_back(j); l.blk.push_back(off); }
-    l.ea.resize(off); l.eb.resize(off);
-    schur_walk_row(x, s, [&](uint32_t e, uint32_t f, int j) { if (j > s) { l.ea[cur[j]] = e; l.eb[cur[j]++] = f; } });
-    for (int j : touched) cnt[j] = 0;
-  }
-}
-
-// row lists of the product: transposes of the (k, s) blocks (k ascending), the diagonal, the (s, j) blocks
-static void schur_row_lists(int ns, const std::vector<int32_t>& pair_i, const std::vector<int32_t>& pair_j, SchurLists& l) {
-  const size_t npairs = pair_i.size();
-  l.rst.assign((size_t)ns + 1, 0);
-  for (int s = 0; s < ns; ++s) l.rst[(size_t)s + 1] = 1;
-  for (size_t q = 0; q < npairs; ++q) { l.rst[(size_t)pair_i[q] + 1]++; l.rst[(size_t)pair_j[q] + 1]++; }
-  for (int s = 0; s < ns; ++s) l.rst[(size_t)s + 1] += l.rst[s];
-  l.rblk.resize(l.rst[ns]); l.rcol.resize(l.rst[ns]);
-  std::vector<uint32_t> pos(l.rst.begin(), l.rst.end() - 1);
-  auto put = [&](int row, size_t blk, uint32_t col) { const uint32_t t = pos[row]++; l.rblk[t] = (uint32_t)blk; l.rcol[t] = col; };
-  for (size_t q = 0; q < npairs; ++q) put(pair_j[q], ns + q, ((uint32_t)pair_i[q] << 1) | 1u);
-  for (int s = 0; s < ns; ++s) put(s, s, (uint32_t)s << 1);
-  for (size_t q = 0; q < npairs; ++q) put(pair_i[q], ns + q, (uint32_t)pair_j[q] << 1);
-}
-
-static pcd_status schur_upload(BaSchur::Structure& T, const SchurIndex& x, const SchurLists& l) {
-  const std::vector<uint32_t> blk32(l.blk.begin(), l.blk.end()); std::vector<uint32_t> pij(2 * T.npairs);
-  for (uint64_t q = 0; q < T.npairs; ++q) { pij[2 * q] = (uint32_t)T.h_pair_i[q]; pij[2 * q + 1] = (uint32_t)T.h_pair_j[q]; }
-  auto up = [](auto& buf, const auto& v) { return upload(buf, v.data(), v.size()); };
-  PCD_TRY(up(T.img_slot, T.h_slot)); PCD_TRY(up(T.slot_img, x.slot_img)); PCD_TRY(up(T.blk_start, blk32));
-  PCD_TRY(up(T.ent_a, l.ea)); PCD_TRY(up(T.ent_b, l.eb)); PCD_TRY(up(T.pair_ij, pij));
-  PCD_TRY(up(T.iota, l.iota)); PCD_TRY(up(T.obs_pos, l.obs_pos));
-  PCD_TRY(up(T.row_start, l.rst)); PCD_TRY(up(T.row_blk, l.rblk)); PCD_TRY(up(T.row_col, l.rcol));
-  return PCD_OK;
-}
-
-static pcd_status schur_build(pcd_ba* b) {
-  if (!b->schur) b->schur.reset(new BaSchur());
-  BaSchur::Structure& T = b->schur->st;
-  if (T.built) return PCD_OK;
-  const auto t0 = std::chrono::steady_clock::now();
-  SchurIndex x; SchurLists l;
-  PCD_TRY(schur_read_back(b, x));
-  schur_assign_slots(x, T.h_slot, l);
-  T.ns = (int)x.slot_img.size();
-  schur_point_lists(b->P, x);
-  schur_diag_blocks(x, l);
-  schur_pair_blocks(x, T.h_pair_i, T.h_pair_j, l);
-  if (l.ea.size() >= 0xFFFFFFF0ull || l.blk.size() >= 0xFFFFFFF0ull) {
-    set_error("point elimination: %zu block entries exceed the 32-bit layout", l.ea.size());
-    return PCD_ERR_UNSUPPORTED;
-  }
-  T.npairs = T.h_pair_i.size(); T.nent = l.ea.size();
-  schur_row_lists(T.ns, T.h_pair_i, T.h_pair_j, l);
-  PCD_TRY(schur_upload(T, x, l));
-  T.built = true;
-  T.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const BaSchur::Structure& T = b->schur->st;
+  if (info) { info->num_slots = T.ns; info->num_pairs = T.npairs; info->num_entries = T.nent; }
   return PCD_OK;
 }
 
@@ -1151,12 +1019,44 @@ extern "C" {
 pcd_status pcd_ba_schur_structure(pcd_ba* b, int32_t* image_slot, int32_t* num_slots, uint64_t* num_pairs,
                                   int32_t* pair_i, int32_t* pair_j) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b)); PCD_TRY(schur_build(b));
+    PCD_TRY(schur_guard(b)); PCD_TRY(schur_build(b, nullptr));
     const BaSchur::Structure& T = b->schur->st;
-    if (image_slot) std::memcpy(image_slot, T.h_slot.data(), (size_t)b->I * sizeof(int32_t));
+    PCD_HIP_TRY(hipDeviceSynchronize());   // the tail of a build is enqueued, not waited for
+    PCD_TRY(copy_back(image_slot, T.img_slot, (size_t)b->I));
     if (num_slots) *num_slots = T.ns; if (num_pairs) *num_pairs = T.npairs;
-    if (pair_i && T.npairs) std::memcpy(pair_i, T.h_pair_i.data(), T.npairs * sizeof(int32_t));
-    if (pair_j && T.npairs) std::memcpy(pair_j, T.h_pair_j.data(), T.npairs * sizeof(int32_t));
+    if ((pair_i || pair_j) && T.npairs) {   // on demand: the interleaved device list, split here
+      std::vector<uint32_t> ij(2 * T.npairs);
+      PCD_TRY(copy_back(ij.data(), T.pair_ij, ij.size()));
+      for (uint64_t q = 0; q < T.npairs; ++q) {
+        if (pair_i) pair_i[q] = (int32_t)ij[2 * q];
+        if (pair_j) pair_j[q] = (int32_t)ij[2 * q + 1];
+      }
+    }
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_build_device(pcd_ba* b, void* stream, pcd_ba_schur_build_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    if (info) std::memset(info, 0, sizeof *info);
+    PCD_TRY(schur_guard(b));
+    PCD_REFUSE_CAPTURE(stream);
+    return schur_build(b, (hipStream_t)stream, info);
+  });
+}
+
+pcd_status pcd_ba_schur_structure_lists(pcd_ba* b, const pcd_ba_schur_lists* o) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_guard(b)); PCD_REQUIRE(o, "null pointer");
+    PCD_TRY(schur_build(b, nullptr));
+    const BaSchur::Structure& T = b->schur->st;
+    const size_t ns = (size_t)T.ns, nrow = ns + 2 * T.npairs;
+    PCD_HIP_TRY(hipDeviceSynchronize());   // a build on another stream may still be running
+    PCD_TRY(copy_back(o->slot_image, T.slot_img, ns)); PCD_TRY(copy_back(o->obs_pos, T.obs_pos, b->O));
+    PCD_TRY(copy_back(o->blk_start, T.blk_start, (size_t)T.nblk() + 1));
+    PCD_TRY(copy_back(o->ent_a, T.ent_a, T.nent)); PCD_TRY(copy_back(o->ent_b, T.ent_b, T.nent));
+    PCD_TRY(copy_back(o->pair_ij, T.pair_ij, 2 * T.npairs)); PCD_TRY(copy_back(o->row_start, T.row_start, ns + 1));
+    PCD_TRY(copy_back(o->row_blk, T.row_blk, nrow)); PCD_TRY(copy_back(o->row_col, T.row_col, nrow));
     return PCD_OK;
   });
 }
@@ -1164,9 +1064,10 @@ pcd_status pcd_ba_schur_structure(pcd_ba* b, int32_t* image_slot, int32_t* num_s
 pcd_status pcd_ba_schur_stats(pcd_ba* b, pcd_ba_schur_info* info) {
   PCD_TRY(schur_guard(b)); PCD_REQUIRE(info, "null pointer");
   std::memset(info, 0, sizeof *info);
-  if (!b->schur || !b->schur->st.built) return PCD_OK;
+  if (!b->schur) return PCD_OK;
+  info->scratch_bytes = b->schur->device_bytes();   // what the handle holds, built or not (an edit keeps the buffers)
+  if (!b->schur->st.built) return PCD_OK;
   info->build_ms = b->schur->st.build_ms; info->num_entries = b->schur->st.nent;
-  info->scratch_bytes = b->schur->device_bytes();
   return PCD_OK;
 }
 
@@ -1177,9 +1078,9 @@ pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pc
     PCD_REQUIRE(opt->damping == PCD_DAMP_MARQUARDT || opt->damping == PCD_DAMP_LEVENBERG, "damping");
     PCD_REQUIRE(opt->mu >= 0.0, "mu must be >= 0");
     PCD_REFUSE_CAPTURE(stream);
-    PCD_TRY(schur_build(b));
-    const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
     hipStream_t s = (hipStream_t)stream;
+    PCD_TRY(schur_build(b, s));
+    const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
     const int I = b->I, P = b->P, ns = T.ns;
     const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));   // grid of k_schur_points = length of its partials
     N.valid = false;
@@ -1220,7 +1121,7 @@ pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pc
 pcd_status pcd_ba_schur(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o) {
   return pcd::guard([&]() -> pcd_status {
     PCD_TRY(schur_guard(b)); PCD_REQUIRE(opt && o, "null pointer");
-    PCD_TRY(schur_build(b));
+    PCD_TRY(schur_build(b, nullptr));
     const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
     const size_t n = slot_vec(T.ns);
     pcd_ba_schur_out d{};
@@ -1259,7 +1160,7 @@ pcd_status pcd_ba_plus_device(pcd_ba* b, const double* d_dpose, const double* d_
   return pcd::guard([&]() -> pcd_status {
     PCD_TRY(schur_guard(b));
     PCD_REFUSE_CAPTURE(stream);
-    PCD_TRY(schur_build(b));
+    PCD_TRY(schur_build(b, (hipStream_t)stream));
     // zero-length arrays may be NULL (ns = 0 when every pose is constant)
     PCD_REQUIRE((d_dpose || b->schur->st.ns == 0) && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) &&
                 (d_points_out || b->P == 0), "null pointer");
@@ -1318,7 +1219,7 @@ pcd_status pcd_ba_schur_solve_cholesky_device(pcd_ba* b, const double* d_S, cons
     PCD_TRY(schur_guard(b));
     PCD_REQUIRE(!d_S == !d_rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
     PCD_REFUSE_CAPTURE(stream);
-    if (d_S) PCD_TRY(schur_build(b));
+    if (d_S) PCD_TRY(schur_build(b, (hipStream_t)stream));
     else PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_cholesky_device", true));
     const int ns = b->schur->st.ns;
     PCD_REQUIRE(d_dpose || ns == 0, "null pointer");
@@ -1343,7 +1244,7 @@ pcd_status pcd_ba_schur_solve_cholesky(pcd_ba* b, const double* Sh, const double
   return pcd::guard([&]() -> pcd_status {
     PCD_TRY(schur_guard(b));
     PCD_REQUIRE(!Sh == !rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
-    if (Sh) PCD_TRY(schur_build(b));
+    if (Sh) PCD_TRY(schur_build(b, nullptr));
     else PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_cholesky", true));
     BaSchur::Chol& K = b->schur->chol;
     const size_t n = slot_vec(b->schur->st.ns);
@@ -1381,7 +1282,7 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
     PCD_TRY(schur_guard(b)); PCD_TRY(lm_check_opts(opts));
     hipStream_t s = nullptr;
     PCD_REFUSE_CAPTURE(s);
-    PCD_TRY(schur_build(b));
+    PCD_TRY(schur_build(b, s));
     BaSchur& S = *b->schur; BaSchur::Lm& M = S.lm;
     const auto t0 = std::chrono::steady_clock::now();
     const unsigned ngp = std::max(1u, std::min(1024u, div_up((uint64_t)S.st.ns + b->P, 256)));

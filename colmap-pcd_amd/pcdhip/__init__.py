@@ -114,6 +114,18 @@ class BASchurInfo(C.Structure):
     _fields_ = [("build_ms", C.c_double), ("num_entries", C.c_uint64), ("scratch_bytes", C.c_uint64)]
 
 
+class BASchurBuildInfo(C.Structure):
+    _fields_ = [("build_ms", C.c_double), ("num_slots", C.c_int32), ("num_syncs", C.c_int32), ("num_pairs", C.c_uint64),
+                ("num_entries", C.c_uint64)]
+
+
+_SCHUR_LISTS = ("slot_image", "obs_pos", "blk_start", "ent_a", "ent_b", "pair_ij", "row_start", "row_blk", "row_col")
+
+
+class BASchurLists(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _SCHUR_LISTS]
+
+
 PRECOND_IDENTITY, PRECOND_SCHUR_JACOBI = 0, 1
 _PRECOND = {"identity": PRECOND_IDENTITY, "schur_jacobi": PRECOND_SCHUR_JACOBI}
 PCG_MAX_ITERATIONS, PCG_Q_TOLERANCE, PCG_R_TOLERANCE, PCG_BREAKDOWN, PCG_ZERO_RHS = range(5)
@@ -284,6 +296,7 @@ ABI_SYMBOLS = [
     "pcd_proj_set_new_images_device", "pcd_ba_proj_opts_default", "pcd_ba_project_lidar_device",
     "pcd_ba_filter_opts_default", "pcd_ba_filter_points_device", "pcd_ba_filter_points",
     "pcd_ba_remove_observations_device",
+    "pcd_ba_schur_build_device", "pcd_ba_schur_structure_lists",
 ]
 
 
@@ -385,6 +398,9 @@ def lib():
         L.pcd_ba_solve_opts_default.argtypes = [C.POINTER(BASolveOpts)]
         L.pcd_ba_solve_opts_default.restype = None
         L.pcd_ba_solve.argtypes = [C.c_void_p, C.POINTER(BASolveOpts), C.POINTER(BASolveSummary), C.c_void_p]
+    if hasattr(L, "pcd_ba_schur_build_device"):
+        L.pcd_ba_schur_build_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BASchurBuildInfo)]
+        L.pcd_ba_schur_structure_lists.argtypes = [C.c_void_p, C.POINTER(BASchurLists)]
     if hasattr(L, "pcd_ba_schur_solve_cholesky_device"):
         L.pcd_ba_schur_solve_cholesky_device.argtypes = [C.c_void_p] * 6
         L.pcd_ba_schur_solve_cholesky.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1331,6 +1347,31 @@ class BA:
         _check(L.pcd_ba_schur_structure(self._h, _vp(slot), C.byref(ns), C.byref(npair), _vp(pi), _vp(pj)))
         n = npair.value
         return dict(image_slot=slot, num_slots=ns.value, pairs=np.stack([pi[:n], pj[:n]], axis=1))
+
+    def schur_build(self, stream=None):
+        """pcd_ba_schur_build_device: builds the co-visibility structure now, on the device, if the handle has none (a
+        fresh handle, or one whose observations remove_observations changed).  stream: a torch stream (None: the current
+        one).  Returns dict(build_ms (0: already built), num_slots, num_syncs, num_pairs, num_entries)."""
+        cur = self._torch()[2]
+        info = BASchurBuildInfo()
+        _check(lib().pcd_ba_schur_build_device(self._h, C.c_void_p(cur if stream is None else stream.cuda_stream),
+                                               C.byref(info)))
+        self._schur_dims = (int(info.num_slots), int(info.num_pairs))
+        return {k: getattr(info, k) for k, _ in BASchurBuildInfo._fields_}
+
+    def schur_lists(self):
+        """pcd_ba_schur_structure_lists: every list of the co-visibility structure as numpy arrays (slot_image int32, the
+        rest uint32; the layout is the header's), with the counts num_slots, num_pairs, num_entries"""
+        info = BASchurBuildInfo()
+        _check(lib().pcd_ba_schur_build_device(self._h, None, C.byref(info)))
+        ns, npair, nent = int(info.num_slots), int(info.num_pairs), int(info.num_entries)
+        size = dict(slot_image=ns, obs_pos=self.O, blk_start=ns + npair + 1, ent_a=nent, ent_b=nent, pair_ij=2 * npair,
+                    row_start=ns + 1, row_blk=ns + 2 * npair, row_col=ns + 2 * npair)
+        out = {k: np.zeros(size[k], np.int32 if k == "slot_image" else np.uint32) for k in _SCHUR_LISTS}
+        o = BASchurLists(*[_vp(out[k]) if size[k] else None for k in _SCHUR_LISTS])
+        _check(lib().pcd_ba_schur_structure_lists(self._h, C.byref(o)))
+        out.update(num_slots=ns, num_pairs=npair, num_entries=nent)
+        return out
 
     def schur_stats(self):
         i = BASchurInfo()

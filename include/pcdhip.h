@@ -706,7 +706,8 @@ pcd_status pcd_ba_set_parameters_device(pcd_ba* ba, const double* d_poses, const
  * Guards of every entry point below, before anything is allocated or launched: no gfx950 device -> NO_DEVICE; a
  * capturing stream -> UNSUPPORTED (as every _device call); a handle with some camera_refine byte set -> UNSUPPORTED
  * (the camera rows are not part of the reduced system).  All scratch is owned by the handle (freed by
- * pcd_ba_destroy); the co-visibility structure is built on the first call (host counting sorts, build_ms). */
+ * pcd_ba_destroy); the co-visibility structure is built on the first call and again after an edit dropped it, on the
+ * device and on the stream of the call that needs it (the host forms: the legacy stream; build_ms). */
 typedef enum { PCD_DAMP_MARQUARDT = 0, PCD_DAMP_LEVENBERG = 1 } pcd_ba_damping;
 typedef struct {
   double mu;          /* >= 0 */
@@ -742,11 +743,33 @@ pcd_status pcd_ba_schur_back_substitute_device(pcd_ba* ba, const double* d_dpose
 pcd_status pcd_ba_plus_device(pcd_ba* ba, const double* d_dpose /*[ns][6]*/, const double* d_dpoint /*[P][3]*/,
                               double* d_poses_out /*[I][7]*/, double* d_points_out /*[P][3]*/, void* stream);
 typedef struct {
-  double build_ms;          /* host time of the structure build (0: not built yet) */
+  double build_ms;          /* wall time of the structure build (0: not built yet) */
   uint64_t num_entries;     /* (a, b) observation pairs of all blocks              */
   uint64_t scratch_bytes;   /* device memory the elimination holds in the handle   */
 } pcd_ba_schur_info;
 pcd_status pcd_ba_schur_stats(pcd_ba* ba, pcd_ba_schur_info* info);
+/* The co-visibility structure, built explicitly: sorts, scans and a load-balanced expansion over the
+ * handle's own device arrays, no atomics, bitwise the same lists on every build.  Nothing of the size of the
+ * observations or the entries crosses PCIe; the stream is synchronised at most twice (the slot and entry counts, which
+ * size the entry buffers, then the pair count).  More than 2^32 - 16 entries or blocks -> UNSUPPORTED, decided from
+ * the 64-bit count before an entry buffer exists; the handle stays usable for everything else. */
+typedef struct {
+  double build_ms;                 /* wall time of the build, its synchronisations included (0: already built) */
+  int32_t num_slots, num_syncs;    /* stream synchronisations the build made */
+  uint64_t num_pairs, num_entries;
+} pcd_ba_schur_build_info;
+/* builds the structure now, on `stream`, if the handle has none (after pcd_ba_create, or after an edit dropped it) */
+pcd_status pcd_ba_schur_build_device(pcd_ba* ba, void* stream, pcd_ba_schur_build_info* info /*may be NULL*/);
+/* The structure's lists, device -> host (built first, on the legacy stream, if the handle has none).  Every pointer may
+ * be NULL.  With ns = num_slots, nblk = ns + num_pairs: slot_image [ns]; obs_pos [O] image-major position of every
+ * observation; blk_start [nblk + 1] (the ns diagonal blocks, then the pair blocks in ascending (i, j)); ent_a, ent_b
+ * [num_entries] image-major positions, ascending (a, b) within a block; pair_ij [2 num_pairs]; row_start [ns + 1],
+ * row_blk / row_col [ns + 2 num_pairs]: per slot s the transposed (k, s) blocks in ascending k (col = k << 1 | 1), the
+ * diagonal block (col = s << 1), the (s, j) blocks in ascending j (col = j << 1). */
+typedef struct {
+  int32_t* slot_image; uint32_t *obs_pos, *blk_start, *ent_a, *ent_b, *pair_ij, *row_start, *row_blk, *row_col;
+} pcd_ba_schur_lists;
+pcd_status pcd_ba_schur_structure_lists(pcd_ba* ba, const pcd_ba_schur_lists* out);
 
 /* Reduced camera system on the device: block-sparse preconditioned conjugate gradients on S dpose = rhs of the LAST
  * Schur call on the handle, read from the handle's own S_diag / S_off / rhs (INVALID, with a message that says which,

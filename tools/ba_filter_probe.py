@@ -10,10 +10,10 @@ loses them:
   host route     what the library offered before pcd_ba_remove_observations_device: the flags copied to the host, the
                  observation arrays compacted there (numpy), the handle destroyed, pcd_ba_create on the compacted problem
                  (every observation uploaded, track CSR / sliced ELL / image-major order / pose rows rebuilt by host
-                 counting sorts), then the structure build of the first Schur call (pcd_ba_schur_structure).
+                 counting sorts), then the structure build of the first Schur call (pcd_ba_schur_build_device).
   device route   pcd_ba_remove_observations_device on the live handle (rebuild_ms as the call reports it, and the call's
                  wall time), then the same structure build, which both routes need: the structure depends on the
-                 observations.
+                 observations.  The build runs on the device; its stream synchronisations are reported.
 
 The probe also times pcd_ba_filter_points_device beside pcd_ba_filter_tracks_device on the full handle.
 Medians of --reps after one warm-up; wall times with the device idle before and after."""
@@ -103,7 +103,7 @@ def main():
         d_erase = torch.from_numpy(erase).to(dev)
         h = dict(d2h_compact=[], create=[], structure=[], total=[])
         d = dict(rebuild=[], wall=[], structure=[], total=[])
-        kept = 0
+        kept = syncs = 0
         for rep in range(a.reps + 1):
             ba = pcdhip.BA(**scene)
             ba.schur_structure()
@@ -119,7 +119,9 @@ def main():
                 ba.close()
                 return pcdhip.BA(**dict(new, poses=poses, points=points))
             fresh, t_create = wall(recreate)
-            st_host, t_struct = wall(fresh.schur_structure)
+            b_host, t_struct = wall(fresh.schur_build)
+            st_host = fresh.schur_structure()
+            syncs = max(syncs, b_host["num_syncs"])
             kept = fresh.O
             fresh.close()
             if rep:
@@ -129,7 +131,9 @@ def main():
             ba = pcdhip.BA(**scene)
             ba.schur_structure()
             info, t_wall = wall(lambda: ba.remove_observations(d_erase))
-            st_dev, t_struct = wall(ba.schur_structure)
+            b_dev, t_struct = wall(ba.schur_build)
+            st_dev = ba.schur_structure()
+            syncs = max(syncs, b_dev["num_syncs"])
             assert ba.O == kept and np.array_equal(st_dev["pairs"], st_host["pairs"])
             ba.close()
             if rep:
@@ -140,6 +144,7 @@ def main():
             " | total %s ms" % (med(h["d2h_compact"]), med(h["create"]), med(h["structure"]), med(h["total"])))
         log("  device route: rebuild_ms %s | wall time of the call %s ms | Schur structure build %s ms | total %s ms"
             % (med(d["rebuild"]), med(d["wall"]), med(d["structure"]), med(d["total"])))
+        log("  structure builds: at most %d stream synchronisations each (num_syncs)" % syncs)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:

@@ -3,7 +3,7 @@
 
   python tools/ba_schur_probe.py [--out profiles/ba_solve_probe.txt] [--reps 15] [--only M|B]
 
-Parts: structure build (host counting sorts, once per handle), normal-equation pass, elimination, dense fill,
+Parts: structure build (on the device, once per handle and after every edit of the observations), normal-equation pass, elimination, dense fill,
 torch.linalg.cholesky + solve, back-substitution + plus, cost pass, a whole LM iteration of pcdhip.ba_solve_lm; then
 the block-sparse PCG beside the Cholesky (at the defaults and to r_tolerance 1e-10, each call with its one read of the
 record), the time per CG iteration, and a whole LM iteration through pcd_ba_solve; then the library's own blocked
@@ -68,13 +68,27 @@ def probe(tag, reps, log):
     scene = synth.ba_scene(cams, pts, seed=11, order="image")
     ba = pcdhip.BA(**scene)
     log("== %s: %d images, %d points, %d observations, %d LiDAR terms" % (tag, ba.I, ba.P, ba.O, ba.L))
+    torch.cuda.synchronize()
     t0 = time.perf_counter()
-    st = ba.schur_structure()
+    built = ba.schur_build()
+    torch.cuda.synchronize()
     wall = (time.perf_counter() - t0) * 1e3
+    st = ba.schur_structure()
     info = ba.schur_stats()
     ns, npair = st["num_slots"], len(st["pairs"])
-    log("structure build (host, once per handle): %.1f ms (library) / %.1f ms (call); %d slots, %d pairs, %d entries"
-        % (info["build_ms"], wall, ns, npair, info["num_entries"]))
+    log("structure build (device, once per handle): %.1f ms (library) / %.1f ms (call, device idle before and after); "
+        "%d stream synchronisations; %d slots, %d pairs, %d entries"
+        % (built["build_ms"], wall, built["num_syncs"], ns, npair, info["num_entries"]))
+    rebuilds = []
+    for _ in range(5):              # again, as after an edit: a no-op removal drops the structure, the scratch stays
+        ba.remove_observations(torch.zeros(ba.O, dtype=torch.uint8, device="cuda"))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        again = ba.schur_build()
+        torch.cuda.synchronize()
+        rebuilds.append((time.perf_counter() - t0) * 1e3)
+        assert again["num_syncs"] <= 2 and again["num_entries"] == built["num_entries"]
+    log("structure rebuild on the live handle (scratch kept):  %s" % stats(rebuilds))
     mu = 1e-4
     ba.schur(mu, dense=True)     # allocates the scratch
     torch.cuda.synchronize()
