@@ -16,6 +16,15 @@
 //   k_edit_record                        the counts the host reads (the ONE synchronisation), with img_obs_start
 // No atomics; nothing depends on the launch geometry.  The new layout is built in pcd_ba::edit_next, every buffer of it
 // reserved before the first launch, and swapped in at the end.
+//
+// pcd_ba_add_observations_device is the growing edit: rows and points appended.  Its passes:
+//   k_add_keys, sort_pairs               the new rows' keys (clamped, with the verdict on their range) sorted stably, once
+//                                        by point and once by image
+//   k_add_lower, k_add_starts            new rows in front of every key (a lower bound per key) -> the new CSR bounds
+//   k_add_move_old / k_add_place_new     old list entries shifted, new ones behind them in input order
+//   k_add_vflag, exclusive_sum, k_add_vobs   the packed pose rows, the new ones appended
+//   edit_derive                          the tail both edits share: lengths, length sort, slices, segments, k_lidar_tracks
+//   k_add_record                         verdict and counts (the ONE synchronisation); the two fills follow it
 #include "ba_handle.h"
 #include "prim.h"
 
@@ -180,6 +189,39 @@ static pcd_status scan_flags(BaEditScratch& N, const uint32_t* flag, uint32_t* p
   return exclusive_sum(N.prim, flag, pos, 0u, n, s);
 }
 
+// The LiDAR terms the derived layouts follow (start null: the handle has none)
+struct EditTerms { const uint32_t* start; const uint32_t* list; const double* abcd; const double* w; };
+
+// What both edits derive from the new CSRs in N (pt_obs_start / pt_obs_list, img_obs_start) and the new rows (obs_image,
+// obs_xy): the tracks in order of length (pt_order, slice_start), the sliced-ELL copies (fill_sell: when they are
+// reserved already), the segments of the images and the terms of every track in the new thread order.  P, nslices and O
+// are those of the new layout; O only bounds a track's length.
+static pcd_status edit_derive(BaEditScratch& N, uint32_t P, uint32_t I, uint32_t nslices, uint64_t O, bool fill_sell,
+                              const EditTerms& terms, hipStream_t s) {
+  auto grid = [](uint64_t n) { return dim3(div_up(n, 256)); };
+  const uint32_t ntr = nslices * 64u;
+  // tracks in ascending order of length, ties in ascending point id; a length is below 2^length_bits(O)
+  hipLaunchKernelGGL(k_edit_lengths, grid(P), dim3(256), 0, s, P, N.pt_obs_start.p, N.len.p, N.iota.p);
+  PCD_TRY(sort_pairs(N.prim, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(N.pt_order.p), (size_t)P, 0u,
+                     length_bits(O), s));
+  hipLaunchKernelGGL(k_edit_slice_width, grid(std::max<uint64_t>(ntr, (uint64_t)nslices + 1)), dim3(256), 0, s, P, nslices,
+                     N.len_sorted.p, N.pt_order.p, N.width.p);
+  PCD_TRY(scan_flags(N, N.width.p, N.slice_start.p, (size_t)nslices + 1, s));
+  if (fill_sell)
+    hipLaunchKernelGGL(k_ba_fill_sell, grid(ntr), dim3(256), 0, s, N.pt_order.p, N.slice_start.p, N.pt_obs_start.p,
+                       N.pt_obs_list.p, N.obs_image.p, N.obs_xy.p, (int)nslices, N.sell_img.p, N.sell_xy.p);
+  // segments of the images
+  hipLaunchKernelGGL(k_edit_seg_count, grid((uint64_t)I + 1), dim3(256), 0, s, I, N.img_obs_start.p, N.seg_cnt.p);
+  PCD_TRY(scan_flags(N, N.seg_cnt.p, N.img_seg_start.p, (size_t)I + 1, s));
+  hipLaunchKernelGGL(k_edit_segs, grid((uint64_t)I + 1), dim3(256), 0, s, I, N.img_obs_start.p, N.img_seg_start.p,
+                     N.seg_img.p, N.seg_begin.p);
+  // the terms of every track in the new thread order
+  if (terms.start)
+    hipLaunchKernelGGL(k_lidar_tracks, grid(ntr), dim3(256), 0, s, ntr, N.pt_order.p, terms.start, terms.list, terms.abcd,
+                       terms.w, N.l_cnt.p, N.l_first.p);
+  return PCD_OK;
+}
+
 // Every buffer the rebuild writes, at the sizes of the handle as it is: nothing grows when rows are dropped, so nothing
 // is allocated after the first launch
 static pcd_status edit_reserve(pcd_ba* b) {
@@ -227,7 +269,7 @@ static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t*
                                pcd_ba_remove_info* info) {
   BaEditScratch& N = b->edit_next;
   const uint32_t O = (uint32_t)b->O, L = (uint32_t)b->L, P = (uint32_t)b->P, I = (uint32_t)b->I;
-  const uint32_t nslices = (uint32_t)b->nslices, ntr = nslices * 64u;
+  const uint32_t nslices = (uint32_t)b->nslices;
   PCD_TRY(edit_reserve(b));
   EventPair ev;
   if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
@@ -267,21 +309,8 @@ static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t*
     }
     hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)P + 1), dim3(256), 0, s, P, b->pt_obs_start.p, N.t_pos.p, N.pt_obs_start.p);
     hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)I + 1), dim3(256), 0, s, I, b->img_obs_start.p, N.i_pos.p, N.img_obs_start.p);
-    // tracks in ascending order of length, ties in ascending point id; a length is below 2^length_bits(O)
-    hipLaunchKernelGGL(k_edit_lengths, grid(P), dim3(256), 0, s, P, N.pt_obs_start.p, N.len.p, N.iota.p);
-    PCD_TRY(sort_pairs(N.prim, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(N.pt_order.p), (size_t)P, 0u,
-                       length_bits(O), s));
-    hipLaunchKernelGGL(k_edit_slice_width, grid(std::max<uint64_t>(ntr, (uint64_t)nslices + 1)), dim3(256), 0, s, P, nslices,
-                       N.len_sorted.p, N.pt_order.p, N.width.p);
-    PCD_TRY(scan_flags(N, N.width.p, N.slice_start.p, (size_t)nslices + 1, s));
-    hipLaunchKernelGGL(k_ba_fill_sell, grid(ntr), dim3(256), 0, s, N.pt_order.p, N.slice_start.p, N.pt_obs_start.p,
-                       N.pt_obs_list.p, N.obs_image.p, N.obs_xy.p, (int)nslices, N.sell_img.p, N.sell_xy.p);
-    // segments of the images
-    hipLaunchKernelGGL(k_edit_seg_count, grid((uint64_t)I + 1), dim3(256), 0, s, I, N.img_obs_start.p, N.seg_cnt.p);
-    PCD_TRY(scan_flags(N, N.seg_cnt.p, N.img_seg_start.p, (size_t)I + 1, s));
-    hipLaunchKernelGGL(k_edit_segs, grid((uint64_t)I + 1), dim3(256), 0, s, I, N.img_obs_start.p, N.img_seg_start.p,
-                       N.seg_img.p, N.seg_begin.p);
-    // the terms, their CSR, and those of every track in the new thread order
+    // the terms and their CSR
+    EditTerms terms{};
     if (L) {
       const bool meta = b->has_lidar_meta;
       hipLaunchKernelGGL(k_edit_compact_terms, grid(L), dim3(256), 0, s, L, N.lf.p, N.lp.p, b->lidar_point.p, b->lidar_abcd.p,
@@ -290,9 +319,9 @@ static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t*
       hipLaunchKernelGGL(k_edit_compact_list, grid(L), dim3(256), 0, s, L, b->pt_lidar_list.p, N.lt_flag.p, N.lt_pos.p, N.lp.p,
                          N.l_list.p);
       hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)P + 1), dim3(256), 0, s, P, b->pt_lidar_start.p, N.lt_pos.p, N.l_start.p);
-      hipLaunchKernelGGL(k_lidar_tracks, grid(ntr), dim3(256), 0, s, ntr, N.pt_order.p, N.l_start.p, N.l_list.p, N.l_abcd.p,
-                         N.l_w.p, N.l_cnt.p, N.l_first.p);
+      terms = EditTerms{N.l_start.p, N.l_list.p, N.l_abcd.p, N.l_w.p};
     }
+    PCD_TRY(edit_derive(N, P, I, nslices, O, /*fill_sell=*/true, terms, s));
     hipLaunchKernelGGL(k_edit_record, dim3(1), dim3(256), 0, s, O, L, I, P, N.pos.p, L ? N.lp.p : nullptr, N.img_seg_start.p,
                        vrows ? N.v_pos.p : nullptr, b->pt_obs_start.p, N.pt_obs_start.p, N.record.p);
     PCD_HIP_TRY(hipGetLastError());
@@ -341,6 +370,279 @@ static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t*
   return PCD_OK;
 }
 
+// ---- the addition ------------------------------------------------------------------------------------
+// In the concatenated order every new row has a larger index than every old row, so in the stable counting sort
+// pcd_ba_create does (build_csr) the old entries of a key keep their order and the new entries of the key follow them in
+// input order.  With the new rows sorted stably by key and add[k] = the new rows of keys below k:
+//   start'[k] = start[k] + add[k]                    (the old bound of a new key is O)
+//   old entry e of key k          -> e + add[k]
+//   sorted new row of rank r, key k -> start'[k] + oldlen[k] + (r - add[k]) = oldend[k] + r, and holds O + row
+enum { kAddBad = 0, kAddSegs, kAddPoseRows, kAddSlots, kAddWords };
+
+// key[r] of new row r, clamped into [0, nkeys): every later pass stays in bounds whatever the row holds.
+// bad[workgroup] = its rows out of range: the verdict, summed by k_add_record
+__global__ __launch_bounds__(256) void k_add_keys(uint32_t A, const int* __restrict__ in, uint32_t nkeys,
+                                                  uint32_t* __restrict__ key, uint32_t* __restrict__ iota,
+                                                  uint32_t* __restrict__ bad) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  int out = 0;
+  if (r < A) {
+    const int k = in[r];
+    out = (k < 0 || (uint32_t)k >= nkeys) ? 1 : 0;
+    key[r] = out ? 0u : (uint32_t)k;
+    iota[r] = r;
+  }
+  const int n = __syncthreads_count(out);
+  if (threadIdx.x == 0) bad[blockIdx.x] = (uint32_t)n;
+}
+// add[k] for k = 0 .. nkeys: the first sorted new row whose key is not below k (a lower bound: no histogram, no atomics)
+__global__ __launch_bounds__(256) void k_add_lower(uint32_t nkeys, uint32_t A, const uint32_t* __restrict__ sorted,
+                                                   uint32_t* __restrict__ add) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k > nkeys) return;
+  uint32_t lo = 0, hi = A;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (sorted[mid] < k) lo = mid + 1; else hi = mid;
+  }
+  add[k] = lo;
+}
+// start'[k] for k = 0 .. nnew; the old CSR has nold keys and n entries (its bound from nold on)
+__global__ __launch_bounds__(256) void k_add_starts(uint32_t nold, uint32_t nnew, uint32_t n, const uint32_t* __restrict__ old_start,
+                                                    const uint32_t* __restrict__ add, uint32_t* __restrict__ start) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k > nnew) return;
+  start[k] = (k <= nold ? old_start[k] : n) + add[k];
+}
+__global__ __launch_bounds__(256) void k_add_move_old(uint32_t O, const uint32_t* __restrict__ list, const int* __restrict__ key_of,
+                                                      const uint32_t* __restrict__ add, uint32_t* __restrict__ out) {
+  const uint32_t e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= O) return;
+  const uint32_t o = list[e];
+  out[e + add[key_of[o]]] = o;
+}
+__global__ __launch_bounds__(256) void k_add_place_new(uint32_t A, const uint32_t* __restrict__ sorted_key,
+                                                       const uint32_t* __restrict__ sorted_row, uint32_t nold,
+                                                       const uint32_t* __restrict__ old_start, uint32_t O,
+                                                       uint32_t* __restrict__ out) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= A) return;
+  const uint32_t k = sorted_key[r];
+  const uint32_t end = k < nold ? old_start[k + 1] : O;
+  out[end + r] = O + sorted_row[r];
+}
+// flag[r] = 1: new row r is on a variable-pose image (a row out of range counts as none: the call is refused anyway)
+__global__ __launch_bounds__(256) void k_add_vflag(uint32_t A, const int* __restrict__ obs_image, uint32_t I,
+                                                   const uint8_t* __restrict__ cpose, uint32_t* __restrict__ flag) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r > A) return;
+  uint32_t f = 0;
+  if (r < A) {
+    const int i = obs_image[r];
+    f = (i >= 0 && (uint32_t)i < I && !cpose[i]) ? 1u : 0u;
+  }
+  flag[r] = f;
+}
+// the packed pose rows: the old ones as they are (old null: every old observation had one, the identity), then the
+// flagged new rows
+__global__ __launch_bounds__(256) void k_add_vobs(uint32_t V, uint32_t A, uint32_t O, const uint32_t* __restrict__ old,
+                                                  const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
+                                                  uint32_t* __restrict__ vobs) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t < V) { vobs[t] = old ? old[t] : t; return; }
+  const uint32_t r = t - V;
+  if (r < A && flag[r]) vobs[V + pos[r]] = O + r;
+}
+__global__ __launch_bounds__(256) void k_add_extend(uint32_t nold, uint32_t nnew, uint32_t n, const uint32_t* __restrict__ old_start,
+                                                    uint32_t* __restrict__ start) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k > nnew) return;
+  start[k] = k <= nold ? old_start[k] : n;
+}
+// one workgroup: the verdict and the counts (integer sums: any order)
+__global__ __launch_bounds__(256) void k_add_record(uint32_t nbad, const uint32_t* __restrict__ bad, uint32_t I,
+                                                    const uint32_t* __restrict__ img_seg_start, uint32_t A, uint32_t V,
+                                                    const uint32_t* __restrict__ v_pos, uint32_t nslices,
+                                                    const uint32_t* __restrict__ slice_start, uint32_t* __restrict__ rec) {
+  uint32_t n = 0;
+  for (uint32_t k = threadIdx.x; k < nbad; k += 256) n += bad[k];
+  const int any = __syncthreads_or(n != 0);
+  if (threadIdx.x == 0) {
+    rec[kAddBad] = any ? 1u : 0u;
+    rec[kAddSegs] = img_seg_start[I];
+    rec[kAddPoseRows] = v_pos ? V + v_pos[A] : V + A;
+    rec[kAddSlots] = slice_start[nslices];
+  }
+}
+
+// One CSR of the grown handle (start [nnew + 1], list [O + A]) from the old one (nold keys) and the new rows' keys
+static pcd_status add_merge_csr(BaEditScratch& N, const int* d_key, uint32_t A, uint32_t nold, uint32_t nnew, uint32_t O,
+                                const uint32_t* old_start, const uint32_t* old_list, const int* old_key_of_obs,
+                                uint32_t* bad, uint32_t* start, uint32_t* list, hipStream_t s) {
+  auto grid = [](uint64_t n) { return dim3(div_up(n, 256)); };
+  if (A) {
+    hipLaunchKernelGGL(k_add_keys, grid(A), dim3(256), 0, s, A, d_key, nnew, N.a_key.p, N.a_iota.p, bad);
+    PCD_TRY(sort_pairs(N.prim, N.a_key.p, N.a_key_sorted.p, N.a_iota.p, N.a_row.p, (size_t)A, 0u, length_bits(nnew), s));
+  }
+  hipLaunchKernelGGL(k_add_lower, grid((uint64_t)nnew + 1), dim3(256), 0, s, nnew, A, N.a_key_sorted.p, N.a_add.p);
+  hipLaunchKernelGGL(k_add_starts, grid((uint64_t)nnew + 1), dim3(256), 0, s, nold, nnew, O, old_start, N.a_add.p, start);
+  if (O) hipLaunchKernelGGL(k_add_move_old, grid(O), dim3(256), 0, s, O, old_list, old_key_of_obs, N.a_add.p, list);
+  if (A) hipLaunchKernelGGL(k_add_place_new, grid(A), dim3(256), 0, s, A, N.a_key_sorted.p, N.a_row.p, nold, old_start, O, list);
+  return PCD_OK;
+}
+
+// segments of the grown handle at most: an image that gains a > 0 rows gains at most 1 + a / kImgSeg segments
+static size_t add_seg_bound(const pcd_ba* b, uint64_t A) {
+  return (size_t)b->nseg + (size_t)std::min<uint64_t>(A, (uint64_t)b->I) + (size_t)(A / kImgSeg);
+}
+
+// Every buffer whose size follows from the counts, before the first launch.  Buffers grow here, unlike in edit_reserve.
+static pcd_status add_reserve(pcd_ba* b, uint64_t A, uint64_t Pn) {
+  BaEditScratch& N = b->edit_next;
+  const size_t O2 = b->O + A, P2 = (size_t)b->P + Pn, I = (size_t)b->I, L = b->L;
+  const size_t ns2 = (P2 + 63) / 64, ntr2 = ns2 * 64, nseg = add_seg_bound(b, A), nb = div_up(A, 256);
+  PCD_TRY(N.obs_image.reserve(at_least_1(O2))); PCD_TRY(N.obs_point.reserve(at_least_1(O2)));
+  PCD_TRY(N.obs_xy.reserve(at_least_1(2 * O2)));
+  PCD_TRY(N.pt_obs_start.reserve(P2 + 1)); PCD_TRY(N.pt_obs_list.reserve(at_least_1(O2)));
+  PCD_TRY(N.pt_order.reserve(ntr2)); PCD_TRY(N.slice_start.reserve(ns2 + 1));
+  PCD_TRY(N.img_obs_start.reserve(I + 1)); PCD_TRY(N.img_obs.reserve(at_least_1(O2)));
+  PCD_TRY(N.img_pt.reserve(at_least_1(O2))); PCD_TRY(N.img_xy.reserve(std::max<size_t>(2 * O2, 2)));
+  PCD_TRY(N.seg_img.reserve(at_least_1(nseg))); PCD_TRY(N.seg_begin.reserve(nseg + 1)); PCD_TRY(N.img_seg_start.reserve(I + 1));
+  if (b->has_cpose) { PCD_TRY(N.vobs.reserve(at_least_1(O2))); PCD_TRY(N.v_flag.reserve(A + 1)); PCD_TRY(N.v_pos.reserve(A + 1)); }
+  PCD_TRY(N.len.reserve(P2)); PCD_TRY(N.len_sorted.reserve(P2)); PCD_TRY(N.iota.reserve(P2));
+  PCD_TRY(N.width.reserve(ns2 + 1)); PCD_TRY(N.seg_cnt.reserve(I + 1));
+  PCD_TRY(N.record.reserve(kAddWords)); PCD_TRY(N.h_record.reserve(kAddWords + I + 1));
+  PCD_TRY(N.l_start.reserve(P2 + 1));
+  if (L) { PCD_TRY(N.l_cnt.reserve(ntr2)); PCD_TRY(N.l_first.reserve(5 * ntr2)); }
+  if (Pn) {
+    PCD_TRY(N.points.reserve(3 * P2));
+    if (b->has_cpt) PCD_TRY(N.point_const.reserve(P2));
+  }
+  for (DevBuf<uint32_t>* d : {&N.a_key, &N.a_key_sorted, &N.a_iota, &N.a_row}) PCD_TRY(d->reserve(at_least_1(A)));
+  PCD_TRY(N.a_add.reserve(std::max(P2, I) + 1)); PCD_TRY(N.a_bad.reserve(at_least_1(2 * nb)));
+  // the cost partials of the grown handle, as pcd_ba_create sizes them
+  PCD_TRY(b->cost_partial.reserve((size_t)std::max(std::max(1u, div_up(ns2, 2)), cost_sweep_blocks(O2, L)) + 1));
+  // rocPRIM's storage: the largest need over every scan and sort below
+  size_t need = 0, bytes = 0;
+  for (size_t n : {(size_t)A + 1, ns2 + 1, I + 1}) {
+    PCD_HIP_TRY(exclusive_sum_at(nullptr, bytes, N.seg_cnt.p, N.img_seg_start.p, 0u, n, nullptr));
+    need = std::max(need, bytes);
+  }
+  PCD_HIP_TRY(sort_pairs_at(nullptr, bytes, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(N.pt_order.p), P2, 0u,
+                            length_bits(O2), nullptr));
+  need = std::max(need, bytes);
+  for (size_t nkeys : {P2, I}) {
+    if (!A) break;
+    PCD_HIP_TRY(sort_pairs_at(nullptr, bytes, N.a_key.p, N.a_key_sorted.p, N.a_iota.p, N.a_row.p, (size_t)A, 0u,
+                              length_bits(nkeys), nullptr));
+    need = std::max(need, bytes);
+  }
+  PCD_TRY(N.prim.reserve(need));
+  return PCD_OK;
+}
+
+static pcd_status add_rebuild(pcd_ba* b, const double* d_points, uint64_t Pn64, const int* d_image, const int* d_point,
+                              const double* d_xy, uint64_t A64, hipStream_t s, pcd_ba_add_info* info) {
+  BaEditScratch& N = b->edit_next;
+  const uint32_t O = (uint32_t)b->O, A = (uint32_t)A64, O2 = O + A, L = (uint32_t)b->L, I = (uint32_t)b->I;
+  const uint32_t P = (uint32_t)b->P, Pn = (uint32_t)Pn64, P2 = P + Pn, ns2 = (P2 + 63u) / 64u, V = (uint32_t)b->n_pose_rows;
+  const uint32_t nb = div_up(A, 256);
+  const bool vrows = b->has_cpose;
+  PCD_TRY(add_reserve(b, A, Pn));
+  EventPair ev;
+  if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
+  auto grid = [](uint64_t n) { return dim3(div_up(n, 256)); };
+  {
+    ScopedKernelTimer t("ba_add_merge", s);
+    // the rows and the points: the old ones, then the new ones
+    if (O) {
+      PCD_HIP_TRY(hipMemcpyAsync(N.obs_image.p, b->obs_image.p, (size_t)O * sizeof(int), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(N.obs_point.p, b->obs_point.p, (size_t)O * sizeof(int), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(N.obs_xy.p, b->obs_xy.p, 2 * (size_t)O * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    if (A) {
+      PCD_HIP_TRY(hipMemcpyAsync(N.obs_image.p + O, d_image, (size_t)A * sizeof(int), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(N.obs_point.p + O, d_point, (size_t)A * sizeof(int), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(N.obs_xy.p + 2 * (size_t)O, d_xy, 2 * (size_t)A * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    if (Pn) {
+      PCD_HIP_TRY(hipMemcpyAsync(N.points.p, b->points.p, 3 * (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(N.points.p + 3 * (size_t)P, d_points, 3 * (size_t)Pn * sizeof(double), hipMemcpyDeviceToDevice, s));
+      if (b->has_cpt) {
+        PCD_HIP_TRY(hipMemcpyAsync(N.point_const.p, b->point_const.p, (size_t)P, hipMemcpyDeviceToDevice, s));
+        PCD_HIP_TRY(hipMemsetAsync(N.point_const.p + P, 0, (size_t)Pn, s));
+      }
+    }
+    // the track CSR over P2 points and the image CSR
+    PCD_TRY(add_merge_csr(N, d_point, A, P, P2, O, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_point.p, N.a_bad.p,
+                          N.pt_obs_start.p, N.pt_obs_list.p, s));
+    PCD_TRY(add_merge_csr(N, d_image, A, I, I, O, b->img_obs_start.p, b->img_obs.p, b->obs_image.p, N.a_bad.p + nb,
+                          N.img_obs_start.p, N.img_obs.p, s));
+    if (vrows) {
+      hipLaunchKernelGGL(k_add_vflag, grid((uint64_t)A + 1), dim3(256), 0, s, A, d_image, I, b->image_const_pose.p, N.v_flag.p);
+      PCD_TRY(scan_flags(N, N.v_flag.p, N.v_pos.p, (size_t)A + 1, s));
+      if (V + A)
+        hipLaunchKernelGGL(k_add_vobs, grid((uint64_t)V + A), dim3(256), 0, s, V, A, O, V == O ? nullptr : b->vobs.p,
+                           N.v_flag.p, N.v_pos.p, N.vobs.p);
+    }
+    // the terms stay; their CSR covers the new points, which have none
+    hipLaunchKernelGGL(k_add_extend, grid((uint64_t)P2 + 1), dim3(256), 0, s, P, P2, L, b->pt_lidar_start.p, N.l_start.p);
+  }
+  {
+    ScopedKernelTimer t("ba_add_rebuild", s);
+    EditTerms terms{};
+    if (L) terms = EditTerms{N.l_start.p, b->pt_lidar_list.p, b->lidar_abcd.p, b->lidar_w.p};
+    // the sliced-ELL copies wait for their size: the number of slots is in the record
+    PCD_TRY(edit_derive(N, P2, I, ns2, O2, /*fill_sell=*/false, terms, s));
+    hipLaunchKernelGGL(k_add_record, dim3(1), dim3(256), 0, s, 2 * nb, N.a_bad.p, I, N.img_seg_start.p, A, V,
+                       vrows ? N.v_pos.p : nullptr, ns2, N.slice_start.p, N.record.p);
+    PCD_HIP_TRY(hipGetLastError());
+  }
+  // the one synchronisation: the verdict, the counts and the image bounds (O(I) bytes)
+  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p, N.record.p, kAddWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p + kAddWords, N.img_obs_start.p, ((size_t)I + 1) * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, s));
+  if (info) (void)ev.stop(s);
+  PCD_HIP_TRY(hipStreamSynchronize(s));
+  const uint32_t* rec = N.h_record.p;
+  PCD_REQUIRE(!rec[kAddBad], "obs_image / obs_point of a new row out of range");   // nothing has been swapped in
+  const size_t nslots = rec[kAddSlots];
+  PCD_TRY(N.sell_img.reserve(at_least_1(nslots))); PCD_TRY(N.sell_xy.reserve(std::max<size_t>(2 * nslots, 2)));
+  if (nslots)
+    hipLaunchKernelGGL(k_ba_fill_sell, grid((uint64_t)ns2 * 64), dim3(256), 0, s, N.pt_order.p, N.slice_start.p,
+                       N.pt_obs_start.p, N.pt_obs_list.p, N.obs_image.p, N.obs_xy.p, (int)ns2, N.sell_img.p, N.sell_xy.p);
+  if (O2)
+    hipLaunchKernelGGL(k_ba_fill_image_major, grid(O2), dim3(256), 0, s, N.img_obs.p, N.obs_point.p, N.obs_xy.p, (uint64_t)O2,
+                       N.img_pt.p, N.img_xy.p);
+  PCD_HIP_TRY(hipGetLastError());
+  // success: the new layout becomes the handle's; the retired buffers are the next edit's
+  b->obs_image.swap(N.obs_image); b->obs_point.swap(N.obs_point); b->obs_xy.swap(N.obs_xy);
+  b->pt_obs_start.swap(N.pt_obs_start); b->pt_obs_list.swap(N.pt_obs_list);
+  b->pt_order.swap(N.pt_order); b->slice_start.swap(N.slice_start); b->sell_img.swap(N.sell_img); b->sell_xy.swap(N.sell_xy);
+  b->img_obs_start.swap(N.img_obs_start); b->img_obs.swap(N.img_obs); b->img_pt.swap(N.img_pt); b->img_xy.swap(N.img_xy);
+  b->seg_img.swap(N.seg_img); b->seg_begin.swap(N.seg_begin); b->img_seg_start.swap(N.img_seg_start);
+  if (vrows) b->vobs.swap(N.vobs);
+  b->pt_lidar_start.swap(N.l_start);
+  if (L) { b->pt_lidar_cnt.swap(N.l_cnt); b->pt_lidar_first.swap(N.l_first); }
+  if (Pn) {
+    b->points.swap(N.points);
+    if (b->has_cpt) b->point_const.swap(N.point_const);
+  }
+  b->O = O2; b->P = (int)P2; b->nslices = (int)ns2;
+  b->nseg = rec[kAddSegs];
+  b->n_pose_rows = rec[kAddPoseRows];
+  b->h_img_obs_start.assign(rec + kAddWords, rec + kAddWords + I + 1);
+  b->pose_row_stale = true;
+  ba_schur_drop_structure(b);
+  if (info) {
+    info->num_obs = O2; info->num_points = P2; info->num_pose_rows = b->n_pose_rows;
+    float ms = 0.f;
+    PCD_HIP_TRY(ev.elapsed(&ms));
+    info->rebuild_ms = ms;
+  }
+  return PCD_OK;
+}
+
 }  // namespace pcd
 
 using namespace pcd;
@@ -356,5 +658,49 @@ extern "C" pcd_status pcd_ba_remove_observations_device(pcd_ba* b, const uint8_t
     if (!d_obs_erase && !d_point_delete) return PCD_OK;   // nothing flagged: nothing changes, nothing is invalidated
     PCD_HIP_TRY(hipSetDevice(b->device));
     return edit_rebuild(b, d_obs_erase, d_point_delete, d_obs_map, (hipStream_t)stream, info);
+  });
+}
+
+extern "C" pcd_status pcd_ba_add_observations_device(pcd_ba* b, const double* d_new_points, uint64_t num_new_points,
+                                                     const int32_t* d_obs_image, const int32_t* d_obs_point,
+                                                     const double* d_obs_xy, uint64_t num_new_obs, void* stream,
+                                                     pcd_ba_add_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    if (info) std::memset(info, 0, sizeof *info);
+    PCD_REQUIRE(b, "null handle");
+    PCD_TRY(require_device(b->device));
+    PCD_TRY(refuse_capture((hipStream_t)stream, "pcd_ba_add_observations_device"));
+    if (info) { info->num_obs = b->O; info->num_points = (uint64_t)b->P; info->num_pose_rows = b->n_pose_rows; }
+    PCD_REQUIRE(num_new_points == 0 || d_new_points, "new points");
+    PCD_REQUIRE(num_new_obs == 0 || (d_obs_image && d_obs_point && d_obs_xy), "new observations");
+    PCD_REQUIRE(num_new_obs < 0xFFFFFFF0ull && b->O + num_new_obs < 0xFFFFFFF0ull, "too many residual blocks");
+    PCD_REQUIRE(num_new_points <= (uint64_t)INT32_MAX && (uint64_t)b->P + num_new_points <= (uint64_t)INT32_MAX, "too many points");
+    if (!num_new_obs && !num_new_points) return PCD_OK;   // nothing to add: nothing changes, nothing is invalidated
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    PCD_TRY(add_rebuild(b, d_new_points, num_new_points, d_obs_image, d_obs_point, d_obs_xy, num_new_obs, (hipStream_t)stream, info));
+    if (info) { info->num_obs_added = num_new_obs; info->num_points_added = num_new_points; }
+    return PCD_OK;
+  });
+}
+
+extern "C" pcd_status pcd_ba_add_observations(pcd_ba* b, const double* new_points, uint64_t num_new_points,
+                                              const int32_t* obs_image, const int32_t* obs_point, const double* obs_xy,
+                                              uint64_t num_new_obs, pcd_ba_add_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    if (info) std::memset(info, 0, sizeof *info);
+    PCD_REQUIRE(b, "null handle");
+    PCD_TRY(require_device(b->device));
+    PCD_REQUIRE(num_new_points == 0 || new_points, "new points");
+    PCD_REQUIRE(num_new_obs == 0 || (obs_image && obs_point && obs_xy), "new observations");
+    PCD_REQUIRE(num_new_obs < 0xFFFFFFF0ull && num_new_points <= (uint64_t)INT32_MAX, "too many rows");
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    DevBuf<double> d_points, d_xy;
+    DevBuf<int> d_image, d_point;
+    PCD_TRY(upload(d_points, new_points, 3 * (size_t)num_new_points));
+    PCD_TRY(upload(d_image, obs_image, (size_t)num_new_obs)); PCD_TRY(upload(d_point, obs_point, (size_t)num_new_obs));
+    PCD_TRY(upload(d_xy, obs_xy, 2 * (size_t)num_new_obs));
+    // the device form waits for the null stream before it returns; the fills it enqueues behind that wait read the
+    // handle's own copies, so the staging can go when this scope ends
+    return pcd_ba_add_observations_device(b, d_points.p, num_new_points, d_image.p, d_point.p, d_xy.p, num_new_obs, nullptr, info);
   });
 }

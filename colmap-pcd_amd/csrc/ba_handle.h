@@ -6,7 +6,8 @@
 //   ba_solve.hip  point elimination, PCG, LM loop (its own state hangs off pcd_ba::schur)
 //   ba_schur_structure.hip  the co-visibility structure of the elimination, built on the device (ba_schur_structure.h)
 //   ba_lidar.hip  replaces the LiDAR terms of a live handle: pcd_ba_set_lidar_device / pcd_ba_associate_lidar_device
-//   ba_edit.hip   drops observations and points from a live handle: pcd_ba_remove_observations_device
+//   ba_edit.hip   drops observations and points from a live handle, and adds them: pcd_ba_remove_observations_device,
+//                 pcd_ba_add_observations_device
 #pragma once
 #include <memory>
 
@@ -71,7 +72,7 @@ struct BaLidarScratch {
   PinnedBuf<uint64_t> h_count;
 };
 
-// Scratch of pcd_ba_remove_observations_device (ba_edit.hip).  The first two groups are the layouts under construction:
+// Scratch of pcd_ba_remove_observations_device and pcd_ba_add_observations_device (ba_edit.hip).  The first two groups are the layouts under construction:
 // on success they are swapped with the live arrays of pcd_ba, so the buffers a call retires are the next call's.
 struct BaEditScratch {
   DevBuf<int> obs_image, obs_point, pt_order, sell_img, img_pt;
@@ -82,6 +83,10 @@ struct BaEditScratch {
   // through the track lists, through the image lists, the variable-pose ones; terms in term order, through the point lists
   DevBuf<uint32_t> flag, pos, t_flag, t_pos, i_flag, i_pos, v_flag, v_pos, lf, lp, lt_flag, lt_pos;
   DevBuf<uint32_t> len, len_sorted, iota, width, seg_cnt, record;
+  // the addition alone: the grown points and their constness; the new rows' keys (clamped into range), their stable sort
+  // (keys, rows), the new entries in front of every key [max(P', I) + 1], the bad rows of every workgroup
+  DevBuf<double> points; DevBuf<uint8_t> point_const;
+  DevBuf<uint32_t> a_key, a_key_sorted, a_iota, a_row, a_add, a_bad;
   DevBuf<char> prim;                                      // rocPRIM temporary storage (scan, sort)
   PinnedBuf<uint32_t> h_record;                           // the counts, then img_obs_start [I+1]
 };
@@ -130,7 +135,7 @@ void ba_schur_invalidate(pcd_ba* b);
 void ba_schur_drop_structure(pcd_ba* b);
 
 // Kernels one unit defines and another launches too (the handle's derived layouts are made in three places: on creation,
-// when the terms change, when observations are dropped).  ba_build.hip: the sliced-ELL fill and the image-major copies;
+// when the terms change, when observations are dropped or added).  ba_build.hip: the sliced-ELL fill and the image-major copies;
 // ba_lidar.hip: the terms of every track in the thread order of k_ba_points.
 __global__ void k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __restrict__ slice_start,
                                const uint32_t* __restrict__ pt_start, const uint32_t* __restrict__ pt_list,

@@ -229,6 +229,12 @@ class BARemoveInfo(C.Structure):
                                            "num_points_emptied")] + [("rebuild_ms", C.c_double)]
 
 
+class BAAddInfo(C.Structure):
+    """pcd_ba_add_info (pcdhip.h)."""
+    _fields_ = [(n, C.c_uint64) for n in ("num_obs", "num_obs_added", "num_points", "num_points_added",
+                                           "num_pose_rows")] + [("rebuild_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -295,7 +301,7 @@ ABI_SYMBOLS = [
     "pcd_ba_associate_lidar_device",
     "pcd_proj_set_new_images_device", "pcd_ba_proj_opts_default", "pcd_ba_project_lidar_device",
     "pcd_ba_filter_opts_default", "pcd_ba_filter_points_device", "pcd_ba_filter_points",
-    "pcd_ba_remove_observations_device",
+    "pcd_ba_remove_observations_device", "pcd_ba_add_observations_device", "pcd_ba_add_observations",
     "pcd_ba_schur_build_device", "pcd_ba_schur_structure_lists",
 ]
 
@@ -425,6 +431,11 @@ def lib():
         L.pcd_ba_filter_points_device.argtypes = [C.c_void_p, C.POINTER(BAFilterOpts), C.POINTER(BAFilterOut), C.c_void_p]
         L.pcd_ba_remove_observations_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.POINTER(BARemoveInfo)]
+    if hasattr(L, "pcd_ba_add_observations_device"):
+        L.pcd_ba_add_observations_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_uint64, C.c_void_p, C.POINTER(BAAddInfo)]
+        L.pcd_ba_add_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_uint64, C.POINTER(BAAddInfo)]
     _LIB = L
     return L
 
@@ -1324,6 +1335,37 @@ class BA:
             out["obs_map"] = m
         return out
 
+    def add_observations(self, obs_image, obs_point, obs_xy, new_points=None):
+        """pcd_ba_add_observations_device: append new_points ([Pn][3] or None; they get the ids P .. P + Pn - 1) and the
+        rows obs_image / obs_point [A] int32, obs_xy [A][2] (numpy or torch device tensors; obs_point may name old and
+        new points).  Afterwards the handle equals one created from the concatenated arrays: old observation indices
+        stay, the new rows are O .. O + A - 1 in the order given, new points are variable and carry no LiDAR term.
+        Arrays with one entry per point that the caller passes later (max_range, select, point_delete, set_parameters)
+        must have the new length.  Rows out of range raise PcdError(PCD_ERR_INVALID) and leave the handle untouched.
+        Synchronises the current stream once.  Returns the info dict (num_obs, num_obs_added, num_points,
+        num_points_added, num_pose_rows, rebuild_ms)."""
+        _, _, stream = self._torch()
+        oi, op, xy = self._stage(obs_image, np.int32), self._stage(obs_point, np.int32), self._stage(obs_xy, np.float64)
+        x = self._stage(new_points, np.float64)
+        A = 0 if oi is None else int(oi.numel())
+        if (0 if op is None else int(op.numel())) != A or (0 if xy is None else int(xy.numel())) != 2 * A:
+            raise ValueError("add_observations: obs_image, obs_point [A] and obs_xy [A][2] must agree")
+        Pn = 0 if x is None else int(x.numel())
+        if Pn % 3:
+            raise ValueError("add_observations: new_points must be [Pn][3]")
+        Pn //= 3
+        info = BAAddInfo()
+        # an empty tensor has a null data pointer: a count of 0 goes with NULL
+        _check(lib().pcd_ba_add_observations_device(self._h, _ptr(x) if Pn else None, Pn, _ptr(oi) if A else None,
+                                                    _ptr(op) if A else None, _ptr(xy) if A else None, A,
+                                                    C.c_void_p(stream), C.byref(info)))
+        if A or Pn:
+            self.O, self.P = int(info.num_obs), int(info.num_points)
+            self.obs_image = self.obs_point = self.obs_xy = None      # stale: the handle has the current rows
+            self.points = self.point_const = None
+            self.__dict__.pop("_schur_dims", None)                    # the co-visibility structure is built anew
+        return {k: getattr(info, k) for k, _ in BAAddInfo._fields_}
+
     def device_parameters(self):
         a, b = C.c_void_p(), C.c_void_p()
         _check(lib().pcd_ba_device_parameters(self._h, C.byref(a), C.byref(b)))
@@ -1728,26 +1770,38 @@ def register_refine(ba, cloud, rounds, kd_max=1.5, kd_min=0.2, drop=0.1, gate_mo
     return out
 
 
-def refine_filter(ba, max_refinements=5, max_change=0.0005, max_reproj_error=8.0, min_tri_angle=1.5, **solve_opts):
+def refine_filter(ba, max_refinements=5, max_change=0.0005, max_reproj_error=8.0, min_tri_angle=1.5, complete=None,
+                  **solve_opts):
     """The loop of IncrementalMapperController's IterativeGlobalRefinement (controllers/incremental_mapper.cc:150-199) on
     one handle: ba_solve(**solve_opts), BA.filter_points_device, BA.remove_observations with the filter's flags, until a
     round changes less than max_change of the observations it started with (changed = num_filtered / observations before
     the round's removal; a handle without observations counts as unchanged) or max_refinements rounds have run.  No
     observation payload crosses PCIe; per round the host reads the filter's 4-double summary and the removal's counts.
-    CompleteAndMergeTracks and retriangulation add observations: they are the host's business and are left out, so
-    `changed` counts the filtered observations alone.  Returns one (solve summary, filter summary, remove info) per
-    round; the filter summary is a dict of num_filtered, mean_reproj_error, num_points_with_error, num_negative_depth,
-    changed."""
+    CompleteAndMergeTracks and retriangulation add observations: finding them is the host's business.  complete, if
+    given, is called as complete(ba, round) between the solve and the filter (the place of CompleteAndMergeTracks at
+    :178) and returns None or a dict(obs_image, obs_point, obs_xy, new_points) that goes in through
+    BA.add_observations; the rows it adds count in `changed` with the filtered ones, as in the reference's
+    num_changed_observations, and the round's tuple gains the add info as a fourth entry.  Without complete the
+    function behaves as before: `changed` counts the filtered observations alone.  Returns one (solve summary, filter
+    summary, remove info) per round; the filter summary is a dict of num_filtered, mean_reproj_error,
+    num_points_with_error, num_negative_depth, changed."""
     out = []
-    for _ in range(int(max_refinements)):
+    for r in range(int(max_refinements)):
         num_obs = ba.O
         summary, _its = ba_solve(ba, **solve_opts)
+        added = None
+        if complete is not None:
+            rows = complete(ba, r)
+            if rows is not None:
+                added = ba.add_observations(rows["obs_image"], rows["obs_point"], rows["obs_xy"], rows.get("new_points"))
         f = ba.filter_points_device(max_reproj_error, min_tri_angle)
         info = ba.remove_observations(f["obs_erase"], f["point_delete"])
         sm = f["summary"].cpu().numpy()
-        changed = float(sm[0]) / num_obs if num_obs else 0.0
-        out.append((summary, dict(num_filtered=int(sm[0]), mean_reproj_error=float(sm[1]),
-                                  num_points_with_error=int(sm[2]), num_negative_depth=int(sm[3]), changed=changed), info))
+        num_changed = float(sm[0]) + (added["num_obs_added"] if added else 0)
+        changed = num_changed / num_obs if num_obs else 0.0
+        fl = dict(num_filtered=int(sm[0]), mean_reproj_error=float(sm[1]), num_points_with_error=int(sm[2]),
+                  num_negative_depth=int(sm[3]), changed=changed)
+        out.append((summary, fl, info) if complete is None else (summary, fl, info, added))
         if changed < max_change:
             break
     return out

@@ -13,6 +13,7 @@
 // blocks.  Pure host code up to Evaluate(): the structure logic is unit-tested without a GPU.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <map>
@@ -478,6 +479,82 @@ class BundleAdjusterHip {
     }
     if (ok) *ok = true;
     return (size_t)summary[0];
+  }
+  // ---- rows and points added to the LIVE handle (HIP): what IncrementalMapper::CompleteAndMergeTracks and Retriangulate
+  // (controllers/incremental_mapper.cc:157-162, :178) change in the problem between two adjustments ----------------------
+  // A completed track is a list of elements on a point the problem has; a retriangulated point is an entry of new_points
+  // with its elements; a merge (Reconstruction::MergePoints3D) is FilterPoints-style removal of the two points by the
+  // caller followed by one new point with the union of their elements.
+  struct NewElement { image_t image_id; point2D_t point2D_idx; point3D_t point3D_id; double xy[2]; };
+  typedef std::pair<point3D_t, std::array<double, 3>> NewPoint;
+  // The flat rows AddObservations hands to pcd_ba_add_observations, in that order: new point k becomes row P + k, an
+  // element's point is the new row of its id if new_points has it (a re-created id is a new row; the row a deleted point
+  // left behind stays dead), otherwise the row point_ids_ has for it.
+  struct Addition {
+    std::vector<int32_t> obs_image, obs_point;
+    std::vector<double> obs_xy, points;
+    std::vector<point2D_t> obs_point2D;
+    std::vector<point3D_t> point_ids;
+  };
+  // false, *out untouched: an image that is not in the problem, a point id that is neither in point_ids_ nor among
+  // new_points, or an id twice in new_points.  Pure host code.
+  bool PlanAddition(const std::vector<NewElement>& elements, const std::vector<NewPoint>& new_points, Addition* out) const {
+    Addition a;
+    std::unordered_map<point3D_t, int> fresh;
+    const int P = (int)point_ids_.size();
+    for (const NewPoint& np : new_points) {
+      if (!fresh.emplace(np.first, P + (int)a.point_ids.size()).second) return false;
+      a.point_ids.push_back(np.first);
+      a.points.insert(a.points.end(), np.second.begin(), np.second.end());
+    }
+    for (const NewElement& e : elements) {
+      const auto im = image_index_.find(e.image_id);
+      if (im == image_index_.end()) return false;
+      int p;
+      const auto f = fresh.find(e.point3D_id);
+      if (f != fresh.end()) p = f->second;
+      else {
+        const auto it = point_index_.find(e.point3D_id);
+        if (it == point_index_.end()) return false;
+        p = it->second;
+      }
+      a.obs_image.push_back(im->second);
+      a.obs_point.push_back(p);
+      a.obs_point2D.push_back(e.point2D_idx);
+      a.obs_xy.push_back(e.xy[0]);
+      a.obs_xy.push_back(e.xy[1]);
+    }
+    *out = std::move(a);
+    return true;
+  }
+  // pcd_ba_add_observations on the live handle, and the same rows appended to point_ids_, obs_image_, obs_point_,
+  // obs_point2D_, obs_xy_, the point mirrors (points_, point_const_ = 0) and point3D_num_observations_, so that
+  // FilterPoints, NumResiduals(), a later Create() and Solve's write-back (which keeps this handle) agree with the handle.
+  // New points are variable and carry no LiDAR term until the next ReassociateLidar / ProjectLidar, whose per-point
+  // arguments then cover them.  Returns the number of rows added; *ok (may be NULL) is false, with nothing changed, without
+  // a live handle, when PlanAddition refuses, or when the call fails (pcd_last_error()).
+  size_t AddObservations(const std::vector<NewElement>& elements, const std::vector<NewPoint>& new_points, bool* ok = nullptr) {
+    if (ok) *ok = false;
+    if (!ba_) return 0;
+    Addition a;
+    if (!PlanAddition(elements, new_points, &a)) return 0;
+    if (pcd_ba_add_observations(ba_, a.points.data(), a.point_ids.size(), a.obs_image.data(), a.obs_point.data(),
+                                a.obs_xy.data(), a.obs_image.size(), nullptr) != PCD_OK)
+      return 0;
+    for (size_t k = 0; k < a.point_ids.size(); ++k) {
+      point_index_[a.point_ids[k]] = (int)point_ids_.size();
+      point_ids_.push_back(a.point_ids[k]);
+      point_const_.push_back(0);
+      point3D_num_observations_[a.point_ids[k]] = 0;   // a re-created id starts over
+    }
+    points_.insert(points_.end(), a.points.begin(), a.points.end());
+    for (size_t o = 0; o < a.obs_image.size(); ++o) {
+      AddObservation(a.obs_image[o], a.obs_point[o], a.obs_point2D[o], &a.obs_xy[2 * o]);
+      point3D_num_observations_[point_ids_[a.obs_point[o]]] += 1;
+    }
+    reassociated_ = true;   // the live handle is the problem: Solve keeps it
+    if (ok) *ok = true;
+    return a.obs_image.size();
   }
   const BundleAdjustmentConfig& config() const { return config_; }
   // what Solve hands to pcd_ba_solve: AUTO goes by the number of images in the config, as the reference does

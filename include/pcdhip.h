@@ -1067,6 +1067,55 @@ pcd_status pcd_ba_remove_observations_device(pcd_ba* ba,
     void* stream, pcd_ba_remove_info* info /* host, may be NULL */);
 
 /* ------------------------------------------------------------------------
+ * Observations and points added to a live handle on the device            
+ *   the growing half of controllers/incremental_mapper.cc:157-198: CompleteAndMergeTracks and Retriangulate between
+ *   the adjustments.  A completed track is an addition; a retriangulated point is a new point with its rows; a merge
+ *   (MergePoints3D) is pcd_ba_remove_observations_device of two points followed by the addition of one.
+ * Contract (that of pcd_ba_set_lidar_device and pcd_ba_remove_observations_device): afterwards the handle is
+ *   indistinguishable from one pcd_ba_create built from a description with
+ *     points      = the handle's current device points followed by d_new_points (ids P .. P + num_new_points - 1),
+ *     obs_*       = the handle's rows followed by the new rows in the order given (ids O .. O + num_new_obs - 1; old
+ *                   observation indices do not change, so there is no map),
+ *     point_const = (only if the handle has one) extended by zeros: new points are variable,
+ *   and everything else unchanged: I, C, the poses as they are on the device, cameras, masks, refine mask, loss, the
+ *   LiDAR terms with their type / lidar_xyz meta.  Every derived array is the one pcd_ba_create would upload, byte for
+ *   byte, so every later result is bit-identical to the fresh handle's.  New points carry no LiDAR term until the next
+ *   pcd_ba_associate_lidar_device / pcd_ba_project_lidar_device / pcd_ba_set_lidar_device.
+ * Arrays of the caller's with one entry per point (d_max_range, d_point_mode, the select masks of the associate /
+ *   project options, point_delete flags, parameter uploads) must have the new length from then on.
+ * Rows are validated ON THE DEVICE: obs_image in [0, I), obs_point in [0, P + num_new_points).  The verdict travels with
+ *   the counts in the call's one status record; on a bad row the call returns PCD_ERR_INVALID and nothing has changed:
+ *   the new layout is built in buffers of its own and swapped in only after the record says OK.
+ * Guards, the handle exactly as it was: a NULL handle -> INVALID; no gfx950 -> NO_DEVICE; a capturing stream ->
+ *   UNSUPPORTED before anything is allocated; a count with a NULL array -> INVALID; O + num_new_obs >= 0xFFFFFFF0 or
+ *   P + num_new_points > INT32_MAX -> INVALID from the counts alone.  num_new_obs == 0 && num_new_points == 0 is a valid
+ *   call that changes nothing and invalidates nothing.  Every buffer whose size follows from the counts is reserved before
+ *   the first kernel; the sliced-ELL copies, whose size depends on the rows, are reserved behind the synchronisation and
+ *   ahead of the swap.  A failed allocation leaves the handle intact.
+ * The call synchronises `stream` ONCE, to read O(I) bytes: the verdict, the counts and the image bounds.  The two fill
+ *   kernels are enqueued behind that read; later work on the handle must be ordered behind `stream`.  rebuild_ms is the
+ *   device time up to the synchronisation.
+ * What a successful call invalidates: pointers handed out by pcd_ba_evaluate_blocks*, pcd_ba_lidar_device and (when
+ *   points were added) pcd_ba_device_parameters; the Schur state of the last call and the co-visibility structure.
+ * No atomics; no order depends on launch geometry: a repeated call is bitwise identical.
+ * --------------------------------------------------------------------- */
+typedef struct {
+  uint64_t num_obs, num_obs_added;         /* after / added */
+  uint64_t num_points, num_points_added;
+  uint64_t num_pose_rows;                  /* observations on variable-pose images, after */
+  double rebuild_ms;                       /* device time up to the call's one synchronisation */
+} pcd_ba_add_info;
+pcd_status pcd_ba_add_observations_device(pcd_ba* ba,
+    const double* d_new_points   /* [num_new_points][3] or NULL when 0: they get ids P .. P+num_new_points-1 */,
+    uint64_t num_new_points,
+    const int32_t* d_obs_image, const int32_t* d_obs_point, const double* d_obs_xy /* [num_new_obs] ([..][2]) */,
+    uint64_t num_new_obs, void* stream, pcd_ba_add_info* info /* host, may be NULL */);
+/* host arrays: uploads them and calls the device form on the null stream */
+pcd_status pcd_ba_add_observations(pcd_ba* ba, const double* new_points, uint64_t num_new_points,
+                                   const int32_t* obs_image, const int32_t* obs_point, const double* obs_xy,
+                                   uint64_t num_new_obs, pcd_ba_add_info* info /* may be NULL */);
+
+/* ------------------------------------------------------------------------
  * Exact SIFT descriptor matching (stretch row a19)
  *   replaces feature/sift.cc:1041-1054 MatchSiftFeaturesCPUBruteForce =
  *     feature/sift.cc:171-204 ComputeSiftDistanceMatrix (int32 dot of uint8 x 128) +
