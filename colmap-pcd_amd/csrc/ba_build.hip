@@ -3,13 +3,14 @@
 // ba_handle.h), one stage per layout.  The host only sorts indices (counting sorts); the 16-byte observation payloads
 // never make a second trip over PCIe and are never gathered by a host loop: two fill kernels gather them on the device
 // from the uploaded arrays, on the null stream behind the synchronous uploads; pcd_ba_create waits for them once.
+// The stages upload into the handle's own BaLayout / BaTerms (ba_handle.h); ba_edit.hip uses the two fill launchers too.
 #include "ba_handle.h"
 
-using namespace pcd;
+namespace pcd {
 
 // sliced ELL: thread = (slice, lane): track p = order[slice*64 + lane], its j-th observation goes to slot
 // slice_start[slice] + 64 j + lane
-__global__ void pcd::k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __restrict__ slice_start,
+__global__ void k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __restrict__ slice_start,
                                const uint32_t* __restrict__ pt_start, const uint32_t* __restrict__ pt_list,
                                const int* __restrict__ obs_image, const double* __restrict__ obs_xy, int nslices,
                                int* __restrict__ sell_img, double* __restrict__ sell_xy) {
@@ -32,8 +33,12 @@ __global__ void pcd::k_ba_fill_sell(const int* __restrict__ order, const uint32_
     }
   }
 }
+void launch_fill_sell(const BaLayout& y, int nslices, hipStream_t s) {
+  hipLaunchKernelGGL(k_ba_fill_sell, dim3(div_up((size_t)nslices * 64, 256)), dim3(256), 0, s, y.pt_order.p, y.slice_start.p,
+                     y.pt_obs_start.p, y.pt_obs_list.p, y.obs_image.p, y.obs_xy.p, nslices, y.sell_img.p, y.sell_xy.p);
+}
 // image-major copies: e-th observation of the image-major order = observation img_obs[e] of the caller's order
-__global__ void pcd::k_ba_fill_image_major(const uint32_t* __restrict__ img_obs, const int* __restrict__ obs_point,
+__global__ void k_ba_fill_image_major(const uint32_t* __restrict__ img_obs, const int* __restrict__ obs_point,
                                       const double* __restrict__ obs_xy, uint64_t O, int* __restrict__ img_pt,
                                       double* __restrict__ img_xy) {
   const uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
@@ -42,6 +47,16 @@ __global__ void pcd::k_ba_fill_image_major(const uint32_t* __restrict__ img_obs,
   img_pt[e] = obs_point[o];
   *reinterpret_cast<double2*>(img_xy + 2 * e) = *reinterpret_cast<const double2*>(obs_xy + 2 * (size_t)o);
 }
+
+void launch_fill_image_major(const BaLayout& y, uint64_t O, hipStream_t s) {
+  if (!O) return;
+  hipLaunchKernelGGL(k_ba_fill_image_major, dim3(div_up(O, 256)), dim3(256), 0, s, y.img_obs.p, y.obs_point.p, y.obs_xy.p, O,
+                     y.img_pt.p, y.img_xy.p);
+}
+
+}  // namespace pcd
+
+using namespace pcd;
 
 // stable counting sort of element ids by key -> CSR (start[nkeys+1], list[n])
 static void build_csr(const int32_t* key, uint64_t n, int nkeys, std::vector<uint32_t>& start,
@@ -143,12 +158,8 @@ static pcd_status build_track_layout(const pcd_ba_desc* d, pcd_ba* b, std::vecto
   UP(pt_order, order.data(), order.size());
   UP(slice_start, slice_start.data(), slice_start.size());
   UP(pt_obs_start, st.data(), st.size()); UP(pt_obs_list, li.data(), li.size());
-  PCD_TRY(b->sell_img.reserve(std::max<size_t>(nslots, 1)));
-  PCD_TRY(b->sell_xy.reserve(std::max<size_t>(2 * nslots, 2)));
-  if (nslots)
-    hipLaunchKernelGGL(k_ba_fill_sell, dim3(div_up((size_t)nslices * 64, 256)), dim3(256), 0, nullptr, b->pt_order.p,
-                       b->slice_start.p, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p, b->obs_xy.p, nslices,
-                       b->sell_img.p, b->sell_xy.p);
+  PCD_TRY(b->reserve_sell(nslots));
+  if (nslots) launch_fill_sell(*b, nslices, nullptr);
   return PCD_OK;
 }
 
@@ -201,9 +212,7 @@ static pcd_status build_image_layout(const pcd_ba_desc* d, pcd_ba* b) {
   UP(img_obs, li.data(), li.size());
   PCD_TRY(b->img_pt.reserve(std::max<size_t>(b->O, 1)));
   PCD_TRY(b->img_xy.reserve(std::max<size_t>(2 * b->O, 2)));
-  if (b->O)
-    hipLaunchKernelGGL(k_ba_fill_image_major, dim3(div_up(b->O, 256)), dim3(256), 0, nullptr, b->img_obs.p,
-                       b->obs_point.p, b->obs_xy.p, b->O, b->img_pt.p, b->img_xy.p);
+  launch_fill_image_major(*b, b->O, nullptr);
   return PCD_OK;
 }
 
@@ -241,7 +250,7 @@ pcd_status pcd_ba_create(const pcd_ba_desc* d, pcd_ba** out) {
   PCD_TRY(build_image_layout(d, b));
   PCD_TRY(build_pose_rows(d, b));
   // one cost partial per workgroup of whichever of the two cost-producing kernels has the larger grid (cost_blocks)
-  PCD_TRY(b->cost_partial.reserve((size_t)std::max(cost_blocks(b, true), cost_blocks(b, false)) + 1));
+  PCD_TRY(reserve_cost_partial(b, (size_t)b->nslices, b->O, b->L));
   PCD_TRY(b->cost.reserve(1));
   // the two fill kernels ran on the null stream behind the synchronous uploads: one wait, one check
   if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {

@@ -14,8 +14,9 @@
 //   k_edit_seg_count, exclusive_sum, k_edit_segs   segments of <= kImgSeg observations per image
 //   k_ba_fill_sell, k_ba_fill_image_major, k_lidar_tracks   the fills pcd_ba_create and ba_lidar.hip use
 //   k_edit_record                        the counts the host reads (the ONE synchronisation), with img_obs_start
-// No atomics; nothing depends on the launch geometry.  The new layout is built in pcd_ba::edit_next, every buffer of it
-// reserved before the first launch, and swapped in at the end.
+// No atomics; nothing depends on the launch geometry.  The new state is a BaLayout and a BaTerms (ba_handle.h) built in
+// pcd_ba::edit_next, every buffer of it reserved before the first launch, and swapped in at the end.  Both edits go through
+// edit_reserve_shared, edit_derive, edit_read_record (the synchronisation) and edit_commit (the tail behind it).
 //
 // pcd_ba_add_observations_device is the growing edit: rows and points appended.  Its passes:
 //   k_add_keys, sort_pairs               the new rows' keys (clamped, with the verdict on their range) sorted stably, once
@@ -24,7 +25,7 @@
 //   k_add_move_old / k_add_place_new     old list entries shifted, new ones behind them in input order
 //   k_add_vflag, exclusive_sum, k_add_vobs   the packed pose rows, the new ones appended
 //   edit_derive                          the tail both edits share: lengths, length sort, slices, segments, k_lidar_tracks
-//   k_add_record                         verdict and counts (the ONE synchronisation); the two fills follow it
+//   k_add_record                         verdict and counts (the ONE synchronisation); the two fills follow it (edit_commit)
 #include "ba_handle.h"
 #include "prim.h"
 
@@ -178,103 +179,112 @@ __global__ __launch_bounds__(256) void k_edit_record(uint32_t O, uint32_t L, uin
   }
 }
 
-// key bits of the sort by track length: a length is at most O
-static unsigned length_bits(uint64_t O) {
-  unsigned bits = 1;
-  while (bits < 32 && (1ull << bits) <= O) ++bits;
-  return bits;
-}
-
+static dim3 grid(uint64_t n) { return dim3(div_up(n, 256)); }   // of 256 threads
 static pcd_status scan_flags(BaEditScratch& N, const uint32_t* flag, uint32_t* pos, size_t n, hipStream_t s) {
   return exclusive_sum(N.prim, flag, pos, 0u, n, s);
 }
 
-// The LiDAR terms the derived layouts follow (start null: the handle has none)
-struct EditTerms { const uint32_t* start; const uint32_t* list; const double* abcd; const double* w; };
-
-// What both edits derive from the new CSRs in N (pt_obs_start / pt_obs_list, img_obs_start) and the new rows (obs_image,
-// obs_xy): the tracks in order of length (pt_order, slice_start), the sliced-ELL copies (fill_sell: when they are
-// reserved already), the segments of the images and the terms of every track in the new thread order.  P, nslices and O
-// are those of the new layout; O only bounds a track's length.
+// What both edits derive from the new CSRs in N.layout (pt_obs_start / pt_obs_list, img_obs_start) and the new rows
+// (obs_image, obs_xy): the tracks in order of length (pt_order, slice_start), the sliced-ELL copies (fill_sell: when they
+// are reserved already), the segments of the images and the per-track copies of N.terms in the new thread order, from
+// N.terms' own pt_lidar_start and the list, planes and weights of `rows` (null: the handle has no terms).  P, nslices and
+// O are those of the new layout; O only bounds a track's length.
 static pcd_status edit_derive(BaEditScratch& N, uint32_t P, uint32_t I, uint32_t nslices, uint64_t O, bool fill_sell,
-                              const EditTerms& terms, hipStream_t s) {
-  auto grid = [](uint64_t n) { return dim3(div_up(n, 256)); };
+                              const BaTerms* rows, hipStream_t s) {
+  BaLayout& Y = N.layout;
   const uint32_t ntr = nslices * 64u;
-  // tracks in ascending order of length, ties in ascending point id; a length is below 2^length_bits(O)
-  hipLaunchKernelGGL(k_edit_lengths, grid(P), dim3(256), 0, s, P, N.pt_obs_start.p, N.len.p, N.iota.p);
-  PCD_TRY(sort_pairs(N.prim, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(N.pt_order.p), (size_t)P, 0u,
-                     length_bits(O), s));
+  // tracks in ascending order of length, ties in ascending point id; a length is at most O
+  hipLaunchKernelGGL(k_edit_lengths, grid(P), dim3(256), 0, s, P, Y.pt_obs_start.p, N.len.p, N.iota.p);
+  PCD_TRY(sort_pairs(N.prim, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(Y.pt_order.p), (size_t)P, 0u,
+                     key_bits(O), s));
   hipLaunchKernelGGL(k_edit_slice_width, grid(std::max<uint64_t>(ntr, (uint64_t)nslices + 1)), dim3(256), 0, s, P, nslices,
-                     N.len_sorted.p, N.pt_order.p, N.width.p);
-  PCD_TRY(scan_flags(N, N.width.p, N.slice_start.p, (size_t)nslices + 1, s));
-  if (fill_sell)
-    hipLaunchKernelGGL(k_ba_fill_sell, grid(ntr), dim3(256), 0, s, N.pt_order.p, N.slice_start.p, N.pt_obs_start.p,
-                       N.pt_obs_list.p, N.obs_image.p, N.obs_xy.p, (int)nslices, N.sell_img.p, N.sell_xy.p);
+                     N.len_sorted.p, Y.pt_order.p, N.width.p);
+  PCD_TRY(scan_flags(N, N.width.p, Y.slice_start.p, (size_t)nslices + 1, s));
+  if (fill_sell) launch_fill_sell(Y, (int)nslices, s);
   // segments of the images
-  hipLaunchKernelGGL(k_edit_seg_count, grid((uint64_t)I + 1), dim3(256), 0, s, I, N.img_obs_start.p, N.seg_cnt.p);
-  PCD_TRY(scan_flags(N, N.seg_cnt.p, N.img_seg_start.p, (size_t)I + 1, s));
-  hipLaunchKernelGGL(k_edit_segs, grid((uint64_t)I + 1), dim3(256), 0, s, I, N.img_obs_start.p, N.img_seg_start.p,
-                     N.seg_img.p, N.seg_begin.p);
-  // the terms of every track in the new thread order
-  if (terms.start)
-    hipLaunchKernelGGL(k_lidar_tracks, grid(ntr), dim3(256), 0, s, ntr, N.pt_order.p, terms.start, terms.list, terms.abcd,
-                       terms.w, N.l_cnt.p, N.l_first.p);
+  hipLaunchKernelGGL(k_edit_seg_count, grid((uint64_t)I + 1), dim3(256), 0, s, I, Y.img_obs_start.p, N.seg_cnt.p);
+  PCD_TRY(scan_flags(N, N.seg_cnt.p, Y.img_seg_start.p, (size_t)I + 1, s));
+  hipLaunchKernelGGL(k_edit_segs, grid((uint64_t)I + 1), dim3(256), 0, s, I, Y.img_obs_start.p, Y.img_seg_start.p,
+                     Y.seg_img.p, Y.seg_begin.p);
+  if (rows) launch_lidar_tracks(Y, (int)nslices, *rows, N.terms, s);
   return PCD_OK;
 }
 
-// Every buffer the rebuild writes, at the sizes of the handle as it is: nothing grows when rows are dropped, so nothing
-// is allocated after the first launch
-static pcd_status edit_reserve(pcd_ba* b) {
-  BaEditScratch& N = b->edit_next;
-  const size_t O = b->O, L = b->L, P = (size_t)b->P, I = (size_t)b->I, ntr = (size_t)b->nslices * 64;
-  PCD_TRY(N.obs_image.reserve(at_least_1(O))); PCD_TRY(N.obs_point.reserve(at_least_1(O)));
-  PCD_TRY(N.obs_xy.reserve(at_least_1(2 * O)));
-  PCD_TRY(N.pt_obs_start.reserve(P + 1)); PCD_TRY(N.pt_obs_list.reserve(at_least_1(O)));
-  PCD_TRY(N.pt_order.reserve(at_least_1(ntr))); PCD_TRY(N.slice_start.reserve((size_t)b->nslices + 1));
-  PCD_TRY(N.sell_img.reserve(b->sell_img.n)); PCD_TRY(N.sell_xy.reserve(b->sell_xy.n));   // slices only get narrower
-  PCD_TRY(N.img_obs_start.reserve(I + 1)); PCD_TRY(N.img_obs.reserve(at_least_1(O)));
-  PCD_TRY(N.img_pt.reserve(at_least_1(O))); PCD_TRY(N.img_xy.reserve(std::max<size_t>(2 * O, 2)));
-  PCD_TRY(N.seg_img.reserve(at_least_1(b->nseg))); PCD_TRY(N.seg_begin.reserve((size_t)b->nseg + 1));
-  PCD_TRY(N.img_seg_start.reserve(I + 1));
-  if (b->has_cpose) { PCD_TRY(N.vobs.reserve(at_least_1(O))); PCD_TRY(N.v_flag.reserve(O + 1)); PCD_TRY(N.v_pos.reserve(O + 1)); }
-  PCD_TRY(N.flag.reserve(O + 1)); PCD_TRY(N.pos.reserve(O + 1));
-  PCD_TRY(N.t_flag.reserve(O + 1)); PCD_TRY(N.t_pos.reserve(O + 1));
-  PCD_TRY(N.i_flag.reserve(O + 1)); PCD_TRY(N.i_pos.reserve(O + 1));
-  PCD_TRY(N.len.reserve(P)); PCD_TRY(N.len_sorted.reserve(P)); PCD_TRY(N.iota.reserve(P));
-  PCD_TRY(N.width.reserve((size_t)b->nslices + 1)); PCD_TRY(N.seg_cnt.reserve(I + 1));
-  PCD_TRY(N.record.reserve(kRecWords)); PCD_TRY(N.h_record.reserve(kRecWords + I + 1));
-  if (L) {
-    PCD_TRY(N.l_point.reserve(L)); PCD_TRY(N.l_abcd.reserve(4 * L)); PCD_TRY(N.l_w.reserve(L));
-    if (b->has_lidar_meta) { PCD_TRY(N.l_type.reserve(L)); PCD_TRY(N.l_xyz.reserve(3 * L)); }
-    PCD_TRY(N.l_start.reserve(P + 1)); PCD_TRY(N.l_list.reserve(L));
-    PCD_TRY(N.l_cnt.reserve(at_least_1(ntr))); PCD_TRY(N.l_first.reserve(at_least_1(5 * ntr)));
-    PCD_TRY(N.lf.reserve(L + 1)); PCD_TRY(N.lp.reserve(L + 1)); PCD_TRY(N.lt_flag.reserve(L + 1)); PCD_TRY(N.lt_pos.reserve(L + 1));
-  }
-  // rocPRIM's storage: the largest need over every scan size the rebuild uses (no monotonicity in n is assumed) and the
-  // sort as the rebuild calls it, so that no call below has to grow the buffer
-  size_t need = 0;
-  for (size_t n : {O + 1, L + 1, (size_t)b->nslices + 1, I + 1}) {
-    size_t bytes = 0;
-    PCD_HIP_TRY(exclusive_sum_at(nullptr, bytes, N.flag.p, N.pos.p, 0u, n, nullptr));
-    need = std::max(need, bytes);
-  }
-  size_t bytes = 0;
-  PCD_HIP_TRY(sort_pairs_at(nullptr, bytes, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(N.pt_order.p), P, 0u,
-                            length_bits(O), nullptr));
-  PCD_TRY(N.prim.reserve(std::max(need, bytes)));
+// What both edits reserve ahead of their first launch: the layout under construction at the sizes z, the work buffers
+// of edit_derive, the record (`words` counts, then img_obs_start)
+static pcd_status edit_reserve_shared(BaEditScratch& N, const BaLayoutSizes& z, size_t words) {
+  PCD_TRY(N.layout.reserve_layout(z));
+  PCD_TRY(N.len.reserve(z.P)); PCD_TRY(N.len_sorted.reserve(z.P)); PCD_TRY(N.iota.reserve(z.P));
+  PCD_TRY(N.width.reserve(z.nslices + 1)); PCD_TRY(N.seg_cnt.reserve(z.I + 1));
+  PCD_TRY(N.record.reserve(words)); PCD_TRY(N.h_record.reserve(words + z.I + 1));
   return PCD_OK;
+}
+
+// The one synchronisation of an edit: the record and the image bounds (O(I) bytes) arrive in N.h_record.  rebuild_ms ends
+// here: the wait completes the event, no second one is needed.
+static pcd_status edit_read_record(BaEditScratch& N, size_t words, uint32_t I, EventPair* ev, hipStream_t s) {
+  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p, N.record.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p + words, N.layout.img_obs_start.p, ((size_t)I + 1) * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, s));
+  if (ev) (void)ev->stop(s);
+  PCD_HIP_TRY(hipStreamSynchronize(s));
+  return PCD_OK;
+}
+
+// The tail of both edits behind that synchronisation: the fills that need a count of the record, then success -- what was
+// built (the layout, the groups `terms` of the terms, the grown points when P grows) becomes the handle's with the counts c
+// and the record's image bounds; the retired buffers are the next edit's.  nslots null: the sliced-ELL copies are filled.
+struct EditCounts { uint32_t O, L, P, nslices, nseg, n_pose_rows; };
+static pcd_status edit_commit(pcd_ba* b, const EditCounts& c, const uint32_t* nslots, unsigned terms, size_t words,
+                              EventPair* ev, float* rebuild_ms, hipStream_t s) {
+  BaEditScratch& N = b->edit_next;
+  if (nslots) {
+    PCD_TRY(N.layout.reserve_sell(*nslots));
+    if (*nslots) launch_fill_sell(N.layout, (int)c.nslices, s);
+  }
+  launch_fill_image_major(N.layout, c.O, s);
+  PCD_HIP_TRY(hipGetLastError());
+  b->swap_layout(N.layout, b->has_cpose);
+  b->swap_terms(N.terms, terms);
+  if (c.P != (uint32_t)b->P) { b->points.swap(N.points); if (b->has_cpt) b->point_const.swap(N.point_const); }
+  b->O = c.O; b->L = c.L; b->P = (int)c.P; b->nslices = (int)c.nslices;
+  b->nseg = c.nseg; b->n_pose_rows = c.n_pose_rows;
+  b->h_img_obs_start.assign(N.h_record.p + words, N.h_record.p + words + b->I + 1);
+  b->pose_row_stale = true;
+  ba_schur_drop_structure(b);
+  if (ev) PCD_HIP_TRY(ev->elapsed(rebuild_ms));
+  return PCD_OK;
+}
+
+// Every buffer the removal writes, at the sizes of the handle as it is: nothing grows when rows are dropped, so nothing
+// is allocated after the first launch
+static pcd_status edit_reserve(pcd_ba* b, unsigned terms) {
+  BaEditScratch& N = b->edit_next;
+  const size_t O = b->O, L = b->L, P = (size_t)b->P, I = (size_t)b->I, ns = (size_t)b->nslices;
+  // slices only get narrower: the sliced-ELL copies at the live capacity
+  PCD_TRY(edit_reserve_shared(N, BaLayoutSizes{O, P, I, ns, b->nseg, b->has_cpose, b->sell_img.n, b->sell_xy.n}, kRecWords));
+  if (b->has_cpose) { PCD_TRY(N.v_flag.reserve(O + 1)); PCD_TRY(N.v_pos.reserve(O + 1)); }
+  for (DevBuf<uint32_t>* d : {&N.flag, &N.pos, &N.t_flag, &N.t_pos, &N.i_flag, &N.i_pos}) PCD_TRY(d->reserve(O + 1));
+  PCD_TRY(N.terms.reserve_terms(terms, L, P, ns * 64));
+  if (L) for (DevBuf<uint32_t>* d : {&N.lf, &N.lp, &N.lt_flag, &N.lt_pos}) PCD_TRY(d->reserve(L + 1));
+  size_t need = 0;
+  PCD_TRY(prim_storage_u32({O + 1, L + 1, ns + 1, I + 1}, {{P, key_bits(O)}}, need));
+  return N.prim.reserve(need);
 }
 
 static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t* d_pdel, uint32_t* d_map, hipStream_t s,
                                pcd_ba_remove_info* info) {
   BaEditScratch& N = b->edit_next;
+  BaLayout& Y = N.layout;
+  BaTerms& T = N.terms;
   const uint32_t O = (uint32_t)b->O, L = (uint32_t)b->L, P = (uint32_t)b->P, I = (uint32_t)b->I;
   const uint32_t nslices = (uint32_t)b->nslices;
-  PCD_TRY(edit_reserve(b));
+  const bool vrows = b->has_cpose, meta = b->has_lidar_meta;
+  // the terms this call builds: every group when the handle has terms (the meta when it has that), none otherwise
+  const unsigned terms = L ? kTermRows | (meta ? kTermMeta : 0u) | kTermIndex | kTermTracks : 0u;
+  PCD_TRY(edit_reserve(b, terms));
   EventPair ev;
   if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
-  auto grid = [](uint64_t n) { return dim3(div_up(n, 256)); };
-  const bool vrows = b->has_cpose;
   {
     ScopedKernelTimer t("ba_edit_scan", s);
     hipLaunchKernelGGL(k_edit_obs_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, d_erase, d_pdel, b->obs_point.p, N.flag.p);
@@ -300,71 +310,40 @@ static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t*
     // the observations, the track CSR and the image CSR
     if (O) {
       hipLaunchKernelGGL(k_edit_compact_obs, grid(O), dim3(256), 0, s, O, N.flag.p, N.pos.p, b->obs_image.p, b->obs_point.p,
-                         b->obs_xy.p, vrows ? N.v_flag.p : nullptr, N.v_pos.p, N.obs_image.p, N.obs_point.p, N.obs_xy.p,
-                         N.vobs.p, d_map);
+                         b->obs_xy.p, vrows ? N.v_flag.p : nullptr, N.v_pos.p, Y.obs_image.p, Y.obs_point.p, Y.obs_xy.p,
+                         Y.vobs.p, d_map);
       hipLaunchKernelGGL(k_edit_compact_list, grid(O), dim3(256), 0, s, O, b->pt_obs_list.p, N.t_flag.p, N.t_pos.p, N.pos.p,
-                         N.pt_obs_list.p);
+                         Y.pt_obs_list.p);
       hipLaunchKernelGGL(k_edit_compact_list, grid(O), dim3(256), 0, s, O, b->img_obs.p, N.i_flag.p, N.i_pos.p, N.pos.p,
-                         N.img_obs.p);
+                         Y.img_obs.p);
     }
-    hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)P + 1), dim3(256), 0, s, P, b->pt_obs_start.p, N.t_pos.p, N.pt_obs_start.p);
-    hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)I + 1), dim3(256), 0, s, I, b->img_obs_start.p, N.i_pos.p, N.img_obs_start.p);
+    hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)P + 1), dim3(256), 0, s, P, b->pt_obs_start.p, N.t_pos.p, Y.pt_obs_start.p);
+    hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)I + 1), dim3(256), 0, s, I, b->img_obs_start.p, N.i_pos.p, Y.img_obs_start.p);
     // the terms and their CSR
-    EditTerms terms{};
     if (L) {
-      const bool meta = b->has_lidar_meta;
       hipLaunchKernelGGL(k_edit_compact_terms, grid(L), dim3(256), 0, s, L, N.lf.p, N.lp.p, b->lidar_point.p, b->lidar_abcd.p,
-                         b->lidar_w.p, meta ? b->lidar_type.p : nullptr, meta ? b->lidar_xyz.p : nullptr, N.l_point.p,
-                         N.l_abcd.p, N.l_w.p, N.l_type.p, N.l_xyz.p);
+                         b->lidar_w.p, meta ? b->lidar_type.p : nullptr, meta ? b->lidar_xyz.p : nullptr, T.lidar_point.p,
+                         T.lidar_abcd.p, T.lidar_w.p, T.lidar_type.p, T.lidar_xyz.p);
       hipLaunchKernelGGL(k_edit_compact_list, grid(L), dim3(256), 0, s, L, b->pt_lidar_list.p, N.lt_flag.p, N.lt_pos.p, N.lp.p,
-                         N.l_list.p);
-      hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)P + 1), dim3(256), 0, s, P, b->pt_lidar_start.p, N.lt_pos.p, N.l_start.p);
-      terms = EditTerms{N.l_start.p, N.l_list.p, N.l_abcd.p, N.l_w.p};
+                         T.pt_lidar_list.p);
+      hipLaunchKernelGGL(k_edit_starts, grid((uint64_t)P + 1), dim3(256), 0, s, P, b->pt_lidar_start.p, N.lt_pos.p,
+                         T.pt_lidar_start.p);
     }
-    PCD_TRY(edit_derive(N, P, I, nslices, O, /*fill_sell=*/true, terms, s));
-    hipLaunchKernelGGL(k_edit_record, dim3(1), dim3(256), 0, s, O, L, I, P, N.pos.p, L ? N.lp.p : nullptr, N.img_seg_start.p,
-                       vrows ? N.v_pos.p : nullptr, b->pt_obs_start.p, N.pt_obs_start.p, N.record.p);
+    PCD_TRY(edit_derive(N, P, I, nslices, O, /*fill_sell=*/true, L ? &T : nullptr, s));
+    hipLaunchKernelGGL(k_edit_record, dim3(1), dim3(256), 0, s, O, L, I, P, N.pos.p, L ? N.lp.p : nullptr, Y.img_seg_start.p,
+                       vrows ? N.v_pos.p : nullptr, b->pt_obs_start.p, Y.pt_obs_start.p, N.record.p);
     PCD_HIP_TRY(hipGetLastError());
   }
-  // the one synchronisation: the counts and the image bounds (O(I) bytes)
-  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p, N.record.p, kRecWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p + kRecWords, N.img_obs_start.p, ((size_t)I + 1) * sizeof(uint32_t),
-                             hipMemcpyDeviceToHost, s));
-  if (info) (void)ev.stop(s);   // rebuild_ms ends here: the wait below completes the event, no second one is needed
-  PCD_HIP_TRY(hipStreamSynchronize(s));
+  PCD_TRY(edit_read_record(N, kRecWords, I, info ? &ev : nullptr, s));
   const uint32_t* rec = N.h_record.p;
   const uint32_t nO = rec[kRecObs], nL = rec[kRecTerms];
-  if (nO)
-    hipLaunchKernelGGL(k_ba_fill_image_major, grid(nO), dim3(256), 0, s, N.img_obs.p, N.obs_point.p, N.obs_xy.p, (uint64_t)nO,
-                       N.img_pt.p, N.img_xy.p);
-  PCD_HIP_TRY(hipGetLastError());
-  // success: the new layout becomes the handle's; the retired buffers are the next call's
-  b->obs_image.swap(N.obs_image); b->obs_point.swap(N.obs_point); b->obs_xy.swap(N.obs_xy);
-  b->pt_obs_start.swap(N.pt_obs_start); b->pt_obs_list.swap(N.pt_obs_list);
-  b->pt_order.swap(N.pt_order); b->slice_start.swap(N.slice_start); b->sell_img.swap(N.sell_img); b->sell_xy.swap(N.sell_xy);
-  b->img_obs_start.swap(N.img_obs_start); b->img_obs.swap(N.img_obs); b->img_pt.swap(N.img_pt); b->img_xy.swap(N.img_xy);
-  b->seg_img.swap(N.seg_img); b->seg_begin.swap(N.seg_begin); b->img_seg_start.swap(N.img_seg_start);
-  if (vrows) b->vobs.swap(N.vobs);
-  if (L) {
-    b->lidar_point.swap(N.l_point); b->lidar_abcd.swap(N.l_abcd); b->lidar_w.swap(N.l_w);
-    if (b->has_lidar_meta) { b->lidar_type.swap(N.l_type); b->lidar_xyz.swap(N.l_xyz); }
-    b->pt_lidar_start.swap(N.l_start); b->pt_lidar_list.swap(N.l_list);
-    b->pt_lidar_cnt.swap(N.l_cnt); b->pt_lidar_first.swap(N.l_first);
-  }
+  float ms = 0.f;
+  PCD_TRY(edit_commit(b, EditCounts{nO, nL, P, nslices, rec[kRecSegs], rec[kRecPoseRows]}, nullptr, terms, kRecWords,
+                      info ? &ev : nullptr, &ms, s));
   if (info) {
     info->num_obs = nO; info->num_obs_removed = O - nO;
     info->num_lidar = nL; info->num_lidar_removed = L - nL;
     info->num_points_emptied = rec[kRecEmptied];
-  }
-  b->O = nO; b->L = nL;
-  b->nseg = rec[kRecSegs];
-  b->n_pose_rows = rec[kRecPoseRows];
-  b->h_img_obs_start.assign(rec + kRecWords, rec + kRecWords + I + 1);
-  b->pose_row_stale = true;
-  ba_schur_drop_structure(b);
-  if (info) {
-    float ms = 0.f;
-    PCD_HIP_TRY(ev.elapsed(&ms));
     info->rebuild_ms = ms;
   }
   return PCD_OK;
@@ -479,10 +458,9 @@ __global__ __launch_bounds__(256) void k_add_record(uint32_t nbad, const uint32_
 static pcd_status add_merge_csr(BaEditScratch& N, const int* d_key, uint32_t A, uint32_t nold, uint32_t nnew, uint32_t O,
                                 const uint32_t* old_start, const uint32_t* old_list, const int* old_key_of_obs,
                                 uint32_t* bad, uint32_t* start, uint32_t* list, hipStream_t s) {
-  auto grid = [](uint64_t n) { return dim3(div_up(n, 256)); };
   if (A) {
     hipLaunchKernelGGL(k_add_keys, grid(A), dim3(256), 0, s, A, d_key, nnew, N.a_key.p, N.a_iota.p, bad);
-    PCD_TRY(sort_pairs(N.prim, N.a_key.p, N.a_key_sorted.p, N.a_iota.p, N.a_row.p, (size_t)A, 0u, length_bits(nnew), s));
+    PCD_TRY(sort_pairs(N.prim, N.a_key.p, N.a_key_sorted.p, N.a_iota.p, N.a_row.p, (size_t)A, 0u, key_bits(nnew), s));
   }
   hipLaunchKernelGGL(k_add_lower, grid((uint64_t)nnew + 1), dim3(256), 0, s, nnew, A, N.a_key_sorted.p, N.a_add.p);
   hipLaunchKernelGGL(k_add_starts, grid((uint64_t)nnew + 1), dim3(256), 0, s, nold, nnew, O, old_start, N.a_add.p, start);
@@ -491,79 +469,54 @@ static pcd_status add_merge_csr(BaEditScratch& N, const int* d_key, uint32_t A, 
   return PCD_OK;
 }
 
-// segments of the grown handle at most: an image that gains a > 0 rows gains at most 1 + a / kImgSeg segments
-static size_t add_seg_bound(const pcd_ba* b, uint64_t A) {
-  return (size_t)b->nseg + (size_t)std::min<uint64_t>(A, (uint64_t)b->I) + (size_t)(A / kImgSeg);
-}
-
-// Every buffer whose size follows from the counts, before the first launch.  Buffers grow here, unlike in edit_reserve.
-static pcd_status add_reserve(pcd_ba* b, uint64_t A, uint64_t Pn) {
+// Every buffer whose size follows from the counts, before the first launch.  Buffers grow here, unlike in edit_reserve;
+// the sliced-ELL copies wait for their size
+static pcd_status add_reserve(pcd_ba* b, size_t A, size_t Pn, unsigned terms) {
   BaEditScratch& N = b->edit_next;
   const size_t O2 = b->O + A, P2 = (size_t)b->P + Pn, I = (size_t)b->I, L = b->L;
-  const size_t ns2 = (P2 + 63) / 64, ntr2 = ns2 * 64, nseg = add_seg_bound(b, A), nb = div_up(A, 256);
-  PCD_TRY(N.obs_image.reserve(at_least_1(O2))); PCD_TRY(N.obs_point.reserve(at_least_1(O2)));
-  PCD_TRY(N.obs_xy.reserve(at_least_1(2 * O2)));
-  PCD_TRY(N.pt_obs_start.reserve(P2 + 1)); PCD_TRY(N.pt_obs_list.reserve(at_least_1(O2)));
-  PCD_TRY(N.pt_order.reserve(ntr2)); PCD_TRY(N.slice_start.reserve(ns2 + 1));
-  PCD_TRY(N.img_obs_start.reserve(I + 1)); PCD_TRY(N.img_obs.reserve(at_least_1(O2)));
-  PCD_TRY(N.img_pt.reserve(at_least_1(O2))); PCD_TRY(N.img_xy.reserve(std::max<size_t>(2 * O2, 2)));
-  PCD_TRY(N.seg_img.reserve(at_least_1(nseg))); PCD_TRY(N.seg_begin.reserve(nseg + 1)); PCD_TRY(N.img_seg_start.reserve(I + 1));
-  if (b->has_cpose) { PCD_TRY(N.vobs.reserve(at_least_1(O2))); PCD_TRY(N.v_flag.reserve(A + 1)); PCD_TRY(N.v_pos.reserve(A + 1)); }
-  PCD_TRY(N.len.reserve(P2)); PCD_TRY(N.len_sorted.reserve(P2)); PCD_TRY(N.iota.reserve(P2));
-  PCD_TRY(N.width.reserve(ns2 + 1)); PCD_TRY(N.seg_cnt.reserve(I + 1));
-  PCD_TRY(N.record.reserve(kAddWords)); PCD_TRY(N.h_record.reserve(kAddWords + I + 1));
-  PCD_TRY(N.l_start.reserve(P2 + 1));
-  if (L) { PCD_TRY(N.l_cnt.reserve(ntr2)); PCD_TRY(N.l_first.reserve(5 * ntr2)); }
+  const size_t ns2 = (P2 + 63) / 64, nb = div_up(A, 256);
+  // segments of the grown handle at most: an image that gains a > 0 rows gains at most 1 + a / kImgSeg segments
+  const size_t nseg = (size_t)b->nseg + (size_t)std::min<uint64_t>(A, (uint64_t)b->I) + (size_t)(A / kImgSeg);
+  PCD_TRY(edit_reserve_shared(N, BaLayoutSizes{O2, P2, I, ns2, nseg, b->has_cpose, 0, 0}, kAddWords));
+  if (b->has_cpose) { PCD_TRY(N.v_flag.reserve(A + 1)); PCD_TRY(N.v_pos.reserve(A + 1)); }
+  PCD_TRY(N.terms.reserve_terms(terms, L, P2, ns2 * 64));
   if (Pn) {
     PCD_TRY(N.points.reserve(3 * P2));
     if (b->has_cpt) PCD_TRY(N.point_const.reserve(P2));
   }
   for (DevBuf<uint32_t>* d : {&N.a_key, &N.a_key_sorted, &N.a_iota, &N.a_row}) PCD_TRY(d->reserve(at_least_1(A)));
   PCD_TRY(N.a_add.reserve(std::max(P2, I) + 1)); PCD_TRY(N.a_bad.reserve(at_least_1(2 * nb)));
-  // the cost partials of the grown handle, as pcd_ba_create sizes them
-  PCD_TRY(b->cost_partial.reserve((size_t)std::max(std::max(1u, div_up(ns2, 2)), cost_sweep_blocks(O2, L)) + 1));
-  // rocPRIM's storage: the largest need over every scan and sort below
-  size_t need = 0, bytes = 0;
-  for (size_t n : {(size_t)A + 1, ns2 + 1, I + 1}) {
-    PCD_HIP_TRY(exclusive_sum_at(nullptr, bytes, N.seg_cnt.p, N.img_seg_start.p, 0u, n, nullptr));
-    need = std::max(need, bytes);
-  }
-  PCD_HIP_TRY(sort_pairs_at(nullptr, bytes, N.len.p, N.len_sorted.p, N.iota.p, reinterpret_cast<uint32_t*>(N.pt_order.p), P2, 0u,
-                            length_bits(O2), nullptr));
-  need = std::max(need, bytes);
-  for (size_t nkeys : {P2, I}) {
-    if (!A) break;
-    PCD_HIP_TRY(sort_pairs_at(nullptr, bytes, N.a_key.p, N.a_key_sorted.p, N.a_iota.p, N.a_row.p, (size_t)A, 0u,
-                              length_bits(nkeys), nullptr));
-    need = std::max(need, bytes);
-  }
-  PCD_TRY(N.prim.reserve(need));
-  return PCD_OK;
+  PCD_TRY(reserve_cost_partial(b, ns2, O2, L));   // the cost partials of the grown handle
+  size_t need = 0;   // the track lengths; the new rows by point and by image (not sorted when there are none)
+  PCD_TRY(prim_storage_u32({A + 1, ns2 + 1, I + 1}, {{P2, key_bits(O2)}, {A, key_bits(P2)}, {A, key_bits(I)}}, need));
+  return N.prim.reserve(need);
 }
 
 static pcd_status add_rebuild(pcd_ba* b, const double* d_points, uint64_t Pn64, const int* d_image, const int* d_point,
                               const double* d_xy, uint64_t A64, hipStream_t s, pcd_ba_add_info* info) {
   BaEditScratch& N = b->edit_next;
+  BaLayout& Y = N.layout;
   const uint32_t O = (uint32_t)b->O, A = (uint32_t)A64, O2 = O + A, L = (uint32_t)b->L, I = (uint32_t)b->I;
   const uint32_t P = (uint32_t)b->P, Pn = (uint32_t)Pn64, P2 = P + Pn, ns2 = (P2 + 63u) / 64u, V = (uint32_t)b->n_pose_rows;
   const uint32_t nb = div_up(A, 256);
   const bool vrows = b->has_cpose;
-  PCD_TRY(add_reserve(b, A, Pn));
+  // the terms this call builds: the index's start (the new points have none) and the per-track copies in the new order
+  const unsigned terms = kTermStart | (L ? kTermTracks : 0u);
+  PCD_TRY(add_reserve(b, A, Pn, terms));
   EventPair ev;
   if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
-  auto grid = [](uint64_t n) { return dim3(div_up(n, 256)); };
   {
     ScopedKernelTimer t("ba_add_merge", s);
     // the rows and the points: the old ones, then the new ones
     if (O) {
-      PCD_HIP_TRY(hipMemcpyAsync(N.obs_image.p, b->obs_image.p, (size_t)O * sizeof(int), hipMemcpyDeviceToDevice, s));
-      PCD_HIP_TRY(hipMemcpyAsync(N.obs_point.p, b->obs_point.p, (size_t)O * sizeof(int), hipMemcpyDeviceToDevice, s));
-      PCD_HIP_TRY(hipMemcpyAsync(N.obs_xy.p, b->obs_xy.p, 2 * (size_t)O * sizeof(double), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(Y.obs_image.p, b->obs_image.p, (size_t)O * sizeof(int), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(Y.obs_point.p, b->obs_point.p, (size_t)O * sizeof(int), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(Y.obs_xy.p, b->obs_xy.p, 2 * (size_t)O * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     if (A) {
-      PCD_HIP_TRY(hipMemcpyAsync(N.obs_image.p + O, d_image, (size_t)A * sizeof(int), hipMemcpyDeviceToDevice, s));
-      PCD_HIP_TRY(hipMemcpyAsync(N.obs_point.p + O, d_point, (size_t)A * sizeof(int), hipMemcpyDeviceToDevice, s));
-      PCD_HIP_TRY(hipMemcpyAsync(N.obs_xy.p + 2 * (size_t)O, d_xy, 2 * (size_t)A * sizeof(double), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(Y.obs_image.p + O, d_image, (size_t)A * sizeof(int), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(Y.obs_point.p + O, d_point, (size_t)A * sizeof(int), hipMemcpyDeviceToDevice, s));
+      PCD_HIP_TRY(hipMemcpyAsync(Y.obs_xy.p + 2 * (size_t)O, d_xy, 2 * (size_t)A * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     if (Pn) {
       PCD_HIP_TRY(hipMemcpyAsync(N.points.p, b->points.p, 3 * (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -575,69 +528,36 @@ static pcd_status add_rebuild(pcd_ba* b, const double* d_points, uint64_t Pn64, 
     }
     // the track CSR over P2 points and the image CSR
     PCD_TRY(add_merge_csr(N, d_point, A, P, P2, O, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_point.p, N.a_bad.p,
-                          N.pt_obs_start.p, N.pt_obs_list.p, s));
+                          Y.pt_obs_start.p, Y.pt_obs_list.p, s));
     PCD_TRY(add_merge_csr(N, d_image, A, I, I, O, b->img_obs_start.p, b->img_obs.p, b->obs_image.p, N.a_bad.p + nb,
-                          N.img_obs_start.p, N.img_obs.p, s));
+                          Y.img_obs_start.p, Y.img_obs.p, s));
     if (vrows) {
       hipLaunchKernelGGL(k_add_vflag, grid((uint64_t)A + 1), dim3(256), 0, s, A, d_image, I, b->image_const_pose.p, N.v_flag.p);
       PCD_TRY(scan_flags(N, N.v_flag.p, N.v_pos.p, (size_t)A + 1, s));
       if (V + A)
         hipLaunchKernelGGL(k_add_vobs, grid((uint64_t)V + A), dim3(256), 0, s, V, A, O, V == O ? nullptr : b->vobs.p,
-                           N.v_flag.p, N.v_pos.p, N.vobs.p);
+                           N.v_flag.p, N.v_pos.p, Y.vobs.p);
     }
-    // the terms stay; their CSR covers the new points, which have none
-    hipLaunchKernelGGL(k_add_extend, grid((uint64_t)P2 + 1), dim3(256), 0, s, P, P2, L, b->pt_lidar_start.p, N.l_start.p);
+    hipLaunchKernelGGL(k_add_extend, grid((uint64_t)P2 + 1), dim3(256), 0, s, P, P2, L, b->pt_lidar_start.p,
+                       N.terms.pt_lidar_start.p);
   }
   {
     ScopedKernelTimer t("ba_add_rebuild", s);
-    EditTerms terms{};
-    if (L) terms = EditTerms{N.l_start.p, b->pt_lidar_list.p, b->lidar_abcd.p, b->lidar_w.p};
-    // the sliced-ELL copies wait for their size: the number of slots is in the record
-    PCD_TRY(edit_derive(N, P2, I, ns2, O2, /*fill_sell=*/false, terms, s));
-    hipLaunchKernelGGL(k_add_record, dim3(1), dim3(256), 0, s, 2 * nb, N.a_bad.p, I, N.img_seg_start.p, A, V,
-                       vrows ? N.v_pos.p : nullptr, ns2, N.slice_start.p, N.record.p);
+    // the sliced-ELL copies wait for their size: the number of slots is in the record.  The per-track copies read the
+    // live rows and list.
+    PCD_TRY(edit_derive(N, P2, I, ns2, O2, /*fill_sell=*/false, L ? b : nullptr, s));
+    hipLaunchKernelGGL(k_add_record, dim3(1), dim3(256), 0, s, 2 * nb, N.a_bad.p, I, Y.img_seg_start.p, A, V,
+                       vrows ? N.v_pos.p : nullptr, ns2, Y.slice_start.p, N.record.p);
     PCD_HIP_TRY(hipGetLastError());
   }
-  // the one synchronisation: the verdict, the counts and the image bounds (O(I) bytes)
-  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p, N.record.p, kAddWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p + kAddWords, N.img_obs_start.p, ((size_t)I + 1) * sizeof(uint32_t),
-                             hipMemcpyDeviceToHost, s));
-  if (info) (void)ev.stop(s);
-  PCD_HIP_TRY(hipStreamSynchronize(s));
+  PCD_TRY(edit_read_record(N, kAddWords, I, info ? &ev : nullptr, s));
   const uint32_t* rec = N.h_record.p;
-  PCD_REQUIRE(!rec[kAddBad], "obs_image / obs_point of a new row out of range");   // nothing has been swapped in
-  const size_t nslots = rec[kAddSlots];
-  PCD_TRY(N.sell_img.reserve(at_least_1(nslots))); PCD_TRY(N.sell_xy.reserve(std::max<size_t>(2 * nslots, 2)));
-  if (nslots)
-    hipLaunchKernelGGL(k_ba_fill_sell, grid((uint64_t)ns2 * 64), dim3(256), 0, s, N.pt_order.p, N.slice_start.p,
-                       N.pt_obs_start.p, N.pt_obs_list.p, N.obs_image.p, N.obs_xy.p, (int)ns2, N.sell_img.p, N.sell_xy.p);
-  if (O2)
-    hipLaunchKernelGGL(k_ba_fill_image_major, grid(O2), dim3(256), 0, s, N.img_obs.p, N.obs_point.p, N.obs_xy.p, (uint64_t)O2,
-                       N.img_pt.p, N.img_xy.p);
-  PCD_HIP_TRY(hipGetLastError());
-  // success: the new layout becomes the handle's; the retired buffers are the next edit's
-  b->obs_image.swap(N.obs_image); b->obs_point.swap(N.obs_point); b->obs_xy.swap(N.obs_xy);
-  b->pt_obs_start.swap(N.pt_obs_start); b->pt_obs_list.swap(N.pt_obs_list);
-  b->pt_order.swap(N.pt_order); b->slice_start.swap(N.slice_start); b->sell_img.swap(N.sell_img); b->sell_xy.swap(N.sell_xy);
-  b->img_obs_start.swap(N.img_obs_start); b->img_obs.swap(N.img_obs); b->img_pt.swap(N.img_pt); b->img_xy.swap(N.img_xy);
-  b->seg_img.swap(N.seg_img); b->seg_begin.swap(N.seg_begin); b->img_seg_start.swap(N.img_seg_start);
-  if (vrows) b->vobs.swap(N.vobs);
-  b->pt_lidar_start.swap(N.l_start);
-  if (L) { b->pt_lidar_cnt.swap(N.l_cnt); b->pt_lidar_first.swap(N.l_first); }
-  if (Pn) {
-    b->points.swap(N.points);
-    if (b->has_cpt) b->point_const.swap(N.point_const);
-  }
-  b->O = O2; b->P = (int)P2; b->nslices = (int)ns2;
-  b->nseg = rec[kAddSegs];
-  b->n_pose_rows = rec[kAddPoseRows];
-  b->h_img_obs_start.assign(rec + kAddWords, rec + kAddWords + I + 1);
-  b->pose_row_stale = true;
-  ba_schur_drop_structure(b);
+  PCD_REQUIRE(!rec[kAddBad], "obs_image / obs_point of a new row out of range");   // nothing swapped, no slot reserved
+  float ms = 0.f;
+  PCD_TRY(edit_commit(b, EditCounts{O2, L, P2, ns2, rec[kAddSegs], rec[kAddPoseRows]}, rec + kAddSlots, terms, kAddWords,
+                      info ? &ev : nullptr, &ms, s));
   if (info) {
     info->num_obs = O2; info->num_points = P2; info->num_pose_rows = b->n_pose_rows;
-    float ms = 0.f;
-    PCD_HIP_TRY(ev.elapsed(&ms));
     info->rebuild_ms = ms;
   }
   return PCD_OK;

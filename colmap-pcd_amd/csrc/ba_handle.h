@@ -1,6 +1,6 @@
 // ba_handle.h -- the bundle-adjustment handle as every BA unit sees it, and the sizes builder and launchers must agree
-// on (kImgSeg, kCostBlocks, cost_blocks, the element counts of the block form).  Internal; no kernel is defined here
-// (three that several units launch are declared).
+// on (kImgSeg, kCostBlocks, cost_blocks, the element counts of the block form).  Internal; no kernel is defined or declared
+// here.  What the handle derives from its observations and LiDAR terms is named once, as BaLayout and BaTerms (below).
 //   ba_build.hip  makes and destroys it: pcd_ba_create uploads the problem and builds the derived layouts below
 //   ba.hip        evaluates on it: the kernels that read BaDev, and every pcd_ba_evaluate* / filter entry point
 //   ba_solve.hip  point elimination, PCG, LM loop (its own state hangs off pcd_ba::schur)
@@ -26,25 +26,12 @@ struct BaDev {
   const double* points; const uint8_t* point_const;
   const int* obs_image; const int* obs_point; const double* obs_xy;
   const int* lidar_point; const double* lidar_abcd; const double* lidar_w;
-  // per-track (sliced ELL, length-sorted) and per-image (contiguous) copies of the observations
-  const int* pt_order;            // [nslices*64]  thread -> point id (-1 = padding)
-  const uint32_t* slice_start;    // [nslices+1]   first slot of each 64-track slice
-  const int* sell_img;            // [nslots]      image of the observation, -1 = padding
-  const double* sell_xy;          // [nslots][2]
+  // the derived layouts: BaLayout and BaTerms below say what each array holds
+  const int* pt_order; const uint32_t* slice_start; const int* sell_img; const double* sell_xy;
   const uint32_t* pt_lidar_start; const uint32_t* pt_lidar_list;
-  // The LiDAR terms in the order of k_ba_points' threads (both nullptr when L == 0).  The terms change only as a whole
-  // (pcd_ba_create, or pcd_ba_set_lidar_device / pcd_ba_associate_lidar_device, which rebuild these two arrays with the
-  // CSR above and swap all of them in together: ba_lidar.hip), never between the launches of one evaluation, so the
-  // kernel reads its one plane per point coalesced and ahead of everything else, not through point -> list -> term;
-  // only a second or third term of a point goes through the lists.
-  const uint32_t* pt_lidar_cnt;   // [nslices*64] number of LiDAR terms of the track of thread t
-  const double* pt_lidar_first;   // [5][nslices*64] plane (a, b, c, d) and weight of the first of them, component-major
-  const uint32_t* img_obs_start;  // [I+1]
-  const int* img_pt;              // [O] point of the e-th observation of the image-major order
-  const uint32_t* img_obs;        // [O] its index in the caller's observation order (W is written there)
-  const uint32_t* seg_img;        // [nseg] image of each segment of <= kImgSeg observations (image-major order)
-  const uint32_t* seg_begin;      // [nseg+1] first observation (image-major position) of each segment
-  const uint32_t* img_seg_start;  // [I+1] segments of each image
+  const uint32_t* pt_lidar_cnt; const double* pt_lidar_first;   // both nullptr when L == 0
+  const uint32_t* img_obs_start; const int* img_pt; const uint32_t* img_obs;
+  const uint32_t* seg_img; const uint32_t* seg_begin; const uint32_t* img_seg_start;
   const uint8_t* cam_refine;      // [cam_params_len] 1 = parameter optimised (nullptr: all constant)
   const uint32_t* cam_img_start;  // [C+1] images of each camera (CSR, ascending image index)
   const uint32_t* cam_img_list;
@@ -57,10 +44,111 @@ struct BaDev {
   int shared_cam;                 // >= 0: every image maps to this camera (one physical camera, the usual dataset); -1: per image
 };
 
-// Scratch of the device rebuild of the LiDAR terms (ba_lidar.hip).  The first group is the layout under construction:
-// on success it is swapped with the live arrays of pcd_ba, so the buffers a call retires are the next call's.
+// ---- the derived state of a handle -------------------------------------------------------------------------------
+// It is derived in three places, byte for byte the same -- on creation (ba_build.hip, host counting sorts), when the terms
+// change (ba_lidar.hip), when observations are dropped or added (ba_edit.hip); WHAT is derived is listed here alone.  pcd_ba
+// is a BaLayout and a BaTerms; a rebuild of a live handle reserves and writes a second one and swaps it in on success, so
+// the buffers a call retires are the next call's scratch.
+// The swap invariant: a live buffer is never exchanged for one that the call did not both reserve and write.  A rebuild
+// therefore names the groups it builds once, for its reserve and its swap alike.  With L == 0 no per-track copies are built
+// (the kernels get nullptr) and an edit builds no term group at all: the at_least_1 buffers of pcd_ba_create stay.
+inline size_t at_least_1(size_t n) { return std::max<size_t>(n, 1); }   // for a buffer a kernel is handed even when its count is 0
+
+// The sizes of a BaLayout: pcd_ba's counts (nseg: an upper bound will do), whether some pose is constant (vobs exists) and
+// the capacity of the sliced-ELL copies (0: reserved later, when the slot count is known: reserve_sell)
+struct BaLayoutSizes { size_t O, P, I, nslices, nseg; bool pose_rows; size_t sell_img, sell_xy; };
+// What follows from the observation rows
+struct BaLayout {
+  DevBuf<int> obs_image, obs_point;   // [O] the rows, in the caller's order
+  DevBuf<double> obs_xy;              // [O][2]
+  // the track CSR (point -> its observations, ascending): the sliced-ELL fill and pcd_ba_filter_tracks read it
+  DevBuf<uint32_t> pt_obs_start, pt_obs_list;
+  // per-track copies of the observations: sliced ELL, the tracks in ascending order of length (ties: ascending point id)
+  DevBuf<int> pt_order;               // [nslices*64]  thread of k_ba_points -> point id (-1 = padding)
+  DevBuf<uint32_t> slice_start;       // [nslices+1]   first slot of each 64-track slice
+  DevBuf<int> sell_img;               // [nslots]      image of the observation, -1 = padding
+  DevBuf<double> sell_xy;             // [nslots][2]
+  // per-image copies: the image-major order, contiguous
+  DevBuf<uint32_t> img_obs_start;     // [I+1]
+  DevBuf<uint32_t> img_obs;           // [O] index of the e-th image-major observation in the caller's order (W is written there)
+  DevBuf<int> img_pt;                 // [O] its point
+  DevBuf<double> img_xy;              // [O][2]
+  DevBuf<uint32_t> seg_img;           // [nseg] image of each segment of <= kImgSeg observations (image-major order)
+  DevBuf<uint32_t> seg_begin;         // [nseg+1] first observation (image-major position) of each segment
+  DevBuf<uint32_t> img_seg_start;     // [I+1] segments of each image
+  DevBuf<uint32_t> vobs;              // [n_pose_rows] observation of every packed pose row (only when some pose is constant)
+
+  pcd_status reserve_layout(const BaLayoutSizes& z) {
+    const size_t O1 = at_least_1(z.O);
+    PCD_TRY(obs_image.reserve(O1)); PCD_TRY(obs_point.reserve(O1)); PCD_TRY(obs_xy.reserve(at_least_1(2 * z.O)));
+    PCD_TRY(pt_obs_start.reserve(z.P + 1)); PCD_TRY(pt_obs_list.reserve(O1));
+    PCD_TRY(pt_order.reserve(at_least_1(z.nslices * 64))); PCD_TRY(slice_start.reserve(z.nslices + 1));
+    PCD_TRY(sell_img.reserve(z.sell_img)); PCD_TRY(sell_xy.reserve(z.sell_xy));
+    PCD_TRY(img_obs_start.reserve(z.I + 1)); PCD_TRY(img_obs.reserve(O1));
+    PCD_TRY(img_pt.reserve(O1)); PCD_TRY(img_xy.reserve(std::max<size_t>(2 * z.O, 2)));
+    PCD_TRY(seg_img.reserve(at_least_1(z.nseg))); PCD_TRY(seg_begin.reserve(z.nseg + 1)); PCD_TRY(img_seg_start.reserve(z.I + 1));
+    if (z.pose_rows) PCD_TRY(vobs.reserve(O1));
+    return PCD_OK;
+  }
+  pcd_status reserve_sell(size_t nslots) {
+    PCD_TRY(sell_img.reserve(at_least_1(nslots)));
+    return sell_xy.reserve(std::max<size_t>(2 * nslots, 2));
+  }
+  // every buffer; vobs only when the call built it (pose_rows as it reserved)
+  void swap_layout(BaLayout& o, bool pose_rows) {
+    obs_image.swap(o.obs_image); obs_point.swap(o.obs_point); obs_xy.swap(o.obs_xy);
+    pt_obs_start.swap(o.pt_obs_start); pt_obs_list.swap(o.pt_obs_list);
+    pt_order.swap(o.pt_order); slice_start.swap(o.slice_start); sell_img.swap(o.sell_img); sell_xy.swap(o.sell_xy);
+    img_obs_start.swap(o.img_obs_start); img_obs.swap(o.img_obs); img_pt.swap(o.img_pt); img_xy.swap(o.img_xy);
+    seg_img.swap(o.seg_img); seg_begin.swap(o.seg_begin); img_seg_start.swap(o.img_seg_start);
+    if (pose_rows) vobs.swap(o.vobs);
+  }
+};
+
+// The LiDAR terms and what follows from them, in the three groups the rebuilds replace (the rows' meta and the index's
+// list are parts a rebuild may leave out):
+//   removal (L > 0)   rows (meta when the handle has it), index, per-track copies
+//   addition          the index's start alone (the terms stay, the new points have none); per-track copies when L > 0
+//   the terms change  rows with meta, index; per-track copies when the new L > 0
+enum : unsigned { kTermRows = 1, kTermMeta = 2, kTermStart = 4, kTermList = 8, kTermTracks = 16, kTermIndex = kTermStart | kTermList };
+struct BaTerms {
+  // the rows: point, plane (a, b, c, d) and weight of each of the L terms; its pcd_lidar_type and LiDAR point, for the
+  // outlier filter.  pcd_ba_create knows neither: the two do not exist until pcd_ba_lidar_device asks for them (zeros)
+  // or pcd_ba_set_lidar_device installs them (pcd_ba::has_lidar_meta).
+  DevBuf<int> lidar_point; DevBuf<double> lidar_abcd, lidar_w;
+  DevBuf<uint8_t> lidar_type; DevBuf<double> lidar_xyz;
+  // the index: CSR point -> its terms, ascending term number
+  DevBuf<uint32_t> pt_lidar_start, pt_lidar_list;
+  // The terms in the order of k_ba_points' threads (not built when L == 0).  The terms and the thread order change only
+  // as a whole, never between the launches of one evaluation, so the kernel reads its one plane per point coalesced and
+  // ahead of everything else, not through point -> list -> term; only a second or third term of a point goes through
+  // the lists.
+  DevBuf<uint32_t> pt_lidar_cnt;      // [nslices*64] number of LiDAR terms of the track of thread t
+  DevBuf<double> pt_lidar_first;      // [5][nslices*64] plane (a, b, c, d) and weight of the first of them, component-major
+
+  // L terms over P points and ntr = nslices*64 threads
+  pcd_status reserve_terms(unsigned groups, size_t L, size_t P, size_t ntr) {
+    const size_t L1 = at_least_1(L);
+    if (groups & kTermRows) { PCD_TRY(lidar_point.reserve(L1)); PCD_TRY(lidar_abcd.reserve(at_least_1(4 * L))); PCD_TRY(lidar_w.reserve(L1)); }
+    if (groups & kTermMeta) { PCD_TRY(lidar_type.reserve(L1)); PCD_TRY(lidar_xyz.reserve(at_least_1(3 * L))); }
+    if (groups & kTermStart) PCD_TRY(pt_lidar_start.reserve(P + 1));
+    if (groups & kTermList) PCD_TRY(pt_lidar_list.reserve(L1));
+    if (groups & kTermTracks) { PCD_TRY(pt_lidar_cnt.reserve(at_least_1(ntr))); PCD_TRY(pt_lidar_first.reserve(at_least_1(5 * ntr))); }
+    return PCD_OK;
+  }
+  // groups: those the call reserved with and wrote in full
+  void swap_terms(BaTerms& o, unsigned groups) {
+    if (groups & kTermRows) { lidar_point.swap(o.lidar_point); lidar_abcd.swap(o.lidar_abcd); lidar_w.swap(o.lidar_w); }
+    if (groups & kTermMeta) { lidar_type.swap(o.lidar_type); lidar_xyz.swap(o.lidar_xyz); }
+    if (groups & kTermStart) pt_lidar_start.swap(o.pt_lidar_start);
+    if (groups & kTermList) pt_lidar_list.swap(o.pt_lidar_list);
+    if (groups & kTermTracks) { pt_lidar_cnt.swap(o.pt_lidar_cnt); pt_lidar_first.swap(o.pt_lidar_first); }
+  }
+};
+
+// Scratch of the device rebuild of the LiDAR terms (ba_lidar.hip): the terms under construction, then the work buffers
 struct BaLidarScratch {
-  DevBuf<int> point; DevBuf<double> abcd, w, xyz, first; DevBuf<uint8_t> type; DevBuf<uint32_t> start, list, cnt;
+  BaTerms terms;
   DevBuf<uint32_t> flag, pos, part, status, keys, iota;   // per row: kept / position; per workgroup and total: the record
   DevBuf<char> prim;                                      // rocPRIM temporary storage (scan, sort)
   PinnedBuf<uint32_t> h_status;
@@ -72,13 +160,10 @@ struct BaLidarScratch {
   PinnedBuf<uint64_t> h_count;
 };
 
-// Scratch of pcd_ba_remove_observations_device and pcd_ba_add_observations_device (ba_edit.hip).  The first two groups are the layouts under construction:
-// on success they are swapped with the live arrays of pcd_ba, so the buffers a call retires are the next call's.
+// Scratch of the two edits (ba_edit.hip): the layout and the terms under construction, then the work buffers
 struct BaEditScratch {
-  DevBuf<int> obs_image, obs_point, pt_order, sell_img, img_pt;
-  DevBuf<double> obs_xy, sell_xy, img_xy;
-  DevBuf<uint32_t> pt_obs_start, pt_obs_list, slice_start, img_obs_start, img_obs, seg_img, seg_begin, img_seg_start, vobs;
-  DevBuf<int> l_point; DevBuf<double> l_abcd, l_w, l_xyz, l_first; DevBuf<uint8_t> l_type; DevBuf<uint32_t> l_start, l_list, l_cnt;
+  BaLayout layout;
+  BaTerms terms;
   // keep flags and their scans (n + 1 entries each: the last scan value is the count): observations in the caller's order,
   // through the track lists, through the image lists, the variable-pose ones; terms in term order, through the point lists
   DevBuf<uint32_t> flag, pos, t_flag, t_pos, i_flag, i_pos, v_flag, v_pos, lf, lp, lt_flag, lt_pos;
@@ -98,8 +183,7 @@ struct BaSchurDelete { void operator()(BaSchur* s) const; };
 
 // Element counts of the block form, each written once: a vector over n images or slots, n 6x6 blocks (per image; the
 // reduced system's diagonal or pair blocks), the 6x3 blocks W / Y of O observations, the 3x3 blocks of P points and a
-// vector over them.  at_least_1: for a buffer a kernel is handed even when its count is 0.
-inline size_t at_least_1(size_t n) { return std::max<size_t>(n, 1); }
+// vector over them.
 inline size_t slot_vec(uint64_t n) { return 6 * (size_t)n; }
 inline size_t blocks_6x6(uint64_t n) { return 36 * (size_t)n; }
 inline size_t obs_blocks(uint64_t O) { return 18 * (size_t)O; }
@@ -134,24 +218,16 @@ void ba_schur_invalidate(pcd_ba* b);
 // does (ba_edit.hip, when the observations change).  Scratch buffers stay.
 void ba_schur_drop_structure(pcd_ba* b);
 
-// Kernels one unit defines and another launches too (the handle's derived layouts are made in three places: on creation,
-// when the terms change, when observations are dropped or added).  ba_build.hip: the sliced-ELL fill and the image-major copies;
-// ba_lidar.hip: the terms of every track in the thread order of k_ba_points.
-__global__ void k_ba_fill_sell(const int* __restrict__ order, const uint32_t* __restrict__ slice_start,
-                               const uint32_t* __restrict__ pt_start, const uint32_t* __restrict__ pt_list,
-                               const int* __restrict__ obs_image, const double* __restrict__ obs_xy, int nslices,
-                               int* __restrict__ sell_img, double* __restrict__ sell_xy);
-__global__ void k_ba_fill_image_major(const uint32_t* __restrict__ img_obs, const int* __restrict__ obs_point,
-                                      const double* __restrict__ obs_xy, uint64_t O, int* __restrict__ img_pt,
-                                      double* __restrict__ img_xy);
-__global__ __launch_bounds__(256) void k_lidar_tracks(uint32_t ntr, const int* __restrict__ order,
-                                                      const uint32_t* __restrict__ start, const uint32_t* __restrict__ list,
-                                                      const double* __restrict__ abcd, const double* __restrict__ w,
-                                                      uint32_t* __restrict__ cnt, double* __restrict__ first);
+// The fills the derivations share, each launched in one place, beside its kernel.  ba_build.hip: the sliced-ELL copies of y
+// and its image-major copies (no launch when O == 0).  ba_lidar.hip: the per-track copies of `next` in the thread order of
+// y, from next's own pt_lidar_start and the list, planes and weights of `rows` (the addition: the live ones; else next).
+void launch_fill_sell(const BaLayout& y, int nslices, hipStream_t s);
+void launch_fill_image_major(const BaLayout& y, uint64_t O, hipStream_t s);
+void launch_lidar_tracks(const BaLayout& y, int nslices, const BaTerms& rows, BaTerms& next, hipStream_t s);
 
 }  // namespace pcd
 
-struct pcd_ba {
+struct pcd_ba : pcd::BaLayout, pcd::BaTerms {
   int device = 0;
   int C = 0, I = 0, P = 0, nslices = 0;
   uint64_t O = 0, L = 0, cam_params_len = 0;
@@ -159,8 +235,8 @@ struct pcd_ba {
   double loss_scale = 1.0;
   int uniform_model = -1;  // >= 0: every camera has this model
   int shared_cam = -1;     // >= 0: every image maps to this camera (BaDev::shared_cam)
-  pcd::DevBuf<int> cam_model, cam_off, image_cam, obs_image, obs_point, lidar_point, pt_order, sell_img, img_pt;
-  pcd::DevBuf<double> cam_params, poses, points, obs_xy, lidar_abcd, lidar_w, sell_xy, img_xy, pt_lidar_first;
+  pcd::DevBuf<int> cam_model, cam_off, image_cam;
+  pcd::DevBuf<double> cam_params, poses, points;
   pcd::DevBuf<uint8_t> image_const_pose, image_const_tvec, point_const;
   bool has_cpose = false, has_ctvec = false, has_cpt = false;
   // host mirrors of what pcd_ba_project_lidar_device decides on the host (focal lengths, the coefficient latch, the
@@ -168,15 +244,10 @@ struct pcd_ba {
   std::vector<double> h_cam_params;
   std::vector<int> h_cam_model, h_cam_off, h_image_cam;
   std::vector<uint32_t> h_img_obs_start;
-  // per term, beside lidar_point / lidar_abcd / lidar_w: its pcd_lidar_type and LiDAR point, for the outlier filter.
-  // pcd_ba_create knows neither: the buffers then do not exist until pcd_ba_lidar_device asks for them (zeros).
-  pcd::DevBuf<uint8_t> lidar_type;
-  pcd::DevBuf<double> lidar_xyz;
-  bool has_lidar_meta = false;
+  bool has_lidar_meta = false;   // lidar_type / lidar_xyz exist (BaTerms)
   pcd::BaLidarScratch lidar_next;
   pcd::BaEditScratch edit_next;
-  pcd::DevBuf<uint32_t> slice_start, pt_lidar_start, pt_lidar_list, img_obs_start, img_obs, cam_img_start, cam_img_list;
-  pcd::DevBuf<uint32_t> seg_img, seg_begin, img_seg_start, pt_lidar_cnt;
+  pcd::DevBuf<uint32_t> cam_img_start, cam_img_list;
   uint32_t nseg = 0;
   pcd::DevBuf<double> img_partial;
   pcd::DevBuf<uint8_t> cam_refine;
@@ -192,14 +263,11 @@ struct pcd_ba {
   std::vector<uint32_t> h_pose_row;
   bool pose_row_stale = false;
   uint64_t n_pose_rows = 0;
-  pcd::DevBuf<uint32_t> vobs;            // [n_pose_rows] observation of every packed row
   pcd::DevBuf<double> p_jq, p_jt;        // packed pose Jacobians (only when some pose is constant)
   pcd::PinnedBuf<double> h_blocks;       // residuals | jac_q | jac_t | jac_X | jac_lidar | jac_cam
   // pcd_ba_evaluate_blocks_compact: records and packed camera blocks (h_blocks is shared with the full route)
   int cam_stride = 0;                    // largest pcd_camera_num_params over the cameras
   pcd::DevBuf<double> o_rec, p_jc;
-  // the track CSR (point -> its observations, ascending): the sliced-ELL fill and pcd_ba_filter_tracks read it
-  pcd::DevBuf<uint32_t> pt_obs_start, pt_obs_list;
   // filter scratch; f_sq / f_depth also stage pcd_ba_observation_errors
   pcd::DevBuf<double> f_sq, f_depth, f_part, f_summary;
   pcd::DevBuf<uint8_t> f_u8;
@@ -236,11 +304,16 @@ struct pcd_ba {
 namespace pcd {
 
 // Grid of the kernel that writes cost_partial[blockIdx.x]: k_ba_points takes two 64-track slices per workgroup,
-// k_ba_cost sweeps the residual blocks with a capped grid.  pcd_ba_create sizes cost_partial from the SAME function.
-// The sweep's grid alone, for a term count the handle does not have yet (ba_lidar.hip sizes cost_partial before the swap).
+// k_ba_cost sweeps the residual blocks with a capped grid.
+inline unsigned cost_point_blocks(size_t nslices) { return std::max(1u, div_up(nslices, 2)); }
 inline unsigned cost_sweep_blocks(uint64_t O, uint64_t L) { return std::max(1u, std::min(kCostBlocks, div_up(O + L, 256))); }
 inline unsigned cost_blocks(const pcd_ba* b, bool want_blocks) {
-  return want_blocks ? std::max(1u, div_up((size_t)b->nslices, 2)) : cost_sweep_blocks(b->O, b->L);
+  return want_blocks ? cost_point_blocks((size_t)b->nslices) : cost_sweep_blocks(b->O, b->L);
+}
+// cost_partial from the SAME functions: one partial per workgroup of the larger of the two grids, for counts the handle
+// may not have yet (a rebuild sizes it before its swap)
+inline pcd_status reserve_cost_partial(pcd_ba* b, size_t nslices, uint64_t O, uint64_t L) {
+  return b->cost_partial.reserve((size_t)std::max(cost_point_blocks(nslices), cost_sweep_blocks(O, L)) + 1);
 }
 
 }  // namespace pcd

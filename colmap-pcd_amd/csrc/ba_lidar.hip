@@ -12,8 +12,8 @@
 //   sort_pairs       (point, term), stable, only when the terms' points are not already non-decreasing
 //   k_lidar_bounds   CSR bounds of every point by bisection of the sorted points
 //   k_lidar_tracks   thread of k_ba_points -> number of terms and the first of them, component-major
-// No atomics; every order is that of the rows: nothing depends on the launch geometry.  The new layout is built in
-// pcd_ba::lidar_next and swapped in at the end; a refusal returns before the swap.
+// No atomics; every order is that of the rows: nothing depends on the launch geometry.  The new terms are a BaTerms
+// (ba_handle.h) built in pcd_ba::lidar_next and swapped in at the end, group by group; a refusal returns before the swap.
 // pcd_ba_project_lidar_device makes its rows here too, in front of the same rebuild: the projector (proj.h)
 // writes found / lidar6 per observation, k_lidar_proj_pick picks per track, k_lidar_proj_merge folds the Proj rows into the
 // association's, k_lidar_proj_count* sum the counts of the info record.
@@ -177,6 +177,11 @@ __global__ __launch_bounds__(256) void k_lidar_tracks(uint32_t ntr, const int* _
   }
   cnt[t] = n;
   for (int k = 0; k < 5; ++k) first[(size_t)k * ntr + t] = f[k];
+}
+void launch_lidar_tracks(const BaLayout& y, int nslices, const BaTerms& rows, BaTerms& next, hipStream_t s) {
+  const uint32_t ntr = (uint32_t)nslices * 64u;
+  hipLaunchKernelGGL(k_lidar_tracks, dim3(div_up(ntr, 256)), dim3(256), 0, s, ntr, y.pt_order.p, next.pt_lidar_start.p,
+                     rows.pt_lidar_list.p, rows.lidar_abcd.p, rows.lidar_w.p, next.pt_lidar_cnt.p, next.pt_lidar_first.p);
 }
 
 // ---- pcd_ba_project_lidar_device ------------------------------------------------------------------------
@@ -353,42 +358,34 @@ static pcd_status lidar_rebuild(pcd_ba* b, uint64_t Q, const int32_t* d_point, c
       return PCD_ERR_INVALID;
     }
   const uint32_t L = hs.L;
-  const size_t ntr = (size_t)b->nslices * 64;
-  // the layout under construction, sized as pcd_ba_create sizes the live one
-  PCD_TRY(N.point.reserve(std::max<size_t>(L, 1))); PCD_TRY(N.abcd.reserve(std::max<size_t>(4 * (size_t)L, 1)));
-  PCD_TRY(N.w.reserve(std::max<size_t>(L, 1))); PCD_TRY(N.type.reserve(std::max<size_t>(L, 1)));
-  PCD_TRY(N.xyz.reserve(std::max<size_t>(3 * (size_t)L, 1)));
-  PCD_TRY(N.start.reserve((size_t)P + 1)); PCD_TRY(N.list.reserve(std::max<size_t>(L, 1)));
-  if (L) { PCD_TRY(N.cnt.reserve(std::max<size_t>(ntr, 1))); PCD_TRY(N.first.reserve(std::max<size_t>(5 * ntr, 1))); }
+  // what this call builds: the rows with their meta and the index, sized as pcd_ba_create sizes the live ones; the
+  // per-track copies only when there are terms
+  BaTerms& T = N.terms;
+  const unsigned built = kTermRows | kTermMeta | kTermIndex | (L ? kTermTracks : 0u);
+  PCD_TRY(T.reserve_terms(built, L, (size_t)P, (size_t)b->nslices * 64));
   const bool sorted = !hs.part.unsorted;
   if (L && !sorted) { PCD_TRY(N.keys.reserve(L)); PCD_TRY(N.iota.reserve(L)); }
-  // one cost partial per workgroup of the larger of the two cost-producing grids: the sweep's follows O + L
-  PCD_TRY(b->cost_partial.reserve((size_t)std::max(cost_blocks(b, true), cost_sweep_blocks(b->O, L)) + 1));
+  PCD_TRY(reserve_cost_partial(b, (size_t)b->nslices, b->O, L));   // the sweep's grid follows O + L
   {
     ScopedKernelTimer t("ba_lidar_rebuild", s);
     LidarWeights wt;
     for (int k = 0; k < 4; ++k) wt.w[k] = weight[k];
     if (L)
       hipLaunchKernelGGL(k_lidar_compact, dim3(nb), dim3(256), 0, s, q32, N.flag.p, N.pos.p, d_point, d_type, d_abcd, d_xyz,
-                         wt, N.point.p, N.abcd.p, N.w.p, N.type.p, N.xyz.p, sorted ? N.list.p : N.iota.p);
-    const uint32_t* sorted_pt = reinterpret_cast<const uint32_t*>(N.point.p);
-    if (L && !sorted) {
-      unsigned bits = 1;
-      while (bits < 32 && (1ull << bits) < (uint64_t)P) ++bits;   // points are < P: ceil(log2 P) key bits
-      PCD_TRY(sort_pairs(N.prim, reinterpret_cast<uint32_t*>(N.point.p), N.keys.p, N.iota.p, N.list.p, (size_t)L, 0u, bits, s));
+                         wt, T.lidar_point.p, T.lidar_abcd.p, T.lidar_w.p, T.lidar_type.p, T.lidar_xyz.p,
+                         sorted ? T.pt_lidar_list.p : N.iota.p);
+    const uint32_t* sorted_pt = reinterpret_cast<const uint32_t*>(T.lidar_point.p);
+    if (L && !sorted) {   // points are at most P - 1
+      PCD_TRY(sort_pairs(N.prim, reinterpret_cast<uint32_t*>(T.lidar_point.p), N.keys.p, N.iota.p, T.pt_lidar_list.p, (size_t)L,
+                         0u, key_bits((uint64_t)P - 1), s));
       sorted_pt = N.keys.p;
     }
-    hipLaunchKernelGGL(k_lidar_bounds, dim3(div_up((uint64_t)P + 1, 256)), dim3(256), 0, s, P, L, sorted_pt, N.start.p);
-    if (L && ntr)
-      hipLaunchKernelGGL(k_lidar_tracks, dim3(div_up(ntr, 256)), dim3(256), 0, s, (uint32_t)ntr, b->pt_order.p, N.start.p,
-                         N.list.p, N.abcd.p, N.w.p, N.cnt.p, N.first.p);
+    hipLaunchKernelGGL(k_lidar_bounds, dim3(div_up((uint64_t)P + 1, 256)), dim3(256), 0, s, P, L, sorted_pt, T.pt_lidar_start.p);
+    if (L) launch_lidar_tracks(*b, b->nslices, T, T, s);
     PCD_HIP_TRY(hipGetLastError());
   }
-  // success: the new layout becomes the handle's; the retired buffers are the next call's
-  b->lidar_point.swap(N.point); b->lidar_abcd.swap(N.abcd); b->lidar_w.swap(N.w);
-  b->lidar_type.swap(N.type); b->lidar_xyz.swap(N.xyz);
-  b->pt_lidar_start.swap(N.start); b->pt_lidar_list.swap(N.list);
-  if (L) { b->pt_lidar_cnt.swap(N.cnt); b->pt_lidar_first.swap(N.first); }
+  // success: what was built becomes the handle's; the retired buffers are the next call's
+  b->swap_terms(T, built);
   b->L = L;
   b->has_lidar_meta = true;
   ba_schur_invalidate(b);
@@ -399,7 +396,7 @@ static pcd_status lidar_rebuild(pcd_ba* b, uint64_t Q, const int32_t* d_point, c
 static pcd_status lidar_meta(pcd_ba* b) {
   if (b->has_lidar_meta) return PCD_OK;
   const size_t L = b->L;
-  PCD_TRY(b->lidar_type.reserve(std::max<size_t>(L, 1))); PCD_TRY(b->lidar_xyz.reserve(std::max<size_t>(3 * L, 1)));
+  PCD_TRY(b->reserve_terms(kTermMeta, L, 0, 0));
   PCD_HIP_TRY(hipMemset(b->lidar_type.p, 0, std::max<size_t>(L, 1)));
   PCD_HIP_TRY(hipMemset(b->lidar_xyz.p, 0, std::max<size_t>(3 * L, 1) * sizeof(double)));
   b->has_lidar_meta = true;

@@ -31,6 +31,32 @@ inline hipError_t sort_pairs_at(void* storage, size_t& bytes, K* keys_in, K* key
   return rocprim::radix_sort_pairs<Config>(storage, bytes, keys_in, keys_out, vals_in, vals_out, n, begin_bit, end_bit, s);
 }
 
+// key bits of a sort whose keys are at most max_value (end_bit of sort_pairs): the smallest b with 2^b > max_value, 1 .. 32
+inline unsigned key_bits(uint64_t max_value) {
+  unsigned bits = 1;
+  while (bits < 32 && (1ull << bits) <= max_value) ++bits;
+  return bits;
+}
+// The largest temporary storage over exclusive sums of uint32_t of the given lengths and sorts of (uint32_t, uint32_t)
+// pairs of the given shapes (n == 0: a sort that is not run, not asked about): what a scratch reserves ahead of its first
+// launch so that no call has to grow the buffer.  No monotonicity in n is assumed.
+struct SortShape { size_t n; unsigned end_bit; };
+inline pcd_status prim_storage_u32(std::initializer_list<size_t> scans, std::initializer_list<SortShape> sorts, size_t& need) {
+  uint32_t* const u = nullptr;   // a size query reads no pointer
+  need = 0;
+  size_t bytes = 0;
+  for (size_t n : scans) {
+    PCD_HIP_TRY(exclusive_sum_at(nullptr, bytes, u, u, 0u, n, nullptr));
+    need = std::max(need, bytes);
+  }
+  for (const SortShape& k : sorts) {
+    if (!k.n) continue;
+    PCD_HIP_TRY(sort_pairs_at(nullptr, bytes, u, u, u, u, k.n, 0u, k.end_bit, nullptr));
+    need = std::max(need, bytes);
+  }
+  return PCD_OK;
+}
+
 // size query, tmp.reserve, run: `op(storage, bytes)` is one of the forms above with its arguments bound
 template <class Op>
 inline pcd_status prim_run(DevBuf<char>& tmp, Op&& op) {

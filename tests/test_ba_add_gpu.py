@@ -8,7 +8,9 @@ tolerance anywhere.
 Shapes: the scenes of tests/test_ba_lidar_gpu (P = 65 / 130: two and three 64-track slices), track scenes cut so that P
 crosses a slice edge (60 -> 64, 64 -> 65, 64 -> 128), a two-image scene whose image 0 crosses the kImgSeg = 1024 segment
 edge, and both sides of the sizes at which rocPRIM's radix sort of the new rows changes algorithm (one block up to 1024
-rows, merge sort up to 2^20, Onesweep above)."""
+rows, merge sort up to 2^20, Onesweep above), and one handle taken through the removal, the addition and
+set_lidar_device in turn (three images, one constant; P 70 -> 140 across a slice edge; through L = 0), each rebuild
+working in the buffers the others retired."""
 import os
 import subprocess
 
@@ -19,6 +21,7 @@ from pcdhip import synth
 from tests import ba_add_ref as ar
 from tests import ba_filter_ref as fr
 from tests import ba_lidar_ref as lr
+from tests import ba_schur_ref as sr
 from tests import test_ba_filter_gpu as fg
 from tests import test_ba_lidar_gpu as bl
 from tests import test_ba_load_order_gpu as lo
@@ -295,6 +298,73 @@ def test_set_lidar_terms_keep_their_meta(gpu, oracle):
     assert a.L == len(y["lidar_point"]) > 0 and y["type"].any()
     fg.in_use(gpu, a)
     check_added(gpu, a, desc, add, meta=dict(type=y["type"], lidar_xyz=y["lidar_xyz"]))
+    a.close()
+
+
+def chain_scene(oracle):
+    """140 tracks of 1 .. 3 observations over 3 images (279 rows), image 1 constant, every 5th point constant, 0 .. 3
+    LiDAR terms per point"""
+    if "chain" not in _CACHE:
+        rng = np.random.default_rng(97)
+        I, P = 3, 140
+        s = lo._base(rng, I, P, lo.CAMERAS["shared"])
+        length = rng.permutation(np.arange(P) % 3 + 1)
+        obs_point = np.repeat(np.arange(P), length).astype(np.int32)
+        j = np.arange(len(obs_point)) - np.repeat(np.cumsum(length) - length, length)
+        cpose = np.zeros(I, np.uint8); cpose[1] = 1
+        s.update(obs_image=((obs_point + j) % I).astype(np.int32), obs_point=obs_point, image_const_pose=cpose,
+                 point_const=(np.arange(P) % 5 == 2).astype(np.uint8))
+        lo._lidar(rng, s, rng.permutation(np.repeat(np.arange(P), np.arange(P) % 4)))
+        _CACHE["chain"] = sr.reproject(oracle, s, rng)
+    return _CACHE["chain"]
+
+
+def check_terms(gpu, a, desc, Q, seed):
+    """set_lidar_device with Q rows on the live handle `a` (whose description is `desc`), compare with a fresh handle that
+    holds the terms of those rows; returns (fresh description, meta)"""
+    bare = {k: v for k, v in desc.items() if not k.startswith("lidar_")}
+    point, typ, abcd, xyz = bl.make_rows(bare, Q, "shuffled", seed, False)
+    y = lr.terms(typ, abcd, WEIGHT, point, xyz)
+    assert a.set_lidar_device(typ, abcd, WEIGHT, point=point, lidar_xyz=xyz) == len(y["lidar_point"]) == a.L > 0
+    kw = dict(bare, lidar_point=y["lidar_point"], lidar_abcd=y["lidar_abcd"], lidar_weight=y["lidar_weight"])
+    b = gpu.BA(**bare)
+    b.set_lidar_device(y["type"], y["lidar_abcd"], WEIGHT, point=y["lidar_point"], lidar_xyz=y["lidar_xyz"])
+    bl.assert_same(fg.all_results(gpu, a, kw), fg.all_results(gpu, b, kw))
+    b.close()
+    return kw, dict(type=y["type"], lidar_xyz=y["lidar_xyz"])
+
+
+def test_every_rebuild_in_turn_on_one_handle(gpu, oracle):
+    """removal, addition and set_lidar_device alternate on one handle, so each works in the buffers the others retired:
+    created with terms (no type / lidar_xyz yet), through a handle without any term, P 70 -> 90 -> 130 -> 140"""
+    s = chain_scene(oracle)
+    s2, add3 = ar.split(s, 0.1, 10, seed=101, shuffle=True)
+    s1, add2 = ar.split(s2, 0.1, 40, seed=102, shuffle=True)
+    s0, add1 = ar.split(s1, 0.1, 20, seed=103, shuffle=True)
+    assert len(s0["points"]) == 70 and s0["image_const_pose"].sum() == 1 and len(s["obs_point"]) == 279
+    a = gpu.BA(**s0)
+    L0 = a.L
+    fg.in_use(gpu, a)
+    erase, pdel = fg.random_flags(s0, 104, 0.1, 3)
+    pdel[np.flatnonzero(np.bincount(s0["lidar_point"], minlength=70) == 3)[0]] = 1
+    kw, _, _ = fg.check_removed(gpu, a, s0, erase, pdel)                # 2: has_lidar_meta is still false
+    assert 0 < a.L < L0
+    fg.in_use(gpu, a)
+    kw = check_added(gpu, a, kw, add1)                                  # 3
+    L1 = a.L
+    kw, meta = check_terms(gpu, a, kw, 20, 105)                         # 4: fewer terms, on points 1 .. 10
+    assert a.L < min(L1, 20) and kw["lidar_point"].max() <= 10
+    fg.in_use(gpu, a)
+    kw = check_added(gpu, a, kw, add2, meta=meta)                       # 5: two slices become three
+    assert (a.P + 63) // 64 == 3
+    fg.in_use(gpu, a)
+    pdel = np.zeros(a.P, np.uint8); pdel[kw["lidar_point"]] = 1
+    kw, meta, _ = fg.check_removed(gpu, a, kw, None, pdel, meta=meta)   # 6: every term goes
+    assert a.L == 0 and a.O > 100
+    kw, meta = check_terms(gpu, a, kw, 200, 106)                        # 7
+    fg.in_use(gpu, a)
+    kw = check_added(gpu, a, kw, add3, meta=meta)                       # 8
+    assert a.P == 140 and a.L == len(meta["type"]) > 20
     a.close()
 
 
