@@ -126,6 +126,22 @@ static pcd_status upload_problem(const pcd_ba_desc* d, pcd_ba* b) {
   if (d->point_const) { b->has_cpt = true; UP(point_const, d->point_const, b->P); }
   if (d->camera_refine) { b->has_refine = true; UP(cam_refine, d->camera_refine, d->cam_params_len); }
   for (uint64_t k = 0; d->camera_refine && k < d->cam_params_len; ++k) b->refines_intrinsics |= d->camera_refine[k] != 0;
+  // camera slots of the reduced system with refined intrinsics (pcd_ba_schur_cam*)
+  b->h_cam_slot.assign(b->C, -1); b->h_param_cam.assign(d->cam_params_len, -1);
+  for (int c = 0; c < b->C; ++c) {
+    const int K = cam_num_params(d->cam_model[c]);
+    uint8_t act[PCD_CAM_JAC_STRIDE] = {};
+    bool any = false;
+    for (int j = 0; j < K && (uint64_t)d->cam_param_offset[c] + j < d->cam_params_len; ++j) {
+      b->h_param_cam[d->cam_param_offset[c] + j] = c;
+      act[j] = d->camera_refine && d->camera_refine[d->cam_param_offset[c] + j] != 0;
+      any |= act[j] != 0;
+    }
+    if (!any) continue;
+    b->h_cam_slot[c] = (int)b->h_slot_cam.size();
+    b->h_slot_cam.push_back(c);
+    b->h_cam_active.insert(b->h_cam_active.end(), act, act + PCD_CAM_JAC_STRIDE);
+  }
   return PCD_OK;
 }
 

@@ -276,6 +276,12 @@ struct pcd_ba : pcd::BaLayout, pcd::BaTerms {
   pcd::DevBuf<uint8_t> f_tri_u8;
   // point elimination (pcd_ba_schur*): built on the first call, so pcd_ba_create costs existing users nothing
   bool refines_intrinsics = false;   // some camera_refine byte is set: the reduced system would need camera rows
+  // the camera slots of pcd_ba_schur_cam* (fixed at pcd_ba_create): the cameras with a refined parameter below their
+  // model's K, ascending camera index.  h_cam_slot [C] (-1: none), h_slot_cam [ncs], h_cam_active [ncs][12] (1 = refined),
+  // h_param_cam [cam_params_len] camera of every packed parameter.  Not limited here: the _cam calls refuse more than
+  // PCD_BA_MAX_CAMERA_SLOTS.
+  std::vector<int> h_cam_slot, h_slot_cam, h_param_cam;
+  std::vector<uint8_t> h_cam_active;
   std::unique_ptr<pcd::BaSchur, pcd::BaSchurDelete> schur;
   // the optional constant masks as the kernels take them: nullptr when the problem gave none
   const uint8_t* const_poses() const { return has_cpose ? image_const_pose.p : nullptr; }

@@ -7,6 +7,9 @@
 // (ba_handle.h) for H, g, W and the cost, and pcd_ba_evaluate_device for the cost of a trial step.  No evaluation
 // kernel is compiled here.
 //
+// Refined intrinsics ride beside all this, opt-in (pcd_ba_schur_cam*, pcd_ba_solve with refine_intrinsics): the camera rows
+// of the reduced system are a dense border whose kernels live in ba_solve_cam.hip; the state and the entry points are here.
+//
 // Host side, behind the kernels: BaSchur, the solver state grouped by owner; schur_build, which has the co-visibility
 // structure built on the device (ba_schur_structure.hip) on the stream of the call that needs it; the PCG batches;
 // pcd_ba_solve over lm_check_opts, lm_reserve, lm_enqueue_linear, lm_try_step, lm_decide.
@@ -18,6 +21,7 @@
 #include "ba_chol.h"
 #include "ba_handle.h"
 #include "ba_schur_structure.h"
+#include "ba_solve_cam.h"
 #include "common.h"
 
 namespace pcd {
@@ -28,11 +32,7 @@ namespace pcd {
 // positions e (the layout k_ba_images walks): W and Y = W V^-1 of the observations of an image are contiguous, so the
 // entries of a pair block (a in image i, b in image j) gather from two short ranges.  No atomics anywhere: every sum
 // runs in an order fixed by the structure, so results are bitwise reproducible run to run.
-constexpr double kDiagMin = 1e-6, kDiagMax = 1e32;   // Ceres' LevenbergMarquardtStrategy min/max_diagonal
-
-__device__ __forceinline__ double damp_of(int mode, double mu, double h) {
-  return mode == 0 ? mu * fmin(fmax(h, kDiagMin), kDiagMax) : mu;
-}
+// kDiagMin / kDiagMax / damp_of: ba_solve_cam.h, shared with the camera rows.
 
 // thread = point: V = H_pt + D through a 3x3 Cholesky -> V^-1, V^-1 g, D.  Constant points are not eliminated, points
 // whose damped V is not numerically positive definite are skipped (V^-1 = 0: delta 0, no contribution) and counted.
@@ -739,23 +739,32 @@ struct BaSchur {
     uint64_t bytes() const { return dev_bytes(Minv, x0, x1, r, z, p0, p1, w, pw, partial, out, state, info); }
   } cg;
   struct Lm {   // pcd_ba_solve: the step, the accepted parameters, the record of an iteration
-    DevBuf<double> dpose, dpoint, poses, points, cand_cost, gpart;
+    DevBuf<double> dpose, dpoint, poses, points, cam_params, cand_cost, gpart;   // dpose: dcam behind it with camera rows
     DevBuf<LmRecord> rec; PinnedBuf<LmRecord> host;
-    uint64_t bytes() const { return dev_bytes(dpose, dpoint, poses, points, cand_cost, gpart, rec); }
+    uint64_t bytes() const { return dev_bytes(dpose, dpoint, poses, points, cam_params, cand_cost, gpart, rec); }
   } lm;
+  struct Cam {   // pcd_ba_schur_cam*: the camera slots (uploaded once), the camera blocks and what is eliminated from them
+    bool slots = false;   // cam_slot .. param_cam are on the device
+    bool valid = false;   // the last Schur call was pcd_ba_schur_cam_device and has filled the buffers below
+    DevBuf<int> cam_slot, slot_cam, param_cam; DevBuf<uint8_t> active;
+    DevBuf<double> Hcam, gcam, Ecam, Wcam, Wc, Z, partial, B, Scam, rhs, D, dense, out;   // dense / out: host-form staging
+    uint64_t bytes() const {
+      return dev_bytes(cam_slot, slot_cam, param_cam, active, Hcam, gcam, Ecam, Wcam, Wc, Z, partial, B, Scam, rhs, D, dense, out);
+    }
+  } cam;
   struct Chol {   // pcd_ba_schur_solve_cholesky*: the padded dense scratch of ba_chol.h, allocated on first use
     DevBuf<double> A, S, rhs, out;   // S / rhs (freed after each call) / out: staging of the host form
     DevBuf<pcd_ba_chol_info> info, info_out;
     uint64_t bytes() const { return dev_bytes(A, S, rhs, out, info, info_out); }
   } chol;
-  uint64_t device_bytes() const { return st.bytes() + num.bytes() + cg.bytes() + lm.bytes() + chol.bytes(); }
+  uint64_t device_bytes() const { return st.bytes() + num.bytes() + cg.bytes() + lm.bytes() + chol.bytes() + cam.bytes(); }
 };
 
 void BaSchurDelete::operator()(BaSchur* s) const { delete s; }
-void ba_schur_invalidate(pcd_ba* b) { if (b->schur) b->schur->num.valid = false; }
+void ba_schur_invalidate(pcd_ba* b) { if (b->schur) b->schur->num.valid = b->schur->cam.valid = false; }
 void ba_schur_drop_structure(pcd_ba* b) {
   if (!b->schur) return;
-  b->schur->num.valid = false;
+  b->schur->num.valid = b->schur->cam.valid = false;
   b->schur->st.built = false;   // the build assigns every member of the structure anew
 }
 
@@ -924,9 +933,10 @@ static pcd_status lm_check_opts(const pcd_ba_solve_opts* o) {
   return PCD_OK;
 }
 
-static pcd_status lm_reserve(pcd_ba* b, unsigned ngp) {
+static pcd_status lm_reserve(pcd_ba* b, unsigned ngp, int ncs) {
   BaSchur::Lm& M = b->schur->lm;
-  PCD_TRY(M.dpose.reserve(at_least_1(slot_vec(b->schur->st.ns)))); PCD_TRY(M.poses.reserve(7 * (size_t)b->I));
+  PCD_TRY(M.dpose.reserve(at_least_1(slot_vec(b->schur->st.ns) + (size_t)kCamS * ncs))); PCD_TRY(M.poses.reserve(7 * (size_t)b->I));
+  if (ncs) PCD_TRY(M.cam_params.reserve(at_least_1(b->cam_params_len)));
   PCD_TRY(M.dpoint.reserve(point_vec(b->P))); PCD_TRY(M.points.reserve(point_vec(b->P)));
   PCD_TRY(M.cand_cost.reserve(1)); PCD_TRY(M.rec.reserve(1)); PCD_TRY(M.host.reserve(1));
   return M.gpart.reserve(ngp);
@@ -939,15 +949,29 @@ static pcd_status copy_parameters(const pcd_ba* b, double* dst_poses, double* ds
   PCD_HIP_TRY(hipMemcpyAsync(dst_points, src_points, point_vec(b->P) * sizeof(double), hipMemcpyDeviceToDevice, s));
   return PCD_OK;
 }
+// the camera parameters beside them, when the loop moves them: save = the handle's into lm.cam_params, else back
+static pcd_status copy_camera_parameters(pcd_ba* b, bool save, hipStream_t s) {
+  double* kept = b->schur->lm.cam_params.p;
+  if (b->cam_params_len)
+    PCD_HIP_TRY(hipMemcpyAsync(save ? kept : b->cam_params.p, save ? b->cam_params.p : kept,
+                               b->cam_params_len * sizeof(double), hipMemcpyDeviceToDevice, s));
+  return PCD_OK;
+}
+
+static pcd_status chol_solve_cam(pcd_ba* b, double* d_delta, pcd_ba_chol_info* d_info, hipStream_t s);   // below
 
 // The linear solve of an iteration into lm.dpose / cg.info: the direct solve (an exact step: nothing left to run, *enq =
 // max_iterations), or pcg_begin and the first batch (*enq = its iterations)
-static pcd_status lm_enqueue_linear(pcd_ba* b, const pcd_ba_solve_opts* o, int* enq, hipStream_t s) {
+static pcd_status lm_enqueue_linear(pcd_ba* b, const pcd_ba_solve_opts* o, bool cam, int* enq, hipStream_t s) {
   BaSchur& S = *b->schur;
   *enq = o->linear.max_iterations;
   if (o->linear_solver == PCD_LINEAR_CHOLESKY) {
     PCD_TRY(S.cg.info.reserve(1));
-    if (S.st.ns) {
+    if (cam) {   // the bordered system: dpose, then dcam
+      ScopedKernelTimer t("ba_schur_cholesky", s);
+      PCD_TRY(chol_solve_cam(b, S.lm.dpose.p, nullptr, s));
+      hipLaunchKernelGGL(k_chol_lm_info, dim3(1), dim3(1), 0, s, S.chol.info.p, S.cg.info.p);
+    } else if (S.st.ns) {
       ScopedKernelTimer t("ba_schur_cholesky", s);
       PCD_TRY(chol_solve(b, nullptr, nullptr, S.lm.dpose.p, nullptr, s));
       hipLaunchKernelGGL(k_chol_lm_info, dim3(1), dim3(1), 0, s, S.chol.info.p, S.cg.info.p);
@@ -965,14 +989,19 @@ static pcd_status lm_enqueue_linear(pcd_ba* b, const pcd_ba_solve_opts* o, int* 
 // Tail of an iteration up to the synchronised read-back of its record into lm.host.  It is enqueued behind the first
 // batch without looking at the flag: at the defaults the PCG has ended by then and the iteration costs one copy.  If the
 // step came from an unfinished solve, the accepted parameters go back, the batches go on and the tail runs once more.
-static pcd_status lm_try_step(pcd_ba* b, const pcd_ba_solve_opts* o, int enq, unsigned ngp, EventPair& ev,
+static pcd_status lm_try_step(pcd_ba* b, const pcd_ba_solve_opts* o, bool cam, int enq, unsigned ngp, EventPair& ev,
                               double* linear_ms, hipStream_t s) {
   BaSchur& S = *b->schur; BaSchur::Lm& M = S.lm;
   pcd_ba_out co{}; co.cost = M.cand_cost.p;
   for (;;) {
     if (o->linear_solver == PCD_LINEAR_PCG) pcg_finish(b, M.dpose.p, S.cg.info.p, s);
-    PCD_TRY(pcd_ba_schur_back_substitute_device(b, M.dpose.p, M.dpoint.p, S.num.md.p, s));
-    PCD_TRY(pcd_ba_plus_device(b, M.dpose.p, M.dpoint.p, b->poses.p, b->points.p, s));
+    if (cam) {   // the direct solve only: the loop below ends after one pass
+      PCD_TRY(pcd_ba_schur_cam_back_substitute_device(b, M.dpose.p, M.dpoint.p, S.num.md.p, s));
+      PCD_TRY(pcd_ba_plus_cam_device(b, M.dpose.p, M.dpoint.p, b->poses.p, b->points.p, b->cam_params.p, s));
+    } else {
+      PCD_TRY(pcd_ba_schur_back_substitute_device(b, M.dpose.p, M.dpoint.p, S.num.md.p, s));
+      PCD_TRY(pcd_ba_plus_device(b, M.dpose.p, M.dpoint.p, b->poses.p, b->points.p, s));
+    }
     PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
     hipLaunchKernelGGL(k_ba_lm_record, dim3(1), dim3(256), 0, s, S.num.cost.p, M.cand_cost.p, S.num.md.p, M.gpart.p,
                        (int)ngp, S.num.skip_cnt.p, S.cg.info.p, M.rec.p);
@@ -1011,6 +1040,168 @@ static LmDecision lm_decide(const LmRecord& rec, const pcd_ba_solve_opts& o, dou
   } else if (!restore_only) { radius /= factor; factor *= 2.0; }
   r.radius = d.radius = radius; d.factor = factor;
   return d;
+}
+
+// pcd_ba_schur_device behind its handle guard: pcd_ba_schur_cam_device runs the same pose part on a refined handle
+static pcd_status schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o, void* stream,
+                               const char* fn) {
+  PCD_REQUIRE(opt && o, "null pointer");
+  PCD_REQUIRE(opt->damping == PCD_DAMP_MARQUARDT || opt->damping == PCD_DAMP_LEVENBERG, "damping");
+  PCD_REQUIRE(opt->mu >= 0.0, "mu must be >= 0");
+  PCD_TRY(refuse_capture((hipStream_t)stream, fn));
+  hipStream_t s = (hipStream_t)stream;
+  PCD_TRY(schur_build(b, s));
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
+  const int I = b->I, P = b->P, ns = T.ns;
+  const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));   // grid of k_schur_points = length of its partials
+  N.valid = b->schur->cam.valid = false;
+  PCD_TRY(N.Himg.reserve(blocks_6x6(I))); PCD_TRY(N.gimg.reserve(slot_vec(I)));
+  PCD_TRY(N.Hpt.reserve(point_blocks(P))); PCD_TRY(N.gpt.reserve(point_vec(P)));
+  PCD_TRY(N.Wim.reserve(at_least_1(obs_blocks(b->O)))); PCD_TRY(N.Y.reserve(at_least_1(obs_blocks(b->O))));
+  PCD_TRY(N.Vinv.reserve(point_blocks(P))); PCD_TRY(N.Vg.reserve(point_vec(P))); PCD_TRY(N.Dpt.reserve(point_vec(P)));
+  PCD_TRY(N.Dimg.reserve(at_least_1(slot_vec(ns)))); PCD_TRY(N.Sdiag.reserve(at_least_1(blocks_6x6(ns))));
+  PCD_TRY(N.Soff.reserve(at_least_1(blocks_6x6(T.npairs)))); PCD_TRY(N.rhs.reserve(at_least_1(slot_vec(ns))));
+  PCD_TRY(N.skip_partial.reserve(nbp)); PCD_TRY(N.skip_cnt.reserve(1));
+  PCD_TRY(N.md_partial.reserve(nbp)); PCD_TRY(N.md.reserve(1)); PCD_TRY(N.cost.reserve(1));
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  double* Sdiag = o->S_diag ? o->S_diag : N.Sdiag.p; double* Soff = o->S_off ? o->S_off : N.Soff.p;
+  {
+    ScopedKernelTimer t("ba_schur_normal", s);
+    // iota as the W order: W lands in image-major order (k_ba_images' contiguous store path)
+    PCD_TRY(ba_normal_equations(b, T.iota.p, N.Hpt.p, N.gpt.p, o->cost ? o->cost : N.cost.p, N.Himg.p, N.gimg.p,
+                                N.Wim.p, s));
+  }
+  {
+    ScopedKernelTimer t("ba_schur_eliminate", s);
+    schur_eliminate(b, opt, nbp, Sdiag, Soff, o->rhs ? o->rhs : N.rhs.p,
+                    o->num_skipped ? reinterpret_cast<unsigned long long*>(o->num_skipped) : N.skip_cnt.p, s);
+  }
+  if (o->S && T.ns) {
+    ScopedKernelTimer t("ba_schur_dense", s);
+    const size_t n = slot_vec(T.ns);
+    PCD_HIP_TRY(hipMemsetAsync(o->S, 0, n * n * sizeof(double), s));
+    hipLaunchKernelGGL(k_schur_dense, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, T.ns, T.nblk(),
+                       T.pair_ij.p, Sdiag, Soff, o->S);
+  }
+  PCD_HIP_TRY(hipGetLastError());
+  N.valid = true; N.own_diag = !o->S_diag; N.own_off = !o->S_off; N.own_rhs = !o->rhs;
+  return PCD_OK;
+}
+
+// ---- camera rows: refined intrinsics in the reduced system (pcd_ba_schur_cam*, ba_solve_cam.h) --------------------
+static int cam_slots(const pcd_ba* b) { return (int)b->h_slot_cam.size(); }
+
+// Every _cam entry point: the guards of the plain calls without their refusal of a refined handle; instead more camera
+// slots than the bordered system carries -> UNSUPPORTED.  Before anything is allocated or launched.
+static pcd_status schur_cam_guard(pcd_ba* b) {
+  PCD_TRY(require_device(b ? b->device : 0));
+  PCD_REQUIRE(b, "null handle");
+  if (cam_slots(b) > PCD_BA_MAX_CAMERA_SLOTS) {
+    set_error("%d cameras have refined parameters; the reduced system carries at most PCD_BA_MAX_CAMERA_SLOTS = %d "
+              "camera slots (cameras shared by many images)", cam_slots(b), PCD_BA_MAX_CAMERA_SLOTS);
+    return PCD_ERR_UNSUPPORTED;
+  }
+  return PCD_OK;
+}
+
+// the state of a pcd_ba_schur_cam* call: what schur_state_guard asks, and that the last Schur call carried camera rows
+static pcd_status schur_cam_state_guard(const pcd_ba* b, const char* fn, bool blocks) {
+  PCD_TRY(schur_state_guard(b, fn, blocks));
+  if (!b->schur->cam.valid) {
+    set_error("%s: no Schur state with camera rows (call pcd_ba_schur_cam[_device] first)", fn);
+    return PCD_ERR_INVALID;
+  }
+  return PCD_OK;
+}
+
+// the camera slots on the device, once (the structure exists: schur_build ran)
+static pcd_status cam_upload_slots(pcd_ba* b) {
+  BaSchur::Cam& K = b->schur->cam;
+  if (K.slots) return PCD_OK;
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  PCD_TRY(upload(K.cam_slot, b->h_cam_slot.data(), b->h_cam_slot.size()));
+  PCD_TRY(upload(K.slot_cam, b->h_slot_cam.data(), b->h_slot_cam.size()));
+  PCD_TRY(upload(K.param_cam, b->h_param_cam.data(), b->h_param_cam.size()));
+  PCD_TRY(upload(K.active, b->h_cam_active.data(), b->h_cam_active.size()));
+  K.slots = true;
+  return PCD_OK;
+}
+
+// pcd_ba_schur_cam_device on a handle with camera slots, behind its guards
+static pcd_status schur_cam_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_cam_out* o, void* stream) {
+  PCD_REQUIRE(opt && o, "null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  PCD_TRY(refuse_capture(s, "pcd_ba_schur_cam_device"));
+  PCD_TRY(schur_build(b, s));
+  PCD_TRY(cam_upload_slots(b));
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; BaSchur::Cam& K = b->schur->cam;
+  const int ncs = cam_slots(b), ns = T.ns, P = b->P;
+  const size_t nc = (size_t)kCamS * ncs;
+  PCD_TRY(K.Hcam.reserve((size_t)kCamS * kCamS * b->C)); PCD_TRY(K.gcam.reserve((size_t)kCamS * b->C));
+  PCD_TRY(K.Ecam.reserve(at_least_1((size_t)kCamS * 6 * b->I))); PCD_TRY(K.Wcam.reserve(at_least_1(36 * (size_t)b->O)));
+  PCD_TRY(K.Wc.reserve(at_least_1(36 * (size_t)P * ncs))); PCD_TRY(K.Z.reserve(at_least_1(36 * (size_t)P * ncs)));
+  PCD_TRY(K.partial.reserve(cam_pairs(ncs) * kCamEnt * cam_chunks(P)));
+  PCD_TRY(K.B.reserve(at_least_1((size_t)ns * nc * 6))); PCD_TRY(K.Scam.reserve(nc * nc));
+  PCD_TRY(K.rhs.reserve(nc)); PCD_TRY(K.D.reserve(nc));
+  pcd_ba_schur_out po{};
+  po.cost = o->cost; po.S_diag = o->S_diag; po.S_off = o->S_off; po.rhs = o->rhs; po.num_skipped = o->num_skipped;
+  PCD_TRY(schur_device(b, opt, &po, stream, "pcd_ba_schur_cam_device"));   // the pose part, unchanged
+  {
+    pcd_ba_out co{};   // its own scopes: ba_cameras, ba_cam_w
+    co.H_cam = K.Hcam.p; co.g_cam = K.gcam.p; co.E_cam = K.Ecam.p; co.W_cam = K.Wcam.p;
+    PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
+  }
+  SchurCamIn in{};
+  in.P = P; in.I = b->I; in.ns = ns; in.ncs = ncs;
+  in.shared = ncs == 1 && b->shared_cam >= 0 && b->h_cam_slot[b->shared_cam] == 0;
+  in.cam_slot = K.cam_slot.p; in.slot_cam = K.slot_cam.p; in.active = K.active.p;
+  in.image_cam = b->image_cam.p; in.obs_image = b->obs_image.p;
+  in.pt_obs_start = b->pt_obs_start.p; in.pt_obs_list = b->pt_obs_list.p;
+  in.img_obs_start = b->img_obs_start.p; in.img_pt = b->img_pt.p;
+  in.slot_img = T.slot_img.p; in.image_const_tvec = b->const_tvec();
+  in.Vinv = N.Vinv.p; in.gpt = N.gpt.p; in.Wim = N.Wim.p;
+  in.Hcam = K.Hcam.p; in.gcam = K.gcam.p; in.Ecam = K.Ecam.p; in.Wcam = K.Wcam.p;
+  in.mu = opt->mu; in.mode = opt->damping;
+  const SchurCamOut out{K.Wc.p, K.Z.p, K.partial.p, K.B.p, K.Scam.p, K.rhs.p, K.D.p};
+  {
+    ScopedKernelTimer t("ba_schur_cam_eliminate", s);
+    schur_cam_eliminate(in, out, s);
+  }
+  {
+    ScopedKernelTimer t("ba_schur_cam_border", s);
+    schur_cam_border(in, out, s);
+  }
+  if (o->S) {
+    ScopedKernelTimer t("ba_schur_dense", s);
+    const size_t n = slot_vec(ns) + nc;
+    PCD_HIP_TRY(hipMemsetAsync(o->S, 0, n * n * sizeof(double), s));
+    schur_cam_dense(ns, ncs, T.nblk(), T.pair_ij.p, po.S_diag ? po.S_diag : N.Sdiag.p, po.S_off ? po.S_off : N.Soff.p,
+                    K.B.p, K.Scam.p, o->S, s);
+  }
+  const auto copy_out = [&](double* dst, const double* src, size_t n) -> pcd_status {
+    if (dst && n) PCD_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return PCD_OK;
+  };
+  PCD_TRY(copy_out(o->B, K.B.p, (size_t)ns * nc * 6)); PCD_TRY(copy_out(o->S_cam, K.Scam.p, nc * nc));
+  PCD_TRY(copy_out(o->rhs_cam, K.rhs.p, nc));
+  PCD_HIP_TRY(hipGetLastError());
+  K.valid = true;
+  return PCD_OK;
+}
+
+// the direct solve of the bordered system from the handle's own blocks into d_delta [6 ns + 12 ncs]; status in chol.info
+static pcd_status chol_solve_cam(pcd_ba* b, double* d_delta, pcd_ba_chol_info* d_info, hipStream_t s) {
+  const BaSchur::Structure& T = b->schur->st; const BaSchur::Numeric& N = b->schur->num;
+  BaSchur::Chol& K = b->schur->chol; const BaSchur::Cam& Cm = b->schur->cam;
+  const int ns = T.ns, ncs = cam_slots(b), n = (int)slot_vec(ns) + kCamS * ncs;
+  PCD_TRY(K.A.reserve(chol_scratch_doubles(n))); PCD_TRY(K.info.reserve(1));
+  chol_begin(K.A.p, n, K.info.p, s);
+  if (T.nblk())
+    hipLaunchKernelGGL(k_chol_fill_blocks, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, ns, T.nblk(),
+                       T.pair_ij.p, N.Sdiag.p, N.Soff.p, N.rhs.p, chol_padded(n), K.A.p);
+  schur_cam_fill_chol(ns, ncs, Cm.B.p, Cm.Scam.p, Cm.rhs.p, chol_padded(n), K.A.p, s);
+  chol_factor_solve(K.A.p, n, K.info.p, d_delta, d_info, s);
+  return PCD_OK;
 }
 
 extern "C" {
@@ -1074,47 +1265,7 @@ pcd_status pcd_ba_schur_stats(pcd_ba* b, pcd_ba_schur_info* info) {
 pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o, void* stream) {
   return pcd::guard([&]() -> pcd_status {
     PCD_TRY(schur_guard(b));
-    PCD_REQUIRE(opt && o, "null pointer");
-    PCD_REQUIRE(opt->damping == PCD_DAMP_MARQUARDT || opt->damping == PCD_DAMP_LEVENBERG, "damping");
-    PCD_REQUIRE(opt->mu >= 0.0, "mu must be >= 0");
-    PCD_REFUSE_CAPTURE(stream);
-    hipStream_t s = (hipStream_t)stream;
-    PCD_TRY(schur_build(b, s));
-    const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
-    const int I = b->I, P = b->P, ns = T.ns;
-    const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));   // grid of k_schur_points = length of its partials
-    N.valid = false;
-    PCD_TRY(N.Himg.reserve(blocks_6x6(I))); PCD_TRY(N.gimg.reserve(slot_vec(I)));
-    PCD_TRY(N.Hpt.reserve(point_blocks(P))); PCD_TRY(N.gpt.reserve(point_vec(P)));
-    PCD_TRY(N.Wim.reserve(at_least_1(obs_blocks(b->O)))); PCD_TRY(N.Y.reserve(at_least_1(obs_blocks(b->O))));
-    PCD_TRY(N.Vinv.reserve(point_blocks(P))); PCD_TRY(N.Vg.reserve(point_vec(P))); PCD_TRY(N.Dpt.reserve(point_vec(P)));
-    PCD_TRY(N.Dimg.reserve(at_least_1(slot_vec(ns)))); PCD_TRY(N.Sdiag.reserve(at_least_1(blocks_6x6(ns))));
-    PCD_TRY(N.Soff.reserve(at_least_1(blocks_6x6(T.npairs)))); PCD_TRY(N.rhs.reserve(at_least_1(slot_vec(ns))));
-    PCD_TRY(N.skip_partial.reserve(nbp)); PCD_TRY(N.skip_cnt.reserve(1));
-    PCD_TRY(N.md_partial.reserve(nbp)); PCD_TRY(N.md.reserve(1)); PCD_TRY(N.cost.reserve(1));
-    PCD_HIP_TRY(hipSetDevice(b->device));
-    double* Sdiag = o->S_diag ? o->S_diag : N.Sdiag.p; double* Soff = o->S_off ? o->S_off : N.Soff.p;
-    {
-      ScopedKernelTimer t("ba_schur_normal", s);
-      // iota as the W order: W lands in image-major order (k_ba_images' contiguous store path)
-      PCD_TRY(ba_normal_equations(b, T.iota.p, N.Hpt.p, N.gpt.p, o->cost ? o->cost : N.cost.p, N.Himg.p, N.gimg.p,
-                                  N.Wim.p, s));
-    }
-    {
-      ScopedKernelTimer t("ba_schur_eliminate", s);
-      schur_eliminate(b, opt, nbp, Sdiag, Soff, o->rhs ? o->rhs : N.rhs.p,
-                      o->num_skipped ? reinterpret_cast<unsigned long long*>(o->num_skipped) : N.skip_cnt.p, s);
-    }
-    if (o->S && T.ns) {
-      ScopedKernelTimer t("ba_schur_dense", s);
-      const size_t n = slot_vec(T.ns);
-      PCD_HIP_TRY(hipMemsetAsync(o->S, 0, n * n * sizeof(double), s));
-      hipLaunchKernelGGL(k_schur_dense, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, T.ns, T.nblk(),
-                         T.pair_ij.p, Sdiag, Soff, o->S);
-    }
-    PCD_HIP_TRY(hipGetLastError());
-    N.valid = true; N.own_diag = !o->S_diag; N.own_off = !o->S_off; N.own_rhs = !o->rhs;
-    return PCD_OK;
+    return schur_device(b, opt, o, stream, "pcd_ba_schur_device");
   });
 }
 
@@ -1267,6 +1418,133 @@ pcd_status pcd_ba_schur_solve_cholesky(pcd_ba* b, const double* Sh, const double
   });
 }
 
+// ---- refined intrinsics: camera rows in the reduced system -------------------------------------------
+// On a handle without camera slots every call is its plain counterpart.
+pcd_status pcd_ba_camera_slots(pcd_ba* b, int32_t* camera_slot, int32_t* num_slots, uint8_t* active) {
+  PCD_TRY(require_device(b ? b->device : 0));
+  PCD_REQUIRE(b, "null handle");
+  if (camera_slot) std::copy(b->h_cam_slot.begin(), b->h_cam_slot.end(), camera_slot);
+  if (num_slots) *num_slots = cam_slots(b);
+  if (active) std::copy(b->h_cam_active.begin(), b->h_cam_active.end(), active);
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_schur_cam_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_cam_out* o, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_cam_guard(b));
+    if (cam_slots(b)) return schur_cam_device(b, opt, o, stream);
+    PCD_REQUIRE(opt && o, "null pointer");
+    pcd_ba_schur_out po{};
+    po.cost = o->cost; po.S_diag = o->S_diag; po.S_off = o->S_off; po.rhs = o->rhs; po.S = o->S;
+    po.num_skipped = o->num_skipped;
+    return pcd_ba_schur_device(b, opt, &po, stream);
+  });
+}
+
+pcd_status pcd_ba_schur_cam(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_cam_out* o) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_cam_guard(b)); PCD_REQUIRE(opt && o, "null pointer");
+    if (!cam_slots(b)) {
+      pcd_ba_schur_out po{};
+      po.cost = o->cost; po.S_diag = o->S_diag; po.S_off = o->S_off; po.rhs = o->rhs; po.S = o->S;
+      po.num_skipped = o->num_skipped;
+      return pcd_ba_schur(b, opt, &po);
+    }
+    PCD_TRY(schur_build(b, nullptr));
+    const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; BaSchur::Cam& K = b->schur->cam;
+    const size_t n0 = slot_vec(T.ns), nc = (size_t)kCamS * cam_slots(b), n = n0 + nc;
+    pcd_ba_schur_cam_out d{};
+    if (o->S) { PCD_TRY(K.dense.reserve(n * n)); d.S = K.dense.p; }
+    PCD_TRY(schur_cam_device(b, opt, &d, nullptr));
+    PCD_TRY(copy_back(o->cost, N.cost, 1)); PCD_TRY(copy_back(o->num_skipped, N.skip_cnt, 1));
+    PCD_TRY(copy_back(o->S_diag, N.Sdiag, blocks_6x6(T.ns))); PCD_TRY(copy_back(o->S_off, N.Soff, blocks_6x6(T.npairs)));
+    PCD_TRY(copy_back(o->rhs, N.rhs, n0)); PCD_TRY(copy_back(o->B, K.B, (size_t)T.ns * nc * 6));
+    PCD_TRY(copy_back(o->S_cam, K.Scam, nc * nc)); PCD_TRY(copy_back(o->rhs_cam, K.rhs, nc));
+    PCD_TRY(copy_back(o->S, K.dense, n * n));
+    PCD_HIP_TRY(hipDeviceSynchronize());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_cam_solve_cholesky_device(pcd_ba* b, double* d_delta, pcd_ba_chol_info* d_info, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_cam_guard(b));
+    if (!cam_slots(b)) return pcd_ba_schur_solve_cholesky_device(b, nullptr, nullptr, d_delta, d_info, stream);
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(schur_cam_state_guard(b, "pcd_ba_schur_cam_solve_cholesky_device", true));
+    PCD_REQUIRE(d_delta, "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
+    ScopedKernelTimer t("ba_schur_cholesky", s);
+    PCD_TRY(chol_solve_cam(b, d_delta, d_info, s));
+    PCD_HIP_TRY(hipGetLastError());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_cam_back_substitute_device(pcd_ba* b, const double* d_delta, double* d_dpoint,
+                                                   double* d_model_decrease, void* stream) {
+  PCD_TRY(schur_cam_guard(b));
+  if (!cam_slots(b)) return pcd_ba_schur_back_substitute_device(b, d_delta, d_dpoint, d_model_decrease, stream);
+  PCD_REFUSE_CAPTURE(stream);
+  PCD_TRY(schur_cam_state_guard(b, "pcd_ba_schur_cam_back_substitute_device", false));
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; const BaSchur::Cam& K = b->schur->cam;
+  PCD_REQUIRE(d_delta && (d_dpoint || b->P == 0), "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
+  const int P = b->P, ncs = cam_slots(b); const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
+  const double* d_dcam = d_delta + slot_vec(T.ns);
+  ScopedKernelTimer t("ba_schur_back", s);
+  const SchurCamBack kb{P, ncs, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p, T.obs_pos.p, T.img_slot.p,
+                        N.Wim.p, N.Vinv.p, N.gpt.p, N.Dpt.p, K.Wc.p, K.active.p};
+  schur_cam_back(kb, d_delta, d_dcam, d_dpoint, N.md_partial.p, s);
+  if (d_model_decrease) {
+    hipLaunchKernelGGL(k_schur_model_decrease, dim3(1), dim3(256), 0, s, T.ns, T.slot_img.p, b->const_tvec(), N.gimg.p,
+                       N.Dimg.p, d_delta, N.md_partial.p, (int)nbp, d_model_decrease);
+    schur_cam_model_decrease(ncs, K.slot_cam.p, K.active.p, K.gcam.p, K.D.p, d_dcam, d_model_decrease, s);
+  }
+  PCD_HIP_TRY(hipGetLastError());
+  return PCD_OK;
+}
+
+pcd_status pcd_ba_plus_cam_device(pcd_ba* b, const double* d_delta, const double* d_dpoint, double* d_poses_out,
+                                  double* d_points_out, double* d_cam_params_out, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_cam_guard(b));
+    hipStream_t s = (hipStream_t)stream;
+    if (!cam_slots(b)) {
+      PCD_TRY(pcd_ba_plus_device(b, d_delta, d_dpoint, d_poses_out, d_points_out, stream));
+      if (d_cam_params_out && d_cam_params_out != b->cam_params.p && b->cam_params_len)
+        PCD_HIP_TRY(hipMemcpyAsync(d_cam_params_out, b->cam_params.p, b->cam_params_len * sizeof(double),
+                                   hipMemcpyDeviceToDevice, s));
+      return PCD_OK;
+    }
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(schur_build(b, s));
+    PCD_TRY(cam_upload_slots(b));
+    const BaSchur::Structure& T = b->schur->st; const BaSchur::Cam& K = b->schur->cam;
+    PCD_REQUIRE(d_delta && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) && (d_points_out || b->P == 0),
+                "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device));
+    ScopedKernelTimer t("ba_plus", s);
+    hipLaunchKernelGGL(k_ba_plus, dim3(div_up((uint64_t)b->I + b->P, 256)), dim3(256), 0, s, b->I, b->P, T.img_slot.p,
+                       b->const_tvec(), b->const_points(), b->poses.p, b->points.p, d_delta, d_dpoint, d_poses_out,
+                       d_points_out);
+    if (d_cam_params_out)
+      ba_plus_cam(b->cam_params_len, K.param_cam.p, b->cam_off.p, K.cam_slot.p, K.active.p, b->cam_params.p,
+                  d_delta + slot_vec(T.ns), d_cam_params_out, s);
+    PCD_HIP_TRY(hipGetLastError());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_get_camera_parameters(pcd_ba* b, double* cam_params) {
+  PCD_TRY(require_device(b ? b->device : 0));
+  PCD_REQUIRE(b && cam_params, "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  if (b->cam_params_len)
+    PCD_HIP_TRY(hipMemcpy(cam_params, b->cam_params.p, b->cam_params_len * sizeof(double), hipMemcpyDeviceToHost));
+  return PCD_OK;
+}
+
 void pcd_ba_solve_opts_default(pcd_ba_solve_opts* o) {
   if (!o) return;
   std::memset(o, 0, sizeof *o);
@@ -1279,37 +1557,54 @@ void pcd_ba_solve_opts_default(pcd_ba_solve_opts* o) {
 pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_summary* summary,
                         pcd_ba_solve_iteration* iterations) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b)); PCD_TRY(lm_check_opts(opts));
+    // refine_intrinsics: the camera rows ride along (pcd_ba_schur_cam*); without camera slots the flag changes nothing
+    const int ncs = (opts && opts->refine_intrinsics && b) ? cam_slots(b) : 0;
+    PCD_TRY(ncs ? schur_cam_guard(b) : schur_guard(b)); PCD_TRY(lm_check_opts(opts));
+    const bool cam = ncs > 0;
+    if (cam && opts->linear_solver != PCD_LINEAR_CHOLESKY) {
+      set_error("pcd_ba_solve: refine_intrinsics needs linear_solver = PCD_LINEAR_CHOLESKY (the PCG has no camera rows)");
+      return PCD_ERR_UNSUPPORTED;
+    }
     hipStream_t s = nullptr;
     PCD_REFUSE_CAPTURE(s);
     PCD_TRY(schur_build(b, s));
+    if (cam) PCD_TRY(cam_upload_slots(b));
     BaSchur& S = *b->schur; BaSchur::Lm& M = S.lm;
     const auto t0 = std::chrono::steady_clock::now();
     const unsigned ngp = std::max(1u, std::min(1024u, div_up((uint64_t)S.st.ns + b->P, 256)));
-    PCD_TRY(lm_reserve(b, ngp));
+    const unsigned ngr = ngp + (cam ? 1u : 0u);   // partials of the gradient norm: one more for g_cam
+    PCD_TRY(lm_reserve(b, ngr, ncs));
     PCD_HIP_TRY(hipSetDevice(b->device));
     EventPair ev; PCD_TRY(ev.create());   // around the linear solve of an iteration
     // the accepted parameters: a rejected step copies them back into the handle
     PCD_TRY(copy_parameters(b, M.poses.p, M.points.p, b->poses.p, b->points.p, s));
+    if (cam) PCD_TRY(copy_camera_parameters(b, true, s));
     pcd_ba_solve_summary sm{}; sm.termination = PCD_SOLVE_MAX_ITERATIONS;
     double radius = opts->initial_radius, factor = 2.0;
     for (int it = 0; it < opts->max_num_iterations; ++it) {
       if (radius < opts->min_radius) { sm.termination = PCD_SOLVE_MIN_RADIUS; break; }
       pcd_ba_schur_opts so{}; so.mu = 1.0 / radius; so.damping = opts->damping;
-      pcd_ba_schur_out none{};
-      PCD_TRY(pcd_ba_schur_device(b, &so, &none, s));
+      if (cam) {
+        pcd_ba_schur_cam_out none{};
+        PCD_TRY(schur_cam_device(b, &so, &none, s));
+      } else {
+        pcd_ba_schur_out none{};
+        PCD_TRY(pcd_ba_schur_device(b, &so, &none, s));
+      }
       hipLaunchKernelGGL(k_ba_grad_max, dim3(ngp), dim3(256), 0, s, S.st.ns, S.st.slot_img.p, b->const_tvec(), S.num.gimg.p,
                          b->P, b->const_points(), S.num.gpt.p, M.gpart.p);
+      if (cam) ba_cam_grad_max(ncs, S.cam.slot_cam.p, S.cam.active.p, S.cam.gcam.p, M.gpart.p + ngp, s);
       int enq = 0;
       PCD_HIP_TRY(ev.start(s));
-      PCD_TRY(lm_enqueue_linear(b, opts, &enq, s));
+      PCD_TRY(lm_enqueue_linear(b, opts, cam, &enq, s));
       PCD_HIP_TRY(ev.stop(s));
-      PCD_TRY(lm_try_step(b, opts, enq, ngp, ev, &sm.linear_solver_ms, s));
+      PCD_TRY(lm_try_step(b, opts, cam, enq, ngr, ev, &sm.linear_solver_ms, s));
       const LmRecord& rec = *M.host.p;
       if (it == 0) sm.initial_cost = sm.final_cost = rec.cost;
       const LmDecision d = lm_decide(rec, *opts, radius, factor, opts->linear_solver == PCD_LINEAR_CHOLESKY);
       if (d.it.accepted) PCD_TRY(copy_parameters(b, M.poses.p, M.points.p, b->poses.p, b->points.p, s));
       else PCD_TRY(copy_parameters(b, b->poses.p, b->points.p, M.poses.p, M.points.p, s));
+      if (cam) PCD_TRY(copy_camera_parameters(b, d.it.accepted, s));
       if (d.termination == PCD_SOLVE_GRADIENT_TOLERANCE) { sm.termination = d.termination; break; }   // no iteration recorded
       radius = d.radius; factor = d.factor;
       if (iterations) iterations[it] = d.it;
@@ -1318,7 +1613,10 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
       if (d.termination >= 0) { sm.termination = d.termination; break; }
     }
     PCD_HIP_TRY(hipStreamSynchronize(s));
-    S.num.valid = false;   // the Schur state belongs to parameters the loop has moved on from
+    if (cam && b->cam_params_len)   // the host mirror follows the accepted camera parameters (pcd_ba_project_lidar_device)
+      PCD_HIP_TRY(hipMemcpy(b->h_cam_params.data(), b->cam_params.p, b->cam_params_len * sizeof(double),
+                            hipMemcpyDeviceToHost));
+    S.num.valid = S.cam.valid = false;   // the Schur state belongs to parameters the loop has moved on from
     sm.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (summary) *summary = sm;
     return PCD_OK;

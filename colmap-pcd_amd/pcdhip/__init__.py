@@ -110,6 +110,14 @@ class BASchurOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("cost", "S_diag", "S_off", "rhs", "S", "num_skipped")]
 
 
+class BASchurCamOut(C.Structure):
+    """pcd_ba_schur_cam_out"""
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "S_diag", "S_off", "rhs", "B", "S_cam", "rhs_cam", "S", "num_skipped")]
+
+
+MAX_CAMERA_SLOTS = 8
+
+
 class BASchurInfo(C.Structure):
     _fields_ = [("build_ms", C.c_double), ("num_entries", C.c_uint64), ("scratch_bytes", C.c_uint64)]
 
@@ -169,10 +177,10 @@ class BASolveOpts(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int32), ("damping", C.c_int32), ("initial_radius", C.c_double),
                 ("max_radius", C.c_double), ("min_radius", C.c_double), ("min_relative_decrease", C.c_double),
                 ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double), ("linear", BAPcgOpts),
-                ("linear_solver", C.c_int32), ("reserved", C.c_int32 * 7)]
+                ("linear_solver", C.c_int32), ("refine_intrinsics", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
-assert C.sizeof(BASolveOpts) == 152   # linear_solver took the first word of reserved: the size did not change
+assert C.sizeof(BASolveOpts) == 152   # linear_solver and refine_intrinsics came out of reserved: the size did not change
 
 
 class BASolveIteration(C.Structure):
@@ -295,6 +303,8 @@ ABI_SYMBOLS = [
     "pcd_ba_pcg_opts_default", "pcd_ba_schur_solve_pcg_device", "pcd_ba_schur_solve_pcg", "pcd_ba_get_parameters",
     "pcd_ba_solve_opts_default", "pcd_ba_solve",
     "pcd_ba_schur_solve_cholesky_device", "pcd_ba_schur_solve_cholesky",
+    "pcd_ba_camera_slots", "pcd_ba_schur_cam_device", "pcd_ba_schur_cam", "pcd_ba_schur_cam_solve_cholesky_device",
+    "pcd_ba_schur_cam_back_substitute_device", "pcd_ba_plus_cam_device", "pcd_ba_get_camera_parameters",
     "pcd_normals_options_default", "pcd_cloud_estimate_normals_device", "pcd_cloud_estimate_normals",
     "pcd_voxel_options_default", "pcd_cloud_voxel_downsample", "pcd_cloud_voxel_downsample_device",
     "pcd_ba_set_lidar_device", "pcd_ba_get_lidar", "pcd_ba_lidar_device", "pcd_ba_assoc_opts_default",
@@ -411,6 +421,14 @@ def lib():
         L.pcd_ba_schur_solve_cholesky_device.argtypes = [C.c_void_p] * 6
         L.pcd_ba_schur_solve_cholesky.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.POINTER(BACholInfo)]
+    if hasattr(L, "pcd_ba_schur_cam_device"):
+        L.pcd_ba_camera_slots.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+        L.pcd_ba_schur_cam_device.argtypes = [C.c_void_p, C.POINTER(BASchurOpts), C.POINTER(BASchurCamOut), C.c_void_p]
+        L.pcd_ba_schur_cam.argtypes = [C.c_void_p, C.POINTER(BASchurOpts), C.POINTER(BASchurCamOut)]
+        L.pcd_ba_schur_cam_solve_cholesky_device.argtypes = [C.c_void_p] * 4
+        L.pcd_ba_schur_cam_back_substitute_device.argtypes = [C.c_void_p] * 5
+        L.pcd_ba_plus_cam_device.argtypes = [C.c_void_p] * 7
+        L.pcd_ba_get_camera_parameters.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "pcd_ba_set_lidar_device"):
         L.pcd_ba_set_lidar_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
@@ -1537,6 +1555,105 @@ class BA:
                                                  _vp(dpose), C.byref(info)))
         return dpose, {n: getattr(info, n) for n, _ in BACholInfo._fields_}
 
+    # ---- refined intrinsics: camera rows in the reduced system (pcd_ba_schur_cam*) ----
+    def camera_slots(self):
+        """dict(camera_slot [C] int32 (-1: no refined parameter), num_slots, active [num_slots][12] uint8): the camera
+        unknowns of the reduced system, n = 6 ns + 12 num_slots"""
+        ncs = C.c_int32(0)
+        _check(lib().pcd_ba_camera_slots(self._h, None, C.byref(ncs), None))
+        slot = np.zeros(self.C, np.int32)
+        active = np.zeros((ncs.value, CAM_JAC_STRIDE), np.uint8)
+        _check(lib().pcd_ba_camera_slots(self._h, _vp(slot), C.byref(ncs), _vp(active) if active.size else None))
+        return dict(camera_slot=slot, num_slots=ncs.value, active=active)
+
+    def _cam_dims(self):
+        """(ns, ncs).  The pose slots are the variable-pose images: counted here, since the structure queries of the
+        plain route are refused on a handle with refined intrinsics"""
+        if not hasattr(self, "_ncs"):
+            self._ncs = self.camera_slots()["num_slots"]
+        ns = self.I if self.image_const_pose is None else int(np.count_nonzero(self.image_const_pose == 0))
+        return ns, self._ncs
+
+    def schur_cam(self, mu, damping="marquardt", dense=False,
+                  want=("cost", "S_diag", "rhs", "B", "S_cam", "rhs_cam", "num_skipped"), num_pairs=None):
+        """schur() with the camera rows: dict of torch device tensors cost [1], S_diag [ns][6][6], rhs [ns][6],
+        B [ns][ncs][12][6], S_cam [ncs][ncs][12][12], rhs_cam [ncs][12], num_skipped [1] and, with dense=True,
+        S [n][n], n = 6 ns + 12 ncs (both triangles).  S_off [num_pairs][6][6] needs the pair count: it is that of the
+        same problem without camera_refine (schur_structure() there).  As in schur(), S_diag / S_off / rhs named in want
+        leave the handle for caller memory: schur_cam_solve_cholesky reads the handle's own, so keep them out of want
+        before it."""
+        torch, dev, stream = self._torch()
+        ns, ncs = self._cam_dims()
+        n = 6 * ns + CAM_JAC_STRIDE * ncs
+        f64 = dict(dtype=torch.float64, device=dev)
+        shapes = dict(cost=(1,), S_diag=(ns, 6, 6), rhs=(ns, 6), B=(ns, ncs, CAM_JAC_STRIDE, 6),
+                      S_cam=(ncs, ncs, CAM_JAC_STRIDE, CAM_JAC_STRIDE), rhs_cam=(ncs, CAM_JAC_STRIDE), S=(n, n))
+        if "S_off" in want:
+            if num_pairs is None:
+                raise ValueError("S_off needs num_pairs")
+            shapes["S_off"] = (int(num_pairs), 6, 6)
+        out = {k: torch.zeros(shapes[k], **f64) for k in want if k in shapes and k != "S"}
+        if "num_skipped" in want:
+            out["num_skipped"] = torch.zeros(1, dtype=torch.int64, device=dev)
+        if dense:
+            out["S"] = torch.zeros(shapes["S"], **f64)
+        # an empty tensor has a null data pointer, which reads as "not asked for": nothing would be written anyway
+        o = BASchurCamOut(*[_ptr(out[k]) if k in out and out[k].numel() else None for k, _ in BASchurCamOut._fields_])
+        opts = BASchurOpts(float(mu), _DAMPING[damping])
+        _check(lib().pcd_ba_schur_cam_device(self._h, C.byref(opts), C.byref(o), C.c_void_p(stream)))
+        return out
+
+    def schur_cam_solve_cholesky(self, delta=None):
+        """direct solve of the bordered system of the last schur_cam() call from the handle's own blocks: (delta [n] torch
+        device tensor = dpose [ns][6] then dcam [ncs][12], zeros when the factorisation failed; info dict as
+        schur_solve_cholesky)"""
+        torch, dev, stream = self._torch()
+        ns, ncs = self._cam_dims()
+        n = 6 * ns + CAM_JAC_STRIDE * ncs
+        if delta is None:
+            delta = torch.empty(n, dtype=torch.float64, device=dev)
+        d_info = torch.zeros(C.sizeof(BACholInfo), dtype=torch.uint8, device=dev)
+        pad = torch.zeros(1, dtype=torch.float64, device=dev)   # n = 0: an empty tensor's pointer is null
+        _check(lib().pcd_ba_schur_cam_solve_cholesky_device(self._h, _ptr(delta if n else pad), _ptr(d_info),
+                                                            C.c_void_p(stream)))
+        i = d_info.cpu().numpy().view(CHOL_INFO_DTYPE)[0]
+        return delta, {k: (float(i[k]) if CHOL_INFO_DTYPE[k] == np.float64 else int(i[k]))
+                       for k in CHOL_INFO_DTYPE.names if k != "pad"}
+
+    def back_substitute_cam(self, delta, dpoint=None, model_decrease=True):
+        """point steps of the last schur_cam() call for delta [n] (dpose then dcam; torch, device): returns
+        (dpoint [P][3], model decrease [1] or None)"""
+        torch, dev, stream = self._torch()
+        delta = delta.to(device=dev, dtype=torch.float64).contiguous().reshape(-1)
+        pad = torch.zeros(1, dtype=torch.float64, device=dev)
+        if dpoint is None:
+            dpoint = torch.empty((self.P, 3), dtype=torch.float64, device=dev)
+        md = torch.empty(1, dtype=torch.float64, device=dev) if model_decrease else None
+        _check(lib().pcd_ba_schur_cam_back_substitute_device(self._h, _ptr(delta if delta.numel() else pad), _ptr(dpoint),
+                                                             _ptr(md), C.c_void_p(stream)))
+        return dpoint, md
+
+    def plus_cam(self, delta, dpoint):
+        """candidate parameters from the handle's current ones: plus() on poses and points, p + dcam on the active camera
+        parameters (everything constant copied bit for bit).  Returns (poses [I][7], points [P][3], cam_params
+        [cam_params_len]) torch device tensors"""
+        torch, dev, stream = self._torch()
+        delta = delta.to(device=dev, dtype=torch.float64).contiguous().reshape(-1)
+        dpoint = dpoint.to(device=dev, dtype=torch.float64).contiguous()
+        pad = torch.zeros(1, dtype=torch.float64, device=dev)
+        poses = torch.empty((self.I, 7), dtype=torch.float64, device=dev)
+        points = torch.empty((self.P, 3), dtype=torch.float64, device=dev)
+        cams = torch.empty(len(self.cam_params), dtype=torch.float64, device=dev)
+        _check(lib().pcd_ba_plus_cam_device(self._h, _ptr(delta if delta.numel() else pad), _ptr(dpoint), _ptr(poses),
+                                            _ptr(points), _ptr(cams), C.c_void_p(stream)))
+        return poses, points, cams
+
+    def get_camera_parameters(self):
+        """the handle's current camera parameters, device -> host: packed numpy [cam_params_len]"""
+        out = np.empty(len(self.cam_params))
+        _check(lib().pcd_ba_get_camera_parameters(self._h, _vp(out)))
+        return out
+
     def get_parameters(self):
         """the handle's current parameters, device -> host: (poses [I][7], points [P][3]) numpy"""
         poses, points = np.empty((self.I, 7)), np.empty((self.P, 3))
@@ -1711,12 +1828,14 @@ def _pcg_info(i):
 
 def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max_radius=None, min_radius=None,
              min_relative_decrease=None, function_tolerance=None, gradient_tolerance=None, linear=None,
-             linear_solver="pcg"):
+             linear_solver="pcg", refine_intrinsics=False):
     """pcd_ba_solve: the LM loop in the library (Schur, PCG, back-substitution, cost pass; no torch).  Options left
     None keep pcd_ba_solve_opts_default; linear is a dict of pcg_opts() arguments.  linear_solver="cholesky" takes the
     exact step of the library's blocked Cholesky instead of the PCG's inexact one (linear_iterations is then 0 and
     linear_termination a CHOL_* status).  Returns (summary dict, list of one dict per iteration); the handle holds
-    the accepted parameters (BA.get_parameters())."""
+    the accepted parameters (BA.get_parameters()).  refine_intrinsics=True solves for the refined camera parameters
+    too (camera rows in the reduced system; the direct solver only) and leaves the accepted ones in the handle
+    (BA.get_camera_parameters()); without it a handle with camera_refine is refused."""
     L = lib()
     o = BASolveOpts()
     L.pcd_ba_solve_opts_default(C.byref(o))
@@ -1730,6 +1849,7 @@ def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max
         if v is not None:
             setattr(o, name, float(v))
     o.linear_solver = _LINEAR[linear_solver] if isinstance(linear_solver, str) else int(linear_solver)
+    o.refine_intrinsics = int(bool(refine_intrinsics))
     if linear is not None:
         o.linear = linear if isinstance(linear, BAPcgOpts) else pcg_opts(**linear)
     its = (BASolveIteration * max(o.max_num_iterations, 1))()

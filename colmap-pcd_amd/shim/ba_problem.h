@@ -77,6 +77,10 @@ struct BundleAdjustmentOptions {  // optim/bundle_adjustment.h:52-91 (this fork'
   double loss_function_scale = 1.0;
   bool refine_focal_length = false, refine_principal_point = false, refine_extra_params = false;
   bool refine_extrinsics = true;
+  // Refined intrinsics on the device route (pcd_ba_solve with refine_intrinsics: camera rows in the reduced system, the
+  // direct solver whatever linear_solver_type says).  false: BundleAdjusterHip::Solve returns false when a refine_* switch
+  // leaves a camera parameter variable, and the caller stays on the Ceres route.
+  bool refine_intrinsics_on_device = false;
   // ceres::Solver::Options members BundleAdjusterHip::Solve reads (optim/bundle_adjustment.h:96-103)
   int max_num_iterations = 100;
   int max_linear_solver_iterations = 200;
@@ -218,14 +222,17 @@ class BundleAdjusterHip {
   // Create, pcd_ba_solve (LM with the linear solver options_.linear_solver_type selects, the block-sparse PCG on the
   // reduced camera system unless told otherwise), then the accepted poses and
   // points go back into the Reconstruction through image_ids_ / point_ids_; constant poses and points are not
-  // written at all.  false when there are no residuals (as the reference, :489-491), when intrinsics are refined
-  // (the device route does not carry camera rows: the caller stays on the Ceres route) or when a call fails
-  // (pcd_last_error()).
+  // written at all.  false when there are no residuals (as the reference, :489-491), when intrinsics are refined and
+  // options_.refine_intrinsics_on_device is off (the caller stays on the Ceres route) or when a call fails
+  // (pcd_last_error(); with refined intrinsics also when the library refuses: more refined cameras than
+  // PCD_BA_MAX_CAMERA_SLOTS).  With refine_intrinsics_on_device the accepted parameters of every variable camera go back
+  // into rec->cameras beside poses and points.
   bool Solve(Reconstruction* rec, int device = 0) {
     summary_ = pcd_ba_solve_summary{};
     if (NumResiduals() == 0) return false;
-    for (uint8_t v : cam_refine_)
-      if (v) return false;
+    bool refined = false;
+    for (uint8_t v : cam_refine_) refined |= v != 0;
+    if (refined && !options_.refine_intrinsics_on_device) return false;
     // after ReassociateLidar the live handle IS the problem (its parameters and terms are the flat arrays'): keep it
     if (!(reassociated_ && ba_) && !Create(device)) return false;
     reassociated_ = false;
@@ -235,9 +242,18 @@ class BundleAdjusterHip {
     o.function_tolerance = options_.function_tolerance;
     o.gradient_tolerance = options_.gradient_tolerance;
     o.linear.max_iterations = options_.max_linear_solver_iterations;
-    o.linear_solver = UsesDirectSolver() ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG;
+    o.linear_solver = (refined || UsesDirectSolver()) ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG;
+    o.refine_intrinsics = refined ? 1 : 0;
     if (pcd_ba_solve(ba_, &o, &summary_, nullptr) != PCD_OK) return false;
     if (pcd_ba_get_parameters(ba_, poses_.data(), points_.data()) != PCD_OK) return false;
+    if (refined) {
+      if (pcd_ba_get_camera_parameters(ba_, cam_params_.data()) != PCD_OK) return false;
+      for (size_t c = 0; c < camera_ids_.size(); ++c) {
+        if (!CameraVariable((int)c)) continue;
+        Camera& cam = rec->cameras.at(camera_ids_[c]);
+        std::copy(cam_params_.begin() + cam_off_[c], cam_params_.begin() + cam_off_[c] + cam.params.size(), cam.params.begin());
+      }
+    }
     for (size_t i = 0; i < image_ids_.size(); ++i) {
       if (image_const_pose_[i]) continue;
       Image& im = rec->images.at(image_ids_[i]);

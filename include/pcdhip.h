@@ -870,7 +870,9 @@ typedef struct {
   double initial_radius, max_radius, min_radius, min_relative_decrease, function_tolerance, gradient_tolerance;
   pcd_ba_pcg_opts linear;
   int32_t linear_solver;            /* pcd_ba_linear_solver; 0 (a zero-filled struct, the defaults) = PCG */
-  int32_t reserved[7];
+  int32_t refine_intrinsics;        /* 1: solve for the refined camera parameters too (pcd_ba_schur_cam* below);  */
+                                    /* 0 (a zero-filled struct, the defaults): a refined handle is refused        */
+  int32_t reserved[6];
 } pcd_ba_solve_opts;
 typedef struct {
   double cost, candidate_cost, model_decrease, relative_decrease;
@@ -889,6 +891,68 @@ typedef struct {
 void pcd_ba_solve_opts_default(pcd_ba_solve_opts* opts);
 pcd_status pcd_ba_solve(pcd_ba* ba, const pcd_ba_solve_opts* opts, pcd_ba_solve_summary* summary,
                         pcd_ba_solve_iteration* iterations /*[max_num_iterations] or NULL*/);
+
+/* Refined intrinsics in the reduced system: the calls above stay refused on a handle with a camera_refine
+ * byte set; the calls below, beside them, carry the camera rows.  Camera slots are the cameras with at least one
+ * refined parameter, in ascending camera index, ncs of them; each has PCD_CAM_JAC_STRIDE coordinates of which the
+ * refined entries below the model's K are active and the others inactive exactly as a constant-tvec coordinate is
+ * (identity row and column, right-hand side 0, delta 0).  Reduced unknowns: [6 ns pose tangents | 12 ncs camera
+ * coordinates], n = 6 ns + 12 ncs.  With V_p, W_a as above and cam(o) the camera slot of observation o's image:
+ *   Wc_p[r] = sum over the observations o of point p with cam(o) = r, ascending o, of W_cam[o]       (12 x 3)
+ *   Z_p[r]  = Wc_p[r] V_p^-1                                            (0 for constant and skipped points)
+ *   S_cam[r][r'] = delta_rr' (H_cam[r] + D_r) - sum_p Z_p[r] Wc_p[r']^T
+ *   B[i][r]      = [cam(image of slot i) = r] E_cam[image] - sum over the eliminated observations e of the image,
+ *                  image-major, of Z_pt(e)[r] W_e^T                      (constant-tvec columns zero)
+ *   rhs_cam[r]   = -g_cam[r] + sum_p Z_p[r] g_p
+ *   S = [[S_pose, B^T], [B, S_cam]],  D_r,kk = the damping of H_cam[r][k][k] on the active coordinates
+ *   dX_p = -V_p^-1 (g_p + sum_a W_a^T dpose[slot(a)] + sum_r Wc_p[r]^T dcam[r])
+ * and the model decrease gains 1/2 sum over the active camera coordinates of (-dcam g_cam + D dcam^2).  An observation
+ * in a constant-pose image has no slot but still couples its camera to its point.  The pose part (S_diag, S_off, rhs)
+ * is that of pcd_ba_schur_device, bit for bit.  The direct solve only: the PCG knows no border.  Camera slots couple
+ * every image of a camera, so they are kept dense and few: more than PCD_BA_MAX_CAMERA_SLOTS (for example one refined
+ * camera per image) -> PCD_ERR_UNSUPPORTED from every call below and from pcd_ba_solve with refine_intrinsics, before
+ * anything is allocated or launched; the handle stays usable.  The other guards (NULL, no device, capturing stream,
+ * "no Schur state") are those of the plain calls.  On a handle without camera slots every call below is valid and
+ * returns bit for bit what its plain counterpart returns.  No atomics, fixed-order sums: bitwise reproducible. */
+#define PCD_BA_MAX_CAMERA_SLOTS 8
+/* host query, no device work: camera_slot [C] (-1: no refined parameter), the number of slots, active [ncs][12]
+ * (1 = the coordinate is solved for); every output may be NULL */
+pcd_status pcd_ba_camera_slots(pcd_ba* ba, int32_t* camera_slot, int32_t* num_slots, uint8_t* active);
+/* every pointer may be NULL (not written) */
+typedef struct {
+  double *cost, *S_diag, *S_off, *rhs;   /* as pcd_ba_schur_out */
+  double* B;                             /* [ns][ncs][12][6] */
+  double* S_cam;                         /* [ncs][ncs][12][12], both triangles */
+  double* rhs_cam;                       /* [ncs][12] */
+  double* S;                             /* [n][n] dense, row-major, both triangles */
+  uint64_t* num_skipped;
+} pcd_ba_schur_cam_out;
+/* Normal-equation pass with the camera blocks (pcd_ba_evaluate_device's H_cam, g_cam, E_cam, W_cam) into handle
+ * scratch, then the elimination.  B, S_cam and rhs_cam always stay in the handle; the outputs are copies. */
+pcd_status pcd_ba_schur_cam_device(pcd_ba* ba, const pcd_ba_schur_opts* opts, const pcd_ba_schur_cam_out* d_out,
+                                   void* stream);
+pcd_status pcd_ba_schur_cam(pcd_ba* ba, const pcd_ba_schur_opts* opts, const pcd_ba_schur_cam_out* out);   /* host outputs */
+/* Direct solve (pcd_ba_schur_solve_cholesky_device's factorisation) of the bordered system from the handle's own blocks
+ * of the last pcd_ba_schur_cam* (INVALID without one, or when that call sent S_diag / S_off / rhs to caller memory);
+ * d_delta [n] = dpose [ns][6], then dcam [ncs][12] (0 on inactive coordinates; all 0 when the factorisation failed). */
+pcd_status pcd_ba_schur_cam_solve_cholesky_device(pcd_ba* ba, double* d_delta, pcd_ba_chol_info* d_info /*may be NULL*/,
+                                                  void* stream);
+/* point steps and model decrease for d_delta [n], from the state of the last pcd_ba_schur_cam* */
+pcd_status pcd_ba_schur_cam_back_substitute_device(pcd_ba* ba, const double* d_delta, double* d_dpoint /*[P][3]*/,
+                                                   double* d_model_decrease /*[1] or NULL*/, void* stream);
+/* pcd_ba_plus_device, and p + dcam on the active camera parameters; constant cameras and parameters are copied bit for
+ * bit.  Reads the handle's current parameters; in-place safe.  d_cam_params_out may be NULL (not written). */
+pcd_status pcd_ba_plus_cam_device(pcd_ba* ba, const double* d_delta, const double* d_dpoint, double* d_poses_out,
+                                  double* d_points_out, double* d_cam_params_out /*[cam_params_len]*/, void* stream);
+/* current camera parameters, device -> host */
+pcd_status pcd_ba_get_camera_parameters(pcd_ba* ba, double* cam_params /*[cam_params_len] host*/);
+/* pcd_ba_solve with refine_intrinsics = 1: each iteration runs pcd_ba_schur_cam_device, the direct solve of the bordered
+ * system, the back-substitution, Plus on poses, points and the active camera parameters, and the cost pass; the
+ * trust-region rule is unchanged, the gradient max-norm includes g_cam over the active coordinates, the accepted camera
+ * parameters are kept beside the accepted poses and points and restored on a rejected step.  On return the handle
+ * holds the accepted camera parameters, on the device and in the host mirror pcd_ba_project_lidar_device reads.
+ * refine_intrinsics = 1 with PCD_LINEAR_PCG on a handle that has camera slots -> PCD_ERR_UNSUPPORTED (use
+ * PCD_LINEAR_CHOLESKY).  On a handle without camera slots the flag changes nothing. */
 
 /* ------------------------------------------------------------------------
  * Re-association of a handle's LiDAR terms on the device        
