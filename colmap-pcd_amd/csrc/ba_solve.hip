@@ -8,7 +8,8 @@
 // kernel is compiled here.
 //
 // Refined intrinsics ride beside all this, opt-in (pcd_ba_schur_cam*, pcd_ba_solve with refine_intrinsics): the camera rows
-// of the reduced system are a dense border whose kernels live in ba_solve_cam.hip; the state and the entry points are here.
+// of the reduced system are a dense border whose kernels live in ba_solve_cam.hip, the kernels of the PCG on the bordered
+// system (pcd_ba_schur_cam_solve_pcg*, PCD_LINEAR_PCG_CAM) in ba_pcg_cam.hip; the state and the entry points are here.
 //
 // Host side, behind the kernels: BaSchur, the solver state grouped by owner; schur_build, which has the co-visibility
 // structure built on the device (ba_schur_structure.hip) on the stream of the call that needs it; the PCG batches;
@@ -375,28 +376,7 @@ __global__ __launch_bounds__(256) void k_ba_plus(int I, int P, const int* __rest
 // p and x are double-buffered (iteration it reads buffer it & 1 and writes the other): the product forms the new
 // direction of a partner slot on the fly from z and the old p instead of waiting for a fourth launch, and a breakdown
 // leaves the last finite x untouched.  All sums run in an order fixed by the structure.
-struct PcgState {
-  double rho, alpha, beta, pw, q, rn2, bnorm, xr;
-  int k, done, term, xsel;
-  unsigned fallbacks; int pad;
-};
-struct PcgRule { int max_iterations, min_iterations; double q_tolerance, r_tolerance; };
-
-// sum over the workgroup (256 threads), every thread gets the result; fixed order: wavefront butterfly, then the 4 waves
-__device__ __forceinline__ double block_sum256(double v, double* lds4) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();   // lds4 may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-}
-// strided sum of partial[i * stride] (i < n) over one workgroup
-__device__ __forceinline__ double block_sum_strided(const double* __restrict__ partial, int n, int stride, double* lds4) {
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) a += partial[(size_t)i * stride];
-  return block_sum256(a, lds4);
-}
+// PcgState, PcgRule, block_sum256, block_sum_strided: ba_solve_cam.h, shared with the bordered PCG.
 
 // thread = slot: M_i^-1 (SCHUR_JACOBI: inverse of the 6x6 diagonal block through its Cholesky factor, identity when a
 // pivot is not positive and finite -- counted; IDENTITY: I), x = 0, r = rhs, z = M^-1 r, both direction buffers 0;
@@ -734,9 +714,12 @@ struct BaSchur {
   } num;
   struct Pcg {   // pcd_ba_schur_solve_pcg*
     DevBuf<double> Minv, x0, x1, r, z, p0, p1, w, pw, partial, out;   // out: staging of the host form
+    DevBuf<double> Minv_cam, camw;   // the bordered solve: the vectors above then carry the camera part behind the poses
     DevBuf<PcgState> state; DevBuf<pcd_ba_pcg_info> info; PinnedBuf<int> flag;
     int it = 0;   // iterations enqueued in the running solve (buffer parity)
-    uint64_t bytes() const { return dev_bytes(Minv, x0, x1, r, z, p0, p1, w, pw, partial, out, state, info); }
+    uint64_t bytes() const {
+      return dev_bytes(Minv, x0, x1, r, z, p0, p1, w, pw, partial, out, Minv_cam, camw, state, info);
+    }
   } cg;
   struct Lm {   // pcd_ba_solve: the step, the accepted parameters, the record of an iteration
     DevBuf<double> dpose, dpoint, poses, points, cam_params, cand_cost, gpart;   // dpose: dcam behind it with camera rows
@@ -837,31 +820,52 @@ static PcgRule pcg_rule(const pcd_ba_pcg_opts* o) {
   return PcgRule{o->max_iterations, o->min_iterations, o->q_tolerance, o->r_tolerance};
 }
 
-// preconditioner, x = 0, r = rhs, the scalars of iteration 0
-static pcd_status pcg_begin(pcd_ba* b, const pcd_ba_pcg_opts* o, hipStream_t s) {
+static int cam_slots(const pcd_ba* b) { return (int)b->h_slot_cam.size(); }
+
+// the bordered solve's view of the handle (cam: the last Schur call carried camera rows)
+static PcgCamVec pcg_cam_vec(pcd_ba* b) {
   BaSchur& S = *b->schur; BaSchur::Pcg& C = S.cg;
-  const int ns = S.st.ns; const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256));
+  return PcgCamVec{S.st.ns, cam_slots(b), C.state.p, S.cam.B.p, S.cam.Scam.p, S.cam.rhs.p, C.Minv_cam.p, C.z.p, C.r.p,
+                   C.w.p, C.camw.p, C.pw.p, C.partial.p};
+}
+
+// preconditioner, x = 0, r = rhs, the scalars of iteration 0.  cam: the bordered system, whose vectors carry the
+// 12 ncs camera coordinates behind the poses and whose partial lists one entry per camera slot behind the workgroups
+static pcd_status pcg_begin(pcd_ba* b, const pcd_ba_pcg_opts* o, bool cam, hipStream_t s) {
+  BaSchur& S = *b->schur; BaSchur::Pcg& C = S.cg;
+  const int ns = S.st.ns, ncs = cam ? cam_slots(b) : 0; const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256));
+  const size_t nc = (size_t)kCamS * ncs;
   PCD_TRY(C.Minv.reserve(at_least_1(blocks_6x6(ns))));
-  for (DevBuf<double>* d : {&C.x0, &C.x1, &C.r, &C.z, &C.p0, &C.p1, &C.w}) PCD_TRY(d->reserve(at_least_1(slot_vec(ns))));
-  PCD_TRY(C.pw.reserve(at_least_1(ns))); PCD_TRY(C.partial.reserve(4 * (size_t)nb));
+  for (DevBuf<double>* d : {&C.x0, &C.x1, &C.r, &C.z, &C.p0, &C.p1, &C.w}) PCD_TRY(d->reserve(at_least_1(slot_vec(ns) + nc)));
+  PCD_TRY(C.pw.reserve(at_least_1(ns + nc))); PCD_TRY(C.partial.reserve(4 * ((size_t)nb + ncs)));
   PCD_TRY(C.state.reserve(1)); PCD_TRY(C.info.reserve(1)); PCD_TRY(C.flag.reserve(4));
+  if (cam) { PCD_TRY(C.Minv_cam.reserve(nc * kCamS)); PCD_TRY(C.camw.reserve(at_least_1(nc * ns))); }
   C.it = 0;
   hipLaunchKernelGGL(k_pcg_init, dim3(nb), dim3(256), 0, s, ns, o->preconditioner, S.num.Sdiag.p, S.num.rhs.p, C.Minv.p,
                      C.x0.p, C.r.p, C.z.p, C.p0.p, C.p1.p, C.partial.p);
-  hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(256), 0, s, (int)nb, C.partial.p, pcg_rule(o), C.state.p);
+  if (cam) pcg_cam_init(pcg_cam_vec(b), o->preconditioner, C.x0.p, C.p0.p, C.p1.p, s);
+  hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(256), 0, s, (int)nb + ncs, C.partial.p, pcg_rule(o), C.state.p);
   return PCD_OK;
 }
 
-// `count` more iterations (three launches each; all of them return at once when the solve has ended)
-static void pcg_enqueue(pcd_ba* b, const pcd_ba_pcg_opts* o, int count, hipStream_t s) {
+// `count` more iterations (three launches each, four on the bordered system; all of them return at once when the solve
+// has ended)
+static void pcg_enqueue(pcd_ba* b, const pcd_ba_pcg_opts* o, bool cam, int count, hipStream_t s) {
   const BaSchur::Structure& T = b->schur->st; const BaSchur::Numeric& N = b->schur->num; BaSchur::Pcg& C = b->schur->cg;
   const int ns = T.ns;
-  if (!ns) return;
-  const unsigned nb = div_up((uint64_t)ns, 256); const PcgRule rule = pcg_rule(o);
+  if (!ns && !cam) return;
+  const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256)); const PcgRule rule = pcg_rule(o);
   for (int c = 0; c < count; ++c, ++C.it) {
     const int it = C.it;
     double* p_old = (it & 1) ? C.p1.p : C.p0.p; double* p_new = (it & 1) ? C.p0.p : C.p1.p;
     double* x_old = (it & 1) ? C.x1.p : C.x0.p; double* x_new = (it & 1) ? C.x0.p : C.x1.p;
+    if (cam) {
+      const PcgCamVec v = pcg_cam_vec(b);
+      pcg_cam_product(v, T.row_start.p, T.row_blk.p, T.row_col.p, N.Sdiag.p, N.Soff.p, p_old, p_new, s);
+      pcg_cam_update(v, C.state.p, C.Minv.p, N.rhs.p, p_new, x_old, x_new, s);
+      hipLaunchKernelGGL(k_pcg_step, dim3(1), dim3(256), 0, s, (int)nb + v.ncs, it, C.partial.p, rule, C.state.p);
+      continue;
+    }
     hipLaunchKernelGGL(k_pcg_spmv, dim3(div_up((uint64_t)ns, 4)), dim3(256), 0, s, ns, C.state.p, T.row_start.p,
                        T.row_blk.p, T.row_col.p, N.Sdiag.p, N.Soff.p, C.z.p, p_old, p_new, C.w.p, C.pw.p);
     hipLaunchKernelGGL(k_pcg_update, dim3(nb), dim3(256), 0, s, ns, C.state.p, C.pw.p, C.Minv.p, N.rhs.p, p_new, C.w.p,
@@ -870,24 +874,25 @@ static void pcg_enqueue(pcd_ba* b, const pcd_ba_pcg_opts* o, int count, hipStrea
   }
 }
 
-static void pcg_finish(pcd_ba* b, double* d_dpose, pcd_ba_pcg_info* d_info, hipStream_t s) {
-  const int ns = b->schur->st.ns; BaSchur::Pcg& C = b->schur->cg;
+// x into d_delta: k_pcg_finish copies 6 slots' worth per slot, and the bordered vector is 6 (ns + 2 ncs) long
+static void pcg_finish(pcd_ba* b, bool cam, double* d_delta, pcd_ba_pcg_info* d_info, hipStream_t s) {
+  const int ns = b->schur->st.ns + (cam ? 2 * cam_slots(b) : 0); BaSchur::Pcg& C = b->schur->cg;
   hipLaunchKernelGGL(k_pcg_finish, dim3(std::max(1u, div_up(slot_vec(ns), 256))), dim3(256), 0, s, ns, C.state.p, C.x0.p,
-                     C.x1.p, d_dpose, d_info);
+                     C.x1.p, d_delta, d_info);
 }
 
 // batches until the device says done; `enqueued` iterations are already in the stream.  One flag copy per batch.
-static pcd_status pcg_run(pcd_ba* b, const pcd_ba_pcg_opts* o, int enqueued, hipStream_t s) {
+static pcd_status pcg_run(pcd_ba* b, const pcd_ba_pcg_opts* o, bool cam, int enqueued, hipStream_t s) {
   BaSchur::Pcg& C = b->schur->cg;
   int batch = kPcgFirstBatch;
-  if (!enqueued) { pcg_enqueue(b, o, std::min(batch, o->max_iterations), s); enqueued = std::min(batch, o->max_iterations); }
+  if (!enqueued) { pcg_enqueue(b, o, cam, std::min(batch, o->max_iterations), s); enqueued = std::min(batch, o->max_iterations); }
   for (;;) {
     PCD_HIP_TRY(hipMemcpyAsync(C.flag.p, &C.state.p->done, sizeof(int), hipMemcpyDeviceToHost, s));
     PCD_HIP_TRY(hipStreamSynchronize(s));
-    if (C.flag.p[0] || !b->schur->st.ns || enqueued >= o->max_iterations) return PCD_OK;
+    if (C.flag.p[0] || (!b->schur->st.ns && !cam) || enqueued >= o->max_iterations) return PCD_OK;
     batch = std::min(2 * batch, kPcgMaxBatch);
     const int n = std::min(batch, o->max_iterations - enqueued);
-    pcg_enqueue(b, o, n, s); enqueued += n;
+    pcg_enqueue(b, o, cam, n, s); enqueued += n;
   }
 }
 
@@ -929,7 +934,8 @@ static pcd_status lm_check_opts(const pcd_ba_solve_opts* o) {
   PCD_REQUIRE(o->damping == PCD_DAMP_MARQUARDT || o->damping == PCD_DAMP_LEVENBERG, "damping");
   PCD_REQUIRE(o->max_num_iterations >= 0, "max_num_iterations must be >= 0");
   PCD_REQUIRE(o->initial_radius > 0.0 && o->max_radius > 0.0, "radius must be > 0");
-  PCD_REQUIRE(o->linear_solver == PCD_LINEAR_PCG || o->linear_solver == PCD_LINEAR_CHOLESKY, "linear_solver");
+  PCD_REQUIRE(o->linear_solver == PCD_LINEAR_PCG || o->linear_solver == PCD_LINEAR_CHOLESKY ||
+              o->linear_solver == PCD_LINEAR_PCG_CAM, "linear_solver");
   return PCD_OK;
 }
 
@@ -979,9 +985,9 @@ static pcd_status lm_enqueue_linear(pcd_ba* b, const pcd_ba_solve_opts* o, bool 
       PCD_HIP_TRY(hipMemsetAsync(S.cg.info.p, 0, sizeof(pcd_ba_pcg_info), s));   // 0 iterations, PCD_CHOL_OK
     }
   } else {
-    PCD_TRY(pcg_begin(b, &o->linear, s));
+    PCD_TRY(pcg_begin(b, &o->linear, cam, s));   // cam: PCD_LINEAR_PCG_CAM, the bordered system
     *enq = std::min(kPcgFirstBatch, o->linear.max_iterations);
-    pcg_enqueue(b, &o->linear, *enq, s);
+    pcg_enqueue(b, &o->linear, cam, *enq, s);
   }
   return PCD_OK;
 }
@@ -994,8 +1000,8 @@ static pcd_status lm_try_step(pcd_ba* b, const pcd_ba_solve_opts* o, bool cam, i
   BaSchur& S = *b->schur; BaSchur::Lm& M = S.lm;
   pcd_ba_out co{}; co.cost = M.cand_cost.p;
   for (;;) {
-    if (o->linear_solver == PCD_LINEAR_PCG) pcg_finish(b, M.dpose.p, S.cg.info.p, s);
-    if (cam) {   // the direct solve only: the loop below ends after one pass
+    if (o->linear_solver != PCD_LINEAR_CHOLESKY) pcg_finish(b, cam, M.dpose.p, S.cg.info.p, s);
+    if (cam) {
       PCD_TRY(pcd_ba_schur_cam_back_substitute_device(b, M.dpose.p, M.dpoint.p, S.num.md.p, s));
       PCD_TRY(pcd_ba_plus_cam_device(b, M.dpose.p, M.dpoint.p, b->poses.p, b->points.p, b->cam_params.p, s));
     } else {
@@ -1010,8 +1016,9 @@ static pcd_status lm_try_step(pcd_ba* b, const pcd_ba_solve_opts* o, bool cam, i
     if (float ms = 0.f; ev.elapsed(&ms) == hipSuccess) *linear_ms += ms;
     if (M.host.p->pcg.termination >= 0 || enq >= o->linear.max_iterations) break;
     PCD_TRY(copy_parameters(b, b->poses.p, b->points.p, M.poses.p, M.points.p, s));
+    if (cam) PCD_TRY(copy_camera_parameters(b, false, s));
     PCD_HIP_TRY(ev.start(s));
-    PCD_TRY(pcg_run(b, &o->linear, enq, s)); enq = o->linear.max_iterations;
+    PCD_TRY(pcg_run(b, &o->linear, cam, enq, s)); enq = o->linear.max_iterations;
     PCD_HIP_TRY(ev.stop(s));
   }
   PCD_HIP_TRY(hipGetLastError());
@@ -1089,7 +1096,6 @@ static pcd_status schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pc
 }
 
 // ---- camera rows: refined intrinsics in the reduced system (pcd_ba_schur_cam*, ba_solve_cam.h) --------------------
-static int cam_slots(const pcd_ba* b) { return (int)b->h_slot_cam.size(); }
 
 // Every _cam entry point: the guards of the plain calls without their refusal of a refined handle; instead more camera
 // slots than the bordered system carries -> UNSUPPORTED.  Before anything is allocated or launched.
@@ -1341,9 +1347,9 @@ pcd_status pcd_ba_schur_solve_pcg_device(pcd_ba* b, const pcd_ba_pcg_opts* opts,
     PCD_REQUIRE(d_dpose || b->schur->st.ns == 0, "null pointer");
     PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
     ScopedKernelTimer t("ba_schur_pcg", s);
-    PCD_TRY(pcg_begin(b, opts, s));
-    PCD_TRY(pcg_run(b, opts, 0, s));
-    pcg_finish(b, d_dpose, d_info, s);
+    PCD_TRY(pcg_begin(b, opts, false, s));
+    PCD_TRY(pcg_run(b, opts, false, 0, s));
+    pcg_finish(b, false, d_dpose, d_info, s);
     PCD_HIP_TRY(hipGetLastError());
     return PCD_OK;
   });
@@ -1481,6 +1487,42 @@ pcd_status pcd_ba_schur_cam_solve_cholesky_device(pcd_ba* b, double* d_delta, pc
   });
 }
 
+pcd_status pcd_ba_schur_cam_solve_pcg_device(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* d_delta,
+                                             pcd_ba_pcg_info* d_info, void* stream) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_cam_guard(b));
+    if (!cam_slots(b)) return pcd_ba_schur_solve_pcg_device(b, opts, d_delta, d_info, stream);
+    PCD_TRY(pcg_check_opts(opts));
+    PCD_REFUSE_CAPTURE(stream);
+    PCD_TRY(schur_cam_state_guard(b, "pcd_ba_schur_cam_solve_pcg_device", true));
+    PCD_REQUIRE(d_delta, "null pointer");
+    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
+    ScopedKernelTimer t("ba_schur_pcg", s);
+    PCD_TRY(pcg_begin(b, opts, true, s));
+    PCD_TRY(pcg_run(b, opts, true, 0, s));
+    pcg_finish(b, true, d_delta, d_info, s);
+    PCD_HIP_TRY(hipGetLastError());
+    return PCD_OK;
+  });
+}
+
+pcd_status pcd_ba_schur_cam_solve_pcg(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* delta, pcd_ba_pcg_info* info) {
+  return pcd::guard([&]() -> pcd_status {
+    PCD_TRY(schur_cam_guard(b));
+    if (!cam_slots(b)) return pcd_ba_schur_solve_pcg(b, opts, delta, info);
+    PCD_TRY(pcg_check_opts(opts));
+    PCD_TRY(schur_cam_state_guard(b, "pcd_ba_schur_cam_solve_pcg", true));
+    PCD_REQUIRE(delta, "null pointer");
+    BaSchur::Pcg& C = b->schur->cg;
+    const size_t n = slot_vec(b->schur->st.ns) + (size_t)kCamS * cam_slots(b);
+    PCD_TRY(C.out.reserve(n)); PCD_TRY(C.info.reserve(1));
+    PCD_TRY(pcd_ba_schur_cam_solve_pcg_device(b, opts, C.out.p, C.info.p, nullptr));
+    PCD_TRY(copy_back(delta, C.out, n)); PCD_TRY(copy_back(info, C.info, 1));
+    PCD_HIP_TRY(hipDeviceSynchronize());
+    return PCD_OK;
+  });
+}
+
 pcd_status pcd_ba_schur_cam_back_substitute_device(pcd_ba* b, const double* d_delta, double* d_dpoint,
                                                    double* d_model_decrease, void* stream) {
   PCD_TRY(schur_cam_guard(b));
@@ -1561,10 +1603,14 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
     const int ncs = (opts && opts->refine_intrinsics && b) ? cam_slots(b) : 0;
     PCD_TRY(ncs ? schur_cam_guard(b) : schur_guard(b)); PCD_TRY(lm_check_opts(opts));
     const bool cam = ncs > 0;
-    if (cam && opts->linear_solver != PCD_LINEAR_CHOLESKY) {
-      set_error("pcd_ba_solve: refine_intrinsics needs linear_solver = PCD_LINEAR_CHOLESKY (the PCG has no camera rows)");
+    if (cam && opts->linear_solver == PCD_LINEAR_PCG) {
+      set_error("pcd_ba_solve: refine_intrinsics needs linear_solver = PCD_LINEAR_CHOLESKY or PCD_LINEAR_PCG_CAM "
+                "(PCD_LINEAR_PCG is the PCG on the pose rows alone)");
       return PCD_ERR_UNSUPPORTED;
     }
+    pcd_ba_solve_opts lo = *opts;   // without camera rows PCD_LINEAR_PCG_CAM is PCD_LINEAR_PCG
+    if (!cam && lo.linear_solver == PCD_LINEAR_PCG_CAM) lo.linear_solver = PCD_LINEAR_PCG;
+    opts = &lo;
     hipStream_t s = nullptr;
     PCD_REFUSE_CAPTURE(s);
     PCD_TRY(schur_build(b, s));

@@ -78,4 +78,50 @@ void ba_plus_cam(uint64_t len, const int* param_cam, const int* cam_off, const i
 void ba_cam_grad_max(int ncs, const int* slot_cam, const uint8_t* active, const double* gcam, double* partial,
                      hipStream_t s);
 
+// ---- the bordered PCG (pcd_ba_schur_cam_solve_pcg*) ---------------------------------------------------
+// State and rule of a PCG solve, plain or bordered (the kernels of the plain one are ba_solve.hip's)
+struct PcgState {
+  double rho, alpha, beta, pw, q, rn2, bnorm, xr;
+  int k, done, term, xsel;
+  unsigned fallbacks; int pad;
+};
+struct PcgRule { int max_iterations, min_iterations; double q_tolerance, r_tolerance; };
+
+// sum over the workgroup (256 threads), every thread gets the result; fixed order: wavefront butterfly, then the 4 waves
+__device__ __forceinline__ double block_sum256(double v, double* lds4) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();   // lds4 may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+// strided sum of partial[i * stride] (i < n) over one workgroup
+__device__ __forceinline__ double block_sum_strided(const double* __restrict__ partial, int n, int stride, double* lds4) {
+  double a = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) a += partial[(size_t)i * stride];
+  return block_sum256(a, lds4);
+}
+
+// Vectors of the bordered solve: [6 ns pose | 12 ncs camera] in one buffer each, so that the plain kernels that only sum
+// partials (k_pcg_begin, k_pcg_step) and copy x (k_pcg_finish) serve both solves.
+struct PcgCamVec {
+  int ns, ncs;
+  const PcgState* st;
+  const double* B; const double* Scam; const double* rhs_cam;   // the handle's border, camera block and right-hand side
+  double* Minv_cam;                 // [ncs][12][12]
+  double* z; double* r; double* w;  // [6 ns + 12 ncs]
+  double* camw;                     // [12 ncs][ns]: B[i] p_i of every pose slot, entry-major
+  double* pw;                       // [ns + 12 ncs]: p_i . w_i of the pose slots, then p_e w_e of the camera coordinates
+  double* partial;                  // [nb + ncs][4], nb = max(1, div_up(ns, 256)): pose workgroups, then camera slots
+};
+// camera part of k_pcg_init: 12 x 12 block-Jacobi inverses, x = 0, r = rhs_cam, z = M^-1 r, directions 0, partial[nb + r]
+void pcg_cam_init(const PcgCamVec& v, int precond, double* x0, double* p0, double* p1, hipStream_t s);
+// one iteration's product: pose rows with the border (B crosses memory once), then the camera rows
+void pcg_cam_product(const PcgCamVec& v, const uint32_t* row_start, const uint32_t* row_blk, const uint32_t* row_col,
+                     const double* Sdiag, const double* Soff, const double* p_old, double* p_new, hipStream_t s);
+// k_pcg_update over both parts: pose workgroups, then one workgroup per camera slot
+void pcg_cam_update(const PcgCamVec& v, PcgState* st, const double* Minv, const double* rhs, const double* p,
+                    const double* x_old, double* x_new, hipStream_t s);
+
 }  // namespace pcd

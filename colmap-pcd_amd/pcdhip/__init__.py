@@ -157,8 +157,8 @@ PCG_INFO_DTYPE = np.dtype([("iterations", np.int32), ("termination", np.int32), 
 assert PCG_INFO_DTYPE.itemsize == C.sizeof(BAPcgInfo) == 48
 
 
-LINEAR_PCG, LINEAR_CHOLESKY = 0, 1
-_LINEAR = {"pcg": LINEAR_PCG, "cholesky": LINEAR_CHOLESKY}
+LINEAR_PCG, LINEAR_CHOLESKY, LINEAR_PCG_CAM = 0, 1, 2
+_LINEAR = {"pcg": LINEAR_PCG, "cholesky": LINEAR_CHOLESKY, "pcg_cam": LINEAR_PCG_CAM}
 CHOL_OK, CHOL_NOT_POSITIVE_DEFINITE = 0, 1
 
 
@@ -305,6 +305,7 @@ ABI_SYMBOLS = [
     "pcd_ba_schur_solve_cholesky_device", "pcd_ba_schur_solve_cholesky",
     "pcd_ba_camera_slots", "pcd_ba_schur_cam_device", "pcd_ba_schur_cam", "pcd_ba_schur_cam_solve_cholesky_device",
     "pcd_ba_schur_cam_back_substitute_device", "pcd_ba_plus_cam_device", "pcd_ba_get_camera_parameters",
+    "pcd_ba_schur_cam_solve_pcg_device", "pcd_ba_schur_cam_solve_pcg",
     "pcd_normals_options_default", "pcd_cloud_estimate_normals_device", "pcd_cloud_estimate_normals",
     "pcd_voxel_options_default", "pcd_cloud_voxel_downsample", "pcd_cloud_voxel_downsample_device",
     "pcd_ba_set_lidar_device", "pcd_ba_get_lidar", "pcd_ba_lidar_device", "pcd_ba_assoc_opts_default",
@@ -429,6 +430,10 @@ def lib():
         L.pcd_ba_schur_cam_back_substitute_device.argtypes = [C.c_void_p] * 5
         L.pcd_ba_plus_cam_device.argtypes = [C.c_void_p] * 7
         L.pcd_ba_get_camera_parameters.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "pcd_ba_schur_cam_solve_pcg_device"):
+        L.pcd_ba_schur_cam_solve_pcg_device.argtypes = [C.c_void_p, C.POINTER(BAPcgOpts), C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]
+        L.pcd_ba_schur_cam_solve_pcg.argtypes = [C.c_void_p, C.POINTER(BAPcgOpts), C.c_void_p, C.POINTER(BAPcgInfo)]
     if hasattr(L, "pcd_ba_set_lidar_device"):
         L.pcd_ba_set_lidar_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
@@ -1620,6 +1625,33 @@ class BA:
         return delta, {k: (float(i[k]) if CHOL_INFO_DTYPE[k] == np.float64 else int(i[k]))
                        for k in CHOL_INFO_DTYPE.names if k != "pad"}
 
+    def schur_cam_solve_pcg(self, delta=None, **opts):
+        """bordered PCG on the system of the last schur_cam() call from the handle's own blocks (keep S_diag / S_off / rhs
+        out of want before it).  opts: pcg_opts() arguments.  Returns (delta [n] torch device tensor = dpose [ns][6] then
+        dcam [ncs][12], info dict as schur_solve_pcg).  Without camera slots it is schur_solve_pcg."""
+        torch, dev, stream = self._torch()
+        ns, ncs = self._cam_dims()
+        n = 6 * ns + CAM_JAC_STRIDE * ncs
+        if delta is None:
+            delta = torch.empty(n, dtype=torch.float64, device=dev)
+        d_info = torch.zeros(C.sizeof(BAPcgInfo), dtype=torch.uint8, device=dev)
+        pad = torch.zeros(1, dtype=torch.float64, device=dev)   # n = 0: an empty tensor's pointer is null
+        o = pcg_opts(**opts)
+        _check(lib().pcd_ba_schur_cam_solve_pcg_device(self._h, C.byref(o), _ptr(delta if n else pad), _ptr(d_info),
+                                                       C.c_void_p(stream)))
+        i = d_info.cpu().numpy().view(PCG_INFO_DTYPE)[0]
+        return delta, {k: (float(i[k]) if PCG_INFO_DTYPE[k] == np.float64 else int(i[k]))
+                       for k in PCG_INFO_DTYPE.names if k != "pad"}
+
+    def schur_cam_solve_pcg_host(self, **opts):
+        """pcd_ba_schur_cam_solve_pcg: the same solve with host outputs (numpy delta [n], info dict)"""
+        ns, ncs = self._cam_dims()
+        delta = np.zeros(max(1, 6 * ns + CAM_JAC_STRIDE * ncs))
+        info = BAPcgInfo()
+        o = pcg_opts(**opts)
+        _check(lib().pcd_ba_schur_cam_solve_pcg(self._h, C.byref(o), _vp(delta), C.byref(info)))
+        return delta[:6 * ns + CAM_JAC_STRIDE * ncs], _pcg_info(info)
+
     def back_substitute_cam(self, delta, dpoint=None, model_decrease=True):
         """point steps of the last schur_cam() call for delta [n] (dpose then dcam; torch, device): returns
         (dpoint [P][3], model decrease [1] or None)"""
@@ -1834,8 +1866,8 @@ def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max
     exact step of the library's blocked Cholesky instead of the PCG's inexact one (linear_iterations is then 0 and
     linear_termination a CHOL_* status).  Returns (summary dict, list of one dict per iteration); the handle holds
     the accepted parameters (BA.get_parameters()).  refine_intrinsics=True solves for the refined camera parameters
-    too (camera rows in the reduced system; the direct solver only) and leaves the accepted ones in the handle
-    (BA.get_camera_parameters()); without it a handle with camera_refine is refused."""
+    too (camera rows in the reduced system; linear_solver="cholesky" or "pcg_cam", the bordered PCG) and leaves the
+    accepted ones in the handle (BA.get_camera_parameters()); without it a handle with camera_refine is refused."""
     L = lib()
     o = BASolveOpts()
     L.pcd_ba_solve_opts_default(C.byref(o))

@@ -77,8 +77,8 @@ struct BundleAdjustmentOptions {  // optim/bundle_adjustment.h:52-91 (this fork'
   double loss_function_scale = 1.0;
   bool refine_focal_length = false, refine_principal_point = false, refine_extra_params = false;
   bool refine_extrinsics = true;
-  // Refined intrinsics on the device route (pcd_ba_solve with refine_intrinsics: camera rows in the reduced system, the
-  // direct solver whatever linear_solver_type says).  false: BundleAdjusterHip::Solve returns false when a refine_* switch
+  // Refined intrinsics on the device route (pcd_ba_solve with refine_intrinsics: camera rows in the reduced system, solved
+  // as refined_linear_solver_type below says, whatever linear_solver_type says).  false: BundleAdjusterHip::Solve returns false when a refine_* switch
   // leaves a camera parameter variable, and the caller stays on the Ceres route.
   bool refine_intrinsics_on_device = false;
   // ceres::Solver::Options members BundleAdjusterHip::Solve reads (optim/bundle_adjustment.h:96-103)
@@ -93,6 +93,11 @@ struct BundleAdjustmentOptions {  // optim/bundle_adjustment.h:52-91 (this fork'
   enum class LinearSolverType { ITERATIVE, DIRECT, AUTO };
   LinearSolverType linear_solver_type = LinearSolverType::ITERATIVE;
   static constexpr size_t kMaxNumImagesDirectSolver = 1000;
+  // Linear solver when refine_intrinsics_on_device leaves a camera parameter variable (it applies to nothing else).
+  // DIRECT: the blocked Cholesky of the bordered system (PCD_LINEAR_CHOLESKY).  ITERATIVE: the bordered PCG
+  // (PCD_LINEAR_PCG_CAM), the reference's ITERATIVE_SCHUR + SCHUR_JACOBI with the intrinsics as parameter blocks.  AUTO:
+  // by kMaxNumImagesDirectSolver, as linear_solver_type.
+  LinearSolverType refined_linear_solver_type = LinearSolverType::DIRECT;
 };
 
 class BundleAdjustmentConfig {  // optim/bundle_adjustment.h:118-200, .cc:76-233
@@ -220,7 +225,8 @@ class BundleAdjusterHip {
 
   // ---- solve (HIP): the device route end to end, after SetUp() ---------------------------------
   // Create, pcd_ba_solve (LM with the linear solver options_.linear_solver_type selects, the block-sparse PCG on the
-  // reduced camera system unless told otherwise), then the accepted poses and
+  // reduced camera system unless told otherwise; with refined intrinsics the one options_.refined_linear_solver_type
+  // selects, the direct solve of the bordered system unless told otherwise), then the accepted poses and
   // points go back into the Reconstruction through image_ids_ / point_ids_; constant poses and points are not
   // written at all.  false when there are no residuals (as the reference, :489-491), when intrinsics are refined and
   // options_.refine_intrinsics_on_device is off (the caller stays on the Ceres route) or when a call fails
@@ -242,7 +248,8 @@ class BundleAdjusterHip {
     o.function_tolerance = options_.function_tolerance;
     o.gradient_tolerance = options_.gradient_tolerance;
     o.linear.max_iterations = options_.max_linear_solver_iterations;
-    o.linear_solver = (refined || UsesDirectSolver()) ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG;
+    if (refined) o.linear_solver = RefinedUsesDirectSolver() ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG_CAM;
+    else o.linear_solver = UsesDirectSolver() ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG;
     o.refine_intrinsics = refined ? 1 : 0;
     if (pcd_ba_solve(ba_, &o, &summary_, nullptr) != PCD_OK) return false;
     if (pcd_ba_get_parameters(ba_, poses_.data(), points_.data()) != PCD_OK) return false;
@@ -578,6 +585,13 @@ class BundleAdjusterHip {
     using T = BundleAdjustmentOptions::LinearSolverType;
     return options_.linear_solver_type == T::DIRECT ||
            (options_.linear_solver_type == T::AUTO &&
+            config_.NumImages() <= BundleAdjustmentOptions::kMaxNumImagesDirectSolver);
+  }
+  // the same choice for a solve with refined intrinsics (options_.refined_linear_solver_type)
+  bool RefinedUsesDirectSolver() const {
+    using T = BundleAdjustmentOptions::LinearSolverType;
+    return options_.refined_linear_solver_type == T::DIRECT ||
+           (options_.refined_linear_solver_type == T::AUTO &&
             config_.NumImages() <= BundleAdjustmentOptions::kMaxNumImagesDirectSolver);
   }
 

@@ -828,7 +828,7 @@ pcd_status pcd_ba_schur_solve_pcg(pcd_ba* ba, const pcd_ba_pcg_opts* opts, doubl
  * calls; d_dpose may be NULL only when ns = 0.  The host form with S given stages the n^2 doubles of S on the device for
  * the call and frees them again (a hipMalloc / hipFree pair per call, 288 MB at n = 6000): a caller in a loop wants the
  * _device form, or the handle's own blocks, which need no staging. */
-typedef enum { PCD_LINEAR_PCG = 0, PCD_LINEAR_CHOLESKY = 1 } pcd_ba_linear_solver;
+typedef enum { PCD_LINEAR_PCG = 0, PCD_LINEAR_CHOLESKY = 1, PCD_LINEAR_PCG_CAM = 2 /* the bordered PCG, below */ } pcd_ba_linear_solver;
 typedef enum { PCD_CHOL_OK = 0, PCD_CHOL_NOT_POSITIVE_DEFINITE = 1 } pcd_ba_chol_status;
 typedef struct {
   int32_t status;          /* pcd_ba_chol_status */
@@ -908,7 +908,8 @@ pcd_status pcd_ba_solve(pcd_ba* ba, const pcd_ba_solve_opts* opts, pcd_ba_solve_
  *   dX_p = -V_p^-1 (g_p + sum_a W_a^T dpose[slot(a)] + sum_r Wc_p[r]^T dcam[r])
  * and the model decrease gains 1/2 sum over the active camera coordinates of (-dcam g_cam + D dcam^2).  An observation
  * in a constant-pose image has no slot but still couples its camera to its point.  The pose part (S_diag, S_off, rhs)
- * is that of pcd_ba_schur_device, bit for bit.  The direct solve only: the PCG knows no border.  Camera slots couple
+ * is that of pcd_ba_schur_device, bit for bit.  Two solvers read the bordered system: the direct solve and the
+ * bordered PCG (pcd_ba_schur_cam_solve_pcg*).  Camera slots couple
  * every image of a camera, so they are kept dense and few: more than PCD_BA_MAX_CAMERA_SLOTS (for example one refined
  * camera per image) -> PCD_ERR_UNSUPPORTED from every call below and from pcd_ba_solve with refine_intrinsics, before
  * anything is allocated or launched; the handle stays usable.  The other guards (NULL, no device, capturing stream,
@@ -937,6 +938,24 @@ pcd_status pcd_ba_schur_cam(pcd_ba* ba, const pcd_ba_schur_opts* opts, const pcd
  * d_delta [n] = dpose [ns][6], then dcam [ncs][12] (0 on inactive coordinates; all 0 when the factorisation failed). */
 pcd_status pcd_ba_schur_cam_solve_cholesky_device(pcd_ba* ba, double* d_delta, pcd_ba_chol_info* d_info /*may be NULL*/,
                                                   void* stream);
+/* Bordered PCG: preconditioned conjugate gradients on the bordered system of the last pcd_ba_schur_cam*, from the
+ * handle's own blocks (INVALID as for the direct solve above).  With x = [dpose | dcam], b = [rhs | rhs_cam]:
+ *   w_pose[i] = sum over the row list of i of (S block) p_j + sum_r B[i][r]^T p_cam[r]
+ *   w_cam[r]  = sum_i B[i][r] p_pose[i] + sum_r' S_cam[r][r'] p_cam[r']
+ * Recurrence, pcd_ba_pcg_opts, pcd_ba_pcg_info, terminations, x_0 = 0, the Q / r / max-iteration order, BREAKDOWN and
+ * ZERO_RHS are exactly those of pcd_ba_schur_solve_pcg*, with every dot product and norm over the whole vector, poses
+ * and cameras (rhs_norm includes rhs_cam); the done flag stays on the device and the host looks at it in batches of 8,
+ * 16 and 32 iterations.  PCD_PRECOND_SCHUR_JACOBI: the 6 x 6 pose block inverses and the inverse of every camera slot's
+ * 12 x 12 diagonal block S_cam[r][r] through its Cholesky factor (Ceres' SCHUR_JACOBI with the intrinsics as one more
+ * parameter block per camera); inactive coordinates stay identity rows / columns of that inverse, exactly; a block with
+ * a non-positive or non-finite pivot falls back to the identity and is counted in precond_fallbacks.  fp64, no atomics,
+ * every sum in an order fixed by the structure: bitwise repeatable.  Inactive camera coordinates and constant-tvec
+ * coordinates of x are exactly 0.  B crosses memory once per iteration; an iteration is four launches.  d_delta [n] has
+ * the layout of pcd_ba_schur_cam_solve_cholesky_device.  All scratch belongs to the handle (pcd_ba_schur_stats). */
+pcd_status pcd_ba_schur_cam_solve_pcg_device(pcd_ba* ba, const pcd_ba_pcg_opts* opts, double* d_delta /*[n]*/,
+                                             pcd_ba_pcg_info* d_info /*device, may be NULL*/, void* stream);
+pcd_status pcd_ba_schur_cam_solve_pcg(pcd_ba* ba, const pcd_ba_pcg_opts* opts, double* delta /*host*/,
+                                      pcd_ba_pcg_info* info);
 /* point steps and model decrease for d_delta [n], from the state of the last pcd_ba_schur_cam* */
 pcd_status pcd_ba_schur_cam_back_substitute_device(pcd_ba* ba, const double* d_delta, double* d_dpoint /*[P][3]*/,
                                                    double* d_model_decrease /*[1] or NULL*/, void* stream);
@@ -951,8 +970,11 @@ pcd_status pcd_ba_get_camera_parameters(pcd_ba* ba, double* cam_params /*[cam_pa
  * trust-region rule is unchanged, the gradient max-norm includes g_cam over the active coordinates, the accepted camera
  * parameters are kept beside the accepted poses and points and restored on a rejected step.  On return the handle
  * holds the accepted camera parameters, on the device and in the host mirror pcd_ba_project_lidar_device reads.
+ * linear_solver = PCD_LINEAR_PCG_CAM runs the bordered PCG instead (`linear` as for PCD_LINEAR_PCG; BREAKDOWN counts as a
+ * rejected step; one small device-to-host copy per iteration and one more per extra PCG batch); without camera slots,
+ * or with refine_intrinsics = 0 on an unrefined handle, it is PCD_LINEAR_PCG.
  * refine_intrinsics = 1 with PCD_LINEAR_PCG on a handle that has camera slots -> PCD_ERR_UNSUPPORTED (use
- * PCD_LINEAR_CHOLESKY).  On a handle without camera slots the flag changes nothing. */
+ * PCD_LINEAR_CHOLESKY or PCD_LINEAR_PCG_CAM).  On a handle without camera slots the flag changes nothing. */
 
 /* ------------------------------------------------------------------------
  * Re-association of a handle's LiDAR terms on the device        
