@@ -42,6 +42,16 @@ constexpr int kClipNk = 7;      // x boundaries of a region row: cells 2 bx - 2 
 constexpr int kClipRows = 9;    // quad rows of the region: (by - 1 .. by + 1) x (bz - 1 .. bz + 1)
 constexpr int kATile = 128;     // points stage A stages at most (2 DMA instructions); the rest of its range joins stage B
 constexpr int kClipRanges = 10; // 8 rows + the left and right parts of the row stage A took its records from
+// The work schedule inside a block class (k_nn_brick_clip below): the first kSchedStaticPct % of a wavefront's strided
+// rounds are static, the rest of the class's items is handed out in chunks of kSchedChunk from a cursor.
+#ifndef PCD_SCHED_STATIC_PCT
+#define PCD_SCHED_STATIC_PCT 50
+#endif
+#ifndef PCD_SCHED_CHUNK
+#define PCD_SCHED_CHUNK 2
+#endif
+constexpr uint32_t kSchedStaticPct = PCD_SCHED_STATIC_PCT, kSchedChunk = PCD_SCHED_CHUNK;
+static_assert(kSchedStaticPct < 100 && kSchedChunk >= 1 && (kSchedChunk & (kSchedChunk - 1)) == 0, "a share below 1, a power of two");
 #ifdef PCD_ABLATE   // timing-only ablations (tools/nn_ablate.py; results are wrong): brick_kernel.h
 constexpr int kAblateClipMath = 0x10000, kAblateBound = 0x20000, kAblateStageA = 0x40000, kAblateSelect = 0x80000;
 #else
@@ -146,7 +156,8 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
                                                           const uint64_t* __restrict__ ksorted,
                                                           const uint4* __restrict__ items, NnCounters* __restrict__ ctr,
                                                           uint64_t* __restrict__ keys, uint32_t* __restrict__ fb_list,
-                                                          uint32_t* __restrict__ fb_count, int flags) {
+                                                          uint32_t* __restrict__ fb_count, int flags,
+                                                          unsigned long long* __restrict__ wave_rec) {
   constexpr int G = 8;
   constexpr int NK = kClipNk, NC = kClipNk - 1;   // x boundaries / cells of a region row
   const int collect_stats = flags & 1;
@@ -155,6 +166,10 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
   __shared__ __attribute__((aligned(16))) float4 s_a[4][kATile];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform for the compiler too: LDS tile addresses and M0 values stay in SGPRs
+  // statistics passes with bit 4: the wavefront's record {start, end, items} (wall_clock64 ticks) for
+  // tools/brick_tail_probe.py; a scalar address, so that the loop below does not carry it in VGPRs
+  unsigned long long* const rec = wave_rec + 3u * (blockIdx.x * 4u + (uint32_t)wave);
+  if ((flags & 4) && lane == 0) rec[0] = wall_clock64();
   const uint32_t nitems = ctr->nitems;
   const uint32_t nwaves = gridDim.x * 4;
   unsigned long long st_staged = 0, st_pairs = 0, st_groups = 0;
@@ -174,18 +189,77 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
   // block classes walks its own contiguous eighth of the item list (items are in brick order, x fastest):
   // bricks that are neighbours in space -- and share most of their staged rows -- meet in one L2.
   // (speed only: any mapping gives the same results.)
-  uint32_t item, item_end, stride;
-  if ((gridDim.x & 7u) == 0) {
-    const uint32_t cls = blockIdx.x & 7u, per = (nitems + 7u) / 8u;
-    stride = (gridDim.x >> 3) * 4;
-    item = cls * per + (blockIdx.x >> 3) * 4 + wave;
-    item_end = min(nitems, (cls + 1) * per);
-  } else {
-    stride = nwaves;
-    item = blockIdx.x * 4 + wave;
-    item_end = nitems;
+  //
+  // Inside a class [c0, item_end) the S wavefronts of the class take items in two phases.  Static: wavefront w takes
+  // c0 + w, c0 + w + S, ... for R_s = floor(kSchedStaticPct % of ceil(per / S)) rounds, per = the items of a full class
+  // (the last class may hold up to 7 fewer, and then fewer static items or no dynamic ones).  Dynamic: the rest,
+  // [stat_end, item_end) with stat_end = min(c0 + R_s S, item_end), goes out in chunks of kSchedChunk consecutive
+  // items; a wavefront that runs out takes chunk number atomicAdd(cursor of the class, 1).  The items cost between 1
+  // and ~12 tiles x 1..8 queries: with the static schedule alone the kernel waits for the wavefront that drew the
+  // dearest ~57 items.  flags & 8: static only (stat_end = item_end; the A/B reference).
+  // The cursors count from 0 in NnCounters, cleared with the block (nn.hip take_counters); they run past the last
+  // chunk by at most one grab per wavefront.
+  // The loop below is pipelined two items deep (record of item k + 2, metadata of item k + 1), so a wavefront knows
+  // its next two indices i1, i2; a grab is issued at the top of the iteration BEFORE the one that needs its result
+  // (`pend`, consumed after that iteration's s_waitcnt vmcnt(0)): its latency hides under an item, and it is older
+  // than every DMA the counted waits of the tile loop count.
+  constexpr uint32_t kNone = 0xFFFFFFFFu;
+  uint32_t i0, item_end, stride, stat_end;
+  unsigned int* cursor;
+  {
+    uint32_t c0, full;   // full: items of a full class
+    if ((gridDim.x & 7u) == 0) {
+      const uint32_t cls = blockIdx.x & 7u, per = (nitems + 7u) / 8u;
+      stride = (gridDim.x >> 3) * 4;
+      c0 = min(nitems, cls * per);
+      i0 = c0 + (blockIdx.x >> 3) * 4 + wave;
+      item_end = min(nitems, (cls + 1) * per);
+      cursor = &ctr->sched_cursor[kSchedCursorWords * cls];
+      full = per;
+    } else {
+      stride = nwaves;
+      c0 = 0;
+      i0 = blockIdx.x * 4 + wave;
+      item_end = nitems;
+      cursor = &ctr->sched_cursor[0];
+      full = nitems;
+    }
+    const uint32_t rounds = (full + stride - 1) / stride;
+    stat_end = (flags & 8) ? item_end : min(c0 + (rounds * kSchedStaticPct / 100u) * stride, item_end);
   }
-  if (item >= item_end) return;
+  // one returning atomic from one lane (the other lanes hold 0); the value is read with PCD_UNI once it has landed
+  // The address is the cursor + an offset of 0 in a VGPR the compiler cannot see through: for an address it knows to
+  // be wave-uniform it rewrites the atomic into "one lane adds the number of active lanes, every lane adds its rank",
+  // which needs the result on the spot -- an s_waitcnt vmcnt(0) right behind the atomic, its whole latency exposed in
+  // every item.  (An offset, not the pointer: a laundered pointer loses its address space and becomes a FLAT atomic,
+  // which counts in lgkmcnt as well and would be waited for by the LDS reads.)
+  auto grab = [&]() -> uint32_t {
+    uint32_t v = 0, off = 0;
+    asm volatile("" : "+v"(off));
+    if (lane == 0) v = atomicAdd(cursor + off, 1u);
+    return v;
+  };
+  auto chunk_first = [&](uint32_t v) -> uint32_t { return stat_end + kSchedChunk * PCD_UNI(v); };
+  // does the item after item i of this wavefront come out of a new chunk?  (i >= item_end: there is no item i)
+  auto wants_chunk = [&](uint32_t i) -> bool {
+    if (i >= item_end) return false;
+    if (i < stat_end) return i + stride >= stat_end && stat_end < item_end;
+    return ((i - stat_end) & (kSchedChunk - 1)) == kSchedChunk - 1;
+  };
+  // the item after item i; `chunk`: first item of the chunk grabbed for it, where wants_chunk(i).  >= item_end: none
+  auto successor = [&](uint32_t i, uint32_t chunk) -> uint32_t {
+    if (i >= item_end) return kNone;
+    if (i < stat_end) return i + stride < stat_end ? i + stride : stat_end < item_end ? chunk : kNone;
+    return ((i - stat_end) & (kSchedChunk - 1)) != kSchedChunk - 1 ? i + 1 : chunk;
+  };
+  if (i0 >= stat_end) i0 = stat_end < item_end ? chunk_first(grab()) : kNone;   // (no static round: few items)
+  if (i0 >= item_end) {
+    if ((flags & 4) && lane == 0) { rec[1] = wall_clock64(); rec[2] = 0; }
+    return;
+  }
+  uint32_t i1 = successor(i0, wants_chunk(i0) ? chunk_first(grab()) : kNone);
+  uint32_t pend = 0;
+  if (wants_chunk(i1)) pend = grab();
   const char* __restrict__ src_bytes = reinterpret_cast<const char*>(sorted);
   float4* const bufA = s_a[wave];
 #define PCD_RL(v, r) ((uint32_t)__builtin_amdgcn_readlane((int)(v), (int)(r)))
@@ -229,18 +303,21 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
     return ARange{sA, nA | (e << 8)};
   };
 
-  uint4 it0 = items[PCD_UNI(item)];   // through uniform (scalar) indices: brick_kernel.h PCD_UNI
+  uint4 it0 = items[PCD_UNI(i0)];   // through uniform (scalar) indices: brick_kernel.h PCD_UNI
   ClipMeta m0 = clip_load_meta(g, it0, qsorted, ksorted, cell_start, lpos);
-  uint4 it1 = items[PCD_UNI(min(item + stride, item_end - 1))];
+  uint4 it1 = items[PCD_UNI(min(i1, item_end - 1))];
   ARange a0 = issue_a(m0);
 
-  for (; item < item_end; item += stride) {
-    // stage A of this item (issued while the previous item was compared) has landed; nothing else is in flight
+  while (i0 < item_end) {
+    // stage A of this item (issued while the previous item was compared) has landed, and so has the chunk grabbed
+    // during the previous item; nothing else is in flight
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
+    const uint32_t i2 = successor(i1, chunk_first(pend));
+    if (wants_chunk(i2)) pend = grab();   // for the item after i2: needed at the top of the next iteration
     // ---- prefetch: metadata of the next item, item record of the one after (clamped to the last item) ----
     const ClipMeta m1 = clip_load_meta(g, it1, qsorted, ksorted, cell_start, lpos);
-    const uint4 it2 = items[PCD_UNI(min(item + 2 * stride, item_end - 1))];
+    const uint4 it2 = items[PCD_UNI(min(i2, item_end - 1))];
 
     const uint32_t cnt = (uint32_t)item_count(it0);
     // The item's queries as wave-uniform values in VGPRs (an SGPR operand halves the VALU rate: brick_kernel.h PCD_CMP_PAIR).  Through
@@ -499,6 +576,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
       st_staged += nA + T; st_pairs += (unsigned long long)slots * cnt; st_groups += 1;
     }
     it0 = it1; it1 = it2; m0 = m1; a0 = a1;
+    i0 = i1; i1 = i2;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last (redundant) stage-A prefetch must not outlive the wavefront's LDS
   if (lane < (int)fb_left) fb_list[fb_base + lane] = 0xFFFFFFFFu;   // rest of the last chunk
@@ -506,6 +584,7 @@ __global__ __launch_bounds__(256, 4) void k_nn_brick_clip(GridParams g, const fl
     atomicAdd(&ctr->staged_points, st_staged);
     atomicAdd(&ctr->pair_evals, st_pairs);
     atomicAdd(&ctr->brick_groups, st_groups);
+    if (flags & 4) { rec[1] = wall_clock64(); rec[2] = st_groups; }
   }
 #undef PCD_BND
 #undef PCD_RL

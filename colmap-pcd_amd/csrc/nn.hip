@@ -518,6 +518,7 @@ __global__ __launch_bounds__(1024) void k_bk_slots(PrepArgs pa, uint32_t Q, uint
   // LDS histogram as one row of the [ranges][ncoarse] matrix
   __shared__ uint32_t s_h[kBkMaxCoarse], s_w[16], s_base;
   // the counters of the NEXT grid-path call: every user of that block (the call before this one) has finished
+  static_assert(sizeof(NnCounters) / 4 <= 1024, "one thread per word of the block");
   if (blockIdx.x == 0 && threadIdx.x < sizeof(NnCounters) / 4) reinterpret_cast<uint32_t*>(ctr_next)[threadIdx.x] = 0;
   for (uint32_t c = threadIdx.x; c < ncoarse; c += 1024) s_h[c] = 0;
   __syncthreads();
@@ -1029,6 +1030,9 @@ constexpr int g_brick_blocks_per_cu = PCD_BRICK_MINWAVES;
 // switched off (A/B timing and tests: it then stages the whole region; results identical)
 static std::atomic<int> g_nn_kernel{0};
 static std::atomic<int> g_bk_sort{0};   // 1: force the radix-sort bookkeeping (A/B timing, tests)
+// how the brick kernel's items are spread over its wavefronts: 0 = static rounds, then chunks from a cursor per block
+// class (brick_clip_kernel.h), 1 = the static strided schedule alone (A/B timing and tests; results identical)
+static std::atomic<int> g_nn_schedule{0};
 
 // slot table of the cloud (built on first use)
 static pcd_status brick_slots(pcd_cloud* c, QueryScratch* sc, const BrickParams& b, hipStream_t s) {
@@ -1151,6 +1155,7 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
   const uint64_t* carried_keys = call.prep != kPrepPlain ? d_keys : nullptr;   // refine, gate-bounded: the keys the queries come with matter
   const GridParams& g = c->grid;
   const int nn_kernel = g_nn_kernel.load(), bk_sort = g_bk_sort.load(), collect_stats = g_collect_stats.load();
+  const int nn_schedule = g_nn_schedule.load();
   const BrickParams b = make_bricks(g);
   PCD_TRY(sc->qsorted.reserve(Q));
   PCD_TRY(sc->ksorted.reserve(Q));
@@ -1218,9 +1223,17 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
   {
     ScopedKernelTimer t("nn_brick", s);
     const unsigned blocks = (unsigned)std::min<uint64_t>(div_up(div_up(Q, kGroup), 4) + 1, 256 * (uint64_t)g_brick_blocks_per_cu);
-    const int fl = (collect_stats & ~2) | (nn_kernel == 1 ? 2 : 0);
+    // flags: 1 statistics, 2 clip off, 4 per-wavefront records (statistics passes only), 8 static schedule
+    int fl = (collect_stats & ~(2 | 4 | 8)) | (nn_kernel == 1 ? 2 : 0) | (nn_schedule == 1 ? 8 : 0);
+    if ((collect_stats & 5) == 5) {
+      PCD_TRY(sc->wave_rec.reserve(3 * (size_t)blocks * 4));
+      sc->wave_rec_n = blocks * 4;
+      fl |= 4;
+    } else {
+      sc->wave_rec_n = 0;
+    }
     hipLaunchKernelGGL(k_nn_brick_clip, dim3(blocks), dim3(256), 0, s, g, c->sorted.p, c->cell_start.p, sc->qsorted.p,
-                       sc->ksorted.p, sc->items.p, ctr, d_keys, sc->fb_list.p, &ctr->fb_count, fl);
+                       sc->ksorted.p, sc->items.p, ctr, d_keys, sc->fb_list.p, &ctr->fb_count, fl, sc->wave_rec.p);
   }
   {
     ScopedKernelTimer t("nn_fallback", s);
@@ -1256,6 +1269,7 @@ static pcd_status nn_device(pcd_cloud* c, const NnCall& call, uint64_t Q, int al
   QueryScratch* sc = scratch_of(c);
   if (Q == 0) return PCD_OK;
   PCD_REQUIRE(Q < 0xFFFFFFF0ull, "more than 2^32 queries in one call");
+  sc->wave_rec_n = 0;   // (the grid path of a statistics pass sets it)
   NnPath path;
   PCD_TRY(choose_path(c->m == 0, algo, Q, call.prep, &path));
   const int collect_stats = g_collect_stats.load();
@@ -1395,6 +1409,41 @@ pcd_status pcd_nn_set_search(int kernel) {
   return PCD_OK;
 }
 
+/* tuning hook: the brick kernel's work schedule (g_nn_schedule above).  Negative: leave it as it is. */
+pcd_status pcd_nn_set_schedule(int schedule) {
+  if (schedule < 0) return PCD_OK;
+  PCD_REQUIRE(schedule <= 1, "schedule must be 0 (static rounds + dynamic chunks) or 1 (static)");
+  g_nn_schedule = schedule;
+  return PCD_OK;
+}
+
+/* tools / tests: the compile-time constants of schedule 0 -- static share of the rounds in percent, items per chunk */
+pcd_status pcd_nn_schedule_params(int* static_pct, int* chunk) {
+  PCD_REQUIRE(static_pct && chunk, "null pointer");
+  *static_pct = (int)kSchedStaticPct;
+  *chunk = (int)kSchedChunk;
+  return PCD_OK;
+}
+
+/* tools / tests: the records of the last grid-path call of a statistics pass with bit 4 -- {start, end, items} per
+   wavefront of the brick kernel, wall_clock64 ticks -- and the call's number of work items.  Fills up to cap_waves
+   records; *nwaves = wavefronts launched (0: the last call kept no records).  Syncs. */
+pcd_status pcd_nn_last_wave_records(pcd_cloud* c, uint64_t* records, uint64_t cap_waves, uint64_t* nwaves, uint64_t* nitems) {
+  PCD_REQUIRE(c && nwaves && nitems, "null pointer");
+  *nwaves = *nitems = 0;
+  if (!c->scratch || !c->scratch->counters.p) return PCD_OK;
+  QueryScratch* sc = c->scratch;
+  PCD_HIP_TRY(hipSetDevice(c->device));
+  PCD_HIP_TRY(hipDeviceSynchronize());
+  NnCounters h;
+  PCD_HIP_TRY(hipMemcpy(&h, sc->counters.p + sc->ctr_cur, sizeof h, hipMemcpyDeviceToHost));
+  *nitems = h.nitems;
+  *nwaves = sc->wave_rec_n;
+  const uint64_t n = std::min<uint64_t>(cap_waves, sc->wave_rec_n);
+  if (n && records) PCD_HIP_TRY(hipMemcpy(records, sc->wave_rec.p, n * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PCD_OK;
+}
+
 pcd_status pcd_nn_set_bookkeeping(int radix_sort) {
   g_bk_sort = radix_sort ? 1 : 0;
   return PCD_OK;
@@ -1411,7 +1460,7 @@ pcd_status pcd_nn_set_tuning(int brick_cells, int halo_cells, int collect_stats)
 #ifdef PCD_ABLATE
   g_collect_stats = collect_stats;
 #else
-  g_collect_stats = collect_stats & 1;   // the ablation bits exist only in -DPCD_ABLATE builds
+  g_collect_stats = collect_stats & 5;   // (4: per-wavefront records of the brick kernel) the ablation bits exist only in -DPCD_ABLATE builds
 #endif
   return PCD_OK;
 }

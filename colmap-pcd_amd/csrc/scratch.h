@@ -1,10 +1,20 @@
 // scratch.h -- grow-only per-cloud device scratch shared by nn.hip and assoc.hip
 #pragma once
+#include <cstddef>
+
 #include "cloud.h"
 
 namespace pcd {
 
-struct NnCounters {
+// k_nn_brick_clip's cursors (brick_clip_kernel.h): one per block class = per XCD, each on a 128-byte line of its own --
+// eight cursors on one line had the eight L2s pass that line around with every grab.  The array and the struct are
+// aligned to the line, so that in both blocks no cursor shares its line with nitems / fb_count, which every XCD touches
+#ifndef PCD_SCHED_CURSOR_WORDS
+#define PCD_SCHED_CURSOR_WORDS 32
+#endif
+constexpr int kSchedCursorWords = PCD_SCHED_CURSOR_WORDS;
+
+struct alignas(128) NnCounters {
   unsigned long long brick_groups, staged_points, fallback_queries, fallback_points, pair_evals;
   unsigned int nitems, fb_count;
   unsigned int pad[2];   // pad[0] = length of the squeezed fallback list
@@ -12,7 +22,10 @@ struct NnCounters {
   unsigned int pad2[3];
   unsigned int fb_max_steps, fb_max_leaves;   // statistics passes: longest walk of k_nn_fallback (steps, leaf scans)
   unsigned long long fb_steps, fb_leaves;
+  alignas(128) unsigned int sched_cursor[8 * kSchedCursorWords];   // [kSchedCursorWords * class]: chunks handed out of the class's dynamic range
 };
+
+static_assert(sizeof(NnCounters) % 128 == 0 && offsetof(NnCounters, sched_cursor) % 128 == 0, "cursors on line boundaries in both blocks");
 
 struct QueryScratch {
   DevBuf<float4> qf4;          // (float)query, w = 1 valid / 0 not finite
@@ -34,6 +47,10 @@ struct QueryScratch {
   DevBuf<NnCounters> counters;   // two blocks, used alternately by the grid-path calls (nn.hip counters_for)
   int ctr_cur = 0;               // the block of the last call
   bool ctr_next_clean = false;   // the other block is zero (or will be when the stream gets there)
+  // statistics passes that ask for it (pcd_nn_set_tuning bit 4): {start, end, items} of every wavefront of the last
+  // k_nn_brick_clip launch, wall_clock64 ticks; reserved in such a pass only
+  DevBuf<unsigned long long> wave_rec;
+  uint32_t wave_rec_n = 0;
   DevBuf<char> tmp;
   DevBuf<double> d_q;          // staging of host queries
   DevBuf<uint32_t> d_idx; DevBuf<float> d_sq; DevBuf<uint8_t> d_found;

@@ -374,6 +374,9 @@ def lib():
     L.pcd_search_range_schedule.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p]
     L.pcd_profile_get.argtypes = [C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]
     L.pcd_nn_last_stats.argtypes = [C.c_void_p, C.POINTER(NNStats)]
+    if hasattr(L, "pcd_nn_last_wave_records"):   # (a library of an older tree, loaded through PCDHIP_LIB for A/B runs)
+        L.pcd_nn_last_wave_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_uint64)]
     L.pcd_normals_options_default.argtypes = [C.POINTER(NormalsOptions)]
     L.pcd_normals_options_default.restype = None
     L.pcd_cloud_estimate_normals_device.argtypes = [C.c_void_p, C.POINTER(NormalsOptions), C.c_void_p, C.c_void_p,
@@ -683,6 +686,18 @@ class Cloud:
         s = NNStats()
         _check(lib().pcd_nn_last_stats(self._h, C.byref(s)))
         return {n: getattr(s, n) for n, _ in NNStats._fields_}
+
+    def last_wave_records(self):
+        """(records, nitems) of the last grid-path call: nitems = its work items; records = uint64 [waves, 3] of
+        {start, end, items} per wavefront of the brick kernel (wall-clock ticks), kept only by a statistics pass with
+        set_nn_tuning(collect_stats=5), else empty"""
+        L = lib()
+        nw, ni = C.c_uint64(0), C.c_uint64(0)
+        _check(L.pcd_nn_last_wave_records(self._h, None, 0, C.byref(nw), C.byref(ni)))
+        rec = np.zeros((nw.value, 3), np.uint64)
+        if nw.value:
+            _check(L.pcd_nn_last_wave_records(self._h, _vp(rec), nw.value, C.byref(nw), C.byref(ni)))
+        return rec, int(ni.value)
 
 
 def associate_from_payload_device(device, d_q, Q, d_max_range, mr_count, gate_mode, d_keys, d_payload, d_out,
@@ -1073,6 +1088,19 @@ def set_nn_search(kernel=0):
     """first stage of the grid path: 0 = clipped brick kernel (default), 1 = the same with the clip off (stages the whole
     region: the A/B reference)"""
     _check(lib().pcd_nn_set_search(int(kernel)))
+
+
+def set_nn_schedule(schedule=0):
+    """how the brick kernel's work items are spread over its wavefronts: 0 = static rounds, then chunks handed out from a
+    cursor per block class (default), 1 = the static strided schedule alone (the A/B reference; results identical)"""
+    _check(lib().pcd_nn_set_schedule(int(schedule)))
+
+
+def nn_schedule_params():
+    """(static share of a wavefront's rounds in percent, items per chunk) of schedule 0: compile-time constants"""
+    a, b = C.c_int(0), C.c_int(0)
+    _check(lib().pcd_nn_schedule_params(C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def set_sift_tuning(nchunk=0, batch_partials=0):
