@@ -122,12 +122,39 @@ __device__ __forceinline__ T vgpr_pin(T v) {
   return v;
 }
 
+// How a write-once output leaves the chip.  Every byte of a store reaches memory either way; the policies differ in what
+// the line does to the caches on its way:
+//   plain          the line stays in the XCD's L2: right for what the next kernel, or a pinned-buffer copy, reads back
+//   nt             non-temporal: a streamed line, first to go; for outputs nothing in the evaluation reads again
+//   write_through  the sc1 form: written through, the line is dropped from L2 behind the write
+enum class StorePolicy { plain, nt, write_through };
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// 16 bytes of one lane under a policy the compiler sees and counts (no inline assembly: the waits of the loads around
+// such a store are hipcc's own).  write_through has no flat form; it goes through wave_rows_rsrc below.
+template <StorePolicy SP>
+__device__ __forceinline__ void store_f64x2(f64x2* p, f64x2 v) {
+  static_assert(SP != StorePolicy::write_through, "write-through stores take a buffer descriptor");
+  if (SP == StorePolicy::nt) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
+// Buffer descriptor of `bytes` bytes at a wave-uniform address (raw buffer, no swizzle; dword 3 = DATA_FORMAT 32 bit).
+// The base is the wavefront's own, so the 32-bit lane offsets stay small however large the array; the hardware drops a
+// store at or past `bytes`.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_rows_rsrc(double* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
+}
+constexpr int kAuxSc1 = 16;   // aux bits of the raw buffer store builtins: sc1 (write-through)
+
 // Coalesced store of one row of N doubles per lane, rows of consecutive lanes adjacent in memory
 // (out[(row0 + lane) * N + k] = v[k] for lane < cnt): the rows are transposed through a per-wavefront LDS
 // scratch of 64 * N doubles and leave as 16-B-per-lane stores of consecutive addresses (1 KiB per instruction)
 // instead of N stores that each touch 64 different cache lines.  Every lane of the wavefront must call it.
 // (lane = threadIdx.x & 63, handed in by a caller that wants the addresses derived from its own copy of it)
-template <int N>
+// SP: the store policy above; with write_through row0 and cnt must be wave-uniform for the compiler too.
+template <int N, StorePolicy SP = StorePolicy::plain>
 __device__ __forceinline__ void wave_store_rows(double* __restrict__ out, uint64_t row0, int cnt, const double (&v)[N],
                                                 double* __restrict__ lds, int lane) {
   static_assert(N % 2 == 0, "rows are moved in 16-byte units");
@@ -137,21 +164,46 @@ __device__ __forceinline__ void wave_store_rows(double* __restrict__ out, uint64
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  const double2* src = reinterpret_cast<const double2*>(lds);
-  double2* dst = reinterpret_cast<double2*>(out + row0 * N);
+  const f64x2* src = reinterpret_cast<const f64x2*>(lds);
+  f64x2* dst = reinterpret_cast<f64x2*>(out + row0 * N);
   const int units = cnt * (N / 2);
+  if (SP == StorePolicy::write_through) {
+    const __amdgpu_buffer_rsrc_t rsrc = wave_rows_rsrc(out + row0 * N, units * 16);
 #pragma unroll
-  for (int j = 0; j < N / 2; ++j) {
-    const int u = j * 64 + lane;
-    if (u < units) dst[u] = src[u];
+    for (int j = 0; j < N / 2; ++j) {
+      const int u = j * 64 + lane;
+      if (u < units) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, src[u]), rsrc, u * 16, 0, kAuxSc1);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) {
+      const int u = j * 64 + lane;
+      if (u < units) store_f64x2<SP == StorePolicy::nt ? StorePolicy::nt : StorePolicy::plain>(dst + u, src[u]);
+    }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();   // the scratch may be rewritten after this
 }
-template <int N>
+template <int N, StorePolicy SP = StorePolicy::plain>
 __device__ __forceinline__ void wave_store_rows(double* __restrict__ out, uint64_t row0, int cnt, const double (&v)[N],
                                                 double* __restrict__ lds) {
-  wave_store_rows<N>(out, row0, cnt, v, lds, (int)(threadIdx.x & 63));
+  wave_store_rows<N, SP>(out, row0, cnt, v, lds, (int)(threadIdx.x & 63));
+}
+
+// The scattered twin: this lane's row alone, out[row * N + k] = v[k], for rows that are not adjacent in memory.  plain
+// leaves the stores as the compiler forms them; nt sends the row as 16-byte units (the rows are 16-byte aligned, as
+// wave_store_rows takes them to be).  A lane's own row has no wave-uniform base, so there is no write-through form.
+template <int N, StorePolicy SP>
+__device__ __forceinline__ void lane_store_row(double* __restrict__ out, uint64_t row, const double (&v)[N]) {
+  static_assert(N % 2 == 0 && SP != StorePolicy::write_through, "16-byte units; plain or nt");
+  double* dst = out + row * N;
+  if (SP == StorePolicy::plain) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) dst[k] = v[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < N / 2; ++k) store_f64x2<SP>(reinterpret_cast<f64x2*>(dst) + k, f64x2{v[2 * k], v[2 * k + 1]});
+  }
 }
 
 // ------------------------------------------------------------- points ------
@@ -464,6 +516,13 @@ __device__ __forceinline__ const uint8_t* const_byte(const BaDev& d, bool has_pc
 // store of i.  Indices past the end of the segment are clamped to its last observation: no branch around the loads
 // (a constant-pose image that only writes its zero W rows loads as well), and what the surplus lanes and the surplus
 // last prefetch return is not used.  Same values into the same arithmetic.
+//
+// W leaves non-temporally (kWStore).  It is half of the pass's bytes (144 B per observation), written once and read by
+// nothing in the evaluation; as plain stores its lines pass through L2 and the Infinity Cache between two gathers of a
+// point's line, and the gathers of this pass and of k_ba_cost behind it miss more often.  Measured on the bench scene
+// (profiles/ba_store_policy_bench_lines.txt): nt 0.248 -> 0.220 ms and k_ba_cost 0.098 -> 0.093 ms; write-through (sc1)
+// stores 0.256 ms, slower than plain.  Same addresses, same values.
+constexpr StorePolicy kWStore = StorePolicy::nt;
 template <int MODEL, bool WANT_W>
 __global__ __launch_bounds__(256, (MODEL == 4 && WANT_W) ? 4 : 1) void k_ba_images(BaDev d, double* __restrict__ partial,
                                                                        double* __restrict__ W_o) {
@@ -594,11 +653,9 @@ __global__ __launch_bounds__(256, (MODEL == 4 && WANT_W) ? 4 : 1) void k_ba_imag
         const uint32_t o_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)oa);
         const bool contiguous = __all(!active || oa == o_first + (uint32_t)lane_i);
         if (contiguous) {
-          wave_store_rows<18>(W_o, o_first, cnt, w, s_w[wave], lane_i);
+          wave_store_rows<18, kWStore>(W_o, o_first, cnt, w, s_w[wave], lane_i);
         } else if (active) {
-          double* dst = W_o + 18 * (size_t)oa;
-#pragma unroll
-          for (int k = 0; k < 18; ++k) dst[k] = w[k];
+          lane_store_row<18, kWStore>(W_o, oa, w);
         }
       }
     }
