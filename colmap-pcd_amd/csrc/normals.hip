@@ -416,19 +416,20 @@ static pcd_status normals_device(pcd_cloud* c, const pcd_normals_options& o, uin
   if (c->n == 0) return PCD_OK;
   QueryScratch* sc = scratch_of(c);
   const GridParams& g = c->grid;
+  // the reach is checked before the first launch: a refused call leaves the handle and the outputs as they were
+  NormalsParams P;
+  P.r2 = o.radius * o.radius;
+  const double reach = (double)o.radius * (1.0 + 1e-5) + 2.0 * (double)g.slack;
+  P.R = (int)std::floor(reach / (double)g.h) + 1;
+  if (c->m != 0 && P.R > kNrMaxReach) {   // (radius <= 8 h was checked: only the slack could bring this about)
+    set_error("radius %g reaches %d cells of %g", (double)o.radius, P.R, (double)g.h);
+    return PCD_ERR_UNSUPPORTED;
+  }
   hipLaunchKernelGGL(k_normals_unindexed, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->pts4.p, c->n, o.only_missing,
                      c->pn8.p, d_count, d_curv);
   if (c->m == 0) {
     PCD_HIP_TRY(hipGetLastError());
     return PCD_OK;
-  }
-  NormalsParams P;
-  P.r2 = o.radius * o.radius;
-  const double reach = (double)o.radius * (1.0 + 1e-5) + 2.0 * (double)g.slack;
-  P.R = (int)std::floor(reach / (double)g.h) + 1;
-  if (P.R > kNrMaxReach) {   // (radius <= 8 h was checked: only a slack of a whole cell could bring this about)
-    set_error("radius %g reaches %d cells of %g", (double)o.radius, P.R, (double)g.h);
-    return PCD_ERR_UNSUPPORTED;
   }
   P.Rq = (P.R + 1) / 2;
   P.min_k = std::max(o.min_neighbors, 3);

@@ -148,7 +148,9 @@ pcd_cloud* pcd_cloud_shards_get(pcd_cloud_shards* s, int shard);    /* borrowed:
  * Limits: radius <= 8 * cell_size of the handle (PCD_ERR_INVALID otherwise: create the handle with a larger
  * cell_size); ONE handle holding the whole cloud -- a shard of pcd_cloud_create_sharded or a handle with
  * index_stride != 1 / index_base != 0 is refused with PCD_ERR_UNSUPPORTED, its neighbourhoods cross handle borders:
- * estimate on one handle, download, then shard.  An empty cloud returns PCD_OK with zero counts.
+ * estimate on one handle, download, then shard.  An empty cloud returns PCD_OK with zero counts.  Where the cloud's
+ * largest absolute coordinate times 2e-6 takes a radius of up to 8 cells past 9 cells: PCD_ERR_UNSUPPORTED ("reaches").
+ * A refused call of either entry point leaves the stored normals and the outputs as they were.
  * --------------------------------------------------------------------- */
 typedef enum { PCD_NORMALS_ORIENT_NONE = 0, PCD_NORMALS_ORIENT_VIEWPOINT = 1 } pcd_normals_orient;
 typedef struct {

@@ -1,7 +1,8 @@
 """The numpy reference of the normal estimation (tests/normals_ref.py) checked on its own, without a GPU: its neighbour
 sets against scipy's k-d tree, its sensitivity to the summation order against the tolerances the device test uses, the
-eigenvalue gaps of the parity clouds those tolerances rely on, the hand cases, and the entry point's refusal on a box
-without a device."""
+eigenvalue gaps of the parity clouds those tolerances rely on, the hand cases, the same checks on the scenes of
+tests/test_normals_edge_gpu.py with the figures and range-table branches those tests quote, and the entry point's
+refusal on a box without a device."""
 import ctypes as C
 
 import numpy as np
@@ -85,6 +86,106 @@ def test_orientation_tie_rule():
     xyz = nr.plane_lattice(n=9, spacing=0.125, z=0.0)     # the viewpoint (0,0,0) lies in the plane: n . (v - p) = 0
     ref = nr.estimate(xyz, 0.3)
     assert ref["ok"].all() and np.allclose(ref["normal"], [0, 0, 1], atol=1e-12)
+
+
+# ---- the scenes of tests/test_normals_edge_gpu.py: the same four checks, and the figures their tests quote ----
+@pytest.mark.parametrize("name", nr.EDGE_SCENES)
+def test_edge_scene_reference(name):
+    xyz, cell, r, opts, vectors, expect = nr.edge_scene(name)
+    ref = nr.edge_ref(name)
+    I, J = nr.edge_pairs(name)
+    Ik, Jk = nr.pairs_kdtree(xyz, r)
+    assert np.array_equal(I, Ik) and np.array_equal(J, Jk)
+    k = ref["count"][ref["finite"]]
+    narrow = ref["ok"] & (ref["gap"] < nr.GAP_MIN)
+    print(name, "estimated / too few / degenerate %d %d %d, k %d .. %d, gap<1e-3: %d rows, rank %.3g .. %.3g" % (
+        ref["ok"].sum(), ref["too_few"].sum(), ref["degenerate"].sum(), k.min(), k.max(), narrow.sum(),
+        ref["rank"][ref["finite"]].min(), ref["rank"][ref["finite"]].max()))
+    est, few, deg, kmin, kmax = expect
+    assert (int(ref["ok"].sum()), int(ref["too_few"].sum()), int(ref["degenerate"].sum())) == (est, few, deg)
+    assert kmin is None or (int(k.min()), int(k.max())) == (kmin, kmax)
+    assert k.min() >= 10 or not name.startswith("tail_")
+    assert not np.any((ref["rank"] > 1e-12) & (ref["rank"] < 1e-8))
+    if vectors:                                                # the share is capped wherever vectors are compared
+        assert narrow.sum() <= 0.01 * ref["ok"].sum()
+    # another summation order stays inside the device tolerances
+    alt = nr.from_pairs(xyz, I, J, perm=np.random.default_rng(5).permutation(I.shape[0]), **opts)
+    assert np.array_equal(alt["count"], ref["count"]) and np.array_equal(alt["ok"], ref["ok"])
+    assert np.all(np.abs(alt["curvature"] - ref["curvature"]) <= nr.curvature_tol(ref))
+    norm = np.linalg.norm(alt["normal"].astype(np.float32).astype(np.float64), axis=1)
+    assert np.all(np.abs(norm[ref["ok"]] - 1.0) <= 2.0 ** -22)
+    if vectors:
+        wide = ref["ok"] & ~narrow
+        dn = np.abs(alt["normal"].astype(np.float32).astype(np.float64) - ref["normal"].astype(np.float32))
+        assert np.all(dn[wide] <= nr.normal_tol(ref)[wide, None])
+
+
+def test_near_line_ranks_are_decades_from_the_rule():
+    for j, (lo, hi) in zip(nr.NEAR_LINE_JITTER, ((3e-8, 4e-7), (3e-6, 4e-5))):
+        rank = nr.edge_ref("near_line_%g" % j)["rank"]
+        assert lo <= rank.min() and rank.max() <= hi
+
+
+def test_orient_none_reference():
+    xyz, ref = nr.orient_none_ref()
+    _, with_vp = nr.parity_ref("uniform", 0.25)
+    big = ref["normal"][np.arange(xyz.shape[0]), np.argmax(np.abs(ref["normal"]), axis=1)]
+    assert np.all(big[ref["ok"]] > 0)
+    assert np.array_equal(np.abs(ref["normal"]), np.abs(with_vp["normal"]))      # the same vectors up to the sign
+    assert (ref["normal"] != with_vp["normal"]).any()
+    assert nr.orient_none_sure(ref).sum() >= 0.95 * ref["ok"].sum()
+
+
+def test_kept_mask_threshold():
+    xyz, stored = nr.only_missing_scene()
+    kept = nr.kept_mask(stored)
+    assert np.array_equal(kept[:7], [False, False, False, True, True, False, True])
+    assert int(kept[:25].sum()) == 10 and list(kept[25:]) == [True, False]
+    assert float(stored[2, 0]) == 9.999999974752427e-07
+
+
+def test_range_table_geometry_hand_cases():
+    # one leaf: a table of one row that holds every point
+    xyz, cell, r = nr.edge_scene("tail_65")[:3]
+    geo = nr.range_table_geometry(xyz, nr.grid_info(xyz, cell), r)
+    assert geo["leaves"].tolist() == [[0, 0, 0]] and geo["nrows"].tolist() == [1] and geo["rows"][0].tolist() == [65]
+    # one point in the middle of every cell of 2 x 60 x 60 (30 x 30 quads), r = 8 cells: R = 9, Rq = 5
+    h = 0.125
+    g = [(np.arange(n) + 0.5) * h for n in (2, 60, 60)]
+    xyz = np.stack(np.meshgrid(*g, indexing="ij"), axis=-1).reshape(-1, 3).astype(np.float32)
+    info = nr.grid_info(xyz, h)
+    assert info["dims"] == [2, 60, 60]
+    geo = nr.range_table_geometry(xyz, info, 1.0)
+    assert (geo["R"], geo["Rq"], geo["R_noslack"]) == (9, 5, 9) and geo["leaves"].shape[0] == 900
+    at = {tuple(l): i for i, l in enumerate(geo["leaves"].tolist())}
+    i = at[(0, 15, 15)]
+    assert geo["nrows"][i] == 121 and np.all(geo["rows"][i] == 8)               # 2 x cells of 4 cells a quad
+    assert geo["nrows"][at[(0, 0, 0)]] == 36 and geo["nrows"][at[(0, 3, 29)]] == 9 * 6
+    assert geo["nrows"].max() == 121
+    # the dims of the last row: lattice points bin as the device bins them (one per cell)
+    assert sum(int(w.sum()) for w in geo["rows"]) == sum(8 * n for n in geo["nrows"])
+
+
+def test_edge_scenes_reach_their_branches():
+    """what the GPU tests assert from the handle's info, here from the grid a handle of that cell size gets"""
+    geo = {n: nr.range_table_geometry(nr.edge_scene(n)[0], nr.grid_info(*nr.edge_scene(n)[:2]), nr.edge_scene(n)[2])
+           for n in ("wide_dense", "wide_dense_r7", "wide_sparse", "far", "wide_extent", "reach_0.7")}
+    d = geo["wide_dense"]
+    col = np.unique(d["leaves"][:, 1:], axis=0, return_index=True)[1]             # one leaf per (y, z) column
+    nrows = d["nrows"][col]
+    assert ((nrows > 64).sum(), (nrows == 64).sum(), (nrows < 64).sum(), nrows.max()) == (96, 4, 56, 121)
+    assert (d["R"], d["Rq"]) == (9, 5)
+    assert geo["wide_dense_r7"]["Rq"] == 4 and geo["wide_dense_r7"]["nrows"].max() == 81
+    wide = [w for n, w in zip(geo["wide_sparse"]["nrows"], geo["wide_sparse"]["rows"]) if n > 64]
+    assert any(w[64:].sum() == 0 for w in wide)
+    assert any(np.any((w[64:-1] == 0) & (w[65:] > 0)) for w in wide)
+    for n in ("far", "wide_extent"):
+        assert (geo[n]["R_noslack"], geo[n]["R"]) == (2, 3) and 3.7e-3 < geo[n]["slack"] < 3.9e-3
+    assert nr.grid_info(*nr.edge_scene("wide_extent")[:2])["dims"] == [40010, 10, 10]
+    assert (geo["reach_0.7"]["R_noslack"], geo["reach_0.7"]["R"]) == (8, 9)
+    # radius = 8 h on that handle: 10 cells
+    xyz, cell = nr.edge_scene("reach_0.7")[:2]
+    assert nr.range_table_geometry(xyz, nr.grid_info(xyz, cell), 0.8)["R"] == 10
 
 
 def test_entry_point_refuses_without_a_device(pcdhip):

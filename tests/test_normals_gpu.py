@@ -28,8 +28,9 @@ def _cloud(gpu, xyz, cell_size, nrm=None):
     return c
 
 
-def _compare(out, nrm_dev, ref, rows=None, vectors=True):
-    """device result (estimate_normals' dict + the downloaded normals) against the reference on `rows` (default all)"""
+def _compare(out, nrm_dev, ref, rows=None, vectors=True, sure=None):
+    """device result (estimate_normals' dict + the downloaded normals) against the reference on `rows` (default all);
+    sure: the rows whose sign must be the reference's (default: where the viewpoint decides it)"""
     n = ref["count"].shape[0]
     sel = np.ones(n, bool) if rows is None else np.isin(np.arange(n), rows)
     assert np.array_equal(out["count"][sel], ref["count"][sel])
@@ -51,7 +52,8 @@ def _compare(out, nrm_dev, ref, rows=None, vectors=True):
     dev = nrm_dev.astype(np.float64)
     same = np.abs(dev - ref32).max(axis=1)
     mirrored = np.abs(dev + ref32).max(axis=1)
-    sure = ref["dot_rel"] > 1e-6                         # the orientation is decided: signs must agree
+    if sure is None:
+        sure = ref["dot_rel"] > 1e-6                     # the orientation is decided: signs must agree
     err = np.where(sure, same, np.minimum(same, mirrored))
     tol_n = nr.normal_tol(ref)
     print("normals: max err / tol = %.3g over %d rows" % (float(np.max(err[wide] / tol_n[wide], initial=0.0)),
