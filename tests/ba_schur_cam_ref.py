@@ -272,3 +272,161 @@ def cam_case_scene(oracle, case, seed=40, **kw):
     s = camera_scene(oracle, models, seed + case, **kw)
     s["loss_type"], s["loss_scale"] = 2, 2.0
     return s, refine_mask(s, cams, groups)
+
+
+def gradient_max(ne):
+    """max |g| as pcd_ba_solve reports it (gradient_max_norm): over the active pose coordinates of the slots, every
+    non-constant point (skipped points included, as k_ba_grad_max) and, on a CamNormalEquations, the active camera
+    coordinates.  Returns (maximum, dict of the three partial maxima 'pose', 'point', 'camera')"""
+    pr = ne.pr
+    gp = np.abs(ne.gimg[pr["slot_img"]])[pr["active"]]
+    gx = np.abs(ne.gpt[pr["point_const"] == 0])
+    parts = dict(pose=float(gp.max()) if gp.size else 0.0, point=float(gx.max()) if gx.size else 0.0, camera=0.0)
+    if hasattr(ne, "gcam") and ne.ncs:
+        gc = np.abs(ne.gcam[ne.slot_cam].reshape(-1, S12))[ne.cam_active]
+        parts["camera"] = float(gc.max()) if gc.size else 0.0
+    return max(parts.values()), parts
+
+
+# ---- the boundary scenes of tests/test_ba_schur_cam_edge_{cpu,gpu}.py.  Every one sets image_const_pose explicitly, so
+# ---- that ns is what the case says (ba_schur_ref.camera_scene draws constant poses at random).
+def edge_scene(oracle, models, seed, I, P, const=(0,), cauchy=True, **kw):
+    """camera_scene (images dealt out in pairs over the cameras) with exactly the images `const` at a constant pose,
+    Cauchy loss unless cauchy=False"""
+    s = camera_scene(oracle, models, seed, I=I, P=P, **kw)
+    s["image_const_pose"] = np.zeros(I, np.uint8)
+    s["image_const_pose"][list(const)] = 1
+    if cauchy:
+        s["loss_type"], s["loss_scale"] = 2, 2.0
+    return s
+
+
+# name -> (models, seed, I, P, constant-pose images, ns, ncs): n = 6 ns + 12 ncs
+SLOT_CASES = {
+    # three chunks of the camera point sums (the third partial), six slot pairs: the first shape where the pair decode
+    # sees q = 3..5; n = 102 (2 panels)
+    "three_slots": ([4, 2, 1], 31, 12, 600, (0,), 11, 3),
+    # every camera model the other cases leave out; active counts [3, 5, 8, 5, 4, 5, 12, 8]: K = 3 and K = 5 meet the
+    # dead-row logic; 36 slot pairs, 96 camera coordinates (two trips of the one-wavefront loops); n = 186 (2 panels)
+    "eight_mixed": ([0, 3, 5, 7, 8, 9, 10, 4], 34, 16, 150, (0,), 15, 8),
+    # eight PINHOLE cameras, 41 images of which 13 are constant: ns = 28, n = 264 (3 panels), the camera rows occupy
+    # 168..263 across the panel edge at 192
+    "eight_wide": ([1] * 8, 37, 41, 300, tuple(range(0, 39, 3)), 28, 8),
+}
+
+
+def slot_scene(oracle, name):
+    """(scene, refine) of SLOT_CASES[name], every parameter refined"""
+    models, seed, I, P, const, _, _ = SLOT_CASES[name]
+    s = edge_scene(oracle, models, seed, I, P, const)
+    return s, refine_mask(s)
+
+
+# (ncs, ns): one OPENCV camera or OPENCV + SIMPLE_RADIAL, I = ns + 1 images of which image 0 alone is constant, 150
+# points.  n = 96 exactly (one full panel) twice; camera rows astride the first panel edge twice (n = 102: rows 90..101
+# and 78..101); camera rows opening panel 1 (6 ns = 96, n = 120)
+PANEL_CASES = [(1, 14), (2, 12), (1, 15), (2, 13), (2, 16)]
+
+
+def panel_scene(oracle, ncs, ns):
+    """(scene, refine) of one PANEL_CASES entry"""
+    s = edge_scene(oracle, [4] if ncs == 1 else [4, 2], 50 + 7 * ns + ncs, ns + 1, 150)
+    return s, refine_mask(s)
+
+
+def chunks_65_scene(oracle):
+    """OPENCV + SIMPLE_RADIAL, 6 images (image 0 constant: ns = 5, n = 54), 16 700 points: 66 chunks of 256 points, so
+    lanes 0 and 1 of the chunk reduction take two partials each, and the last chunk is partial (60 points)"""
+    s = edge_scene(oracle, [4, 2], 61, 6, 16700, cauchy=False)
+    return s, refine_mask(s)
+
+
+def _mask_of(scene, per_camera):
+    """camera_refine bytes from one tuple of parameter indices per camera"""
+    out = []
+    for cp, g in zip(scene["cam_params_list"], per_camera):
+        m = np.zeros(len(cp), np.uint8)
+        m[list(g)] = 1
+        out.append(m)
+    return np.concatenate(out)
+
+
+# name -> (models, one tuple of refined parameters per camera): masks with holes
+MASK_CASES = {
+    "principal_point": ([4], [(2, 3)]),
+    "distortion_only": ([4], [(4, 5, 6, 7)]),
+    "one_parameter": ([4], [(1,)]),
+    "thin_prism_ends": ([10], [(0, 11)]),
+    "two_masks": ([4, 2], [(0, 3, 5), (1, 3)]),
+}
+
+
+def mask_scene(oracle, name):
+    """(scene, refine) of MASK_CASES[name]: 6 images, image 0 constant, 150 points"""
+    models, groups = MASK_CASES[name]
+    s = edge_scene(oracle, models, 70 + sorted(MASK_CASES).index(name), 6, 150)
+    return s, _mask_of(s, groups)
+
+
+def const_points_scene(oracle):
+    """OPENCV + SIMPLE_RADIAL, 8 images, every point constant: nothing is eliminated, so S_cam is H_cam plus its damping,
+    B is E_cam, rhs_cam is -g_cam and the off-diagonal blocks of S_cam are zero"""
+    s = edge_scene(oracle, [4, 2], 83, 8, 150)
+    s["point_const"] = np.ones(150, np.uint8)
+    return s, refine_mask(s)
+
+
+def const_pose_camera_scene(oracle):
+    """two cameras, 8 images dealt out in pairs; every image of camera 1 (2, 3, 6, 7) has a constant pose: ns = 4, the
+    B column of slot 1 carries no E_cam term, and its S_cam blocks are still non-zero through the shared points"""
+    s = edge_scene(oracle, [4, 2], 85, 8, 150, const=(2, 3, 6, 7))
+    return s, refine_mask(s)
+
+
+def unused_camera_scene(oracle):
+    """test_ba_pcg_cam_cpu.unused_camera_scene with images 0 and 1 constant (ns = 4): the gauge is fixed, so the pose
+    part and camera 0 keep safe pivots without damping, and the first coordinate of the unused slot, 6 ns + 12 = 36, is
+    the first column that fails at Levenberg mu = 0"""
+    from tests.test_ba_pcg_cam_cpu import unused_camera_scene as base
+    s, refine = base(oracle)
+    s["image_const_pose"] = np.zeros(len(s["poses"]), np.uint8)
+    s["image_const_pose"][:2] = 1
+    return s, refine
+
+
+def gradient_scene(oracle, where):
+    """(scene, refine or None) whose largest gradient entry sits
+    'camera': in a coordinate of camera slot 7 -- the eight_mixed scene with the trivial loss, the focal lengths of
+              camera 7 (OPENCV) x 1.5 and its two images at a constant pose, so that their pose gradients do not count;
+              the coordinates 84 .. 95 are read by the second trip of the one-wavefront loops over 12 ncs = 96;
+    'pose':   in a pose coordinate -- eight_wide as it is;
+    'point':  in the last point of the 16 700-point scene, on a handle without refinement (refine None): the plane of
+              its LiDAR term is moved 1000 m away.  The point is read by the last workgroup of the gradient maximum."""
+    if where == "camera":
+        models, seed, I, P, const, _, _ = SLOT_CASES["eight_mixed"]
+        s = edge_scene(oracle, models, seed, I, P, const, cauchy=False)
+        s["image_const_pose"][np.asarray(s["image_camera"]) == 7] = 1
+        cp = [np.array(c, np.float64) for c in s["cam_params_list"]]
+        cp[7][:2] *= 1.5
+        s["cam_params_list"] = cp
+        return s, refine_mask(s)
+    if where == "pose":
+        return slot_scene(oracle, "eight_wide")
+    s, _ = chunks_65_scene(oracle)
+    last = s["points"].shape[0] - 1
+    s["point_const"][last] = 0
+    k = np.flatnonzero(np.asarray(s["lidar_point"]) == last)
+    assert k.size == 1
+    s["lidar_abcd"] = np.array(s["lidar_abcd"], np.float64)
+    s["lidar_abcd"][k, 3] += 1000.0
+    return s, None
+
+
+def lm_eight_scene(oracle):
+    """(scene, refine, initial radius) of the LM loop at eight slots: eight_wide with the trivial loss, the points
+    perturbed by N(0, 2 m) and every focal length x 1.05 (as test_ba_schur_cam_gpu._lm_scene), started at radius 1e7"""
+    models, seed, I, P, const, _, _ = SLOT_CASES["eight_wide"]
+    s = edge_scene(oracle, models, seed, I, P, const, cauchy=False)
+    s["points"] = s["points"] + np.random.default_rng(1037).normal(0, 2.0, s["points"].shape)
+    s["cam_params_list"] = [np.array(c, np.float64) * np.r_[1.05, 1.05, 1.0, 1.0] for c in s["cam_params_list"]]
+    return s, refine_mask(s), 1e7

@@ -36,7 +36,8 @@ def _dev(a):
 
 
 def _parity(gpu, oracle, s, refine, mu, mode, well_conditioned):
-    """every check of one (scene, refine, damping): blocks, pose part, solve, back-substitution, plus"""
+    """every check of one (scene, refine, damping): blocks, pose part, solve, back-substitution, plus.  Returns the
+    reference; its attribute `device` holds the direct solve's info and step, the device's dense S and right-hand side"""
     base = cref.without_refine(s)
     ne = cref.CamNormalEquations(oracle, base, refine, mu, mode)
     sb = ne.schur_cam_blocks()
@@ -73,6 +74,7 @@ def _parity(gpu, oracle, s, refine, mu, mode, well_conditioned):
     delta, info = ba.schur_cam_solve_cholesky()
     delta = delta.cpu().numpy()
     assert info["n"] == n
+    ne.device = dict(info=info, S=S, rhs=rhs, delta=delta.copy(), slots=slots)      # for the caller's own assertions
     if info["status"] == gpu.CHOL_OK:
         e = eta(S, rhs, delta)
         print(f"n {n} ncs {ncs} eta {e:.3e} (bound {ETA_CAM_BOUND:.3e})")
