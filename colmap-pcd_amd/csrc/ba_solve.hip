@@ -1,19 +1,22 @@
 // ba_solve.hip -- the device solver of bundle adjustment: point elimination of the damped normal
-// equations into the reduced camera system (k_schur_*), the manifold update (k_ba_plus), the block-sparse
-// preconditioned CG on that system (k_pcg_*), the direct solve of it (the handle's blocks or the caller's dense S into
-// the scratch of ba_chol.hip, which factors and solves) and the Levenberg-Marquardt loop around them (pcd_ba_solve).
+// equations into the reduced camera system (k_schur_*), the manifold update (k_ba_plus), the batches of the
+// block-sparse preconditioned CG on that system (kernels: ba_pcg.hip), the direct solve of it (the handle's blocks or
+// the caller's dense S into the scratch of ba_chol.hip, which factors and solves) and the Levenberg-Marquardt loop
+// around them (pcd_ba_solve).
 //
 // The blocks it eliminates come from ba.hip, which this unit reaches through two calls only: ba_normal_equations
 // (ba_handle.h) for H, g, W and the cost, and pcd_ba_evaluate_device for the cost of a trial step.  No evaluation
 // kernel is compiled here.
 //
 // Refined intrinsics ride beside all this, opt-in (pcd_ba_schur_cam*, pcd_ba_solve with refine_intrinsics): the camera rows
-// of the reduced system are a dense border whose kernels live in ba_solve_cam.hip, the kernels of the PCG on the bordered
-// system (pcd_ba_schur_cam_solve_pcg*, PCD_LINEAR_PCG_CAM) in ba_pcg_cam.hip; the state and the entry points are here.
+// of the reduced system are a dense border whose kernels live in ba_solve_cam.hip; the state and the entry points are
+// here.  Every host path takes the number of camera slots, ncs: 0 is the plain system, and a _cam entry point on a handle
+// without camera slots is its plain counterpart.
 //
 // Host side, behind the kernels: BaSchur, the solver state grouped by owner; schur_build, which has the co-visibility
 // structure built on the device (ba_schur_structure.hip) on the stream of the call that needs it; the PCG batches;
-// pcd_ba_solve over lm_check_opts, lm_reserve, lm_enqueue_linear, lm_try_step, lm_decide.
+// one internal function per operation, which the plain and the _cam entry point both call; pcd_ba_solve over
+// lm_check_opts, lm_reserve, lm_enqueue_linear, lm_try_step, lm_decide.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -21,6 +24,7 @@
 
 #include "ba_chol.h"
 #include "ba_handle.h"
+#include "ba_pcg.h"
 #include "ba_schur_structure.h"
 #include "ba_solve_cam.h"
 #include "common.h"
@@ -198,15 +202,15 @@ __global__ __launch_bounds__(256) void k_schur_blocks(SchurBlocks sb) {
   }
 }
 
-// dense S [n][n] (n = 6 ns, both triangles) from the blocks; the caller zeroed it.  thread = (block, entry)
+// the pose blocks, both triangles, into the dense S with leading dimension n (6 ns; 6 ns + 12 ncs with camera rows,
+// whose entries are k_schur_cam_dense's); the caller zeroed it.  thread = (block, entry)
 __global__ __launch_bounds__(256) void k_schur_dense(int ns, uint32_t nblk, const uint32_t* __restrict__ pair_ij,
                                                      const double* __restrict__ Sdiag, const double* __restrict__ Soff,
-                                                     double* __restrict__ S) {
+                                                     size_t n, double* __restrict__ S) {
   const uint64_t t = blockIdx.x * (uint64_t)256 + threadIdx.x;
   if (t >= (uint64_t)nblk * 36) return;
   const uint32_t blk = (uint32_t)(t / 36);
   const int k = (int)(t - 36 * (uint64_t)blk), r = k / 6, s = k - 6 * (k / 6);
-  const size_t n = 6 * (size_t)ns;
   if (blk < (uint32_t)ns) {
     S[(6 * (size_t)blk + r) * n + 6 * (size_t)blk + s] = Sdiag[36 * (size_t)blk + k];
   } else {
@@ -239,8 +243,8 @@ __global__ __launch_bounds__(256) void k_chol_fill_blocks(int ns, uint32_t nblk,
   }
 }
 
-// thread = point: delta X_p = -V^-1 (g_p + sum_{a in p} W_a^T delta c_img(a)), its observations in ascending caller
-// order; partial of the model decrease -delta^T g + delta^T D delta over the points (fixed-order block sum)
+// thread = point: delta X_p = -V^-1 (g_p + sum_{a in p} W_a^T delta c_img(a)) and the partial of the model decrease
+// over the points: schur_back_point (ba_solve_cam.h, shared with k_schur_cam_back) with no camera term
 __global__ __launch_bounds__(256) void k_schur_back(int P, const uint32_t* __restrict__ pt_start,
                                                     const uint32_t* __restrict__ pt_list, const int* __restrict__ obs_image,
                                                     const uint32_t* __restrict__ obs_pos, const int* __restrict__ img_slot,
@@ -248,37 +252,8 @@ __global__ __launch_bounds__(256) void k_schur_back(int P, const uint32_t* __res
                                                     const double* __restrict__ gpt, const double* __restrict__ Dpt,
                                                     const double* __restrict__ dpose, double* __restrict__ dpoint,
                                                     double* __restrict__ md_partial) {
-  __shared__ double s_m[4];
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  double md = 0.0;
-  if (p < P) {
-    const double* g = gpt + 3 * (size_t)p;
-    double r0 = g[0], r1 = g[1], r2 = g[2];
-    for (uint32_t k = pt_start[p]; k < pt_start[p + 1]; ++k) {
-      const uint32_t o = pt_list[k];
-      const int s = img_slot[obs_image[o]];
-      if (s < 0) continue;
-      const double* w = Wim + 18 * (size_t)obs_pos[o];
-      const double* dc = dpose + 6 * (size_t)s;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        const double c = dc[a];
-        r0 += w[3 * a] * c; r1 += w[3 * a + 1] * c; r2 += w[3 * a + 2] * c;
-      }
-    }
-    const double* v = Vinv + 9 * (size_t)p;
-    const double dx0 = -(v[0] * r0 + v[1] * r1 + v[2] * r2);
-    const double dx1 = -(v[3] * r0 + v[4] * r1 + v[5] * r2);
-    const double dx2 = -(v[6] * r0 + v[7] * r1 + v[8] * r2);
-    dpoint[3 * (size_t)p] = dx0; dpoint[3 * (size_t)p + 1] = dx1; dpoint[3 * (size_t)p + 2] = dx2;
-    const double* d = Dpt + 3 * (size_t)p;
-    md = -(dx0 * g[0] + dx1 * g[1] + dx2 * g[2]) + (d[0] * dx0 * dx0 + d[1] * dx1 * dx1 + d[2] * dx2 * dx2);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) md += __shfl_xor(md, off);
-  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = md;
-  __syncthreads();
-  if (threadIdx.x == 0) md_partial[blockIdx.x] = (s_m[0] + s_m[1]) + (s_m[2] + s_m[3]);
+  schur_back_point(P, pt_start, pt_list, obs_image, obs_pos, img_slot, Wim, Vinv, gpt, Dpt, dpose, dpoint, md_partial,
+                   [](int, double&, double&, double&) {});
 }
 
 // one workgroup: 1/2 (slot terms + point partials), strided per thread then a fixed tree
@@ -366,266 +341,6 @@ __global__ __launch_bounds__(256) void k_ba_plus(int I, int P, const int* __rest
     double* o = points_out + 3 * (size_t)p;
     const double y0 = c ? x[0] : x[0] + d[0], y1 = c ? x[1] : x[1] + d[1], y2 = c ? x[2] : x[2] + d[2];
     o[0] = y0; o[1] = y1; o[2] = y2;
-  }
-}
-
-// ---- block-sparse preconditioned CG on the reduced camera system (pcd_ba_schur_solve_pcg*) -----------
-// S x = rhs from the handle's own blocks.  An iteration is three plain launches (product, vector update, scalars);
-// scalars, the iteration count and the done flag live in PcgState on the device and every kernel of an iteration
-// returns at once when done is set, so the host enqueues a batch of iterations between two looks at the flag.
-// p and x are double-buffered (iteration it reads buffer it & 1 and writes the other): the product forms the new
-// direction of a partner slot on the fly from z and the old p instead of waiting for a fourth launch, and a breakdown
-// leaves the last finite x untouched.  All sums run in an order fixed by the structure.
-// PcgState, PcgRule, block_sum256, block_sum_strided: ba_solve_cam.h, shared with the bordered PCG.
-
-// thread = slot: M_i^-1 (SCHUR_JACOBI: inverse of the 6x6 diagonal block through its Cholesky factor, identity when a
-// pivot is not positive and finite -- counted; IDENTITY: I), x = 0, r = rhs, z = M^-1 r, both direction buffers 0;
-// partials [nb][4] of r.z, rhs.rhs and the fallback count.  An identity row / column of the block (constant tvec
-// coordinate) gives an identity row / column of the factor and of the inverse, exactly.
-__global__ __launch_bounds__(256) void k_pcg_init(int ns, int precond, const double* __restrict__ Sdiag,
-                                                  const double* __restrict__ rhs, double* __restrict__ Minv,
-                                                  double* __restrict__ x0, double* __restrict__ r, double* __restrict__ z,
-                                                  double* __restrict__ p0, double* __restrict__ p1,
-                                                  double* __restrict__ partial) {
-  __shared__ double s_l[4];
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double rz = 0.0, bb = 0.0, fb = 0.0;
-  if (i < ns) {
-    double mi[36];
-#pragma unroll
-    for (int k = 0; k < 36; ++k) mi[k] = (k % 7 == 0) ? 1.0 : 0.0;
-    if (precond != 0) {
-      const double* A = Sdiag + 36 * (size_t)i;
-      double L[36];
-#pragma unroll
-      for (int k = 0; k < 36; ++k) L[k] = 0.0;
-      bool ok = true;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        double d = A[7 * j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= L[6 * j + k] * L[6 * j + k];
-        ok = ok && d > 0.0 && d <= 1.7976931348623157e308;
-        const double ljj = ok ? sqrt(d) : 1.0;
-        L[7 * j] = ljj;
-#pragma unroll
-        for (int a = j + 1; a < 6; ++a) {
-          double s = A[6 * a + j];
-#pragma unroll
-          for (int k = 0; k < j; ++k) s -= L[6 * a + k] * L[6 * j + k];
-          L[6 * a + j] = s / ljj;
-        }
-      }
-      if (ok) {
-        double M[36];   // L^-1, lower
-#pragma unroll
-        for (int k = 0; k < 36; ++k) M[k] = 0.0;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          M[7 * j] = 1.0 / L[7 * j];
-#pragma unroll
-          for (int a = j + 1; a < 6; ++a) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = j; k < a; ++k) s += L[6 * a + k] * M[6 * k + j];
-            M[6 * a + j] = -s / L[7 * a];
-          }
-        }
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-          for (int c = 0; c <= a; ++c) {
-            double s = 0.0;   // (M^T M)_ac, k from a (>= c) upwards
-#pragma unroll
-            for (int k = a; k < 6; ++k) s += M[6 * k + a] * M[6 * k + c];
-            mi[6 * a + c] = s; mi[6 * c + a] = s;
-          }
-      } else {
-        fb = 1.0;
-      }
-    }
-    double* mo = Minv + 36 * (size_t)i;
-#pragma unroll
-    for (int k = 0; k < 36; ++k) mo[k] = mi[k];
-    double b[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) b[k] = rhs[6 * (size_t)i + k];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      double s = 0.0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) s += mi[6 * a + c] * b[c];
-      const size_t o = 6 * (size_t)i + a;
-      z[o] = s; r[o] = b[a]; x0[o] = 0.0; p0[o] = 0.0; p1[o] = 0.0;
-      rz += b[a] * s; bb += b[a] * b[a];
-    }
-  }
-  rz = block_sum256(rz, s_l); bb = block_sum256(bb, s_l); fb = block_sum256(fb, s_l);
-  if (threadIdx.x == 0) {
-    double* o = partial + 4 * (size_t)blockIdx.x;
-    o[0] = rz; o[1] = bb; o[2] = fb; o[3] = 0.0;
-  }
-}
-
-// one workgroup: the scalars of iteration 0.  ||rhs|| = 0 -> ZERO_RHS, max_iterations <= 0 -> MAX_ITERATIONS, x = 0
-__global__ __launch_bounds__(256) void k_pcg_begin(int nb, const double* __restrict__ partial, PcgRule rule,
-                                                   PcgState* __restrict__ st) {
-  __shared__ double s_l[4];
-  const double rz = block_sum_strided(partial, nb, 4, s_l);
-  const double bb = block_sum_strided(partial + 1, nb, 4, s_l);
-  const double fb = block_sum_strided(partial + 2, nb, 4, s_l);
-  if (threadIdx.x != 0) return;
-  PcgState s;
-  s.rho = rz; s.alpha = 0.0; s.beta = 0.0; s.pw = 0.0; s.q = 0.0; s.rn2 = bb; s.bnorm = sqrt(bb); s.xr = 0.0;
-  s.k = 0; s.done = 0; s.term = PCD_PCG_MAX_ITERATIONS; s.xsel = 0; s.fallbacks = (unsigned)fb; s.pad = 0;
-  if (!(bb > 0.0)) {   // zero (or not a number: nothing to iterate on)
-    s.done = 1; s.term = bb == 0.0 ? PCD_PCG_ZERO_RHS : PCD_PCG_BREAKDOWN;
-  } else if (!(rz > 0.0) || !(rz <= 1.7976931348623157e308)) {
-    s.done = 1; s.term = PCD_PCG_BREAKDOWN;
-  } else if (rule.max_iterations <= 0) {
-    s.done = 1;
-  }
-  *st = s;
-}
-
-// one wavefront per slot row: w_i = sum over the row list (ascending partner slot; block, transposed flag) of
-// B p_j with p_j = z_j + beta p_old_j, lane-strided blocks, six accumulators, xor butterfly.  Lane 0 stores the row's
-// new direction, w_i and p_i . w_i.
-__global__ __launch_bounds__(256) void k_pcg_spmv(int ns, const PcgState* __restrict__ st,
-                                                  const uint32_t* __restrict__ row_start, const uint32_t* __restrict__ row_blk,
-                                                  const uint32_t* __restrict__ row_col, const double* __restrict__ Sdiag,
-                                                  const double* __restrict__ Soff, const double* __restrict__ z,
-                                                  const double* __restrict__ p_old, double* __restrict__ p_new,
-                                                  double* __restrict__ w, double* __restrict__ pw_partial) {
-  if (st->done) return;
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (i >= ns) return;
-  const double beta = st->beta;
-  double acc[6] = {0, 0, 0, 0, 0, 0};
-  for (uint32_t t = row_start[i] + lane; t < row_start[i + 1]; t += 64) {
-    const uint32_t blk = row_blk[t], cj = row_col[t];
-    const bool tr = cj & 1u;
-    const size_t j = cj >> 1;
-    const double* B = blk < (uint32_t)ns ? Sdiag + 36 * (size_t)blk : Soff + 36 * (size_t)(blk - (uint32_t)ns);
-    double bv[36], pj[6];
-#pragma unroll
-    for (int k = 0; k < 36; ++k) bv[k] = B[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) pj[k] = z[6 * j + k] + beta * p_old[6 * j + k];
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      double s = 0.0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) s += (tr ? bv[6 * c + a] : bv[6 * a + c]) * pj[c];
-      acc[a] += s;
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc[a] += __shfl_xor(acc[a], off);
-  if (lane == 0) {
-    double pw = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const size_t o = 6 * (size_t)i + k;
-      const double pk = z[o] + beta * p_old[o];
-      p_new[o] = pk; w[o] = acc[k];
-      pw += pk * acc[k];
-    }
-    pw_partial[i] = pw;
-  }
-}
-
-// thread = slot: alpha = rho / p.w (every workgroup sums the ns row partials in the same order), then
-// x_new = x_old + alpha p, r -= alpha w, z = M^-1 r and the partials [nb][4] of r.z, r.r, x.(rhs + r), x.r.
-// p.w <= 0 or a non-finite alpha: nothing is updated (k_pcg_step ends the solve with BREAKDOWN).
-__global__ __launch_bounds__(256) void k_pcg_update(int ns, PcgState* __restrict__ st, const double* __restrict__ pw_partial,
-                                                    const double* __restrict__ Minv, const double* __restrict__ rhs,
-                                                    const double* __restrict__ p, const double* __restrict__ w,
-                                                    const double* __restrict__ x_old, double* __restrict__ x_new,
-                                                    double* __restrict__ r, double* __restrict__ z,
-                                                    double* __restrict__ partial) {
-  __shared__ double s_l[4];
-  if (st->done) return;
-  const double pw = block_sum_strided(pw_partial, ns, 1, s_l);
-  const double alpha = st->rho / pw;
-  const bool good = pw > 0.0 && alpha <= 1.7976931348623157e308 && alpha >= -1.7976931348623157e308;
-  if (blockIdx.x == 0 && threadIdx.x == 0) { st->pw = pw; st->alpha = alpha; }
-  if (!good) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double rz = 0.0, rr = 0.0, xbr = 0.0, xr = 0.0;
-  if (i < ns) {
-    double rv[6], xv[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const size_t o = 6 * (size_t)i + k;
-      xv[k] = x_old[o] + alpha * p[o];
-      rv[k] = r[o] - alpha * w[o];
-      x_new[o] = xv[k]; r[o] = rv[k];
-    }
-    const double* mi = Minv + 36 * (size_t)i;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      double s = 0.0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) s += mi[6 * a + c] * rv[c];
-      z[6 * (size_t)i + a] = s;
-      rz += rv[a] * s; rr += rv[a] * rv[a];
-      xbr += xv[a] * (rhs[6 * (size_t)i + a] + rv[a]); xr += xv[a] * rv[a];
-    }
-  }
-  rz = block_sum256(rz, s_l); rr = block_sum256(rr, s_l); xbr = block_sum256(xbr, s_l); xr = block_sum256(xr, s_l);
-  if (threadIdx.x == 0) {
-    double* o = partial + 4 * (size_t)blockIdx.x;
-    o[0] = rz; o[1] = rr; o[2] = xbr; o[3] = xr;
-  }
-}
-
-// one workgroup: sums of the partials, Q_k = -1/2 x.(rhs + r), the stopping rule (Q, then r, then the iteration
-// limit), beta and the counter.  `it` is the iteration's index (the buffer that holds its x is (it + 1) & 1).
-__global__ __launch_bounds__(256) void k_pcg_step(int nb, int it, const double* __restrict__ partial, PcgRule rule,
-                                                  PcgState* __restrict__ st) {
-  __shared__ double s_l[4];
-  if (st->done) return;
-  const double pw = st->pw, alpha = st->alpha;
-  if (!(pw > 0.0 && alpha <= 1.7976931348623157e308 && alpha >= -1.7976931348623157e308)) {
-    if (threadIdx.x == 0) { st->done = 1; st->term = PCD_PCG_BREAKDOWN; }
-    return;
-  }
-  const double rz = block_sum_strided(partial, nb, 4, s_l);
-  const double rr = block_sum_strided(partial + 1, nb, 4, s_l);
-  const double xbr = block_sum_strided(partial + 2, nb, 4, s_l);
-  const double xr = block_sum_strided(partial + 3, nb, 4, s_l);
-  if (threadIdx.x != 0) return;
-  const double q = -0.5 * xbr;
-  const double lim = 1.7976931348623157e308;
-  if (!(rz >= 0.0 && rz <= lim && rr <= lim && q >= -lim && q <= lim)) {   // the x of this iteration is not used
-    st->done = 1; st->term = PCD_PCG_BREAKDOWN;
-    return;
-  }
-  const int k = st->k + 1;
-  const double zeta = (double)k * (q - st->q) / q;
-  int done = 0, term = PCD_PCG_MAX_ITERATIONS;
-  if (k >= rule.min_iterations && rule.q_tolerance >= 0.0 && zeta < rule.q_tolerance) { done = 1; term = PCD_PCG_Q_TOLERANCE; }
-  else if (k >= rule.min_iterations && rule.r_tolerance >= 0.0 && sqrt(rr) <= rule.r_tolerance * st->bnorm) { done = 1; term = PCD_PCG_R_TOLERANCE; }
-  else if (k >= rule.max_iterations) { done = 1; }
-  st->beta = rz / st->rho; st->rho = rz; st->q = q; st->rn2 = rr; st->xr = xr;
-  st->k = k; st->xsel = (it + 1) & 1; st->term = term; st->done = done;
-}
-
-// the selected x into the caller's dpose, the record into info (termination -1: still running)
-__global__ __launch_bounds__(256) void k_pcg_finish(int ns, const PcgState* __restrict__ st, const double* __restrict__ x0,
-                                                    const double* __restrict__ x1, double* __restrict__ dpose,
-                                                    pcd_ba_pcg_info* __restrict__ info) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (dpose && t < 6 * ns) dpose[t] = (st->xsel ? x1 : x0)[t];
-  if (t == 0 && info) {
-    pcd_ba_pcg_info o;
-    o.iterations = st->k; o.termination = st->done ? st->term : -1; o.precond_fallbacks = st->fallbacks;
-    o.rhs_norm = st->bnorm; o.residual_norm = sqrt(st->rn2); o.q = st->q; o.step_dot_residual = st->xr;
-    *info = o;
   }
 }
 
@@ -756,17 +471,28 @@ void ba_schur_drop_structure(pcd_ba* b) {
 using namespace pcd;
 
 // ---- point elimination: guards and the co-visibility structure ----------------------------------------------
-// Every Schur entry point: no gfx950 device -> NO_DEVICE, no handle -> INVALID, refined intrinsics -> UNSUPPORTED
-// (the reduced system would need the camera rows), all before anything is allocated or launched.
-static pcd_status schur_guard(pcd_ba* b) {
+static int cam_slots(const pcd_ba* b) { return (int)b->h_slot_cam.size(); }
+
+// Every Schur entry point, before anything is allocated or launched: no gfx950 device -> NO_DEVICE, no handle ->
+// INVALID.  A plain call (cam false), and a _cam call on a handle without camera slots, which is its plain counterpart:
+// refined intrinsics -> UNSUPPORTED (the reduced system would need the camera rows).  A _cam call: more camera slots
+// than the bordered system carries -> UNSUPPORTED.  *ncs: the camera slots the call works with, 0 for the plain system.
+static pcd_status schur_guard(pcd_ba* b, bool cam, int* ncs) {
   PCD_TRY(require_device(b ? b->device : 0));
   PCD_REQUIRE(b, "null handle");
-  if (b->refines_intrinsics) {
+  *ncs = cam ? cam_slots(b) : 0;
+  if (*ncs > PCD_BA_MAX_CAMERA_SLOTS) {
+    set_error("%d cameras have refined parameters; the reduced system carries at most PCD_BA_MAX_CAMERA_SLOTS = %d "
+              "camera slots (cameras shared by many images)", *ncs, PCD_BA_MAX_CAMERA_SLOTS);
+    return PCD_ERR_UNSUPPORTED;
+  }
+  if (!*ncs && b->refines_intrinsics) {
     set_error("point elimination with refined intrinsics (camera_refine) is not supported");
     return PCD_ERR_UNSUPPORTED;
   }
   return PCD_OK;
 }
+static pcd_status schur_guard(pcd_ba* b) { int ncs; return schur_guard(b, false, &ncs); }
 
 // The co-visibility structure, if the handle has none (after pcd_ba_create, or after an edit dropped it): built on the
 // device, on the stream of the call that needs it (ba_schur_structure.hip).  A capturing stream is refused before
@@ -800,8 +526,9 @@ static pcd_status pcg_check_opts(const pcd_ba_pcg_opts* o) {
 }
 
 // Can a solver read the handle's own system?  The state of a Schur call (what the back-substitution reads), and with
-// `blocks` its S_diag / S_off / rhs in the handle's buffers (what the PCG and the direct solve read).
-static pcd_status schur_state_guard(const pcd_ba* b, const char* fn, bool blocks) {
+// `blocks` its S_diag / S_off / rhs in the handle's buffers (what the PCG and the direct solve read).  With camera
+// slots (ncs > 0), also that the last Schur call carried camera rows.
+static pcd_status schur_state_guard(const pcd_ba* b, const char* fn, bool blocks, int ncs) {
   if (!b->schur || !b->schur->num.valid) {
     set_error("%s: no Schur state (call pcd_ba_schur[_device] first)", fn);
     return PCD_ERR_INVALID;
@@ -813,6 +540,10 @@ static pcd_status schur_state_guard(const pcd_ba* b, const char* fn, bool blocks
               N.own_rhs ? "" : "rhs ");
     return PCD_ERR_INVALID;
   }
+  if (ncs && !b->schur->cam.valid) {
+    set_error("%s: no Schur state with camera rows (call pcd_ba_schur_cam[_device] first)", fn);
+    return PCD_ERR_INVALID;
+  }
   return PCD_OK;
 }
 
@@ -820,94 +551,74 @@ static PcgRule pcg_rule(const pcd_ba_pcg_opts* o) {
   return PcgRule{o->max_iterations, o->min_iterations, o->q_tolerance, o->r_tolerance};
 }
 
-static int cam_slots(const pcd_ba* b) { return (int)b->h_slot_cam.size(); }
-
-// the bordered solve's view of the handle (cam: the last Schur call carried camera rows)
-static PcgCamVec pcg_cam_vec(pcd_ba* b) {
-  BaSchur& S = *b->schur; BaSchur::Pcg& C = S.cg;
-  return PcgCamVec{S.st.ns, cam_slots(b), C.state.p, S.cam.B.p, S.cam.Scam.p, S.cam.rhs.p, C.Minv_cam.p, C.z.p, C.r.p,
-                   C.w.p, C.camw.p, C.pw.p, C.partial.p};
+// a solve's view of the handle; ncs camera slots ride behind the poses (0: the plain system)
+static PcgVec pcg_vec(pcd_ba* b, int ncs) {
+  BaSchur& S = *b->schur; const BaSchur::Structure& T = S.st; BaSchur::Pcg& C = S.cg;
+  PcgVec v{};
+  v.ns = T.ns; v.ncs = ncs; v.st = C.state.p;
+  v.row_start = T.row_start.p; v.row_blk = T.row_blk.p; v.row_col = T.row_col.p;
+  v.Sdiag = S.num.Sdiag.p; v.Soff = S.num.Soff.p; v.rhs = S.num.rhs.p;
+  v.B = S.cam.B.p; v.Scam = S.cam.Scam.p; v.rhs_cam = S.cam.rhs.p;
+  v.Minv = C.Minv.p; v.Minv_cam = C.Minv_cam.p; v.x0 = C.x0.p; v.x1 = C.x1.p; v.p0 = C.p0.p; v.p1 = C.p1.p;
+  v.z = C.z.p; v.r = C.r.p; v.w = C.w.p; v.camw = C.camw.p; v.pw = C.pw.p; v.partial = C.partial.p;
+  return v;
 }
 
-// preconditioner, x = 0, r = rhs, the scalars of iteration 0.  cam: the bordered system, whose vectors carry the
-// 12 ncs camera coordinates behind the poses and whose partial lists one entry per camera slot behind the workgroups
-static pcd_status pcg_begin(pcd_ba* b, const pcd_ba_pcg_opts* o, bool cam, hipStream_t s) {
-  BaSchur& S = *b->schur; BaSchur::Pcg& C = S.cg;
-  const int ns = S.st.ns, ncs = cam ? cam_slots(b) : 0; const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256));
+// preconditioner, x = 0, r = rhs, the scalars of iteration 0.  With camera slots the vectors carry the 12 ncs camera
+// coordinates behind the poses and the partial lists one entry per camera slot behind the workgroups
+static pcd_status pcg_begin(pcd_ba* b, const pcd_ba_pcg_opts* o, int ncs, hipStream_t s) {
+  BaSchur::Pcg& C = b->schur->cg;
+  const int ns = b->schur->st.ns; const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256));
   const size_t nc = (size_t)kCamS * ncs;
   PCD_TRY(C.Minv.reserve(at_least_1(blocks_6x6(ns))));
   for (DevBuf<double>* d : {&C.x0, &C.x1, &C.r, &C.z, &C.p0, &C.p1, &C.w}) PCD_TRY(d->reserve(at_least_1(slot_vec(ns) + nc)));
   PCD_TRY(C.pw.reserve(at_least_1(ns + nc))); PCD_TRY(C.partial.reserve(4 * ((size_t)nb + ncs)));
   PCD_TRY(C.state.reserve(1)); PCD_TRY(C.info.reserve(1)); PCD_TRY(C.flag.reserve(4));
-  if (cam) { PCD_TRY(C.Minv_cam.reserve(nc * kCamS)); PCD_TRY(C.camw.reserve(at_least_1(nc * ns))); }
+  if (ncs) { PCD_TRY(C.Minv_cam.reserve(nc * kCamS)); PCD_TRY(C.camw.reserve(at_least_1(nc * ns))); }
   C.it = 0;
-  hipLaunchKernelGGL(k_pcg_init, dim3(nb), dim3(256), 0, s, ns, o->preconditioner, S.num.Sdiag.p, S.num.rhs.p, C.Minv.p,
-                     C.x0.p, C.r.p, C.z.p, C.p0.p, C.p1.p, C.partial.p);
-  if (cam) pcg_cam_init(pcg_cam_vec(b), o->preconditioner, C.x0.p, C.p0.p, C.p1.p, s);
-  hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(256), 0, s, (int)nb + ncs, C.partial.p, pcg_rule(o), C.state.p);
+  pcg_init(pcg_vec(b, ncs), o->preconditioner, pcg_rule(o), s);
   return PCD_OK;
 }
 
-// `count` more iterations (three launches each, four on the bordered system; all of them return at once when the solve
-// has ended)
-static void pcg_enqueue(pcd_ba* b, const pcd_ba_pcg_opts* o, bool cam, int count, hipStream_t s) {
-  const BaSchur::Structure& T = b->schur->st; const BaSchur::Numeric& N = b->schur->num; BaSchur::Pcg& C = b->schur->cg;
-  const int ns = T.ns;
-  if (!ns && !cam) return;
-  const unsigned nb = std::max(1u, div_up((uint64_t)ns, 256)); const PcgRule rule = pcg_rule(o);
-  for (int c = 0; c < count; ++c, ++C.it) {
-    const int it = C.it;
-    double* p_old = (it & 1) ? C.p1.p : C.p0.p; double* p_new = (it & 1) ? C.p0.p : C.p1.p;
-    double* x_old = (it & 1) ? C.x1.p : C.x0.p; double* x_new = (it & 1) ? C.x0.p : C.x1.p;
-    if (cam) {
-      const PcgCamVec v = pcg_cam_vec(b);
-      pcg_cam_product(v, T.row_start.p, T.row_blk.p, T.row_col.p, N.Sdiag.p, N.Soff.p, p_old, p_new, s);
-      pcg_cam_update(v, C.state.p, C.Minv.p, N.rhs.p, p_new, x_old, x_new, s);
-      hipLaunchKernelGGL(k_pcg_step, dim3(1), dim3(256), 0, s, (int)nb + v.ncs, it, C.partial.p, rule, C.state.p);
-      continue;
-    }
-    hipLaunchKernelGGL(k_pcg_spmv, dim3(div_up((uint64_t)ns, 4)), dim3(256), 0, s, ns, C.state.p, T.row_start.p,
-                       T.row_blk.p, T.row_col.p, N.Sdiag.p, N.Soff.p, C.z.p, p_old, p_new, C.w.p, C.pw.p);
-    hipLaunchKernelGGL(k_pcg_update, dim3(nb), dim3(256), 0, s, ns, C.state.p, C.pw.p, C.Minv.p, N.rhs.p, p_new, C.w.p,
-                       x_old, x_new, C.r.p, C.z.p, C.partial.p);
-    hipLaunchKernelGGL(k_pcg_step, dim3(1), dim3(256), 0, s, (int)nb, it, C.partial.p, rule, C.state.p);
-  }
-}
-
-// x into d_delta: k_pcg_finish copies 6 slots' worth per slot, and the bordered vector is 6 (ns + 2 ncs) long
-static void pcg_finish(pcd_ba* b, bool cam, double* d_delta, pcd_ba_pcg_info* d_info, hipStream_t s) {
-  const int ns = b->schur->st.ns + (cam ? 2 * cam_slots(b) : 0); BaSchur::Pcg& C = b->schur->cg;
-  hipLaunchKernelGGL(k_pcg_finish, dim3(std::max(1u, div_up(slot_vec(ns), 256))), dim3(256), 0, s, ns, C.state.p, C.x0.p,
-                     C.x1.p, d_delta, d_info);
+// `count` more iterations (all their launches return at once when the solve has ended)
+static void pcg_enqueue(pcd_ba* b, const pcd_ba_pcg_opts* o, int ncs, int count, hipStream_t s) {
+  const PcgVec v = pcg_vec(b, ncs); const PcgRule rule = pcg_rule(o); BaSchur::Pcg& C = b->schur->cg;
+  if (!v.ns && !ncs) return;   // nothing was enqueued: the parity stays
+  for (int c = 0; c < count; ++c, ++C.it) pcg_iterate(v, C.it, rule, s);
 }
 
 // batches until the device says done; `enqueued` iterations are already in the stream.  One flag copy per batch.
-static pcd_status pcg_run(pcd_ba* b, const pcd_ba_pcg_opts* o, bool cam, int enqueued, hipStream_t s) {
+static pcd_status pcg_run(pcd_ba* b, const pcd_ba_pcg_opts* o, int ncs, int enqueued, hipStream_t s) {
   BaSchur::Pcg& C = b->schur->cg;
   int batch = kPcgFirstBatch;
-  if (!enqueued) { pcg_enqueue(b, o, cam, std::min(batch, o->max_iterations), s); enqueued = std::min(batch, o->max_iterations); }
+  if (!enqueued) { pcg_enqueue(b, o, ncs, std::min(batch, o->max_iterations), s); enqueued = std::min(batch, o->max_iterations); }
   for (;;) {
     PCD_HIP_TRY(hipMemcpyAsync(C.flag.p, &C.state.p->done, sizeof(int), hipMemcpyDeviceToHost, s));
     PCD_HIP_TRY(hipStreamSynchronize(s));
-    if (C.flag.p[0] || (!b->schur->st.ns && !cam) || enqueued >= o->max_iterations) return PCD_OK;
+    if (C.flag.p[0] || (!b->schur->st.ns && !ncs) || enqueued >= o->max_iterations) return PCD_OK;
     batch = std::min(2 * batch, kPcgMaxBatch);
     const int n = std::min(batch, o->max_iterations - enqueued);
-    pcg_enqueue(b, o, cam, n, s); enqueued += n;
+    pcg_enqueue(b, o, ncs, n, s); enqueued += n;
   }
 }
 
-// Direct solve: scratch on first use, fill (the handle's blocks when d_S is null, else the caller's dense S), factor and
-// solve.  No synchronisation; the status record stays in chol.info.
-static pcd_status chol_solve(pcd_ba* b, const double* d_S, const double* d_rhs, double* d_dpose,
+// Direct solve of the system [6 ns | 12 ncs]: scratch on first use, fill (the handle's blocks when d_S is null, else the
+// caller's dense S, which only the plain system has: ncs = 0), factor and solve.  No synchronisation; the status record
+// stays in chol.info.
+static pcd_status chol_solve(pcd_ba* b, int ncs, const double* d_S, const double* d_rhs, double* d_delta,
                              pcd_ba_chol_info* d_info, hipStream_t s) {
-  const BaSchur::Structure& T = b->schur->st; const BaSchur::Numeric& N = b->schur->num; BaSchur::Chol& K = b->schur->chol;
-  const int ns = T.ns, n = (int)slot_vec(ns);
+  const BaSchur::Structure& T = b->schur->st; const BaSchur::Numeric& N = b->schur->num;
+  BaSchur::Chol& K = b->schur->chol; const BaSchur::Cam& Cm = b->schur->cam;
+  PCD_REQUIRE(!d_S || !ncs, "a caller's dense S has no camera rows");
+  const int ns = T.ns, n = (int)slot_vec(ns) + kCamS * ncs;
   PCD_TRY(K.A.reserve(chol_scratch_doubles(n))); PCD_TRY(K.info.reserve(1));
   chol_begin(K.A.p, n, K.info.p, s);
   if (d_S) chol_fill_dense(K.A.p, n, d_S, d_rhs, s);
-  else hipLaunchKernelGGL(k_chol_fill_blocks, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, ns, T.nblk(),
-                          T.pair_ij.p, N.Sdiag.p, N.Soff.p, N.rhs.p, chol_padded(n), K.A.p);
-  chol_factor_solve(K.A.p, n, K.info.p, d_dpose, d_info, s);
+  else if (T.nblk())
+    hipLaunchKernelGGL(k_chol_fill_blocks, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, ns, T.nblk(),
+                       T.pair_ij.p, N.Sdiag.p, N.Soff.p, N.rhs.p, chol_padded(n), K.A.p);
+  if (ncs) schur_cam_fill_chol(ns, ncs, Cm.B.p, Cm.Scam.p, Cm.rhs.p, chol_padded(n), K.A.p, s);
+  chol_factor_solve(K.A.p, n, K.info.p, d_delta, d_info, s);
   return PCD_OK;
 }
 
@@ -964,30 +675,30 @@ static pcd_status copy_camera_parameters(pcd_ba* b, bool save, hipStream_t s) {
   return PCD_OK;
 }
 
-static pcd_status chol_solve_cam(pcd_ba* b, double* d_delta, pcd_ba_chol_info* d_info, hipStream_t s);   // below
+// the internal forms of the entry points lm_try_step calls, below
+static pcd_status back_substitute_device(pcd_ba* b, bool cam, const double* d_delta, double* d_dpoint,
+                                         double* d_model_decrease, void* stream);
+static pcd_status plus_device(pcd_ba* b, bool cam, const double* d_delta, const double* d_dpoint, double* d_poses_out,
+                              double* d_points_out, double* d_cam_params_out, void* stream);
 
-// The linear solve of an iteration into lm.dpose / cg.info: the direct solve (an exact step: nothing left to run, *enq =
-// max_iterations), or pcg_begin and the first batch (*enq = its iterations)
-static pcd_status lm_enqueue_linear(pcd_ba* b, const pcd_ba_solve_opts* o, bool cam, int* enq, hipStream_t s) {
+// The linear solve of an iteration into lm.dpose (dpose, then dcam) / cg.info: the direct solve (an exact step: nothing
+// left to run, *enq = max_iterations), or pcg_begin and the first batch (*enq = its iterations)
+static pcd_status lm_enqueue_linear(pcd_ba* b, const pcd_ba_solve_opts* o, int ncs, int* enq, hipStream_t s) {
   BaSchur& S = *b->schur;
   *enq = o->linear.max_iterations;
   if (o->linear_solver == PCD_LINEAR_CHOLESKY) {
     PCD_TRY(S.cg.info.reserve(1));
-    if (cam) {   // the bordered system: dpose, then dcam
+    if (S.st.ns || ncs) {
       ScopedKernelTimer t("ba_schur_cholesky", s);
-      PCD_TRY(chol_solve_cam(b, S.lm.dpose.p, nullptr, s));
-      hipLaunchKernelGGL(k_chol_lm_info, dim3(1), dim3(1), 0, s, S.chol.info.p, S.cg.info.p);
-    } else if (S.st.ns) {
-      ScopedKernelTimer t("ba_schur_cholesky", s);
-      PCD_TRY(chol_solve(b, nullptr, nullptr, S.lm.dpose.p, nullptr, s));
+      PCD_TRY(chol_solve(b, ncs, nullptr, nullptr, S.lm.dpose.p, nullptr, s));
       hipLaunchKernelGGL(k_chol_lm_info, dim3(1), dim3(1), 0, s, S.chol.info.p, S.cg.info.p);
     } else {
       PCD_HIP_TRY(hipMemsetAsync(S.cg.info.p, 0, sizeof(pcd_ba_pcg_info), s));   // 0 iterations, PCD_CHOL_OK
     }
   } else {
-    PCD_TRY(pcg_begin(b, &o->linear, cam, s));   // cam: PCD_LINEAR_PCG_CAM, the bordered system
+    PCD_TRY(pcg_begin(b, &o->linear, ncs, s));   // with camera slots: PCD_LINEAR_PCG_CAM, the bordered system
     *enq = std::min(kPcgFirstBatch, o->linear.max_iterations);
-    pcg_enqueue(b, &o->linear, cam, *enq, s);
+    pcg_enqueue(b, &o->linear, ncs, *enq, s);
   }
   return PCD_OK;
 }
@@ -995,19 +706,15 @@ static pcd_status lm_enqueue_linear(pcd_ba* b, const pcd_ba_solve_opts* o, bool 
 // Tail of an iteration up to the synchronised read-back of its record into lm.host.  It is enqueued behind the first
 // batch without looking at the flag: at the defaults the PCG has ended by then and the iteration costs one copy.  If the
 // step came from an unfinished solve, the accepted parameters go back, the batches go on and the tail runs once more.
-static pcd_status lm_try_step(pcd_ba* b, const pcd_ba_solve_opts* o, bool cam, int enq, unsigned ngp, EventPair& ev,
+static pcd_status lm_try_step(pcd_ba* b, const pcd_ba_solve_opts* o, int ncs, int enq, unsigned ngp, EventPair& ev,
                               double* linear_ms, hipStream_t s) {
   BaSchur& S = *b->schur; BaSchur::Lm& M = S.lm;
+  const bool cam = ncs > 0;
   pcd_ba_out co{}; co.cost = M.cand_cost.p;
   for (;;) {
-    if (o->linear_solver != PCD_LINEAR_CHOLESKY) pcg_finish(b, cam, M.dpose.p, S.cg.info.p, s);
-    if (cam) {
-      PCD_TRY(pcd_ba_schur_cam_back_substitute_device(b, M.dpose.p, M.dpoint.p, S.num.md.p, s));
-      PCD_TRY(pcd_ba_plus_cam_device(b, M.dpose.p, M.dpoint.p, b->poses.p, b->points.p, b->cam_params.p, s));
-    } else {
-      PCD_TRY(pcd_ba_schur_back_substitute_device(b, M.dpose.p, M.dpoint.p, S.num.md.p, s));
-      PCD_TRY(pcd_ba_plus_device(b, M.dpose.p, M.dpoint.p, b->poses.p, b->points.p, s));
-    }
+    if (o->linear_solver != PCD_LINEAR_CHOLESKY) pcg_finish(pcg_vec(b, ncs), M.dpose.p, S.cg.info.p, s);
+    PCD_TRY(back_substitute_device(b, cam, M.dpose.p, M.dpoint.p, S.num.md.p, s));
+    PCD_TRY(plus_device(b, cam, M.dpose.p, M.dpoint.p, b->poses.p, b->points.p, cam ? b->cam_params.p : nullptr, s));
     PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
     hipLaunchKernelGGL(k_ba_lm_record, dim3(1), dim3(256), 0, s, S.num.cost.p, M.cand_cost.p, S.num.md.p, M.gpart.p,
                        (int)ngp, S.num.skip_cnt.p, S.cg.info.p, M.rec.p);
@@ -1018,7 +725,7 @@ static pcd_status lm_try_step(pcd_ba* b, const pcd_ba_solve_opts* o, bool cam, i
     PCD_TRY(copy_parameters(b, b->poses.p, b->points.p, M.poses.p, M.points.p, s));
     if (cam) PCD_TRY(copy_camera_parameters(b, false, s));
     PCD_HIP_TRY(ev.start(s));
-    PCD_TRY(pcg_run(b, &o->linear, cam, enq, s)); enq = o->linear.max_iterations;
+    PCD_TRY(pcg_run(b, &o->linear, ncs, enq, s)); enq = o->linear.max_iterations;
     PCD_HIP_TRY(ev.stop(s));
   }
   PCD_HIP_TRY(hipGetLastError());
@@ -1049,19 +756,84 @@ static LmDecision lm_decide(const LmRecord& rec, const pcd_ba_solve_opts& o, dou
   return d;
 }
 
-// pcd_ba_schur_device behind its handle guard: pcd_ba_schur_cam_device runs the same pose part on a refined handle
-static pcd_status schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o, void* stream,
-                               const char* fn) {
+// ---- one host path per operation: ncs = 0 is the plain call, ncs > 0 carries the camera rows (ba_solve_cam.h) ------
+
+// the pose outputs of a pcd_ba_schur_cam* call in the plain call's form
+static pcd_ba_schur_out pose_out(const pcd_ba_schur_cam_out& o) {
+  pcd_ba_schur_out po{};
+  po.cost = o.cost; po.S_diag = o.S_diag; po.S_off = o.S_off; po.rhs = o.rhs; po.S = o.S; po.num_skipped = o.num_skipped;
+  return po;
+}
+
+// the camera slots on the device, once (the structure exists: schur_build ran)
+static pcd_status cam_upload_slots(pcd_ba* b) {
+  BaSchur::Cam& K = b->schur->cam;
+  if (K.slots) return PCD_OK;
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  PCD_TRY(upload(K.cam_slot, b->h_cam_slot.data(), b->h_cam_slot.size()));
+  PCD_TRY(upload(K.slot_cam, b->h_slot_cam.data(), b->h_slot_cam.size()));
+  PCD_TRY(upload(K.param_cam, b->h_param_cam.data(), b->h_param_cam.size()));
+  PCD_TRY(upload(K.active, b->h_cam_active.data(), b->h_cam_active.size()));
+  K.slots = true;
+  return PCD_OK;
+}
+
+// The camera rows behind the pose elimination: the camera blocks of the evaluation (its own scopes: ba_cameras,
+// ba_cam_w), then Wc, Z, S_cam, rhs_cam and the border B into the handle
+static pcd_status schur_cam_rows(pcd_ba* b, int ncs, const pcd_ba_schur_opts* opt, hipStream_t s) {
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; BaSchur::Cam& K = b->schur->cam;
+  {
+    pcd_ba_out co{};
+    co.H_cam = K.Hcam.p; co.g_cam = K.gcam.p; co.E_cam = K.Ecam.p; co.W_cam = K.Wcam.p;
+    PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
+  }
+  SchurCamIn in{};
+  in.P = b->P; in.I = b->I; in.ns = T.ns; in.ncs = ncs;
+  in.shared = ncs == 1 && b->shared_cam >= 0 && b->h_cam_slot[b->shared_cam] == 0;
+  in.cam_slot = K.cam_slot.p; in.slot_cam = K.slot_cam.p; in.active = K.active.p;
+  in.image_cam = b->image_cam.p; in.obs_image = b->obs_image.p;
+  in.pt_obs_start = b->pt_obs_start.p; in.pt_obs_list = b->pt_obs_list.p;
+  in.img_obs_start = b->img_obs_start.p; in.img_pt = b->img_pt.p;
+  in.slot_img = T.slot_img.p; in.image_const_tvec = b->const_tvec();
+  in.Vinv = N.Vinv.p; in.gpt = N.gpt.p; in.Wim = N.Wim.p;
+  in.Hcam = K.Hcam.p; in.gcam = K.gcam.p; in.Ecam = K.Ecam.p; in.Wcam = K.Wcam.p;
+  in.mu = opt->mu; in.mode = opt->damping;
+  const SchurCamOut out{K.Wc.p, K.Z.p, K.partial.p, K.B.p, K.Scam.p, K.rhs.p, K.D.p};
+  {
+    ScopedKernelTimer t("ba_schur_cam_eliminate", s);
+    schur_cam_eliminate(in, out, s);
+  }
+  {
+    ScopedKernelTimer t("ba_schur_cam_border", s);
+    schur_cam_border(in, out, s);
+  }
+  return PCD_OK;
+}
+
+// pcd_ba_schur_device (ncs = 0, co null) and pcd_ba_schur_cam_device behind their handle guard.  o: the pose outputs and
+// the dense S [n][n], n = 6 ns + 12 ncs; co: where B, S_cam and rhs_cam go beside the handle's own copy.
+static pcd_status schur_device(pcd_ba* b, int ncs, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o,
+                               const pcd_ba_schur_cam_out* co, void* stream) {
   PCD_REQUIRE(opt && o, "null pointer");
   PCD_REQUIRE(opt->damping == PCD_DAMP_MARQUARDT || opt->damping == PCD_DAMP_LEVENBERG, "damping");
   PCD_REQUIRE(opt->mu >= 0.0, "mu must be >= 0");
-  PCD_TRY(refuse_capture((hipStream_t)stream, fn));
   hipStream_t s = (hipStream_t)stream;
+  PCD_TRY(refuse_capture(s, ncs ? "pcd_ba_schur_cam_device" : "pcd_ba_schur_device"));
   PCD_TRY(schur_build(b, s));
-  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
+  if (ncs) PCD_TRY(cam_upload_slots(b));
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; BaSchur::Cam& K = b->schur->cam;
   const int I = b->I, P = b->P, ns = T.ns;
+  const size_t nc = (size_t)kCamS * ncs;
   const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));   // grid of k_schur_points = length of its partials
-  N.valid = b->schur->cam.valid = false;
+  N.valid = K.valid = false;
+  if (ncs) {
+    PCD_TRY(K.Hcam.reserve((size_t)kCamS * kCamS * b->C)); PCD_TRY(K.gcam.reserve((size_t)kCamS * b->C));
+    PCD_TRY(K.Ecam.reserve(at_least_1((size_t)kCamS * 6 * I))); PCD_TRY(K.Wcam.reserve(at_least_1(36 * (size_t)b->O)));
+    PCD_TRY(K.Wc.reserve(at_least_1(36 * (size_t)P * ncs))); PCD_TRY(K.Z.reserve(at_least_1(36 * (size_t)P * ncs)));
+    PCD_TRY(K.partial.reserve(cam_pairs(ncs) * kCamEnt * cam_chunks(P)));
+    PCD_TRY(K.B.reserve(at_least_1((size_t)ns * nc * 6))); PCD_TRY(K.Scam.reserve(nc * nc));
+    PCD_TRY(K.rhs.reserve(nc)); PCD_TRY(K.D.reserve(nc));
+  }
   PCD_TRY(N.Himg.reserve(blocks_6x6(I))); PCD_TRY(N.gimg.reserve(slot_vec(I)));
   PCD_TRY(N.Hpt.reserve(point_blocks(P))); PCD_TRY(N.gpt.reserve(point_vec(P)));
   PCD_TRY(N.Wim.reserve(at_least_1(obs_blocks(b->O)))); PCD_TRY(N.Y.reserve(at_least_1(obs_blocks(b->O))));
@@ -1083,130 +855,176 @@ static pcd_status schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pc
     schur_eliminate(b, opt, nbp, Sdiag, Soff, o->rhs ? o->rhs : N.rhs.p,
                     o->num_skipped ? reinterpret_cast<unsigned long long*>(o->num_skipped) : N.skip_cnt.p, s);
   }
-  if (o->S && T.ns) {
-    ScopedKernelTimer t("ba_schur_dense", s);
-    const size_t n = slot_vec(T.ns);
-    PCD_HIP_TRY(hipMemsetAsync(o->S, 0, n * n * sizeof(double), s));
-    hipLaunchKernelGGL(k_schur_dense, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, T.ns, T.nblk(),
-                       T.pair_ij.p, Sdiag, Soff, o->S);
-  }
-  PCD_HIP_TRY(hipGetLastError());
-  N.valid = true; N.own_diag = !o->S_diag; N.own_off = !o->S_off; N.own_rhs = !o->rhs;
-  return PCD_OK;
-}
-
-// ---- camera rows: refined intrinsics in the reduced system (pcd_ba_schur_cam*, ba_solve_cam.h) --------------------
-
-// Every _cam entry point: the guards of the plain calls without their refusal of a refined handle; instead more camera
-// slots than the bordered system carries -> UNSUPPORTED.  Before anything is allocated or launched.
-static pcd_status schur_cam_guard(pcd_ba* b) {
-  PCD_TRY(require_device(b ? b->device : 0));
-  PCD_REQUIRE(b, "null handle");
-  if (cam_slots(b) > PCD_BA_MAX_CAMERA_SLOTS) {
-    set_error("%d cameras have refined parameters; the reduced system carries at most PCD_BA_MAX_CAMERA_SLOTS = %d "
-              "camera slots (cameras shared by many images)", cam_slots(b), PCD_BA_MAX_CAMERA_SLOTS);
-    return PCD_ERR_UNSUPPORTED;
-  }
-  return PCD_OK;
-}
-
-// the state of a pcd_ba_schur_cam* call: what schur_state_guard asks, and that the last Schur call carried camera rows
-static pcd_status schur_cam_state_guard(const pcd_ba* b, const char* fn, bool blocks) {
-  PCD_TRY(schur_state_guard(b, fn, blocks));
-  if (!b->schur->cam.valid) {
-    set_error("%s: no Schur state with camera rows (call pcd_ba_schur_cam[_device] first)", fn);
-    return PCD_ERR_INVALID;
-  }
-  return PCD_OK;
-}
-
-// the camera slots on the device, once (the structure exists: schur_build ran)
-static pcd_status cam_upload_slots(pcd_ba* b) {
-  BaSchur::Cam& K = b->schur->cam;
-  if (K.slots) return PCD_OK;
-  PCD_HIP_TRY(hipSetDevice(b->device));
-  PCD_TRY(upload(K.cam_slot, b->h_cam_slot.data(), b->h_cam_slot.size()));
-  PCD_TRY(upload(K.slot_cam, b->h_slot_cam.data(), b->h_slot_cam.size()));
-  PCD_TRY(upload(K.param_cam, b->h_param_cam.data(), b->h_param_cam.size()));
-  PCD_TRY(upload(K.active, b->h_cam_active.data(), b->h_cam_active.size()));
-  K.slots = true;
-  return PCD_OK;
-}
-
-// pcd_ba_schur_cam_device on a handle with camera slots, behind its guards
-static pcd_status schur_cam_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_cam_out* o, void* stream) {
-  PCD_REQUIRE(opt && o, "null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  PCD_TRY(refuse_capture(s, "pcd_ba_schur_cam_device"));
-  PCD_TRY(schur_build(b, s));
-  PCD_TRY(cam_upload_slots(b));
-  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; BaSchur::Cam& K = b->schur->cam;
-  const int ncs = cam_slots(b), ns = T.ns, P = b->P;
-  const size_t nc = (size_t)kCamS * ncs;
-  PCD_TRY(K.Hcam.reserve((size_t)kCamS * kCamS * b->C)); PCD_TRY(K.gcam.reserve((size_t)kCamS * b->C));
-  PCD_TRY(K.Ecam.reserve(at_least_1((size_t)kCamS * 6 * b->I))); PCD_TRY(K.Wcam.reserve(at_least_1(36 * (size_t)b->O)));
-  PCD_TRY(K.Wc.reserve(at_least_1(36 * (size_t)P * ncs))); PCD_TRY(K.Z.reserve(at_least_1(36 * (size_t)P * ncs)));
-  PCD_TRY(K.partial.reserve(cam_pairs(ncs) * kCamEnt * cam_chunks(P)));
-  PCD_TRY(K.B.reserve(at_least_1((size_t)ns * nc * 6))); PCD_TRY(K.Scam.reserve(nc * nc));
-  PCD_TRY(K.rhs.reserve(nc)); PCD_TRY(K.D.reserve(nc));
-  pcd_ba_schur_out po{};
-  po.cost = o->cost; po.S_diag = o->S_diag; po.S_off = o->S_off; po.rhs = o->rhs; po.num_skipped = o->num_skipped;
-  PCD_TRY(schur_device(b, opt, &po, stream, "pcd_ba_schur_cam_device"));   // the pose part, unchanged
-  {
-    pcd_ba_out co{};   // its own scopes: ba_cameras, ba_cam_w
-    co.H_cam = K.Hcam.p; co.g_cam = K.gcam.p; co.E_cam = K.Ecam.p; co.W_cam = K.Wcam.p;
-    PCD_TRY(pcd_ba_evaluate_device(b, &co, s));
-  }
-  SchurCamIn in{};
-  in.P = P; in.I = b->I; in.ns = ns; in.ncs = ncs;
-  in.shared = ncs == 1 && b->shared_cam >= 0 && b->h_cam_slot[b->shared_cam] == 0;
-  in.cam_slot = K.cam_slot.p; in.slot_cam = K.slot_cam.p; in.active = K.active.p;
-  in.image_cam = b->image_cam.p; in.obs_image = b->obs_image.p;
-  in.pt_obs_start = b->pt_obs_start.p; in.pt_obs_list = b->pt_obs_list.p;
-  in.img_obs_start = b->img_obs_start.p; in.img_pt = b->img_pt.p;
-  in.slot_img = T.slot_img.p; in.image_const_tvec = b->const_tvec();
-  in.Vinv = N.Vinv.p; in.gpt = N.gpt.p; in.Wim = N.Wim.p;
-  in.Hcam = K.Hcam.p; in.gcam = K.gcam.p; in.Ecam = K.Ecam.p; in.Wcam = K.Wcam.p;
-  in.mu = opt->mu; in.mode = opt->damping;
-  const SchurCamOut out{K.Wc.p, K.Z.p, K.partial.p, K.B.p, K.Scam.p, K.rhs.p, K.D.p};
-  {
-    ScopedKernelTimer t("ba_schur_cam_eliminate", s);
-    schur_cam_eliminate(in, out, s);
-  }
-  {
-    ScopedKernelTimer t("ba_schur_cam_border", s);
-    schur_cam_border(in, out, s);
-  }
-  if (o->S) {
+  if (ncs) PCD_TRY(schur_cam_rows(b, ncs, opt, s));
+  if (o->S && (ns || ncs)) {   // test and debugging output; with camera rows one launch for the pose blocks, one for the rest
     ScopedKernelTimer t("ba_schur_dense", s);
     const size_t n = slot_vec(ns) + nc;
     PCD_HIP_TRY(hipMemsetAsync(o->S, 0, n * n * sizeof(double), s));
-    schur_cam_dense(ns, ncs, T.nblk(), T.pair_ij.p, po.S_diag ? po.S_diag : N.Sdiag.p, po.S_off ? po.S_off : N.Soff.p,
-                    K.B.p, K.Scam.p, o->S, s);
+    if (T.nblk())
+      hipLaunchKernelGGL(k_schur_dense, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, ns, T.nblk(),
+                         T.pair_ij.p, Sdiag, Soff, n, o->S);
+    if (ncs) schur_cam_dense(ns, ncs, K.B.p, K.Scam.p, o->S, s);
   }
-  const auto copy_out = [&](double* dst, const double* src, size_t n) -> pcd_status {
-    if (dst && n) PCD_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return PCD_OK;
-  };
-  PCD_TRY(copy_out(o->B, K.B.p, (size_t)ns * nc * 6)); PCD_TRY(copy_out(o->S_cam, K.Scam.p, nc * nc));
-  PCD_TRY(copy_out(o->rhs_cam, K.rhs.p, nc));
+  if (ncs) {
+    const auto copy_out = [&](double* dst, const double* src, size_t n) -> pcd_status {
+      if (dst && n) PCD_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+      return PCD_OK;
+    };
+    PCD_TRY(copy_out(co->B, K.B.p, (size_t)ns * nc * 6)); PCD_TRY(copy_out(co->S_cam, K.Scam.p, nc * nc));
+    PCD_TRY(copy_out(co->rhs_cam, K.rhs.p, nc));
+  }
   PCD_HIP_TRY(hipGetLastError());
-  K.valid = true;
+  N.valid = true; N.own_diag = !o->S_diag; N.own_off = !o->S_off; N.own_rhs = !o->rhs;
+  K.valid = ncs > 0;
   return PCD_OK;
 }
 
-// the direct solve of the bordered system from the handle's own blocks into d_delta [6 ns + 12 ncs]; status in chol.info
-static pcd_status chol_solve_cam(pcd_ba* b, double* d_delta, pcd_ba_chol_info* d_info, hipStream_t s) {
-  const BaSchur::Structure& T = b->schur->st; const BaSchur::Numeric& N = b->schur->num;
-  BaSchur::Chol& K = b->schur->chol; const BaSchur::Cam& Cm = b->schur->cam;
-  const int ns = T.ns, ncs = cam_slots(b), n = (int)slot_vec(ns) + kCamS * ncs;
-  PCD_TRY(K.A.reserve(chol_scratch_doubles(n))); PCD_TRY(K.info.reserve(1));
-  chol_begin(K.A.p, n, K.info.p, s);
-  if (T.nblk())
-    hipLaunchKernelGGL(k_chol_fill_blocks, dim3(div_up(blocks_6x6(T.nblk()), 256)), dim3(256), 0, s, ns, T.nblk(),
-                       T.pair_ij.p, N.Sdiag.p, N.Soff.p, N.rhs.p, chol_padded(n), K.A.p);
-  schur_cam_fill_chol(ns, ncs, Cm.B.p, Cm.Scam.p, Cm.rhs.p, chol_padded(n), K.A.p, s);
-  chol_factor_solve(K.A.p, n, K.info.p, d_delta, d_info, s);
+// the host forms pcd_ba_schur and pcd_ba_schur_cam behind their handle guard and null check: schur_device into the
+// handle's own buffers and a staged dense S, then every requested output copied back
+static pcd_status schur_host(pcd_ba* b, int ncs, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o,
+                             const pcd_ba_schur_cam_out* co) {
+  PCD_TRY(schur_build(b, nullptr));
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; BaSchur::Cam& K = b->schur->cam;
+  const size_t n0 = slot_vec(T.ns), nc = (size_t)kCamS * ncs, n = n0 + nc;
+  DevBuf<double>& dense = ncs ? K.dense : N.dense;
+  pcd_ba_schur_out d{}; const pcd_ba_schur_cam_out dc{};
+  if (o->S) { PCD_TRY(dense.reserve(at_least_1(n * n))); d.S = dense.p; }
+  PCD_TRY(schur_device(b, ncs, opt, &d, &dc, nullptr));
+  PCD_TRY(copy_back(o->cost, N.cost, 1)); PCD_TRY(copy_back(o->num_skipped, N.skip_cnt, 1));
+  PCD_TRY(copy_back(o->S_diag, N.Sdiag, blocks_6x6(T.ns))); PCD_TRY(copy_back(o->S_off, N.Soff, blocks_6x6(T.npairs)));
+  PCD_TRY(copy_back(o->rhs, N.rhs, n0));
+  if (ncs) {
+    PCD_TRY(copy_back(co->B, K.B, (size_t)T.ns * nc * 6)); PCD_TRY(copy_back(co->S_cam, K.Scam, nc * nc));
+    PCD_TRY(copy_back(co->rhs_cam, K.rhs, nc));
+  }
+  PCD_TRY(copy_back(o->S, dense, n * n));
+  PCD_HIP_TRY(hipDeviceSynchronize());
+  return PCD_OK;
+}
+
+// pcd_ba_schur[_cam]_back_substitute_device.  d_delta: dpose [6 ns], then dcam [12 ncs]
+static pcd_status back_substitute_device(pcd_ba* b, bool cam, const double* d_delta, double* d_dpoint,
+                                         double* d_model_decrease, void* stream) {
+  int ncs;
+  PCD_TRY(schur_guard(b, cam, &ncs));
+  const char* fn = ncs ? "pcd_ba_schur_cam_back_substitute_device" : "pcd_ba_schur_back_substitute_device";
+  hipStream_t s = (hipStream_t)stream;
+  PCD_TRY(refuse_capture(s, fn));
+  PCD_TRY(schur_state_guard(b, fn, false, ncs));
+  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; const BaSchur::Cam& K = b->schur->cam;
+  // a zero-length array may be NULL (an empty torch tensor has data_ptr() 0): ns = 0 when every pose is constant
+  PCD_REQUIRE((d_delta || (T.ns == 0 && !ncs)) && (d_dpoint || b->P == 0), "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  const int P = b->P; const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
+  const double* d_dcam = d_delta + slot_vec(T.ns);
+  ScopedKernelTimer t("ba_schur_back", s);
+  if (ncs) {
+    const SchurCamBack kb{P, ncs, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p, T.obs_pos.p, T.img_slot.p,
+                          N.Wim.p, N.Vinv.p, N.gpt.p, N.Dpt.p, K.Wc.p, K.active.p};
+    schur_cam_back(kb, d_delta, d_dcam, d_dpoint, N.md_partial.p, s);
+  } else {
+    hipLaunchKernelGGL(k_schur_back, dim3(nbp), dim3(256), 0, s, P, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p,
+                       T.obs_pos.p, T.img_slot.p, N.Wim.p, N.Vinv.p, N.gpt.p, N.Dpt.p, d_delta, d_dpoint, N.md_partial.p);
+  }
+  if (d_model_decrease) {
+    hipLaunchKernelGGL(k_schur_model_decrease, dim3(1), dim3(256), 0, s, T.ns, T.slot_img.p, b->const_tvec(), N.gimg.p,
+                       N.Dimg.p, d_delta, N.md_partial.p, (int)nbp, d_model_decrease);
+    if (ncs) schur_cam_model_decrease(ncs, K.slot_cam.p, K.active.p, K.gcam.p, K.D.p, d_dcam, d_model_decrease, s);
+  }
+  PCD_HIP_TRY(hipGetLastError());
+  return PCD_OK;
+}
+
+// pcd_ba_plus[_cam]_device.  d_cam_params_out (null from the plain call): the camera parameters with dcam added on the
+// active ones; without camera slots a copy of the handle's, outside the ba_plus scope
+static pcd_status plus_device(pcd_ba* b, bool cam, const double* d_delta, const double* d_dpoint, double* d_poses_out,
+                              double* d_points_out, double* d_cam_params_out, void* stream) {
+  int ncs;
+  PCD_TRY(schur_guard(b, cam, &ncs));
+  hipStream_t s = (hipStream_t)stream;
+  PCD_TRY(refuse_capture(s, ncs ? "pcd_ba_plus_cam_device" : "pcd_ba_plus_device"));
+  PCD_TRY(schur_build(b, s));
+  if (ncs) PCD_TRY(cam_upload_slots(b));
+  const BaSchur::Structure& T = b->schur->st; const BaSchur::Cam& K = b->schur->cam;
+  // zero-length arrays may be NULL (ns = 0 when every pose is constant)
+  PCD_REQUIRE((d_delta || (T.ns == 0 && !ncs)) && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) &&
+              (d_points_out || b->P == 0), "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  {
+    ScopedKernelTimer t("ba_plus", s);
+    hipLaunchKernelGGL(k_ba_plus, dim3(div_up((uint64_t)b->I + b->P, 256)), dim3(256), 0, s, b->I, b->P, T.img_slot.p,
+                       b->const_tvec(), b->const_points(), b->poses.p, b->points.p, d_delta, d_dpoint, d_poses_out,
+                       d_points_out);
+    if (ncs && d_cam_params_out)
+      ba_plus_cam(b->cam_params_len, K.param_cam.p, b->cam_off.p, K.cam_slot.p, K.active.p, b->cam_params.p,
+                  d_delta + slot_vec(T.ns), d_cam_params_out, s);
+    PCD_HIP_TRY(hipGetLastError());
+  }
+  if (!ncs && d_cam_params_out && d_cam_params_out != b->cam_params.p && b->cam_params_len)
+    PCD_HIP_TRY(hipMemcpyAsync(d_cam_params_out, b->cam_params.p, b->cam_params_len * sizeof(double),
+                               hipMemcpyDeviceToDevice, s));
+  return PCD_OK;
+}
+
+// pcd_ba_schur[_cam]_solve_pcg_device.  d_delta [6 ns + 12 ncs]
+static pcd_status solve_pcg_device(pcd_ba* b, bool cam, const pcd_ba_pcg_opts* opts, double* d_delta,
+                                   pcd_ba_pcg_info* d_info, void* stream) {
+  int ncs;
+  PCD_TRY(schur_guard(b, cam, &ncs)); PCD_TRY(pcg_check_opts(opts));
+  const char* fn = ncs ? "pcd_ba_schur_cam_solve_pcg_device" : "pcd_ba_schur_solve_pcg_device";
+  hipStream_t s = (hipStream_t)stream;
+  PCD_TRY(refuse_capture(s, fn));
+  PCD_TRY(schur_state_guard(b, fn, true, ncs));
+  PCD_REQUIRE(d_delta || (b->schur->st.ns == 0 && !ncs), "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  ScopedKernelTimer t("ba_schur_pcg", s);
+  PCD_TRY(pcg_begin(b, opts, ncs, s));
+  PCD_TRY(pcg_run(b, opts, ncs, 0, s));
+  pcg_finish(pcg_vec(b, ncs), d_delta, d_info, s);
+  PCD_HIP_TRY(hipGetLastError());
+  return PCD_OK;
+}
+
+// pcd_ba_schur[_cam]_solve_pcg: the device form into the handle's staging, then copied back
+static pcd_status solve_pcg_host(pcd_ba* b, bool cam, const pcd_ba_pcg_opts* opts, double* delta, pcd_ba_pcg_info* info) {
+  int ncs;
+  PCD_TRY(schur_guard(b, cam, &ncs)); PCD_TRY(pcg_check_opts(opts));
+  PCD_TRY(schur_state_guard(b, ncs ? "pcd_ba_schur_cam_solve_pcg" : "pcd_ba_schur_solve_pcg", true, ncs));
+  BaSchur::Pcg& C = b->schur->cg;
+  const size_t n = slot_vec(b->schur->st.ns) + (size_t)kCamS * ncs;
+  PCD_REQUIRE(delta || n == 0, "null pointer");
+  PCD_TRY(C.out.reserve(at_least_1(n))); PCD_TRY(C.info.reserve(1));
+  PCD_TRY(solve_pcg_device(b, cam, opts, C.out.p, C.info.p, nullptr));
+  PCD_TRY(copy_back(delta, C.out, n)); PCD_TRY(copy_back(info, C.info, 1));
+  PCD_HIP_TRY(hipDeviceSynchronize());
+  return PCD_OK;
+}
+
+// pcd_ba_schur[_cam]_solve_cholesky_device.  The caller's dense system (d_S, d_rhs) is the plain call's alone
+static pcd_status solve_cholesky_device(pcd_ba* b, bool cam, const double* d_S, const double* d_rhs, double* d_delta,
+                                        pcd_ba_chol_info* d_info, void* stream) {
+  int ncs;
+  PCD_TRY(schur_guard(b, cam, &ncs));
+  PCD_REQUIRE(!d_S == !d_rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
+  const char* fn = ncs ? "pcd_ba_schur_cam_solve_cholesky_device" : "pcd_ba_schur_solve_cholesky_device";
+  hipStream_t s = (hipStream_t)stream;
+  PCD_TRY(refuse_capture(s, fn));
+  if (d_S) PCD_TRY(schur_build(b, s));
+  else PCD_TRY(schur_state_guard(b, fn, true, ncs));
+  const int ns = b->schur->st.ns;
+  PCD_REQUIRE(d_delta || (ns == 0 && !ncs), "null pointer");
+  PCD_HIP_TRY(hipSetDevice(b->device));
+  if (ns == 0 && !ncs) {   // nothing to solve, nothing launched
+    if (d_info) {
+      pcd_ba_chol_info o{}; o.status = PCD_CHOL_OK; o.failed_column = -1;
+      PCD_HIP_TRY(hipMemcpyAsync(d_info, &o, sizeof o, hipMemcpyHostToDevice, s));
+      PCD_HIP_TRY(hipStreamSynchronize(s));   // o leaves scope
+    }
+    return PCD_OK;
+  }
+  ScopedKernelTimer t("ba_schur_cholesky", s);
+  PCD_TRY(chol_solve(b, ncs, d_S, d_rhs, d_delta, d_info, s));
+  PCD_HIP_TRY(hipGetLastError());
   return PCD_OK;
 }
 
@@ -1271,63 +1089,26 @@ pcd_status pcd_ba_schur_stats(pcd_ba* b, pcd_ba_schur_info* info) {
 pcd_status pcd_ba_schur_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o, void* stream) {
   return pcd::guard([&]() -> pcd_status {
     PCD_TRY(schur_guard(b));
-    return schur_device(b, opt, o, stream, "pcd_ba_schur_device");
+    return schur_device(b, 0, opt, o, nullptr, stream);
   });
 }
 
 pcd_status pcd_ba_schur(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_out* o) {
   return pcd::guard([&]() -> pcd_status {
     PCD_TRY(schur_guard(b)); PCD_REQUIRE(opt && o, "null pointer");
-    PCD_TRY(schur_build(b, nullptr));
-    const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
-    const size_t n = slot_vec(T.ns);
-    pcd_ba_schur_out d{};
-    if (o->S) { PCD_TRY(N.dense.reserve(at_least_1(n * n))); d.S = N.dense.p; }
-    PCD_TRY(pcd_ba_schur_device(b, opt, &d, nullptr));
-    PCD_TRY(copy_back(o->cost, N.cost, 1)); PCD_TRY(copy_back(o->num_skipped, N.skip_cnt, 1));
-    PCD_TRY(copy_back(o->S_diag, N.Sdiag, blocks_6x6(T.ns))); PCD_TRY(copy_back(o->S_off, N.Soff, blocks_6x6(T.npairs)));
-    PCD_TRY(copy_back(o->rhs, N.rhs, n)); PCD_TRY(copy_back(o->S, N.dense, n * n));
-    PCD_HIP_TRY(hipDeviceSynchronize());
-    return PCD_OK;
+    return schur_host(b, 0, opt, o, nullptr);
   });
 }
 
 pcd_status pcd_ba_schur_back_substitute_device(pcd_ba* b, const double* d_dpose, double* d_dpoint,
                                                double* d_model_decrease, void* stream) {
-  PCD_TRY(schur_guard(b));
-  PCD_REFUSE_CAPTURE(stream);
-  PCD_TRY(schur_state_guard(b, "pcd_ba_schur_back_substitute_device", false));
-  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num;
-  // a zero-length array may be NULL (an empty torch tensor has data_ptr() 0): ns = 0 when every pose is constant
-  PCD_REQUIRE((d_dpose || T.ns == 0) && (d_dpoint || b->P == 0), "null pointer");
-  PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
-  const int P = b->P; const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
-  ScopedKernelTimer t("ba_schur_back", s);
-  hipLaunchKernelGGL(k_schur_back, dim3(nbp), dim3(256), 0, s, P, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p,
-                     T.obs_pos.p, T.img_slot.p, N.Wim.p, N.Vinv.p, N.gpt.p, N.Dpt.p, d_dpose, d_dpoint, N.md_partial.p);
-  if (d_model_decrease)
-    hipLaunchKernelGGL(k_schur_model_decrease, dim3(1), dim3(256), 0, s, T.ns, T.slot_img.p, b->const_tvec(), N.gimg.p,
-                       N.Dimg.p, d_dpose, N.md_partial.p, (int)nbp, d_model_decrease);
-  PCD_HIP_TRY(hipGetLastError());
-  return PCD_OK;
+  return back_substitute_device(b, false, d_dpose, d_dpoint, d_model_decrease, stream);
 }
 
 pcd_status pcd_ba_plus_device(pcd_ba* b, const double* d_dpose, const double* d_dpoint, double* d_poses_out,
                               double* d_points_out, void* stream) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b));
-    PCD_REFUSE_CAPTURE(stream);
-    PCD_TRY(schur_build(b, (hipStream_t)stream));
-    // zero-length arrays may be NULL (ns = 0 when every pose is constant)
-    PCD_REQUIRE((d_dpose || b->schur->st.ns == 0) && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) &&
-                (d_points_out || b->P == 0), "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
-    ScopedKernelTimer t("ba_plus", s);
-    hipLaunchKernelGGL(k_ba_plus, dim3(div_up((uint64_t)b->I + b->P, 256)), dim3(256), 0, s, b->I, b->P,
-                       b->schur->st.img_slot.p, b->const_tvec(), b->const_points(), b->poses.p, b->points.p, d_dpose,
-                       d_dpoint, d_poses_out, d_points_out);
-    PCD_HIP_TRY(hipGetLastError());
-    return PCD_OK;
+    return plus_device(b, false, d_dpose, d_dpoint, d_poses_out, d_points_out, nullptr, stream);
   });
 }
 
@@ -1340,60 +1121,16 @@ void pcd_ba_pcg_opts_default(pcd_ba_pcg_opts* o) {
 
 pcd_status pcd_ba_schur_solve_pcg_device(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* d_dpose,
                                          pcd_ba_pcg_info* d_info, void* stream) {
-  return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b)); PCD_TRY(pcg_check_opts(opts));
-    PCD_REFUSE_CAPTURE(stream);
-    PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_pcg_device", true));
-    PCD_REQUIRE(d_dpose || b->schur->st.ns == 0, "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
-    ScopedKernelTimer t("ba_schur_pcg", s);
-    PCD_TRY(pcg_begin(b, opts, false, s));
-    PCD_TRY(pcg_run(b, opts, false, 0, s));
-    pcg_finish(b, false, d_dpose, d_info, s);
-    PCD_HIP_TRY(hipGetLastError());
-    return PCD_OK;
-  });
+  return pcd::guard([&]() -> pcd_status { return solve_pcg_device(b, false, opts, d_dpose, d_info, stream); });
 }
 
 pcd_status pcd_ba_schur_solve_pcg(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* dpose, pcd_ba_pcg_info* info) {
-  return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b)); PCD_TRY(pcg_check_opts(opts));
-    PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_pcg", true));
-    BaSchur::Pcg& C = b->schur->cg;
-    const size_t n = slot_vec(b->schur->st.ns);
-    PCD_REQUIRE(dpose || n == 0, "null pointer");
-    PCD_TRY(C.out.reserve(at_least_1(n))); PCD_TRY(C.info.reserve(1));
-    PCD_TRY(pcd_ba_schur_solve_pcg_device(b, opts, C.out.p, C.info.p, nullptr));
-    PCD_TRY(copy_back(dpose, C.out, n)); PCD_TRY(copy_back(info, C.info, 1));
-    PCD_HIP_TRY(hipDeviceSynchronize());
-    return PCD_OK;
-  });
+  return pcd::guard([&]() -> pcd_status { return solve_pcg_host(b, false, opts, dpose, info); });
 }
 
 pcd_status pcd_ba_schur_solve_cholesky_device(pcd_ba* b, const double* d_S, const double* d_rhs, double* d_dpose,
                                               pcd_ba_chol_info* d_info, void* stream) {
-  return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_guard(b));
-    PCD_REQUIRE(!d_S == !d_rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
-    PCD_REFUSE_CAPTURE(stream);
-    if (d_S) PCD_TRY(schur_build(b, (hipStream_t)stream));
-    else PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_cholesky_device", true));
-    const int ns = b->schur->st.ns;
-    PCD_REQUIRE(d_dpose || ns == 0, "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
-    if (ns == 0) {   // nothing to solve, nothing launched
-      if (d_info) {
-        pcd_ba_chol_info o{}; o.status = PCD_CHOL_OK; o.failed_column = -1;
-        PCD_HIP_TRY(hipMemcpyAsync(d_info, &o, sizeof o, hipMemcpyHostToDevice, s));
-        PCD_HIP_TRY(hipStreamSynchronize(s));   // o leaves scope
-      }
-      return PCD_OK;
-    }
-    ScopedKernelTimer t("ba_schur_cholesky", s);
-    PCD_TRY(chol_solve(b, d_S, d_rhs, d_dpose, d_info, s));
-    PCD_HIP_TRY(hipGetLastError());
-    return PCD_OK;
-  });
+  return pcd::guard([&]() -> pcd_status { return solve_cholesky_device(b, false, d_S, d_rhs, d_dpose, d_info, stream); });
 }
 
 pcd_status pcd_ba_schur_solve_cholesky(pcd_ba* b, const double* Sh, const double* rhs, double* dpose,
@@ -1402,7 +1139,7 @@ pcd_status pcd_ba_schur_solve_cholesky(pcd_ba* b, const double* Sh, const double
     PCD_TRY(schur_guard(b));
     PCD_REQUIRE(!Sh == !rhs, "S and rhs: give both (caller's dense system) or neither (the handle's own blocks)");
     if (Sh) PCD_TRY(schur_build(b, nullptr));
-    else PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_cholesky", true));
+    else PCD_TRY(schur_state_guard(b, "pcd_ba_schur_solve_cholesky", true, 0));
     BaSchur::Chol& K = b->schur->chol;
     const size_t n = slot_vec(b->schur->st.ns);
     PCD_REQUIRE(dpose || n == 0, "null pointer");
@@ -1437,144 +1174,44 @@ pcd_status pcd_ba_camera_slots(pcd_ba* b, int32_t* camera_slot, int32_t* num_slo
 
 pcd_status pcd_ba_schur_cam_device(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_cam_out* o, void* stream) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_cam_guard(b));
-    if (cam_slots(b)) return schur_cam_device(b, opt, o, stream);
-    PCD_REQUIRE(opt && o, "null pointer");
-    pcd_ba_schur_out po{};
-    po.cost = o->cost; po.S_diag = o->S_diag; po.S_off = o->S_off; po.rhs = o->rhs; po.S = o->S;
-    po.num_skipped = o->num_skipped;
-    return pcd_ba_schur_device(b, opt, &po, stream);
+    int ncs;
+    PCD_TRY(schur_guard(b, true, &ncs)); PCD_REQUIRE(opt && o, "null pointer");
+    const pcd_ba_schur_out po = pose_out(*o);
+    return schur_device(b, ncs, opt, &po, o, stream);
   });
 }
 
 pcd_status pcd_ba_schur_cam(pcd_ba* b, const pcd_ba_schur_opts* opt, const pcd_ba_schur_cam_out* o) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_cam_guard(b)); PCD_REQUIRE(opt && o, "null pointer");
-    if (!cam_slots(b)) {
-      pcd_ba_schur_out po{};
-      po.cost = o->cost; po.S_diag = o->S_diag; po.S_off = o->S_off; po.rhs = o->rhs; po.S = o->S;
-      po.num_skipped = o->num_skipped;
-      return pcd_ba_schur(b, opt, &po);
-    }
-    PCD_TRY(schur_build(b, nullptr));
-    const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; BaSchur::Cam& K = b->schur->cam;
-    const size_t n0 = slot_vec(T.ns), nc = (size_t)kCamS * cam_slots(b), n = n0 + nc;
-    pcd_ba_schur_cam_out d{};
-    if (o->S) { PCD_TRY(K.dense.reserve(n * n)); d.S = K.dense.p; }
-    PCD_TRY(schur_cam_device(b, opt, &d, nullptr));
-    PCD_TRY(copy_back(o->cost, N.cost, 1)); PCD_TRY(copy_back(o->num_skipped, N.skip_cnt, 1));
-    PCD_TRY(copy_back(o->S_diag, N.Sdiag, blocks_6x6(T.ns))); PCD_TRY(copy_back(o->S_off, N.Soff, blocks_6x6(T.npairs)));
-    PCD_TRY(copy_back(o->rhs, N.rhs, n0)); PCD_TRY(copy_back(o->B, K.B, (size_t)T.ns * nc * 6));
-    PCD_TRY(copy_back(o->S_cam, K.Scam, nc * nc)); PCD_TRY(copy_back(o->rhs_cam, K.rhs, nc));
-    PCD_TRY(copy_back(o->S, K.dense, n * n));
-    PCD_HIP_TRY(hipDeviceSynchronize());
-    return PCD_OK;
+    int ncs;
+    PCD_TRY(schur_guard(b, true, &ncs)); PCD_REQUIRE(opt && o, "null pointer");
+    const pcd_ba_schur_out po = pose_out(*o);
+    return schur_host(b, ncs, opt, &po, o);
   });
 }
 
 pcd_status pcd_ba_schur_cam_solve_cholesky_device(pcd_ba* b, double* d_delta, pcd_ba_chol_info* d_info, void* stream) {
-  return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_cam_guard(b));
-    if (!cam_slots(b)) return pcd_ba_schur_solve_cholesky_device(b, nullptr, nullptr, d_delta, d_info, stream);
-    PCD_REFUSE_CAPTURE(stream);
-    PCD_TRY(schur_cam_state_guard(b, "pcd_ba_schur_cam_solve_cholesky_device", true));
-    PCD_REQUIRE(d_delta, "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
-    ScopedKernelTimer t("ba_schur_cholesky", s);
-    PCD_TRY(chol_solve_cam(b, d_delta, d_info, s));
-    PCD_HIP_TRY(hipGetLastError());
-    return PCD_OK;
-  });
+  return pcd::guard([&]() -> pcd_status { return solve_cholesky_device(b, true, nullptr, nullptr, d_delta, d_info, stream); });
 }
 
 pcd_status pcd_ba_schur_cam_solve_pcg_device(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* d_delta,
                                              pcd_ba_pcg_info* d_info, void* stream) {
-  return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_cam_guard(b));
-    if (!cam_slots(b)) return pcd_ba_schur_solve_pcg_device(b, opts, d_delta, d_info, stream);
-    PCD_TRY(pcg_check_opts(opts));
-    PCD_REFUSE_CAPTURE(stream);
-    PCD_TRY(schur_cam_state_guard(b, "pcd_ba_schur_cam_solve_pcg_device", true));
-    PCD_REQUIRE(d_delta, "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
-    ScopedKernelTimer t("ba_schur_pcg", s);
-    PCD_TRY(pcg_begin(b, opts, true, s));
-    PCD_TRY(pcg_run(b, opts, true, 0, s));
-    pcg_finish(b, true, d_delta, d_info, s);
-    PCD_HIP_TRY(hipGetLastError());
-    return PCD_OK;
-  });
+  return pcd::guard([&]() -> pcd_status { return solve_pcg_device(b, true, opts, d_delta, d_info, stream); });
 }
 
 pcd_status pcd_ba_schur_cam_solve_pcg(pcd_ba* b, const pcd_ba_pcg_opts* opts, double* delta, pcd_ba_pcg_info* info) {
-  return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_cam_guard(b));
-    if (!cam_slots(b)) return pcd_ba_schur_solve_pcg(b, opts, delta, info);
-    PCD_TRY(pcg_check_opts(opts));
-    PCD_TRY(schur_cam_state_guard(b, "pcd_ba_schur_cam_solve_pcg", true));
-    PCD_REQUIRE(delta, "null pointer");
-    BaSchur::Pcg& C = b->schur->cg;
-    const size_t n = slot_vec(b->schur->st.ns) + (size_t)kCamS * cam_slots(b);
-    PCD_TRY(C.out.reserve(n)); PCD_TRY(C.info.reserve(1));
-    PCD_TRY(pcd_ba_schur_cam_solve_pcg_device(b, opts, C.out.p, C.info.p, nullptr));
-    PCD_TRY(copy_back(delta, C.out, n)); PCD_TRY(copy_back(info, C.info, 1));
-    PCD_HIP_TRY(hipDeviceSynchronize());
-    return PCD_OK;
-  });
+  return pcd::guard([&]() -> pcd_status { return solve_pcg_host(b, true, opts, delta, info); });
 }
 
 pcd_status pcd_ba_schur_cam_back_substitute_device(pcd_ba* b, const double* d_delta, double* d_dpoint,
                                                    double* d_model_decrease, void* stream) {
-  PCD_TRY(schur_cam_guard(b));
-  if (!cam_slots(b)) return pcd_ba_schur_back_substitute_device(b, d_delta, d_dpoint, d_model_decrease, stream);
-  PCD_REFUSE_CAPTURE(stream);
-  PCD_TRY(schur_cam_state_guard(b, "pcd_ba_schur_cam_back_substitute_device", false));
-  const BaSchur::Structure& T = b->schur->st; BaSchur::Numeric& N = b->schur->num; const BaSchur::Cam& K = b->schur->cam;
-  PCD_REQUIRE(d_delta && (d_dpoint || b->P == 0), "null pointer");
-  PCD_HIP_TRY(hipSetDevice(b->device)); hipStream_t s = (hipStream_t)stream;
-  const int P = b->P, ncs = cam_slots(b); const unsigned nbp = std::max(1u, div_up((uint64_t)P, 256));
-  const double* d_dcam = d_delta + slot_vec(T.ns);
-  ScopedKernelTimer t("ba_schur_back", s);
-  const SchurCamBack kb{P, ncs, b->pt_obs_start.p, b->pt_obs_list.p, b->obs_image.p, T.obs_pos.p, T.img_slot.p,
-                        N.Wim.p, N.Vinv.p, N.gpt.p, N.Dpt.p, K.Wc.p, K.active.p};
-  schur_cam_back(kb, d_delta, d_dcam, d_dpoint, N.md_partial.p, s);
-  if (d_model_decrease) {
-    hipLaunchKernelGGL(k_schur_model_decrease, dim3(1), dim3(256), 0, s, T.ns, T.slot_img.p, b->const_tvec(), N.gimg.p,
-                       N.Dimg.p, d_delta, N.md_partial.p, (int)nbp, d_model_decrease);
-    schur_cam_model_decrease(ncs, K.slot_cam.p, K.active.p, K.gcam.p, K.D.p, d_dcam, d_model_decrease, s);
-  }
-  PCD_HIP_TRY(hipGetLastError());
-  return PCD_OK;
+  return back_substitute_device(b, true, d_delta, d_dpoint, d_model_decrease, stream);
 }
 
 pcd_status pcd_ba_plus_cam_device(pcd_ba* b, const double* d_delta, const double* d_dpoint, double* d_poses_out,
                                   double* d_points_out, double* d_cam_params_out, void* stream) {
   return pcd::guard([&]() -> pcd_status {
-    PCD_TRY(schur_cam_guard(b));
-    hipStream_t s = (hipStream_t)stream;
-    if (!cam_slots(b)) {
-      PCD_TRY(pcd_ba_plus_device(b, d_delta, d_dpoint, d_poses_out, d_points_out, stream));
-      if (d_cam_params_out && d_cam_params_out != b->cam_params.p && b->cam_params_len)
-        PCD_HIP_TRY(hipMemcpyAsync(d_cam_params_out, b->cam_params.p, b->cam_params_len * sizeof(double),
-                                   hipMemcpyDeviceToDevice, s));
-      return PCD_OK;
-    }
-    PCD_REFUSE_CAPTURE(stream);
-    PCD_TRY(schur_build(b, s));
-    PCD_TRY(cam_upload_slots(b));
-    const BaSchur::Structure& T = b->schur->st; const BaSchur::Cam& K = b->schur->cam;
-    PCD_REQUIRE(d_delta && (d_dpoint || b->P == 0) && (d_poses_out || b->I == 0) && (d_points_out || b->P == 0),
-                "null pointer");
-    PCD_HIP_TRY(hipSetDevice(b->device));
-    ScopedKernelTimer t("ba_plus", s);
-    hipLaunchKernelGGL(k_ba_plus, dim3(div_up((uint64_t)b->I + b->P, 256)), dim3(256), 0, s, b->I, b->P, T.img_slot.p,
-                       b->const_tvec(), b->const_points(), b->poses.p, b->points.p, d_delta, d_dpoint, d_poses_out,
-                       d_points_out);
-    if (d_cam_params_out)
-      ba_plus_cam(b->cam_params_len, K.param_cam.p, b->cam_off.p, K.cam_slot.p, K.active.p, b->cam_params.p,
-                  d_delta + slot_vec(T.ns), d_cam_params_out, s);
-    PCD_HIP_TRY(hipGetLastError());
-    return PCD_OK;
+    return plus_device(b, true, d_delta, d_dpoint, d_poses_out, d_points_out, d_cam_params_out, stream);
   });
 }
 
@@ -1600,8 +1237,8 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
                         pcd_ba_solve_iteration* iterations) {
   return pcd::guard([&]() -> pcd_status {
     // refine_intrinsics: the camera rows ride along (pcd_ba_schur_cam*); without camera slots the flag changes nothing
-    const int ncs = (opts && opts->refine_intrinsics && b) ? cam_slots(b) : 0;
-    PCD_TRY(ncs ? schur_cam_guard(b) : schur_guard(b)); PCD_TRY(lm_check_opts(opts));
+    int ncs;
+    PCD_TRY(schur_guard(b, opts && opts->refine_intrinsics, &ncs)); PCD_TRY(lm_check_opts(opts));
     const bool cam = ncs > 0;
     if (cam && opts->linear_solver == PCD_LINEAR_PCG) {
       set_error("pcd_ba_solve: refine_intrinsics needs linear_solver = PCD_LINEAR_CHOLESKY or PCD_LINEAR_PCG_CAM "
@@ -1630,21 +1267,16 @@ pcd_status pcd_ba_solve(pcd_ba* b, const pcd_ba_solve_opts* opts, pcd_ba_solve_s
     for (int it = 0; it < opts->max_num_iterations; ++it) {
       if (radius < opts->min_radius) { sm.termination = PCD_SOLVE_MIN_RADIUS; break; }
       pcd_ba_schur_opts so{}; so.mu = 1.0 / radius; so.damping = opts->damping;
-      if (cam) {
-        pcd_ba_schur_cam_out none{};
-        PCD_TRY(schur_cam_device(b, &so, &none, s));
-      } else {
-        pcd_ba_schur_out none{};
-        PCD_TRY(pcd_ba_schur_device(b, &so, &none, s));
-      }
+      const pcd_ba_schur_out none{}; const pcd_ba_schur_cam_out none_cam{};   // everything stays in the handle
+      PCD_TRY(schur_device(b, ncs, &so, &none, &none_cam, s));
       hipLaunchKernelGGL(k_ba_grad_max, dim3(ngp), dim3(256), 0, s, S.st.ns, S.st.slot_img.p, b->const_tvec(), S.num.gimg.p,
                          b->P, b->const_points(), S.num.gpt.p, M.gpart.p);
       if (cam) ba_cam_grad_max(ncs, S.cam.slot_cam.p, S.cam.active.p, S.cam.gcam.p, M.gpart.p + ngp, s);
       int enq = 0;
       PCD_HIP_TRY(ev.start(s));
-      PCD_TRY(lm_enqueue_linear(b, opts, cam, &enq, s));
+      PCD_TRY(lm_enqueue_linear(b, opts, ncs, &enq, s));
       PCD_HIP_TRY(ev.stop(s));
-      PCD_TRY(lm_try_step(b, opts, cam, enq, ngr, ev, &sm.linear_solver_ms, s));
+      PCD_TRY(lm_try_step(b, opts, ncs, enq, ngr, ev, &sm.linear_solver_ms, s));
       const LmRecord& rec = *M.host.p;
       if (it == 0) sm.initial_cost = sm.final_cost = rec.cost;
       const LmDecision d = lm_decide(rec, *opts, radius, factor, opts->linear_solver == PCD_LINEAR_CHOLESKY);

@@ -56,9 +56,54 @@ void schur_cam_border(const SchurCamIn& in, const SchurCamOut& out, hipStream_t 
 // (leading dimension np); the pose part is k_chol_fill_blocks'
 void schur_cam_fill_chol(int ns, int ncs, const double* B, const double* Scam, const double* rhs_cam, int np, double* A,
                          hipStream_t s);
-// dense S [n][n], n = 6 ns + 12 ncs, both triangles, from the pose blocks and the camera blocks; the caller zeroed it
-void schur_cam_dense(int ns, int ncs, uint32_t nblk, const uint32_t* pair_ij, const double* Sdiag, const double* Soff,
-                     const double* B, const double* Scam, double* S, hipStream_t s);
+// B (on both sides of the diagonal) and S_cam into the dense S [n][n], n = 6 ns + 12 ncs; the pose blocks are
+// k_schur_dense's (ba_solve.hip) with the leading dimension n
+void schur_cam_dense(int ns, int ncs, const double* B, const double* Scam, double* S, hipStream_t s);
+// The back-substitution of k_schur_back (ba_solve.hip) and k_schur_cam_back, thread = point:
+//   delta X_p = -V^-1 (g_p + sum_{a in p} W_a^T dpose[slot(a)] + cam_term),
+// the observations in ascending caller order; then the workgroup's partial of the model decrease
+// -delta^T g + delta^T D delta over the points (fixed-order block sum).  cam_term(p, r0, r1, r2) adds the camera rows'
+// share to the three sums, behind the pose terms; the plain kernel's adds nothing.
+template <class CamTerm>
+__device__ __forceinline__ void schur_back_point(int P, const uint32_t* pt_start, const uint32_t* pt_list,
+                                                 const int* obs_image, const uint32_t* obs_pos, const int* img_slot,
+                                                 const double* Wim, const double* Vinv, const double* gpt,
+                                                 const double* Dpt, const double* dpose, double* dpoint,
+                                                 double* md_partial, CamTerm cam_term) {
+  __shared__ double s_m[4];
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  double md = 0.0;
+  if (p < P) {
+    const double* g = gpt + 3 * (size_t)p;
+    double r0 = g[0], r1 = g[1], r2 = g[2];
+    for (uint32_t k = pt_start[p]; k < pt_start[p + 1]; ++k) {
+      const uint32_t o = pt_list[k];
+      const int s = img_slot[obs_image[o]];
+      if (s < 0) continue;
+      const double* w = Wim + 18 * (size_t)obs_pos[o];
+      const double* dc = dpose + 6 * (size_t)s;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const double c = dc[a];
+        r0 += w[3 * a] * c; r1 += w[3 * a + 1] * c; r2 += w[3 * a + 2] * c;
+      }
+    }
+    cam_term(p, r0, r1, r2);
+    const double* v = Vinv + 9 * (size_t)p;
+    const double dx0 = -(v[0] * r0 + v[1] * r1 + v[2] * r2);
+    const double dx1 = -(v[3] * r0 + v[4] * r1 + v[5] * r2);
+    const double dx2 = -(v[6] * r0 + v[7] * r1 + v[8] * r2);
+    dpoint[3 * (size_t)p] = dx0; dpoint[3 * (size_t)p + 1] = dx1; dpoint[3 * (size_t)p + 2] = dx2;
+    const double* d = Dpt + 3 * (size_t)p;
+    md = -(dx0 * g[0] + dx1 * g[1] + dx2 * g[2]) + (d[0] * dx0 * dx0 + d[1] * dx1 * dx1 + d[2] * dx2 * dx2);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) md += __shfl_xor(md, off);
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = md;
+  __syncthreads();
+  if (threadIdx.x == 0) md_partial[blockIdx.x] = (s_m[0] + s_m[1]) + (s_m[2] + s_m[3]);
+}
+
 // k_schur_back with the Wc_p^T dcam term: dpoint [P][3] and the point partials of the model decrease [div_up(P, 256)]
 struct SchurCamBack {
   int P, ncs;
@@ -77,51 +122,5 @@ void ba_plus_cam(uint64_t len, const int* param_cam, const int* cam_off, const i
 // partial[0] = max |g_cam| over the active camera coordinates
 void ba_cam_grad_max(int ncs, const int* slot_cam, const uint8_t* active, const double* gcam, double* partial,
                      hipStream_t s);
-
-// ---- the bordered PCG (pcd_ba_schur_cam_solve_pcg*) ---------------------------------------------------
-// State and rule of a PCG solve, plain or bordered (the kernels of the plain one are ba_solve.hip's)
-struct PcgState {
-  double rho, alpha, beta, pw, q, rn2, bnorm, xr;
-  int k, done, term, xsel;
-  unsigned fallbacks; int pad;
-};
-struct PcgRule { int max_iterations, min_iterations; double q_tolerance, r_tolerance; };
-
-// sum over the workgroup (256 threads), every thread gets the result; fixed order: wavefront butterfly, then the 4 waves
-__device__ __forceinline__ double block_sum256(double v, double* lds4) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();   // lds4 may still be read from the previous call
-  if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-}
-// strided sum of partial[i * stride] (i < n) over one workgroup
-__device__ __forceinline__ double block_sum_strided(const double* __restrict__ partial, int n, int stride, double* lds4) {
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) a += partial[(size_t)i * stride];
-  return block_sum256(a, lds4);
-}
-
-// Vectors of the bordered solve: [6 ns pose | 12 ncs camera] in one buffer each, so that the plain kernels that only sum
-// partials (k_pcg_begin, k_pcg_step) and copy x (k_pcg_finish) serve both solves.
-struct PcgCamVec {
-  int ns, ncs;
-  const PcgState* st;
-  const double* B; const double* Scam; const double* rhs_cam;   // the handle's border, camera block and right-hand side
-  double* Minv_cam;                 // [ncs][12][12]
-  double* z; double* r; double* w;  // [6 ns + 12 ncs]
-  double* camw;                     // [12 ncs][ns]: B[i] p_i of every pose slot, entry-major
-  double* pw;                       // [ns + 12 ncs]: p_i . w_i of the pose slots, then p_e w_e of the camera coordinates
-  double* partial;                  // [nb + ncs][4], nb = max(1, div_up(ns, 256)): pose workgroups, then camera slots
-};
-// camera part of k_pcg_init: 12 x 12 block-Jacobi inverses, x = 0, r = rhs_cam, z = M^-1 r, directions 0, partial[nb + r]
-void pcg_cam_init(const PcgCamVec& v, int precond, double* x0, double* p0, double* p1, hipStream_t s);
-// one iteration's product: pose rows with the border (B crosses memory once), then the camera rows
-void pcg_cam_product(const PcgCamVec& v, const uint32_t* row_start, const uint32_t* row_blk, const uint32_t* row_col,
-                     const double* Sdiag, const double* Soff, const double* p_old, double* p_new, hipStream_t s);
-// k_pcg_update over both parts: pose workgroups, then one workgroup per camera slot
-void pcg_cam_update(const PcgCamVec& v, PcgState* st, const double* Minv, const double* rhs, const double* p,
-                    const double* x_old, double* x_new, hipStream_t s);
 
 }  // namespace pcd

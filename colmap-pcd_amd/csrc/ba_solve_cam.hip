@@ -229,65 +229,33 @@ __global__ __launch_bounds__(256) void k_chol_fill_cam(int ns, int ncs, const do
   }
 }
 
-// thread = entry of a pose block (as k_schur_dense, with the leading dimension of the bordered system), then of B
-// (written on both sides of the diagonal), then of the camera part
-__global__ __launch_bounds__(256) void k_schur_cam_dense(int ns, int ncs, uint32_t nblk, const uint32_t* __restrict__ pair_ij,
-                                                         const double* __restrict__ Sdiag, const double* __restrict__ Soff,
-                                                         const double* __restrict__ B, const double* __restrict__ Scam,
-                                                         double* __restrict__ S) {
+// thread = entry of B (written on both sides of the diagonal), then of the camera part; the pose blocks are
+// k_schur_dense's (ba_solve.hip)
+__global__ __launch_bounds__(256) void k_schur_cam_dense(int ns, int ncs, const double* __restrict__ B,
+                                                         const double* __restrict__ Scam, double* __restrict__ S) {
   const uint64_t t = blockIdx.x * (uint64_t)256 + threadIdx.x;
-  const uint64_t nP = (uint64_t)nblk * 36, nB = (uint64_t)ns * ncs * (kCamS * 6), nc = (uint64_t)kCamS * ncs;
+  const uint64_t nB = (uint64_t)ns * ncs * (kCamS * 6), nc = (uint64_t)kCamS * ncs;
   const size_t n0 = 6 * (size_t)ns, n = n0 + nc;
-  if (t < nP) {
-    const uint32_t blk = (uint32_t)(t / 36);
-    const int k = (int)(t - 36 * (uint64_t)blk), r = k / 6, s = k - 6 * (k / 6);
-    if (blk < (uint32_t)ns) {
-      S[(6 * (size_t)blk + r) * n + 6 * (size_t)blk + s] = Sdiag[36 * (size_t)blk + k];
-    } else {
-      const uint32_t pq = blk - (uint32_t)ns;
-      const size_t i = pair_ij[2 * (size_t)pq], j = pair_ij[2 * (size_t)pq + 1];
-      const double v = Soff[36 * (size_t)pq + k];
-      S[(6 * i + r) * n + 6 * j + s] = v;
-      S[(6 * j + s) * n + 6 * i + r] = v;
-    }
-  } else if (t < nP + nB) {
-    const uint64_t u = t - nP;
-    const int c = (int)(u % 6), a = (int)((u / 6) % kCamS);
-    const uint64_t ir = u / (6 * kCamS);
-    const size_t r = ir % ncs, i = ir / ncs;
-    const double v = B[u];
-    S[(n0 + kCamS * r + a) * n + 6 * i + c] = v;
-    S[(6 * i + c) * n + n0 + kCamS * r + a] = v;
-  } else if (t < nP + nB + nc * nc) {
-    const uint64_t u = t - nP - nB;
+  if (t < nB) {   // B [ns][ncs][12][6] = [ns][12 ncs][6]: entry (camera coordinate e, column c) of slot i
+    const uint64_t q = t / 6;
+    const size_t c = t - 6 * q, i = q / nc, e = q - i * nc;
+    const double v = B[t];
+    S[(n0 + e) * n + 6 * i + c] = v;
+    S[(6 * i + c) * n + n0 + e] = v;
+  } else if (t < nB + nc * nc) {
+    const uint64_t u = t - nB;
     const size_t row = u / nc, col = u - row * nc;
     S[(n0 + row) * n + n0 + col] = Scam[(((row / kCamS) * ncs + col / kCamS) * kCamS + row % kCamS) * kCamS + col % kCamS];
   }
 }
 
-// thread = point: delta X_p = -V^-1 (g_p + sum_{a in p} W_a^T dpose[slot(a)] + sum_r Wc_p[r]^T dcam[r]); k_schur_back
-// with the camera term (inactive camera coordinates count as 0 whatever the caller passed) and its model-decrease partial
+// thread = point: k_schur_back (schur_back_point) with the camera term sum_r Wc_p[r]^T dcam[r] behind the pose terms;
+// inactive camera coordinates count as 0 whatever the caller passed
 __global__ __launch_bounds__(256) void k_schur_cam_back(SchurCamBack kb, const double* __restrict__ dpose,
                                                         const double* __restrict__ dcam, double* __restrict__ dpoint,
                                                         double* __restrict__ md_partial) {
-  __shared__ double s_m[4];
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  double md = 0.0;
-  if (p < kb.P) {
-    const double* g = kb.gpt + 3 * (size_t)p;
-    double r0 = g[0], r1 = g[1], r2 = g[2];
-    for (uint32_t k = kb.pt_obs_start[p]; k < kb.pt_obs_start[p + 1]; ++k) {
-      const uint32_t o = kb.pt_obs_list[k];
-      const int s = kb.img_slot[kb.obs_image[o]];
-      if (s < 0) continue;
-      const double* w = kb.Wim + 18 * (size_t)kb.obs_pos[o];
-      const double* dc = dpose + 6 * (size_t)s;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        const double c = dc[a];
-        r0 += w[3 * a] * c; r1 += w[3 * a + 1] * c; r2 += w[3 * a + 2] * c;
-      }
-    }
+  schur_back_point(kb.P, kb.pt_obs_start, kb.pt_obs_list, kb.obs_image, kb.obs_pos, kb.img_slot, kb.Wim, kb.Vinv, kb.gpt,
+                   kb.Dpt, dpose, dpoint, md_partial, [&](int p, double& r0, double& r1, double& r2) {
     for (int r = 0; r < kb.ncs; ++r) {
       const double* w = kb.Wc + 36 * ((size_t)p * kb.ncs + r);
 #pragma unroll
@@ -296,19 +264,7 @@ __global__ __launch_bounds__(256) void k_schur_cam_back(SchurCamBack kb, const d
         r0 += w[3 * a] * c; r1 += w[3 * a + 1] * c; r2 += w[3 * a + 2] * c;
       }
     }
-    const double* v = kb.Vinv + 9 * (size_t)p;
-    const double dx0 = -(v[0] * r0 + v[1] * r1 + v[2] * r2);
-    const double dx1 = -(v[3] * r0 + v[4] * r1 + v[5] * r2);
-    const double dx2 = -(v[6] * r0 + v[7] * r1 + v[8] * r2);
-    dpoint[3 * (size_t)p] = dx0; dpoint[3 * (size_t)p + 1] = dx1; dpoint[3 * (size_t)p + 2] = dx2;
-    const double* d = kb.Dpt + 3 * (size_t)p;
-    md = -(dx0 * g[0] + dx1 * g[1] + dx2 * g[2]) + (d[0] * dx0 * dx0 + d[1] * dx1 * dx1 + d[2] * dx2 * dx2);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) md += __shfl_xor(md, off);
-  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = md;
-  __syncthreads();
-  if (threadIdx.x == 0) md_partial[blockIdx.x] = (s_m[0] + s_m[1]) + (s_m[2] + s_m[3]);
+  });
 }
 
 // one wavefront: the camera term of the model decrease onto what k_schur_model_decrease wrote
@@ -381,11 +337,9 @@ void schur_cam_fill_chol(int ns, int ncs, const double* B, const double* Scam, c
   hipLaunchKernelGGL(k_chol_fill_cam, dim3(div_up(n, 256)), dim3(256), 0, s, ns, ncs, B, Scam, rhs_cam, np, A);
 }
 
-void schur_cam_dense(int ns, int ncs, uint32_t nblk, const uint32_t* pair_ij, const double* Sdiag, const double* Soff,
-                     const double* B, const double* Scam, double* S, hipStream_t s) {
-  const uint64_t n = (uint64_t)nblk * 36 + (uint64_t)ns * ncs * (kCamS * 6) + (uint64_t)(kCamS * ncs) * (kCamS * ncs);
-  hipLaunchKernelGGL(k_schur_cam_dense, dim3(div_up(n, 256)), dim3(256), 0, s, ns, ncs, nblk, pair_ij, Sdiag, Soff, B,
-                     Scam, S);
+void schur_cam_dense(int ns, int ncs, const double* B, const double* Scam, double* S, hipStream_t s) {
+  const uint64_t n = (uint64_t)ns * ncs * (kCamS * 6) + (uint64_t)(kCamS * ncs) * (kCamS * ncs);
+  hipLaunchKernelGGL(k_schur_cam_dense, dim3(div_up(n, 256)), dim3(256), 0, s, ns, ncs, B, Scam, S);
 }
 
 void schur_cam_back(const SchurCamBack& k, const double* dpose, const double* dcam, double* dpoint, double* md_partial,

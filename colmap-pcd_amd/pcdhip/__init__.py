@@ -1428,6 +1428,13 @@ class BA:
         dev = torch.device("cuda", self.device)
         return torch, dev, torch.cuda.current_stream(dev).cuda_stream
 
+    def _schur_counts(self):
+        """(num_slots, num_pairs) of the co-visibility structure, cached until an edit drops the structure"""
+        if not hasattr(self, "_schur_dims"):
+            st = self.schur_structure()
+            self._schur_dims = (st["num_slots"], st["pairs"].shape[0])
+        return self._schur_dims
+
     def schur_structure(self):
         """co-visibility structure: dict(image_slot [I] int32 (-1 = constant pose), num_slots, pairs [num_pairs][2]
         int32 slot pairs i < j sharing an eliminated point, ascending)"""
@@ -1476,10 +1483,7 @@ class BA:
         tensors cost [1], S_diag [ns][6][6], S_off [num_pairs][6][6], rhs [ns][6], num_skipped [1] (int64) and, with
         dense=True, S [6 ns][6 ns]"""
         torch, dev, stream = self._torch()
-        if not hasattr(self, "_schur_dims"):
-            st = self.schur_structure()
-            self._schur_dims = (st["num_slots"], st["pairs"].shape[0])
-        ns, npair = self._schur_dims
+        ns, npair = self._schur_counts()
         f64 = dict(dtype=torch.float64, device=dev)
         shapes = dict(cost=(1,), S_diag=(ns, 6, 6), S_off=(npair, 6, 6), rhs=(ns, 6), S=(6 * ns, 6 * ns))
         out = {k: torch.empty(shapes[k], **f64) for k in want if k in shapes}
@@ -1522,18 +1526,13 @@ class BA:
         in the handle: want without them).  opts: pcg_opts() arguments.  Returns (dpose [ns][6] torch device tensor,
         info dict: iterations, termination, precond_fallbacks, rhs_norm, residual_norm, q, step_dot_residual)"""
         torch, dev, stream = self._torch()
-        if not hasattr(self, "_schur_dims"):
-            st = self.schur_structure()
-            self._schur_dims = (st["num_slots"], st["pairs"].shape[0])
-        ns = self._schur_dims[0]
+        ns = self._schur_counts()[0]
         if dpose is None:
             dpose = torch.empty((ns, 6), dtype=torch.float64, device=dev)
         d_info = torch.zeros(C.sizeof(BAPcgInfo), dtype=torch.uint8, device=dev)
         o = pcg_opts(**opts)
         _check(lib().pcd_ba_schur_solve_pcg_device(self._h, C.byref(o), _ptr(dpose), _ptr(d_info), C.c_void_p(stream)))
-        i = d_info.cpu().numpy().view(PCG_INFO_DTYPE)[0]
-        return dpose, {k: (float(i[k]) if PCG_INFO_DTYPE[k] == np.float64 else int(i[k]))
-                       for k in PCG_INFO_DTYPE.names if k != "pad"}
+        return dpose, _device_info(d_info, PCG_INFO_DTYPE)
 
     def schur_solve_pcg_host(self, **opts):
         """pcd_ba_schur_solve_pcg: the same solve with host outputs (numpy dpose [ns][6], info dict)"""
@@ -1551,10 +1550,7 @@ class BA:
         Returns (dpose [ns][6] torch device tensor -- zeros when the factorisation failed --, info dict: status,
         failed_column, n, n_padded, panels, min_pivot, max_pivot)"""
         torch, dev, stream = self._torch()
-        if not hasattr(self, "_schur_dims"):
-            st = self.schur_structure()
-            self._schur_dims = (st["num_slots"], st["pairs"].shape[0])
-        ns = self._schur_dims[0]
+        ns = self._schur_counts()[0]
         if S is not None:
             S = S.to(device=dev, dtype=torch.float64).contiguous()
             if tuple(S.shape) != (6 * ns, 6 * ns):
@@ -1571,9 +1567,7 @@ class BA:
         ps = None if S is None else _ptr(S if S.numel() else one)
         pr = None if rhs is None else _ptr(rhs if rhs.numel() else one)
         _check(lib().pcd_ba_schur_solve_cholesky_device(self._h, ps, pr, _ptr(dpose), _ptr(d_info), C.c_void_p(stream)))
-        i = d_info.cpu().numpy().view(CHOL_INFO_DTYPE)[0]
-        return dpose, {k: (float(i[k]) if CHOL_INFO_DTYPE[k] == np.float64 else int(i[k]))
-                       for k in CHOL_INFO_DTYPE.names if k != "pad"}
+        return dpose, _device_info(d_info, CHOL_INFO_DTYPE)
 
     def schur_solve_cholesky_host(self, S=None, rhs=None):
         """pcd_ba_schur_solve_cholesky, the host form of the C ABI that C and C++ callers use: the same solve with host
@@ -1649,9 +1643,7 @@ class BA:
         pad = torch.zeros(1, dtype=torch.float64, device=dev)   # n = 0: an empty tensor's pointer is null
         _check(lib().pcd_ba_schur_cam_solve_cholesky_device(self._h, _ptr(delta if n else pad), _ptr(d_info),
                                                             C.c_void_p(stream)))
-        i = d_info.cpu().numpy().view(CHOL_INFO_DTYPE)[0]
-        return delta, {k: (float(i[k]) if CHOL_INFO_DTYPE[k] == np.float64 else int(i[k]))
-                       for k in CHOL_INFO_DTYPE.names if k != "pad"}
+        return delta, _device_info(d_info, CHOL_INFO_DTYPE)
 
     def schur_cam_solve_pcg(self, delta=None, **opts):
         """bordered PCG on the system of the last schur_cam() call from the handle's own blocks (keep S_diag / S_off / rhs
@@ -1667,9 +1659,7 @@ class BA:
         o = pcg_opts(**opts)
         _check(lib().pcd_ba_schur_cam_solve_pcg_device(self._h, C.byref(o), _ptr(delta if n else pad), _ptr(d_info),
                                                        C.c_void_p(stream)))
-        i = d_info.cpu().numpy().view(PCG_INFO_DTYPE)[0]
-        return delta, {k: (float(i[k]) if PCG_INFO_DTYPE[k] == np.float64 else int(i[k]))
-                       for k in PCG_INFO_DTYPE.names if k != "pad"}
+        return delta, _device_info(d_info, PCG_INFO_DTYPE)
 
     def schur_cam_solve_pcg_host(self, **opts):
         """pcd_ba_schur_cam_solve_pcg: the same solve with host outputs (numpy delta [n], info dict)"""
@@ -1878,6 +1868,12 @@ def pcg_opts(max_iterations=None, min_iterations=None, preconditioner=None, q_to
     if r_tolerance is not None:
         o.r_tolerance = float(r_tolerance)
     return o
+
+
+def _device_info(d_info, dtype):
+    """a device info record (uint8 tensor; PCG_INFO_DTYPE or CHOL_INFO_DTYPE) as a dict of Python numbers"""
+    i = d_info.cpu().numpy().view(dtype)[0]
+    return {k: (float(i[k]) if dtype[k] == np.float64 else int(i[k])) for k in dtype.names if k != "pad"}
 
 
 def _pcg_info(i):

@@ -7,8 +7,8 @@ S_diag / S_off / pairs / rhs of ba_pcg_ref, B [ns][ncs][12][6], S_cam [ncs][ncs]
 
   pcg_cam               numpy's own summation order; `descending` walks the pose row lists, the slots of the camera-row sum
                         and the camera slots of the border term in descending order (the order-sensitivity switch)
-  pcg_cam_device_order  every sum in the order csrc/ba_pcg_cam.hip states for k_pcg_cam_init, k_pcg_cam_spmv,
-                        k_pcg_cam_rows and k_pcg_cam_update (and ba_solve.hip for the pose part), no fused multiply-add
+  pcg_cam_device_order  every sum in the order csrc/ba_pcg.hip states for k_pcg_cam_init, k_pcg_cam_spmv,
+                        k_pcg_cam_rows and k_pcg_cam_update (and for the plain kernels of the pose part), no fused multiply-add
   lm_cam_pcg            ba_schur_cam_ref.lm_cam with pcg_cam as its linear solver (a BREAKDOWN is a rejected step)
 With ncs = 0 the first two are ba_pcg_ref.pcg / pcg_device_order bit for bit.  Test infrastructure: small scenes only."""
 import numpy as np

@@ -137,7 +137,7 @@ def pcg(S_diag, S_off, pairs, rhs, max_iterations=100, min_iterations=0, precond
 # numpy's reductions (np.sum pairwise, BLAS mat-vec with fused multiply-adds) round in an order numpy chooses.  On the
 # ill-conditioned reduced systems a last-bit difference in a CG scalar grows by many orders of magnitude in x within a
 # few iterations, so a parity check at the level of the order sensitivity needs a reference whose every sum is in a
-# stated order.  pcg_device_order() is the same algorithm with the order csrc/ba_solve.hip documents: sums over the 6
+# stated order.  pcg_device_order() is the same algorithm with the order csrc/ba_pcg.hip documents: sums over the 6
 # coordinates of a slot sequentially from 0, slots combined per 256-thread workgroup by the xor butterfly of each
 # 64-lane wavefront and (w0 + w1) + (w2 + w3), workgroup partials strided over 256 threads and combined the same way,
 # a row's blocks lane-strided and combined by the butterfly, no fused multiply-add (as ba_schur_ref.point_inverse

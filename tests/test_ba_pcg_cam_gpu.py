@@ -2,7 +2,7 @@
 against the numpy references of tests/ba_pcg_cam_ref.py.
 
 Fixed-iteration parity: 8 iterations with the tolerances off against pcg_cam_device_order (every sum in the order
-csrc/ba_pcg_cam.hip states) on the device's own blocks; x, Q and ||r|| / ||rhs|| within PARITY_BOUND = 100 x the
+csrc/ba_pcg.hip states) on the device's own blocks; x, Q and ||r|| / ||rhs|| within PARITY_BOUND = 100 x the
 reference's own ascending / descending sensitivity, measured and re-measured in tests/test_ba_pcg_cam_cpu.py (1.6584e-03
 on the gauge-free Levenberg mu = 0 systems, hence 1.6584e-01); rhs_norm within 1e-14, precond_fallbacks equal, inactive
 camera coordinates and constant-tvec coordinates exactly 0.  Every test prints its figures before it asserts.

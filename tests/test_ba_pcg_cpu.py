@@ -139,7 +139,7 @@ def test_row_order_changes_rounding_only(systems):
 @pytest.mark.parametrize("k", range(len(SCENES)))
 @pytest.mark.parametrize("mu", MUS)
 def test_reference_roundings_agree(systems, k, mu):
-    """pcg() (numpy's summation orders) and pcg_device_order() (every sum in the order csrc/ba_solve.hip states) are the same
+    """pcg() (numpy's summation orders) and pcg_device_order() (every sum in the order csrc/ba_pcg.hip states) are the same
     algorithm: same iteration counts and terminations at the defaults and to r_tolerance 1e-12, the tight solutions
     equal to 1e-9 (both are within that of numpy.linalg.solve)"""
     _, sb = systems[(k, mu)]

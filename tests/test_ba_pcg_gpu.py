@@ -10,7 +10,7 @@ images share no point -- so its own size is no scale; ||rhs|| is).  Largest valu
 block-Jacobi); most of these small systems have at most two blocks per row and show no difference at all.
 PARITY_BOUND = 100 x 5.4345e-13 = 5.4345e-11 for device against reference.
 
-The device is compared with ba_pcg_ref.pcg_device_order: the same algorithm with every sum in the order csrc/ba_solve.hip
+The device is compared with ba_pcg_ref.pcg_device_order: the same algorithm with every sum in the order csrc/ba_pcg.hip
 states (as ba_schur_ref.point_inverse follows k_schur_points).  With pcg(), whose sums round in the order numpy and
 its BLAS choose, the check cannot be met by any implementation: on these systems (cond(S) 1e7 ... 1e19) pcg() and
 pcg_device_order() -- two roundings of the same arithmetic on the CPU alone -- differ in x by up to 7.3e-10 with the

@@ -1,4 +1,5 @@
-"""ISA of the point-elimination kernels (csrc/ba_solve.hip), checked without a GPU: no scratch (a spill would
+"""ISA of the kernels of csrc/ba_solve.hip (the point elimination, the manifold update, the gradient max-norm and the LM
+record), checked without a GPU: no scratch (a spill would
 put per-lane fp64 traffic on the memory path these kernels are bound by) and the VGPR counts stated below, pinned from
 above so that growth shows up here rather than as a loss of wavefronts in flight.  k_schur_blocks holds 36 fp64
 accumulators plus the 2 x 18 doubles of an entry: 156 VGPRs, 3 wavefronts per SIMD."""
@@ -20,6 +21,8 @@ VGPRS = {                     # counts of the gfx950 build (hipcc -O3), DESIGN 4
     "k_schur_model_decrease": 42,
     "k_sum_u32": 8,
     "k_ba_plus": 58,
+    "k_ba_grad_max": 16,
+    "k_ba_lm_record": 30,
 }
 
 
