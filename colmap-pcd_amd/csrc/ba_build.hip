@@ -54,6 +54,42 @@ void launch_fill_image_major(const BaLayout& y, uint64_t O, hipStream_t s) {
                      y.img_pt.p, y.img_xy.p);
 }
 
+// What upload_problem and build_image_layout make of the description, taken from a handle that has it already: no
+// payload goes through the host.  The rows, the terms and everything derived from them are the caller's to build.
+// Every buffer is reserved before the first copy is enqueued.
+pcd_status ba_clone_problem(const pcd_ba* a, pcd_ba* b, hipStream_t s) {
+  b->device = a->device;
+  b->C = a->C; b->I = a->I; b->P = a->P;
+  b->loss_type = a->loss_type; b->loss_scale = a->loss_scale;
+  b->cam_params_len = a->cam_params_len; b->cam_stride = a->cam_stride;
+  b->uniform_model = a->uniform_model; b->shared_cam = a->shared_cam;
+  b->h_cam_params = a->h_cam_params; b->h_cam_model = a->h_cam_model; b->h_cam_off = a->h_cam_off;
+  b->h_image_cam = a->h_image_cam;
+  b->refines_intrinsics = a->refines_intrinsics;
+  b->h_cam_slot = a->h_cam_slot; b->h_slot_cam = a->h_slot_cam; b->h_param_cam = a->h_param_cam;
+  b->h_cam_active = a->h_cam_active;
+  b->has_cpose = true; b->has_ctvec = a->has_ctvec; b->has_cpt = a->has_cpt; b->has_refine = a->has_refine;
+  struct Copy { void* dst; const void* src; size_t bytes; };
+  std::vector<Copy> copies;
+  auto plan = [&](auto& dst, const auto& src, size_t n) -> pcd_status {   // n elements of a's buffer into b's
+    PCD_TRY(dst.reserve(at_least_1(n)));
+    if (n) copies.push_back(Copy{dst.p, src.p, n * sizeof(*dst.p)});
+    return PCD_OK;
+  };
+  const size_t C = (size_t)a->C, I = (size_t)a->I, P = (size_t)a->P, K = (size_t)a->cam_params_len;
+  PCD_TRY(plan(b->cam_model, a->cam_model, C)); PCD_TRY(plan(b->cam_off, a->cam_off, C));
+  PCD_TRY(plan(b->cam_params, a->cam_params, K));
+  PCD_TRY(plan(b->poses, a->poses, 7 * I)); PCD_TRY(plan(b->image_cam, a->image_cam, I));
+  PCD_TRY(plan(b->points, a->points, 3 * P));
+  PCD_TRY(plan(b->cam_img_start, a->cam_img_start, C + 1)); PCD_TRY(plan(b->cam_img_list, a->cam_img_list, I));
+  PCD_TRY(b->image_const_pose.reserve(at_least_1(I)));
+  if (a->has_ctvec) PCD_TRY(plan(b->image_const_tvec, a->image_const_tvec, I));
+  if (a->has_cpt) PCD_TRY(plan(b->point_const, a->point_const, P));
+  if (a->has_refine) PCD_TRY(plan(b->cam_refine, a->cam_refine, K));
+  for (const Copy& c : copies) PCD_HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, s));
+  return PCD_OK;
+}
+
 }  // namespace pcd
 
 using namespace pcd;

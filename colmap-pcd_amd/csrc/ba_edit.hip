@@ -16,7 +16,9 @@
 //   k_edit_record                        the counts the host reads (the ONE synchronisation), with img_obs_start
 // No atomics; nothing depends on the launch geometry.  The new state is a BaLayout and a BaTerms (ba_handle.h) built in
 // pcd_ba::edit_next, every buffer of it reserved before the first launch, and swapped in at the end.  Both edits go through
-// edit_reserve_shared, edit_derive, edit_read_record (the synchronisation) and edit_commit (the tail behind it).
+// edit_reserve_shared, edit_derive, edit_read_record (the synchronisation) and edit_commit (the tail behind it).  The
+// removal's passes up to the record are edit_reserve / edit_compact (declared in ba_handle.h): they only read the handle
+// and take the scratch to build in, so the window derivation (ba_window.hip) runs the same passes into a new handle.
 //
 // pcd_ba_add_observations_device is the growing edit: rows and points appended.  Its passes:
 //   k_add_keys, sort_pairs               the new rows' keys (clamped, with the verdict on their range) sorted stably, once
@@ -32,7 +34,6 @@
 namespace pcd {
 
 constexpr uint32_t kDropped = 0xFFFFFFFFu;
-enum { kRecObs = 0, kRecTerms, kRecSegs, kRecPoseRows, kRecEmptied, kRecWords };
 
 // flag[o] = 1: observation o stays.  Thread O writes the closing 0.
 __global__ __launch_bounds__(256) void k_edit_obs_flag(uint32_t O, const uint8_t* __restrict__ erase,
@@ -222,7 +223,7 @@ static pcd_status edit_reserve_shared(BaEditScratch& N, const BaLayoutSizes& z, 
 
 // The one synchronisation of an edit: the record and the image bounds (O(I) bytes) arrive in N.h_record.  rebuild_ms ends
 // here: the wait completes the event, no second one is needed.
-static pcd_status edit_read_record(BaEditScratch& N, size_t words, uint32_t I, EventPair* ev, hipStream_t s) {
+pcd_status edit_read_record(BaEditScratch& N, size_t words, uint32_t I, EventPair* ev, hipStream_t s) {
   PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p, N.record.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   PCD_HIP_TRY(hipMemcpyAsync(N.h_record.p + words, N.layout.img_obs_start.p, ((size_t)I + 1) * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, s));
@@ -256,14 +257,13 @@ static pcd_status edit_commit(pcd_ba* b, const EditCounts& c, const uint32_t* ns
   return PCD_OK;
 }
 
-// Every buffer the removal writes, at the sizes of the handle as it is: nothing grows when rows are dropped, so nothing
+// Every buffer the compaction writes, at the sizes of the handle as it is: nothing grows when rows are dropped, so nothing
 // is allocated after the first launch
-static pcd_status edit_reserve(pcd_ba* b, unsigned terms) {
-  BaEditScratch& N = b->edit_next;
+pcd_status edit_reserve(const pcd_ba* b, BaEditScratch& N, unsigned terms, bool pose_rows, size_t words) {
   const size_t O = b->O, L = b->L, P = (size_t)b->P, I = (size_t)b->I, ns = (size_t)b->nslices;
   // slices only get narrower: the sliced-ELL copies at the live capacity
-  PCD_TRY(edit_reserve_shared(N, BaLayoutSizes{O, P, I, ns, b->nseg, b->has_cpose, b->sell_img.n, b->sell_xy.n}, kRecWords));
-  if (b->has_cpose) { PCD_TRY(N.v_flag.reserve(O + 1)); PCD_TRY(N.v_pos.reserve(O + 1)); }
+  PCD_TRY(edit_reserve_shared(N, BaLayoutSizes{O, P, I, ns, b->nseg, pose_rows, b->sell_img.n, b->sell_xy.n}, words));
+  if (pose_rows) { PCD_TRY(N.v_flag.reserve(O + 1)); PCD_TRY(N.v_pos.reserve(O + 1)); }
   for (DevBuf<uint32_t>* d : {&N.flag, &N.pos, &N.t_flag, &N.t_pos, &N.i_flag, &N.i_pos}) PCD_TRY(d->reserve(O + 1));
   PCD_TRY(N.terms.reserve_terms(terms, L, P, ns * 64));
   if (L) for (DevBuf<uint32_t>* d : {&N.lf, &N.lp, &N.lt_flag, &N.lt_pos}) PCD_TRY(d->reserve(L + 1));
@@ -272,19 +272,13 @@ static pcd_status edit_reserve(pcd_ba* b, unsigned terms) {
   return N.prim.reserve(need);
 }
 
-static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t* d_pdel, uint32_t* d_map, hipStream_t s,
-                               pcd_ba_remove_info* info) {
-  BaEditScratch& N = b->edit_next;
+pcd_status edit_compact(const pcd_ba* b, BaEditScratch& N, const uint8_t* d_erase, const uint8_t* d_pdel, const uint8_t* cpose,
+                        uint32_t* d_map, hipStream_t s) {
   BaLayout& Y = N.layout;
   BaTerms& T = N.terms;
   const uint32_t O = (uint32_t)b->O, L = (uint32_t)b->L, P = (uint32_t)b->P, I = (uint32_t)b->I;
   const uint32_t nslices = (uint32_t)b->nslices;
-  const bool vrows = b->has_cpose, meta = b->has_lidar_meta;
-  // the terms this call builds: every group when the handle has terms (the meta when it has that), none otherwise
-  const unsigned terms = L ? kTermRows | (meta ? kTermMeta : 0u) | kTermIndex | kTermTracks : 0u;
-  PCD_TRY(edit_reserve(b, terms));
-  EventPair ev;
-  if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
+  const bool vrows = cpose != nullptr, meta = b->has_lidar_meta;
   {
     ScopedKernelTimer t("ba_edit_scan", s);
     hipLaunchKernelGGL(k_edit_obs_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, d_erase, d_pdel, b->obs_point.p, N.flag.p);
@@ -294,8 +288,7 @@ static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t*
     hipLaunchKernelGGL(k_edit_list_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, b->img_obs.p, N.flag.p, N.i_flag.p);
     PCD_TRY(scan_flags(N, N.i_flag.p, N.i_pos.p, (size_t)O + 1, s));
     if (vrows) {
-      hipLaunchKernelGGL(k_edit_vobs_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, N.flag.p, b->obs_image.p,
-                         b->image_const_pose.p, N.v_flag.p);
+      hipLaunchKernelGGL(k_edit_vobs_flag, grid((uint64_t)O + 1), dim3(256), 0, s, O, N.flag.p, b->obs_image.p, cpose, N.v_flag.p);
       PCD_TRY(scan_flags(N, N.v_flag.p, N.v_pos.p, (size_t)O + 1, s));
     }
     if (L) {
@@ -334,6 +327,20 @@ static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t*
                        vrows ? N.v_pos.p : nullptr, b->pt_obs_start.p, Y.pt_obs_start.p, N.record.p);
     PCD_HIP_TRY(hipGetLastError());
   }
+  return PCD_OK;
+}
+
+static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t* d_pdel, uint32_t* d_map, hipStream_t s,
+                               pcd_ba_remove_info* info) {
+  BaEditScratch& N = b->edit_next;
+  const uint32_t O = (uint32_t)b->O, L = (uint32_t)b->L, P = (uint32_t)b->P, I = (uint32_t)b->I;
+  const uint32_t nslices = (uint32_t)b->nslices;
+  // the terms this call builds: every group when the handle has terms (the meta when it has that), none otherwise
+  const unsigned terms = L ? kTermRows | (b->has_lidar_meta ? kTermMeta : 0u) | kTermIndex | kTermTracks : 0u;
+  PCD_TRY(edit_reserve(b, N, terms, b->has_cpose, kRecWords));
+  EventPair ev;
+  if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
+  PCD_TRY(edit_compact(b, N, d_erase, d_pdel, b->const_poses(), d_map, s));
   PCD_TRY(edit_read_record(N, kRecWords, I, info ? &ev : nullptr, s));
   const uint32_t* rec = N.h_record.p;
   const uint32_t nO = rec[kRecObs], nL = rec[kRecTerms];

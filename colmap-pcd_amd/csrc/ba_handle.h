@@ -8,6 +8,8 @@
 //   ba_lidar.hip  replaces the LiDAR terms of a live handle: pcd_ba_set_lidar_device / pcd_ba_associate_lidar_device
 //   ba_edit.hip   drops observations and points from a live handle, and adds them: pcd_ba_remove_observations_device,
 //                 pcd_ba_add_observations_device
+//   ba_window.hip derives a second handle, the sphere window of a global round, from a live one and carries its
+//                 parameters back: pcd_ba_window_create_device, pcd_ba_window_commit_device
 #pragma once
 #include <memory>
 
@@ -224,6 +226,34 @@ void ba_schur_drop_structure(pcd_ba* b);
 void launch_fill_sell(const BaLayout& y, int nslices, hipStream_t s);
 void launch_fill_image_major(const BaLayout& y, uint64_t O, hipStream_t s);
 void launch_lidar_tracks(const BaLayout& y, int nslices, const BaTerms& rows, BaTerms& next, hipStream_t s);
+
+}  // namespace pcd
+
+struct pcd_ba;
+
+namespace pcd {
+
+// The compaction of a handle's rows (ba_edit.hip), shared by the removal, which swaps the result into the handle it
+// read, and the window derivation (ba_window.hip), which makes it a new handle's.  `src` is only read; N is the scratch
+// the new BaLayout / BaTerms are built in (the removal: src's own edit_next; the window: the new handle's).
+//   edit_reserve      every buffer edit_compact writes, at the sizes of src: nothing is allocated after the first launch.
+//                     terms: the groups to build (0: src has no terms); pose_rows: vobs is built; words: the record's length
+//   edit_compact      observation o stays iff !d_erase[o] && !d_pdel[obs_point[o]], term l iff !d_pdel[lidar_point[l]]
+//                     (either may be null).  cpose (null: no packed pose rows) is the constness mask the pose rows are
+//                     taken with.  Flags, scans, compaction of rows and both CSRs, the derived layouts, the sliced-ELL and
+//                     per-track fills; the counts go to N.record[0 .. kRecWords).  Enqueued on s, no wait.
+//   edit_read_record  the ONE synchronisation: `words` of the record and the new image bounds arrive in N.h_record;
+//                     ev (may be null) is stopped in front of the wait
+enum { kRecObs = 0, kRecTerms, kRecSegs, kRecPoseRows, kRecEmptied, kRecWords };
+pcd_status edit_reserve(const pcd_ba* src, BaEditScratch& N, unsigned terms, bool pose_rows, size_t words);
+pcd_status edit_compact(const pcd_ba* src, BaEditScratch& N, const uint8_t* d_erase, const uint8_t* d_pdel,
+                        const uint8_t* cpose, uint32_t* d_map, hipStream_t s);
+pcd_status edit_read_record(BaEditScratch& N, size_t words, uint32_t I, EventPair* ev, hipStream_t s);
+// ba_build.hip: what a handle holds besides its rows and terms, copied from a live one on the device (the window
+// derivation): counts that do not change (C, I, P), cameras with their host mirrors, camera slots and refine state,
+// image_cam and the cam_img CSR, the parameters as they are on the device now, image_const_tvec / point_const /
+// cam_refine.  image_const_pose is reserved [I] and left to the caller, has_cpose is set.  Copies are enqueued on s.
+pcd_status ba_clone_problem(const pcd_ba* src, pcd_ba* dst, hipStream_t s);
 
 }  // namespace pcd
 

@@ -243,6 +243,18 @@ class BAAddInfo(C.Structure):
                                            "num_pose_rows")] + [("rebuild_ms", C.c_double)]
 
 
+class BAWindowOpts(C.Structure):
+    """pcd_ba_window_opts (pcdhip.h)."""
+    _fields_ = [("center_image", C.c_int32), ("radius", C.c_double), ("d_image_set", C.c_void_p),
+                ("d_extra_const_pose", C.c_void_p), ("reserved", C.c_int32 * 8)]
+
+
+class BAWindowInfo(C.Structure):
+    """pcd_ba_window_info (pcdhip.h)."""
+    _fields_ = [(n, C.c_uint64) for n in ("num_images_in", "num_points_active", "num_obs", "num_lidar",
+                                           "num_pose_rows")] + [("build_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -314,6 +326,7 @@ ABI_SYMBOLS = [
     "pcd_ba_filter_opts_default", "pcd_ba_filter_points_device", "pcd_ba_filter_points",
     "pcd_ba_remove_observations_device", "pcd_ba_add_observations_device", "pcd_ba_add_observations",
     "pcd_ba_schur_build_device", "pcd_ba_schur_structure_lists",
+    "pcd_ba_window_opts_default", "pcd_ba_window_create_device", "pcd_ba_window_commit_device",
 ]
 
 
@@ -462,6 +475,12 @@ def lib():
                                                      C.c_uint64, C.c_void_p, C.POINTER(BAAddInfo)]
         L.pcd_ba_add_observations.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint64, C.POINTER(BAAddInfo)]
+    if hasattr(L, "pcd_ba_window_create_device"):
+        L.pcd_ba_window_opts_default.argtypes = [C.POINTER(BAWindowOpts)]
+        L.pcd_ba_window_opts_default.restype = None
+        L.pcd_ba_window_create_device.argtypes = [C.c_void_p, C.POINTER(BAWindowOpts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(BAWindowInfo)]
+        L.pcd_ba_window_commit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _LIB = L
     return L
 
@@ -1417,6 +1436,70 @@ class BA:
             self.__dict__.pop("_schur_dims", None)                    # the co-visibility structure is built anew
         return {k: getattr(info, k) for k, _ in BAAddInfo._fields_}
 
+    def sphere_window(self, center_image=None, radius=40.0, image_set=None, extra_const_pose=None, want=()):
+        """pcd_ba_window_create_device: the sphere sub-problem of one global round (AdjustGlobalBundleByLidar) as a NEW
+        handle derived on the device; this handle is only read.  The images within `radius` of center_image's projection
+        centre are "in" (or those flagged in image_set [I], with center_image None); every other image gets a constant
+        pose, as do those flagged in extra_const_pose [I]; the points seen from an "in" image keep all their observations
+        and LiDAR terms, the others keep none.  I, P and C are unchanged: indices mean the same in both handles.
+        Synchronises the current stream once.  Returns (BA, info): info holds num_images_in, num_points_active, num_obs,
+        num_lidar, num_pose_rows, build_ms and, for the names in `want`, the device tensors image_in [I] uint8,
+        point_active [P] uint8 and obs_map [O] int32 (row in the window, -1: not in it).  BA.commit_window carries the
+        window's parameters back; close the window when done."""
+        torch, dev, stream = self._torch()
+        o = BAWindowOpts()
+        lib().pcd_ba_window_opts_default(C.byref(o))
+        o.center_image = -1 if center_image is None else int(center_image)
+        o.radius = float(radius)
+        iset, extra = self._stage(image_set, np.uint8), self._stage(extra_const_pose, np.uint8)
+        for name, t in (("image_set", iset), ("extra_const_pose", extra)):
+            if t is not None and int(t.numel()) != self.I:
+                raise ValueError(f"sphere_window: {name} must have one entry per image")
+        o.d_image_set = None if iset is None else iset.data_ptr()
+        o.d_extra_const_pose = None if extra is None else extra.data_ptr()
+        bad = set(want) - {"image_in", "point_active", "obs_map"}
+        if bad:
+            raise ValueError(f"sphere_window: unknown output {sorted(bad)}")
+        t_in = torch.empty(self.I, dtype=torch.uint8, device=dev)   # always: the window's host mask mirror needs it
+        t_act = torch.empty(self.P, dtype=torch.uint8, device=dev) if "point_active" in want else None
+        t_map = torch.empty(self.O, dtype=torch.int32, device=dev) if "obs_map" in want and self.O else None
+        h, info = C.c_void_p(), BAWindowInfo()
+        _check(lib().pcd_ba_window_create_device(self._h, C.byref(o), _ptr(t_in), _ptr(t_act), _ptr(t_map),
+                                                 C.c_void_p(stream), C.byref(h), C.byref(info)))
+        w = BA.__new__(BA)
+        w.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("_h", "_schur_dims")})
+        w._h = h
+        w.O, w.L = int(info.num_obs), int(info.num_lidar)
+        w.obs_image = w.obs_point = w.obs_xy = None                # the handle has the rows and the terms
+        w.lidar_point = w.lidar_abcd = w.lidar_weight = None
+        # the host mirror of the window's pose mask (BA._cam_dims counts the pose slots from it): src's | !in | extra,
+        # from O(I) bytes read back behind the call's own synchronisation
+        cpose = t_in.cpu().numpy() == 0
+        if self.image_const_pose is not None:
+            cpose |= self.image_const_pose != 0
+        if extra is not None:
+            cpose |= extra.cpu().numpy() != 0
+        w.image_const_pose = cpose.astype(np.uint8)
+        w.__dict__.pop("_ncs", None)
+        w.poses = w.points = None                                  # BA.get_parameters() has the current ones
+        out = {k: getattr(info, k) for k, _ in BAWindowInfo._fields_}
+        if "image_in" in want:
+            out["image_in"] = t_in
+        if "point_active" in want:
+            out["point_active"] = t_act
+        if "obs_map" in want:
+            out["obs_map"] = t_map if t_map is not None else torch.empty(0, dtype=torch.int32, device=dev)
+        return w, out
+
+    def commit_window(self, win):
+        """pcd_ba_window_commit_device: the window's poses and points (and, when it refines intrinsics, its camera
+        parameters) over this handle's, device to device on the current stream.  Exact: the window's constant poses and
+        inactive points never moved.  The Schur state of this handle's last call is dropped, its structure stays."""
+        _, _, stream = self._torch()
+        _check(lib().pcd_ba_window_commit_device(win._h, self._h, C.c_void_p(stream)))
+        if win.camera_refine is not None and np.any(win.camera_refine):
+            self.cam_params = self.get_camera_parameters()
+
     def device_parameters(self):
         a, b = C.c_void_p(), C.c_void_p()
         _check(lib().pcd_ba_device_parameters(self._h, C.byref(a), C.byref(b)))
@@ -1923,7 +2006,8 @@ def ba_solve(ba, max_num_iterations=None, damping=None, initial_radius=None, max
 
 def register_refine(ba, cloud, rounds, kd_max=1.5, kd_min=0.2, drop=0.1, gate_mode=GATE_MAPPER_GLOBAL, select=None,
                     projector=None, cam_size=None, point_mode=None, image_select=None, proj_weight=1.0, **solve_opts):
-    """The loop of IncrementalMapper::AdjustGlobalBundleByLidar (sfm/incremental_mapper.cc:1413-1478) on one handle,
+    """The association / solve half of IncrementalMapper::AdjustGlobalBundleByLidar (sfm/incremental_mapper.cc:1413-1478)
+    on whatever the handle holds, without the sphere selection of :1347-1408 (global_round is the whole function),
     GlobalOptNum advancing once per round: in round r every selected point searches within search_range_schedule(r)
     (kd_max, kd_min, drop), BA.associate_lidar installs the accepted associations, ba_solve(**solve_opts) refines.
     Nothing goes through the host and nothing that depends on the observations alone is rebuilt; no device work of its
@@ -1944,6 +2028,33 @@ def register_refine(ba, cloud, rounds, kd_max=1.5, kd_min=0.2, drop=0.1, gate_mo
         summary, its = ba_solve(ba, **solve_opts)
         out.append((info, summary, its))
     return out
+
+
+def global_round(ba, cloud, center_image, radius, opt_num, kd_max=1.5, kd_min=0.2, drop=0.1, extra_const_pose=None,
+                 **solve_opts):
+    """One call of IncrementalMapper::AdjustGlobalBundleByLidar (sfm/incremental_mapper.cc:1297-1493) on the device:
+    BA.sphere_window(center_image, radius, extra_const_pose) derives the sphere sub-problem, the window's active points
+    search `cloud` within search_range_schedule(opt_num) per point (:1423-1427) and BA.associate_lidar installs the
+    accepted associations on the window, ba_solve(**solve_opts) refines it, BA.commit_window carries the parameters back
+    into `ba`, and opt_num [P] (int32 numpy or torch device tensor, updated in place: GlobalOptNum, :1483-1487) advances
+    for the active points.  `ba` keeps its rows, terms and co-visibility structure.  Returns (window info, association
+    info, solve summary, iterations)."""
+    torch, dev, _ = ba._torch()
+    win, winfo = ba.sphere_window(center_image, radius, extra_const_pose=extra_const_pose, want=("point_active",))
+    try:
+        active = winfo.pop("point_active")
+        host_num = opt_num.cpu().numpy() if isinstance(opt_num, torch.Tensor) else np.asarray(opt_num)
+        rng = search_range_schedule(np.ascontiguousarray(host_num, np.int32), kd_max, kd_min, drop)
+        ainfo = win.associate_lidar(cloud, max_range=rng, gate_mode=GATE_MAPPER_GLOBAL, select=active)
+        summary, its = ba_solve(win, **solve_opts)
+        ba.commit_window(win)
+    finally:
+        win.close()
+    if isinstance(opt_num, torch.Tensor):
+        opt_num += active.to(opt_num.dtype)
+    else:
+        opt_num += active.cpu().numpy().astype(opt_num.dtype)
+    return winfo, ainfo, summary, its
 
 
 def refine_filter(ba, max_refinements=5, max_change=0.0005, max_reproj_error=8.0, min_tri_angle=1.5, complete=None,

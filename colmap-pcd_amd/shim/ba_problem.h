@@ -242,15 +242,7 @@ class BundleAdjusterHip {
     // after ReassociateLidar the live handle IS the problem (its parameters and terms are the flat arrays'): keep it
     if (!(reassociated_ && ba_) && !Create(device)) return false;
     reassociated_ = false;
-    pcd_ba_solve_opts o;
-    pcd_ba_solve_opts_default(&o);
-    o.max_num_iterations = options_.max_num_iterations;
-    o.function_tolerance = options_.function_tolerance;
-    o.gradient_tolerance = options_.gradient_tolerance;
-    o.linear.max_iterations = options_.max_linear_solver_iterations;
-    if (refined) o.linear_solver = RefinedUsesDirectSolver() ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG_CAM;
-    else o.linear_solver = UsesDirectSolver() ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG;
-    o.refine_intrinsics = refined ? 1 : 0;
+    const pcd_ba_solve_opts o = SolveOpts(refined);
     if (pcd_ba_solve(ba_, &o, &summary_, nullptr) != PCD_OK) return false;
     if (pcd_ba_get_parameters(ba_, poses_.data(), points_.data()) != PCD_OK) return false;
     if (refined) {
@@ -579,6 +571,122 @@ class BundleAdjusterHip {
     if (ok) *ok = true;
     return a.obs_image.size();
   }
+  // ---- one global round (HIP): IncrementalMapper::AdjustGlobalBundleByLidar (sfm/incremental_mapper.cc:1297-1493) on the
+  // LIVE handle, which holds the whole map (after Create() or Solve()) ----------------------------------------------------
+  // pcd_ba_window_create_device derives the sphere sub-problem around center_image_id (:1347-1408: images farther than
+  // `radius` from its projection centre get a constant pose, only points seen from inside take part, with all their
+  // observations) as a second handle; its active points search `cloud` within kd_max - GlobalOptNum * drop, at least
+  // kd_min (:1423-1427), and the accepted associations become the window's LiDAR terms; pcd_ba_solve refines the window
+  // with Solve's options; pcd_ba_window_commit_device carries the parameters back into the live handle.  Nothing is
+  // downloaded to select and nothing is uploaded or rebuilt on the live handle, which keeps its rows, its terms and its
+  // co-visibility structure.  Then the variable poses inside the sphere and the active variable points go back into the
+  // Reconstruction and the flat mirrors, and GlobalOptNum advances for the active points (:1483-1487).  terms (may be
+  // NULL) receives the round's LiDAR terms by point id.
+  // The round's terms live on the window and go with it: the live handle, the flat lidar_* mirrors and
+  // config_.lidar_maps_ keep what they held before the call (the whole map's terms, if any), as the reference's
+  // ba_config of one round does not outlive it.  A Solve after GlobalRound keeps the live handle (it IS the problem, at
+  // the committed parameters) and therefore adjusts the whole map WITHOUT the round's terms; a caller who wants them on
+  // the whole map takes them from `terms` into the config of a new SetUp.
+  // false without a live handle or cloud, for an image that is not in the problem, when intrinsics are refined and
+  // options_.refine_intrinsics_on_device is off, or when a call fails (pcd_last_error()); the problem is then as it was.
+  struct GlobalRoundInfo { pcd_ba_window_info window; pcd_ba_assoc_info assoc; pcd_ba_solve_summary solve; };
+  template <typename Cloud>
+  bool GlobalRound(Reconstruction* rec, Cloud& cloud, image_t center_image_id, double radius, double kd_max = 1.5,
+                   double kd_min = 0.2, double drop = 0.1, GlobalRoundInfo* info = nullptr,
+                   std::unordered_map<point3D_t, LidarPoint>* terms = nullptr) {
+    if (info) *info = GlobalRoundInfo{};
+    if (!ba_ || !cloud.handle()) return false;
+    const auto center = image_index_.find(center_image_id);
+    if (center == image_index_.end()) return false;
+    bool refined = false;
+    for (uint8_t v : cam_refine_) refined |= v != 0;
+    if (refined && !options_.refine_intrinsics_on_device) return false;
+    const size_t P = point_ids_.size(), I = image_ids_.size();
+    struct DevMem {   // freed on every return
+      void* p = nullptr;
+      ~DevMem() { if (p) (void)hipFree(p); }
+    } d_flags, d_range;
+    struct Window {   // destroyed on every return
+      pcd_ba* h = nullptr;
+      ~Window() { pcd_ba_destroy(h); }
+    } win;
+    if (hipMalloc(&d_flags.p, I + P + 1) != hipSuccess || hipMalloc(&d_range.p, (P + 1) * sizeof(double)) != hipSuccess)
+      return false;
+    uint8_t* d_in = static_cast<uint8_t*>(d_flags.p), *d_active = d_in + I;
+    GlobalRoundInfo r{};
+    pcd_ba_window_opts wo;
+    pcd_ba_window_opts_default(&wo);
+    wo.center_image = center->second;
+    wo.radius = radius;
+    if (pcd_ba_window_create_device(ba_, &wo, d_in, d_active, nullptr, nullptr, &win.h, &r.window) != PCD_OK) return false;
+    std::vector<int32_t> opt_num(P, 0);
+    for (size_t p = 0; p < P; ++p) {
+      const auto it = rec->points3D.find(point_ids_[p]);
+      if (it != rec->points3D.end()) opt_num[p] = it->second.global_opt_num;
+    }
+    std::vector<double> range(P);
+    if (pcd_search_range_schedule(opt_num.data(), P, kd_max, kd_min, drop, range.data()) != PCD_OK) return false;
+    if (hipMemcpy(d_range.p, range.data(), P * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return false;
+    pcd_ba_assoc_opts ao;
+    pcd_ba_assoc_opts_default(&ao);
+    ao.gate_mode = PCD_GATE_MAPPER_GLOBAL;
+    ao.icp_weight = options_.icp_lidar_constraint_weight;
+    ao.icp_ground_weight = options_.icp_ground_lidar_constraint_weight;
+    ao.d_max_range = static_cast<const double*>(d_range.p);
+    ao.max_range_count = P;
+    ao.d_select = d_active;
+    if (pcd_ba_associate_lidar_device(win.h, cloud.handle(), &ao, nullptr, &r.assoc) != PCD_OK) return false;
+    const pcd_ba_solve_opts so = SolveOpts(refined);
+    if (pcd_ba_solve(win.h, &so, &r.solve, nullptr) != PCD_OK) return false;
+    std::vector<uint8_t> flags(I + P + 1);
+    if (hipMemcpy(flags.data(), d_flags.p, I + P, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (terms) {
+      terms->clear();
+      uint64_t L = 0;
+      if (pcd_ba_get_lidar(win.h, &L, nullptr, nullptr, nullptr, nullptr, nullptr) != PCD_OK) return false;
+      std::vector<int32_t> point(L);
+      std::vector<double> abcd(4 * L), w(L), xyz(3 * L);
+      std::vector<uint8_t> type(L);
+      if (pcd_ba_get_lidar(win.h, &L, point.data(), abcd.data(), w.data(), type.data(), xyz.data()) != PCD_OK) return false;
+      for (uint64_t l = 0; l < L; ++l) {
+        LidarPoint lp;
+        lp.type = type[l] == PCD_LIDAR_ICP_GROUND ? LidarPointType::IcpGround : LidarPointType::Icp;
+        for (int k = 0; k < 3; ++k) lp.xyz[k] = xyz[3 * l + k];
+        for (int k = 0; k < 4; ++k) lp.abcd[k] = abcd[4 * l + k];
+        if (lp.type == LidarPointType::IcpGround) lp.color = {255, 255, 0};
+        else lp.color = {0, 0, 255};
+        (*terms)[point_ids_[point[l]]] = lp;
+      }
+    }
+    // from here on the problem changes: the live handle first, then its mirrors
+    if (pcd_ba_window_commit_device(win.h, ba_, nullptr) != PCD_OK) return false;
+    if (pcd_ba_get_parameters(ba_, poses_.data(), points_.data()) != PCD_OK) return false;
+    if (refined && pcd_ba_get_camera_parameters(ba_, cam_params_.data()) != PCD_OK) return false;
+    const uint8_t* in = flags.data(), *active = flags.data() + I;
+    for (size_t i = 0; i < I; ++i) {
+      if (image_const_pose_[i] || !in[i]) continue;
+      Image& im = rec->images.at(image_ids_[i]);
+      std::copy(poses_.begin() + 7 * i, poses_.begin() + 7 * i + 4, im.qvec);
+      std::copy(poses_.begin() + 7 * i + 4, poses_.begin() + 7 * i + 7, im.tvec);
+    }
+    for (size_t p = 0; p < P; ++p) {
+      if (!active[p]) continue;
+      auto it = rec->points3D.find(point_ids_[p]);
+      if (it == rec->points3D.end()) continue;
+      if (!point_const_[p]) std::copy(points_.begin() + 3 * p, points_.begin() + 3 * p + 3, it->second.xyz);
+      it->second.global_opt_num += 1;
+    }
+    if (refined)
+      for (size_t c = 0; c < camera_ids_.size(); ++c) {
+        if (!CameraVariable((int)c)) continue;
+        Camera& cam = rec->cameras.at(camera_ids_[c]);
+        std::copy(cam_params_.begin() + cam_off_[c], cam_params_.begin() + cam_off_[c] + cam.params.size(), cam.params.begin());
+      }
+    reassociated_ = true;   // the live handle is the problem: Solve keeps it
+    summary_ = r.solve;
+    if (info) *info = r;
+    return true;
+  }
   const BundleAdjustmentConfig& config() const { return config_; }
   // what Solve hands to pcd_ba_solve: AUTO goes by the number of images in the config, as the reference does
   bool UsesDirectSolver() const {
@@ -586,6 +694,19 @@ class BundleAdjusterHip {
     return options_.linear_solver_type == T::DIRECT ||
            (options_.linear_solver_type == T::AUTO &&
             config_.NumImages() <= BundleAdjustmentOptions::kMaxNumImagesDirectSolver);
+  }
+  // the options Solve and GlobalRound hand to pcd_ba_solve
+  pcd_ba_solve_opts SolveOpts(bool refined) const {
+    pcd_ba_solve_opts o;
+    pcd_ba_solve_opts_default(&o);
+    o.max_num_iterations = options_.max_num_iterations;
+    o.function_tolerance = options_.function_tolerance;
+    o.gradient_tolerance = options_.gradient_tolerance;
+    o.linear.max_iterations = options_.max_linear_solver_iterations;
+    if (refined) o.linear_solver = RefinedUsesDirectSolver() ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG_CAM;
+    else o.linear_solver = UsesDirectSolver() ? PCD_LINEAR_CHOLESKY : PCD_LINEAR_PCG;
+    o.refine_intrinsics = refined ? 1 : 0;
+    return o;
   }
   // the same choice for a solve with refined intrinsics (options_.refined_linear_solver_type)
   bool RefinedUsesDirectSolver() const {

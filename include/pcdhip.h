@@ -687,7 +687,9 @@ pcd_status pcd_ba_observation_errors(pcd_ba* ba, double* sq_err /*[O]*/, double*
 pcd_status pcd_ba_observation_errors_device(pcd_ba* ba, double* d_sq_err, double* d_depth, void* stream);
 /* device-side parameter pointers for zero-copy updates: [I][7] and [P][3] doubles */
 pcd_status pcd_ba_device_parameters(pcd_ba* ba, double** d_poses, double** d_points);
-/* device -> device parameter update on `stream` (NULL keeps the old values) */
+/* device -> device parameter update on `stream` (NULL keeps the old values).  Invalidates nothing: a Schur state of the
+ * old parameters stays readable, and ordering it against the update is the caller's business.
+ * pcd_ba_window_commit_device, which also writes parameters, differs there: it drops the source's Schur state. */
 pcd_status pcd_ba_set_parameters_device(pcd_ba* ba, const double* d_poses, const double* d_points, void* stream);
 
 /* Point elimination on the device: one Levenberg-Marquardt step of the normal equations without the
@@ -1202,6 +1204,63 @@ pcd_status pcd_ba_add_observations_device(pcd_ba* ba,
 pcd_status pcd_ba_add_observations(pcd_ba* ba, const double* new_points, uint64_t num_new_points,
                                    const int32_t* obs_image, const int32_t* obs_point, const double* obs_xy,
                                    uint64_t num_new_obs, pcd_ba_add_info* info /* may be NULL */);
+
+/* ------------------------------------------------------------------------
+ * The sphere window of a global round: a second handle derived on the device   
+ *   the selection of sfm/incremental_mapper.cc:1347-1408 (IncrementalMapper::AdjustGlobalBundleByLidar) and of
+ *   optim/bundle_adjustment.cc:694-806 (AddImageInSphereToProblem): a sphere of ba_spherical_search_radius around the
+ *   newest image's projection centre; images outside get a constant pose; only points seen from inside take part, with
+ *   ALL their observations and their LiDAR terms.
+ * pcd_ba_window_create_device derives that sub-problem from a live handle as a NEW handle; src is only read.
+ * Selection, in the reference's arithmetic (fp64, no FMA, sums left to right; the stored quaternion is NOT normalised):
+ *   R = Eigen's Quaterniond(w, x, y, z).toRotationMatrix():
+ *     tx=2x ty=2y tz=2z  twx=tx*w twy=ty*w twz=tz*w  txx=tx*x txy=ty*x txz=tz*x  tyy=ty*y tyz=tz*y  tzz=tz*z
+ *     R00=1-(tyy+tzz) R01=txy-twz R02=txz+twy  R10=txy+twz R11=1-(txx+tzz) R12=tyz-twx  R20=txz-twy R21=tyz+twx R22=1-(txx+tyy)
+ *   c_k = -((R0k*t0 + R1k*t1) + R2k*t2);  dist = sqrt((dx*dx + dy*dy) + dz*dz);  image i is IN iff dist <= radius.
+ *   With d_image_set the caller names the "in" images instead (any non-zero byte).
+ *   Point p is ACTIVE iff one of its observations lies on an "in" image.
+ *   Observation o of src is in the window iff active[obs_point[o]]; LiDAR term l iff active[lidar_point[l]];
+ *   image_const_pose' = src's mask | !in | d_extra_const_pose.
+ * Contract (that of the edits above): the window is indistinguishable from a handle pcd_ba_create builds from src's
+ *   cameras, image_const_tvec / point_const / camera_refine and loss, src's parameters as they are on the device now,
+ *   image_const_pose = image_const_pose' (always an array), and obs_* / lidar_* compacted as above in their old order
+ *   (terms keep their type / lidar_xyz meta).  I, P and C are unchanged: image and point indices mean the same in both
+ *   handles; an inactive point is a row without a residual block.  Every derived array is the fresh handle's byte for
+ *   byte, so every later call on the window is bit-identical to the fresh handle's.
+ * The window owns all its buffers: the handles are destroyed in either order, and nothing of src -- results, handed-out
+ *   pointers, Schur state, structure -- changes.
+ * Guards, before anything is allocated or launched: NULL src / opts / window -> INVALID; no gfx950 -> NO_DEVICE; a
+ *   capturing stream -> UNSUPPORTED; exactly one of center_image >= 0 and d_image_set must be given, center_image < I,
+ *   radius >= 0 and not NaN (+inf: every image is in) -> INVALID otherwise.  A failed allocation leaves *window NULL.
+ *   A window without an active point (O == 0, L == 0) is a valid handle.
+ * The call synchronises `stream` ONCE, to read O(I) bytes (the counts and the image bounds); the image-major fill is
+ *   enqueued behind it.  No atomics, nothing depends on launch geometry: a repeated call gives the same bytes.
+ * pcd_ba_window_commit_device copies the window's poses and points over src's, device to device on `stream` (exact: the
+ *   window's constant poses and inactive points never moved), and, when the window refines intrinsics, its camera
+ *   parameters with the host mirror.  It drops src's Schur state of the last call (it belongs to the old parameters);
+ *   the co-visibility structure stays.  INVALID: a NULL handle, different devices, differing I, P or cam_params_len.
+ * --------------------------------------------------------------------- */
+typedef struct {
+  int32_t center_image;              /* image whose projection centre is the sphere's; -1: use d_image_set */
+  double  radius;                    /* ba_spherical_search_radius; image i is in iff dist(c_i, c_center) <= radius */
+  const uint8_t* d_image_set;        /* device [I] or NULL: the images that are "in", given by the caller instead of a
+                                        sphere (center_image must be -1 then; radius ignored) */
+  const uint8_t* d_extra_const_pose; /* device [I] or NULL: OR-ed into the pose constness
+                                        (fix_existing_images :1323-1329, first_image_fixed_frames :1341-1345) */
+  int32_t reserved[8];
+} pcd_ba_window_opts;
+typedef struct {
+  uint64_t num_images_in, num_points_active;
+  uint64_t num_obs, num_lidar, num_pose_rows;   /* of the window */
+  double build_ms;                               /* device time up to the call's one synchronisation */
+} pcd_ba_window_info;
+void pcd_ba_window_opts_default(pcd_ba_window_opts* o);   /* -1, 40.0, NULL, NULL */
+pcd_status pcd_ba_window_create_device(pcd_ba* src, const pcd_ba_window_opts* opts,
+    uint8_t* d_image_in      /* [I] or NULL, out */,
+    uint8_t* d_point_active  /* [P] or NULL, out */,
+    uint32_t* d_obs_map      /* [O of src] or NULL, out: row in the window, 0xFFFFFFFF = not in it */,
+    void* stream, pcd_ba** window, pcd_ba_window_info* info /* host, may be NULL */);
+pcd_status pcd_ba_window_commit_device(pcd_ba* window, pcd_ba* src, void* stream);
 
 /* ------------------------------------------------------------------------
  * Exact SIFT descriptor matching (stretch row a19)
