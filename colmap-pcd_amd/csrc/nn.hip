@@ -795,30 +795,43 @@ struct FbFused {   // inputs of k_nn_fallback<1 / 2> (the kernel as the only lau
 // FUSED: 0 = queries from qf4, keys in and out raw (the grid path's second stage; refining), 1 / 2 = the kernel is the
 // only launch of the call (plain / gate-bounded).  A template parameter, not a run-time mode: with the mode tested at
 // run time the grid path's instance compiled differently and ran 17 % slower (0.365 -> 0.425 ms on workload M).
+// One wavefront per workgroup: a workgroup's LDS (and its place in the CU's workgroup count) goes back only when its
+// LAST walk ends, and the walks differ widely in length (12.8 steps on average, up to ~80 on workload M) -- with four
+// walks per workgroup the wavefronts of a workgroup were finished for 27 % of its life, with one every walk gives back
+// everything it holds when it ends (256 / 128 / 64 threads: 0.173 / 0.163 / 0.159 ms on workload M,
+// profiles/fb_release_probe.txt).  At most 80 SGPRs: a SIMD's scalar registers admit an eighth wavefront only up to
+// there (MI355X: 800 / (allocation + 16)), the walk's uniform state took 94-96 without the bound, and the bound costs
+// one VGPR (0.159 -> 0.152 ms).
+// dynamic LDS of a workgroup: its walk's stack, one entry per level that pushes
+constexpr size_t fb_stack_bytes(int nlev) { return (size_t)(nlev - 2) * (64 * 4 + 64 * 4 + 8); }
+static_assert(fb_stack_bytes(kMaxPyrLevels) <= 64 * 1024, "the deepest pyramid's stack fits a workgroup's LDS");
 template <int FUSED>
-__global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams py, const float4* __restrict__ sorted,
-                                                      const uint32_t* __restrict__ cell_start,
-                                                      const float* __restrict__ aabb,
-                                                      const float4* __restrict__ seeds,
-                                                      const float4* __restrict__ qf4,
-                                                      const uint32_t* __restrict__ list,  // NULL: queries 0..count-1
-                                                      const uint32_t* __restrict__ count_ptr, uint32_t count_imm,
-                                                      uint64_t* __restrict__ keys, NnCounters* __restrict__ ctr,
-                                                      int collect_stats, FbFused fu) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80)))
+void k_nn_fallback(GridParams g, PyramidParams py, const float4* __restrict__ sorted,
+                   const uint32_t* __restrict__ cell_start, const float* __restrict__ aabb,
+                   const float4* __restrict__ seeds, const float4* __restrict__ qf4,
+                   const uint32_t* __restrict__ list,  // NULL: queries 0..count-1
+                   const uint32_t* __restrict__ count_ptr, uint32_t count_imm, uint64_t* __restrict__ keys,
+                   NnCounters* __restrict__ ctr, int collect_stats, FbFused fu,
+                   unsigned long long* __restrict__ wave_rec) {
   // the stack: levels 2 .. nlev - 1 push (a level-1 node's children are leaves).  Per lane the child's bound and its
-  // own child range as first | (count - 1) << 26 (cloud.h kMaxPyrRecords): 16 KB, 8 workgroups per CU
-  constexpr int kStack = kMaxPyrLevels - 2;
-  __shared__ float s_lb[4][kStack][64];
-  __shared__ uint32_t s_rng[4][kStack][64];
-  __shared__ unsigned long long s_mask[4][kStack];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // uniform for the compiler: LDS addresses on the scalar unit
+  // own child range as first | (count - 1) << 26 (cloud.h kMaxPyrRecords), per level the mask of the children still
+  // to visit.  Dynamic LDS of nlev - 2 levels (fb_stack_bytes; none for a two-level pyramid, which never pushes):
+  // the levels a cloud's pyramid does not have would only keep other workgroups off the CU (kMaxPyrLevels - 2 = 8
+  // levels for four walks were 16 KB a workgroup, workload M's pyramid pushes at three)
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_stack[];
+  const int lane = threadIdx.x;
+  const int nst = py.nlev - 2;   // levels of the stack
+  float* const s_lb = reinterpret_cast<float*>(s_stack);                                        // [nst][64]
+  uint32_t* const s_rng = reinterpret_cast<uint32_t*>(s_stack) + (size_t)nst * 64;               // [nst][64]
+  unsigned long long* const s_mask = reinterpret_cast<unsigned long long*>(s_stack + (size_t)nst * 512);   // [nst]
   const uint32_t count = count_ptr ? *count_ptr : count_imm;
-  const uint32_t nwaves = gridDim.x * 4;
   const int top = py.nlev - 1;  // >= 1
+  const bool probe = (collect_stats & 16) != 0;   // (uniform) a pass that keeps per-wavefront records
+  const unsigned long long t_start = probe ? wall_clock64() : 0ull;
   unsigned long long st_pts = 0, st_q = 0, st_steps = 0, st_leaves = 0;
   uint32_t st_max_steps = 0, st_max_leaves = 0;
-  for (uint32_t e = blockIdx.x * 4 + wave; e < count; e += nwaves) {
+  for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
     const uint32_t qi = list ? list[e] : e;
     float qx, qy, qz;
     uint64_t best;
@@ -891,10 +904,10 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
       if (m == 0) {
         if (lev == top) break;
         ++lev;   // pop
-        cur_lb = s_lb[wave][lev - 2][lane];
-        const uint32_t pr = s_rng[wave][lev - 2][lane];
+        cur_lb = s_lb[(lev - 2) * 64 + lane];
+        const uint32_t pr = s_rng[(lev - 2) * 64 + lane];
         rs = pr & (kMaxPyrRecords - 1u); rn = (pr >> 26) + 1u;
-        const unsigned long long pm = s_mask[wave][lev - 2];
+        const unsigned long long pm = s_mask[lev - 2];
         cur_m = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(pm >> 32)) << 32) |
                 (uint32_t)__builtin_amdgcn_readfirstlane((int)pm);
         continue;
@@ -963,9 +976,9 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
         }
       } else {
         // push the level, descend into child `sl`: its children's records are named by its own
-        s_lb[wave][lev - 2][lane] = cur_lb;
-        s_rng[wave][lev - 2][lane] = rs | ((rn - 1u) << 26);   // (lanes past the last child hold its copy: rn >= 1)
-        if (lane == 0) s_mask[wave][lev - 2] = cur_m;
+        s_lb[(lev - 2) * 64 + lane] = cur_lb;
+        s_rng[(lev - 2) * 64 + lane] = rs | ((rn - 1u) << 26);   // (lanes past the last child hold its copy: rn >= 1)
+        if (lane == 0) s_mask[lev - 2] = cur_m;
         const uint32_t cf = (uint32_t)__builtin_amdgcn_readlane((int)rs, sl), cn = (uint32_t)__builtin_amdgcn_readlane((int)rn, sl);
         --lev;
         PCD_FB_EXPAND(cf, cn);
@@ -978,32 +991,27 @@ __global__ __launch_bounds__(256) void k_nn_fallback(GridParams g, PyramidParams
     st_max_steps = q_steps > st_max_steps ? q_steps : st_max_steps;
     st_max_leaves = q_leaves > st_max_leaves ? q_leaves : st_max_leaves;
   }
-  if (collect_stats) {   // (uniform) one set of global atomics per WORKGROUP: same-address atomics serialise at ~10 ns
-    __shared__ unsigned long long s_st[4];   // each, and this grid has 65 k wavefronts (per wavefront: a 3 ms launch)
-    __shared__ unsigned int s_mx[2];
-    if (threadIdx.x < 4) s_st[threadIdx.x] = 0;
-    if (threadIdx.x < 2) s_mx[threadIdx.x] = 0;
-    __syncthreads();
-    if (lane == 0) {
-      atomicAdd(&s_st[0], st_pts); atomicAdd(&s_st[1], st_q); atomicAdd(&s_st[2], st_steps); atomicAdd(&s_st[3], st_leaves);
-      atomicMax(&s_mx[0], st_max_steps); atomicMax(&s_mx[1], st_max_leaves);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && s_st[1]) {
-      atomicAdd(&ctr->fallback_points, s_st[0]);
-      atomicAdd(&ctr->pair_evals, s_st[0]);
-      atomicAdd(&ctr->fallback_queries, s_st[1]);
-      atomicAdd(&ctr->fb_steps, s_st[2]); atomicAdd(&ctr->fb_leaves, s_st[3]);
-      atomicMax(&ctr->fb_max_steps, s_mx[0]); atomicMax(&ctr->fb_max_leaves, s_mx[1]);
-    }
+  if (probe && lane == 0) {
+    unsigned long long* const rec = wave_rec + 3u * blockIdx.x;
+    rec[0] = t_start; rec[1] = wall_clock64(); rec[2] = st_steps;
+  }
+  // (uniform) statistics passes only: one set of global atomics per wavefront.  Same-address atomics serialise at
+  // ~10 ns each, so a pass over the whole grid of 65 k wavefronts takes ~3 ms instead of 0.15; the plain kernel pays nothing
+  if ((collect_stats & 1) && lane == 0 && st_q) {
+    atomicAdd(&ctr->fallback_points, st_pts);
+    atomicAdd(&ctr->pair_evals, st_pts);
+    atomicAdd(&ctr->fallback_queries, st_q);
+    atomicAdd(&ctr->fb_steps, st_steps); atomicAdd(&ctr->fb_leaves, st_leaves);
+    atomicMax(&ctr->fb_max_steps, st_max_steps); atomicMax(&ctr->fb_max_leaves, st_max_leaves);
   }
 }
 
 // ------------------------------------------------------------- host driver ---
-// k_nn_fallback's grid: up to 4 x 16384 wavefronts, i.e. one or two queries per wavefront for lists up to 128 k and
-// the hardware's workgroup dispatch as the load balancer (query costs spread 1:4).  2048 / 4096 / 16384 / 65536
-// workgroups: 0.384 / 0.387 / 0.368 / 0.369 ms at workload M, 0.136 / 0.125 / 0.126 / 0.125 ms on an eighth of it.
-constexpr unsigned g_fb_max_blocks = 16384;
+// k_nn_fallback's grid: up to 65536 wavefronts (= workgroups), i.e. one or two queries per wavefront for lists up to 128 k
+// and the hardware's workgroup dispatch as the load balancer (query costs spread 1:4).  With four wavefronts per workgroup,
+// 2048 / 4096 / 16384 / 65536 workgroups: 0.384 / 0.387 / 0.368 / 0.369 ms at workload M, 0.136 / 0.125 / 0.126 / 0.125 ms
+// on an eighth of it.
+constexpr unsigned g_fb_max_blocks = 65536;
 // where k_nn_fallback finds its queries: prepared records (FUSED == 0) or the caller's doubles (FUSED != 0); the
 // queries list[0 .. *list_count), or without a list 0 .. n - 1 (n: an upper bound when the list's length is on the device)
 struct FbQueries {
@@ -1012,11 +1020,18 @@ struct FbQueries {
   const uint32_t *list, *list_count;
 };
 template <int FUSED>
-static void launch_fallback(const pcd_cloud* c, const float4* seeds, const FbQueries& src, uint64_t n, uint64_t* keys,
-                            NnCounters* ctr, int collect_stats, hipStream_t s) {
-  hipLaunchKernelGGL(k_nn_fallback<FUSED>, dim3((unsigned)std::min<uint64_t>(div_up(n, 4), g_fb_max_blocks)), dim3(256), 0,
+static pcd_status launch_fallback(const pcd_cloud* c, const float4* seeds, const FbQueries& src, uint64_t n, uint64_t* keys,
+                                  NnCounters* ctr, int collect_stats, hipStream_t s) {
+  const unsigned blocks = (unsigned)std::min<uint64_t>(n, g_fb_max_blocks);
+  QueryScratch* sc = c->scratch;   // (the callers' scratch_of(c))
+  if (collect_stats & 16) {   // a pass that keeps {start, end, steps} of every wavefront
+    PCD_TRY(sc->fb_rec.reserve(3 * (size_t)blocks));
+    sc->fb_rec_n = blocks;
+  }
+  hipLaunchKernelGGL(k_nn_fallback<FUSED>, dim3(blocks), dim3(64), fb_stack_bytes(c->pyr.nlev),
                      s, c->grid, c->pyr, c->sorted.p, c->cell_start.p, c->blk_aabb.p, seeds, src.qf4, src.list,
-                     src.list_count, src.list_count ? 0u : (uint32_t)n, keys, ctr, collect_stats, src.fused);
+                     src.list_count, src.list_count ? 0u : (uint32_t)n, keys, ctr, collect_stats, src.fused, sc->fb_rec.p);
+  return PCD_OK;
 }
 // process-global tuning state (pcd_nn_set_*: experiments and tests, not part of the stable ABI): independent atomic
 // switches, each read once at the top of a call
@@ -1086,7 +1101,7 @@ static pcd_status fb_seed_table(pcd_cloud* c, QueryScratch* sc, hipStream_t s) {
   PCD_TRY(keys.reserve(n));
   hipLaunchKernelGGL(k_seed_init, dim3(div_up(n, 256)), dim3(256), 0, s, c->grid, py.seed_dims[0], py.seed_dims[1],
                      py.seed_dims[2], seeds.p, qf4.p, keys.p);
-  launch_fallback<0>(c, seeds.p, {qf4.p}, n, keys.p, nullptr, 0, s);
+  PCD_TRY(launch_fallback<0>(c, seeds.p, {qf4.p}, n, keys.p, nullptr, 0, s));
   hipLaunchKernelGGL(k_seed_gather, dim3(div_up(n, 256)), dim3(256), 0, s, keys.p, n, c->shard_index(), c->pts4.p, seeds.p);
   PCD_HIP_TRY(hipGetLastError());
   PCD_HIP_TRY(hipStreamSynchronize(s));   // one-off per cloud; qf4 / keys go out of scope
@@ -1240,7 +1255,7 @@ static pcd_status run_grid(pcd_cloud* c, QueryScratch* sc, uint64_t Q, uint64_t*
     PCD_TRY(sc->fb_dense.reserve(Q));
     hipLaunchKernelGGL(k_fb_compact, dim3(div_up(fb_cap, kFbcThreads * kFbcPer)), dim3(kFbcThreads), 0, s, sc->fb_list.p,
                        &ctr->fb_count, sc->fb_dense.p, &ctr->pad[0]);
-    launch_fallback<0>(c, sc->fb_seed.p, {sc->qf4.p, {}, sc->fb_dense.p, &ctr->pad[0]}, Q, d_keys, ctr, collect_stats, s);
+    PCD_TRY(launch_fallback<0>(c, sc->fb_seed.p, {sc->qf4.p, {}, sc->fb_dense.p, &ctr->pad[0]}, Q, d_keys, ctr, collect_stats, s));
   }
   PCD_HIP_TRY(hipGetLastError());
   if (counting) counters_left_clean(sc);   // every launch went through: k_bk_slots has left the other block clean
@@ -1269,7 +1284,7 @@ static pcd_status nn_device(pcd_cloud* c, const NnCall& call, uint64_t Q, int al
   QueryScratch* sc = scratch_of(c);
   if (Q == 0) return PCD_OK;
   PCD_REQUIRE(Q < 0xFFFFFFF0ull, "more than 2^32 queries in one call");
-  sc->wave_rec_n = 0;   // (the grid path of a statistics pass sets it)
+  sc->wave_rec_n = sc->fb_rec_n = 0;   // (a statistics pass sets them: the grid path / the fallback walk)
   NnPath path;
   PCD_TRY(choose_path(c->m == 0, algo, Q, call.prep, &path));
   const int collect_stats = g_collect_stats.load();
@@ -1287,8 +1302,8 @@ static pcd_status nn_device(pcd_cloud* c, const NnCall& call, uint64_t Q, int al
       PCD_TRY(take_counters(sc, CtrUse::kClearForStats, collect_stats, s, &ctr));
       ScopedKernelTimer t("nn_fallback", s);
       const FbQueries src{nullptr, FbFused{call.pa.q, call.pa.max_range, call.pa.mr_count, call.pa.fixed_range}};
-      if (call.prep == kPrepBounded) launch_fallback<2>(c, sc->fb_seed.p, src, Q, d_keys, ctr, collect_stats, s);
-      else launch_fallback<1>(c, sc->fb_seed.p, src, Q, d_keys, ctr, collect_stats, s);
+      if (call.prep == kPrepBounded) PCD_TRY(launch_fallback<2>(c, sc->fb_seed.p, src, Q, d_keys, ctr, collect_stats, s));
+      else PCD_TRY(launch_fallback<1>(c, sc->fb_seed.p, src, Q, d_keys, ctr, collect_stats, s));
       break;
     }
     case NnPath::kPrepareWalk: {
@@ -1297,7 +1312,7 @@ static pcd_status nn_device(pcd_cloud* c, const NnCall& call, uint64_t Q, int al
       launch_prepare(call, Q, sc->qf4.p, d_keys, s);
       PCD_TRY(take_counters(sc, CtrUse::kClear, collect_stats, s, &ctr));
       ScopedKernelTimer t("nn_fallback", s);
-      launch_fallback<0>(c, sc->fb_seed.p, {sc->qf4.p}, Q, d_keys, ctr, collect_stats, s);
+      PCD_TRY(launch_fallback<0>(c, sc->fb_seed.p, {sc->qf4.p}, Q, d_keys, ctr, collect_stats, s));
       break;
     }
     case NnPath::kGrid:
@@ -1444,6 +1459,23 @@ pcd_status pcd_nn_last_wave_records(pcd_cloud* c, uint64_t* records, uint64_t ca
   return PCD_OK;
 }
 
+/* tools / tests: the same for k_nn_fallback, from the last call of a statistics pass with bit 16 -- {start, end, walk
+   steps} per wavefront, in the order blockIdx.x * waves_per_block + wave.  Syncs. */
+pcd_status pcd_nn_last_fb_wave_records(pcd_cloud* c, uint64_t* records, uint64_t cap_waves, uint64_t* nwaves,
+                                       uint64_t* waves_per_block) {
+  PCD_REQUIRE(c && nwaves && waves_per_block, "null pointer");
+  *nwaves = 0;
+  *waves_per_block = 1;
+  if (!c->scratch) return PCD_OK;
+  QueryScratch* sc = c->scratch;
+  PCD_HIP_TRY(hipSetDevice(c->device));
+  PCD_HIP_TRY(hipDeviceSynchronize());
+  *nwaves = sc->fb_rec_n;
+  const uint64_t n = std::min<uint64_t>(cap_waves, sc->fb_rec_n);
+  if (n && records) PCD_HIP_TRY(hipMemcpy(records, sc->fb_rec.p, n * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return PCD_OK;
+}
+
 pcd_status pcd_nn_set_bookkeeping(int radix_sort) {
   g_bk_sort = radix_sort ? 1 : 0;
   return PCD_OK;
@@ -1460,7 +1492,7 @@ pcd_status pcd_nn_set_tuning(int brick_cells, int halo_cells, int collect_stats)
 #ifdef PCD_ABLATE
   g_collect_stats = collect_stats;
 #else
-  g_collect_stats = collect_stats & 5;   // (4: per-wavefront records of the brick kernel) the ablation bits exist only in -DPCD_ABLATE builds
+  g_collect_stats = collect_stats & 21;   // (4 / 16: per-wavefront records of the brick kernel / of the fallback walk) the ablation bits exist only in -DPCD_ABLATE builds
 #endif
   return PCD_OK;
 }

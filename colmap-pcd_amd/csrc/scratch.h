@@ -51,6 +51,9 @@ struct QueryScratch {
   // k_nn_brick_clip launch, wall_clock64 ticks; reserved in such a pass only
   DevBuf<unsigned long long> wave_rec;
   uint32_t wave_rec_n = 0;
+  // the same for k_nn_fallback (bit 16): {start, end, walk steps} of every wavefront of its last launch
+  DevBuf<unsigned long long> fb_rec;
+  uint32_t fb_rec_n = 0;
   DevBuf<char> tmp;
   DevBuf<double> d_q;          // staging of host queries
   DevBuf<uint32_t> d_idx; DevBuf<float> d_sq; DevBuf<uint8_t> d_found;

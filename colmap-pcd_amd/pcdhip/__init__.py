@@ -390,6 +390,9 @@ def lib():
     if hasattr(L, "pcd_nn_last_wave_records"):   # (a library of an older tree, loaded through PCDHIP_LIB for A/B runs)
         L.pcd_nn_last_wave_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_uint64)]
+    if hasattr(L, "pcd_nn_last_fb_wave_records"):
+        L.pcd_nn_last_fb_wave_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]
     L.pcd_normals_options_default.argtypes = [C.POINTER(NormalsOptions)]
     L.pcd_normals_options_default.restype = None
     L.pcd_cloud_estimate_normals_device.argtypes = [C.c_void_p, C.POINTER(NormalsOptions), C.c_void_p, C.c_void_p,
@@ -717,6 +720,18 @@ class Cloud:
         if nw.value:
             _check(L.pcd_nn_last_wave_records(self._h, _vp(rec), nw.value, C.byref(nw), C.byref(ni)))
         return rec, int(ni.value)
+
+    def last_fb_wave_records(self):
+        """(records, waves per workgroup) of the last call that ran the fallback walk: records = uint64 [waves, 3] of
+        {start, end, walk steps} per wavefront of k_nn_fallback (wall-clock ticks), in the order workgroup * waves per
+        workgroup + wave; kept only by a pass with set_nn_tuning(collect_stats=16), else empty"""
+        L = lib()
+        nw, wpb = C.c_uint64(0), C.c_uint64(0)
+        _check(L.pcd_nn_last_fb_wave_records(self._h, None, 0, C.byref(nw), C.byref(wpb)))
+        rec = np.zeros((nw.value, 3), np.uint64)
+        if nw.value:
+            _check(L.pcd_nn_last_fb_wave_records(self._h, _vp(rec), nw.value, C.byref(nw), C.byref(wpb)))
+        return rec, int(wpb.value)
 
 
 def associate_from_payload_device(device, d_q, Q, d_max_range, mr_count, gate_mode, d_keys, d_payload, d_out,

@@ -1394,6 +1394,7 @@ pcd_status pcd_profile_get(pcd_kernel_time* entries, int cap, int* count);
 /* Not declared here on purpose: the tuning hooks bench.py / tools / tests use (pcd_nn_set_tuning, pcd_nn_set_search,
  * pcd_nn_set_schedule(0 | 1): the brick kernel's work schedule, 1 = static rounds alone; pcd_nn_schedule_params and
  * pcd_nn_last_wave_records: its constants and the per-wavefront records of a statistics pass with bit 4;
+ * pcd_nn_last_fb_wave_records: the same records of the fallback walk, bit 16;
  * pcd_nn_set_bookkeeping, pcd_sift_set_tuning(int nchunk, uint64_t batch_partials_int4): column chunks per stripe walk
  * and partial results per sub-batch in 16-byte units) set PROCESS-GLOBAL state -- they are for experiments on one
  * handle at a time, not part of the ABI, and the thread-safety statement at the top of this header does not cover

@@ -258,11 +258,8 @@ def l2(q, p):
     return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
 
 
-def main():
-    N = int(float(sys.argv[1])) if len(sys.argv) > 1 else 10_000_000
-    Q = int(float(sys.argv[2])) if len(sys.argv) > 2 else 1_000_000
-    per = int(sys.argv[3]) if len(sys.argv) > 3 else 5000
-    seed_cells = [int(s) for s in os.environ.get("FB_SIM_SEED_CELLS", "2,8").split(",")]
+def workload(N, Q, seed_cells):
+    """cloud, index, exact neighbours, the two fallback classes and the seed lattices of the bench's workload"""
     t = time.time()
     xyz, _ = synth.cloud_planes(N)
     q = synth.queries(xyz, Q, seed=99)
@@ -308,11 +305,6 @@ def main():
     open_ = ~empty & ~(nn_in_region & (dnn_f < bound))
     print("queries %d: empty-halo / outside %d, open %d -> fallback %d" % (Q, empty.sum(), open_.sum(),
                                                                           empty.sum() + open_.sum()), flush=True)
-    rng = np.random.default_rng(5)
-    samples = {}
-    for name, sel in (("empty", empty), ("open", open_)):
-        ids = np.nonzero(sel)[0]
-        samples[name] = np.sort(rng.choice(ids, min(per, len(ids)), replace=False))
     # seeds: the exact nearest point to the centre of every cell of a lattice of s x s x s grid cells
     seeds = {}
     for s in seed_cells:
@@ -323,6 +315,37 @@ def main():
         _, si = tree.query(ctr, workers=-1)
         seeds[s] = (sd, si)
         print("seed lattice %d cells: %s = %d seeds, %.1fs" % (s, sd.tolist(), len(si), time.time() - t), flush=True)
+    return dict(xyz=xyz, qf=qf, ix=ix, dims=dims, craw=craw, cell=cell, empty=empty, open_=open_, dnn_f=dnn_f, seeds=seeds)
+
+
+def start_key(W, i, name, seed_s):
+    """the key a walk of query i starts from: kKeyInit (empty) or the region-restricted result (open), and the seed"""
+    ix, qf = W["ix"], W["qf"]
+    if name == "empty":
+        best = (F(np.finfo(F).max), 0)
+    else:
+        rb = ix.region_min(qf[i], W["cell"][i])
+        best = (F(rb[0]), rb[1]) if rb[1] >= 0 else (F(np.finfo(F).max), 0)
+    if seed_s is not None:
+        sd, si = W["seeds"][seed_s]
+        sc = np.clip(W["craw"][i], 0, W["dims"] - 1).astype(np.int64) // seed_s
+        k = si[(sc[2] * sd[1] + sc[1]) * sd[0] + sc[0]]
+        best = min(best, (l2(qf[i], W["xyz"][k]), int(k)))
+    return best
+
+
+def main():
+    N = int(float(sys.argv[1])) if len(sys.argv) > 1 else 10_000_000
+    Q = int(float(sys.argv[2])) if len(sys.argv) > 2 else 1_000_000
+    per = int(sys.argv[3]) if len(sys.argv) > 3 else 5000
+    seed_cells = [int(s) for s in os.environ.get("FB_SIM_SEED_CELLS", "2,8").split(",")]
+    W = workload(N, Q, seed_cells)
+    ix, qf, empty, open_, dnn_f = W["ix"], W["qf"], W["empty"], W["open_"], W["dnn_f"]
+    rng = np.random.default_rng(5)
+    samples = {}
+    for name, sel in (("empty", empty), ("open", open_)):
+        ids = np.nonzero(sel)[0]
+        samples[name] = np.sort(rng.choice(ids, min(per, len(ids)), replace=False))
     rows = []
     for name, ids in samples.items():
         for case, seed_s, slab in [("a today", None, False)] + \
@@ -332,16 +355,7 @@ def main():
             ix.reset_traffic()
             st = np.zeros((len(ids), 3), np.int64)
             for r, i in enumerate(ids):
-                if name == "empty":
-                    best = (F(np.finfo(F).max), 0)
-                else:
-                    rb = ix.region_min(qf[i], cell[i])
-                    best = (F(rb[0]), rb[1]) if rb[1] >= 0 else (F(np.finfo(F).max), 0)
-                if seed_s is not None:
-                    sd, si = seeds[seed_s]
-                    sc = np.clip(craw[i], 0, dims - 1).astype(np.int64) // seed_s
-                    k = si[(sc[2] * sd[1] + sc[1]) * sd[0] + sc[0]]
-                    best = min(best, (l2(qf[i], xyz[k]), int(k)))
+                best = start_key(W, i, name, seed_s)
                 steps, leaves, pts, res = ix.walk(qf[i], best, slab)
                 if res[0] > dnn_f[i]:   # (below it: float ties / rounding against the double-precision tree)
                     raise SystemExit("model walk is not exact for query %d: %r vs %r" % (i, res, dnn_f[i]))
