@@ -1171,31 +1171,9 @@ __global__ __launch_bounds__(256) void k_ba_proj_centers(int I, const double* __
                                                          double* __restrict__ centers) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= I) return;
-  const double* pose = poses + 7 * (size_t)i;
-  double q[4] = {pose[0], pose[1], pose[2], pose[3]};
-  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  if (n == 0.0) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; }
-  else { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; }
-  const double qc[4] = {q[0], -q[1], -q[2], -q[3]};
-  const double mt[3] = {-pose[4], -pose[5], -pose[6]}, zero[3] = {0.0, 0.0, 0.0};
   double c[3];
-  pose_transform(qc, zero, mt, c);
+  proj_center(poses + 7 * (size_t)i, c);
   centers[3 * (size_t)i] = c[0]; centers[3 * (size_t)i + 1] = c[1]; centers[3 * (size_t)i + 2] = c[2];
-}
-
-// CalculateTriangulationAngle (base/triangulation.cc:122-145): a NaN (the acos argument outside [-1, 1] by rounding)
-// passes through fabs and the min (std::min(a, b) = b < a ? b : a) and then fails every >=
-__device__ __forceinline__ double tri_angle(const double c1[3], const double c2[3], const double X[3]) {
-  const double b0 = c1[0] - c2[0], b1 = c1[1] - c2[1], b2 = c1[2] - c2[2];
-  const double r0 = X[0] - c1[0], r1 = X[1] - c1[1], r2 = X[2] - c1[2];
-  const double s0 = X[0] - c2[0], s1 = X[1] - c2[1], s2 = X[2] - c2[2];
-  const double base2 = b0 * b0 + b1 * b1 + b2 * b2;
-  const double ray1 = r0 * r0 + r1 * r1 + r2 * r2, ray2 = s0 * s0 + s1 * s1 + s2 * s2;
-  const double den = 2.0 * sqrt(ray1 * ray2);
-  if (den == 0.0) return 0.0;
-  const double angle = fabs(acos((ray1 + ray2 - base2) / den));
-  const double other = 3.14159265358979323846 - angle;
-  return other < angle ? other : angle;
 }
 
 // thread = point, on what stage 1 (k_ba_filter_tracks) left in obs_erase / point_delete / point_error, all three

@@ -43,11 +43,12 @@ __global__ __launch_bounds__(256) void k_edit_obs_flag(uint32_t O, const uint8_t
   if (o > O) return;
   flag[o] = (o < O && !(erase && erase[o]) && !(pdel && pdel[obs_point[o]])) ? 1u : 0u;
 }
-__global__ __launch_bounds__(256) void k_edit_term_flag(uint32_t L, const uint8_t* __restrict__ pdel,
+__global__ __launch_bounds__(256) void k_edit_term_flag(uint32_t L, const uint8_t* __restrict__ erase,
+                                                        const uint8_t* __restrict__ pdel,
                                                         const int* __restrict__ lidar_point, uint32_t* __restrict__ flag) {
   const uint32_t l = blockIdx.x * 256u + threadIdx.x;
   if (l > L) return;
-  flag[l] = (l < L && !(pdel && pdel[lidar_point[l]])) ? 1u : 0u;
+  flag[l] = (l < L && !(erase && erase[l]) && !(pdel && pdel[lidar_point[l]])) ? 1u : 0u;
 }
 // out[k] = flag[list[k]], out[n] = 0
 __global__ __launch_bounds__(256) void k_edit_list_flag(uint32_t n, const uint32_t* __restrict__ list,
@@ -272,8 +273,8 @@ pcd_status edit_reserve(const pcd_ba* b, BaEditScratch& N, unsigned terms, bool 
   return N.prim.reserve(need);
 }
 
-pcd_status edit_compact(const pcd_ba* b, BaEditScratch& N, const uint8_t* d_erase, const uint8_t* d_pdel, const uint8_t* cpose,
-                        uint32_t* d_map, hipStream_t s) {
+pcd_status edit_compact(const pcd_ba* b, BaEditScratch& N, const uint8_t* d_erase, const uint8_t* d_pdel,
+                        const uint8_t* d_term_erase, const uint8_t* cpose, uint32_t* d_map, hipStream_t s) {
   BaLayout& Y = N.layout;
   BaTerms& T = N.terms;
   const uint32_t O = (uint32_t)b->O, L = (uint32_t)b->L, P = (uint32_t)b->P, I = (uint32_t)b->I;
@@ -292,7 +293,8 @@ pcd_status edit_compact(const pcd_ba* b, BaEditScratch& N, const uint8_t* d_eras
       PCD_TRY(scan_flags(N, N.v_flag.p, N.v_pos.p, (size_t)O + 1, s));
     }
     if (L) {
-      hipLaunchKernelGGL(k_edit_term_flag, grid((uint64_t)L + 1), dim3(256), 0, s, L, d_pdel, b->lidar_point.p, N.lf.p);
+      hipLaunchKernelGGL(k_edit_term_flag, grid((uint64_t)L + 1), dim3(256), 0, s, L, d_term_erase, d_pdel, b->lidar_point.p,
+                         N.lf.p);
       PCD_TRY(scan_flags(N, N.lf.p, N.lp.p, (size_t)L + 1, s));
       hipLaunchKernelGGL(k_edit_list_flag, grid((uint64_t)L + 1), dim3(256), 0, s, L, b->pt_lidar_list.p, N.lf.p, N.lt_flag.p);
       PCD_TRY(scan_flags(N, N.lt_flag.p, N.lt_pos.p, (size_t)L + 1, s));
@@ -340,7 +342,7 @@ static pcd_status edit_rebuild(pcd_ba* b, const uint8_t* d_erase, const uint8_t*
   PCD_TRY(edit_reserve(b, N, terms, b->has_cpose, kRecWords));
   EventPair ev;
   if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
-  PCD_TRY(edit_compact(b, N, d_erase, d_pdel, b->const_poses(), d_map, s));
+  PCD_TRY(edit_compact(b, N, d_erase, d_pdel, nullptr, b->const_poses(), d_map, s));
   PCD_TRY(edit_read_record(N, kRecWords, I, info ? &ev : nullptr, s));
   const uint32_t* rec = N.h_record.p;
   const uint32_t nO = rec[kRecObs], nL = rec[kRecTerms];

@@ -10,6 +10,8 @@
 //                 pcd_ba_add_observations_device
 //   ba_window.hip derives a second handle, the sphere window of a global round, from a live one and carries its
 //                 parameters back: pcd_ba_window_create_device, pcd_ba_window_commit_device
+//   ba_local.hip  the local round's start: FindLocalBundle on the handle and the local sub-problem as a second handle:
+//                 pcd_ba_local_bundle_device, pcd_ba_local_window_create_device
 #pragma once
 #include <memory>
 
@@ -178,6 +180,16 @@ struct BaEditScratch {
   PinnedBuf<uint32_t> h_record;                           // the counts, then img_obs_start [I+1]
 };
 
+// Scratch of pcd_ba_local_bundle_device (ba_local.hip): rows of `image` per point [P]; per image the sort key
+// (~shared) and the image, before and after the stable sort [I]; the percentile of every rank [I]; the ranks taken [I];
+// the head (candidates, rows of `image`, num_eff, short case)
+struct BaLocalScratch {
+  DevBuf<uint32_t> mult, key, key_sorted, iota, img_sorted, head;
+  DevBuf<double> tri;
+  DevBuf<uint8_t> used;
+  DevBuf<char> prim;
+};
+
 // The point-elimination state is complete in ba_solve.hip only.  The deleter is defined there, so a pcd_ba can be
 // made and destroyed where BaSchur is an incomplete type (the default deleter would need the complete one).
 struct BaSchur;
@@ -238,8 +250,8 @@ namespace pcd {
 // the new BaLayout / BaTerms are built in (the removal: src's own edit_next; the window: the new handle's).
 //   edit_reserve      every buffer edit_compact writes, at the sizes of src: nothing is allocated after the first launch.
 //                     terms: the groups to build (0: src has no terms); pose_rows: vobs is built; words: the record's length
-//   edit_compact      observation o stays iff !d_erase[o] && !d_pdel[obs_point[o]], term l iff !d_pdel[lidar_point[l]]
-//                     (either may be null).  cpose (null: no packed pose rows) is the constness mask the pose rows are
+//   edit_compact      observation o stays iff !d_erase[o] && !d_pdel[obs_point[o]], term l iff !d_term_erase[l] &&
+//                     !d_pdel[lidar_point[l]] (each may be null).  cpose (null: no packed pose rows) is the constness mask the pose rows are
 //                     taken with.  Flags, scans, compaction of rows and both CSRs, the derived layouts, the sliced-ELL and
 //                     per-track fills; the counts go to N.record[0 .. kRecWords).  Enqueued on s, no wait.
 //   edit_read_record  the ONE synchronisation: `words` of the record and the new image bounds arrive in N.h_record;
@@ -247,13 +259,34 @@ namespace pcd {
 enum { kRecObs = 0, kRecTerms, kRecSegs, kRecPoseRows, kRecEmptied, kRecWords };
 pcd_status edit_reserve(const pcd_ba* src, BaEditScratch& N, unsigned terms, bool pose_rows, size_t words);
 pcd_status edit_compact(const pcd_ba* src, BaEditScratch& N, const uint8_t* d_erase, const uint8_t* d_pdel,
-                        const uint8_t* cpose, uint32_t* d_map, hipStream_t s);
+                        const uint8_t* d_term_erase, const uint8_t* cpose, uint32_t* d_map, hipStream_t s);
 pcd_status edit_read_record(BaEditScratch& N, size_t words, uint32_t I, EventPair* ev, hipStream_t s);
 // ba_build.hip: what a handle holds besides its rows and terms, copied from a live one on the device (the window
 // derivation): counts that do not change (C, I, P), cameras with their host mirrors, camera slots and refine state,
 // image_cam and the cam_img CSR, the parameters as they are on the device now, image_const_tvec / point_const /
 // cam_refine.  image_const_pose is reserved [I] and left to the caller, has_cpose is set.  Copies are enqueued on s.
 pcd_status ba_clone_problem(const pcd_ba* src, pcd_ba* dst, hipStream_t s);
+
+// ba_window.hip: the derivation both windows share.  A selection names what it adds to the sequence
+//   reserve (its own buffers, before the first launch), ba_clone_problem, select (its kernels: the window's pose mask in
+//   w->image_const_pose, and the masks the compaction takes), edit_compact into the window's edit_next, record (its
+//   counts behind the removal's, record words kRecWords .. words), edit_read_record (the ONE synchronisation), the
+//   image-major fill, the swaps.
+// On success *out is the window and its edit_next.h_record holds the `words` counts; build_ms (may be null) is the device
+// time up to the synchronisation.
+struct WindowMasks { const uint8_t* obs_erase = nullptr; const uint8_t* point_delete = nullptr; const uint8_t* term_erase = nullptr; };
+struct WindowSelection {
+  size_t words = kRecWords;
+  virtual ~WindowSelection() = default;
+  virtual pcd_status reserve(const pcd_ba* src, pcd_ba* w) = 0;
+  virtual pcd_status select(const pcd_ba* src, pcd_ba* w, hipStream_t s, WindowMasks* m) = 0;
+  virtual pcd_status record(pcd_ba* w, hipStream_t s) = 0;
+};
+pcd_status window_derive(const pcd_ba* src, WindowSelection& sel, uint32_t* d_map, hipStream_t s, pcd_ba** out, float* build_ms);
+// k_win_images of ba_window.hip: in[i] (the caller's set, or the sphere around `center`), the window's pose mask
+// cpose[i] = src's | !in | extra, and part[workgroup of 256 images] = its images that are in
+void launch_win_images(const pcd_ba* src, int center, double radius, const uint8_t* set, const uint8_t* extra, uint8_t* in,
+                       uint8_t* cpose, uint32_t* part, hipStream_t s);
 
 }  // namespace pcd
 
@@ -277,6 +310,7 @@ struct pcd_ba : pcd::BaLayout, pcd::BaTerms {
   bool has_lidar_meta = false;   // lidar_type / lidar_xyz exist (BaTerms)
   pcd::BaLidarScratch lidar_next;
   pcd::BaEditScratch edit_next;
+  pcd::BaLocalScratch local_next;
   pcd::DevBuf<uint32_t> cam_img_start, cam_img_list;
   uint32_t nseg = 0;
   pcd::DevBuf<double> img_partial;

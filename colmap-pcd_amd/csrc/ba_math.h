@@ -129,6 +129,33 @@ __device__ __forceinline__ void pose_transform(const double q[4], const double t
   P[2] = X[2] + w * uz + (a * uy - bq * ux) + t[2];
 }
 
+// ProjectionCenterFromPose (base/pose.cc:164-171): the normalised quaternion conjugated and applied to -tvec; a zero
+// quaternion counts as the identity.  k_ba_proj_centers (ba.hip) and the local bundle (ba_local.hip) share it.
+__device__ __forceinline__ void proj_center(const double* __restrict__ pose, double c[3]) {
+  double q[4] = {pose[0], pose[1], pose[2], pose[3]};
+  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  if (n == 0.0) { q[0] = 1.0; q[1] = q[2] = q[3] = 0.0; }
+  else { q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n; }
+  const double qc[4] = {q[0], -q[1], -q[2], -q[3]};
+  const double mt[3] = {-pose[4], -pose[5], -pose[6]}, zero[3] = {0.0, 0.0, 0.0};
+  pose_transform(qc, zero, mt, c);
+}
+
+// CalculateTriangulationAngle (base/triangulation.cc:122-145): a NaN (the acos argument outside [-1, 1] by rounding)
+// passes through fabs and the min (std::min(a, b) = b < a ? b : a) and then fails every >=
+__device__ __forceinline__ double tri_angle(const double c1[3], const double c2[3], const double X[3]) {
+  const double b0 = c1[0] - c2[0], b1 = c1[1] - c2[1], b2 = c1[2] - c2[2];
+  const double r0 = X[0] - c1[0], r1 = X[1] - c1[1], r2 = X[2] - c1[2];
+  const double s0 = X[0] - c2[0], s1 = X[1] - c2[1], s2 = X[2] - c2[2];
+  const double base2 = b0 * b0 + b1 * b1 + b2 * b2;
+  const double ray1 = r0 * r0 + r1 * r1 + r2 * r2, ray2 = s0 * s0 + s1 * s1 + s2 * s2;
+  const double den = 2.0 * sqrt(ray1 * ray2);
+  if (den == 0.0) return 0.0;
+  const double angle = fabs(acos((ray1 + ray2 - base2) / den));
+  const double other = 3.14159265358979323846 - angle;
+  return other < angle ? other : angle;
+}
+
 struct ReprojBlock {
   double r[2];
   double M[6];   // d r / d P  (2x3) = A * d(u,v)/dP ;  J_t = M

@@ -15,7 +15,8 @@
 //   edit_read_record    the ONE synchronisation; the image-major fill follows it
 // The removal builds in the handle's own scratch and swaps; here the scratch is the NEW handle's (its edit_next), and the
 // swap makes the result that handle's layout and terms.  The source is only read.  No atomics; nothing depends on the
-// launch geometry.
+// launch geometry.  The sequence itself is window_derive (declared in ba_handle.h): the sphere's selection here and the
+// local round's (ba_local.hip) are the two WindowSelections it runs.
 #include "ba_handle.h"
 
 namespace pcd {
@@ -97,8 +98,15 @@ __global__ __launch_bounds__(256) void k_win_record(uint32_t nbi, uint32_t nbp, 
   if (threadIdx.x == 0) { rec[kWinImagesIn] = s_i[0]; rec[kWinPointsActive] = s_p[0]; }
 }
 
-static pcd_status window_create(const pcd_ba* src, const pcd_ba_window_opts* o, uint8_t* d_in, uint8_t* d_active,
-                                uint32_t* d_map, hipStream_t s, pcd_ba** out, pcd_ba_window_info* info) {
+void launch_win_images(const pcd_ba* src, int center, double radius, const uint8_t* set, const uint8_t* extra, uint8_t* in,
+                       uint8_t* cpose, uint32_t* part, hipStream_t s) {
+  const uint32_t I = (uint32_t)src->I;
+  hipLaunchKernelGGL(k_win_images, dim3(div_up(I, 256)), dim3(256), 0, s, I, src->poses.p, center, radius, set,
+                     src->const_poses(), extra, in, cpose, part);
+}
+
+pcd_status window_derive(const pcd_ba* src, WindowSelection& sel, uint32_t* d_map, hipStream_t s, pcd_ba** out,
+                         float* build_ms) {
   struct Destroy { void operator()(pcd_ba* p) const { pcd_ba_destroy(p); } };
   std::unique_ptr<pcd_ba, Destroy> owner(new pcd_ba());   // destroys the window on every failing return below
   pcd_ba* w = owner.get();
@@ -107,34 +115,27 @@ static pcd_status window_create(const pcd_ba* src, const pcd_ba_window_opts* o, 
   const bool meta = src->has_lidar_meta;
   const unsigned terms = L ? kTermRows | (meta ? kTermMeta : 0u) | kTermIndex | kTermTracks : 0u;
   // every buffer before the first launch: the selection's flags, the new handle's own arrays, the layout and the terms
-  DevBuf<uint8_t> in_own, pdel;
-  if (!d_in) { PCD_TRY(in_own.reserve(I)); d_in = in_own.p; }
-  PCD_TRY(pdel.reserve(P));
-  const uint32_t nbi = div_up(I, 256), nbp = div_up(P, 256);   // the workgroups of k_win_images / k_win_points
-  DevBuf<uint32_t> part;
-  PCD_TRY(part.reserve((size_t)nbi + nbp));
-  PCD_TRY(edit_reserve(src, N, terms, /*pose_rows=*/true, kWinWords));
+  PCD_TRY(sel.reserve(src, w));
+  PCD_TRY(edit_reserve(src, N, terms, /*pose_rows=*/true, sel.words));
   if (!L) {   // no terms to compact: what pcd_ba_create makes of an empty list (the meta when src has it)
     PCD_TRY(w->reserve_terms(kTermRows | (meta ? kTermMeta : 0u) | kTermIndex, 0, P, 0));
   }
   PCD_TRY(reserve_cost_partial(w, (size_t)src->nslices, src->O, src->L));
   PCD_TRY(w->cost.reserve(1));
   EventPair ev;
-  if (info) { PCD_TRY(ev.create()); (void)ev.start(s); }
+  if (build_ms) { PCD_TRY(ev.create()); (void)ev.start(s); }
   PCD_TRY(ba_clone_problem(src, w, s));
+  WindowMasks m;
   {
     ScopedKernelTimer t("ba_window_select", s);
-    hipLaunchKernelGGL(k_win_images, dim3(nbi), dim3(256), 0, s, I, src->poses.p, (int)o->center_image, o->radius,
-                       o->d_image_set, src->const_poses(), o->d_extra_const_pose, d_in, w->image_const_pose.p, part.p);
-    hipLaunchKernelGGL(k_win_points, dim3(nbp), dim3(256), 0, s, P, src->pt_obs_start.p, src->pt_obs_list.p,
-                       src->obs_image.p, d_in, d_active, pdel.p, part.p + nbi);
+    PCD_TRY(sel.select(src, w, s, &m));
     PCD_HIP_TRY(hipGetLastError());
   }
   if (!L) PCD_HIP_TRY(hipMemsetAsync(w->pt_lidar_start.p, 0, ((size_t)P + 1) * sizeof(uint32_t), s));
-  PCD_TRY(edit_compact(src, N, nullptr, pdel.p, w->image_const_pose.p, d_map, s));
-  hipLaunchKernelGGL(k_win_record, dim3(1), dim3(256), 0, s, nbi, nbp, part.p, N.record.p);
+  PCD_TRY(edit_compact(src, N, m.obs_erase, m.point_delete, m.term_erase, w->image_const_pose.p, d_map, s));
+  PCD_TRY(sel.record(w, s));
   PCD_HIP_TRY(hipGetLastError());
-  PCD_TRY(edit_read_record(N, kWinWords, I, info ? &ev : nullptr, s));
+  PCD_TRY(edit_read_record(N, sel.words, I, build_ms ? &ev : nullptr, s));
   const uint32_t* rec = N.h_record.p;
   // behind the synchronisation: the fill that needs the count, then what was built becomes the window's
   launch_fill_image_major(N.layout, rec[kRecObs], s);
@@ -144,19 +145,60 @@ static pcd_status window_create(const pcd_ba* src, const pcd_ba_window_opts* o, 
   w->O = rec[kRecObs]; w->L = rec[kRecTerms]; w->nslices = src->nslices;
   w->nseg = rec[kRecSegs]; w->n_pose_rows = rec[kRecPoseRows];
   w->has_lidar_meta = meta;
-  w->h_img_obs_start.assign(rec + kWinWords, rec + kWinWords + I + 1);
+  w->h_img_obs_start.assign(rec + sel.words, rec + sel.words + I + 1);
   w->pose_row_stale = true;   // h_pose_row: refreshed by the first pcd_ba_evaluate_blocks, as after a removal
   // The work buffers of N, sized by the source, stay with the window until it is closed (they are the scratch of its own
   // edits).  Freeing them here was measured: ~20 hipFree add 1.3 - 2.9 ms to the call's 3.4 - 4.9 ms at workload M and
   // slow the allocations of the structure build that follows.
+  if (build_ms) PCD_HIP_TRY(ev.elapsed(build_ms));
+  *out = owner.release();
+  return PCD_OK;
+}
+
+// The sphere's selection: the images in, the active points; an inactive point is deleted with its rows and terms
+struct SphereSelection : WindowSelection {
+  const pcd_ba_window_opts* o;
+  uint8_t* d_in;
+  uint8_t* d_active;
+  DevBuf<uint8_t> in_own, pdel;
+  DevBuf<uint32_t> part;
+  uint32_t nbi = 0, nbp = 0;   // the workgroups of k_win_images / k_win_points
+  SphereSelection(const pcd_ba_window_opts* opts, uint8_t* in, uint8_t* active) : o(opts), d_in(in), d_active(active) {
+    words = kWinWords;
+  }
+  pcd_status reserve(const pcd_ba* src, pcd_ba*) override {
+    const uint32_t I = (uint32_t)src->I, P = (uint32_t)src->P;
+    if (!d_in) { PCD_TRY(in_own.reserve(I)); d_in = in_own.p; }
+    PCD_TRY(pdel.reserve(P));
+    nbi = div_up(I, 256); nbp = div_up(P, 256);
+    return part.reserve((size_t)nbi + nbp);
+  }
+  pcd_status select(const pcd_ba* src, pcd_ba* w, hipStream_t s, WindowMasks* m) override {
+    launch_win_images(src, (int)o->center_image, o->radius, o->d_image_set, o->d_extra_const_pose, d_in,
+                      w->image_const_pose.p, part.p, s);
+    hipLaunchKernelGGL(k_win_points, dim3(nbp), dim3(256), 0, s, (uint32_t)src->P, src->pt_obs_start.p, src->pt_obs_list.p,
+                       src->obs_image.p, d_in, d_active, pdel.p, part.p + nbi);
+    m->point_delete = pdel.p;
+    return PCD_OK;
+  }
+  pcd_status record(pcd_ba* w, hipStream_t s) override {
+    hipLaunchKernelGGL(k_win_record, dim3(1), dim3(256), 0, s, nbi, nbp, part.p, w->edit_next.record.p);
+    return PCD_OK;
+  }
+};
+
+static pcd_status window_create(const pcd_ba* src, const pcd_ba_window_opts* o, uint8_t* d_in, uint8_t* d_active,
+                                uint32_t* d_map, hipStream_t s, pcd_ba** out, pcd_ba_window_info* info) {
+  SphereSelection sel(o, d_in, d_active);
+  float ms = 0.f;
+  PCD_TRY(window_derive(src, sel, d_map, s, out, info ? &ms : nullptr));
   if (info) {
-    float ms = 0.f;
-    PCD_HIP_TRY(ev.elapsed(&ms));
+    const pcd_ba* w = *out;
+    const uint32_t* rec = w->edit_next.h_record.p;
     info->num_images_in = rec[kWinImagesIn]; info->num_points_active = rec[kWinPointsActive];
     info->num_obs = w->O; info->num_lidar = w->L; info->num_pose_rows = w->n_pose_rows;
     info->build_ms = ms;
   }
-  *out = owner.release();
   return PCD_OK;
 }
 

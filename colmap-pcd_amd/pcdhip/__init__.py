@@ -255,6 +255,24 @@ class BAWindowInfo(C.Structure):
                                            "num_pose_rows")] + [("build_ms", C.c_double)]
 
 
+class BALocalBundleOpts(C.Structure):
+    """pcd_ba_local_bundle_opts (pcdhip.h)."""
+    _fields_ = [("image", C.c_int32), ("num_images", C.c_int32), ("min_tri_angle_deg", C.c_double),
+                ("reserved", C.c_int32 * 8)]
+
+
+class BALocalWindowOpts(C.Structure):
+    """pcd_ba_local_window_opts (pcdhip.h)."""
+    _fields_ = [("d_image_set", C.c_void_p), ("d_point_variable", C.c_void_p), ("image", C.c_int32),
+                ("max_track_length", C.c_uint32), ("d_extra_const_pose", C.c_void_p), ("reserved", C.c_int32 * 8)]
+
+
+class BALocalWindowInfo(C.Structure):
+    """pcd_ba_local_window_info (pcdhip.h)."""
+    _fields_ = [(n, C.c_uint64) for n in ("num_images_in", "num_points_variable", "num_points_fixed", "num_obs",
+                                           "num_lidar", "num_pose_rows")] + [("build_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -327,6 +345,8 @@ ABI_SYMBOLS = [
     "pcd_ba_remove_observations_device", "pcd_ba_add_observations_device", "pcd_ba_add_observations",
     "pcd_ba_schur_build_device", "pcd_ba_schur_structure_lists",
     "pcd_ba_window_opts_default", "pcd_ba_window_create_device", "pcd_ba_window_commit_device",
+    "pcd_ba_local_bundle_opts_default", "pcd_ba_local_bundle_device", "pcd_ba_local_bundle",
+    "pcd_ba_local_window_opts_default", "pcd_ba_local_window_create_device",
 ]
 
 
@@ -484,6 +504,15 @@ def lib():
         L.pcd_ba_window_create_device.argtypes = [C.c_void_p, C.POINTER(BAWindowOpts), C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(BAWindowInfo)]
         L.pcd_ba_window_commit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "pcd_ba_local_bundle_device"):
+        L.pcd_ba_local_bundle_opts_default.argtypes = [C.POINTER(BALocalBundleOpts)]
+        L.pcd_ba_local_bundle_opts_default.restype = None
+        L.pcd_ba_local_bundle_device.argtypes = [C.c_void_p, C.POINTER(BALocalBundleOpts)] + [C.c_void_p] * 6
+        L.pcd_ba_local_bundle.argtypes = [C.c_void_p, C.POINTER(BALocalBundleOpts)] + [C.c_void_p] * 4
+        L.pcd_ba_local_window_opts_default.argtypes = [C.POINTER(BALocalWindowOpts)]
+        L.pcd_ba_local_window_opts_default.restype = None
+        L.pcd_ba_local_window_create_device.argtypes = [C.c_void_p, C.POINTER(BALocalWindowOpts), C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(BALocalWindowInfo)]
     _LIB = L
     return L
 
@@ -1451,6 +1480,27 @@ class BA:
             self.__dict__.pop("_schur_dims", None)                    # the co-visibility structure is built anew
         return {k: getattr(info, k) for k, _ in BAAddInfo._fields_}
 
+    def _window_object(self, h, info, t_in, extra):
+        """the BA of a window handle `h` derived from this one: this object's description with the window's counts and
+        the host mirror of its pose mask"""
+        w = BA.__new__(BA)
+        w.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("_h", "_schur_dims")})
+        w._h = h
+        w.O, w.L = int(info.num_obs), int(info.num_lidar)
+        w.obs_image = w.obs_point = w.obs_xy = None                # the handle has the rows and the terms
+        w.lidar_point = w.lidar_abcd = w.lidar_weight = None
+        # the host mirror of the window's pose mask (BA._cam_dims counts the pose slots from it): src's | !in | extra,
+        # from O(I) bytes read back behind the call's own synchronisation
+        cpose = t_in.cpu().numpy() == 0
+        if self.image_const_pose is not None:
+            cpose |= self.image_const_pose != 0
+        if extra is not None:
+            cpose |= extra.cpu().numpy() != 0
+        w.image_const_pose = cpose.astype(np.uint8)
+        w.__dict__.pop("_ncs", None)
+        w.poses = w.points = None                                  # BA.get_parameters() has the current ones
+        return w
+
     def sphere_window(self, center_image=None, radius=40.0, image_set=None, extra_const_pose=None, want=()):
         """pcd_ba_window_create_device: the sphere sub-problem of one global round (AdjustGlobalBundleByLidar) as a NEW
         handle derived on the device; this handle is only read.  The images within `radius` of center_image's projection
@@ -1481,27 +1531,85 @@ class BA:
         h, info = C.c_void_p(), BAWindowInfo()
         _check(lib().pcd_ba_window_create_device(self._h, C.byref(o), _ptr(t_in), _ptr(t_act), _ptr(t_map),
                                                  C.c_void_p(stream), C.byref(h), C.byref(info)))
-        w = BA.__new__(BA)
-        w.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("_h", "_schur_dims")})
-        w._h = h
-        w.O, w.L = int(info.num_obs), int(info.num_lidar)
-        w.obs_image = w.obs_point = w.obs_xy = None                # the handle has the rows and the terms
-        w.lidar_point = w.lidar_abcd = w.lidar_weight = None
-        # the host mirror of the window's pose mask (BA._cam_dims counts the pose slots from it): src's | !in | extra,
-        # from O(I) bytes read back behind the call's own synchronisation
-        cpose = t_in.cpu().numpy() == 0
-        if self.image_const_pose is not None:
-            cpose |= self.image_const_pose != 0
-        if extra is not None:
-            cpose |= extra.cpu().numpy() != 0
-        w.image_const_pose = cpose.astype(np.uint8)
-        w.__dict__.pop("_ncs", None)
-        w.poses = w.points = None                                  # BA.get_parameters() has the current ones
+        w = self._window_object(h, info, t_in, extra)
         out = {k: getattr(info, k) for k, _ in BAWindowInfo._fields_}
         if "image_in" in want:
             out["image_in"] = t_in
         if "point_active" in want:
             out["point_active"] = t_act
+        if "obs_map" in want:
+            out["obs_map"] = t_map if t_map is not None else torch.empty(0, dtype=torch.int32, device=dev)
+        return w, out
+
+    def local_bundle(self, image, num_images=6, min_tri_angle=6.0, want=(), read_back=True):
+        """pcd_ba_local_bundle_device: IncrementalMapper::FindLocalBundle for `image` on this handle -- the at most
+        num_images - 1 most connected images with a sufficient triangulation angle (pcdhip.h states the selection).  The
+        library call does not synchronise; this method then reads the bundle back, which waits for the current stream --
+        unless read_back is False: then nothing waits, the first value returned is None and info["num"] is a device
+        tensor [1] (the image_set is all BA.local_window needs).  Returns (bundle, info): bundle is the int32 numpy array
+        of the selected images in selection order; info holds num, the device tensor image_set [I] uint8 (1 for `image`
+        and the bundle) and, for the names in `want`, shared [I] int32, tri_angle [I] float64 (-1: not computed) and
+        bundle [num_images - 1] int32 as the device holds it (-1 behind the last)."""
+        torch, dev, stream = self._torch()
+        bad = set(want) - {"shared", "tri_angle", "bundle"}
+        if bad:
+            raise ValueError(f"local_bundle: unknown output {sorted(bad)}")
+        o = BALocalBundleOpts()
+        lib().pcd_ba_local_bundle_opts_default(C.byref(o))
+        o.image, o.num_images, o.min_tri_angle_deg = int(image), int(num_images), float(min_tri_angle)
+        cap = max(int(num_images) - 1, 1)
+        t_bundle = torch.empty(cap, dtype=torch.int32, device=dev)
+        t_num = torch.empty(1, dtype=torch.int32, device=dev)
+        t_set = torch.empty(self.I, dtype=torch.uint8, device=dev)
+        t_shared = torch.empty(self.I, dtype=torch.int32, device=dev) if "shared" in want else None
+        t_tri = torch.empty(self.I, dtype=torch.float64, device=dev) if "tri_angle" in want else None
+        _check(lib().pcd_ba_local_bundle_device(self._h, C.byref(o), _ptr(t_bundle), _ptr(t_num), _ptr(t_set),
+                                                _ptr(t_shared), _ptr(t_tri), C.c_void_p(stream)))
+        num = int(t_num.item()) if read_back else t_num
+        out = dict(image_set=t_set, num=num)
+        for name, t in (("shared", t_shared), ("tri_angle", t_tri), ("bundle", t_bundle)):
+            if name in want:
+                out[name] = t
+        return (t_bundle[:num].cpu().numpy() if read_back else None), out
+
+    def local_window(self, image_set, point_variable=None, image=None, max_track_length=1000, extra_const_pose=None,
+                     want=()):
+        """pcd_ba_local_window_create_device: the sub-problem of one local round (AdjustLocalBundle) as a NEW handle
+        derived on the device; this handle is only read.  image_set [I] flags `image` and its bundle (BA.local_bundle's
+        image_set); the variable points are point_variable [P], or, with `image`, those `image` observes with a track of
+        at most max_track_length rows.  A row stays if its image is in the set or its point is variable; a point that
+        keeps only part of its track becomes constant; a LiDAR term stays if its point is variable; every image outside
+        the set gets a constant pose, as do those flagged in extra_const_pose [I].  Synchronises the current stream once.
+        Returns (BA, info): info holds num_images_in, num_points_variable, num_points_fixed, num_obs, num_lidar,
+        num_pose_rows, build_ms and, for the names in `want`, the device tensors point_variable [P] uint8 and obs_map
+        [O] int32 (row in the window, -1: not in it).  BA.commit_window carries the window's parameters back; close
+        the window when done."""
+        torch, dev, stream = self._torch()
+        o = BALocalWindowOpts()
+        lib().pcd_ba_local_window_opts_default(C.byref(o))
+        iset, extra = self._stage(image_set, np.uint8), self._stage(extra_const_pose, np.uint8)
+        var = self._stage(point_variable, np.uint8)
+        for name, t, n in (("image_set", iset, self.I), ("extra_const_pose", extra, self.I), ("point_variable", var, self.P)):
+            if t is not None and int(t.numel()) != n:
+                raise ValueError(f"local_window: {name} has the wrong length")
+        o.d_image_set = None if iset is None else iset.data_ptr()
+        o.d_extra_const_pose = None if extra is None else extra.data_ptr()
+        o.d_point_variable = None if var is None else var.data_ptr()
+        o.image = -1 if image is None else int(image)
+        o.max_track_length = int(max_track_length)
+        bad = set(want) - {"point_variable", "obs_map"}
+        if bad:
+            raise ValueError(f"local_window: unknown output {sorted(bad)}")
+        t_var = torch.empty(self.P, dtype=torch.uint8, device=dev) if "point_variable" in want else None
+        t_map = torch.empty(self.O, dtype=torch.int32, device=dev) if "obs_map" in want and self.O else None
+        h, info = C.c_void_p(), BALocalWindowInfo()
+        _check(lib().pcd_ba_local_window_create_device(self._h, C.byref(o), _ptr(t_var), _ptr(t_map), C.c_void_p(stream),
+                                                       C.byref(h), C.byref(info)))
+        w = self._window_object(h, info, iset, extra)
+        w.point_const = None                                       # the handle has the window's point mask
+        out = {k: getattr(info, k) for k, _ in BALocalWindowInfo._fields_}
+        if "point_variable" in want:
+            out["point_variable"] = t_var
         if "obs_map" in want:
             out["obs_map"] = t_map if t_map is not None else torch.empty(0, dtype=torch.int32, device=dev)
         return w, out
@@ -2070,6 +2178,43 @@ def global_round(ba, cloud, center_image, radius, opt_num, kd_max=1.5, kd_min=0.
     else:
         opt_num += active.cpu().numpy().astype(opt_num.dtype)
     return winfo, ainfo, summary, its
+
+
+def local_round(ba, cloud, image, projector=None, cam_size=None, num_images=6, min_tri_angle=6.0, point_variable=None,
+                max_track_length=1000, extra_const_pose=None, opt_num=None, kd_max=1.5, kd_min=0.2, drop=0.1,
+                image_select=None, point_mode=None, proj_weight=1.0, **solve_opts):
+    """One call of IncrementalMapper::AdjustLocalBundle (sfm/incremental_mapper.cc:1004-1213) on the device:
+    BA.local_bundle(image, num_images, min_tri_angle) picks the bundle, BA.local_window derives the sub-problem (the
+    variable points: point_variable [P], or those `image` observes with at most max_track_length rows), the window takes
+    its LiDAR terms -- with a `projector` (over `cloud`; cam_size, image_select, point_mode, proj_weight as
+    BA.project_lidar, the range of mode-2 points from opt_num) through BA.project_lidar, else the variable points search
+    `cloud` within search_range_schedule(opt_num) per point (:1159-1164; opt_num None: zeros) through BA.associate_lidar --
+    ba_solve(**solve_opts) refines it and BA.commit_window carries the parameters back into `ba`.  `ba` keeps its rows,
+    terms and co-visibility structure; the camera-constness rule (:1064-1080) stays with the caller.  Returns (bundle,
+    window info, term info, solve summary, iterations)."""
+    torch, dev, _ = ba._torch()
+    bundle, binfo = ba.local_bundle(image, num_images, min_tri_angle)
+    win, winfo = ba.local_window(binfo["image_set"], point_variable=point_variable,
+                                 image=None if point_variable is not None else image,
+                                 max_track_length=max_track_length, extra_const_pose=extra_const_pose,
+                                 want=("point_variable",))
+    try:
+        variable = winfo.pop("point_variable")
+        if opt_num is None:
+            host_num = np.zeros(ba.P, np.int32)
+        else:
+            host_num = opt_num.cpu().numpy() if isinstance(opt_num, torch.Tensor) else np.asarray(opt_num)
+        rng = search_range_schedule(np.ascontiguousarray(host_num, np.int32), kd_max, kd_min, drop)
+        if projector is not None:
+            tinfo = win.project_lidar(projector, cam_size, image_select=image_select, point_mode=point_mode, max_range=rng,
+                                      gate_mode=GATE_MAPPER_LOCAL, proj_weight=proj_weight)
+        else:
+            tinfo = win.associate_lidar(cloud, max_range=rng, gate_mode=GATE_MAPPER_LOCAL, select=variable)
+        summary, its = ba_solve(win, **solve_opts)
+        ba.commit_window(win)
+    finally:
+        win.close()
+    return bundle, winfo, tinfo, summary, its
 
 
 def refine_filter(ba, max_refinements=5, max_change=0.0005, max_reproj_error=8.0, min_tri_angle=1.5, complete=None,

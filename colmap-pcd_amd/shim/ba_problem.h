@@ -687,6 +687,113 @@ class BundleAdjusterHip {
     if (info) *info = r;
     return true;
   }
+  // ---- one local round (HIP): IncrementalMapper::AdjustLocalBundle (sfm/incremental_mapper.cc:1004-1213) on the LIVE
+  // handle, which holds the whole map -----------------------------------------------------------------------------------
+  // pcd_ba_local_bundle_device picks the bundle of image_id (FindLocalBundle, :1747-1914); pcd_ba_local_window_create_device
+  // derives the sub-problem of the image, its bundle and the points the image observes with at most max_track_length rows
+  // (:1110-1134) as a second handle; those points search `cloud` within kd_max - GlobalOptNum * drop, at least kd_min
+  // (:1159-1164), and the accepted associations become the window's LiDAR terms; pcd_ba_solve refines the window with
+  // Solve's options; pcd_ba_window_commit_device carries the parameters back.  Then the variable poses of the bundle and
+  // the points go back into the Reconstruction and the flat mirrors.  The camera-constness rule (:1064-1080), the
+  // depth-projection terms (ProjectLidar on a handle of one's own) and GlobalOptNum stay with the caller.  The live handle
+  // keeps its rows, its terms and its co-visibility structure; the round's terms go with the window.
+  // false without a live handle or cloud, for an image that is not in the problem, when intrinsics are refined and
+  // options_.refine_intrinsics_on_device is off, or when a call fails (pcd_last_error()).  Up to and including a failed
+  // commit the problem is then as it was.  Behind the commit only the read-backs of the live handle's parameters can
+  // fail: the handle then holds the round's result, the flat mirrors and the Reconstruction do not, and Create() or the
+  // next successful read brings them together.
+  struct LocalRoundInfo {
+    std::vector<image_t> bundle;
+    pcd_ba_local_window_info window; pcd_ba_assoc_info assoc; pcd_ba_solve_summary solve;
+  };
+  template <typename Cloud>
+  bool LocalRound(Reconstruction* rec, Cloud& cloud, image_t image_id, int num_images = 6, double min_tri_angle = 6.0,
+                  uint32_t max_track_length = 1000, double kd_max = 1.5, double kd_min = 0.2, double drop = 0.1,
+                  LocalRoundInfo* info = nullptr) {
+    if (info) *info = LocalRoundInfo{};
+    if (!ba_ || !cloud.handle() || num_images < 2) return false;
+    const auto image = image_index_.find(image_id);
+    if (image == image_index_.end()) return false;
+    bool refined = false;
+    for (uint8_t v : cam_refine_) refined |= v != 0;
+    if (refined && !options_.refine_intrinsics_on_device) return false;
+    const size_t P = point_ids_.size(), I = image_ids_.size(), cap = (size_t)num_images - 1;
+    struct DevMem {   // freed on every return
+      void* p = nullptr;
+      ~DevMem() { if (p) (void)hipFree(p); }
+    } d_flags, d_range, d_bundle;
+    struct Window {   // destroyed on every return
+      pcd_ba* h = nullptr;
+      ~Window() { pcd_ba_destroy(h); }
+    } win;
+    if (hipMalloc(&d_flags.p, I + P + 1) != hipSuccess || hipMalloc(&d_range.p, (P + 1) * sizeof(double)) != hipSuccess ||
+        hipMalloc(&d_bundle.p, (cap + 1) * sizeof(int32_t)) != hipSuccess)
+      return false;
+    uint8_t* d_set = static_cast<uint8_t*>(d_flags.p), *d_variable = d_set + I;
+    int32_t* d_ids = static_cast<int32_t*>(d_bundle.p), *d_num = d_ids + cap;
+    LocalRoundInfo r{};
+    pcd_ba_local_bundle_opts bo;
+    pcd_ba_local_bundle_opts_default(&bo);
+    bo.image = image->second;
+    bo.num_images = num_images;
+    bo.min_tri_angle_deg = min_tri_angle;
+    if (pcd_ba_local_bundle_device(ba_, &bo, d_ids, d_num, d_set, nullptr, nullptr, nullptr) != PCD_OK) return false;
+    pcd_ba_local_window_opts wo;
+    pcd_ba_local_window_opts_default(&wo);
+    wo.d_image_set = d_set;
+    wo.image = image->second;
+    wo.max_track_length = max_track_length;
+    if (pcd_ba_local_window_create_device(ba_, &wo, d_variable, nullptr, nullptr, &win.h, &r.window) != PCD_OK) return false;
+    std::vector<int32_t> ids(cap + 1);
+    if (hipMemcpy(ids.data(), d_bundle.p, (cap + 1) * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (int32_t k = 0; k < ids[cap]; ++k) r.bundle.push_back(image_ids_[ids[k]]);
+    std::vector<int32_t> opt_num(P, 0);
+    for (size_t p = 0; p < P; ++p) {
+      const auto it = rec->points3D.find(point_ids_[p]);
+      if (it != rec->points3D.end()) opt_num[p] = it->second.global_opt_num;
+    }
+    std::vector<double> range(P);
+    if (pcd_search_range_schedule(opt_num.data(), P, kd_max, kd_min, drop, range.data()) != PCD_OK) return false;
+    if (hipMemcpy(d_range.p, range.data(), P * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return false;
+    pcd_ba_assoc_opts ao;
+    pcd_ba_assoc_opts_default(&ao);
+    ao.gate_mode = PCD_GATE_MAPPER_LOCAL;
+    ao.icp_weight = options_.icp_lidar_constraint_weight;
+    ao.icp_ground_weight = options_.icp_ground_lidar_constraint_weight;
+    ao.d_max_range = static_cast<const double*>(d_range.p);
+    ao.max_range_count = P;
+    ao.d_select = d_variable;
+    if (pcd_ba_associate_lidar_device(win.h, cloud.handle(), &ao, nullptr, &r.assoc) != PCD_OK) return false;
+    const pcd_ba_solve_opts so = SolveOpts(refined);
+    if (pcd_ba_solve(win.h, &so, &r.solve, nullptr) != PCD_OK) return false;
+    std::vector<uint8_t> flags(I + P + 1);
+    if (hipMemcpy(flags.data(), d_flags.p, I + P, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    // from here on the problem changes: the live handle first, then its mirrors
+    if (pcd_ba_window_commit_device(win.h, ba_, nullptr) != PCD_OK) return false;
+    if (pcd_ba_get_parameters(ba_, poses_.data(), points_.data()) != PCD_OK) return false;
+    if (refined && pcd_ba_get_camera_parameters(ba_, cam_params_.data()) != PCD_OK) return false;
+    for (size_t i = 0; i < I; ++i) {
+      if (image_const_pose_[i] || !flags[i]) continue;
+      Image& im = rec->images.at(image_ids_[i]);
+      std::copy(poses_.begin() + 7 * i, poses_.begin() + 7 * i + 4, im.qvec);
+      std::copy(poses_.begin() + 7 * i + 4, poses_.begin() + 7 * i + 7, im.tvec);
+    }
+    for (size_t p = 0; p < P; ++p) {   // a point the window held constant kept its bits: the copy changes nothing there
+      if (point_const_[p]) continue;
+      auto it = rec->points3D.find(point_ids_[p]);
+      if (it != rec->points3D.end()) std::copy(points_.begin() + 3 * p, points_.begin() + 3 * p + 3, it->second.xyz);
+    }
+    if (refined)
+      for (size_t c = 0; c < camera_ids_.size(); ++c) {
+        if (!CameraVariable((int)c)) continue;
+        Camera& cam = rec->cameras.at(camera_ids_[c]);
+        std::copy(cam_params_.begin() + cam_off_[c], cam_params_.begin() + cam_off_[c] + cam.params.size(), cam.params.begin());
+      }
+    reassociated_ = true;   // the live handle is the problem: Solve keeps it
+    summary_ = r.solve;
+    if (info) *info = r;
+    return true;
+  }
   const BundleAdjustmentConfig& config() const { return config_; }
   // what Solve hands to pcd_ba_solve: AUTO goes by the number of images in the config, as the reference does
   bool UsesDirectSolver() const {

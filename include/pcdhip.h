@@ -1263,6 +1263,92 @@ pcd_status pcd_ba_window_create_device(pcd_ba* src, const pcd_ba_window_opts* op
 pcd_status pcd_ba_window_commit_device(pcd_ba* window, pcd_ba* src, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The local round on a live handle: FindLocalBundle and the local sub-problem   
+ *   IncrementalMapper::FindLocalBundle (sfm/incremental_mapper.cc:1747-1914) picks the images of the local bundle;
+ *   AdjustLocalBundle (:1004-1213) with AddImageToProblem / AddPointToProblem / ParameterizePoints
+ *   (optim/bundle_adjustment.cc:814-985, 1107-1131) makes their sub-problem.
+ * pcd_ba_local_bundle_device: the selection, fp64 without FMA, one operation at a time.
+ *   n         = the rows of `image` (NumPoints3D).
+ *   shared[j] = the pairs (row of `image`, row of j) on the same point, j != image (per ROW, as the reference counts: a
+ *               point `image` sees through two rows counts twice); shared[image] = 0.
+ *   Candidates: the images with shared > 0, by shared descending, TIES BY IMAGE INDEX ASCENDING (a chosen deviation: the
+ *               reference's tie order is what std::sort makes of an unordered_map's iteration order).
+ *   num_eff   = min(num_images - 1, #candidates).  #candidates == num_eff: the bundle is the candidates in that order, no
+ *               angle is computed and d_tri_angle is -1 everywhere (:1798-1803).
+ *   Otherwise tri[j] = Percentile(75) (util/math.h:231-246) of CalculateTriangulationAngles (base/triangulation.cc:147-181)
+ *               between ProjectionCenter(image), ProjectionCenter(j) -- the NORMALISED quaternion, as the filter's
+ *               centres, not the sphere window's -- and the point of EVERY row of `image` (the test at :1861 is against
+ *               the image's own set: all n rows enter, a duplicated row twice).  idx = (int)std::round(0.75 * (n - 1)),
+ *               halves away from zero; the result is the idx-th smallest angle, A NaN ANGLE ORDERING BEHIND EVERY NUMBER
+ *               (a chosen deviation: nth_element over NaN is unspecified).  d_tri_angle[j] holds it for every candidate
+ *               with (double)shared[j] >= 0.1 * n (the loosest pass's bound; below it no pass reads an angle), else -1.
+ *   Passes:   thresholds (m / d, f * n), m = min_tri_angle_deg * DegToRad, (d, f) = (1, .6) (1.5, .6) (2, .5) (2.5, .4)
+ *               (3, .3) (4, .2) (5, .1) (6, .1).  A pass visits the candidates in order; one with (double)shared < f * n
+ *               ends the pass; an unused one with tri >= m / d is appended; the pass stops at num_eff.  Then the bundle is
+ *               filled up with the unused candidates in order (:1895-1911).
+ *   Outputs: d_bundle in selection order with -1 behind the last, d_num, d_image_set = 1 for `image` and the bundle.
+ *   The device form does not synchronise; no floating-point atomics (the integer LDS histograms of the percentile's
+ *   radix select are exact), nothing depends on the launch geometry: a repeated call gives the same bytes.
+ *   Guards, before anything is allocated or launched: NULL ba / opts / d_bundle / d_num / d_image_set -> INVALID; no
+ *   gfx950 -> NO_DEVICE; a capturing stream -> UNSUPPORTED; image outside [0, I), num_images < 2, min_tri_angle_deg
+ *   negative or NaN -> INVALID.  An image without a row is valid: num = 0 and only `image` is in the set.
+ * pcd_ba_local_window_create_device: the sub-problem as a second handle; src is only read.  With in = d_image_set != 0
+ *   and V = the variable flags (d_point_variable != 0, or, with `image`: observed by `image` and track length <=
+ *   max_track_length):
+ *   row o stays iff in[obs_image[o]] || V[obs_point[o]]  (rows on "in" images: AddImageToProblem; the outside rows of
+ *               variable points: the constant-pose blocks of AddPointToProblem);
+ *   kept[p]   = the rows of p that stay; a point with kept == 0 is a row without a residual block;
+ *   point_const'[p] = src's || (0 < kept[p] < track length of p)  (ParameterizePoints :1110-1121; a non-variable point
+ *               whose whole track lies on "in" images stays variable, as in the reference);
+ *   LiDAR term l stays iff V[lidar_point[l]] (the reference installs terms for variable points only);
+ *   image_const_pose' = src's | !in | d_extra_const_pose.
+ *   Cameras, image_const_tvec, camera_refine, the loss and I / P / C are the source's.  SetConstantCamera for a camera
+ *   with images outside the bundle (:1064-1080) stays with the caller.
+ *   Contract: the sphere window's, word for word -- the window is byte for byte the handle pcd_ba_create builds from
+ *   the compacted description (image_const_pose and point_const always arrays); the source, its Schur state and
+ *   structure are untouched; ONE synchronisation, to read O(I) bytes; no floating-point atomics; a repeated call gives
+ *   the same bytes.  pcd_ba_window_commit_device carries a local window back unchanged (the new constant points and the
+ *   outside poses never move: the copy is exact).  num_points_fixed counts the points the rule above made constant
+ *   (0 < kept < length on a point the source does not hold constant).
+ *   Guards: as for the sphere window (NULL src / opts / window -> INVALID, NO_DEVICE, UNSUPPORTED), d_image_set NULL ->
+ *   INVALID, exactly one of d_point_variable and image >= 0, image < I.
+ * --------------------------------------------------------------------- */
+typedef struct {
+  int32_t image;              /* the newly registered image; must have a variable or constant pose, any */
+  int32_t num_images;         /* local_ba_num_images (6): at most num_images - 1 other images */
+  double  min_tri_angle_deg;  /* local_ba_min_tri_angle (6.0) */
+  int32_t reserved[8];
+} pcd_ba_local_bundle_opts;
+void pcd_ba_local_bundle_opts_default(pcd_ba_local_bundle_opts* o);   /* -1, 6, 6.0 */
+pcd_status pcd_ba_local_bundle_device(pcd_ba* ba, const pcd_ba_local_bundle_opts* opts,
+    int32_t* d_bundle    /* [num_images - 1], selection order, -1 behind the last */,
+    int32_t* d_num       /* [1] */,
+    uint8_t* d_image_set /* [I]: 1 for `image` and the bundle */,
+    uint32_t* d_shared   /* [I] or NULL */, double* d_tri_angle /* [I] or NULL */, void* stream);
+/* host form: null stream, waits.  bundle [num_images - 1], num [1]; shared / tri_angle [I] or NULL */
+pcd_status pcd_ba_local_bundle(pcd_ba* ba, const pcd_ba_local_bundle_opts* opts, int32_t* bundle, int32_t* num,
+                               uint32_t* shared, double* tri_angle);
+typedef struct {
+  const uint8_t* d_image_set;        /* device [I], required: `image` and its bundle (what the call above wrote) */
+  const uint8_t* d_point_variable;   /* device [P] or NULL: the caller's point3D_ids after its track-length rule */
+  int32_t image;                     /* used when d_point_variable is NULL (-1 otherwise): variable = observed by
+                                        `image` and track length <= max_track_length */
+  uint32_t max_track_length;         /* kMaxTrackLength: 1000 with LiDAR constraints (:1113), 15 without (:1129) */
+  const uint8_t* d_extra_const_pose; /* device [I] or NULL (:1049-1062, :1084-1100) */
+  int32_t reserved[8];
+} pcd_ba_local_window_opts;
+typedef struct {
+  uint64_t num_images_in, num_points_variable, num_points_fixed;
+  uint64_t num_obs, num_lidar, num_pose_rows;   /* of the window */
+  double build_ms;                               /* device time up to the call's one synchronisation */
+} pcd_ba_local_window_info;
+void pcd_ba_local_window_opts_default(pcd_ba_local_window_opts* o);   /* NULL, NULL, -1, 1000, NULL */
+pcd_status pcd_ba_local_window_create_device(pcd_ba* src, const pcd_ba_local_window_opts* opts,
+    uint8_t* d_point_variable_out /* [P] or NULL, out: V */,
+    uint32_t* d_obs_map           /* [O of src] or NULL, out: row in the window, 0xFFFFFFFF = not in it */,
+    void* stream, pcd_ba** window, pcd_ba_local_window_info* info /* host, may be NULL */);
+
+/* ------------------------------------------------------------------------
  * Exact SIFT descriptor matching (stretch row a19)
  *   replaces feature/sift.cc:1041-1054 MatchSiftFeaturesCPUBruteForce =
  *     feature/sift.cc:171-204 ComputeSiftDistanceMatrix (int32 dot of uint8 x 128) +
